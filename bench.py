@@ -16,6 +16,11 @@ step. Started by torchrun (RANK/LOCAL_RANK/WORLD_SIZE in the environment) this p
 line, and fails if any rank fails or fewer than N devices are visible — it never falls back to fewer ranks.
 
 Prints ONE JSON line (< 4 KB: compact_line) on rank 0, LAST on stdout; the full record goes to bench_detail.json.
+
+A plain run does only what the headline needs: set-up, --warmup steps, the --steps timed steps, the line. --full adds everything
+reported beside it (instrumented second pass + roofline, pinned-duration and host-PCM passes, sub-results, serving data point,
+duration-boundary report, CPU baseline). --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy; the inputs
+are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -662,6 +667,45 @@ def write_detail(res):
     return wrote
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def last_outputs(jobs, budget=DUMP_BUDGET_BYTES):
+    """What the last timed step handed its caller, on the host, per model handle (`model<i>_` prefix when there are several):
+      * `pcm`: every utterance's PCM in batch order, concatenated (row b of the device buffer holds lengths[b] valid samples, the
+        rest of the row is untouched capacity), float32 as computed;
+      * `lengths` (samples) and `frames` (frames) per utterance, float64 (exact).
+    If the PCM would take the files past `budget` bytes, a fixed sample of it is kept instead: `pcm` holds the samples at the
+    sorted positions `pcm_index` (float64), drawn with a fixed seed, the same number from every model."""
+    out = {}
+    pcms = []
+    for i, j in enumerate(jobs):
+        buf, lengths, frames = j["last"]
+        pre = "" if len(jobs) == 1 else "model%d_" % i
+        rows = buf.cpu().numpy()
+        pcms.append((pre, np.concatenate([rows[b, :int(n)] for b, n in enumerate(lengths)]).astype(np.float32, copy=False)))
+        out[pre + "lengths"] = np.asarray(lengths, np.float64)
+        out[pre + "frames"] = np.asarray(frames, np.float64)
+    room = budget - sum(a.nbytes for a in out.values()) - 4096
+    if sum(p.nbytes for _, p in pcms) > room:
+        keep = room // (len(pcms) * (4 + 8))  # a kept sample costs its float32 value and its float64 position
+        rng = np.random.default_rng(20240601)
+        for pre, p in pcms:
+            idx = np.sort(rng.choice(p.size, size=min(keep, p.size), replace=False))
+            out[pre + "pcm"] = p[idx]
+            out[pre + "pcm_index"] = idx.astype(np.float64)
+    else:
+        for pre, p in pcms:
+            out[pre + "pcm"] = p
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launcher(args):
     """--gpus N without torchrun: start the N ranks as fresh child processes. Nothing here touches the GPU
     (torch.cuda.device_count() does not initialise it on this image), and no process that did is ever re-exec'd."""
@@ -733,7 +777,20 @@ def main():
     ap.add_argument("--single-pass", action="store_true",
                     help="instrumented (serialised) warmup + timed region only, no further passes: every launch of the run is then one "
                          "the HIP events timed, which is what a rocprofv3 --kernel-trace of this command is compared against")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the instrumented second pass and its roofline, the pinned-duration and "
+                         "host-PCM passes, the default-schedule roofline, the sub-results, the serving data point, the duration-boundary "
+                         "report and the CPU baseline (each still subject to its --no-* option). Without it a run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (PCM, lengths, frames; see last_outputs) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, print the line — no further passes, no CPU work beside them
+        # (--single-pass keeps its own instrumented timed region: that is the headline of such a run, not an extra pass)
+        args.no_extra_passes = args.no_sub_results = args.no_serving = args.no_cpu_baseline = True
+        if not args.single_pass:
+            args.no_prof = True
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus > 1 or os.environ.get("VITS_BENCH_LAUNCH") == "1"):  # (VITS_BENCH_LAUNCH=1: launcher path at N = 1, for tests)
@@ -814,6 +871,7 @@ def main():
             _, lengths, frames = m.process_batch(ids, mode=mode, noise_kind=pkg.NOISE_COUNTER, fixed_duration=pinned, out_device=out.data_ptr(),
                                                  out_device_stride=cap, skip_host_copy=not host_pcm, keep_pcm=False,
                                                  vocoder_chunk_frames=args.chunk_frames, **kw)
+            j["last"] = (out, lengths, frames)  # (the fp32 PCM buffer of this step: what --dump-outputs writes)
             if dist_on:
                 # the path's only exchange: ragged all-gather of the PCM over RCCL/xGMI, pipelined — the lengths of this step are
                 # queued now (fixed-size, no host round trip), the PCM of the PREVIOUS step is gathered while the next one is
@@ -864,24 +922,24 @@ def main():
     # The timed region of the contract — EXACTLY K steps between barrier + synchronize — runs the library's DEFAULT schedule (no per-kernel events:
     # the three resblocks of a vocoder stage on concurrent streams). Rounds 1-5 timed the instrumented schedule here and paid 2.4 % of the headline
     # for their own instrumentation. The per-kernel HIP events of the roofline block come from a SECOND pass of the same K steps
-    # right behind it (every rank runs it: the steps contain the PCM exchange), whose step time is reported as `instrumented_ms_per_step`.
+    # right behind it (--full only; every rank runs it: the steps contain the PCM exchange), whose step time is reported as `instrumented_ms_per_step`.
     # --single-pass (the rocprofv3 runs of tools/jobs/profile.sh: every launch of the trace must be a serialised one) keeps ONE instrumented region.
     extra = {}
     if args.single_pass and not args.no_prof:
         for m in models:
             m.prof_reset()
-        elapsed, total_samples, frames = timed(args.steps)
-    else:
-        elapsed, total_samples, frames = timed(args.steps)
-        if not args.no_prof:
-            for m in models:
-                m.prof_reset()
-                m.prof_enable(True)
-            step()  # (the first serialised step re-lays the grouped launch out; untimed)
-            for m in models:
-                m.prof_reset()
-            e, s_, _ = timed(args.steps)
-            extra["instrumented"] = (e, s_)
+    elapsed, total_samples, frames = timed(args.steps)
+    # what the last timed step returned, copied to the host before any further pass reuses the output buffers
+    outputs = last_outputs(jobs) if args.dump_outputs and rank == 0 else None
+    if not args.single_pass and not args.no_prof:
+        for m in models:
+            m.prof_reset()
+            m.prof_enable(True)
+        step()  # (the first serialised step re-lays the grouped launch out; untimed)
+        for m in models:
+            m.prof_reset()
+        e, s_, _ = timed(args.steps)
+        extra["instrumented"] = (e, s_)
     for m in models:
         m.prof_enable(False)
     # further passes of the same K steps, reported BESIDE the headline: (b) durations pinned to 2 frames per id (SURVEY §8d run ii: equal
@@ -1095,6 +1153,8 @@ def main():
         dist.destroy_process_group()
     for m in models:
         m.close()
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         # the JSON line goes out LAST: RCCL writes a version banner to the C stdout, which would otherwise follow it
         import ctypes

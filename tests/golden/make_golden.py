@@ -27,6 +27,8 @@ checked against (scripts/verify_layers.py:25) — computes; the oracle's VO_MODE
                            Pins vo_opts.arith (VO_ARITH_F16 / BF16, default scope: stage one exact) and VITS_ARITH_*.
 
 usage: python tests/golden/make_golden.py            (from the repo root, after building csrc/libvits_hip.so)
+  fullsize_export_manifest.json  the layout and per-tensor statistics of a DEFAULT-config (full-size) export by the same exporter:
+                           python tests/golden/make_golden.py --fullsize-manifest REFERENCE_TREE
 """
 import ast
 import importlib.util
@@ -505,7 +507,92 @@ def reference_exported_tiny():
     return open(path, "rb").read()
 
 
+def fullsize_export_manifest(reference_root):
+    """fullsize_export_manifest.json: what the reference's own exporter writes for a DEFAULT-config transformers.VitsModel (the
+    MMS-TTS architecture, 36.3 M parameters, torch seed 3), recorded as data — the bytes in front of the tensors (vocabulary, flags,
+    config strings), and per tensor, in file order, its name, dtype, ggml ne and the mean / standard deviation of its values — plus
+    the size of that file and of the checkpoint the reference ships as an LFS pointer (scripts/vits-english.ggml). The 74.5 MB file
+    itself is not stored: tests/test_exporter_fullsize.py rebuilds one of the same layout from this record."""
+    import base64
+    import contextlib
+    import json
+    import tempfile
+    from transformers import VitsConfig, VitsModel
+    sys.path.insert(0, os.path.join(reference_root, "scripts"))
+    import export_vits  # import-safe: __main__ guard at export_vits.py:95
+    torch.manual_seed(3)
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = export_vits.remove_weight_norm_and_convert_to_fp16(VitsModel(VitsConfig()).eval())
+
+    class Tok:  # what serialize_model_to_binary reads of a tokenizer (export_vits.py:8-27); the MMS-TTS English vocabulary has 38 entries
+        phonemize = False
+        is_uroman = False
+        add_blank = True
+        normalize = True
+        pad_token = "<pad>"
+        unk_token = "<unk>"
+
+        def get_vocab(self):
+            v = {"<pad>": 0, " ": 1, "'": 2, "-": 3}
+            v.update({c: 4 + i for i, c in enumerate("abcdefghijklmnopqrstuvwxyz")})
+            v.update({c: 30 + i for i, c in enumerate("0123456")})
+            v["<unk>"] = 37
+            return v
+
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "vits-default.ggml")
+        with contextlib.redirect_stdout(io.StringIO()):
+            export_vits.serialize_model_to_binary(model.config, model.state_dict(), Tok(), path)
+        data = open(path, "rb").read()
+    with open(os.path.join(reference_root, "scripts", "vits-english.ggml")) as fh:  # an LFS pointer: three text lines
+        shipped = int([ln.split()[1] for ln in fh if ln.startswith("size ")][0])
+    # walk the layout of SURVEY.md App. C: the header ends where the tensor count begins
+    off = 0
+
+    def u32():
+        nonlocal off
+        (v,) = struct.unpack_from("<I", data, off)
+        off += 4
+        return v
+
+    def s():
+        nonlocal off
+        n = u32()
+        off += n
+        return data[off - n:off].decode("utf-8")
+
+    for _ in range(u32()):
+        s()
+        u32()
+    u32(), u32()
+    s(), s()
+    for _ in range(u32()):
+        s()
+        s()
+    header = data[:off]
+    tensors = []
+    for _ in range(u32()):
+        name = s()
+        dt, rank = u32(), u32()
+        ne = [u32() for _ in range(rank)]
+        nb = u32()
+        a = np.frombuffer(data, dtype=np.float32 if dt == 0 else np.float16, count=nb // (4 if dt == 0 else 2), offset=off).astype(np.float64)
+        off += nb
+        tensors.append([name, dt, ne, float(a.mean()), float(a.std())])
+    assert off == len(data)
+    rec = {"note": "scripts/export_vits.py of the reference (remove_weight_norm_and_convert_to_fp16 + serialize_model_to_binary) on "
+                   "transformers.VitsModel(VitsConfig()) after torch.manual_seed(3); written by tests/golden/make_golden.py --fullsize-manifest",
+           "export_bytes": len(data), "shipped_checkpoint_bytes": shipped, "header_base64": base64.b64encode(header).decode(),
+           "tensors": tensors}
+    with open(os.path.join(HERE, "fullsize_export_manifest.json"), "w") as fh:
+        json.dump(rec, fh, separators=(",", ":"))
+    print("fullsize_export_manifest.json:", len(tensors), "tensors,", len(data), "bytes exported")
+
+
 def main():
+    if sys.argv[1:2] == ["--fullsize-manifest"]:  # usage: make_golden.py --fullsize-manifest REFERENCE_TREE
+        fullsize_export_manifest(sys.argv[2])
+        return
     pkg = load_package()
     # (A) exporter-written tiny HF model
     data = reference_exported_tiny()

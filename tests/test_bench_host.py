@@ -137,3 +137,39 @@ def test_the_record_states_the_host_cores_and_a_workload_label_that_survives_the
     got = json.loads(bench.compact_line(res))
     assert len(got["config"]["workload"]) <= 110
     assert got["cpu_baseline"]["cores"] == 128 and got["cpu_baseline"]["threads"] == 32 and got["cpu_baseline"]["host_threads"] == 256 and "EPYC" in got["cpu_baseline"]["cpu_model"]
+
+
+def test_dump_outputs_keep_the_valid_pcm_and_stay_within_the_budget(tmp_path):
+    """--dump-outputs: per utterance only the first lengths[b] samples of its row (the rest is untouched capacity), float32 PCM and
+    float64 counts, a `model<i>_` prefix with several handles; past the byte budget a fixed-seed sample of the PCM with its positions."""
+    import numpy as np
+    bench = _load(os.path.join(ROOT, "bench.py"), "bench_under_test4")
+
+    class Buf:  # what last_outputs reads of the device buffer
+        def __init__(self, a):
+            self.a = a
+
+        def cpu(self):
+            return self
+
+        def numpy(self):
+            return self.a
+
+    rows = np.arange(3 * 10, dtype=np.float32).reshape(3, 10)
+    job = {"last": (Buf(rows), np.array([4, 0, 10], np.int64), np.array([1, 0, 3], np.int64))}
+    out = bench.last_outputs([job])
+    assert sorted(out) == ["frames", "lengths", "pcm"]
+    assert out["pcm"].dtype == np.float32 and np.array_equal(out["pcm"], np.concatenate([rows[0, :4], rows[2]]))
+    assert out["lengths"].dtype == np.float64 and out["lengths"].tolist() == [4, 0, 10] and out["frames"].tolist() == [1, 0, 3]
+    big = np.random.default_rng(1).standard_normal((2, 4000)).astype(np.float32)
+    jobs = [{"last": (Buf(big), np.array([4000, 3000]), np.array([9, 7]))} for _ in range(2)]
+    a, b = bench.last_outputs(jobs, budget=40000), bench.last_outputs(jobs, budget=40000)
+    assert sorted(a) == sorted("model%d_%s" % (i, k) for i in range(2) for k in ("pcm", "pcm_index", "lengths", "frames"))
+    assert sum(x.nbytes for x in a.values()) <= 40000
+    full = np.concatenate([big[0], big[1, :3000]])
+    for i in range(2):
+        idx = a["model%d_pcm_index" % i].astype(np.int64)
+        assert idx.size > 0 and np.all(np.diff(idx) > 0) and np.array_equal(a["model%d_pcm" % i], full[idx])
+        assert np.array_equal(a["model%d_pcm" % i], b["model%d_pcm" % i])  # the same sample every run
+    bench.write_outputs(str(tmp_path / "d"), out)
+    assert np.array_equal(np.load(tmp_path / "d" / "pcm.npy"), out["pcm"])

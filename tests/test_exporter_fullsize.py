@@ -1,63 +1,48 @@
-"""Full-size drill of the model-file path against the REFERENCE'S OWN exporter (build container only, CPU): a default-config
-transformers.VitsModel (the MMS-TTS architecture, 36.3 M parameters) goes through /root/reference/scripts/export_vits.py:5-93 into a
-temporary file, and that file — 698 tensors, within the 80 bytes of the checkpoint the reference ships as an LFS pointer
-(/root/reference/scripts/vits-english.ggml: 74,551,853 B; the difference is the tokenizer's vocabulary strings) — passes the product's
-host-only load check (vits_model_file_validate == everything Engine::load checks: format, hyper-parameters, every tensor the engine asks
-for with its shape and dtype), survives the product's reader / writer byte for byte, and loads and runs in the oracle. Nothing here
-travels to the GPU box (the reference tree does not exist there: the test skips); the tiny exporter-written fixture
-tests/golden/tiny_hf_export.ggml covers the GPU side. VERDICT r4 next 8."""
-import contextlib
-import io
+"""Full-size drill of the model-file path against the REFERENCE'S OWN exporter (CPU): what scripts/export_vits.py:5-93 of the
+reference writes for a default-config transformers.VitsModel (the MMS-TTS architecture, 36.3 M parameters) is recorded in
+tests/golden/fullsize_export_manifest.json (tests/golden/make_golden.py --fullsize-manifest): the bytes in front of the tensors, every
+tensor's name, dtype and shape in file order with the mean / standard deviation of its values, the size of the exported file and of the
+checkpoint the reference ships as an LFS pointer (scripts/vits-english.ggml: 74,551,853 B; the difference is the tokenizer's vocabulary
+strings). From that record the test rebuilds a file of the same layout — header bytes verbatim, each tensor's values drawn from its
+recorded mean and deviation with a fixed seed — and that file (698 tensors, within the 80 bytes of the shipped checkpoint) passes the
+product's host-only load check (vits_model_file_validate == everything Engine::load checks: format, hyper-parameters, every tensor the
+engine asks for with its shape and dtype), survives the product's reader / writer byte for byte, and loads and runs in the oracle. The
+tiny exporter-written fixture tests/golden/tiny_hf_export.ggml covers the GPU side. VERDICT r4 next 8."""
+import base64
+import json
 import os
-import sys
+import struct
 
 import numpy as np
 import pytest
 
-REF_SCRIPTS = "/root/reference/scripts"
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF_SCRIPTS, "export_vits.py")), reason="reference tree not present (GPU box)")
+MANIFEST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fullsize_export_manifest.json")
 
 
 @pytest.fixture(scope="module")
-def exported(tmp_path_factory):
-    torch = pytest.importorskip("torch")
-    transformers = pytest.importorskip("transformers")
-    sys.path.insert(0, REF_SCRIPTS)
-    try:
-        import export_vits  # import-safe: __main__ guard at export_vits.py:95
-    finally:
-        sys.path.pop(0)
-    torch.manual_seed(3)
-    model = transformers.VitsModel(transformers.VitsConfig()).eval()
-    model = export_vits.remove_weight_norm_and_convert_to_fp16(model)
+def manifest():
+    with open(MANIFEST) as fh:
+        return json.load(fh)
 
-    class Tok:  # what serialize_model_to_binary reads of a tokenizer (export_vits.py:8-27); the MMS-TTS English vocabulary has 38 entries
-        phonemize = False
-        is_uroman = False
-        add_blank = True
-        normalize = True
-        pad_token = "<pad>"
-        unk_token = "<unk>"
 
-        def get_vocab(self):
-            v = {"<pad>": 0, " ": 1, "'": 2, "-": 3}
-            v.update({c: 4 + i for i, c in enumerate("abcdefghijklmnopqrstuvwxyz")})
-            v.update({c: 30 + i for i, c in enumerate("0123456")})
-            v["<unk>"] = 37
-            return v
-
-    path = tmp_path_factory.mktemp("export") / "vits-default.ggml"
-    with contextlib.redirect_stdout(io.StringIO()):
-        export_vits.serialize_model_to_binary(model.config, model.state_dict(), Tok(), str(path))
-    data = path.read_bytes()
-    path.unlink()
+@pytest.fixture(scope="module")
+def exported(manifest):
+    rng = np.random.default_rng(3)
+    parts = [base64.b64decode(manifest["header_base64"]), struct.pack("<I", len(manifest["tensors"]))]
+    for name, dt, ne, mean, std in manifest["tensors"]:
+        n = int(np.prod(ne))
+        vals = (mean + std * rng.standard_normal(n)).astype(np.float32 if dt == 0 else np.float16)
+        raw = vals.tobytes()
+        parts += [struct.pack("<I", len(name)), name.encode(), struct.pack("<II", dt, len(ne)), struct.pack("<%dI" % len(ne), *ne),
+                  struct.pack("<I", len(raw)), raw]
+    data = b"".join(parts)
+    assert len(data) == manifest["export_bytes"]
     return data
 
 
-def test_default_config_export_matches_the_shipped_checkpoints_size_and_manifest(exported):
+def test_default_config_export_matches_the_shipped_checkpoints_size_and_manifest(manifest, exported):
     from modelfile_py import parse_model_file
-    with open(os.path.join(REF_SCRIPTS, "vits-english.ggml")) as fh:  # an LFS pointer: three text lines
-        shipped = int([ln.split()[1] for ln in fh if ln.startswith("size ")][0])
+    shipped = manifest["shipped_checkpoint_bytes"]
     assert shipped == 74551853
     assert abs(len(exported) - shipped) <= 80, (len(exported), shipped)
     f = parse_model_file(exported)

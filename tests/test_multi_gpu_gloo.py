@@ -293,7 +293,8 @@ int ncclAllGather(const void* s, void* r, size_t n, int dt, void* c, void* st) {
 
 
 def _gather_id_worker(rank, world, port, stub, log, q):
-    os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "VITS_RCCL_LIB": stub, "STUB_RCCL_LOG": log})
+    # (no device visible to these CPU ranks, on a machine with a GPU as well: the last call must find none)
+    os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "VITS_RCCL_LIB": stub, "STUB_RCCL_LOG": log, "HIP_VISIBLE_DEVICES": "-1"})
     dist.init_process_group("gloo", rank=rank, world_size=world)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from conftest import load_package
