@@ -143,6 +143,18 @@ VITS_API int vits_model_get_arith_scope(const vits_model* model);
 VITS_API int vits_model_set_ggml_tables(vits_model* model, int on);
 VITS_API int vits_model_get_ggml_tables(const vits_model* model);
 
+/* ---- speaker conditioning (multi-speaker VITS files: num_speakers > 1, speaker_embedding_size > 0) ----------------------
+ * transformers VitsModel(speaker_id=s): the embedding g = embed_speaker[s] enters the duration predictor (conv_pre(x) + cond(g)),
+ * every WaveNet layer of the flow (in_layers[i](h) + its slice of cond_layer(g), before tanh * sigmoid) and the decoder
+ * (conv_pre(spec) + cond(g)). The three speaker terms are folded into a per-speaker table of biases built once at load. The
+ * reference defines no speakers (vits.cpp:461,603,936 assert them away), so conditioning is the same in both modes.
+ * vits_model_set_speaker sets the speaker of every utterance a call does not name (vits_model_process, vits_model_process_ids,
+ * and vits_process_opts.speaker_ids == NULL); the default is -1 = none. Returns 0, or -1 for a speaker outside
+ * [-1, num_speakers) or >= 0 on a single-speaker model. */
+VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker);
+VITS_API int32_t vits_model_get_speaker(const vits_model* model);
+VITS_API int32_t vits_model_num_speakers(const vits_model* model); /* 1 for a single-speaker model */
+
 /* Noise source for the two N(0,1) draws (vits.cpp:948 [T,2] and :1059 [L,192]). */
 #define VITS_NOISE_REFERENCE 0 /* libstdc++ minstd_rand0 + normal_distribution<float>, global, host-serial */
 #define VITS_NOISE_COUNTER 1   /* include/vits_synth_noise.h, evaluated on the device                       */
@@ -188,6 +200,12 @@ typedef struct vits_process_opts {
                                           noise_seed + noise_seed_offsets[b] instead of noise_seed + b. Lets a dispatcher
                                           re-order or re-shard utterances (e.g. balance ranks by frames) without changing
                                           any utterance's audio. */
+    const int32_t* speaker_ids;   /* optional host [B]: the speaker of utterance b (multi-speaker models, vits_model_num_speakers > 1);
+                                     -1 = no speaker conditioning (transformers VitsModel with speaker_id=None). Every utterance of a
+                                     batch may have its own speaker. NULL = every utterance uses the model default (vits_model_set_speaker).
+                                     Copied when the call returns (vits_model_submit_batch included). A speaker outside
+                                     [-1, num_speakers), any speaker >= 0 on a single-speaker model, or one with
+                                     vits_model_set_ggml_tables(model, 1) fails the call with -1 and a message naming the utterance. */
 } vits_process_opts;
 
 typedef struct vits_batch_result {
@@ -253,6 +271,8 @@ VITS_API int64_t vits_model_get_tap(vits_model* model, const char* name, int32_t
 #define VITS_SYNTH_FULL 0 /* VitsConfig defaults == facebook/mms-tts-* architecture */
 #define VITS_SYNTH_TINY 1 /* hidden 16 / small vocoder: small enough to commit as a fixture */
 #define VITS_SYNTH_BF16 0x100 /* OR-ed in: store conv weights as bf16 (tensor type tag 2, an extension of the format) */
+#define VITS_SYNTH_SPEAKERS 0x200 /* OR-ed in: a multi-speaker model (TINY: 4 speakers, embedding 8; FULL: 109 speakers, embedding 256): the
+                                     tensors of the model without the flag, unchanged, then embed_speaker and the three kinds of cond layers */
 VITS_API int vits_synth_model_bytes(uint64_t seed, int32_t arch, char** bytes, size_t* size);
 VITS_API void vits_free_bytes(char* bytes);
 /* Parse a model file and write it back (host only): byte-exact round trip of the reference's format

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("VITS_HIP_LIB", os.path.join(_HERE, "csrc", "libvits_h
 
 MODE_DEFAULT, MODE_REFERENCE, MODE_HF = -1, 0, 1
 NOISE_REFERENCE, NOISE_COUNTER, NOISE_EXPLICIT = 0, 1, 2
-SYNTH_FULL, SYNTH_TINY, SYNTH_BF16 = 0, 1, 0x100
+SYNTH_FULL, SYNTH_TINY, SYNTH_BF16, SYNTH_SPEAKERS = 0, 1, 0x100, 0x200
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_arith", "vits_model_get_arith", "vits_model_file_validate", "vits_op_set_arith",
     "vits_model_set_arith_scope", "vits_model_get_arith_scope", "vits_model_submit_batch", "vits_model_wait", "vits_model_pending",
     "vits_model_set_ggml_tables", "vits_model_get_ggml_tables",
+    "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -56,7 +57,7 @@ class ProcessOpts(C.Structure):
         ("fixed_duration", C.c_int32), ("collect_taps", C.c_int32), ("out_device", C.c_void_p),
         ("out_device_stride", C.c_int64), ("skip_host_copy", C.c_int32), ("async_", C.c_int32),
         ("vocoder_chunk_frames", C.c_int32), ("frames_only", C.c_int32), ("on_chunk", ChunkCallback), ("on_chunk_user", C.c_void_p),
-        ("noise_seed_offsets", C.c_void_p),
+        ("noise_seed_offsets", C.c_void_p), ("speaker_ids", C.c_void_p),
     ]
 
 
@@ -144,6 +145,12 @@ def lib():
     L.vits_model_set_ggml_tables.argtypes = [vp, i32]
     L.vits_model_get_ggml_tables.restype = i32
     L.vits_model_get_ggml_tables.argtypes = [vp]
+    L.vits_model_set_speaker.restype = i32
+    L.vits_model_set_speaker.argtypes = [vp, i32]
+    L.vits_model_get_speaker.restype = i32
+    L.vits_model_get_speaker.argtypes = [vp]
+    L.vits_model_num_speakers.restype = i32
+    L.vits_model_num_speakers.argtypes = [vp]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -340,6 +347,20 @@ class Model:
         if lib().vits_model_set_ggml_tables(self._h, int(on)) != 0:
             raise VitsError(last_error())
 
+    def set_speaker(self, speaker):
+        """the speaker of every utterance a call does not name (process_ids / the text entry point / speaker_ids=None); -1 = none"""
+        if lib().vits_model_set_speaker(self._h, int(speaker)) != 0:
+            raise VitsError(last_error())
+
+    @property
+    def speaker(self):
+        return int(lib().vits_model_get_speaker(self._h))
+
+    @property
+    def num_speakers(self):
+        """1 for a single-speaker model"""
+        return int(lib().vits_model_num_speakers(self._h))
+
     @property
     def ggml_tables(self):
         return bool(lib().vits_model_get_ggml_tables(self._h))
@@ -378,10 +399,12 @@ class Model:
 
     def process_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321,
                       noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False, out_device=None,
-                      out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False, noise_seed_offsets=None, keep_pcm=True):
+                      out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False, noise_seed_offsets=None, keep_pcm=True,
+                      speaker_ids=None):
         """ids: int32 [B, id_stride]. Returns (list of per-utterance PCM arrays or None, lengths, frames).
         vocoder_chunk_frames > 0 runs the vocoder window by window (bit-identical PCM, bounded activations);
-        on_chunk(utt, offset, pcm ndarray) is then called as each window's samples reach the host (return True to abort)."""
+        on_chunk(utt, offset, pcm ndarray) is then called as each window's samples reach the host (return True to abort).
+        speaker_ids: one speaker per utterance (-1 = none; None = the model default, set_speaker)."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         if ids.ndim == 1:
             ids = ids[None, :]
@@ -403,6 +426,10 @@ class Model:
         if nso is not None and nso.size != B:
             raise ValueError("noise_seed_offsets needs one entry per utterance")
         o.noise_seed_offsets = _ptr(nso)
+        spk = None if speaker_ids is None else np.ascontiguousarray(speaker_ids, dtype=np.int32).ravel()
+        if spk is not None and spk.size != B:
+            raise ValueError("speaker_ids needs one entry per utterance")
+        o.speaker_ids = _ptr(spk)
         cb_error = []
         if on_chunk is not None:
             def _cb(_user, utt, offset, pcm, n):
@@ -429,7 +456,7 @@ class Model:
             lib().vits_free_batch_result(C.byref(res))
 
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
-                     skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None):
+                     skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None):
         """vits_model_submit_batch: queue one batch on this handle's pipeline (at most two in flight); its stage one runs under the
         previous batch's vocoder. Results come from wait(), in submission order, bit-identical to process_batch."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
@@ -449,6 +476,10 @@ class Model:
         if nso is not None and nso.size != B:
             raise ValueError("noise_seed_offsets needs one entry per utterance")
         o.noise_seed_offsets = _ptr(nso)
+        spk = None if speaker_ids is None else np.ascontiguousarray(speaker_ids, dtype=np.int32).ravel()
+        if spk is not None and spk.size != B:
+            raise ValueError("speaker_ids needs one entry per utterance")
+        o.speaker_ids = _ptr(spk)
         if lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o)) != 0:
             raise VitsError(last_error())
 

@@ -228,6 +228,23 @@ VITS_API int vits_model_set_ggml_tables(vits_model* model, int on) {
     VITS_CATCH(-1)
 }
 VITS_API int vits_model_get_ggml_tables(const vits_model* model) { return model ? model->eng.ggml_tables : -1; }
+VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    const int n = model->eng.hp.num_speakers;
+    if (speaker != -1 && (n <= 1 || speaker < -1 || speaker >= n)) {
+        set_err(n <= 1 ? "vits_model_set_speaker(" + std::to_string(speaker) + "): this model has a single speaker and no speaker conditioning (use -1)"
+                       : "vits_model_set_speaker(" + std::to_string(speaker) + "): outside [-1, " + std::to_string(n) + ")");
+        return -1;
+    }
+    model->eng.speaker = speaker;
+    return 0;
+}
+VITS_API int32_t vits_model_get_speaker(const vits_model* model) { return model ? model->eng.speaker : -2; }
+VITS_API int32_t vits_model_num_speakers(const vits_model* model) { return model ? model->eng.num_speakers() : -1; }
 
 VITS_API int vits_model_process_batch(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch, int32_t id_stride,
                                       const vits_process_opts* opts, vits_batch_result* out) {

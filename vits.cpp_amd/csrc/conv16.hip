@@ -64,6 +64,8 @@ struct Conv16Params {
     int x_ts;           // time stride (slots per group row)
     const uint16_t* wp;
     const float* bias;
+    const int* bias_rows;  // multi-speaker calls: effective-bias table row per utterance (PackedConv::bias_rs), or nullptr
+    int64_t bias_rs;
     const int* len_in;
     const int* len_out;
     int t_in, t_out;
@@ -107,6 +109,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int b = blockIdx.z;
     const int t0 = blockIdx.x * BN;
+    const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;  // multi-speaker calls: this utterance's bias row
     const int len_in = p.len_in ? p.len_in[b] : p.t_in;
     int ncols;
     if (EPI == E16_CONVT || EPI == E16_CONVT_GROUP) ncols = len_in + 1;
@@ -341,7 +344,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
             const int ch0 = (mt0 + mr) * 32 + 8 * g + rowoff;
             if (ch0 >= p.cout) continue;
             float4v bias = {0.f, 0.f, 0.f, 0.f};
-            if (p.bias) bias = *reinterpret_cast<const float4v*>(p.bias + ch0);
+            if (pbias) bias = *reinterpret_cast<const float4v*>(pbias + ch0);
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
                 const int t = colbase + nr * 32;
@@ -384,7 +387,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
             for (int r = 0; r < 16; ++r) {
                 const int co = (mt0 + mr) * 32 + (r & 3) + 8 * (r >> 2) + rowoff;
                 if (co >= p.cout) continue;
-                const float bias = p.bias ? p.bias[co] : 0.f;
+                const float bias = pbias ? pbias[co] : 0.f;
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) {
                     const int t = colbase + nr * 32;
@@ -410,7 +413,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
         for (int r = 0; r < 16; ++r) {
             const int ch = chbase + (r & 3) + 8 * (r >> 2) + rowoff;
             if (ch >= half) continue;
-            const float b0 = p.bias ? p.bias[ch] : 0.f, b1 = p.bias ? p.bias[ch + half] : 0.f;
+            const float b0 = pbias ? pbias[ch] : 0.f, b1 = pbias ? pbias[ch + half] : 0.f;
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
                 const int t = colbase + nr * 32;
@@ -431,7 +434,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
                     const int rho = (mt0 + mr) * 32 + (r & 3) + 8 * (r >> 2) + rowoff;
                     if (rho >= p.rows) continue;
                     const int ph = rho / p.cout, co = rho - ph * p.cout;
-                    const float bias = p.bias ? p.bias[co] : 0.f;
+                    const float bias = pbias ? pbias[co] : 0.f;
 #pragma unroll
                     for (int nr = 0; nr < NR; ++nr) {
                         const int q = colbase + nr * 32;
@@ -454,7 +457,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
                     if (rho0 >= p.rows) continue;
                     const int ph = rho0 / p.cout, co0 = rho0 - ph * p.cout;
                     float4v bias = {0.f, 0.f, 0.f, 0.f};
-                    if (p.bias) bias = *reinterpret_cast<const float4v*>(p.bias + co0);
+                    if (pbias) bias = *reinterpret_cast<const float4v*>(pbias + co0);
 #pragma unroll
                     for (int nr = 0; nr < NR; ++nr) {
                         const int q = colbase + nr * 32;
@@ -830,6 +833,8 @@ hipError_t launch_conv16(const PackedConv& w, const Conv16Call& c, int arith, hi
     p.x_ts = c.x.ts;
     p.wp = w.wp16;
     p.bias = w.bias;
+    p.bias_rows = w.bias_rs ? c.spk : nullptr;
+    p.bias_rs = w.bias_rs;
     p.len_in = c.len_in;
     p.len_out = c.len_out;
     p.t_in = c.t_in;

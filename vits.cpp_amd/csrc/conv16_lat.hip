@@ -48,6 +48,8 @@ struct Conv16LatParams {
     int xf_cs;
     const uint16_t* wp;  // A fragments (pack_conv_weights16)
     const float* bias;
+    const int* bias_rows;  // multi-speaker calls: effective-bias table row per utterance (PackedConv::bias_rs), or nullptr
+    int64_t bias_rs;
     const int* lens;
     int tmax;
     int dil, pad_l, pitch;
@@ -98,12 +100,13 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
     const float* rg = p.resg ? p.resg + (int64_t)b * p.g_bs : nullptr;
     const float* ag = p.accg ? p.accg + (int64_t)b * p.g_bs : nullptr;
     uint16_t* y16 = p.y16 ? p.y16 + (int64_t)b * p.y16_bs : nullptr;
+    const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;  // multi-speaker calls: this utterance's bias row
     float4v rv[4][NR], av[4][NR], bias4[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int ch0 = rt * 32 + 8 * g + rowoff;
         bias4[g] = float4v{0.f, 0.f, 0.f, 0.f};
-        if (p.bias) bias4[g] = *reinterpret_cast<const float4v*>(p.bias + ch0);
+        if (pbias) bias4[g] = *reinterpret_cast<const float4v*>(pbias + ch0);
 #pragma unroll
         for (int nr = 0; nr < NR; ++nr) {
             const int t = colbase + nr * 32;
@@ -318,7 +321,8 @@ bool conv16_lat_pre_wanted(const PackedConv& w, int batch, int tmax) {
     const int64_t tiles = (int64_t)((tmax + 31) / 32) * (w.cout / 32) * batch;
     return tiles <= kn.lat16h_max_tiles;
 }
-hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s) {
+hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s,
+                                 const int* spk) {
     if (!conv16_lat_pre_wanted(w, batch, tmax) || !x.p || !y16.p) return hipErrorInvalidValue;
     Conv16LatParams p = {};
     p.xf = x.p;
@@ -326,6 +330,8 @@ hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* le
     p.xf_cs = x.cs;
     p.wp = w.wp16;
     p.bias = w.bias;
+    p.bias_rows = w.bias_rs ? spk : nullptr;
+    p.bias_rs = w.bias_rs;
     p.lens = lens;
     p.tmax = tmax;
     p.dil = 1;
@@ -350,6 +356,8 @@ static Conv16LatParams c16l_params(const PackedConv& w, const Conv16Call& c, int
     p.x_ts = c.x.ts;
     p.wp = w.wp16;
     p.bias = w.bias;
+    p.bias_rows = w.bias_rs ? c.spk : nullptr;
+    p.bias_rs = w.bias_rs;
     p.lens = c.len_out;
     p.tmax = c.t_out;
     p.dil = c.dil;

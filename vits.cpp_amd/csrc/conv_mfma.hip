@@ -60,6 +60,8 @@ struct ConvParams {
     int a_cs;
     const float* wp;
     const float* bias;
+    const int* bias_rows;  // multi-speaker calls: effective-bias table row per utterance (PackedConv::bias_rs), or nullptr
+    int64_t bias_rs;
     const int* len_in;
     const int* len_out;
     int t_in, t_out;
@@ -153,6 +155,8 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
     const int wm = wid / WN, wn = wid % WN;
     const int b = bz;
     const int t0 = bx * BN;
+    // multi-speaker calls: this utterance's row of the effective-bias table (a uniform pointer; without rows, the packed bias as before)
+    const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;
     if constexpr (DB) VITS_ABL_SETPRIO(3);
     VITS_WSTART();
     const int len_in = p.len_in ? p.len_in[b] : p.t_in;
@@ -368,7 +372,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
             if (EPI == EPI_STD) idx = (mt0 + mr) * 32 + 8 * g + (lane & 3) + 4 * (lane >> 5);
             else if (EPI == EPI_GATE) idx = (mt0 / 2) * 32 + 8 * g + (lane & 3) + 4 * (lane >> 5) + (mr == 0 ? 0 : p.cout / 2);
             else idx = (mt0 + mr) * 4 + g;  // stride-8 transposed conv: 8 phases = 8 GEMM rows per output channel
-            bias_w[mr][g] = p.bias ? p.bias[idx < p.cout ? idx : p.cout - 1] : 0.f;
+            bias_w[mr][g] = pbias ? pbias[idx < p.cout ? idx : p.cout - 1] : 0.f;
         }
     // gated conv on MR = 1 tiles (the 128 x 32 tile): the tanh rows and the sigmoid rows of a channel group are two WAVES (even / odd
     // row tile); the even wave also needs the sigmoid rows' bias
@@ -377,7 +381,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int idx = (mt0 / 2) * 32 + 8 * g + (lane & 3) + 4 * (lane >> 5) + p.cout / 2;
-            bias_s[g] = p.bias ? p.bias[idx < p.cout ? idx : p.cout - 1] : 0.f;
+            bias_s[g] = pbias ? pbias[idx < p.cout ? idx : p.cout - 1] : 0.f;
         }
     }
 
@@ -692,7 +696,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
             for (int r = 0; r < 16; ++r) {
                 const int co = (mt0 + mr) * 32 + (r & 3) + 8 * (r >> 2) + rowoff;
                 if (co >= p.cout) continue;
-                const float bias = p.bias ? p.bias[co] : 0.f;
+                const float bias = pbias ? pbias[co] : 0.f;
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) {
                     const int t = colbase + nr * 32;
@@ -774,7 +778,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
         for (int r = 0; r < 16; ++r) {
             const int ch = chbase + (r & 3) + 8 * (r >> 2) + rowoff;
             if (ch >= half) continue;
-            const float b0 = p.bias ? p.bias[ch] : 0.f, b1 = p.bias ? p.bias[ch + half] : 0.f;
+            const float b0 = pbias ? pbias[ch] : 0.f, b1 = pbias ? pbias[ch + half] : 0.f;
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
                 const int t = colbase + nr * 32;
@@ -832,8 +836,8 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int co = (mt0 + mr) * 16 + 4 * g + 2 * (lane >> 5);
-                    b2[mr][g][0] = p.bias ? p.bias[co] : 0.f;
-                    b2[mr][g][1] = p.bias ? p.bias[co + 1] : 0.f;
+                    b2[mr][g][0] = pbias ? pbias[co] : 0.f;
+                    b2[mr][g][1] = pbias ? pbias[co + 1] : 0.f;
                 }
 #pragma unroll
             for (int mr = 0; mr < MR; ++mr)
@@ -870,7 +874,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
                 const int rho = (mt0 + mr) * 32 + (r & 3) + 8 * (r >> 2) + rowoff;
                 if (rho >= p.rows) continue;
                 const int co = rho / s, ph = rho - co * s;
-                const float bias = p.bias ? p.bias[co] : 0.f;
+                const float bias = pbias ? pbias[co] : 0.f;
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) {
                     const int q = colbase + nr * 32;
@@ -923,6 +927,7 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
     const int len_in = p.len_in ? p.len_in[b] : p.t_in;
     const int ncols = p.len_out ? p.len_out[b] : p.t_out;
     if (t0 >= ncols || len_in <= 0) return;
+    const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;  // (see conv_mfma_body)
 #ifdef VITS_PHASE_TIMING
 #define L16_STAMP(k)                                                                                      \
     do {                                                                                                  \
@@ -968,14 +973,14 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
             if (EPI == EPI_STD) {
                 const int co = mtile * 32 + 16 * half + 4 * jg + r;
                 const bool ok = co < p.cout && t_e < ncols;
-                ep_bias[r] = (p.bias && co < p.cout) ? p.bias[co] : 0.f;
+                ep_bias[r] = (pbias && co < p.cout) ? pbias[co] : 0.f;
                 ep_res[r] = (rb_e && ok) ? rb_e[(int64_t)co * p.r_cs + t_e] : 0.f;
                 ep_acc[r] = (ab_e && ok) ? ab_e[(int64_t)co * p.a_cs + t_e] : 0.f;
                 ep_b1[r] = 0.f;
             } else {
                 const int ch = (int)blockIdx.y * 32 + 16 * half + 4 * jg + r, halfc = p.cout / 2;
-                ep_bias[r] = (p.bias && ch < halfc) ? p.bias[ch] : 0.f;
-                ep_b1[r] = (p.bias && ch < halfc) ? p.bias[ch + halfc] : 0.f;
+                ep_bias[r] = (pbias && ch < halfc) ? pbias[ch] : 0.f;
+                ep_b1[r] = (pbias && ch < halfc) ? pbias[ch + halfc] : 0.f;
                 ep_res[r] = ep_acc[r] = 0.f;
             }
         }
@@ -1490,6 +1495,7 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
             const int i = have[slot];
             if (hipError_t e = make_conv_params(*w[i], c[i], TILE_128x128, g.m[slot])) return e;
             if (g.m[slot].oneshot) return hipErrorInvalidValue;  // (never: 128 x 128 tiles have MR * NR = 4)
+            if (g.m[slot].bias_rows) return hipErrorInvalidValue;  // (never: the grouped launch serves the resblocks, which carry no speaker term)
             g.m[slot].nbuf = 2;
             z += c[i].batch;
             ncols_max = std::max(ncols_max, c[i].t_out);
@@ -1591,6 +1597,8 @@ hipError_t make_conv_params(const PackedConv& w, const ConvCall& c, int tile, Co
     p.a_cs = c.acc.cs;
     p.wp = w.wp;
     p.bias = w.bias;
+    p.bias_rows = w.bias_rs ? c.spk : nullptr;
+    p.bias_rs = w.bias_rs;
     p.len_in = c.len_in;
     p.len_out = c.len_out;
     p.t_in = c.t_in;

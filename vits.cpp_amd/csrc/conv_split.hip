@@ -357,6 +357,7 @@ bool conv_split_supported(const PackedConv& w, int dil) {
 
 hipError_t launch_conv_split(const PackedConv& w, const ConvCall& c, hipStream_t s) {
     if (!conv_split_supported(w, c.dil) || !c.xs3.p || c.pre_act || c.y2 || (c.post_act != 0 && c.post_act != 2) || (!c.y.p && !c.ys3.p)) return hipErrorInvalidValue;
+    if (w.bias_rs && c.spk) return hipErrorInvalidValue;  // (no per-utterance bias here: the split path serves the resblocks only)
     ConvSplitParams p{};
     p.x = c.xs3.p, p.x_bs = c.xs3.bs, p.x_ps = c.xs3.ps, p.x_ts = c.xs3.ts;
     p.wp = w.wps;

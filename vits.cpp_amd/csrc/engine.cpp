@@ -47,6 +47,7 @@ hipError_t Engine::conv16_transparent(const char* name, const PackedConv& w, con
     Conv16Call k;
     k.x = x16;
     k.len_in = c.len_in;
+    k.spk = c.spk;
     k.len_out = c.len_out;
     k.batch = c.batch;
     k.t_in = c.t_in;
@@ -113,12 +114,35 @@ int Engine::sync(std::string& err) {
     return 0;
 }
 
+int Engine::check_speakers(const vits_process_opts& o, int B, std::string& err) const {
+    for (int b = 0; b < B; ++b) {
+        const int s = speaker_of(o, b);
+        if (s == -1) continue;
+        const std::string who = (o.speaker_ids ? "speaker_ids[" + std::to_string(b) + "] = " : "the model's default speaker (utterance " + std::to_string(b) + ") = ") +
+                                std::to_string(s);
+        if (hp.num_speakers <= 1) {
+            err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
+            return -1;
+        }
+        if (s < -1 || s >= hp.num_speakers) {
+            err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+            return -1;
+        }
+        if (ggml_tables == 1) {
+            err = who + ": vits_model_set_ggml_tables(model, 1) runs stage one in the CPU oracle's exact order, which has no speaker conditioning (use -1, or tables mode 0 / 2)";
+            return -1;
+        }
+    }
+    return 0;
+}
+
 int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                           std::string& err) {
     if (pending()) {
         err = "batches in flight: call vits_model_wait for every submitted batch first";
         return -1;
     }
+    if (check_speakers(o, B, err)) return -1;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -141,6 +165,7 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
     for (int h = 0; h < 2; ++h) {
         vits_process_opts oh = o;
         oh.noise_seed_offsets = offs.data() + b0[h];
+        if (o.speaker_ids) oh.speaker_ids = o.speaker_ids + b0[h];
         if (o.out_device) oh.out_device = (float*)o.out_device + (int64_t)b0[h] * o.out_device_stride;
         if (submit_batch(ids + (size_t)b0[h] * id_stride, id_lens ? id_lens + b0[h] : nullptr, nb[h], id_stride, oh, err)) break;
         ++queued;
@@ -207,6 +232,7 @@ int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int 
         err = "vits_model_submit_batch: VITS_NOISE_COUNTER only, and no collect_taps / on_chunk / frames_only / async";
         return -1;
     }
+    if (check_speakers(o, B, err)) return -1;  // (the speakers are copied into the call's header below: the caller's array may go at once)
     Pending& p = pend_[submit_seq_ & 1];
     if (!p.done) {
         HIP_OK(hipEventCreateWithFlags(&p.s1_done, hipEventDisableTiming));

@@ -192,6 +192,14 @@ class Engine {
     // takes this flag around every entry point that touches the engine; a second thread gets "model busy" instead of a race.
     std::atomic<bool> busy{false};
     int set_arith(int arith, std::string& err);  // VITS_ARITH_*: packs the 16-bit weight fragments on first use
+    // speaker conditioning (multi-speaker models): the speaker of utterances the call does not name (vits_process_opts::speaker_ids == NULL,
+    // vits_model_process / _ids); -1 = none
+    int speaker = -1;
+    int num_speakers() const { return hp.num_speakers > 1 ? hp.num_speakers : 1; }
+    // 0, or -1 + a message naming the utterance: every speaker of the call in [-1, num_speakers), none >= 0 on a single-speaker model or with
+    // the exact-order stage one (ggml_tables == 1)
+    int check_speakers(const vits_process_opts& o, int B, std::string& err) const;
+    int speaker_of(const vits_process_opts& o, int b) const { return o.speaker_ids ? o.speaker_ids[b] : speaker; }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -334,6 +342,9 @@ class Engine {
     bool pack(const ModelFile& f, const std::string& wname, const std::string& bname, int epi, ConvShape want, PackedConv& out, std::string& err,
               int ct_stride = 0, int transform = 0);
     bool load_dds(const ModelFile& f, const std::string& base, DdsW& d, std::string& err);
+    // multi-speaker models: the effective-bias table (speaker_bias_kernel) and the conditioned layers pointed into its row 0
+    bool load_speakers(const ModelFile& f, std::string& err);
+    float* spk_table_ = nullptr;
     hipError_t conv(const char* name, const PackedConv& w, ConvCall c, hipStream_t on = nullptr);  // on == nullptr: the main stream
     hipError_t run_dds(const DdsW& d, TensorRef x, TensorRef y, TensorRef p, const int* lens, int batch, int tmax, int64_t sum_t);
     // The DDS block on the latency kernels (stage1_lat.hip) with the per-token ops around it fused in: the head (a conv flow's 1 -> H conv +
@@ -344,6 +355,7 @@ class Engine {
         int zc = 0;
         const PackedConv* head_conv = nullptr;  // or: 1x1 conv of head_x
         TensorRef head_x;
+        const int* spk = nullptr;  // head_conv's effective-bias table rows (multi-speaker calls)
         const PackedConv* tail_conv = nullptr;
         TensorRef tail_y;
     };

@@ -188,12 +188,14 @@ int Engine::run_flow(Call& c) {
     const int* ll = c.d_len_full[0];
     TensorRef hout = TR(s2.hout, 2 * H, ls), gate = TR(s2.gate, H, ls);
     TensorRef hh = hout;  // channels [0,H) = h, [H,2H) = skip accumulator "outputs" (vits.cpp:460)
+    const int* spk = c.spk;  // (multi-speaker calls: read by the speaker-conditioned in_layers only)
     auto mk2 = [&](TensorRef xin, TensorRef yout) {
         ConvCall c;
         c.x = xin;
         c.y = yout;
         c.len_in = ll;
         c.len_out = ll;
+        c.spk = spk;
         c.batch = B;
         c.t_in = c.t_out = Lmax;
         c.sum_in = c.sum_out = sum_frames;
@@ -240,6 +242,7 @@ int Engine::run_flow(Call& c) {
                 fc.x1 = x1;
                 fc.x1.p += (int64_t)b0 * x1.bs;
                 fc.lens = ll + b0;
+                fc.spk = spk ? spk + b0 : nullptr;
                 fc.batch = nb;
                 fc.tmax = 0;
                 for (int b = b0; b < b0 + nb; ++b) fc.tmax = std::max(fc.tmax, frames[b]);
@@ -254,6 +257,7 @@ int Engine::run_flow(Call& c) {
             fc.x0 = x0;
             fc.x1 = x1;
             fc.lens = ll;
+            fc.spk = spk;
             fc.batch = B;
             fc.tmax = Lmax;
             fc.hidden = H;
@@ -300,6 +304,7 @@ int Engine::run_flow(Call& c) {
                 if (l + 1 == hp.wn_layers) w.h_out = TensorRef();
                 w.outputs = sub(hout, H);
                 w.lens = ll;
+                w.spk = spk;
                 w.batch = B;
                 w.tmax = Lmax;
                 w.hidden = H;

@@ -100,13 +100,16 @@ struct Call {
 
     // stage one (sized by B x T)
     struct S1 {
-        int *ids, *lens, *cum, *frames, *stage_lens, *stage_mul, *stage_add, *seed_off;
+        int *ids, *lens, *cum, *frames, *stage_lens, *stage_mul, *stage_add, *seed_off, *spk_row;
         float *x, *qkv, *att, *tmp, *ffn, *stats, *dpx, *dpy, *dpp, *cond, *z, *u, *dur;
         float *ex_scores, *ex_tok;  // emulated-ggml mode 1 only
         uint16_t* x16;
     } s1{};
     std::vector<int> smul, sadd;  // vocoder stage lengths as affine functions of the frame count: len_i = L * smul[i] + sadd[i]
     int c_first = 0;              // physical row of z holding the log-durations after the duration predictor's flips
+    // multi-speaker calls: the effective-bias table row of every utterance (device [B]: speaker + 1) — null when every utterance of the call is
+    // speaker -1, so that such a call queues exactly the kernels (and reads exactly the biases) of a single-speaker model
+    const int* spk = nullptr;
     RefNoiseAhead* ref_ahead = nullptr;  // batch 1, reference noise: the prior noise drawn while stage one runs (engine.cpp)
 
     // the one data-dependent shape (vits.cpp:1133)

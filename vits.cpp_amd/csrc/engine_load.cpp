@@ -245,6 +245,105 @@ bool Engine::pack(const ModelFile& f, const std::string& wname, const std::strin
     return true;
 }
 
+// Speaker conditioning (transformers modeling_vits.py, VitsModel with num_speakers > 1): g = embed_speaker[s] enters three places, each as a 1x1
+// conv of g added to the output of a conv that has a bias — duration_predictor.conv_pre (+ duration_predictor.cond), every WaveNet layer i of coupling
+// layer f (in_layers[i] + channels [2H i, 2H (i + 1)) of flows.f.wavenet.cond_layer) and decoder.conv_pre (+ decoder.cond). Those terms are constant
+// over time, so each is folded into the conv's bias: one table row per speaker (row 0 = speaker -1 = the plain biases) holds every conditioned bias,
+// and the conditioned PackedConvs point into row 0 with bias_rs = the row stride. Segments start at multiples of four floats (float4 bias loads).
+bool Engine::load_speakers(const ModelFile& f, std::string& err) {
+    const int H = hp.hidden, E = hp.speaker_embedding_size, N = hp.num_speakers, nl = hp.wn_layers;
+    auto tensor = [&](const std::string& name, std::initializer_list<int64_t> want, std::vector<float>& out) -> bool {
+        const TensorEntry* t = f.find(name);
+        if (!t) {
+            err = "[ERROR] tensor not found: " + name;
+            return false;
+        }
+        if (t->dtype > DT_BF16 || !shape_is(*t, want)) {
+            err = "tensor '" + name + "' has shape " + shape_str(*t) + ", expected " + shape_str(want);
+            return false;
+        }
+        out = t->to_f32();
+        return true;
+    };
+    struct Seg {
+        PackedConv* pc;
+        std::string w, b;
+        int n, row0;  // channels, first row of the cond conv's output that belongs to this segment
+        int64_t off = 0;
+    };
+    std::vector<Seg> segs;
+    segs.push_back({&dp_pre_, "duration_predictor.cond.weight", "duration_predictor.cond.bias", H, 0});
+    for (int i = 0; i < hp.n_flows; ++i)
+        for (int l = 0; l < nl; ++l)
+            segs.push_back({&flow_[i].in_layers[l], "flow.flows." + std::to_string(i) + ".wavenet.cond_layer.weight", "flow.flows." + std::to_string(i) + ".wavenet.cond_layer.bias",
+                            2 * H, 2 * H * l});
+    segs.push_back({&dec_pre_, "decoder.cond.weight", "decoder.cond.bias", hp.up_init, 0});
+    int64_t rs = 0;
+    for (Seg& s : segs) {
+        if (!s.pc->bias || s.pc->cout != s.n) {
+            err = "speaker conditioning needs a bias on every conditioned conv";
+            return false;
+        }
+        s.off = rs;
+        rs += (s.n + 3) / 4 * 4;
+    }
+    std::vector<float> emb;
+    if (!tensor("embed_speaker.weight", {E, N}, emb)) return false;
+    // the cond convs: one per conditioned place (the flow's covers all nl layers of its coupling layer), checked before anything is allocated
+    std::map<std::string, std::pair<std::vector<float>, std::vector<float>>> cond;
+    for (const Seg& s : segs) {
+        if (cond.count(s.w)) continue;
+        const int rows = s.w.find("cond_layer") != std::string::npos ? 2 * H * nl : s.n;
+        auto& wb = cond[s.w];
+        if (!tensor(s.w, {1, E, rows}, wb.first) || !tensor(s.b, {rows}, wb.second)) return false;
+    }
+    const size_t table_floats = (size_t)(N + 1) * rs;
+    if (dry_run_) {
+        weight_bytes += (int64_t)table_floats * 4;
+        return true;
+    }
+    // device: the table (resident), the embedding and the cond convs (temporaries of this function)
+    std::vector<void*> tmp;
+    auto dev = [&](const float* p, size_t n) -> float* {
+        float* d = nullptr;
+        if (hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) return nullptr;
+        tmp.push_back(d);
+        if (hipMemcpy(d, p, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    };
+    bool ok = hipMalloc((void**)&spk_table_, table_floats * sizeof(float)) == hipSuccess;
+    if (ok) {
+        owned_.push_back(spk_table_);
+        weight_bytes += (int64_t)table_floats * 4;
+    }
+    const float* d_emb = ok ? dev(emb.data(), emb.size()) : nullptr;
+    ok = ok && d_emb;
+    std::map<std::string, std::pair<float*, float*>> d_cond;
+    for (auto& kv : cond) {
+        if (!ok) break;
+        float* w = dev(kv.second.first.data(), kv.second.first.size());
+        float* b = dev(kv.second.second.data(), kv.second.second.size());
+        ok = w && b;
+        d_cond[kv.first] = {w, b};
+    }
+    for (const Seg& s : segs) {
+        if (!ok) break;
+        const auto& wb = d_cond[s.w];
+        ok = launch_speaker_bias(s.pc->bias, wb.first + (int64_t)s.row0 * E, wb.second + s.row0, d_emb, s.n, E, N, spk_table_ + s.off, rs, stream) == hipSuccess;
+    }
+    ok = ok && hipStreamSynchronize(stream) == hipSuccess;
+    for (void* p : tmp) hipFree(p);
+    if (!ok) {
+        err = "could not build the speaker bias table on the device";
+        return false;
+    }
+    for (Seg& s : segs) {
+        s.pc->bias = spk_table_ + s.off;  // row 0: the plain biases (a call without speakers reads exactly these values)
+        s.pc->bias_rs = rs;
+    }
+    return true;
+}
+
 bool Engine::load_dds(const ModelFile& f, const std::string& base, DdsW& d, std::string& err) {
     const int H = hp.hidden;
     d.pw.resize(hp.dds_layers);  // (sized first: set_arith keeps pointers to the PackedConv entries)
@@ -486,6 +585,7 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
         vocoder_group_ok_ = (hp.flow_size % 8 == 0) && (hp.up_init % 8 == 0);
         for (const UpStageW& U : ups_) vocoder_group_ok_ = vocoder_group_ok_ && (U.channels % 8 == 0);
     }
+    if (hp.num_speakers > 1 && !load_speakers(f, err)) return false;
     if (!dry_run_ && hipDeviceSynchronize() != hipSuccess) {
         err = "device error while uploading weights";
         return false;

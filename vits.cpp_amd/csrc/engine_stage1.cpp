@@ -76,6 +76,7 @@ hipError_t Engine::run_dds_lat(const DdsW& d, const DdsEnds& e, TensorRef a, Ten
                 c.head_w = e.head_w, c.head_b = e.head_b, c.z = e.z, c.cond = e.cond, c.zc = e.zc;
             } else if (e.head_conv) {
                 c.head_conv = e.head_conv, c.x = e.head_x;
+                c.spk = e.spk;
                 flop += 2.0 * H * H * (double)sum_t;
                 bytes += (double)e.head_conv->bytes;
             } else
@@ -106,14 +107,15 @@ int Engine::layout_stage_one(Call& c) {
     const int H = hp.hidden, F = hp.flow_size;
     Call::S1& s1 = c.s1;
     size_t x16_elems1 = 0;
-    const size_t hdr_ints = (size_t)B * id_stride + 2 * (size_t)B + 2 * (size_t)(n_up + 1);
+    const size_t hdr_ints = (size_t)B * id_stride + 3 * (size_t)B + 2 * (size_t)(n_up + 1);
     auto layout1 = [&](Arena& a) {
-        // host-written header, one block = one H2D copy: ids | lens | stage_mul | stage_add | seed_off
+        // host-written header, one block = one H2D copy: ids | lens | stage_mul | stage_add | seed_off | spk_row
         s1.ids = a.alloc<int>(hdr_ints);
         s1.lens = s1.ids + (size_t)B * id_stride;
         s1.stage_mul = s1.lens + B;
         s1.stage_add = s1.stage_mul + (n_up + 1);
         s1.seed_off = s1.stage_add + (n_up + 1);
+        s1.spk_row = s1.seed_off + B;
         s1.cum = a.alloc<int>((size_t)B * id_stride);
         s1.frames = a.alloc<int>(B);
         s1.stage_lens = a.alloc<int>((size_t)(n_up + 1) * B);
@@ -192,6 +194,15 @@ int Engine::layout_stage_one(Call& c) {
         // counter-noise stream of utterance b: noise_seed + seed_off[b] (default b; a dispatcher that re-orders utterances
         // across ranks passes each one's global index so that its audio does not depend on where it ran)
         for (int b = 0; b < B; ++b) hs.p[(size_t)B * id_stride + B + 2 * (n_up + 1) + b] = o.noise_seed_offsets ? o.noise_seed_offsets[b] : b;
+        // speaker s of utterance b -> row s + 1 of the effective-bias table (row 0: speaker -1, the plain biases); the kernels get the rows only
+        // when some utterance has a speaker
+        bool any_spk = false;
+        for (int b = 0; b < B; ++b) {
+            const int sp = speaker_of(o, b);
+            hs.p[(size_t)B * id_stride + 2 * B + 2 * (n_up + 1) + b] = sp + 1;
+            any_spk = any_spk || sp >= 0;
+        }
+        c.spk = any_spk ? s1.spk_row : nullptr;
         HIP_OK(hipMemcpyAsync(s1.ids, hs.p, sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
         HIP_OK(hipEventRecord(hs.ev, stream));
         hs.pending = true;
@@ -309,12 +320,14 @@ int Engine::run_duration_predictor(Call& c) {
     auto TR = make_ref;
     auto sub = sub_rows;
     TensorRef x = TR(s1.x, H, ts);
+    const int* spk = c.spk;
     auto mk = [&](TensorRef xin, TensorRef yout, int tmax_) {
         ConvCall c;
         c.x = xin;
         c.y = yout;
         c.len_in = dl;
         c.len_out = dl;
+        c.spk = spk;  // (read by the speaker-conditioned conv_pre only)
         c.batch = B;
         c.t_in = c.t_out = tmax_;
         c.sum_in = c.sum_out = sum_t;
@@ -325,6 +338,7 @@ int Engine::run_duration_predictor(Call& c) {
     {
         DdsEnds e;  // conv_pre (vits.cpp:939) -> DDS block -> conv_proj (:941): three launches on small grids
         e.head_conv = &dp_pre_, e.head_x = x, e.tail_conv = &dp_proj_, e.tail_y = cond;
+        e.spk = spk;
         if (dds_lat_ok(dp_dds_, e, B, Tmax)) {
             HIP_OK(run_dds_lat(dp_dds_, e, dpy, dpp, dl, B, Tmax, sum_t));
         } else {

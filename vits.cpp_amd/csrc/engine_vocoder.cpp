@@ -40,23 +40,24 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
     // one to four utterances: conv_pre reads the fp32 flow output itself and runs on conv16_lat_kernel (conv16_lat.hip: no converter launch; same bits)
     const bool pre_lat = !prof.on && F == dec_pre_.cin && conv16_lat_pre_wanted(dec_pre_, B, Lw);
     if (pre_lat) {
-        HIP_OK(launch_conv16_lat_pre(dec_pre_, zwin, d_len[0], B, Lw, cur16, hp.lrelu, arith_now_, stream));
+        HIP_OK(launch_conv16_lat_pre(dec_pre_, zwin, d_len[0], B, Lw, cur16, hp.lrelu, arith_now_, stream, c.spk));
     } else {
         prof.begin("to_group16", 0, 6.0 * F * (double)ssum[0], stream, true);
         HIP_OK(launch_to_group16(zwin, d_len[0], B, F, Lw, 1.0f, z16, arith_now_, stream));
         prof.end(stream);
     }
     if (!pre_lat) {
-        Conv16Call c;
-        c.x = z16;
-        c.len_in = c.len_out = d_len[0];
-        c.batch = B;
-        c.t_in = c.t_out = Lw;
-        c.sum_in = c.sum_out = ssum[0];
-        c.pad_l = (dec_pre_.kt - 1) / 2;
-        c.y16 = cur16;
-        c.y16_slope = hp.lrelu;  // only reader: the first upsampler, behind its leaky_relu (vits.cpp:613)
-        HIP_OK(conv16("hifigan_conv_pre", dec_pre_, c, stream, 2.0 * (F + hp.up_init) * (double)ssum[0] + (double)dec_pre_.bytes16));
+        Conv16Call cv;
+        cv.x = z16;
+        cv.len_in = cv.len_out = d_len[0];
+        cv.spk = c.spk;  // (multi-speaker calls: conv_pre carries the speaker term)
+        cv.batch = B;
+        cv.t_in = cv.t_out = Lw;
+        cv.sum_in = cv.sum_out = ssum[0];
+        cv.pad_l = (dec_pre_.kt - 1) / 2;
+        cv.y16 = cur16;
+        cv.y16_slope = hp.lrelu;  // only reader: the first upsampler, behind its leaky_relu (vits.cpp:613)
+        HIP_OK(conv16("hifigan_conv_pre", dec_pre_, cv, stream, 2.0 * (F + hp.up_init) * (double)ssum[0] + (double)dec_pre_.bytes16));
     }
     for (int i = 0; i < n_up; ++i) {
         const UpStageW& U = ups_[i];
@@ -420,18 +421,19 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
     auto TR = make_ref;
     TensorRef h0 = TR(s2.h0, hp.up_init, lws);
     {
-        ConvCall c;
-        c.x = zwin;
-        c.y = h0;
-        c.len_in = d_len[0];
-        c.len_out = d_len[0];
-        c.batch = B;
-        c.t_in = c.t_out = Lw;
-        c.sum_in = c.sum_out = ssum[0];
-        c.pad_l = (dec_pre_.kt - 1) / 2;  // padding 3 (vits.cpp:601)
-        c.post_act = 2;  // its only reader is the first upsampler, which takes leaky_relu(h0) (vits.cpp:613): activate at the writer
-        c.post_slope = hp.lrelu;
-        HIP_OK(conv("hifigan_conv_pre", dec_pre_, c));
+        ConvCall cv;
+        cv.x = zwin;
+        cv.y = h0;
+        cv.len_in = d_len[0];
+        cv.len_out = d_len[0];
+        cv.spk = c.spk;  // (multi-speaker calls: conv_pre carries the speaker term)
+        cv.batch = B;
+        cv.t_in = cv.t_out = Lw;
+        cv.sum_in = cv.sum_out = ssum[0];
+        cv.pad_l = (dec_pre_.kt - 1) / 2;  // padding 3 (vits.cpp:601)
+        cv.post_act = 2;  // its only reader is the first upsampler, which takes leaky_relu(h0) (vits.cpp:613): activate at the writer
+        cv.post_slope = hp.lrelu;
+        HIP_OK(conv("hifigan_conv_pre", dec_pre_, cv));
     }
     TensorRef cur = h0;
     const size_t nk = hp.rb_k.size();

@@ -203,6 +203,10 @@ enum ConvTile : int {
 struct PackedConv {
     float* wp = nullptr;    // packed weights
     float* bias = nullptr;  // [cout] (original channel order) or nullptr
+    // speaker-conditioned layers of a multi-speaker model (the duration predictor's conv_pre, every WaveNet in_layer, the decoder's conv_pre): bias
+    // points into row 0 of the engine's effective-bias table (speaker -1 = the plain biases) and bias_rs is that table's row stride (floats). A call
+    // with speakers passes one row index per utterance (ConvCall::spk ...); the kernels then read bias + bias_rs * spk[b]. 0: not conditioned.
+    int64_t bias_rs = 0;
     int cin = 0, cout = 0, kt = 0;
     int rows = 0;      // GEMM M (cout, or cout*stride for the transposed conv)
     int mtiles = 0;       // number of 32-row tiles in the packed array (padded to a multiple of 4)
@@ -237,6 +241,7 @@ struct ConvCall {
     TensorRef x, y, res, acc;  // res/acc optional (p == nullptr)
     const int* len_in = nullptr;   // per-utterance valid input length (nullptr: t_in)
     const int* len_out = nullptr;  // per-utterance valid output length (nullptr: t_out)
+    const int* spk = nullptr;      // per-utterance row of the effective-bias table (device [batch]; read only when w.bias_rs != 0), or nullptr = row 0
     int batch = 1;
     int t_in = 0, t_out = 0;  // maximum lengths (grid extent)
     // profiler accounting only: sum over the batch of the per-utterance valid input / output lengths (< 0: batch * t_in / t_out).
@@ -292,6 +297,7 @@ struct Conv16Call {
     Ref16 x;  // input, group layout (already activated: the writer / converter applies the leaky_relu)
     const int* len_in = nullptr;
     const int* len_out = nullptr;
+    const int* spk = nullptr;  // effective-bias table rows (see ConvCall::spk)
     int batch = 1, t_in = 0, t_out = 0, dil = 1, pad_l = 0;
     int post_act = 0;  // standard outputs: 1 relu, 2 leaky_relu(post_slope) of the stored value; group outputs: 1 relu
     float post_slope = 0.f;
@@ -385,6 +391,7 @@ hipError_t launch_rbblock32(const PackedConv* const* c1, const PackedConv* const
 struct WaveNet32Call {
     TensorRef h, h_out, outputs;
     const int* lens = nullptr;
+    const int* spk = nullptr;  // effective-bias table rows of the gated conv's bias (see ConvCall::spk)
     int batch = 1, tmax = 0, hidden = 0, dil = 1;
 };
 bool wavenet32_supported(int hidden, int kt, int dil, const PackedConv& in, const PackedConv& rs);
@@ -395,6 +402,7 @@ hipError_t launch_wavenet16(const PackedConv& in, const PackedConv& rs, const Wa
 struct FlowCouple16Call {
     TensorRef x0, x1;  // conditioning half (read), updated half (in place): fp32 [b][F/2][t]
     const int* lens = nullptr;
+    const int* spk = nullptr;  // effective-bias table rows of the in_layers' biases (see ConvCall::spk)
     int batch = 1, tmax = 0, hidden = 0, half = 0;
 };
 bool flow_couple16_supported(int hidden, int half, int kt, int rate, int layers, const PackedConv& pre, const PackedConv* in, const PackedConv* rs, const PackedConv& post);
@@ -411,7 +419,8 @@ hipError_t launch_conv16_lat(const PackedConv& w, const Conv16Call& c, int arith
 bool conv16_lat_group_wanted(const PackedConv* const* w, const Conv16Call* c);  // the same-position convs of a stage's three resblocks (k = 3, 7, 11) as ONE launch
 hipError_t launch_conv16_lat_group(const PackedConv* const* w, const Conv16Call* c, int arith, hipStream_t s);
 bool conv16_lat_pre_wanted(const PackedConv& w, int batch, int tmax);  // the vocoder's conv_pre on a small grid, straight from the fp32 flow output (no converter launch)
-hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s);
+hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s,
+                                 const int* spk = nullptr);
 hipError_t launch_conv16(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s);
 // ConvTranspose1d (kernel = 2 x stride) in the group layout as a streaming kernel (convt16.hip): all stride x c_out rows of a tile of input
 // positions per block; bit-identical to launch_conv16 on the same call
@@ -462,6 +471,7 @@ struct DdsLatCall {
     const PackedConv* tail_conv = nullptr;
     TensorRef y2;
     const int* lens = nullptr;
+    const int* spk = nullptr;  // effective-bias table rows of head_conv's bias (see ConvCall::spk)
     int batch = 1, channels = 0, tmax = 0, k = 3, dil = 1;
     float eps = 1e-5f;
     GgmlTables tabs;
@@ -493,6 +503,10 @@ hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, i
 hipError_t launch_zp(TensorRef mean, TensorRef logvar, const int* cum, int cum_stride, const int* tok_lens, const int* frames, TensorRef noise, int noise_kind,
                      uint64_t seed, const int* seed_off, float noise_scale, TensorRef zp, int batch, int channels, int lmax, hipStream_t s);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
+// one segment of the effective-bias table of a multi-speaker model (built once at load): row 0 (speaker -1) = bias, row 1 + s =
+// bias + (cond_w . emb[s] + cond_b) for the n channels of the segment; cond_w is the conditioning 1x1 conv [n][E], emb [n_spk][E]
+hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const float* cond_b, const float* emb, int n, int E, int n_spk, float* table,
+                               int64_t row_stride, hipStream_t s);
 hipError_t launch_rb_sum3_std(TensorRef y0, TensorRef y1, TensorRef y2, TensorRef out, int channels, const int* lens, int batch, int tmax, float scale, int scale_div, int post_act,
                               float post_slope, hipStream_t s);  // fp32 [b][c][t]: ((y0 + y1) [+ y2]) scaled [+ leaky_relu]: side-by-side resblocks of the fp32 path (small grids)
 hipError_t launch_fill_rows(TensorRef x, int channels, float v, int batch, int tmax, hipStream_t s);

@@ -46,6 +46,32 @@ hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Effective-bias table of a multi-speaker model (built once at load; transformers modeling_vits.py: the speaker terms of
+// VitsStochasticDurationPredictor.forward, VitsWaveNet.forward and VitsHifiGan.forward are per-utterance constants over time).
+// Thread = (table row r, channel c) of one segment: row 0 (speaker -1) is the plain bias, row 1 + s is
+// bias[c] + (sum_e cond_w[c][e] * emb[s][e] + cond_b[c]) — the 1x1 conditioning conv of g = emb[s], products summed in e order.
+__global__ void speaker_bias_kernel(const float* __restrict__ bias, const float* __restrict__ cw, const float* __restrict__ cb, const float* __restrict__ emb,
+                                    int n, int E, float* __restrict__ table, int64_t rs) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (c >= n) return;
+    float v = bias[c];
+    if (r > 0) {
+        const float* g = emb + (int64_t)(r - 1) * E;
+        const float* w = cw + (int64_t)c * E;
+        float acc = 0.f;
+        for (int e = 0; e < E; ++e) acc = fmaf(w[e], g[e], acc);
+        v = v + (acc + cb[c]);
+    }
+    table[(int64_t)r * rs + c] = v;
+}
+hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const float* cond_b, const float* emb, int n, int E, int n_spk, float* table,
+                               int64_t row_stride, hipStream_t s) {
+    if (n <= 0 || E <= 0 || n_spk < 1 || !bias || !cond_w || !cond_b || !emb || !table) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(speaker_bias_kernel, dim3((n + 255) / 256, n_spk + 1), dim3(256), 0, s, bias, cond_w, cond_b, emb, n, E, table, row_stride);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Relative-position self-attention core (vits.cpp:296-356; helpers :195-235).  SURVEY.md App. F1 closed form:
 //   s_ij = q_i.k_j + [|j-i|<=w] q_i.Ek[j-i+w];  p = softmax_j;  o_i = sum_j p_ij v_j + sum_{|j-i|<=w} p_ij Ev[j-i+w]
 // The reference materialises dense (2T-1)-row relative tables and pads/reshapes them (pure data movement);

@@ -317,6 +317,7 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         getf("speaking_rate", speaking_rate);
         geti("sampling_rate", sampling_rate);
         geti("speaker_embedding_size", speaker_embedding_size);
+        geti("num_speakers", num_speakers);
         if (!f.cfg("hidden_act").empty()) hidden_act = f.cfg("hidden_act");
         if (!f.cfg("use_stochastic_duration_prediction").empty()) stochastic_duration = f.cfg("use_stochastic_duration_prediction") == "True";
     } catch (const std::exception& e) {
@@ -336,8 +337,11 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         err = "Only stochastic duration prediction is supported";
         return false;
     }
-    if (speaker_embedding_size != 0) {
-        err = "speaker conditioning is not implemented (reference asserts the same, vits.cpp:461,603,936)";
+    // speaker conditioning (transformers VitsModel: embed_speaker exists only for num_speakers > 1; the reference asserts it away,
+    // vits.cpp:461,603,936): num_speakers == 1 with an embedding size loads and is never conditioned, as in transformers
+    if (num_speakers < 1 || speaker_embedding_size < 0 || (num_speakers > 1 && speaker_embedding_size == 0)) {
+        err = "inconsistent speaker configuration: num_speakers " + std::to_string(num_speakers) + " with speaker_embedding_size " +
+              std::to_string(speaker_embedding_size) + " (a multi-speaker model needs speaker_embedding_size > 0)";
         return false;
     }
     if (up_rates.size() != up_k.size() || rb_k.size() != rb_d.size() || heads <= 0 || hidden % heads != 0 || flow_size % 2 != 0) {
@@ -424,6 +428,9 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
     Synth s;
     s.seed = seed;
     s.bf16 = (arch_flags & VITS_SYNTH_BF16) != 0;
+    // VITS_SYNTH_SPEAKERS: a multi-speaker model — the same tensors as without the flag (same values), then the speaker tensors behind them
+    const bool speakers = (arch_flags & VITS_SYNTH_SPEAKERS) != 0;
+    const int spk_n = speakers ? (arch == VITS_SYNTH_TINY ? 4 : 109) : 1, spk_e = speakers ? (arch == VITS_SYNTH_TINY ? 8 : 256) : 0;
     ModelFile& f = s.f;
     // tokenizer block: a 38-entry single-character vocabulary in the style of the MMS checkpoints
     {
@@ -458,8 +465,8 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         put("hidden_act", "relu");
         put("layer_norm_eps", "1e-05");
         put("use_stochastic_duration_prediction", "True");
-        puti("num_speakers", 1);
-        puti("speaker_embedding_size", 0);
+        puti("num_speakers", spk_n);
+        puti("speaker_embedding_size", spk_e);
         puti("upsample_initial_channel", h.up_init);
         put("upsample_rates", list_str(h.up_rates));
         put("upsample_kernel_sizes", list_str(h.up_k));
@@ -560,6 +567,14 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
             dds(b + "conv_dds.");
             s.conv(b + "conv_proj", 3 * h.dp_bins - 1, H, 1, 2.0f * std::sqrt((float)H / 192.0f));
         }
+    }
+    if (speakers) {
+        // names and shapes of transformers' VitsModel(num_speakers, speaker_embedding_size) after weight-norm removal; the gains make the
+        // speaker terms large enough that two speakers visibly differ in durations and audio
+        s.add("embed_speaker.weight", {spk_n, spk_e}, false, 1.0f);
+        s.conv("duration_predictor.cond", H, spk_e, 1, 0.6f);
+        for (int i = 0; i < h.n_flows; ++i) s.conv("flow.flows." + std::to_string(i) + ".wavenet.cond_layer", 2 * H * h.wn_layers, spk_e, 1, 0.3f);
+        s.conv("decoder.cond", h.up_init, spk_e, 1, 0.5f);
     }
     return std::move(s.f);
 }

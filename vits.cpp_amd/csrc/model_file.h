@@ -69,6 +69,7 @@ struct HParams {
     std::string hidden_act = "relu";
     bool stochastic_duration = true;
     int speaker_embedding_size = 0;
+    int num_speakers = 1;  // > 1: a multi-speaker model (embed_speaker + the cond layers; speaker_embedding_size > 0)
     bool load(const ModelFile& f, std::string& err);
 };
 

@@ -57,6 +57,8 @@ struct DdsLatParams {
     int64_t c_bs;
     int c_cs;
     const float *h_w, *h_b;  // HEAD_FROM1: w [H], bias [H]; HEAD_CONV: bias [H]
+    const int* h_rows;       // HEAD_CONV of a multi-speaker call: effective-bias table row per utterance (PackedConv::bias_rs), or nullptr
+    int64_t h_rs;
     const float* h_wl16;     // HEAD_CONV: 16x16x4 A fragments of the H x h_cin 1x1 conv
     int h_nchunks;
     const float *dw_w, *dw_b, *g1, *b1, *pw_b, *g2, *b2;
@@ -119,6 +121,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
     const int b = blockIdx.y, t0 = blockIdx.x * NT;
     const int len = p.lens ? p.lens[b] : p.tmax;
     if (t0 >= len) return;
+    if (p.h_rows) p.h_b += p.h_rs * p.h_rows[b];  // multi-speaker calls: this utterance's row of the head conv's bias
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int tl = tid & 15, rr = tid >> 4, rstep = nthr >> 4;  // element-parallel phases: column tl, channels rr, rr + rstep, ...
     const int jg = lane >> 4, col = lane & 15;
@@ -358,6 +361,7 @@ hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s) {
         head = DDS_HEAD_CONV;
         p.x = c.x.p, p.x_bs = c.x.bs, p.x_cs = c.x.cs;
         p.h_wl16 = hc.wp_l16, p.h_b = hc.bias, p.h_nchunks = hc.nchunks;
+        p.h_rows = hc.bias_rs ? c.spk : nullptr, p.h_rs = hc.bias_rs;
     } else {
         p.x = c.x.p, p.x_bs = c.x.bs, p.x_cs = c.x.cs;
     }

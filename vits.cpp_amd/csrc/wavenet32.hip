@@ -37,6 +37,8 @@ struct WaveNet32Params {
     int o_cs;
     const float *w_in, *b_in;  // gated conv: packed EPI_GATE fragments (tile 2i = tanh rows of channels 32i.., 2i+1 = sigmoid rows)
     const float *w_rs, *b_rs;  // 1x1 res/skip conv: packed EPI_STD fragments, rs_rows = 2H (H on the last layer)
+    const int* bias_rows;      // multi-speaker calls: effective-bias table row per utterance for b_in (PackedConv::bias_rs), or nullptr
+    int64_t bias_rs;
     int rs_rows;
     const int* lens;
     int tmax;
@@ -94,11 +96,12 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
     }
     // biases of this lane's rows (accumulator register r <-> channel 32*wid + 8*(r/4) + 4*krow + r%4)
     float bt[16], bs[16];
+    const float* const b_in = p.bias_rows ? p.b_in + p.bias_rs * p.bias_rows[b] : p.b_in;  // multi-speaker calls: this utterance's bias row
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int ch = gw * 32 + (r >> 2) * 8 + krow * 4 + (r & 3);
-        bt[r] = p.b_in[ch];
-        bs[r] = p.b_in[H + ch];
+        bt[r] = b_in[ch];
+        bs[r] = b_in[H + ch];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -332,11 +335,12 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
         }
     }
     float bt[16], bs[16];
+    const float* const b_in = p.bias_rows ? p.b_in + p.bias_rs * p.bias_rows[b] : p.b_in;  // multi-speaker calls: this utterance's bias row
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int ch = gw * 32 + (r >> 2) * 8 + krow * 4 + (r & 3);
-        bt[r] = p.b_in[ch];
-        bs[r] = p.b_in[H + ch];
+        bt[r] = b_in[ch];
+        bs[r] = b_in[H + ch];
     }
     __syncthreads();
     WN_STAMP(1);
@@ -504,6 +508,8 @@ struct FlowCouple16Params {
     const float* b_pre;
     const uint16_t* w_in[4];
     const float* b_in[4];
+    const int* bias_rows;  // multi-speaker calls: effective-bias table row per utterance for b_in[l] (one row stride for all four), or nullptr
+    int64_t bias_rs;
     const uint16_t* w_rs[4];
     const float* b_rs[4];
     const uint16_t* w_post;
@@ -573,10 +579,11 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
             const int gg = tid / (2 * P), j = tid - gg * (2 * P);
             xs[gg * XS + (j < P ? j : BM + j)] = wn_int4v{0, 0, 0, 0};
         }
+        const int64_t spk_off = p.bias_rows ? p.bias_rs * p.bias_rows[b] : 0;  // multi-speaker calls: this utterance's bias row
         for (int i2 = tid; i2 < LB_N; i2 += NTH) {
             float bv;
             if (i2 < LB_IN) bv = p.b_pre[i2];
-            else if (i2 < LB_RS) bv = p.b_in[(i2 - LB_IN) / (2 * H)][(i2 - LB_IN) % (2 * H)];
+            else if (i2 < LB_RS) bv = p.b_in[(i2 - LB_IN) / (2 * H)][spk_off + (i2 - LB_IN) % (2 * H)];
             else if (i2 < LB_POST) {
                 const int l = (i2 - LB_RS) / (2 * H), r = (i2 - LB_RS) % (2 * H);
                 bv = (l + 1 < NL || r < H) ? p.b_rs[l][r] : 0.f;  // (the last layer's 1x1 conv has H rows)
@@ -818,6 +825,8 @@ hipError_t launch_wavenet32(const PackedConv& in, const PackedConv& rs, const Wa
     p.o_cs = c.outputs.cs;
     p.w_in = in.wp;
     p.b_in = in.bias;
+    p.bias_rows = in.bias_rs ? c.spk : nullptr;
+    p.bias_rs = in.bias_rs;
     p.w_rs = rs.wp;
     p.b_rs = rs.bias;
     p.rs_rows = rs.cout;
@@ -853,6 +862,8 @@ hipError_t launch_wavenet16(const PackedConv& in, const PackedConv& rs, const Wa
     p.f.o_cs = c.outputs.cs;
     p.f.w_in = nullptr;
     p.f.b_in = in.bias;
+    p.f.bias_rows = in.bias_rs ? c.spk : nullptr;
+    p.f.bias_rs = in.bias_rs;
     p.f.w_rs = nullptr;
     p.f.b_rs = rs.bias;
     p.f.rs_rows = rs.cout;
@@ -896,7 +907,10 @@ hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, con
     p.x1_cs = c.x1.cs;
     p.w_pre = pre.wp16;
     p.b_pre = pre.bias;
+    p.bias_rows = in[0].bias_rs ? c.spk : nullptr;
+    p.bias_rs = in[0].bias_rs;
     for (int l = 0; l < 4; ++l) {
+        if (in[l].bias_rs != in[0].bias_rs) return hipErrorInvalidValue;  // (one table: every layer has the same row stride)
         p.w_in[l] = in[l].wp16;
         p.b_in[l] = in[l].bias;
         p.w_rs[l] = rs[l].wp16;
