@@ -225,6 +225,30 @@ VITS_API vits_result vits_model_process_ids(vits_model* model, const int32_t* id
 VITS_API int vits_model_process_batch(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch,
                                       int32_t id_stride, const vits_process_opts* opts, vits_batch_result* out);
 VITS_API void vits_free_batch_result(vits_batch_result* r);
+
+/* ---- voice conversion (VITS SynthesizerTrn.voice_conversion) -------------------------------------------------------------
+ * Speech of speaker A in, the same speech in speaker B's voice out. Per utterance b, with PCM y_b of pcm_lengths[b] = N_b samples at
+ * the model's sampling rate:
+ *   spec   = |STFT(y_b)| (periodic Hann, n_fft = 2 (spectrogram_bins - 1), hop = product of the upsample rates, reflection pad of
+ *            (n_fft - hop) / 2 at the utterance's own ends, center = False, sqrt(re^2 + im^2 + 1e-6)): L_b = floor(N_b / hop) frames
+ *   z_q    = posterior_encoder(spec, g_src): mean + eps * exp(log_std), eps the [F][L_b] draw prior sampling makes (same noise kinds)
+ *   z_p    = flow(z_q, g_src) forward;  z = flow(z_p, g_tgt) reverse;  PCM = decoder(z, g_tgt), as in vits_model_process_batch
+ * src_speakers / tgt_speakers: host [B], -1 = no conditioning (a single-speaker model takes -1 only). src = tgt resynthesises.
+ * Options: mode, the noise fields, collect_taps, out_device(_stride), skip_host_copy, vocoder_chunk_frames and on_chunk mean what they
+ * mean for vits_model_process_batch; fixed_duration, frames_only, async and speaker_ids are refused. vits_model_set_ggml_tables affects
+ * stage one only, which a conversion never runs: it has no effect here. out: frames[b] = L_b, lengths / stride / data as in TTS.
+ * Taps (collect_taps): "spec" [bins][L], "post_mean" / "post_logstd" / "z_q" [F][L], and "noise_prior" (eps), "z_p" (the forward
+ * flow's output), "z_flow", "pre_tanh", "waveform".
+ * vits_model_prepare_conversion builds what a conversion needs on the device (posterior encoder, its speaker terms, the forward-flow
+ * packs); the first conversion runs it implicitly. A handle that never converts keeps its TTS memory and weight_bytes. Returns 0,
+ * or -1 + message (no posterior encoder in the file, a tensor of the wrong shape). */
+VITS_API int vits_model_prepare_conversion(vits_model* model);
+VITS_API int vits_model_convert_batch(vits_model* model, const float* pcm, const int64_t* pcm_lengths, int32_t batch, int64_t pcm_stride,
+                                      const int32_t* src_speakers, const int32_t* tgt_speakers, const vits_process_opts* opts,
+                                      vits_batch_result* out);
+/* One utterance; the model's default mode and the reference noise stream, like vits_model_process. */
+VITS_API vits_result vits_model_convert(vits_model* model, const float* pcm, size_t n, int32_t src_speaker, int32_t tgt_speaker);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -273,6 +297,8 @@ VITS_API int64_t vits_model_get_tap(vits_model* model, const char* name, int32_t
 #define VITS_SYNTH_BF16 0x100 /* OR-ed in: store conv weights as bf16 (tensor type tag 2, an extension of the format) */
 #define VITS_SYNTH_SPEAKERS 0x200 /* OR-ed in: a multi-speaker model (TINY: 4 speakers, embedding 8; FULL: 109 speakers, embedding 256): the
                                      tensors of the model without the flag, unchanged, then embed_speaker and the three kinds of cond layers */
+#define VITS_SYNTH_POSTERIOR 0x400 /* OR-ed in: append posterior_encoder.* (transformers names and shapes; FULL: 513 bins, 16 WaveNet layers;
+                                      TINY: 9 bins, 2 layers) behind every other tensor, for voice conversion */
 VITS_API int vits_synth_model_bytes(uint64_t seed, int32_t arch, char** bytes, size_t* size);
 VITS_API void vits_free_bytes(char* bytes);
 /* Parse a model file and write it back (host only): byte-exact round trip of the reference's format

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("VITS_HIP_LIB", os.path.join(_HERE, "csrc", "libvits_h
 
 MODE_DEFAULT, MODE_REFERENCE, MODE_HF = -1, 0, 1
 NOISE_REFERENCE, NOISE_COUNTER, NOISE_EXPLICIT = 0, 1, 2
-SYNTH_FULL, SYNTH_TINY, SYNTH_BF16, SYNTH_SPEAKERS = 0, 1, 0x100, 0x200
+SYNTH_FULL, SYNTH_TINY, SYNTH_BF16, SYNTH_SPEAKERS, SYNTH_POSTERIOR = 0, 1, 0x100, 0x200, 0x400
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_arith_scope", "vits_model_get_arith_scope", "vits_model_submit_batch", "vits_model_wait", "vits_model_pending",
     "vits_model_set_ggml_tables", "vits_model_get_ggml_tables",
     "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
+    "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -151,6 +152,12 @@ def lib():
     L.vits_model_get_speaker.argtypes = [vp]
     L.vits_model_num_speakers.restype = i32
     L.vits_model_num_speakers.argtypes = [vp]
+    L.vits_model_prepare_conversion.restype = i32
+    L.vits_model_prepare_conversion.argtypes = [vp]
+    L.vits_model_convert_batch.restype = i32
+    L.vits_model_convert_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, C.POINTER(ProcessOpts), C.POINTER(BatchResult)]
+    L.vits_model_convert.restype = VitsResult
+    L.vits_model_convert.argtypes = [vp, vp, C.c_size_t, i32, i32]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -454,6 +461,85 @@ class Model:
             return pcm, lengths, frames
         finally:
             lib().vits_free_batch_result(C.byref(res))
+
+    def prepare_conversion(self):
+        """vits_model_prepare_conversion: build the posterior encoder and the forward-flow weights now (the first conversion does it otherwise)"""
+        if lib().vits_model_prepare_conversion(self._h) != 0:
+            raise VitsError(last_error())
+
+    def convert_batch(self, pcm, lengths=None, src=-1, tgt=-1, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_prior=None,
+                      collect_taps=False, out_device=None, out_device_stride=0, skip_host_copy=False, vocoder_chunk_frames=0, on_chunk=None,
+                      noise_seed_offsets=None, keep_pcm=True, **refused):
+        """Voice conversion (vits_model_convert_batch). pcm: float32 [B, stride] (or one 1-D utterance) at the model's sampling rate; lengths:
+        valid samples per row (None = the whole row); src / tgt: the source and target speaker, one int for every utterance or one per
+        utterance (-1 = none). Returns (list of per-utterance PCM arrays or None, lengths, frames) like process_batch. Keyword arguments
+        that conversion refuses (fixed_duration, frames_only, async_, speaker_ids) are passed on, so that the library says why."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        B, stride = pcm.shape
+        lens = np.full(B, stride, np.int64) if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64).ravel()
+        if lens.size != B:
+            raise ValueError("lengths needs one entry per utterance")
+        sp = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,))) for v in (src, tgt)]
+        o = ProcessOpts()
+        o.struct_size = C.sizeof(ProcessOpts)
+        o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
+        npr = _f32(noise_prior)
+        o.noise_prior = _ptr(npr)
+        o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
+        o.collect_taps = int(collect_taps)
+        o.out_device = out_device
+        o.out_device_stride = out_device_stride
+        o.skip_host_copy = int(skip_host_copy)
+        o.vocoder_chunk_frames = int(vocoder_chunk_frames)
+        o.fixed_duration = int(refused.pop("fixed_duration", 0))
+        o.frames_only = int(refused.pop("frames_only", False))
+        o.async_ = int(refused.pop("async_", False))
+        spk = refused.pop("speaker_ids", None)
+        if refused:
+            raise TypeError("unknown arguments: %s" % sorted(refused))
+        spk = None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()
+        o.speaker_ids = _ptr(spk)
+        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
+        if nso is not None and nso.size != B:
+            raise ValueError("noise_seed_offsets needs one entry per utterance")
+        o.noise_seed_offsets = _ptr(nso)
+        cb_error = []
+        if on_chunk is not None:
+            def _cb(_user, utt, offset, p, n):
+                try:
+                    return 1 if on_chunk(int(utt), int(offset), np.ctypeslib.as_array(p, shape=(n,)).copy()) else 0
+                except BaseException as e:  # never let an exception unwind through the C frames
+                    cb_error.append(e)
+                    return 1
+            o.on_chunk = ChunkCallback(_cb)
+        res = BatchResult()
+        if lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o), C.byref(res)) != 0:
+            if cb_error:
+                raise cb_error[0]
+            raise VitsError(last_error())
+        try:
+            lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()
+            frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
+            out = None
+            if res.data and keep_pcm:
+                full = np.ctypeslib.as_array(res.data, shape=(B, res.stride))
+                out = [full[b, : lengths[b]].copy() for b in range(B)]
+            return out, lengths, frames
+        finally:
+            lib().vits_free_batch_result(C.byref(res))
+
+    def convert(self, pcm, src=-1, tgt=-1):
+        """vits_model_convert: one utterance, the model's default mode and the reference noise stream (like process)"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
+        r = lib().vits_model_convert(self._h, _ptr(pcm), pcm.size, int(src), int(tgt))
+        if not r.data:
+            raise VitsError(last_error())
+        try:
+            return np.ctypeslib.as_array(r.data, shape=(r.size,)).copy()
+        finally:
+            lib().vits_free_result(r)
 
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
                      skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None):

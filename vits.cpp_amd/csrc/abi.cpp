@@ -276,6 +276,80 @@ VITS_API int vits_model_process_batch(vits_model* model, const int32_t* ids, con
     VITS_CATCH(-1)
 }
 
+VITS_API int vits_model_prepare_conversion(vits_model* model) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    std::string err;
+    const int rc = model->eng.prepare_conversion(err);
+    if (rc != 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_model_convert_batch(vits_model* model, const float* pcm, const int64_t* pcm_lengths, int32_t batch, int64_t pcm_stride,
+                                      const int32_t* src_speakers, const int32_t* tgt_speakers, const vits_process_opts* opts, vits_batch_result* out) {
+    VITS_TRY
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!model || !pcm || !pcm_lengths) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    vits_process_opts o;
+    std::memset(&o, 0, sizeof(o));
+    o.mode = VITS_MODE_DEFAULT;
+    o.noise_kind = VITS_NOISE_COUNTER;
+    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
+    std::string err;
+    int rc;
+    try {
+        rc = model->eng.convert_batch(pcm, pcm_lengths, batch, pcm_stride, src_speakers, tgt_speakers, o, out, err);
+    } catch (...) {
+        if (out) vits_free_batch_result(out);
+        throw;
+    }
+    if (rc != 0) {
+        set_err(err);
+        if (out) vits_free_batch_result(out);
+    }
+    return rc;
+    VITS_CATCH(-1)
+}
+
+VITS_API vits_result vits_model_convert(vits_model* model, const float* pcm, size_t n, int32_t src_speaker, int32_t tgt_speaker) {
+    vits_result r{nullptr, 0};
+    VITS_TRY
+    if (!model || !pcm || n == 0) {
+        set_err(n == 0 ? "empty input (no samples)" : "null argument");
+        return r;
+    }
+    VITS_ENTER(model, r)
+    vits_process_opts o;
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.mode = VITS_MODE_DEFAULT;
+    o.noise_kind = VITS_NOISE_REFERENCE;
+    vits_batch_result br;
+    std::memset(&br, 0, sizeof(br));
+    std::string err;
+    const int64_t len = (int64_t)n;
+    if (model->eng.convert_batch(pcm, &len, 1, len, &src_speaker, &tgt_speaker, o, &br, err) != 0) {
+        set_err(err);
+        vits_free_batch_result(&br);
+        return r;
+    }
+    r.size = (size_t)br.lengths[0];
+    r.data = br.data;  // (one utterance: its row is the result)
+    br.data = nullptr;
+    vits_free_batch_result(&br);
+    return r;
+    VITS_CATCH(r)
+}
+
 VITS_API int vits_model_submit_batch(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch, int32_t id_stride,
                                      const vits_process_opts* opts) {
     VITS_TRY

@@ -426,7 +426,6 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         c.Lmax = std::max(c.Lmax, frames[b]);
         c.sum_frames += frames[b];
     }
-    const int Lmax = c.Lmax;
     c.slen.assign(n_up + 1, std::vector<int>(B));
     c.smax.assign(n_up + 1, 0);
     for (int i = 0; i <= n_up; ++i)
@@ -459,6 +458,16 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         return 0;
     }
 
+    return run_stage_two(c, out, pend, want_async);
+}
+
+// ---- stage two from the known frame counts on: vocoder windows, arena, latent (prior sampling, or the conversion front end), flow, vocoder,
+// results. Shared by process_impl and convert_batch.
+int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const int B = c.B, n_up = c.n_up, Lmax = c.Lmax;
+    const std::vector<int>& frames = c.frames;
     // ---- vocoder windows (long-form / streaming, vits.h vocoder_chunk_frames) ------------------------------------
     // Window w owns frames [f0, f1) and computes frames [lo, hi) = the owned range widened by the vocoder's receptive
     // field (halo_frames_): every sample it emits sees exactly the inputs it sees in a whole-utterance run, in the same
@@ -480,7 +489,12 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     const int M = c.M = c.smul[n_up];  // samples per frame
 
     if (layout_stage_two(c)) return -1;
-    if (run_prior_sampling(c)) return -1;
+    if (c.vc) {
+        // voice conversion (engine_convert.cpp): spectrogram, posterior encoder and forward flow with the source speaker give z_p; the reverse
+        // flow and the vocoder below then run with the target speaker
+        if (run_conversion_front(c)) return -1;
+        c.spk = c.vc->spk_tgt;
+    } else if (run_prior_sampling(c)) return -1;
     if (run_flow(c)) return -1;
 
     // ---- HiFiGAN (vits.cpp:583-644), window by window ---------------------------------------------------------------

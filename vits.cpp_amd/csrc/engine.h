@@ -192,6 +192,11 @@ class Engine {
     // takes this flag around every entry point that touches the engine; a second thread gets "model busy" instead of a race.
     std::atomic<bool> busy{false};
     int set_arith(int arith, std::string& err);  // VITS_ARITH_*: packs the 16-bit weight fragments on first use
+    // voice conversion (engine_convert.cpp, include/vits.h vits_model_convert_batch): prepare_conversion builds the posterior encoder, its speaker
+    // terms and the forward-flow packs on the device (once; a handle that never converts never pays for them)
+    int prepare_conversion(std::string& err);
+    int convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
+                      vits_batch_result* out, std::string& err);
     // speaker conditioning (multi-speaker models): the speaker of utterances the call does not name (vits_process_opts::speaker_ids == NULL,
     // vits_model_process / _ids); -1 = none
     int speaker = -1;
@@ -229,6 +234,20 @@ class Engine {
     float *dp_translate_ = nullptr, *dp_logscale_ = nullptr;
     std::vector<DpFlowW> dp_flows_;  // index f-1 for flows.f, f = 1..dp_flows
     std::vector<FlowLayerW> flow_;
+    // voice conversion (engine_convert.cpp): host copies of what prepare_conversion packs (posterior_encoder.*, every flow.flows.*.conv_post, embed_speaker),
+    // kept at load; then the packed posterior encoder, the forward flow's conv_post (x1 += mean: not negated), the posterior's effective-bias table and
+    // the STFT tables
+    std::vector<TensorEntry> vc_src_;
+    bool vc_ready_ = false;
+    struct PosteriorW {
+        PackedConv pre, proj;
+        std::vector<PackedConv> in_layers, res_skip;
+    } post_;
+    std::vector<PackedConv> flow_fwd_post_;
+    float* post_spk_table_ = nullptr;
+    float* stft_tw_ = nullptr;  // [n_fft / 2] complex
+    float* stft_win_ = nullptr;
+    int n_fft_ = 0, hop_ = 0, stft_pad_ = 0;
     PackedConv dec_pre_;
     std::vector<UpStageW> ups_;
     float* dec_post_w_ = nullptr;
@@ -369,7 +388,12 @@ class Engine {
     int run_duration_predictor(Call& c);
     int layout_stage_two(Call& c);
     int run_prior_sampling(Call& c);
-    int run_flow(Call& c);
+    int run_flow(Call& c) { return run_coupling(c, false); }
+    int run_coupling(Call& c, bool forward);  // the residual coupling flow: reverse (TTS), or forward (voice conversion)
+    int run_conversion_front(Call& c);        // spectrogram -> posterior encoder -> forward flow (engine_convert.cpp)
+    int run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async);
+    // a tap of a tensor held with its channels reversed (the flow's physical layout for an odd number of coupling layers)
+    void snapshot_flipped(const char* name, TensorRef t, int channels, int stride, int batch, const std::vector<int>& lens);
     int run_vocoder_window32(Call& c, WinCtx& w);
     int run_vocoder_window16(Call& c, WinCtx& w);
 };

@@ -1,0 +1,440 @@
+// engine_convert.cpp — voice conversion (VITS SynthesizerTrn.voice_conversion; include/vits.h vits_model_convert_batch): PCM of a source
+// speaker -> linear spectrogram (spectrogram.hip) -> posterior encoder with the source speaker (transformers VitsPosteriorEncoder: conv_pre,
+// WaveNet, conv_proj, sample) -> coupling flow forward with the source speaker = z_p; from there the text-to-speech tail: the flow in reverse
+// and the vocoder, both with the target speaker (engine.cpp run_stage_two).
+#include "engine_internal.h"
+
+namespace vits {
+
+// ---- weights: built on first use, from the host copies load() kept -------------------------------------------------------------
+int Engine::prepare_conversion(std::string& err) {
+    if (vc_ready_) return 0;
+    const int H = hp.hidden, F = hp.flow_size, nl = hp.post_wn_layers, bins = hp.spec_bins;
+    ModelFile f;
+    f.tensors = vc_src_;
+    if (!f.find("posterior_encoder.conv_pre.weight")) {
+        err = "model file has no posterior encoder (posterior_encoder.* tensors): voice conversion needs them";
+        return -1;
+    }
+    // the STFT of spectrogram_torch: n_fft = 2 (bins - 1), hop = the vocoder's samples per frame, reflection pad (n_fft - hop) / 2
+    int hop = 1;
+    for (int r : hp.up_rates) hop *= r;
+    const int n_fft = 2 * (bins - 1);
+    if (n_fft < 16 || n_fft > 2048 || (n_fft & (n_fft - 1))) {
+        err = "spectrogram_bins = " + std::to_string(bins) + " gives n_fft = " + std::to_string(n_fft) + ": the spectrogram kernel needs a power of two in [16, 2048]";
+        return -1;
+    }
+    if (hop > n_fft || ((n_fft - hop) & 1)) {
+        err = "hop " + std::to_string(hop) + " (product of the upsample rates) does not fit n_fft " + std::to_string(n_fft) + ": (n_fft - hop) / 2 must be a whole pad";
+        return -1;
+    }
+    if (nl < 1) {
+        err = "posterior_encoder_num_wavenet_layers must be at least 1";
+        return -1;
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    const size_t first_pack = packs_.size();
+    // (vectors sized before anything is packed: packs_ keeps pointers to their entries)
+    post_.in_layers.assign(nl, PackedConv());
+    post_.res_skip.assign(nl, PackedConv());
+    flow_fwd_post_.assign(hp.n_flows, PackedConv());
+    const std::string b = "posterior_encoder.";
+    if (!pack(f, b + "conv_pre.weight", b + "conv_pre.bias", EPI_STD, {H, bins, 1}, post_.pre, err)) return -1;
+    for (int l = 0; l < nl; ++l) {
+        const std::string sl = std::to_string(l);
+        if (!pack(f, b + "wavenet.in_layers." + sl + ".weight", b + "wavenet.in_layers." + sl + ".bias", EPI_GATE, {2 * H, H, hp.wn_k}, post_.in_layers[l], err)) return -1;
+        if (!pack(f, b + "wavenet.res_skip_layers." + sl + ".weight", b + "wavenet.res_skip_layers." + sl + ".bias", EPI_STD, {l + 1 < nl ? 2 * H : H, H, 1},
+                  post_.res_skip[l], err))
+            return -1;
+    }
+    if (!pack(f, b + "conv_proj.weight", b + "conv_proj.bias", EPI_STD, {2 * F, H, 1}, post_.proj, err)) return -1;
+    // the forward flow's conv_post: x1 += mean — the reverse flow's packs without the negation, same output-channel reversal
+    for (int i = 0; i < hp.n_flows; ++i) {
+        const std::string fb = "flow.flows." + std::to_string(i) + ".";
+        const bool flipped = ((hp.n_flows - i) % 2) == 1;
+        if (!pack(f, fb + "conv_post.weight", fb + "conv_post.bias", EPI_STD, {F / 2, H, 1}, flow_fwd_post_[i], err, 0, flipped ? 4 : 0)) return -1;
+    }
+    // speaker terms of the posterior's WaveNet: its own effective-bias table (row 0 = speaker -1 = the plain biases), built like load_speakers' table
+    if (hp.num_speakers > 1) {
+        const int E = hp.speaker_embedding_size, N = hp.num_speakers;
+        const TensorEntry *te = f.find("embed_speaker.weight"), *tw = f.find(b + "wavenet.cond_layer.weight"), *tb = f.find(b + "wavenet.cond_layer.bias");
+        if (!te || !tw || !tb) {
+            err = std::string("[ERROR] tensor not found: ") + (!te ? "embed_speaker.weight" : !tw ? "posterior_encoder.wavenet.cond_layer.weight" : "posterior_encoder.wavenet.cond_layer.bias");
+            return -1;
+        }
+        if (te->count() != (int64_t)E * N || tw->count() != (int64_t)2 * H * nl * E || tb->count() != (int64_t)2 * H * nl || te->dtype > DT_BF16 || tw->dtype > DT_BF16 ||
+            tb->dtype > DT_BF16) {
+            err = "tensor 'posterior_encoder.wavenet.cond_layer' must be a [" + std::to_string(2 * H * nl) + ", " + std::to_string(E) + ", 1] conv with a bias";
+            return -1;
+        }
+        const int64_t rs = (int64_t)nl * 2 * H;  // segments of 2H floats: multiples of four (float4 bias loads)
+        const size_t table_floats = (size_t)(N + 1) * rs;
+        std::vector<void*> tmp;
+        auto dev = [&](const std::vector<float>& v) -> float* {
+            float* d = nullptr;
+            if (hipMalloc((void**)&d, std::max<size_t>(v.size(), 1) * sizeof(float)) != hipSuccess) return nullptr;
+            tmp.push_back(d);
+            if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return d;
+        };
+        bool ok = hipMalloc((void**)&post_spk_table_, table_floats * sizeof(float)) == hipSuccess;
+        if (ok) {
+            owned_.push_back(post_spk_table_);
+            weight_bytes += (int64_t)table_floats * 4;
+        }
+        const float* d_emb = ok ? dev(te->to_f32()) : nullptr;
+        const float* d_w = ok ? dev(tw->to_f32()) : nullptr;
+        const float* d_b = ok ? dev(tb->to_f32()) : nullptr;
+        ok = ok && d_emb && d_w && d_b;
+        for (int l = 0; l < nl && ok; ++l)
+            ok = launch_speaker_bias(post_.in_layers[l].bias, d_w + (int64_t)2 * H * l * E, d_b + 2 * H * l, d_emb, 2 * H, E, N, post_spk_table_ + (int64_t)2 * H * l, rs,
+                                     stream) == hipSuccess;
+        ok = ok && hipStreamSynchronize(stream) == hipSuccess;
+        for (void* p : tmp) hipFree(p);
+        if (!ok) {
+            err = "could not build the posterior encoder's speaker bias table on the device";
+            return -1;
+        }
+        for (int l = 0; l < nl; ++l) {
+            post_.in_layers[l].bias = post_spk_table_ + (int64_t)2 * H * l;
+            post_.in_layers[l].bias_rs = rs;
+        }
+    }
+    // STFT tables, in double, rounded once to fp32: twiddles exp(-2 pi i m / n) and the periodic Hann window (torch.hann_window(n))
+    {
+        std::vector<float> tw((size_t)n_fft), win((size_t)n_fft);
+        const double pi = 3.14159265358979323846;
+        for (int m = 0; m < n_fft / 2; ++m) {
+            tw[2 * m] = (float)std::cos(2.0 * pi * m / n_fft);
+            tw[2 * m + 1] = (float)-std::sin(2.0 * pi * m / n_fft);
+        }
+        for (int m = 0; m < n_fft; ++m) win[m] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * m / n_fft));
+        if (!(stft_tw_ = upload(tw)) || !(stft_win_ = upload(win))) {
+            err = "hipMalloc failed for the STFT tables";
+            return -1;
+        }
+    }
+    n_fft_ = n_fft;
+    hop_ = hop;
+    stft_pad_ = (n_fft - hop) / 2;
+    // a handle already in a 16-bit arithmetic: the new convs get their fragments now (set_arith packs only on a change of mode)
+    if (arith == VITS_ARITH_F16 || arith == VITS_ARITH_BF16) {
+        for (size_t i = first_pack; i < packs_.size(); ++i) {
+            PackSrc& ps = packs_[i];
+            const std::vector<float> w = ps.widen();
+            const std::vector<uint16_t> packed = pack_conv_weights16(w.data(), ps.cout, ps.cin, ps.k, ps.epi, ps.ct_stride, arith);
+            uint16_t* d = nullptr;
+            HIP_OK(hipMalloc((void**)&d, packed.size() * sizeof(uint16_t)));
+            ps.pc->wp16 = d;
+            ps.pc->bytes16 = (int64_t)packed.size() * 2;
+            HIP_OK(hipMemcpy(d, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
+    }
+    lat16_ready_ = false;  // (the latency kernels' copy of the new layers is made by ensure_lat16 at the next small call)
+    HIP_OK(hipDeviceSynchronize());
+    vc_ready_ = true;
+    return 0;
+}
+
+// ---- one conversion call -------------------------------------------------------------------------------------------------------
+int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
+                          vits_batch_result* out, std::string& err) {
+    if (pending()) {
+        err = "batches in flight: call vits_model_wait for every submitted batch first";
+        return -1;
+    }
+    if (B <= 0 || !pcm || !pcm_lens || pcm_stride <= 0) {
+        err = B <= 0 ? "empty batch" : "null PCM, null lengths or pcm_stride <= 0";
+        return -1;
+    }
+    if (o.fixed_duration > 0 || o.frames_only || o.async) {
+        err = std::string("voice conversion does not take ") + (o.fixed_duration > 0 ? "fixed_duration" : o.frames_only ? "frames_only" : "async") +
+              " (the frame counts come from the input PCM; the call is synchronous)";
+        return -1;
+    }
+    if (o.speaker_ids) {
+        err = "voice conversion takes its speakers from src_speakers and tgt_speakers, not from opts.speaker_ids";
+        return -1;
+    }
+    if (o.on_chunk && o.skip_host_copy) {
+        err = "on_chunk needs a host copy (skip_host_copy = 0)";
+        return -1;
+    }
+    for (int b = 0; b < B; ++b)
+        for (int side = 0; side < 2; ++side) {
+            const int32_t* arr = side ? tgt : src;
+            const int s = arr ? arr[b] : -1;
+            if (s == -1) continue;
+            const std::string who = std::string(side ? "tgt_speakers[" : "src_speakers[") + std::to_string(b) + "] = " + std::to_string(s) + " (" +
+                                    (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
+            if (hp.num_speakers <= 1) {
+                err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
+                return -1;
+            }
+            if (s < -1 || s >= hp.num_speakers) {
+                err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+                return -1;
+            }
+        }
+    if (prepare_conversion(err)) return -1;
+    const int hop = hop_, pad = stft_pad_, min_n = std::max(hop, pad + 1);
+    int64_t nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = pcm_lens[b];
+        if (n > pcm_stride) {
+            err = "pcm_lengths[" + std::to_string(b) + "] = " + std::to_string(n) + " exceeds pcm_stride " + std::to_string(pcm_stride);
+            return -1;
+        }
+        if (n < min_n) {
+            err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples: at least " + std::to_string(min_n) +
+                  " are needed (one hop, and more than the reflection pad of " + std::to_string(pad) + ")";
+            return -1;
+        }
+        if (n > ((int64_t)1 << 30)) {
+            err = "utterance " + std::to_string(b) + " is longer than 2^30 samples";
+            return -1;
+        }
+        nmax = std::max(nmax, n);
+    }
+    a1_slot_ = 0;
+    Call c(o, err, nullptr, B, 0);
+    Call::Vc vc;
+    c.vc = &vc;
+    c.md = o.mode == VITS_MODE_DEFAULT ? mode : o.mode;
+    c.refmode = c.md == VITS_MODE_REFERENCE;
+    const int n_up = c.n_up = (int)ups_.size();
+    clear_taps();
+    tap_batch_ = B;
+    arith_now_ = arith_kernels();
+    // frame counts and vocoder stage lengths, all on the host (spectrogram_torch: floor(N / hop) frames)
+    std::vector<int>& frames = c.frames;
+    frames.resize(B);
+    for (int b = 0; b < B; ++b) {
+        frames[b] = (int)(pcm_lens[b] / hop);
+        c.Lmax = std::max(c.Lmax, frames[b]);
+        c.sum_frames += frames[b];
+    }
+    if (!lat16_ready_ && knobs.lat16_lazy_tokens > 0 && (int64_t)B * c.Lmax <= knobs.lat16_lazy_tokens && ensure_lat16(err)) return -1;
+    std::vector<int>& smul = c.smul;
+    std::vector<int>& sadd = c.sadd;
+    smul.assign(n_up + 1, 0);
+    sadd.assign(n_up + 1, 0);
+    smul[0] = 1;
+    for (int i = 0; i < n_up; ++i) {  // (as layout_stage_one)
+        const int s = ups_[i].stride, K = ups_[i].k;
+        const int crop = c.refmode ? 0 : (K - s) / 2;
+        smul[i + 1] = smul[i] * s;
+        sadd[i + 1] = sadd[i] * s + (K - s - 2 * crop);
+    }
+    c.slen.assign(n_up + 1, std::vector<int>(B));
+    c.smax.assign(n_up + 1, 0);
+    for (int i = 0; i <= n_up; ++i)
+        for (int b = 0; b < B; ++b) {
+            c.slen[i][b] = frames[b] * smul[i] + sadd[i];
+            c.smax[i] = std::max(c.smax[i], c.slen[i][b]);
+        }
+    // ---- the call's own arena (stage-one slot 0): header ints | PCM | spectrogram | posterior statistics ----------------------
+    const int ls = round_up(c.Lmax, 32), bins = hp.spec_bins, F = hp.flow_size;
+    const int64_t pstride = round_up((int)nmax, 64);
+    const size_t hdr_ints = (size_t)(n_up + 1) * B + 4 * (size_t)B;
+    auto layout = [&](Arena& a) {
+        c.s1.stage_lens = a.alloc<int>(hdr_ints);  // stage_lens [n_up + 1][B] | n_samples | seed_off | src rows | tgt rows
+        vc.nsamp = c.s1.stage_lens + (size_t)(n_up + 1) * B;
+        c.s1.seed_off = vc.nsamp + B;
+        vc.pcm = a.alloc<float>((size_t)B * pstride);
+        vc.spec = a.alloc<float>((size_t)B * bins * ls);
+        vc.stats = a.alloc<float>((size_t)B * 2 * F * ls);
+    };
+    {
+        Arena measure;
+        measure.cap = (size_t)1 << 60;
+        layout(measure);
+        const size_t need = measure.off + 4096;
+        measure.cap = 0;
+        if (need > a1().cap) HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(a1().reserve(need));
+        layout(a1());
+    }
+    vc.pcm_stride = pstride;
+    {
+        std::vector<int> hdr(hdr_ints, 0);
+        bool any_src = false, any_tgt = false;
+        for (int i = 0; i <= n_up; ++i)
+            for (int b = 0; b < B; ++b) hdr[(size_t)i * B + b] = c.slen[i][b];
+        for (int b = 0; b < B; ++b) {
+            int* h = hdr.data() + (size_t)(n_up + 1) * B;
+            h[b] = (int)pcm_lens[b];
+            h[B + b] = o.noise_seed_offsets ? o.noise_seed_offsets[b] : b;
+            const int s = src ? src[b] : -1, t = tgt ? tgt[b] : -1;
+            h[2 * B + b] = s + 1;
+            h[3 * B + b] = t + 1;
+            any_src = any_src || s >= 0;
+            any_tgt = any_tgt || t >= 0;
+        }
+        // (pageable sources: both copies are complete when hipMemcpy* returns to the host, so the caller's PCM and hdr may go)
+        HIP_OK(hipMemcpyAsync(c.s1.stage_lens, hdr.data(), sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpy2DAsync(vc.pcm, (size_t)pstride * 4, pcm, (size_t)pcm_stride * 4, (size_t)nmax * 4, (size_t)B, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        prof.fence();
+        vc.spk_src = any_src ? vc.nsamp + 2 * B : nullptr;
+        vc.spk_tgt = any_tgt ? vc.nsamp + 3 * B : nullptr;
+    }
+    c.s1.lens = c.s1.stage_lens;  // (frames per utterance = stage-0 lengths)
+    c.s1.frames = c.s1.stage_lens;
+    return run_stage_two(c, out, nullptr, false);
+}
+
+// ---- spectrogram -> posterior encoder -> forward flow: z_p in s2.zp ------------------------------------------------------------------------------
+int Engine::run_conversion_front(Call& c) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    Call::Vc& vc = *c.vc;
+    Call::S2& s2 = c.s2;
+    const int B = c.B, Lmax = c.Lmax, ls = c.ls, H = hp.hidden, F = hp.flow_size, bins = hp.spec_bins, nl = hp.post_wn_layers;
+    const std::vector<int>& frames = c.frames;
+    const int64_t sum_frames = c.sum_frames;
+    const int* ll = c.d_len_full[0];
+    auto TR = make_ref;
+    auto sub = sub_rows;
+    // spectrogram
+    c.rx.phase("vits.spectrogram");
+    TensorRef spec = TR(vc.spec, bins, ls);
+    {
+        SpectrogramCall sc;
+        sc.pcm = vc.pcm;
+        sc.pcm_stride = vc.pcm_stride;
+        sc.n_samples = vc.nsamp;
+        sc.frames = ll;
+        sc.tw = reinterpret_cast<const float2*>(stft_tw_);
+        sc.win = stft_win_;
+        sc.n_fft = n_fft_;
+        sc.hop = hop_;
+        sc.pad = stft_pad_;
+        sc.bins = bins;
+        sc.batch = B;
+        sc.tmax = Lmax;
+        sc.out = spec;
+        // algorithmic bytes: every sample once, every bin once
+        int64_t samples = 0;
+        for (int b = 0; b < B; ++b) samples += (int64_t)frames[b] * hop_ + 2 * stft_pad_;
+        int log2n = 0;
+        while ((1 << log2n) < n_fft_) ++log2n;
+        prof.begin("spectrogram", 5.0 * n_fft_ * log2n * (double)sum_frames, 4.0 * (double)samples + 4.0 * (double)bins * sum_frames, stream, true);
+        HIP_OK(launch_spectrogram(sc, stream));
+        prof.end(stream);
+    }
+    if (o.collect_taps) snapshot("spec", spec, bins, Lmax, B, frames);
+    // posterior encoder, conditioned on the source speaker
+    c.rx.phase("vits.posterior");
+    TensorRef hout = TR(s2.hout, 2 * H, ls), gate = TR(s2.gate, H, ls), hh = hout, stats = TR(vc.stats, 2 * F, ls);
+    const int* spk = vc.spk_src;
+    auto mk = [&](TensorRef xin, TensorRef yout) {
+        ConvCall k;
+        k.x = xin;
+        k.y = yout;
+        k.len_in = ll;
+        k.len_out = ll;
+        k.spk = spk;
+        k.batch = B;
+        k.t_in = k.t_out = Lmax;
+        k.sum_in = k.sum_out = sum_frames;
+        return k;
+    };
+    // conv_pre and conv_proj stay fp32 in every arithmetic mode (bins -> H from a spectrogram in the hundreds; the statistics feed exp())
+    const int arith_saved = arith_now_;
+    arith_now_ = VITS_ARITH_F32;
+    HIP_OK(conv("post_conv_pre", post_.pre, mk(spec, hh)));
+    arith_now_ = arith_saved;
+    prof.begin("fill_zero", 0, 0, stream);
+    HIP_OK(launch_fill_rows(sub(hout, H), H, 0.f, B, Lmax, stream));
+    prof.end(stream);
+    // the WaveNet: the flow's layer shape (engine_flow.cpp run_coupling), fused per layer where the kernels take it
+    bool fuse_wn = !knobs.no_wn_fuse && (ls & 3) == 0 && (int64_t)((Lmax + 31) / 32) * B >= 384 && (reinterpret_cast<uintptr_t>(hout.p) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(gate.p) & 15) == 0;
+    for (int l = 0, dl = 1; l < nl && fuse_wn; ++l, dl *= hp.wn_rate)
+        fuse_wn = (arith_now_ == VITS_ARITH_F32 ? wavenet32_supported(H, hp.wn_k, dl, post_.in_layers[l], post_.res_skip[l])
+                                                : wavenet16_supported(H, hp.wn_k, dl, post_.in_layers[l], post_.res_skip[l])) &&
+                  post_.res_skip[l].cout == (l + 1 < nl ? 2 * H : H);
+    if (fuse_wn) {
+        TensorRef hcur = hh;
+        for (int l = 0, dl = 1; l < nl; ++l, dl *= hp.wn_rate) {
+            WaveNet32Call w;
+            w.h = hcur;
+            w.h_out = hcur.p == gate.p ? hh : gate;
+            if (l + 1 == nl) w.h_out = TensorRef();
+            w.outputs = sub(hout, H);
+            w.lens = ll;
+            w.spk = spk;
+            w.batch = B;
+            w.tmax = Lmax;
+            w.hidden = H;
+            w.dil = dl;
+            if (prof.on) {
+                char full[160];
+                std::snprintf(full, sizeof(full), "post_wavenet_layer|k%d|d%d|%c%d|e1|c%dx%d", hp.wn_k, dl, arith_now_ == VITS_ARITH_F32 ? 'w' : 'W', H, H,
+                              post_.res_skip[l].cout);
+                prof.begin(full, 2.0 * ((double)2 * H * H * hp.wn_k + (double)post_.res_skip[l].cout * H) * (double)sum_frames,
+                           4.0 * (double)sum_frames * (H + 2.0 * post_.res_skip[l].cout) + (double)post_.in_layers[l].bytes + (double)post_.res_skip[l].bytes, stream, true);
+            }
+            if (arith_now_ == VITS_ARITH_F32) HIP_OK(launch_wavenet32(post_.in_layers[l], post_.res_skip[l], w, stream));
+            else HIP_OK(launch_wavenet16(post_.in_layers[l], post_.res_skip[l], w, arith_now_, stream));
+            prof.end(stream);
+            if (w.h_out.p) hcur = w.h_out;
+        }
+    } else {
+        for (int l = 0, dl = 1; l < nl; ++l, dl *= hp.wn_rate) {
+            ConvCall k = mk(hh, gate);
+            k.dil = dl;
+            k.pad_l = (hp.wn_k * dl - dl) / 2;
+            HIP_OK(conv("post_wavenet_gated_conv", post_.in_layers[l], k));
+            ConvCall r = l + 1 < nl ? mk(gate, hout) : mk(gate, sub(hout, H));  // rows [0,H): h += res; rows [H,2H): outputs += skip
+            r.res = l + 1 < nl ? hout : sub(hout, H);
+            HIP_OK(conv("post_conv1x1", post_.res_skip[l], r));
+        }
+    }
+    arith_now_ = VITS_ARITH_F32;
+    HIP_OK(conv("post_conv_proj", post_.proj, mk(sub(hout, H), stats)));
+    arith_now_ = arith_saved;
+    if (o.collect_taps) {
+        snapshot("post_mean", stats, F, Lmax, B, frames);
+        snapshot("post_logstd", sub(stats, F), F, Lmax, B, frames);
+    }
+    // eps: the [F][L] draw prior sampling would make (engine_flow.cpp run_prior_sampling), then z_q — in the forward flow's physical input layout
+    TensorRef zp = TR(s2.zp, F, ls), noise = TR(s2.noise, F, ls);
+    if (o.noise_kind != VITS_NOISE_COUNTER) {
+        std::vector<float> hn((size_t)B * F * ls, 0.f);
+        for (int b = 0; b < B; ++b) {
+            const int L = frames[b];
+            if (o.noise_kind == VITS_NOISE_EXPLICIT) {
+                if (!o.noise_prior) {
+                    err = "noise_prior missing";
+                    return -1;
+                }
+                for (int ch = 0; ch < F; ++ch)
+                    std::memcpy(&hn[((size_t)b * F + ch) * ls], o.noise_prior + ((size_t)b * F + ch) * o.noise_prior_stride, sizeof(float) * std::min<int64_t>(L, o.noise_prior_stride));
+            } else {
+                std::vector<float> tmpn((size_t)F * L);
+                reference_noise_fill(tmpn.data(), tmpn.size());
+                for (int ch = 0; ch < F; ++ch) std::memcpy(&hn[((size_t)b * F + ch) * ls], &tmpn[(size_t)ch * L], sizeof(float) * L);
+            }
+        }
+        HIP_OK(hipMemcpyAsync(s2.noise, hn.data(), sizeof(float) * hn.size(), hipMemcpyHostToDevice, stream));
+        prof.fence();
+        HIP_OK(hipStreamSynchronize(stream));  // hn goes out of scope
+        if (o.collect_taps) snapshot("noise_prior", noise, F, Lmax, B, frames);
+    }
+    const int nk = o.noise_kind == VITS_NOISE_COUNTER ? VITS_NOISE_COUNTER : VITS_NOISE_EXPLICIT;
+    prof.begin("posterior_sample", 0, 0, stream, true);
+    HIP_OK(launch_posterior_sample(stats, sub(stats, F), ll, noise, nk, o.noise_seed, c.s1.seed_off, zp, B, F, Lmax, hp.n_flows % 2, stream));
+    prof.end(stream);
+    if (o.collect_taps) {
+        // (the logical z_q: with an odd layer count zp holds it reversed)
+        if (hp.n_flows % 2) snapshot_flipped("z_q", zp, F, Lmax, B, frames);
+        else snapshot("z_q", zp, F, Lmax, B, frames);
+    }
+    // forward flow, source speaker
+    c.spk = vc.spk_src;
+    return run_coupling(c, true);
+}
+
+}  // namespace vits

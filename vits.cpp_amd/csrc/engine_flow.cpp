@@ -170,7 +170,10 @@ int Engine::run_prior_sampling(Call& c) {
 }
 
 // ---- residual coupling flow, reverse (vits.cpp:519-538,500-517,452-498) ------------------------------------
-int Engine::run_flow(Call& c) {
+// forward (voice conversion, transformers VitsResidualCouplingBlock.forward with reverse = False): layers 0 .. n-1, x1 += mean, through the
+// same kernels with the not-negated conv_post packs (flow_fwd_post_). Layer i sees the same channel-flip parity (n - i) in both directions,
+// so both read and write the one physical layout: the forward flow ends in the layout prior sampling writes z_p in.
+int Engine::run_coupling(Call& c, bool forward) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
     const int B = c.B, n_up = c.n_up;
@@ -184,7 +187,7 @@ int Engine::run_flow(Call& c) {
     const int ls = c.ls;
     const int64_t sum_frames = c.sum_frames;
     TensorRef zp = TR(s2.zp, F, ls);
-    c.rx.phase("vits.flow");
+    c.rx.phase(forward ? "vits.flow_forward" : "vits.flow");
     const int* ll = c.d_len_full[0];
     TensorRef hout = TR(s2.hout, 2 * H, ls), gate = TR(s2.gate, H, ls);
     TensorRef hh = hout;  // channels [0,H) = h, [H,2H) = skip accumulator "outputs" (vits.cpp:460)
@@ -207,9 +210,10 @@ int Engine::run_flow(Call& c) {
     // tail the other's blocks take the free CUs (4 x 320 blocks in ~5 rounds instead of 8). Same kernel, same operands per utterance: same bits.
     int chains = 1, chain_b0[3] = {0, B, B};
     bool all_fused = arith_now_ != VITS_ARITH_F32 && !knobs.no_flow_fuse;
+    auto post_of = [&](int i) -> const PackedConv& { return forward ? flow_fwd_post_[i] : flow_[i].post; };
     for (int i = 0; i < hp.n_flows && all_fused; ++i)
         all_fused = (int)flow_[i].in_layers.size() == hp.wn_layers && (int)flow_[i].res_skip.size() == hp.wn_layers &&
-                    flow_couple16_supported(H, F / 2, hp.wn_k, hp.wn_rate, hp.wn_layers, flow_[i].pre, flow_[i].in_layers.data(), flow_[i].res_skip.data(), flow_[i].post);
+                    flow_couple16_supported(H, F / 2, hp.wn_k, hp.wn_rate, hp.wn_layers, flow_[i].pre, flow_[i].in_layers.data(), flow_[i].res_skip.data(), post_of(i));
     if (all_fused && !prof.on && side_[0] && B >= 2 && knobs.flow_chains > 1) {
         int64_t blocks = 0;
         for (int b = 0; b < B; ++b) blocks += (frames[b] + 47) / 48;
@@ -228,8 +232,10 @@ int Engine::run_flow(Call& c) {
         HIP_OK(hipEventRecord(ev_fork_, stream));
         HIP_OK(hipStreamWaitEvent(side_[0], ev_fork_, 0));
     }
-    for (int i = hp.n_flows - 1; i > -1; --i) {
+    for (int step = 0; step < hp.n_flows; ++step) {
+        const int i = forward ? step : hp.n_flows - 1 - step;
         const FlowLayerW& Lw = flow_[i];
+        const PackedConv& post = post_of(i);
         const bool flipped = ((hp.n_flows - i) % 2) == 1;
         TensorRef x0 = sub(zp, flipped ? F / 2 : 0), x1 = sub(zp, flipped ? 0 : F / 2);
         // 16-bit modes: the whole coupling layer as ONE kernel (flow_couple16_kernel, wavenet32.hip; bit-identical to the launches below)
@@ -248,7 +254,7 @@ int Engine::run_flow(Call& c) {
                 for (int b = b0; b < b0 + nb; ++b) fc.tmax = std::max(fc.tmax, frames[b]);
                 fc.hidden = H;
                 fc.half = F / 2;
-                HIP_OK(launch_flow_couple16(Lw.pre, Lw.in_layers.data(), Lw.res_skip.data(), Lw.post, fc, arith_now_, ch == 0 ? stream : side_[0]));
+                HIP_OK(launch_flow_couple16(Lw.pre, Lw.in_layers.data(), Lw.res_skip.data(), post, fc, arith_now_, ch == 0 ? stream : side_[0]));
             }
             continue;
         }
@@ -265,14 +271,14 @@ int Engine::run_flow(Call& c) {
             if (prof.on) {
                 char full[160];
                 std::snprintf(full, sizeof(full), "flow_coupling_layer|k%d|d1|C%d|e1|c%dx%d", hp.wn_k, H, F / 2, F / 2);
-                double macs = (double)(F / 2) * H + (double)H * (F / 2), wbytes = (double)Lw.pre.bytes16 + (double)Lw.post.bytes16;
+                double macs = (double)(F / 2) * H + (double)H * (F / 2), wbytes = (double)Lw.pre.bytes16 + (double)post.bytes16;
                 for (int l = 0; l < hp.wn_layers; ++l) {
                     macs += (double)2 * H * H * hp.wn_k + (double)Lw.res_skip[l].cout * H;
                     wbytes += (double)Lw.in_layers[l].bytes16 + (double)Lw.res_skip[l].bytes16;
                 }
                 prof.begin(full, 2.0 * macs * (double)sum_frames, 4.0 * (double)sum_frames * (F / 2) * 3.0 + wbytes, stream, true);
             }
-            HIP_OK(launch_flow_couple16(Lw.pre, Lw.in_layers.data(), Lw.res_skip.data(), Lw.post, fc, arith_now_, stream));
+            HIP_OK(launch_flow_couple16(Lw.pre, Lw.in_layers.data(), Lw.res_skip.data(), post, fc, arith_now_, stream));
             prof.end(stream);
             continue;
         }
@@ -337,15 +343,19 @@ int Engine::run_flow(Call& c) {
             }
             dil *= hp.wn_rate;
         }
-        ConvCall pc = mk2(sub(hout, H), x1);  // x1 <- x1 - (W out + b): weights negated at load (vits.cpp:506,513)
+        ConvCall pc = mk2(sub(hout, H), x1);  // x1 <- x1 - (W out + b): weights negated at load (vits.cpp:506,513); forward: x1 + (W out + b)
         pc.res = x1;
-        HIP_OK(conv("flow_conv1x1", Lw.post, pc));
+        HIP_OK(conv("flow_conv1x1", post, pc));
     }
     if (chains > 1) {
         HIP_OK(hipEventRecord(ev_done_[0], side_[0]));
         HIP_OK(hipStreamWaitEvent(stream, ev_done_[0], 0));
     }
-    if (o.collect_taps) snapshot("z_flow", zp, F, Lmax, B, frames);
+    if (o.collect_taps) {
+        if (forward) snapshot("z_p", zp, F, Lmax, B, frames);
+        else if (hp.n_flows % 2) snapshot_flipped("z_flow", zp, F, Lmax, B, frames);  // (odd layer count: the logical channels are the physical ones reversed)
+        else snapshot("z_flow", zp, F, Lmax, B, frames);
+    }
     (void)n_up;
     (void)s1;
     return 0;

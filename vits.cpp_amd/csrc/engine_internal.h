@@ -111,6 +111,14 @@ struct Call {
     // speaker -1, so that such a call queues exactly the kernels (and reads exactly the biases) of a single-speaker model
     const int* spk = nullptr;
     RefNoiseAhead* ref_ahead = nullptr;  // batch 1, reference noise: the prior noise drawn while stage one runs (engine.cpp)
+    // voice conversion (engine_convert.cpp): the call's input and the two speaker row arrays; null for text-to-speech
+    struct Vc {
+        float *pcm = nullptr, *spec = nullptr, *stats = nullptr;
+        int* nsamp = nullptr;  // device [B]
+        int64_t pcm_stride = 0;
+        const int *spk_src = nullptr, *spk_tgt = nullptr;  // device [B] effective-bias rows, or null (every utterance -1)
+    };
+    Vc* vc = nullptr;
 
     // the one data-dependent shape (vits.cpp:1133)
     std::vector<int> frames;

@@ -166,7 +166,7 @@ static bool get_conv(const ModelFile& f, const std::string& wname, std::vector<f
     return true;
 }
 
-// transform: 0 none | 1 reverse input channels | 2 negate | 3 negate + reverse output channels
+// transform: 0 none | 1 reverse input channels | 2 negate | 3 negate + reverse output channels | 4 reverse output channels
 // want = {cout, cin, k} the hyper-parameters imply (-1: taken from the file)
 bool Engine::pack(const ModelFile& f, const std::string& wname, const std::string& bname, int epi, ConvShape want, PackedConv& out, std::string& err,
                   int ct_stride, int transform) {
@@ -205,12 +205,13 @@ bool Engine::pack(const ModelFile& f, const std::string& wname, const std::strin
             for (int ci = 0; ci < cin; ++ci)
                 for (int j = 0; j < k; ++j) w2[((size_t)co * cin + ci) * k + j] = w[((size_t)co * cin + (cin - 1 - ci)) * k + j];
         w.swap(w2);
-    } else if (transform == 2 || transform == 3) {
+    } else if (transform >= 2 && transform <= 4) {
         std::vector<float> w2(w.size()), b2(bias.size());
+        const float sg = transform == 4 ? 1.f : -1.f;
         for (int co = 0; co < cout; ++co) {
-            const int src = transform == 3 ? cout - 1 - co : co;
-            for (int e = 0; e < cin * k; ++e) w2[(size_t)co * cin * k + e] = -w[(size_t)src * cin * k + e];
-            if (!bias.empty()) b2[co] = -bias[src];
+            const int src = transform != 2 ? cout - 1 - co : co;
+            for (int e = 0; e < cin * k; ++e) w2[(size_t)co * cin * k + e] = sg * w[(size_t)src * cin * k + e];
+            if (!bias.empty()) b2[co] = sg * bias[src];
         }
         w.swap(w2);
         bias.swap(b2);
@@ -516,8 +517,8 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
                 return false;
         }
     }
-    // HiFiGAN
-    if (!pack(f, "decoder.conv_pre.weight", "decoder.conv_pre.bias", EPI_STD, {hp.up_init, F, -1}, dec_pre_, err)) return false;
+    // HiFiGAN. After an odd number of coupling layers the flow's output holds its channels reversed (the flips above): conv_pre reads them so.
+    if (!pack(f, "decoder.conv_pre.weight", "decoder.conv_pre.bias", EPI_STD, {hp.up_init, F, -1}, dec_pre_, err, 0, hp.n_flows % 2 ? 1 : 0)) return false;
     if (!(dec_pre_.kt & 1)) {
         err = "decoder.conv_pre needs an odd kernel size";
         return false;
@@ -600,6 +601,13 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
             exact_src_.push_back(t);
         }
         if (knobs.lat16_eager && ensure_lat16(err)) return false;
+        // voice conversion: what vits_model_prepare_conversion packs stays on the host until then (engine_convert.cpp); a file without a posterior
+        // encoder keeps nothing, and nothing here can fail the load
+        if (f.find("posterior_encoder.conv_pre.weight"))
+            for (const TensorEntry& t : f.tensors)
+                if (t.name.rfind("posterior_encoder.", 0) == 0 || t.name == "embed_speaker.weight" ||
+                    (t.name.rfind("flow.flows.", 0) == 0 && t.name.find(".conv_post.") != std::string::npos))
+                    vc_src_.push_back(t);
     }
     return true;
 }
@@ -652,6 +660,21 @@ void Engine::snapshot(const char* name, TensorRef t, int channels, int stride, i
     for (int b = 1; b < batch; ++b)
         hipMemcpy2DAsync(tp.dev + (size_t)b * channels * stride, (size_t)stride * 4, t.p + (size_t)b * t.bs, (size_t)t.cs * 4, (size_t)stride * 4, (size_t)channels,
                          hipMemcpyDeviceToDevice, stream);
+    taps_[name] = tp;
+}
+
+void Engine::snapshot_flipped(const char* name, TensorRef t, int channels, int stride, int batch, const std::vector<int>& lens) {
+    prof.fence();
+    Tap tp;
+    tp.channels = channels;
+    tp.stride = stride;
+    tp.lens = lens;
+    const size_t n = (size_t)batch * channels * stride;
+    if (hipMalloc((void**)&tp.dev, n * sizeof(float)) != hipSuccess) return;
+    for (int b = 0; b < batch; ++b)
+        for (int ch = 0; ch < channels; ++ch)
+            hipMemcpyAsync(tp.dev + ((size_t)b * channels + ch) * stride, t.p + (size_t)b * t.bs + (size_t)(channels - 1 - ch) * t.cs, (size_t)stride * 4,
+                           hipMemcpyDeviceToDevice, stream);
     taps_[name] = tp;
 }
 

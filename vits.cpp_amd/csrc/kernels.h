@@ -510,6 +510,24 @@ hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const flo
 hipError_t launch_rb_sum3_std(TensorRef y0, TensorRef y1, TensorRef y2, TensorRef out, int channels, const int* lens, int batch, int tmax, float scale, int scale_div, int post_act,
                               float post_slope, hipStream_t s);  // fp32 [b][c][t]: ((y0 + y1) [+ y2]) scaled [+ leaky_relu]: side-by-side resblocks of the fp32 path (small grids)
 hipError_t launch_fill_rows(TensorRef x, int channels, float v, int batch, int tmax, hipStream_t s);
+
+// ---- voice conversion front end (spectrogram.hip) -------------------------------------------------------------------------------
+// Linear magnitude spectrogram (VITS spectrogram_torch, center = False): frame t of utterance b covers samples [t hop - pad, t hop - pad + n_fft)
+// of its PCM, reflected at the utterance's own ends; out [b][bin][t] = sqrt(re^2 + im^2 + 1e-6) for t < frames[b], 0 for frames[b] <= t < tmax.
+struct SpectrogramCall {
+    const float* pcm = nullptr;  // device [batch][pcm_stride]
+    int64_t pcm_stride = 0;
+    const int* n_samples = nullptr;  // device [batch]: valid samples (pad < n_samples)
+    const int* frames = nullptr;     // device [batch]
+    const float2* tw = nullptr;      // device [n_fft / 2]: exp(-2 pi i m / n_fft), built in double on the host
+    const float* win = nullptr;      // device [n_fft]: periodic Hann
+    int n_fft = 0, hop = 0, pad = 0, bins = 0, batch = 0, tmax = 0;
+    TensorRef out;
+};
+hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s);
+// z_q = mean + eps * exp(log_std) over [0, frames[b]) (eps: the counter stream of prior sampling, or `noise`); flip: channel c -> row channels - 1 - c
+hipError_t launch_posterior_sample(TensorRef mean, TensorRef logstd, const int* frames, TensorRef noise, int noise_kind, uint64_t seed, const int* seed_off,
+                                   TensorRef zq, int batch, int channels, int lmax, int flip, hipStream_t s);
 // fp32 -> int16 PCM rows on the device (test/main.cpp:31-33); lens (device, optional) limits each row
 hipError_t launch_pcm16(const float* src, int64_t src_stride, int16_t* dst, int64_t dst_stride, const int64_t* lens, int rows, int64_t cols, hipStream_t s);
 hipError_t launch_conv_post(TensorRef x, const float* w, int cin, int k, float slope, TensorRef pre_tanh, TensorRef wave, const int* lens, int batch,

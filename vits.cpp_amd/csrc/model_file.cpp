@@ -318,6 +318,8 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         geti("sampling_rate", sampling_rate);
         geti("speaker_embedding_size", speaker_embedding_size);
         geti("num_speakers", num_speakers);
+        geti("spectrogram_bins", spec_bins);
+        geti("posterior_encoder_num_wavenet_layers", post_wn_layers);
         if (!f.cfg("hidden_act").empty()) hidden_act = f.cfg("hidden_act");
         if (!f.cfg("use_stochastic_duration_prediction").empty()) stochastic_duration = f.cfg("use_stochastic_duration_prediction") == "True";
     } catch (const std::exception& e) {
@@ -431,6 +433,9 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
     // VITS_SYNTH_SPEAKERS: a multi-speaker model — the same tensors as without the flag (same values), then the speaker tensors behind them
     const bool speakers = (arch_flags & VITS_SYNTH_SPEAKERS) != 0;
     const int spk_n = speakers ? (arch == VITS_SYNTH_TINY ? 4 : 109) : 1, spk_e = speakers ? (arch == VITS_SYNTH_TINY ? 8 : 256) : 0;
+    // VITS_SYNTH_POSTERIOR: the posterior encoder behind everything else (TINY: 9 bins = n_fft 16 over its hop of 8, two WaveNet layers)
+    const bool posterior = (arch_flags & VITS_SYNTH_POSTERIOR) != 0;
+    const int spec_bins = posterior && arch == VITS_SYNTH_TINY ? 9 : 513, post_layers = arch == VITS_SYNTH_TINY ? 2 : 16;
     ModelFile& f = s.f;
     // tokenizer block: a 38-entry single-character vocabulary in the style of the MMS checkpoints
     {
@@ -461,7 +466,7 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         puti("ffn_dim", h.ffn_dim);
         puti("ffn_kernel_size", h.ffn_k);
         puti("flow_size", h.flow_size);
-        puti("spectrogram_bins", 513);
+        puti("spectrogram_bins", spec_bins);
         put("hidden_act", "relu");
         put("layer_norm_eps", "1e-05");
         put("use_stochastic_duration_prediction", "True");
@@ -492,6 +497,7 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         put("noise_scale_duration", "0.8");
         puti("sampling_rate", h.sampling_rate);
         put("model_type", "vits");
+        if (posterior) puti("posterior_encoder_num_wavenet_layers", post_layers);
     }
     const int H = h.hidden, hd = H / h.heads, F = h.flow_size;
     // text encoder (HF state_dict order)
@@ -575,6 +581,23 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         s.conv("duration_predictor.cond", H, spk_e, 1, 0.6f);
         for (int i = 0; i < h.n_flows; ++i) s.conv("flow.flows." + std::to_string(i) + ".wavenet.cond_layer", 2 * H * h.wn_layers, spk_e, 1, 0.3f);
         s.conv("decoder.cond", h.up_init, spk_e, 1, 0.5f);
+    }
+    if (posterior) {
+        // transformers VitsPosteriorEncoder after weight-norm removal. Small gains: spectrogram magnitudes reach the hundreds, and exp(log_std)
+        // and the latents the flow sees stay of order one
+        const std::string b = "posterior_encoder.";
+        s.conv(b + "conv_pre", H, spec_bins, 1, 0.05f);
+        for (int l = 0; l < post_layers; ++l) {
+            s.add(b + "wavenet.in_layers." + std::to_string(l) + ".bias", {2 * H}, false, 0.02f);
+            s.add(b + "wavenet.in_layers." + std::to_string(l) + ".weight", {2 * H, H, h.wn_k}, true, 1.0f / std::sqrt((float)H * h.wn_k));
+        }
+        for (int l = 0; l < post_layers; ++l) {
+            const int co = l < post_layers - 1 ? 2 * H : H;
+            s.add(b + "wavenet.res_skip_layers." + std::to_string(l) + ".bias", {co}, false, 0.02f);
+            s.add(b + "wavenet.res_skip_layers." + std::to_string(l) + ".weight", {co, H, 1}, true, 1.0f / std::sqrt((float)H));
+        }
+        if (speakers) s.conv(b + "wavenet.cond_layer", 2 * H * post_layers, spk_e, 1, 0.3f);
+        s.conv(b + "conv_proj", 2 * F, H, 1, 0.15f);
     }
     return std::move(s.f);
 }

@@ -70,6 +70,8 @@ struct HParams {
     bool stochastic_duration = true;
     int speaker_embedding_size = 0;
     int num_speakers = 1;  // > 1: a multi-speaker model (embed_speaker + the cond layers; speaker_embedding_size > 0)
+    // posterior encoder (voice conversion only; TTS never reads these): linear-spectrogram bins in, WaveNet depth
+    int spec_bins = 513, post_wn_layers = 16;
     bool load(const ModelFile& f, std::string& err);
 };
 
