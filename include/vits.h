@@ -206,7 +206,29 @@ typedef struct vits_process_opts {
                                      Copied when the call returns (vits_model_submit_batch included). A speaker outside
                                      [-1, num_speakers), any speaker >= 0 on a single-speaker model, or one with
                                      vits_model_set_ggml_tables(model, 1) fails the call with -1 and a message naming the utterance. */
+    /* ---- prosody and token timings (transformers VitsModel.speaking_rate / noise_scale / noise_scale_duration, per utterance) ----
+     * Each array is optional host memory, NULL = every utterance uses the model value (vits_model_set_prosody). The arrays are copied
+     * when the call returns (vits_model_submit_batch included). Only the scales change: every noise draw stays where it is. Refused
+     * (-1, the message names the utterance / token): a rate that is not finite or outside [0.1, 10], a noise scale that is not finite or
+     * outside [0, 10], an override outside [-1, 10000], speaking_rates or duration_override with fixed_duration > 0. */
+    const float* speaking_rates;        /* [B]: d = ceil(exp(logw) * (float)(1.0 / rate)) (vits.cpp:996) */
+    const float* noise_scales;          /* [B]: scale of the prior draw (vits.cpp:1061) */
+    const float* noise_scale_durations; /* [B]: scale of the [2][T] duration draw (vits.cpp:948-949) */
+    const int32_t* duration_override;   /* [B][id_stride]: >= 0: token t of utterance b lasts that many frames; -1: the predicted duration
+                                           (scaled by the utterance's rate). The predictor still runs and still draws its noise. Frames
+                                           L = max(1, sum of d), as always. */
+    int32_t* durations_out;             /* [B][id_stride]: receives the frames of every token as used, 0 past id_lengths[b]. Filled before
+                                           the call returns, before the first on_chunk call, and (vits_model_submit_batch) no later than the
+                                           matching vits_model_wait: the buffer must stay valid until then. With fixed_duration > 0 every
+                                           token holds fixed_duration. frames_only fills it too. */
 } vits_process_opts;
+
+/* The model-level prosody: what vits_model_process, vits_model_process_ids and every call whose prosody arrays are NULL use. Initially the
+ * model file's speaking_rate, noise_scale and noise_scale_duration. Returns 0, or -1 (the handle keeps its values) for a rate that is not
+ * finite or outside [0.1, 10], or a noise scale that is not finite or outside [0, 10]. Voice conversion ignores these values (it has no
+ * duration prediction, and VITS's posterior draw has no noise scale); vits_model_convert_batch refuses the five per-utterance fields. */
+VITS_API int vits_model_set_prosody(vits_model* model, float speaking_rate, float noise_scale, float noise_scale_duration);
+VITS_API int vits_model_get_prosody(const vits_model* model, float* speaking_rate, float* noise_scale, float* noise_scale_duration);
 
 typedef struct vits_batch_result {
     float* data;      /* host [batch][stride] PCM (NULL when skip_host_copy) */
@@ -235,7 +257,8 @@ VITS_API void vits_free_batch_result(vits_batch_result* r);
  *   z_p    = flow(z_q, g_src) forward;  z = flow(z_p, g_tgt) reverse;  PCM = decoder(z, g_tgt), as in vits_model_process_batch
  * src_speakers / tgt_speakers: host [B], -1 = no conditioning (a single-speaker model takes -1 only). src = tgt resynthesises.
  * Options: mode, the noise fields, collect_taps, out_device(_stride), skip_host_copy, vocoder_chunk_frames and on_chunk mean what they
- * mean for vits_model_process_batch; fixed_duration, frames_only, async and speaker_ids are refused. vits_model_set_ggml_tables affects
+ * mean for vits_model_process_batch; fixed_duration, frames_only, async, speaker_ids and the five prosody fields (speaking_rates ..
+ * durations_out) are refused, and the model-level prosody (vits_model_set_prosody) has no effect. vits_model_set_ggml_tables affects
  * stage one only, which a conversion never runs: it has no effect here. out: frames[b] = L_b, lengths / stride / data as in TTS.
  * Taps (collect_taps): "spec" [bins][L], "post_mean" / "post_logstd" / "z_q" [F][L], and "noise_prior" (eps), "z_p" (the forward
  * flow's output), "z_flow", "pre_tanh", "waveform".

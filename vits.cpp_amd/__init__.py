@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_arith_scope", "vits_model_get_arith_scope", "vits_model_submit_batch", "vits_model_wait", "vits_model_pending",
     "vits_model_set_ggml_tables", "vits_model_get_ggml_tables",
     "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
+    "vits_model_set_prosody", "vits_model_get_prosody",
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
@@ -59,6 +60,8 @@ class ProcessOpts(C.Structure):
         ("out_device_stride", C.c_int64), ("skip_host_copy", C.c_int32), ("async_", C.c_int32),
         ("vocoder_chunk_frames", C.c_int32), ("frames_only", C.c_int32), ("on_chunk", ChunkCallback), ("on_chunk_user", C.c_void_p),
         ("noise_seed_offsets", C.c_void_p), ("speaker_ids", C.c_void_p),
+        ("speaking_rates", C.c_void_p), ("noise_scales", C.c_void_p), ("noise_scale_durations", C.c_void_p),
+        ("duration_override", C.c_void_p), ("durations_out", C.c_void_p),
     ]
 
 
@@ -152,6 +155,10 @@ def lib():
     L.vits_model_get_speaker.argtypes = [vp]
     L.vits_model_num_speakers.restype = i32
     L.vits_model_num_speakers.argtypes = [vp]
+    L.vits_model_set_prosody.restype = i32
+    L.vits_model_set_prosody.argtypes = [vp, C.c_float, C.c_float, C.c_float]
+    L.vits_model_get_prosody.restype = i32
+    L.vits_model_get_prosody.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.vits_model_prepare_conversion.restype = i32
     L.vits_model_prepare_conversion.argtypes = [vp]
     L.vits_model_convert_batch.restype = i32
@@ -222,6 +229,33 @@ def _ptr(a):
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out):
+    """Fills the prosody fields of a ProcessOpts; returns the arrays it points at (the caller keeps them alive for the call).
+    Scalars are broadcast to the batch, None leaves a field NULL (the model value)."""
+    keep = []
+    for name, v in (("speaking_rates", speaking_rate), ("noise_scales", noise_scale), ("noise_scale_durations", noise_scale_duration)):
+        if v is None:
+            continue
+        if np.ndim(v) and np.size(v) not in (1, B):
+            raise ValueError("%s needs a scalar or one value per utterance" % name)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).ravel() if np.ndim(v) else np.float32(v), (B,)))
+        setattr(o, name, _ptr(a))
+        keep.append(a)
+    if duration_override is not None:
+        a = np.ascontiguousarray(duration_override, dtype=np.int32).reshape(B, -1)
+        if a.shape[1] != stride:
+            raise ValueError("duration_override needs [B, id_stride] = [%d, %d] entries" % (B, stride))
+        o.duration_override = _ptr(a)
+        keep.append(a)
+    if durations_out is not None:
+        if not (isinstance(durations_out, np.ndarray) and durations_out.dtype == np.int32 and durations_out.flags.c_contiguous
+                and durations_out.size == B * stride and durations_out.flags.writeable):
+            raise ValueError("durations_out must be a writeable C-contiguous int32 array of [B, id_stride] = [%d, %d]" % (B, stride))
+        o.durations_out = _ptr(durations_out)
+        keep.append(durations_out)
+    return keep
 
 
 def synth_model_bytes(seed=0x5EED, arch=SYNTH_FULL):
@@ -368,6 +402,45 @@ class Model:
         """1 for a single-speaker model"""
         return int(lib().vits_model_num_speakers(self._h))
 
+    # -- prosody: the transformers.VitsModel attributes, the model-level values (vits_model_set_prosody) --------------------------
+    def get_prosody(self):
+        """(speaking_rate, noise_scale, noise_scale_duration) the reference entry points and calls without per-utterance values use"""
+        v = [C.c_float() for _ in range(3)]
+        if lib().vits_model_get_prosody(self._h, *[C.byref(x) for x in v]) != 0:
+            raise VitsError(last_error())
+        return tuple(float(x.value) for x in v)
+
+    def set_prosody(self, speaking_rate=None, noise_scale=None, noise_scale_duration=None):
+        """sets the given values (None keeps the current one); a rejected value leaves all three unchanged"""
+        cur = self.get_prosody()
+        new = [cur[i] if v is None else float(v) for i, v in enumerate((speaking_rate, noise_scale, noise_scale_duration))]
+        if lib().vits_model_set_prosody(self._h, *new) != 0:
+            raise VitsError(last_error())
+
+    @property
+    def speaking_rate(self):
+        return self.get_prosody()[0]
+
+    @speaking_rate.setter
+    def speaking_rate(self, v):
+        self.set_prosody(speaking_rate=v)
+
+    @property
+    def noise_scale(self):
+        return self.get_prosody()[1]
+
+    @noise_scale.setter
+    def noise_scale(self, v):
+        self.set_prosody(noise_scale=v)
+
+    @property
+    def noise_scale_duration(self):
+        return self.get_prosody()[2]
+
+    @noise_scale_duration.setter
+    def noise_scale_duration(self, v):
+        self.set_prosody(noise_scale_duration=v)
+
     @property
     def ggml_tables(self):
         return bool(lib().vits_model_get_ggml_tables(self._h))
@@ -407,11 +480,14 @@ class Model:
     def process_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321,
                       noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False, out_device=None,
                       out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False, noise_seed_offsets=None, keep_pcm=True,
-                      speaker_ids=None):
+                      speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None, durations_out=None):
         """ids: int32 [B, id_stride]. Returns (list of per-utterance PCM arrays or None, lengths, frames).
         vocoder_chunk_frames > 0 runs the vocoder window by window (bit-identical PCM, bounded activations);
         on_chunk(utt, offset, pcm ndarray) is then called as each window's samples reach the host (return True to abort).
-        speaker_ids: one speaker per utterance (-1 = none; None = the model default, set_speaker)."""
+        speaker_ids: one speaker per utterance (-1 = none; None = the model default, set_speaker).
+        speaking_rate / noise_scale / noise_scale_duration: a scalar for the whole batch or one value per utterance (None = the model values);
+        duration_override: int32 [B, id_stride] (>= 0: the token's frames, -1: the prediction); durations_out: a caller-owned int32 [B, id_stride]
+        array that receives every token's frames."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         if ids.ndim == 1:
             ids = ids[None, :]
@@ -437,6 +513,7 @@ class Model:
         if spk is not None and spk.size != B:
             raise ValueError("speaker_ids needs one entry per utterance")
         o.speaker_ids = _ptr(spk)
+        keep = _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)  # noqa: F841
         cb_error = []
         if on_chunk is not None:
             def _cb(_user, utt, offset, pcm, n):
@@ -473,7 +550,8 @@ class Model:
         """Voice conversion (vits_model_convert_batch). pcm: float32 [B, stride] (or one 1-D utterance) at the model's sampling rate; lengths:
         valid samples per row (None = the whole row); src / tgt: the source and target speaker, one int for every utterance or one per
         utterance (-1 = none). Returns (list of per-utterance PCM arrays or None, lengths, frames) like process_batch. Keyword arguments
-        that conversion refuses (fixed_duration, frames_only, async_, speaker_ids) are passed on, so that the library says why."""
+        that conversion refuses (fixed_duration, frames_only, async_, speaker_ids, and the prosody arguments of process_batch) are passed on, so that
+        the library says why. The model-level prosody (speaking_rate, noise_scale, noise_scale_duration) does not affect a conversion."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 1:
             pcm = pcm[None, :]
@@ -497,6 +575,14 @@ class Model:
         o.frames_only = int(refused.pop("frames_only", False))
         o.async_ = int(refused.pop("async_", False))
         spk = refused.pop("speaker_ids", None)
+        keep = []
+        for arg, field, dtype in (("speaking_rate", "speaking_rates", np.float32), ("noise_scale", "noise_scales", np.float32),
+                                  ("noise_scale_duration", "noise_scale_durations", np.float32), ("duration_override", "duration_override", np.int32),
+                                  ("durations_out", "durations_out", np.int32)):
+            v = refused.pop(arg, None)
+            if v is not None:
+                keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype).ravel(), (max(B, np.size(v)),))))
+                setattr(o, field, _ptr(keep[-1]))
         if refused:
             raise TypeError("unknown arguments: %s" % sorted(refused))
         spk = None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()
@@ -542,9 +628,11 @@ class Model:
             lib().vits_free_result(r)
 
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
-                     skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None):
+                     skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None,
+                     noise_scale_duration=None, duration_override=None, durations_out=None):
         """vits_model_submit_batch: queue one batch on this handle's pipeline (at most two in flight); its stage one runs under the
-        previous batch's vocoder. Results come from wait(), in submission order, bit-identical to process_batch."""
+        previous batch's vocoder. Results come from wait(), in submission order, bit-identical to process_batch. The prosody arguments are
+        those of process_batch; durations_out is filled by the matching wait() at the latest (this handle keeps it alive until then)."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         if ids.ndim == 1:
             ids = ids[None, :]
@@ -566,14 +654,20 @@ class Model:
         if spk is not None and spk.size != B:
             raise ValueError("speaker_ids needs one entry per utterance")
         o.speaker_ids = _ptr(spk)
+        keep = _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)  # noqa: F841
         if lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o)) != 0:
             raise VitsError(last_error())
+        if not hasattr(self, "_durations_in_flight"):
+            self._durations_in_flight = []
+        self._durations_in_flight.append(durations_out)  # (the library writes it no later than the matching wait)
 
     def wait(self, keep_pcm=True):
         """vits_model_wait: (pcm list or None, lengths, frames) of the oldest submitted batch."""
         res = BatchResult()
         if lib().vits_model_wait(self._h, C.byref(res)) != 0:
             raise VitsError(last_error())
+        if getattr(self, "_durations_in_flight", None):
+            self._durations_in_flight.pop(0)
         try:
             B = res.batch
             lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()

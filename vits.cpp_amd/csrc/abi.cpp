@@ -245,6 +245,29 @@ VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker) {
 }
 VITS_API int32_t vits_model_get_speaker(const vits_model* model) { return model ? model->eng.speaker : -2; }
 VITS_API int32_t vits_model_num_speakers(const vits_model* model) { return model ? model->eng.num_speakers() : -1; }
+VITS_API int vits_model_set_prosody(vits_model* model, float speaking_rate, float noise_scale, float noise_scale_duration) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    std::string err;
+    if (model->eng.set_prosody(speaking_rate, noise_scale, noise_scale_duration, err) != 0) {
+        set_err(err);
+        return -1;
+    }
+    return 0;
+}
+VITS_API int vits_model_get_prosody(const vits_model* model, float* speaking_rate, float* noise_scale, float* noise_scale_duration) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (speaking_rate) *speaking_rate = model->eng.speaking_rate;
+    if (noise_scale) *noise_scale = model->eng.noise_scale;
+    if (noise_scale_duration) *noise_scale_duration = model->eng.noise_scale_dur;
+    return 0;
+}
 
 VITS_API int vits_model_process_batch(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch, int32_t id_stride,
                                       const vits_process_opts* opts, vits_batch_result* out) {

@@ -136,6 +136,56 @@ int Engine::check_speakers(const vits_process_opts& o, int B, std::string& err) 
     return 0;
 }
 
+namespace {
+bool rate_ok(float r) { return std::isfinite(r) && r >= 0.1f && r <= 10.f; }
+bool noise_scale_ok(float v) { return std::isfinite(v) && v >= 0.f && v <= 10.f; }
+std::string fmt_float(float v) {
+    char buf[32];
+    std::snprintf(buf, sizeof(buf), "%.9g", (double)v);
+    return buf;
+}
+}  // namespace
+
+int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
+    if (!rate_ok(rate) || !noise_scale_ok(ns) || !noise_scale_ok(nsd)) {
+        err = "vits_model_set_prosody(" + fmt_float(rate) + ", " + fmt_float(ns) + ", " + fmt_float(nsd) + "): " +
+              (!rate_ok(rate) ? "speaking_rate must be finite and in [0.1, 10]" : "noise scales must be finite and in [0, 10]");
+        return -1;
+    }
+    speaking_rate = rate, noise_scale = ns, noise_scale_dur = nsd;
+    return 0;
+}
+
+int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const {
+    if (o.fixed_duration > 0 && (o.speaking_rates || o.duration_override)) {
+        err = std::string(o.speaking_rates ? "speaking_rates" : "duration_override") + " cannot be combined with fixed_duration > 0 (every token already lasts fixed_duration frames)";
+        return -1;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (o.speaking_rates && !rate_ok(o.speaking_rates[b])) {
+            err = "speaking_rates[" + std::to_string(b) + "] = " + fmt_float(o.speaking_rates[b]) + ": must be finite and in [0.1, 10]";
+            return -1;
+        }
+        for (const auto& [arr, name] : {std::make_pair(o.noise_scales, "noise_scales"), std::make_pair(o.noise_scale_durations, "noise_scale_durations")})
+            if (arr && !noise_scale_ok(arr[b])) {
+                err = std::string(name) + "[" + std::to_string(b) + "] = " + fmt_float(arr[b]) + ": must be finite and in [0, 10]";
+                return -1;
+            }
+        if (o.duration_override) {
+            const int len = std::min(id_stride, std::max(0, id_lens ? id_lens[b] : id_stride));  // (entries past the utterance are never read)
+            for (int t = 0; t < len; ++t) {
+                const int32_t v = o.duration_override[(size_t)b * id_stride + t];
+                if (v < -1 || v > 10000) {
+                    err = "duration_override[" + std::to_string(b) + "][" + std::to_string(t) + "] = " + std::to_string(v) +
+                          " (utterance " + std::to_string(b) + ", token " + std::to_string(t) + "): must be -1 (the prediction) or in [0, 10000]";
+                    return -1;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                           std::string& err) {
     if (pending()) {
@@ -143,6 +193,7 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
         return -1;
     }
     if (check_speakers(o, B, err)) return -1;
+    if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -166,6 +217,11 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
         vits_process_opts oh = o;
         oh.noise_seed_offsets = offs.data() + b0[h];
         if (o.speaker_ids) oh.speaker_ids = o.speaker_ids + b0[h];
+        if (o.speaking_rates) oh.speaking_rates = o.speaking_rates + b0[h];
+        if (o.noise_scales) oh.noise_scales = o.noise_scales + b0[h];
+        if (o.noise_scale_durations) oh.noise_scale_durations = o.noise_scale_durations + b0[h];
+        if (o.duration_override) oh.duration_override = o.duration_override + (size_t)b0[h] * id_stride;
+        if (o.durations_out) oh.durations_out = o.durations_out + (size_t)b0[h] * id_stride;
         if (o.out_device) oh.out_device = (float*)o.out_device + (int64_t)b0[h] * o.out_device_stride;
         if (submit_batch(ids + (size_t)b0[h] * id_stride, id_lens ? id_lens + b0[h] : nullptr, nb[h], id_stride, oh, err)) break;
         ++queued;
@@ -233,6 +289,7 @@ int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int 
         return -1;
     }
     if (check_speakers(o, B, err)) return -1;  // (the speakers are copied into the call's header below: the caller's array may go at once)
+    if (check_prosody(o, B, id_stride, id_lens, err)) return -1;  // (so are the prosody arrays; durations_out is written when the frame counts are read)
     Pending& p = pend_[submit_seq_ & 1];
     if (!p.done) {
         HIP_OK(hipEventCreateWithFlags(&p.s1_done, hipEventDisableTiming));
@@ -288,6 +345,24 @@ struct StreamSwap {
     ~StreamSwap() { slot = saved; }
 };
 }  // namespace
+
+// opts.durations_out: the durations of stage one (dur [B][id_stride], integer-valued floats, 0 past each utterance) queued for the host beside the
+// frame counts, into grow-only pinned memory; store_durations converts them once that copy has landed
+hipError_t Engine::copy_durations(const Call& c, float*& pinned, size_t& cap) {
+    const size_t n = (size_t)c.B * c.id_stride;
+    if (cap < n) {
+        if (pinned) hipHostFree(pinned);
+        pinned = nullptr;
+        cap = 0;
+        if (hipError_t e = hipHostMalloc((void**)&pinned, sizeof(float) * (n + n / 4 + 64), hipHostMallocDefault)) return e;
+        cap = n + n / 4 + 64;
+    }
+    return hipMemcpyAsync(pinned, c.s1.dur, sizeof(float) * n, hipMemcpyDeviceToHost, stream);
+}
+void Engine::store_durations(const Call& c, const float* pinned) const {
+    const size_t n = (size_t)c.B * c.id_stride;
+    for (size_t i = 0; i < n; ++i) c.o.durations_out[i] = (int32_t)pinned[i];
+}
 
 int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                          std::string& err, Pending* pend) {
@@ -359,7 +434,10 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         // The reference's own call (vits_model_process: one utterance, libstdc++ noise). Its two noise tensors are drawn on the host: [T, 2] at
         // vits.cpp:948 and [L, 192] at :1059 — ~1.25 ms for 128 ids, and L is known only behind stage one. A helper thread draws the stream from NOW on,
         // while this thread queues stage one and the device runs it (RefNoiseAhead, engine_support.cpp); run_prior_sampling names the size.
-        const size_t want = (size_t)hp.flow_size * ((size_t)knobs.ref_ahead_frames_per_id * c.Tmax + 64);
+        // (sized by the utterance's length scale: a slowed-down utterance needs proportionally more frames per id)
+        const double ls = o.speaking_rates ? 1.0 / (double)o.speaking_rates[0] : 1.0 / (double)speaking_rate;
+        const size_t per_id = (size_t)std::ceil(knobs.ref_ahead_frames_per_id * std::max(1.0, ls));
+        const size_t want = (size_t)hp.flow_size * (per_id * c.Tmax + 64);
         if (ref_noise_cap_ < want) {
             if (ref_noise_pinned_) hipHostFree(ref_noise_pinned_);
             ref_noise_pinned_ = nullptr;
@@ -397,10 +475,12 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
             pend->frames_cap = (size_t)B + 64;
         }
         HIP_OK(hipMemcpyAsync(pend->frames_pinned, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+        if (o.durations_out) HIP_OK(copy_durations(c, pend->dur_pinned, pend->dur_cap));
         HIP_OK(hipEventRecord(pend->s1_done, stream));
         prof.fence();
         HIP_OK(hipEventSynchronize(pend->s1_done));
         std::copy(pend->frames_pinned, pend->frames_pinned + B, frames.begin());
+        if (o.durations_out) store_durations(c, pend->dur_pinned);
     } else {
         // (pinned destination, owned by the engine: into the caller-side std::vector the copy went through the runtime's staging buffer, + 15 us per batch-1 call)
         if (frames_host_cap_ < (size_t)B) {
@@ -411,11 +491,16 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
             frames_host_cap_ = (size_t)B + 64;
         }
         HIP_OK(hipMemcpyAsync(frames_host_, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+        if (o.durations_out) HIP_OK(copy_durations(c, dur_host_, dur_host_cap_));
         prof.fence();
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
         std::copy(frames_host_, frames_host_ + B, frames.begin());
+        if (o.durations_out) store_durations(c, dur_host_);
     }
+    if (o.durations_out && o.fixed_duration > 0)  // (no device read: every token lasts fixed_duration frames)
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < id_stride; ++t) o.durations_out[(size_t)b * id_stride + t] = t < c.tlen[b] ? o.fixed_duration : 0;
     if (overlap) {
         // stage two runs on the main stream, behind this batch's stage one (pinned durations: no host read ordered them yet)
         if (o.fixed_duration > 0) HIP_OK(hipEventRecord(pend->s1_done, stream));

@@ -205,6 +205,14 @@ class Engine {
     // the exact-order stage one (ggml_tables == 1)
     int check_speakers(const vits_process_opts& o, int B, std::string& err) const;
     int speaker_of(const vits_process_opts& o, int b) const { return o.speaker_ids ? o.speaker_ids[b] : speaker; }
+    // prosody (include/vits.h vits_model_set_prosody): the values of every utterance a call gives none for (the prosody arrays of
+    // vits_process_opts == NULL, vits_model_process / _ids); the model file's speaking_rate / noise_scale / noise_scale_duration at load
+    float speaking_rate = 1.f, noise_scale = 0.667f, noise_scale_dur = 0.8f;
+    // 0, or -1 + a message (the handle keeps its values): rate finite in [0.1, 10], noise scales finite in [0, 10]
+    int set_prosody(float rate, float ns, float nsd, std::string& err);
+    // 0, or -1 + a message naming the utterance (and the token): the call's prosody arrays in range, neither speaking_rates nor
+    // duration_override together with fixed_duration
+    int check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const;
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -301,6 +309,8 @@ class Engine {
         size_t frames_cap = 0;  // ints
         int* win_pinned = nullptr;  // vocoder-window length table of a windowed batch (host side of its H2D copy)
         size_t win_cap = 0;         // ints
+        float* dur_pinned = nullptr;  // opts.durations_out: the batch's durations, copied beside the frame counts
+        size_t dur_cap = 0;           // floats
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -317,6 +327,8 @@ class Engine {
     int process_split(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err);
     int process_impl(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err,
                      Pending* pend);
+    hipError_t copy_durations(const Call& c, float*& pinned, size_t& cap);
+    void store_durations(const Call& c, const float* pinned) const;
     // The three resblocks of a vocoder stage (kernel sizes 3/7/11) are independent chains of six convolutions; they run on
     // three streams so that the tail of one kernel's grid overlaps the head of another's. side_[j-1] carries resblock j.
     hipStream_t side_[2] = {nullptr, nullptr};
@@ -325,6 +337,8 @@ class Engine {
     void* pinned_ = nullptr;   // grow-only pinned staging for streamed PCM
     int* frames_host_ = nullptr;  // pinned [frames_host_cap_]: destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
     size_t frames_host_cap_ = 0;
+    float* dur_host_ = nullptr;  // pinned: a synchronous call's durations for opts.durations_out, copied beside the frame counts
+    size_t dur_host_cap_ = 0;    // floats
     size_t pinned_cap_ = 0;
     // arithmetic of the convolutions being queued right now: `arith`, or fp32 while stage one runs under
     // VITS_ARITH_SCOPE_FLOW_VOCODER (every conv wrapper and fused kernel reads this one, never `arith` itself)

@@ -156,6 +156,12 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
         err = "voice conversion takes its speakers from src_speakers and tgt_speakers, not from opts.speaker_ids";
         return -1;
     }
+    if (o.speaking_rates || o.noise_scales || o.noise_scale_durations || o.duration_override || o.durations_out) {
+        err = std::string("voice conversion does not take opts.") +
+              (o.speaking_rates ? "speaking_rates" : o.noise_scales ? "noise_scales" : o.noise_scale_durations ? "noise_scale_durations" : o.duration_override ? "duration_override" : "durations_out") +
+              " (it has no duration prediction, and the posterior draw has no noise scale)";
+        return -1;
+    }
     if (o.on_chunk && o.skip_host_copy) {
         err = "on_chunk needs a host copy (skip_host_copy = 0)";
         return -1;

@@ -161,7 +161,7 @@ int Engine::run_prior_sampling(Call& c) {
     }
     prof.begin("prior_sample_gather", 0, 0, stream);
     HIP_OK(launch_zp(sub(stats, 0), sub(stats, F), s1.cum, id_stride, dl, s1.frames, noise, o.noise_kind == VITS_NOISE_COUNTER ? VITS_NOISE_COUNTER : VITS_NOISE_EXPLICIT,
-                     o.noise_seed, s1.seed_off, hp.noise_scale, zp, B, F, Lmax, stream));
+                     o.noise_seed, s1.seed_off, noise_scale, s1.noise_scale, zp, B, F, Lmax, stream));
     prof.end(stream);
     if (o.collect_taps) snapshot("z_p", zp, F, Lmax, B, frames);
     (void)n_up;

@@ -101,6 +101,10 @@ struct Call {
     // stage one (sized by B x T)
     struct S1 {
         int *ids, *lens, *cum, *frames, *stage_lens, *stage_mul, *stage_add, *seed_off, *spk_row;
+        // per-utterance prosody (header sections present only when the call passes the array, null otherwise): length scale 1 / rate,
+        // prior noise scale, duration noise scale [B]; duration overrides [B][id_stride]
+        float *len_scale, *noise_scale, *noise_scale_dur;
+        int* dur_ovr;
         float *x, *qkv, *att, *tmp, *ffn, *stats, *dpx, *dpy, *dpp, *cond, *z, *u, *dur;
         float *ex_scores, *ex_tok;  // emulated-ggml mode 1 only
         uint16_t* x16;

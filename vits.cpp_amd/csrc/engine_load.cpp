@@ -15,6 +15,7 @@ Engine::~Engine() {
         if (p.host) hipHostFree(p.host);
         if (p.frames_pinned) hipHostFree(p.frames_pinned);
         if (p.win_pinned) hipHostFree(p.win_pinned);
+        if (p.dur_pinned) hipHostFree(p.dur_pinned);
         if (p.s1_done) hipEventDestroy(p.s1_done);
         if (p.done) hipEventDestroy(p.done);
     }
@@ -26,6 +27,7 @@ Engine::~Engine() {
     }
     if (pinned_) hipHostFree(pinned_);
     if (frames_host_) hipHostFree(frames_host_);
+    if (dur_host_) hipHostFree(dur_host_);
     for (HStage& hs : hstage_) {
         if (hs.p) hipHostFree(hs.p);
         if (hs.ev) hipEventDestroy(hs.ev);
@@ -372,6 +374,7 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
     ModelFile f;
     if (!f.parse(bytes, size, err)) return false;
     if (!hp.load(f, err)) return false;
+    speaking_rate = hp.speaking_rate, noise_scale = hp.noise_scale, noise_scale_dur = hp.noise_scale_dur;
     tok.init(f);
     int ndev = 0;
     if (!dry_run_ && (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)) {

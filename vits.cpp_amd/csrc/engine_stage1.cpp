@@ -107,15 +107,29 @@ int Engine::layout_stage_one(Call& c) {
     const int H = hp.hidden, F = hp.flow_size;
     Call::S1& s1 = c.s1;
     size_t x16_elems1 = 0;
-    const size_t hdr_ints = (size_t)B * id_stride + 3 * (size_t)B + 2 * (size_t)(n_up + 1);
+    const size_t base_ints = (size_t)B * id_stride + 3 * (size_t)B + 2 * (size_t)(n_up + 1);
+    // per-utterance prosody: a section per array the call passes (a call without them copies exactly the header it always did)
+    const size_t hdr_ints = base_ints + (size_t)B * ((o.speaking_rates ? 1 : 0) + (o.noise_scales ? 1 : 0) + (o.noise_scale_durations ? 1 : 0)) +
+                            (o.duration_override ? (size_t)B * id_stride : 0);
     auto layout1 = [&](Arena& a) {
-        // host-written header, one block = one H2D copy: ids | lens | stage_mul | stage_add | seed_off | spk_row
+        // host-written header, one block = one H2D copy: ids | lens | stage_mul | stage_add | seed_off | spk_row [| len_scale] [| noise_scale]
+        // [| noise_scale_dur] [| dur_ovr]
         s1.ids = a.alloc<int>(hdr_ints);
         s1.lens = s1.ids + (size_t)B * id_stride;
         s1.stage_mul = s1.lens + B;
         s1.stage_add = s1.stage_mul + (n_up + 1);
         s1.seed_off = s1.stage_add + (n_up + 1);
         s1.spk_row = s1.seed_off + B;
+        int* sec = s1.ids + base_ints;
+        auto section = [&](bool present, size_t n) -> int* {
+            int* p = present ? sec : nullptr;
+            if (present) sec += n;
+            return p;
+        };
+        s1.len_scale = (float*)section(o.speaking_rates, B);
+        s1.noise_scale = (float*)section(o.noise_scales, B);
+        s1.noise_scale_dur = (float*)section(o.noise_scale_durations, B);
+        s1.dur_ovr = section(o.duration_override, (size_t)B * id_stride);
         s1.cum = a.alloc<int>((size_t)B * id_stride);
         s1.frames = a.alloc<int>(B);
         s1.stage_lens = a.alloc<int>((size_t)(n_up + 1) * B);
@@ -203,6 +217,16 @@ int Engine::layout_stage_one(Call& c) {
             any_spk = any_spk || sp >= 0;
         }
         c.spk = any_spk ? s1.spk_row : nullptr;
+        // prosody sections at their offsets in the device header (length scale = (float)(1.0 / rate): the expression the model-level value uses)
+        auto host_of = [&](const void* dev) { return hs.p + ((const int*)dev - s1.ids); };
+        if (o.speaking_rates)
+            for (int b = 0; b < B; ++b) {
+                const float ls = (float)(1.0 / (double)o.speaking_rates[b]);
+                std::memcpy(host_of(s1.len_scale) + b, &ls, sizeof(float));
+            }
+        if (o.noise_scales) std::memcpy(host_of(s1.noise_scale), o.noise_scales, sizeof(float) * B);
+        if (o.noise_scale_durations) std::memcpy(host_of(s1.noise_scale_dur), o.noise_scale_durations, sizeof(float) * B);
+        if (o.duration_override) std::memcpy(host_of(s1.dur_ovr), o.duration_override, sizeof(int) * (size_t)B * id_stride);
         HIP_OK(hipMemcpyAsync(s1.ids, hs.p, sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
         HIP_OK(hipEventRecord(hs.ev, stream));
         hs.pending = true;
@@ -350,7 +374,7 @@ int Engine::run_duration_predictor(Call& c) {
     std::vector<float> host_noise;
     if (o.noise_kind == VITS_NOISE_COUNTER) {
         prof.begin("noise_dur", 0, 0, stream);
-        HIP_OK(launch_noise_dur(z, dl, B, Tmax, o.noise_seed, s1.seed_off, hp.noise_scale_dur, stream));
+        HIP_OK(launch_noise_dur(z, dl, B, Tmax, o.noise_seed, s1.seed_off, noise_scale_dur, s1.noise_scale_dur, stream));
         prof.end(stream);
     } else if (c.ref_ahead) {
         // the reference's own call: the [T, 2] draws (vits.cpp:948) come from the helper thread (it holds the stream's lock: nobody else may draw now),
@@ -372,7 +396,7 @@ int Engine::run_duration_predictor(Call& c) {
         HIP_OK(hipEventRecord(dur_noise_ev_, stream));
         prof.fence();
         if (o.collect_taps) snapshot("noise_dur", z, 2, Tmax, B, tlen);
-        HIP_OK(launch_scale_rows(z, 2, hp.noise_scale_dur, B, Tmax, stream));
+        HIP_OK(launch_scale_rows(z, 2, noise_scale_dur, s1.noise_scale_dur, B, Tmax, stream));
     } else {
         host_noise.assign((size_t)B * 2 * ts, 0.f);
         for (int b = 0; b < B; ++b) {
@@ -391,7 +415,7 @@ int Engine::run_duration_predictor(Call& c) {
         HIP_OK(hipMemcpyAsync(s1.z, host_noise.data(), sizeof(float) * host_noise.size(), hipMemcpyHostToDevice, stream));
         prof.fence();
         if (o.collect_taps) snapshot("noise_dur", z, 2, Tmax, B, tlen);
-        HIP_OK(launch_scale_rows(z, 2, hp.noise_scale_dur, B, Tmax, stream));
+        HIP_OK(launch_scale_rows(z, 2, noise_scale_dur, s1.noise_scale_dur, B, Tmax, stream));
     }
     int c_first = 0;  // physical row holding logical latent channel 0
     const float inv_sqrt = (float)(1.0 / std::sqrt((double)H));
@@ -423,8 +447,8 @@ int Engine::run_duration_predictor(Call& c) {
     }
     if (o.collect_taps) snapshot("log_duration", sub(z, c_first), 1, Tmax, B, tlen);
     prof.begin("durations", 0, 0, stream);
-    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / hp.speaking_rate), o.fixed_duration, s1.dur, s1.cum, s1.frames, s1.stage_lens, n_up + 1,
-                            s1.stage_mul, s1.stage_add, stream));
+    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, s1.dur_ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames,
+                            s1.stage_lens, n_up + 1, s1.stage_mul, s1.stage_add, stream));
     prof.end(stream);
     c.c_first = c_first;
     return 0;

@@ -164,7 +164,7 @@ int Engine::run_stage_one_exact(Call& c) {
     std::vector<float> host_noise;
     if (o.noise_kind == VITS_NOISE_COUNTER) {
         prof.begin("noise_dur", 0, 0, stream);
-        HIP_OK(launch_noise_dur(z, dl, B, Tmax, o.noise_seed, s1.seed_off, hp.noise_scale_dur, stream));  // one multiply per element (:948-949)
+        HIP_OK(launch_noise_dur(z, dl, B, Tmax, o.noise_seed, s1.seed_off, noise_scale_dur, s1.noise_scale_dur, stream));  // one multiply per element (:948-949)
         prof.end(stream);
     } else if (c.ref_ahead) {
         // (batch 1, reference noise: the helper thread of engine.cpp holds the stream — take the [T, 2] tensor from it)
@@ -174,7 +174,7 @@ int Engine::run_stage_one_exact(Call& c) {
         HIP_OK(hipMemcpyAsync(s1.z, host_noise.data(), sizeof(float) * host_noise.size(), hipMemcpyHostToDevice, stream));
         prof.fence();
         if (o.collect_taps) snapshot("noise_dur", z, 2, Tmax, B, tlen);
-        HIP_OK(launch_scale_rows(z, 2, hp.noise_scale_dur, B, Tmax, stream));
+        HIP_OK(launch_scale_rows(z, 2, noise_scale_dur, s1.noise_scale_dur, B, Tmax, stream));
         HIP_OK(hipStreamSynchronize(stream));  // host_noise goes out of scope
     } else {
         host_noise.assign((size_t)B * 2 * ts, 0.f);
@@ -194,7 +194,7 @@ int Engine::run_stage_one_exact(Call& c) {
         HIP_OK(hipMemcpyAsync(s1.z, host_noise.data(), sizeof(float) * host_noise.size(), hipMemcpyHostToDevice, stream));
         prof.fence();
         if (o.collect_taps) snapshot("noise_dur", z, 2, Tmax, B, tlen);
-        HIP_OK(launch_scale_rows(z, 2, hp.noise_scale_dur, B, Tmax, stream));
+        HIP_OK(launch_scale_rows(z, 2, noise_scale_dur, s1.noise_scale_dur, B, Tmax, stream));
         HIP_OK(hipStreamSynchronize(stream));  // host_noise goes out of scope
     }
     const int nb = hp.dp_bins;
@@ -245,8 +245,8 @@ int Engine::run_stage_one_exact(Call& c) {
     }
     if (o.collect_taps) snapshot("log_duration", sub(z, c_first), 1, Tmax, B, tlen);
     prof.begin("durations", 0, 0, stream);
-    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / hp.speaking_rate), o.fixed_duration, s1.dur, s1.cum, s1.frames, s1.stage_lens, n_up + 1, s1.stage_mul,
-                            s1.stage_add, stream, /*exact=*/true));
+    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, s1.dur_ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames,
+                            s1.stage_lens, n_up + 1, s1.stage_mul, s1.stage_add, stream, /*exact=*/true));
     prof.end(stream);
     c.c_first = c_first;
     return 0;

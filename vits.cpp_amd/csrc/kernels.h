@@ -436,7 +436,8 @@ hipError_t launch_conv_post16(Ref16 x, const float* w, int cin, int k, TensorRef
 // ---- small kernels ------------------------------------------------------------------------------------
 hipError_t launch_embed(const int* ids, int id_stride, const int* lens, const float* table, int hidden, float scale, TensorRef x, int batch, int tmax,
                         hipStream_t s);
-hipError_t launch_scale_rows(TensorRef x, int channels, float scale, int batch, int tmax, hipStream_t s);
+// x[b][c][t] *= scale, or scales[b] when scales (device [B]) is given
+hipError_t launch_scale_rows(TensorRef x, int channels, float scale, const float* scales, int batch, int tmax, hipStream_t s);
 // EMULATED ggml lookup tables (INFERRED from upstream ggerganov/ggml of the reference's era, the maxilevi/ggml fork is
 // absent): device copies of the two 65536-entry fp16 tables ggml builds at init — gelu[i] = fp16(tanh-GELU(fp16 value i)), exp[i] =
 // fp16(expf(fp16 value i)) — built on the host with the C library (Engine::set_ggml_tables). Kernels that receive a non-null pointer route
@@ -497,11 +498,15 @@ hipError_t launch_exact_attention(TensorRef q, TensorRef k, TensorRef v, const f
 hipError_t launch_exact_affine(TensorRef z, int c_first, float t0, float t1, float e0, float e1, const int* lens, int batch, int tmax, hipStream_t s);
 hipError_t launch_exact_spline(TensorRef z, int row, TensorRef u, float* res, float* inside, float* tmp, int stride, const int* lens, int batch, int tmax, int nb, float B,
                                float inv_sqrt, float constant, bool refmode, const uint16_t* exp_tab, hipStream_t s);
-hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, hipStream_t s);
-hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, int tmax, float length_scale, int fixed, float* dur, int* cum, int* frames,
-                            int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, hipStream_t s, bool exact = false);
+// Per-utterance prosody: each of the three takes an optional device array next to its scalar (scales / length_scales / noise_scales [B]: utterance
+// b's value instead of the scalar; null = the scalar for every utterance, as before). launch_durations also takes optional override rows
+// ovr [B][tmax] (>= 0: the token's duration; -1: the prediction).
+hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, const float* scales, hipStream_t s);
+hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, int tmax, float length_scale, const float* length_scales, const int* ovr, int fixed,
+                            float* dur, int* cum, int* frames, int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, hipStream_t s,
+                            bool exact = false);
 hipError_t launch_zp(TensorRef mean, TensorRef logvar, const int* cum, int cum_stride, const int* tok_lens, const int* frames, TensorRef noise, int noise_kind,
-                     uint64_t seed, const int* seed_off, float noise_scale, TensorRef zp, int batch, int channels, int lmax, hipStream_t s);
+                     uint64_t seed, const int* seed_off, float noise_scale, const float* noise_scales, TensorRef zp, int batch, int channels, int lmax, hipStream_t s);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 // one segment of the effective-bias table of a multi-speaker model (built once at load): row 0 (speaker -1) = bias, row 1 + s =
 // bias + (cond_w . emb[s] + cond_b) for the n channels of the segment; cond_w is the conditioning 1x1 conv [n][E], emb [n_spk][E]

@@ -1594,47 +1594,56 @@ hipError_t launch_affine(TensorRef z, int c_first, const float* translate, const
     return hipGetLastError();
 }
 
-// duration latents: z[c][t] = N(0,1) * noise_scale_duration (vits.cpp:948-949), counter-based stream
-__global__ void noise_dur_kernel(float* z, int64_t z_bs, int z_cs, const int* lens, int tmax, uint64_t seed, const int* seed_off, float scale) {
+// duration latents: z[c][t] = N(0,1) * noise_scale_duration (vits.cpp:948-949), counter-based stream. scales (optional, device [B]): the
+// scale of utterance b instead of `scale` (per-utterance prosody); the draw itself does not depend on it
+__global__ void noise_dur_kernel(float* z, int64_t z_bs, int z_cs, const int* lens, int tmax, uint64_t seed, const int* seed_off, float scale, const float* scales) {
     const int b = blockIdx.z, c = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
     const int len = lens ? lens[b] : tmax;
     if (t >= len) return;
-    z[(int64_t)b * z_bs + (int64_t)c * z_cs + t] = vits_counter_normal(seed + (uint64_t)(seed_off ? seed_off[b] : b), VITS_STREAM_NOISE_DUR, (uint64_t)c * len + t) * scale;
+    const float sc = scales ? scales[b] : scale;  // (b = blockIdx.z: one value per block)
+    z[(int64_t)b * z_bs + (int64_t)c * z_cs + t] = vits_counter_normal(seed + (uint64_t)(seed_off ? seed_off[b] : b), VITS_STREAM_NOISE_DUR, (uint64_t)c * len + t) * sc;
 }
-hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, hipStream_t s) {
+hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, const float* scales, hipStream_t s) {
     dim3 grid((tmax + 63) / 64, 2, batch);
-    VITS_KLAUNCH(noise_dur_kernel, grid, dim3(64), 0, s, z.p, z.bs, z.cs, lens, tmax, seed, seed_off, scale);
+    VITS_KLAUNCH(noise_dur_kernel, grid, dim3(64), 0, s, z.p, z.bs, z.cs, lens, tmax, seed, seed_off, scale, scales);
     return hipGetLastError();
 }
 
-__global__ void scale_rows_kernel(float* x, int64_t bs, int cs, float scale, int tmax) {
+__global__ void scale_rows_kernel(float* x, int64_t bs, int cs, float scale, const float* scales, int tmax) {
     const int b = blockIdx.z, c = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= tmax) return;
-    x[(int64_t)b * bs + (int64_t)c * cs + t] *= scale;
+    x[(int64_t)b * bs + (int64_t)c * cs + t] *= scales ? scales[b] : scale;
 }
-hipError_t launch_scale_rows(TensorRef x, int channels, float scale, int batch, int tmax, hipStream_t s) {
+hipError_t launch_scale_rows(TensorRef x, int channels, float scale, const float* scales, int batch, int tmax, hipStream_t s) {
     dim3 grid((tmax + 63) / 64, channels, batch);
-    VITS_KLAUNCH(scale_rows_kernel, grid, dim3(64), 0, s, x.p, x.bs, x.cs, scale, tmax);
+    VITS_KLAUNCH(scale_rows_kernel, grid, dim3(64), 0, s, x.p, x.bs, x.cs, scale, scales, tmax);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // durations: d = ceil(exp(logw) * length_scale) (vits.cpp:996), per-utterance inclusive cumsum (:1001),
 // frames L = max(1, sum) (:999-1000,1133) and the per-stage vocoder lengths. One block per utterance.
+// Per-utterance prosody (optional device arrays): length_scales[b] replaces length_scale; ovr[b][t] >= 0 replaces the token's duration
+// before the sum, the cumulative sum and the dur write (ovr rows have the stride of dur, tmax).
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void durations_kernel(const float* logw, int64_t l_bs, int l_cs, int c, const int* lens, int tmax, float length_scale,
-                                                        int fixed, float* dur, int* cum, int* frames, int* stage_lens, int n_stage, const int* stage_mul,
-                                                        const int* stage_add, int batch, int exact) {
+                                                        const float* length_scales, const int* ovr, int fixed, float* dur, int* cum, int* frames,
+                                                        int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, int batch, int exact) {
     __shared__ int part[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int len = lens ? lens[b] : tmax;
     const int per = (tmax + 255) / 256;
     const int beg = tid * per, end = min(beg + per, len);
+    const float ls = length_scales ? length_scales[b] : length_scale;
     int s = 0;
     for (int t = beg; t < end; ++t) {
         const float lw = logw[(int64_t)b * l_bs + (int64_t)c * l_cs + t];
         // exact: the emulated-ggml mode — exp as the fixed polynomial both sides share (include/vits_exact_math.h) instead of the device library's
-        float d = exact ? vx_duration(lw, length_scale) : ceilf(expf(lw) * length_scale);
+        float d = exact ? vx_duration(lw, ls) : ceilf(expf(lw) * ls);
+        if (ovr) {
+            const int v = ovr[(int64_t)b * tmax + t];
+            if (v >= 0) d = (float)v;
+        }
         if (fixed > 0) d = (float)fixed;
         dur[(int64_t)b * tmax + t] = d;
         s += (int)d;
@@ -1689,10 +1698,10 @@ hipError_t launch_rb_sum3_std(TensorRef y0, TensorRef y1, TensorRef y2, TensorRe
     return hipGetLastError();
 }
 
-hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, int tmax, float length_scale, int fixed, float* dur, int* cum, int* frames,
-                            int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, hipStream_t s, bool exact) {
-    VITS_KLAUNCH(durations_kernel, dim3(batch), dim3(256), 0, s, logw.p, logw.bs, logw.cs, c, lens, tmax, length_scale, fixed, dur, cum, frames, stage_lens,
-                       n_stage, stage_mul, stage_add, batch, exact ? 1 : 0);
+hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, int tmax, float length_scale, const float* length_scales, const int* ovr, int fixed,
+                            float* dur, int* cum, int* frames, int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, hipStream_t s, bool exact) {
+    VITS_KLAUNCH(durations_kernel, dim3(batch), dim3(256), 0, s, logw.p, logw.bs, logw.cs, c, lens, tmax, length_scale, length_scales, ovr, fixed, dur, cum, frames,
+                       stage_lens, n_stage, stage_mul, stage_add, batch, exact ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1703,7 +1712,8 @@ hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, i
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void zp_kernel(const float* mean, int64_t m_bs, int m_cs, const float* logvar, int64_t v_bs, int v_cs, const int* cum,
                                                  int cum_stride, const int* tok_lens, const int* frames, const float* noise, int64_t n_bs, int n_cs,
-                                                 int noise_kind, uint64_t seed, const int* seed_off, float noise_scale, float* zp, int64_t z_bs, int z_cs, int channels, int tmax_tok) {
+                                                 int noise_kind, uint64_t seed, const int* seed_off, float noise_scale, const float* noise_scales, float* zp, int64_t z_bs,
+                                                 int z_cs, int channels, int tmax_tok) {
     __shared__ int tok[256];
     const int b = blockIdx.y, j0 = blockIdx.x * 256, tid = threadIdx.x;
     const int L = frames[b];
@@ -1724,6 +1734,7 @@ __global__ __launch_bounds__(256) void zp_kernel(const float* mean, int64_t m_bs
     __syncthreads();
     if (j >= L) return;
     const int a = tok[tid];
+    const float ns = noise_scales ? noise_scales[b] : noise_scale;  // (per-utterance prosody; b = blockIdx.y)
     // channels are split over blockIdx.z (every element is independent): one block per 256 frames walked all 192 channels
     // serially through the counter-based normal, 100 us at batch 1
     const int cpb = (channels + gridDim.z - 1) / gridDim.z;
@@ -1735,16 +1746,16 @@ __global__ __launch_bounds__(256) void zp_kernel(const float* mean, int64_t m_bs
         if (noise_kind == VITS_NOISE_COUNTER) e = vits_counter_normal(seed + (uint64_t)(seed_off ? seed_off[b] : b), VITS_STREAM_NOISE_PRIOR, (uint64_t)c * L + j);
         else e = noise[(int64_t)b * n_bs + (int64_t)c * n_cs + j];
         float n = e * expf(lv);  // vits.cpp:1060
-        n = n * noise_scale;     // :1061
+        n = n * ns;              // :1061
         zp[(int64_t)b * z_bs + (int64_t)c * z_cs + j] = mu + n;
     }
 }
 
 hipError_t launch_zp(TensorRef mean, TensorRef logvar, const int* cum, int cum_stride, const int* tok_lens, const int* frames, TensorRef noise, int noise_kind,
-                     uint64_t seed, const int* seed_off, float noise_scale, TensorRef zp, int batch, int channels, int lmax, hipStream_t s) {
+                     uint64_t seed, const int* seed_off, float noise_scale, const float* noise_scales, TensorRef zp, int batch, int channels, int lmax, hipStream_t s) {
     dim3 grid((lmax + 255) / 256, batch, 16);
     VITS_KLAUNCH(zp_kernel, grid, dim3(256), 0, s, mean.p, mean.bs, mean.cs, logvar.p, logvar.bs, logvar.cs, cum, cum_stride, tok_lens, frames, noise.p,
-                       noise.bs, noise.cs, noise_kind, seed, seed_off, noise_scale, zp.p, zp.bs, zp.cs, channels, cum_stride);
+                       noise.bs, noise.cs, noise_kind, seed, seed_off, noise_scale, noise_scales, zp.p, zp.bs, zp.cs, channels, cum_stride);
     return hipGetLastError();
 }
 
