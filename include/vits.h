@@ -272,6 +272,46 @@ VITS_API int vits_model_convert_batch(vits_model* model, const float* pcm, const
 /* One utterance; the model's default mode and the reference noise stream, like vits_model_process. */
 VITS_API vits_result vits_model_convert(vits_model* model, const float* pcm, size_t n, int32_t src_speaker, int32_t tgt_speaker);
 
+/* ---- forced alignment: token timings of recorded speech ----------------------------------------------------------------------
+ * VITS's own monotonic alignment search (the one it is trained with: SynthesizerTrn.forward, monotonic_align.maximum_path) between the
+ * text encoder's prior statistics per token and z_p of a recording. Per utterance b, T = id_lengths[b] tokens, L = floor(N_b / hop) frames:
+ *   m, ls  = the prior mean and log-deviation per token, exactly as vits_model_process_batch computes them for these ids (taps
+ *            "prior_mean", "prior_logvar"; the text encoder takes no speaker term)
+ *   z      = z_p exactly as vits_model_convert_batch computes it for this PCM with src = speakers[b], except that the posterior draw
+ *            is z_q = mean + noise_scale * eps * exp(log_std): 1 = VITS's training draw (the conversion's z_q bit for bit), 0 = the
+ *            posterior mean (deterministic: no noise is drawn, whatever the noise fields say)
+ *   logp[t][j] = sum_c(-0.5 log 2pi - ls[c][t]) - 0.5 sum_c (z[c][j] - m[c][t])^2 exp(-2 ls[c][t]), in fp32 in every arithmetic mode
+ *   v[y][x] = logp[x][y] + max(v[y-1][x-1], v[y-1][x]) over the band max(0, T + y - L) <= x <= min(T - 1, y) (-1e9 outside, v[-1][-1] = 0);
+ *            the path is read back from (L - 1, T - 1), stepping down a token iff x == y or v[y-1][x] < v[y-1][x-1] (a tie stays)
+ * durations[b][t] = frames of token t (>= 1 each, summing to frames[b]; 0 past id_lengths[b]); scores[b] = v[L-1][T-1], the
+ * log-likelihood of the best path. The durations are what opts.duration_override of vits_model_process_batch takes: "say this text with
+ * the rhythm of that recording". No duration predictor, reverse flow or vocoder runs, and the reference noise stream is advanced by
+ * the posterior draw only (not at all with noise_scale 0).
+ * Options: mode, the noise fields and collect_taps mean what they mean for vits_model_convert_batch; fixed_duration, frames_only, async,
+ * out_device, skip_host_copy, vocoder_chunk_frames, on_chunk, speaker_ids and the five prosody fields are refused, as are a noise_scale
+ * that is not finite or outside [0, 10], a speaker outside the model's range, a file without a posterior encoder, batches in flight and
+ * an utterance with more tokens than frames (no monotonic path exists; the message names the utterance, its tokens and its frames).
+ * vits_model_set_ggml_tables mode 1 governs the duration predictor's stage one only, which an alignment never runs: it is ignored here,
+ * as in conversion. The first alignment prepares the conversion weights (vits_model_prepare_conversion) if nothing did before.
+ * Taps (collect_taps): "prior_mean", "prior_logvar" [F][T]; "spec", "post_mean", "post_logstd", "z_q", "z_p" as in conversion;
+ * "align_logp" [T][L]; "align_path" [L]: the token index of every frame, as floats. Returns 0, or -1 + message. */
+VITS_API int vits_model_align_batch(vits_model* model,
+        const float* pcm, const int64_t* pcm_lengths, int32_t batch, int64_t pcm_stride,   /* as vits_model_convert_batch */
+        const int32_t* ids, const int32_t* id_lengths, int32_t id_stride,                  /* as vits_model_process_batch */
+        const int32_t* speakers,        /* host [B] or NULL (= -1 everywhere): the speaker of the recording (posterior encoder, forward flow) */
+        float noise_scale,              /* scale of the posterior draw: 1 = VITS's training draw, 0 = the posterior mean (deterministic) */
+        const vits_process_opts* opts,  /* mode, noise fields, collect_taps; everything else refused, see above */
+        int32_t* durations,             /* out, host [B][id_stride]: frames per token, 0 past id_lengths[b]; sums to frames[b] */
+        int64_t* frames,                /* out, host [B], optional */
+        float* scores);                 /* out, host [B], optional: log-likelihood of the best path */
+/* One utterance from text, through the model's tokenizer; the posterior mean (noise_scale 0). Writes up to cap ids and durations,
+ * returns the token count, -1 on failure. Phonetic models refuse as the other text entry points do. */
+VITS_API int64_t vits_model_align(vits_model* model, const float* pcm, size_t n, const char* text, int32_t speaker,
+                                  int32_t* ids, int32_t* durations, size_t cap);
+/* Samples per frame (the product of the vocoder's upsample rates = the STFT hop): token t of an alignment starts at
+ * sum(durations[0 .. t)) * hop / sampling_rate seconds. */
+VITS_API int32_t vits_model_hop(const vits_model* model);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -386,6 +426,12 @@ VITS_API int vits_op_rel_attention(int32_t batch, int32_t heads, int32_t head_di
 VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, int32_t t_stride, float eps,
                                     const float* x, const float* residual, const float* gamma, const float* beta,
                                     float* y);
+
+/* The alignment kernels (align_logp + align_mas; see vits_model_align_batch) on caller-supplied statistics: m, ls host [batch][F][Tmax] (prior mean and
+ * log-deviation per token), z host [batch][F][Lmax], Tmax = max T[b], Lmax = max L[b], 1 <= T[b] <= L[b]. durations: out, host [batch][Tmax] (0 past
+ * T[b]); scores: out, host [batch], optional. */
+VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, int32_t F, const float* m, const float* ls, const float* z,
+                           int32_t* durations, float* scores);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

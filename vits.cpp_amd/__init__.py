@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
     "vits_model_set_prosody", "vits_model_get_prosody",
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
+    "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -165,6 +166,14 @@ def lib():
     L.vits_model_convert_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, C.POINTER(ProcessOpts), C.POINTER(BatchResult)]
     L.vits_model_convert.restype = VitsResult
     L.vits_model_convert.argtypes = [vp, vp, C.c_size_t, i32, i32]
+    L.vits_model_align_batch.restype = i32
+    L.vits_model_align_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32, vp, C.c_float, C.POINTER(ProcessOpts), vp, vp, vp]
+    L.vits_model_align.restype = i64
+    L.vits_model_align.argtypes = [vp, vp, C.c_size_t, C.c_char_p, i32, vp, vp, C.c_size_t]
+    L.vits_model_hop.restype = i32
+    L.vits_model_hop.argtypes = [vp]
+    L.vits_op_align.restype = i32
+    L.vits_op_align.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -627,6 +636,95 @@ class Model:
         finally:
             lib().vits_free_result(r)
 
+    def align_batch(self, pcm, ids, lengths=None, id_lengths=None, speakers=-1, noise_scale=0.0, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER,
+                    noise_seed=4321, noise_prior=None, collect_taps=False, noise_seed_offsets=None, **refused):
+        """Forced alignment (vits_model_align_batch): which frames of each recording belong to which token of its transcript, by VITS's monotonic
+        alignment search. pcm: float32 [B, stride] (or one 1-D utterance), lengths: valid samples per row; ids: int32 [B, id_stride] (or 1-D),
+        id_lengths: tokens per row; speakers: the speaker of the recordings, one int or one per utterance (-1 = none); noise_scale: scale of the
+        posterior draw (0 = the posterior mean, deterministic; 1 = VITS's training draw). Returns (durations int32 [B, id_stride]: frames per token,
+        0 past id_lengths[b]; frames int64 [B]; scores float32 [B]: log-likelihood of the best path). durations is what process_batch takes as
+        duration_override. Keyword arguments the call refuses (those of convert_batch, and out_device, skip_host_copy, vocoder_chunk_frames) are
+        passed on, so that the library says why."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        B, stride = pcm.shape
+        if ids.shape[0] != B:
+            raise ValueError("pcm and ids need one row per utterance each")
+        id_stride = ids.shape[1]
+        lens = np.full(B, stride, np.int64) if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64).ravel()
+        ilens = np.full(B, id_stride, np.int32) if id_lengths is None else np.ascontiguousarray(id_lengths, dtype=np.int32).ravel()
+        if lens.size != B or ilens.size != B:
+            raise ValueError("lengths and id_lengths need one entry per utterance")
+        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(speakers, np.int32), (B,)))
+        o = ProcessOpts()
+        o.struct_size = C.sizeof(ProcessOpts)
+        o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
+        npr = _f32(noise_prior)
+        o.noise_prior = _ptr(npr)
+        o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
+        o.collect_taps = int(collect_taps)
+        o.out_device = refused.pop("out_device", None)
+        o.skip_host_copy = int(refused.pop("skip_host_copy", False))
+        o.vocoder_chunk_frames = int(refused.pop("vocoder_chunk_frames", 0))
+        o.fixed_duration = int(refused.pop("fixed_duration", 0))
+        o.frames_only = int(refused.pop("frames_only", False))
+        o.async_ = int(refused.pop("async_", False))
+        on_chunk = refused.pop("on_chunk", None)
+        if on_chunk is not None:
+            o.on_chunk = ChunkCallback(lambda _user, utt, offset, p, n: 1)  # (refused before anything could call it)
+        spk = refused.pop("speaker_ids", None)
+        keep = []
+        for arg, field, dtype in (("speaking_rate", "speaking_rates", np.float32), ("noise_scales", "noise_scales", np.float32),
+                                  ("noise_scale_duration", "noise_scale_durations", np.float32), ("duration_override", "duration_override", np.int32),
+                                  ("durations_out", "durations_out", np.int32)):
+            v = refused.pop(arg, None)
+            if v is not None:
+                keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype).ravel(), (max(B, np.size(v)),))))
+                setattr(o, field, _ptr(keep[-1]))
+        if refused:
+            raise TypeError("unknown arguments: %s" % sorted(refused))
+        spk = None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()
+        o.speaker_ids = _ptr(spk)
+        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
+        if nso is not None and nso.size != B:
+            raise ValueError("noise_seed_offsets needs one entry per utterance")
+        o.noise_seed_offsets = _ptr(nso)
+        durations = np.zeros((B, id_stride), np.int32)
+        frames = np.zeros(B, np.int64)
+        scores = np.zeros(B, np.float32)
+        if lib().vits_model_align_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(ids), _ptr(ilens), id_stride, _ptr(sp), float(noise_scale),
+                                        C.byref(o), _ptr(durations), _ptr(frames), _ptr(scores)) != 0:
+            raise VitsError(last_error())
+        return durations, frames, scores
+
+    def align(self, pcm, text, speaker=-1):
+        """vits_model_align: one utterance from text through the model's tokenizer, the posterior mean. Returns (ids, durations)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
+        raw = text.encode() if isinstance(text, str) else bytes(text)
+        cap = 2 * len(raw) + 8
+        ids = np.zeros(cap, np.int32)
+        durations = np.zeros(cap, np.int32)
+        n = lib().vits_model_align(self._h, _ptr(pcm), pcm.size, raw, int(speaker), _ptr(ids), _ptr(durations), cap)
+        if n < 0:
+            raise VitsError(last_error())
+        if n > cap:  # (cannot happen with a tokenizer that emits at most one id and one blank per byte; ask again rather than truncate)
+            cap = int(n)
+            ids = np.zeros(cap, np.int32)
+            durations = np.zeros(cap, np.int32)
+            n = lib().vits_model_align(self._h, _ptr(pcm), pcm.size, raw, int(speaker), _ptr(ids), _ptr(durations), cap)
+            if n < 0:
+                raise VitsError(last_error())
+        return ids[:n].copy(), durations[:n].copy()
+
+    @property
+    def hop(self):
+        """samples per frame (vits_model_hop)"""
+        return int(lib().vits_model_hop(self._h))
+
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
                      skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None,
                      noise_scale_duration=None, duration_override=None, durations_out=None):
@@ -710,6 +808,15 @@ class Model:
         return json.loads(buf.value.decode())
 
 
+def durations_to_seconds(durations, model):
+    """Start and end of every token in seconds from an alignment's durations (frames per token; 1-D, or [B, T] row by row): cumulative frames
+    x hop / sampling rate. Returns (starts, ends), float64, shaped like durations."""
+    d = np.asarray(durations, np.int64)
+    ends = np.cumsum(d, axis=-1)
+    scale = model.hop / float(model.sampling_rate)
+    return (ends - d) * scale, ends * scale
+
+
 # ---- operator-level wrappers (parity tests) ----------------------------------------------------------
 def op_set_arith(arith):
     """Arithmetic of op_conv1d / op_conv_transpose1d on this thread (ARITH_F32 | ARITH_BF16 | ARITH_F16)."""
@@ -746,6 +853,23 @@ def op_conv_transpose1d(x, w, bias, stride, crop, pre_slope=1.0, lens=None):
     if lib().vits_op_conv_transpose1d(C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
+
+
+def op_align(m, ls, z, T=None, L=None):
+    """align_logp + align_mas on caller-supplied statistics (vits_op_align). m, ls: [B, F, Tmax]; z: [B, F, Lmax]; T, L: per-utterance token /
+    frame counts (None = the whole rows). Returns (durations int32 [B, Tmax], scores float32 [B])."""
+    m, ls, z = (np.ascontiguousarray(a, dtype=np.float32) for a in (m, ls, z))
+    B, F, tmax = m.shape
+    lmax = z.shape[2]
+    T = np.full(B, tmax, np.int32) if T is None else np.ascontiguousarray(T, dtype=np.int32)
+    L = np.full(B, lmax, np.int32) if L is None else np.ascontiguousarray(L, dtype=np.int32)
+    if ls.shape != m.shape or z.shape[:2] != (B, F) or T.size != B or L.size != B or int(T.max()) != tmax or int(L.max()) != lmax:
+        raise ValueError("op_align: m, ls [B, F, max T]; z [B, F, max L]")
+    d = np.zeros((B, tmax), np.int32)
+    sc = np.zeros(B, np.float32)
+    if lib().vits_op_align(B, _ptr(T), _ptr(L), F, _ptr(m), _ptr(ls), _ptr(z), _ptr(d), _ptr(sc)) != 0:
+        raise VitsError(last_error())
+    return d, sc
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

@@ -343,6 +343,63 @@ VITS_API int vits_model_convert_batch(vits_model* model, const float* pcm, const
     VITS_CATCH(-1)
 }
 
+VITS_API int vits_model_align_batch(vits_model* model, const float* pcm, const int64_t* pcm_lengths, int32_t batch, int64_t pcm_stride, const int32_t* ids,
+                                    const int32_t* id_lengths, int32_t id_stride, const int32_t* speakers, float noise_scale, const vits_process_opts* opts,
+                                    int32_t* durations, int64_t* frames, float* scores) {
+    VITS_TRY
+    if (!model || !pcm || !pcm_lengths || !ids || !durations) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    vits_process_opts o;
+    std::memset(&o, 0, sizeof(o));
+    o.mode = VITS_MODE_DEFAULT;
+    o.noise_kind = VITS_NOISE_COUNTER;
+    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
+    std::string err;
+    const int rc = model->eng.align_batch(pcm, pcm_lengths, batch, pcm_stride, ids, id_lengths, id_stride, speakers, noise_scale, o, durations, frames, scores, err);
+    if (rc != 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+
+VITS_API int64_t vits_model_align(vits_model* model, const float* pcm, size_t n, const char* text, int32_t speaker, int32_t* ids, int32_t* durations, size_t cap) {
+    VITS_TRY
+    if (!model || !pcm || !text || n == 0 || (cap && (!ids || !durations))) {
+        set_err(n == 0 && model && pcm && text ? "empty input (no samples)" : "null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    std::vector<int32_t> v;
+    std::string err;
+    if (!model->eng.tok.tokenize_checked(text, v, err)) {
+        set_err(err);
+        return -1;
+    }
+    if (v.empty()) {
+        set_err("empty input (no ids)");
+        return -1;
+    }
+    vits_process_opts o;
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.mode = VITS_MODE_DEFAULT;
+    o.noise_kind = VITS_NOISE_COUNTER;  // (noise_scale 0: nothing is drawn)
+    std::vector<int32_t> d(v.size(), 0);
+    const int64_t len = (int64_t)n;
+    if (model->eng.align_batch(pcm, &len, 1, len, v.data(), nullptr, (int)v.size(), &speaker, 0.f, o, d.data(), nullptr, nullptr, err) != 0) {
+        set_err(err);
+        return -1;
+    }
+    for (size_t i = 0; i < v.size() && i < cap; ++i) {
+        ids[i] = v[i];
+        durations[i] = d[i];
+    }
+    return (int64_t)v.size();
+    VITS_CATCH(-1)
+}
+
 VITS_API vits_result vits_model_convert(vits_model* model, const float* pcm, size_t n, int32_t src_speaker, int32_t tgt_speaker) {
     vits_result r{nullptr, 0};
     VITS_TRY
@@ -457,6 +514,12 @@ VITS_API int64_t vits_model_tokenize(vits_model* model, const char* text, int32_
 }
 
 VITS_API int32_t vits_model_sampling_rate(const vits_model* model) { return model ? model->eng.hp.sampling_rate : 0; }
+VITS_API int32_t vits_model_hop(const vits_model* model) {
+    if (!model) return 0;
+    int hop = 1;
+    for (int r : model->eng.hp.up_rates) hop *= r;
+    return hop;
+}
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 
@@ -864,6 +927,57 @@ VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, int32_t F, const float* m, const float* ls, const float* z, int32_t* durations,
+                           float* scores) {
+    VITS_TRY
+    using namespace vits;
+    if (batch <= 0 || !T || !L || F <= 0 || !m || !ls || !z || !durations) return fail("null argument or empty batch");
+    int tmax = 0, lmax = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (T[b] < 1 || T[b] > L[b]) return fail("vits_op_align: 1 <= T[b] <= L[b] is required");
+        tmax = std::max(tmax, T[b]);
+        lmax = std::max(lmax, L[b]);
+    }
+    if (tmax > 4096) return fail("vits_op_align: at most 4096 tokens");
+    const int ts = (tmax + 31) / 32 * 32, lstr = (lmax + 31) / 32 * 32;
+    const size_t bit_words = align_mas_bits_in_lds(tmax, lmax) ? 0 : align_mas_bits_words(tmax, lmax);
+    DevBuf dm, ds, dz, da, dq, dc, dlp, dbits, dscore;
+    DevInts dt, dl, ddur;
+    if (!dm.put(m, (size_t)batch * F * tmax) || !ds.put(ls, (size_t)batch * F * tmax) || !dz.put(z, (size_t)batch * F * lmax) ||
+        !da.put(nullptr, (size_t)batch * 2 * F * ts) || !dq.put(nullptr, (size_t)batch * 2 * F * lstr) || !dc.put(nullptr, (size_t)batch * ts) ||
+        !dlp.put(nullptr, (size_t)batch * ts * lstr) || !dbits.put(nullptr, (size_t)batch * bit_words * 2) || !dscore.put(nullptr, batch) || !dt.put(T, batch) ||
+        !dl.put(L, batch) || hipMalloc((void**)&ddur.p, (size_t)batch * tmax * 4) != hipSuccess)
+        return fail("device allocation failed");
+    AlignCall c;
+    c.mean = tref(dm.p, F, tmax);
+    c.logs = tref(ds.p, F, tmax);
+    c.z = tref(dz.p, F, lmax);
+    c.tlens = dt.p;
+    c.frames = dl.p;
+    c.channels = F;
+    c.batch = batch;
+    c.tmax = tmax;
+    c.lmax = lmax;
+    c.t_stride = ts;
+    c.l_stride = lstr;
+    c.plane_a = da.p;
+    c.plane_z = dq.p;
+    c.ct = dc.p;
+    c.logp = dlp.p;
+    c.bits = bit_words ? reinterpret_cast<unsigned long long*>(dbits.p) : nullptr;
+    c.dur = ddur.p;
+    c.dur_stride = tmax;
+    c.score = dscore.p;
+    hipError_t e = launch_align_logp(c, nullptr);
+    if (e == hipSuccess) e = launch_align_mas(c, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(durations, ddur.p, (size_t)batch * tmax * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    if (scores && hipMemcpy(scores, dscore.p, (size_t)batch * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     return 0;
     VITS_CATCH(-1)
 }

@@ -85,7 +85,8 @@ struct Arena {
 struct Tap {
     float* dev = nullptr;  // snapshot [batch][channels][stride]
     int channels = 0, stride = 0;
-    std::vector<int> lens;  // per utterance
+    std::vector<int> lens;   // per utterance
+    std::vector<int> chans;  // per utterance channel counts (align_logp: [T_b][L_b]); empty = `channels` for every utterance
 };
 
 struct EncoderLayerW {
@@ -197,6 +198,10 @@ class Engine {
     int prepare_conversion(std::string& err);
     int convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
                       vits_batch_result* out, std::string& err);
+    // forced alignment (engine_align.cpp, include/vits.h vits_model_align_batch): text encoder (prior statistics per token) + the conversion front end (z_p of
+    // the recording) -> align_logp -> align_mas (align.hip); durations [B][id_stride], frames [B] (optional), scores [B] (optional) on the host
+    int align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* ids, const int32_t* id_lens, int id_stride,
+                    const int32_t* speakers, float noise_scale, const vits_process_opts& o, int32_t* durations, int64_t* frames, float* scores, std::string& err);
     // speaker conditioning (multi-speaker models): the speaker of utterances the call does not name (vits_process_opts::speaker_ids == NULL,
     // vits_model_process / _ids); -1 = none
     int speaker = -1;
@@ -337,6 +342,8 @@ class Engine {
     void* pinned_ = nullptr;   // grow-only pinned staging for streamed PCM
     int* frames_host_ = nullptr;  // pinned [frames_host_cap_]: destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
     size_t frames_host_cap_ = 0;
+    int* align_host_ = nullptr;  // pinned [align_host_cap_]: durations and scores of an alignment call (engine_align.cpp)
+    size_t align_host_cap_ = 0;
     float* dur_host_ = nullptr;  // pinned: a synchronous call's durations for opts.durations_out, copied beside the frame counts
     size_t dur_host_cap_ = 0;    // floats
     size_t pinned_cap_ = 0;
@@ -405,6 +412,9 @@ class Engine {
     int run_flow(Call& c) { return run_coupling(c, false); }
     int run_coupling(Call& c, bool forward);  // the residual coupling flow: reverse (TTS), or forward (voice conversion)
     int run_conversion_front(Call& c);        // spectrogram -> posterior encoder -> forward flow (engine_convert.cpp)
+    // the PCM side of a conversion or alignment call (engine_convert.cpp): lengths checked, then frame counts, arena (current stage-one slot), uploads
+    int check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::string& err) const;
+    int layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax);
     int run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async);
     // a tap of a tensor held with its channels reversed (the flow's physical layout for an odd number of coupling layers)
     void snapshot_flipped(const char* name, TensorRef t, int channels, int stride, int batch, const std::vector<int>& lens);

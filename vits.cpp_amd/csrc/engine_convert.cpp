@@ -136,55 +136,10 @@ int Engine::prepare_conversion(std::string& err) {
     return 0;
 }
 
-// ---- one conversion call -------------------------------------------------------------------------------------------------------
-int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
-                          vits_batch_result* out, std::string& err) {
-    if (pending()) {
-        err = "batches in flight: call vits_model_wait for every submitted batch first";
-        return -1;
-    }
-    if (B <= 0 || !pcm || !pcm_lens || pcm_stride <= 0) {
-        err = B <= 0 ? "empty batch" : "null PCM, null lengths or pcm_stride <= 0";
-        return -1;
-    }
-    if (o.fixed_duration > 0 || o.frames_only || o.async) {
-        err = std::string("voice conversion does not take ") + (o.fixed_duration > 0 ? "fixed_duration" : o.frames_only ? "frames_only" : "async") +
-              " (the frame counts come from the input PCM; the call is synchronous)";
-        return -1;
-    }
-    if (o.speaker_ids) {
-        err = "voice conversion takes its speakers from src_speakers and tgt_speakers, not from opts.speaker_ids";
-        return -1;
-    }
-    if (o.speaking_rates || o.noise_scales || o.noise_scale_durations || o.duration_override || o.durations_out) {
-        err = std::string("voice conversion does not take opts.") +
-              (o.speaking_rates ? "speaking_rates" : o.noise_scales ? "noise_scales" : o.noise_scale_durations ? "noise_scale_durations" : o.duration_override ? "duration_override" : "durations_out") +
-              " (it has no duration prediction, and the posterior draw has no noise scale)";
-        return -1;
-    }
-    if (o.on_chunk && o.skip_host_copy) {
-        err = "on_chunk needs a host copy (skip_host_copy = 0)";
-        return -1;
-    }
-    for (int b = 0; b < B; ++b)
-        for (int side = 0; side < 2; ++side) {
-            const int32_t* arr = side ? tgt : src;
-            const int s = arr ? arr[b] : -1;
-            if (s == -1) continue;
-            const std::string who = std::string(side ? "tgt_speakers[" : "src_speakers[") + std::to_string(b) + "] = " + std::to_string(s) + " (" +
-                                    (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
-            if (hp.num_speakers <= 1) {
-                err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
-                return -1;
-            }
-            if (s < -1 || s >= hp.num_speakers) {
-                err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
-                return -1;
-            }
-        }
-    if (prepare_conversion(err)) return -1;
+// the PCM side of a call (conversion and alignment): every utterance inside its row, at least one hop and more than the reflection pad; nmax = the longest
+int Engine::check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::string& err) const {
     const int hop = hop_, pad = stft_pad_, min_n = std::max(hop, pad + 1);
-    int64_t nmax = 0;
+    nmax = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t n = pcm_lens[b];
         if (n > pcm_stride) {
@@ -202,16 +157,16 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
         }
         nmax = std::max(nmax, n);
     }
-    a1_slot_ = 0;
-    Call c(o, err, nullptr, B, 0);
-    Call::Vc vc;
-    c.vc = &vc;
-    c.md = o.mode == VITS_MODE_DEFAULT ? mode : o.mode;
-    c.refmode = c.md == VITS_MODE_REFERENCE;
-    const int n_up = c.n_up = (int)ups_.size();
-    clear_taps();
-    tap_batch_ = B;
-    arith_now_ = arith_kernels();
+    return 0;
+}
+
+// frame counts, vocoder stage lengths and the call's own arena (the current stage-one slot): header ints | PCM | spectrogram | posterior statistics;
+// uploads the header and the PCM. Leaves c.s1.lens / frames / stage_lens / seed_off pointing into that header.
+int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    Call::Vc& vc = *c.vc;
+    const int B = c.B, hop = hop_, n_up = c.n_up;
     // frame counts and vocoder stage lengths, all on the host (spectrogram_torch: floor(N / hop) frames)
     std::vector<int>& frames = c.frames;
     frames.resize(B);
@@ -239,7 +194,7 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
             c.slen[i][b] = frames[b] * smul[i] + sadd[i];
             c.smax[i] = std::max(c.smax[i], c.slen[i][b]);
         }
-    // ---- the call's own arena (stage-one slot 0): header ints | PCM | spectrogram | posterior statistics ----------------------
+    // ---- the call's own arena (the current stage-one slot): header ints | PCM | spectrogram | posterior statistics ----------------------
     const int ls = round_up(c.Lmax, 32), bins = hp.spec_bins, F = hp.flow_size;
     const int64_t pstride = round_up((int)nmax, 64);
     const size_t hdr_ints = (size_t)(n_up + 1) * B + 4 * (size_t)B;
@@ -287,6 +242,69 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
     }
     c.s1.lens = c.s1.stage_lens;  // (frames per utterance = stage-0 lengths)
     c.s1.frames = c.s1.stage_lens;
+    return 0;
+}
+
+// ---- one conversion call -------------------------------------------------------------------------------------------------------
+int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
+                          vits_batch_result* out, std::string& err) {
+    if (pending()) {
+        err = "batches in flight: call vits_model_wait for every submitted batch first";
+        return -1;
+    }
+    if (B <= 0 || !pcm || !pcm_lens || pcm_stride <= 0) {
+        err = B <= 0 ? "empty batch" : "null PCM, null lengths or pcm_stride <= 0";
+        return -1;
+    }
+    if (o.fixed_duration > 0 || o.frames_only || o.async) {
+        err = std::string("voice conversion does not take ") + (o.fixed_duration > 0 ? "fixed_duration" : o.frames_only ? "frames_only" : "async") +
+              " (the frame counts come from the input PCM; the call is synchronous)";
+        return -1;
+    }
+    if (o.speaker_ids) {
+        err = "voice conversion takes its speakers from src_speakers and tgt_speakers, not from opts.speaker_ids";
+        return -1;
+    }
+    if (o.speaking_rates || o.noise_scales || o.noise_scale_durations || o.duration_override || o.durations_out) {
+        err = std::string("voice conversion does not take opts.") +
+              (o.speaking_rates ? "speaking_rates" : o.noise_scales ? "noise_scales" : o.noise_scale_durations ? "noise_scale_durations" : o.duration_override ? "duration_override" : "durations_out") +
+              " (it has no duration prediction, and the posterior draw has no noise scale)";
+        return -1;
+    }
+    if (o.on_chunk && o.skip_host_copy) {
+        err = "on_chunk needs a host copy (skip_host_copy = 0)";
+        return -1;
+    }
+    for (int b = 0; b < B; ++b)
+        for (int side = 0; side < 2; ++side) {
+            const int32_t* arr = side ? tgt : src;
+            const int s = arr ? arr[b] : -1;
+            if (s == -1) continue;
+            const std::string who = std::string(side ? "tgt_speakers[" : "src_speakers[") + std::to_string(b) + "] = " + std::to_string(s) + " (" +
+                                    (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
+            if (hp.num_speakers <= 1) {
+                err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
+                return -1;
+            }
+            if (s < -1 || s >= hp.num_speakers) {
+                err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+                return -1;
+            }
+        }
+    if (prepare_conversion(err)) return -1;
+    int64_t nmax = 0;
+    if (check_conversion_pcm(pcm_lens, B, pcm_stride, nmax, err)) return -1;
+    a1_slot_ = 0;
+    Call c(o, err, nullptr, B, 0);
+    Call::Vc vc;
+    c.vc = &vc;
+    c.md = o.mode == VITS_MODE_DEFAULT ? mode : o.mode;
+    c.refmode = c.md == VITS_MODE_REFERENCE;
+    c.n_up = (int)ups_.size();
+    clear_taps();
+    tap_batch_ = B;
+    arith_now_ = arith_kernels();
+    if (layout_conversion(c, pcm, pcm_lens, pcm_stride, src, tgt, nmax)) return -1;
     return run_stage_two(c, out, nullptr, false);
 }
 
@@ -407,7 +425,7 @@ int Engine::run_conversion_front(Call& c) {
     }
     // eps: the [F][L] draw prior sampling would make (engine_flow.cpp run_prior_sampling), then z_q — in the forward flow's physical input layout
     TensorRef zp = TR(s2.zp, F, ls), noise = TR(s2.noise, F, ls);
-    if (o.noise_kind != VITS_NOISE_COUNTER) {
+    if (o.noise_kind != VITS_NOISE_COUNTER && vc.eps_scale != 0.f) {  // (scale 0 = the posterior mean: no noise drawn, uploaded or read)
         std::vector<float> hn((size_t)B * F * ls, 0.f);
         for (int b = 0; b < B; ++b) {
             const int L = frames[b];
@@ -431,7 +449,7 @@ int Engine::run_conversion_front(Call& c) {
     }
     const int nk = o.noise_kind == VITS_NOISE_COUNTER ? VITS_NOISE_COUNTER : VITS_NOISE_EXPLICIT;
     prof.begin("posterior_sample", 0, 0, stream, true);
-    HIP_OK(launch_posterior_sample(stats, sub(stats, F), ll, noise, nk, o.noise_seed, c.s1.seed_off, zp, B, F, Lmax, hp.n_flows % 2, stream));
+    HIP_OK(launch_posterior_sample(stats, sub(stats, F), ll, noise, nk, o.noise_seed, c.s1.seed_off, zp, B, F, Lmax, hp.n_flows % 2, stream, vc.eps_scale));
     prof.end(stream);
     if (o.collect_taps) {
         // (the logical z_q: with an odd layer count zp holds it reversed)

@@ -1,6 +1,7 @@
 // engine_internal.h — shared by the engine's translation units only (engine.cpp: one call from ids to PCM; engine_load.cpp:
 // weights; engine_stage1.cpp: text encoder + duration predictor; engine_flow.cpp: prior sampling + coupling flow;
-// engine_vocoder.cpp: HiFiGAN; engine_support.cpp: profiler, arenas, tokenizer, noise, roctx ranges).
+// engine_vocoder.cpp: HiFiGAN; engine_convert.cpp / engine_align.cpp: voice conversion and forced alignment; engine_support.cpp: profiler, arenas,
+// tokenizer, noise, roctx ranges).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -121,6 +122,7 @@ struct Call {
         int* nsamp = nullptr;  // device [B]
         int64_t pcm_stride = 0;
         const int *spk_src = nullptr, *spk_tgt = nullptr;  // device [B] effective-bias rows, or null (every utterance -1)
+        float eps_scale = 1.f;  // scale of the posterior draw (alignment's noise_scale; conversion: 1, VITS's draw)
     };
     Vc* vc = nullptr;
 

@@ -27,6 +27,7 @@ Engine::~Engine() {
     }
     if (pinned_) hipHostFree(pinned_);
     if (frames_host_) hipHostFree(frames_host_);
+    if (align_host_) hipHostFree(align_host_);
     if (dur_host_) hipHostFree(dur_host_);
     for (HStage& hs : hstage_) {
         if (hs.p) hipHostFree(hs.p);
@@ -686,13 +687,14 @@ int64_t Engine::get_tap(const char* name, int utt, float* dst, size_t cap) {
     if (it == taps_.end() || utt < 0 || utt >= tap_batch_) return 0;
     const Tap& tp = it->second;
     const int len = tp.lens[utt];
-    const int64_t n = (int64_t)tp.channels * len;
+    const int nch = tp.chans.empty() ? tp.channels : tp.chans[utt];
+    const int64_t n = (int64_t)nch * len;
     if (dst && cap) {
         hipStreamSynchronize(stream);
         std::vector<float> host((size_t)tp.channels * tp.stride);
         hipMemcpy(host.data(), tp.dev + (size_t)utt * tp.channels * tp.stride, host.size() * 4, hipMemcpyDeviceToHost);
         size_t w = 0;
-        for (int c = 0; c < tp.channels && w < cap; ++c)
+        for (int c = 0; c < nch && w < cap; ++c)
             for (int t = 0; t < len && w < cap; ++t) dst[w++] = host[(size_t)c * tp.stride + t];
     }
     return n;

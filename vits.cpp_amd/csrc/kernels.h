@@ -530,9 +530,31 @@ struct SpectrogramCall {
     TensorRef out;
 };
 hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s);
-// z_q = mean + eps * exp(log_std) over [0, frames[b]) (eps: the counter stream of prior sampling, or `noise`); flip: channel c -> row channels - 1 - c
+// z_q = mean + (eps * eps_scale) * exp(log_std) over [0, frames[b]) (eps: the counter stream of prior sampling, or `noise`; eps_scale 1 is VITS's draw
+// (eps * 1.0f is exact), 0 the posterior mean: no noise is drawn or read then); flip: channel c -> row channels - 1 - c
 hipError_t launch_posterior_sample(TensorRef mean, TensorRef logstd, const int* frames, TensorRef noise, int noise_kind, uint64_t seed, const int* seed_off,
-                                   TensorRef zq, int batch, int channels, int lmax, int flip, hipStream_t s);
+                                   TensorRef zq, int batch, int channels, int lmax, int flip, hipStream_t s, float eps_scale = 1.0f);
+// Forced alignment (align.hip). launch_align_logp: logp [b][t_stride][l_stride] (fp32, entries t < tlens[b], j < frames[b]) from the prior statistics per
+// token (mean, logs: [b][channels][t]) and z_p (z: [b][channels][j]) through the operand planes plane_a / plane_z ([b][2 channels][t_stride | l_stride]) and
+// ct ([b][t_stride]); t_stride and l_stride are multiples of 32. launch_align_mas: the monotonic alignment search over logp: dur [b][dur_stride] (frames per
+// token, 0 past tlens[b]), score [b], path [b][l_stride] (token of every frame, as floats; optional). `bits` (one decision bit per frame and token,
+// align_mas_bits_words(tmax, lmax) 64-bit words per utterance) is needed only when align_mas_bits_in_lds(tmax, lmax) is false.
+struct AlignCall {
+    TensorRef mean, logs, z;
+    const int* tlens = nullptr;   // device [batch]
+    const int* frames = nullptr;  // device [batch]; tlens[b] <= frames[b] (checked on the host)
+    int channels = 0, batch = 0, tmax = 0, lmax = 0, t_stride = 0, l_stride = 0;
+    float *plane_a = nullptr, *plane_z = nullptr, *ct = nullptr, *logp = nullptr;
+    unsigned long long* bits = nullptr;
+    int* dur = nullptr;
+    int dur_stride = 0;
+    float *path = nullptr, *score = nullptr;
+};
+constexpr size_t kAlignLdsBitBytes = 128 * 1024;  // decision bits of one utterance stay in LDS up to this size (160 KB per CU, beside the row exchange)
+size_t align_mas_bits_words(int tmax, int lmax);
+bool align_mas_bits_in_lds(int tmax, int lmax);
+hipError_t launch_align_logp(const AlignCall& c, hipStream_t s);
+hipError_t launch_align_mas(const AlignCall& c, hipStream_t s);
 // fp32 -> int16 PCM rows on the device (test/main.cpp:31-33); lens (device, optional) limits each row
 hipError_t launch_pcm16(const float* src, int64_t src_stride, int16_t* dst, int64_t dst_stride, const int64_t* lens, int rows, int64_t cols, hipStream_t s);
 hipError_t launch_conv_post(TensorRef x, const float* w, int cin, int k, float slope, TensorRef pre_tanh, TensorRef wave, const int* lens, int batch,

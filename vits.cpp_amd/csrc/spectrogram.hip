@@ -95,12 +95,12 @@ hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s) {
     return hipGetLastError();
 }
 
-// z_q[b][c][t] = mean + eps * exp(log_std) for t < frames[b] (VitsPosteriorEncoder.forward), eps drawn like prior sampling's (zp_kernel,
+// z_q[b][c][t] = mean + (eps * eps_scale) * exp(log_std) for t < frames[b] (VitsPosteriorEncoder.forward), eps drawn like prior sampling's (zp_kernel,
 // misc_kernels.hip: the counter stream VITS_STREAM_NOISE_PRIOR, index c * L + t, or the explicit / reference tensor). flip = 1 writes
 // channel c to row F - 1 - c: the physical layout of the forward flow's input when the flow has an odd number of layers (engine_flow.cpp).
 __global__ __launch_bounds__(256) void posterior_sample_kernel(const float* mean, int64_t m_bs, int m_cs, const float* logstd, int64_t v_bs, int v_cs,
                                                                const int* frames, const float* noise, int64_t n_bs, int n_cs, int noise_kind, uint64_t seed,
-                                                               const int* seed_off, float* zq, int64_t z_bs, int z_cs, int channels, int flip) {
+                                                               const int* seed_off, float* zq, int64_t z_bs, int z_cs, int channels, int flip, float eps_scale) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     const int L = frames[b];
     if (j >= L) return;
@@ -109,20 +109,24 @@ __global__ __launch_bounds__(256) void posterior_sample_kernel(const float* mean
     for (int c = blockIdx.z * cpb; c < c_end; ++c) {
         const float mu = mean[(int64_t)b * m_bs + (int64_t)c * m_cs + j];
         const float ls = logstd[(int64_t)b * v_bs + (int64_t)c * v_cs + j];
-        float e;
+        float e = 0.f;
+        if (eps_scale == 0.f) {
+            zq[(int64_t)b * z_bs + (int64_t)(flip ? channels - 1 - c : c) * z_cs + j] = mu;  // the posterior mean: nothing drawn, nothing read
+            continue;
+        }
         if (noise_kind == VITS_NOISE_COUNTER) e = vits_counter_normal(seed + (uint64_t)(seed_off ? seed_off[b] : b), VITS_STREAM_NOISE_PRIOR, (uint64_t)c * L + j);
         else e = noise[(int64_t)b * n_bs + (int64_t)c * n_cs + j];
         const int row = flip ? channels - 1 - c : c;
-        zq[(int64_t)b * z_bs + (int64_t)row * z_cs + j] = mu + e * expf(ls);
+        zq[(int64_t)b * z_bs + (int64_t)row * z_cs + j] = mu + (e * eps_scale) * expf(ls);
     }
 }
 
 hipError_t launch_posterior_sample(TensorRef mean, TensorRef logstd, const int* frames, TensorRef noise, int noise_kind, uint64_t seed, const int* seed_off,
-                                   TensorRef zq, int batch, int channels, int lmax, int flip, hipStream_t s) {
+                                   TensorRef zq, int batch, int channels, int lmax, int flip, hipStream_t s, float eps_scale) {
     if (batch <= 0 || lmax <= 0) return hipSuccess;
     dim3 grid((lmax + 255) / 256, batch, 16);
     VITS_KLAUNCH(posterior_sample_kernel, grid, dim3(256), 0, s, mean.p, mean.bs, mean.cs, logstd.p, logstd.bs, logstd.cs, frames, noise.p, noise.bs,
-                 noise.cs, noise_kind, seed, seed_off, zq.p, zq.bs, zq.cs, channels, flip);
+                 noise.cs, noise_kind, seed, seed_off, zq.p, zq.bs, zq.cs, channels, flip, eps_scale);
     return hipGetLastError();
 }
 
