@@ -155,6 +155,38 @@ VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker);
 VITS_API int32_t vits_model_get_speaker(const vits_model* model);
 VITS_API int32_t vits_model_num_speakers(const vits_model* model); /* 1 for a single-speaker model */
 
+/* ---- custom voices: speaker embeddings registered at run time (multi-speaker models) -----------------------------------
+ * A voice is a vector of E = vits_model_speaker_embedding_size floats that is NOT a row of the file's embed_speaker: a blend of two speakers, a
+ * fine-tuned or externally estimated embedding. Registering it appends one row to the per-speaker bias tables (the same 1x1 conditioning convs as the
+ * file's speakers, in the same order of operations: a voice whose vector equals a file speaker's embedding gives that speaker's audio bit for bit) and
+ * returns a VOICE ID. Ids are num_speakers + k, k = 0, 1, ... in order of registration, stable until vits_model_clear_voices;
+ * vits_model_num_speakers keeps returning the file's count. A voice id is accepted wherever a speaker index is: vits_process_opts.speaker_ids,
+ * vits_model_set_speaker, vits_model_submit_batch, src_speakers / tgt_speakers of vits_model_convert_batch / vits_model_convert, speakers of
+ * vits_model_align_batch / vits_model_align; one batch may mix -1, file speakers and voices, and such a call queues exactly the kernels of a call
+ * with file speakers. Every speaker check then reads "outside [-1, num_speakers + num_voices)".
+ *   vits_model_speaker_embedding_size  E; 0 for a single-speaker model (and for NULL).
+ *   vits_model_get_speaker_embedding   id in [0, num_speakers): the file's embed_speaker row, widened exactly to fp32; id of a voice: the vector as
+ *                                      registered. Copies min(E, cap) floats to dst and returns E; -1 + message otherwise.
+ *   vits_model_add_voices              emb: host [n][E], ids_out: [n]. All n voices or none. Returns 0.
+ *   vits_model_set_voice               overwrites a registered voice in place (its id stays).
+ *   vits_model_clear_voices            forgets every voice; ids start again at num_speakers. The device memory is kept for the next registration.
+ *   vits_model_num_voices              registered voices (0 for NULL).
+ * Refused with -1 and a message, the handle unchanged: a single-speaker model, n <= 0, a NULL pointer, a value that is not finite (the message names
+ * voice and element), an id that is not a registered voice (set_voice) or neither speaker nor voice (get_speaker_embedding), any of the three mutating
+ * calls while batches are in flight ("batches in flight") or from inside an on_chunk callback ("model busy"), vits_model_clear_voices while the handle's
+ * default speaker is a voice (reset it first), a device allocation that fails (the registry keeps what it had). With
+ * vits_model_set_ggml_tables(model, 1) voices are refused by the calls exactly as speakers are.
+ * Memory: a handle that never registers a voice allocates nothing. The first registration makes the conditioning convs resident (MMS-TTS architecture
+ * with speakers: 6,848 x 256 fp32 = 7 MB, plus the posterior encoder's once conversion is prepared); each voice then costs one table row (27 KB, plus
+ * the posterior's 24 KB); capacity doubles as the registry grows. All of it is counted in vits_model_weight_bytes. Voices registered before
+ * vits_model_prepare_conversion and after it give the same conversion. */
+VITS_API int32_t vits_model_speaker_embedding_size(const vits_model* model);
+VITS_API int vits_model_get_speaker_embedding(vits_model* model, int32_t id, float* dst, size_t cap);
+VITS_API int vits_model_add_voices(vits_model* model, const float* emb, int32_t n, int32_t* ids_out);
+VITS_API int vits_model_set_voice(vits_model* model, int32_t voice_id, const float* emb);
+VITS_API int vits_model_clear_voices(vits_model* model);
+VITS_API int32_t vits_model_num_voices(const vits_model* model);
+
 /* Noise source for the two N(0,1) draws (vits.cpp:948 [T,2] and :1059 [L,192]). */
 #define VITS_NOISE_REFERENCE 0 /* libstdc++ minstd_rand0 + normal_distribution<float>, global, host-serial */
 #define VITS_NOISE_COUNTER 1   /* include/vits_synth_noise.h, evaluated on the device                       */

@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_arith_scope", "vits_model_get_arith_scope", "vits_model_submit_batch", "vits_model_wait", "vits_model_pending",
     "vits_model_set_ggml_tables", "vits_model_get_ggml_tables",
     "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
+    "vits_model_speaker_embedding_size", "vits_model_get_speaker_embedding", "vits_model_add_voices", "vits_model_set_voice",
+    "vits_model_clear_voices", "vits_model_num_voices",
     "vits_model_set_prosody", "vits_model_get_prosody",
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align",
@@ -156,6 +158,18 @@ def lib():
     L.vits_model_get_speaker.argtypes = [vp]
     L.vits_model_num_speakers.restype = i32
     L.vits_model_num_speakers.argtypes = [vp]
+    L.vits_model_speaker_embedding_size.restype = i32
+    L.vits_model_speaker_embedding_size.argtypes = [vp]
+    L.vits_model_get_speaker_embedding.restype = i32
+    L.vits_model_get_speaker_embedding.argtypes = [vp, i32, f32p, sz]
+    L.vits_model_add_voices.restype = i32
+    L.vits_model_add_voices.argtypes = [vp, f32p, i32, vp]
+    L.vits_model_set_voice.restype = i32
+    L.vits_model_set_voice.argtypes = [vp, i32, f32p]
+    L.vits_model_clear_voices.restype = i32
+    L.vits_model_clear_voices.argtypes = [vp]
+    L.vits_model_num_voices.restype = i32
+    L.vits_model_num_voices.argtypes = [vp]
     L.vits_model_set_prosody.restype = i32
     L.vits_model_set_prosody.argtypes = [vp, C.c_float, C.c_float, C.c_float]
     L.vits_model_get_prosody.restype = i32
@@ -410,6 +424,63 @@ class Model:
     def num_speakers(self):
         """1 for a single-speaker model"""
         return int(lib().vits_model_num_speakers(self._h))
+
+    # -- custom voices: speaker embeddings registered at run time (include/vits.h vits_model_add_voices) ---------------------------
+    @property
+    def speaker_embedding_size(self):
+        """E, the length of a speaker embedding; 0 for a single-speaker model"""
+        return int(lib().vits_model_speaker_embedding_size(self._h))
+
+    @property
+    def num_voices(self):
+        return int(lib().vits_model_num_voices(self._h))
+
+    def speaker_embedding(self, id):
+        """fp32 [E]: the file's embed_speaker row of a speaker, or the vector a voice was registered with"""
+        out = np.zeros(max(self.speaker_embedding_size, 1), np.float32)
+        n = lib().vits_model_get_speaker_embedding(self._h, int(id), _ptr(out), out.size)
+        if n < 0:
+            raise VitsError(last_error())
+        return out[:n]
+
+    def add_voices(self, emb):
+        """registers the rows of emb ([n][E], or one vector [E]) as voices; returns their ids (num_speakers + k, in order of registration), which
+        every speaker argument accepts from then on"""
+        emb = np.ascontiguousarray(emb, dtype=np.float32)
+        E = self.speaker_embedding_size
+        if emb.ndim == 1 and E > 0:
+            emb = emb[None]
+        if E > 0 and (emb.ndim != 2 or emb.shape[1] != E):
+            raise ValueError("voices are rows of %d floats" % E)
+        n = int(emb.shape[0]) if emb.ndim >= 1 else 0
+        ids = np.zeros(max(n, 1), np.int32)
+        if lib().vits_model_add_voices(self._h, _ptr(emb), n, _ptr(ids)) != 0:
+            raise VitsError(last_error())
+        return ids[:n].tolist()
+
+    def set_voice(self, voice_id, emb):
+        """overwrites a registered voice in place"""
+        emb = np.ascontiguousarray(emb, dtype=np.float32).ravel()
+        if emb.size != self.speaker_embedding_size and self.speaker_embedding_size > 0:
+            raise ValueError("a voice is %d floats" % self.speaker_embedding_size)
+        if lib().vits_model_set_voice(self._h, int(voice_id), _ptr(emb)) != 0:
+            raise VitsError(last_error())
+
+    def clear_voices(self):
+        """forgets every voice; ids start again at num_speakers"""
+        if lib().vits_model_clear_voices(self._h) != 0:
+            raise VitsError(last_error())
+
+    def add_voice_mix(self, ids, weights):
+        """registers sum(weights[k] * speaker_embedding(ids[k])) — fp32, accumulated left to right in numpy — as one voice and returns its id
+        (a blend of speakers and / or voices; Python only: the C ABI has one way in, vits_model_add_voices)"""
+        ids, weights = list(ids), np.asarray(weights, np.float32).ravel()
+        if len(ids) != weights.size or not ids:
+            raise ValueError("one weight per id, at least one")
+        acc = np.zeros(self.speaker_embedding_size, np.float32)
+        for k, i in enumerate(ids):
+            acc = (acc + weights[k] * self.speaker_embedding(i)).astype(np.float32)
+        return self.add_voices(acc)[0]
 
     # -- prosody: the transformers.VitsModel attributes, the model-level values (vits_model_set_prosody) --------------------------
     def get_prosody(self):

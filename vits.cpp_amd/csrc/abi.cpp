@@ -234,9 +234,9 @@ VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker) {
         return -1;
     }
     VITS_ENTER(model, -1)
-    const int n = model->eng.hp.num_speakers;
-    if (speaker != -1 && (n <= 1 || speaker < -1 || speaker >= n)) {
-        set_err(n <= 1 ? "vits_model_set_speaker(" + std::to_string(speaker) + "): this model has a single speaker and no speaker conditioning (use -1)"
+    const int n = model->eng.speaker_limit();  // (file speakers + registered voices: the range rule of every speaker check)
+    if (speaker != -1 && (model->eng.hp.num_speakers <= 1 || !model->eng.speaker_in_range(speaker))) {
+        set_err(model->eng.hp.num_speakers <= 1 ? "vits_model_set_speaker(" + std::to_string(speaker) + "): this model has a single speaker and no speaker conditioning (use -1)"
                        : "vits_model_set_speaker(" + std::to_string(speaker) + "): outside [-1, " + std::to_string(n) + ")");
         return -1;
     }
@@ -245,6 +245,73 @@ VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker) {
 }
 VITS_API int32_t vits_model_get_speaker(const vits_model* model) { return model ? model->eng.speaker : -2; }
 VITS_API int32_t vits_model_num_speakers(const vits_model* model) { return model ? model->eng.num_speakers() : -1; }
+
+// ---- custom voices (engine_voices.cpp) ----------------------------------------------------------------------------------------
+VITS_API int32_t vits_model_speaker_embedding_size(const vits_model* model) {
+    return model && model->eng.hp.num_speakers > 1 ? model->eng.hp.speaker_embedding_size : 0;
+}
+VITS_API int32_t vits_model_num_voices(const vits_model* model) { return model ? model->eng.num_voices() : 0; }
+VITS_API int vits_model_get_speaker_embedding(vits_model* model, int32_t id, float* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    std::string err;
+    const int rc = model->eng.get_speaker_embedding(id, dst, cap, err);
+    if (rc < 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+// the three mutating calls: never with batches in flight (a growing table moves under the kernels that read it), never from inside a callback
+// (VITS_ENTER: "model busy")
+#define VITS_VOICES_ENTER(model)                                                                       \
+    VITS_ENTER(model, -1)                                                                              \
+    if ((model)->eng.pending()) {                                                                      \
+        set_err("batches in flight: call vits_model_wait for every submitted batch first");          \
+        return -1;                                                                                     \
+    }
+VITS_API int vits_model_add_voices(vits_model* model, const float* emb, int32_t n, int32_t* ids_out) {
+    VITS_TRY
+    if (!model || !emb || !ids_out) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_VOICES_ENTER(model)
+    std::string err;
+    const int rc = model->eng.add_voices(emb, n, ids_out, err);
+    if (rc != 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_set_voice(vits_model* model, int32_t voice_id, const float* emb) {
+    VITS_TRY
+    if (!model || !emb) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_VOICES_ENTER(model)
+    std::string err;
+    const int rc = model->eng.set_voice(voice_id, emb, err);
+    if (rc != 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_clear_voices(vits_model* model) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_VOICES_ENTER(model)
+    std::string err;
+    const int rc = model->eng.clear_voices(err);
+    if (rc != 0) set_err(err);
+    return rc;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_model_set_prosody(vits_model* model, float speaking_rate, float noise_scale, float noise_scale_duration) {
     if (!model) {
         set_err("null argument");

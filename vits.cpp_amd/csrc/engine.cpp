@@ -124,8 +124,8 @@ int Engine::check_speakers(const vits_process_opts& o, int B, std::string& err) 
             err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
             return -1;
         }
-        if (s < -1 || s >= hp.num_speakers) {
-            err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+        if (!speaker_in_range(s)) {
+            err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
             return -1;
         }
         if (ggml_tables == 1) {

@@ -209,6 +209,17 @@ class Engine {
     // 0, or -1 + a message naming the utterance: every speaker of the call in [-1, num_speakers), none >= 0 on a single-speaker model or with
     // the exact-order stage one (ggml_tables == 1)
     int check_speakers(const vits_process_opts& o, int B, std::string& err) const;
+    // custom voices (engine_voices.cpp, include/vits.h vits_model_add_voices): speaker embeddings registered at run time. Voice k has the id
+    // num_speakers + k and row 1 + num_speakers + k of the effective-bias tables, so the per-call row upload (speaker + 1) and every kernel stay as they are.
+    // The ONE range rule of every speaker check (check_speakers, conversion, alignment, vits_model_set_speaker): -1 <= s < speaker_limit().
+    int num_voices() const { return hp.speaker_embedding_size > 0 ? (int)(voices_.size() / (size_t)hp.speaker_embedding_size) : 0; }
+    int speaker_limit() const { return hp.num_speakers + num_voices(); }
+    bool speaker_in_range(int s) const { return s >= -1 && s < speaker_limit(); }
+    // each returns 0, or -1 + a message with the handle unchanged; none runs with batches in flight (the ABI checks pending() first)
+    int add_voices(const float* emb, int n, int32_t* ids_out, std::string& err);
+    int set_voice(int id, const float* emb, std::string& err);
+    int clear_voices(std::string& err);
+    int get_speaker_embedding(int id, float* dst, size_t cap, std::string& err) const;  // E, or -1
     int speaker_of(const vits_process_opts& o, int b) const { return o.speaker_ids ? o.speaker_ids[b] : speaker; }
     // prosody (include/vits.h vits_model_set_prosody): the values of every utterance a call gives none for (the prosody arrays of
     // vits_process_opts == NULL, vits_model_process / _ids); the model file's speaking_rate / noise_scale / noise_scale_duration at load
@@ -257,7 +268,6 @@ class Engine {
         std::vector<PackedConv> in_layers, res_skip;
     } post_;
     std::vector<PackedConv> flow_fwd_post_;
-    float* post_spk_table_ = nullptr;
     float* stft_tw_ = nullptr;  // [n_fft / 2] complex
     float* stft_win_ = nullptr;
     int n_fft_ = 0, hop_ = 0, stft_pad_ = 0;
@@ -384,7 +394,33 @@ class Engine {
     bool load_dds(const ModelFile& f, const std::string& base, DdsW& d, std::string& err);
     // multi-speaker models: the effective-bias table (speaker_bias_kernel) and the conditioned layers pointed into its row 0
     bool load_speakers(const ModelFile& f, std::string& err);
-    float* spk_table_ = nullptr;
+    // An effective-bias table that can grow: rows 0 .. num_speakers are built at load (load_speakers; the posterior encoder's by prepare_conversion),
+    // voices append rows (voices.hip). The conditioned PackedConvs point into row 0, so a table that moves repoints them (voice_rows); the 16-bit and
+    // latency packs hold weights only and read the bias through the PackedConv at launch. The conditioning convs stay on the host until the first
+    // registration makes them resident (d_w / d_b / d_segs).
+    struct VoiceTable {
+        float* table = nullptr;
+        int64_t rs = 0;    // row stride, floats
+        int cap_rows = 0;  // rows allocated
+        struct Seg {
+            PackedConv* pc;
+            int n;
+            int64_t off;
+        };
+        std::vector<Seg> segs;
+        std::vector<float> cond_w, cond_b;  // host: the segments' conv rows, concatenated [sum n][E] / [sum n] (released once resident)
+        float *d_w = nullptr, *d_b = nullptr;
+        VoiceSeg* d_segs = nullptr;
+        int tiles = 0;
+    } vt_main_, vt_post_;
+    std::vector<float> spk_emb_;  // host [num_speakers][E]: embed_speaker widened to fp32 (vits_model_get_speaker_embedding, Model.add_voice_mix)
+    std::vector<float> voices_;   // host [num_voices][E]: the registered vectors
+    struct VoiceResident;  // engine_voices.cpp: a table's conditioning convs staged on the device, not yet the table's
+    int voice_table_stage(VoiceTable& t, VoiceResident& r, std::string& err);
+    // rows row_first .. row_first + n - 1 of every table in `tabs` from n host vectors: grows a table that is too small (capacity doubling, device-to-device
+    // copy of rows [0, row_first), PackedConvs repointed), makes the conditioning convs resident on first use, one launch per table, one synchronisation;
+    // every allocation is staged and handed over at the end: on failure nothing has changed, weight_bytes included
+    int voice_rows(const std::vector<VoiceTable*>& tabs, const float* emb, int n, int row_first, std::string& err);
     hipError_t conv(const char* name, const PackedConv& w, ConvCall c, hipStream_t on = nullptr);  // on == nullptr: the main stream
     hipError_t run_dds(const DdsW& d, TensorRef x, TensorRef y, TensorRef p, const int* lens, int batch, int tmax, int64_t sum_t);
     // The DDS block on the latency kernels (stage1_lat.hip) with the per-token ops around it fused in: the head (a conv flow's 1 -> H conv +

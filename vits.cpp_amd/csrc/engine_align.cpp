@@ -60,8 +60,8 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
             err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
             return -1;
         }
-        if (s < -1 || s >= hp.num_speakers) {
-            err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+        if (!speaker_in_range(s)) {
+            err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
             return -1;
         }
     }

@@ -77,17 +77,19 @@ int Engine::prepare_conversion(std::string& err) {
             if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
             return d;
         };
-        bool ok = hipMalloc((void**)&post_spk_table_, table_floats * sizeof(float)) == hipSuccess;
+        float* table = nullptr;
+        bool ok = hipMalloc((void**)&table, table_floats * sizeof(float)) == hipSuccess;
         if (ok) {
-            owned_.push_back(post_spk_table_);
+            owned_.push_back(table);
             weight_bytes += (int64_t)table_floats * 4;
         }
+        const std::vector<float> cond_w = tw->to_f32(), cond_b = tb->to_f32();
         const float* d_emb = ok ? dev(te->to_f32()) : nullptr;
-        const float* d_w = ok ? dev(tw->to_f32()) : nullptr;
-        const float* d_b = ok ? dev(tb->to_f32()) : nullptr;
+        const float* d_w = ok ? dev(cond_w) : nullptr;
+        const float* d_b = ok ? dev(cond_b) : nullptr;
         ok = ok && d_emb && d_w && d_b;
         for (int l = 0; l < nl && ok; ++l)
-            ok = launch_speaker_bias(post_.in_layers[l].bias, d_w + (int64_t)2 * H * l * E, d_b + 2 * H * l, d_emb, 2 * H, E, N, post_spk_table_ + (int64_t)2 * H * l, rs,
+            ok = launch_speaker_bias(post_.in_layers[l].bias, d_w + (int64_t)2 * H * l * E, d_b + 2 * H * l, d_emb, 2 * H, E, N, table + (int64_t)2 * H * l, rs,
                                      stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(stream) == hipSuccess;
         for (void* p : tmp) hipFree(p);
@@ -96,9 +98,20 @@ int Engine::prepare_conversion(std::string& err) {
             return -1;
         }
         for (int l = 0; l < nl; ++l) {
-            post_.in_layers[l].bias = post_spk_table_ + (int64_t)2 * H * l;
+            post_.in_layers[l].bias = table + (int64_t)2 * H * l;
             post_.in_layers[l].bias_rs = rs;
         }
+        // custom voices (engine_voices.cpp): this table takes the same rows as load_speakers' — the voices registered so far now (the same kernel and
+        // vectors as a registration after this call: the same rows either way), later ones as they come
+        VoiceTable vt;  // (becomes vt_post_ only once it holds the registered voices' rows: a failure below leaves the registry serving the main table alone)
+        vt.table = table;
+        vt.rs = rs;
+        vt.cap_rows = N + 1;
+        for (int l = 0; l < nl; ++l) vt.segs.push_back({&post_.in_layers[l], 2 * H, (int64_t)2 * H * l});
+        vt.cond_w = cond_w;
+        vt.cond_b = cond_b;
+        if (num_voices() > 0 && voice_rows({&vt}, voices_.data(), num_voices(), 1 + N, err)) return -1;
+        vt_post_ = std::move(vt);
     }
     // STFT tables, in double, rounded once to fp32: twiddles exp(-2 pi i m / n) and the periodic Hann window (torch.hann_window(n))
     {
@@ -286,8 +299,8 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
                 err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
                 return -1;
             }
-            if (s < -1 || s >= hp.num_speakers) {
-                err = who + " is outside [-1, " + std::to_string(hp.num_speakers) + ")";
+            if (!speaker_in_range(s)) {
+                err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
                 return -1;
             }
         }

@@ -315,9 +315,10 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
         if (hipMemcpy(d, p, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
         return d;
     };
-    bool ok = hipMalloc((void**)&spk_table_, table_floats * sizeof(float)) == hipSuccess;
+    float* table = nullptr;
+    bool ok = hipMalloc((void**)&table, table_floats * sizeof(float)) == hipSuccess;
     if (ok) {
-        owned_.push_back(spk_table_);
+        owned_.push_back(table);
         weight_bytes += (int64_t)table_floats * 4;
     }
     const float* d_emb = ok ? dev(emb.data(), emb.size()) : nullptr;
@@ -333,7 +334,7 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
     for (const Seg& s : segs) {
         if (!ok) break;
         const auto& wb = d_cond[s.w];
-        ok = launch_speaker_bias(s.pc->bias, wb.first + (int64_t)s.row0 * E, wb.second + s.row0, d_emb, s.n, E, N, spk_table_ + s.off, rs, stream) == hipSuccess;
+        ok = launch_speaker_bias(s.pc->bias, wb.first + (int64_t)s.row0 * E, wb.second + s.row0, d_emb, s.n, E, N, table + s.off, rs, stream) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(stream) == hipSuccess;
     for (void* p : tmp) hipFree(p);
@@ -342,9 +343,21 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
         return false;
     }
     for (Seg& s : segs) {
-        s.pc->bias = spk_table_ + s.off;  // row 0: the plain biases (a call without speakers reads exactly these values)
+        s.pc->bias = table + s.off;  // row 0: the plain biases (a call without speakers reads exactly these values)
         s.pc->bias_rs = rs;
     }
+    // custom voices (engine_voices.cpp): the table may grow later, and a registered vector goes through these same conditioning convs — host copies
+    // of their rows in segment order and of the embedding (what vits_model_get_speaker_embedding returns); nothing more on the device until a voice comes
+    vt_main_.table = table;
+    vt_main_.rs = rs;
+    vt_main_.cap_rows = N + 1;
+    for (const Seg& s : segs) {
+        vt_main_.segs.push_back({s.pc, s.n, s.off});
+        const auto& wb = cond[s.w];
+        vt_main_.cond_w.insert(vt_main_.cond_w.end(), wb.first.begin() + (int64_t)s.row0 * E, wb.first.begin() + (int64_t)(s.row0 + s.n) * E);
+        vt_main_.cond_b.insert(vt_main_.cond_b.end(), wb.second.begin() + s.row0, wb.second.begin() + s.row0 + s.n);
+    }
+    spk_emb_ = std::move(emb);
     return true;
 }
 

@@ -512,6 +512,20 @@ hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 // bias + (cond_w . emb[s] + cond_b) for the n channels of the segment; cond_w is the conditioning 1x1 conv [n][E], emb [n_spk][E]
 hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const float* cond_b, const float* emb, int n, int E, int n_spk, float* table,
                                int64_t row_stride, hipStream_t s);
+// rows of an effective-bias table for voices registered at run time (voices.hip): ONE launch for every segment of the table and all n_voices new rows.
+// A segment = the n channels at float offset `off` of a table row, conditioned by rows w [n][E] / cb [n] of a 1x1 conv (device pointers); tile0 = the
+// sum of voice_seg_tiles(n) over the segments before it, `tiles` the sum over all. Row row_first + v = row 0 + (w . emb[v] + cb) in speaker_bias_kernel's
+// order of operations. The table must hold row_first + n_voices rows. Any n_voices: the launcher walks slices of the grid's y limit; few voices take a
+// variant with one chain per thread (the same arithmetic per output).
+struct VoiceSeg {
+    const float* w;
+    const float* cb;
+    int64_t off;
+    int n, tile0;
+};
+int voice_seg_tiles(int n);
+hipError_t launch_voice_rows(const VoiceSeg* segs, int nseg, int tiles, const float* emb, int n_voices, int E, float* table, int64_t row_stride, int row_first,
+                             hipStream_t s);
 hipError_t launch_rb_sum3_std(TensorRef y0, TensorRef y1, TensorRef y2, TensorRef out, int channels, const int* lens, int batch, int tmax, float scale, int scale_div, int post_act,
                               float post_slope, hipStream_t s);  // fp32 [b][c][t]: ((y0 + y1) [+ y2]) scaled [+ leaky_relu]: side-by-side resblocks of the fp32 path (small grids)
 hipError_t launch_fill_rows(TensorRef x, int channels, float v, int batch, int tmax, hipStream_t s);
