@@ -281,6 +281,84 @@ def _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, dur
     return keep
 
 
+def _opts(B, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False,
+          out_device=None, out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, frames_only=False, noise_seed_offsets=None,
+          speaker_ids=None):
+    """A ProcessOpts with the fields every batch call shares. Returns (opts, keep): keep holds the arrays opts points at (the caller keeps
+    it alive for the call)."""
+    o = ProcessOpts()
+    o.struct_size = C.sizeof(ProcessOpts)
+    o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
+    nd, npr = _f32(noise_dur), _f32(noise_prior)
+    o.noise_dur, o.noise_prior = _ptr(nd), _ptr(npr)
+    o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
+    o.fixed_duration, o.collect_taps = fixed_duration, int(collect_taps)
+    o.out_device = out_device
+    o.out_device_stride = out_device_stride
+    o.skip_host_copy, o.async_ = int(skip_host_copy), int(async_)
+    o.vocoder_chunk_frames = int(vocoder_chunk_frames)
+    o.frames_only = int(frames_only)
+    nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
+    if nso is not None and nso.size != B:
+        raise ValueError("noise_seed_offsets needs one entry per utterance")
+    o.noise_seed_offsets = _ptr(nso)
+    spk = None if speaker_ids is None else np.ascontiguousarray(speaker_ids, dtype=np.int32).ravel()
+    if spk is not None and spk.size != B:
+        raise ValueError("speaker_ids needs one entry per utterance")
+    o.speaker_ids = _ptr(spk)
+    return o, [nd, npr, nso, spk]
+
+
+def _refused_fields(refused, B, noise_scale_arg="noise_scale"):
+    """Keyword arguments that a call refuses travel in its options all the same, so that the library says why: pops them from `refused` (anything
+    left over is unknown: TypeError) and returns ({ProcessOpts field: value}, the arrays the values point at). noise_scale_arg: the keyword
+    that carries opts.noise_scales (alignment has a noise_scale argument of its own)."""
+    fields = {"fixed_duration": int(refused.pop("fixed_duration", 0)), "frames_only": int(refused.pop("frames_only", False)),
+              "async_": int(refused.pop("async_", False))}
+    spk = refused.pop("speaker_ids", None)
+    keep = [None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()]
+    fields["speaker_ids"] = _ptr(keep[0])
+    for arg, field, dtype in (("speaking_rate", "speaking_rates", np.float32), (noise_scale_arg, "noise_scales", np.float32),
+                              ("noise_scale_duration", "noise_scale_durations", np.float32), ("duration_override", "duration_override", np.int32),
+                              ("durations_out", "durations_out", np.int32)):
+        v = refused.pop(arg, None)
+        if v is not None:
+            keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype).ravel(), (max(B, np.size(v)),))))
+            fields[field] = _ptr(keep[-1])
+    if refused:
+        raise TypeError("unknown arguments: %s" % sorted(refused))
+    return fields, keep
+
+
+def _chunk_sink(o, on_chunk):
+    """Points o.on_chunk at a wrapper of the caller's sink on_chunk(utt, offset, pcm ndarray). Returns the list that receives an exception the sink
+    raised (the wrapper then asks the library to abort: an exception must never unwind through the C frames)."""
+    cb_error = []
+    if on_chunk is not None:
+        def _cb(_user, utt, offset, pcm, n):
+            try:
+                return 1 if on_chunk(int(utt), int(offset), np.ctypeslib.as_array(pcm, shape=(n,)).copy()) else 0
+            except BaseException as e:
+                cb_error.append(e)
+                return 1
+        o.on_chunk = ChunkCallback(_cb)
+    return cb_error
+
+
+def _take_result(res, B, keep_pcm):
+    """(list of per-utterance PCM arrays or None, lengths, frames) of a BatchResult, which is freed"""
+    try:
+        lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()
+        frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
+        pcm = None
+        if res.data and keep_pcm:
+            full = np.ctypeslib.as_array(res.data, shape=(B, res.stride))
+            pcm = [full[b, : lengths[b]].copy() for b in range(B)]
+        return pcm, lengths, frames
+    finally:
+        lib().vits_free_batch_result(C.byref(res))
+
+
 def synth_model_bytes(seed=0x5EED, arch=SYNTH_FULL):
     """Deterministic synthetic model file in the reference's on-disk format (host-only, no GPU needed)."""
     p, n = C.c_void_p(), C.c_size_t()
@@ -573,51 +651,16 @@ class Model:
             ids = ids[None, :]
         B, stride = ids.shape
         lens = np.full(B, stride, np.int32) if id_lengths is None else np.ascontiguousarray(id_lengths, dtype=np.int32)
-        o = ProcessOpts()
-        o.struct_size = C.sizeof(ProcessOpts)
-        o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
-        nd, npr = _f32(noise_dur), _f32(noise_prior)
-        o.noise_dur, o.noise_prior = _ptr(nd), _ptr(npr)
-        o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
-        o.fixed_duration, o.collect_taps = fixed_duration, int(collect_taps)
-        o.out_device = out_device
-        o.out_device_stride = out_device_stride
-        o.skip_host_copy, o.async_ = int(skip_host_copy), int(async_)
-        o.vocoder_chunk_frames = int(vocoder_chunk_frames)
-        o.frames_only = int(frames_only)
-        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
-        if nso is not None and nso.size != B:
-            raise ValueError("noise_seed_offsets needs one entry per utterance")
-        o.noise_seed_offsets = _ptr(nso)
-        spk = None if speaker_ids is None else np.ascontiguousarray(speaker_ids, dtype=np.int32).ravel()
-        if spk is not None and spk.size != B:
-            raise ValueError("speaker_ids needs one entry per utterance")
-        o.speaker_ids = _ptr(spk)
-        keep = _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)  # noqa: F841
-        cb_error = []
-        if on_chunk is not None:
-            def _cb(_user, utt, offset, pcm, n):
-                try:
-                    return 1 if on_chunk(int(utt), int(offset), np.ctypeslib.as_array(pcm, shape=(n,)).copy()) else 0
-                except BaseException as e:  # never let an exception unwind through the C frames
-                    cb_error.append(e)
-                    return 1
-            o.on_chunk = ChunkCallback(_cb)
+        o, keep = _opts(B, mode, noise_kind, noise_seed, noise_dur, noise_prior, fixed_duration, collect_taps, out_device, out_device_stride, skip_host_copy,
+                        async_, vocoder_chunk_frames, frames_only, noise_seed_offsets, speaker_ids)
+        keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
+        cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
         if lib().vits_model_process_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), C.byref(res)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
-        try:
-            lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()
-            frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
-            pcm = None
-            if res.data and keep_pcm:
-                full = np.ctypeslib.as_array(res.data, shape=(B, res.stride))
-                pcm = [full[b, : lengths[b]].copy() for b in range(B)]
-            return pcm, lengths, frames
-        finally:
-            lib().vits_free_batch_result(C.byref(res))
+        return _take_result(res, B, keep_pcm)
 
     def prepare_conversion(self):
         """vits_model_prepare_conversion: build the posterior encoder and the forward-flow weights now (the first conversion does it otherwise)"""
@@ -640,61 +683,20 @@ class Model:
         if lens.size != B:
             raise ValueError("lengths needs one entry per utterance")
         sp = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,))) for v in (src, tgt)]
-        o = ProcessOpts()
-        o.struct_size = C.sizeof(ProcessOpts)
-        o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
-        npr = _f32(noise_prior)
-        o.noise_prior = _ptr(npr)
-        o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
-        o.collect_taps = int(collect_taps)
-        o.out_device = out_device
-        o.out_device_stride = out_device_stride
-        o.skip_host_copy = int(skip_host_copy)
-        o.vocoder_chunk_frames = int(vocoder_chunk_frames)
-        o.fixed_duration = int(refused.pop("fixed_duration", 0))
-        o.frames_only = int(refused.pop("frames_only", False))
-        o.async_ = int(refused.pop("async_", False))
-        spk = refused.pop("speaker_ids", None)
-        keep = []
-        for arg, field, dtype in (("speaking_rate", "speaking_rates", np.float32), ("noise_scale", "noise_scales", np.float32),
-                                  ("noise_scale_duration", "noise_scale_durations", np.float32), ("duration_override", "duration_override", np.int32),
-                                  ("durations_out", "durations_out", np.int32)):
-            v = refused.pop(arg, None)
-            if v is not None:
-                keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype).ravel(), (max(B, np.size(v)),))))
-                setattr(o, field, _ptr(keep[-1]))
-        if refused:
-            raise TypeError("unknown arguments: %s" % sorted(refused))
-        spk = None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()
-        o.speaker_ids = _ptr(spk)
-        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
-        if nso is not None and nso.size != B:
-            raise ValueError("noise_seed_offsets needs one entry per utterance")
-        o.noise_seed_offsets = _ptr(nso)
-        cb_error = []
-        if on_chunk is not None:
-            def _cb(_user, utt, offset, p, n):
-                try:
-                    return 1 if on_chunk(int(utt), int(offset), np.ctypeslib.as_array(p, shape=(n,)).copy()) else 0
-                except BaseException as e:  # never let an exception unwind through the C frames
-                    cb_error.append(e)
-                    return 1
-            o.on_chunk = ChunkCallback(_cb)
+        fields, keep = _refused_fields(refused, B)
+        o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, out_device=out_device,
+                        out_device_stride=out_device_stride, skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames,
+                        noise_seed_offsets=noise_seed_offsets)
+        keep += kept
+        for field, v in fields.items():
+            setattr(o, field, v)
+        cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
         if lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o), C.byref(res)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
-        try:
-            lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()
-            frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
-            out = None
-            if res.data and keep_pcm:
-                full = np.ctypeslib.as_array(res.data, shape=(B, res.stride))
-                out = [full[b, : lengths[b]].copy() for b in range(B)]
-            return out, lengths, frames
-        finally:
-            lib().vits_free_batch_result(C.byref(res))
+        return _take_result(res, B, keep_pcm)
 
     def convert(self, pcm, src=-1, tgt=-1):
         """vits_model_convert: one utterance, the model's default mode and the reference noise stream (like process)"""
@@ -731,39 +733,15 @@ class Model:
         if lens.size != B or ilens.size != B:
             raise ValueError("lengths and id_lengths need one entry per utterance")
         sp = np.ascontiguousarray(np.broadcast_to(np.asarray(speakers, np.int32), (B,)))
-        o = ProcessOpts()
-        o.struct_size = C.sizeof(ProcessOpts)
-        o.mode, o.noise_kind, o.noise_seed = mode, noise_kind, noise_seed
-        npr = _f32(noise_prior)
-        o.noise_prior = _ptr(npr)
-        o.noise_prior_stride = 0 if npr is None else npr.shape[-1]
-        o.collect_taps = int(collect_taps)
-        o.out_device = refused.pop("out_device", None)
-        o.skip_host_copy = int(refused.pop("skip_host_copy", False))
-        o.vocoder_chunk_frames = int(refused.pop("vocoder_chunk_frames", 0))
-        o.fixed_duration = int(refused.pop("fixed_duration", 0))
-        o.frames_only = int(refused.pop("frames_only", False))
-        o.async_ = int(refused.pop("async_", False))
+        own = {k: refused.pop(k) for k in ("out_device", "skip_host_copy", "vocoder_chunk_frames") if k in refused}
         on_chunk = refused.pop("on_chunk", None)
+        fields, keep = _refused_fields(refused, B, noise_scale_arg="noise_scales")
+        o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, noise_seed_offsets=noise_seed_offsets, **own)
+        keep += kept
+        for field, v in fields.items():
+            setattr(o, field, v)
         if on_chunk is not None:
             o.on_chunk = ChunkCallback(lambda _user, utt, offset, p, n: 1)  # (refused before anything could call it)
-        spk = refused.pop("speaker_ids", None)
-        keep = []
-        for arg, field, dtype in (("speaking_rate", "speaking_rates", np.float32), ("noise_scales", "noise_scales", np.float32),
-                                  ("noise_scale_duration", "noise_scale_durations", np.float32), ("duration_override", "duration_override", np.int32),
-                                  ("durations_out", "durations_out", np.int32)):
-            v = refused.pop(arg, None)
-            if v is not None:
-                keep.append(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype).ravel(), (max(B, np.size(v)),))))
-                setattr(o, field, _ptr(keep[-1]))
-        if refused:
-            raise TypeError("unknown arguments: %s" % sorted(refused))
-        spk = None if spk is None else np.ascontiguousarray(spk, dtype=np.int32).ravel()
-        o.speaker_ids = _ptr(spk)
-        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
-        if nso is not None and nso.size != B:
-            raise ValueError("noise_seed_offsets needs one entry per utterance")
-        o.noise_seed_offsets = _ptr(nso)
         durations = np.zeros((B, id_stride), np.int32)
         frames = np.zeros(B, np.int64)
         scores = np.zeros(B, np.float32)
@@ -807,23 +785,9 @@ class Model:
             ids = ids[None, :]
         B, stride = ids.shape
         lens = np.full(B, stride, np.int32) if id_lengths is None else np.ascontiguousarray(id_lengths, dtype=np.int32)
-        o = ProcessOpts()
-        o.struct_size = C.sizeof(ProcessOpts)
-        o.mode, o.noise_kind, o.noise_seed = mode, NOISE_COUNTER, noise_seed
-        o.fixed_duration = fixed_duration
-        o.out_device = out_device
-        o.out_device_stride = out_device_stride
-        o.skip_host_copy = int(skip_host_copy)
-        o.vocoder_chunk_frames = int(vocoder_chunk_frames)
-        nso = None if noise_seed_offsets is None else np.ascontiguousarray(noise_seed_offsets, dtype=np.int32)
-        if nso is not None and nso.size != B:
-            raise ValueError("noise_seed_offsets needs one entry per utterance")
-        o.noise_seed_offsets = _ptr(nso)
-        spk = None if speaker_ids is None else np.ascontiguousarray(speaker_ids, dtype=np.int32).ravel()
-        if spk is not None and spk.size != B:
-            raise ValueError("speaker_ids needs one entry per utterance")
-        o.speaker_ids = _ptr(spk)
-        keep = _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)  # noqa: F841
+        o, keep = _opts(B, mode, NOISE_COUNTER, noise_seed, fixed_duration=fixed_duration, out_device=out_device, out_device_stride=out_device_stride,
+                        skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames, noise_seed_offsets=noise_seed_offsets, speaker_ids=speaker_ids)
+        keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
         if lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o)) != 0:
             raise VitsError(last_error())
         if not hasattr(self, "_durations_in_flight"):
@@ -837,17 +801,7 @@ class Model:
             raise VitsError(last_error())
         if getattr(self, "_durations_in_flight", None):
             self._durations_in_flight.pop(0)
-        try:
-            B = res.batch
-            lengths = np.ctypeslib.as_array(res.lengths, shape=(B,)).copy()
-            frames = np.ctypeslib.as_array(res.frames, shape=(B,)).copy()
-            pcm = None
-            if res.data and keep_pcm:
-                full = np.ctypeslib.as_array(res.data, shape=(B, res.stride))
-                pcm = [full[b, : lengths[b]].copy() for b in range(B)]
-            return pcm, lengths, frames
-        finally:
-            lib().vits_free_batch_result(C.byref(res))
+        return _take_result(res, res.batch, keep_pcm)
 
     @property
     def pending(self):

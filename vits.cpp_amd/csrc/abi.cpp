@@ -45,6 +45,62 @@ VITS_API const char* vits_last_error(void) { return g_last_error.c_str(); }
         return ret;                                                                                                                     \
     }
 
+// ... and none beside submitted batches, for the entry points that change what those read (Engine::refuse_pending has the message)
+#define VITS_ENTER_IDLE(model, ret)                          \
+    VITS_ENTER(model, ret)                                   \
+    {                                                        \
+        std::string pending_err_;                            \
+        if ((model)->eng.refuse_pending(pending_err_)) {     \
+            set_err(pending_err_);                           \
+            return ret;                                      \
+        }                                                    \
+    }
+
+// the options of a call: the defaults, then what the caller gave (as much of it as the caller's struct_size and ours have in common)
+static vits_process_opts default_opts(const vits_process_opts* given, int noise_kind) {
+    vits_process_opts o;
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.mode = VITS_MODE_DEFAULT;
+    o.noise_kind = noise_kind;
+    if (given) std::memcpy(&o, given, std::min<size_t>(sizeof(o), given->struct_size ? given->struct_size : sizeof(o)));
+    return o;
+}
+
+// One engine call, run(err) -> 0 or an error code: on failure the message is set and a half-filled *out goes back — also when the engine throws
+// (std::bad_alloc on the PCM buffer: nothing half-filled reaches the caller, *out is left zeroed, a waited-for batch stays waitable)
+template <class Run>
+static int run_engine(vits_batch_result* out, Run&& run) {
+    std::string err;
+    int rc;
+    try {
+        rc = run(err);
+    } catch (...) {
+        if (out) vits_free_batch_result(out);
+        throw;
+    }
+    if (rc != 0) {
+        set_err(err);
+        if (out) vits_free_batch_result(out);
+    }
+    return rc;
+}
+
+// The result of a one-utterance batch as a vits_result (vits.cpp:1226-1231: a buffer of exactly `size` samples owned by the library). One utterance:
+// stride == its length, so its row IS the result (no second buffer, no copy); the copy is for a result that is not of that shape. Empties br.
+static vits_result take_row(vits_batch_result& br) {
+    vits_result r{nullptr, (size_t)br.lengths[0]};
+    if (br.batch == 1 && br.stride >= r.size) {
+        r.data = br.data;
+        br.data = nullptr;
+    } else {
+        r.data = new float[r.size];
+        std::memcpy(r.data, br.data, sizeof(float) * r.size);
+    }
+    vits_free_batch_result(&br);
+    return r;
+}
+
 // reference: src/vits.cpp:1205-1215
 VITS_API vits_model* vits_model_load_from_bytes(const char* bytes, size_t size) {
     VITS_TRY
@@ -107,31 +163,12 @@ static vits_result process_ids_impl(vits_model* model, const int32_t* ids, size_
         return r;
     }
     VITS_ENTER(model, r)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.struct_size = sizeof(o);
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_REFERENCE;
+    const vits_process_opts o = default_opts(nullptr, VITS_NOISE_REFERENCE);
     vits_batch_result br;
     std::memset(&br, 0, sizeof(br));
-    std::string err;
     const int32_t len = (int32_t)n;
-    if (model->eng.process_batch(ids, &len, 1, (int)n, o, &br, err) != 0) {
-        set_err(err);
-        vits_free_batch_result(&br);
-        return r;
-    }
-    // vits.cpp:1226-1231: a fresh buffer of exactly `size` samples owned by the library
-    r.size = (size_t)br.lengths[0];
-    if (br.batch == 1 && br.stride >= r.size) {  // one utterance: its row IS the result (no second buffer, no copy)
-        r.data = br.data;
-        br.data = nullptr;
-    } else {
-        r.data = new float[r.size];
-        std::memcpy(r.data, br.data, sizeof(float) * r.size);
-    }
-    vits_free_batch_result(&br);
-    return r;
+    if (run_engine(&br, [&](std::string& err) { return model->eng.process_batch(ids, &len, 1, (int)n, o, &br, err); }) != 0) return r;
+    return take_row(br);
 }
 
 // reference: src/vits.cpp:1225-1232 -> vits_model::process :1101-1191
@@ -180,17 +217,8 @@ VITS_API int vits_model_set_arith(vits_model* model, int arith) {
         set_err("bad arithmetic mode");
         return -1;
     }
-    VITS_ENTER(model, -1)
-    std::string err;
-    if (model->eng.pending()) {
-        set_err("batches in flight: call vits_model_wait for every submitted batch first");
-        return -1;
-    }
-    if (model->eng.set_arith(arith, err) != 0) {
-        set_err(err);
-        return -1;
-    }
-    return 0;
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_arith(arith, err); });
     VITS_CATCH(-1)
 }
 VITS_API int vits_model_get_arith(const vits_model* model) { return model ? model->eng.arith : -1; }
@@ -199,11 +227,7 @@ VITS_API int vits_model_set_arith_scope(vits_model* model, int scope) {
         set_err("bad arithmetic scope");
         return -1;
     }
-    VITS_ENTER(model, -1)
-    if (model->eng.pending()) {
-        set_err("batches in flight: call vits_model_wait for every submitted batch first");
-        return -1;
-    }
+    VITS_ENTER_IDLE(model, -1)
     model->eng.arith_scope = scope;
     return 0;
 }
@@ -214,17 +238,8 @@ VITS_API int vits_model_set_ggml_tables(vits_model* model, int on) {
         set_err("null argument");
         return -1;
     }
-    VITS_ENTER(model, -1)
-    if (model->eng.pending()) {
-        set_err("batches in flight: call vits_model_wait for every submitted batch first");
-        return -1;
-    }
-    std::string err;
-    if (model->eng.set_ggml_tables(on, err) != 0) {
-        set_err(err);
-        return -1;
-    }
-    return 0;
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_ggml_tables(on, err); });
     VITS_CATCH(-1)
 }
 VITS_API int vits_model_get_ggml_tables(const vits_model* model) { return model ? model->eng.ggml_tables : -1; }
@@ -234,10 +249,9 @@ VITS_API int vits_model_set_speaker(vits_model* model, int32_t speaker) {
         return -1;
     }
     VITS_ENTER(model, -1)
-    const int n = model->eng.speaker_limit();  // (file speakers + registered voices: the range rule of every speaker check)
-    if (speaker != -1 && (model->eng.hp.num_speakers <= 1 || !model->eng.speaker_in_range(speaker))) {
-        set_err(model->eng.hp.num_speakers <= 1 ? "vits_model_set_speaker(" + std::to_string(speaker) + "): this model has a single speaker and no speaker conditioning (use -1)"
-                       : "vits_model_set_speaker(" + std::to_string(speaker) + "): outside [-1, " + std::to_string(n) + ")");
+    std::string err;  // (file speakers + registered voices: the range rule of every speaker check)
+    if (speaker != -1 && model->eng.check_speaker(speaker, "vits_model_set_speaker(" + std::to_string(speaker) + ")", err, ": outside [-1, ")) {
+        set_err(err);
         return -1;
     }
     model->eng.speaker = speaker;
@@ -264,25 +278,16 @@ VITS_API int vits_model_get_speaker_embedding(vits_model* model, int32_t id, flo
     return rc;
     VITS_CATCH(-1)
 }
-// the three mutating calls: never with batches in flight (a growing table moves under the kernels that read it), never from inside a callback
-// (VITS_ENTER: "model busy")
-#define VITS_VOICES_ENTER(model)                                                                       \
-    VITS_ENTER(model, -1)                                                                              \
-    if ((model)->eng.pending()) {                                                                      \
-        set_err("batches in flight: call vits_model_wait for every submitted batch first");          \
-        return -1;                                                                                     \
-    }
+// the three mutating calls: never with batches in flight (VITS_ENTER_IDLE: a growing table moves under the kernels that read it), never from inside a
+// callback (VITS_ENTER: "model busy")
 VITS_API int vits_model_add_voices(vits_model* model, const float* emb, int32_t n, int32_t* ids_out) {
     VITS_TRY
     if (!model || !emb || !ids_out) {
         set_err("null argument");
         return -1;
     }
-    VITS_VOICES_ENTER(model)
-    std::string err;
-    const int rc = model->eng.add_voices(emb, n, ids_out, err);
-    if (rc != 0) set_err(err);
-    return rc;
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.add_voices(emb, n, ids_out, err); });
     VITS_CATCH(-1)
 }
 VITS_API int vits_model_set_voice(vits_model* model, int32_t voice_id, const float* emb) {
@@ -291,11 +296,8 @@ VITS_API int vits_model_set_voice(vits_model* model, int32_t voice_id, const flo
         set_err("null argument");
         return -1;
     }
-    VITS_VOICES_ENTER(model)
-    std::string err;
-    const int rc = model->eng.set_voice(voice_id, emb, err);
-    if (rc != 0) set_err(err);
-    return rc;
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_voice(voice_id, emb, err); });
     VITS_CATCH(-1)
 }
 VITS_API int vits_model_clear_voices(vits_model* model) {
@@ -304,11 +306,8 @@ VITS_API int vits_model_clear_voices(vits_model* model) {
         set_err("null argument");
         return -1;
     }
-    VITS_VOICES_ENTER(model)
-    std::string err;
-    const int rc = model->eng.clear_voices(err);
-    if (rc != 0) set_err(err);
-    return rc;
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.clear_voices(err); });
     VITS_CATCH(-1)
 }
 
@@ -318,12 +317,7 @@ VITS_API int vits_model_set_prosody(vits_model* model, float speaking_rate, floa
         return -1;
     }
     VITS_ENTER(model, -1)
-    std::string err;
-    if (model->eng.set_prosody(speaking_rate, noise_scale, noise_scale_duration, err) != 0) {
-        set_err(err);
-        return -1;
-    }
-    return 0;
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_prosody(speaking_rate, noise_scale, noise_scale_duration, err); });
 }
 VITS_API int vits_model_get_prosody(const vits_model* model, float* speaking_rate, float* noise_scale, float* noise_scale_duration) {
     if (!model) {
@@ -345,24 +339,8 @@ VITS_API int vits_model_process_batch(vits_model* model, const int32_t* ids, con
         return -1;
     }
     VITS_ENTER(model, -1)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_COUNTER;
-    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
-    std::string err;
-    int rc;
-    try {
-        rc = model->eng.process_batch(ids, id_lengths, batch, id_stride, o, out, err);
-    } catch (...) {
-        if (out) vits_free_batch_result(out);  // (std::bad_alloc on the PCM buffer: nothing half-filled reaches the caller)
-        throw;
-    }
-    if (rc != 0) {
-        set_err(err);
-        if (out) vits_free_batch_result(out);
-    }
-    return rc;
+    const vits_process_opts o = default_opts(opts, VITS_NOISE_COUNTER);
+    return run_engine(out, [&](std::string& err) { return model->eng.process_batch(ids, id_lengths, batch, id_stride, o, out, err); });
     VITS_CATCH(-1)
 }
 
@@ -373,10 +351,7 @@ VITS_API int vits_model_prepare_conversion(vits_model* model) {
         return -1;
     }
     VITS_ENTER(model, -1)
-    std::string err;
-    const int rc = model->eng.prepare_conversion(err);
-    if (rc != 0) set_err(err);
-    return rc;
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.prepare_conversion(err); });
     VITS_CATCH(-1)
 }
 
@@ -389,24 +364,8 @@ VITS_API int vits_model_convert_batch(vits_model* model, const float* pcm, const
         return -1;
     }
     VITS_ENTER(model, -1)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_COUNTER;
-    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
-    std::string err;
-    int rc;
-    try {
-        rc = model->eng.convert_batch(pcm, pcm_lengths, batch, pcm_stride, src_speakers, tgt_speakers, o, out, err);
-    } catch (...) {
-        if (out) vits_free_batch_result(out);
-        throw;
-    }
-    if (rc != 0) {
-        set_err(err);
-        if (out) vits_free_batch_result(out);
-    }
-    return rc;
+    const vits_process_opts o = default_opts(opts, VITS_NOISE_COUNTER);
+    return run_engine(out, [&](std::string& err) { return model->eng.convert_batch(pcm, pcm_lengths, batch, pcm_stride, src_speakers, tgt_speakers, o, out, err); });
     VITS_CATCH(-1)
 }
 
@@ -419,15 +378,10 @@ VITS_API int vits_model_align_batch(vits_model* model, const float* pcm, const i
         return -1;
     }
     VITS_ENTER(model, -1)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_COUNTER;
-    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
-    std::string err;
-    const int rc = model->eng.align_batch(pcm, pcm_lengths, batch, pcm_stride, ids, id_lengths, id_stride, speakers, noise_scale, o, durations, frames, scores, err);
-    if (rc != 0) set_err(err);
-    return rc;
+    const vits_process_opts o = default_opts(opts, VITS_NOISE_COUNTER);
+    return run_engine(nullptr, [&](std::string& err) {
+        return model->eng.align_batch(pcm, pcm_lengths, batch, pcm_stride, ids, id_lengths, id_stride, speakers, noise_scale, o, durations, frames, scores, err);
+    });
     VITS_CATCH(-1)
 }
 
@@ -448,17 +402,11 @@ VITS_API int64_t vits_model_align(vits_model* model, const float* pcm, size_t n,
         set_err("empty input (no ids)");
         return -1;
     }
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.struct_size = sizeof(o);
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_COUNTER;  // (noise_scale 0: nothing is drawn)
+    const vits_process_opts o = default_opts(nullptr, VITS_NOISE_COUNTER);  // (noise_scale 0: nothing is drawn)
     std::vector<int32_t> d(v.size(), 0);
     const int64_t len = (int64_t)n;
-    if (model->eng.align_batch(pcm, &len, 1, len, v.data(), nullptr, (int)v.size(), &speaker, 0.f, o, d.data(), nullptr, nullptr, err) != 0) {
-        set_err(err);
+    if (run_engine(nullptr, [&](std::string& e) { return model->eng.align_batch(pcm, &len, 1, len, v.data(), nullptr, (int)v.size(), &speaker, 0.f, o, d.data(), nullptr, nullptr, e); }) != 0)
         return -1;
-    }
     for (size_t i = 0; i < v.size() && i < cap; ++i) {
         ids[i] = v[i];
         durations[i] = d[i];
@@ -475,25 +423,12 @@ VITS_API vits_result vits_model_convert(vits_model* model, const float* pcm, siz
         return r;
     }
     VITS_ENTER(model, r)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.struct_size = sizeof(o);
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_REFERENCE;
+    const vits_process_opts o = default_opts(nullptr, VITS_NOISE_REFERENCE);
     vits_batch_result br;
     std::memset(&br, 0, sizeof(br));
-    std::string err;
     const int64_t len = (int64_t)n;
-    if (model->eng.convert_batch(pcm, &len, 1, len, &src_speaker, &tgt_speaker, o, &br, err) != 0) {
-        set_err(err);
-        vits_free_batch_result(&br);
-        return r;
-    }
-    r.size = (size_t)br.lengths[0];
-    r.data = br.data;  // (one utterance: its row is the result)
-    br.data = nullptr;
-    vits_free_batch_result(&br);
-    return r;
+    if (run_engine(&br, [&](std::string& err) { return model->eng.convert_batch(pcm, &len, 1, len, &src_speaker, &tgt_speaker, o, &br, err); }) != 0) return r;
+    return take_row(br);
     VITS_CATCH(r)
 }
 
@@ -505,15 +440,8 @@ VITS_API int vits_model_submit_batch(vits_model* model, const int32_t* ids, cons
         return -1;
     }
     VITS_ENTER(model, -1)
-    vits_process_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.mode = VITS_MODE_DEFAULT;
-    o.noise_kind = VITS_NOISE_COUNTER;
-    if (opts) std::memcpy(&o, opts, std::min<size_t>(sizeof(o), opts->struct_size ? opts->struct_size : sizeof(o)));
-    std::string err;
-    const int rc = model->eng.submit_batch(ids, id_lengths, batch, id_stride, o, err);
-    if (rc != 0) set_err(err);
-    return rc;
+    const vits_process_opts o = default_opts(opts, VITS_NOISE_COUNTER);
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.submit_batch(ids, id_lengths, batch, id_stride, o, err); });
     VITS_CATCH(-1)
 }
 
@@ -525,20 +453,7 @@ VITS_API int vits_model_wait(vits_model* model, vits_batch_result* out) {
         return -1;
     }
     VITS_ENTER(model, -1)
-    std::string err;
-    int rc;
-    try {
-        rc = model->eng.wait_batch(out, err);
-    } catch (...) {
-        // (std::bad_alloc on the PCM buffer: the arrays already allocated go back, *out is left zeroed, the batch stays waitable)
-        if (out) vits_free_batch_result(out);
-        throw;
-    }
-    if (rc != 0) {
-        set_err(err);
-        if (out) vits_free_batch_result(out);
-    }
-    return rc;
+    return run_engine(out, [&](std::string& err) { return model->eng.wait_batch(out, err); });
     VITS_CATCH(-1)
 }
 
@@ -556,10 +471,7 @@ VITS_API int vits_model_sync(vits_model* model) {
     VITS_TRY
     if (!model) return -1;
     VITS_ENTER(model, -1)
-    std::string err;
-    const int rc = model->eng.sync(err);
-    if (rc) set_err(err);
-    return rc;
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.sync(err); });
     VITS_CATCH(-1)
 }
 
@@ -671,11 +583,7 @@ VITS_API int64_t vits_model_file_tokenize(const char* model_bytes, size_t size, 
 
 VITS_API int vits_prof_enable(vits_model* model, int32_t on) {
     if (!model) return -1;
-    VITS_ENTER(model, -1)
-    if (model->eng.pending()) {
-        set_err("batches in flight: call vits_model_wait for every submitted batch first");
-        return -1;
-    }
+    VITS_ENTER_IDLE(model, -1)
     model->eng.prof.on = on != 0;
     return 0;
 }

@@ -114,20 +114,26 @@ int Engine::sync(std::string& err) {
     return 0;
 }
 
+int Engine::check_speaker(int s, const std::string& who, std::string& err, const char* outside) const {
+    if (s == -1) return 0;
+    if (hp.num_speakers <= 1) {
+        err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
+        return -1;
+    }
+    if (!speaker_in_range(s)) {
+        err = who + outside + std::to_string(speaker_limit()) + ")";
+        return -1;
+    }
+    return 0;
+}
+
 int Engine::check_speakers(const vits_process_opts& o, int B, std::string& err) const {
     for (int b = 0; b < B; ++b) {
         const int s = speaker_of(o, b);
         if (s == -1) continue;
         const std::string who = (o.speaker_ids ? "speaker_ids[" + std::to_string(b) + "] = " : "the model's default speaker (utterance " + std::to_string(b) + ") = ") +
                                 std::to_string(s);
-        if (hp.num_speakers <= 1) {
-            err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
-            return -1;
-        }
-        if (!speaker_in_range(s)) {
-            err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
-            return -1;
-        }
+        if (check_speaker(s, who, err)) return -1;
         if (ggml_tables == 1) {
             err = who + ": vits_model_set_ggml_tables(model, 1) runs stage one in the CPU oracle's exact order, which has no speaker conditioning (use -1, or tables mode 0 / 2)";
             return -1;
@@ -188,10 +194,7 @@ int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, cons
 
 int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                           std::string& err) {
-    if (pending()) {
-        err = "batches in flight: call vits_model_wait for every submitted batch first";
-        return -1;
-    }
+    if (refuse_pending(err)) return -1;
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
@@ -265,7 +268,7 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
             if (out->data)
                 for (int b = 0; b < nb[h]; ++b) {
                     float* dst = out->data + (size_t)(b0[h] + b) * stride;
-                    std::memcpy(dst, p.host + (size_t)b * p.stride, sizeof(float) * p.stride);
+                    std::memcpy(dst, (const float*)p.host.p + (size_t)b * p.stride, sizeof(float) * p.stride);
                     // (columns past a row's own length are unspecified in the unsplit result too; keep them defined)
                     if (p.stride < stride) std::memset(dst + p.stride, 0, sizeof(float) * (stride - p.stride));
                 }
@@ -327,7 +330,7 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
         out->data = nullptr;
         if (p.host_copy) {
             out->data = new float[(size_t)p.B * p.stride];
-            std::memcpy(out->data, p.host, sizeof(float) * (size_t)p.B * p.stride);
+            std::memcpy(out->data, p.host.p, sizeof(float) * (size_t)p.B * p.stride);
         }
     }
     p.active = false;
@@ -335,29 +338,12 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
     return 0;
 }
 
-namespace {
-// the stream member of the engine is "the stream being queued on": stage one of a pipelined batch swaps the front-end stream in
-struct StreamSwap {
-    hipStream_t& slot;
-    hipStream_t saved;
-    StreamSwap(hipStream_t& s, hipStream_t to) : slot(s), saved(s) { slot = to; }
-    void restore() { slot = saved; }
-    ~StreamSwap() { slot = saved; }
-};
-}  // namespace
-
 // opts.durations_out: the durations of stage one (dur [B][id_stride], integer-valued floats, 0 past each utterance) queued for the host beside the
 // frame counts, into grow-only pinned memory; store_durations converts them once that copy has landed
-hipError_t Engine::copy_durations(const Call& c, float*& pinned, size_t& cap) {
+hipError_t Engine::copy_durations(const Call& c, PinnedBuf<float>& pinned) {
     const size_t n = (size_t)c.B * c.id_stride;
-    if (cap < n) {
-        if (pinned) hipHostFree(pinned);
-        pinned = nullptr;
-        cap = 0;
-        if (hipError_t e = hipHostMalloc((void**)&pinned, sizeof(float) * (n + n / 4 + 64), hipHostMallocDefault)) return e;
-        cap = n + n / 4 + 64;
-    }
-    return hipMemcpyAsync(pinned, c.s1.dur, sizeof(float) * n, hipMemcpyDeviceToHost, stream);
+    if (hipError_t e = pinned.ensure(n, n + n / 4 + 64)) return e;
+    return hipMemcpyAsync(pinned.p, c.s1.dur, sizeof(float) * n, hipMemcpyDeviceToHost, stream);
 }
 void Engine::store_durations(const Call& c, const float* pinned) const {
     const size_t n = (size_t)c.B * c.id_stride;
@@ -421,7 +407,8 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     // pipelined batch: stage one goes to the front-end stream (the per-kernel profiler needs kernels that do not overlap: then,
     // and under VITS_NO_PIPELINE, everything stays on the main stream and a pipelined batch is merely a deferred result)
     const bool overlap = pend && front_ && !prof.on;
-    StreamSwap s1_stream(stream, overlap ? front_ : stream);
+    // (the stream member of the engine is "the stream being queued on": stage one of a pipelined batch swaps the front-end stream in)
+    ScopedSet<hipStream_t> s1_stream(stream, overlap ? front_ : stream);
     hipStream_t const main_stream = s1_stream.saved;
     if (overlap && async_tail_) {
         // an earlier opts.async call returned without synchronising: its flow / vocoder may still be reading stage-one arena 0 on the
@@ -438,14 +425,8 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         const double ls = o.speaking_rates ? 1.0 / (double)o.speaking_rates[0] : 1.0 / (double)speaking_rate;
         const size_t per_id = (size_t)std::ceil(knobs.ref_ahead_frames_per_id * std::max(1.0, ls));
         const size_t want = (size_t)hp.flow_size * (per_id * c.Tmax + 64);
-        if (ref_noise_cap_ < want) {
-            if (ref_noise_pinned_) hipHostFree(ref_noise_pinned_);
-            ref_noise_pinned_ = nullptr;
-            ref_noise_cap_ = 0;
-            HIP_OK(hipHostMalloc((void**)&ref_noise_pinned_, want * sizeof(float), hipHostMallocDefault));
-            ref_noise_cap_ = want;
-        }
-        ref_ahead_.start((size_t)2 * c.tlen[0], ref_noise_pinned_, ref_noise_cap_);
+        HIP_OK(ref_noise_pinned_.ensure(want, want));
+        ref_ahead_.start((size_t)2 * c.tlen[0], ref_noise_pinned_.p, ref_noise_pinned_.cap);
         c.ref_ahead = &ref_ahead_;
     }
     if (layout_stage_one(c)) return -1;
@@ -467,36 +448,24 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     } else if (pend) {
         // through pinned memory behind an event on the stage-one stream: the host waits for this batch's stage one only, while the
         // previous batch's vocoder keeps the device busy
-        if (pend->frames_cap < (size_t)B) {
-            if (pend->frames_pinned) hipHostFree(pend->frames_pinned);
-            pend->frames_pinned = nullptr;
-            pend->frames_cap = 0;
-            HIP_OK(hipHostMalloc((void**)&pend->frames_pinned, sizeof(int) * (size_t)(B + 64), hipHostMallocDefault));
-            pend->frames_cap = (size_t)B + 64;
-        }
-        HIP_OK(hipMemcpyAsync(pend->frames_pinned, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
-        if (o.durations_out) HIP_OK(copy_durations(c, pend->dur_pinned, pend->dur_cap));
+        HIP_OK(pend->frames_pinned.ensure((size_t)B, (size_t)B + 64));
+        HIP_OK(hipMemcpyAsync(pend->frames_pinned.p, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+        if (o.durations_out) HIP_OK(copy_durations(c, pend->dur_pinned));
         HIP_OK(hipEventRecord(pend->s1_done, stream));
         prof.fence();
         HIP_OK(hipEventSynchronize(pend->s1_done));
-        std::copy(pend->frames_pinned, pend->frames_pinned + B, frames.begin());
-        if (o.durations_out) store_durations(c, pend->dur_pinned);
+        std::copy(pend->frames_pinned.p, pend->frames_pinned.p + B, frames.begin());
+        if (o.durations_out) store_durations(c, pend->dur_pinned.p);
     } else {
         // (pinned destination, owned by the engine: into the caller-side std::vector the copy went through the runtime's staging buffer, + 15 us per batch-1 call)
-        if (frames_host_cap_ < (size_t)B) {
-            if (frames_host_) hipHostFree(frames_host_);
-            frames_host_ = nullptr;
-            frames_host_cap_ = 0;
-            HIP_OK(hipHostMalloc((void**)&frames_host_, sizeof(int) * ((size_t)B + 64), hipHostMallocDefault));
-            frames_host_cap_ = (size_t)B + 64;
-        }
-        HIP_OK(hipMemcpyAsync(frames_host_, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
-        if (o.durations_out) HIP_OK(copy_durations(c, dur_host_, dur_host_cap_));
+        HIP_OK(frames_host_.ensure((size_t)B, (size_t)B + 64));
+        HIP_OK(hipMemcpyAsync(frames_host_.p, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+        if (o.durations_out) HIP_OK(copy_durations(c, dur_host_));
         prof.fence();
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
-        std::copy(frames_host_, frames_host_ + B, frames.begin());
-        if (o.durations_out) store_durations(c, dur_host_);
+        std::copy(frames_host_.p, frames_host_.p + B, frames.begin());
+        if (o.durations_out) store_durations(c, dur_host_.p);
     }
     if (o.durations_out && o.fixed_duration > 0)  // (no device read: every token lasts fixed_duration frames)
         for (int b = 0; b < B; ++b)
@@ -507,17 +476,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         HIP_OK(hipStreamWaitEvent(main_stream, pend->s1_done, 0));
     }
     s1_stream.restore();
-    for (int b = 0; b < B; ++b) {
-        c.Lmax = std::max(c.Lmax, frames[b]);
-        c.sum_frames += frames[b];
-    }
-    c.slen.assign(n_up + 1, std::vector<int>(B));
-    c.smax.assign(n_up + 1, 0);
-    for (int i = 0; i <= n_up; ++i)
-        for (int b = 0; b < B; ++b) {
-            c.slen[i][b] = frames[b] * c.smul[i] + c.sadd[i];
-            c.smax[i] = std::max(c.smax[i], c.slen[i][b]);
-        }
+    c.frames_known();
     if (o.collect_taps) {
         TensorRef d;
         d.p = c.s1.dur;
@@ -625,15 +584,9 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         if (pend) {
             // a pipelined batch: the table travels through pinned memory owned by the slot (it outlives this call), so that the submit does not
             // drain the main stream — the previous batch's vocoder is running there (the synchronise below serialised windowed submits)
-            if (pend->win_cap < wl.size()) {
-                if (pend->win_pinned) hipHostFree(pend->win_pinned);
-                pend->win_pinned = nullptr;
-                pend->win_cap = 0;
-                HIP_OK(hipHostMalloc((void**)&pend->win_pinned, sizeof(int) * (wl.size() + wl.size() / 4 + 64), hipHostMallocDefault));
-                pend->win_cap = wl.size() + wl.size() / 4 + 64;
-            }
-            std::memcpy(pend->win_pinned, wl.data(), sizeof(int) * wl.size());
-            HIP_OK(hipMemcpyAsync(c.s2.win_lens, pend->win_pinned, sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
+            HIP_OK(pend->win_pinned.ensure(wl.size(), wl.size() + wl.size() / 4 + 64));
+            std::memcpy(pend->win_pinned.p, wl.data(), sizeof(int) * wl.size());
+            HIP_OK(hipMemcpyAsync(c.s2.win_lens, pend->win_pinned.p, sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
             prof.fence();
         } else {
             HIP_OK(hipMemcpyAsync(c.s2.win_lens, wl.data(), sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
@@ -643,14 +596,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     }
     if (o.on_chunk) {
         const size_t need = (size_t)B * out_stride * sizeof(float);
-        if (need > pinned_cap_) {
-            if (pinned_) hipHostFree(pinned_);
-            pinned_ = nullptr;
-            pinned_cap_ = 0;
-            HIP_OK(hipHostMalloc((void**)&pinned_, need, hipHostMallocDefault));
-            pinned_cap_ = need;
-        }
-        host_pcm = (float*)pinned_;
+        HIP_OK(pinned_.ensure(need, need));
+        host_pcm = (float*)pinned_.p;
     }
     // hands the finished window `w` to the caller's sink (blocks until its PCM is on the host)
     auto deliver = [&](size_t w) -> int {
@@ -740,14 +687,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
-            if (need > pend->host_cap) {
-                if (pend->host) hipHostFree(pend->host);
-                pend->host = nullptr;
-                pend->host_cap = 0;
-                HIP_OK(hipHostMalloc((void**)&pend->host, need + need / 8, hipHostMallocDefault));
-                pend->host_cap = need + need / 8;
-            }
-            HIP_OK(hipMemcpy2DAsync(pend->host, pend->stride * 4, wave_dst, (size_t)wave_stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+            HIP_OK(pend->host.ensure(need, need + need / 8));
+            HIP_OK(hipMemcpy2DAsync(pend->host.p, pend->stride * 4, wave_dst, (size_t)wave_stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
         }
         HIP_OK(hipEventRecord(pend->done, stream));
         prof.fence();

@@ -10,6 +10,7 @@
 #include <memory>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/vits.h"
@@ -80,6 +81,33 @@ struct Arena {
         return off <= cap ? p : nullptr;
     }
     ~Arena();
+};
+
+// Grow-only pinned host memory. ensure(n, grown): room for n elements, allocating `grown` (>= n: the site's own slack) when it has to grow; the
+// old contents are gone then.
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    hipError_t ensure(size_t n, size_t grown) {
+        if (cap >= n) return hipSuccess;
+        if (p) hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * grown, hipHostMallocDefault);
+        if (e == hipSuccess) cap = grown;
+        return e;
+    }
+    void swap(PinnedBuf& o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+    ~PinnedBuf() {
+        if (p) hipHostFree(p);
+    }
 };
 
 struct Tap {
@@ -188,6 +216,12 @@ class Engine {
     int submit_batch(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, std::string& err);
     int wait_batch(vits_batch_result* out, std::string& err);
     int pending() const { return (int)(submit_seq_.load(std::memory_order_acquire) - wait_seq_.load(std::memory_order_acquire)); }  // (any thread may ask)
+    // the refusal of every entry point that must not run beside submitted batches: true + the message while some are in flight
+    bool refuse_pending(std::string& err) const {
+        if (!pending()) return false;
+        err = "batches in flight: call vits_model_wait for every submitted batch first";
+        return true;
+    }
     int sync(std::string& err);
     // One call at a time per handle (the reference's contract too: process writes member tensors, src/include/vits.h:22-30). The ABI
     // takes this flag around every entry point that touches the engine; a second thread gets "model busy" instead of a race.
@@ -209,9 +243,12 @@ class Engine {
     // 0, or -1 + a message naming the utterance: every speaker of the call in [-1, num_speakers), none >= 0 on a single-speaker model or with
     // the exact-order stage one (ggml_tables == 1)
     int check_speakers(const vits_process_opts& o, int B, std::string& err) const;
+    // one speaker id against the rule of every speaker check: 0, or -1 + `who` and what is wrong with it (a single-speaker model takes -1 only;
+    // otherwise -1 <= s < speaker_limit()). `outside`: the wording between `who` and the range (vits_model_set_speaker has its own)
+    int check_speaker(int s, const std::string& who, std::string& err, const char* outside = " is outside [-1, ") const;
     // custom voices (engine_voices.cpp, include/vits.h vits_model_add_voices): speaker embeddings registered at run time. Voice k has the id
     // num_speakers + k and row 1 + num_speakers + k of the effective-bias tables, so the per-call row upload (speaker + 1) and every kernel stay as they are.
-    // The ONE range rule of every speaker check (check_speakers, conversion, alignment, vits_model_set_speaker): -1 <= s < speaker_limit().
+    // The ONE range rule of every speaker check (check_speaker): -1 <= s < speaker_limit().
     int num_voices() const { return hp.speaker_embedding_size > 0 ? (int)(voices_.size() / (size_t)hp.speaker_embedding_size) : 0; }
     int speaker_limit() const { return hp.num_speakers + num_voices(); }
     bool speaker_in_range(int s) const { return s >= -1 && s < speaker_limit(); }
@@ -291,6 +328,9 @@ class Engine {
         }
     };
     std::vector<PackSrc> packs_;
+    // the 16-bit A fragments of one conv on the device (VITS_ARITH_F16 / _BF16). *d is the buffer as soon as it is allocated: the caller owns it, also when
+    // the upload behind it failed
+    hipError_t pack16_device(const PackSrc& ps, int arith16, uint16_t** d, int64_t* bytes);
     struct Lat16Lazy {
         PackedConv* pc;
         size_t n;  // floats of the packed array
@@ -300,6 +340,15 @@ class Engine {
     int ensure_lat16(std::string& err);
     Ref16 x16_[3];           // per-stream scratch for the 16-bit copy of a conv input (transparent 16-bit path)
     size_t x16_cap_[3] = {0, 0, 0};
+    // the scratch of the layout just made: `elems` elements behind every pointer that is not null
+    void set_x16_scratch(uint16_t* p0, uint16_t* p1, uint16_t* p2, size_t elems) {
+        uint16_t* const p[3] = {p0, p1, p2};
+        for (int j = 0; j < 3; ++j) {
+            x16_[j] = Ref16();
+            x16_[j].p = p[j];
+            x16_cap_[j] = p[j] ? elems : 0;
+        }
+    }
     bool vocoder_group_ok_ = false;  // every vocoder channel count is a multiple of 8: group-layout fast path available
     hipError_t conv16_transparent(const char* name, const PackedConv& w, const ConvCall& c, hipStream_t stream);
     hipError_t conv16(const char* name, const PackedConv& w, const Conv16Call& c, hipStream_t stream, double bytes);
@@ -318,45 +367,35 @@ class Engine {
         size_t stride = 0;
         std::vector<int64_t> lengths, frames;
         bool host_copy = false;
-        float* host = nullptr;
-        size_t host_cap = 0;  // bytes
-        int* frames_pinned = nullptr;
-        size_t frames_cap = 0;  // ints
-        int* win_pinned = nullptr;  // vocoder-window length table of a windowed batch (host side of its H2D copy)
-        size_t win_cap = 0;         // ints
-        float* dur_pinned = nullptr;  // opts.durations_out: the batch's durations, copied beside the frame counts
-        size_t dur_cap = 0;           // floats
+        PinnedBuf<char> host;  // (sized in bytes; read as float [B][stride])
+        PinnedBuf<int> frames_pinned;
+        PinnedBuf<int> win_pinned;    // vocoder-window length table of a windowed batch (host side of its H2D copy)
+        PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
     hipStream_t front_ = nullptr;             // stage one of pipelined batches (created on first use)
     // batch-1 calls with the reference noise stream: the prior noise is drawn into pinned memory while stage one runs (engine.cpp)
-    float* ref_noise_pinned_ = nullptr;
-    size_t ref_noise_cap_ = 0;  // floats
+    PinnedBuf<float> ref_noise_pinned_;
     RefNoiseAhead ref_ahead_;
-    float* dur_noise_pinned_ = nullptr;  // the [T, 2] duration noise of such a call
-    size_t dur_noise_cap_ = 0;
+    PinnedBuf<float> dur_noise_pinned_;  // the [T, 2] duration noise of such a call
     hipEvent_t dur_noise_ev_ = nullptr;
     bool async_tail_ = false;                 // the last process_batch returned with device work still queued (opts.async)
     hipEvent_t ev_async_ = nullptr;           // orders the front-end stream behind that tail
     int process_split(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err);
     int process_impl(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err,
                      Pending* pend);
-    hipError_t copy_durations(const Call& c, float*& pinned, size_t& cap);
+    hipError_t copy_durations(const Call& c, PinnedBuf<float>& pinned);
     void store_durations(const Call& c, const float* pinned) const;
     // The three resblocks of a vocoder stage (kernel sizes 3/7/11) are independent chains of six convolutions; they run on
     // three streams so that the tail of one kernel's grid overlaps the head of another's. side_[j-1] carries resblock j.
     hipStream_t side_[2] = {nullptr, nullptr};
     hipEvent_t ev_fork_ = nullptr, ev_done_[3] = {nullptr, nullptr, nullptr};
     int halo_frames_ = 0;      // receptive field of the vocoder in frames, one side (computed at load)
-    void* pinned_ = nullptr;   // grow-only pinned staging for streamed PCM
-    int* frames_host_ = nullptr;  // pinned [frames_host_cap_]: destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
-    size_t frames_host_cap_ = 0;
-    int* align_host_ = nullptr;  // pinned [align_host_cap_]: durations and scores of an alignment call (engine_align.cpp)
-    size_t align_host_cap_ = 0;
-    float* dur_host_ = nullptr;  // pinned: a synchronous call's durations for opts.durations_out, copied beside the frame counts
-    size_t dur_host_cap_ = 0;    // floats
-    size_t pinned_cap_ = 0;
+    PinnedBuf<char> pinned_;       // staging for streamed PCM (sized in bytes)
+    PinnedBuf<int> frames_host_;   // destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
+    PinnedBuf<int> align_host_;    // durations and scores of an alignment call (engine_align.cpp)
+    PinnedBuf<float> dur_host_;    // a synchronous call's durations for opts.durations_out, copied beside the frame counts
     // arithmetic of the convolutions being queued right now: `arith`, or fp32 while stage one runs under
     // VITS_ARITH_SCOPE_FLOW_VOCODER (every conv wrapper and fused kernel reads this one, never `arith` itself)
     int arith_now_ = VITS_ARITH_F32;
@@ -375,8 +414,7 @@ class Engine {
     GgmlTables ggml_tabs_;              // what the stage-one kernels receive: null pointers unless ggml_tables
     uint16_t* ggml_tab_dev_ = nullptr;  // [2][65536]: gelu, exp
     struct HStage {  // pinned staging of the per-call host header (ids, lengths, stage tables)
-        int* p = nullptr;
-        size_t cap = 0;
+        PinnedBuf<int> buf;
         hipEvent_t ev = nullptr;
         bool pending = false;
     } hstage_[2];
@@ -413,6 +451,10 @@ class Engine {
         VoiceSeg* d_segs = nullptr;
         int tiles = 0;
     } vt_main_, vt_post_;
+    // Builds the table of vt (segments, row stride and the segments' host conv rows filled in by the caller) for the file's speakers: allocates
+    // num_speakers + 1 rows, one speaker_bias launch per segment (row 0 = the conv's plain bias), repoints the segments' convs into row 0. false: the
+    // device failed (the convs keep their biases; the caller has the message)
+    bool build_speaker_table(VoiceTable& vt, const std::vector<float>& emb);
     std::vector<float> spk_emb_;  // host [num_speakers][E]: embed_speaker widened to fp32 (vits_model_get_speaker_embedding, Model.add_voice_mix)
     std::vector<float> voices_;   // host [num_voices][E]: the registered vectors
     struct VoiceResident;  // engine_voices.cpp: a table's conditioning convs staged on the device, not yet the table's
@@ -447,6 +489,14 @@ class Engine {
     int run_prior_sampling(Call& c);
     int run_flow(Call& c) { return run_coupling(c, false); }
     int run_coupling(Call& c, bool forward);  // the residual coupling flow: reverse (TTS), or forward (voice conversion)
+    // One WaveNet stack (the flow's coupling layers, the posterior encoder) over h = rows [0, H) of s2.hout: zeroes the skip accumulator (rows [H, 2H)), then
+    // every layer as one fused launch where the kernels take it, else as gated conv + res/skip 1x1. Speaker rows: c.spk.
+    struct WaveNetLabels {
+        const char *layer, *gated_conv, *conv1x1;  // profiler entries
+    };
+    int run_wavenet(Call& c, const std::vector<PackedConv>& in_layers, const std::vector<PackedConv>& res_skip, int n_layers, const WaveNetLabels& lab);
+    int upload_host_noise(Call& c);  // opts.noise_prior or the reference stream -> s2.noise for every utterance, and the noise_prior tap
+    void set_stage_affine(Call& c) const;  // c.smul / c.sadd: vocoder stage lengths as affine functions of the frame count
     int run_conversion_front(Call& c);        // spectrogram -> posterior encoder -> forward flow (engine_convert.cpp)
     // the PCM side of a conversion or alignment call (engine_convert.cpp): lengths checked, then frame counts, arena (current stage-one slot), uploads
     int check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::string& err) const;

@@ -10,10 +10,7 @@ namespace vits {
 int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* ids, const int32_t* id_lens, int id_stride,
                         const int32_t* speakers, float noise_scale, const vits_process_opts& o, int32_t* durations, int64_t* frames_out, float* scores,
                         std::string& err) {
-    if (pending()) {
-        err = "batches in flight: call vits_model_wait for every submitted batch first";
-        return -1;
-    }
+    if (refuse_pending(err)) return -1;
     if (B <= 0 || id_stride <= 0) {
         err = "empty batch";
         return -1;
@@ -22,28 +19,22 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
         err = "null PCM, lengths, ids or durations, or pcm_stride <= 0";
         return -1;
     }
-    {
-        const char* what = o.fixed_duration > 0        ? "fixed_duration"
-                           : o.frames_only             ? "frames_only"
-                           : o.async                   ? "async"
-                           : o.out_device              ? "out_device"
-                           : o.skip_host_copy          ? "skip_host_copy"
-                           : o.vocoder_chunk_frames > 0 ? "vocoder_chunk_frames"
-                           : o.on_chunk                ? "on_chunk"
-                                                       : nullptr;
-        if (what) {
-            err = std::string("alignment does not take opts.") + what + " (it produces no audio: the frame counts come from the input PCM and the call is synchronous)";
-            return -1;
-        }
+    if (const char* what = first_set({{"fixed_duration", o.fixed_duration > 0},
+                                      {"frames_only", o.frames_only != 0},
+                                      {"async", o.async != 0},
+                                      {"out_device", o.out_device != nullptr},
+                                      {"skip_host_copy", o.skip_host_copy != 0},
+                                      {"vocoder_chunk_frames", o.vocoder_chunk_frames > 0},
+                                      {"on_chunk", o.on_chunk != nullptr}})) {
+        err = std::string("alignment does not take opts.") + what + " (it produces no audio: the frame counts come from the input PCM and the call is synchronous)";
+        return -1;
     }
     if (o.speaker_ids) {
         err = "alignment takes the speaker of the recording from its speakers argument, not from opts.speaker_ids";
         return -1;
     }
-    if (o.speaking_rates || o.noise_scales || o.noise_scale_durations || o.duration_override || o.durations_out) {
-        err = std::string("alignment does not take opts.") +
-              (o.speaking_rates ? "speaking_rates" : o.noise_scales ? "noise_scales" : o.noise_scale_durations ? "noise_scale_durations" : o.duration_override ? "duration_override" : "durations_out") +
-              " (it has no duration prediction; the scale of the posterior draw is the call's noise_scale)";
+    if (const char* what = prosody_opt_set(o)) {
+        err = std::string("alignment does not take opts.") + what + " (it has no duration prediction; the scale of the posterior draw is the call's noise_scale)";
         return -1;
     }
     if (!std::isfinite(noise_scale) || noise_scale < 0.f || noise_scale > 10.f) {
@@ -56,14 +47,7 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
         const int s = speakers ? speakers[b] : -1;
         if (s == -1) continue;
         const std::string who = "speakers[" + std::to_string(b) + "] = " + std::to_string(s) + " (speaker of recording " + std::to_string(b) + ")";
-        if (hp.num_speakers <= 1) {
-            err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
-            return -1;
-        }
-        if (!speaker_in_range(s)) {
-            err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
-            return -1;
-        }
+        if (check_speaker(s, who, err)) return -1;
     }
     Call c(o, err, ids, B, id_stride);
     Call::Vc vc;
@@ -120,11 +104,7 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
     arith_now_ = arith_kernels();
 
     // ---- the audio side: the conversion front end; its own arena goes to stage-one slot 1 (no batch is in flight: the slot is free) -------------------
-    struct SlotGuard {
-        int& slot;
-        ~SlotGuard() { slot = 0; }
-    } slot_guard{a1_slot_};
-    a1_slot_ = 1;
+    ScopedSet<int> slot(a1_slot_, 1);
     if (layout_conversion(c, pcm, pcm_lens, pcm_stride, speakers, nullptr, nmax)) return -1;
     const int Lmax = c.Lmax, ls = c.ls = round_up(Lmax, 32);
     const int* d_frames = c.s1.frames;
@@ -152,22 +132,8 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
         // results, one block = one D2H copy: durations [B][id_stride] ints | scores [B] floats
         d_dur = a.alloc<int>((size_t)B * id_stride + B);
     };
-    {
-        Arena measure;
-        measure.cap = (size_t)1 << 60;
-        layout(measure);
-        const size_t need = measure.off + 4096;
-        measure.cap = 0;
-        if (need > a2_.cap) HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(a2_.reserve(need));
-        layout(a2_);
-        for (int j = 0; j < 3; ++j) {
-            x16_[j] = Ref16();
-            x16_cap_[j] = 0;
-        }
-        x16_[0].p = s2.x16[0];
-        x16_cap_[0] = x16_elems;
-    }
+    if (arena_layout(a2_, stream, err, layout)) return -1;
+    set_x16_scratch(s2.x16[0], nullptr, nullptr, x16_elems);
     if (run_conversion_front(c)) return -1;  // z_p in s2.zp, logical channel order
 
     // ---- likelihood matrix and search (align.hip), fp32 in every arithmetic mode ----------------------------------------------------------------
@@ -207,19 +173,13 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
     }
     // ---- results: one copy, one wait -------------------------------------------------------------------------------------------------------------
     const size_t n_res = (size_t)B * id_stride + B;
-    if (align_host_cap_ < n_res) {
-        if (align_host_) hipHostFree(align_host_);
-        align_host_ = nullptr;
-        align_host_cap_ = 0;
-        HIP_OK(hipHostMalloc((void**)&align_host_, sizeof(int) * (n_res + n_res / 4 + 64), hipHostMallocDefault));
-        align_host_cap_ = n_res + n_res / 4 + 64;
-    }
-    HIP_OK(hipMemcpyAsync(align_host_, d_dur, sizeof(int) * n_res, hipMemcpyDeviceToHost, stream));
+    HIP_OK(align_host_.ensure(n_res, n_res + n_res / 4 + 64));
+    HIP_OK(hipMemcpyAsync(align_host_.p, d_dur, sizeof(int) * n_res, hipMemcpyDeviceToHost, stream));
     prof.fence();
     HIP_OK(hipStreamSynchronize(stream));
     prof.fence();
-    std::memcpy(durations, align_host_, sizeof(int32_t) * (size_t)B * id_stride);
-    if (scores) std::memcpy(scores, align_host_ + (size_t)B * id_stride, sizeof(float) * B);
+    std::memcpy(durations, align_host_.p, sizeof(int32_t) * (size_t)B * id_stride);
+    if (scores) std::memcpy(scores, align_host_.p + (size_t)B * id_stride, sizeof(float) * B);
     if (frames_out)
         for (int b = 0; b < B; ++b) frames_out[b] = c.frames[b];
     return 0;

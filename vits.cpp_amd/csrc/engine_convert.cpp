@@ -67,49 +67,17 @@ int Engine::prepare_conversion(std::string& err) {
             err = "tensor 'posterior_encoder.wavenet.cond_layer' must be a [" + std::to_string(2 * H * nl) + ", " + std::to_string(E) + ", 1] conv with a bias";
             return -1;
         }
-        const int64_t rs = (int64_t)nl * 2 * H;  // segments of 2H floats: multiples of four (float4 bias loads)
-        const size_t table_floats = (size_t)(N + 1) * rs;
-        std::vector<void*> tmp;
-        auto dev = [&](const std::vector<float>& v) -> float* {
-            float* d = nullptr;
-            if (hipMalloc((void**)&d, std::max<size_t>(v.size(), 1) * sizeof(float)) != hipSuccess) return nullptr;
-            tmp.push_back(d);
-            if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-            return d;
-        };
-        float* table = nullptr;
-        bool ok = hipMalloc((void**)&table, table_floats * sizeof(float)) == hipSuccess;
-        if (ok) {
-            owned_.push_back(table);
-            weight_bytes += (int64_t)table_floats * 4;
-        }
-        const std::vector<float> cond_w = tw->to_f32(), cond_b = tb->to_f32();
-        const float* d_emb = ok ? dev(te->to_f32()) : nullptr;
-        const float* d_w = ok ? dev(cond_w) : nullptr;
-        const float* d_b = ok ? dev(cond_b) : nullptr;
-        ok = ok && d_emb && d_w && d_b;
-        for (int l = 0; l < nl && ok; ++l)
-            ok = launch_speaker_bias(post_.in_layers[l].bias, d_w + (int64_t)2 * H * l * E, d_b + 2 * H * l, d_emb, 2 * H, E, N, table + (int64_t)2 * H * l, rs,
-                                     stream) == hipSuccess;
-        ok = ok && hipStreamSynchronize(stream) == hipSuccess;
-        for (void* p : tmp) hipFree(p);
-        if (!ok) {
-            err = "could not build the posterior encoder's speaker bias table on the device";
-            return -1;
-        }
-        for (int l = 0; l < nl; ++l) {
-            post_.in_layers[l].bias = table + (int64_t)2 * H * l;
-            post_.in_layers[l].bias_rs = rs;
-        }
         // custom voices (engine_voices.cpp): this table takes the same rows as load_speakers' — the voices registered so far now (the same kernel and
         // vectors as a registration after this call: the same rows either way), later ones as they come
         VoiceTable vt;  // (becomes vt_post_ only once it holds the registered voices' rows: a failure below leaves the registry serving the main table alone)
-        vt.table = table;
-        vt.rs = rs;
-        vt.cap_rows = N + 1;
+        vt.rs = (int64_t)nl * 2 * H;  // segments of 2H floats: multiples of four (float4 bias loads)
         for (int l = 0; l < nl; ++l) vt.segs.push_back({&post_.in_layers[l], 2 * H, (int64_t)2 * H * l});
-        vt.cond_w = cond_w;
-        vt.cond_b = cond_b;
+        vt.cond_w = tw->to_f32();
+        vt.cond_b = tb->to_f32();
+        if (!build_speaker_table(vt, te->to_f32())) {
+            err = "could not build the posterior encoder's speaker bias table on the device";
+            return -1;
+        }
         if (num_voices() > 0 && voice_rows({&vt}, voices_.data(), num_voices(), 1 + N, err)) return -1;
         vt_post_ = std::move(vt);
     }
@@ -134,13 +102,7 @@ int Engine::prepare_conversion(std::string& err) {
     if (arith == VITS_ARITH_F16 || arith == VITS_ARITH_BF16) {
         for (size_t i = first_pack; i < packs_.size(); ++i) {
             PackSrc& ps = packs_[i];
-            const std::vector<float> w = ps.widen();
-            const std::vector<uint16_t> packed = pack_conv_weights16(w.data(), ps.cout, ps.cin, ps.k, ps.epi, ps.ct_stride, arith);
-            uint16_t* d = nullptr;
-            HIP_OK(hipMalloc((void**)&d, packed.size() * sizeof(uint16_t)));
-            ps.pc->wp16 = d;
-            ps.pc->bytes16 = (int64_t)packed.size() * 2;
-            HIP_OK(hipMemcpy(d, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            HIP_OK(pack16_device(ps, arith, &ps.pc->wp16, &ps.pc->bytes16));  // (a buffer whose upload failed is the conv's all the same: freed with the handle)
         }
     }
     lat16_ready_ = false;  // (the latency kernels' copy of the new layers is made by ensure_lat16 at the next small call)
@@ -181,32 +143,11 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
     Call::Vc& vc = *c.vc;
     const int B = c.B, hop = hop_, n_up = c.n_up;
     // frame counts and vocoder stage lengths, all on the host (spectrogram_torch: floor(N / hop) frames)
-    std::vector<int>& frames = c.frames;
-    frames.resize(B);
-    for (int b = 0; b < B; ++b) {
-        frames[b] = (int)(pcm_lens[b] / hop);
-        c.Lmax = std::max(c.Lmax, frames[b]);
-        c.sum_frames += frames[b];
-    }
+    c.frames.resize(B);
+    for (int b = 0; b < B; ++b) c.frames[b] = (int)(pcm_lens[b] / hop);
+    set_stage_affine(c);
+    c.frames_known();
     if (!lat16_ready_ && knobs.lat16_lazy_tokens > 0 && (int64_t)B * c.Lmax <= knobs.lat16_lazy_tokens && ensure_lat16(err)) return -1;
-    std::vector<int>& smul = c.smul;
-    std::vector<int>& sadd = c.sadd;
-    smul.assign(n_up + 1, 0);
-    sadd.assign(n_up + 1, 0);
-    smul[0] = 1;
-    for (int i = 0; i < n_up; ++i) {  // (as layout_stage_one)
-        const int s = ups_[i].stride, K = ups_[i].k;
-        const int crop = c.refmode ? 0 : (K - s) / 2;
-        smul[i + 1] = smul[i] * s;
-        sadd[i + 1] = sadd[i] * s + (K - s - 2 * crop);
-    }
-    c.slen.assign(n_up + 1, std::vector<int>(B));
-    c.smax.assign(n_up + 1, 0);
-    for (int i = 0; i <= n_up; ++i)
-        for (int b = 0; b < B; ++b) {
-            c.slen[i][b] = frames[b] * smul[i] + sadd[i];
-            c.smax[i] = std::max(c.smax[i], c.slen[i][b]);
-        }
     // ---- the call's own arena (the current stage-one slot): header ints | PCM | spectrogram | posterior statistics ----------------------
     const int ls = round_up(c.Lmax, 32), bins = hp.spec_bins, F = hp.flow_size;
     const int64_t pstride = round_up((int)nmax, 64);
@@ -219,16 +160,7 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
         vc.spec = a.alloc<float>((size_t)B * bins * ls);
         vc.stats = a.alloc<float>((size_t)B * 2 * F * ls);
     };
-    {
-        Arena measure;
-        measure.cap = (size_t)1 << 60;
-        layout(measure);
-        const size_t need = measure.off + 4096;
-        measure.cap = 0;
-        if (need > a1().cap) HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(a1().reserve(need));
-        layout(a1());
-    }
+    if (arena_layout(a1(), stream, err, layout)) return -1;
     vc.pcm_stride = pstride;
     {
         std::vector<int> hdr(hdr_ints, 0);
@@ -261,27 +193,21 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
 // ---- one conversion call -------------------------------------------------------------------------------------------------------
 int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
                           vits_batch_result* out, std::string& err) {
-    if (pending()) {
-        err = "batches in flight: call vits_model_wait for every submitted batch first";
-        return -1;
-    }
+    if (refuse_pending(err)) return -1;
     if (B <= 0 || !pcm || !pcm_lens || pcm_stride <= 0) {
         err = B <= 0 ? "empty batch" : "null PCM, null lengths or pcm_stride <= 0";
         return -1;
     }
-    if (o.fixed_duration > 0 || o.frames_only || o.async) {
-        err = std::string("voice conversion does not take ") + (o.fixed_duration > 0 ? "fixed_duration" : o.frames_only ? "frames_only" : "async") +
-              " (the frame counts come from the input PCM; the call is synchronous)";
+    if (const char* what = first_set({{"fixed_duration", o.fixed_duration > 0}, {"frames_only", o.frames_only != 0}, {"async", o.async != 0}})) {
+        err = std::string("voice conversion does not take ") + what + " (the frame counts come from the input PCM; the call is synchronous)";
         return -1;
     }
     if (o.speaker_ids) {
         err = "voice conversion takes its speakers from src_speakers and tgt_speakers, not from opts.speaker_ids";
         return -1;
     }
-    if (o.speaking_rates || o.noise_scales || o.noise_scale_durations || o.duration_override || o.durations_out) {
-        err = std::string("voice conversion does not take opts.") +
-              (o.speaking_rates ? "speaking_rates" : o.noise_scales ? "noise_scales" : o.noise_scale_durations ? "noise_scale_durations" : o.duration_override ? "duration_override" : "durations_out") +
-              " (it has no duration prediction, and the posterior draw has no noise scale)";
+    if (const char* what = prosody_opt_set(o)) {
+        err = std::string("voice conversion does not take opts.") + what + " (it has no duration prediction, and the posterior draw has no noise scale)";
         return -1;
     }
     if (o.on_chunk && o.skip_host_copy) {
@@ -295,14 +221,7 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
             if (s == -1) continue;
             const std::string who = std::string(side ? "tgt_speakers[" : "src_speakers[") + std::to_string(b) + "] = " + std::to_string(s) + " (" +
                                     (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
-            if (hp.num_speakers <= 1) {
-                err = who + ": this model has a single speaker and no speaker conditioning (use -1)";
-                return -1;
-            }
-            if (!speaker_in_range(s)) {
-                err = who + " is outside [-1, " + std::to_string(speaker_limit()) + ")";
-                return -1;
-            }
+            if (check_speaker(s, who, err)) return -1;
         }
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
@@ -327,7 +246,7 @@ int Engine::run_conversion_front(Call& c) {
     const vits_process_opts& o = c.o;
     Call::Vc& vc = *c.vc;
     Call::S2& s2 = c.s2;
-    const int B = c.B, Lmax = c.Lmax, ls = c.ls, H = hp.hidden, F = hp.flow_size, bins = hp.spec_bins, nl = hp.post_wn_layers;
+    const int B = c.B, Lmax = c.Lmax, ls = c.ls, H = hp.hidden, F = hp.flow_size, bins = hp.spec_bins;
     const std::vector<int>& frames = c.frames;
     const int64_t sum_frames = c.sum_frames;
     const int* ll = c.d_len_full[0];
@@ -363,8 +282,8 @@ int Engine::run_conversion_front(Call& c) {
     if (o.collect_taps) snapshot("spec", spec, bins, Lmax, B, frames);
     // posterior encoder, conditioned on the source speaker
     c.rx.phase("vits.posterior");
-    TensorRef hout = TR(s2.hout, 2 * H, ls), gate = TR(s2.gate, H, ls), hh = hout, stats = TR(vc.stats, 2 * F, ls);
-    const int* spk = vc.spk_src;
+    TensorRef hout = TR(s2.hout, 2 * H, ls), stats = TR(vc.stats, 2 * F, ls);
+    const int* spk = c.spk = vc.spk_src;  // (the posterior encoder and the forward flow: the source speaker)
     auto mk = [&](TensorRef xin, TensorRef yout) {
         ConvCall k;
         k.x = xin;
@@ -378,88 +297,24 @@ int Engine::run_conversion_front(Call& c) {
         return k;
     };
     // conv_pre and conv_proj stay fp32 in every arithmetic mode (bins -> H from a spectrogram in the hundreds; the statistics feed exp())
-    const int arith_saved = arith_now_;
-    arith_now_ = VITS_ARITH_F32;
-    HIP_OK(conv("post_conv_pre", post_.pre, mk(spec, hh)));
-    arith_now_ = arith_saved;
-    prof.begin("fill_zero", 0, 0, stream);
-    HIP_OK(launch_fill_rows(sub(hout, H), H, 0.f, B, Lmax, stream));
-    prof.end(stream);
-    // the WaveNet: the flow's layer shape (engine_flow.cpp run_coupling), fused per layer where the kernels take it
-    bool fuse_wn = !knobs.no_wn_fuse && (ls & 3) == 0 && (int64_t)((Lmax + 31) / 32) * B >= 384 && (reinterpret_cast<uintptr_t>(hout.p) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(gate.p) & 15) == 0;
-    for (int l = 0, dl = 1; l < nl && fuse_wn; ++l, dl *= hp.wn_rate)
-        fuse_wn = (arith_now_ == VITS_ARITH_F32 ? wavenet32_supported(H, hp.wn_k, dl, post_.in_layers[l], post_.res_skip[l])
-                                                : wavenet16_supported(H, hp.wn_k, dl, post_.in_layers[l], post_.res_skip[l])) &&
-                  post_.res_skip[l].cout == (l + 1 < nl ? 2 * H : H);
-    if (fuse_wn) {
-        TensorRef hcur = hh;
-        for (int l = 0, dl = 1; l < nl; ++l, dl *= hp.wn_rate) {
-            WaveNet32Call w;
-            w.h = hcur;
-            w.h_out = hcur.p == gate.p ? hh : gate;
-            if (l + 1 == nl) w.h_out = TensorRef();
-            w.outputs = sub(hout, H);
-            w.lens = ll;
-            w.spk = spk;
-            w.batch = B;
-            w.tmax = Lmax;
-            w.hidden = H;
-            w.dil = dl;
-            if (prof.on) {
-                char full[160];
-                std::snprintf(full, sizeof(full), "post_wavenet_layer|k%d|d%d|%c%d|e1|c%dx%d", hp.wn_k, dl, arith_now_ == VITS_ARITH_F32 ? 'w' : 'W', H, H,
-                              post_.res_skip[l].cout);
-                prof.begin(full, 2.0 * ((double)2 * H * H * hp.wn_k + (double)post_.res_skip[l].cout * H) * (double)sum_frames,
-                           4.0 * (double)sum_frames * (H + 2.0 * post_.res_skip[l].cout) + (double)post_.in_layers[l].bytes + (double)post_.res_skip[l].bytes, stream, true);
-            }
-            if (arith_now_ == VITS_ARITH_F32) HIP_OK(launch_wavenet32(post_.in_layers[l], post_.res_skip[l], w, stream));
-            else HIP_OK(launch_wavenet16(post_.in_layers[l], post_.res_skip[l], w, arith_now_, stream));
-            prof.end(stream);
-            if (w.h_out.p) hcur = w.h_out;
-        }
-    } else {
-        for (int l = 0, dl = 1; l < nl; ++l, dl *= hp.wn_rate) {
-            ConvCall k = mk(hh, gate);
-            k.dil = dl;
-            k.pad_l = (hp.wn_k * dl - dl) / 2;
-            HIP_OK(conv("post_wavenet_gated_conv", post_.in_layers[l], k));
-            ConvCall r = l + 1 < nl ? mk(gate, hout) : mk(gate, sub(hout, H));  // rows [0,H): h += res; rows [H,2H): outputs += skip
-            r.res = l + 1 < nl ? hout : sub(hout, H);
-            HIP_OK(conv("post_conv1x1", post_.res_skip[l], r));
-        }
+    {
+        ScopedSet<int> f32(arith_now_, VITS_ARITH_F32);
+        HIP_OK(conv("post_conv_pre", post_.pre, mk(spec, hout)));
     }
-    arith_now_ = VITS_ARITH_F32;
-    HIP_OK(conv("post_conv_proj", post_.proj, mk(sub(hout, H), stats)));
-    arith_now_ = arith_saved;
+    static const WaveNetLabels labels{"post_wavenet_layer", "post_wavenet_gated_conv", "post_conv1x1"};
+    if (run_wavenet(c, post_.in_layers, post_.res_skip, hp.post_wn_layers, labels)) return -1;
+    {
+        ScopedSet<int> f32(arith_now_, VITS_ARITH_F32);
+        HIP_OK(conv("post_conv_proj", post_.proj, mk(sub(hout, H), stats)));
+    }
     if (o.collect_taps) {
         snapshot("post_mean", stats, F, Lmax, B, frames);
         snapshot("post_logstd", sub(stats, F), F, Lmax, B, frames);
     }
     // eps: the [F][L] draw prior sampling would make (engine_flow.cpp run_prior_sampling), then z_q — in the forward flow's physical input layout
     TensorRef zp = TR(s2.zp, F, ls), noise = TR(s2.noise, F, ls);
-    if (o.noise_kind != VITS_NOISE_COUNTER && vc.eps_scale != 0.f) {  // (scale 0 = the posterior mean: no noise drawn, uploaded or read)
-        std::vector<float> hn((size_t)B * F * ls, 0.f);
-        for (int b = 0; b < B; ++b) {
-            const int L = frames[b];
-            if (o.noise_kind == VITS_NOISE_EXPLICIT) {
-                if (!o.noise_prior) {
-                    err = "noise_prior missing";
-                    return -1;
-                }
-                for (int ch = 0; ch < F; ++ch)
-                    std::memcpy(&hn[((size_t)b * F + ch) * ls], o.noise_prior + ((size_t)b * F + ch) * o.noise_prior_stride, sizeof(float) * std::min<int64_t>(L, o.noise_prior_stride));
-            } else {
-                std::vector<float> tmpn((size_t)F * L);
-                reference_noise_fill(tmpn.data(), tmpn.size());
-                for (int ch = 0; ch < F; ++ch) std::memcpy(&hn[((size_t)b * F + ch) * ls], &tmpn[(size_t)ch * L], sizeof(float) * L);
-            }
-        }
-        HIP_OK(hipMemcpyAsync(s2.noise, hn.data(), sizeof(float) * hn.size(), hipMemcpyHostToDevice, stream));
-        prof.fence();
-        HIP_OK(hipStreamSynchronize(stream));  // hn goes out of scope
-        if (o.collect_taps) snapshot("noise_prior", noise, F, Lmax, B, frames);
-    }
+    // (scale 0 = the posterior mean: no noise drawn, uploaded or read)
+    if (o.noise_kind != VITS_NOISE_COUNTER && vc.eps_scale != 0.f && upload_host_noise(c)) return -1;
     const int nk = o.noise_kind == VITS_NOISE_COUNTER ? VITS_NOISE_COUNTER : VITS_NOISE_EXPLICIT;
     prof.begin("posterior_sample", 0, 0, stream, true);
     HIP_OK(launch_posterior_sample(stats, sub(stats, F), ll, noise, nk, o.noise_seed, c.s1.seed_off, zp, B, F, Lmax, hp.n_flows % 2, stream, vc.eps_scale));
@@ -470,7 +325,6 @@ int Engine::run_conversion_front(Call& c) {
         else snapshot("z_q", zp, F, Lmax, B, frames);
     }
     // forward flow, source speaker
-    c.spk = vc.spk_src;
     return run_coupling(c, true);
 }
 

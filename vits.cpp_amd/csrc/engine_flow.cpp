@@ -8,16 +8,11 @@
 namespace vits {
 
 int Engine::layout_stage_two(Call& c) {
-    std::string& err = c.err;
     const vits_process_opts& o = c.o;
     const int B = c.B, n_up = c.n_up;
     const int H = hp.hidden, F = hp.flow_size;
-    const std::vector<int>& frames = c.frames;
     const int Lmax = c.Lmax;
-    Call::S1& s1 = c.s1;
     Call::S2& s2 = c.s2;
-    auto TR = make_ref;
-    auto sub = sub_rows;
     const std::vector<Call::Win>& wins = c.wins;
     const bool windowed = c.windowed;
     const int Lw_max = c.Lw_max;
@@ -73,25 +68,9 @@ int Engine::layout_stage_two(Call& c) {
         s2.pre = o.collect_taps ? a.alloc<float>((size_t)B * S_stride) : nullptr;
         s2.wave = a.alloc<float>((size_t)B * S_stride);
     };
-    {
-        Arena measure;
-        measure.cap = (size_t)1 << 60;
-        layout2(measure);
-        const size_t need = measure.off + 4096;
-        measure.cap = 0;
-        if (need > a2_.cap) HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(a2_.reserve(need));
-        layout2(a2_);
-        for (int j = 0; j < 3; ++j) {
-            x16_[j] = Ref16();
-            x16_[j].p = s2.x16[j];
-            x16_cap_[j] = s2.x16[j] ? x16_elems2 : 0;
-        }
-    }
-    for (int i = 0; i <= n_up && i < 8; ++i) c.d_len_full[i] = s1.stage_lens + (size_t)i * B;
-    (void)sub;
-    (void)TR;
-    (void)frames;
+    if (arena_layout(a2_, stream, c.err, layout2)) return -1;
+    set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);
+    for (int i = 0; i <= n_up && i < 8; ++i) c.d_len_full[i] = c.s1.stage_lens + (size_t)i * B;
     return 0;
 }
 
@@ -99,8 +78,7 @@ int Engine::layout_stage_two(Call& c) {
 int Engine::run_prior_sampling(Call& c) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
-    const int B = c.B, n_up = c.n_up;
-    const int H = hp.hidden, F = hp.flow_size;
+    const int B = c.B, F = hp.flow_size;
     const std::vector<int>& frames = c.frames;
     const int Lmax = c.Lmax;
     Call::S1& s1 = c.s1;
@@ -109,7 +87,6 @@ int Engine::run_prior_sampling(Call& c) {
     auto sub = sub_rows;
     const int id_stride = c.id_stride, ls = c.ls;
     const int* dl = s1.lens;
-    const bool need_noise_buf = o.noise_kind != VITS_NOISE_COUNTER;
     TensorRef stats = TR(s1.stats, 2 * F, c.ts);
     c.rx.phase("vits.prior_sampling");
     TensorRef zp = TR(s2.zp, F, ls), noise = TR(s2.noise, F, ls);
@@ -117,55 +94,131 @@ int Engine::run_prior_sampling(Call& c) {
         // batch 1, reference noise: the tensor was (mostly) drawn while stage one ran (engine.cpp); it is one dense [F][L] block in pinned memory
         const int L = frames[0];
         const size_t n = (size_t)F * (size_t)L;
-        if (n > ref_noise_cap_) {  // (more frames per id than the block was sized for: a larger block once the helper rests at the old capacity; keep what was drawn)
+        PinnedBuf<float> block;  // a larger one; after the swap the old one, which goes only when the helper has moved over and finished
+        if (n > ref_noise_pinned_.cap) {  // (more frames per id than the block was sized for: a larger block once the helper rests at the old capacity; keep what was drawn)
             while (c.ref_ahead->drawn() < c.ref_ahead->capacity()) std::this_thread::yield();
-            float* bigger = nullptr;
-            HIP_OK(hipHostMalloc((void**)&bigger, n * sizeof(float), hipHostMallocDefault));
-            std::memcpy(bigger, ref_noise_pinned_, sizeof(float) * c.ref_ahead->drawn());
-            float* old = ref_noise_pinned_;
-            ref_noise_pinned_ = bigger;
-            ref_noise_cap_ = n;
-            c.ref_ahead->rebase(ref_noise_pinned_, ref_noise_cap_);
-            c.ref_ahead->finish(n);
-            hipHostFree(old);
-        } else
-            c.ref_ahead->finish(n);
+            HIP_OK(block.ensure(n, n));
+            std::memcpy(block.p, ref_noise_pinned_.p, sizeof(float) * c.ref_ahead->drawn());
+            ref_noise_pinned_.swap(block);
+            c.ref_ahead->rebase(ref_noise_pinned_.p, ref_noise_pinned_.cap);
+        }
+        c.ref_ahead->finish(n);
         c.ref_ahead = nullptr;
         noise.cs = L;
         noise.bs = (int64_t)F * L;
-        HIP_OK(hipMemcpyAsync(s2.noise, ref_noise_pinned_, sizeof(float) * n, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(s2.noise, ref_noise_pinned_.p, sizeof(float) * n, hipMemcpyHostToDevice, stream));
         prof.fence();
         if (o.async) HIP_OK(hipStreamSynchronize(stream));  // (the pinned block is reused by the next call)
         if (o.collect_taps) snapshot("noise_prior", noise, F, Lmax, B, frames);
-    } else if (need_noise_buf) {
-        std::vector<float> hn((size_t)B * F * ls, 0.f);
-        for (int b = 0; b < B; ++b) {
-            const int L = frames[b];
-            if (o.noise_kind == VITS_NOISE_EXPLICIT) {
-                if (!o.noise_prior) {
-                    err = "noise_prior missing";
-                    return -1;
-                }
-                for (int c = 0; c < F; ++c)
-                    std::memcpy(&hn[((size_t)b * F + c) * ls], o.noise_prior + ((size_t)b * F + c) * o.noise_prior_stride, sizeof(float) * std::min<int64_t>(L, o.noise_prior_stride));
-            } else {
-                std::vector<float> tmpn((size_t)F * L);  // tensor_randn_like(prior_means ne=[L,F]) (vits.cpp:1059)
-                reference_noise_fill(tmpn.data(), tmpn.size());
-                for (int c = 0; c < F; ++c) std::memcpy(&hn[((size_t)b * F + c) * ls], &tmpn[(size_t)c * L], sizeof(float) * L);
-            }
-        }
-        HIP_OK(hipMemcpyAsync(s2.noise, hn.data(), sizeof(float) * hn.size(), hipMemcpyHostToDevice, stream));
-        prof.fence();
-        HIP_OK(hipStreamSynchronize(stream));  // hn goes out of scope
-        if (o.collect_taps) snapshot("noise_prior", noise, F, Lmax, B, frames);
-    }
+    } else if (o.noise_kind != VITS_NOISE_COUNTER && upload_host_noise(c))
+        return -1;
     prof.begin("prior_sample_gather", 0, 0, stream);
     HIP_OK(launch_zp(sub(stats, 0), sub(stats, F), s1.cum, id_stride, dl, s1.frames, noise, o.noise_kind == VITS_NOISE_COUNTER ? VITS_NOISE_COUNTER : VITS_NOISE_EXPLICIT,
                      o.noise_seed, s1.seed_off, noise_scale, s1.noise_scale, zp, B, F, Lmax, stream));
     prof.end(stream);
     if (o.collect_taps) snapshot("z_p", zp, F, Lmax, B, frames);
-    (void)n_up;
-    (void)H;
+    return 0;
+}
+
+// Host noise of every utterance (opts.noise_prior, or the reference stream: tensor_randn_like(prior_means ne=[L,F]), vits.cpp:1059, utterance by
+// utterance) as [F][L] rows of s2.noise, and the noise_prior tap
+int Engine::upload_host_noise(Call& c) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const int B = c.B, F = hp.flow_size, ls = c.ls;
+    std::vector<float> hn((size_t)B * F * ls, 0.f);
+    for (int b = 0; b < B; ++b) {
+        const int L = c.frames[b];
+        if (o.noise_kind == VITS_NOISE_EXPLICIT) {
+            if (!o.noise_prior) {
+                err = "noise_prior missing";
+                return -1;
+            }
+            for (int ch = 0; ch < F; ++ch)
+                std::memcpy(&hn[((size_t)b * F + ch) * ls], o.noise_prior + ((size_t)b * F + ch) * o.noise_prior_stride, sizeof(float) * std::min<int64_t>(L, o.noise_prior_stride));
+        } else {
+            std::vector<float> tmpn((size_t)F * L);
+            reference_noise_fill(tmpn.data(), tmpn.size());
+            for (int ch = 0; ch < F; ++ch) std::memcpy(&hn[((size_t)b * F + ch) * ls], &tmpn[(size_t)ch * L], sizeof(float) * L);
+        }
+    }
+    HIP_OK(hipMemcpyAsync(c.s2.noise, hn.data(), sizeof(float) * hn.size(), hipMemcpyHostToDevice, stream));
+    prof.fence();
+    HIP_OK(hipStreamSynchronize(stream));  // hn goes out of scope
+    if (o.collect_taps) snapshot("noise_prior", make_ref(c.s2.noise, F, ls), F, c.Lmax, B, c.frames);
+    return 0;
+}
+
+// ---- one WaveNet stack (vits.cpp:452-498; transformers VitsWaveNet) -----------------------------------------------------------
+int Engine::run_wavenet(Call& c, const std::vector<PackedConv>& in_layers, const std::vector<PackedConv>& res_skip, int n_layers, const WaveNetLabels& lab) {
+    std::string& err = c.err;
+    const int B = c.B, Lmax = c.Lmax, H = hp.hidden;
+    const int64_t sum_frames = c.sum_frames;
+    const int* ll = c.d_len_full[0];
+    TensorRef hout = make_ref(c.s2.hout, 2 * H, c.ls), gate = make_ref(c.s2.gate, H, c.ls);
+    TensorRef hh = hout, outputs = sub_rows(hout, H);  // channels [0,H) = h, [H,2H) = skip accumulator "outputs" (vits.cpp:460)
+    auto mk = [&](TensorRef xin, TensorRef yout) {
+        ConvCall k;
+        k.x = xin;
+        k.y = yout;
+        k.len_in = ll;
+        k.len_out = ll;
+        k.spk = c.spk;  // (multi-speaker calls: read by the speaker-conditioned in_layers only)
+        k.batch = B;
+        k.t_in = k.t_out = Lmax;
+        k.sum_in = k.sum_out = sum_frames;
+        return k;
+    };
+    prof.begin("fill_zero", 0, 0, stream);
+    HIP_OK(launch_fill_rows(outputs, H, 0.f, B, Lmax, stream));
+    prof.end(stream);
+    // Each layer as ONE kernel (wavenet32.hip; bit-identical to the two launches below). A fused block reads a
+    // 2-frame halo of its neighbours' h columns, so h alternates between hout[0,H) and the buffer the two-launch path uses for the
+    // gate output; `outputs` (hout[H,2H)) is updated in place.
+    // (large grids only: at batch 1 a layer is four blocks, and a block's six waves on four SIMDs run two MFMA chains deep:
+    // 68 us against 39 us for the two launches with their split-gate tiles)
+    const bool f32 = arith_now_ == VITS_ARITH_F32;
+    bool fuse = !knobs.no_wn_fuse && (c.ls & 3) == 0 && (int64_t)((Lmax + 31) / 32) * B >= 384 && (reinterpret_cast<uintptr_t>(hout.p) & 15) == 0 &&
+                (reinterpret_cast<uintptr_t>(gate.p) & 15) == 0;
+    for (int l = 0, dl = 1; l < n_layers && fuse; ++l, dl *= hp.wn_rate)
+        fuse = (f32 ? wavenet32_supported(H, hp.wn_k, dl, in_layers[l], res_skip[l]) : wavenet16_supported(H, hp.wn_k, dl, in_layers[l], res_skip[l])) &&
+               res_skip[l].cout == (l + 1 < n_layers ? 2 * H : H);
+    TensorRef hcur = hh;
+    for (int l = 0, dl = 1; l < n_layers; ++l, dl *= hp.wn_rate) {
+        const PackedConv &in = in_layers[l], &rs = res_skip[l];
+        const bool last = l + 1 == n_layers;
+        if (fuse) {
+            WaveNet32Call w;
+            w.h = hcur;
+            w.h_out = last ? TensorRef() : (hcur.p == gate.p ? hh : gate);
+            w.outputs = outputs;
+            w.lens = ll;
+            w.spk = c.spk;
+            w.batch = B;
+            w.tmax = Lmax;
+            w.hidden = H;
+            w.dil = dl;  // (1: the fused kernels take no other, see *_supported)
+            if (prof.on) {
+                char full[160];
+                std::snprintf(full, sizeof(full), "%s|k%d|d%d|%c%d|e1|c%dx%d", lab.layer, hp.wn_k, dl, f32 ? 'w' : 'W', H, H, rs.cout);
+                prof.begin(full, 2.0 * ((double)2 * H * H * hp.wn_k + (double)rs.cout * H) * (double)sum_frames,
+                           4.0 * (double)sum_frames * (H + 2.0 * rs.cout) + (double)in.bytes + (double)rs.bytes, stream, true);
+            }
+            if (f32) HIP_OK(launch_wavenet32(in, rs, w, stream));
+            else HIP_OK(launch_wavenet16(in, rs, w, arith_now_, stream));
+            prof.end(stream);
+            if (w.h_out.p) hcur = w.h_out;
+            continue;
+        }
+        ConvCall k = mk(hh, gate);
+        k.dil = dl;
+        k.pad_l = (hp.wn_k * dl - dl) / 2;  // vits.cpp:470
+        HIP_OK(conv(lab.gated_conv, in, k));
+        // all but the last layer: rows [0,H): h += res ; rows [H,2H): outputs += skip (vits.cpp:484-489); the last: outputs += res_skip (vits.cpp:491)
+        ConvCall r = mk(gate, last ? outputs : hout);
+        r.res = r.y;
+        HIP_OK(conv(lab.conv1x1, rs, r));
+    }
     return 0;
 }
 
@@ -176,21 +229,17 @@ int Engine::run_prior_sampling(Call& c) {
 int Engine::run_coupling(Call& c, bool forward) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
-    const int B = c.B, n_up = c.n_up;
+    const int B = c.B;
     const int H = hp.hidden, F = hp.flow_size;
     const std::vector<int>& frames = c.frames;
     const int Lmax = c.Lmax;
-    Call::S1& s1 = c.s1;
-    Call::S2& s2 = c.s2;
-    auto TR = make_ref;
     auto sub = sub_rows;
     const int ls = c.ls;
     const int64_t sum_frames = c.sum_frames;
-    TensorRef zp = TR(s2.zp, F, ls);
+    TensorRef zp = make_ref(c.s2.zp, F, ls);
     c.rx.phase(forward ? "vits.flow_forward" : "vits.flow");
     const int* ll = c.d_len_full[0];
-    TensorRef hout = TR(s2.hout, 2 * H, ls), gate = TR(s2.gate, H, ls);
-    TensorRef hh = hout;  // channels [0,H) = h, [H,2H) = skip accumulator "outputs" (vits.cpp:460)
+    TensorRef hout = make_ref(c.s2.hout, 2 * H, ls);
     const int* spk = c.spk;  // (multi-speaker calls: read by the speaker-conditioned in_layers only)
     auto mk2 = [&](TensorRef xin, TensorRef yout) {
         ConvCall c;
@@ -282,67 +331,9 @@ int Engine::run_coupling(Call& c, bool forward) {
             prof.end(stream);
             continue;
         }
-        HIP_OK(conv("flow_conv1x1", Lw.pre, mk2(x0, hh)));  // h -> hout[0,H)
-        prof.begin("fill_zero", 0, 0, stream);
-        HIP_OK(launch_fill_rows(sub(hout, H), H, 0.f, B, Lmax, stream));
-        prof.end(stream);
-        int dil = 1;
-        // fp32: each WaveNet layer as ONE kernel (wavenet32.hip; bit-identical to the two launches below). A fused block reads a
-        // 2-frame halo of its neighbours' h columns, so h alternates between hout[0,H) and the buffer the two-launch path uses for the
-        // gate output; `outputs` (hout[H,2H)) is updated in place.
-        // (large grids only: at batch 1 a layer is four blocks, and a block's six waves on four SIMDs run two MFMA chains deep:
-        // 68 us against 39 us for the two launches with their split-gate tiles)
-        bool fuse_wn = !knobs.no_wn_fuse && (ls & 3) == 0 && (int64_t)((Lmax + 31) / 32) * B >= 384 &&
-                       (reinterpret_cast<uintptr_t>(hout.p) & 15) == 0 && (reinterpret_cast<uintptr_t>(gate.p) & 15) == 0;
-        for (int l = 0; l < hp.wn_layers && fuse_wn; ++l) {
-            int dl = 1;
-            for (int q = 0; q < l; ++q) dl *= hp.wn_rate;
-            fuse_wn = (arith_now_ == VITS_ARITH_F32 ? wavenet32_supported(H, hp.wn_k, dl, Lw.in_layers[l], Lw.res_skip[l])
-                                               : wavenet16_supported(H, hp.wn_k, dl, Lw.in_layers[l], Lw.res_skip[l])) &&
-                      Lw.res_skip[l].cout == (l + 1 < hp.wn_layers ? 2 * H : H);
-        }
-        if (fuse_wn) {
-            TensorRef hcur = hh;  // rows [0,H) of hout
-            for (int l = 0; l < hp.wn_layers; ++l) {
-                WaveNet32Call w;
-                w.h = hcur;
-                w.h_out = hcur.p == gate.p ? hh : gate;
-                if (l + 1 == hp.wn_layers) w.h_out = TensorRef();
-                w.outputs = sub(hout, H);
-                w.lens = ll;
-                w.spk = spk;
-                w.batch = B;
-                w.tmax = Lmax;
-                w.hidden = H;
-                w.dil = 1;
-                if (prof.on) {
-                    char full[160];
-                    std::snprintf(full, sizeof(full), "flow_wavenet_layer|k%d|d1|%c%d|e1|c%dx%d", hp.wn_k, arith_now_ == VITS_ARITH_F32 ? 'w' : 'W', H, H, Lw.res_skip[l].cout);
-                    prof.begin(full, 2.0 * ((double)2 * H * H * hp.wn_k + (double)Lw.res_skip[l].cout * H) * (double)sum_frames,
-                               4.0 * (double)sum_frames * (H + 2.0 * Lw.res_skip[l].cout) + (double)Lw.in_layers[l].bytes + (double)Lw.res_skip[l].bytes, stream, true);
-                }
-                if (arith_now_ == VITS_ARITH_F32) HIP_OK(launch_wavenet32(Lw.in_layers[l], Lw.res_skip[l], w, stream));
-                else HIP_OK(launch_wavenet16(Lw.in_layers[l], Lw.res_skip[l], w, arith_now_, stream));
-                prof.end(stream);
-                if (w.h_out.p) hcur = w.h_out;
-            }
-        }
-        for (int l = 0; l < hp.wn_layers && !fuse_wn; ++l) {
-            ConvCall c = mk2(hh, gate);
-            c.dil = dil;
-            c.pad_l = (hp.wn_k * dil - dil) / 2;  // vits.cpp:470
-            HIP_OK(conv("flow_wavenet_gated_conv", Lw.in_layers[l], c));
-            if (l < hp.wn_layers - 1) {
-                ConvCall r = mk2(gate, hout);  // rows [0,H): h += res ; rows [H,2H): outputs += skip (vits.cpp:484-489)
-                r.res = hout;
-                HIP_OK(conv("flow_conv1x1", Lw.res_skip[l], r));
-            } else {
-                ConvCall r = mk2(gate, sub(hout, H));  // outputs += res_skip (vits.cpp:491)
-                r.res = sub(hout, H);
-                HIP_OK(conv("flow_conv1x1", Lw.res_skip[l], r));
-            }
-            dil *= hp.wn_rate;
-        }
+        HIP_OK(conv("flow_conv1x1", Lw.pre, mk2(x0, hout)));  // h -> hout[0,H)
+        static const WaveNetLabels labels{"flow_wavenet_layer", "flow_wavenet_gated_conv", "flow_conv1x1"};
+        if (run_wavenet(c, Lw.in_layers, Lw.res_skip, hp.wn_layers, labels)) return -1;
         ConvCall pc = mk2(sub(hout, H), x1);  // x1 <- x1 - (W out + b): weights negated at load (vits.cpp:506,513); forward: x1 + (W out + b)
         pc.res = x1;
         HIP_OK(conv("flow_conv1x1", post, pc));
@@ -356,8 +347,6 @@ int Engine::run_coupling(Call& c, bool forward) {
         else if (hp.n_flows % 2) snapshot_flipped("z_flow", zp, F, Lmax, B, frames);  // (odd layer count: the logical channels are the physical ones reversed)
         else snapshot("z_flow", zp, F, Lmax, B, frames);
     }
-    (void)n_up;
-    (void)s1;
     return 0;
 }
 

@@ -84,6 +84,50 @@ static inline TensorRef sub_rows(TensorRef t, int c0) {
     return t;
 }
 
+// The buffers of one phase in an arena: `layout` runs once on a measuring arena and once on the real one, grown in between if it has to be (behind
+// a stream synchronisation: growing frees memory that queued kernels may still read). 0, or -1 with err set.
+template <class Layout>
+int arena_layout(Arena& a, hipStream_t stream, std::string& err, Layout&& layout) {
+    Arena measure;
+    measure.cap = (size_t)1 << 60;
+    layout(measure);
+    const size_t need = measure.off + 4096;
+    measure.cap = 0;
+    if (need > a.cap) HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(a.reserve(need));
+    layout(a);
+    return 0;
+}
+
+// a member that holds another value for a while: the stream being queued on, the arithmetic of the convs being queued, the stage-one slot
+template <class T>
+struct ScopedSet {
+    T& slot;
+    T saved;
+    ScopedSet(T& s, T to) : slot(s), saved(s) { slot = to; }
+    void restore() { slot = saved; }
+    ~ScopedSet() { slot = saved; }
+};
+
+// "this call does not take opts.X": the first option of the list that the caller set, or null
+struct OptSet {
+    const char* name;
+    bool set;
+};
+inline const char* first_set(std::initializer_list<OptSet> opts) {
+    for (const OptSet& s : opts)
+        if (s.set) return s.name;
+    return nullptr;
+}
+// the per-utterance prosody of a text-to-speech call, which neither conversion nor alignment has a use for
+inline const char* prosody_opt_set(const vits_process_opts& o) {
+    return first_set({{"speaking_rates", o.speaking_rates != nullptr},
+                      {"noise_scales", o.noise_scales != nullptr},
+                      {"noise_scale_durations", o.noise_scale_durations != nullptr},
+                      {"duration_override", o.duration_override != nullptr},
+                      {"durations_out", o.durations_out != nullptr}});
+}
+
 void reference_noise_fill(float* dst, size_t n);  // the reference's process-global libstdc++ stream (vits.cpp:31)
 
 // ---- everything one vits_model_process_batch call carries from phase to phase -------------------------------------------------
@@ -132,6 +176,20 @@ struct Call {
     std::vector<std::vector<int>> slen;  // [stage][utterance]
     std::vector<int> smax;               // [stage] longest
     int64_t sum_frames = 0;
+    // `frames` is known (and smul / sadd): the longest, the sum, and every utterance's length at every vocoder stage
+    void frames_known() {
+        for (int f : frames) {
+            Lmax = std::max(Lmax, f);
+            sum_frames += f;
+        }
+        slen.assign(n_up + 1, std::vector<int>(B));
+        smax.assign(n_up + 1, 0);
+        for (int i = 0; i <= n_up; ++i)
+            for (int b = 0; b < B; ++b) {
+                slen[i][b] = frames[b] * smul[i] + sadd[i];
+                smax[i] = std::max(smax[i], slen[i][b]);
+            }
+    }
 
     // vocoder windows (long-form / streaming)
     struct Win {

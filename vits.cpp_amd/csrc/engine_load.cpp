@@ -12,10 +12,6 @@ Engine::~Engine() {
         if (s) hipStreamSynchronize(s);
     clear_taps();
     for (Pending& p : pend_) {
-        if (p.host) hipHostFree(p.host);
-        if (p.frames_pinned) hipHostFree(p.frames_pinned);
-        if (p.win_pinned) hipHostFree(p.win_pinned);
-        if (p.dur_pinned) hipHostFree(p.dur_pinned);
         if (p.s1_done) hipEventDestroy(p.s1_done);
         if (p.done) hipEventDestroy(p.done);
     }
@@ -25,17 +21,9 @@ Engine::~Engine() {
         for (PackSrc& ps : packs_)
             if (ps.pc->wp16) hipFree(ps.pc->wp16);
     }
-    if (pinned_) hipHostFree(pinned_);
-    if (frames_host_) hipHostFree(frames_host_);
-    if (align_host_) hipHostFree(align_host_);
-    if (dur_host_) hipHostFree(dur_host_);
-    for (HStage& hs : hstage_) {
-        if (hs.p) hipHostFree(hs.p);
+    for (HStage& hs : hstage_)
         if (hs.ev) hipEventDestroy(hs.ev);
-    }
     if (ev_async_) hipEventDestroy(ev_async_);
-    if (ref_noise_pinned_) hipHostFree(ref_noise_pinned_);
-    if (dur_noise_pinned_) hipHostFree(dur_noise_pinned_);
     if (dur_noise_ev_) hipEventDestroy(dur_noise_ev_);
     if (ev_fork_) hipEventDestroy(ev_fork_);
     for (hipEvent_t e : ev_done_)
@@ -306,13 +294,35 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
         weight_bytes += (int64_t)table_floats * 4;
         return true;
     }
-    // device: the table (resident), the embedding and the cond convs (temporaries of this function)
+    // custom voices (engine_voices.cpp): the table may grow later, and a registered vector goes through these same conditioning convs — host copies
+    // of their rows in segment order and of the embedding (what vits_model_get_speaker_embedding returns); nothing more on the device until a voice comes
+    VoiceTable vt;
+    vt.rs = rs;
+    for (const Seg& s : segs) {
+        vt.segs.push_back({s.pc, s.n, s.off});
+        const auto& wb = cond[s.w];
+        vt.cond_w.insert(vt.cond_w.end(), wb.first.begin() + (int64_t)s.row0 * E, wb.first.begin() + (int64_t)(s.row0 + s.n) * E);
+        vt.cond_b.insert(vt.cond_b.end(), wb.second.begin() + s.row0, wb.second.begin() + s.row0 + s.n);
+    }
+    if (!build_speaker_table(vt, emb)) {
+        err = "could not build the speaker bias table on the device";
+        return false;
+    }
+    vt_main_ = std::move(vt);
+    spk_emb_ = std::move(emb);
+    return true;
+}
+
+bool Engine::build_speaker_table(VoiceTable& vt, const std::vector<float>& emb) {
+    const int E = hp.speaker_embedding_size, N = hp.num_speakers;
+    const size_t table_floats = (size_t)(N + 1) * vt.rs;
+    // device: the table (resident), the embedding and the segments' conv rows (temporaries of this function)
     std::vector<void*> tmp;
-    auto dev = [&](const float* p, size_t n) -> float* {
+    auto dev = [&](const std::vector<float>& v) -> float* {
         float* d = nullptr;
-        if (hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) return nullptr;
+        if (hipMalloc((void**)&d, std::max<size_t>(v.size(), 1) * sizeof(float)) != hipSuccess) return nullptr;
         tmp.push_back(d);
-        if (hipMemcpy(d, p, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        if (hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
         return d;
     };
     float* table = nullptr;
@@ -321,43 +331,25 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
         owned_.push_back(table);
         weight_bytes += (int64_t)table_floats * 4;
     }
-    const float* d_emb = ok ? dev(emb.data(), emb.size()) : nullptr;
-    ok = ok && d_emb;
-    std::map<std::string, std::pair<float*, float*>> d_cond;
-    for (auto& kv : cond) {
+    const float* d_emb = ok ? dev(emb) : nullptr;
+    const float* d_w = ok ? dev(vt.cond_w) : nullptr;
+    const float* d_b = ok ? dev(vt.cond_b) : nullptr;
+    ok = ok && d_emb && d_w && d_b;
+    int64_t row = 0;  // of cond_w / cond_b: the segments' conv rows lie there in segment order
+    for (const VoiceTable::Seg& s : vt.segs) {
         if (!ok) break;
-        float* w = dev(kv.second.first.data(), kv.second.first.size());
-        float* b = dev(kv.second.second.data(), kv.second.second.size());
-        ok = w && b;
-        d_cond[kv.first] = {w, b};
-    }
-    for (const Seg& s : segs) {
-        if (!ok) break;
-        const auto& wb = d_cond[s.w];
-        ok = launch_speaker_bias(s.pc->bias, wb.first + (int64_t)s.row0 * E, wb.second + s.row0, d_emb, s.n, E, N, table + s.off, rs, stream) == hipSuccess;
+        ok = launch_speaker_bias(s.pc->bias, d_w + row * E, d_b + row, d_emb, s.n, E, N, table + s.off, vt.rs, stream) == hipSuccess;
+        row += s.n;
     }
     ok = ok && hipStreamSynchronize(stream) == hipSuccess;
     for (void* p : tmp) hipFree(p);
-    if (!ok) {
-        err = "could not build the speaker bias table on the device";
-        return false;
-    }
-    for (Seg& s : segs) {
+    if (!ok) return false;
+    for (const VoiceTable::Seg& s : vt.segs) {
         s.pc->bias = table + s.off;  // row 0: the plain biases (a call without speakers reads exactly these values)
-        s.pc->bias_rs = rs;
+        s.pc->bias_rs = vt.rs;
     }
-    // custom voices (engine_voices.cpp): the table may grow later, and a registered vector goes through these same conditioning convs — host copies
-    // of their rows in segment order and of the embedding (what vits_model_get_speaker_embedding returns); nothing more on the device until a voice comes
-    vt_main_.table = table;
-    vt_main_.rs = rs;
-    vt_main_.cap_rows = N + 1;
-    for (const Seg& s : segs) {
-        vt_main_.segs.push_back({s.pc, s.n, s.off});
-        const auto& wb = cond[s.w];
-        vt_main_.cond_w.insert(vt_main_.cond_w.end(), wb.first.begin() + (int64_t)s.row0 * E, wb.first.begin() + (int64_t)(s.row0 + s.n) * E);
-        vt_main_.cond_b.insert(vt_main_.cond_b.end(), wb.second.begin() + s.row0, wb.second.begin() + s.row0 + s.n);
-    }
-    spk_emb_ = std::move(emb);
+    vt.table = table;
+    vt.cap_rows = N + 1;
     return true;
 }
 
@@ -713,6 +705,16 @@ int64_t Engine::get_tap(const char* name, int utt, float* dst, size_t cap) {
     return n;
 }
 
+hipError_t Engine::pack16_device(const PackSrc& ps, int arith16, uint16_t** d, int64_t* bytes) {
+    const std::vector<float> w = ps.widen();
+    const std::vector<uint16_t> packed = pack_conv_weights16(w.data(), ps.cout, ps.cin, ps.k, ps.epi, ps.ct_stride, arith16);
+    uint16_t* p = nullptr;
+    if (hipError_t e = hipMalloc((void**)&p, packed.size() * sizeof(uint16_t))) return e;
+    *d = p;
+    *bytes = (int64_t)packed.size() * 2;
+    return hipMemcpy(p, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+}
+
 int Engine::set_arith(int a, std::string& err) {
     if (a == arith) return 0;
     if (a == VITS_ARITH_F32_SPLIT) {
@@ -756,12 +758,7 @@ int Engine::set_arith(int a, std::string& err) {
         std::vector<int64_t> fresh_bytes(packs_.size(), 0);
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < packs_.size() && e == hipSuccess; ++i) {
-            const PackSrc& ps = packs_[i];
-            const std::vector<float> w = ps.widen();
-            const std::vector<uint16_t> packed = pack_conv_weights16(w.data(), ps.cout, ps.cin, ps.k, ps.epi, ps.ct_stride, a);
-            e = hipMalloc((void**)&fresh[i], packed.size() * sizeof(uint16_t));
-            if (e == hipSuccess) e = hipMemcpy(fresh[i], packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-            fresh_bytes[i] = (int64_t)packed.size() * 2;
+            e = pack16_device(packs_[i], a, &fresh[i], &fresh_bytes[i]);
         }
         if (e != hipSuccess) {
             for (uint16_t* d : fresh)

@@ -100,6 +100,22 @@ hipError_t Engine::run_dds_lat(const DdsW& d, const DdsEnds& e, TensorRef a, Ten
     return hipSuccess;
 }
 
+// vocoder stage lengths as affine functions of the frame count L: len_i = L*mul_i + add_i (Q1: the reference
+// never crops the transposed conv, so every stage gains K - s samples; vits.cpp:187)
+void Engine::set_stage_affine(Call& c) const {
+    const int n_up = c.n_up;
+    std::vector<int>&smul = c.smul, &sadd = c.sadd;
+    smul.assign(n_up + 1, 0);
+    sadd.assign(n_up + 1, 0);
+    smul[0] = 1;
+    for (int i = 0; i < n_up; ++i) {
+        const int s = ups_[i].stride, K = ups_[i].k;
+        const int crop = c.refmode ? 0 : (K - s) / 2;
+        smul[i + 1] = smul[i] * s;
+        sadd[i + 1] = sadd[i] * s + (K - s - 2 * crop);
+    }
+}
+
 int Engine::layout_stage_one(Call& c) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
@@ -154,36 +170,10 @@ int Engine::layout_stage_one(Call& c) {
         x16_elems1 = arith_now_ != VITS_ARITH_F32 ? (size_t)B * round_up(std::max({hp.ffn_dim, 2 * F, H}), 8) * round_up(ts, 8) : 0;
         s1.x16 = x16_elems1 ? a.alloc<uint16_t>(x16_elems1) : nullptr;
     };
-    {
-        Arena measure;
-        measure.cap = (size_t)1 << 60;
-        layout1(measure);
-        const size_t need = measure.off + 4096;
-        measure.cap = 0;
-        if (need > a1().cap) HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(a1().reserve(need));
-        layout1(a1());
-        for (int i = 0; i < 3; ++i) {
-            x16_[i] = Ref16();
-            x16_cap_[i] = 0;
-        }
-        x16_[0].p = s1.x16;
-        x16_cap_[0] = x16_elems1;
-    }
-    // vocoder stage lengths as affine functions of the frame count L: len_i = L*mul_i + add_i (Q1: the reference
-    // never crops the transposed conv, so every stage gains K - s samples; vits.cpp:187)
-    std::vector<int>& smul = c.smul;
-    std::vector<int>& sadd = c.sadd;
-    smul.assign(n_up + 1, 0);
-    sadd.assign(n_up + 1, 0);
-    smul[0] = 1;
-    sadd[0] = 0;
-    for (int i = 0; i < n_up; ++i) {
-        const int s = ups_[i].stride, K = ups_[i].k;
-        const int crop = c.refmode ? 0 : (K - s) / 2;
-        smul[i + 1] = smul[i] * s;
-        sadd[i + 1] = sadd[i] * s + (K - s - 2 * crop);
-    }
+    if (arena_layout(a1(), stream, err, layout1)) return -1;
+    set_x16_scratch(s1.x16, nullptr, nullptr, x16_elems1);
+    set_stage_affine(c);
+    const std::vector<int>&smul = c.smul, &sadd = c.sadd;
     const int32_t* ids = c.ids;
     const std::vector<int>& tlen = c.tlen;
     {
@@ -194,31 +184,26 @@ int Engine::layout_stage_one(Call& c) {
         if (hs.pending) HIP_OK(hipEventSynchronize(hs.ev));
         hs.pending = false;
         if (!hs.ev) HIP_OK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-        if (hs.cap < hdr_ints) {
-            if (hs.p) hipHostFree(hs.p);
-            hs.p = nullptr;
-            hs.cap = 0;
-            HIP_OK(hipHostMalloc((void**)&hs.p, (hdr_ints + hdr_ints / 4 + 64) * sizeof(int), hipHostMallocDefault));
-            hs.cap = hdr_ints + hdr_ints / 4 + 64;
-        }
-        std::memcpy(hs.p, ids, sizeof(int) * (size_t)B * id_stride);
-        std::memcpy(hs.p + (size_t)B * id_stride, tlen.data(), sizeof(int) * B);
-        std::memcpy(hs.p + (size_t)B * id_stride + B, smul.data(), sizeof(int) * (n_up + 1));
-        std::memcpy(hs.p + (size_t)B * id_stride + B + (n_up + 1), sadd.data(), sizeof(int) * (n_up + 1));
+        HIP_OK(hs.buf.ensure(hdr_ints, hdr_ints + hdr_ints / 4 + 64));
+        int* const hdr = hs.buf.p;
+        std::memcpy(hdr, ids, sizeof(int) * (size_t)B * id_stride);
+        std::memcpy(hdr + (size_t)B * id_stride, tlen.data(), sizeof(int) * B);
+        std::memcpy(hdr + (size_t)B * id_stride + B, smul.data(), sizeof(int) * (n_up + 1));
+        std::memcpy(hdr + (size_t)B * id_stride + B + (n_up + 1), sadd.data(), sizeof(int) * (n_up + 1));
         // counter-noise stream of utterance b: noise_seed + seed_off[b] (default b; a dispatcher that re-orders utterances
         // across ranks passes each one's global index so that its audio does not depend on where it ran)
-        for (int b = 0; b < B; ++b) hs.p[(size_t)B * id_stride + B + 2 * (n_up + 1) + b] = o.noise_seed_offsets ? o.noise_seed_offsets[b] : b;
+        for (int b = 0; b < B; ++b) hdr[(size_t)B * id_stride + B + 2 * (n_up + 1) + b] = o.noise_seed_offsets ? o.noise_seed_offsets[b] : b;
         // speaker s of utterance b -> row s + 1 of the effective-bias table (row 0: speaker -1, the plain biases); the kernels get the rows only
         // when some utterance has a speaker
         bool any_spk = false;
         for (int b = 0; b < B; ++b) {
             const int sp = speaker_of(o, b);
-            hs.p[(size_t)B * id_stride + 2 * B + 2 * (n_up + 1) + b] = sp + 1;
+            hdr[(size_t)B * id_stride + 2 * B + 2 * (n_up + 1) + b] = sp + 1;
             any_spk = any_spk || sp >= 0;
         }
         c.spk = any_spk ? s1.spk_row : nullptr;
         // prosody sections at their offsets in the device header (length scale = (float)(1.0 / rate): the expression the model-level value uses)
-        auto host_of = [&](const void* dev) { return hs.p + ((const int*)dev - s1.ids); };
+        auto host_of = [&](const void* dev) { return hdr + ((const int*)dev - s1.ids); };
         if (o.speaking_rates)
             for (int b = 0; b < B; ++b) {
                 const float ls = (float)(1.0 / (double)o.speaking_rates[b]);
@@ -227,7 +212,7 @@ int Engine::layout_stage_one(Call& c) {
         if (o.noise_scales) std::memcpy(host_of(s1.noise_scale), o.noise_scales, sizeof(float) * B);
         if (o.noise_scale_durations) std::memcpy(host_of(s1.noise_scale_dur), o.noise_scale_durations, sizeof(float) * B);
         if (o.duration_override) std::memcpy(host_of(s1.dur_ovr), o.duration_override, sizeof(int) * (size_t)B * id_stride);
-        HIP_OK(hipMemcpyAsync(s1.ids, hs.p, sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(s1.ids, hdr, sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
         HIP_OK(hipEventRecord(hs.ev, stream));
         hs.pending = true;
         prof.fence();
@@ -380,19 +365,14 @@ int Engine::run_duration_predictor(Call& c) {
         // the reference's own call: the [T, 2] draws (vits.cpp:948) come from the helper thread (it holds the stream's lock: nobody else may draw now),
         // through a small pinned block — a copy from pageable memory in the middle of stage one would make the host wait for the text encoder
         const size_t n = (size_t)2 * ts;
-        if (dur_noise_cap_ < n) {
-            if (dur_noise_pinned_) hipHostFree(dur_noise_pinned_);
-            dur_noise_pinned_ = nullptr;
-            dur_noise_cap_ = 0;
-            HIP_OK(hipHostMalloc((void**)&dur_noise_pinned_, (n + 256) * sizeof(float), hipHostMallocDefault));
-            dur_noise_cap_ = n + 256;
-        }
+        HIP_OK(dur_noise_pinned_.ensure(n, n + 256));
+        float* const pinned = dur_noise_pinned_.p;
         if (dur_noise_ev_) HIP_OK(hipEventSynchronize(dur_noise_ev_));  // (the previous call's copy out of this block)
         else HIP_OK(hipEventCreateWithFlags(&dur_noise_ev_, hipEventDisableTiming));
         const float* tmpn = c.ref_ahead->duration_noise();  // memory order [2][T]
-        std::memset(dur_noise_pinned_, 0, sizeof(float) * n);
-        for (int ch = 0; ch < 2; ++ch) std::memcpy(dur_noise_pinned_ + (size_t)ch * ts, tmpn + (size_t)ch * tlen[0], sizeof(float) * tlen[0]);
-        HIP_OK(hipMemcpyAsync(s1.z, dur_noise_pinned_, sizeof(float) * n, hipMemcpyHostToDevice, stream));
+        std::memset(pinned, 0, sizeof(float) * n);
+        for (int ch = 0; ch < 2; ++ch) std::memcpy(pinned + (size_t)ch * ts, tmpn + (size_t)ch * tlen[0], sizeof(float) * tlen[0]);
+        HIP_OK(hipMemcpyAsync(s1.z, pinned, sizeof(float) * n, hipMemcpyHostToDevice, stream));
         HIP_OK(hipEventRecord(dur_noise_ev_, stream));
         prof.fence();
         if (o.collect_taps) snapshot("noise_dur", z, 2, Tmax, B, tlen);
