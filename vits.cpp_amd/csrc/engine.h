@@ -138,6 +138,10 @@ struct ResBlockW {
     std::vector<PackedConv> c1, c2;
     std::vector<int> dil;
     int k;
+    // the three conv pairs as the whole-resblock kernels take them
+    void pairs3(const PackedConv* (&w1)[3], const PackedConv* (&w2)[3]) const {
+        for (int d = 0; d < 3; ++d) w1[d] = &c1[d], w2[d] = &c2[d];
+    }
 };
 struct UpStageW {
     PackedConv up;
@@ -391,6 +395,19 @@ class Engine {
     // three streams so that the tail of one kernel's grid overlaps the head of another's. side_[j-1] carries resblock j.
     hipStream_t side_[2] = {nullptr, nullptr};
     hipEvent_t ev_fork_ = nullptr, ev_done_[3] = {nullptr, nullptr, nullptr};
+    // How a stage's resblock chains are spread over them (engine_vocoder.cpp). par: chain jj on side_[jj - 1], the first on the main stream, else all on the
+    // main stream. The last launch of chain j waits for chain j - 1's (the additions into the shared sum keep the reference's order) unless the resblocks run
+    // side by side (sum3: own outputs + one sum launch behind the join of ALL chains); those may be enqueued longest (last) first.
+    struct RbChains {
+        size_t nk;
+        bool par, sum3, longest_first;
+        size_t resblock(size_t jj) const { return longest_first ? nk - 1 - jj : jj; }  // the jj-th chain enqueued
+    };
+    hipStream_t rb_stream(const RbChains& r, size_t jj) const { return r.par && jj > 0 ? side_[jj - 1] : stream; }
+    hipError_t rb_fork(size_t n_side);                                          // the first n_side side streams behind what the main stream holds now
+    hipError_t rb_chain_wait(const RbChains& r, size_t j, hipStream_t sj);     // in front of the last launch of resblock j's chain
+    hipError_t rb_chain_done(const RbChains& r, size_t j, hipStream_t sj);     // behind it
+    hipError_t rb_join(const RbChains& r);                                      // the main stream behind the chains
     int halo_frames_ = 0;      // receptive field of the vocoder in frames, one side (computed at load)
     PinnedBuf<char> pinned_;       // staging for streamed PCM (sized in bytes)
     PinnedBuf<int> frames_host_;   // destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
