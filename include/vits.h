@@ -417,7 +417,14 @@ VITS_API int64_t vits_prof_report(vits_model* model, char* buf, size_t cap);
  * of the same reference lines. All tensors are dense fp32, layout [batch][channels][time], time fastest
  * (== the reference's ggml ne order [time, channels, batch]). lens may be NULL (all = T). */
 
-/* Arithmetic of the operator-level conv entry points below on this thread (VITS_ARITH_*; default fp32). */
+/* Arithmetic of the operator-level conv entry points below on this thread (VITS_ARITH_*; default fp32).
+ * VITS_ARITH_F32_SPLIT: vits_op_conv1d and vits_op_resblock_pair run the split kernels (conv_split.hip) exactly as the
+ * engine launches them — weights packed as two bf16 planes, the input converted to its three planes (leaky_relu(pre_slope)
+ * first), bias / residual / accum + out_scale in the epilogue — or return -1 with the cause in vits_last_error: a shape the
+ * split kernels do not take (c_in a multiple of 32 and >= 128, c_out a multiple of 128, k in {3, 7, 11}, dilation in
+ * {1, 3, 5}), post_act != 0, a weight that is not the exact sum of two bf16 values. They never fall back to another kernel.
+ * The plane buffers are filled with bf16 NaNs before the conversion, so a read past an utterance's length shows in the
+ * result. vits_op_conv_transpose1d has no split form (the upsamplers are fp32 kernels in that mode) and refuses. */
 VITS_API int vits_op_set_arith(int32_t arith);
 
 /* conv1d_with_bias (vits.cpp:171-176 -> custom-ops.h:680-694) with the fusions the engine uses.
@@ -436,6 +443,20 @@ typedef struct vits_conv1d_desc {
 } vits_conv1d_desc;
 VITS_API int vits_op_conv1d(const vits_conv1d_desc* d, const float* x, const float* w, const float* bias,
                             const float* residual, const float* accum, const int32_t* lens, float* y);
+
+/* One conv pair of a HiFiGAN ResBlock (vits.cpp:545-581), C -> C, k odd, "same" padding, one slope:
+ *   y = x + b2 + conv2(leaky_relu(b1 + conv1(leaky_relu(x)))),  conv1 at `dilation`, conv2 at dilation 1.
+ * VITS_ARITH_F32: two conv launches (the intermediate is stored activated). VITS_ARITH_F32_SPLIT: the launch sequence of the
+ * engine's un-fused split ResBlocks — the converter writes the planes of leaky_relu(x), conv1 writes ONLY the three planes of
+ * its activated result, conv2 reads them with x as its residual — or a refusal as for vits_op_conv1d. The 16-bit modes
+ * refuse. w1, w2 are [C][C][K] (torch layout); b1, b2 may be NULL. */
+typedef struct vits_resblock_pair_desc {
+    int32_t batch, channels, t, t_stride;
+    int32_t k, dilation;
+    float slope;
+} vits_resblock_pair_desc;
+VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float* x, const float* w1, const float* b1,
+                                   const float* w2, const float* b2, const int32_t* lens, float* y);
 
 /* conv_transpose_1d_with_bias (vits.cpp:178-193). w is [Cin][Cout][K] (torch layout), K == 2*stride.
  * crop = (K-stride)/2 in HF mode (HF modeling_vits.py:483-490), 0 in reference mode (vits.cpp:187, Q1).

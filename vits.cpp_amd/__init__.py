@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_clear_voices", "vits_model_num_voices",
     "vits_model_set_prosody", "vits_model_get_prosody",
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
-    "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align",
+    "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -77,6 +77,11 @@ class Conv1dDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32),
                 ("k", C.c_int32), ("dilation", C.c_int32), ("pad_left", C.c_int32), ("pre_act", C.c_int32),
                 ("pre_slope", C.c_float), ("post_act", C.c_int32), ("out_scale", C.c_float)]
+
+
+class ResblockPairDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32),
+                ("dilation", C.c_int32), ("slope", C.c_float)]
 
 
 class ConvT1dDesc(C.Structure):
@@ -216,6 +221,8 @@ def lib():
     L.vits_prof_report.argtypes = [vp, C.c_char_p, sz]
     L.vits_op_conv1d.restype = i32
     L.vits_op_conv1d.argtypes = [C.POINTER(Conv1dDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.vits_op_resblock_pair.restype = i32
+    L.vits_op_resblock_pair.argtypes = [C.POINTER(ResblockPairDesc), vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_conv_transpose1d.restype = i32
     L.vits_op_conv_transpose1d.argtypes = [C.POINTER(ConvT1dDesc), vp, vp, vp, vp, vp]
     L.vits_op_rel_attention.restype = i32
@@ -844,7 +851,8 @@ def durations_to_seconds(durations, model):
 
 # ---- operator-level wrappers (parity tests) ----------------------------------------------------------
 def op_set_arith(arith):
-    """Arithmetic of op_conv1d / op_conv_transpose1d on this thread (ARITH_F32 | ARITH_BF16 | ARITH_F16)."""
+    """Arithmetic of op_conv1d / op_conv_transpose1d / op_resblock_pair on this thread (ARITH_F32 | ARITH_BF16 | ARITH_F16 | ARITH_F32_SPLIT: the split
+    kernels or a VitsError that names the cause, never another kernel — include/vits.h vits_op_set_arith)."""
     f = lib().vits_op_set_arith
     f.restype, f.argtypes = C.c_int32, [C.c_int32]
     if f(arith) != 0:
@@ -863,6 +871,21 @@ def op_conv1d(x, w, bias=None, dilation=1, pad_left=None, pre_slope=None, post_a
     bias, residual, accum = _f32(bias), _f32(residual), _f32(accum)
     lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
     if lib().vits_op_conv1d(C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(accum), _ptr(lens), _ptr(y)) != 0:
+        raise VitsError(last_error())
+    return y
+
+
+def op_resblock_pair(x, w1, b1, w2, b2, dilation, slope, lens=None):
+    """y = x + b2 + conv2(leaky_relu(b1 + conv1(leaky_relu(x)))), conv1 at `dilation`, conv2 at dilation 1 (vits_op_resblock_pair): two fp32 convs, or in
+    ARITH_F32_SPLIT the engine's un-fused split ResBlock sequence (conv1 writes only the three planes conv2 reads)."""
+    x, w1, w2, b1, b2 = _f32(x), _f32(w1), _f32(w2), _f32(b1), _f32(b2)
+    B, ch, T = x.shape
+    k = w1.shape[2]
+    assert w1.shape == (ch, ch, k) and w2.shape == (ch, ch, k)
+    d = ResblockPairDesc(B, ch, T, T, k, dilation, slope)
+    y = np.zeros((B, ch, T), np.float32)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lib().vits_op_resblock_pair(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
 

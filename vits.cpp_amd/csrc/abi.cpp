@@ -765,10 +765,108 @@ hipError_t run_op_conv(vits::PackedConv& pc, const vits::ConvCall& c, const floa
     q.tile = c.tile;
     return launch_conv16(pc, q, g_op_arith, nullptr);
 }
+
+// ---- VITS_ARITH_F32_SPLIT at operator level: the engine's own sequence (pack_conv_weights_split, launch_split_planes, launch_conv_split) or a refusal
+// that names its cause — never another kernel, so that a test cannot believe the split kernels ran when they did not.
+struct DevU16 {
+    uint16_t* p = nullptr;
+    ~DevU16() {
+        if (p) hipFree(p);
+    }
+    bool fill(size_t n, int byte) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * 2) == hipSuccess && hipMemset(p, byte, n * 2) == hipSuccess; }
+    bool put(const std::vector<uint16_t>& h) { return hipMalloc((void**)&p, std::max<size_t>(h.size(), 1) * 2) == hipSuccess && hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice) == hipSuccess; }
+};
+// three-plane activation buffer [batch][3][channels / 8][ts][8], every byte 0xFF (bf16 NaN): a slot the writer skips (t >= len[b]) and a conv reads shows in the result
+bool split3_nan(DevU16& d, int batch, int channels, int ts, vits::Split3Ref* r) {
+    if (!d.fill((size_t)batch * 3 * channels * ts, 0xFF)) return false;
+    r->p = d.p;
+    r->ts = ts;
+    r->ps = (int64_t)channels * ts;
+    r->bs = 3 * r->ps;
+    return true;
+}
+// why the split kernels do not take a conv (conv_split.hip conv_split_candidate / conv_split_supported), or "" if they do
+std::string split_refusal(int cin, int cout, int k, int dil) {
+    char m[200] = "";
+    if (cin < 128 || (cin & 31)) std::snprintf(m, sizeof(m), "VITS_ARITH_F32_SPLIT: c_in = %d is not taken by the split kernels (a multiple of 32, at least 128)", cin);
+    else if (cout < 128 || (cout & 127)) std::snprintf(m, sizeof(m), "VITS_ARITH_F32_SPLIT: c_out = %d is not taken by the split kernels (a multiple of 128)", cout);
+    else if (k != 3 && k != 7 && k != 11) std::snprintf(m, sizeof(m), "VITS_ARITH_F32_SPLIT: k = %d taps are not taken by the split kernels (3, 7 or 11)", k);
+    else if (dil != 1 && dil != 3 && dil != 5) std::snprintf(m, sizeof(m), "VITS_ARITH_F32_SPLIT: dilation %d is not taken by the split kernels (1, 3 or 5)", dil);
+    return m;
+}
+// the split weight planes and the bias of one conv on the device; `why` names the cause when the split kernels do not take it
+bool split_conv_upload(const float* w, const float* bias, int cout, int cin, int k, int dil, vits::PackedConv& pc, DevU16& dw, DevBuf& db, std::string& why) {
+    using namespace vits;
+    why = split_refusal(cin, cout, k, dil);
+    if (!why.empty()) return false;
+    std::vector<uint16_t> packed;
+    if (!pack_conv_weights_split(w, cout, cin, k, packed)) {
+        why = "VITS_ARITH_F32_SPLIT: a weight is not the exact sum of two bf16 values (the split kernels take fp16- or bf16-valued weights)";
+        return false;
+    }
+    if (!dw.put(packed) || (bias && !db.put(bias, cout))) {
+        why = "device allocation failed";
+        return false;
+    }
+    pc.cin = cin;
+    pc.cout = cout;
+    pc.kt = k;
+    pc.epi = EPI_STD;
+    pc.nchunks = (cin + 31) / 32;
+    pc.wps = dw.p;
+    pc.bytes_s = (int64_t)packed.size() * 2;
+    pc.bias = db.p;
+    if (!conv_split_supported(pc, dil)) {
+        why = "VITS_ARITH_F32_SPLIT: conv_split_supported refuses this conv";
+        return false;
+    }
+    return true;
+}
+bool split_lens_ok(const int32_t* lens, int batch, int t, int t_stride) {
+    if (batch < 1 || t < 1 || t_stride < t) return false;
+    for (int b = 0; lens && b < batch; ++b)
+        if (lens[b] < 0 || lens[b] > t) return false;
+    return true;
+}
+int op_conv1d_split(const vits_conv1d_desc* d, const float* x, const float* w, const float* bias, const float* residual, const float* accum, const int32_t* lens, float* y) {
+    using namespace vits;
+    if (d->post_act != 0) return fail("VITS_ARITH_F32_SPLIT: post_act (relu / gate) does not exist on the split kernels");
+    if (!split_lens_ok(lens, d->batch, d->t, d->t_stride)) return fail("VITS_ARITH_F32_SPLIT: 0 <= lens[b] <= t <= t_stride is required");
+    PackedConv pc;
+    DevU16 dw, dxs;
+    DevBuf db, dx, dy, dr, da;
+    DevInts dl;
+    std::string why;
+    if (!split_conv_upload(w, bias, d->cout, d->cin, d->k, d->dilation, pc, dw, db, why)) return fail(why.c_str());
+    const size_t nx = (size_t)d->batch * d->cin * d->t_stride, ny = (size_t)d->batch * d->cout * d->t_stride;
+    Split3Ref xs;
+    if (!dx.put(x, nx) || !dy.put(nullptr, ny) || !dl.put(lens, d->batch) || !split3_nan(dxs, d->batch, d->cin, d->t_stride, &xs)) return fail("device allocation failed");
+    if (residual && !dr.put(residual, ny)) return fail("device allocation failed");
+    if (accum && !da.put(accum, ny)) return fail("device allocation failed");
+    hipError_t e = launch_split_planes(tref(dx.p, d->cin, d->t_stride), d->cin, dl.p, d->batch, d->t, d->pre_act ? d->pre_slope : 1.0f, xs, nullptr);
+    if (e == hipSuccess) {
+        ConvCall c;
+        c.xs3 = xs;
+        c.y = tref(dy.p, d->cout, d->t_stride);
+        if (residual) c.res = tref(dr.p, d->cout, d->t_stride);
+        if (accum) c.acc = tref(da.p, d->cout, d->t_stride);
+        c.len_in = c.len_out = dl.p;
+        c.batch = d->batch;
+        c.t_in = c.t_out = d->t;
+        c.dil = d->dilation;
+        c.pad_l = d->pad_left;
+        c.scale = d->out_scale;
+        e = launch_conv_split(pc, c, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+}
 }  // namespace
 
 VITS_API int vits_op_set_arith(int32_t arith) {
-    if (arith != VITS_ARITH_F32 && arith != VITS_ARITH_BF16 && arith != VITS_ARITH_F16) return fail("bad arithmetic mode");
+    if (arith != VITS_ARITH_F32 && arith != VITS_ARITH_BF16 && arith != VITS_ARITH_F16 && arith != VITS_ARITH_F32_SPLIT) return fail("bad arithmetic mode");
     g_op_arith = arith;
     return 0;
 }
@@ -778,6 +876,7 @@ VITS_API int vits_op_conv1d(const vits_conv1d_desc* d, const float* x, const flo
     VITS_TRY
     using namespace vits;
     if (!d || !x || !w || !y) return fail("null argument");
+    if (g_op_arith == VITS_ARITH_F32_SPLIT) return op_conv1d_split(d, x, w, bias, residual, accum, lens, y);
     const int gate = d->post_act == 2;
     const int cy = gate ? d->cout / 2 : d->cout;
     PackedConv pc;
@@ -824,11 +923,89 @@ VITS_API int vits_op_conv1d(const vits_conv1d_desc* d, const float* x, const flo
     VITS_CATCH(-1)
 }
 
+VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   const int32_t* lens, float* y) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !w1 || !w2 || !y) return fail("null argument");
+    if (g_op_arith != VITS_ARITH_F32 && g_op_arith != VITS_ARITH_F32_SPLIT) return fail("vits_op_resblock_pair: VITS_ARITH_F32 or VITS_ARITH_F32_SPLIT only");
+    if (!split_lens_ok(lens, d->batch, d->t, d->t_stride)) return fail("vits_op_resblock_pair: 0 <= lens[b] <= t <= t_stride is required");
+    if (d->channels < 1 || d->k < 1 || !(d->k & 1) || d->dilation < 1) return fail("vits_op_resblock_pair: an odd tap count and a dilation >= 1 are required");
+    const int C = d->channels, k = d->k;
+    const size_t n = (size_t)d->batch * C * d->t_stride;
+    DevBuf dx, dy, db1, db2;
+    DevInts dl;
+    if (!dx.put(x, n) || !dy.put(nullptr, n) || !dl.put(lens, d->batch)) return fail("device allocation failed");
+    const TensorRef bx = tref(dx.p, C, d->t_stride), by = tref(dy.p, C, d->t_stride);
+    // conv 1 / conv 2 of a pair as engine_vocoder.cpp builds them (mk_c1 / mk_c2)
+    ConvCall c1, c2;
+    c1.len_in = c1.len_out = dl.p;
+    c1.batch = d->batch;
+    c1.t_in = c1.t_out = d->t;
+    c1.dil = d->dilation;
+    c1.pad_l = (k * d->dilation - d->dilation) / 2;
+    c2 = c1;
+    c2.dil = 1;
+    c2.pad_l = (k - 1) / 2;
+    c2.res = bx;
+    c2.y = by;
+    PackedConv p1, p2;
+    hipError_t e;
+    DevU16 ws1, ws2, du, dt;
+    DevBuf dw1, dw2, dwl1, dwl2, bt;
+    if (g_op_arith == VITS_ARITH_F32_SPLIT) {
+        std::string why;
+        if (!split_conv_upload(w1, b1, C, C, k, d->dilation, p1, ws1, db1, why) || !split_conv_upload(w2, b2, C, C, k, 1, p2, ws2, db2, why)) return fail(why.c_str());
+        Split3Ref su, st;
+        if (!split3_nan(du, d->batch, C, d->t_stride, &su) || !split3_nan(dt, d->batch, C, d->t_stride, &st)) return fail("device allocation failed");
+        // the un-fused split resblock: planes of leaky_relu(x); conv 1 writes ONLY the planes of leaky_relu(t); conv 2 reads them, res = x
+        c1.xs3 = su;
+        c1.ys3 = st;
+        c1.ys3_slope = d->slope;
+        c2.xs3 = st;
+        e = launch_split_planes(bx, C, dl.p, d->batch, d->t, d->slope, su, nullptr);
+        if (e == hipSuccess) e = launch_conv_split(p1, c1, nullptr);
+        if (e == hipSuccess) e = launch_conv_split(p2, c2, nullptr);
+    } else {
+        auto upload = [&](const float* w, const float* b, PackedConv& pc, DevBuf& dw, DevBuf& dwl, DevBuf& db) {
+            pc.cin = pc.cout = C;
+            pc.kt = k;
+            pc.epi = EPI_STD;
+            const std::vector<float> packed = pack_conv_weights(w, C, C, k, EPI_STD, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+            if (conv_lat16_candidate(EPI_STD, k, C)) {
+                const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, k);
+                if (!dwl.put(pl.data(), pl.size())) return false;
+                pc.wp_l16 = dwl.p;
+            }
+            if (!dw.put(packed.data(), packed.size()) || (b && !db.put(b, C))) return false;
+            pc.wp = dw.p;
+            pc.bias = db.p;
+            return true;
+        };
+        if (!upload(w1, b1, p1, dw1, dwl1, db1) || !upload(w2, b2, p2, dw2, dwl2, db2) || !bt.put(nullptr, n)) return fail("device allocation failed");
+        c1.x = bx;
+        c1.y = tref(bt.p, C, d->t_stride);
+        c1.pre_act = 1;
+        c1.slope = d->slope;
+        c1.post_act = 2;  // t is stored activated: its only reader is conv 2
+        c1.post_slope = d->slope;
+        c2.x = c1.y;
+        e = launch_conv(p1, c1, nullptr);
+        if (e == hipSuccess) e = launch_conv(p2, c2, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y) {
     VITS_TRY
     using namespace vits;
     if (!d || !x || !w || !y) return fail("null argument");
     if (d->k != 2 * d->stride) return fail("kernel must be 2*stride");
+    if (g_op_arith == VITS_ARITH_F32_SPLIT) return fail("VITS_ARITH_F32_SPLIT: the transposed conv has no split kernel");
     PackedConv pc;
     pc.cin = d->cin;
     pc.cout = d->cout;
