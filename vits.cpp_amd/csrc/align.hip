@@ -19,13 +19,13 @@
 
 #include <algorithm>
 
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
 
 namespace {
 constexpr float kAlignNeg = -1e9f;
-typedef float align_f32x16 __attribute__((ext_vector_type(16)));
 }  // namespace
 
 // planes: A [b][2F][t_stride] = s | m s (0 past the utterance's tokens), Z [b][2F][l_stride] = -0.5 z^2 | z (0 past its frames); blockIdx.z = a chunk of channels
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64) void align_logp_kernel(const float* __restrict_
     // operand lane maps of v_mfma_f32_32x32x2_f32: A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
     const float* ap = A + ((int64_t)b * K2 + (lane >> 5)) * t_stride + t0 + (lane & 31);
     const float* zp = Z + ((int64_t)b * K2 + (lane >> 5)) * l_stride + j0 + (lane & 31);
-    align_f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    floatx16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int k = 0;
     for (; k + 8 <= K2; k += 8) {  // (four steps' operands in flight; the accumulation order stays k ascending)
         float a[4], q[4];

@@ -28,33 +28,11 @@
 #include <vector>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 #include "model_file.h"
 
 namespace vits {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-
-// round-to-nearest-even pair conversion (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32), low half = a
-template <bool BF>
-__device__ __forceinline__ unsigned pack16(float a, float b) {
-    float2v f = {a, b};
-    if constexpr (BF) return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2v));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(f, half2v));
-}
-template <bool BF>
-__device__ __forceinline__ float unpack16(unsigned short h) {
-    if constexpr (BF) return __builtin_bit_cast(float, (unsigned)h << 16);
-    else return (float)__builtin_bit_cast(_Float16, h);
-}
 
 enum Epi16 : int { E16_STD = 0, E16_GATE = 1, E16_CONVT = 2, E16_GROUP = 3, E16_CONVT_GROUP = 4 };
 
@@ -142,7 +120,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
             voff[m] = tc * 16;
             oob[m] = t != tc;
         }
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         auto issue = [&](int c, int buf) __attribute__((always_inline)) {
             int4v* lbase = xs16 + buf * bufslots;
 #pragma unroll
@@ -225,18 +203,12 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
     const int lane_slot = h * xwp + wn * (NR * 32) + (lane & 31) + p.lds_off;
     // A fragments: 1 KiB per (row tile, chunk, tap, k-half), through a buffer descriptor (no VALU address arithmetic in the loop)
     const size_t tile_frags = (size_t)p.nchunks * STEPS;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     int wvoff[MR];
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr) wvoff[mr] = (int)(((size_t)(mt0 + mr) * tile_frags * 64 + lane) * 16);
     const int total_steps = p.nchunks * STEPS;
-    auto load_a = [&](int mr, int step) __attribute__((always_inline)) -> int4v {
-        return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[mr], step * 1024, 0));
-    };
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
+    auto load_a = [&](int mr, int step) __attribute__((always_inline)) -> int4v { return load_frag<int4v>(wrsrc, wvoff[mr], step); };
 
     // ring of 4 A-fragment sets, fetched 2 steps ahead; slot = global step mod 4. A chunk has 2*KT steps, so for odd KT the
     // slot of a chunk's first step alternates between 0 and 2: two compiled variants of the chunk body (BASE = 0 / 2).
@@ -277,7 +249,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
 #pragma unroll
                 for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = mfma(ring[(BASE + s) & 3][mr], b_cur[nr], acc[mr][nr]);
+                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = mfma16<BF>(ring[(BASE + s) & 3][mr], b_cur[nr], acc[mr][nr]);
                 ++gstep;
             }
         }
@@ -331,7 +303,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
             for (int nr = 0; nr < NR; ++nr) {
                 const int t = colbase + nr * 32;
                 dst[nr] = float4v{0.f, 0.f, 0.f, 0.f};
-                if (rg && ch0 < p.cout && t < ncols) dst[nr] = *reinterpret_cast<const float4v*>(rg + ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7));
+                if (rg && ch0 < p.cout && t < ncols) dst[nr] = *reinterpret_cast<const float4v*>(rg + group_off(ch0, p.g_ts, t));
             }
         };
         load_res(0, rv[0]);
@@ -349,7 +321,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
             for (int nr = 0; nr < NR; ++nr) {
                 const int t = colbase + nr * 32;
                 if (t >= ncols) continue;
-                const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+                const int64_t go = group_off(ch0, p.g_ts, t);
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -359,21 +331,9 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
                 }
                 if (ag) {
                     const float4v a4 = *reinterpret_cast<const float4v*>(ag + go);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = a4[e] + v[e];
-                        v[e] = p.scale_div ? v[e] / p.scale : v[e] * p.scale;
-                    }
+                    group_add_scale(v, a4, p.scale, p.scale_div);
                 }
-                if (yg) *reinterpret_cast<float4v*>(yg + go) = float4v{v[0], v[1], v[2], v[3]};
-                if (y16) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);  // slope 1 = identity
-                    int2v w2;
-                    w2.x = (int)pack16<BF>(v[0], v[1]);
-                    w2.y = (int)pack16<BF>(v[2], v[3]);
-                    *reinterpret_cast<int2v*>(y16 + ((int64_t)(ch0 >> 3) * p.y16_ts + t) * 8 + (ch0 & 7)) = w2;
-                }
+                group_store<BF>(v, yg, go, y16, p.y16_ts, p.y16_slope, ch0, t);
             }
         }
     } else if constexpr (EPI == E16_STD) {
@@ -397,7 +357,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
                     if (rb) v = rb[(int64_t)co * p.r_cs + t] + v;
                     if (ab) {
                         v = ab[(int64_t)co * p.a_cs + t] + v;
-                        v = p.scale_div ? v / p.scale : v * p.scale;
+                        v = scale_or_div(v, p.scale, p.scale_div);
                     }
                     if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
                     yb[(int64_t)co * p.y_cs + t] = v;
@@ -466,15 +426,7 @@ __global__ __launch_bounds__(320) void conv16_kernel(const Conv16Params p) {
                         float v[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = acc[mr][nr][4 * g + e] + bias[e];
-                        if (yg) *reinterpret_cast<float4v*>(yg + ((int64_t)(co0 >> 3) * p.g_ts + n) * 8 + (co0 & 7)) = float4v{v[0], v[1], v[2], v[3]};
-                        if (y16) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                            int2v w2;
-                            w2.x = (int)pack16<BF>(v[0], v[1]);
-                            w2.y = (int)pack16<BF>(v[2], v[3]);
-                            *reinterpret_cast<int2v*>(y16 + ((int64_t)(co0 >> 3) * p.y16_ts + n) * 8 + (co0 & 7)) = w2;
-                        }
+                        group_store<BF>(v, yg, group_off(co0, p.g_ts, n), y16, p.y16_ts, p.y16_slope, co0, n);
                     }
                 }
         }
@@ -552,8 +504,6 @@ __global__ __launch_bounds__(256) void conv_post16_kernel(const uint16_t* __rest
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int hi = emit_hi ? emit_hi[b] : len;
     if (t >= len || t < emit_lo || t >= hi) return;
-    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
     auto dot2 = [](int xa, int wa, float acc) __attribute__((always_inline)) -> float {
         if constexpr (BF) return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2v, xa), __builtin_bit_cast(bf2v, wa), acc, false);
         else return __builtin_amdgcn_fdot2(__builtin_bit_cast(half2v, xa), __builtin_bit_cast(half2v, wa), acc, false);

@@ -10,34 +10,17 @@
 //   * the whole input tile [C/8 groups][32 NR + (k-1) d slots] goes to LDS in ONE shot (LDS-DMA, all waves), no barrier inside the K loop;
 //   * a wave owns one 32-row tile x NR 32-column tiles; its A fragments come straight from memory through a ring of 16 (fetched 14 steps
 //     ahead: the weights of a batch-1 step are not in L2);
-//   * K order = (chunk, tap, k-half) on v_mfma_f32_32x32x16_{f16,bf16}, epilogue = conv16_kernel's group epilogue expression for
-//     expression: bit-identical to conv16_kernel / rbpair16_kernel / rbblock16_kernel (kernel-choice test).
+//   * K order = (chunk, tap, k-half) on v_mfma_f32_32x32x16_{f16,bf16}, epilogue = the shared group epilogue (kernel_common.h:
+//     group_add_scale / group_store): bit-identical to conv16_kernel / rbpair16_kernel / rbblock16_kernel (kernel-choice test).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
-
-namespace c16l {
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-template <bool BF>
-__device__ __forceinline__ unsigned pack16(float a, float b) {
-    float2v f = {a, b};
-    if constexpr (BF) return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2v));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(f, half2v));
-}
-}  // namespace c16l
 
 struct Conv16LatParams {
     const uint16_t* x;  // group layout [b][C/8][x_ts][8], already activated
@@ -69,8 +52,7 @@ struct Conv16LatParams {
 // Block = WM waves = WM consecutive 32-row tiles of the same 32 NR columns. (The body as a device function: conv16_lat_kernel runs it for one conv,
 // conv16_lat_group_kernel for the same-position convs of a stage's three resblocks in ONE launch.)
 template <int KT, int C, int WM, int NR, bool BF, bool XF32>  // C: input channels (= output channels for the resblock convs; the launch's grid says how many row tiles)
-__device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::int4v* xs, const int b) {
-    using namespace c16l;
+__device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, int4v* xs, const int b) {
     constexpr int G = C / 8, NCH = C / 32, STEPS = 2 * KT, TOTAL = NCH * STEPS, BN = 32 * NR;
     // xs: [G][pitch] slots of 8 x 16 bit; slot s of a row <-> time t0 - pad_l + s
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -83,11 +65,9 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
     typedef const __attribute__((address_space(3))) int4v* LdsV;
 
     // ---- the weight stream: requested first, so that its first round trip and the fill's are one ----
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     const int wvoff = (int)(((size_t)rt * TOTAL * 64 + lane) * 16);
-    auto load_a = [&](int step) __attribute__((always_inline)) -> int4v {
-        return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, step * 1024, 0));
-    };
+    auto load_a = [&](int step) __attribute__((always_inline)) -> int4v { return load_frag<int4v>(wrsrc, wvoff, step); };
     constexpr int RS = 16, RD = RS - 2;
     int4v ring[RS];
 #pragma unroll
@@ -112,7 +92,7 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
             const int t = colbase + nr * 32;
             rv[g][nr] = float4v{0.f, 0.f, 0.f, 0.f};
             av[g][nr] = float4v{0.f, 0.f, 0.f, 0.f};
-            const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+            const int64_t go = group_off(ch0, p.g_ts, t);
             if (rg && t < len) rv[g][nr] = *reinterpret_cast<const float4v*>(rg + go);
             if (ag && t < len) av[g][nr] = *reinterpret_cast<const float4v*>(ag + go);
         }
@@ -144,7 +124,7 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
         }
     } else {
         const uint16_t* xb = p.x + (int64_t)b * p.x_bs;
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         const int tx0 = t0 - p.pad_l;
         const int xw = BN + (KT - 1) * dil;  // slots a row holds (<= pitch)
         constexpr int NP = 2;  // 64-slot pieces per row: (k - 1) d <= 50. (A literal: hipcc 7.2 drops the kernel's host stub when an array sized by a template-dependent expression meets the LDS-DMA builtin.)
@@ -182,10 +162,6 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
     }
     __syncthreads();
 
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
     floatx16 acc[NR];
 #pragma unroll
     for (int j = 0; j < NR; ++j)
@@ -218,12 +194,12 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[nr] = mfma(ring[s % RS], b_cur[nr], acc[nr]);
+                    for (int nr = 0; nr < NR; ++nr) acc[nr] = mfma16<BF>(ring[s % RS], b_cur[nr], acc[nr]);
                 }
         }
     }
 
-    // ---- epilogue: conv16_kernel's group epilogue (MR = 1): this lane owns channels ch0 .. ch0 + 3 of one time step per group ----
+    // ---- epilogue: the shared group epilogue (MR = 1): this lane owns channels ch0 .. ch0 + 3 of one time step per group ----
     // (no block of this launch reads what another writes: the residual / sum may alias the output element for element only)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -232,36 +208,22 @@ __device__ __forceinline__ void conv16_lat_body(const Conv16LatParams& p, c16l::
         for (int nr = 0; nr < NR; ++nr) {
             const int t = colbase + nr * 32;
             if (t >= len) continue;
-            const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+            const int64_t go = group_off(ch0, p.g_ts, t);
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 v[e] = acc[nr][4 * g + e] + bias4[g][e];
                 if (rg) v[e] = rv[g][nr][e] + v[e];
             }
-            if (ag) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = av[g][nr][e] + v[e];
-                    v[e] = p.scale_div ? v[e] / p.scale : v[e] * p.scale;
-                }
-            }
-            if (yg) *reinterpret_cast<float4v*>(yg + go) = float4v{v[0], v[1], v[2], v[3]};
-            if (y16) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);  // slope 1 = identity
-                int2v w2;
-                w2.x = (int)pack16<BF>(v[0], v[1]);
-                w2.y = (int)pack16<BF>(v[2], v[3]);
-                *reinterpret_cast<int2v*>(y16 + ((int64_t)(ch0 >> 3) * p.y16_ts + t) * 8 + (ch0 & 7)) = w2;
-            }
+            if (ag) group_add_scale(v, av[g][nr], p.scale, p.scale_div);
+            group_store<BF>(v, yg, go, y16, p.y16_ts, p.y16_slope, ch0, t);
         }
     }
 }
 
 template <int KT, int C, int WM, int NR, bool BF, bool XF32 = false>
 __global__ __launch_bounds__(WM * 64) void conv16_lat_kernel(const Conv16LatParams p) {
-    extern __shared__ __attribute__((aligned(16))) c16l::int4v xs_dyn16[];
+    extern __shared__ __attribute__((aligned(16))) int4v xs_dyn16[];
     conv16_lat_body<KT, C, WM, NR, BF, XF32>(p, xs_dyn16, (int)blockIdx.z);
 }
 
@@ -273,7 +235,7 @@ struct Conv16LatGroupParams {
 };
 template <int C, int WM, int NR, bool BF>
 __global__ __launch_bounds__(WM * 64) void conv16_lat_group_kernel(const Conv16LatGroupParams gp) {
-    extern __shared__ __attribute__((aligned(16))) c16l::int4v xs_dyn16g[];
+    extern __shared__ __attribute__((aligned(16))) int4v xs_dyn16g[];
     const int member = (int)blockIdx.z % 3, b = (int)blockIdx.z / 3;
     if (member == 0) conv16_lat_body<3, C, WM, NR, BF, false>(gp.m[0], xs_dyn16g, b);
     else if (member == 1) conv16_lat_body<7, C, WM, NR, BF, false>(gp.m[1], xs_dyn16g, b);

@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "kernel_common.h"
 #include "kernels.h"
 
 // The kernel template is instantiated for ~40 (taps, dilation, tile, epilogue) combinations; one translation unit takes
@@ -41,7 +42,6 @@
 
 namespace vits {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int CK = 32;  // input channels per LDS chunk
 
@@ -229,7 +229,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
                 t = t < 0 ? 0 : (t > tlast ? tlast : t);
                 off4[j] = (unsigned)(r * p.x_cs + t) * 4u;
             }
-            const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, 0x7fffffff, 0x00020000);
+            const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
             constexpr int NI4 = CK / R4 * P4;  // DMA instructions of one dwordx4 fill
             auto issue = [&](int c, int buf) __attribute__((always_inline)) {
                 float* lbase = xs + buf * (CK * XWP);
@@ -392,16 +392,15 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
     // A fragments come through a buffer descriptor: the address is (SGPR descriptor) + (per-lane byte offset, loop
     // invariant VGPR) + (scalar step offset), so the K loop needs NO vector ALU work for addressing. VALU and MFMA share
     // the issue port: every v_add / v_lshl_add_u64 in the loop is MFMA time (measured ~8 % of the k = 11 K loop).
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     int wvoff[MR];
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr) wvoff[mr] = (int)(((size_t)(mt0 + mr < p.mtiles ? mt0 + mr : p.mtiles - 1) * tile4 + lane) * 16);
-    typedef float vfloat4 __attribute__((ext_vector_type(4)));
     // (the small single-buffer kernels run 3-5 blocks per CU and are not MFMA-issue bound: plain loads measured 3-6 % faster there)
     const float4* __restrict__ wq = reinterpret_cast<const float4*>(p.wp) + (size_t)(mt0 + MR <= p.mtiles ? mt0 : 0) * tile4 + lane;
     auto load_a = [&](int mr, int step) __attribute__((always_inline)) -> float4 {
         if constexpr (DB) {
-            const vfloat4 v = __builtin_bit_cast(vfloat4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[mr], step * 1024, 0));
+            const float4v v = load_frag<float4v>(wrsrc, wvoff[mr], step);
             return make_float4(v.x, v.y, v.z, v.w);
         } else {
             return wq[(size_t)mr * tile4 + (size_t)step * 64];
@@ -676,7 +675,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
                             if (rb) v = r4[e] + v;
                             if (ab) {
                                 v = a4[e] + v;
-                                v = p.scale_div ? v / p.scale : v * p.scale;
+                                v = scale_or_div(v, p.scale, p.scale_div);
                             }
                             if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
                             o[e] = v;
@@ -706,7 +705,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
                     if (rb) v = rb[(int64_t)co * p.r_cs + t] + v;
                     if (ab) {
                         v = ab[(int64_t)co * p.a_cs + t] + v;
-                        v = p.scale_div ? v / p.scale : v * p.scale;
+                        v = scale_or_div(v, p.scale, p.scale_div);
                     }
                     if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
                     yb[(int64_t)co * p.y_cs + t] = v;
@@ -916,7 +915,6 @@ __global__ __launch_bounds__(DB ? 320 : 256) VITS_WAVES_ATTR void conv_mfma_kern
 //   layers conv_lat16_candidate names): one 16-byte load per lane feeds four MFMAs = 16 input channels, fetched 14 loads ahead (read out
 //   of the 32 x 32 array — half of every float4 unused — the stream was latency-bound: 768 -> 192, k = 3: 38 us against 41 for the 32 x 32
 //   tile); K order = (chunk, tap, channel), as everywhere.
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 template <int EPI, int P>  // P: LDS row pitch (floats) = 16 columns + span + shift (<= 3) rounded up: 24 (span <= 4), 40 (<= 20), 72 (<= 52); a
                            // compile-time constant so that the B reads of a tap are ONE base register + immediate offsets
 __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
@@ -950,11 +948,10 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
     const int NQ = 2 * G;          // quads (16 channels of one tap: four MFMAs, one float4 of A per lane)
     // A stream: descriptor + per-lane byte offset (loop-invariant VGPR) + scalar quad offset — no vector ALU work per load; the array
     // carries AHEAD quads of slack at its end (repack_conv_weights_l16), so the look-ahead needs no clamp
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wl16), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wl16);
     const int wvoff = (int)((((size_t)(mtile < p.mtiles ? mtile : p.mtiles - 1) * 2 + half) * (size_t)NQ * 64 + lane) * 16);
-    typedef float vfloat4 __attribute__((ext_vector_type(4)));
     auto load_q = [&](int q) __attribute__((always_inline)) -> float4 {
-        const vfloat4 v = __builtin_bit_cast(vfloat4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, q * 1024, 0));
+        const float4v v = load_frag<float4v>(wrsrc, wvoff, q);
         return make_float4(v.x, v.y, v.z, v.w);
     };
     constexpr int R = 32, AHEAD = 30;  // A ring: 32 float4, fetched 30 quads (120 MFMAs, ~4k cycles) ahead: the weights of a batch-1 step come from HBM / the MALL, not from L2
@@ -1144,7 +1141,7 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
     for (int s8 = 0; s8 < 8; ++s8) bq[0][s8] = xl[(4 * s8) * P];  // tap 0 = (chunk 0, tap 0)
     int cj = 0, toff = 0;  // tap counter within the chunk; LDS offset (floats) of the current tap = chunk * 32 * P + tap * dil
     const int wrap = CK * P - (KT - 1) * dil;
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    float4v acc = {0.f, 0.f, 0.f, 0.f};
     for (int q0 = 0; q0 < NQ; q0 += R) {
 #pragma unroll
         for (int tp = 0; tp < R / 2; ++tp) {  // (no break in here: the ring and the B registers need compile-time indices)
@@ -1195,7 +1192,7 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
             if (rb) v = ep_res[r] + v;
             if (ab) {
                 v = ep_acc[r] + v;
-                v = p.scale_div ? v / p.scale : v * p.scale;
+                v = scale_or_div(v, p.scale, p.scale_div);
             }
             if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
             yb[(int64_t)co * p.y_cs + t] = v;

@@ -28,32 +28,23 @@
 #include <vector>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 #include "model_file.h"
 
 namespace vits {
 
 // (helpers)
-typedef float cs_floatx16 __attribute__((ext_vector_type(16)));
-typedef float cs_float2v __attribute__((ext_vector_type(2)));
-typedef int cs_int4v __attribute__((ext_vector_type(4)));
-typedef int cs_int2v __attribute__((ext_vector_type(2)));
-typedef __bf16 cs_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cs_bf2v __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ unsigned cs_pack(float a, float b) {  // v_cvt_pk_bf16_f32: round to nearest even, low half = a
-    cs_float2v f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, cs_bf2v));
-}
 __device__ __forceinline__ float cs_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float cs_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 // four fp32 values -> their three bf16 planes (8 bytes each): piece k = RNE(what pieces < k left), exact remainders
-__device__ __forceinline__ void cs_split4(const float* v, cs_int2v* out) {
+__device__ __forceinline__ void cs_split4(const float* v, int2v* out) {
     float r[4] = {v[0], v[1], v[2], v[3]};
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-        const unsigned a = cs_pack(r[0], r[1]), b = cs_pack(r[2], r[3]);
-        out[p] = cs_int2v{(int)a, (int)b};
+        const unsigned a = pack16<true>(r[0], r[1]), b = pack16<true>(r[2], r[3]);
+        out[p] = int2v{(int)a, (int)b};
         r[0] -= cs_lo(a), r[1] -= cs_hi(a), r[2] -= cs_lo(b), r[3] -= cs_hi(b);
     }
 }
@@ -99,7 +90,7 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
     constexpr int WN = 4 / WM, BN = 128 * WN, NR = 4, STEPS = KT * 2;
     constexpr int XWP = (BN + (KT - 1) * DIL + 7) / 8 * 8;  // slots per LDS group row
     constexpr int BUF = 3 * 4 * XWP;                         // slots per buffer: [plane][group][XWP]
-    extern __shared__ __attribute__((aligned(16))) cs_int4v xs[];
+    extern __shared__ __attribute__((aligned(16))) int4v xs[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int b = blockIdx.z, t0 = blockIdx.x * BN;
     const int len_in = p.len_in ? p.len_in[b] : p.t_in;
@@ -123,9 +114,9 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
             voff[m] = tc * 16;
             oob[m] = t != tc;
         }
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         auto issue = [&](int c, int buf) __attribute__((always_inline)) {
-            cs_int4v* lbase = xs + buf * BUF;
+            int4v* lbase = xs + buf * BUF;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
@@ -139,8 +130,8 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
         };
         auto finish = [&](int buf) __attribute__((always_inline)) {
             if (!interior) {
-                cs_int4v* lbase = xs + buf * BUF;
-                const cs_int4v z = {0, 0, 0, 0};
+                int4v* lbase = xs + buf * BUF;
+                const int4v z = {0, 0, 0, 0};
 #pragma unroll
                 for (int q = 0; q < 12; ++q)
 #pragma unroll
@@ -165,26 +156,23 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
     // ---- compute waves: row tile wm of the block, four column tiles from column 128 wn ----
     const int wm = wid % WM, wn = wid / WM;
     const int mt = blockIdx.y * WM + wm;
-    cs_floatx16 acc[NR];
+    floatx16 acc[NR];
 #pragma unroll
     for (int n = 0; n < NR; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
     const int h = lane >> 5;
-    typedef const __attribute__((address_space(3))) cs_int4v* LdsV;
+    typedef const __attribute__((address_space(3))) int4v* LdsV;
     const int lane_slot = h * XWP + 128 * wn + (lane & 31);
     const int total_steps = p.nchunks * STEPS;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     const int wvoff = (int)((((size_t)mt * total_steps * 2) * 64 + lane) * 16);
-    auto load_a = [&](int step, int pl) __attribute__((always_inline)) -> cs_int4v {
-        return __builtin_bit_cast(cs_int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (step * 2 + pl) * 1024, 0));
-    };
-    auto mfma = [&](cs_int4v a, cs_int4v bq, cs_floatx16 c) __attribute__((always_inline)) -> cs_floatx16 {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cs_bf16x8, a), __builtin_bit_cast(cs_bf16x8, bq), c, 0, 0, 0);
+    auto load_a = [&](int step, int pl) __attribute__((always_inline)) -> int4v {
+        return load_frag<int4v>(wrsrc, wvoff, step * 2 + pl);
     };
     // ring of 4 A-fragment sets (two planes each), fetched two steps ahead; a chunk has 2 KT steps, so for odd KT the ring phase of a chunk's first
     // step alternates between 0 and 2 (conv16.hip: the chunk loop walks pairs of chunks, both phases straight-line code)
-    cs_int4v ring[4][2];
+    int4v ring[4][2];
     ring[0][0] = load_a(0, 0), ring[0][1] = load_a(0, 1);
     ring[1][0] = load_a(total_steps > 1 ? 1 : 0, 0), ring[1][1] = load_a(total_steps > 1 ? 1 : 0, 1);
     int gstep = 0;
@@ -201,19 +189,19 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
                     ring[(BASE + s + 2) & 3][1] = load_a(nstep, 1);
                 }
                 LdsV bp = xbase + 2 * kk * XWP + j * DIL;
-                cs_int4v bq[3][NR];
+                int4v bq[3][NR];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int n = 0; n < NR; ++n) bq[pl][n] = bp[pl * 4 * XWP + 32 * n];
-                const cs_int4v w1 = ring[(BASE + s) & 3][0], w2 = ring[(BASE + s) & 3][1];
+                const int4v w1 = ring[(BASE + s) & 3][0], w2 = ring[(BASE + s) & 3][1];
 #pragma unroll
                 for (int n = 0; n < NR; ++n) {
-                    acc[n] = mfma(w1, bq[2][n], acc[n]);  // a3 w1 (the smallest term first)
-                    acc[n] = mfma(w2, bq[1][n], acc[n]);  // a2 w2
-                    acc[n] = mfma(w2, bq[0][n], acc[n]);  // a1 w2
-                    acc[n] = mfma(w1, bq[1][n], acc[n]);  // a2 w1
-                    acc[n] = mfma(w1, bq[0][n], acc[n]);  // a1 w1
+                    acc[n] = mfma16<true>(w1, bq[2][n], acc[n]);  // a3 w1 (the smallest term first)
+                    acc[n] = mfma16<true>(w2, bq[1][n], acc[n]);  // a2 w2
+                    acc[n] = mfma16<true>(w2, bq[0][n], acc[n]);  // a1 w2
+                    acc[n] = mfma16<true>(w1, bq[1][n], acc[n]);  // a2 w1
+                    acc[n] = mfma16<true>(w1, bq[0][n], acc[n]);  // a1 w1
                 }
                 ++gstep;
             }
@@ -269,18 +257,18 @@ __global__ __launch_bounds__(320) void conv_split_kernel(const ConvSplitParams p
                 if (rb) v[e] = rv[n][e] + v[e];
                 if (ab) {
                     v[e] = ab[(int64_t)(ch0 + e) * p.a_cs + t] + v[e];
-                    v[e] = p.scale_div ? v[e] / p.scale : v[e] * p.scale;
+                    v[e] = scale_or_div(v[e], p.scale, p.scale_div);
                 }
             }
             if (ysb) {
                 float x[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[e] = fmaxf(v[e], v[e] * p.ys_slope);  // slope 1 = identity
-                cs_int2v pl[3];
+                int2v pl[3];
                 cs_split4(x, pl);
-                uint16_t* dst = ysb + ((int64_t)(ch0 >> 3) * p.ys_ts + t) * 8 + (ch0 & 7);
+                uint16_t* dst = ysb + group_off(ch0, p.ys_ts, t);
 #pragma unroll
-                for (int q = 0; q < 3; ++q) *reinterpret_cast<cs_int2v*>(dst + q * p.ys_ps) = pl[q];
+                for (int q = 0; q < 3; ++q) *reinterpret_cast<int2v*>(dst + q * p.ys_ps) = pl[q];
             }
             if (yb) {
 #pragma unroll
@@ -306,12 +294,12 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* x, int64
     for (int e = 0; e < 8; ++e) v[e] = xb[(int64_t)e * x_cs];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * slope);
-    cs_int2v lo[3], hi[3];
+    int2v lo[3], hi[3];
     cs_split4(v, lo);
     cs_split4(v + 4, hi);
     uint16_t* dst = ys + (int64_t)b * ys_bs + ((int64_t)g * ys_ts + t) * 8;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<cs_int4v*>(dst + q * ys_ps) = cs_int4v{lo[q].x, lo[q].y, hi[q].x, hi[q].y};
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<int4v*>(dst + q * ys_ps) = int4v{lo[q].x, lo[q].y, hi[q].x, hi[q].y};
 }
 
 hipError_t launch_split_planes(TensorRef x, int channels, const int* lens, int batch, int tmax, float slope, Split3Ref out, hipStream_t s) {

@@ -15,7 +15,7 @@
 //                        phases one after the other (a wave's row tiles w, w + 4, ...) wrote the quarters of a line tens of microseconds
 //                        apart: the half-written lines left L2 before they were complete and the layer ran at 1.3 TB/s, slower than
 //                        the GEMM tile; with whole lines 0.41 against 0.53 ms per step for the two stride-8 upsamplers.
-// Same A fragments, same k-order (chunk, tap, k-half), same epilogue expressions as conv16_kernel<2, -1, ..., E16_CONVT_GROUP>:
+// Same A fragments, same k-order (chunk, tap, k-half), same epilogue (kernel_common.h: group_store) as conv16_kernel<2, -1, ..., E16_CONVT_GROUP>:
 // bit-identical (GPU test); VITS_NO_CONVT16S=1 keeps the GEMM-tile path, VITS_NO_CONVT16L=1 only for the stride-8 layers.
 // Batch 64 x 128 ids, f16: the four upsamplers 1.05 -> 0.79 ms per step; config 5 (bf16): 79.8 -> 76.8 ms.
 #include <hip/hip_runtime.h>
@@ -26,27 +26,10 @@
 #include <type_traits>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
-
-namespace ct16 {
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-template <bool BF>
-__device__ __forceinline__ unsigned pack16(float a, float b) {
-    float2v f = {a, b};
-    if constexpr (BF) return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2v));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(f, half2v));
-}
-}  // namespace ct16
 
 struct ConvT16Params {
     const uint16_t* x;  // group layout [b][cin/8][x_ts][8], already activated by its writer
@@ -72,7 +55,6 @@ struct ConvT16Params {
 // RS: weight-fragment ring (8 or 16 slots; 2 c_in / 16 must be a multiple of it)
 template <int NR, int CSPLIT, int RS, bool BF>
 __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) {
-    using namespace ct16;
     constexpr int BN = NR * CSPLIT * 32;       // input positions (GEMM columns) per block
     constexpr int XW = (BN + 1 + 7) / 8 * 8;   // slots per group row: column 0 = position t0 - 1 (tap 1 reads x[q - 1])
     extern __shared__ __attribute__((aligned(16))) int4v xs[];  // [cin/8][XW]
@@ -90,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
     // ---- the input tile, every channel group, straight into LDS (all four waves issue the DMA; positions outside the sequence are zero) ----
     {
         const uint16_t* xb = p.x + (int64_t)b * p.x_bs;
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         const int ts = t0 - 1;
         constexpr int NP = (XW + 63) / 64;
         int voff[NP];
@@ -122,16 +104,12 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
     }
     __syncthreads();
 
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
     typedef const __attribute__((address_space(3))) int4v* LdsV;
     const int cgrp = wid % CSPLIT;                 // this wave's column group
     const int cbase = cgrp * (NR * 32) + col;      // tile-local position of column tile 0
     const int nrt = p.rows >> 5;
     const int total = nchunks * 4;                 // k-steps per row tile: chunk x {tap 0, tap 1} x {k-half 0, 1}
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     const int out_len = p.len_out ? p.len_out[b] : p.t_out;
     float* yg = p.yg ? p.yg + (int64_t)b * p.g_bs : nullptr;
     uint16_t* y16 = p.y16 ? p.y16 + (int64_t)b * p.y16_bs : nullptr;
@@ -149,8 +127,8 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
     auto fetch = [&]() __attribute__((always_inline)) -> int4v {
         const int pc = lp < npass ? lp : npass - 1;  // past the end: re-read the last fragment (value unused)
         const int sc = lp < npass ? ls : total - 1;
-        const int soff = ((rt_first + pc * RSTEP) * total + sc) * 1024;
-        const int4v v = __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lanev, soff, 0));
+        const int step = (rt_first + pc * RSTEP) * total + sc;
+        const int4v v = load_frag<int4v>(wrsrc, lanev, step);
         if (++ls == total) {
             ls = 0;
             ++lp;
@@ -190,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) bq[nr] = xb[off + nr * 32];
 #pragma unroll
-                for (int nr = 0; nr < NR; ++nr) acc[nr] = mfma(ring[u], bq[nr], acc[nr]);
+                for (int nr = 0; nr < NR; ++nr) acc[nr] = mfma16<BF>(ring[u], bq[nr], acc[nr]);
             }
             xb += (RS / 4) * 4 * XW;  // RS / 4 chunks = RS channel groups
         }
@@ -208,15 +186,7 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[nr][4 * g + e] + bias[e];
-                if (yg) *reinterpret_cast<float4v*>(yg + ((int64_t)(co0 >> 3) * p.g_ts + n) * 8 + (co0 & 7)) = float4v{v[0], v[1], v[2], v[3]};
-                if (y16) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                    int2v w2;
-                    w2.x = (int)pack16<BF>(v[0], v[1]);
-                    w2.y = (int)pack16<BF>(v[2], v[3]);
-                    *reinterpret_cast<int2v*>(y16 + ((int64_t)(co0 >> 3) * p.y16_ts + n) * 8 + (co0 & 7)) = w2;
-                }
+                group_store<BF>(v, yg, group_off(co0, p.g_ts, n), y16, p.y16_ts, p.y16_slope, co0, n);
             }
         }
     }
@@ -230,7 +200,6 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
 // Work units of a block: (channel block, phase half, 64-position column pair), dealt to the four waves round robin.
 template <int BN, bool BF>
 __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Params p) {
-    using namespace ct16;
     constexpr int XW = (BN + 1 + 7) / 8 * 8;
     constexpr int NR = 2, PH = 4;
     extern __shared__ __attribute__((aligned(16))) int4v xs[];  // [cin/8][XW]
@@ -246,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
     const int h = lane >> 5, col = lane & 31;
     {
         const uint16_t* xb = p.x + (int64_t)b * p.x_bs;
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         const int ts = t0 - 1;
         constexpr int NP = (XW + 63) / 64;
         int voff[NP];
@@ -278,13 +247,9 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
     }
     __syncthreads();
 
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
     typedef const __attribute__((address_space(3))) int4v* LdsV;
     const int total = nchunks * 4;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.wp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(p.wp);
     const int out_len = p.len_out ? p.len_out[b] : p.t_out;
     float* yg = p.yg ? p.yg + (int64_t)b * p.g_bs : nullptr;
     uint16_t* y16 = p.y16 ? p.y16 + (int64_t)b * p.y16_bs : nullptr;
@@ -309,9 +274,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
         int sbase[PH];  // scalar byte offset of the first fragment of each phase's row tile
 #pragma unroll
         for (int k = 0; k < PH; ++k) sbase[k] = (((half * PH + k) * ncb + cb) * total) * 1024;
-        auto load_a = [&](int k, int step) __attribute__((always_inline)) -> int4v {
-            return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lanev, sbase[k] + step * 1024, 0));
-        };
+        auto load_a = [&](int k, int step) __attribute__((always_inline)) -> int4v { return load_frag<int4v>(wrsrc, lanev, step, sbase[k]); };
         // ring of four register sets per phase, two steps (16 MFMAs, 512 cycles) ahead
         int4v ring[4][PH];
 #pragma unroll
@@ -341,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
 #pragma unroll
                 for (int k = 0; k < PH; ++k)
 #pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[k][nr] = mfma(ring[u][k], bq[nr], acc[k][nr]);
+                    for (int nr = 0; nr < NR; ++nr) acc[k][nr] = mfma16<BF>(ring[u][k], bq[nr], acc[k][nr]);
             }
             xb += 4 * XW;
         }
@@ -396,15 +359,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
                         float v[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = t[i][e] + bias[e];
-                        if (yg) *reinterpret_cast<float4v*>(yg + ((int64_t)(co0 >> 3) * p.g_ts + n) * 8 + (co0 & 7)) = float4v{v[0], v[1], v[2], v[3]};
-                        if (y16) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                            int2v w2;
-                            w2.x = (int)pack16<BF>(v[0], v[1]);
-                            w2.y = (int)pack16<BF>(v[2], v[3]);
-                            *reinterpret_cast<int2v*>(y16 + ((int64_t)(co0 >> 3) * p.y16_ts + n) * 8 + (co0 & 7)) = w2;
-                        }
+                        group_store<BF>(v, yg, group_off(co0, p.g_ts, n), y16, p.y16_ts, p.y16_slope, co0, n);
                     }
                 }
             }
@@ -425,15 +380,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = acc[k][nr][4 * g + e] + bias[e];
-                    if (yg) *reinterpret_cast<float4v*>(yg + ((int64_t)(co0 >> 3) * p.g_ts + n) * 8 + (co0 & 7)) = float4v{v[0], v[1], v[2], v[3]};
-                    if (y16) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                        int2v w2;
-                        w2.x = (int)pack16<BF>(v[0], v[1]);
-                        w2.y = (int)pack16<BF>(v[2], v[3]);
-                        *reinterpret_cast<int2v*>(y16 + ((int64_t)(co0 >> 3) * p.y16_ts + n) * 8 + (co0 & 7)) = w2;
-                    }
+                    group_store<BF>(v, yg, group_off(co0, p.g_ts, n), y16, p.y16_ts, p.y16_slope, co0, n);
                 }
             }
         }

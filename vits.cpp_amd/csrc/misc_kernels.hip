@@ -8,6 +8,7 @@
 #include "../../include/vits.h"
 #include "../../include/vits_synth_noise.h"
 #include "../../include/vits_exact_math.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
@@ -83,15 +84,6 @@ constexpr int ATT_Q = 16;
 // latencies that only more waves hide — and 256 on large ones (16-wave blocks pack worse: 73 -> 107 us per launch at batch 64).
 // Both give the same bits: scores and outputs are per-element sums in a fixed order, and the softmax always runs on 16 lanes per query.
 
-// ---------------------------------------------------------------------------------------------------------
-// EMULATED ggml lookup tables (Q8; kernels.h GgmlTables): when a table pointer is given, GELU / the soft-max exponential go through the
-// 65536-entry fp16 table indexed by the fp16 bits of the argument, as upstream ggml's ggml_vec_gelu_f32 / ggml_compute_forward_soft_max_f32
-// do (the tables are built on the HOST with the C library's tanhf / expf, like ggml_init). Null pointers = the default arithmetic.
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ggml_table_lookup(const uint16_t* tab, float x) {
-    const uint16_t i = __builtin_bit_cast(uint16_t, (_Float16)x);  // GGML_FP32_TO_FP16: round to nearest even
-    return (float)__builtin_bit_cast(_Float16, tab[i]);
-}
 // Which of the block's 16 queries the 16-lane group t16 = tid / 16 normalises. ds_read_b32 / ds_write_b32 are served in groups of 32 lanes
 // on banks (address / 4) mod 32, and the score rows are lp = 4 (mod 64) floats apart: two ADJACENT queries in one group of 32 lanes put
 // their 16 columns on overlapping bank ranges (2-way conflicts on three passes over every row: the LDS_BANK_CONFLICT / LDS_IDX_ACTIVE = 0.37
@@ -321,7 +313,6 @@ __global__ __launch_bounds__(ATT_THREADS) void rel_attention_kernel(const float*
 // Every sum has ONE order for every grid, so results do not depend on the batch.
 // LDS: Q^T [hd][16] | q.Ek [16][nrel] | scores [16][lp], lp = 4 mod 64 (conflict-free A reads of P).
 // ---------------------------------------------------------------------------------------------------------
-typedef float att_float4v __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int att_lp(int len) { return (len + 63) / 64 * 64 + 4; }  // >= len + 4, = 4 (mod 64)
 
@@ -411,7 +402,7 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
     // windows up to 7, the MMS-TTS architecture has 4; wider windows take further tiles on the other waves)
     for (int ct = wid; ct * 16 < nrel; ct += NW) {
         const int rcol = ct * 16 + ln;
-        att_float4v acc = {0.f, 0.f, 0.f, 0.f};
+        float4v acc = {0.f, 0.f, 0.f, 0.f};
         const float* rp = rel_k + (int64_t)(rcol < nrel ? rcol : 0) * hd + lk;
 #pragma unroll
         for (int s0 = 0; s0 < MAXS; s0 += 8) {
@@ -434,14 +425,14 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
     ATT_STAMP(1);
     // ---- scores: S[16 q][16 keys] per key tile, K = hd; the K operands of this wave's next two tiles are in flight ----
     {
-        auto tile_chain = [&](const float* kop) __attribute__((always_inline)) -> att_float4v {
-            att_float4v acc = {0.f, 0.f, 0.f, 0.f};
+        auto tile_chain = [&](const float* kop) __attribute__((always_inline)) -> float4v {
+            float4v acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s2 = 0; s2 < MAXS; ++s2)
                 if (s2 < nsteps) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[s2], kop[s2], acc, 0, 0, 0);
             return acc;
         };
-        auto tile_store = [&](int n, const att_float4v acc) __attribute__((always_inline)) {
+        auto tile_store = [&](int n, const float4v acc) __attribute__((always_inline)) {
             const int key = n * 16 + ln;
             if (key < len) {
 #pragma unroll
@@ -460,7 +451,7 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
             // the first tile's MFMA chain runs BESIDE wave 0's relative-key product: the barrier that publishes q.Ek stands behind the chain, in front of the
             // first store (the other variants have it in front of the phase)
             if (n + NW < ntiles) load_tile(n + NW, k1);
-            att_float4v a0 = {0.f, 0.f, 0.f, 0.f};
+            float4v a0 = {0.f, 0.f, 0.f, 0.f};
             if (n < ntiles) a0 = tile_chain(k0);
             __syncthreads();
             if (n < ntiles) tile_store(n, a0);
@@ -518,11 +509,11 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
     const int ndt = hd >> 4;
     const int ng = (len + 15) >> 4;
     const int klast4 = (len - 1) & ~3;  // the last 16-byte piece of a row that starts inside the sequence (rows are padded to x4)
-    auto load_v = [&](int g, const float* vrow, att_float4v& vv) __attribute__((always_inline)) {
+    auto load_v = [&](int g, const float* vrow, float4v& vv) __attribute__((always_inline)) {
         const int gc = g < ng ? g : ng - 1;
         const int key0 = 16 * gc + 4 * lk;
         if (v16) {
-            const att_float4v t = *reinterpret_cast<const att_float4v*>(vrow + (key0 < klast4 ? key0 : klast4));
+            const float4v t = *reinterpret_cast<const float4v*>(vrow + (key0 < klast4 ? key0 : klast4));
             vv[0] = key0 < len ? t[0] : 0.f;
             vv[1] = key0 + 1 < len ? t[1] : 0.f;
             vv[2] = key0 + 2 < len ? t[2] : 0.f;
@@ -535,7 +526,7 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
             }
         }
     };
-    att_float4v vpre[8];  // (eight groups = 128 keys: the whole row of a 128-token utterance)
+    float4v vpre[8];  // (eight groups = 128 keys: the whole row of a 128-token utterance)
     float evp[4];
     if constexpr (LAT) {
         if (wid < ndt) {
@@ -560,35 +551,35 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
     __syncthreads();
     ATT_STAMP(3);
     // ---- O[16 q][hd] = P V: d tile dt, K = keys in groups of 16 (see the head comment), four groups in flight ----
-    att_float4v oacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // d tiles wid and wid + NW (NW >= 4, head_dim <= 128)
+    float4v oacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // d tiles wid and wid + NW (NW >= 4, head_dim <= 128)
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int dt = wid + NW * u;
         if (dt < ndt) {
             const float* prow = sc + ln * lp + 4 * lk;
             const float* vrow = vb + (int64_t)(dt * 16 + ln) * v_cs;
-            att_float4v pr[4], vr[4];
-            auto load_group = [&](int g, att_float4v& pa, att_float4v& vv) __attribute__((always_inline)) {
+            float4v pr[4], vr[4];
+            auto load_group = [&](int g, float4v& pa, float4v& vv) __attribute__((always_inline)) {
                 const int gc = g < ng ? g : ng - 1;
-                pa = *reinterpret_cast<const att_float4v*>(prow + 16 * gc);
+                pa = *reinterpret_cast<const float4v*>(prow + 16 * gc);
                 load_v(g, vrow, vv);
             };
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (LAT && u == 0) {  // (V requested before the softmax; P exists only now)
-                    pr[i] = *reinterpret_cast<const att_float4v*>(prow + 16 * (i < ng ? i : ng - 1));
+                    pr[i] = *reinterpret_cast<const float4v*>(prow + 16 * (i < ng ? i : ng - 1));
                     vr[i] = vpre[i];
                 } else {
                     load_group(i, pr[i], vr[i]);
                 }
             }
-            att_float4v a4 = oacc[u];
+            float4v a4 = oacc[u];
             for (int g = 0; g < ng; g += 4) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const att_float4v pa = pr[i], vv = vr[i];
+                    const float4v pa = pr[i], vv = vr[i];
                     if (LAT && u == 0 && g == 0) {  // (groups 4-7: V came with the first four)
-                        pr[i] = *reinterpret_cast<const att_float4v*>(prow + 16 * (4 + i < ng ? 4 + i : ng - 1));
+                        pr[i] = *reinterpret_cast<const float4v*>(prow + 16 * (4 + i < ng ? 4 + i : ng - 1));
                         vr[i] = vpre[4 + i];
                     } else {
                         load_group(g + 4 + i, pr[i], vr[i]);
@@ -611,7 +602,7 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
         for (int u = 0; u < 2; ++u) {
             const int dt = wid + NW * u;
             if (dt < ndt) {
-                att_float4v a4 = oacc[u];
+                float4v a4 = oacc[u];
                 for (int s = 0; s < rsteps; ++s) {
                     const int r = 4 * s + lk;
                     const int j = i0 + ln + r - window;
@@ -717,9 +708,6 @@ hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const flo
 //   DDS:     vits.cpp:679-688 (permute, cont, norm, permute, cont, gelu, add)
 // Block = 64 time steps x all channels; the tile is held in LDS so x is read from HBM once.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-// vits.cpp:673,687 ggml_gelu: erf-GELU (HF) by default; with a table, ggml's tanh-GELU through its fp16 lookup table (Q8, emulated)
-__device__ __forceinline__ float gelu_op(float x, const uint16_t* gelu_tab) { return gelu_tab ? ggml_table_lookup(gelu_tab, x) : gelu_erf(x); }
 
 // channel groups per block of the two LayerNorm kernels: 16 x 64 threads, every thread walks channels/16 rows. (4 groups
 // made each thread chain 48 dependent loads: 26-58 us per launch at batch 1, where these launches have 2 blocks.) The
@@ -927,10 +915,6 @@ hipError_t launch_dds_depthwise(TensorRef x, TensorRef g, const float* w, const 
 // latency per layer (12 layers per utterance); this one is ~10.
 // The block reads a halo of its neighbours' columns: x_out must not be x (Engine::run_dds rotates three buffers).
 // ---------------------------------------------------------------------------------------------------------
-typedef float dds_floatx16 __attribute__((ext_vector_type(16)));
-typedef int dds_int4v __attribute__((ext_vector_type(4)));
-typedef _Float16 dds_half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 dds_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct DdsLayerParams {
     const float* x;
@@ -976,7 +960,7 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
     float* ht = xt + ((H * xw + 3) & ~3);  // [H][NT]   depthwise output -> gelu(LN1) -> pointwise output
     float* red = ht + H * NT;              // [2][LN_GROUPS][NT]
     float* prm = red + 2 * LN_GROUPS * NT;  // [6][H] dw_b, g1, b1, pw_b, g2, b2; then [H][k] dw_w
-    dds_int4v* h16 = reinterpret_cast<dds_int4v*>(prm + ((6 * H + H * p.k + 3) & ~3));  // [H/8][NT] 16-bit operand slots (ARITH != 0)
+    int4v* h16 = reinterpret_cast<int4v*>(prm + ((6 * H + H * p.k + 3) & ~3));  // [H/8][NT] 16-bit operand slots (ARITH != 0)
     const int b = blockIdx.y, t0 = blockIdx.x * NT;
     DDS_STAMP(0);
     const int len = p.lens ? p.lens[b] : p.tmax;
@@ -1002,7 +986,7 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
         }
     }
     float4 af[ARITH == 0 ? MAXCH * 4 : 1];
-    dds_int4v ah[ARITH != 0 ? MAXCH * 2 : 1];
+    int4v ah[ARITH != 0 ? MAXCH * 2 : 1];
     {
         // flat index over [H][xw], up to 24 loads in flight per thread (a load-then-store loop exposed one memory latency per element)
         const float* xb = p.x + (int64_t)b * p.x_bs;
@@ -1033,7 +1017,7 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
 #pragma unroll
                         for (int q = 0; q < MAXCH * 4; ++q) af[q] = wp4[(q < p.nchunks * 4 ? q : 0) * 64];
                     } else {
-                        const dds_int4v* wq = reinterpret_cast<const dds_int4v*>(p.wp16) + (size_t)wid * p.nchunks * 2 * 64 + lane;
+                        const int4v* wq = reinterpret_cast<const int4v*>(p.wp16) + (size_t)wid * p.nchunks * 2 * 64 + lane;
 #pragma unroll
                         for (int q = 0; q < MAXCH * 2; ++q) ah[q] = wq[(q < p.nchunks * 2 ? q : 0) * 64];
                     }
@@ -1140,7 +1124,7 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
     __syncthreads();
     DDS_STAMP(3);
     // ---- pointwise conv on the matrix cores: wave w owns output rows 32w..32w+31 (the MFMA chain of conv_mfma.hip / conv16.hip) ----
-    dds_floatx16 acc;
+    floatx16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     if (wid < nmt) {
@@ -1161,18 +1145,15 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
                 }
             }
         } else {
-            const dds_int4v* bcol = h16 + (lane >> 5) * NT + (lane & 31);
+            const int4v* bcol = h16 + (lane >> 5) * NT + (lane & 31);
 #pragma unroll
             for (int c = 0; c < MAXCH; ++c) {
                 if (c < p.nchunks) {
 #pragma unroll
                     for (int kk = 0; kk < 2; ++kk) {
-                        const dds_int4v a = ah[c * 2 + kk];
-                        const dds_int4v bq = bcol[(c * 4 + 2 * kk) * NT];
-                        if constexpr (ARITH == 1)
-                            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(dds_bf16x8, a), __builtin_bit_cast(dds_bf16x8, bq), acc, 0, 0, 0);
-                        else
-                            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(dds_half8, a), __builtin_bit_cast(dds_half8, bq), acc, 0, 0, 0);
+                        const int4v a = ah[c * 2 + kk];
+                        const int4v bq = bcol[(c * 4 + 2 * kk) * NT];
+                        acc = mfma16<ARITH == 1>(a, bq, acc);
                     }
                 }
             }
@@ -1686,7 +1667,7 @@ __global__ __launch_bounds__(256) void rb_sum3_std_kernel(const float* y0, const
     const int64_t go = (int64_t)b * bs + (int64_t)c * cs + t;
     float x = y0[go] + y1[go];
     if (y2) x = x + y2[go];
-    x = scale_div ? x / scale : x * scale;
+    x = scale_or_div(x, scale, scale_div);
     if (post_act == 2) x = fmaxf(x, x * post_slope);
     out[(int64_t)b * o_bs + (int64_t)c * o_cs + t] = x;
 }

@@ -11,8 +11,9 @@
 // resblock): 10-14 B per element and resblock instead of 36. The price is the halo: a tile of W = 384 columns yields W - 24 (k - 1) / 2
 // outputs (k = 3: 360, 7: 312, 11: 264), i.e. 1.07 / 1.23 / 1.45 x the MFMA work, which these stages have to spare (C = 64 runs 256-column
 // tiles on four waves, 1.10 / 1.39 x, so that two blocks share a CU: see launch_rbblock16).
-// Same operands, rounding points and k-order of accumulation (chunk, tap, k-half) as rbpair16_kernel / conv16_kernel: bit-identical to
-// the pair path (GPU test), which stays for C >= 128 (MFMA-bound: the halo would cost more than the bytes) and behind VITS_NO_RBBLOCK16=1.
+// Same operands, rounding points (kernel_common.h: pack16 / group_add_scale / group_store) and k-order of accumulation (chunk, tap, k-half) as
+// rbpair16_kernel / conv16_kernel: bit-identical to the pair path (GPU test), which stays for C >= 128 (MFMA-bound: the halo would cost more
+// than the bytes) and behind VITS_NO_RBBLOCK16=1.
 // Round 6: on grids of thousands of tiles a block walks a SEGMENT of tiles and takes the halo on its left from the tile before
 // (template parameter STREAM; rbb_stream_tiles_for() says where): 1.19 x instead of 1.45 x the MFMA work at k = 11, which also brings the
 // C = 64 / k = 11 resblocks to this kernel.
@@ -23,27 +24,11 @@
 #include <cstdlib>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
 
-namespace rbb {
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-
-template <bool BF>
-__device__ __forceinline__ unsigned pack16(float a, float b) {
-    float2v f = {a, b};
-    if constexpr (BF) return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2v));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(f, half2v));
-}
 // Two 8-byte halves of two 16-byte slots per lane -> one whole slot per lane. In the MFMA C layout lane l < 32 holds channels 0-3 and lane
 // l + 32 channels 4-7 of a channel group at one column; writing them as two ds_write_b64 at a 16-byte stride is a 4-way bank conflict
 // (PMC: 0.08-0.20 of the LDS cycles of the pair kernels). v_permlane32_swap exchanges the upper half of one register with the lower half of
@@ -53,7 +38,6 @@ __device__ __forceinline__ int4v slot_pair(int2v a, int2v b) {
     const auto y = __builtin_amdgcn_permlane32_swap((unsigned)a.y, (unsigned)b.y, false, false);
     return int4v{(int)x[0], (int)y[0], (int)x[1], (int)y[1]};
 }
-}  // namespace rbb
 
 struct RbBlockParams {
     const float* y0;  // stage input (the fp32 stream), group layout [b][C/8][g_ts][8]
@@ -103,7 +87,6 @@ __device__ unsigned long long vits_rbb_phase[16 * 65536];
 // (The body as a device function: rbblock16_kernel runs it for one resblock, rbblock16_group3_kernel for the three resblocks of a stage in ONE launch.)
 template <int KT, int C, int NSTRIP, int NRW, int MRW, int D0, int D1, int D2, bool BF, bool STREAM>
 __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int b) {
-    using namespace rbb;
     constexpr int NCH = C / 32, W = NSTRIP * NRW * 32;  // (LDS tile: C / 8 channel groups x PITCH slots)
     constexpr int P2 = (KT - 1) / 2;
     constexpr int DMAX = D0 > D1 ? (D0 > D2 ? D0 : D2) : (D1 > D2 ? D1 : D2);
@@ -186,7 +169,7 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
                 for (int nr = 0; nr < NRW; ++nr) {
                     const int t = tg0 + u0 + 32 * nr;
                     float4v v = {0.f, 0.f, 0.f, 0.f};
-                    if (t >= 0 && t < len) v = *reinterpret_cast<const float4v*>(yb + ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7));
+                    if (t >= 0 && t < len) v = *reinterpret_cast<const float4v*>(yb + group_off(ch0, p.g_ts, t));
 #pragma unroll
                     for (int e = 0; e < 4; ++e) yv[m][nr][4 * g + e] = v[e];
                 }
@@ -227,10 +210,6 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
 
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
     floatx16 acc[MRW][NRW];
     // one conv over the LDS tile: output column u reads slots u + off0 + j * dstep; acc = sum over (chunk, tap, k-half) — the order of
     // rbpair16_kernel / conv16_kernel
@@ -242,13 +221,11 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
         LdsV base = (LdsV)(tile + h * PITCH + PADX + u0 + off0);
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(wp), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         int wvoff[MRW];
 #pragma unroll
         for (int m = 0; m < MRW; ++m) wvoff[m] = (int)(((size_t)(rt0 + m) * TOTAL * 64 + lane_v) * 16);
-        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> int4v {
-            return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[m], step * 1024, 0));
-        };
+        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> int4v { return load_frag<int4v>(wrsrc, wvoff[m], step); };
         // weight-fragment ring: a step is NRW 32-cycle MFMAs per row tile, an L2 round trip several steps (C = 32, k >= 7: six slots — eight spill at the 168-VGPR cap of three blocks per CU)
         constexpr int RS = MRW == 1 ? ((C == 32 && KT > 3) ? 6 : 8) : 4, RD = RS - 2;
         int4v ring[RS][MRW];
@@ -285,7 +262,7 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
 #pragma unroll
                     for (int m = 0; m < MRW; ++m)
 #pragma unroll
-                        for (int nr = 0; nr < NRW; ++nr) acc[m][nr] = mfma(ring[s % RS][m], b_cur[nr], acc[m][nr]);
+                        for (int nr = 0; nr < NRW; ++nr) acc[m][nr] = mfma16<BF>(ring[s % RS][m], b_cur[nr], acc[m][nr]);
                 }
         }
     };
@@ -368,7 +345,7 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
                     for (int nr = 0; nr < NRW; ++nr) {
                         const int u = u0 + 32 * nr, t = tg0 + u;
                         av[m][g][nr] = float4v{0.f, 0.f, 0.f, 0.f};
-                        if (u >= ulo && u < ADV && t < len) av[m][g][nr] = *reinterpret_cast<const float4v*>(ag + ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7));
+                        if (u >= ulo && u < ADV && t < len) av[m][g][nr] = *reinterpret_cast<const float4v*>(ag + group_off(ch0, p.g_ts, t));
                     }
                 }
         }
@@ -381,26 +358,12 @@ __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int
                 for (int nr = 0; nr < NRW; ++nr) {
                     const int u = u0 + 32 * nr, t = tg0 + u;
                     if (u < ulo || u >= ADV || t >= len) continue;
-                    const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+                    const int64_t go = group_off(ch0, p.g_ts, t);
                     float v[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = yv[m][nr][4 * g + e];
-                    if (ag) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            v[e] = av[m][g][nr][e] + v[e];
-                            v[e] = p.scale_div ? v[e] / p.scale : v[e] * p.scale;
-                        }
-                    }
-                    if (yg) *reinterpret_cast<float4v*>(yg + go) = float4v{v[0], v[1], v[2], v[3]};
-                    if (y16) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                        int2v w2;
-                        w2.x = (int)pack16<BF>(v[0], v[1]);
-                        w2.y = (int)pack16<BF>(v[2], v[3]);
-                        *reinterpret_cast<int2v*>(y16 + ((int64_t)(ch0 >> 3) * p.y16_ts + t) * 8 + (ch0 & 7)) = w2;
-                    }
+                    if (ag) group_add_scale(v, av[m][g][nr], p.scale, p.scale_div);
+                    group_store<BF>(v, yg, go, y16, p.y16_ts, p.y16_slope, ch0, t);
                 }
             }
     }
@@ -453,30 +416,30 @@ __global__ __launch_bounds__(256) void rb_sum3_kernel(const float* y0, const flo
     float v[8];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-        const rbb::float4v a = *reinterpret_cast<const rbb::float4v*>(y0 + go + 4 * hh), b1 = *reinterpret_cast<const rbb::float4v*>(y1 + go + 4 * hh);
-        rbb::float4v c2 = {0.f, 0.f, 0.f, 0.f};
-        if (y2) c2 = *reinterpret_cast<const rbb::float4v*>(y2 + go + 4 * hh);
+        const float4v a = *reinterpret_cast<const float4v*>(y0 + go + 4 * hh), b1 = *reinterpret_cast<const float4v*>(y1 + go + 4 * hh);
+        float4v c2 = {0.f, 0.f, 0.f, 0.f};
+        if (y2) c2 = *reinterpret_cast<const float4v*>(y2 + go + 4 * hh);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float x = a[e] + b1[e];  // (the second resblock's a + v; its scale is 1: v * 1 = v)
             if (y2) x = x + c2[e];
-            x = scale_div ? x / scale : x * scale;
+            x = scale_or_div(x, scale, scale_div);
             v[4 * hh + e] = x;
         }
     }
     if (yg) {
-        *reinterpret_cast<rbb::float4v*>(yg + go) = rbb::float4v{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<rbb::float4v*>(yg + go + 4) = rbb::float4v{v[4], v[5], v[6], v[7]};
+        *reinterpret_cast<float4v*>(yg + go) = float4v{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<float4v*>(yg + go + 4) = float4v{v[4], v[5], v[6], v[7]};
     }
     if (y16) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], v[e] * y16_slope);
-        rbb::int4v w;
-        w.x = (int)rbb::pack16<BF>(v[0], v[1]);
-        w.y = (int)rbb::pack16<BF>(v[2], v[3]);
-        w.z = (int)rbb::pack16<BF>(v[4], v[5]);
-        w.w = (int)rbb::pack16<BF>(v[6], v[7]);
-        *reinterpret_cast<rbb::int4v*>(y16 + (int64_t)b * y16_bs + ((int64_t)grp * y16_ts + t) * 8) = w;
+        int4v w;
+        w.x = (int)pack16<BF>(v[0], v[1]);
+        w.y = (int)pack16<BF>(v[2], v[3]);
+        w.z = (int)pack16<BF>(v[4], v[5]);
+        w.w = (int)pack16<BF>(v[6], v[7]);
+        *reinterpret_cast<int4v*>(y16 + (int64_t)b * y16_bs + ((int64_t)grp * y16_ts + t) * 8) = w;
     }
 }
 

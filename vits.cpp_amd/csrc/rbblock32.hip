@@ -17,12 +17,11 @@
 #include <cstdlib>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
 
-typedef float rbb32_floatx16 __attribute__((ext_vector_type(16)));
-typedef float rbb32_float4v __attribute__((ext_vector_type(4)));
 
 struct RbBlock32Params {
     const float* x;  // stage input y_0 (fp32, [b][c][t])
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
     const float* xb = p.x + (int64_t)b * p.x_bs;
 
     // ---- the fp32 stream of this wave's 32 rows x NR column tiles in the MFMA C layout: register r <-> row 8 (r / 4) + 4 krow + r % 4 ----
-    rbb32_floatx16 yv[NR];
+    floatx16 yv[NR];
 #pragma unroll
     for (int nr = 0; nr < NR; ++nr) {
         const int t = tg0 + u0 + 32 * nr;
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
     }
     // leaky_relu(src [+ bias]) of this wave's rows x columns into the LDS tile, zero outside the sequence (what a conv sees as padding):
     // x_p from the stream (bias = nullptr), t_p from the first conv's accumulators
-    auto write_tile = [&](const rbb32_floatx16 (&src)[NR], const float* bias_p) __attribute__((always_inline)) {
+    auto write_tile = [&](const floatx16 (&src)[NR], const float* bias_p) __attribute__((always_inline)) {
 #pragma unroll
         for (int nr = 0; nr < NR; ++nr) {
             const int u = u0 + 32 * nr, t = tg0 + u;
@@ -116,15 +115,15 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
 
-    rbb32_floatx16 acc[NR];
+    floatx16 acc[NR];
     // Weight fragments (float4 = 4 MFMA k-steps of the wave's row tile) travel through a ring of four register sets, two steps ahead. The first
     // two fragments of a conv are requested BEFORE the barriers and the tile write in front of it (prefetch): fetched at the top of the conv
     // they cost an exposed L2 round trip six times per block.
-    rbb32_float4v ring[4];
+    float4v ring[4];
     const int wvoff = (int)(((size_t)wm * TOTAL * 64 + lane) * 16);
-    auto load_a = [&](const float* wp, int step) __attribute__((always_inline)) -> rbb32_float4v {
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, 0x7fffffff, 0x00020000);
-        return __builtin_bit_cast(rbb32_float4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, step * 1024, 0));
+    auto load_a = [&](const float* wp, int step) __attribute__((always_inline)) -> float4v {
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
+        return load_frag<float4v>(wrsrc, wvoff, step);
     };
     auto prefetch = [&](const float* wp) __attribute__((always_inline)) {
         ring[0] = load_a(wp, 0);
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
                     const int s = (c * KT + j) * 4 + p4;  // compile time after unrolling
                     ring[(s + 2) & 3] = load_a(wp, s + 2 < TOTAL ? s + 2 : TOTAL - 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    const rbb32_float4v a4 = ring[s & 3];
+                    const float4v a4 = ring[s & 3];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int pair = p4 * 4 + q;
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
                 float v = yv[nr][r];
                 if (ab) {
                     v = av[r] + v;
-                    v = p.scale_div ? v / p.scale : v * p.scale;
+                    v = scale_or_div(v, p.scale, p.scale_div);
                 }
                 if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
                 yb[(int64_t)row * p.y_cs + t] = v;

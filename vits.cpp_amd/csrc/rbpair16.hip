@@ -5,8 +5,8 @@
 // does, keeps it in LDS in the group layout, and runs the second conv from there. Per element and pair that is
 // read x16 (2 B) + residual (4) + write y' (4) + its 16-bit copy (2) = 12 B instead of 16 B — these stages run at the HBM
 // roof in the 16-bit modes (conv16.hip), so bytes are time. Same operands, same k-order of accumulation
-// (chunk, tap, k-half) and same rounding points as conv16_kernel: the results are bit-identical to the two-kernel path
-// (GPU test), which the engine keeps for C >= 128 and as the VITS_NO_FUSE16=1 fallback.
+// (chunk, tap, k-half) and the rounding points conv16_kernel has (kernel_common.h: pack16 / group_store): the results are
+// bit-identical to the two-kernel path (GPU test), which the engine keeps for C >= 128 and as the VITS_NO_FUSE16=1 fallback.
 //
 // Block = 4 waves, no producer wave: the whole input tile (C/8 groups x (256 + (k-1)(d+1)) slots) is streamed in with LDS-DMA
 // by all four waves at once, then conv1 -> t tile (LDS) -> conv2 -> epilogue; 3-4 blocks per CU overlap one block's DMA and
@@ -19,26 +19,10 @@
 #include <type_traits>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-
-template <bool BF>
-__device__ __forceinline__ unsigned rb_pack16(float a, float b) {
-    float2v f = {a, b};
-    if constexpr (BF) return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf2v));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(f, half2v));
-}
 
 #ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/rb16_micro.hip): per-block phase timestamps
 __device__ unsigned long long vits_rb_phase[16 * 65536];  // [block][0..6] 100 MHz stamps, [7] HW_ID, [8] XCC_ID, [9..10] shader clock around conv1
@@ -125,7 +109,7 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
     // ---- phase 0: the input tile, all groups, straight into LDS (slot s <-> global time t0 - P2 - P1 + s) -------------------
     {
         const uint16_t* xb = p.x + (int64_t)b * p.x_bs;
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         const int tx0 = t0 - P2 - P1;
         constexpr int NP = (XWP + 63) / 64;
 #pragma unroll
@@ -156,10 +140,6 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 
-    auto mfma = [&](int4v a, int4v bq, floatx16 c) __attribute__((always_inline)) -> floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, bq), c, 0, 0, 0);
-    };
     floatx16 acc[MR][NR];
 
     // one conv over the LDS tile `base` (group row pitch `pitch` slots, tap step `dstep` slots): acc = sum over (chunk, tap, k-half)
@@ -170,14 +150,12 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
             for (int j = 0; j < NR; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(wp), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         constexpr int TOTAL = NCH * STEPS;
         int wvoff[MR];
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) wvoff[mr] = (int)(((size_t)(rt0 + mr) * TOTAL * 64 + lane) * 16);
-        auto load_a = [&](int mr, int step) __attribute__((always_inline)) -> int4v {
-            return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[mr], step * 1024, 0));
-        };
+        auto load_a = [&](int mr, int step) __attribute__((always_inline)) -> int4v { return load_frag<int4v>(wrsrc, wvoff[mr], step); };
         // weight-fragment ring: RS slots, fetched RD steps ahead. A step is NR 32-cycle MFMAs per row tile (64-128 cycles): two steps of
         // look-ahead do not cover an L2 round trip. Eight slots where they measured faster: C = 128 (-6 %) and C = 32 (-5 %); C = 64
         // (144-149 VGPRs with them) came out 5-10 % slower on k = 3 / 7, and C = 256 is capped at 128 VGPRs (spills)
@@ -226,7 +204,7 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
 #pragma unroll
                     for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
-                        for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = mfma(ring[s % RS][mr], b_cur[nr], acc[mr][nr]);
+                        for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = mfma16<BF>(ring[s % RS][mr], b_cur[nr], acc[mr][nr]);
                 }
         }
     };
@@ -263,8 +241,8 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
                         v[e] = fmaxf(v[e], v[e] * p.slope);
                         if (tm < 0 || tm >= len) v[e] = 0.f;  // the second conv's zero padding
                     }
-                    w[g].x = (int)rb_pack16<BF>(v[0], v[1]);
-                    w[g].y = (int)rb_pack16<BF>(v[2], v[3]);
+                    w[g].x = (int)pack16<BF>(v[0], v[1]);
+                    w[g].y = (int)pack16<BF>(v[2], v[3]);
                 }
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -283,7 +261,7 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
     conv(p.w2, (LdsV)(ts + h * TW + cb + (lane & 31)), TW, 1);
     RB_STAMP(4);
 
-    // ---- phase 4: epilogue (as conv16's group epilogue): + b2, + residual, resblock sum / scale, fp32 stream + 16-bit copy ----
+    // ---- phase 4: epilogue (the shared group epilogue, kernel_common.h): + b2, + residual, resblock sum / scale, fp32 stream + 16-bit copy ----
 #ifdef VAR_NOEPI
     {
         float sacc = 0.f;
@@ -326,7 +304,7 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
                 dst[nr] = float4v{0.f, 0.f, 0.f, 0.f};
                 if constexpr (AVRING) adst[nr] = float4v{0.f, 0.f, 0.f, 0.f};
                 if (!col_ok(nr, t)) continue;
-                const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+                const int64_t go = group_off(ch0, p.g_ts, t);
                 if (rg) dst[nr] = *reinterpret_cast<const float4v*>(rg + go);
                 if constexpr (AVRING) {
                     if (ag) adst[nr] = *reinterpret_cast<const float4v*>(ag + go);
@@ -347,7 +325,7 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
             for (int nr = 0; nr < NR; ++nr) {
                 int t;
                 if (!col_ok(nr, t)) continue;
-                const int64_t go = ((int64_t)(ch0 >> 3) * p.g_ts + t) * 8 + (ch0 & 7);
+                const int64_t go = group_off(ch0, p.g_ts, t);
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -358,21 +336,9 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
                     float4v a4;
                     if constexpr (AVRING) a4 = av[it % RD][nr];
                     else a4 = *reinterpret_cast<const float4v*>(ag + go);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = a4[e] + v[e];
-                        v[e] = p.scale_div ? v[e] / p.scale : v[e] * p.scale;
-                    }
+                    group_add_scale(v, a4, p.scale, p.scale_div);
                 }
-                if (yg) *reinterpret_cast<float4v*>(yg + go) = float4v{v[0], v[1], v[2], v[3]};
-                if (y16) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * p.y16_slope);
-                    int2v w2;
-                    w2.x = (int)rb_pack16<BF>(v[0], v[1]);
-                    w2.y = (int)rb_pack16<BF>(v[2], v[3]);
-                    *reinterpret_cast<int2v*>(y16 + ((int64_t)(ch0 >> 3) * p.y16_ts + t) * 8 + (ch0 & 7)) = w2;
-                }
+                group_store<BF>(v, yg, go, y16, p.y16_ts, p.y16_slope, ch0, t);
             }
         }
     }

@@ -21,12 +21,11 @@
 #include <cstdlib>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
 
-typedef float rb32_floatx16 __attribute__((ext_vector_type(16)));
-typedef float rb32_float4v __attribute__((ext_vector_type(4)));
 
 struct RbPair32Params {
     const float* x;  // raw y (fp32, [b][c][t])
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
     const int shift = tx0 - ts0;
     const float* xb = p.x + (int64_t)b * p.x_bs;
     {
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(xb);
         const int tlast = (len - 1) & ~3;  // last float4 that starts inside the sequence (rows are padded to multiples of 4)
         constexpr int N4 = C * XW4;
         constexpr int NI = (N4 + 63) / 64;  // 1 KB DMA instructions for the tile
@@ -109,12 +108,12 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
     __syncthreads();
     // leaky_relu in place + zero padding outside the sequence (what conv_mfma.hip's producer does per chunk)
     {
-        rb32_float4v* x4 = reinterpret_cast<rb32_float4v*>(xs);
+        float4v* x4 = reinterpret_cast<float4v*>(xs);
         constexpr int N4 = C * XW4;
         for (int g = tid; g < N4; g += 256) {
             const int r = g / XW4, c4 = g - r * XW4;
             const int t = ts0 + 4 * c4;
-            rb32_float4v v = x4[g];
+            float4v v = x4[g];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float u = v[e];
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
     }
     __syncthreads();
 
-    rb32_floatx16 acc[NR];
+    floatx16 acc[NR];
     typedef const __attribute__((address_space(3))) float* LdsF;
 
     // one conv over the LDS tile: lane base `base` (row krow, this wave's first column), row pitch `pitch`, tap step `dstep`.
@@ -136,12 +135,12 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
         for (int j = 0; j < NR; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         const int wvoff = (int)(((size_t)wm * TOTAL * 64 + lane) * 16);
-        auto load_a = [&](int step) __attribute__((always_inline)) -> rb32_float4v {
-            return __builtin_bit_cast(rb32_float4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, step * 1024, 0));
+        auto load_a = [&](int step) __attribute__((always_inline)) -> float4v {
+            return load_frag<float4v>(wrsrc, wvoff, step);
         };
-        rb32_float4v ring[4];
+        float4v ring[4];
         ring[0] = load_a(0);
         ring[1] = load_a(1 < TOTAL ? 1 : 0);
 #pragma unroll
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
                     const int s = (c * KT + j) * 4 + p4;  // compile time after unrolling
                     ring[(s + 2) & 3] = load_a(s + 2 < TOTAL ? s + 2 : TOTAL - 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    const rb32_float4v a4 = ring[s & 3];
+                    const float4v a4 = ring[s & 3];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int pair = p4 * 4 + q;
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
                 v = rv[r] + v;
                 if (ab) {
                     v = ab[(int64_t)row * p.a_cs + t] + v;
-                    v = p.scale_div ? v / p.scale : v * p.scale;
+                    v = scale_or_div(v, p.scale, p.scale_div);
                 }
                 if (p.post_act == 2) v = fmaxf(v, v * p.post_slope);
                 yb[(int64_t)row * p.y_cs + t] = v;

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
@@ -32,14 +33,6 @@ namespace {
 
 constexpr int LAT_NT = 16;      // tokens per block = one MFMA column tile
 constexpr int LAT_GROUPS = 16;  // LayerNorm channel groups (add_layer_norm_kernel / dds_layer_kernel: LN_GROUPS)
-typedef float lat_float4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lat_table_lookup(const uint16_t* tab, float x) {
-    const uint16_t i = __builtin_bit_cast(uint16_t, (_Float16)x);
-    return (float)__builtin_bit_cast(_Float16, tab[i]);
-}
-__device__ __forceinline__ float lat_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float lat_gelu_op(float x, const uint16_t* gelu_tab) { return gelu_tab ? lat_table_lookup(gelu_tab, x) : lat_gelu_erf(x); }
 
 }  // namespace
 
@@ -81,14 +74,14 @@ struct DdsLatParams {
 // one 16 x 16 output tile of a 1x1 conv: rows of fragment stream `frag` (= wl16 + ((mtile * 2 + half) * NQ) * 256 floats, NQ = 2 * nchunks quads of
 // 64 lanes x float4), B operands from the LDS tile bt[channel][pitch] at column `col`; the chain runs over the channels in ascending order
 template <int MAXQ>
-__device__ __forceinline__ void lat_load_quads(lat_float4v (&aq)[MAXQ], const float* frag, int nq, int lane) {
-    const lat_float4v* f4 = reinterpret_cast<const lat_float4v*>(frag) + lane;
+__device__ __forceinline__ void lat_load_quads(float4v (&aq)[MAXQ], const float* frag, int nq, int lane) {
+    const float4v* f4 = reinterpret_cast<const float4v*>(frag) + lane;
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) aq[q] = f4[(q < nq ? q : 0) * 64];
 }
 template <int MAXQ>
-__device__ __forceinline__ lat_float4v lat_chain(const lat_float4v (&aq)[MAXQ], int nq, const float* bt, int pitch, int jg, int col) {
-    lat_float4v acc = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ float4v lat_chain(const float4v (&aq)[MAXQ], int nq, const float* bt, int pitch, int jg, int col) {
+    float4v acc = {0.f, 0.f, 0.f, 0.f};
     const float* b0 = bt + jg * pitch + col;
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) {
@@ -126,10 +119,10 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
     const int tl = tid & 15, rr = tid >> 4, rstep = nthr >> 4;  // element-parallel phases: column tl, channels rr, rr + rstep, ...
     const int jg = lane >> 4, col = lane & 15;
     // ---- everything this block reads from memory, issued at once: the wave's weight fragments first (they are needed last) ----
-    lat_float4v aq[MAXQ];
+    float4v aq[MAXQ];
     const int nq = 2 * p.nchunks;
     lat_load_quads<MAXQ>(aq, p.wl16 + (size_t)wid * nq * 256, nq, lane);
-    lat_float4v hq[HEAD == DDS_HEAD_CONV ? MAXQ : 1];
+    float4v hq[HEAD == DDS_HEAD_CONV ? MAXQ : 1];
     if constexpr (HEAD == DDS_HEAD_CONV) lat_load_quads<MAXQ>(hq, p.h_wl16 + (size_t)wid * (2 * p.h_nchunks) * 256, 2 * p.h_nchunks, lane);
     {
         float pv[2][6], wv[2] = {0.f, 0.f};
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
         // x = W_pre . enc + b (vits.cpp:939; conv_lat16_kernel's chain and epilogue), every column tile of the halo'd tile; zero outside the sequence
         const int nct = hcols >> 4;
         for (int ct = 0; ct < nct; ++ct) {
-            const lat_float4v acc = lat_chain<MAXQ>(hq, 2 * p.h_nchunks, et, hcols, jg, ct * 16 + col);
+            const float4v acc = lat_chain<MAXQ>(hq, 2 * p.h_nchunks, et, hcols, jg, ct * 16 + col);
             const int i = ct * 16 + col, t = t0 - pad + i;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -268,13 +261,13 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
         layer_norm_stats(mean, inv);
         for (int c = rr; c < H; c += rstep) {
             const float hv = ht[c * NT + tl];
-            ht[c * NT + tl] = lat_gelu_op((hv - mean) * inv * g1[c] + b1[c], p.gelu_tab);
+            ht[c * NT + tl] = gelu_op((hv - mean) * inv * g1[c] + b1[c], p.gelu_tab);
         }
     }
     __syncthreads();
     // ---- pointwise conv: wave w owns output rows 16w .. 16w + 15 ----
     {
-        const lat_float4v acc = lat_chain<MAXQ>(aq, nq, ht, NT, jg, col);
+        const float4v acc = lat_chain<MAXQ>(aq, nq, ht, NT, jg, col);
         __syncthreads();  // every wave is done reading ht
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
         }
     }
     // (TAIL_PROJ: the tail conv's fragments travel while LayerNorm 2 runs)
-    lat_float4v tq[TAIL == DDS_TAIL_PROJ ? MAXQ : 1];
+    float4v tq[TAIL == DDS_TAIL_PROJ ? MAXQ : 1];
     const bool tail_wave = TAIL == DDS_TAIL_PROJ && wid < 2 * p.t_mtiles && wid * 16 < p.t_rows;
     if constexpr (TAIL == DDS_TAIL_PROJ) {
         if (tail_wave) lat_load_quads<MAXQ>(tq, p.t_wl16 + (size_t)wid * nq * 256, nq, lane);
@@ -296,7 +289,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
         const int t = t0 + tl;
         for (int c = rr; c < H; c += rstep) {
             float v = (ht[c * NT + tl] - mean) * inv * g2[c] + b2[c];
-            v = lat_gelu_op(v, p.gelu_tab);
+            v = gelu_op(v, p.gelu_tab);
             asm volatile("" : "+v"(v));  // (the three-launch path adds in a separate statement behind a branch: no fma of gelu's last product with this add)
             const float o = xt[c * xw + pad + tl] + v;
             if constexpr (TAIL == DDS_TAIL_NONE) {
@@ -309,7 +302,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
     if constexpr (TAIL == DDS_TAIL_PROJ) {
         __syncthreads();
         if (tail_wave) {
-            const lat_float4v acc = lat_chain<MAXQ>(tq, nq, ht, NT, jg, col);
+            const float4v acc = lat_chain<MAXQ>(tq, nq, ht, NT, jg, col);
             const int t = t0 + col;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

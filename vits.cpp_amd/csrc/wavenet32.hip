@@ -18,12 +18,11 @@
 #include <type_traits>
 
 #include "../../include/vits.h"
+#include "kernel_common.h"
 #include "kernels.h"
 
 namespace vits {
 
-typedef float wn_floatx16 __attribute__((ext_vector_type(16)));
-typedef float wn_float4v __attribute__((ext_vector_type(4)));
 
 struct WaveNet32Params {
     const float* h;  // [b][H][t]
@@ -77,7 +76,7 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
     const int shift = tx0 - ts0;
     const float* hb = p.h + (int64_t)b * p.h_bs;
     {
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hb), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrsrc = stream_rsrc(hb);
         const int tlast = (len - 1) & ~3;
         constexpr int N4 = H * XW4;
         constexpr int NI = (N4 + 63) / 64;
@@ -106,13 +105,13 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     {  // zero padding outside the sequence
-        wn_float4v* x4 = reinterpret_cast<wn_float4v*>(xs);
+        float4v* x4 = reinterpret_cast<float4v*>(xs);
         constexpr int N4 = H * XW4;
         if (ts0 < 0 || ts0 + XWP > len) {
             for (int g = tid; g < N4; g += 64 * NW) {
                 const int r = g / XW4, c4 = g - r * XW4;
                 const int t = ts0 + 4 * c4;
-                wn_float4v v = x4[g];
+                float4v v = x4[g];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (t + e < 0 || t + e >= len) v[e] = 0.f;
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
     __syncthreads();
 
     typedef const __attribute__((address_space(3))) float* LdsF;
-    wn_floatx16 acc[2][NR];
+    floatx16 acc[2][NR];
 
     // one conv over the LDS tile for this wave's TWO row tiles mt0, mt0 + 1 (order per output: chunk, tap, channel pair)
     auto conv = [&](const float* wp, int mt0, auto total_c, auto taps_c, LdsF base, const int pitch) __attribute__((always_inline)) {
@@ -134,14 +133,14 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
             for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][nr][r] = 0.f;
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         int wvoff[2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) wvoff[m] = (int)(((size_t)(mt0 + m) * TOTAL * 64 + lane) * 16);
-        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> wn_float4v {
-            return __builtin_bit_cast(wn_float4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[m], step * 1024, 0));
+        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> float4v {
+            return load_frag<float4v>(wrsrc, wvoff[m], step);
         };
-        wn_float4v ring[4][2];
+        float4v ring[4][2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             ring[0][m] = load_a(m, 0);
@@ -246,9 +245,6 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
 // anyway) into the group layout [c/8][frame][8] — one ds_read_b128 per MFMA operand. Saves two converter launches per layer as well.
 // Bit-identical to to_group16 + conv16 (gate) + to_group16 + conv16 (1x1) (GPU test).
 // ---------------------------------------------------------------------------------------------------------------------------------
-typedef int wn_int4v __attribute__((ext_vector_type(4)));
-typedef _Float16 wn_half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wn_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct WaveNet16Params {
     WaveNet32Params f;  // h / h_out / outputs / biases / lens as in the fp32 kernel (w_in / w_rs unused)
@@ -292,9 +288,9 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
     constexpr int P = (KT - 1) / 2;
     constexpr int XS = BM + KT - 1;  // slots per group row of the h tile
     constexpr int TOTAL1 = NCH * KT * 2, TOTAL2 = NCH * 2;  // A-fragment steps per row tile
-    extern __shared__ __attribute__((aligned(16))) wn_int4v l16[];
-    wn_int4v* xs = l16;  // [G][XS]
-    wn_int4v* ts = l16;  // [G][BM]  (acts take the h tile's place)
+    extern __shared__ __attribute__((aligned(16))) int4v l16[];
+    int4v* xs = l16;  // [G][XS]
+    int4v* ts = l16;  // [G][BM]  (acts take the h tile's place)
     static_assert(BM <= XS, "acts take the h tile's place");
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
         for (int u = 0; u < PER; ++u) {
             const int idx = tid + u * NTH;
             if (idx < NSLOT) {
-                wn_int4v q;
+                int4v q;
                 q.x = (int)((unsigned)wn_round16<BF>(v[u][0]) | ((unsigned)wn_round16<BF>(v[u][1]) << 16));
                 q.y = (int)((unsigned)wn_round16<BF>(v[u][2]) | ((unsigned)wn_round16<BF>(v[u][3]) << 16));
                 q.z = (int)((unsigned)wn_round16<BF>(v[u][4]) | ((unsigned)wn_round16<BF>(v[u][5]) << 16));
@@ -345,12 +341,8 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
     __syncthreads();
     WN_STAMP(1);
 
-    typedef const __attribute__((address_space(3))) wn_int4v* LdsV;
-    wn_floatx16 acc[2][NCW];
-    auto mfma = [&](wn_int4v a, wn_int4v bq, wn_floatx16 c) __attribute__((always_inline)) -> wn_floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wn_bf16x8, a), __builtin_bit_cast(wn_bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wn_half8, a), __builtin_bit_cast(wn_half8, bq), c, 0, 0, 0);
-    };
+    typedef const __attribute__((address_space(3))) int4v* LdsV;
+    floatx16 acc[2][NCW];
     // one conv for this wave's two row tiles mt0, mt0 + 1 and its NCW column tiles: order per output = chunk, tap, k-half (conv16.hip's)
     auto conv = [&](const uint16_t* wp, int mt0, auto total_c, auto taps_c, LdsV base, const int pitch) __attribute__((always_inline)) {
         constexpr int TOTAL = decltype(total_c)::value, TAPS = decltype(taps_c)::value;
@@ -360,15 +352,15 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
             for (int n = 0; n < NCW; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(wp), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         int wvoff[2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) wvoff[m] = (int)(((size_t)(mt0 + m) * TOTAL * 64 + lane) * 16);
-        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> wn_int4v {
-            return __builtin_bit_cast(wn_int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff[m], step * 1024, 0));
+        auto load_a = [&](int m, int step) __attribute__((always_inline)) -> int4v {
+            return load_frag<int4v>(wrsrc, wvoff[m], step);
         };
         constexpr int RS = 8, RD = 6;
-        wn_int4v ring[RS][2];
+        int4v ring[RS][2];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -377,7 +369,7 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
             const int kk = s & 1, cj = s >> 1, j = cj % TAPS, c = cj / TAPS;
             return (c * 4 + 2 * kk) * pitch + j;
         };
-        wn_int4v b_nxt[NCW];
+        int4v b_nxt[NCW];
 #pragma unroll
         for (int n = 0; n < NCW; ++n) b_nxt[n] = base[bslot(0) + 32 * n];
 #pragma unroll
@@ -385,7 +377,7 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
 #pragma unroll
             for (int m = 0; m < 2; ++m) ring[(s + RD) % RS][m] = load_a(m, s + RD < TOTAL ? s + RD : TOTAL - 1);
             __builtin_amdgcn_sched_barrier(0);
-            wn_int4v bq[NCW];
+            int4v bq[NCW];
 #pragma unroll
             for (int n = 0; n < NCW; ++n) {
                 bq[n] = b_nxt[n];
@@ -395,7 +387,7 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int n = 0; n < NCW; ++n) acc[m][n] = mfma(ring[s % RS][m], bq[n], acc[m][n]);
+                for (int n = 0; n < NCW; ++n) acc[m][n] = mfma16<BF>(ring[s % RS][m], bq[n], acc[m][n]);
         }
     };
 
@@ -428,7 +420,7 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
         for (int k = 0; k < 2; ++k) {
             const auto x = __builtin_amdgcn_permlane32_swap(w[2 * k][0], w[2 * k + 1][0], false, false);
             const auto y = __builtin_amdgcn_permlane32_swap(w[2 * k][1], w[2 * k + 1][1], false, false);
-            ts[(gw * 4 + 2 * k + krow) * BM + col] = wn_int4v{(int)x[0], (int)y[0], (int)x[1], (int)y[1]};
+            ts[(gw * 4 + 2 * k + krow) * BM + col] = int4v{(int)x[0], (int)y[0], (int)x[1], (int)y[1]};
         }
     }
     WN_STAMP(7);
@@ -531,9 +523,9 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
     constexpr int NTH = 64 * NG * NCT / NCW;
     static_assert(NCW <= NCT, "a wave owns at most the block's column tiles");
     static_assert(HALO == NL * P, "one k = 5 halo per WaveNet layer");
-    extern __shared__ __attribute__((aligned(16))) wn_int4v l16[];
-    wn_int4v* xs = l16;               // [NGRP][XS]  round(h), slot P + column (two zero slots on either side)
-    wn_int4v* ts = l16 + NGRP * XS;   // [NGRP][BM]  acts | round(x0) (12 groups) | round(out)
+    extern __shared__ __attribute__((aligned(16))) int4v l16[];
+    int4v* xs = l16;               // [NGRP][XS]  round(h), slot P + column (two zero slots on either side)
+    int4v* ts = l16 + NGRP * XS;   // [NGRP][BM]  acts | round(x0) (12 groups) | round(out)
     float* ex = reinterpret_cast<float*>(l16);  // [3][2][16][NCT][64] fp32: the last layer's rs rows on their way to the skip waves (over xs + ts)
     float* lb = reinterpret_cast<float*>(l16 + NGRP * XS + NGRP * BM);  // biases: pre[H] | in[NL][2H] | rs[NL][2H] | post[HF]
     constexpr int LB_IN = H, LB_RS = H + NL * 2 * H, LB_POST = H + 2 * NL * 2 * H, LB_N = LB_POST + HF;
@@ -550,7 +542,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
     bool inside[NCW];
 #pragma unroll
     for (int n = 0; n < NCW; ++n) inside[n] = tb + col0 + 32 * n >= 0 && tb + col0 + 32 * n < len;
-    typedef const __attribute__((address_space(3))) wn_int4v* LdsV;
+    typedef const __attribute__((address_space(3))) int4v* LdsV;
 
     // ---- x0 tile (rounded, zero outside the sequence) -> ts[0:12][BM]; zero halo slots of xs; biases -> LDS ----
     {
@@ -568,7 +560,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
         }
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
-            wn_int4v q;
+            int4v q;
             q.x = (int)((unsigned)wn_round16<BF>(v[u][0]) | ((unsigned)wn_round16<BF>(v[u][1]) << 16));
             q.y = (int)((unsigned)wn_round16<BF>(v[u][2]) | ((unsigned)wn_round16<BF>(v[u][3]) << 16));
             q.z = (int)((unsigned)wn_round16<BF>(v[u][4]) | ((unsigned)wn_round16<BF>(v[u][5]) << 16));
@@ -577,7 +569,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
         }
         if (tid < NGRP * 2 * P) {
             const int gg = tid / (2 * P), j = tid - gg * (2 * P);
-            xs[gg * XS + (j < P ? j : BM + j)] = wn_int4v{0, 0, 0, 0};
+            xs[gg * XS + (j < P ? j : BM + j)] = int4v{0, 0, 0, 0};
         }
         const int64_t spk_off = p.bias_rows ? p.bias_rs * p.bias_rows[b] : 0;  // multi-speaker calls: this utterance's bias row
         for (int i2 = tid; i2 < LB_N; i2 += NTH) {
@@ -593,22 +585,18 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
     }
     __syncthreads();
 
-    wn_floatx16 acc[2][NCW];
-    auto mfma = [&](wn_int4v a, wn_int4v bq, wn_floatx16 c) __attribute__((always_inline)) -> wn_floatx16 {
-        if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wn_bf16x8, a), __builtin_bit_cast(wn_bf16x8, bq), c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wn_half8, a), __builtin_bit_cast(wn_half8, bq), c, 0, 0, 0);
-    };
+    floatx16 acc[2][NCW];
     // one conv for NM row tiles mt0.. of this wave's NCW column tiles: order per output = chunk, tap, k-half (conv16.hip's, wavenet16_kernel's).
     // In two parts: conv_begin issues the loads of the first RD weight fragments, conv_run multiplies. A block is alone on its CU and runs ten
     // convs separated by barriers and tile writes: begun right behind the previous conv, a conv's first fragments travel while the gate, the
     // tile write and the barrier in front of it run — inside conv_run that L2 round trip was exposed ten times per block.
     constexpr int RS = 8, RD = 6;
-    wn_int4v ring[RS][2];
+    int4v ring[RS][2];
     int wvoff[2];
-    auto load_a = [&](const uint16_t* wp, int m, int step) __attribute__((always_inline)) -> wn_int4v {
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(wp), 0, 0x7fffffff, 0x00020000);
+    auto load_a = [&](const uint16_t* wp, int m, int step) __attribute__((always_inline)) -> int4v {
+        const __amdgpu_buffer_rsrc_t wrsrc = stream_rsrc(wp);
         const int vo = wvoff[m];
-        return __builtin_bit_cast(wn_int4v, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, vo, step * 1024, 0));
+        return load_frag<int4v>(wrsrc, vo, step);
     };
     auto conv_begin = [&](const uint16_t* wp, int mt0, auto total_c, auto nm_c) __attribute__((always_inline)) {
         constexpr int TOTAL = decltype(total_c)::value, NM = decltype(nm_c)::value;
@@ -631,7 +619,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
             const int kk = s & 1, cj = s >> 1, j = cj % TAPS, c = cj / TAPS;
             return (c * 4 + 2 * kk) * pitch + j;
         };
-        wn_int4v b_nxt[NCW];
+        int4v b_nxt[NCW];
 #pragma unroll
         for (int n = 0; n < NCW; ++n) b_nxt[n] = base[bslot(0) + 32 * n];
 #pragma unroll
@@ -639,7 +627,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
 #pragma unroll
             for (int m = 0; m < NM; ++m) ring[(s + RD) % RS][m] = load_a(wp, m, s + RD < TOTAL ? s + RD : TOTAL - 1);
             __builtin_amdgcn_sched_barrier(0);
-            wn_int4v bq[NCW];
+            int4v bq[NCW];
 #pragma unroll
             for (int n = 0; n < NCW; ++n) {
                 bq[n] = b_nxt[n];
@@ -649,7 +637,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
 #pragma unroll
             for (int m = 0; m < NM; ++m)
 #pragma unroll
-                for (int n = 0; n < NCW; ++n) acc[m][n] = mfma(ring[s % RS][m], bq[n], acc[m][n]);
+                for (int n = 0; n < NCW; ++n) acc[m][n] = mfma16<BF>(ring[s % RS][m], bq[n], acc[m][n]);
         }
     };
     using C_PRE = std::integral_constant<int, (HF / 32) * 2>;
@@ -660,7 +648,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
     using IK = std::integral_constant<int, KT>;
     // 16 values of one row tile (MFMA C layout: register 4 g + e = channel 8 g + 4 krow + e of the tile) -> rounded, whole 16-byte slots of the
     // tile's four channel groups at this lane's column (v_permlane32_swap trades halves between two groups, see wavenet16_kernel)
-    auto put_tile = [&](wn_int4v* dst, int grp0, int pitch, int slot, const float* v, bool ok) __attribute__((always_inline)) {
+    auto put_tile = [&](int4v* dst, int grp0, int pitch, int slot, const float* v, bool ok) __attribute__((always_inline)) {
         unsigned w[4][2];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -674,7 +662,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
         for (int k = 0; k < 2; ++k) {
             const auto x = __builtin_amdgcn_permlane32_swap(w[2 * k][0], w[2 * k + 1][0], false, false);
             const auto y = __builtin_amdgcn_permlane32_swap(w[2 * k][1], w[2 * k + 1][1], false, false);
-            dst[(grp0 + 2 * k + krow) * pitch + slot] = wn_int4v{(int)x[0], (int)y[0], (int)x[1], (int)y[1]};
+            dst[(grp0 + 2 * k + krow) * pitch + slot] = int4v{(int)x[0], (int)y[0], (int)x[1], (int)y[1]};
         }
     };
     auto rowof = [&](int tile, int r) __attribute__((always_inline)) -> int { return tile * 32 + (r >> 2) * 8 + krow * 4 + (r & 3); };
