@@ -195,7 +195,8 @@ VITS_API int32_t vits_model_num_voices(const vits_model* model);
 VITS_API void vits_reference_noise_seed(uint32_t seed);
 
 /* Streaming sink: `pcm` points at samples [offset, offset+n) of utterance `utt` (host memory owned by the library,
- * valid during the call only). Chunks of one utterance arrive in order and tile it exactly. */
+ * valid during the call only). Chunks of one utterance arrive in order and tile it exactly. With an output rate set (vits_model_set_rates)
+ * offset and n count samples at that rate, and the chunks tile [0, lengths[b]) of the delivered PCM. */
 typedef int (*vits_chunk_callback)(void* user, int32_t utt, size_t offset, const float* pcm, size_t n);
 
 typedef struct vits_process_opts {
@@ -209,7 +210,7 @@ typedef struct vits_process_opts {
     int32_t fixed_duration;      /* >0: every id lasts this many frames (pinned-length benchmark run) */
     int32_t collect_taps;        /* 1: keep stage outputs for vits_model_get_tap */
     void* out_device;            /* optional device buffer [B][out_device_stride] fp32 to receive the PCM */
-    int64_t out_device_stride;   /* samples; must be >= the longest utterance */
+    int64_t out_device_stride;   /* samples; must be >= the longest utterance (as delivered: at the output rate if one is set) */
     int32_t skip_host_copy;      /* 1: leave PCM on the device only (requires out_device or tap access) */
     int32_t async;               /* 1: return without synchronising the stream (requires skip_host_copy and
                                     fixed_duration>0, the only case with no data-dependent host read);
@@ -265,7 +266,7 @@ VITS_API int vits_model_get_prosody(const vits_model* model, float* speaking_rat
 typedef struct vits_batch_result {
     float* data;      /* host [batch][stride] PCM (NULL when skip_host_copy) */
     size_t stride;    /* samples between utterances */
-    int64_t* lengths; /* [batch] samples per utterance */
+    int64_t* lengths; /* [batch] samples per utterance (at the handle's output rate, vits_model_set_rates; default: the model's) */
     int64_t* frames;  /* [batch] spectrogram frames per utterance (L) */
     size_t batch;
 } vits_batch_result;
@@ -282,7 +283,8 @@ VITS_API void vits_free_batch_result(vits_batch_result* r);
 
 /* ---- voice conversion (VITS SynthesizerTrn.voice_conversion) -------------------------------------------------------------
  * Speech of speaker A in, the same speech in speaker B's voice out. Per utterance b, with PCM y_b of pcm_lengths[b] = N_b samples at
- * the model's sampling rate:
+ * the model's sampling rate (a recording at another rate: vits_model_set_rates' input rate resamples it on the device first, and N_b below is
+ * the resampled count):
  *   spec   = |STFT(y_b)| (periodic Hann, n_fft = 2 (spectrogram_bins - 1), hop = product of the upsample rates, reflection pad of
  *            (n_fft - hop) / 2 at the utterance's own ends, center = False, sqrt(re^2 + im^2 + 1e-6)): L_b = floor(N_b / hop) frames
  *   z_q    = posterior_encoder(spec, g_src): mean + eps * exp(log_std), eps the [F][L_b] draw prior sampling makes (same noise kinds)
@@ -343,6 +345,43 @@ VITS_API int64_t vits_model_align(vits_model* model, const float* pcm, size_t n,
 /* Samples per frame (the product of the vocoder's upsample rates = the STFT hop): token t of an alignment starts at
  * sum(durations[0 .. t)) * hop / sampling_rate seconds. */
 VITS_API int32_t vits_model_hop(const vits_model* model);
+
+/* ---- any sample rate: a device resampler on both sides of the model -----------------------------------------------------------
+ * The model speaks one rate (vits_model_sampling_rate). With an OUTPUT rate set, every PCM the handle delivers (vits_model_process,
+ * _process_ids, _process_batch, _submit_batch / _wait, _convert, _convert_batch) is the model-rate waveform resampled on the device:
+ * lengths[], stride, the out_device_stride check, out_device, the host copy and on_chunk's offsets and counts are all in OUTPUT
+ * samples (lengths[b] = ceil(N_b L / M) for a model-rate waveform of N_b samples); frames[] and durations_out are unchanged, and
+ * frames_only reports lengths[] at the output rate. Streaming still tiles: after every vocoder window the output samples whose
+ * filter taps all lie in finished model-rate samples are delivered, so chunks arrive in order and tile [0, lengths[b]) exactly, the
+ * concatenation equals the unchunked result bit for bit, and a window that finalises nothing for an utterance makes no call for it.
+ * With an INPUT rate set, the PCM given to vits_model_convert(_batch) and vits_model_align(_batch) is at that rate: it is uploaded and
+ * resampled to the model's rate on the device, N' = ceil(N L / M) samples, L_b = floor(N' / hop) frames; the length checks apply to N'
+ * (their messages name both counts). Alignment timings stay frames * hop / sampling_rate seconds. 0 = the model's own rate (a rate equal
+ * to the model's is stored as 0): no resampling kernel is queued, nothing is allocated, every bit is what it was.
+ * Taps: "waveform" stays the model-rate waveform; "waveform_out" [1][lengths[b]] is the delivered PCM (output rate set); "pcm_model"
+ * [1][N'] the resampled recording (input rate set).
+ *
+ * The filter (one definition, both directions). fi -> fo, d = gcd(fi, fo), L = fo / d, M = fi / d. Output sample j sits at input time
+ * j M / L: q = j M (64-bit), n_c = q / L, p = q % L. Prototype: a Kaiser-windowed sinc with Z = 32 zero crossings, rolloff = 0.92,
+ * beta = 9: s = rolloff min(1, L / M), W = Z / s, R = ceil(W), K = 2 R + 1,
+ *   g(t) = s sinc(s t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta) for |t| < W, else 0      (sinc(x) = sin(pi x) / (pi x))
+ *   h[p][k] = g(R - k + p / L), computed in double on the host and rounded once to fp32 (no per-phase renormalisation)
+ *   y[j] = sum_k h[p][k] x[n_c - R + k], x = 0 outside the utterance's own [0, N); N_out = ceil(N L / M)
+ * evaluated as ONE ascending chain per output sample: acc = 0; acc = fmaf(h[p][k], x[.], acc) for k = 0 .. K - 1. Nothing about tiles,
+ * batch position or streaming windows enters a sample. Rates in [4000, 192000] Hz; a pair whose table exceeds 2^20 floats (L K, e.g.
+ * 16000 -> 44101) is refused with a message naming L and K. The table of a pair is built and uploaded at its first use, kept with the
+ * handle and counted in vits_model_weight_bytes.
+ *
+ * vits_model_set_rates: 0, or -1 + message with the handle unchanged: a rate outside the range other than 0, a table that is too large,
+ * batches in flight, or a call from inside on_chunk ("model busy"). */
+VITS_API int vits_model_set_rates(vits_model* model, int32_t input_rate, int32_t output_rate);
+VITS_API int vits_model_get_rates(const vits_model* model, int32_t* input_rate, int32_t* output_rate);
+/* The filter itself: host only, no device needed. vits_resample_plan: 0 and L, M, K (each pointer optional), or -1 + message.
+ * vits_resample_taps: writes h as [L][K] when cap >= L K (dst may be NULL with cap 0 to ask for the size); returns L K, -1 on failure.
+ * vits_resample_length: ceil(n L / M), -1 on failure. */
+VITS_API int vits_resample_plan(int32_t in_rate, int32_t out_rate, int32_t* L, int32_t* M, int32_t* K);
+VITS_API int64_t vits_resample_taps(int32_t in_rate, int32_t out_rate, float* dst, size_t cap);
+VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t n);
 
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
@@ -485,6 +524,14 @@ VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, 
  * T[b]); scores: out, host [batch], optional. */
 VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, int32_t F, const float* m, const float* ls, const float* z,
                            int32_t* durations, float* scores);
+
+/* The resampling kernel (see vits_model_set_rates for the filter) on a ragged batch: x host [batch][x_stride] at in_rate, lens host
+ * [batch] (samples of each row, 0 <= lens[b] <= x_stride; NULL: every row has x_stride), y host [batch][y_stride] at out_rate. Row b gets
+ * its ceil(lens[b] L / M) output samples; everything behind them in y is left as it was, and nothing behind lens[b] in x is read. Equal
+ * rates copy. Refused (-1 + message): a pair vits_resample_plan refuses, a length outside its row, a y_stride shorter than the longest
+ * output row. */
+VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens,
+                              float* y, int64_t y_stride);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

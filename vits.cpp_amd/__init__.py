@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_prosody", "vits_model_get_prosody",
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
+    "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -193,6 +194,18 @@ def lib():
     L.vits_model_hop.argtypes = [vp]
     L.vits_op_align.restype = i32
     L.vits_op_align.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.vits_model_set_rates.restype = i32
+    L.vits_model_set_rates.argtypes = [vp, i32, i32]
+    L.vits_model_get_rates.restype = i32
+    L.vits_model_get_rates.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.vits_resample_plan.restype = i32
+    L.vits_resample_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.vits_resample_taps.restype = i64
+    L.vits_resample_taps.argtypes = [i32, i32, f32p, sz]
+    L.vits_resample_length.restype = i64
+    L.vits_resample_length.argtypes = [i32, i32, i64]
+    L.vits_op_resample.restype = i32
+    L.vits_op_resample.argtypes = [i32, i32, i32, vp, i64, vp, vp, i64]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -606,6 +619,23 @@ class Model:
     def noise_scale_duration(self, v):
         self.set_prosody(noise_scale_duration=v)
 
+    # -- any sample rate (vits_model_set_rates): 0 = the model's own rate --------------------------------------------------------------
+    @property
+    def rates(self):
+        """(input_rate, output_rate) of the handle; 0 = the model's own rate (a rate equal to it reads back as 0)"""
+        v = [C.c_int32(), C.c_int32()]
+        if lib().vits_model_get_rates(self._h, C.byref(v[0]), C.byref(v[1])) != 0:
+            raise VitsError(last_error())
+        return int(v[0].value), int(v[1].value)
+
+    def set_rates(self, input_rate=None, output_rate=None):
+        """vits_model_set_rates: input_rate = the rate of the PCM given to convert* / align*, output_rate = the rate of every PCM the handle delivers
+        (lengths, strides and on_chunk offsets are then in output samples). None leaves a rate as it is, 0 = the model's rate."""
+        cur = self.rates
+        new = [int(cur[i] if v is None else v) for i, v in enumerate((input_rate, output_rate))]
+        if lib().vits_model_set_rates(self._h, *new) != 0:
+            raise VitsError(last_error())
+
     @property
     def ggml_tables(self):
         return bool(lib().vits_model_get_ggml_tables(self._h))
@@ -918,6 +948,58 @@ def op_align(m, ls, z, T=None, L=None):
     if lib().vits_op_align(B, _ptr(T), _ptr(L), F, _ptr(m), _ptr(ls), _ptr(z), _ptr(d), _ptr(sc)) != 0:
         raise VitsError(last_error())
     return d, sc
+
+
+def resample_plan(in_rate, out_rate):
+    """vits_resample_plan: (L, M, K) of the polyphase filter in_rate -> out_rate (host only)"""
+    v = [C.c_int32(), C.c_int32(), C.c_int32()]
+    if lib().vits_resample_plan(int(in_rate), int(out_rate), *[C.byref(x) for x in v]) != 0:
+        raise VitsError(last_error())
+    return tuple(int(x.value) for x in v)
+
+
+def resample_taps(in_rate, out_rate):
+    """vits_resample_taps: the filter's fp32 tap table h [L, K] (host only)"""
+    n = lib().vits_resample_taps(int(in_rate), int(out_rate), None, 0)
+    if n < 0:
+        raise VitsError(last_error())
+    L, _, K = resample_plan(in_rate, out_rate)
+    h = np.zeros((L, K), np.float32)
+    if lib().vits_resample_taps(int(in_rate), int(out_rate), _ptr(h), h.size) != n:
+        raise VitsError(last_error())
+    return h
+
+
+def resample_length(in_rate, out_rate, n):
+    """vits_resample_length: ceil(n L / M), the samples at out_rate of n samples at in_rate (host only)"""
+    r = lib().vits_resample_length(int(in_rate), int(out_rate), int(n))
+    if r < 0:
+        raise VitsError(last_error())
+    return int(r)
+
+
+def resample(x, in_rate, out_rate, lens=None, out=None):
+    """The resampling kernel on a ragged batch (vits_op_resample). x: float32 [B, x_stride] (or one 1-D row) at in_rate; lens: samples per row (None =
+    the whole row). Returns (y float32 [B, y_stride], n_out int64 [B]): row b holds its n_out[b] = ceil(lens[b] L / M) samples at out_rate, zeros behind them.
+    out: a caller-owned float32 [B, y_stride] array to write into instead (what lies behind a row's samples stays as it was)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    if int(in_rate) == int(out_rate):
+        n_out = ln.copy()
+    else:
+        n_out = np.array([resample_length(in_rate, out_rate, max(int(v), 0)) for v in ln], np.int64)
+    if out is None:
+        out = np.zeros((B, max(int(n_out.max()), 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    if lib().vits_op_resample(int(in_rate), int(out_rate), B, _ptr(x), stride, _ptr(ln), _ptr(out), out.shape[1]) != 0:
+        raise VitsError(last_error())
+    return out, n_out
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

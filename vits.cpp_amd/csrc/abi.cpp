@@ -499,6 +499,75 @@ VITS_API int32_t vits_model_hop(const vits_model* model) {
     for (int r : model->eng.hp.up_rates) hop *= r;
     return hop;
 }
+// ---- any sample rate (include/vits.h: the filter and what the rates mean) ---------------------------------------------------------------
+VITS_API int vits_model_set_rates(vits_model* model, int32_t input_rate, int32_t output_rate) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_rates(input_rate, output_rate, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_get_rates(const vits_model* model, int32_t* input_rate, int32_t* output_rate) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (input_rate) *input_rate = model->eng.input_rate();
+    if (output_rate) *output_rate = model->eng.output_rate();
+    return 0;
+}
+VITS_API int vits_resample_plan(int32_t in_rate, int32_t out_rate, int32_t* L, int32_t* M, int32_t* K) {
+    VITS_TRY
+    vits::ResamplePlan p;
+    std::string err;
+    if (!vits::resample_plan(in_rate, out_rate, p, err)) {
+        set_err("vits_resample_plan: " + err);
+        return -1;
+    }
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (K) *K = p.K;
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_resample_taps(int32_t in_rate, int32_t out_rate, float* dst, size_t cap) {
+    VITS_TRY
+    vits::ResamplePlan p;
+    std::string err;
+    if (!vits::resample_plan(in_rate, out_rate, p, err)) {
+        set_err("vits_resample_taps: " + err);
+        return -1;
+    }
+    const size_t n = (size_t)p.L * p.K;
+    if (!dst && cap) {
+        set_err("vits_resample_taps: null argument (dst is NULL with cap > 0)");
+        return -1;
+    }
+    if (dst && cap >= n) {
+        const std::vector<float> h = vits::resample_taps(p);
+        std::memcpy(dst, h.data(), sizeof(float) * n);
+    }
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t n) {
+    VITS_TRY
+    vits::ResamplePlan p;
+    std::string err;
+    if (!vits::resample_plan(in_rate, out_rate, p, err)) {
+        set_err("vits_resample_length: " + err);
+        return -1;
+    }
+    if (n < 0 || n > ((int64_t)1 << 40)) {
+        set_err("vits_resample_length: n = " + std::to_string(n) + " is outside [0, 2^40]");
+        return -1;
+    }
+    return p.out_len(n);
+    VITS_CATCH(-1)
+}
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 
@@ -1130,6 +1199,57 @@ VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, in
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipMemcpy(durations, ddur.p, (size_t)batch * tmax * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     if (scores && hipMemcpy(scores, dscore.p, (size_t)batch * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, float* y, int64_t y_stride) {
+    VITS_TRY
+    using namespace vits;
+    if (batch <= 0 || !x || !y || x_stride <= 0 || y_stride <= 0) return fail("vits_op_resample: null argument or empty batch");
+    ResamplePlan p;
+    std::string err;
+    if (!resample_plan(in_rate, out_rate, p, err)) return fail(("vits_op_resample: " + err).c_str());
+    std::vector<int32_t> n(batch);
+    int64_t longest = 0, longest_b = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int64_t len = lens ? lens[b] : x_stride;
+        if (len < 0 || len > x_stride) return fail(("vits_op_resample: lens[" + std::to_string(b) + "] = " + std::to_string(len) + " is outside [0, x_stride = " + std::to_string(x_stride) + "]").c_str());
+        if (len > ((int64_t)1 << 30) || p.out_len(len) > INT32_MAX) return fail(("vits_op_resample: row " + std::to_string(b) + " is too long (" + std::to_string(len) + " samples)").c_str());
+        n[b] = (int32_t)len;
+        if (p.out_len(len) > longest) longest = p.out_len(len), longest_b = b;
+    }
+    if (y_stride < longest)
+        return fail(("vits_op_resample: y_stride = " + std::to_string(y_stride) + " is shorter than the longest output row (row " + std::to_string(longest_b) + ": " +
+                     std::to_string(n[longest_b]) + " samples in, " + std::to_string(longest) + " out)").c_str());
+    if (p.L == 1 && p.M == 1) {  // equal rates copy
+        for (int b = 0; b < batch; ++b) std::memcpy(y + (size_t)b * y_stride, x + (size_t)b * x_stride, sizeof(float) * (size_t)n[b]);
+        return 0;
+    }
+    // taps as the kernel reads them: [K][L]
+    const std::vector<float> h = resample_taps(p);
+    std::vector<float> ht(h.size());
+    for (int ph = 0; ph < p.L; ++ph)
+        for (int k = 0; k < p.K; ++k) ht[(size_t)k * p.L + ph] = h[(size_t)ph * p.K + k];
+    DevBuf dx, dy, dh;
+    DevInts dn;
+    // (y goes up too: what lies behind a row's output samples must come back as it was)
+    if (!dx.put(x, (size_t)batch * x_stride) || !dy.put(y, (size_t)batch * y_stride) || !dh.put(ht.data(), ht.size()) || !dn.put(n.data(), batch))
+        return fail("device allocation failed");
+    ResampleCall c;
+    c.x = dx.p;
+    c.x_stride = x_stride;
+    c.lens = dn.p;
+    c.y = dy.p;
+    c.y_stride = y_stride;
+    c.taps = dh.p;
+    c.plan = p;
+    c.batch = batch;
+    c.max_range = longest;
+    hipError_t e = launch_resample(c, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(y, dy.p, (size_t)batch * y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     return 0;
     VITS_CATCH(-1)
 }

@@ -1,6 +1,8 @@
 // engine.cpp — one call from ids to PCM (see engine.h): input checks, the two arenas, the single host read of the frame counts,
 // vocoder windows / streaming, results. The phases themselves live in engine_stage1.cpp, engine_flow.cpp and engine_vocoder.cpp.
 // Compiled with hipcc as host C++.
+#include <numeric>
+
 #include "engine_internal.h"
 
 namespace vits {
@@ -160,6 +162,49 @@ int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
     }
     speaking_rate = rate, noise_scale = ns, noise_scale_dur = nsd;
     return 0;
+}
+
+int Engine::set_rates(int in_rate, int out_rate, std::string& err) {
+    int stored[2] = {in_rate, out_rate};
+    for (int side = 0; side < 2; ++side) {
+        int& r = stored[side];
+        if (r == 0 || r == hp.sampling_rate) {
+            r = 0;
+            continue;
+        }
+        ResamplePlan p;
+        std::string why;
+        if (!(side == 0 ? resample_plan(r, hp.sampling_rate, p, why) : resample_plan(hp.sampling_rate, r, p, why))) {
+            err = std::string("vits_model_set_rates: ") + (side == 0 ? "input_rate: " : "output_rate: ") + why + " (the model's rate is " + std::to_string(hp.sampling_rate) + " Hz; 0 = that rate)";
+            return -1;
+        }
+    }
+    input_rate_ = stored[0], output_rate_ = stored[1];
+    return 0;
+}
+
+const RateTable* Engine::rate_table(int fi, int fo, std::string& err) {
+    const auto it = rate_tabs_.find({fi, fo});
+    if (it != rate_tabs_.end()) return &it->second;
+    RateTable t;
+    if (!resample_plan(fi, fo, t.plan, err)) return nullptr;
+    // the kernel reads [K][L]: at one tap the threads of a wave differ in their phase only (resample.hip)
+    const std::vector<float> h = resample_taps(t.plan);
+    std::vector<float> ht(h.size());
+    for (int p = 0; p < t.plan.L; ++p)
+        for (int k = 0; k < t.plan.K; ++k) ht[(size_t)k * t.plan.L + p] = h[(size_t)p * t.plan.K + k];
+    if (!(t.taps = upload(ht))) {  // (owned by the handle and counted in weight_bytes from here on)
+        err = "resampling table: device allocation failed";
+        return nullptr;
+    }
+    return &rate_tabs_.emplace(std::make_pair(fi, fo), t).first->second;
+}
+
+hipError_t Engine::resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples) {
+    prof.begin(name, 2.0 * rc.plan.K * (double)out_samples, 4.0 * ((double)in_samples + (double)out_samples), stream, /*chain=*/true);
+    const hipError_t e = launch_resample(rc, stream);
+    prof.end(stream);
+    return e;
 }
 
 int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const {
@@ -488,12 +533,15 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         // dispatcher query: predicted frames / samples per utterance, no audio (buffer sizing, shard balancing by frames)
         if (out) {
             out->batch = (size_t)B;
-            out->stride = (size_t)c.smax[n_up];
+            // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
+            ResamplePlan plan;
+            if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
+            out->stride = (size_t)plan.out_len(c.smax[n_up]);
             out->lengths = new int64_t[B];
             out->frames = new int64_t[B];
             out->data = nullptr;
             for (int b = 0; b < B; ++b) {
-                out->lengths[b] = c.slen[n_up][b];
+                out->lengths[b] = plan.out_len(c.slen[n_up][b]);
                 out->frames[b] = frames[b];
             }
         }
@@ -531,6 +579,23 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     // caller cannot know in advance, or collect_taps — streams as ONE window: the sink gets each utterance in a single call)
     for (const Call::Win& w : wins) c.Lw_max = std::max(c.Lw_max, w.hi - w.lo);
     const int M = c.M = c.smul[n_up];  // samples per frame
+    if (output_rate_) {
+        // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and
+        // resample.hip writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities
+        if (!(c.rate_out = rate_table(hp.sampling_rate, output_rate_, err))) return -1;
+        c.out_len.resize(B);
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = c.rate_out->plan.out_len(c.slen[n_up][b]);
+            if (n > (int64_t)INT32_MAX - 64) {
+                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples at the output rate: too long";
+                return -1;
+            }
+            c.out_len[b] = (int)n;
+            c.out_max = std::max(c.out_max, (int)n);
+        }
+        c.out_ws = round_up(std::max(c.out_max, 1), 32);
+    }
+    const bool rs = c.rate_out != nullptr;
 
     if (layout_stage_two(c)) return -1;
     if (c.vc) {
@@ -548,16 +613,35 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     const std::vector<int>& sadd = c.sadd;
     c.wave_dst = c.s2.wave;
     c.wave_stride = c.S_stride;
+    // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
+    const std::vector<int>& pcm_len = rs ? c.out_len : c.slen[n_up];
+    const int pcm_max = rs ? c.out_max : smax[n_up];
     if (o.out_device) {
-        if (o.out_device_stride < smax[n_up]) {
+        if (o.out_device_stride < pcm_max) {
             err = "out_device_stride is smaller than the longest utterance";
+            if (rs) err += " (" + std::to_string(pcm_max) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
             return -1;
         }
-        c.wave_dst = (float*)o.out_device;
-        c.wave_stride = o.out_device_stride;
+        if (!rs) {
+            c.wave_dst = (float*)o.out_device;
+            c.wave_stride = o.out_device_stride;
+        }
     }
     float* const wave_dst = c.wave_dst;
     const int64_t wave_stride = c.wave_stride;
+    float* const pcm_dst = !rs ? wave_dst : o.out_device ? (float*)o.out_device : c.s2.wave_out;
+    const int64_t pcm_stride = !rs ? wave_stride : o.out_device ? o.out_device_stride : (int64_t)c.out_ws;
+    ResampleCall rsc;
+    if (rs) {
+        rsc.x = c.s2.wave;
+        rsc.x_stride = c.S_stride;
+        rsc.lens = c.s1.stage_lens + (size_t)n_up * B;  // (device: every utterance's samples at the model's rate)
+        rsc.y = pcm_dst;
+        rsc.y_stride = pcm_stride;
+        rsc.taps = c.rate_out->taps;
+        rsc.plan = c.rate_out->plan;
+        rsc.batch = B;
+    }
     std::vector<hipEvent_t> chunk_ev;
     struct EvGuard {
         std::vector<hipEvent_t>& v;
@@ -566,7 +650,30 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         }
     } chunk_ev_guard{chunk_ev};
     float* host_pcm = nullptr;  // pinned [B][smax] staging of the streamed PCM
-    const size_t out_stride = (size_t)smax[n_up];
+    const size_t out_stride = (size_t)pcm_max;
+    // streaming at another rate: after window w the model-rate samples [0, E_w) of an utterance are final (E_w: what deliver computes below), and with them
+    // the output samples whose taps all lie in there (ResamplePlan::final_prefix; everything once the utterance has ended: the zeros behind its end are
+    // final). Window w resamples and delivers [o_(w-1), o_w): rg [window][2][B], on the device as s2.out_ranges.
+    std::vector<int> rg;
+    if (rs && o.on_chunk) {
+        rg.assign(wins.size() * (size_t)2 * B, 0);
+        std::vector<int> prev(B, 0);
+        for (size_t w = 0; w < wins.size(); ++w)
+            for (int b = 0; b < B; ++b) {
+                const Call::Win& wn = wins[w];
+                int done = prev[b];
+                if (frames[b] > wn.f0) {
+                    const int64_t n = c.slen[n_up][b], e = frames[b] <= wn.f1 ? n : (int64_t)wn.f1 * M;
+                    done = std::max(done, (int)c.rate_out->plan.final_prefix(e, n));
+                }
+                rg[(w * 2) * B + b] = prev[b];
+                rg[(w * 2 + 1) * B + b] = done;
+                prev[b] = done;
+            }
+        HIP_OK(hipMemcpyAsync(c.s2.out_ranges, rg.data(), sizeof(int) * rg.size(), hipMemcpyHostToDevice, stream));
+        prof.fence();
+        HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
+    }
     if (windowed) {
         // per window and utterance: frames inside the window -> stage lengths (0 everywhere when the utterance has none),
         // and the end of the sample range this window emits for it (window-local index)
@@ -604,6 +711,12 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         const Call::Win& wn = wins[w];
         if (hipEventSynchronize(chunk_ev[w]) != hipSuccess) return -1;
         for (int b = 0; b < B; ++b) {
+            if (rs) {
+                // (a window that finalises nothing for an utterance makes no call for it)
+                const size_t j0 = (size_t)rg[(w * 2) * B + b], j1 = (size_t)rg[(w * 2 + 1) * B + b];
+                if (j1 > j0 && o.on_chunk(o.on_chunk_user, b, j0, host_pcm + (size_t)b * out_stride + j0, j1 - j0)) return 1;
+                continue;
+            }
             if (frames[b] <= wn.f0) continue;
             const size_t off = (size_t)wn.f0 * M;
             const size_t end = frames[b] <= wn.f1 ? (size_t)c.slen[n_up][b] : (size_t)wn.f1 * M;
@@ -645,8 +758,28 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             // the device works on this one
             // (+ the no-crop tail of utterances that end inside this window, Q1; the same columns of longer utterances are not
             // final yet and travel again with the next window)
-            const size_t g0 = (size_t)wn.f0 * M, g1 = std::min(out_stride, (size_t)wn.f1 * M + (size_t)sadd[n_up]);
-            HIP_OK(hipMemcpy2DAsync(host_pcm + g0, out_stride * 4, wave_dst + g0, (size_t)wave_stride * 4, (g1 - g0) * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+            size_t g0 = (size_t)wn.f0 * M, g1 = std::min(out_stride, (size_t)wn.f1 * M + (size_t)sadd[n_up]);
+            if (rs) {
+                // the output samples this window made final, one launch for every utterance, then the columns they span
+                g0 = out_stride, g1 = 0;
+                int64_t in_s = 0, out_s = 0;
+                for (int b = 0; b < B; ++b) {
+                    const int j0 = rg[(wi * 2) * B + b], j1 = rg[(wi * 2 + 1) * B + b];
+                    if (j1 <= j0) continue;
+                    g0 = std::min(g0, (size_t)j0), g1 = std::max(g1, (size_t)j1);
+                    rsc.max_range = std::max(rsc.max_range, (int64_t)(j1 - j0));
+                    out_s += j1 - j0;
+                    in_s += (int64_t)(j1 - j0) * rsc.plan.M / rsc.plan.L;
+                }
+                if (g1 > g0) {
+                    rsc.j0 = c.s2.out_ranges + (wi * 2) * B;
+                    rsc.j1 = rsc.j0 + B;
+                    HIP_OK(resample("resample_out", rsc, in_s, out_s));
+                }
+                rsc.max_range = 0;
+            }
+            if (g1 > g0)
+                HIP_OK(hipMemcpy2DAsync(host_pcm + g0, out_stride * 4, pcm_dst + g0, (size_t)pcm_stride * 4, (g1 - g0) * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
             prof.fence();
             hipEvent_t ev;
             HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -664,6 +797,18 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             snapshot("waveform", w.wv, 1, w.smax[n_up], B, c.slen[n_up]);
         }
     }
+    if (rs && !o.on_chunk) {
+        // nobody waits for parts of it: one launch over every utterance, behind the last window
+        rsc.max_range = c.out_max;
+        HIP_OK(resample("resample_out", rsc, c.sum_frames * M + (int64_t)B * sadd[n_up], std::accumulate(c.out_len.begin(), c.out_len.end(), (int64_t)0)));
+    }
+    if (rs && o.collect_taps) {
+        TensorRef t;
+        t.p = pcm_dst;
+        t.bs = pcm_stride;
+        t.cs = (int)pcm_stride;
+        snapshot("waveform_out", t, 1, c.out_max, B, c.out_len);
+    }
     if (o.on_chunk)
         if (int rc = deliver(wins.size() - 1)) {
             hipStreamSynchronize(stream);
@@ -677,18 +822,18 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         // a pipelined batch: everything the host will hand out is known now; the PCM (if a host copy was asked for) goes to the
         // slot's pinned staging behind the kernels, and `done` marks the end of the batch on the device
         pend->B = B;
-        pend->stride = (size_t)smax[n_up];
+        pend->stride = (size_t)pcm_max;
         pend->lengths.resize(B);
         pend->frames.resize(B);
         for (int b = 0; b < B; ++b) {
-            pend->lengths[b] = c.slen[n_up][b];
+            pend->lengths[b] = pcm_len[b];
             pend->frames[b] = frames[b];
         }
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
             HIP_OK(pend->host.ensure(need, need + need / 8));
-            HIP_OK(hipMemcpy2DAsync(pend->host.p, pend->stride * 4, wave_dst, (size_t)wave_stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpy2DAsync(pend->host.p, pend->stride * 4, pcm_dst, (size_t)pcm_stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
         }
         HIP_OK(hipEventRecord(pend->done, stream));
         prof.fence();
@@ -696,11 +841,11 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     }
     if (out) {
         out->batch = (size_t)B;
-        out->stride = (size_t)smax[n_up];
+        out->stride = (size_t)pcm_max;
         out->lengths = new int64_t[B];
         out->frames = new int64_t[B];
         for (int b = 0; b < B; ++b) {
-            out->lengths[b] = c.slen[n_up][b];
+            out->lengths[b] = pcm_len[b];
             out->frames[b] = frames[b];
         }
         out->data = nullptr;
@@ -708,7 +853,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             out->data = new float[(size_t)B * out->stride];
             if (o.on_chunk) std::memcpy(out->data, host_pcm, sizeof(float) * (size_t)B * out->stride);  // already streamed to the host
             else
-                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, wave_dst, (size_t)wave_stride * 4, out->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, pcm_dst, (size_t)pcm_stride * 4, out->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
             prof.fence();
         }
     }

@@ -205,6 +205,12 @@ class RefNoiseAhead {
     bool active_ = false;
 };
 
+// sample-rate conversion (resample.hip): the filter of one (input rate, output rate) pair on the device, built at the pair's first use
+struct RateTable {
+    ResamplePlan plan;
+    const float* taps = nullptr;  // device [K][L]
+};
+
 struct Call;    // engine_internal.h: the state of one process_batch call
 struct WinCtx;  // engine_internal.h: one vocoder window
 
@@ -270,6 +276,12 @@ class Engine {
     // 0, or -1 + a message naming the utterance (and the token): the call's prosody arrays in range, neither speaking_rates nor
     // duration_override together with fixed_duration
     int check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const;
+    // any sample rate (include/vits.h vits_model_set_rates): 0 = the model's own rate (a rate equal to it is stored as 0). input: the PCM given to
+    // conversion and alignment; output: every PCM the handle delivers. 0, or -1 + a message with the handle unchanged (a rate outside the range, a
+    // table that is too large). Nothing touches the device here: a pair's table is uploaded by the first call that uses it (rate_table).
+    int set_rates(int in_rate, int out_rate, std::string& err);
+    int input_rate() const { return input_rate_; }
+    int output_rate() const { return output_rate_; }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -438,6 +450,11 @@ class Engine {
     int hstage_next_ = 0;
     std::map<std::string, Tap> taps_;
     int tap_batch_ = 0;
+    int input_rate_ = 0, output_rate_ = 0;
+    std::map<std::pair<int, int>, RateTable> rate_tabs_;  // keyed by (fi, fo); device tables are owned_ and counted in weight_bytes
+    const RateTable* rate_table(int fi, int fo, std::string& err);  // null + message: the pair is refused, or the upload failed
+    // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
+    hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 
     float* upload(const std::vector<float>& v);
     struct ConvShape {
@@ -516,8 +533,9 @@ class Engine {
     void set_stage_affine(Call& c) const;  // c.smul / c.sadd: vocoder stage lengths as affine functions of the frame count
     int run_conversion_front(Call& c);        // spectrogram -> posterior encoder -> forward flow (engine_convert.cpp)
     // the PCM side of a conversion or alignment call (engine_convert.cpp): lengths checked, then frame counts, arena (current stage-one slot), uploads
-    int check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::string& err) const;
-    int layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax);
+    int check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::vector<int64_t>& n_model, std::string& err) const;
+    int layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax,
+                          const std::vector<int64_t>& n_model);
     int run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async);
     // a tap of a tensor held with its channels reversed (the flow's physical layout for an odd number of coupling layers)
     void snapshot_flipped(const char* name, TensorRef t, int channels, int stride, int batch, const std::vector<int>& lens);

@@ -78,12 +78,13 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
     }
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
-    if (check_conversion_pcm(pcm_lens, B, pcm_stride, nmax, err)) return -1;
+    std::vector<int64_t> n_model;  // samples at the model's rate (an input rate resamples the recording: vits_model_set_rates)
+    if (check_conversion_pcm(pcm_lens, B, pcm_stride, nmax, n_model, err)) return -1;
     for (int b = 0; b < B; ++b) {
-        const int64_t L = pcm_lens[b] / hop_;
+        const int64_t L = n_model[b] / hop_;
         if (c.tlen[b] > L) {  // (L >= 1: at least one hop of samples was checked above)
             err = "utterance " + std::to_string(b) + " has " + std::to_string(c.tlen[b]) + " tokens but only " + std::to_string(L) + " frames (" +
-                  std::to_string(pcm_lens[b]) + " samples / hop " + std::to_string(hop_) + "): every token needs at least one frame, no monotonic path exists";
+                  std::to_string(n_model[b]) + " samples / hop " + std::to_string(hop_) + "): every token needs at least one frame, no monotonic path exists";
             return -1;
         }
     }
@@ -105,7 +106,7 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
 
     // ---- the audio side: the conversion front end; its own arena goes to stage-one slot 1 (no batch is in flight: the slot is free) -------------------
     ScopedSet<int> slot(a1_slot_, 1);
-    if (layout_conversion(c, pcm, pcm_lens, pcm_stride, speakers, nullptr, nmax)) return -1;
+    if (layout_conversion(c, pcm, pcm_lens, pcm_stride, speakers, nullptr, nmax, n_model)) return -1;
     const int Lmax = c.Lmax, ls = c.ls = round_up(Lmax, 32);
     const int* d_frames = c.s1.frames;
     c.d_len_full[0] = c.s1.stage_lens;

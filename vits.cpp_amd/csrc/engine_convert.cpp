@@ -112,22 +112,32 @@ int Engine::prepare_conversion(std::string& err) {
 }
 
 // the PCM side of a call (conversion and alignment): every utterance inside its row, at least one hop and more than the reflection pad; nmax = the longest
-int Engine::check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::string& err) const {
+// as given, n_model = every utterance's samples at the model's rate (the given count, or with an input rate set ceil(N L / M): what the length rule applies to)
+int Engine::check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::vector<int64_t>& n_model, std::string& err) const {
     const int hop = hop_, pad = stft_pad_, min_n = std::max(hop, pad + 1);
+    ResamplePlan plan;
+    if (input_rate_ && !resample_plan(input_rate_, hp.sampling_rate, plan, err)) return -1;
     nmax = 0;
+    n_model.resize(B);
     for (int b = 0; b < B; ++b) {
         const int64_t n = pcm_lens[b];
         if (n > pcm_stride) {
             err = "pcm_lengths[" + std::to_string(b) + "] = " + std::to_string(n) + " exceeds pcm_stride " + std::to_string(pcm_stride);
             return -1;
         }
-        if (n < min_n) {
-            err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples: at least " + std::to_string(min_n) +
-                  " are needed (one hop, and more than the reflection pad of " + std::to_string(pad) + ")";
-            return -1;
-        }
         if (n > ((int64_t)1 << 30)) {
             err = "utterance " + std::to_string(b) + " is longer than 2^30 samples";
+            return -1;
+        }
+        const int64_t nm = n_model[b] = n < 0 ? n : plan.out_len(n);
+        if (nm < min_n) {
+            err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples" +
+                  (input_rate_ ? " at " + std::to_string(input_rate_) + " Hz = " + std::to_string(nm) + " at the model's " + std::to_string(hp.sampling_rate) + " Hz" : std::string()) +
+                  ": at least " + std::to_string(min_n) + " are needed (one hop, and more than the reflection pad of " + std::to_string(pad) + ")";
+            return -1;
+        }
+        if (nm > ((int64_t)1 << 30)) {
+            err = "utterance " + std::to_string(b) + " is longer than 2^30 samples at the model's rate (" + std::to_string(n) + " given, " + std::to_string(nm) + " resampled)";
             return -1;
         }
         nmax = std::max(nmax, n);
@@ -137,23 +147,30 @@ int Engine::check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_str
 
 // frame counts, vocoder stage lengths and the call's own arena (the current stage-one slot): header ints | PCM | spectrogram | posterior statistics;
 // uploads the header and the PCM. Leaves c.s1.lens / frames / stage_lens / seed_off pointing into that header.
-int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax) {
+int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, int64_t nmax,
+                              const std::vector<int64_t>& n_model) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
     Call::Vc& vc = *c.vc;
     const int B = c.B, hop = hop_, n_up = c.n_up;
     // frame counts and vocoder stage lengths, all on the host (spectrogram_torch: floor(N / hop) frames)
     c.frames.resize(B);
-    for (int b = 0; b < B; ++b) c.frames[b] = (int)(pcm_lens[b] / hop);
+    for (int b = 0; b < B; ++b) c.frames[b] = (int)(n_model[b] / hop);
+    // an input rate (vits_model_set_rates): the caller's PCM goes to scratch of this arena and resample.hip writes vc.pcm at the model's rate
+    const RateTable* rate_in = nullptr;
+    if (input_rate_ && !(rate_in = rate_table(input_rate_, hp.sampling_rate, err))) return -1;
+    const int64_t nmax_model = *std::max_element(n_model.begin(), n_model.end());
     set_stage_affine(c);
     c.frames_known();
     if (!lat16_ready_ && knobs.lat16_lazy_tokens > 0 && (int64_t)B * c.Lmax <= knobs.lat16_lazy_tokens && ensure_lat16(err)) return -1;
     // ---- the call's own arena (the current stage-one slot): header ints | PCM | spectrogram | posterior statistics ----------------------
     const int ls = round_up(c.Lmax, 32), bins = hp.spec_bins, F = hp.flow_size;
-    const int64_t pstride = round_up((int)nmax, 64);
-    const size_t hdr_ints = (size_t)(n_up + 1) * B + 4 * (size_t)B;
+    const int64_t pstride = round_up((int)nmax_model, 64), raw_stride = round_up((int)nmax, 64);
+    const size_t hdr_ints = (size_t)(n_up + 1) * B + (rate_in ? 5 : 4) * (size_t)B;
+    float* raw = nullptr;
     auto layout = [&](Arena& a) {
-        c.s1.stage_lens = a.alloc<int>(hdr_ints);  // stage_lens [n_up + 1][B] | n_samples | seed_off | src rows | tgt rows
+        c.s1.stage_lens = a.alloc<int>(hdr_ints);  // stage_lens [n_up + 1][B] | n_samples | seed_off | src rows | tgt rows [| samples as given]
+        raw = rate_in ? a.alloc<float>((size_t)B * raw_stride) : nullptr;
         vc.nsamp = c.s1.stage_lens + (size_t)(n_up + 1) * B;
         c.s1.seed_off = vc.nsamp + B;
         vc.pcm = a.alloc<float>((size_t)B * pstride);
@@ -169,7 +186,8 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
             for (int b = 0; b < B; ++b) hdr[(size_t)i * B + b] = c.slen[i][b];
         for (int b = 0; b < B; ++b) {
             int* h = hdr.data() + (size_t)(n_up + 1) * B;
-            h[b] = (int)pcm_lens[b];
+            h[b] = (int)n_model[b];
+            if (rate_in) h[4 * B + b] = (int)pcm_lens[b];
             h[B + b] = o.noise_seed_offsets ? o.noise_seed_offsets[b] : b;
             const int s = src ? src[b] : -1, t = tgt ? tgt[b] : -1;
             h[2 * B + b] = s + 1;
@@ -179,9 +197,32 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
         }
         // (pageable sources: both copies are complete when hipMemcpy* returns to the host, so the caller's PCM and hdr may go)
         HIP_OK(hipMemcpyAsync(c.s1.stage_lens, hdr.data(), sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
-        HIP_OK(hipMemcpy2DAsync(vc.pcm, (size_t)pstride * 4, pcm, (size_t)pcm_stride * 4, (size_t)nmax * 4, (size_t)B, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpy2DAsync(rate_in ? raw : vc.pcm, (size_t)(rate_in ? raw_stride : pstride) * 4, pcm, (size_t)pcm_stride * 4, (size_t)nmax * 4, (size_t)B,
+                                hipMemcpyHostToDevice, stream));
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
+        if (rate_in) {
+            ResampleCall rc;
+            rc.x = raw;
+            rc.x_stride = raw_stride;
+            rc.lens = vc.nsamp + 4 * B;
+            rc.y = vc.pcm;
+            rc.y_stride = pstride;
+            rc.taps = rate_in->taps;
+            rc.plan = rate_in->plan;
+            rc.batch = B;
+            rc.max_range = nmax_model;
+            int64_t in_s = 0, out_s = 0;
+            for (int b = 0; b < B; ++b) in_s += pcm_lens[b], out_s += n_model[b];
+            HIP_OK(resample("resample_in", rc, in_s, out_s));
+            if (o.collect_taps) {
+                TensorRef t;
+                t.p = vc.pcm;
+                t.bs = pstride;
+                t.cs = (int)pstride;
+                snapshot("pcm_model", t, 1, (int)nmax_model, B, std::vector<int>(n_model.begin(), n_model.end()));
+            }
+        }
         vc.spk_src = any_src ? vc.nsamp + 2 * B : nullptr;
         vc.spk_tgt = any_tgt ? vc.nsamp + 3 * B : nullptr;
     }
@@ -225,7 +266,8 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
         }
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
-    if (check_conversion_pcm(pcm_lens, B, pcm_stride, nmax, err)) return -1;
+    std::vector<int64_t> n_model;
+    if (check_conversion_pcm(pcm_lens, B, pcm_stride, nmax, n_model, err)) return -1;
     a1_slot_ = 0;
     Call c(o, err, nullptr, B, 0);
     Call::Vc vc;
@@ -236,7 +278,7 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
     clear_taps();
     tap_batch_ = B;
     arith_now_ = arith_kernels();
-    if (layout_conversion(c, pcm, pcm_lens, pcm_stride, src, tgt, nmax)) return -1;
+    if (layout_conversion(c, pcm, pcm_lens, pcm_stride, src, tgt, nmax, n_model)) return -1;
     return run_stage_two(c, out, nullptr, false);
 }
 

@@ -205,6 +205,8 @@ struct Call {
         uint16_t* x16[3];
         uint16_t *sp_u, *sp_t[3], *sp_y[3];  // VITS_ARITH_F32_SPLIT: split planes of the stage input, and per concurrent resblock of t and of the stream
         int* win_lens;  // [window][n_up + 2][B]: stage lengths of each utterance inside the window, then its emit end
+        float* wave_out;    // output rate set, no out_device: the delivered PCM [B][out_ws]
+        int* out_ranges;    // output rate set, streaming: [window][2][B]: the output samples [j0, j1) of each utterance that window w finalises
     } s2{};
     int ls = 0, lws = 0, S_stride = 0;
     size_t big = 0;        // floats of the largest vocoder activation (of one window)
@@ -213,6 +215,10 @@ struct Call {
     const int* d_len_full[8] = {};
     float* wave_dst = nullptr;
     int64_t wave_stride = 0;
+    // output rate set (Engine::output_rate): the filter, every utterance's delivered length ceil(N L / M), the longest, and the row stride of s2.wave_out
+    const RateTable* rate_out = nullptr;
+    std::vector<int> out_len;
+    int out_max = 0, out_ws = 0;
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
 };

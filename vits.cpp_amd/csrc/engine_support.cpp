@@ -369,5 +369,65 @@ Arena::~Arena() {
     if (base) hipFree(base);
 }
 
+// ---- sample-rate conversion: the filter (kernels.h ResamplePlan), host side, double precision ----------------------------------------
+namespace {
+constexpr double kRsZeros = 32.0, kRsRolloff = 0.92, kRsBeta = 9.0;
+// modified Bessel function of the first kind, order 0, by its power series sum_m ((x / 2)^2)^m / (m!)^2 (every term positive: no cancellation)
+double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int m = 1; m < 1000; ++m) {
+        term *= q / ((double)m * (double)m);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+}  // namespace
+
+bool resample_plan(int in_rate, int out_rate, ResamplePlan& p, std::string& err) {
+    for (int r : {in_rate, out_rate})
+        if (r < kResampleMinRate || r > kResampleMaxRate) {
+            err = "sample rate " + std::to_string(r) + " is outside [" + std::to_string(kResampleMinRate) + ", " + std::to_string(kResampleMaxRate) + "] Hz";
+            return false;
+        }
+    int a = in_rate, b = out_rate;
+    while (b) {
+        const int t = a % b;
+        a = b;
+        b = t;
+    }
+    ResamplePlan q;
+    q.L = out_rate / a;
+    q.M = in_rate / a;
+    q.s = kRsRolloff * std::min(1.0, (double)q.L / (double)q.M);
+    q.W = kRsZeros / q.s;
+    q.R = (int)std::ceil(q.W);
+    q.K = 2 * q.R + 1;
+    if ((int64_t)q.L * q.K > kResampleMaxTaps) {
+        err = "resampling " + std::to_string(in_rate) + " -> " + std::to_string(out_rate) + " Hz needs a tap table of L = " + std::to_string(q.L) + " phases x K = " +
+              std::to_string(q.K) + " taps, more than " + std::to_string(kResampleMaxTaps) + " floats (the rates share too small a common divisor)";
+        return false;
+    }
+    p = q;
+    return true;
+}
+
+std::vector<float> resample_taps(const ResamplePlan& p) {
+    const double pi = 3.14159265358979323846, i0b = bessel_i0(kRsBeta);
+    std::vector<float> h((size_t)p.L * p.K);
+    for (int ph = 0; ph < p.L; ++ph)
+        for (int k = 0; k < p.K; ++k) {
+            const double t = (double)(p.R - k) + (double)ph / (double)p.L;
+            double g = 0.0;
+            if (std::fabs(t) < p.W) {
+                const double u = t / p.W, a = pi * (p.s * t);  // (sinc(s t): the argument rounded before the multiplication by pi, as the tests' restatement has it)
+                g = p.s * (a == 0.0 ? 1.0 : std::sin(a) / a) * bessel_i0(kRsBeta * std::sqrt(1.0 - u * u)) / i0b;
+            }
+            h[(size_t)ph * p.K + k] = (float)g;
+        }
+    return h;
+}
+
 
 }  // namespace vits

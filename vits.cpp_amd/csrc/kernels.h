@@ -9,9 +9,11 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace vits {
@@ -573,5 +575,41 @@ hipError_t launch_align_mas(const AlignCall& c, hipStream_t s);
 hipError_t launch_pcm16(const float* src, int64_t src_stride, int16_t* dst, int64_t dst_stride, const int64_t* lens, int rows, int64_t cols, hipStream_t s);
 hipError_t launch_conv_post(TensorRef x, const float* w, int cin, int k, float slope, TensorRef pre_tanh, TensorRef wave, const int* lens, int batch,
                             int tmax, hipStream_t s, int emit_lo = 0, const int* emit_hi = nullptr, int arith = 0);
+
+// ---- sample-rate conversion (resample.hip; the filter: include/vits.h vits_resample_plan, DESIGN.md §8 "Any sample rate") ----------------
+// fi -> fo as a rational L / M polyphase filter: output j of a row sits at input time j M / L; q = j M (int64), n_c = q / L, p = q % L,
+// y[j] = sum_k h[p][k] x[n_c - R + k], x = 0 outside the row's own [0, len). h is a Kaiser-windowed sinc (32 zero crossings, roll-off 0.92, beta 9)
+// built in double on the host and rounded once to fp32. The bits of y[j] are ONE ascending chain, acc = 0; acc = fmaf(h[p][k], x, acc) for k = 0 .. K - 1:
+// nothing about tiles, batch position or the range asked for enters a sample.
+constexpr int kResampleMinRate = 4000, kResampleMaxRate = 192000;
+constexpr int64_t kResampleMaxTaps = (int64_t)1 << 20;  // floats of the largest table accepted (L K)
+struct ResamplePlan {
+    int L = 1, M = 1, R = 0, K = 1;
+    double s = 1.0, W = 0.0;  // cutoff scale and half width (input samples) of the prototype
+    int64_t out_len(int64_t n) const { return (n * L + M - 1) / M; }
+    // the longest output prefix whose taps all lie in the final input samples [0, e) of a row of n samples (all of it once e == n: the zeros behind the
+    // row's end are final)
+    int64_t final_prefix(int64_t e, int64_t n) const {
+        if (e >= n) return out_len(n);
+        return e - R <= 0 ? 0 : std::min(out_len(n), ((e - R) * L + M - 1) / M);
+    }
+};
+// host only. false + a message naming the cause: a rate outside [4000, 192000], or a table of more than 2^20 floats
+bool resample_plan(int in_rate, int out_rate, ResamplePlan& p, std::string& err);
+std::vector<float> resample_taps(const ResamplePlan& p);  // [L][K], h[p][k] = g(R - k + p / L)
+constexpr int kResampleTile = 1024;  // output samples per block (halved down to 256 while the staged input span would not fit: steep downsampling)
+struct ResampleCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;  // device [batch]: valid input samples of each row (<= x_stride); nothing behind them is read
+    const int *j0 = nullptr, *j1 = nullptr;  // device [batch], optional: the output range [j0, j1) of each row (clamped to its N_out); null = the whole row
+    float* y = nullptr;  // device [batch][y_stride]; samples outside the range are left as they are
+    int64_t y_stride = 0;
+    const float* taps = nullptr;  // device [K][L] (the TRANSPOSE of resample_taps: threads of a wave differ in p)
+    ResamplePlan plan;
+    int batch = 0;
+    int64_t max_range = 0;  // the longest range of the call (host side: sizes the grid)
+};
+hipError_t launch_resample(const ResampleCall& c, hipStream_t s);
 
 }  // namespace vits
