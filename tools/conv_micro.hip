@@ -15,6 +15,7 @@
 #define VITS_MICRO_KT KT_
 #define VITS_MICRO_DIL DIL_
 #include "../vits.cpp_amd/csrc/conv_mfma.hip"
+#include "../vits.cpp_amd/csrc/conv_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 #ifndef KT_
 #define KT_ 11

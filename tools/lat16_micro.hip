@@ -7,6 +7,7 @@
 #define VITS_MICRO_KT 3
 #define VITS_MICRO_DIL 1
 #include "../vits.cpp_amd/csrc/conv_mfma.hip"
+#include "../vits.cpp_amd/csrc/conv_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 #ifndef CIN_
 #define CIN_ 768

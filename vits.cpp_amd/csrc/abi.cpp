@@ -854,7 +854,7 @@ bool split3_nan(DevU16& d, int batch, int channels, int ts, vits::Split3Ref* r) 
     r->bs = 3 * r->ps;
     return true;
 }
-// why the split kernels do not take a conv (conv_split.hip conv_split_candidate / conv_split_supported), or "" if they do
+// why the split kernels do not take a conv (conv_plan.cpp conv_split_candidate / conv_split_supported), or "" if they do
 std::string split_refusal(int cin, int cout, int k, int dil) {
     char m[200] = "";
     if (cin < 128 || (cin & 31)) std::snprintf(m, sizeof(m), "VITS_ARITH_F32_SPLIT: c_in = %d is not taken by the split kernels (a multiple of 32, at least 128)", cin);

@@ -540,19 +540,8 @@ hipError_t launch_conv_post16(Ref16 x, const float* w, int cin, int k, TensorRef
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // Packed layout: [row tile][chunk][tap][k-half kk][lane][8]; lane l's 8 values = A[row = tile*32 + (l&31)][ci = chunk*32 + (2*kk + (l>>5))*8 + e][tap]
 std::vector<uint16_t> pack_conv_weights16(const float* w, int cout, int cin, int k, int epi, int ct_stride, int arith) {
-    const int half = cout / 2;
-    int rows, kt;
-    if (epi == EPI_CONVT) {
-        rows = cout * ct_stride;
-        kt = k / ct_stride;
-    } else {
-        rows = cout;
-        kt = k;
-    }
-    int mtiles = (rows + 31) / 32;
-    if (epi == EPI_GATE) mtiles = 2 * ((half + 31) / 32);
-    mtiles = (mtiles + 3) / 4 * 4;
-    const int nchunks = (cin + 31) / 32;
+    const ConvPackDims pd = conv_pack_dims(cout, cin, k, epi, ct_stride);
+    const int half = cout / 2, kt = pd.kt, mtiles = pd.mtiles, nchunks = pd.nchunks;
     std::vector<uint16_t> out((size_t)mtiles * nchunks * kt * 2 * 64 * 8, 0);
     auto cvt = [&](float v) -> uint16_t { return arith == VITS_ARITH_BF16 ? f32_to_bf16(v) : f32_to_f16(v); };
     for (int mt = 0; mt < mtiles; ++mt)
@@ -588,21 +577,6 @@ std::vector<uint16_t> pack_conv_weights16(const float* w, int cout, int cin, int
 
 #endif  // host part
 
-struct Tile16 {
-    int wm, wn, mr, nr;
-};
-static Tile16 tile16_shape(int tile) {
-    switch (tile) {
-        case 0: return {2, 2, 2, 4};  // 128 x 256
-        case 1: return {1, 4, 2, 2};  // 64 x 256
-        case 2: return {1, 4, 1, 2};  // 32 x 256
-        case 3: return {1, 4, 2, 1};  // 64 x 128
-        case 5: return {2, 2, 2, 2};  // 128 x 128
-        case 6: return {4, 1, 1, 4};  // 128 x 128, one row tile per wave: every A fragment feeds 4 MFMAs
-        default: return {1, 4, 1, 1};  // 32 x 128
-    }
-}
-
 // The kernel template is instantiated for ~90 (taps, dilation, tile, epilogue) combinations per operand type, so the Makefile
 // compiles this file eight times: VITS_CONV16_BF = 0 / 1 (fp16 / bf16) x VITS_CONV16_PART = 0 (standard-layout epilogues,
 // transposed convs, host code), 1 (group epilogue, taps 1/3/5), 2 (taps 7), 3 (taps 11). Each part defines one dispatcher.
@@ -613,71 +587,52 @@ static Tile16 tile16_shape(int tile) {
 #define VITS_CONV16_BF 0
 #endif
 constexpr bool kBF = VITS_CONV16_BF != 0;
+static_assert(int(E16_STD) == C16_STD && int(E16_GATE) == C16_GATE && int(E16_CONVT) == C16_CONVT && int(E16_GROUP) == C16_GROUP && int(E16_CONVT_GROUP) == C16_CONVT_GROUP, "conv_plan.h names the epilogues");
 
 template <int KT, int DIL, int EPI>
-static hipError_t launch_tile16(int tile, const Conv16Params& p, int mtiles_used, int ncols_max, int batch, hipStream_t s) {
-    const Tile16 ts = tile16_shape(tile);
-    const int bn = ts.wn * ts.nr * 32;
-    const int bm = ts.wm * ts.mr;
-    dim3 grid((ncols_max + bn - 1) / bn, (mtiles_used + bm - 1) / bm, batch);
-    const size_t lds = (size_t)p.nbuf * 4 * p.xwp * 16;
+static hipError_t launch_tile16(const Conv16Plan& pl, const Conv16Params& p, hipStream_t s) {
+    dim3 grid(pl.gx, pl.gy, pl.gz);
+    const size_t lds = pl.lds;
 #define VITS_LAUNCH16(WM, WN, MR, NR)                                                                                                \
     do {                                                                                                                             \
-        static BigLdsOnce big_lds_set;                                                                                 \
-        if (lds > 64 * 1024 && big_lds_set.needed()) {                                                       \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16_kernel<KT, DIL, WM, WN, MR, NR, EPI, kBF>),     \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                            \
-            if (ea != hipSuccess) return ea;                                                                                         \
-            big_lds_set.done();                                                                      \
-        }                                                                                                                            \
+        static BigLdsOnce big_lds_set; \
+        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv16_kernel<KT, DIL, WM, WN, MR, NR, EPI, kBF>), lds)) return ea; \
         VITS_KLAUNCH((conv16_kernel<KT, DIL, WM, WN, MR, NR, EPI, kBF>), grid, dim3(320), lds, s, p);                          \
     } while (0)
-    // which tiles exist for which epilogue: the standard-layout epilogues (stage one, flow, transparent fallback) only come in the
-    // 64- and 32-row tiles; the gate needs MR == 2; run-time-dilation variants skip the 128 x 256 tile
-    constexpr bool group = EPI == E16_GROUP || EPI == E16_CONVT_GROUP;
-    switch (tile) {
-        case 0:
-            if constexpr (group && DIL != 0) VITS_LAUNCH16(2, 2, 2, 4);
-            else return hipErrorInvalidValue;
-            break;
-        case 1: VITS_LAUNCH16(1, 4, 2, 2); break;
-        case 2:
-            if constexpr (group) VITS_LAUNCH16(1, 4, 1, 2);
-            else return hipErrorInvalidValue;
-            break;
-        case 3: VITS_LAUNCH16(1, 4, 2, 1); break;
-        case 5:
-            if constexpr (group && DIL != 0) VITS_LAUNCH16(2, 2, 2, 2);
-            else return hipErrorInvalidValue;
-            break;
-        case 6:
-            if constexpr (group && DIL != 0) VITS_LAUNCH16(4, 1, 1, 4);
-            else return hipErrorInvalidValue;
-            break;
-        default:
-            if constexpr (EPI != E16_GATE) VITS_LAUNCH16(1, 4, 1, 1);
-            else return hipErrorInvalidValue;
-            break;
+    // (the arms an epilogue lacks are the backstop: plan_conv16 asks conv16_tile_exists before it chooses)
+#define VITS_TILE16_ARM(LABEL, T)                                      \
+    LABEL:                                                             \
+        if constexpr (conv16_tile_exists(EPI, DIL, T)) {               \
+            constexpr TileShape ts = tile16_shape(T);                  \
+            VITS_LAUNCH16(ts.wm, ts.wn, ts.mr, ts.nr);                 \
+            break;                                                     \
+        } else {                                                       \
+            return hipErrorInvalidValue;                               \
+        }
+    switch (pl.tile) {
+        VITS_TILE16_ARM(case 0, 0)
+        VITS_TILE16_ARM(case 1, 1)
+        VITS_TILE16_ARM(case 2, 2)
+        VITS_TILE16_ARM(case 3, 3)
+        VITS_TILE16_ARM(case 5, 5)
+        VITS_TILE16_ARM(case 6, 6)
+        VITS_TILE16_ARM(default, 4)
     }
+#undef VITS_TILE16_ARM
 #undef VITS_LAUNCH16
     return hipGetLastError();
 }
 
-// does the 128 x 256 tile exist for this (epilogue, taps, dilation)? (mirrors launch_tile16 / the dispatchers below)
-static bool conv16_has_tile0(int epi16, int kt, int dil) {
-    if (epi16 == E16_CONVT_GROUP) return true;
-    if (epi16 != E16_GROUP) return false;
-    if (kt == 1) return true;
-    if (kt == 3 || kt == 7 || kt == 11) return dil == 1 || dil == 3 || dil == 5;
-    return false;
-}
-
-#define VITS_DISPATCH16(NAME) hipError_t NAME(int epi16, int kt, int tile, const Conv16Params& p, int mtiles_used, int ncols_max, int batch, hipStream_t s)
-#define VITS_T16(KT, DIL, EPI) return launch_tile16<KT, DIL, EPI>(tile, p, mtiles_used, ncols_max, batch, s)
+#define VITS_DISPATCH16(NAME) hipError_t NAME(int epi16, int kt, const Conv16Plan& pl, const Conv16Params& p, hipStream_t s)
+// (the instantiation plan_conv16 named: conv16_template_dil)
+#define VITS_T16(KT, DIL, EPI) \
+    if (epi16 == EPI && kt == KT && pl.dil_ct == DIL) return launch_tile16<KT, DIL, EPI>(pl, p, s)
+#define VITS_T16_RB(KT) VITS_T16(KT, 1, E16_GROUP); VITS_T16(KT, 3, E16_GROUP); VITS_T16(KT, 5, E16_GROUP); VITS_T16(KT, 0, E16_GROUP)
+#define VITS_CAT16(a, b) a##b
 #if VITS_CONV16_BF
-#define VITS_FN16(part) conv16_dispatch_bf16_p##part
+#define VITS_FN16(part) VITS_CAT16(conv16_dispatch_bf16_p, part)
 #else
-#define VITS_FN16(part) conv16_dispatch_f16_p##part
+#define VITS_FN16(part) VITS_CAT16(conv16_dispatch_f16_p, part)
 #endif
 VITS_DISPATCH16(conv16_dispatch_f16_p0);
 VITS_DISPATCH16(conv16_dispatch_f16_p1);
@@ -688,95 +643,36 @@ VITS_DISPATCH16(conv16_dispatch_bf16_p1);
 VITS_DISPATCH16(conv16_dispatch_bf16_p2);
 VITS_DISPATCH16(conv16_dispatch_bf16_p3);
 
+VITS_DISPATCH16(VITS_FN16(VITS_CONV16_PART)) {
 #if VITS_CONV16_PART == 0
-VITS_DISPATCH16(VITS_FN16(0)) {
-    if (epi16 == E16_CONVT) {
-        if (kt == 2) VITS_T16(2, -1, E16_CONVT);
-        return hipErrorInvalidValue;
-    }
-    if (epi16 == E16_CONVT_GROUP) {
-        if (kt == 2) VITS_T16(2, -1, E16_CONVT_GROUP);
-        return hipErrorInvalidValue;
-    }
-    if (epi16 == E16_GATE) {
-        if (kt == 5) VITS_T16(5, 0, E16_GATE);
-        if (kt == 3) VITS_T16(3, 0, E16_GATE);
-        return hipErrorInvalidValue;
-    }
-    if (epi16 == E16_STD) {
-        switch (kt) {
-            case 1: VITS_T16(1, 1, E16_STD);
-            case 3: VITS_T16(3, 0, E16_STD);
-            case 5: VITS_T16(5, 0, E16_STD);
-            case 7: VITS_T16(7, 0, E16_STD);
-            case 11: VITS_T16(11, 0, E16_STD);
-            default: return hipErrorInvalidValue;
-        }
-    }
+    VITS_T16(2, -1, E16_CONVT);
+    VITS_T16(2, -1, E16_CONVT_GROUP);
+    VITS_T16(5, 0, E16_GATE);
+    VITS_T16(3, 0, E16_GATE);
+    VITS_T16(1, 1, E16_STD);
+    VITS_T16(3, 0, E16_STD);
+    VITS_T16(5, 0, E16_STD);
+    VITS_T16(7, 0, E16_STD);
+    VITS_T16(11, 0, E16_STD);
+#elif VITS_CONV16_PART == 1
+    VITS_T16(1, 1, E16_GROUP);
+    VITS_T16_RB(3);
+    VITS_T16(5, 0, E16_GROUP);
+#elif VITS_CONV16_PART == 2
+    VITS_T16_RB(7);
+#else
+    VITS_T16_RB(11);
+#endif
     return hipErrorInvalidValue;
 }
-#endif
-#if VITS_CONV16_PART == 1
-VITS_DISPATCH16(VITS_FN16(1)) {
-    if (epi16 != E16_GROUP) return hipErrorInvalidValue;
-    if (kt == 1) VITS_T16(1, 1, E16_GROUP);
-    if (kt == 3) {
-        if (p.dil == 1) VITS_T16(3, 1, E16_GROUP);
-        if (p.dil == 3) VITS_T16(3, 3, E16_GROUP);
-        if (p.dil == 5) VITS_T16(3, 5, E16_GROUP);
-        VITS_T16(3, 0, E16_GROUP);
-    }
-    if (kt == 5) VITS_T16(5, 0, E16_GROUP);
-    return hipErrorInvalidValue;
-}
-#endif
-#if VITS_CONV16_PART == 2
-VITS_DISPATCH16(VITS_FN16(2)) {
-    if (epi16 != E16_GROUP || kt != 7) return hipErrorInvalidValue;
-    if (p.dil == 1) VITS_T16(7, 1, E16_GROUP);
-    if (p.dil == 3) VITS_T16(7, 3, E16_GROUP);
-    if (p.dil == 5) VITS_T16(7, 5, E16_GROUP);
-    VITS_T16(7, 0, E16_GROUP);
-}
-#endif
-#if VITS_CONV16_PART == 3
-VITS_DISPATCH16(VITS_FN16(3)) {
-    if (epi16 != E16_GROUP || kt != 11) return hipErrorInvalidValue;
-    if (p.dil == 1) VITS_T16(11, 1, E16_GROUP);
-    if (p.dil == 3) VITS_T16(11, 3, E16_GROUP);
-    if (p.dil == 5) VITS_T16(11, 5, E16_GROUP);
-    VITS_T16(11, 0, E16_GROUP);
-}
-#endif
+#undef VITS_T16_RB
 #undef VITS_T16
 
 #if VITS_CONV16_PART == 0 && !VITS_CONV16_BF
-int choose_conv16_tile(int rows, int epi, int ncols_max, int mtiles_used, int batch) {
-    int tile;
-    const bool small_t = ncols_max <= 128;
-    // c_out multiple of 128: 128 x 128 tiles (default) read the input tile once per 128 rows at 3 blocks per CU. 128 x 256 tiles
-    // (VITS_T16_TILE0=1) hold one block per CU (196 VGPRs: K loop and epilogue run back to back: 33.6 ms per step); 64 x 256 tiles
-    // (VITS_T16_TILE0=2: 29.6 ms) overlap epilogue traffic with MFMAs but fetch the input once per 64 rows.
-    const int tile0 = kernel_knobs().t16_tile0;
-    if (epi == EPI_GATE) tile = small_t ? 3 : 1;
-    else if (rows % 128 == 0) tile = small_t ? 3 : (tile0 == 1 ? 0 : tile0 == 2 ? 1 : tile0 == 3 ? 5 : tile0 == 4 ? 3 : 6);
-    else if (rows % 64 == 0) tile = small_t ? 3 : 1;
-    else tile = small_t ? 4 : 2;
-    // small grids (batch 1, short inputs): step down until the launch has >= 512 blocks
-    auto blocks = [&](int tl) {
-        const Tile16 t2 = tile16_shape(tl);
-        const int64_t nb = (ncols_max + t2.wn * t2.nr * 32 - 1) / (t2.wn * t2.nr * 32);
-        const int64_t mb = (mtiles_used + t2.wm * t2.mr - 1) / (t2.wm * t2.mr);
-        return nb * mb * batch;
-    };
-    if (blocks(tile) < 512 && (tile == 0 || tile == 1 || tile == 5 || tile == 6)) tile = 3;
-    if (epi != EPI_GATE && blocks(tile) < 512 && (tile == 3 || tile == 2)) tile = 4;
-    return tile;
-}
-
 hipError_t launch_conv16(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s) {
-    if (!w.wp16) return hipErrorInvalidValue;
-    if (conv16_lat_wanted(w, c)) return launch_conv16_lat(w, c, arith, s);  // (small grids of the wide vocoder stages: conv16_lat.hip)
+    const Conv16Plan pl = plan_conv16(w, c);
+    if (!pl.ok) return hipErrorInvalidValue;
+    if (pl.lat) return launch_conv16_lat(w, c, pl.l, arith, s);  // (small grids of the wide vocoder stages: conv16_lat.hip)
     Conv16Params p;
     p.x = c.x.p;
     p.x_bs = c.x.bs;
@@ -818,46 +714,15 @@ hipError_t launch_conv16(const PackedConv& w, const Conv16Call& c, int arith, hi
     p.y16_bs = c.y16.bs;
     p.y16_ts = c.y16.ts;
     p.y16_slope = c.y16_slope;
-    const bool group = c.yg || c.y16.p;
-    int epi16;
-    if (w.epi == EPI_CONVT) epi16 = group ? E16_CONVT_GROUP : E16_CONVT;
-    else if (w.epi == EPI_GATE) epi16 = E16_GATE;
-    else epi16 = group ? E16_GROUP : E16_STD;
-    if (epi16 == E16_GROUP && (w.cout & 7)) return hipErrorInvalidValue;
-    const int ncols_max = w.epi == EPI_CONVT ? c.t_in + 1 : c.t_out;
-    if (w.epi == EPI_CONVT) {
-        p.dil = -1;
-        p.pad_l = 0;
-    } else {
-        p.dil = w.kt == 1 ? 1 : c.dil;
-        p.pad_l = c.pad_l;
-    }
-    int tile = c.tile >= 0 ? c.tile : choose_conv16_tile(w.rows, w.epi, ncols_max, w.mtiles_used, c.batch);
-    if ((tile == 0 || tile == 5 || tile == 6) && !conv16_has_tile0(epi16, w.kt, p.dil)) tile = 1;
-    if (tile == 2 && !(epi16 == E16_GROUP || epi16 == E16_CONVT_GROUP)) tile = 4;
-    const Tile16 ts = tile16_shape(tile);
-    const int bn = ts.wn * ts.nr * 32;
-    const int span = (w.kt - 1) * p.dil;
-    p.lds_off = span < 0 ? -span : 0;
-    p.xwp = (bn + (span < 0 ? -span : span) + 7) / 8 * 8;
-    if (p.xwp > 384) return hipErrorInvalidValue;
-    {
-        // third LDS buffer where a chunk is less MFMA time than an HBM round trip (~6k cycles): taps x 2 k-halves x MR*NR MFMAs x 32 cycles
-        const bool short_chunk = w.kt * 2 * ts.mr * ts.nr * 32 < 6000 && w.nchunks >= 3;
-        p.nbuf = short_chunk ? 3 : 2;
-        if ((size_t)p.nbuf * 4 * p.xwp * 16 > 150 * 1024) p.nbuf = 2;
-    }
+    p.dil = pl.dil;
+    p.pad_l = w.epi == EPI_CONVT ? 0 : c.pad_l;
+    p.lds_off = pl.lds_off;
+    p.xwp = pl.xwp;
+    p.nbuf = pl.nbuf;
     const bool bf = arith == VITS_ARITH_BF16;
-    const int part = epi16 != E16_GROUP ? 0 : (w.kt == 7 ? 2 : w.kt == 11 ? 3 : 1);
-#define VITS_CALL16(P) (bf ? conv16_dispatch_bf16_p##P(epi16, w.kt, tile, p, w.mtiles_used, ncols_max, c.batch, s) \
-                           : conv16_dispatch_f16_p##P(epi16, w.kt, tile, p, w.mtiles_used, ncols_max, c.batch, s))
-    switch (part) {
-        case 0: return VITS_CALL16(0);
-        case 1: return VITS_CALL16(1);
-        case 2: return VITS_CALL16(2);
-        default: return VITS_CALL16(3);
-    }
-#undef VITS_CALL16
+    static constexpr decltype(&conv16_dispatch_f16_p0) dispatch[2][4] = {{conv16_dispatch_f16_p0, conv16_dispatch_f16_p1, conv16_dispatch_f16_p2, conv16_dispatch_f16_p3},
+                                                                        {conv16_dispatch_bf16_p0, conv16_dispatch_bf16_p1, conv16_dispatch_bf16_p2, conv16_dispatch_bf16_p3}};
+    return dispatch[bf][pl.part](pl.epi16, w.kt, pl, p, s);
 }
 #endif
 

@@ -243,71 +243,12 @@ __global__ __launch_bounds__(WM * 64) void conv16_lat_group_kernel(const Conv16L
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-// Which convs: the group-layout ResBlock convs (same length in and out, bias, no activation of the stored value) of a C = 128 / 256
-// stage with k = 3 / 7 / 11, while the launch has at most VITS_LAT16H_MAX_TILES (C = 256) / VITS_LAT16H_MAX_TILES_C128 32 x 32 output tiles (one to four utterances).
-// Measured (f16, ms per batch of 1 / 2 / 3 / 4 x 128 ids; fused pairs -> this kernel): 1.485 -> 1.428, 1.596 -> 1.553, 1.826 -> 1.780, 1.974 -> 1.939; C = 128 at batch 1 (1792 tiles): + 6 ... 12 us.
-bool conv16_lat_shape_ok(int channels, int kt, int dil, int batch, int tmax) {
-    const KernelKnobs& kn = kernel_knobs();
-    if (kn.no_lat16h) return false;
-    if (!(channels == 128 || channels == 256) || !(kt == 3 || kt == 7 || kt == 11) || dil < 1 || (kt - 1) * dil > 50) return false;
-    const int64_t tiles = (int64_t)((tmax + 31) / 32) * (channels / 32) * batch;
-    return tiles <= (channels == 256 ? kn.lat16h_max_tiles : kn.lat16h_max_tiles_c128);
-}
-bool conv16_lat_wanted(const PackedConv& w, const Conv16Call& c) {
-    if (c.tile >= 0 || w.cin != w.cout || !conv16_lat_shape_ok(w.cin, w.kt, c.dil, c.batch, c.t_out)) return false;
-    if (w.epi != EPI_STD || !(c.yg || c.y16.p) || !w.wp16 || !w.bias) return false;
-    if (c.len_in != c.len_out || c.t_in != c.t_out || c.post_act != 0 || c.ct_crop != 0 || c.pad_l != (w.kt - 1) * c.dil / 2) return false;
-    return !(c.y.p || c.res.p || c.acc.p || c.y2);
-}
-
+// (which convs take these kernels, block shape, pitch, grid and LDS bytes: conv_plan.cpp)
 template <int KT, int C, int WM, int NR, bool BF>
-static hipError_t launch_c16l(const Conv16LatParams& p, int batch, hipStream_t s) {
-    const size_t lds = (size_t)(C / 8) * p.pitch * 16 + 8 * 16;  // (+ the slots the look-ahead of the last tap reads past the tile, value unused)
+static hipError_t launch_c16l(const Conv16LatParams& p, const Conv16LatPlan& l, hipStream_t s) {
     static BigLdsOnce big;
-    if (lds > 64 * 1024 && big.needed()) {
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv16_lat_kernel<KT, C, WM, NR, BF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
-        big.done();
-    }
-    dim3 grid((p.tmax + 32 * NR - 1) / (32 * NR), C / 32 / WM, batch);
-    VITS_KLAUNCH((conv16_lat_kernel<KT, C, WM, NR, BF>), grid, dim3(WM * 64), lds, s, p);
-    return hipGetLastError();
-}
-
-// The vocoder's conv_pre (F -> up_init channels, k = 7, vits.cpp:601) on a small grid, straight from the fp32 flow output: the converter launch
-// (launch_to_group16) and the throughput kernel's 14 us become one launch of this kernel (batch 1: - 15 us). Same rounding expression, same K order,
-// same group epilogue: same bits.
-bool conv16_lat_pre_wanted(const PackedConv& w, int batch, int tmax) {
-    const KernelKnobs& kn = kernel_knobs();
-    if (kn.no_lat16h || kn.no_lat16h_pre || !w.wp16 || !w.bias || w.epi != EPI_STD) return false;
-    if (w.cin != 192 || w.kt != 7 || (w.cout % 64) != 0) return false;
-    const int64_t tiles = (int64_t)((tmax + 31) / 32) * (w.cout / 32) * batch;
-    return tiles <= kn.lat16h_max_tiles;
-}
-hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s,
-                                 const int* spk) {
-    if (!conv16_lat_pre_wanted(w, batch, tmax) || !x.p || !y16.p) return hipErrorInvalidValue;
-    Conv16LatParams p = {};
-    p.xf = x.p;
-    p.xf_bs = x.bs;
-    p.xf_cs = x.cs;
-    p.wp = w.wp16;
-    p.bias = w.bias;
-    p.bias_rows = w.bias_rs ? spk : nullptr;
-    p.bias_rs = w.bias_rs;
-    p.lens = lens;
-    p.tmax = tmax;
-    p.dil = 1;
-    p.pad_l = (w.kt - 1) / 2;
-    p.pitch = (32 + (w.kt - 1) + 7) / 8 * 8;
-    p.y16 = y16.p;
-    p.y16_bs = y16.bs;
-    p.y16_ts = y16.ts;
-    p.y16_slope = y16_slope;
-    p.scale = 1.f;
-    const size_t lds = (size_t)(192 / 8) * p.pitch * 16 + 8 * 16;
-    dim3 grid((tmax + 31) / 32, w.cout / 32 / 2, batch);
-    if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((conv16_lat_kernel<7, 192, 2, 1, true, true>), grid, dim3(128), lds, s, p);
-    else VITS_KLAUNCH((conv16_lat_kernel<7, 192, 2, 1, false, true>), grid, dim3(128), lds, s, p);
+    if (hipError_t e = big.raise(reinterpret_cast<const void*>(&conv16_lat_kernel<KT, C, WM, NR, BF>), l.lds)) return e;
+    VITS_KLAUNCH((conv16_lat_kernel<KT, C, WM, NR, BF>), dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, s, p);
     return hipGetLastError();
 }
 
@@ -335,32 +276,33 @@ static Conv16LatParams c16l_params(const PackedConv& w, const Conv16Call& c, int
     p.y16_slope = c.y16_slope;
     p.scale = c.scale;
     p.scale_div = c.scale_div;
-    p.pitch = (32 * nr + (w.kt - 1) * c.dil + 7) / 8 * 8;
+    p.pitch = conv16_lat_pitch(nr, w.kt, c.dil);
     return p;
 }
 
-// the group launch: members k = 3, 7, 11 of one stage (C = 256), equal shapes; two row tiles x 32 columns per block
-bool conv16_lat_group_wanted(const PackedConv* const* w, const Conv16Call* c) {
-    if (kernel_knobs().no_lat16h_group) return false;
-    static const int kts[3] = {3, 7, 11};
-    for (int i = 0; i < 3; ++i) {
-        if (!conv16_lat_wanted(*w[i], c[i]) || w[i]->kt != kts[i] || w[i]->cin != 256) return false;
-        if (c[i].batch != c[0].batch || c[i].t_out != c[0].t_out || c[i].len_out != c[0].len_out || c[i].dil != c[0].dil) return false;
-    }
-    return true;
+hipError_t launch_conv16_lat_pre(const PackedConv& w, TensorRef x, const int* lens, int batch, int tmax, Ref16 y16, float y16_slope, int arith, hipStream_t s,
+                                 const int* spk) {
+    if (!conv16_lat_pre_wanted(w, batch, tmax) || !x.p || !y16.p) return hipErrorInvalidValue;
+    Conv16Call c;  // (a 'same' conv of dilation 1 into the 16-bit copy only)
+    c.len_out = lens, c.spk = spk, c.t_out = tmax, c.pad_l = (w.kt - 1) / 2, c.y16 = y16, c.y16_slope = y16_slope;
+    Conv16LatParams p = c16l_params(w, c, 1);
+    p.xf = x.p, p.xf_bs = x.bs, p.xf_cs = x.cs;
+    const Conv16LatPlan l = plan_conv16_lat(192, w.cout, w.kt, 1, 21, tmax, batch);
+    const dim3 grid(l.gx, l.gy, l.gz);
+    if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((conv16_lat_kernel<7, 192, 2, 1, true, true>), grid, dim3(l.block), l.lds, s, p);
+    else VITS_KLAUNCH((conv16_lat_kernel<7, 192, 2, 1, false, true>), grid, dim3(l.block), l.lds, s, p);
+    return hipGetLastError();
 }
+
 hipError_t launch_conv16_lat_group(const PackedConv* const* w, const Conv16Call* c, int arith, hipStream_t s) {
     if (!conv16_lat_group_wanted(w, c)) return hipErrorInvalidValue;
     Conv16LatGroupParams gp;
-    const int shape = kernel_knobs().lat16h_group_shape;  // 10 WM + NR
-    const int wm = shape / 10, nr = shape % 10;
-    int pitch = 0;
-    for (int i = 0; i < 3; ++i) {
-        gp.m[i] = c16l_params(*w[i], c[i], nr);
-        pitch = gp.m[i].pitch > pitch ? gp.m[i].pitch : pitch;
-    }
-    const size_t lds = (size_t)(256 / 8) * pitch * 16 + 8 * 16;
-    dim3 grid((c[0].t_out + 32 * nr - 1) / (32 * nr), 256 / 32 / wm, 3 * c[0].batch);
+    // (the LDS of the widest member, k = 11; every member keeps its own pitch)
+    const Conv16LatPlan l = plan_conv16_lat(256, 256, 11, c[0].dil, kernel_knobs().lat16h_group_shape, c[0].t_out, 3 * c[0].batch);
+    const int wm = l.wm, nr = l.nr;
+    for (int i = 0; i < 3; ++i) gp.m[i] = c16l_params(*w[i], c[i], nr);
+    const size_t lds = l.lds;
+    const dim3 grid(l.gx, l.gy, l.gz);
     const bool bf = arith == VITS_ARITH_BF16;
 #define VITS_C16LG(WM_, NR_)                                                                                                                        \
     if (wm == WM_ && nr == NR_) {                                                                                                                   \
@@ -376,15 +318,12 @@ hipError_t launch_conv16_lat_group(const PackedConv* const* w, const Conv16Call*
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv16_lat(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s) {
-    if (!conv16_lat_wanted(w, c)) return hipErrorInvalidValue;
+hipError_t launch_conv16_lat(const PackedConv& w, const Conv16Call& c, const Conv16LatPlan& l, int arith, hipStream_t s) {
     const bool bf = arith == VITS_ARITH_BF16;
-    // shape (VITS_LAT16H_SHAPE = 10 WM + NR): two row tiles x 32 columns per block by default (batch 1: 1.483 ms against 1.498 with 64 columns and 1.492 with four row tiles x 64)
-    const int shape = kernel_knobs().lat16h_shape;
-    const int wm = shape / 10, nr = shape % 10;
+    const int wm = l.wm, nr = l.nr;
     const Conv16LatParams p = c16l_params(w, c, nr);
 #define VITS_C16L_GO(K, CC, WM_, NR_)                                                                                                           \
-    if (w.kt == K && w.cin == CC && wm == WM_ && nr == NR_) return bf ? launch_c16l<K, CC, WM_, NR_, true>(p, c.batch, s) : launch_c16l<K, CC, WM_, NR_, false>(p, c.batch, s)
+    if (w.kt == K && w.cin == CC && wm == WM_ && nr == NR_) return bf ? launch_c16l<K, CC, WM_, NR_, true>(p, l, s) : launch_c16l<K, CC, WM_, NR_, false>(p, l, s)
 #define VITS_C16L_SHAPES(K, CC) \
     VITS_C16L_GO(K, CC, 2, 1);  \
     VITS_C16L_GO(K, CC, 2, 2);  \

@@ -1220,29 +1220,18 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
     }
 }
 
-// the launch: TILE_LAT16 from resolve_conv_tile
-static int lat16_pitch(int span) { return span <= 4 ? 24 : span <= 20 ? 40 : span <= 52 ? 72 : 0; }
-static hipError_t launch_lat16(const PackedConv& w, const ConvParams& p0, int ncols_max, int batch, hipStream_t s) {
+// the launch: TILE_LAT16 from plan_conv
+static hipError_t launch_lat16(const PackedConv& w, const ConvPlan& pl, const ConvParams& p0, hipStream_t s) {
     ConvParams p = p0;
-    const int span = (w.kt - 1) * p.dil;
-    const int pitch = lat16_pitch(span);
-    if (!pitch || !w.wp_l16) return hipErrorInvalidValue;
+    const int pitch = pl.pitch;
     // 16-byte aligned rows: float4 fill from the 4-aligned time below the tile's first input
     p.l16_fill4 = (reinterpret_cast<uintptr_t>(p.x) & 15) == 0 && (p.x_cs & 3) == 0 && (p.x_bs & 3) == 0;
-    p.xw = pitch;
-    p.kt_rt = w.kt;
-    p.wl16 = w.wp_l16;
-    size_t lds = ((size_t)w.nchunks + 1) * CK * pitch * sizeof(float);  // (+ one chunk of slack rows: the look-ahead of the last tap)
-    if (p.ln_gamma) lds += ((size_t)2 * 16 * 32 + 2 * (size_t)w.cin) * sizeof(float);  // LayerNorm on load: partial sums of up to 32 columns; gamma, beta
-    dim3 grid((ncols_max + 15) / 16, (w.mtiles_used + 1) / 2, batch);
+    const size_t lds = pl.lds;
+    dim3 grid(pl.gx, pl.gy, pl.gz);
 #define VITS_L16(E, PP)                                                                                                                          \
     do {                                                                                                                                         \
-        static BigLdsOnce big;                                                                                                                   \
-        if (lds > 64 * 1024 && big.needed()) {                                                                                                   \
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_lat16_kernel<E, PP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) \
-                return e;                                                                                                                        \
-            big.done();                                                                                                                          \
-        }                                                                                                                                        \
+        static BigLdsOnce big;                                                                                \
+        if (hipError_t e = big.raise(reinterpret_cast<const void*>(&conv_lat16_kernel<E, PP>), lds)) return e;                    \
         VITS_KLAUNCH((conv_lat16_kernel<E, PP>), grid, dim3(256), lds, s, p);                                                                    \
     } while (0)
     if (w.epi == EPI_GATE) {
@@ -1280,55 +1269,17 @@ __global__ __launch_bounds__(320) VITS_WAVES_ATTR void conv_group_kernel(const C
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
-hipError_t make_conv_params(const PackedConv& w, const ConvCall& c, int tile, ConvParams& p);
-struct TileShape {
-    int wm, wn, mr, nr;
-};
-static TileShape tile_shape(int tile) {
-    switch (tile) {
-        case TILE_128x128: return {2, 2, 2, 2};
-        case TILE_64x256: return {1, 4, 2, 2};
-        case TILE_32x256: return {1, 4, 1, 2};
-        case TILE_64x64: return {1, 4, 2, 1};  // 64 x 128
-        case TILE_LAT16:  // (conv_lat16_kernel has its own grid; parameters are set up as for the narrow tile)
-        case TILE_NARROW: return {4, 1, 1, 1};  // 128 x 32: four row tiles of ONE 32-column strip
-        default: return {1, 4, 1, 1};          // TILE_32x64: 32 x 128
-    }
-}
+static_assert(CK == kConvCK, "conv_plan.h plans with the kernels' chunk size");
+void make_conv_params(const PackedConv& w, const ConvCall& c, const ConvPlan& pl, ConvParams& p);
 
 #if VITS_CONV_PART == 0
-int choose_conv_tile(int rows, int epi, int t_hint) {
-    // rows <= 64 (few MFMAs per staged tile): 128-column tiles -> twice as many independent blocks per CU keep more
-    // loads in flight (measured 120.5 -> 116.4 ms per step); VITS_NARROW_TILES=0 restores 256-column tiles
-    const int narrow = kernel_knobs().narrow_tiles;
-    const bool small_t = t_hint <= 128 || (narrow && rows <= narrow);
-    if (epi == EPI_GATE) return small_t ? TILE_64x64 : TILE_64x256;
-    const int t128 = kernel_knobs().tile128;
-    if (rows % 128 == 0 && t128) return TILE_128x128;
-    if (rows % 64 == 0) return small_t ? TILE_64x64 : TILE_64x256;
-    return small_t ? TILE_32x64 : TILE_32x256;
-}
-
 // Packed layout: [mtile][chunk][tap][p4 = pair/4][lane][q = pair%4]; the value for (mtile, chunk c, tap j, pair p,
 // lane l) is A[row = mtile*32 + (l&31)][ci = c*32 + 2p + (l>>5)][tap j] — lane l's A operand of the MFMA
 // that consumes input channels (2p, 2p+1) of chunk c at tap j.
 std::vector<float> pack_conv_weights(const float* w, int cout, int cin, int k, int epi, int ct_stride, int* rows_out, int* mtiles_used_out,
                                      int* mtiles_out, int* nchunks_out) {
-    const int bm_tiles = 4;  // padded so that every tile shape (1, 2 or 4 row tiles per block) divides it
-    const int half = cout / 2;
-    int rows, kt;
-    if (epi == EPI_CONVT) {
-        rows = cout * ct_stride;
-        kt = k / ct_stride;  // == 2 taps per phase
-    } else {
-        rows = cout;
-        kt = k;
-    }
-    int mtiles = (rows + 31) / 32;
-    if (epi == EPI_GATE) mtiles = 2 * ((half + 31) / 32);
-    *mtiles_used_out = mtiles;
-    mtiles = (mtiles + bm_tiles - 1) / bm_tiles * bm_tiles;
-    const int nchunks = (cin + CK - 1) / CK;
+    const ConvPackDims pd = conv_pack_dims(cout, cin, k, epi, ct_stride);
+    const int half = cout / 2, kt = pd.kt, mtiles = pd.mtiles, nchunks = pd.nchunks;
     std::vector<float> out((size_t)mtiles * nchunks * kt * (CK / 2) * 64, 0.f);
     for (int mt = 0; mt < mtiles; ++mt)
         for (int c = 0; c < nchunks; ++c)
@@ -1356,16 +1307,11 @@ std::vector<float> pack_conv_weights(const float* w, int cout, int cin, int k, i
                         const size_t idx = (((((size_t)mt * nchunks + c) * kt + j) * (CK / 8) + pr / 4) * 64 + l) * 4 + (pr & 3);
                         out[idx] = v;
                     }
-    *rows_out = rows;
+    *rows_out = pd.rows;
+    *mtiles_used_out = pd.mtiles_used;
     *mtiles_out = mtiles;
     *nchunks_out = nchunks;
     return out;
-}
-
-bool conv_lat16_candidate(int epi, int kt, int cin) {
-    // (>= 64 products per output: everything but the degenerate convs. The long chains — FFN, gated, vocoder — win by the chain (41 -> 17.7 us);
-    // the 1x1 convs, whose chain is only 2.6 us, by the fill and the finer grid: 13-16 -> 7 us at batch 1)
-    return (epi == EPI_STD || (epi == EPI_GATE && kt == 5)) && (int64_t)kt * cin >= 64;
 }
 
 std::vector<float> repack_conv_weights_l16(const std::vector<float>& packed, int mtiles, int nchunks, int kt) {
@@ -1389,95 +1335,65 @@ std::vector<float> repack_conv_weights_l16(const std::vector<float>& packed, int
 #endif  // VITS_CONV_PART == 0
 
 template <int KT, int DIL, bool DB, int EPI>
-static hipError_t launch_tile(const PackedConv& w, int tile, const ConvParams& p, int ncols_max, int batch, hipStream_t s) {
-    const TileShape ts = tile_shape(tile);
-    const int bn = ts.wn * ts.nr * 32;
-    const int bm_tiles = ts.wm * ts.mr;
-    dim3 grid((ncols_max + bn - 1) / bn, (w.mtiles_used + bm_tiles - 1) / bm_tiles, batch);
-    const size_t lds = DB ? (size_t)p.nbuf * CK * ((p.xw + 3 + VITS_XWP_GRAN - 1) / VITS_XWP_GRAN * VITS_XWP_GRAN) * sizeof(float) : (size_t)CK * p.xw * sizeof(float);
+static hipError_t launch_tile(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
+    dim3 grid(pl.gx, pl.gy, pl.gz);
+    const size_t lds = pl.lds;
 #define VITS_LAUNCH(WM, WN, MR, NR)                                                                                                   \
     do {                                                                                                                              \
-        static BigLdsOnce big_lds_set; /* (atomic: distinct model handles may launch from distinct threads) */         \
-        if (lds > 64 * 1024 && big_lds_set.needed()) {                                                                                        \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<KT, DIL, DB, WM, WN, MR, NR, EPI>),       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                             \
-            if (ea != hipSuccess) return ea;                                                                                          \
-            big_lds_set.done();                                                                                                 \
-        }                                                                                                                             \
+        static BigLdsOnce big_lds_set; /* (atomic: distinct model handles may launch from distinct threads) */ \
+        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv_mfma_kernel<KT, DIL, DB, WM, WN, MR, NR, EPI>), lds)) return ea; \
         VITS_KLAUNCH((conv_mfma_kernel<KT, DIL, DB, WM, WN, MR, NR, EPI>), grid, dim3(DB ? 320 : 256), lds, s, p);                             \
     } while (0)
-    switch (tile) {
-        case TILE_128x128:
-            if (EPI == EPI_GATE) return hipErrorInvalidValue;
-            VITS_LAUNCH(2, 2, 2, 2);
-            break;
-        case TILE_64x256: VITS_LAUNCH(1, 4, 2, 2); break;
-        case TILE_64x64: VITS_LAUNCH(1, 4, 2, 1); break;
-        case TILE_32x256:
-            if (EPI == EPI_GATE) return hipErrorInvalidValue;
-            VITS_LAUNCH(1, 4, 1, 2);
-            break;
-        case TILE_NARROW:
-            // (only where launch_conv chooses it: encoder / flow convs on the producer-wave path)
-            if constexpr (DB && DIL == 1 && ((EPI == EPI_STD && KT <= 3) || (EPI == EPI_GATE && KT == 5))) {
-                VITS_LAUNCH(4, 1, 1, 1);  // (gated conv: tanh / sigmoid row tiles on wave pairs, see the epilogue)
-                break;
-            } else {
-                return hipErrorInvalidValue;
-            }
-        default:
-            if (EPI == EPI_GATE) return hipErrorInvalidValue;
-            VITS_LAUNCH(1, 4, 1, 1);
-            break;
+    // (the arms an (epilogue, taps, dilation) lacks are the backstop: plan_conv asks conv_tile_exists before it chooses)
+#define VITS_TILE_ARM(LABEL, T)                                                      \
+    LABEL:                                                                           \
+        if constexpr (conv_tile_exists(EPI, KT, DIL, DB, T)) {                       \
+            constexpr TileShape ts = tile_shape(T);                                  \
+            VITS_LAUNCH(ts.wm, ts.wn, ts.mr, ts.nr);                                 \
+            break;                                                                   \
+        } else {                                                                     \
+            return hipErrorInvalidValue;                                             \
+        }
+    switch (pl.tile) {
+        VITS_TILE_ARM(case TILE_128x128, TILE_128x128)
+        VITS_TILE_ARM(case TILE_64x256, TILE_64x256)
+        VITS_TILE_ARM(case TILE_32x256, TILE_32x256)
+        VITS_TILE_ARM(case TILE_64x64, TILE_64x64)
+        VITS_TILE_ARM(case TILE_NARROW, TILE_NARROW)
+        VITS_TILE_ARM(default, TILE_32x64)
     }
+#undef VITS_TILE_ARM
 #undef VITS_LAUNCH
     return hipGetLastError();
 }
 
-// one launcher per tap count (see VITS_CONV_PART): picks the compile-time dilation and the producer-wave variant
-#define VITS_GO(K, D, E)                                                                     \
-    do {                                                                                     \
-        if ((D) != 0 && db) return launch_tile<K, D, (D) != 0, E>(w, tile, p, ncols_max, batch, s); \
-        return launch_tile<K, D, false, E>(w, tile, p, ncols_max, batch, s);                 \
+// one launcher per tap count (see VITS_CONV_PART): the instantiation plan_conv named — compile-time dilation (conv_template_dil) and producer-wave variant
+#define VITS_GO(K, D, E)                                                                      \
+    do {                                                                                      \
+        if (w.kt == K && pl.dil_ct == D) {                                                    \
+            if ((D) != 0 && pl.db) return launch_tile<K, D, (D) != 0, E>(pl, p, s);           \
+            return launch_tile<K, D, false, E>(pl, p, s);                                     \
+        }                                                                                     \
     } while (0)
-#define VITS_LAUNCHER(K) hipError_t launch_conv_k##K(const PackedConv& w, int tile, const ConvParams& p, int ncols_max, int batch, hipStream_t s, bool db)
+#define VITS_LAUNCHER(K) hipError_t launch_conv_k##K(const PackedConv& w, const ConvPlan& pl, const ConvParams& p, hipStream_t s)
+#define VITS_LAUNCHER_BODY(K) \
+    VITS_LAUNCHER(K) { VITS_GO(K, 1, EPI_STD); VITS_GO(K, 3, EPI_STD); VITS_GO(K, 5, EPI_STD); VITS_GO(K, 0, EPI_STD); return hipErrorInvalidValue; }
 VITS_LAUNCHER(3);
 VITS_LAUNCHER(7);
 VITS_LAUNCHER(11);
 #if VITS_CONV_PART == 1
-VITS_LAUNCHER(3) {
-    if (p.dil == 1) VITS_GO(3, 1, EPI_STD);
-    if (p.dil == 3) VITS_GO(3, 3, EPI_STD);
-    if (p.dil == 5) VITS_GO(3, 5, EPI_STD);
-    VITS_GO(3, 0, EPI_STD);
-}
-#endif
-#if VITS_CONV_PART == 2
-VITS_LAUNCHER(7) {
-    if (p.dil == 1) VITS_GO(7, 1, EPI_STD);
-    if (p.dil == 3) VITS_GO(7, 3, EPI_STD);
-    if (p.dil == 5) VITS_GO(7, 5, EPI_STD);
-    VITS_GO(7, 0, EPI_STD);
-}
-#endif
-#if VITS_CONV_PART == 3
-VITS_LAUNCHER(11) {
-    if (p.dil == 1) VITS_GO(11, 1, EPI_STD);
-    if (p.dil == 3) VITS_GO(11, 3, EPI_STD);
-    if (p.dil == 5) VITS_GO(11, 5, EPI_STD);
-    VITS_GO(11, 0, EPI_STD);
-}
+VITS_LAUNCHER_BODY(3)
+#elif VITS_CONV_PART == 2
+VITS_LAUNCHER_BODY(7)
+#elif VITS_CONV_PART == 3
+VITS_LAUNCHER_BODY(11)
 #endif
 
 #if VITS_CONV_PART == 4
-bool conv_group_supported(const PackedConv& w, int dil) {
-    return w.epi == EPI_STD && (w.kt == 11 || w.kt == 7 || w.kt == 3) && (dil == 1 || dil == 3 || dil == 5) && w.rows % 128 == 0 && w.cin % CK == 0;
-}
 hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int n, hipStream_t s) {
     if (n < 1 || n > 3) return hipErrorInvalidValue;
     ConvGroupParams g;
     std::memset(&g, 0, sizeof(g));
-    const int slot_kt[3] = {11, 7, 3};
     int have[3] = {-1, -1, -1};
     for (int i = 0; i < n; ++i) {
         if (!conv_group_supported(*w[i], c[i].dil) || c[i].dil != c[0].dil || c[i].batch != c[0].batch || w[i]->rows != w[0]->rows || c[i].tile >= 0) return hipErrorInvalidValue;
@@ -1490,27 +1406,22 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
     for (int slot = 0; slot < 3; ++slot) {
         if (have[slot] >= 0) {
             const int i = have[slot];
-            if (hipError_t e = make_conv_params(*w[i], c[i], TILE_128x128, g.m[slot])) return e;
-            if (g.m[slot].oneshot) return hipErrorInvalidValue;  // (never: 128 x 128 tiles have MR * NR = 4)
+            const ConvPlan pl = plan_conv(*w[i], c[i], TILE_128x128);
+            if (!pl.ok || pl.oneshot) return hipErrorInvalidValue;  // (oneshot never: 128 x 128 tiles have MR * NR = 4)
+            make_conv_params(*w[i], c[i], pl, g.m[slot]);
             if (g.m[slot].bias_rows) return hipErrorInvalidValue;  // (never: the grouped launch serves the resblocks, which carry no speaker term)
             g.m[slot].nbuf = 2;
             z += c[i].batch;
             ncols_max = std::max(ncols_max, c[i].t_out);
-            const int xwp = (g.m[slot].xw + 3 + VITS_XWP_GRAN - 1) / VITS_XWP_GRAN * VITS_XWP_GRAN;
-            lds = std::max(lds, (size_t)2 * CK * xwp * sizeof(float));
+            lds = std::max(lds, (size_t)2 * CK * padded_xw(pl.xw) * sizeof(float));
         }
         g.zend[slot] = z;
-        (void)slot_kt;
     }
     dim3 grid((ncols_max + 127) / 128, w[0]->mtiles_used / 4, z);
 #define VITS_GROUP_LAUNCH(D)                                                                                                              \
     do {                                                                                                                                  \
-        static BigLdsOnce big_lds_set;                                                                                      \
-        if (lds > 64 * 1024 && big_lds_set.needed()) {                                                            \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_group_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (ea != hipSuccess) return ea;                                                                                              \
-            big_lds_set.done();                                                                           \
-        }                                                                                                                                 \
+        static BigLdsOnce big_lds_set; \
+        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv_group_kernel<D>), lds)) return ea; \
         VITS_KLAUNCH((conv_group_kernel<D>), grid, dim3(320), lds, s, g);                                                           \
     } while (0)
     if (c[0].dil == 1) VITS_GROUP_LAUNCH(1);
@@ -1522,64 +1433,8 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
 #endif
 
 #if VITS_CONV_PART == 0
-// The tile a launch will run on: shape rule (choose_conv_tile), then the small-grid steps. Also what the engine's profiler prints.
-int resolve_conv_tile(const PackedConv& w, const ConvCall& c) {
-    const int ncols_max = w.epi == EPI_CONVT ? c.t_in + 1 : c.t_out;
-    int tile = c.tile >= 0 ? c.tile : choose_conv_tile(w.rows, w.epi, ncols_max);
-    if (c.tile < 0 && w.epi == EPI_GATE) {
-        const TileShape t2 = tile_shape(tile);
-        const int64_t nb = (ncols_max + t2.wn * t2.nr * 32 - 1) / (t2.wn * t2.nr * 32);
-        if (nb * ((w.mtiles_used + 1) / 2) * c.batch < 512) tile = TILE_64x64;  // 64 x 128 keeps the tanh/sigmoid row pairing
-    }
-    if (c.tile < 0 && w.epi != EPI_GATE) {
-        // small grids (batch 1, short inputs): fewer than ~2 blocks per CU leaves matrix pipes idle -> step down to
-        // smaller tiles until the launch has >= 512 blocks (latency case, BASELINE.json config 2)
-        auto blocks = [&](int tl) {
-            const TileShape t2 = tile_shape(tl);
-            const int64_t nb = (ncols_max + t2.wn * t2.nr * 32 - 1) / (t2.wn * t2.nr * 32);
-            const int64_t mb = (w.mtiles_used + t2.wm * t2.mr - 1) / (t2.wm * t2.mr);
-            return nb * mb * c.batch;
-        };
-        // (k <= 3: 1024 — a short K loop costs a small tile little, and e.g. the encoder's 192 -> 768 FFN conv at batch 64 x 128 tokens is
-        // 768 blocks of 64 x 128 = 1.5 rounds of the 512 resident blocks, but 3 even rounds of 32 x 128: 82 -> 74 us)
-        const int64_t min_blocks_env = kernel_knobs().min_blocks;
-        const int64_t min_blocks = min_blocks_env > 0 ? min_blocks_env : (w.kt <= 3 ? 1024 : 512);
-        if (blocks(tile) < min_blocks && (tile == TILE_128x128 || tile == TILE_64x256)) tile = TILE_64x64;  // 64 x 128
-        if (blocks(tile) < min_blocks && (tile == TILE_64x64 || tile == TILE_32x256)) tile = TILE_32x64;    // 32 x 128
-    }
-    if (c.tile < 0 && w.epi != EPI_CONVT) {
-        // tiny grids (the encoder / duration predictor / flow at batch 1: 6-18 blocks of the 128-column tiles): every block of a
-        // 128-column tile streams the WHOLE input in through its one producer wave, and that stream, not the MFMA chain, is the
-        // launch time (768 -> 192 FFN conv, k = 3, 128 tokens: 78 us for a 31 us chain). Blocks of four row tiles x ONE 32-column
-        // strip need a quarter of the input each. Same per-output accumulation order (the tile shape never changes it).
-        const bool no_narrow = kernel_knobs().no_narrow;
-        const int dil_eff = w.kt == 1 ? 1 : c.dil;
-        const bool shape_ok = dil_eff == 1 && ((w.epi == EPI_STD && w.kt <= 3) || (w.epi == EPI_GATE && w.kt == 5));
-        const TileShape t2 = tile_shape(tile);
-        const int64_t nb = (int64_t)((ncols_max + t2.wn * t2.nr * 32 - 1) / (t2.wn * t2.nr * 32)) * ((w.mtiles_used + t2.wm * t2.mr - 1) / (t2.wm * t2.mr)) * c.batch;
-        // 1x1 convs (QKV / output / projection convs of the encoder, the flow's pre / post convs): the narrow tile on large grids too —
-        // 192 -> 576 at batch 64 x 128 tokens 34 -> 26 us, 192 -> 192 21 -> 13 us; at 1024 tokens (config 5) the 1x1 convs of a step 0.83 ->
-        // 0.65 ms (bf16 run), 1.34 -> 1.05 ms (fp32 run). VITS_NARROW_K1 = longest sequence that takes it (0: small grids only)
-        const int narrow_k1 = kernel_knobs().narrow_k1;
-        const bool k1_short = narrow_k1 > 0 && w.epi == EPI_STD && w.kt == 1 && ncols_max <= narrow_k1;
-        if (!no_narrow && shape_ok && (nb <= 128 || k1_short)) tile = TILE_NARROW;
-        // ... and where the launch time is one wave's MFMA chain (a second copy of the weights exists for the layers with >= 512 products
-        // per output: not the 1x1 convs, whose chain is 2.6 us of a launch that is bound by its fill), 16 x 16 tiles on
-        // v_mfma_f32_16x16x4_f32 (conv_lat16_kernel): the tiny grids of the narrow tile, and any standard conv whose 32 x 32 tiles would
-        // not even fill the SIMDs once (batch 1: the C = 256 stage of the vocoder, conv_pre)
-        const int pitch16 = lat16_pitch((w.kt - 1) * dil_eff);
-        const int64_t waves32 = (int64_t)((ncols_max + 31) / 32) * w.mtiles_used * c.batch;
-        const bool tiny = tile == TILE_NARROW && nb <= 128;
-        const bool unfilled = w.epi == EPI_STD && w.kt >= 3 && dil_eff >= 1 && waves32 <= kernel_knobs().lat16_max_waves;
-        if ((tiny || unfilled) && !kernel_knobs().no_lat16 && w.wp_l16 && pitch16 && (w.epi == EPI_STD || pitch16 == 24) &&
-            ((size_t)w.nchunks + 1) * CK * pitch16 * 4 <= 150 * 1024)
-            tile = TILE_LAT16;
-    }
-    return tile;
-}
-
-// ConvCall -> kernel parameters for the tile `tile` (also used by the grouped launch, part 4)
-hipError_t make_conv_params(const PackedConv& w, const ConvCall& c, int tile, ConvParams& p) {
+// ConvCall + plan -> kernel parameters (also used by the grouped launch, part 4)
+void make_conv_params(const PackedConv& w, const ConvCall& c, const ConvPlan& pl, ConvParams& p) {
     p.x = c.x.p;
     p.x_bs = c.x.bs;
     p.x_cs = c.x.cs;
@@ -1623,91 +1478,40 @@ hipError_t make_conv_params(const PackedConv& w, const ConvCall& c, int tile, Co
     p.ln_out = c.ln_out.p;
     p.lo_bs = c.ln_out.bs;
     p.lo_cs = c.ln_out.cs;
-    const int ncols_max = w.epi == EPI_CONVT ? c.t_in + 1 : c.t_out;
-    const TileShape ts = tile_shape(tile);
-    const int bn = ts.wn * ts.nr * 32;
-    if (w.epi == EPI_CONVT) {
-        p.dil = -1;  // tap m reads x[q - m]
-        p.pad_l = 0;
-    } else {
-        p.dil = w.kt == 1 ? 1 : c.dil;
-        p.pad_l = c.pad_l;
-    }
-    const int span = (w.kt - 1) * p.dil;  // signed extent of the taps
-    p.lds_off = span < 0 ? -span : 0;
-    p.xw = bn + (span < 0 ? -span : span);
-    if ((size_t)2 * CK * p.xw * 4 > 160 * 1024) return hipErrorInvalidValue;
-    {
-        // third LDS buffer (DMA two chunks ahead) where a chunk is less MFMA work than a DMA round trip (~2.5 us = 6k cycles):
-        // taps x (MFMAs per k-step) x 16 k-steps x 64 cycles
-        const int nbuf_env = kernel_knobs().nbuf;
-        const TileShape t3 = ts;
-        const bool short_chunk = w.kt * t3.mr * t3.nr * 1024 < 8000 && w.nchunks >= 3 && bn == 128;
-        p.nbuf = nbuf_env == 2 || nbuf_env == 3 ? nbuf_env : (short_chunk ? 3 : 2);
-        if (w.nchunks < 2 || (size_t)p.nbuf * CK * ((p.xw + 3 + VITS_XWP_GRAN - 1) / VITS_XWP_GRAN * VITS_XWP_GRAN) * 4 > 150 * 1024) p.nbuf = 2;
-        // latency-bound launch on a small tile whose whole input fits in LDS: cooperative one-shot fill (see the kernel)
-        const bool no_oneshot = kernel_knobs().no_oneshot;
-        const int64_t nblocks = (int64_t)((ncols_max + bn - 1) / bn) * ((w.mtiles_used + t3.wm * t3.mr - 1) / (t3.wm * t3.mr)) * c.batch;
-        p.oneshot = 0;
-        if (!no_oneshot && t3.mr * t3.nr <= 2 && nblocks <= 512 && w.nchunks >= 2 &&
-            (size_t)w.nchunks * CK * ((p.xw + 3 + VITS_XWP_GRAN - 1) / VITS_XWP_GRAN * VITS_XWP_GRAN) * 4 <= 150 * 1024) {
-            p.oneshot = 1;
-            p.nbuf = w.nchunks;
-        }
-    }
-    return hipSuccess;
-}
-
-// LayerNorm on load exists in conv_lat16_kernel only (the launches it pays for are the latency-bound ones): a standard conv without an input activation
-// whose tile choice is TILE_LAT16, with the statistics' scratch beside the input tile in LDS, and the input lengths = the output lengths (padded 'same' conv)
-bool conv_ln_on_load_ok(const PackedConv& w, const ConvCall& c) {
-    if (w.epi != EPI_STD || c.pre_act || !w.wp_l16 || c.len_in != c.len_out || c.t_in != c.t_out) return false;
-    if (resolve_conv_tile(w, c) != TILE_LAT16) return false;
-    const int span = (w.kt - 1) * (w.kt == 1 ? 1 : c.dil);
-    const int pitch = lat16_pitch(span);
-    return pitch && span <= 16 && (((size_t)w.nchunks + 1) * CK * pitch + 2 * 16 * 32 + 2 * (size_t)w.cin) * sizeof(float) <= 150 * 1024;
+    p.dil = pl.dil;
+    p.pad_l = w.epi == EPI_CONVT ? 0 : c.pad_l;
+    p.lds_off = pl.lds_off;
+    p.xw = pl.xw;
+    p.nbuf = pl.nbuf;
+    p.oneshot = pl.oneshot;
 }
 
 hipError_t launch_conv(const PackedConv& w, const ConvCall& c, hipStream_t s) {
+    const ConvPlan pl = plan_conv(w, c);
+    if (!pl.ok) return hipErrorInvalidValue;
     ConvParams p;
-    const int ncols_max = w.epi == EPI_CONVT ? c.t_in + 1 : c.t_out;
-    const int tile = resolve_conv_tile(w, c);
-    if (hipError_t e = make_conv_params(w, c, tile, p)) return e;
-    if (c.ln_gamma && (tile != TILE_LAT16 || !c.ln_beta || !c.ln_out.p || !conv_ln_on_load_ok(w, c))) return hipErrorInvalidValue;
-    if (tile == TILE_LAT16) return launch_lat16(w, p, ncols_max, c.batch, s);
-    const int span = (w.kt - 1) * p.dil;  // signed extent of the taps
-    if ((span < 0 ? -span : span) > 64) return hipErrorInvalidValue;  // generic kernels stage at most BN + 64 columns
-    const int batch = c.batch;
-    // compile-time dilation for the combinations the MMS architecture uses; run-time dilation (DIL = 0) otherwise
-    // producer-wave path for every compile-time-dilation conv: with dwordx4 LDS-DMA it also wins for single-chunk inputs
-    // (c_in = 32: 109 -> 120 TFLOP/s on the k = 11 layers; with dword DMA it lost 8 % there). VITS_DB_MIN=2 restores the
-    // register-staged kernels for them.
-    const int db_min = kernel_knobs().db_min;
-    const bool db = w.nchunks >= db_min;
+    make_conv_params(w, c, pl, p);
+    if (c.ln_gamma && (!c.ln_beta || !c.ln_out.p || !pl.ln_ok)) return hipErrorInvalidValue;
+    if (pl.tile == TILE_LAT16) return launch_lat16(w, pl, p, s);
 #ifdef VITS_MICRO_KT  // developer microbenchmark (tools/conv_micro.hip): instantiate a single (taps, dilation) pair
-    VITS_GO(VITS_MICRO_KT, VITS_MICRO_DIL, EPI_STD);
+    if ((VITS_MICRO_DIL) != 0 && pl.db) return launch_tile<VITS_MICRO_KT, VITS_MICRO_DIL, (VITS_MICRO_DIL) != 0, EPI_STD>(pl, p, s);
+    return launch_tile<VITS_MICRO_KT, VITS_MICRO_DIL, false, EPI_STD>(pl, p, s);
 #else
     if (w.epi == EPI_CONVT) {
-        if (w.kt == 2) VITS_GO(2, -1, EPI_CONVT);
-        return hipErrorInvalidValue;
+        VITS_GO(2, -1, EPI_CONVT);
+    } else if (w.epi == EPI_GATE) {
+        VITS_GO(5, 1, EPI_GATE);
+        VITS_GO(5, 0, EPI_GATE);
+    } else {
+        VITS_GO(1, 1, EPI_STD);
+        VITS_GO(5, 1, EPI_STD);
+        VITS_GO(5, 0, EPI_STD);
+        if (w.kt == 3) return launch_conv_k3(w, pl, p, s);
+        if (w.kt == 7) return launch_conv_k7(w, pl, p, s);
+        if (w.kt == 11) return launch_conv_k11(w, pl, p, s);
     }
-    if (w.epi == EPI_GATE) {
-        if (w.kt == 5 && p.dil == 1) VITS_GO(5, 1, EPI_GATE);
-        if (w.kt == 5) VITS_GO(5, 0, EPI_GATE);
-        return hipErrorInvalidValue;
-    }
-    switch (w.kt) {
-        case 1: VITS_GO(1, 1, EPI_STD);
-        case 3: return launch_conv_k3(w, tile, p, ncols_max, batch, s, db);
-        case 5:
-            if (p.dil == 1) VITS_GO(5, 1, EPI_STD);
-            VITS_GO(5, 0, EPI_STD);
-        case 7: return launch_conv_k7(w, tile, p, ncols_max, batch, s, db);
-        case 11: return launch_conv_k11(w, tile, p, ncols_max, batch, s, db);
-        default: break;
-    }
-#endif
     return hipErrorInvalidValue;
+#endif
 }
 
 double conv_flops(const PackedConv& w, const ConvCall&, int64_t total_cols) {

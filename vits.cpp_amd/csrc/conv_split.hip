@@ -334,15 +334,6 @@ bool pack_conv_weights_split(const float* w, int cout, int cin, int k, std::vect
     return true;
 }
 
-// (C = 64 was tried on the 64 x 256 tile below (WM = 2): 92 TFLOP/s-equivalent against 124 for the fused fp32 pairs — a 60 KB chunk per buffer leaves one block per CU,
-// and ONE producer wave's LDS-DMA stream, ~1 KB per 0.12 us, takes as long per chunk as the chunk's MFMAs; the narrow stages keep their fused fp32 kernels)
-bool conv_split_candidate(int epi, int kt, int cin, int cout) {
-    return epi == EPI_STD && (kt == 3 || kt == 7 || kt == 11) && cin >= 128 && (cin & 31) == 0 && (cout & 127) == 0;
-}
-bool conv_split_supported(const PackedConv& w, int dil) {
-    return w.wps && conv_split_candidate(w.epi, w.kt, w.cin, w.cout) && (dil == 1 || dil == 3 || dil == 5);
-}
-
 hipError_t launch_conv_split(const PackedConv& w, const ConvCall& c, hipStream_t s) {
     if (!conv_split_supported(w, c.dil) || !c.xs3.p || c.pre_act || c.y2 || (c.post_act != 0 && c.post_act != 2) || (!c.y.p && !c.ys3.p)) return hipErrorInvalidValue;
     if (w.bias_rs && c.spk) return hipErrorInvalidValue;  // (no per-utterance bias here: the split path serves the resblocks only)
@@ -359,7 +350,7 @@ hipError_t launch_conv_split(const PackedConv& w, const ConvCall& c, hipStream_t
     p.scale = c.scale, p.scale_div = c.scale_div;
     p.post_act = c.post_act, p.post_slope = c.post_slope;
     p.ys = c.ys3.p, p.ys_bs = c.ys3.bs, p.ys_ps = c.ys3.ps, p.ys_ts = c.ys3.ts, p.ys_slope = c.ys3_slope;
-    const int wm = 4;  // (the 64-row tile, WM = 2, is not instantiated: see conv_split_candidate)
+    const int wm = 4;  // (the 64-row tile, WM = 2, is not instantiated: see conv_split_candidate, conv_plan.cpp)
     const int bn = 128 * (4 / wm);
     dim3 grid((c.t_out + bn - 1) / bn, w.cout / (32 * wm), c.batch);
 #define VITS_CS(K, D, M)                                                                                                                          \

@@ -11,11 +11,10 @@ namespace vits {
 // One 16-bit-operand convolution launch (conv16.hip), profiled like conv(): tile names carry a capital T
 hipError_t Engine::conv16(const char* name, const PackedConv& w, const Conv16Call& c, hipStream_t stream, double bytes) {
     if (prof.on) {
-        const int ncols = w.epi == EPI_CONVT ? c.t_in + 1 : c.t_out;
-        const int tile = c.tile >= 0 ? c.tile : (conv16_lat_wanted(w, c) ? 7 : choose_conv16_tile(w.rows, w.epi, ncols, w.mtiles_used, c.batch));
+        const Conv16Plan pl = plan_conv16(w, c);  // (the tile that runs; 7: conv16_lat_kernel)
         const bool group = c.yg || c.y16.p;
         char full[160];
-        std::snprintf(full, sizeof(full), "%s|k%d|d%d|T%d|e%d%s|c%dx%d", name, w.kt, w.epi == EPI_CONVT ? -1 : (w.kt == 1 ? 1 : c.dil), tile, w.epi, group ? "g" : "", w.cin,
+        std::snprintf(full, sizeof(full), "%s|k%d|d%d|T%d|e%d%s|c%dx%d", name, w.kt, pl.dil, pl.tile, w.epi, group ? "g" : "", w.cin,
                       w.cout);
         const int64_t tot_in = c.sum_in >= 0 ? c.sum_in : (int64_t)c.batch * c.t_in;
         const int64_t tot_out = c.sum_out >= 0 ? c.sum_out : (int64_t)c.batch * c.t_out;
@@ -91,9 +90,9 @@ hipError_t Engine::conv(const char* name, const PackedConv& w, ConvCall c, hipSt
     if (prof.on) {
         // name = label|k<taps>|d<dilation>|t<tile>|e<epilogue>|c<cin>x<cout>: one entry per kernel instantiation and shape, so the
         // bench can line entries up with rocprofv3's per-kernel-name statistics
-        const int tile = resolve_conv_tile(w, c);
+        const ConvPlan pl = plan_conv(w, c);
         char full[160];
-        std::snprintf(full, sizeof(full), "%s|k%d|d%d|t%d|e%d|c%dx%d", name, w.kt, w.epi == EPI_CONVT ? -1 : (w.kt == 1 ? 1 : c.dil), tile, w.epi, w.cin,
+        std::snprintf(full, sizeof(full), "%s|k%d|d%d|t%d|e%d|c%dx%d", name, w.kt, pl.dil, pl.tile, w.epi, w.cin,
                       w.cout);
         // algorithmic work over the REAL lengths (sum over utterances), not the padded grid extent
         const int64_t tot_in = c.sum_in >= 0 ? c.sum_in : (int64_t)c.batch * c.t_in;

@@ -718,7 +718,7 @@ hipError_t Engine::pack16_device(const PackSrc& ps, int arith16, uint16_t** d, i
 int Engine::set_arith(int a, std::string& err) {
     if (a == arith) return 0;
     if (a == VITS_ARITH_F32_SPLIT) {
-        // two bf16 planes of A fragments for every conv the split kernels may take (conv_split.hip conv_split_candidate), built once; a conv whose weights are
+        // two bf16 planes of A fragments for every conv the split kernels may take (conv_plan.cpp conv_split_candidate), built once; a conv whose weights are
         // not exactly two bf16 pieces (fp32-stored) simply keeps its fp32 kernels. Transactional like the 16-bit packing below.
         HIP_OK(hipStreamSynchronize(stream));
         std::vector<std::pair<PackedConv*, uint16_t*>> fresh;

@@ -521,7 +521,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
                 shape.batch = B;
                 shape.t_in = shape.t_out = s.t_out;
                 for (size_t d = 0; d < R.dil.size() && grouped; ++d)
-                    grouped = conv_group_supported(R.c1[d], R.dil[d]) && conv_group_supported(R.c2[d], 1) && resolve_conv_tile(R.c1[d], shape) == TILE_128x128;
+                    grouped = conv_group_supported(R.c1[d], R.dil[d]) && conv_group_supported(R.c2[d], 1) && plan_conv(R.c1[d], shape).tile == TILE_128x128;
                 ++members;
             }
             grouped = grouped && members >= 2;

@@ -155,6 +155,13 @@ struct BigLdsOnce {
     }
     bool needed() const { return !(mask.load(std::memory_order_acquire) & bit()); }
     void done() { mask.fetch_or(bit(), std::memory_order_release); }
+    // before a launch with `lds` bytes of dynamic LDS: raise the kernel's limit to the CU's 160 KB, the first time on this device that it needs more than 64 KB
+    hipError_t raise(const void* kernel, size_t lds) {
+        if (lds <= 64 * 1024 || !needed()) return hipSuccess;
+        if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
+        done();
+        return hipSuccess;
+    }
 };
 
 // Per-launch timing without extra queue packets. The engine's per-kernel profiler (bench.py's instrumented region) used to bracket
@@ -197,7 +204,7 @@ enum ConvTile : int {
     TILE_32x256 = 2,
     TILE_64x64 = 3,
     TILE_32x64 = 4,
-    TILE_NARROW = 5,  // 128 rows x 32 columns (256 x 32 for the gated conv): tiny grids only, see choose in launch_conv
+    TILE_NARROW = 5,  // 128 rows x 32 columns (256 x 32 for the gated conv): tiny grids and 1x1 convs only (plan_conv, conv_plan.cpp)
     TILE_LAT16 = 6    // 64 rows x 16 columns on v_mfma_f32_16x16x4_f32 (conv_lat16_kernel): tiny grids with long K chains
 };
 
@@ -276,17 +283,15 @@ bool pack_conv_weights_split(const float* w, int cout, int cin, int k, std::vect
 bool conv_split_supported(const PackedConv& w, int dil);
 hipError_t launch_conv_split(const PackedConv& w, const ConvCall& c, hipStream_t s);
 hipError_t launch_split_planes(TensorRef x, int channels, const int* lens, int batch, int tmax, float slope, Split3Ref out, hipStream_t s);
-bool conv_ln_on_load_ok(const PackedConv& w, const ConvCall& c);
 
 // host-side packing: w is torch layout [cout][cin][k] (EPI_STD / EPI_GATE) or [cin][cout][k] (EPI_CONVT)
 std::vector<float> pack_conv_weights(const float* w, int cout, int cin, int k, int epi, int ct_stride, int* rows, int* mtiles_used, int* mtiles,
                                      int* nchunks);
 // conv_lat16_kernel's A fragments from the packed array: [32-row tile][16-row half][quad = 16 input channels of one tap][lane][4] with lane l = row l & 15,
 // component s = channel 4 s + (l >> 4) of the quad: one 16-byte load per lane feeds four consecutive MFMAs. Same size as `packed`.
-bool conv_lat16_candidate(int epi, int kt, int cin);  // the layers that get a second copy of their fp32 weights for the latency kernel: every STD conv and the 5-tap GATE convs with >= 64 products per output
 std::vector<float> repack_conv_weights_l16(const std::vector<float>& packed, int mtiles, int nchunks, int kt);
-int choose_conv_tile(int rows, int epi, int t_hint);
-int resolve_conv_tile(const PackedConv& w, const ConvCall& c);  // the tile launch_conv will use (small-grid rules included)
+bool conv_lat16_candidate(int epi, int kt, int cin);  // the layers that get a second copy of their fp32 weights for the latency kernel: every STD conv and the 5-tap GATE convs with >= 64 products per output
+bool conv_ln_on_load_ok(const PackedConv& w, const ConvCall& c);  // plan_conv(w, c).ln_ok
 hipError_t launch_conv(const PackedConv& w, const ConvCall& c, hipStream_t s);
 double conv_flops(const PackedConv& w, const ConvCall& c, int64_t total_cols);
 // The same-position convolutions of up to three ResBlocks (11 / 7 / 3 taps, one dilation of {1, 3, 5}, one channel count that is a
@@ -413,11 +418,11 @@ hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, con
 hipError_t launch_rbpair32(const PackedConv& c1, const PackedConv& c2, const RbPair32Call& c, hipStream_t s);
 hipError_t launch_rbpair16(const PackedConv& c1, const PackedConv& c2, const RbPair16Call& c, int arith, hipStream_t s);
 std::vector<uint16_t> pack_conv_weights16(const float* w, int cout, int cin, int k, int epi, int ct_stride, int arith);
-int choose_conv16_tile(int rows, int epi, int ncols_max, int mtiles_used, int batch);
 // conv16_lat.hip: the wide stages' group-layout resblock convs on small grids (batch 1 ... 4); launch_conv16 routes to it (profile tile tag T7)
 bool conv16_lat_shape_ok(int channels, int kt, int dil, int batch, int tmax);
 bool conv16_lat_wanted(const PackedConv& w, const Conv16Call& c);
-hipError_t launch_conv16_lat(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s);
+struct Conv16LatPlan;  // block shape, pitch, grid, LDS bytes (conv_plan.h)
+hipError_t launch_conv16_lat(const PackedConv& w, const Conv16Call& c, const Conv16LatPlan& l, int arith, hipStream_t s);  // (launch_conv16's lat route)
 bool conv16_lat_group_wanted(const PackedConv* const* w, const Conv16Call* c);  // the same-position convs of a stage's three resblocks (k = 3, 7, 11) as ONE launch
 hipError_t launch_conv16_lat_group(const PackedConv* const* w, const Conv16Call* c, int arith, hipStream_t s);
 bool conv16_lat_pre_wanted(const PackedConv& w, int batch, int tmax);  // the vocoder's conv_pre on a small grid, straight from the fp32 flow output (no converter launch)
@@ -613,3 +618,5 @@ struct ResampleCall {
 hipError_t launch_resample(const ResampleCall& c, hipStream_t s);
 
 }  // namespace vits
+
+#include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
