@@ -156,6 +156,28 @@ def test_add_layer_norm_matches_oracle(pkg, oracle):
     assert rel_err(pkg.op_add_layer_norm(x, r, g, b), oracle.add_layer_norm(x, r, g, b)) < TOL
 
 
+def test_add_layer_norm_above_64_kb_of_lds_matches_oracle(pkg, oracle):
+    """512 channels on the 32-step tile are 68 KB of dynamic LDS: the launch has to raise the kernel's limit first (once per device). Then the
+    same kernel under 64 KB."""
+    rng = np.random.default_rng(5)
+    for C in (512, 192):
+        x, r = rnd(rng, 1, C, 8), rnd(rng, 1, C, 8)
+        g, b = rnd(rng, C) + 1, rnd(rng, C)
+        assert rel_err(pkg.op_add_layer_norm(x, r, g, b), oracle.add_layer_norm(x, r, g, b)) < TOL, C
+
+
+def test_rel_attention_valu_kernel_above_64_kb_of_lds_matches_oracle(pkg, oracle):
+    """A head size that is no multiple of 16 takes the kernel without matrix cores; 900 tokens at head size 24 are 66 KB of dynamic LDS there
+    (limit raised once per device). Then the same kernel under 64 KB."""
+    rng = np.random.default_rng(6)
+    heads, hd, w = 2, 24, 4
+    for T in (900, 100):
+        q, k, v = rnd(rng, 1, heads * hd, T, scale=0.3), rnd(rng, 1, heads * hd, T, scale=0.3), rnd(rng, 1, heads * hd, T)
+        rk, rv = rnd(rng, 2 * w + 1, hd, scale=0.1), rnd(rng, 2 * w + 1, hd, scale=0.1)
+        og = pkg.op_rel_attention(q, k, v, rk, rv, heads, w, lens=np.array([T], np.int32))
+        assert rel_err(og, oracle.rel_attention(q, k, v, rk, rv, heads, w, lens=np.array([T], np.int32))) < TOL, T
+
+
 def test_mfma_16x16x4_is_the_same_sequential_fmaf_chain_as_32x32x2(tmp_path):
     """The hardware fact conv_lat16_kernel stands on (small grids): a K chain of v_mfma_f32_16x16x4_f32 is bit for bit the chain of
     v_mfma_f32_32x32x2_f32 and the scalar fmaf chain in k order — tools/mfma_bits.hip, built and run here (1,024 outputs x 256 products);

@@ -47,7 +47,7 @@ def test_the_engine_labels_use_the_same_tile_tags():
     """The profiler label of the streaming upsamplers comes from convt16_stream_tag (same place that picks the instantiation)."""
     src = open(os.path.join(ROOT, "vits.cpp_amd", "csrc", "engine_vocoder.cpp")).read()
     assert "convt16_stream_tag(U.up, tag, sizeof(tag))" in src
-    ct = open(os.path.join(ROOT, "vits.cpp_amd", "csrc", "convt16.hip")).read()
+    ct = open(os.path.join(ROOT, "vits.cpp_amd", "csrc", "launch_plan.cpp")).read()  # (plan_convt16: the choice and its tag)
     assert '"SL%d"' in ct and '"S%d.%d.%d"' in ct
 
 

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <vector>
 #include "../vits.cpp_amd/csrc/misc_kernels.hip"
+#include "../vits.cpp_amd/csrc/launch_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 // fragment order of conv_mfma.hip pack_conv_weights for a 1x1 conv (EPI_STD)
 static std::vector<float> pack1x1(const float* w, int cout, int cin, int* mtiles, int* nchunks) {

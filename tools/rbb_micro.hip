@@ -19,6 +19,7 @@
 #define B_ 64
 #endif
 #include "../vits.cpp_amd/csrc/rbblock16.hip"
+#include "../vits.cpp_amd/csrc/launch_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 
 int main() {

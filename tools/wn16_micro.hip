@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <vector>
 #include "../vits.cpp_amd/csrc/wavenet32.hip"
+#include "../vits.cpp_amd/csrc/launch_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 #ifndef L_
 #define L_ 225

@@ -247,23 +247,16 @@ hipError_t launch_align_mas(const AlignCall& c, hipStream_t s) {
     const size_t lds = (in_lds ? (size_t)words * c.lmax * 8 : 0) + (size_t)2 * words * sizeof(float);
     unsigned long long* gb = in_lds ? nullptr : c.bits;
     const int64_t gb_bs = (int64_t)words * c.lmax;
-#define VITS_ALIGN_MAS(N)                                                                                                                                      \
-    do {                                                                                                                                                       \
-        if (lds > 64 * 1024) {                                                                                                                                 \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&align_mas_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (ea != hipSuccess) return ea;                                                                                                                   \
-        }                                                                                                                                                      \
-        VITS_KLAUNCH(align_mas_kernel<N>, dim3(c.batch), dim3(threads), lds, s, c.logp, c.t_stride, c.l_stride, c.tlens, c.frames, gb, gb_bs, c.dur,           \
-                     c.dur_stride, c.path, c.l_stride, c.score);                                                                                               \
-    } while (0)
+#define VITS_ALIGN_MAS(N)                                                                                                                              \
+    return launch_lds<&align_mas_kernel<N>>(dim3(c.batch), dim3(threads), lds, s, c.logp, c.t_stride, c.l_stride, c.tlens, c.frames, gb, gb_bs, c.dur, c.dur_stride, c.path, \
+                                            c.l_stride, c.score)
     switch (tpl) {
-        case 1: VITS_ALIGN_MAS(1); break;
-        case 2: VITS_ALIGN_MAS(2); break;
-        case 3: VITS_ALIGN_MAS(3); break;
-        default: VITS_ALIGN_MAS(4); break;
+        case 1: VITS_ALIGN_MAS(1);
+        case 2: VITS_ALIGN_MAS(2);
+        case 3: VITS_ALIGN_MAS(3);
+        default: VITS_ALIGN_MAS(4);
     }
 #undef VITS_ALIGN_MAS
-    return hipGetLastError();
 }
 
 }  // namespace vits

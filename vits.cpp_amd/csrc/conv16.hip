@@ -593,19 +593,12 @@ template <int KT, int DIL, int EPI>
 static hipError_t launch_tile16(const Conv16Plan& pl, const Conv16Params& p, hipStream_t s) {
     dim3 grid(pl.gx, pl.gy, pl.gz);
     const size_t lds = pl.lds;
-#define VITS_LAUNCH16(WM, WN, MR, NR)                                                                                                \
-    do {                                                                                                                             \
-        static BigLdsOnce big_lds_set; \
-        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv16_kernel<KT, DIL, WM, WN, MR, NR, EPI, kBF>), lds)) return ea; \
-        VITS_KLAUNCH((conv16_kernel<KT, DIL, WM, WN, MR, NR, EPI, kBF>), grid, dim3(320), lds, s, p);                          \
-    } while (0)
     // (the arms an epilogue lacks are the backstop: plan_conv16 asks conv16_tile_exists before it chooses)
 #define VITS_TILE16_ARM(LABEL, T)                                      \
     LABEL:                                                             \
         if constexpr (conv16_tile_exists(EPI, DIL, T)) {               \
             constexpr TileShape ts = tile16_shape(T);                  \
-            VITS_LAUNCH16(ts.wm, ts.wn, ts.mr, ts.nr);                 \
-            break;                                                     \
+            return launch_lds<&conv16_kernel<KT, DIL, ts.wm, ts.wn, ts.mr, ts.nr, EPI, kBF>>(grid, dim3(320), lds, s, p); \
         } else {                                                       \
             return hipErrorInvalidValue;                               \
         }
@@ -619,8 +612,6 @@ static hipError_t launch_tile16(const Conv16Plan& pl, const Conv16Params& p, hip
         VITS_TILE16_ARM(default, 4)
     }
 #undef VITS_TILE16_ARM
-#undef VITS_LAUNCH16
-    return hipGetLastError();
 }
 
 #define VITS_DISPATCH16(NAME) hipError_t NAME(int epi16, int kt, const Conv16Plan& pl, const Conv16Params& p, hipStream_t s)

@@ -246,10 +246,7 @@ __global__ __launch_bounds__(WM * 64) void conv16_lat_group_kernel(const Conv16L
 // (which convs take these kernels, block shape, pitch, grid and LDS bytes: conv_plan.cpp)
 template <int KT, int C, int WM, int NR, bool BF>
 static hipError_t launch_c16l(const Conv16LatParams& p, const Conv16LatPlan& l, hipStream_t s) {
-    static BigLdsOnce big;
-    if (hipError_t e = big.raise(reinterpret_cast<const void*>(&conv16_lat_kernel<KT, C, WM, NR, BF>), l.lds)) return e;
-    VITS_KLAUNCH((conv16_lat_kernel<KT, C, WM, NR, BF>), dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, s, p);
-    return hipGetLastError();
+    return launch_lds<&conv16_lat_kernel<KT, C, WM, NR, BF>>(dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, s, p);
 }
 
 static Conv16LatParams c16l_params(const PackedConv& w, const Conv16Call& c, int nr) {
@@ -298,7 +295,7 @@ hipError_t launch_conv16_lat_group(const PackedConv* const* w, const Conv16Call*
     if (!conv16_lat_group_wanted(w, c)) return hipErrorInvalidValue;
     Conv16LatGroupParams gp;
     // (the LDS of the widest member, k = 11; every member keeps its own pitch)
-    const Conv16LatPlan l = plan_conv16_lat(256, 256, 11, c[0].dil, kernel_knobs().lat16h_group_shape, c[0].t_out, 3 * c[0].batch);
+    const Conv16LatPlan l = plan_conv16_lat_group(c[0].dil, c[0].t_out, c[0].batch);
     const int wm = l.wm, nr = l.nr;
     for (int i = 0; i < 3; ++i) gp.m[i] = c16l_params(*w[i], c[i], nr);
     const size_t lds = l.lds;

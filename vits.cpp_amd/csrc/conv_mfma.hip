@@ -1228,12 +1228,7 @@ static hipError_t launch_lat16(const PackedConv& w, const ConvPlan& pl, const Co
     p.l16_fill4 = (reinterpret_cast<uintptr_t>(p.x) & 15) == 0 && (p.x_cs & 3) == 0 && (p.x_bs & 3) == 0;
     const size_t lds = pl.lds;
     dim3 grid(pl.gx, pl.gy, pl.gz);
-#define VITS_L16(E, PP)                                                                                                                          \
-    do {                                                                                                                                         \
-        static BigLdsOnce big;                                                                                \
-        if (hipError_t e = big.raise(reinterpret_cast<const void*>(&conv_lat16_kernel<E, PP>), lds)) return e;                    \
-        VITS_KLAUNCH((conv_lat16_kernel<E, PP>), grid, dim3(256), lds, s, p);                                                                    \
-    } while (0)
+#define VITS_L16(E, PP) return launch_lds<&conv_lat16_kernel<E, PP>>(grid, dim3(256), lds, s, p)
     if (w.epi == EPI_GATE) {
         if (pitch != 24) return hipErrorInvalidValue;
         VITS_L16(EPI_GATE, 24);
@@ -1245,7 +1240,6 @@ static hipError_t launch_lat16(const PackedConv& w, const ConvPlan& pl, const Co
         VITS_L16(EPI_STD, 72);
     }
 #undef VITS_L16
-    return hipGetLastError();
 }
 #endif  // VITS_CONV_PART == 0
 
@@ -1338,19 +1332,12 @@ template <int KT, int DIL, bool DB, int EPI>
 static hipError_t launch_tile(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
     dim3 grid(pl.gx, pl.gy, pl.gz);
     const size_t lds = pl.lds;
-#define VITS_LAUNCH(WM, WN, MR, NR)                                                                                                   \
-    do {                                                                                                                              \
-        static BigLdsOnce big_lds_set; /* (atomic: distinct model handles may launch from distinct threads) */ \
-        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv_mfma_kernel<KT, DIL, DB, WM, WN, MR, NR, EPI>), lds)) return ea; \
-        VITS_KLAUNCH((conv_mfma_kernel<KT, DIL, DB, WM, WN, MR, NR, EPI>), grid, dim3(DB ? 320 : 256), lds, s, p);                             \
-    } while (0)
     // (the arms an (epilogue, taps, dilation) lacks are the backstop: plan_conv asks conv_tile_exists before it chooses)
 #define VITS_TILE_ARM(LABEL, T)                                                      \
     LABEL:                                                                           \
         if constexpr (conv_tile_exists(EPI, KT, DIL, DB, T)) {                       \
             constexpr TileShape ts = tile_shape(T);                                  \
-            VITS_LAUNCH(ts.wm, ts.wn, ts.mr, ts.nr);                                 \
-            break;                                                                   \
+            return launch_lds<&conv_mfma_kernel<KT, DIL, DB, ts.wm, ts.wn, ts.mr, ts.nr, EPI>>(grid, dim3(DB ? 320 : 256), lds, s, p); \
         } else {                                                                     \
             return hipErrorInvalidValue;                                             \
         }
@@ -1363,8 +1350,6 @@ static hipError_t launch_tile(const ConvPlan& pl, const ConvParams& p, hipStream
         VITS_TILE_ARM(default, TILE_32x64)
     }
 #undef VITS_TILE_ARM
-#undef VITS_LAUNCH
-    return hipGetLastError();
 }
 
 // one launcher per tap count (see VITS_CONV_PART): the instantiation plan_conv named — compile-time dilation (conv_template_dil) and producer-wave variant
@@ -1418,17 +1403,11 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
         g.zend[slot] = z;
     }
     dim3 grid((ncols_max + 127) / 128, w[0]->mtiles_used / 4, z);
-#define VITS_GROUP_LAUNCH(D)                                                                                                              \
-    do {                                                                                                                                  \
-        static BigLdsOnce big_lds_set; \
-        if (hipError_t ea = big_lds_set.raise(reinterpret_cast<const void*>(&conv_group_kernel<D>), lds)) return ea; \
-        VITS_KLAUNCH((conv_group_kernel<D>), grid, dim3(320), lds, s, g);                                                           \
-    } while (0)
+#define VITS_GROUP_LAUNCH(D) return launch_lds<&conv_group_kernel<D>>(grid, dim3(320), lds, s, g)
     if (c[0].dil == 1) VITS_GROUP_LAUNCH(1);
     else if (c[0].dil == 3) VITS_GROUP_LAUNCH(3);
     else VITS_GROUP_LAUNCH(5);
 #undef VITS_GROUP_LAUNCH
-    return hipGetLastError();
 }
 #endif
 

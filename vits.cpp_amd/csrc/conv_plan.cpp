@@ -186,6 +186,7 @@ Conv16Plan plan_conv16(const PackedConv& w, const Conv16Call& c) {
 }
 
 // ---- conv16_lat.hip ------------------------------------------------------------------------------------------------------------------------
+Conv16LatPlan plan_conv16_lat_group(int dil, int tmax, int batch) { return plan_conv16_lat(256, 256, 11, dil, kernel_knobs().lat16h_group_shape, tmax, 3 * batch); }
 Conv16LatPlan plan_conv16_lat(int cin, int cout, int kt, int dil, int shape, int tmax, int nz) {
     Conv16LatPlan l;
     l.wm = shape / 10, l.nr = shape % 10;

@@ -139,6 +139,7 @@ struct Conv16LatPlan {
     size_t lds = 0;
 };
 Conv16LatPlan plan_conv16_lat(int cin, int cout, int kt, int dil, int shape, int tmax, int nz);
+Conv16LatPlan plan_conv16_lat_group(int dil, int tmax, int batch);  // the grouped launch of a C = 256 stage's k = 3, 7, 11 convs: the LDS of the widest member (VITS_LAT16H_GROUP_SHAPE)
 struct Conv16Plan {
     bool ok = false;
     bool lat = false;  // conv16_lat_kernel (profile tile tag T7): `l` says how; otherwise conv16_kernel on `tile`

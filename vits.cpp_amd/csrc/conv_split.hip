@@ -356,13 +356,7 @@ hipError_t launch_conv_split(const PackedConv& w, const ConvCall& c, hipStream_t
 #define VITS_CS(K, D, M)                                                                                                                          \
     do {                                                                                                                                          \
         constexpr size_t lds = (size_t)2 * 12 * ((128 * (4 / M) + (K - 1) * D + 7) / 8 * 8) * 16;                                                 \
-        static BigLdsOnce big;                                                                                                                    \
-        if (lds > 64 * 1024 && big.needed()) {                                                                                                    \
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_split_kernel<K, D, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e; \
-            big.done();                                                                                                                           \
-        }                                                                                                                                         \
-        VITS_KLAUNCH((conv_split_kernel<K, D, M>), grid, dim3(320), lds, s, p);                                                                   \
-        return hipGetLastError();                                                                                                                 \
+        return launch_lds<&conv_split_kernel<K, D, M>>(grid, dim3(320), lds, s, p);                                                               \
     } while (0)
 #define VITS_CS_D(K, M)                    \
     do {                                   \

@@ -55,8 +55,8 @@ struct ConvT16Params {
 // RS: weight-fragment ring (8 or 16 slots; 2 c_in / 16 must be a multiple of it)
 template <int NR, int CSPLIT, int RS, bool BF>
 __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) {
-    constexpr int BN = NR * CSPLIT * 32;       // input positions (GEMM columns) per block
-    constexpr int XW = (BN + 1 + 7) / 8 * 8;   // slots per group row: column 0 = position t0 - 1 (tap 1 reads x[q - 1])
+    constexpr int BN = convt16_bn(NR, CSPLIT);  // input positions (GEMM columns) per block
+    constexpr int XW = convt16_xw(BN);         // slots per group row: column 0 = position t0 - 1 (tap 1 reads x[q - 1])
     extern __shared__ __attribute__((aligned(16))) int4v xs[];  // [cin/8][XW]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void convt16_kernel(const ConvT16Params p) 
 // Work units of a block: (channel block, phase half, 64-position column pair), dealt to the four waves round robin.
 template <int BN, bool BF>
 __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Params p) {
-    constexpr int XW = (BN + 1 + 7) / 8 * 8;
+    constexpr int XW = convt16_xw(BN);
     constexpr int NR = 2, PH = 4;
     extern __shared__ __attribute__((aligned(16))) int4v xs[];  // [cin/8][XW]
 
@@ -389,113 +389,22 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-bool convt16_stream_supported(const PackedConv& w) {
-    const bool off = kernel_knobs().no_convt16s;
-    // (VITS_CONVT16S_ALL=1: the one-row-tile-at-a-time kernel also for stride 8 — the slow first version, kept for the comparison)
-    const bool all = kernel_knobs().convt16s_all;
-    const bool no_lines = kernel_knobs().no_convt16l;  // (the four-phase variant for strides that are multiples of 4)
-    if (off || w.epi != EPI_CONVT || w.kt != 2 || !w.wp16 || w.cin % 64 != 0 || w.cout % 32 != 0 || w.rows % 32 != 0 || w.cin > 512) return false;
-    if (w.rows <= 128 || all) return true;
-    return !no_lines && w.ct_stride % 4 == 0;
-}
-
-template <int NR, int CSPLIT, int RS, bool BF>
-static hipError_t launch_ct(const ConvT16Params& p, int ncols_max, int batch, hipStream_t s) {
-    constexpr int BN = NR * CSPLIT * 32, XW = (BN + 1 + 7) / 8 * 8;
-    const size_t lds = (size_t)(p.cin / 8) * XW * 16;
-    static BigLdsOnce big_lds_set;
-    if (lds > 64 * 1024 && big_lds_set.needed()) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt16_kernel<NR, CSPLIT, RS, BF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return ea;
-        big_lds_set.done();
-    }
-    dim3 grid((ncols_max + BN - 1) / BN, batch);
-    VITS_KLAUNCH((convt16_kernel<NR, CSPLIT, RS, BF>), grid, dim3(256), lds, s, p);
-    return hipGetLastError();
-}
-
-// which instantiation serves a transposed conv (one place: the launch below and the profiler label of the engine both ask here).
-// convt16_lines_kernel<BN>: four phases per wave, for row counts above 128 with a stride that is a multiple of 4; 128 positions per block,
-// 64 when c_in = 512 (LDS for two blocks per CU). convt16_kernel<NR, CSPLIT, RS>: 128 positions per block; 64 when the input tile of 128
-// would not leave room for two blocks per CU (c_in = 512); 256 positions with two waves per row tile when there are only two row tiles (the
-// last upsampler: 64 rows); sixteen ring slots where the step count allows.
-namespace {
-struct CtChoice {
-    int lines_bn = 0, nr = 0, csplit = 0, rs = 0;
-};
-CtChoice ct_choice(const PackedConv& w) {
-    const bool all_s = kernel_knobs().convt16s_all;
-    CtChoice c;
-    if (w.rows > 128 && w.ct_stride % 4 == 0 && !all_s) {
-        c.lines_bn = w.cin > 256 ? 64 : 128;
-        return c;
-    }
-    c.rs = w.cin % 128 == 0 ? 16 : 8;
-    if (w.rows / 32 <= 2) c.nr = 4, c.csplit = 2;
-    else if (w.cin > 256) c.nr = 2, c.csplit = 1;
-    else c.nr = 4, c.csplit = 1;
-    if (const int ov = kernel_knobs().convt16_r128; ov && w.rows == 128) {  // (developer override: same bits, another block shape)
-        c.nr = ov / 100, c.csplit = ov / 10 % 10, c.rs = (ov % 10) ? 16 : 8;
-        if (c.rs == 16 && w.cin % 128 != 0) c.rs = 8;
-    }
-    return c;
-}
-}  // namespace
-
 hipError_t launch_convt16_stream(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s) {
-    if (!convt16_stream_supported(w) || !c.yg) return hipErrorInvalidValue;
+    const ConvT16Plan l = plan_convt16(w, c.batch, c.t_in);
+    if (!l.ok || !w.wp16 || !c.yg) return hipErrorInvalidValue;
     ConvT16Params p;
-    p.x = c.x.p;
-    p.x_bs = c.x.bs;
-    p.x_ts = c.x.ts;
-    p.wp = w.wp16;
-    p.bias = w.bias;
-    p.len_in = c.len_in;
-    p.len_out = c.len_out;
-    p.t_in = c.t_in;
-    p.t_out = c.t_out;
-    p.cin = w.cin;
-    p.cout = w.cout;
-    p.rows = w.rows;
-    p.s = w.ct_stride;
-    p.crop = c.ct_crop;
-    p.yg = c.yg;
-    p.g_bs = c.g_bs;
-    p.g_ts = c.g_ts;
-    p.y16 = c.y16.p;
-    p.y16_bs = c.y16.bs;
-    p.y16_ts = c.y16.ts;
-    p.y16_slope = c.y16_slope;
+    p.x = c.x.p, p.x_bs = c.x.bs, p.x_ts = c.x.ts, p.wp = w.wp16, p.bias = w.bias, p.len_in = c.len_in, p.len_out = c.len_out, p.t_in = c.t_in;
+    p.t_out = c.t_out, p.cin = w.cin, p.cout = w.cout, p.rows = w.rows, p.s = w.ct_stride, p.crop = c.ct_crop, p.yg = c.yg, p.g_bs = c.g_bs;
+    p.g_ts = c.g_ts, p.y16 = c.y16.p, p.y16_bs = c.y16.bs, p.y16_ts = c.y16.ts, p.y16_slope = c.y16_slope;
     const bool bf = arith == VITS_ARITH_BF16;
-    const int ncols_max = c.t_in + 1;
-    const CtChoice ch = ct_choice(w);
-    if (ch.lines_bn) {
-        // four phases per wave: whole output lines per store burst. 128 positions per block, 64 when c_in = 512 (LDS for two blocks per CU)
-        auto go = [&](auto bn_c, auto bf_c) -> hipError_t {
-            constexpr int BN = decltype(bn_c)::value;
-            constexpr bool BFv = decltype(bf_c)::value;
-            constexpr int XW = (BN + 1 + 7) / 8 * 8;
-            const size_t lds = (size_t)(p.cin / 8) * XW * 16;
-            static BigLdsOnce big_lds_set;
-            if (lds > 64 * 1024 && big_lds_set.needed()) {
-                hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt16_lines_kernel<BN, BFv>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (ea != hipSuccess) return ea;
-                big_lds_set.done();
-            }
-            const int64_t tiles = (int64_t)((ncols_max + BN - 1) / BN) * c.batch;
-            const int nunits = (p.cout >> 5) * (p.s / 4) * (BN / 64);
-            int zsplit = 1;
-            if (tiles <= kernel_knobs().convt16_split_max) zsplit = nunits >= 16 ? 4 : (nunits >= 8 ? 2 : 1);
-            dim3 grid((ncols_max + BN - 1) / BN, c.batch, zsplit);
-            VITS_KLAUNCH((convt16_lines_kernel<BN, BFv>), grid, dim3(256), lds, s, p);
-            return hipGetLastError();
-        };
-        if (ch.lines_bn == 64) return bf ? go(std::integral_constant<int, 64>{}, std::true_type{}) : go(std::integral_constant<int, 64>{}, std::false_type{});
-        return bf ? go(std::integral_constant<int, 128>{}, std::true_type{}) : go(std::integral_constant<int, 128>{}, std::false_type{});
-    }
-#define VITS_CT(NR, CS, RS)                                                                                            \
-    if (ch.nr == NR && ch.csplit == CS && ch.rs == RS)                                                                 \
-        return bf ? launch_ct<NR, CS, RS, true>(p, ncols_max, c.batch, s) : launch_ct<NR, CS, RS, false>(p, ncols_max, c.batch, s)
+    const dim3 grid(l.gx, l.gy, l.gz), block(l.block);
+    // four phases per wave: whole output lines per store burst
+    if (l.lines_bn == 64) return bf ? launch_lds<&convt16_lines_kernel<64, true>>(grid, block, l.lds, s, p) : launch_lds<&convt16_lines_kernel<64, false>>(grid, block, l.lds, s, p);
+    if (l.lines_bn) return bf ? launch_lds<&convt16_lines_kernel<128, true>>(grid, block, l.lds, s, p) : launch_lds<&convt16_lines_kernel<128, false>>(grid, block, l.lds, s, p);
+#define VITS_CT(NR, CS, RS)                                                 \
+    static_assert(convt16_exists(0, NR, CS, RS), "the planner's predicate"); \
+    if (l.nr == NR && l.csplit == CS && l.rs == RS)                         \
+        return bf ? launch_lds<&convt16_kernel<NR, CS, RS, true>>(grid, block, l.lds, s, p) : launch_lds<&convt16_kernel<NR, CS, RS, false>>(grid, block, l.lds, s, p)
     VITS_CT(4, 2, 16);
     VITS_CT(4, 2, 8);
     VITS_CT(2, 1, 16);
@@ -504,12 +413,6 @@ hipError_t launch_convt16_stream(const PackedConv& w, const Conv16Call& c, int a
     VITS_CT(4, 1, 8);
 #undef VITS_CT
     return hipErrorInvalidValue;
-}
-
-void convt16_stream_tag(const PackedConv& w, char* buf, size_t cap) {
-    const CtChoice ch = ct_choice(w);
-    if (ch.lines_bn) std::snprintf(buf, cap, "SL%d", ch.lines_bn);
-    else std::snprintf(buf, cap, "S%d.%d.%d", ch.nr, ch.csplit, ch.rs);
 }
 
 }  // namespace vits

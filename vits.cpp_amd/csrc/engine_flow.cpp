@@ -267,12 +267,12 @@ int Engine::run_coupling(Call& c, bool forward) {
                     flow_couple16_supported(H, F / 2, hp.wn_k, hp.wn_rate, hp.wn_layers, flow_[i].pre, flow_[i].in_layers.data(), flow_[i].res_skip.data(), post_of(i));
     if (all_fused && !prof.on && side_[0] && B >= 2 && knobs.flow_chains > 1) {
         int64_t blocks = 0;
-        for (int b = 0; b < B; ++b) blocks += (frames[b] + 47) / 48;
-        if (blocks > knobs.flow_chain_min_blocks && blocks > kernel_knobs().flow_narrow_max) {
+        for (int b = 0; b < B; ++b) blocks += flow_wide_blocks(frames[b]);
+        if (blocks > knobs.flow_chain_min_blocks && !flow_couple16_narrow(blocks)) {
             // equal shares of the blocks (by utterance, in order)
             int64_t run = 0;
             int cut = 0;
-            while (cut < B - 1 && 2 * (run + (frames[cut] + 47) / 48) <= blocks) run += (frames[cut++] + 47) / 48;
+            while (cut < B - 1 && 2 * (run + flow_wide_blocks(frames[cut])) <= blocks) run += flow_wide_blocks(frames[cut++]);
             if (cut >= 1) {
                 chains = 2;
                 chain_b0[1] = cut;

@@ -70,8 +70,6 @@ struct RoctxRange {
         if (e__ != hipSuccess) return e__; \
     } while (0)
 
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 static inline TensorRef make_ref(float* p, int channels, int stride) {
     TensorRef t;
     t.p = p;

@@ -49,8 +49,7 @@ hipError_t Engine::run_dds(const DdsW& d, TensorRef x, TensorRef y, TensorRef p,
 // Small grids (batch 1, a few short utterances): every DDS layer on the 16-token latency kernel, the per-token ops in front of and behind the block
 // inside its first / last layer (stage1_lat.hip). Same floats as run_dds + the separate launches (tests/test_gpu_edge_and_scale.py).
 bool Engine::dds_lat_ok(const DdsW& d, const DdsEnds& e, int batch, int tmax) const {
-    if (knobs.kernel.no_dds_lat || knobs.no_dds_fuse || arith_now_ != VITS_ARITH_F32 || hp.dds_layers < 2) return false;
-    if ((int64_t)batch * ((tmax + 15) / 16) > knobs.kernel.dds_lat_max_blocks) return false;
+    if (knobs.no_dds_fuse || arith_now_ != VITS_ARITH_F32 || hp.dds_layers < 2 || !dds_lat_grid_ok(batch, tmax)) return false;
     for (int i = 0, dl = 1; i < hp.dds_layers; ++i, dl *= hp.dp_k)
         if (!dds_layer_lat_supported(d.pw[i], hp.hidden, hp.dp_k, dl)) return false;
     auto conv_ok = [&](const PackedConv* c, bool square) {

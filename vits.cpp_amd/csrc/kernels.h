@@ -43,7 +43,7 @@ struct KernelKnobs {
     int ln_tw = 32;              // VITS_LN_TW=64: LayerNorm tiles of 64 time steps (sixteen waves)
     bool rbb_c128 = true;        // VITS_RBB_C128=0: C = 128, k = 3 resblocks as fused pairs instead of rbblock16
     int rbb_c64k11 = -1;         // VITS_RBB_C64K11: C = 64, k = 11 resblocks through rbblock16 as well: 1 always, 0 never (three fused pairs), -1 where the grid is large enough for segments of tiles (VITS_RBB_STREAM_*)
-    int rbb_stream_tiles = -1;   // VITS_RBB_STREAM_TILES: tiles a block of rbblock16 walks with the left halo taken from the previous tile (-1: per shape, see launch_rbb; 0 / 1: always one tile per block, both halos recomputed; N: N for every shape)
+    int rbb_stream_tiles = -1;   // VITS_RBB_STREAM_TILES: tiles a block of rbblock16 walks with the left halo taken from the previous tile (-1: per shape, see plan_rbblock16; 0 / 1: always one tile per block, both halos recomputed; N: N for every shape)
     int rbb_stream_min_blocks = 1536;  // VITS_RBB_STREAM_MIN_BLOCKS: ... while the segments still number at least this many blocks (two rounds of 3 x 256)
     int fuse16_maxc = 256;       // VITS_FUSE16_MAXC: widest stage whose 16-bit conv pairs are fused
     bool fuse32_c128 = true;     // VITS_FUSE32_C128=0: fp32 k = 3 pairs at C = 128 as two launches
@@ -155,10 +155,11 @@ struct BigLdsOnce {
     }
     bool needed() const { return !(mask.load(std::memory_order_acquire) & bit()); }
     void done() { mask.fetch_or(bit(), std::memory_order_release); }
-    // before a launch with `lds` bytes of dynamic LDS: raise the kernel's limit to the CU's 160 KB, the first time on this device that it needs more than 64 KB
-    hipError_t raise(const void* kernel, size_t lds) {
+    // before a launch with `lds` bytes of dynamic LDS: raise the kernel's limit to `limit`, the first time on this device that it needs more than 64 KB.
+    // limit: the CU's 160 KB minus the kernel's static __shared__ bytes
+    hipError_t raise(const void* kernel, size_t lds, int limit = 160 * 1024) {
         if (lds <= 64 * 1024 || !needed()) return hipSuccess;
-        if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
+        if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit)) return e;
         done();
         return hipSuccess;
     }
@@ -182,6 +183,16 @@ inline thread_local LaunchTimer vits_launch_timer;
         else                                                                                                        \
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                      \
     } while (0)
+
+// THE way to launch a kernel with dynamic LDS, launch_lds<&kernel<...>>(grid, block, lds, stream, args...): raises the kernel's limit the first time on a
+// device (BigLdsOnce, one per instantiation). LIMIT: see BigLdsOnce::raise
+template <auto Kernel, int LIMIT = 160 * 1024, class... A>
+inline hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    static BigLdsOnce once;
+    if (hipError_t e = once.raise(reinterpret_cast<const void*>(Kernel), lds, LIMIT)) return e;
+    VITS_KLAUNCH(Kernel, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
 
 #ifdef __HIPCC__
 // The WaveNet gate tanh(a) * sigmoid(s) (vits.cpp:442-450) of every gated-conv epilogue (conv_mfma.hip, conv16.hip, wavenet32.hip), libm's
@@ -620,3 +631,4 @@ hipError_t launch_resample(const ResampleCall& c, hipStream_t s);
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
+#include "launch_plan.h"  // launch policy and geometry of the fused kernels: vocoder resblocks and upsamplers, the flow, attention / LayerNorm / DDS

@@ -79,7 +79,7 @@ hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const flo
 // here the 2w+1 relative logits are 9 extra dot products per query.
 // One block = (utterance, head, 16 queries); scores for the 16 queries x T keys live in LDS.
 // ---------------------------------------------------------------------------------------------------------
-constexpr int ATT_Q = 16;
+constexpr int ATT_Q = kAttQ;  // (launch_plan.h: the planner reads the same)
 // Threads per block: 1024 (16 waves) on small grids — at batch 1 a launch has ~34 blocks and every phase is a chain of LDS / memory
 // latencies that only more waves hide — and 256 on large ones (16-wave blocks pack worse: 73 -> 107 us per launch at batch 64).
 // Both give the same bits: scores and outputs are per-element sums in a fixed order, and the softmax always runs on 16 lanes per query.
@@ -314,7 +314,6 @@ __global__ __launch_bounds__(ATT_THREADS) void rel_attention_kernel(const float*
 // LDS: Q^T [hd][16] | q.Ek [16][nrel] | scores [16][lp], lp = 4 mod 64 (conflict-free A reads of P).
 // ---------------------------------------------------------------------------------------------------------
 
-__host__ __device__ inline int att_lp(int len) { return (len + 63) / 64 * 64 + 4; }  // >= len + 4, = 4 (mod 64)
 
 #ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/att_micro.hip): per-block phase stamps, 100 MHz clock
 __device__ unsigned long long vits_att_phase[8 * 65536];
@@ -632,74 +631,33 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
 
 hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const float* rel_k, const float* rel_v, TensorRef out, const int* lens, int batch,
                                 int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs) {
-    const bool valu_only = kernel_knobs().att_valu;
-    // matrix-core version. The number of waves (= how the key tiles and the d tiles are dealt out) does not change a single sum, so it may
-    // depend on the launch: four waves while two or more blocks fit the LDS of a CU (up to ~1200 tokens: 1024 ids 0.178 ms against 0.222
-    // with six waves), eight once the scores of a block leave room for one block only (2049 tokens: 0.87 against 1.29 ms with four)
-    const bool v_aligned = (v.cs & 3) == 0 && (v.bs & 3) == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0;
-    if (!valu_only && (head_dim & 15) == 0 && head_dim <= 128) {
-        const size_t ldsm = sizeof(float) * ((((size_t)ATT_Q * head_dim + ATT_Q * (2 * window + 1) + 3) & ~(size_t)3) + (size_t)ATT_Q * att_lp(tmax));
-        if (ldsm <= 160 * 1024) {
-            dim3 gridm((tmax + ATT_Q - 1) / ATT_Q, heads, batch);
-            const int nw_env = kernel_knobs().att_nw;
-            int nw = 2 * ldsm > 160 * 1024 ? 8 : 4;
-            // latency-bound launches (at most 128 blocks: up to eight 128-token utterances): eight waves deal the key tiles and the d tiles out one per wave
-            // (per-block stamps at 128 tokens, tools/att_micro.hip: P V 5.0 -> 3.0 us, block life 15.2 -> 13.9; batch 1 / 2 / 4 / 8: -1 ... -3 % per call, round 6)
-            if ((int64_t)gridm.x * gridm.y * gridm.z <= 128) nw = 8;
-            if (nw_env == 4 || nw_env == 8) nw = nw_env;
-#define VITS_ATTM_LAUNCH(NW, MS, SH)                                                                                                                   \
-    do {                                                                                                                                         \
-        if (ldsm > 64 * 1024) {                                                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rel_attention_mfma_kernel<NW, MS, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm); \
-            if (e != hipSuccess) return e;                                                                                                       \
-        }                                                                                                                                        \
-        VITS_KLAUNCH((rel_attention_mfma_kernel<NW, MS, SH>), gridm, dim3(64 * NW), ldsm, s, q.p, q.bs, q.cs, k.p, k.bs, k.cs, v.p, v.bs, v.cs, rel_k, rel_v, out.p, \
-                           out.bs, out.cs, lens, head_dim, tmax, window, q_scale, v_aligned ? 1 : 0, tabs.exp);                                            \
-    } while (0)
-#define VITS_ATTM_LAUNCH_LAT()                                                                                                                          \
-    do {                                                                                                                                         \
-        if (ldsm > 64 * 1024) {                                                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rel_attention_mfma_kernel<8, 24, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm); \
-            if (e != hipSuccess) return e;                                                                                                       \
-        }                                                                                                                                        \
-        VITS_KLAUNCH((rel_attention_mfma_kernel<8, 24, false, true>), gridm, dim3(512), ldsm, s, q.p, q.bs, q.cs, k.p, k.bs, k.cs, v.p, v.bs, v.cs, rel_k, rel_v, out.p, \
-                           out.bs, out.cs, lens, head_dim, tmax, window, q_scale, v_aligned ? 1 : 0, tabs.exp);                                            \
-    } while (0)
-            const int short_max = kernel_knobs().att_short;  // tokens; 0 disables the short variant
-            // (the long variants keep their arrays at 32 k-steps: sized for 24 the four-wave kernel measured 0.22 against 0.18 ms at 1024 tokens)
-            const bool lat = !kernel_knobs().no_att_lat && nw == 8 && head_dim <= 96 && (int64_t)gridm.x * gridm.y * gridm.z <= 128;
-            if (lat) VITS_ATTM_LAUNCH_LAT();
-            else if (nw == 4 && head_dim <= 96 && tmax <= short_max) VITS_ATTM_LAUNCH(4, 24, true);
-            else if (nw == 4) VITS_ATTM_LAUNCH(4, 32, false);
-            else VITS_ATTM_LAUNCH(8, 32, false);
+    // (which kernel, how many waves, which variant, LDS: plan_rel_attention, launch_plan.cpp)
+    const AttentionPlan l = plan_rel_attention(batch, heads, head_dim, tmax, window);
+    if (!l.ok) return hipErrorInvalidValue;
+    const dim3 grid(l.gx, l.gy, l.gz), block(l.block);
+    if (l.mfma) {
+        const bool v_aligned = (v.cs & 3) == 0 && (v.bs & 3) == 0 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0;
+#define VITS_ATTM_LAUNCH(NW, MS, SH, LAT)                                                                                                                  \
+    static_assert(att_mfma_exists(NW, MS, SH, LAT), "the planner's predicate");                                                                            \
+    if (l.nw == NW && l.maxs == MS && l.sh == SH && l.lat == LAT)                                                                                          \
+        return launch_lds<&rel_attention_mfma_kernel<NW, MS, SH, LAT>>(grid, block, l.lds, s, q.p, q.bs, q.cs, k.p, k.bs, k.cs, v.p, v.bs, v.cs, rel_k, rel_v, out.p, out.bs, \
+                                                                       out.cs, lens, head_dim, tmax, window, q_scale, v_aligned ? 1 : 0, tabs.exp)
+        VITS_ATTM_LAUNCH(8, 24, false, true);
+        VITS_ATTM_LAUNCH(4, 24, true, false);
+        VITS_ATTM_LAUNCH(4, 32, false, false);
+        VITS_ATTM_LAUNCH(8, 32, false, false);
 #undef VITS_ATTM_LAUNCH
-#undef VITS_ATTM_LAUNCH_LAT
-            return hipGetLastError();
-        }
+        return hipErrorInvalidValue;
     }
-    const int lp = (tmax + 3) & ~3;
-    size_t lds = 0;
-    int vshift = 6;
-    for (; vshift >= 3; --vshift) {
-        lds = sizeof(float) * ((size_t)ATT_Q * head_dim + ATT_Q * (2 * window + 1) + (size_t)ATT_Q * lp + (size_t)head_dim * ((1 << vshift) + 1));
-        if (lds <= 150 * 1024) break;
-    }
-    if (lds > 150 * 1024 || head_dim * (ATT_Q / 4) > 512) return hipErrorInvalidValue;
-    dim3 grid((tmax + ATT_Q - 1) / ATT_Q, heads, batch);
-    const bool small_grid = (int64_t)grid.x * grid.y * grid.z <= 512;
-#define VITS_ATT_LAUNCH(T)                                                                                                                  \
-    do {                                                                                                                                    \
-        if (lds > 64 * 1024) {                                                                                                              \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rel_attention_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                                                  \
-        }                                                                                                                                   \
-        VITS_KLAUNCH(rel_attention_kernel<T>, grid, dim3(T), lds, s, q.p, q.bs, q.cs, k.p, k.bs, k.cs, v.p, v.bs, v.cs, rel_k, rel_v, out.p, out.bs, \
-                           out.cs, lens, head_dim, tmax, window, q_scale, vshift, tabs.exp);                                                         \
-    } while (0)
-    if (small_grid) VITS_ATT_LAUNCH(1024);
-    else VITS_ATT_LAUNCH(256);
+#define VITS_ATT_LAUNCH(T)                                                                                                                           \
+    static_assert(att_valu_exists(T), "the planner's predicate");                                                                                    \
+    if (l.block == T)                                                                                                                                \
+        return launch_lds<&rel_attention_kernel<T>>(grid, block, l.lds, s, q.p, q.bs, q.cs, k.p, k.bs, k.cs, v.p, v.bs, v.cs, rel_k, rel_v, out.p, out.bs, out.cs, lens, head_dim, \
+                                                    tmax, window, q_scale, l.vshift, tabs.exp)
+    VITS_ATT_LAUNCH(1024);
+    VITS_ATT_LAUNCH(256);
 #undef VITS_ATT_LAUNCH
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -712,7 +670,7 @@ hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const flo
 // channel groups per block of the two LayerNorm kernels: 16 x 64 threads, every thread walks channels/16 rows. (4 groups
 // made each thread chain 48 dependent loads: 26-58 us per launch at batch 1, where these launches have 2 blocks.) The
 // partial sums are combined in a fixed order, so results do not depend on the batch.
-constexpr int LN_GROUPS = 16;
+constexpr int LN_GROUPS = kLnGroups;  // (launch_plan.h)
 
 template <int TW>
 __global__ __launch_bounds__(TW * LN_GROUPS) void add_layer_norm_kernel(const float* x, int64_t x_bs, int x_cs, const float* res, int64_t r_bs, int r_cs,
@@ -785,29 +743,15 @@ __global__ __launch_bounds__(TW * LN_GROUPS) void add_layer_norm_kernel(const fl
 
 hipError_t launch_add_layer_norm(TensorRef x, TensorRef res, const float* gamma, const float* beta, TensorRef y, const int* lens, int batch, int channels,
                                  int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs) {
-    // tile width (time steps per block): 32 = eight waves and channels x 128 B of LDS per block (29 KB at 192 channels); VITS_LN_TW=64 = the
-    // sixteen-wave, 57 KB blocks of rounds 1-3. Every token's sums are the same either way (its channels are summed by the same sixteen channel
-    // groups in the same order). The small block matters when this kernel shares the chip with another batch's vocoder (vits_model_submit_batch):
-    // a 57 KB block only finds room in the tail of a vocoder kernel — stage one of a pipelined f16 batch took 10.2 ms of wall with it, 8.8 with
-    // the small one (alone: 1.91 -> 1.87 ms).
-    const int tw_env = kernel_knobs().ln_tw;
-    const int tw = tw_env == 64 ? 64 : 32;
-    const size_t lds = sizeof(float) * ((size_t)channels * tw + 2 * tw * LN_GROUPS);
-    if (lds > 150 * 1024) return hipErrorInvalidValue;
-    dim3 grid((tmax + tw - 1) / tw, batch);
-#define VITS_LN_LAUNCH(TW)                                                                                                                           \
-    do {                                                                                                                                             \
-        if (lds > 64 * 1024) {                                                                                                                       \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(add_layer_norm_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                                                           \
-        }                                                                                                                                            \
-        VITS_KLAUNCH(add_layer_norm_kernel<TW>, grid, dim3(TW * LN_GROUPS), lds, s, x.p, x.bs, x.cs, res.p, res.bs, res.cs, gamma, beta, y.p, y.bs, y.cs, add_to.p, \
-                     add_to.bs, add_to.cs, lens, channels, tmax, eps, post_gelu, tabs.gelu);                                                       \
-    } while (0)
-    if (tw == 32) VITS_LN_LAUNCH(32);
+    const LayerNormPlan l = plan_add_layer_norm(channels, batch, tmax);
+    if (!l.ok) return hipErrorInvalidValue;
+    const dim3 grid(l.gx, l.gy), block(l.block);
+#define VITS_LN_LAUNCH(TW)                                                                                                                                \
+    return launch_lds<&add_layer_norm_kernel<TW>>(grid, block, l.lds, s, x.p, x.bs, x.cs, res.p, res.bs, res.cs, gamma, beta, y.p, y.bs, y.cs, add_to.p, add_to.bs, add_to.cs, lens, \
+                                                  channels, tmax, eps, post_gelu, tabs.gelu)
+    if (l.tw == 32) VITS_LN_LAUNCH(32);
     else VITS_LN_LAUNCH(64);
 #undef VITS_LN_LAUNCH
-    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -891,17 +835,12 @@ __global__ __launch_bounds__(64 * LN_GROUPS) void dds_depthwise_kernel(float* x,
 
 hipError_t launch_dds_depthwise(TensorRef x, TensorRef g, const float* w, const float* bias, const float* gamma, const float* beta, TensorRef y,
                                 const int* lens, int batch, int channels, int tmax, int k, int dil, float eps, hipStream_t s, int arith, GgmlTables tabs) {
-    const int pad = (k * dil - dil) / 2;
-    const size_t lds = sizeof(float) * ((size_t)channels * (64 + 2 * pad) + (size_t)channels * 64 + 2 * 64 * LN_GROUPS);
-    if (lds > 150 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dds_depthwise_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    dim3 grid((tmax + 63) / 64, batch);
-    VITS_KLAUNCH(dds_depthwise_kernel, grid, dim3(64 * LN_GROUPS), lds, s, x.p, x.bs, x.cs, g.p, g.bs, g.cs, w, bias, gamma, beta, y.p, y.bs, y.cs, lens, channels, tmax,
-                       k, dil, eps, arith, tabs.gelu);
-    return hipGetLastError();
+    const LaunchGrid l = plan_dds_depthwise(channels, k, dil, batch, tmax);
+    if (!l.ok) return hipErrorInvalidValue;
+    const dim3 grid(l.gx, l.gy);
+    const size_t lds = l.lds;
+    return launch_lds<&dds_depthwise_kernel>(grid, dim3(l.block), lds, s, x.p, x.bs, x.cs, g.p, g.bs, g.cs, w, bias, gamma, beta, y.p, y.bs, y.cs, lens, channels, tmax, k,
+                                             dil, eps, arith, tabs.gelu);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1237,66 +1176,24 @@ __global__ __launch_bounds__(32 * LN_GROUPS) void dds_layer_kernel(DdsLayerParam
 #ifdef VITS_PHASE_TIMING
 unsigned long long* g_dds_dbg = nullptr;
 #endif
-static size_t dds_layer_lds(int channels, int k, int dil) {
-    const int xw = 32 + (k * dil - dil);
-    return sizeof(float) * (((size_t)channels * xw + 3) / 4 * 4 + (size_t)channels * 32 + 2 * 32 * LN_GROUPS + ((size_t)channels * (6 + k) + 3) / 4 * 4) + (size_t)channels * 64;
-}
-
-bool dds_layer_supported(const PackedConv& pw, int channels, int k, int dil, int arith) {
-    if (channels <= 0 || (channels & 31) || channels > 32 * (LN_GROUPS / 2)) return false;  // one wave per 32 output rows, 8 waves
-    if (pw.cin != channels || pw.cout != channels || pw.kt != 1 || pw.epi != EPI_STD || !pw.bias) return false;
-    if (arith == VITS_ARITH_F32 ? !pw.wp : !pw.wp16) return false;
-    if (k < 1 || dil < 1 || ((k * dil - dil) & 1)) return false;
-    return dds_layer_lds(channels, k, dil) <= 150 * 1024;
-}
-
 hipError_t launch_dds_layer(TensorRef x, TensorRef y, const float* dw_w, const float* dw_b, const float* g1, const float* b1, const PackedConv& pw, const float* g2,
                             const float* b2, const int* lens, int batch, int channels, int tmax, int k, int dil, float eps, int arith, hipStream_t s, GgmlTables tabs) {
     if (!dds_layer_supported(pw, channels, k, dil, arith) || x.p == y.p) return hipErrorInvalidValue;
     DdsLayerParams p;
-    p.x = x.p;
-    p.x_bs = x.bs;
-    p.x_cs = x.cs;
-    p.y = y.p;
-    p.y_bs = y.bs;
-    p.y_cs = y.cs;
-    p.dw_w = dw_w;
-    p.dw_b = dw_b;
-    p.g1 = g1;
-    p.b1 = b1;
-    p.pw_b = pw.bias;
-    p.g2 = g2;
-    p.b2 = b2;
-    p.wp = pw.wp;
-    p.wp16 = pw.wp16;
-    p.lens = lens;
-    p.channels = channels;
-    p.tmax = tmax;
-    p.k = k;
-    p.dil = dil;
-    p.nchunks = pw.nchunks;
-    p.eps = eps;
-    p.gelu_tab = tabs.gelu;
+    p.x = x.p, p.x_bs = x.bs, p.x_cs = x.cs, p.y = y.p, p.y_bs = y.bs, p.y_cs = y.cs, p.dw_w = dw_w, p.dw_b = dw_b, p.g1 = g1, p.b1 = b1;
+    p.pw_b = pw.bias, p.g2 = g2, p.b2 = b2, p.wp = pw.wp, p.wp16 = pw.wp16, p.lens = lens, p.channels = channels, p.tmax = tmax, p.k = k, p.dil = dil;
+    p.nchunks = pw.nchunks, p.eps = eps, p.gelu_tab = tabs.gelu;
 #ifdef VITS_PHASE_TIMING
     p.dbg = g_dds_dbg;
 #endif
-    const size_t lds = dds_layer_lds(channels, k, dil);
-    dim3 grid((tmax + 31) / 32, batch);
-#define VITS_DDS_LAUNCH1(A, M)                                                                                                         \
-    do {                                                                                                                               \
-        static BigLdsOnce big;                                                                                          \
-        if (lds > 64 * 1024 && big.needed()) {                                                                 \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dds_layer_kernel<A, M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess) return e;                                                                                             \
-            big.done();                                                                                \
-        }                                                                                                                              \
-        VITS_KLAUNCH((dds_layer_kernel<A, M>), grid, dim3(32 * LN_GROUPS), lds, s, p);                                           \
-    } while (0)
+    const DdsLayerPlan l = plan_dds_layer(channels, k, dil, batch, tmax);
+    const dim3 grid(l.gx, l.gy), block(l.block);
+#define VITS_DDS_LAUNCH1(A, M) return launch_lds<&dds_layer_kernel<A, M>>(grid, block, l.lds, s, p)
 #define VITS_DDS_LAUNCH(A)                       \
     do {                                         \
-        if (pw.nchunks <= 2) VITS_DDS_LAUNCH1(A, 2);      \
-        else if (pw.nchunks <= 4) VITS_DDS_LAUNCH1(A, 4); \
-        else if (pw.nchunks <= 6) VITS_DDS_LAUNCH1(A, 6); \
+        if (l.m == 2) VITS_DDS_LAUNCH1(A, 2);      \
+        else if (l.m == 4) VITS_DDS_LAUNCH1(A, 4); \
+        else if (l.m == 6) VITS_DDS_LAUNCH1(A, 6); \
         else VITS_DDS_LAUNCH1(A, 8);             \
     } while (0)
     if (arith == VITS_ARITH_F32) VITS_DDS_LAUNCH(0);
@@ -1304,7 +1201,6 @@ hipError_t launch_dds_layer(TensorRef x, TensorRef y, const float* dw_w, const f
     else VITS_DDS_LAUNCH(2);
 #undef VITS_DDS_LAUNCH1
 #undef VITS_DDS_LAUNCH
-    return hipGetLastError();
 }
 
 // conv_pre of a conv flow: 1 -> channels pointwise conv of latent row zc (vits.cpp:864): y[c][t] = w[c]*z[zc][t] + b[c]
@@ -1541,13 +1437,9 @@ hipError_t launch_spline(TensorRef u, TensorRef z, int zc, const int* lens, int 
 #define VITS_SPLINE_LAUNCH(NT, TAB)                                                                                                                 \
     do {                                                                                                                                            \
         const size_t lds_ = ((size_t)3 * tpad + (size_t)(3 * bins - 1) * (tpad < NT ? tpad : NT)) * sizeof(float);                                  \
-        static BigLdsOnce big;                                                                                                                      \
-        if (lds_ > 64 * 1024 && big.needed()) {                                                                                                     \
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spline_kernel<NT, TAB>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)) return e; /* (+ the kernel's static s_part) */ \
-            big.done();                                                                                                                             \
-        }                                                                                                                                           \
-        VITS_KLAUNCH((spline_kernel<NT, TAB>), dim3(batch), dim3(tpad < NT ? tpad : NT), lds_, s, u.p, u.bs, u.cs, z.p, z.bs, z.cs, zc, lens, tmax, bins, tail, inv_sqrt, \
-                     mode, tabs.exp);                                                                                                               \
+        /* (152 KB: + the kernel's static s_part) */                                                                                                \
+        return launch_lds<&spline_kernel<NT, TAB>, 152 * 1024>(dim3(batch), dim3(tpad < NT ? tpad : NT), lds_, s, u.p, u.bs, u.cs, z.p, z.bs, z.cs, zc, lens, tmax, bins, tail, \
+                                                               inv_sqrt, mode, tabs.exp);                                                           \
     } while (0)
     if (tabs.exp) {
         VITS_SPLINE_LAUNCH(512, true);
@@ -1555,7 +1447,6 @@ hipError_t launch_spline(TensorRef u, TensorRef z, int zc, const int* lens, int 
         VITS_SPLINE_LAUNCH(512, false);
     }
 #undef VITS_SPLINE_LAUNCH
-    return hipGetLastError();
 }
 
 // elementwise affine, reverse (vits.cpp:901-925; Q5 sign): logical channel ch lives in physical row (c_first ? 1-ch : ch)

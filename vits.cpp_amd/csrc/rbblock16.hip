@@ -87,14 +87,15 @@ __device__ unsigned long long vits_rbb_phase[16 * 65536];
 // (The body as a device function: rbblock16_kernel runs it for one resblock, rbblock16_group3_kernel for the three resblocks of a stage in ONE launch.)
 template <int KT, int C, int NSTRIP, int NRW, int MRW, int D0, int D1, int D2, bool BF, bool STREAM>
 __device__ __forceinline__ void rbblock16_body(const RbBlockParams& p, const int b) {
-    constexpr int NCH = C / 32, W = NSTRIP * NRW * 32;  // (LDS tile: C / 8 channel groups x PITCH slots)
-    constexpr int P2 = (KT - 1) / 2;
+    constexpr RbBlock16Geom GEO = rbblock16_geom(KT, C, NSTRIP, NRW, MRW, D0, D1, D2);  // (launch_plan.h: the planner reads the same)
+    constexpr int NCH = C / 32;  // (LDS tile: C / 8 channel groups x PITCH slots)
+    constexpr int P2 = GEO.p2;
     constexpr int DMAX = D0 > D1 ? (D0 > D2 ? D0 : D2) : (D1 > D2 ? D1 : D2);
-    constexpr int H = P2 * (3 + D0 + D1 + D2);  // halo per side: every pair costs P2 (second conv) + P2 * D_p (first conv)
-    constexpr int BO = W - 2 * H;               // output columns of a (first) tile
-    constexpr int ADV = W - H;                  // STREAM: distance between the tiles of a segment = output columns of every later tile
-    constexpr int PADX = P2 * DMAX;             // the first conv of a pair reads up to P2 * D_p columns beyond a tile column
-    constexpr int PITCH = (W + 2 * PADX + 7) / 8 * 8;
+    constexpr int H = GEO.h;        // halo per side
+    constexpr int BO = GEO.bo;      // output columns of a (first) tile
+    constexpr int ADV = GEO.adv;    // STREAM: distance between the tiles of a segment = output columns of every later tile
+    constexpr int PADX = GEO.padx;  // the first conv of a pair reads up to P2 * D_p columns beyond a tile column
+    constexpr int PITCH = GEO.pitch;
     constexpr int STEPS = 2 * KT, TOTAL = NCH * STEPS;
     constexpr int G = C / 8;
     static_assert(BO > 0, "tile too narrow for this kernel size");
@@ -453,59 +454,8 @@ hipError_t launch_rb_sum3(const float* y0, const float* y1, const float* y2, int
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <int KT, int C, int NSTRIP, int NRW, int MRW, bool BF, bool STREAM>
-static hipError_t launch_rbb_grid(const RbBlockParams& p, int seg_out, int batch, hipStream_t s) {
-    constexpr int D0 = 1, D1 = 3, D2 = 5;
-    constexpr int P2 = (KT - 1) / 2, W = NSTRIP * NRW * 32, H = P2 * (3 + D0 + D1 + D2), PADX = P2 * D2, PITCH = (W + 2 * PADX + 7) / 8 * 8;
-    const size_t lds = (size_t)(C / 8) * PITCH * 16 + (size_t)6 * C * sizeof(float) + (STREAM ? (size_t)(C / 8) * H * 16 : 0);
-    static BigLdsOnce big_lds_set;
-    if (lds > 64 * 1024 && big_lds_set.needed()) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbblock16_kernel<KT, C, NSTRIP, NRW, MRW, D0, D1, D2, BF, STREAM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return ea;
-        big_lds_set.done();
-    }
-    dim3 grid((p.tmax + seg_out - 1) / seg_out, batch);
-    VITS_KLAUNCH((rbblock16_kernel<KT, C, NSTRIP, NRW, MRW, D0, D1, D2, BF, STREAM>), grid, dim3(C / (32 * MRW) * NSTRIP * 64), lds, s, p);
-    return hipGetLastError();
-}
-// Tiles per block for a launch of `batch` sequences of up to `tmax` columns on tiles of W columns.
-// Segments of several tiles (STREAM) once the one-tile grid is many rounds of the chip: a segment's first tile pays the halo of both sides,
-// and the blocks of the last round run on a partly empty chip — nt grows with the grid up to the shape's limit.
-// Which shapes: measured per kernel on the benchmark batch (64 x 128 ids: 10-14 thousand tiles, i.e. 13-18 per resident block, so that long
-// segments cost in balance what they save in halo — tools/rbb_micro.hip, profiles/round6_rbb_stream_micro.txt): k = 11 at C = 32
-// 1.000 -> 0.892 ms with 6 tiles, k = 7 at C = 64 1.138 -> 1.040 with 3, k = 11 at C = 64 1.584 -> 1.396 with 4; k = 3 (a halo of 12
-// columns) and k = 7 at C = 32 lose 0-25 %: one tile per block there.
-static int rbb_stream_tiles_for(int kt, int C, int W, int batch, int tmax) {
-    const KernelKnobs& kn = kernel_knobs();
-    const int H = (kt - 1) / 2 * 12, BO = W - 2 * H;
-    const long blocks1 = (long)((tmax + BO - 1) / BO) * batch;
-    int want = kn.rbb_stream_tiles;
-    if (want < 0) want = (kt == 11 && C == 32) ? 6 : (kt == 7 && C == 64) ? 3 : (kt == 11 && C == 64) ? 4 : 0;
-    if (want <= 1 || kn.rbb_stream_min_blocks <= 0 || blocks1 < 2L * kn.rbb_stream_min_blocks) return 1;
-    return (int)(blocks1 / kn.rbb_stream_min_blocks < want ? blocks1 / kn.rbb_stream_min_blocks : want);
-}
-template <int KT, int C, int NSTRIP, int NRW, int MRW, bool BF>
-static hipError_t launch_rbb(RbBlockParams p, int batch, hipStream_t s) {
-    constexpr int P2 = (KT - 1) / 2, W = NSTRIP * NRW * 32, H = P2 * 12, BO = W - 2 * H, ADV = W - H;
-    const int nt = rbb_stream_tiles_for(KT, C, W, batch, p.tmax);
-    p.nt = nt;
-    if (nt > 1) return launch_rbb_grid<KT, C, NSTRIP, NRW, MRW, BF, true>(p, BO + (nt - 1) * ADV, batch, s);
-    return launch_rbb_grid<KT, C, NSTRIP, NRW, MRW, BF, false>(p, BO, batch, s);
-}
-
-bool rbblock16_supported(int channels, int kt, const int* dils, int ndil, int batch, int tmax) {
-    const bool c128 = kernel_knobs().rbb_c128;
-    if (channels == 128) return c128 && kt == 3 && ndil == 3 && dils[0] == 1 && dils[1] == 3 && dils[2] == 5;
-    if (!(channels == 32 || channels == 64) || !(kt == 3 || kt == 7 || kt == 11)) return false;
-    // C = 64, k = 11: on one tile per block (1.45 x the MFMA work) the whole-resblock kernel is bound by the matrix cores (at the clock
-    // the power budget leaves them) and loses to three fused pairs, 1.59 against 1.45 ms per step (batch 64 x 128 ids); on segments of four
-    // tiles (1.19 x; round 6) it wins, 13.31 -> 13.19 ms per pipelined batch. VITS_RBB_C64K11=1 runs it on every grid, =0 on none.
-    const int c64k11 = kernel_knobs().rbb_c64k11;
-    if (channels == 64 && kt == 11 && !(c64k11 > 0 || (c64k11 < 0 && rbb_stream_tiles_for(11, 64, 384, batch, tmax) > 1))) return false;
-    return ndil == 3 && dils[0] == 1 && dils[1] == 3 && dils[2] == 5;
-}
-
-static hipError_t rbb_params(const PackedConv* const* c1, const PackedConv* const* c2, const RbBlock16Call& c, RbBlockParams& p) {
+// (in_group: as a member of launch_rbblock16_group3)
+static hipError_t rbb_params(const PackedConv* const* c1, const PackedConv* const* c2, const RbBlock16Call& c, RbBlockParams& p, RbBlock16Plan& l, bool in_group = false) {
     const int C = c1[0]->cin, kt = c1[0]->kt;
     for (int i = 0; i < 3; ++i) {
         if (!c1[i]->wp16 || !c2[i]->wp16 || !c1[i]->bias || !c2[i]->bias || c1[i]->cin != C || c1[i]->cout != C || c2[i]->cin != C || c2[i]->cout != C || c1[i]->kt != kt ||
@@ -516,88 +466,65 @@ static hipError_t rbb_params(const PackedConv* const* c1, const PackedConv* cons
         p.b1[i] = c1[i]->bias;
         p.b2[i] = c2[i]->bias;
     }
-    const int dils[3] = {1, 3, 5};
-    if (!rbblock16_supported(C, kt, dils, 3, c.batch, c.tmax) || !c.y0 || (!c.yg && !c.y16.p)) return hipErrorInvalidValue;
-    p.y0 = c.y0;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    p.slope = c.slope;
-    p.yg = c.yg;
-    p.accg = c.accg;
-    p.g_bs = c.g_bs;
-    p.g_ts = c.g_ts;
-    p.y16 = c.y16.p;
-    p.y16_bs = c.y16.bs;
-    p.y16_ts = c.y16.ts;
-    p.y16_slope = c.y16_slope;
-    p.scale = c.scale;
-    p.scale_div = c.scale_div;
-    p.nt = 1;
+    l = plan_rbblock16(C, kt, c.batch, c.tmax, in_group);
+    if (!l.ok || !c.y0 || (!c.yg && !c.y16.p)) return hipErrorInvalidValue;
+    p.y0 = c.y0, p.lens = c.lens, p.tmax = c.tmax, p.slope = c.slope, p.yg = c.yg, p.accg = c.accg, p.g_bs = c.g_bs, p.g_ts = c.g_ts, p.y16 = c.y16.p;
+    p.y16_bs = c.y16.bs, p.y16_ts = c.y16.ts, p.y16_slope = c.y16_slope, p.scale = c.scale, p.scale_div = c.scale_div;
+    p.nt = in_group ? 1 : l.nt;  // (the grouped launch: one tile per block)
     return hipSuccess;
 }
 
 // the three resblocks (k = 3, 7, 11) of a C = 32 stage as one launch (small grids: one tile per block); c1[m] / c2[m]: member m's three conv pairs
-bool rbblock16_group3_supported(int channels, const int* kts, int batch, int tmax) {
-    if (kernel_knobs().no_rbb_group3 || !(channels == 32 || (channels == 64 && !kernel_knobs().no_rbb_group3_c64)) || kts[0] != 3 || kts[1] != 7 || kts[2] != 11) return false;
-    const int dils[3] = {1, 3, 5};
-    for (int m = 0; m < 2; ++m)
-        if (!rbblock16_supported(channels, kts[m], dils, 3, batch, tmax)) return false;
-    // (k = 11 at C = 64 is a whole-resblock kernel here whatever VITS_RBB_C64K11 says for the single launches: measured in the group)
-    if (channels == 32 && !rbblock16_supported(channels, 11, dils, 3, batch, tmax)) return false;
-    return (long)((tmax + 183) / 184) * batch <= 3072;  // (one tile per block: well below rbb_stream_tiles_for's threshold for segments)
-}
 hipError_t launch_rbblock16_group3(const PackedConv* const (*c1)[3], const PackedConv* const (*c2)[3], const RbBlock16Call* c, int arith, hipStream_t s) {
     RbBlockGroup3Params gp;
     const int C = c1[0][0]->cin;
     const int kts[3] = {c1[0][0]->kt, c1[1][0]->kt, c1[2][0]->kt};
-    if (!rbblock16_group3_supported(C, kts, c[0].batch, c[0].tmax)) return hipErrorInvalidValue;
+    const LaunchGrid l = plan_rbblock16_group3(C, kts, c[0].batch, c[0].tmax);
+    if (!l.ok) return hipErrorInvalidValue;
     for (int m = 0; m < 3; ++m) {
-        if (C == 64 && m == 2) {  // (rbb_params asks rbblock16_supported, which answers for the single launch)
-            KernelKnobs k2 = kernel_knobs();
-            k2.rbb_c64k11 = 1;
-            KernelKnobsScope scope(&k2);
-            if (hipError_t e = rbb_params(c1[m], c2[m], c[m], gp.m[m])) return e;
-        } else if (hipError_t e = rbb_params(c1[m], c2[m], c[m], gp.m[m])) return e;
+        RbBlock16Plan member;
+        if (hipError_t e = rbb_params(c1[m], c2[m], c[m], gp.m[m], member, true)) return e;
         if (c[m].batch != c[0].batch || c[m].tmax != c[0].tmax) return hipErrorInvalidValue;
     }
-    // LDS of the k = 11 member (384 columns + the widest padding); grid.x of the member with the fewest outputs per tile (C = 32: k = 11, 264; C = 64: k = 7 on 256 columns, 184)
-    const int PITCH = (384 + 2 * 25 + 7) / 8 * 8, BOmin = C == 32 ? 264 : 184;
-    const size_t lds = (size_t)(C / 8) * PITCH * 16 + (size_t)6 * C * sizeof(float);
-    dim3 grid((c[0].tmax + BOmin - 1) / BOmin, 3 * c[0].batch);
+    static_assert(rbblock16_group3_exists(32) && rbblock16_group3_exists(64), "the planner's predicate");
+    const dim3 grid(l.gx, l.gy), block(l.block);
     const bool bf = arith == VITS_ARITH_BF16;
-    if (C == 32) {
-        if (bf) VITS_KLAUNCH((rbblock16_group3_kernel<32, true>), grid, dim3(256), lds, s, gp);
-        else VITS_KLAUNCH((rbblock16_group3_kernel<32, false>), grid, dim3(256), lds, s, gp);
-    } else {
-        if (bf) VITS_KLAUNCH((rbblock16_group3_kernel<64, true>), grid, dim3(512), lds, s, gp);
-        else VITS_KLAUNCH((rbblock16_group3_kernel<64, false>), grid, dim3(512), lds, s, gp);
-    }
-    return hipGetLastError();
+    if (C == 32) return bf ? launch_lds<&rbblock16_group3_kernel<32, true>>(grid, block, l.lds, s, gp) : launch_lds<&rbblock16_group3_kernel<32, false>>(grid, block, l.lds, s, gp);
+    return bf ? launch_lds<&rbblock16_group3_kernel<64, true>>(grid, block, l.lds, s, gp) : launch_lds<&rbblock16_group3_kernel<64, false>>(grid, block, l.lds, s, gp);
 }
 
+template <int KT, int C, bool BF>
+static hipError_t launch_rbb(const RbBlockParams& p, const RbBlock16Plan& l, hipStream_t s) {
+    static_assert(rbblock16_exists(KT, C), "the planner would never ask for it");
+    constexpr RbBlock16Tile T = rbblock16_tile(KT, C);
+    const dim3 grid(l.gx, l.gy), block(l.block);
+    if (l.nt > 1) return launch_lds<&rbblock16_kernel<KT, C, T.nstrip, T.nrw, T.mrw, 1, 3, 5, BF, true>>(grid, block, l.lds, s, p);
+    return launch_lds<&rbblock16_kernel<KT, C, T.nstrip, T.nrw, T.mrw, 1, 3, 5, BF, false>>(grid, block, l.lds, s, p);
+}
 hipError_t launch_rbblock16(const PackedConv* const* c1, const PackedConv* const* c2, const RbBlock16Call& c, int arith, hipStream_t s) {
     const int C = c1[0]->cin, kt = c1[0]->kt;
     RbBlockParams p;
-    if (hipError_t e = rbb_params(c1, c2, c, p)) return e;
+    RbBlock16Plan l;
+    if (hipError_t e = rbb_params(c1, c2, c, p, l)) return e;
     const bool bf = arith == VITS_ARITH_BF16;
-    // tile shape (column strips x 32-column tiles per wave): C = 32: 4 x 3 = 384 columns, three blocks per CU. Measured alternatives (batch
-    // 64 x 128 ids, f16): C = 32 with 4 x 4 = 512 columns (two blocks per CU instead of three) +5...12 %; C = 64 as 4 x 3 (eight waves, one
+    // tile shapes (rbblock16_tile: column strips x 32-column tiles per wave x row tiles per wave). C = 32: 4 x 3 = 384 columns, three blocks per CU. Measured
+    // alternatives (batch 64 x 128 ids, f16): C = 32 with 4 x 4 = 512 columns (two blocks per CU instead of three) +5...12 %; C = 64 as 4 x 3 (eight waves, one
     // block per CU: round 3's first version), as 6 x 2 (twelve waves) +-0, as 8 x 2 = 512 columns (sixteen waves at 128 VGPRs, spills) -5 %
     // on k = 11 only, as 2 x 5 (spills) worse than 2 x 4.
-#define VITS_RBB_GO(K, CC, NS, NRW_, MRW_)                                                              \
-    if (kt == K && C == CC) return bf ? launch_rbb<K, CC, NS, NRW_, MRW_, true>(p, c.batch, s) : launch_rbb<K, CC, NS, NRW_, MRW_, false>(p, c.batch, s)
-    VITS_RBB_GO(3, 32, 4, 3, 1);
-    VITS_RBB_GO(7, 32, 4, 3, 1);
-    VITS_RBB_GO(11, 32, 4, 3, 1);
-    // C = 64: four waves (two strips of four column tiles, 256 columns) instead of eight (4 x 3): at 236 VGPRs two blocks share a CU and
+    // C = 64, k = 3 / 7: four waves (two strips of four column tiles, 256 columns) instead of eight (4 x 3): at 236 VGPRs two blocks share a CU and
     // one's loads, tile writes and epilogue overlap the other's MFMA phases — with eight waves a CU ran ONE block at a time, its matrix
     // pipes 30 % busy at 1.4 TB/s: k = 3 0.70 -> 0.55 ms, k = 7 1.09 -> 1.05 (the narrower tile costs 1.39 x instead of 1.23 x the MFMA work there)
-    VITS_RBB_GO(3, 64, 2, 4, 1);
-    VITS_RBB_GO(7, 64, 2, 4, 1);
-    VITS_RBB_GO(11, 64, 4, 3, 1);
     // C = 128, k = 3: the pairs are HBM-bound (4.4 TB/s); eight waves of two row tiles x two column tiles (256-column tiles, 232 outputs).
     // (Eight waves of one row tile on 128-column tiles at 128 VGPRs — two blocks per CU —, sixteen waves on 256 columns, eight on 192: +-2 %.)
-    VITS_RBB_GO(3, 128, 4, 2, 2);
+#define VITS_RBB_GO(K, CC) \
+    if (kt == K && C == CC) return bf ? launch_rbb<K, CC, true>(p, l, s) : launch_rbb<K, CC, false>(p, l, s)
+    VITS_RBB_GO(3, 32);
+    VITS_RBB_GO(7, 32);
+    VITS_RBB_GO(11, 32);
+    VITS_RBB_GO(3, 64);
+    VITS_RBB_GO(7, 64);
+    VITS_RBB_GO(11, 64);
+    VITS_RBB_GO(3, 128);
 #undef VITS_RBB_GO
     return hipErrorInvalidValue;
 }

@@ -51,12 +51,10 @@ template <int C, int NR>
 __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const RbBlock32Params p) {
     constexpr int KT = 3, D0 = 1, D1 = 3, D2 = 5;
     constexpr int NCH = C / 32, WM = C / 32, WN = 4 / WM;
-    constexpr int W = WN * NR * 32;
-    constexpr int P2 = (KT - 1) / 2;
-    constexpr int H = P2 * (3 + D0 + D1 + D2);  // halo per side: every pair costs P2 (second conv) + P2 * D_p (first conv)
-    constexpr int BO = W - 2 * H;
-    constexpr int PADX = P2 * D2;                // the first conv of a pair reads up to P2 * D_p columns beyond a tile column
-    constexpr int PITCH = (W + 2 * PADX + 3) / 4 * 4;
+    constexpr RbBlock32Geom GEO = rbblock32_geom(C, NR);  // (launch_plan.h: the planner reads the same)
+    constexpr int W = GEO.w, P2 = GEO.p2, H = GEO.h, BO = GEO.bo;  // H: halo per side
+    constexpr int PADX = GEO.padx;  // the first conv of a pair reads up to P2 * D_p columns beyond a tile column
+    constexpr int PITCH = GEO.pitch;
     constexpr int TOTAL = NCH * KT * 4;          // A-fragment steps (float4 = 4 MFMA k-steps) per conv and row tile
     static_assert(BO > 0, "tile too narrow");
     extern __shared__ __attribute__((aligned(16))) float tile[];  // [C][PITCH]: x_p, then t_p, then x_{p+1}, ...
@@ -227,26 +225,6 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <int C, int NR>
-static hipError_t launch_rbb32(const RbBlock32Params& p, int batch, hipStream_t s) {
-    constexpr int W = (4 / (C / 32)) * NR * 32, H = 12, BO = W - 2 * H, PADX = 5, PITCH = (W + 2 * PADX + 3) / 4 * 4;
-    const size_t lds = ((size_t)C * PITCH + 6 * C) * sizeof(float);
-    static BigLdsOnce big_lds_set;
-    if (lds > 64 * 1024 && big_lds_set.needed()) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbblock32_kernel<C, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return ea;
-        big_lds_set.done();
-    }
-    dim3 grid((p.tmax + BO - 1) / BO, batch);
-    VITS_KLAUNCH((rbblock32_kernel<C, NR>), grid, dim3(256), lds, s, p);
-    return hipGetLastError();
-}
-
-bool rbblock32_supported(int channels, int kt, const int* dils, int ndil) {
-    if (kt != 3 || !(channels == 32 || channels == 64)) return false;
-    return ndil == 3 && dils[0] == 1 && dils[1] == 3 && dils[2] == 5;
-}
-
 hipError_t launch_rbblock32(const PackedConv* const* c1, const PackedConv* const* c2, const RbBlock32Call& c, hipStream_t s) {
     const int C = c1[0]->cin, kt = c1[0]->kt;
     RbBlock32Params p;
@@ -259,27 +237,15 @@ hipError_t launch_rbblock32(const PackedConv* const* c1, const PackedConv* const
         p.b1[i] = c1[i]->bias;
         p.b2[i] = c2[i]->bias;
     }
-    const int dils[3] = {1, 3, 5};
-    if (!rbblock32_supported(C, kt, dils, 3) || !c.x.p || !c.y.p || c.x.p == c.y.p) return hipErrorInvalidValue;
-    p.x = c.x.p;
-    p.x_bs = c.x.bs;
-    p.x_cs = c.x.cs;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    p.slope = c.slope;
-    p.y = c.y.p;
-    p.y_bs = c.y.bs;
-    p.y_cs = c.y.cs;
-    p.acc = c.acc.p;
-    p.a_bs = c.acc.bs;
-    p.a_cs = c.acc.cs;
-    p.scale = c.scale;
-    p.scale_div = c.scale_div;
-    p.post_act = c.post_act;
+    const RbBlock32Plan l = plan_rbblock32(C, kt, c.batch, c.tmax);
+    if (!l.ok || !c.x.p || !c.y.p || c.x.p == c.y.p) return hipErrorInvalidValue;
+    p.x = c.x.p, p.x_bs = c.x.bs, p.x_cs = c.x.cs, p.lens = c.lens, p.tmax = c.tmax, p.slope = c.slope, p.y = c.y.p, p.y_bs = c.y.bs, p.y_cs = c.y.cs;
+    p.acc = c.acc.p, p.a_bs = c.acc.bs, p.a_cs = c.acc.cs, p.scale = c.scale, p.scale_div = c.scale_div, p.post_act = c.post_act;
     p.post_slope = c.post_slope;
-    // (C = 32 on 384-column tiles — 1.07 x instead of 1.10 x the MFMA work, two blocks per CU instead of three — measured 1.25 against 1.22 ms)
-    if (C == 32) return launch_rbb32<32, 2>(p, c.batch, s);
-    return launch_rbb32<64, 4>(p, c.batch, s);
+    static_assert(rbblock32_exists(32, rbblock32_nr(32)) && rbblock32_exists(64, rbblock32_nr(64)), "the planner's predicate");
+    const dim3 grid(l.gx, l.gy), block(l.block);
+    if (C == 32) return launch_lds<&rbblock32_kernel<32, rbblock32_nr(32)>>(grid, block, l.lds, s, p);
+    return launch_lds<&rbblock32_kernel<64, rbblock32_nr(64)>>(grid, block, l.lds, s, p);
 }
 
 }  // namespace vits

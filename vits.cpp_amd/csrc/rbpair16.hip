@@ -83,12 +83,11 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
     constexpr int MR = ROWS ? 1 : C / 32;  // row tiles per wave
     constexpr int NW = ROWS ? C / 32 : 4;  // waves per block (row split: one per 32-row tile: 4 at C = 128, 8 at C = 256)
     // NR 32-column tiles per wave. Column split: 4 waves x NR tiles = 256 mid columns for C <= 64 (NR = 2). Row split: NR = 4 tiles = 128.
-    constexpr int BM = (ROWS ? 1 : 4) * NR * 32;  // columns of t computed per block
-    constexpr int BO = BM - (KT - 1);  // output columns per block
+    constexpr RbPair16Geom GEO = rbpair16_geom(KT, DIL, C, NR);  // (launch_plan.h: the planner reads the same)
+    static_assert(GEO.rows == ROWS, "the row split is a function of C");
+    constexpr int BO = GEO.bo;  // output columns per block (of GEO.bm columns of t)
     constexpr int P2 = (KT - 1) / 2, P1 = (KT - 1) * DIL / 2;
-    constexpr int XW = BM + (KT - 1) * DIL;
-    constexpr int XWP = (XW + 7) / 8 * 8;
-    constexpr int TW = (BM + KT - 1 + 7) / 8 * 8;
+    constexpr int XWP = GEO.xwp, TW = GEO.tw;
     constexpr int STEPS = 2 * KT;
     extern __shared__ __attribute__((aligned(16))) int4v lds[];  // x tile [G][XWP] | t tile [G][TW]  (C >= 64: the t tile REPLACES the x tile)
     int4v* xs = lds;
@@ -347,98 +346,54 @@ __global__ __launch_bounds__(ROWS ? 2 * C : 256, C >= 256 ? ((KT - 1) * DIL <= 3
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 template <int KT, int DIL, int C, bool BF, int NR>
-static hipError_t launch_rb_nr(const RbPairParams& p, int batch, hipStream_t s) {
-    constexpr bool ROWS = C >= 128;
-    constexpr int BM = (ROWS ? 1 : 4) * NR * 32;
-    constexpr int BO = BM - (KT - 1);
-    constexpr int XWP = (BM + (KT - 1) * DIL + 7) / 8 * 8, TW = (BM + KT - 1 + 7) / 8 * 8;
-    const size_t lds = C >= 64 ? (size_t)(C / 8) * (XWP > TW ? XWP : TW) * 16 : (size_t)(C / 8) * (XWP + TW) * 16;
-    static BigLdsOnce big_lds_set;
-    if (lds > 64 * 1024 && big_lds_set.needed()) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpair16_kernel<KT, DIL, C, NR, BF, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return ea;
-        big_lds_set.done();
-    }
-    dim3 grid((p.tmax + BO - 1) / BO, batch);
-    VITS_KLAUNCH((rbpair16_kernel<KT, DIL, C, NR, BF, ROWS>), grid, dim3(ROWS ? 2 * C : 256), lds, s, p);
-    return hipGetLastError();
+static hipError_t launch_rb_nr(const RbPairParams& p, const RbPair16Plan& l, hipStream_t s) {
+    static_assert(rbpair16_exists(KT, DIL, C, NR), "the planner would never ask for it");
+    return launch_lds<&rbpair16_kernel<KT, DIL, C, NR, BF, (C >= 128)>>(dim3(l.gx, l.gy), dim3(l.block), l.lds, s, p);
 }
-#ifndef VITS_RB16_NARROW_NR
-#define VITS_RB16_NARROW_NR 2
-#endif
 template <int KT, int DIL, int C, bool BF>
-static hipError_t launch_rb(const RbPairParams& p, int batch, hipStream_t s) {
+static hipError_t launch_rb(const RbPairParams& p, const RbPair16Plan& l, hipStream_t s) {
     if constexpr (C >= 128) {
-        // small grids (batch 1 ... 4): the row-split blocks own 128 columns (NR = 4 tiles per wave), i.e. 16 blocks for the 1,808 frames of an
-        // utterance at C = 256 on 256 CUs; blocks of VITS_RB16_NARROW_NR tiles are that many times shorter chains on that many more CUs
-        // (the halo costs more: they lose as soon as the chip is full). Same chains per output: bit-identical.
-        constexpr int BO4 = 4 * 32 - (KT - 1);
-        if ((int64_t)((p.tmax + BO4 - 1) / BO4) * batch <= kernel_knobs().rb16_narrow_max) return launch_rb_nr<KT, DIL, C, BF, VITS_RB16_NARROW_NR>(p, batch, s);
-        return launch_rb_nr<KT, DIL, C, BF, 4>(p, batch, s);
+        if (l.nr != 4) return launch_rb_nr<KT, DIL, C, BF, VITS_RB16_NARROW_NR>(p, l, s);
+        return launch_rb_nr<KT, DIL, C, BF, 4>(p, l, s);
     } else {
-        return launch_rb_nr<KT, DIL, C, BF, 2>(p, batch, s);
+        return launch_rb_nr<KT, DIL, C, BF, 2>(p, l, s);
     }
 }
 
 template <int KT, int C, bool BF>
-static hipError_t launch_rb_dil(int dil, const RbPairParams& p, int batch, hipStream_t s) {
+static hipError_t launch_rb_dil(int dil, const RbPairParams& p, const RbPair16Plan& l, hipStream_t s) {
     switch (dil) {
-        case 1: return launch_rb<KT, 1, C, BF>(p, batch, s);
-        case 3: return launch_rb<KT, 3, C, BF>(p, batch, s);
-        case 5: return launch_rb<KT, 5, C, BF>(p, batch, s);
+        case 1: return launch_rb<KT, 1, C, BF>(p, l, s);
+        case 3: return launch_rb<KT, 3, C, BF>(p, l, s);
+        case 5: return launch_rb<KT, 5, C, BF>(p, l, s);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <int C, bool BF>
-static hipError_t launch_rb_kt(int kt, int dil, const RbPairParams& p, int batch, hipStream_t s) {
+static hipError_t launch_rb_kt(int kt, int dil, const RbPairParams& p, const RbPair16Plan& l, hipStream_t s) {
     switch (kt) {
-        case 3: return launch_rb_dil<3, C, BF>(dil, p, batch, s);
-        case 7: return launch_rb_dil<7, C, BF>(dil, p, batch, s);
-        case 11: return launch_rb_dil<11, C, BF>(dil, p, batch, s);
+        case 3: return launch_rb_dil<3, C, BF>(dil, p, l, s);
+        case 7: return launch_rb_dil<7, C, BF>(dil, p, l, s);
+        case 11: return launch_rb_dil<11, C, BF>(dil, p, l, s);
         default: return hipErrorInvalidValue;
     }
 }
 
-bool rbpair16_supported(int channels, int kt, int dil) {
-    // VITS_FUSE16_MAXC=64 keeps the C = 128 pairs on two kernels
-    const int maxc = kernel_knobs().fuse16_maxc;
-    if (!(kt == 3 || kt == 7 || kt == 11) || channels > maxc) return false;
-    if (channels == 32 || channels == 64 || channels == 128 || channels == 256) return dil == 1 || dil == 3 || dil == 5;
-    return false;
-}
-
 hipError_t launch_rbpair16(const PackedConv& c1, const PackedConv& c2, const RbPair16Call& c, int arith, hipStream_t s) {
-    if (!c1.wp16 || !c2.wp16 || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !rbpair16_supported(c1.cin, c1.kt, c.dil))
+    const RbPair16Plan l = plan_rbpair16(c1.cin, c1.kt, c.dil, c.batch, c.tmax);
+    if (!c1.wp16 || !c2.wp16 || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !l.ok)
         return hipErrorInvalidValue;
     RbPairParams p;
-    p.x = c.x.p;
-    p.x_bs = c.x.bs;
-    p.x_ts = c.x.ts;
-    p.w1 = c1.wp16;
-    p.w2 = c2.wp16;
-    p.b1 = c1.bias;
-    p.b2 = c2.bias;
+    p.x = c.x.p, p.x_bs = c.x.bs, p.x_ts = c.x.ts, p.w1 = c1.wp16, p.w2 = c2.wp16, p.b1 = c1.bias, p.b2 = c2.bias;
     if (!p.b1 || !p.b2) return hipErrorInvalidValue;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    p.slope = c.slope;
-    p.yg = c.yg;
-    p.resg = c.resg;
-    p.accg = c.accg;
-    p.g_bs = c.g_bs;
-    p.g_ts = c.g_ts;
-    p.y16 = c.y16.p;
-    p.y16_bs = c.y16.bs;
-    p.y16_ts = c.y16.ts;
-    p.y16_slope = c.y16_slope;
-    p.scale = c.scale;
-    p.scale_div = c.scale_div;
+    p.lens = c.lens, p.tmax = c.tmax, p.slope = c.slope, p.yg = c.yg, p.resg = c.resg, p.accg = c.accg, p.g_bs = c.g_bs, p.g_ts = c.g_ts;
+    p.y16 = c.y16.p, p.y16_bs = c.y16.bs, p.y16_ts = c.y16.ts, p.y16_slope = c.y16_slope, p.scale = c.scale, p.scale_div = c.scale_div;
     const bool bf = arith == VITS_ARITH_BF16;
-    if (c1.cin == 32) return bf ? launch_rb_kt<32, true>(c1.kt, c.dil, p, c.batch, s) : launch_rb_kt<32, false>(c1.kt, c.dil, p, c.batch, s);
-    if (c1.cin == 64) return bf ? launch_rb_kt<64, true>(c1.kt, c.dil, p, c.batch, s) : launch_rb_kt<64, false>(c1.kt, c.dil, p, c.batch, s);
-    if (c1.cin == 128) return bf ? launch_rb_kt<128, true>(c1.kt, c.dil, p, c.batch, s) : launch_rb_kt<128, false>(c1.kt, c.dil, p, c.batch, s);
-    return bf ? launch_rb_kt<256, true>(c1.kt, c.dil, p, c.batch, s) : launch_rb_kt<256, false>(c1.kt, c.dil, p, c.batch, s);
+    if (c1.cin == 32) return bf ? launch_rb_kt<32, true>(c1.kt, c.dil, p, l, s) : launch_rb_kt<32, false>(c1.kt, c.dil, p, l, s);
+    if (c1.cin == 64) return bf ? launch_rb_kt<64, true>(c1.kt, c.dil, p, l, s) : launch_rb_kt<64, false>(c1.kt, c.dil, p, l, s);
+    if (c1.cin == 128) return bf ? launch_rb_kt<128, true>(c1.kt, c.dil, p, l, s) : launch_rb_kt<128, false>(c1.kt, c.dil, p, l, s);
+    return bf ? launch_rb_kt<256, true>(c1.kt, c.dil, p, l, s) : launch_rb_kt<256, false>(c1.kt, c.dil, p, l, s);
 }
 
 }  // namespace vits

@@ -51,13 +51,13 @@ struct RbPair32Params {
 template <int KT, int DIL, int C>
 __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const RbPair32Params p) {
     constexpr int NCH = C / 32;  // 32-channel chunks
-    constexpr int WM = C / 32, WN = 4 / WM, NR = C >= 128 ? 4 : 2;  // (C = 128: four row tiles, every wave all 128 mid columns)
-    constexpr int BM = WN * NR * 32;   // mid columns (t) per block
-    constexpr int BO = BM - (KT - 1);  // output columns per block
+    constexpr RbPair32Geom GEO = rbpair32_geom(KT, DIL, C);  // (launch_plan.h: the planner reads the same)
+    constexpr int WN = GEO.wn, NR = GEO.nr;  // (C = 128: four row tiles, every wave all 128 mid columns)
+    constexpr int BO = GEO.bo;  // output columns per block (of GEO.bm mid columns)
     constexpr int P2 = (KT - 1) / 2, P1 = (KT - 1) * DIL / 2;
-    constexpr int XWP = (BM + (KT - 1) * DIL + 3 + 3) / 4 * 4;  // x tile row pitch (floats): + up to 3 columns of alignment shift
+    constexpr int XWP = GEO.xwp;  // x tile row pitch (floats): + up to 3 columns of alignment shift
     constexpr int XW4 = XWP / 4;
-    constexpr int TWP = (BM + KT - 1 + 3) / 4 * 4;  // t tile row pitch
+    constexpr int TWP = GEO.twp;  // t tile row pitch
     constexpr int TOTAL = NCH * KT * 4;             // A-fragment steps (float4 = 4 MFMA k-steps) per conv and row tile
     static_assert(TWP <= XWP, "the t tile takes the x tile's place");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // x tile [C][XWP], later t tile [C][TWP]
@@ -224,80 +224,45 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 template <int KT, int DIL, int C>
-static hipError_t launch_rb32(const RbPair32Params& p, int batch, hipStream_t s) {
-    constexpr int WN = 4 / (C / 32), BM = WN * (C >= 128 ? 4 : 2) * 32, BO = BM - (KT - 1);
-    constexpr int XWP = (BM + (KT - 1) * DIL + 3 + 3) / 4 * 4;
-    const size_t ldsz = ((size_t)C * XWP * sizeof(float) + 1023) / 1024 * 1024;  // (the last 1 KB DMA instruction may overhang the tile)
-    static BigLdsOnce big_lds_set;
-    if (ldsz > 64 * 1024 && big_lds_set.needed()) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpair32_kernel<KT, DIL, C>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ea != hipSuccess) return ea;
-        big_lds_set.done();
-    }
-    dim3 grid((p.tmax + BO - 1) / BO, batch);
-    VITS_KLAUNCH((rbpair32_kernel<KT, DIL, C>), grid, dim3(256), ldsz, s, p);
-    return hipGetLastError();
+static hipError_t launch_rb32(const RbPair32Params& p, const LaunchGrid& l, hipStream_t s) {
+    static_assert(rbpair32_exists(KT, DIL, C), "the planner would never ask for it");
+    return launch_lds<&rbpair32_kernel<KT, DIL, C>>(dim3(l.gx, l.gy), dim3(l.block), l.lds, s, p);
 }
 
 template <int KT, int C>
-static hipError_t launch_rb32_dil(int dil, const RbPair32Params& p, int batch, hipStream_t s) {
+static hipError_t launch_rb32_dil(int dil, const RbPair32Params& p, const LaunchGrid& l, hipStream_t s) {
     switch (dil) {
-        case 1: return launch_rb32<KT, 1, C>(p, batch, s);
-        case 3: return launch_rb32<KT, 3, C>(p, batch, s);
-        case 5: return launch_rb32<KT, 5, C>(p, batch, s);
+        case 1: return launch_rb32<KT, 1, C>(p, l, s);
+        case 3: return launch_rb32<KT, 3, C>(p, l, s);
+        case 5: return launch_rb32<KT, 5, C>(p, l, s);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <int C>
-static hipError_t launch_rb32_kt(int kt, int dil, const RbPair32Params& p, int batch, hipStream_t s) {
+static hipError_t launch_rb32_kt(int kt, int dil, const RbPair32Params& p, const LaunchGrid& l, hipStream_t s) {
     switch (kt) {
-        case 3: return launch_rb32_dil<3, C>(dil, p, batch, s);
-        case 7: return launch_rb32_dil<7, C>(dil, p, batch, s);
-        case 11: return launch_rb32_dil<11, C>(dil, p, batch, s);
+        case 3: return launch_rb32_dil<3, C>(dil, p, l, s);
+        case 7: return launch_rb32_dil<7, C>(dil, p, l, s);
+        case 11: return launch_rb32_dil<11, C>(dil, p, l, s);
         default: return hipErrorInvalidValue;
     }
 }
 
-bool rbpair32_supported(int channels, int kt, int dil) {
-    if (!(kt == 3 || kt == 7 || kt == 11)) return false;
-    if (!(dil == 1 || dil == 3 || dil == 5)) return false;
-    if (channels == 32 || channels == 64) return true;
-    // C = 128: only the k = 3 pairs — their 128-column tile with its small halo is 74 KB (two blocks per CU); k = 7 / 11 would be 84-94 KB
-    const bool c128 = kernel_knobs().fuse32_c128;
-    return channels == 128 && kt == 3 && c128;
-}
-
 hipError_t launch_rbpair32(const PackedConv& c1, const PackedConv& c2, const RbPair32Call& c, hipStream_t s) {
-    if (!c1.wp || !c2.wp || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !rbpair32_supported(c1.cin, c1.kt, c.dil) ||
+    const LaunchGrid l = plan_rbpair32(c1.cin, c1.kt, c.dil, c.batch, c.tmax);
+    if (!c1.wp || !c2.wp || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !l.ok ||
         !c1.bias || !c2.bias || c.x.p == c.y.p)
         return hipErrorInvalidValue;
     // 16-byte LDS-DMA: aligned rows
     if ((c.x.cs & 3) || (c.x.bs & 3) || (reinterpret_cast<uintptr_t>(c.x.p) & 15)) return hipErrorInvalidValue;
     RbPair32Params p;
-    p.x = c.x.p;
-    p.x_bs = c.x.bs;
-    p.x_cs = c.x.cs;
-    p.w1 = c1.wp;
-    p.w2 = c2.wp;
-    p.b1 = c1.bias;
-    p.b2 = c2.bias;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    p.slope = c.slope;
-    p.y = c.y.p;
-    p.y_bs = c.y.bs;
-    p.y_cs = c.y.cs;
-    p.acc = c.acc.p;
-    p.a_bs = c.acc.bs;
-    p.a_cs = c.acc.cs;
-    p.scale = c.scale;
-    p.scale_div = c.scale_div;
-    p.post_act = c.post_act;
-    p.post_slope = c.post_slope;
-    if (c1.cin == 32) return launch_rb32_kt<32>(c1.kt, c.dil, p, c.batch, s);
-    if (c1.cin == 64) return launch_rb32_kt<64>(c1.kt, c.dil, p, c.batch, s);
-    return launch_rb32_dil<3, 128>(c.dil, p, c.batch, s);
+    p.x = c.x.p, p.x_bs = c.x.bs, p.x_cs = c.x.cs, p.w1 = c1.wp, p.w2 = c2.wp, p.b1 = c1.bias, p.b2 = c2.bias, p.lens = c.lens, p.tmax = c.tmax;
+    p.slope = c.slope, p.y = c.y.p, p.y_bs = c.y.bs, p.y_cs = c.y.cs, p.acc = c.acc.p, p.a_bs = c.acc.bs, p.a_cs = c.acc.cs, p.scale = c.scale;
+    p.scale_div = c.scale_div, p.post_act = c.post_act, p.post_slope = c.post_slope;
+    if (c1.cin == 32) return launch_rb32_kt<32>(c1.kt, c.dil, p, l, s);
+    if (c1.cin == 64) return launch_rb32_kt<64>(c1.kt, c.dil, p, l, s);
+    return launch_rb32_dil<3, 128>(c.dil, p, l, s);
 }
 
 }  // namespace vits

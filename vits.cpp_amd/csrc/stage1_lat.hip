@@ -31,8 +31,8 @@ namespace vits {
 
 namespace {
 
-constexpr int LAT_NT = 16;      // tokens per block = one MFMA column tile
-constexpr int LAT_GROUPS = 16;  // LayerNorm channel groups (add_layer_norm_kernel / dds_layer_kernel: LN_GROUPS)
+constexpr int LAT_NT = kLatNT;      // tokens per block = one MFMA column tile
+constexpr int LAT_GROUPS = kLnGroups;  // LayerNorm channel groups (add_layer_norm_kernel / dds_layer_kernel: LN_GROUPS)
 
 }  // namespace
 
@@ -313,20 +313,6 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
     }
 }
 
-static size_t dds_lat_lds(int H, int k, int dil, int head, int h_cin) {
-    const int xw = LAT_NT + (k * dil - dil);
-    size_t f = ((size_t)H * xw + 3) / 4 * 4 + (size_t)H * LAT_NT + 2 * LAT_GROUPS * LAT_NT + ((size_t)H * (6 + k) + 3) / 4 * 4;
-    if (head == DDS_HEAD_CONV) f += (size_t)h_cin * ((xw + 15) & ~15);
-    return f * sizeof(float);
-}
-
-bool dds_layer_lat_supported(const PackedConv& pw, int channels, int k, int dil) {
-    if (channels < 32 || (channels & 31) || channels > 256) return false;
-    if (pw.cin != channels || pw.cout != channels || pw.kt != 1 || pw.epi != EPI_STD || !pw.bias || !pw.wp_l16) return false;
-    if (k < 1 || dil < 1 || ((k * dil - dil) & 1)) return false;
-    return dds_lat_lds(channels, k, dil, DDS_HEAD_CONV, channels) <= 150 * 1024;
-}
-
 hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s) {
     const PackedConv& pw = *c.pw;
     if (!dds_layer_lat_supported(pw, c.channels, c.k, c.dil)) return hipErrorInvalidValue;
@@ -368,22 +354,13 @@ hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s) {
         if (!c.y.p || c.y.p == c.x.p) return hipErrorInvalidValue;
         p.y = c.y.p, p.y_bs = c.y.bs, p.y_cs = c.y.cs;
     }
-    const size_t lds = dds_lat_lds(c.channels, c.k, c.dil, head, c.channels);
-    dim3 grid((c.tmax + LAT_NT - 1) / LAT_NT, c.batch);
-    const dim3 block(c.channels / 16 * 64);
-#define VITS_DDSL(HD, TL, M)                                                                                                                 \
-    do {                                                                                                                                     \
-        static BigLdsOnce big;                                                                                                               \
-        if (lds > 64 * 1024 && big.needed()) {                                                                                               \
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dds_layer_lat_kernel<HD, TL, M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) \
-                return e;                                                                                                                    \
-            big.done();                                                                                                                      \
-        }                                                                                                                                    \
-        VITS_KLAUNCH((dds_layer_lat_kernel<HD, TL, M>), grid, block, lds, s, p);                                                             \
-    } while (0)
+    const DdsLayerPlan l = plan_dds_layer_lat(c.channels, c.k, c.dil, head == DDS_HEAD_CONV, c.batch, c.tmax);
+    const size_t lds = l.lds;
+    const dim3 grid(l.gx, l.gy), block(l.block);
+#define VITS_DDSL(HD, TL, M) return launch_lds<&dds_layer_lat_kernel<HD, TL, M>>(grid, block, lds, s, p)
 #define VITS_DDSL_M(HD, TL)                           \
     do {                                              \
-        if (c.channels <= 192) VITS_DDSL(HD, TL, 6);  \
+        if (l.m == 6) VITS_DDSL(HD, TL, 6);           \
         else VITS_DDSL(HD, TL, 8);                    \
     } while (0)
     if (head == DDS_HEAD_NONE && tail == DDS_TAIL_NONE) VITS_DDSL_M(DDS_HEAD_NONE, DDS_TAIL_NONE);
@@ -394,7 +371,6 @@ hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s) {
     else VITS_DDSL_M(DDS_HEAD_CONV, DDS_TAIL_PROJ);
 #undef VITS_DDSL_M
 #undef VITS_DDSL
-    return hipGetLastError();
 }
 
 }  // namespace vits

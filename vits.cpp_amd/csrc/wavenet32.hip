@@ -52,7 +52,8 @@ __global__ __launch_bounds__(4 * H, 1) void wavenet32_kernel(const WaveNet32Para
     constexpr int NR = 1;        // 32-frame column tiles per wave
     constexpr int BM = NC * 32;  // frames per block
     constexpr int P = (KT - 1) / 2;
-    constexpr int XWP = (BM + KT - 1 + 3 + 3) / 4 * 4;  // h tile row pitch (floats): + up to 3 columns of alignment shift
+    static_assert(BM == kWaveNetBM, "launch_plan.h: the planner's block");
+    constexpr int XWP = wavenet32_xwp(KT);  // h tile row pitch (floats): + up to 3 columns of alignment shift
     constexpr int XW4 = XWP / 4;
     constexpr int TWP = BM;              // acts tile row pitch
     constexpr int TOTAL1 = NCH * KT * 4;  // A-fragment steps of the gated conv per row tile
@@ -286,7 +287,8 @@ __global__ __launch_bounds__(4 * H / NCW, 1) void wavenet16_kernel(const WaveNet
     constexpr int NCH = H / 32;
     constexpr int BM = NC * 32;
     constexpr int P = (KT - 1) / 2;
-    constexpr int XS = BM + KT - 1;  // slots per group row of the h tile
+    static_assert(BM == kWaveNetBM, "launch_plan.h: the planner's block");
+    constexpr int XS = wavenet16_xs(KT);  // slots per group row of the h tile
     constexpr int TOTAL1 = NCH * KT * 2, TOTAL2 = NCH * 2;  // A-fragment steps per row tile
     extern __shared__ __attribute__((aligned(16))) int4v l16[];
     int4v* xs = l16;  // [G][XS]
@@ -518,7 +520,8 @@ struct FlowCouple16Params {
 // the columns in a third of the time. Same chains and expressions per output: bit-identical.
 template <bool BF, int NCW, int NCT>
 __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(const FlowCouple16Params p) {
-    constexpr int H = 192, HF = 96, KT = 5, NL = 4, NG = H / 32, BM = 32 * NCT, HALO = 8, BO = BM - 2 * HALO, P = (KT - 1) / 2, XS = BM + KT - 1;
+    constexpr FlowCouple16Geom GEO = flow_couple16_geom(NCW, NCT);  // (launch_plan.h: the planner reads the same)
+    constexpr int H = 192, HF = 96, KT = 5, NL = 4, NG = H / 32, BM = GEO.bm, HALO = GEO.halo, BO = GEO.bo, P = (KT - 1) / 2, XS = GEO.xs;
     constexpr int NGRP = H / 8;  // 16-byte channel groups of an H-channel tile
     constexpr int NTH = 64 * NG * NCT / NCW;
     static_assert(NCW <= NCT, "a wave owns at most the block's column tiles");
@@ -790,7 +793,7 @@ __global__ __launch_bounds__(64 * 6 * NCT / NCW, 1) void flow_couple16_kernel(co
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 bool wavenet32_supported(int hidden, int kt, int dil, const PackedConv& in, const PackedConv& rs) {
-    if (hidden != 192 || kt != 5 || dil != 1) return false;
+    if (!plan_wavenet32(hidden, kt, dil, 1, 1).ok) return false;
     if (!in.wp || !rs.wp || !in.bias || !rs.bias || in.epi != EPI_GATE || rs.epi != EPI_STD) return false;
     if (in.cin != hidden || in.cout != 2 * hidden || in.kt != kt || rs.cin != hidden || rs.kt != 1) return false;
     return rs.cout == 2 * hidden || rs.cout == hidden;
@@ -802,33 +805,15 @@ hipError_t launch_wavenet32(const PackedConv& in, const PackedConv& rs, const Wa
     if ((c.h.cs & 3) || (c.h.bs & 3) || (reinterpret_cast<uintptr_t>(c.h.p) & 15)) return hipErrorInvalidValue;
     if (rs.cout == 2 * H && (!c.h_out.p || c.h_out.p == c.h.p)) return hipErrorInvalidValue;
     WaveNet32Params p;
-    p.h = c.h.p;
-    p.h_bs = c.h.bs;
-    p.h_cs = c.h.cs;
-    p.h_out = c.h_out.p;
-    p.ho_bs = c.h_out.bs;
-    p.ho_cs = c.h_out.cs;
-    p.outputs = c.outputs.p;
-    p.o_bs = c.outputs.bs;
-    p.o_cs = c.outputs.cs;
-    p.w_in = in.wp;
-    p.b_in = in.bias;
-    p.bias_rows = in.bias_rs ? c.spk : nullptr;
-    p.bias_rs = in.bias_rs;
-    p.w_rs = rs.wp;
-    p.b_rs = rs.bias;
-    p.rs_rows = rs.cout;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    constexpr int XWP = (64 + KT - 1 + 3 + 3) / 4 * 4;
-    const size_t ldsz = ((size_t)H * XWP * sizeof(float) + 1023) / 1024 * 1024;
-    dim3 grid((c.tmax + 63) / 64, c.batch);
-    VITS_KLAUNCH((wavenet32_kernel<H, KT>), grid, dim3(4 * H), ldsz, s, p);
-    return hipGetLastError();
+    p.h = c.h.p, p.h_bs = c.h.bs, p.h_cs = c.h.cs, p.h_out = c.h_out.p, p.ho_bs = c.h_out.bs, p.ho_cs = c.h_out.cs, p.outputs = c.outputs.p;
+    p.o_bs = c.outputs.bs, p.o_cs = c.outputs.cs, p.w_in = in.wp, p.b_in = in.bias, p.bias_rows = in.bias_rs ? c.spk : nullptr;
+    p.bias_rs = in.bias_rs, p.w_rs = rs.wp, p.b_rs = rs.bias, p.rs_rows = rs.cout, p.lens = c.lens, p.tmax = c.tmax;
+    const WaveNetPlan l = plan_wavenet32(c.hidden, in.kt, c.dil, c.batch, c.tmax);
+    return launch_lds<&wavenet32_kernel<H, KT>>(dim3(l.gx, l.gy), dim3(l.block), l.lds, s, p);
 }
 
 bool wavenet16_supported(int hidden, int kt, int dil, const PackedConv& in, const PackedConv& rs) {
-    if (hidden != 192 || kt != 5 || dil != 1) return false;
+    if (!plan_wavenet16(hidden, kt, dil, 1, 1).ok) return false;
     if (!in.wp16 || !rs.wp16 || !in.bias || !rs.bias || in.epi != EPI_GATE || rs.epi != EPI_STD) return false;
     if (in.cin != hidden || in.cout != 2 * hidden || in.kt != kt || rs.cin != hidden || rs.kt != 1) return false;
     return rs.cout == 2 * hidden || rs.cout == hidden;
@@ -839,41 +824,20 @@ hipError_t launch_wavenet16(const PackedConv& in, const PackedConv& rs, const Wa
     if (!wavenet16_supported(c.hidden, in.kt, c.dil, in, rs) || arith == VITS_ARITH_F32) return hipErrorInvalidValue;
     if (rs.cout == 2 * H && (!c.h_out.p || c.h_out.p == c.h.p)) return hipErrorInvalidValue;
     WaveNet16Params p;
-    p.f.h = c.h.p;
-    p.f.h_bs = c.h.bs;
-    p.f.h_cs = c.h.cs;
-    p.f.h_out = c.h_out.p;
-    p.f.ho_bs = c.h_out.bs;
-    p.f.ho_cs = c.h_out.cs;
-    p.f.outputs = c.outputs.p;
-    p.f.o_bs = c.outputs.bs;
-    p.f.o_cs = c.outputs.cs;
-    p.f.w_in = nullptr;
-    p.f.b_in = in.bias;
-    p.f.bias_rows = in.bias_rs ? c.spk : nullptr;
-    p.f.bias_rs = in.bias_rs;
-    p.f.w_rs = nullptr;
-    p.f.b_rs = rs.bias;
-    p.f.rs_rows = rs.cout;
-    p.f.lens = c.lens;
-    p.f.tmax = c.tmax;
-    p.w_in16 = in.wp16;
-    p.w_rs16 = rs.wp16;
-    const size_t ldsz = (size_t)(H / 8) * (64 + KT - 1) * 16;
-    dim3 grid((c.tmax + 63) / 64, c.batch);
-    const int ncw = kernel_knobs().wn16_ncw;  // (2: six waves, both column tiles each — measured 40.6 vs 38.4 us per layer)
-    if (ncw == 1) {
-        if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((wavenet16_kernel<H, KT, true, 1>), grid, dim3(4 * H), ldsz, s, p);
-        else VITS_KLAUNCH((wavenet16_kernel<H, KT, false, 1>), grid, dim3(4 * H), ldsz, s, p);
-    } else {
-        if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((wavenet16_kernel<H, KT, true, 2>), grid, dim3(2 * H), ldsz, s, p);
-        else VITS_KLAUNCH((wavenet16_kernel<H, KT, false, 2>), grid, dim3(2 * H), ldsz, s, p);
-    }
-    return hipGetLastError();
+    p.f.h = c.h.p, p.f.h_bs = c.h.bs, p.f.h_cs = c.h.cs, p.f.h_out = c.h_out.p, p.f.ho_bs = c.h_out.bs, p.f.ho_cs = c.h_out.cs;
+    p.f.outputs = c.outputs.p, p.f.o_bs = c.outputs.bs, p.f.o_cs = c.outputs.cs, p.f.w_in = nullptr, p.f.b_in = in.bias;
+    p.f.bias_rows = in.bias_rs ? c.spk : nullptr, p.f.bias_rs = in.bias_rs, p.f.w_rs = nullptr, p.f.b_rs = rs.bias, p.f.rs_rows = rs.cout;
+    p.f.lens = c.lens, p.f.tmax = c.tmax, p.w_in16 = in.wp16, p.w_rs16 = rs.wp16;
+    const WaveNetPlan l = plan_wavenet16(c.hidden, in.kt, c.dil, c.batch, c.tmax);
+    const dim3 grid(l.gx, l.gy), block(l.block);
+    const bool bf = arith == VITS_ARITH_BF16;
+    static_assert(wavenet16_exists(1) && wavenet16_exists(2), "the planner's predicate");
+    if (l.ncw == 1) return bf ? launch_lds<&wavenet16_kernel<H, KT, true, 1>>(grid, block, l.lds, s, p) : launch_lds<&wavenet16_kernel<H, KT, false, 1>>(grid, block, l.lds, s, p);
+    return bf ? launch_lds<&wavenet16_kernel<H, KT, true, 2>>(grid, block, l.lds, s, p) : launch_lds<&wavenet16_kernel<H, KT, false, 2>>(grid, block, l.lds, s, p);
 }
 
 bool flow_couple16_supported(int hidden, int half, int kt, int rate, int layers, const PackedConv& pre, const PackedConv* in, const PackedConv* rs, const PackedConv& post) {
-    if (hidden != 192 || half != 96 || kt != 5 || rate != 1 || layers != 4) return false;
+    if (!plan_flow_couple16(hidden, half, kt, rate, layers, 1, 1).ok) return false;
     if (!pre.wp16 || !pre.bias || pre.cin != half || pre.cout != hidden || pre.kt != 1 || pre.epi != EPI_STD) return false;
     if (!post.wp16 || !post.bias || post.cin != hidden || post.cout != half || post.kt != 1 || post.epi != EPI_STD) return false;
     for (int l = 0; l < layers; ++l) {
@@ -887,16 +851,8 @@ hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, con
                                 hipStream_t s) {
     if (arith == VITS_ARITH_F32 || !flow_couple16_supported(c.hidden, c.half, 5, 1, 4, pre, in, rs, post) || !c.x0.p || !c.x1.p) return hipErrorInvalidValue;
     FlowCouple16Params p;
-    p.x0 = c.x0.p;
-    p.x0_bs = c.x0.bs;
-    p.x0_cs = c.x0.cs;
-    p.x1 = c.x1.p;
-    p.x1_bs = c.x1.bs;
-    p.x1_cs = c.x1.cs;
-    p.w_pre = pre.wp16;
-    p.b_pre = pre.bias;
-    p.bias_rows = in[0].bias_rs ? c.spk : nullptr;
-    p.bias_rs = in[0].bias_rs;
+    p.x0 = c.x0.p, p.x0_bs = c.x0.bs, p.x0_cs = c.x0.cs, p.x1 = c.x1.p, p.x1_bs = c.x1.bs, p.x1_cs = c.x1.cs, p.w_pre = pre.wp16, p.b_pre = pre.bias;
+    p.bias_rows = in[0].bias_rs ? c.spk : nullptr, p.bias_rs = in[0].bias_rs;
     for (int l = 0; l < 4; ++l) {
         if (in[l].bias_rs != in[0].bias_rs) return hipErrorInvalidValue;  // (one table: every layer has the same row stride)
         p.w_in[l] = in[l].wp16;
@@ -904,32 +860,19 @@ hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, con
         p.w_rs[l] = rs[l].wp16;
         p.b_rs[l] = rs[l].bias;
     }
-    p.w_post = post.wp16;
-    p.b_post = post.bias;
-    p.lens = c.lens;
-    p.tmax = c.tmax;
-    constexpr int H = 192, NGRP = H / 8, LB_N = H + 2 * 4 * 2 * H + 96;
-    // small grids (batch 1 ... 4 at 225 frames): 16-frame blocks on one 32-column tile (see the kernel)
-    const int64_t wide_blocks = (int64_t)((c.tmax + 47) / 48) * c.batch;
-    if (wide_blocks <= kernel_knobs().flow_narrow_max) {
-        const size_t ldsz = (size_t)(NGRP * (32 + 4) + NGRP * 32) * 16 + (size_t)LB_N * 4;
-        dim3 grid((c.tmax + 15) / 16, c.batch);
-        if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((flow_couple16_kernel<true, 1, 1>), grid, dim3(384), ldsz, s, p);
-        else VITS_KLAUNCH((flow_couple16_kernel<false, 1, 1>), grid, dim3(384), ldsz, s, p);
-        return hipGetLastError();
-    }
-    const size_t ldsz = (size_t)(NGRP * (64 + 4) + NGRP * 64) * 16 + (size_t)LB_N * 4;
-    // six waves owning both column tiles of their channel group (VITS_FLOW_NCW=1: twelve waves, one column tile each)
-    const int ncw = kernel_knobs().flow_ncw;
-    dim3 grid((c.tmax + 47) / 48, c.batch);
-    if (ncw == 1) {
-        if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((flow_couple16_kernel<true, 1, 2>), grid, dim3(768), ldsz, s, p);
-        else VITS_KLAUNCH((flow_couple16_kernel<false, 1, 2>), grid, dim3(768), ldsz, s, p);
-    } else {
-        if (arith == VITS_ARITH_BF16) VITS_KLAUNCH((flow_couple16_kernel<true, 2, 2>), grid, dim3(384), ldsz, s, p);
-        else VITS_KLAUNCH((flow_couple16_kernel<false, 2, 2>), grid, dim3(384), ldsz, s, p);
-    }
-    return hipGetLastError();
+    p.w_post = post.wp16, p.b_post = post.bias, p.lens = c.lens, p.tmax = c.tmax;
+    const FlowCouple16Plan l = plan_flow_couple16(c.hidden, c.half, in[0].kt, 1, 4, c.batch, c.tmax);  // (rate 1, four layers: what the call's arrays hold and the kernel is built for)
+    const dim3 grid(l.gx, l.gy), block(l.block);
+    const bool bf = arith == VITS_ARITH_BF16;
+#define VITS_FLOW_GO(NCW, NCT)                                                     \
+    static_assert(flow_couple16_exists(NCW, NCT), "the planner's predicate");      \
+    if (l.ncw == NCW && l.nct == NCT)                                              \
+        return bf ? launch_lds<&flow_couple16_kernel<true, NCW, NCT>>(grid, block, l.lds, s, p) : launch_lds<&flow_couple16_kernel<false, NCW, NCT>>(grid, block, l.lds, s, p)
+    VITS_FLOW_GO(1, 1);
+    VITS_FLOW_GO(1, 2);
+    VITS_FLOW_GO(2, 2);
+#undef VITS_FLOW_GO
+    return hipErrorInvalidValue;
 }
 
 }  // namespace vits
