@@ -246,9 +246,10 @@ typedef struct vits_process_opts {
      * outside [0, 10], an override outside [-1, 10000], speaking_rates or duration_override with fixed_duration > 0. */
     const float* speaking_rates;        /* [B]: d = ceil(exp(logw) * (float)(1.0 / rate)) (vits.cpp:996) */
     const float* noise_scales;          /* [B]: scale of the prior draw (vits.cpp:1061) */
-    const float* noise_scale_durations; /* [B]: scale of the [2][T] duration draw (vits.cpp:948-949) */
+    const float* noise_scale_durations; /* [B]: scale of the [2][T] duration draw (vits.cpp:948-949). Validated as always and without effect on a
+                                           model with the deterministic duration predictor, which draws nothing */
     const int32_t* duration_override;   /* [B][id_stride]: >= 0: token t of utterance b lasts that many frames; -1: the predicted duration
-                                           (scaled by the utterance's rate). The predictor still runs and still draws its noise. Frames
+                                           (scaled by the utterance's rate). The predictor still runs and (the stochastic one) still draws its noise. Frames
                                            L = max(1, sum of d), as always. */
     int32_t* durations_out;             /* [B][id_stride]: receives the frames of every token as used, 0 past id_lengths[b]. Filled before
                                            the call returns, before the first on_chunk call, and (vits_model_submit_batch) no later than the
@@ -259,7 +260,9 @@ typedef struct vits_process_opts {
 /* The model-level prosody: what vits_model_process, vits_model_process_ids and every call whose prosody arrays are NULL use. Initially the
  * model file's speaking_rate, noise_scale and noise_scale_duration. Returns 0, or -1 (the handle keeps its values) for a rate that is not
  * finite or outside [0.1, 10], or a noise scale that is not finite or outside [0, 10]. Voice conversion ignores these values (it has no
- * duration prediction, and VITS's posterior draw has no noise scale); vits_model_convert_batch refuses the five per-utterance fields. */
+ * duration prediction, and VITS's posterior draw has no noise scale); vits_model_convert_batch refuses the five per-utterance fields.
+ * On a model with the deterministic duration predictor (vits_model_duration_predictor_kind == 1) noise_scale_duration is validated
+ * and stored as always and has no effect: that predictor draws no noise. */
 VITS_API int vits_model_set_prosody(vits_model* model, float speaking_rate, float noise_scale, float noise_scale_duration);
 VITS_API int vits_model_get_prosody(const vits_model* model, float* speaking_rate, float* noise_scale, float* noise_scale_duration);
 
@@ -414,11 +417,27 @@ VITS_API int64_t vits_model_tokenize(vits_model* model, const char* text, int32_
 VITS_API int32_t vits_model_sampling_rate(const vits_model* model);
 VITS_API int32_t vits_model_vocab_size(const vits_model* model);
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model);
+/* The model's duration predictor: 0 = the stochastic, flow-based one (use_stochastic_duration_prediction = True), 1 = the deterministic one
+ * (False: transformers VitsDurationPredictor), -1 for NULL. A deterministic model computes, per utterance of T tokens with text-encoder output
+ * x [H][T] and speaker embedding g (or none, speaker -1):
+ *   x'[c][t] = x[c][t] + (cond.W g + cond.b)[c] for 0 <= t < T, 0 outside            (the speaker term is added to the INPUT of a padded conv: the
+ *                                                                                     first and last k / 2 tokens see zeros, not cond(g), beyond the ends)
+ *   a1 = LayerNorm_channels(relu(conv_1(x'))), a2 = LayerNorm_channels(relu(conv_2(a1))), each 0 outside [0, T); logw = proj(a2)
+ *   d[t] = ceil(exp(logw[t]) * length_scale), with duration_override and fixed_duration as for the stochastic predictor
+ * in fp32 in every VITS_ARITH_* mode and both arithmetic scopes, the same in VITS_MODE_REFERENCE and VITS_MODE_HF (the reference refuses such
+ * models, vits.cpp:993: there is no reference arithmetic to reproduce). It draws NO noise: VITS_NOISE_REFERENCE does not advance the
+ * process-global stream for a duration draw, VITS_NOISE_EXPLICIT does not need noise_dur, "noise_dur" is not a tap, and noise_scale_duration
+ * (vits_model_set_prosody, opts.noise_scale_durations) is validated and has no effect. One fused kernel where an instantiation exists
+ * ((hidden, filter, k) = (192, 256, 3), (192, 256, 5), (16, 32, 3)), bit for bit the un-fused sequence of existing kernels that every other shape
+ * runs; VITS_NO_DP_DET_FUSE (read at load) forces the un-fused sequence, VITS_DP_DET_LAT_MAX_BLOCKS moves the threshold between the kernel's
+ * two tiles (default 96 blocks of 16 tokens). vits_model_set_ggml_tables(model, 1) — stage one in the exact order shared with the oracle, which
+ * has no such predictor — makes calls on such a model fail with a message saying so; mode 2 (the attention soft-max only) is allowed. */
+VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model);
 
 /* Stage outputs of the LAST call with collect_taps=1, for utterance `utt`, copied to host as a dense
  * [channels][len] fp32 array. Names: "enc_out" [192][T], "prior_mean" [192][T], "prior_logvar" [192][T],
  * "log_duration" [1][T], "durations" [1][T] (integer-valued), "z_p" [192][L], "z_flow" [192][L],
- * "pre_tanh" [1][S], "waveform" [1][S], plus "noise_dur" [2][T] and "noise_prior" [192][L].
+ * "pre_tanh" [1][S], "waveform" [1][S], plus "noise_dur" [2][T] (stochastic duration predictor only) and "noise_prior" [192][L].
  * Returns the element count (0 = unknown tap), copies min(count, cap) floats. */
 VITS_API int64_t vits_model_get_tap(vits_model* model, const char* name, int32_t utt, float* dst, size_t cap);
 
@@ -433,6 +452,9 @@ VITS_API int64_t vits_model_get_tap(vits_model* model, const char* name, int32_t
                                      tensors of the model without the flag, unchanged, then embed_speaker and the three kinds of cond layers */
 #define VITS_SYNTH_POSTERIOR 0x400 /* OR-ed in: append posterior_encoder.* (transformers names and shapes; FULL: 513 bins, 16 WaveNet layers;
                                       TINY: 9 bins, 2 layers) behind every other tensor, for voice conversion */
+#define VITS_SYNTH_DETERMINISTIC 0x800 /* OR-ed in: the deterministic duration predictor (use_stochastic_duration_prediction = False; filter channels
+                                          FULL 256, TINY 32) in the stochastic one's place; every other tensor keeps its name, place and values.
+                                          duration_predictor_filter_channels is written only when it is not 256, as the exporter does */
 VITS_API int vits_synth_model_bytes(uint64_t seed, int32_t arch, char** bytes, size_t* size);
 VITS_API void vits_free_bytes(char* bytes);
 /* Parse a model file and write it back (host only): byte-exact round trip of the reference's format
@@ -518,6 +540,23 @@ VITS_API int vits_op_rel_attention(int32_t batch, int32_t heads, int32_t head_di
 VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, int32_t t_stride, float eps,
                                     const float* x, const float* residual, const float* gamma, const float* beta,
                                     float* y);
+
+/* The deterministic duration predictor (see vits_model_duration_predictor_kind) on caller-supplied tensors, fp32:
+ *   logw = proj(LN2(relu(conv_2(LN1(relu(conv_1(x + spk_row))))))), x + spk_row inside [0, lens[b]) and 0 outside, LN outputs 0 outside.
+ * x host [batch][hidden][t_stride]; w1 [filter][hidden][k], w2 [filter][filter][k], wp [1][filter][1] (torch layout); b1, b2 [filter], bp [1];
+ * g1, be1, g2, be2 [filter] (LayerNorm weight and bias); spk_rows host [batch][hidden] (utterance b's speaker term) or NULL (none); lens may be
+ * NULL; logw out, host [batch][t_stride], entries t < lens[b] written. variant: 0 = the planner's choice, 1 = the fused kernel's 16-token tile,
+ * 2 = its wide tile, 3 = the un-fused sequence (row add, conv, LayerNorm, conv, LayerNorm, 1x1 conv). Variants 1 and 2 return -1 with a message
+ * for a (hidden, filter, k) without an instantiation: they never fall back. All variants give the same bits. The staging buffer of x is filled
+ * with NaNs behind each lens[b] before the valid part is uploaded, so a read past an utterance shows in the result. */
+typedef struct vits_duration_predictor_desc {
+    int32_t batch, hidden, filter, t, t_stride, k;
+    float eps;
+    int32_t variant;
+} vits_duration_predictor_desc;
+VITS_API int vits_op_duration_predictor(const vits_duration_predictor_desc* d, const float* x, const float* w1, const float* b1, const float* g1,
+                                        const float* be1, const float* w2, const float* b2, const float* g2, const float* be2, const float* wp,
+                                        const float* bp, const float* spk_rows, const int32_t* lens, float* logw);
 
 /* The alignment kernels (align_logp + align_mas; see vits_model_align_batch) on caller-supplied statistics: m, ls host [batch][F][Tmax] (prior mean and
  * log-deviation per token), z host [batch][F][Lmax], Tmax = max T[b], Lmax = max L[b], 1 <= T[b] <= L[b]. durations: out, host [batch][Tmax] (0 past

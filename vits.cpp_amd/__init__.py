@@ -21,6 +21,9 @@ LIB_PATH = os.environ.get("VITS_HIP_LIB", os.path.join(_HERE, "csrc", "libvits_h
 MODE_DEFAULT, MODE_REFERENCE, MODE_HF = -1, 0, 1
 NOISE_REFERENCE, NOISE_COUNTER, NOISE_EXPLICIT = 0, 1, 2
 SYNTH_FULL, SYNTH_TINY, SYNTH_BF16, SYNTH_SPEAKERS, SYNTH_POSTERIOR = 0, 1, 0x100, 0x200, 0x400
+SYNTH_DETERMINISTIC = 0x800  # OR-ed in: the deterministic duration predictor in the stochastic one's place
+DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
+DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
@@ -44,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
+    "vits_model_duration_predictor_kind", "vits_op_duration_predictor",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -83,6 +87,11 @@ class Conv1dDesc(C.Structure):
 class ResblockPairDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32),
                 ("dilation", C.c_int32), ("slope", C.c_float)]
+
+
+class DurationPredictorDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("hidden", C.c_int32), ("filter", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32),
+                ("k", C.c_int32), ("eps", C.c_float), ("variant", C.c_int32)]
 
 
 class ConvT1dDesc(C.Structure):
@@ -220,6 +229,10 @@ def lib():
     L.vits_model_vocab_size.argtypes = [vp]
     L.vits_model_weight_bytes.restype = i64
     L.vits_model_weight_bytes.argtypes = [vp]
+    L.vits_model_duration_predictor_kind.restype = i32
+    L.vits_model_duration_predictor_kind.argtypes = [vp]
+    L.vits_op_duration_predictor.restype = i32
+    L.vits_op_duration_predictor.argtypes = [vp] * 15
     L.vits_model_get_tap.restype = i64
     L.vits_model_get_tap.argtypes = [vp, C.c_char_p, i32, f32p, sz]
     L.vits_synth_model_bytes.restype = i32
@@ -665,6 +678,12 @@ class Model:
     def weight_bytes(self):
         return lib().vits_model_weight_bytes(self._h)
 
+    @property
+    def duration_predictor_kind(self):
+        """DP_STOCHASTIC (0), or DP_DETERMINISTIC (1): use_stochastic_duration_prediction = False — durations without noise (noise_scale_duration is
+        validated and has no effect, "noise_dur" is no tap, NOISE_EXPLICIT needs no noise_dur)."""
+        return lib().vits_model_duration_predictor_kind(self._h)
+
     def tokenize(self, text):
         buf = np.zeros(4 * len(text.encode("utf-8")) + 8, np.int32)
         n = lib().vits_model_tokenize(self._h, text.encode("utf-8"), _ptr(buf), buf.size)
@@ -916,6 +935,28 @@ def op_resblock_pair(x, w1, b1, w2, b2, dilation, slope, lens=None):
     y = np.zeros((B, ch, T), np.float32)
     lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
     if lib().vits_op_resblock_pair(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(lens), _ptr(y)) != 0:
+        raise VitsError(last_error())
+    return y
+
+
+def op_duration_predictor(x, w1, b1, g1, be1, w2, b2, g2, be2, wp, bp, spk_rows=None, lens=None, eps=1e-5, variant=DP_VARIANT_PLAN, t=None):
+    """The deterministic duration predictor on caller-supplied tensors (vits_op_duration_predictor): x [B, H, t_stride], w1 [Fc, H, k], w2 [Fc, Fc, k],
+    wp [1, Fc, 1], spk_rows [B, H] or None, lens [B] or None, t = the longest utterance (default: t_stride). variant: DP_VARIANT_PLAN | _LAT | _WIDE (the fused
+    kernel's tiles, or a VitsError: never another path) | _UNFUSED. Returns logw [B, t_stride], zeros where nothing was written."""
+    x, w1, w2, wp = _f32(x), _f32(w1), _f32(w2), _f32(wp)
+    B, H, ts = x.shape
+    Fc, _, k = w1.shape
+    assert w1.shape == (Fc, H, k) and w2.shape == (Fc, Fc, k) and wp.size == Fc
+    vec = [_f32(v).reshape(-1) for v in (b1, g1, be1, b2, g2, be2)]
+    assert all(v.size == Fc for v in vec)
+    b1, g1, be1, b2, g2, be2 = vec
+    bp = _f32(bp).reshape(-1)
+    spk_rows = None if spk_rows is None else _f32(spk_rows).reshape(B, H)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    d = DurationPredictorDesc(B, H, Fc, ts if t is None else t, ts, k, eps, variant)
+    y = np.zeros((B, ts), np.float32)
+    if lib().vits_op_duration_predictor(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(g1), _ptr(be1), _ptr(w2), _ptr(b2), _ptr(g2), _ptr(be2), _ptr(wp), _ptr(bp),
+                                        _ptr(spk_rows), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
 

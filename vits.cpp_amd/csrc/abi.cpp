@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <fstream>
 #include <new>
 #include <string>
@@ -570,6 +571,7 @@ VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t
 }
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
+VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }
 
 VITS_API int64_t vits_model_get_tap(vits_model* model, const char* name, int32_t utt, float* dst, size_t cap) {
     VITS_TRY
@@ -1148,6 +1150,70 @@ VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipMemcpy(y, dy.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_duration_predictor(const vits_duration_predictor_desc* d, const float* x, const float* w1, const float* b1, const float* g1, const float* be1,
+                                        const float* w2, const float* b2, const float* g2, const float* be2, const float* wp, const float* bp, const float* spk_rows,
+                                        const int32_t* lens, float* logw) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !w1 || !b1 || !g1 || !be1 || !w2 || !b2 || !g2 || !be2 || !wp || !bp || !logw) return fail("vits_op_duration_predictor: null argument");
+    const int B = d->batch, H = d->hidden, Fc = d->filter, T = d->t, ts = d->t_stride, k = d->k;
+    if (B < 1 || H < 1 || Fc < 1 || T < 1 || ts < T || k < 1 || !(k & 1)) return fail("vits_op_duration_predictor: batch, hidden, filter, t >= 1, t <= t_stride and an odd k are required");
+    if (d->variant < 0 || d->variant > 3) return fail("vits_op_duration_predictor: variant 0 (planner), 1 (16-token tile), 2 (wide tile) or 3 (un-fused)");
+    if (!split_lens_ok(lens, B, T, ts)) return fail("vits_op_duration_predictor: 0 <= lens[b] <= t <= t_stride is required");
+    const DpDetPlan plan = plan_dp_det(H, Fc, k, B, T, d->variant);
+    if ((d->variant == 1 || d->variant == 2) && !plan.ok)
+        return fail(("vits_op_duration_predictor: the fused kernel has no instantiation for hidden " + std::to_string(H) + ", filter " + std::to_string(Fc) + ", k " + std::to_string(k) +
+                     " (variant " + std::to_string(d->variant) + " never falls back)").c_str());
+    // x behind every utterance's length is NaN on the device: a read past an utterance shows in the result
+    const size_t nx = (size_t)B * H * ts;
+    std::vector<float> xs(nx, std::numeric_limits<float>::quiet_NaN());
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < H; ++c) std::memcpy(&xs[((size_t)b * H + c) * ts], x + ((size_t)b * H + c) * ts, sizeof(float) * (size_t)(lens ? lens[b] : T));
+    struct Conv {
+        PackedConv pc;
+        DevBuf w, wl, b;
+    } cv[3];
+    auto upload = [&](Conv& c, const float* w, const float* bias, int cout, int cin, int taps) {
+        PackedConv& pc = c.pc;
+        pc.cin = cin, pc.cout = cout, pc.kt = taps, pc.epi = EPI_STD;
+        const std::vector<float> packed = pack_conv_weights(w, cout, cin, taps, EPI_STD, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+        const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, taps);
+        if (!c.w.put(packed.data(), packed.size()) || !c.wl.put(pl.data(), pl.size()) || !c.b.put(bias, cout)) return false;
+        pc.wp = c.w.p, pc.wp_l16 = c.wl.p, pc.bias = c.b.p;
+        pc.bytes = (int64_t)packed.size() * 4;
+        return true;
+    };
+    DevBuf dx, dg1, dbe1, dg2, dbe2, drows, dlogw, dxp, da, db;
+    DevInts dl;
+    if (!upload(cv[0], w1, b1, Fc, H, k) || !upload(cv[1], w2, b2, Fc, Fc, k) || !upload(cv[2], wp, bp, 1, Fc, 1) || !dx.put(xs.data(), nx) || !dg1.put(g1, Fc) || !dbe1.put(be1, Fc) ||
+        !dg2.put(g2, Fc) || !dbe2.put(be2, Fc) || !dlogw.put(logw, (size_t)B * ts) || !dl.put(lens, B) || (spk_rows && !drows.put(spk_rows, (size_t)B * H)))
+        return fail("device allocation failed");
+    DpDetCall c;
+    c.x = tref(dx.p, H, ts);
+    c.logw = tref(dlogw.p, 1, ts);
+    c.c1 = &cv[0].pc, c.c2 = &cv[1].pc, c.proj = &cv[2].pc;
+    c.g1 = dg1.p, c.be1 = dbe1.p, c.g2 = dg2.p, c.be2 = dbe2.p;
+    if (spk_rows) c.rows = drows.p, c.row_rs = H;  // (row b for utterance b)
+    c.lens = dl.p;
+    c.batch = B, c.hidden = H, c.filter = Fc, c.tmax = T, c.k = k;
+    c.eps = d->eps;
+    c.variant = d->variant == 3 ? 0 : d->variant;
+    hipError_t e = hipSuccess;
+    if (plan.ok) {
+        e = launch_dp_det(c, nullptr);
+    } else {
+        // the un-fused sequence: the function Engine::run_duration_predictor_det calls
+        const size_t na = (size_t)B * Fc * ts;
+        if (!da.put(nullptr, na) || !db.put(nullptr, na) || (spk_rows && !dxp.put(nullptr, nx))) return fail("device allocation failed");
+        e = launch_dp_det_unfused(c, spk_rows ? tref(dxp.p, H, ts) : TensorRef(), tref(da.p, Fc, ts), tref(db.p, Fc, ts), nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(logw, dlogw.p, (size_t)B * ts * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     return 0;
     VITS_CATCH(-1)
 }

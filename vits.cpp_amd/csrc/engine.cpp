@@ -461,6 +461,12 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         HIP_OK(hipEventRecord(ev_async_, main_stream));
         HIP_OK(hipStreamWaitEvent(front_, ev_async_, 0));
     }
+    // (before the reference stream is touched: a refused call leaves it alone)
+    if (ggml_tables == 1 && !hp.stochastic_duration) {
+        err = "vits_model_set_ggml_tables(model, 1) runs stage one in the CPU oracle's exact order, and this model has a deterministic duration predictor, which the oracle "
+              "(like the reference) does not have (use tables mode 0 or 2)";
+        return -1;
+    }
     if (B == 1 && o.noise_kind == VITS_NOISE_REFERENCE && !o.frames_only && knobs.ref_ahead_frames_per_id > 0) {
         // The reference's own call (vits_model_process: one utterance, libstdc++ noise). Its two noise tensors are drawn on the host: [T, 2] at
         // vits.cpp:948 and [L, 192] at :1059 — ~1.25 ms for 128 ids, and L is known only behind stage one. A helper thread draws the stream from NOW on,
@@ -470,7 +476,8 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         const size_t per_id = (size_t)std::ceil(knobs.ref_ahead_frames_per_id * std::max(1.0, ls));
         const size_t want = (size_t)hp.flow_size * (per_id * c.Tmax + 64);
         HIP_OK(ref_noise_pinned_.ensure(want, want));
-        ref_ahead_.start((size_t)2 * c.tlen[0], ref_noise_pinned_.p, ref_noise_pinned_.cap);
+        // (the deterministic duration predictor draws nothing: the stream goes straight to the prior tensor)
+        ref_ahead_.start(hp.stochastic_duration ? (size_t)2 * c.tlen[0] : 0, ref_noise_pinned_.p, ref_noise_pinned_.cap);
         c.ref_ahead = &ref_ahead_;
     }
     if (layout_stage_one(c)) return -1;

@@ -310,6 +310,17 @@ class Engine {
     DdsW dp_dds_;
     float *dp_translate_ = nullptr, *dp_logscale_ = nullptr;
     std::vector<DpFlowW> dp_flows_;  // index f-1 for flows.f, f = 1..dp_flows
+    // the deterministic duration predictor (hp.stochastic_duration == false; dp_det.hip), fp32 in every arithmetic mode: conv_1, conv_2, proj with their
+    // 16x16x4 fragments made at load, the two LayerNorms. `in`: no conv at all — the H-channel segment of the effective-bias table that holds the speaker
+    // term of the predictor's INPUT (plain "bias" zero, row 1 + s = cond.W g_s + cond.b); the kernels add its row on load, inside the utterance only
+    struct DetDpW {
+        PackedConv c1, c2, proj, in;
+        float *g1 = nullptr, *be1 = nullptr, *g2 = nullptr, *be2 = nullptr;
+    } dp_det_;
+    bool load_det_predictor(const ModelFile& f, std::string& err);
+    bool make_lat16(PackedConv& pc, std::string& err);  // pc.wp_l16 now, from the device copy of the packed weights (what ensure_lat16 does for every layer at the first small call)
+    int run_duration_predictor_det(Call& c);
+    DpDetCall det_call(const Call& c) const;
     std::vector<FlowLayerW> flow_;
     // voice conversion (engine_convert.cpp): host copies of what prepare_conversion packs (posterior_encoder.*, every flow.flows.*.conv_post, embed_speaker),
     // kept at load; then the packed posterior encoder, the forward flow's conv_post (x1 += mean: not negated), the posterior's effective-bias table and

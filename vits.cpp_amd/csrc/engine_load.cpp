@@ -264,7 +264,8 @@ bool Engine::load_speakers(const ModelFile& f, std::string& err) {
         int64_t off = 0;
     };
     std::vector<Seg> segs;
-    segs.push_back({&dp_pre_, "duration_predictor.cond.weight", "duration_predictor.cond.bias", H, 0});
+    // (the deterministic predictor: the same cond conv, added to the predictor's input instead of conv_pre's output — DetDpW::in)
+    segs.push_back({hp.stochastic_duration ? &dp_pre_ : &dp_det_.in, "duration_predictor.cond.weight", "duration_predictor.cond.bias", H, 0});
     for (int i = 0; i < hp.n_flows; ++i)
         for (int l = 0; l < nl; ++l)
             segs.push_back({&flow_[i].in_layers[l], "flow.flows." + std::to_string(i) + ".wavenet.cond_layer.weight", "flow.flows." + std::to_string(i) + ".wavenet.cond_layer.bias",
@@ -489,7 +490,9 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
     }
     if (!pack(f, "text_encoder.project.weight", "text_encoder.project.bias", EPI_STD, {2 * F, H, 1}, enc_proj_, err)) return false;
     // duration predictor
-    {
+    if (!hp.stochastic_duration) {
+        if (!load_det_predictor(f, err)) return false;
+    } else {
         const std::string dp = "duration_predictor.";
         if (!pack(f, dp + "conv_pre.weight", dp + "conv_pre.bias", EPI_STD, {H, H, 1}, dp_pre_, err)) return false;
         if (!pack(f, dp + "conv_proj.weight", dp + "conv_proj.bias", EPI_STD, {H, H, 1}, dp_proj_, err)) return false;
@@ -605,7 +608,7 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
         // THE FILE HOLDS THEM (torch layout, no packing, no folds): keep the text encoder's and the duration predictor's, in their storage type
         // (~20 MB of host memory for the MMS-TTS architecture), and upload them when the mode is first switched on.
         for (const TensorEntry& t : f.tensors) {
-            const bool s1 = t.name.rfind("text_encoder.", 0) == 0 || t.name.rfind("duration_predictor.", 0) == 0;
+            const bool s1 = hp.stochastic_duration && (t.name.rfind("text_encoder.", 0) == 0 || t.name.rfind("duration_predictor.", 0) == 0);  // (mode 1 refuses deterministic models)
             if (!s1 || t.name.find(".post_") != std::string::npos || t.name.rfind("duration_predictor.flows.1.", 0) == 0) continue;
             exact_src_.push_back(t);
         }
@@ -618,6 +621,72 @@ bool Engine::load(const uint8_t* bytes, size_t size, std::string& err) {
                     (t.name.rfind("flow.flows.", 0) == 0 && t.name.find(".conv_post.") != std::string::npos))
                     vc_src_.push_back(t);
     }
+    return true;
+}
+
+// transformers' VitsDurationPredictor (use_stochastic_duration_prediction = False): conv_1 (H -> Fc, k taps), norm_1, conv_2 (Fc -> Fc, k taps), norm_2, proj (Fc -> 1).
+// Fc comes from conv_1's shape; the exporter writes duration_predictor_filter_channels only when it is not 256 (config.to_diff_dict()), so the key defaults to
+// 256 and must agree with the shape. The stochastic predictor's tensors are neither required nor read.
+bool Engine::load_det_predictor(const ModelFile& f, std::string& err) {
+    const std::string dp = "duration_predictor.";
+    const int H = hp.hidden, k = hp.dp_k;
+    if (!(k & 1)) {
+        err = "duration_predictor_kernel_size = " + std::to_string(k) + ": the deterministic duration predictor needs an odd kernel size";
+        return false;
+    }
+    const TensorEntry* w1 = f.find(dp + "conv_1.weight");
+    if (!w1) {
+        err = "[ERROR] tensor not found: " + dp + "conv_1.weight (use_stochastic_duration_prediction = False: the deterministic duration predictor's tensors are needed)";
+        return false;
+    }
+    if (w1->rank != 3 || w1->ne[0] != k || w1->ne[1] != H || w1->ne[2] <= 0) {
+        err = "tensor '" + dp + "conv_1.weight' has shape " + shape_str(*w1) + ", the hyper-parameters need " + shape_str({k, H, -1});
+        return false;
+    }
+    const int Fc = (int)w1->ne[2];
+    if (Fc != hp.dp_filter) {
+        err = "duration_predictor_filter_channels is " + std::to_string(hp.dp_filter) + (f.cfg("duration_predictor_filter_channels").empty() ? " (the default: the key is absent)" : "") +
+              " but tensor '" + dp + "conv_1.weight' has " + std::to_string(Fc) + " output channels";
+        return false;
+    }
+    DetDpW& W = dp_det_;
+    struct Conv {
+        const char* name;
+        ConvShape want;
+        PackedConv* pc;
+    };
+    const Conv convs[3] = {{"conv_1", {Fc, H, k}, &W.c1}, {"conv_2", {Fc, Fc, k}, &W.c2}, {"proj", {1, Fc, 1}, &W.proj}};
+    float** norms[2][2] = {{&W.g1, &W.be1}, {&W.g2, &W.be2}};
+    for (int i = 0; i < 3; ++i) {
+        const std::string base = dp + convs[i].name;
+        if (!pack(f, base + ".weight", base + ".bias", EPI_STD, convs[i].want, *convs[i].pc, err)) return false;
+        if (!dry_run_) packs_.pop_back();  // fp32 in every arithmetic mode and both scopes: no 16-bit or split operands
+        if (!make_lat16(*convs[i].pc, err)) return false;
+        if (i < 2) {
+            const std::string nb = dp + "norm_" + std::to_string(i + 1);
+            if (!(*norms[i][0] = upload_tensor(f, nb + ".weight", err, {Fc}))) return false;
+            if (!(*norms[i][1] = upload_tensor(f, nb + ".bias", err, {Fc}))) return false;
+        }
+    }
+    // the input's segment of the effective-bias table (load_speakers): a zero "bias" of H channels
+    W.in.cin = W.in.cout = H;
+    if (hp.num_speakers > 1 && !(W.in.bias = upload(std::vector<float>((size_t)H, 0.f)))) {
+        err = "hipMalloc failed for the duration predictor's speaker segment";
+        return false;
+    }
+    return true;
+}
+
+bool Engine::make_lat16(PackedConv& pc, std::string& err) {
+    if (dry_run_ || pc.wp_l16) return true;
+    std::vector<float> host((size_t)pc.mtiles * pc.nchunks * pc.kt * (kConvCK / 2) * 64);
+    float* d = nullptr;
+    if (hipMemcpy(host.data(), pc.wp, host.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess) d = upload(repack_conv_weights_l16(host, pc.mtiles, pc.nchunks, pc.kt));
+    if (!d) {
+        err = "hipMalloc failed for the duration predictor's latency-order weight copy";
+        return false;
+    }
+    pc.wp_l16 = d;
     return true;
 }
 

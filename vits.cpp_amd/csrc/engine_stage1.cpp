@@ -155,12 +155,19 @@ int Engine::layout_stage_one(Call& c) {
         s1.tmp = a.alloc<float>((size_t)B * H * ts);
         s1.ffn = a.alloc<float>((size_t)B * hp.ffn_dim * ts);
         s1.stats = a.alloc<float>((size_t)B * 2 * F * ts);
-        s1.dpx = a.alloc<float>((size_t)B * H * ts);
-        s1.dpy = a.alloc<float>((size_t)B * H * ts);
-        s1.dpp = a.alloc<float>((size_t)B * H * ts);
-        s1.cond = a.alloc<float>((size_t)B * H * ts);
+        if (hp.stochastic_duration) {
+            s1.dpx = a.alloc<float>((size_t)B * H * ts);
+            s1.dpy = a.alloc<float>((size_t)B * H * ts);
+            s1.dpp = a.alloc<float>((size_t)B * H * ts);
+            s1.cond = a.alloc<float>((size_t)B * H * ts);
+        } else if (!plan_dp_det(H, hp.dp_filter, hp.dp_k, B, c.Tmax).ok) {
+            // the deterministic predictor, un-fused: x' and the two filter-channel tensors (the fused kernel keeps all three in LDS; no DDS / flow scratch either way)
+            s1.dpx = a.alloc<float>((size_t)B * H * ts);
+            s1.dpy = a.alloc<float>((size_t)B * hp.dp_filter * ts);
+            s1.dpp = a.alloc<float>((size_t)B * hp.dp_filter * ts);
+        }
         s1.z = a.alloc<float>((size_t)B * 2 * ts);
-        s1.u = a.alloc<float>((size_t)B * 32 * ts);
+        if (hp.stochastic_duration) s1.u = a.alloc<float>((size_t)B * 32 * ts);
         if (ggml_tables == 1) {  // exact-order stage one: a score row per (utterance, head, query), three token rows per utterance for the spline step
             s1.ex_scores = a.alloc<float>((size_t)B * hp.heads * c.Tmax * ts);
             s1.ex_tok = a.alloc<float>((size_t)3 * B * ts);
@@ -316,6 +323,7 @@ int Engine::run_text_encoder(Call& c) {
 
 // ---- stochastic duration predictor, reverse (vits.cpp:927-972) ----------------------------------------
 int Engine::run_duration_predictor(Call& c) {
+    if (!hp.stochastic_duration) return run_duration_predictor_det(c);
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
     const int B = c.B, id_stride = c.id_stride, ts = c.ts, Tmax = c.Tmax, n_up = c.n_up, md = c.md;
@@ -431,6 +439,66 @@ int Engine::run_duration_predictor(Call& c) {
     prof.end(stream);
     c.c_first = c_first;
     return 0;
+}
+
+// ---- deterministic duration predictor (transformers VitsDurationPredictor; the reference has none, vits.cpp:993) -----------------------
+// logw = proj(LN(relu(conv_2(LN(relu(conv_1(x + cond(g)))))))) into row 0 of s1.z, fp32 whatever the arithmetic mode; no noise is drawn. One launch of
+// dp_det_kernel where plan_dp_det has an instantiation for the model's shape, otherwise (and under VITS_NO_DP_DET_FUSE) the same floats from six launches.
+DpDetCall Engine::det_call(const Call& c) const {
+    const DetDpW& W = dp_det_;
+    DpDetCall d;
+    d.x = make_ref(c.s1.x, hp.hidden, c.ts);
+    d.logw = sub_rows(make_ref(c.s1.z, 2, c.ts), 0);
+    d.c1 = &W.c1, d.c2 = &W.c2, d.proj = &W.proj;
+    d.g1 = W.g1, d.be1 = W.be1, d.g2 = W.g2, d.be2 = W.be2;
+    if (c.spk && W.in.bias_rs) d.rows = W.in.bias, d.row_rs = W.in.bias_rs, d.row_idx = c.spk;  // (a call without speakers: x' = x)
+    d.lens = c.s1.lens;
+    d.batch = c.B, d.hidden = hp.hidden, d.filter = hp.dp_filter, d.tmax = c.Tmax, d.k = hp.dp_k;
+    d.eps = hp.ln_eps;
+    return d;
+}
+
+int Engine::run_duration_predictor_det(Call& c) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const int B = c.B, ts = c.ts, Tmax = c.Tmax, H = hp.hidden, Fc = hp.dp_filter, k = hp.dp_k;
+    const int64_t sum_t = c.sum_t;
+    Call::S1& s1 = c.s1;
+    const int* dl = s1.lens;
+    const DetDpW& W = dp_det_;
+    c.rx.phase("vits.duration_predictor");
+#define DET_STEP(name, flop, call)         \
+    do {                                   \
+        prof.begin(name, flop, 0, stream); \
+        const hipError_t e__ = (call);     \
+        prof.end(stream);                  \
+        HIP_OK(e__);                       \
+    } while (0)
+    const DpDetCall d = det_call(c);
+    TensorRef z = make_ref(s1.z, 2, ts);
+    // stage one's convs run in arith_now_; these three are fp32 in every mode and scope
+    ScopedSet<int> fp32(arith_now_, VITS_ARITH_F32);
+    if (plan_dp_det(H, Fc, k, B, Tmax).ok) {
+        if (!dp_det_supported(d)) {
+            err = "the deterministic duration predictor's fused kernel has no weights in its operand order";
+            return -1;
+        }
+        prof.begin("dp_det_fused", 2.0 * ((double)k * H * Fc + (double)k * Fc * Fc + Fc) * (double)sum_t, 4.0 * (H + 1) * (double)sum_t + (double)(W.c1.bytes + W.c2.bytes + W.proj.bytes), stream);
+        const hipError_t e = launch_dp_det(d, stream);
+        prof.end(stream);
+        HIP_OK(e);
+    } else {
+        const double flop = 2.0 * ((double)k * H * Fc + (double)k * Fc * Fc + Fc) * (double)sum_t;
+        DET_STEP("dp_det_unfused", flop, launch_dp_det_unfused(d, make_ref(s1.dpx, H, ts), make_ref(s1.dpy, Fc, ts), make_ref(s1.dpp, Fc, ts), stream));
+    }
+    if (o.collect_taps) snapshot("log_duration", d.logw, 1, Tmax, B, c.tlen);
+    prof.begin("durations", 0, 0, stream);
+    HIP_OK(launch_durations(z, 0, dl, B, c.id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, s1.dur_ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames, s1.stage_lens,
+                            c.n_up + 1, s1.stage_mul, s1.stage_add, stream));
+    prof.end(stream);
+    c.c_first = 0;
+    return 0;
+#undef DET_STEP
 }
 
 }  // namespace vits

@@ -62,6 +62,8 @@ struct KernelKnobs {
     bool no_ln_fuse = false;     // VITS_NO_LN_FUSE: the encoder's LayerNorms always as their own launches (never applied on load by the consuming conv_lat16_kernel)
     bool no_dds_lat = false;     // VITS_NO_DDS_LAT: the duration predictor's DDS layers always on dds_layer_kernel (no 16-token latency kernel, no fused 1x1 convs around it)
     int dds_lat_max_blocks = 96; // VITS_DDS_LAT_MAX_BLOCKS: the latency kernel is taken while batch x ceil(tokens / 16) is at most this
+    bool no_dp_det_fuse = false; // VITS_NO_DP_DET_FUSE: the deterministic duration predictor always as its un-fused sequence (row add, conv, LayerNorm, conv, LayerNorm, 1x1 conv)
+    int dp_det_lat_max_blocks = 96;  // VITS_DP_DET_LAT_MAX_BLOCKS: dp_det_kernel takes its 16-token tile while batch x ceil(tokens / 16) is at most this, the wide tile above
     int lat16h_group_shape = 21;  // VITS_LAT16H_GROUP_SHAPE: 10 x row tiles + column tiles per block of conv16_lat_group_kernel (21, 41, 22, 42)
     bool no_lat16h_group = false; // VITS_NO_LAT16H_GROUP: the C = 256 stage's latency convs as 18 launches on three streams (not six grouped launches on one)
     bool no_lat16h_pre = false;  // VITS_NO_LAT16H_PRE: 16-bit modes: the vocoder's conv_pre always as converter launch + conv16_kernel
@@ -87,6 +89,8 @@ struct KernelKnobs {
         flag("VITS_NO_RBB_GROUP3", k.no_rbb_group3);
         flag("VITS_NO_RBB_GROUP3_C64", k.no_rbb_group3_c64);
         num("VITS_DDS_LAT_MAX_BLOCKS", k.dds_lat_max_blocks);
+        flag("VITS_NO_DP_DET_FUSE", k.no_dp_det_fuse);
+        num("VITS_DP_DET_LAT_MAX_BLOCKS", k.dp_det_lat_max_blocks);
         num("VITS_TILE128", k.tile128);
         num("VITS_MIN_BLOCKS", k.min_blocks);
         flag("VITS_NO_NARROW", k.no_narrow);
@@ -497,6 +501,31 @@ struct DdsLatCall {
 };
 bool dds_layer_lat_supported(const PackedConv& pw, int channels, int k, int dil);
 hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s);
+// The deterministic duration predictor (transformers VitsDurationPredictor, eval mode) as ONE kernel (dp_det.hip), fp32 in every arithmetic mode:
+//   x' = x + row (inside the utterance only; the speaker term, added ON LOAD), a1 = LN(relu(conv_1(x'))), a2 = LN(relu(conv_2(a1))), logw = proj(a2)
+// with a1 / a2 zero outside [0, len). conv_1 / conv_2: k taps, zero padding k / 2; proj: 1x1 to one channel. Bit for bit the un-fused sequence
+// launch_add_rows, launch_conv(post_act = 1), launch_add_layer_norm, launch_conv, launch_add_layer_norm, launch_conv (the engine's fallback).
+// rows: a table of per-utterance rows [*][hidden] with row stride row_rs (floats); utterance b reads row row_idx[b], or row b when row_idx is null. rows == nullptr: no add.
+struct DpDetCall {
+    TensorRef x;     // [batch][hidden][t]
+    TensorRef logw;  // [batch][1][t]: the row the durations kernel reads
+    const PackedConv *c1 = nullptr, *c2 = nullptr, *proj = nullptr;  // wp_l16 fragments and biases
+    const float *g1 = nullptr, *be1 = nullptr, *g2 = nullptr, *be2 = nullptr;
+    const float* rows = nullptr;
+    int64_t row_rs = 0;
+    const int* row_idx = nullptr;
+    const int* lens = nullptr;
+    int batch = 1, hidden = 0, filter = 0, tmax = 0, k = 3;
+    float eps = 1e-5f;
+    int variant = 0;  // 0: the planner's tile; 1: the 16-token tile; 2: the wide tile
+};
+struct DpDetPlan;  // launch_plan.h
+bool dp_det_supported(const DpDetCall& c);  // an instantiation exists for (hidden, filter, k) and the three convs carry their 16x16x4 fragments
+hipError_t launch_dp_det(const DpDetCall& c, hipStream_t s);
+// the un-fused sequence itself (six launches; xp is written only when c.rows): the engine's fallback and the operator's variant 3 are this one function
+hipError_t launch_dp_det_unfused(const DpDetCall& c, TensorRef xp, TensorRef a, TensorRef b, hipStream_t s);
+// y[b][c][t] = x[b][c][t] + rows[row(b)][c] for t < lens[b] (nothing is written behind an utterance): the un-fused predictor's first step
+hipError_t launch_add_rows(TensorRef x, TensorRef y, const float* rows, int64_t row_rs, const int* row_idx, const int* lens, int batch, int channels, int tmax, hipStream_t s);
 hipError_t launch_pointwise_from1(TensorRef z, int zc, const float* w, const float* bias, TensorRef cond, TensorRef y, const int* lens, int batch,
                                   int channels, int tmax, hipStream_t s, int arith = 0);
 hipError_t launch_spline(TensorRef u, TensorRef z, int zc, const int* lens, int batch, int tmax, int bins, float tail, float inv_sqrt, int mode,

@@ -232,6 +232,23 @@ bool dds_lat_grid_ok(int batch, int tmax) {
     return !kernel_knobs().no_dds_lat && (int64_t)batch * blocks_for(tmax, kLatNT) <= kernel_knobs().dds_lat_max_blocks;
 }
 
+// One launch for the whole deterministic predictor where an instantiation exists. Small grids take the 16-token tile (many short blocks: batch 1 x 128 ids = 8 blocks
+// of 16 waves), large ones the wide tile, which reads the 1.4 MB of weights once per 62 tokens instead of once per 16.
+DpDetPlan plan_dp_det(int hidden, int filter, int k, int batch, int tmax, int variant) {
+    const KernelKnobs& kn = kernel_knobs();
+    DpDetPlan p;
+    if (variant < 0 || variant > 3 || variant == 3 || (variant == 0 && kn.no_dp_det_fuse)) return p;  // un-fused (ok stays false: nothing to launch here)
+    if (!dp_det_shape_exists(hidden, filter, k)) return p;
+    const bool lat = variant == 1 || (variant == 0 && (int64_t)batch * blocks_for(tmax, kLatNT) <= kn.dp_det_lat_max_blocks);
+    p.nt = lat ? kLatNT : dp_det_wide_nt(k);
+    if (!dp_det_exists(hidden, filter, k, p.nt)) return p;
+    const DpDetGeom g = dp_det_geom(blocks_for(hidden, 32), filter, k, p.nt);
+    if (g.lds > kLdsMax) return p;
+    p.fused = true;
+    set_grid(p, blocks_for(tmax, p.nt), batch, g.block, g.lds);
+    return p;
+}
+
 // ---- the engine-facing predicates: thin calls into the plans (the launchers add the checks of their pointers) -------------------------------
 bool rbpair16_supported(int channels, int kt, int dil) { return plan_rbpair16(channels, kt, dil, 1, 1).ok; }
 static bool dils_135(const int* dils, int ndil) { return ndil == 3 && dils[0] == 1 && dils[1] == 3 && dils[2] == 5; }

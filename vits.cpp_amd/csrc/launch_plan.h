@@ -139,6 +139,25 @@ constexpr size_t dds_lat_lds(int H, int k, int dil, bool head_conv, int h_cin) {
     return sizeof(float) * (((size_t)H * xw + 3) / 4 * 4 + (size_t)H * kLatNT + 2 * kLnGroups * kLatNT + ((size_t)H * (6 + k) + 3) / 4 * 4 + (head_conv ? (size_t)h_cin * ((xw + 15) & ~15) : 0));
 }
 
+// dp_det_kernel<HCH, FC, K, NT> (dp_det.hip): the deterministic duration predictor. A block owns NT tokens of one utterance: the x' tile [32 HCH][xp] with 2 (K / 2)
+// halo columns per side, the a1 tile [FC][ap] on NT + 2 (K / 2) columns (a2 takes its place), one wave per 16 output rows. Pitches = 16 (mod 32): the four
+// channel rows a wave's B operand reads fall on different banks. The LayerNorm partial sums take the x' tile's place.
+struct DpDetGeom {
+    int nt, pad, w1, ct1, ct2, xp, ap, block;  // tokens, halo of one conv, a1 columns, 16-column tiles of conv_1 / conv_2, pitches (floats), threads
+    size_t lds;
+};
+constexpr int dp_det_pitch(int need) { return (need + 15) / 32 * 32 + 16; }  // smallest pitch >= need that is 16 (mod 32)
+constexpr int kDpDetWide = 64;  // the wide tile: a1 on exactly 64 columns, i.e. 64 - 2 (K / 2) tokens per block
+constexpr DpDetGeom dp_det_geom(int HCH, int FC, int K, int NT) {
+    const int pad = K / 2, w1 = NT + 2 * pad, ct1 = blocks_for(w1, 16), ct2 = blocks_for(NT, 16);
+    const int xp = dp_det_pitch(ct1 * 16 + K - 1), need2 = ct2 * 16 + K - 1, ap = dp_det_pitch(need2 > ct1 * 16 ? need2 : ct1 * 16);
+    const size_t xfloats = (size_t)32 * HCH * xp, rfloats = (size_t)(2 * kLnGroups + 2) * ct1 * 16;
+    return {NT, pad, w1, ct1, ct2, xp, ap, FC / 16 * 64, sizeof(float) * ((xfloats > rfloats ? xfloats : rfloats) + (size_t)FC * ap)};
+}
+constexpr int dp_det_wide_nt(int K) { return kDpDetWide - 2 * (K / 2); }
+constexpr bool dp_det_shape_exists(int H, int FC, int K) { return (H == 192 && FC == 256 && (K == 3 || K == 5)) || (H == 16 && FC == 32 && K == 3); }
+constexpr bool dp_det_exists(int H, int FC, int K, int NT) { return dp_det_shape_exists(H, FC, K) && (NT == kLatNT || NT == dp_det_wide_nt(K)); }
+
 // ---- one plan per launch --------------------------------------------------------------------------------------------------------------
 struct LaunchGrid {
     bool ok = false;  // false: the launcher refuses
@@ -198,5 +217,12 @@ struct DdsLayerPlan : LaunchGrid {
 DdsLayerPlan plan_dds_layer(int channels, int k, int dil, int batch, int tmax);
 DdsLayerPlan plan_dds_layer_lat(int channels, int k, int dil, bool head_conv, int batch, int tmax);
 bool dds_lat_grid_ok(int batch, int tmax);  // the latency kernel's grid rule (VITS_NO_DDS_LAT, VITS_DDS_LAT_MAX_BLOCKS)
+// the deterministic duration predictor: `fused` = dp_det_kernel on the nt-token tile (ok: launchable), otherwise the un-fused sequence. variant 0: the planner's choice
+// (VITS_NO_DP_DET_FUSE, VITS_DP_DET_LAT_MAX_BLOCKS); 1 / 2: the 16-token / the wide tile or a refusal (ok false), never the un-fused sequence; 3: un-fused
+struct DpDetPlan : LaunchGrid {
+    bool fused = false;
+    int nt = 0;
+};
+DpDetPlan plan_dp_det(int hidden, int filter, int k, int batch, int tmax, int variant = 0);
 
 }  // namespace vits

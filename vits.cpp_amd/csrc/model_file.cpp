@@ -307,6 +307,7 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         geti("depth_separable_num_layers", dds_layers);
         geti("duration_predictor_flow_bins", dp_bins);
         geti("duration_predictor_num_flows", dp_flows);
+        geti("duration_predictor_filter_channels", dp_filter);
         {
             int tb = (int)dp_tail;  // the reference parses this key with stoi (vits.cpp:861)
             geti("duration_predictor_tail_bound", tb);
@@ -326,7 +327,7 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         err = std::string("bad config value: ") + e.what();
         return false;
     }
-    // what the reference refuses (vits.cpp:379-380,391,461,603-605,936-937,993), refused here too
+    // what the reference refuses (vits.cpp:379-380,391,461,603-605,936-937), refused here too
     if (hidden_act != "relu") {
         err = "activation function not supported " + hidden_act;
         return false;
@@ -335,10 +336,7 @@ bool HParams::load(const ModelFile& f, std::string& err) {
         err = "ffn_kernel_size == 1 not supported ";
         return false;
     }
-    if (!stochastic_duration) {
-        err = "Only stochastic duration prediction is supported";
-        return false;
-    }
+    // use_stochastic_duration_prediction = False (the reference refuses it, vits.cpp:993): transformers' VitsDurationPredictor; its tensors are checked at load
     // speaker conditioning (transformers VitsModel: embed_speaker exists only for num_speakers > 1; the reference asserts it away,
     // vits.cpp:461,603,936): num_speakers == 1 with an embedding size loads and is never conditioned, as in transformers
     if (num_speakers < 1 || speaker_embedding_size < 0 || (num_speakers > 1 && speaker_embedding_size == 0)) {
@@ -436,6 +434,9 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
     // VITS_SYNTH_POSTERIOR: the posterior encoder behind everything else (TINY: 9 bins = n_fft 16 over its hop of 8, two WaveNet layers)
     const bool posterior = (arch_flags & VITS_SYNTH_POSTERIOR) != 0;
     const int spec_bins = posterior && arch == VITS_SYNTH_TINY ? 9 : 513, post_layers = arch == VITS_SYNTH_TINY ? 2 : 16;
+    // VITS_SYNTH_DETERMINISTIC: transformers' VitsDurationPredictor in the stochastic predictor's place; every other tensor keeps its values
+    const bool deterministic = (arch_flags & VITS_SYNTH_DETERMINISTIC) != 0;
+    const int dp_filter = arch == VITS_SYNTH_TINY ? 32 : 256;
     ModelFile& f = s.f;
     // tokenizer block: a 38-entry single-character vocabulary in the style of the MMS checkpoints
     {
@@ -469,7 +470,7 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         puti("spectrogram_bins", spec_bins);
         put("hidden_act", "relu");
         put("layer_norm_eps", "1e-05");
-        put("use_stochastic_duration_prediction", "True");
+        put("use_stochastic_duration_prediction", deterministic ? "False" : "True");
         puti("num_speakers", spk_n);
         puti("speaker_embedding_size", spk_e);
         puti("upsample_initial_channel", h.up_init);
@@ -488,6 +489,7 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         put("duration_predictor_tail_bound", "5.0");
         puti("duration_predictor_kernel_size", h.dp_k);
         puti("duration_predictor_num_flows", h.dp_flows);
+        if (deterministic && dp_filter != 256) puti("duration_predictor_filter_channels", dp_filter);  // (to_diff_dict: only what differs from the default)
         puti("prior_encoder_num_flows", h.n_flows);
         puti("prior_encoder_num_wavenet_layers", h.wn_layers);
         puti("wavenet_kernel_size", h.wn_k);
@@ -553,6 +555,7 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
         s.conv("decoder.conv_post", 1, c, 7, 0.35f, false);
     }
     // stochastic duration predictor (only what inference reads; the reference never touches post_* and flows.1)
+    const size_t dp_first = s.f.tensors.size();
     {
         const std::string dp = "duration_predictor.";
         auto dds = [&](const std::string& b) {
@@ -573,6 +576,22 @@ ModelFile make_synthetic_model(uint64_t seed, int arch_flags) {
             dds(b + "conv_dds.");
             s.conv(b + "conv_proj", 3 * h.dp_bins - 1, H, 1, 2.0f * std::sqrt((float)H / 192.0f));
         }
+    }
+    if (deterministic) {
+        // The deterministic predictor takes the stochastic one's place in the file (state_dict order: conv_1, norm_1, conv_2, norm_2, proj). Its values come from
+        // weight streams of their own, and the stream counter stands where the stochastic tensors left it: every tensor behind keeps its values.
+        s.f.tensors.resize(dp_first);
+        const uint32_t behind = s.ordinal;
+        s.ordinal = 0x100000;
+        const std::string dp = "duration_predictor.";
+        s.conv(dp + "conv_1", dp_filter, H, h.dp_k, 1.4f);
+        s.norm(dp + "norm_1", dp_filter);
+        s.conv(dp + "conv_2", dp_filter, dp_filter, h.dp_k, 1.4f);
+        s.norm(dp + "norm_2", dp_filter);
+        // (gain and bias: log-durations around 0.1 +- 0.5, i.e. one to four frames per id, like the stochastic synthetic models)
+        s.add(dp + "proj.weight", {1, dp_filter, 1}, true, 0.5f / std::sqrt((float)dp_filter));
+        s.add(dp + "proj.bias", {1}, false, 0.05f, 0.1f);
+        s.ordinal = behind;
     }
     if (speakers) {
         // names and shapes of transformers' VitsModel(num_speakers, speaker_embedding_size) after weight-norm removal; the gains make the

@@ -67,7 +67,8 @@ struct HParams {
     float dp_tail = 5.f, noise_scale_dur = 0.8f, noise_scale = 0.667f, speaking_rate = 1.0f;
     int sampling_rate = 16000;
     std::string hidden_act = "relu";
-    bool stochastic_duration = true;
+    bool stochastic_duration = true;  // false: transformers' VitsDurationPredictor (two k-tap convs with ReLU and LayerNorm, a 1x1 projection; no noise)
+    int dp_filter = 256;              // its filter channels (duration_predictor_filter_channels: written by the exporter only when it is not 256)
     int speaker_embedding_size = 0;
     int num_speakers = 1;  // > 1: a multi-speaker model (embed_speaker + the cond layers; speaker_embedding_size > 0)
     // posterior encoder (voice conversion only; TTS never reads these): linear-spectrogram bins in, WaveNet depth
