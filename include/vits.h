@@ -519,6 +519,48 @@ typedef struct vits_resblock_pair_desc {
 VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float* x, const float* w1, const float* b1,
                                    const float* w2, const float* b2, const int32_t* lens, float* y);
 
+/* One whole HiFiGAN ResBlock (vits.cpp:545-581, 622-635) on caller tensors, through the kernel the caller names:
+ *   y_{p+1} = y_p + b2_p + conv2_p(leaky_relu(b1_p + conv1_p(leaky_relu(y_p)))),  p < ndil,  conv1_p at dil[p], conv2_p at dilation 1,
+ *   out = y_ndil, or with accum: (accum + y_ndil) * out_scale (scale_div: / out_scale).
+ * x, accum (optional), y: host [batch][channels][t_stride] fp32; w1, w2: [ndil][C][C][k] (torch layout per conv); b1, b2: [ndil][C] (required: the fused
+ * kernels take convs with a bias); lens optional, 0 <= lens[b] <= t <= t_stride. Arithmetic: vits_op_set_arith, VITS_ARITH_F32 / F16 / BF16 (the split
+ * arithmetic keeps vits_op_resblock_pair). Columns [0, t) of every row of y are written back: what no kernel wrote comes back zero.
+ * variant: 0 the engine's choice for this shape and grid; 1 un-fused: two conv launches per pair as the engine builds them (fp32: launch_conv; 16-bit:
+ * launch_conv16 with the group-layout epilogue); 2 one fused pair kernel per pair (rbpair32_kernel / rbpair16_kernel; nr: the column tiles per wave of the
+ * C >= 128 16-bit pairs, 4 or VITS_RB16_NARROW_NR (2), 0 = the planner's); 3 the whole-ResBlock kernel, one tile per block (rbblock32_kernel / rbblock16_kernel;
+ * C = 64, k = 11 included, which the engine only takes in segments); 4 the 16-bit whole-ResBlock kernel walking segments of `tiles` (>= 2) tiles. Variants 1-4
+ * return -1 with the cause in vits_last_error where no such instantiation exists (ndil != 3 or dilations other than 1, 3, 5 for variants 3 and 4; C = 128,
+ * k = 7 for variant 2 in fp32; variant 4 in fp32; ...): they never fall back to another variant. Every refusal is made before the first device call.
+ * Staging is the engine's: fp32 tensors [b][C][ts] with ts = t rounded up to 32, in the 16-bit modes the group layout [b][C/8][ts][8] for the fp32 stream
+ * and the 16-bit copy of leaky_relu(y_0) (written by the engine's converter kernel); every pair writes a buffer it does not read. Every staged input and every
+ * intermediate buffer holds NaNs (fp32, f16 / bf16) behind lens[b] before the valid part goes in: a read past an utterance shows in the result.
+ * All variants give the same bits. Variant 1 gives the bits of vits_op_conv1d called twice per pair (pre_slope, residual, accum / out_scale on the last
+ * pair) in the same arithmetic; scale_div has no counterpart there. */
+typedef struct vits_resblock_desc {
+    int32_t batch, channels, t, t_stride;
+    int32_t k, ndil;
+    int32_t dil[3];
+    float slope, out_scale;
+    int32_t scale_div;
+    int32_t variant, tiles, nr;
+} vits_resblock_desc;
+VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                              const float* accum, const int32_t* lens, float* y);
+/* What vits_op_resblock would launch for d in the arithmetic of vits_op_set_arith, or -1 and the cause of its refusal. Host arithmetic only: no device call,
+ * so it answers on a machine without a GPU. kernel: the instantiation as the launch-plan tables print it (variant 1: the launcher; its tiles are the conv
+ * planner's and the geometry fields are 0). bo: output columns of a block's first tile; advance: of every later tile of a segment (= bo for one-tile
+ * kernels); halo: input columns a tile reads beyond its outputs, per side; segment: output columns of a block = bo + (tiles - 1) advance; launches: kernel
+ * launches for the whole ResBlock. */
+typedef struct vits_resblock_plan {
+    char kernel[96];
+    int32_t variant; /* the variant that runs (1-4; what 0 resolved to) */
+    int32_t bo, advance, halo, segment, tiles, nr;
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t lds;
+    int32_t launches;
+} vits_resblock_plan;
+VITS_API int vits_op_resblock_plan(const vits_resblock_desc* d, vits_resblock_plan* plan);
+
 /* conv_transpose_1d_with_bias (vits.cpp:178-193). w is [Cin][Cout][K] (torch layout), K == 2*stride.
  * crop = (K-stride)/2 in HF mode (HF modeling_vits.py:483-490), 0 in reference mode (vits.cpp:187, Q1).
  * Output length = stride*T + K - stride - 2*crop. pre-activation leaky_relu(slope) is fused (vits.cpp:613). */

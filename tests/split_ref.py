@@ -1,4 +1,5 @@
-"""numpy side of the VITS_ARITH_F32_SPLIT operator tests (tests/test_gpu_split_ops.py, tests/test_split_emulation.py): the float64 reference of a
+"""numpy side of the operator tests of the fp32-accurate kernels (VITS_ARITH_F32_SPLIT: tests/test_gpu_split_ops.py, tests/test_split_emulation.py; the fused
+fp32 ResBlock kernels: tests/test_gpu_resblock_ops.py, tests/test_resblock_op_host.py): the float64 reference of a
 conv / a ResBlock pair, the sequential fp32 fmaf chain the bound is derived from, and a restatement of the split arithmetic itself
 (vits.cpp_amd/csrc/conv_split.hip: weights = two bf16 pieces, activations = three, five of the six cross products, fp32 accumulation).
 
@@ -158,3 +159,83 @@ def rms_err(got, ref):
     e = np.asarray(got, np.float64) - ref
     rms = np.sqrt((ref ** 2).mean()) + 1e-300
     return float(np.sqrt((e ** 2).mean()) / rms), float(np.abs(e).max() / rms)
+
+
+# ---- a ResBlock conv pair against float64, and the rule applied to a result (shared by the split-operand and the fused fp32 pair tests) --------------------
+def make_pair(C, k, dil, T, B):
+    rng = np.random.default_rng(case_seed(C, C, k, dil, T) + 1)
+    x = rng.standard_normal((B, C, T)).astype(np.float32)
+    w1, w2 = ((rng.standard_normal((C, C, k)) / np.sqrt(C * k)).astype(np.float16).astype(np.float32) for _ in range(2))
+    b1, b2 = (rng.standard_normal(C).astype(np.float32) for _ in range(2))
+    return x, w1, b1, w2, b2
+
+
+def pair_reference(x, w1, b1, w2, b2, lens, dil, slope):
+    """y = x + b2 + conv2(lrelu(b1 + conv1(lrelu(x)))) on the valid columns: (ref float64 [C, columns], chain fp32 [len(rows), columns], rows)"""
+    C, _, k = w1.shape
+    T = x.shape[2]
+    xc = gather_cols(x, lens)
+    A1 = im2col(lrelu32(x, slope), lens, k, dil)
+    # reference: float64 sums; the intermediate is rounded to fp32 before its leaky ReLU (it exists only as an fp32 value)
+    t32 = epilogue64(conv64(w1, A1), b1).astype(np.float32)
+    A2 = im2col(scatter_cols(lrelu32(t32, slope), lens, T), lens, k, 1)
+    ref = epilogue64(conv64(w2, A2), b2, xc)
+    # the chain through both convs: conv 1 on every channel (conv 2 reads them all), conv 2 on the subset
+    tc = epilogue32(chain32(w1.reshape(C, -1), A1), b1)
+    A2c = im2col(scatter_cols(lrelu32(tc, slope), lens, T), lens, k, 1)
+    rows = chain_rows(C, A1.shape[1])
+    chain = epilogue32(chain32(w2.reshape(C, -1)[rows], A2c), b2[rows], xc[rows])
+    return ref, chain, rows
+
+
+def hold_to_the_chain(label, got, lens, ref, chain, rows):
+    """got [B, C, T] from the GPU; ref [C, columns] float64; chain fp32 [len(rows), columns]. Prints, then asserts the 2x rule (overall and per 32-row tile)."""
+    for b, n in enumerate(lens):
+        assert not got[b, :, n:].any(), (label, b, "a column past lens[b] was written")
+    cols = gather_cols(got, lens)
+    assert np.isfinite(cols).all(), (label, "a slot past an utterance's length (NaN) was read")
+    c_rms, c_max = rms_err(chain, ref[rows])
+    g_rms, g_max = rms_err(cols, ref)
+    print("%s: %d outputs (chain on %d): gpu rms %.2e max %.2e of RMS; chain rms %.2e max %.2e; ratio %.2f"
+          % (label, cols.size, chain.size, g_rms, g_max, c_rms, c_max, g_rms / c_rms))
+    assert g_rms <= FACTOR * c_rms, (label, g_rms, c_rms)
+    if 32 * cols.shape[1] >= MIN_ELEMS:
+        for mt in range(cols.shape[0] // 32):
+            t_rms, _ = rms_err(cols[32 * mt:32 * mt + 32], ref[32 * mt:32 * mt + 32])
+            assert t_rms <= FACTOR * c_rms, (label, "row tile", mt, t_rms, c_rms)
+    return g_rms / c_rms
+
+
+def edge_columns(lens, k, bo):
+    """mask over the gathered columns: the last k - 1 columns of every row and the k - 1 columns on each side of every tile boundary m bo inside the row — where
+    a fused kernel masks its intermediate and where one block's outputs depend on its halo"""
+    parts = []
+    for n in lens:
+        t = np.arange(int(n))
+        m = t >= n - (k - 1)
+        for edge in range(bo, int(n), bo):
+            m |= (t >= edge - (k - 1)) & (t < edge + (k - 1))
+        parts.append(m)
+    return np.concatenate(parts) if parts else np.zeros(0, bool)
+
+
+class EdgePool:
+    """Squared errors on the edge windows of a case's calls, pooled: the 2x rule on them alone, so that a fault at an edge is not diluted by the columns around it."""
+
+    def __init__(self):
+        self.g = self.c = self.rg = self.rc = 0.0
+        self.n = 0
+
+    def add(self, cols, ref, chain, rows, mask):
+        if not mask.any():
+            return
+        r = np.asarray(ref, np.float64)[:, mask]
+        self.g += float(((np.asarray(cols, np.float64)[:, mask] - r) ** 2).sum())
+        self.rg += float((r ** 2).sum())
+        self.c += float(((np.asarray(chain, np.float64)[:, mask] - r[rows]) ** 2).sum())
+        self.rc += float((r[rows] ** 2).sum())
+        self.n += int(mask.sum()) * r.shape[0]
+
+    def ratio(self):
+        """rms error of the result over rms error of the chain, each relative to the reference's RMS on its own outputs"""
+        return np.sqrt(self.g / self.rg) / (np.sqrt(self.c / self.rc) + 1e-300)

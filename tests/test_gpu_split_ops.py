@@ -28,22 +28,7 @@ def _split_op_arith(pkg):
     pkg.op_set_arith(pkg.ARITH_F32)
 
 
-def hold_to_the_chain(label, got, lens, ref, chain, rows):
-    """got [B, C, T] from the GPU; ref [C, columns] float64; chain fp32 [len(rows), columns]. Prints, then asserts the 2x rule (overall and per 32-row tile)."""
-    for b, n in enumerate(lens):
-        assert not got[b, :, n:].any(), (label, b, "a column past lens[b] was written")
-    cols = R.gather_cols(got, lens)
-    assert np.isfinite(cols).all(), (label, "a slot past an utterance's length (bf16 NaN) was read")
-    c_rms, c_max = R.rms_err(chain, ref[rows])
-    g_rms, g_max = R.rms_err(cols, ref)
-    print("%s: %d outputs (chain on %d): gpu rms %.2e max %.2e of RMS; chain rms %.2e max %.2e; ratio %.2f"
-          % (label, cols.size, chain.size, g_rms, g_max, c_rms, c_max, g_rms / c_rms))
-    assert g_rms <= R.FACTOR * c_rms, (label, g_rms, c_rms)
-    if 32 * cols.shape[1] >= R.MIN_ELEMS:
-        for mt in range(cols.shape[0] // 32):
-            t_rms, _ = R.rms_err(cols[32 * mt:32 * mt + 32], ref[32 * mt:32 * mt + 32])
-            assert t_rms <= R.FACTOR * c_rms, (label, "row tile", mt, t_rms, c_rms)
-    return g_rms / c_rms
+hold_to_the_chain = R.hold_to_the_chain
 
 
 def check_conv(pkg, cin, cout, k, dil, T, lens, pre_slope=None, residual=False, accum=False, out_scale=1.0, bf16_weights=False, edit_w=None, label=""):
@@ -129,29 +114,14 @@ def test_a_weight_of_1_plus_2_to_the_minus_20_is_two_bf16_values_and_is_computed
 
 
 # ---- the conv pair of a ResBlock: the epilogue that writes the next conv's planes, and the conv that reads planes an epilogue wrote --------------------------
-def make_pair(C, k, dil, T, B):
-    rng = np.random.default_rng(R.case_seed(C, C, k, dil, T) + 1)
-    x = rng.standard_normal((B, C, T)).astype(np.float32)
-    w1, w2 = ((rng.standard_normal((C, C, k)) / np.sqrt(C * k)).astype(np.float16).astype(np.float32) for _ in range(2))
-    b1, b2 = (rng.standard_normal(C).astype(np.float32) for _ in range(2))
-    return x, w1, b1, w2, b2
+make_pair = R.make_pair
 
 
 def check_pair(pkg, C, k, dil, T, label=""):
     lens = [T, max(1, 2 * T // 3), max(1, T // 4)]
     x, w1, b1, w2, b2 = make_pair(C, k, dil, T, len(lens))
     got = pkg.op_resblock_pair(x, w1, b1, w2, b2, dil, SLOPE, lens=lens)
-    xc = R.gather_cols(x, lens)
-    A1 = R.im2col(R.lrelu32(x, SLOPE), lens, k, dil)
-    # reference: float64 sums; the intermediate is rounded to fp32 before its leaky ReLU (it exists only as an fp32 value split into planes)
-    t32 = R.epilogue64(R.conv64(w1, A1), b1).astype(np.float32)
-    A2 = R.im2col(R.scatter_cols(R.lrelu32(t32, SLOPE), lens, T), lens, k, 1)
-    ref = R.epilogue64(R.conv64(w2, A2), b2, xc)
-    # the chain through both convs: conv 1 on every channel (conv 2 reads them all), conv 2 on the subset
-    tc = R.epilogue32(R.chain32(w1.reshape(C, -1), A1), b1)
-    A2c = R.im2col(R.scatter_cols(R.lrelu32(tc, SLOPE), lens, T), lens, k, 1)
-    rows = R.chain_rows(C, A1.shape[1])
-    chain = R.epilogue32(R.chain32(w2.reshape(C, -1)[rows], A2c), b2[rows], xc[rows])
+    ref, chain, rows = R.pair_reference(x, w1, b1, w2, b2, lens, dil, SLOPE)
     return hold_to_the_chain("pair C%d k%d d%d T%d %s" % (C, k, dil, T, label), got, lens, ref, chain, rows)
 
 

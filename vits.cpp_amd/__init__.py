@@ -24,6 +24,7 @@ SYNTH_FULL, SYNTH_TINY, SYNTH_BF16, SYNTH_SPEAKERS, SYNTH_POSTERIOR = 0, 1, 0x10
 SYNTH_DETERMINISTIC = 0x800  # OR-ed in: the deterministic duration predictor in the stochastic one's place
 DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
 DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
+RB_VARIANT_PLAN, RB_VARIANT_UNFUSED, RB_VARIANT_PAIRS, RB_VARIANT_BLOCK, RB_VARIANT_SEGMENTS = 0, 1, 2, 3, 4  # op_resblock
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
@@ -47,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
-    "vits_model_duration_predictor_kind", "vits_op_duration_predictor",
+    "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -87,6 +88,18 @@ class Conv1dDesc(C.Structure):
 class ResblockPairDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32),
                 ("dilation", C.c_int32), ("slope", C.c_float)]
+
+
+class ResblockDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32), ("ndil", C.c_int32),
+                ("dil", C.c_int32 * 3), ("slope", C.c_float), ("out_scale", C.c_float), ("scale_div", C.c_int32), ("variant", C.c_int32),
+                ("tiles", C.c_int32), ("nr", C.c_int32)]
+
+
+class ResblockPlan(C.Structure):
+    _fields_ = [("kernel", C.c_char * 96), ("variant", C.c_int32), ("bo", C.c_int32), ("advance", C.c_int32), ("halo", C.c_int32),
+                ("segment", C.c_int32), ("tiles", C.c_int32), ("nr", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
+                ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64), ("launches", C.c_int32)]
 
 
 class DurationPredictorDesc(C.Structure):
@@ -249,6 +262,10 @@ def lib():
     L.vits_op_conv1d.argtypes = [C.POINTER(Conv1dDesc), vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_resblock_pair.restype = i32
     L.vits_op_resblock_pair.argtypes = [C.POINTER(ResblockPairDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.vits_op_resblock.restype = i32
+    L.vits_op_resblock.argtypes = [C.POINTER(ResblockDesc), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.vits_op_resblock_plan.restype = i32
+    L.vits_op_resblock_plan.argtypes = [C.POINTER(ResblockDesc), C.POINTER(ResblockPlan)]
     L.vits_op_conv_transpose1d.restype = i32
     L.vits_op_conv_transpose1d.argtypes = [C.POINTER(ConvT1dDesc), vp, vp, vp, vp, vp]
     L.vits_op_rel_attention.restype = i32
@@ -935,6 +952,42 @@ def op_resblock_pair(x, w1, b1, w2, b2, dilation, slope, lens=None):
     y = np.zeros((B, ch, T), np.float32)
     lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
     if lib().vits_op_resblock_pair(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(lens), _ptr(y)) != 0:
+        raise VitsError(last_error())
+    return y
+
+
+def _resblock_desc(B, ch, T, ts, k, dils, slope, out_scale, scale_div, variant, tiles, nr):
+    dils = [int(v) for v in dils]
+    return ResblockDesc(B, ch, T, ts, k, len(dils), (C.c_int32 * 3)(*(dils + [0] * 3)[:3]), slope, out_scale, int(scale_div), variant, tiles, nr)
+
+
+def op_resblock_plan(channels, k, dils, t, batch=1, variant=RB_VARIANT_PLAN, tiles=0, nr=0):
+    """What op_resblock would launch in the arithmetic of op_set_arith (vits_op_resblock_plan; host arithmetic, no GPU needed): a dict with kernel, variant (the
+    one that runs), bo, advance, halo, segment, tiles, nr, grid, block, lds, launches — or a VitsError naming the cause of the refusal."""
+    d = _resblock_desc(batch, channels, t, t, k, dils, 0.1, 1.0, 0, variant, tiles, nr)
+    p = ResblockPlan()
+    if lib().vits_op_resblock_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "bo", "advance", "halo", "segment", "tiles", "nr", "block", "lds", "launches")}
+    out["kernel"] = p.kernel.decode()
+    out["grid"] = (p.grid_x, p.grid_y, p.grid_z)
+    return out
+
+
+def op_resblock(x, w1, b1, w2, b2, dils, slope, variant=RB_VARIANT_PLAN, tiles=0, nr=0, accum=None, out_scale=1.0, scale_div=False, lens=None, t=None):
+    """One HiFiGAN ResBlock through the kernel `variant` names (vits_op_resblock): x [B, C, t_stride]; w1, w2 [ndil, C, C, k]; b1, b2 [ndil, C]; dils the
+    dilations of the first convs; accum [B, C, t_stride] or None: out = (accum + y) * out_scale (scale_div: / out_scale); t = the longest utterance (default:
+    t_stride). RB_VARIANT_UNFUSED | _PAIRS | _BLOCK | _SEGMENTS run that kernel or raise a VitsError naming the cause: never another one. Returns [B, C, t_stride],
+    zero where nothing was written."""
+    x, w1, w2, b1, b2, accum = _f32(x), _f32(w1), _f32(w2), _f32(b1), _f32(b2), _f32(accum)
+    B, ch, ts = x.shape
+    nd, _, _, k = w1.shape
+    assert w1.shape == w2.shape == (nd, ch, ch, k) and b1.shape == b2.shape == (nd, ch) and len(dils) == nd
+    assert accum is None or accum.shape == x.shape
+    d = _resblock_desc(B, ch, ts if t is None else t, ts, k, dils, slope, out_scale, scale_div, variant, tiles, nr)
+    y = np.zeros((B, ch, ts), np.float32)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lib().vits_op_resblock(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(accum), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
 

@@ -1071,6 +1071,318 @@ VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float
     VITS_CATCH(-1)
 }
 
+// ---- vits_op_resblock: which kernel a descriptor names (host arithmetic only: launch_plan.h), then the engine's call structs on staged tensors ------------
+namespace {
+struct RbOpPlan {
+    int variant = 0;
+    std::string kernel;
+    int bo = 0, adv = 0, halo = 0, seg = 0, tiles = 1, nr = 0, launches = 0;
+    vits::LaunchGrid g;
+};
+bool rb_fail(std::string& why, const std::string& m) {
+    why = "vits_op_resblock: " + m;
+    return false;
+}
+bool resblock_resolve(const vits_resblock_desc* d, int arith, RbOpPlan& r, std::string& why) {
+    using namespace vits;
+    if (arith != VITS_ARITH_F32 && arith != VITS_ARITH_F16 && arith != VITS_ARITH_BF16)
+        return rb_fail(why, "VITS_ARITH_F32, VITS_ARITH_F16 or VITS_ARITH_BF16 only (the split arithmetic keeps vits_op_resblock_pair)");
+    const int C = d->channels, k = d->k, B = d->batch, T = d->t, nd = d->ndil;
+    if (B < 1 || T < 1 || d->t_stride < T) return rb_fail(why, "batch >= 1 and 1 <= t <= t_stride are required");
+    if (C < 32 || (C & 31)) return rb_fail(why, "channels = " + std::to_string(C) + ": a multiple of 32 is required");
+    if (k < 1 || !(k & 1)) return rb_fail(why, "k = " + std::to_string(k) + ": an odd tap count is required");
+    if (nd < 1 || nd > 3) return rb_fail(why, "ndil = " + std::to_string(nd) + ": one to three conv pairs");
+    for (int p = 0; p < nd; ++p)
+        if (d->dil[p] < 1) return rb_fail(why, "dilation " + std::to_string(d->dil[p]) + ": >= 1 is required");
+    if (d->variant < 0 || d->variant > 4) return rb_fail(why, "variant " + std::to_string(d->variant) + ": 0 (the engine's choice), 1 (un-fused), 2 (fused pairs), 3 (whole ResBlock), 4 (segments of tiles)");
+    const bool f32 = arith == VITS_ARITH_F32, bf = arith == VITS_ARITH_BF16;
+    const bool d135 = nd == 3 && d->dil[0] == 1 && d->dil[1] == 3 && d->dil[2] == 5;
+    const std::string shape = "C = " + std::to_string(C) + ", k = " + std::to_string(k);
+    char name[96];
+    int v = d->variant;
+    if (v == 0) {  // engine_vocoder.cpp's order: the whole-ResBlock kernel, fused pairs (all pairs or none), two launches per pair
+        if (f32) {
+            bool pairs = true;
+            for (int p = 0; p < nd; ++p) pairs = pairs && rbpair32_supported(C, k, d->dil[p]);
+            v = pairs && rbblock32_supported(C, k, d->dil, nd) ? 3 : pairs ? 2 : 1;
+        } else if (rbblock16_supported(C, k, d->dil, nd, B, T)) {
+            v = plan_rbblock16(C, k, B, T).nt > 1 ? 4 : 3;
+        } else {
+            bool pairs = true, lat = C >= 128;
+            for (int p = 0; p < nd; ++p) pairs = pairs && rbpair16_supported(C, k, d->dil[p]), lat = lat && conv16_lat_shape_ok(C, k, d->dil[p], B, T);
+            v = pairs && !lat ? 2 : 1;
+        }
+    }
+    r.variant = v;
+    if (v == 1) {
+        r.kernel = f32 ? "launch_conv" : "launch_conv16";
+        r.launches = 2 * nd;
+        return true;
+    }
+    if (v == 2) {
+        if (d->nr != 0 && (f32 || C < 128)) return rb_fail(why, "nr = " + std::to_string(d->nr) + ": only the 16-bit pairs at C >= 128 have a choice of column tiles");
+        for (int p = 0; p < nd; ++p) {
+            const int dil = d->dil[p];
+            LaunchGrid g;
+            int nr = 0;
+            if (f32) {
+                if (!rbpair32_exists(k, dil, C)) return rb_fail(why, "variant 2: no rbpair32_kernel for " + shape + ", dilation " + std::to_string(dil) + " (k in {3, 7, 11}, dilation in {1, 3, 5}, C = 32, 64, or 128 with k = 3)");
+                g = plan_rbpair32(C, k, dil, B, T);
+                if (!g.ok) return rb_fail(why, "variant 2: plan_rbpair32 refuses " + shape + " (VITS_FUSE32_C128=0)");
+            } else {
+                const RbPair16Plan pl = d->nr ? plan_rbpair16(C, k, dil, B, T, d->nr) : plan_rbpair16(C, k, dil, B, T);
+                if (!pl.ok) return rb_fail(why, "variant 2: no rbpair16_kernel for " + shape + ", dilation " + std::to_string(dil) + ", nr = " + std::to_string(d->nr) + " (k in {3, 7, 11}, dilation in {1, 3, 5}, C in {32, 64, 128, 256}, nr 4 or " + std::to_string(VITS_RB16_NARROW_NR) + " at C >= 128)");
+                g = pl, nr = pl.nr;
+            }
+            if (p > 0) continue;  // the plan query describes the first pair; every pair is checked
+            r.g = g, r.nr = nr;
+            if (f32) {
+                const RbPair32Geom ge = rbpair32_geom(k, dil, C);
+                r.bo = ge.bo;
+                std::snprintf(name, sizeof(name), "rbpair32_kernel<%d, %d, %d>", k, dil, C);
+            } else {
+                const RbPair16Geom ge = rbpair16_geom(k, dil, C, nr);
+                r.bo = ge.bo;
+                std::snprintf(name, sizeof(name), "rbpair16_kernel<%d, %d, %d, %d, %s, %s>", k, dil, C, nr, bf ? "true" : "false", ge.rows ? "true" : "false");
+            }
+            r.adv = r.seg = r.bo;
+            r.halo = (k - 1) / 2 * (1 + dil);
+            r.kernel = name;
+        }
+        r.launches = nd;
+        return true;
+    }
+    // variants 3 and 4: the whole-ResBlock kernels
+    if (!d135) return rb_fail(why, "variant " + std::to_string(v) + ": the whole-ResBlock kernels take three pairs with dilations 1, 3, 5");
+    if (v == 4 && f32) return rb_fail(why, "variant 4: segments of tiles exist in the 16-bit modes only (rbblock32_kernel is one tile per block)");
+    if (d->variant == 4 && d->tiles < 2) return rb_fail(why, "variant 4: tiles = " + std::to_string(d->tiles) + ", at least 2 are required");
+    if (f32) {
+        const RbBlock32Plan pl = plan_rbblock32(C, k, B, T);
+        if (!pl.ok) return rb_fail(why, "variant 3: no rbblock32_kernel for " + shape + " (k = 3, C = 32 or 64)");
+        const RbBlock32Geom ge = rbblock32_geom(C, pl.nr);
+        r.g = pl, r.nr = pl.nr, r.bo = r.adv = r.seg = ge.bo, r.halo = ge.h;
+        std::snprintf(name, sizeof(name), "rbblock32_kernel<%d, %d>", C, pl.nr);
+    } else {
+        const int nt = d->variant == 0 ? plan_rbblock16(C, k, B, T).nt : v == 4 ? d->tiles : 1;
+        const RbBlock16Plan pl = plan_rbblock16(C, k, B, T, false, nt);
+        if (!pl.ok) return rb_fail(why, "variant " + std::to_string(v) + ": no rbblock16_kernel for " + shape + " (k in {3, 7, 11} at C = 32 or 64, k = 3 at C = 128)");
+        const RbBlock16Geom ge = rbblock16_geom(k, C);
+        r.g = pl, r.tiles = nt, r.bo = ge.bo, r.adv = nt > 1 ? ge.adv : ge.bo, r.seg = ge.seg_out(nt), r.halo = ge.h;
+        std::snprintf(name, sizeof(name), "rbblock16_kernel<%d, %d, %d, %d, %d, 1, 3, 5, %s, %s>", k, C, pl.tile.nstrip, pl.tile.nrw, pl.tile.mrw, bf ? "true" : "false", nt > 1 ? "true" : "false");
+    }
+    r.kernel = name;
+    r.launches = 1;
+    return true;
+}
+// device memory with every byte `byte` (0xFF: fp32, f16 and bf16 NaNs alike)
+struct DevBytes {
+    void* p = nullptr;
+    ~DevBytes() {
+        if (p) hipFree(p);
+    }
+    bool fill(size_t bytes, int byte) { return hipMalloc(&p, std::max<size_t>(bytes, 16)) == hipSuccess && hipMemset(p, byte, std::max<size_t>(bytes, 16)) == hipSuccess; }
+    bool put(const void* h, size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)) == hipSuccess && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess; }
+    float* f() const { return static_cast<float*>(p); }
+    uint16_t* h() const { return static_cast<uint16_t*>(p); }
+};
+}  // namespace
+
+VITS_API int vits_op_resblock_plan(const vits_resblock_desc* d, vits_resblock_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_resblock_plan: null argument");
+    RbOpPlan r;
+    std::string why;
+    if (!resblock_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", r.kernel.c_str());
+    out->variant = r.variant, out->bo = r.bo, out->advance = r.adv, out->halo = r.halo, out->segment = r.seg, out->tiles = r.tiles, out->nr = r.nr;
+    out->grid_x = r.g.gx, out->grid_y = r.g.gy, out->grid_z = r.g.ok ? r.g.gz : 0, out->block = r.g.block, out->lds = (int64_t)r.g.lds, out->launches = r.launches;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* accum,
+                              const int32_t* lens, float* y) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !w1 || !b1 || !w2 || !b2 || !y) return fail("vits_op_resblock: null argument (x, w1, b1, w2, b2 and y are required)");
+    const int arith = g_op_arith;
+    RbOpPlan r;
+    std::string why;
+    if (!resblock_resolve(d, arith, r, why)) return fail(why.c_str());
+    const int B = d->batch, C = d->channels, T = d->t, k = d->k, nd = d->ndil, ts = round_up(T, 32);
+    for (int b = 0; lens && b < B; ++b)
+        if (lens[b] < 0 || lens[b] > T) return fail("vits_op_resblock: 0 <= lens[b] <= t is required");
+    const bool f32 = arith == VITS_ARITH_F32;
+    const size_t n = (size_t)B * C * ts, wn = (size_t)C * C * k;
+    // the convs on the device
+    struct Conv {
+        PackedConv pc;
+        DevBytes w, wl, w16, b;
+    };
+    std::vector<Conv> cv(2 * nd);  // pair p: conv 1 = cv[2 p], conv 2 = cv[2 p + 1]
+    for (int i = 0; i < 2 * nd; ++i) {
+        Conv& c = cv[i];
+        PackedConv& pc = c.pc;
+        const float* w = (i & 1 ? w2 : w1) + (size_t)(i / 2) * wn;
+        const float* bias = (i & 1 ? b2 : b1) + (size_t)(i / 2) * C;
+        pc.cin = pc.cout = C, pc.kt = k, pc.epi = EPI_STD;
+        const std::vector<float> packed = pack_conv_weights(w, C, C, k, EPI_STD, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+        if (!c.b.put(bias, (size_t)C * 4)) return fail("device allocation failed");
+        pc.bias = c.b.f();
+        if (f32) {
+            if (!c.w.put(packed.data(), packed.size() * 4)) return fail("device allocation failed");
+            pc.wp = c.w.f(), pc.bytes = (int64_t)packed.size() * 4;
+            if (conv_lat16_candidate(EPI_STD, k, C)) {
+                const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, k);
+                if (!c.wl.put(pl.data(), pl.size() * 4)) return fail("device allocation failed");
+                pc.wp_l16 = c.wl.f();
+            }
+        } else {
+            const std::vector<uint16_t> p16 = pack_conv_weights16(w, C, C, k, EPI_STD, 0, arith);
+            if (!c.w16.put(p16.data(), p16.size() * 2)) return fail("device allocation failed");
+            pc.wp16 = c.w16.h(), pc.bytes16 = (int64_t)p16.size() * 2;
+        }
+    }
+    // host staging: NaN everywhere, then the valid columns. std: [b][C][ts]; group: [b][C/8][ts][8]
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    auto len_of = [&](int b) { return lens ? lens[b] : T; };
+    auto stage = [&](const float* src, bool group) {
+        std::vector<float> h(n, qnan);
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < C; ++c) {
+                const float* s = src + ((size_t)b * C + c) * d->t_stride;
+                if (!group) {
+                    std::memcpy(&h[((size_t)b * C + c) * ts], s, sizeof(float) * (size_t)len_of(b));
+                    continue;
+                }
+                float* g = &h[(size_t)b * C * ts + (size_t)(c / 8) * ts * 8 + (c & 7)];
+                for (int t = 0; t < len_of(b); ++t) g[(size_t)t * 8] = s[t];
+            }
+        return h;
+    };
+    DevInts dl;
+    DevBytes dx, dxg, dacc, dout, dp[2], dt, dx16, dn16[2], dt16;
+    if (!dl.put(lens, B)) return fail("device allocation failed");
+    {
+        const std::vector<float> hx = stage(x, false);
+        if (!dx.put(hx.data(), n * 4) || !dout.fill(n * 4, 0) || !dp[0].fill(n * 4, 0xFF) || !dp[1].fill(n * 4, 0xFF)) return fail("device allocation failed");
+        if (accum) {
+            const std::vector<float> ha = stage(accum, !f32);
+            if (!dacc.put(ha.data(), n * 4)) return fail("device allocation failed");
+        }
+    }
+    hipError_t e = hipSuccess;
+    const float scale = d->out_scale;
+    if (f32) {
+        if (r.variant == 1 && !dt.fill(n * 4, 0xFF)) return fail("device allocation failed");
+        const TensorRef bx = tref(dx.f(), C, ts), bout = tref(dout.f(), C, ts), bacc = accum ? tref(dacc.f(), C, ts) : TensorRef();
+        if (r.variant == 3) {
+            const PackedConv *c1[3] = {&cv[0].pc, &cv[2].pc, &cv[4].pc}, *c2[3] = {&cv[1].pc, &cv[3].pc, &cv[5].pc};
+            RbBlock32Call f;
+            f.x = bx, f.y = bout, f.acc = bacc, f.lens = dl.p, f.batch = B, f.tmax = T, f.slope = d->slope, f.scale = scale, f.scale_div = d->scale_div;
+            e = launch_rbblock32(c1, c2, f, nullptr);
+        } else {
+            TensorRef in = bx;
+            for (int p = 0; p < nd && e == hipSuccess; ++p) {
+                const bool last = p + 1 == nd;
+                const TensorRef out = last ? bout : tref(dp[p & 1].f(), C, ts);  // a pair never writes the buffer it reads
+                if (r.variant == 2) {
+                    RbPair32Call f;
+                    f.x = in, f.y = out, f.lens = dl.p, f.batch = B, f.tmax = T, f.dil = d->dil[p], f.slope = d->slope;
+                    if (last) f.acc = bacc, f.scale = scale, f.scale_div = d->scale_div;
+                    e = launch_rbpair32(cv[2 * p].pc, cv[2 * p + 1].pc, f, nullptr);
+                } else {
+                    // conv 1 / conv 2 as engine_vocoder.cpp builds them (mk_c1 / mk_c2): t is stored activated, its only reader is conv 2
+                    ConvCall c1, c2;
+                    c1.len_in = c1.len_out = dl.p;
+                    c1.batch = B;
+                    c1.t_in = c1.t_out = T;
+                    c1.dil = d->dil[p];
+                    c1.pad_l = (k * d->dil[p] - d->dil[p]) / 2;
+                    c2 = c1;
+                    c1.x = in, c1.y = tref(dt.f(), C, ts);
+                    c1.pre_act = 1, c1.slope = d->slope, c1.post_act = 2, c1.post_slope = d->slope;
+                    c2.x = c1.y, c2.dil = 1, c2.pad_l = (k - 1) / 2, c2.res = in, c2.y = out;
+                    if (last) c2.acc = bacc, c2.scale = scale, c2.scale_div = d->scale_div;
+                    e = launch_conv(cv[2 * p].pc, c1, nullptr);
+                    if (e == hipSuccess) e = launch_conv(cv[2 * p + 1].pc, c2, nullptr);
+                }
+                in = out;
+            }
+        }
+    } else {
+        // group layout: the fp32 stream, and the 16-bit copy of leaky_relu(y_0) from the engine's converter
+        const std::vector<float> hg = stage(x, true);
+        const int64_t g_bs = (int64_t)C * ts;
+        auto r16 = [&](const DevBytes& m) {
+            Ref16 q;
+            q.p = m.h(), q.ts = ts, q.bs = g_bs;
+            return q;
+        };
+        if (!dxg.put(hg.data(), n * 4)) return fail("device allocation failed");
+        const float* accg = accum ? dacc.f() : nullptr;
+        if (r.variant >= 3) {
+            const PackedConv *c1[3] = {&cv[0].pc, &cv[2].pc, &cv[4].pc}, *c2[3] = {&cv[1].pc, &cv[3].pc, &cv[5].pc};
+            RbBlock16Call f;
+            f.y0 = dxg.f(), f.lens = dl.p, f.batch = B, f.tmax = T, f.slope = d->slope, f.yg = dout.f(), f.accg = accg, f.g_bs = g_bs, f.g_ts = ts;
+            f.scale = scale, f.scale_div = d->scale_div, f.force_nt = r.tiles;
+            e = launch_rbblock16(c1, c2, f, arith, nullptr);
+        } else {
+            if (!dx16.fill(n * 2, 0xFF) || !dn16[0].fill(n * 2, 0xFF) || !dn16[1].fill(n * 2, 0xFF) || (r.variant == 1 && !dt16.fill(n * 2, 0xFF))) return fail("device allocation failed");
+            e = launch_to_group16(tref(dx.f(), C, ts), dl.p, B, C, T, d->slope, r16(dx16), arith, nullptr);
+            const float* ing = dxg.f();
+            Ref16 in16 = r16(dx16);
+            for (int p = 0; p < nd && e == hipSuccess; ++p) {
+                const bool last = p + 1 == nd;
+                float* outg = last ? dout.f() : dp[p & 1].f();
+                const Ref16 out16 = last ? Ref16() : r16(dn16[p & 1]);
+                if (r.variant == 2) {
+                    RbPair16Call f;
+                    f.x = in16, f.lens = dl.p, f.batch = B, f.tmax = T, f.dil = d->dil[p], f.slope = d->slope, f.yg = outg, f.resg = ing, f.g_bs = g_bs, f.g_ts = ts;
+                    f.y16 = out16, f.y16_slope = last ? 1.f : d->slope, f.force_nr = r.nr;
+                    if (last) f.accg = accg, f.scale = scale, f.scale_div = d->scale_div;
+                    e = launch_rbpair16(cv[2 * p].pc, cv[2 * p + 1].pc, f, arith, nullptr);
+                } else {
+                    // conv 1 / conv 2 as engine_vocoder.cpp builds them (mk_pair): conv 1 writes only the 16-bit t, conv 2 the stream and its 16-bit copy
+                    Conv16Call c1, c2;
+                    c1.x = in16;
+                    c1.len_in = c1.len_out = dl.p;
+                    c1.batch = B;
+                    c1.t_in = c1.t_out = T;
+                    c1.dil = d->dil[p];
+                    c1.pad_l = (k * d->dil[p] - d->dil[p]) / 2;
+                    c1.y16 = r16(dt16);
+                    c1.y16_slope = d->slope;
+                    c2 = c1;
+                    c2.x = c1.y16, c2.dil = 1, c2.pad_l = (k - 1) / 2, c2.g_bs = g_bs, c2.g_ts = ts, c2.resg = ing, c2.yg = outg;
+                    c2.y16 = out16, c2.y16_slope = last ? 1.f : d->slope;
+                    if (last) c2.accg = accg, c2.scale = scale, c2.scale_div = d->scale_div;
+                    e = launch_conv16(cv[2 * p].pc, c1, arith, nullptr);
+                    if (e == hipSuccess) e = launch_conv16(cv[2 * p + 1].pc, c2, arith, nullptr);
+                }
+                ing = outg, in16 = out16;
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_resblock: ") + r.kernel + ": " + hipGetErrorString(e)).c_str());
+    std::vector<float> ho(n);
+    if (hipMemcpy(ho.data(), dout.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c) {
+            float* dst = y + ((size_t)b * C + c) * d->t_stride;
+            if (f32) {
+                std::memcpy(dst, &ho[((size_t)b * C + c) * ts], sizeof(float) * (size_t)T);
+                continue;
+            }
+            const float* g = &ho[(size_t)b * C * ts + (size_t)(c / 8) * ts * 8 + (c & 7)];
+            for (int t = 0; t < T; ++t) dst[t] = g[(size_t)t * 8];
+        }
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y) {
     VITS_TRY
     using namespace vits;

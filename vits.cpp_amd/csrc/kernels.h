@@ -356,6 +356,7 @@ struct RbPair16Call {
     float y16_slope = 1.f;
     float scale = 1.f;
     int scale_div = 0;
+    int force_nr = 0;  // C >= 128: 4 or VITS_RB16_NARROW_NR = that many column tiles per wave whatever the grid (vits_op_resblock); 0: the planner's choice
 };
 bool rbpair16_supported(int channels, int kt, int dil);
 // One whole ResBlock (three pairs, dilations 1 / 3 / 5) as a single kernel (rbblock16.hip): the fp32 stream stays in registers across the
@@ -373,6 +374,7 @@ struct RbBlock16Call {
     float y16_slope = 1.f;
     float scale = 1.f;
     int scale_div = 0;
+    int force_nt = 0;  // N >= 1: every block walks N tiles (1: the one-tile form) whatever the grid and the knobs (vits_op_resblock); 0: the planner's choice
 };
 bool rbblock16_supported(int channels, int kt, const int* dils, int ndil, int batch, int tmax);  // (batch x tmax: the launch's grid — C = 64, k = 11 only where it is cut into segments)
 hipError_t launch_rbblock16(const PackedConv* const* c1, const PackedConv* const* c2, const RbBlock16Call& c, int arith, hipStream_t s);

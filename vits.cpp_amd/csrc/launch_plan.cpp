@@ -12,8 +12,15 @@ static void set_grid(LaunchGrid& p, int gx, int gy, int block, size_t lds, int g
     p.ok = true, p.gx = gx, p.gy = gy, p.gz = gz, p.block = block, p.lds = lds;
 }
 
-RbPair16Plan plan_rbpair16(int C, int kt, int dil, int batch, int tmax) {
+RbPair16Plan plan_rbpair16(int C, int kt, int dil, int batch, int tmax, int force_nr) {
     RbPair16Plan p;
+    if (force_nr) {  // the caller names the instantiation (vits_op_resblock): no knob, no grid rule
+        if (!rbpair16_exists(kt, dil, C, force_nr)) return p;
+        p.nr = force_nr;
+        const RbPair16Geom g = rbpair16_geom(kt, dil, C, p.nr);
+        set_grid(p, blocks_for(tmax, g.bo), batch, g.block, g.lds);
+        return p;
+    }
     // VITS_FUSE16_MAXC=64 keeps the C = 128 pairs on two kernels
     if (!(kt == 3 || kt == 7 || kt == 11) || !(dil == 1 || dil == 3 || dil == 5) || C > kernel_knobs().fuse16_maxc || !(C == 32 || C == 64 || C == 128 || C == 256)) return p;
     // small grids (batch 1 ... 4): the row-split blocks own 128 columns (NR = 4 tiles per wave), i.e. 16 blocks for the 1,808 frames of an
@@ -41,8 +48,15 @@ static int rbb_stream_tiles_for(int kt, int C, int batch, int tmax) {
     return (int)(blocks1 / kn.rbb_stream_min_blocks < want ? blocks1 / kn.rbb_stream_min_blocks : want);
 }
 
-RbBlock16Plan plan_rbblock16(int C, int kt, int batch, int tmax, bool in_group) {
+RbBlock16Plan plan_rbblock16(int C, int kt, int batch, int tmax, bool in_group, int force_nt) {
     RbBlock16Plan p;
+    if (force_nt > 0) {  // the caller names the form (vits_op_resblock): no knob, no grid rule
+        if (!rbblock16_exists(kt, C)) return p;
+        p.tile = rbblock16_tile(kt, C), p.nt = force_nt;
+        const RbBlock16Geom g = rbblock16_geom(kt, C);
+        set_grid(p, blocks_for(tmax, g.seg_out(force_nt)), batch, g.block, g.lds(force_nt > 1));
+        return p;
+    }
     if (!rbblock16_exists(kt, C) || (C == 128 && !kernel_knobs().rbb_c128)) return p;
     const int nt = rbb_stream_tiles_for(kt, C, batch, tmax);
     // C = 64, k = 11: on one tile per block (1.45 x the MFMA work) the whole-resblock kernel is bound by the matrix cores (at the clock

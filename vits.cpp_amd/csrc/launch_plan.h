@@ -167,13 +167,15 @@ struct LaunchGrid {
 struct RbPair16Plan : LaunchGrid {
     int nr = 0;
 };
-RbPair16Plan plan_rbpair16(int channels, int kt, int dil, int batch, int tmax);
+// force_nr (C >= 128): that many column tiles per wave whatever the grid and VITS_FUSE16_MAXC, or a refusal where no such instantiation exists; 0: the policy
+RbPair16Plan plan_rbpair16(int channels, int kt, int dil, int batch, int tmax, int force_nr = 0);
 struct RbBlock16Plan : LaunchGrid {
     RbBlock16Tile tile = {0, 0, 0};
     int nt = 1;  // tiles a block walks (> 1: the STREAM instantiation)
 };
 // in_group: as a member of the grouped launch, where C = 64, k = 11 is a whole-resblock kernel whatever VITS_RBB_C64K11 says for the single launch
-RbBlock16Plan plan_rbblock16(int channels, int kt, int batch, int tmax, bool in_group = false);
+// force_nt >= 1: that many tiles per block on every shape with an instantiation, whatever the grid and the knobs say (C = 64, k = 11 on one tile included); 0: the policy
+RbBlock16Plan plan_rbblock16(int channels, int kt, int batch, int tmax, bool in_group = false, int force_nt = 0);
 LaunchGrid plan_rbblock16_group3(int channels, const int* kts, int batch, int tmax);
 LaunchGrid plan_rbpair32(int channels, int kt, int dil, int batch, int tmax);
 struct RbBlock32Plan : LaunchGrid {

@@ -466,7 +466,7 @@ static hipError_t rbb_params(const PackedConv* const* c1, const PackedConv* cons
         p.b1[i] = c1[i]->bias;
         p.b2[i] = c2[i]->bias;
     }
-    l = plan_rbblock16(C, kt, c.batch, c.tmax, in_group);
+    l = plan_rbblock16(C, kt, c.batch, c.tmax, in_group, in_group ? 0 : c.force_nt);
     if (!l.ok || !c.y0 || (!c.yg && !c.y16.p)) return hipErrorInvalidValue;
     p.y0 = c.y0, p.lens = c.lens, p.tmax = c.tmax, p.slope = c.slope, p.yg = c.yg, p.accg = c.accg, p.g_bs = c.g_bs, p.g_ts = c.g_ts, p.y16 = c.y16.p;
     p.y16_bs = c.y16.bs, p.y16_ts = c.y16.ts, p.y16_slope = c.y16_slope, p.scale = c.scale, p.scale_div = c.scale_div;

@@ -381,7 +381,7 @@ static hipError_t launch_rb_kt(int kt, int dil, const RbPairParams& p, const RbP
 }
 
 hipError_t launch_rbpair16(const PackedConv& c1, const PackedConv& c2, const RbPair16Call& c, int arith, hipStream_t s) {
-    const RbPair16Plan l = plan_rbpair16(c1.cin, c1.kt, c.dil, c.batch, c.tmax);
+    const RbPair16Plan l = plan_rbpair16(c1.cin, c1.kt, c.dil, c.batch, c.tmax, c.force_nr);
     if (!c1.wp16 || !c2.wp16 || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !l.ok)
         return hipErrorInvalidValue;
     RbPairParams p;
