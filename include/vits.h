@@ -386,6 +386,62 @@ VITS_API int vits_resample_plan(int32_t in_rate, int32_t out_rate, int32_t* L, i
 VITS_API int64_t vits_resample_taps(int32_t in_rate, int32_t out_rate, float* dst, size_t cap);
 VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t n);
 
+/* ---- a stated level: gain, sample peak and ITU-R BS.1770-4 integrated loudness, on the device -----------------------------------
+ * The vocoder's tanh output comes out as it falls; vits_model_set_level(model, kind, value_db, ceiling_db) makes every PCM the handle
+ * delivers (vits_model_process, _process_ids, _process_batch, _submit_batch / _wait, _convert, _convert_batch; out_device, skip_host_copy
+ * and async included: there is no host read) leave at a stated level. The model-rate waveform x of N samples (tap "waveform", unchanged)
+ * is measured, multiplied by one gain g per utterance, and THEN resampled if an output rate is set (vits_model_set_rates): levelling
+ * comes before the resampler, never after. Alignment is unaffected. Levelling is the same arithmetic in every VITS_ARITH_* mode.
+ *
+ * The measurement, at rate fs, mono. K-weighting = two biquads whose coefficients are computed in double on the host from the analogue
+ * prototypes (at 48 kHz they are the table of BS.1770):
+ *   stage 1 (shelf): f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *     b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0,  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *   stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773, the same K and a0 formulas,
+ *     b = [1, -2, 1],  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ * S = (fs + 5) / 10 (integer division) samples make a 100 ms segment; segment i covers the utterance's own samples [i S, (i + 1) S);
+ * z_i = the mean square of the K-weighted signal over it (filter state zero before sample 0, carried through the whole utterance); a
+ * trailing partial segment is dropped. Block j = mean(z_j .. z_(j+3)), j = 0 .. n_seg - 4 (400 ms, 75 % overlap), l_j = -0.691 + 10
+ * log10(block_j). Gates: keep the blocks with l_j > -70; Gamma = -0.691 + 10 log10(mean of the kept blocks) - 10; keep those of them with
+ * l_j > Gamma; L = -0.691 + 10 log10(mean of those), in LUFS. Fewer than four segments, or no block above -70: the utterance is
+ * UNMEASURABLE, L = -inf. P = max |x| over [0, N) is the SAMPLE peak, not the true (inter-sample) peak of BS.1770 annex 2.
+ * On the device filter, sums and gates are fp64; L and P are reported in fp32 and g is computed from the reported values.
+ *
+ *   kind                  gain g (linear)
+ *   VITS_LEVEL_NONE       (default) nothing is queued, nothing is allocated, every bit is what it was
+ *   VITS_LEVEL_MEASURE    1: measured, nothing applied, the PCM bits unchanged
+ *   VITS_LEVEL_GAIN       10^(value_db / 20)
+ *   VITS_LEVEL_PEAK       10^(value_db / 20) / P; 1 if P == 0
+ *   VITS_LEVEL_LOUDNESS   min(10^((value_db - L) / 20), 10^(ceiling_db / 20) / P); 1 if unmeasurable or P == 0
+ * Delivered sample = x * g, one fp32 multiply: no clamp, no limiter beyond the ceiling rule, no dither.
+ * vits_model_set_level: 0, or -1 + message with the handle unchanged: an unknown kind, a value that is not finite, value_db outside
+ * [-70, 0] (LOUDNESS), [-60, 0] (PEAK) or [-60, 40] (GAIN), ceiling_db outside [-60, 0] (LOUDNESS only; the other kinds ignore it),
+ * batches in flight, or a call from inside on_chunk ("model busy").
+ * Streaming: with on_chunk only VITS_LEVEL_GAIN is accepted (every window's finished samples are multiplied once, so the chunks still
+ * tile the utterance and their concatenation equals the unchunked result bit for bit); the other kinds need the whole utterance before
+ * the first sample can leave and are refused with a message that says so. vocoder_chunk_frames without on_chunk works with every kind:
+ * levelling runs behind the last window. Taps: "waveform_level" [1][N] is the multiplied model-rate waveform (the waveform itself under
+ * VITS_LEVEL_MEASURE); "waveform_out" stays the delivered PCM.
+ *
+ * vits_model_last_levels: the rows [B][4] = {L in LUFS (-inf: unmeasurable), P linear, g linear, blocks that passed both gates} of the
+ * most recently completed call on the handle (process*, convert*, or the batch vits_model_wait returned last), written to dst when cap
+ * >= 4 B. Returns 4 B, 0 when that call ran under VITS_LEVEL_NONE, -1 on a null argument. After an async call the values are valid
+ * after vits_model_sync. The device row buffer is counted in vits_model_weight_bytes once allocated. */
+#define VITS_LEVEL_NONE 0
+#define VITS_LEVEL_MEASURE 1
+#define VITS_LEVEL_GAIN 2
+#define VITS_LEVEL_PEAK 3
+#define VITS_LEVEL_LOUDNESS 4
+VITS_API int vits_model_set_level(vits_model* model, int32_t kind, float value_db, float ceiling_db);
+VITS_API int vits_model_get_level(const vits_model* model, int32_t* kind, float* value_db, float* ceiling_db);
+VITS_API int64_t vits_model_last_levels(vits_model* model, float* dst, size_t cap);
+/* The measurement itself: host only, no device needed. vits_loudness_plan: the two biquads as b0 b1 b2 a1 a2 each (coef, optional) and
+ * S (segment, optional) at a rate in [4000, 192000]; 0, or -1 + message. vits_loudness_host: the definition above in double, sequentially,
+ * on n samples at `rate`: *lufs (-inf: unmeasurable), *peak, *blocks (each optional); 0, or -1 + message (a refused rate, pcm NULL with n > 0). */
+VITS_API int vits_loudness_plan(int32_t rate, double coef[10], int32_t* segment);
+VITS_API int vits_loudness_host(const float* pcm, size_t n, int32_t rate, double* lufs, double* peak, int32_t* blocks);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -613,6 +669,23 @@ VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, in
  * output row. */
 VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens,
                               float* y, int64_t y_stride);
+
+/* The levelling kernels (see vits_model_set_level for the definition) on a ragged batch, staged exactly as the engine stages it: x host
+ * [batch][x_stride] at `rate`, lens host [batch] (0 <= lens[b] <= x_stride; NULL: every row has x_stride). The device copy of x holds NaNs
+ * behind every lens[b], so a read past an utterance shows. levels: out, host [batch][4] = {L, P, g, blocks}. y: host [batch][y_stride] or
+ * NULL (measure only); row b gets its lens[b] samples x * g, everything behind them is left as it was. kind: VITS_LEVEL_MEASURE .. _LOUDNESS,
+ * values as vits_model_set_level checks them. Refused (-1 + message): what vits_model_set_level refuses, VITS_LEVEL_NONE, a rate outside
+ * [4000, 192000], a length outside its row, a y_stride shorter than the longest row. */
+typedef struct vits_level_desc {
+    int32_t rate;
+    int32_t batch;
+    int64_t x_stride;
+    int64_t y_stride;
+    int32_t kind;
+    float value_db;
+    float ceiling_db;
+} vits_level_desc;
+VITS_API int vits_op_level(const vits_level_desc* d, const float* x, const int64_t* lens, float* y, float* levels);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

@@ -26,6 +26,8 @@ DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
 DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
 RB_VARIANT_PLAN, RB_VARIANT_UNFUSED, RB_VARIANT_PAIRS, RB_VARIANT_BLOCK, RB_VARIANT_SEGMENTS = 0, 1, 2, 3, 4  # op_resblock
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
+# vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
+LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
 #: every symbol include/vits.h declares (checked by tests/test_abi.py)
@@ -48,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_prepare_conversion", "vits_model_convert_batch", "vits_model_convert",
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
+    "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
@@ -59,6 +62,12 @@ class VitsResult(C.Structure):
 
 # int on_chunk(void* user, int32 utt, size_t offset, const float* pcm, size_t n)  (include/vits.h vits_chunk_callback)
 ChunkCallback = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_size_t, C.POINTER(C.c_float), C.c_size_t)
+
+
+class LevelDesc(C.Structure):
+    """vits_level_desc"""
+    _fields_ = [("rate", C.c_int32), ("batch", C.c_int32), ("x_stride", C.c_int64), ("y_stride", C.c_int64), ("kind", C.c_int32),
+                ("value_db", C.c_float), ("ceiling_db", C.c_float)]
 
 
 class ProcessOpts(C.Structure):
@@ -228,6 +237,18 @@ def lib():
     L.vits_resample_length.argtypes = [i32, i32, i64]
     L.vits_op_resample.restype = i32
     L.vits_op_resample.argtypes = [i32, i32, i32, vp, i64, vp, vp, i64]
+    L.vits_model_set_level.restype = i32
+    L.vits_model_set_level.argtypes = [vp, i32, C.c_float, C.c_float]
+    L.vits_model_get_level.restype = i32
+    L.vits_model_get_level.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.vits_model_last_levels.restype = i64
+    L.vits_model_last_levels.argtypes = [vp, vp, sz]
+    L.vits_loudness_plan.restype = i32
+    L.vits_loudness_plan.argtypes = [i32, vp, C.POINTER(i32)]
+    L.vits_loudness_host.restype = i32
+    L.vits_loudness_host.argtypes = [vp, sz, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
+    L.vits_op_level.restype = i32
+    L.vits_op_level.argtypes = [C.POINTER(LevelDesc), vp, vp, vp, vp]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -648,6 +669,35 @@ class Model:
     @noise_scale_duration.setter
     def noise_scale_duration(self, v):
         self.set_prosody(noise_scale_duration=v)
+
+    # -- a stated level (vits_model_set_level): gain, sample peak or BS.1770 loudness of every PCM the handle delivers ------------------------------
+    @property
+    def level(self):
+        """(kind, value_db, ceiling_db) of the handle; kind is one of LEVEL_NONE .. LEVEL_LOUDNESS"""
+        k, v, c = C.c_int32(), C.c_float(), C.c_float()
+        if lib().vits_model_get_level(self._h, C.byref(k), C.byref(v), C.byref(c)) != 0:
+            raise VitsError(last_error())
+        return int(k.value), float(v.value), float(c.value)
+
+    def set_level(self, kind=LEVEL_NONE, value_db=0.0, ceiling_db=0.0):
+        """vits_model_set_level: LEVEL_NONE (nothing is queued), LEVEL_MEASURE (measured only), LEVEL_GAIN (value_db of gain), LEVEL_PEAK (sample peak at
+        value_db) or LEVEL_LOUDNESS (value_db LUFS, the sample peak kept at or below ceiling_db). The model-rate waveform is measured and multiplied on
+        the device, before the resampler; last_levels() reads what was measured."""
+        if lib().vits_model_set_level(self._h, int(kind), float(value_db), float(ceiling_db)) != 0:
+            raise VitsError(last_error())
+
+    def last_levels(self):
+        """vits_model_last_levels: float32 [B, 4] = (L in LUFS, -inf = unmeasurable; sample peak; gain; blocks that passed both gates) of the most
+        recently completed call, or None when it ran with LEVEL_NONE. After an async call: valid after sync()."""
+        n = lib().vits_model_last_levels(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n // 4, 4), np.float32)
+        if lib().vits_model_last_levels(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
 
     # -- any sample rate (vits_model_set_rates): 0 = the model's own rate --------------------------------------------------------------
     @property
@@ -1094,6 +1144,48 @@ def resample(x, in_rate, out_rate, lens=None, out=None):
     if lib().vits_op_resample(int(in_rate), int(out_rate), B, _ptr(x), stride, _ptr(ln), _ptr(out), out.shape[1]) != 0:
         raise VitsError(last_error())
     return out, n_out
+
+
+def loudness_plan(rate):
+    """vits_loudness_plan: (coef float64 [2, 5] = b0 b1 b2 a1 a2 of the shelf and of the high-pass, S = samples per 100 ms segment) at `rate` (host only)"""
+    coef, seg = np.zeros((2, 5), np.float64), C.c_int32()
+    if lib().vits_loudness_plan(int(rate), _ptr(coef), C.byref(seg)) != 0:
+        raise VitsError(last_error())
+    return coef, int(seg.value)
+
+
+def loudness_host(pcm, rate):
+    """vits_loudness_host: (L in LUFS, -inf = unmeasurable; sample peak; blocks that passed both gates) of one utterance, the definition of
+    include/vits.h in double on the host (no device needed)"""
+    x = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
+    l, p, nb = C.c_double(), C.c_double(), C.c_int32()
+    if lib().vits_loudness_host(_ptr(x), x.size, int(rate), C.byref(l), C.byref(p), C.byref(nb)) != 0:
+        raise VitsError(last_error())
+    return float(l.value), float(p.value), int(nb.value)
+
+
+def level(x, rate, kind=LEVEL_MEASURE, value_db=0.0, ceiling_db=0.0, lens=None, out=None, apply=True):
+    """The levelling kernels on a ragged batch (vits_op_level), staged as the engine stages it. x: float32 [B, x_stride] (or one 1-D row) at `rate`; lens:
+    samples per row (None = the whole row). Returns (y, levels): levels float32 [B, 4] = (L, P, g, blocks); y float32 [B, y_stride] holds row b's lens[b]
+    samples x * g (zeros, or what `out` held, behind them), or is None with apply=False (measure only)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    if not apply:
+        out = None
+    elif out is None:
+        out = np.zeros((B, max(int(ln.max()), 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    d = LevelDesc(int(rate), B, max(stride, 1), out.shape[1] if out is not None else 0, int(kind), float(value_db), float(ceiling_db))
+    levels = np.zeros((B, 4), np.float32)
+    if lib().vits_op_level(C.byref(d), _ptr(x), _ptr(ln), _ptr(out) if out is not None else None, _ptr(levels)) != 0:
+        raise VitsError(last_error())
+    return out, levels
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

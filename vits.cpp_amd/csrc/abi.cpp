@@ -3,6 +3,7 @@
 // src/include/debug.h:29-36); failures return NULL / {NULL,0} / -1 and set vits_last_error().
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -567,6 +568,72 @@ VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t
         return -1;
     }
     return p.out_len(n);
+    VITS_CATCH(-1)
+}
+// ---- a stated level (include/vits.h: the definition and the kinds) -------------------------------------------------------------------
+VITS_API int vits_model_set_level(vits_model* model, int32_t kind, float value_db, float ceiling_db) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_level(kind, value_db, ceiling_db, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_get_level(const vits_model* model, int32_t* kind, float* value_db, float* ceiling_db) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (kind) *kind = model->eng.level_kind();
+    if (value_db) *value_db = model->eng.level_value_db();
+    if (ceiling_db) *ceiling_db = model->eng.level_ceiling_db();
+    return 0;
+}
+VITS_API int64_t vits_model_last_levels(vits_model* model, float* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const float* p = model->eng.last_levels(rows);
+    const size_t n = (size_t)4 * rows;
+    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(float) * n);
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_loudness_plan(int32_t rate, double coef[10], int32_t* segment) {
+    VITS_TRY
+    vits::LoudnessPlan p;
+    std::string err;
+    if (!vits::loudness_plan(rate, p, err)) {
+        set_err("vits_loudness_plan: " + err);
+        return -1;
+    }
+    if (coef) std::memcpy(coef, p.coef.c, sizeof(double) * 10);
+    if (segment) *segment = p.S;
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_loudness_host(const float* pcm, size_t n, int32_t rate, double* lufs, double* peak, int32_t* blocks) {
+    VITS_TRY
+    vits::LoudnessPlan p;
+    std::string err;
+    if (!vits::loudness_plan(rate, p, err)) {
+        set_err("vits_loudness_host: " + err);
+        return -1;
+    }
+    if (!pcm && n) {
+        set_err("vits_loudness_host: null argument (pcm is NULL with n > 0)");
+        return -1;
+    }
+    int nb = 0;
+    vits::loudness_host(pcm, n, p, lufs, peak, &nb);
+    if (blocks) *blocks = nb;
+    return 0;
     VITS_CATCH(-1)
 }
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
@@ -1628,6 +1695,72 @@ VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipMemcpy(y, dy.p, (size_t)batch * y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_level(const vits_level_desc* d, const float* x, const int64_t* lens, float* y, float* levels) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !levels || d->batch <= 0 || d->x_stride <= 0 || (y && d->y_stride <= 0)) return fail("vits_op_level: null argument or empty batch");
+    if (d->kind == VITS_LEVEL_NONE) return fail("vits_op_level: VITS_LEVEL_NONE measures and applies nothing (use VITS_LEVEL_MEASURE)");
+    LoudnessPlan plan;
+    std::string err;
+    if (!loudness_plan(d->rate, plan, err)) return fail(("vits_op_level: " + err).c_str());
+    if (!level_values_ok(d->kind, d->value_db, d->ceiling_db, err)) return fail(("vits_op_level: " + err).c_str());
+    const int B = d->batch;
+    std::vector<int32_t> n(B);
+    int64_t longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = lens ? lens[b] : d->x_stride;
+        if (len < 0 || len > d->x_stride)
+            return fail(("vits_op_level: lens[" + std::to_string(b) + "] = " + std::to_string(len) + " is outside [0, x_stride = " + std::to_string(d->x_stride) + "]").c_str());
+        if (len > ((int64_t)1 << 30)) return fail(("vits_op_level: row " + std::to_string(b) + " is too long (" + std::to_string(len) + " samples)").c_str());
+        n[b] = (int32_t)len;
+        longest = std::max(longest, len);
+    }
+    if (y && d->y_stride < longest) return fail(("vits_op_level: y_stride = " + std::to_string(d->y_stride) + " is shorter than the longest row (" + std::to_string(longest) + " samples)").c_str());
+    // the engine's staging: rows at a stride of a multiple of 32 samples, NaN behind every utterance: a read past one shows in the result
+    const int64_t xs = (longest + 31) / 32 * 32 + 32;
+    std::vector<float> hx((size_t)B * xs, std::numeric_limits<float>::quiet_NaN());
+    for (int b = 0; b < B; ++b) std::memcpy(&hx[(size_t)b * xs], x + (size_t)b * d->x_stride, sizeof(float) * (size_t)n[b]);
+    const size_t scratch = level_scratch_bytes(B, longest, plan.S);
+    DevBuf dx, dy, dlv, dscr;
+    DevInts dn;
+    // (y goes up too: what lies behind a row's samples must come back as it was)
+    if (!dx.put(hx.data(), hx.size()) || !dlv.put(nullptr, (size_t)B * 4) || !dscr.put(nullptr, (scratch + 3) / 4) || !dn.put(n.data(), B) ||
+        (y && !dy.put(y, (size_t)B * d->y_stride)))
+        return fail("device allocation failed");
+    LevelCall c;
+    c.x = dx.p;
+    c.x_stride = xs;
+    c.lens = dn.p;
+    c.batch = B;
+    c.max_len = longest;
+    c.plan = plan;
+    c.scratch = dscr.p;
+    c.kind = d->kind;
+    c.value_db = d->value_db;
+    c.ceiling_db = d->ceiling_db;
+    c.gain = (float)std::pow(10.0, (double)d->value_db / 20.0);
+    c.levels = dlv.p;
+    hipError_t e = launch_level_measure(c, nullptr);
+    if (e == hipSuccess && y) {
+        LevelScale sc;
+        sc.x = dx.p;
+        sc.x_stride = xs;
+        sc.y = dy.p;
+        sc.y_stride = d->y_stride;
+        sc.lens = dn.p;
+        sc.levels = dlv.p;
+        sc.batch = B;
+        sc.max_range = longest;
+        e = launch_level_scale(sc, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(levels, dlv.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    if (y && hipMemcpy(y, dy.p, (size_t)B * d->y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     return 0;
     VITS_CATCH(-1)
 }

@@ -1,6 +1,7 @@
 // engine.cpp — one call from ids to PCM (see engine.h): input checks, the two arenas, the single host read of the frame counts,
 // vocoder windows / streaming, results. The phases themselves live in engine_stage1.cpp, engine_flow.cpp and engine_vocoder.cpp.
 // Compiled with hipcc as host C++.
+#include <cmath>
 #include <numeric>
 
 #include "engine_internal.h"
@@ -111,6 +112,11 @@ hipError_t Engine::conv(const char* name, const PackedConv& w, ConvCall c, hipSt
 int Engine::sync(std::string& err) {
     if (front_) HIP_OK(hipStreamSynchronize(front_));
     HIP_OK(hipStreamSynchronize(stream));
+    if (async_tail_ && last_lv_rows_ && last_lv_ != last_lv_store_.data()) {
+        // the rows of the async call have landed: keep them apart from the pinned copy, which a later submit into that slot overwrites
+        last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * last_lv_rows_);
+        last_lv_ = last_lv_store_.data();
+    }
     async_tail_ = false;
     return 0;
 }
@@ -206,6 +212,96 @@ hipError_t Engine::resample(const char* name, const ResampleCall& rc, int64_t in
     return e;
 }
 
+int Engine::set_level(int kind, float value_db, float ceiling_db, std::string& err) {
+    const char* who = "vits_model_set_level: ";
+    std::string why;
+    if (!level_values_ok(kind, value_db, ceiling_db, why)) {
+        err = who + why;
+        return -1;
+    }
+    if (kind != VITS_LEVEL_NONE) {
+        LoudnessPlan p;
+        if (!loudness_plan(hp.sampling_rate, p, why)) {
+            err = who + ("the model's " + why);
+            return -1;
+        }
+        level_plan_ = p;
+    }
+    level_kind_ = kind;
+    level_value_ = kind >= VITS_LEVEL_GAIN ? value_db : 0.f;
+    level_ceiling_ = kind == VITS_LEVEL_LOUDNESS ? ceiling_db : 0.f;
+    return 0;
+}
+
+int Engine::check_level(const vits_process_opts& o, std::string& err) const {
+    if (o.on_chunk && level_kind_ != VITS_LEVEL_NONE && level_kind_ != VITS_LEVEL_GAIN) {
+        err = "on_chunk streams an utterance while it is being made, and this handle's level (vits_model_set_level: measure, peak or loudness) needs the whole "
+              "utterance before its first sample can leave: only VITS_LEVEL_GAIN streams";
+        return -1;
+    }
+    return 0;
+}
+
+// the tail of a levelling call: loudness, peak and gain of every utterance of the vocoder's waveform (c.wave_dst: the call's own buffer, or out_device under
+// VITS_LEVEL_MEASURE, which changes no PCM path) -> lv_rows_, the multiply into dst (every kind but MEASURE; a
+// streaming call has multiplied window by window already), and the rows on their way to the slot's pinned copy
+int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
+    std::string& err = c.err;
+    const int B = c.B, n_up = c.n_up;
+    if (B > lv_cap_) {
+        // (grow-only; the old rows are the previous call's, already on their way to the host in stream order — hipFree waits for them)
+        const int cap = std::max(B, 64);
+        float* fresh = nullptr;
+        HIP_OK(hipMalloc((void**)&fresh, sizeof(float) * 4 * (size_t)cap));
+        if (lv_rows_) {
+            for (void*& p : owned_)
+                if (p == lv_rows_) p = fresh;
+            hipFree(lv_rows_);
+        } else owned_.push_back(fresh);
+        weight_bytes += (int64_t)sizeof(float) * 4 * (cap - lv_cap_);
+        lv_rows_ = fresh, lv_cap_ = cap;
+    }
+    const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
+    LevelCall lc;
+    lc.x = c.wave_dst;
+    lc.x_stride = c.wave_stride;
+    lc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    lc.batch = B;
+    lc.max_len = c.smax[n_up];
+    lc.plan = level_plan_;
+    lc.scratch = c.s2.lvl_scratch;
+    lc.kind = c.lev;
+    lc.value_db = level_value_;
+    lc.ceiling_db = level_ceiling_;
+    lc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);
+    lc.levels = lv_rows_;
+    // two walks of the cascade (9 fp64 fma a sample each) and the squares; the samples read twice
+    prof.begin("level_measure", 2.0 * (2 * 9 + 1) * (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
+    hipError_t e = launch_level_measure(lc, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    if (c.lev_apply && !c.o.on_chunk) {
+        LevelScale sc;
+        sc.x = c.wave_dst;
+        sc.x_stride = c.wave_stride;
+        sc.y = dst;
+        sc.y_stride = dst_stride;
+        sc.lens = lc.lens;
+        sc.levels = lv_rows_;
+        sc.batch = B;
+        sc.max_range = c.smax[n_up];
+        prof.begin("level_scale", (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
+        e = launch_level_scale(sc, stream);
+        prof.end(stream);
+        HIP_OK(e);
+    }
+    PinnedBuf<float>& host = lv_host_[a1_slot_ & 1];
+    HIP_OK(host.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
+    HIP_OK(hipMemcpyAsync(host.p, lv_rows_, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    prof.fence();
+    return 0;
+}
+
 int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const {
     if (o.fixed_duration > 0 && (o.speaking_rates || o.duration_override)) {
         err = std::string(o.speaking_rates ? "speaking_rates" : "duration_override") + " cannot be combined with fixed_duration > 0 (every token already lasts fixed_duration frames)";
@@ -241,6 +337,8 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
     if (refuse_pending(err)) return -1;
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
+    if (check_level(o, err)) return -1;
+    last_lv_rows_ = 0;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -297,6 +395,16 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
             }
         }
     } release{*this, part};
+    if (!rc && part[0]->lv_rows + part[1]->lv_rows > 0) {
+        // (the parts' rows side by side; part h lives in pipeline slot (wait_seq_ + h) & 1)
+        last_lv_store_.clear();
+        for (int h = 0; h < 2; ++h) {
+            const float* rows = lv_host_[(wait_seq_ + h) & 1].p;
+            last_lv_store_.insert(last_lv_store_.end(), rows, rows + (size_t)4 * part[h]->lv_rows);
+        }
+        last_lv_ = last_lv_store_.data();
+        last_lv_rows_ = (int)(last_lv_store_.size() / 4);
+    }
     if (!rc && out) {
         const size_t stride = std::max(part[0]->stride, part[1]->stride);
         out->batch = (size_t)B;
@@ -377,6 +485,11 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
             std::memcpy(out->data, p.host.p, sizeof(float) * (size_t)p.B * p.stride);
         }
     }
+    // the levels of the batch that has just completed (copied: the slot's pinned rows are the next submit's)
+    const float* rows = lv_host_[wait_seq_ & 1].p;
+    last_lv_store_.assign(rows, rows + (size_t)4 * p.lv_rows);
+    last_lv_ = last_lv_store_.data();
+    last_lv_rows_ = p.lv_rows;
     p.active = false;
     ++wait_seq_;
     return 0;
@@ -602,6 +715,10 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         c.out_ws = round_up(std::max(c.out_max, 1), 32);
     }
     const bool rs = c.rate_out != nullptr;
+    // a level that multiplies (every kind but VITS_LEVEL_MEASURE): the vocoder writes to the call's own buffer, loudness.hip measures it there and
+    // multiplies it into what is delivered, or into the resampler's input. VITS_LEVEL_MEASURE measures the waveform where the vocoder wrote it
+    c.lev = level_kind_;  // (on_chunk with a kind that cannot stream was refused by process_batch / convert_batch, before stage one was queued)
+    const bool la = c.lev_apply = level_kind_ >= VITS_LEVEL_GAIN;
 
     if (layout_stage_two(c)) return -1;
     if (c.vc) {
@@ -628,18 +745,21 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             if (rs) err += " (" + std::to_string(pcm_max) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
             return -1;
         }
-        if (!rs) {
+        if (!rs && !la) {
             c.wave_dst = (float*)o.out_device;
             c.wave_stride = o.out_device_stride;
         }
     }
     float* const wave_dst = c.wave_dst;
     const int64_t wave_stride = c.wave_stride;
-    float* const pcm_dst = !rs ? wave_dst : o.out_device ? (float*)o.out_device : c.s2.wave_out;
-    const int64_t pcm_stride = !rs ? wave_stride : o.out_device ? o.out_device_stride : (int64_t)c.out_ws;
+    // the levelled model-rate waveform: delivered as it is (straight to out_device), or the resampler's input
+    float* const lvl_dst = !la ? nullptr : (!rs && o.out_device) ? (float*)o.out_device : c.s2.wave_lvl;
+    const int64_t lvl_stride = !la ? 0 : (!rs && o.out_device) ? o.out_device_stride : (int64_t)c.S_stride;
+    float* const pcm_dst = rs ? (o.out_device ? (float*)o.out_device : c.s2.wave_out) : la ? lvl_dst : wave_dst;
+    const int64_t pcm_stride = rs ? (o.out_device ? o.out_device_stride : (int64_t)c.out_ws) : la ? lvl_stride : wave_stride;
     ResampleCall rsc;
     if (rs) {
-        rsc.x = c.s2.wave;
+        rsc.x = la ? lvl_dst : c.s2.wave;
         rsc.x_stride = c.S_stride;
         rsc.lens = c.s1.stage_lens + (size_t)n_up * B;  // (device: every utterance's samples at the model's rate)
         rsc.y = pcm_dst;
@@ -679,6 +799,29 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         HIP_OK(hipMemcpyAsync(c.s2.out_ranges, rg.data(), sizeof(int) * rg.size(), hipMemcpyHostToDevice, stream));
         prof.fence();
         HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
+    }
+    // streaming under VITS_LEVEL_GAIN: window w multiplies the model-rate samples it makes final, [E_(w-1), E_w) of every utterance, once: lrg [window][2][B]
+    std::vector<int> lrg;
+    LevelScale lsc;
+    if (la && o.on_chunk) {
+        lrg.assign(wins.size() * (size_t)2 * B, 0);
+        for (size_t w = 0; w < wins.size(); ++w)
+            for (int b = 0; b < B; ++b) {
+                const Call::Win& wn = wins[w];
+                if (frames[b] <= wn.f0) continue;
+                lrg[(w * 2) * B + b] = wn.f0 * M;
+                lrg[(w * 2 + 1) * B + b] = frames[b] <= wn.f1 ? c.slen[n_up][b] : wn.f1 * M;
+            }
+        HIP_OK(hipMemcpyAsync(c.s2.lvl_ranges, lrg.data(), sizeof(int) * lrg.size(), hipMemcpyHostToDevice, stream));
+        prof.fence();
+        HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
+        lsc.x = wave_dst;  // (the call's own buffer: a level that multiplies keeps the vocoder there)
+        lsc.x_stride = wave_stride;
+        lsc.y = lvl_dst;
+        lsc.y_stride = lvl_stride;
+        lsc.lens = c.s1.stage_lens + (size_t)n_up * B;
+        lsc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);  // (the float run_level reports)
+        lsc.batch = B;
     }
     if (windowed) {
         // per window and utterance: frames inside the window -> stage lengths (0 everywhere when the utterance has none),
@@ -765,6 +908,22 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             // (+ the no-crop tail of utterances that end inside this window, Q1; the same columns of longer utterances are not
             // final yet and travel again with the next window)
             size_t g0 = (size_t)wn.f0 * M, g1 = std::min(out_stride, (size_t)wn.f1 * M + (size_t)sadd[n_up]);
+            if (la) {
+                // the gain on what this window made final, before anything reads it (the resampler below, the copy to the host)
+                int64_t n = 0;
+                for (int b = 0; b < B; ++b) {
+                    const int64_t r = lrg[(wi * 2 + 1) * B + b] - lrg[(wi * 2) * B + b];
+                    lsc.max_range = std::max(lsc.max_range, r);
+                    n += r;
+                }
+                lsc.j0 = c.s2.lvl_ranges + (wi * 2) * B;
+                lsc.j1 = lsc.j0 + B;
+                prof.begin("level_scale", (double)n, 8.0 * (double)n, stream, /*chain=*/true);
+                const hipError_t e = launch_level_scale(lsc, stream);
+                prof.end(stream);
+                HIP_OK(e);
+                lsc.max_range = 0;
+            }
             if (rs) {
                 // the output samples this window made final, one launch for every utterance, then the columns they span
                 g0 = out_stride, g1 = 0;
@@ -803,6 +962,16 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             snapshot("waveform", w.wv, 1, w.smax[n_up], B, c.slen[n_up]);
         }
     }
+    if (c.lev) {
+        if (run_level(c, lvl_dst, lvl_stride)) return -1;
+        if (o.collect_taps) {
+            TensorRef t;
+            t.p = la ? lvl_dst : wave_dst;
+            t.bs = la ? lvl_stride : wave_stride;
+            t.cs = (int)t.bs;
+            snapshot("waveform_level", t, 1, smax[n_up], B, c.slen[n_up]);
+        }
+    }
     if (rs && !o.on_chunk) {
         // nobody waits for parts of it: one launch over every utterance, behind the last window
         rsc.max_range = c.out_max;
@@ -835,6 +1004,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             pend->lengths[b] = pcm_len[b];
             pend->frames[b] = frames[b];
         }
+        pend->lv_rows = c.lev ? B : 0;
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -863,10 +1033,16 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             prof.fence();
         }
     }
+    last_lv_ = c.lev ? lv_host_[a1_slot_ & 1].p : nullptr;
+    last_lv_rows_ = c.lev ? B : 0;
     async_tail_ = want_async;
     if (!want_async) {
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
+        if (c.lev) {  // (the rows have landed: keep them apart from the pinned copy, which a later submit into this slot overwrites)
+            last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * B);
+            last_lv_ = last_lv_store_.data();
+        }
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
         if (prof.on && prof.recs.size() > 50000) prof.collect();

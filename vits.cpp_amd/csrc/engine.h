@@ -282,6 +282,18 @@ class Engine {
     int set_rates(int in_rate, int out_rate, std::string& err);
     int input_rate() const { return input_rate_; }
     int output_rate() const { return output_rate_; }
+    // a stated level (include/vits.h vits_model_set_level; loudness.hip): what every PCM the handle delivers is measured and multiplied by. 0, or -1 + a
+    // message with the handle unchanged (an unknown kind, a value outside the kind's range). Nothing touches the device here: the row buffer is
+    // allocated by the first call that levels.
+    int set_level(int kind, float value_db, float ceiling_db, std::string& err);
+    int level_kind() const { return level_kind_; }
+    float level_value_db() const { return level_value_; }
+    float level_ceiling_db() const { return level_ceiling_; }
+    // the rows [B][4] of the most recently completed call (empty: it ran without a level). After an async call they are valid after sync().
+    const float* last_levels(int& rows) const {
+        rows = last_lv_rows_;
+        return last_lv_;
+    }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -398,6 +410,7 @@ class Engine {
         PinnedBuf<int> frames_pinned;
         PinnedBuf<int> win_pinned;    // vocoder-window length table of a windowed batch (host side of its H2D copy)
         PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
+        int lv_rows = 0;              // levelling: rows of lv_host_[slot] this batch fills (0: no level was set)
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -464,6 +477,20 @@ class Engine {
     int input_rate_ = 0, output_rate_ = 0;
     std::map<std::pair<int, int>, RateTable> rate_tabs_;  // keyed by (fi, fo); device tables are owned_ and counted in weight_bytes
     const RateTable* rate_table(int fi, int fo, std::string& err);  // null + message: the pair is refused, or the upload failed
+    // levelling: the handle's setting, the plan at the model's rate, the device rows [lv_cap_][4] of the call being queued (stream-ordered: one buffer
+    // serves both pipeline slots; owned_ and counted in weight_bytes) and their pinned host copies, one per pipeline slot
+    int level_kind_ = VITS_LEVEL_NONE;
+    float level_value_ = 0.f, level_ceiling_ = 0.f;
+    LoudnessPlan level_plan_;
+    float* lv_rows_ = nullptr;
+    int lv_cap_ = 0;
+    PinnedBuf<float> lv_host_[2];
+    const float* last_lv_ = nullptr;
+    int last_lv_rows_ = 0;
+    std::vector<float> last_lv_store_;  // the rows of a waited-for batch (its slot's pinned copy is reused by the next submit)
+    int check_level(const vits_process_opts& o, std::string& err) const;  // the refusal of on_chunk with a kind that needs the whole utterance
+    // measures c.s2.wave and multiplies it into dst (engine.cpp); queued behind the last vocoder window
+    int run_level(Call& c, float* dst, int64_t dst_stride);
     // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
     hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 

@@ -264,6 +264,8 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
                                     (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
             if (check_speaker(s, who, err)) return -1;
         }
+    if (check_level(o, err)) return -1;
+    last_lv_rows_ = 0;
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
     std::vector<int64_t> n_model;

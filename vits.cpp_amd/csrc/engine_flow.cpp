@@ -69,6 +69,9 @@ int Engine::layout_stage_two(Call& c) {
         s2.wave = a.alloc<float>((size_t)B * S_stride);
         s2.wave_out = c.rate_out && !o.out_device ? a.alloc<float>((size_t)B * c.out_ws) : nullptr;
         s2.out_ranges = c.rate_out && o.on_chunk ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
+        s2.wave_lvl = c.lev_apply && (c.rate_out || !o.out_device) ? a.alloc<float>((size_t)B * S_stride) : nullptr;
+        s2.lvl_scratch = c.lev ? a.alloc<char>(level_scratch_bytes(B, smax[n_up], level_plan_.S)) : nullptr;
+        s2.lvl_ranges = c.lev_apply && o.on_chunk ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

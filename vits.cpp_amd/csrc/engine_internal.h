@@ -205,6 +205,9 @@ struct Call {
         int* win_lens;  // [window][n_up + 2][B]: stage lengths of each utterance inside the window, then its emit end
         float* wave_out;    // output rate set, no out_device: the delivered PCM [B][out_ws]
         int* out_ranges;    // output rate set, streaming: [window][2][B]: the output samples [j0, j1) of each utterance that window w finalises
+        float* wave_lvl;    // a level that multiplies (VITS_LEVEL_GAIN ..), unless it goes straight to out_device: the levelled waveform [B][S_stride]
+        void* lvl_scratch;  // a level set: level_scratch_bytes of loudness.hip
+        int* lvl_ranges;    // VITS_LEVEL_GAIN, streaming: [window][2][B]: the model-rate samples [j0, j1) of each utterance that window w finalises
     } s2{};
     int ls = 0, lws = 0, S_stride = 0;
     size_t big = 0;        // floats of the largest vocoder activation (of one window)
@@ -217,6 +220,9 @@ struct Call {
     const RateTable* rate_out = nullptr;
     std::vector<int> out_len;
     int out_max = 0, out_ws = 0;
+    // a level set (Engine::level_kind): the kind of this call, and whether it multiplies (every kind but VITS_LEVEL_MEASURE)
+    int lev = 0;
+    bool lev_apply = false;
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
 };

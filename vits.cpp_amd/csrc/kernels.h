@@ -659,6 +659,60 @@ struct ResampleCall {
 };
 hipError_t launch_resample(const ResampleCall& c, hipStream_t s);
 
+// ---- levelling: BS.1770 loudness, sample peak and gain (loudness.hip; the definition: include/vits.h vits_model_set_level, DESIGN.md §8 "A stated level") ----
+// The K-weighting cascade in transposed direct form II is the 4-state linear system v' = A v + B x, v = (s1, s2, t1, t2):
+//   y1 = b0 x + s1;  s1' = b1 x - a1 y1 + s2;  s2' = b2 x - a2 y1;     y2 = d0 y1 + t1;  t1' = d1 y1 - e1 y2 + t2;  t2' = d2 y1 - e2 y2
+// An utterance is cut into sub-segments of kLevelQ samples anchored at its sample 0 and into groups of kLevelGroup sub-segments: the cut, and so every bit
+// of the result, depends on the utterance's own samples and length alone. Filter, sums and gates are double; the delivered sample is one fp32 multiply.
+constexpr int kLevelQ = 64;      // samples per sub-segment (<= the shortest 100 ms segment, 400 at 4 kHz: a sub-segment touches at most two segments)
+constexpr int kLevelGroup = 16;  // sub-segments per group of the state scan (level_scan_kernel)
+struct LevelCoef {
+    double c[10];   // b0 b1 b2 a1 a2 of the shelf, then of the high-pass
+    double AQ[16];  // A^kLevelQ, row-major: the state after one sub-segment of zeros
+    double AG[16];  // A^(kLevelQ kLevelGroup)
+};
+struct LoudnessPlan {
+    int rate = 0, S = 0;  // S: samples per 100 ms segment, (rate + 5) / 10
+    LevelCoef coef;
+};
+// host only (loudness_host.cpp). false + a message: a rate outside [4000, 192000]
+bool loudness_plan(int rate, LoudnessPlan& p, std::string& err);
+// the values a kind accepts (include/vits.h vits_model_set_level): false + a message naming the value and its range. kind: VITS_LEVEL_*
+bool level_values_ok(int kind, float value_db, float ceiling_db, std::string& err);
+// the definition in double, sequentially; lufs = -inf and blocks = 0 when unmeasurable
+void loudness_host(const float* pcm, size_t n, const LoudnessPlan& p, double* lufs, double* peak, int* blocks);
+// bytes of device scratch a measurement of `batch` rows of at most max_len samples needs (sub-segment states, partial sums, peaks, segment means)
+size_t level_scratch_bytes(int batch, int64_t max_len, int S);
+struct LevelCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;  // device [batch]: valid samples of each row; nothing behind them is read
+    int batch = 0;
+    int64_t max_len = 0;  // the longest row (host side: sizes the grid and the scratch)
+    LoudnessPlan plan;
+    void* scratch = nullptr;  // device, level_scratch_bytes(batch, max_len, plan.S), 8-byte aligned (it holds doubles)
+    int kind = 0;             // VITS_LEVEL_*
+    float value_db = 0.f, ceiling_db = 0.f;
+    float gain = 1.f;         // VITS_LEVEL_GAIN: (float)10^(value_db / 20), rounded on the host (the streaming windows multiply by the same float)
+    float* levels = nullptr;  // device [batch][4]: L (LUFS; -inf: unmeasurable), P, g, blocks that passed both gates
+};
+// level_pass_kernel (states), level_scan_kernel, level_pass_kernel (sums), level_finish_kernel
+hipError_t launch_level_measure(const LevelCall& c, hipStream_t s);
+struct LevelScale {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    float* y = nullptr;  // device [batch][y_stride]; may be x
+    int64_t y_stride = 0;
+    const int* lens = nullptr;                // device [batch]
+    const int *j0 = nullptr, *j1 = nullptr;  // device [batch], optional: the range [j0, j1) of each row (clamped to its length); null = the whole row
+    const float* levels = nullptr;            // device [batch][4]: row b is multiplied by levels[4 b + 2]; null = by `gain`
+    float gain = 1.f;
+    int batch = 0;
+    int64_t max_range = 0;  // the longest range of the call (host side: sizes the grid)
+};
+// y = x * g, one fp32 multiply per sample; samples outside a row's range are left as they are
+hipError_t launch_level_scale(const LevelScale& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
