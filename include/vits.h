@@ -617,6 +617,52 @@ typedef struct vits_resblock_plan {
 } vits_resblock_plan;
 VITS_API int vits_op_resblock_plan(const vits_resblock_desc* d, vits_resblock_plan* plan);
 
+/* One residual-coupling layer of the flow (vits.cpp:500-517, 452-498) on caller tensors, through the kernel the caller names. With H = hidden, per utterance
+ * (the sequence is zero outside [0, lens[b])):
+ *   h = W_pre x0 + b_pre;  out = 0
+ *   l < layers:  g = Conv_k(h, dilation rate^l) + b_in[row_b][l];  a = tanh(g[0:H]) * sigmoid(g[H:2H]);  rs = W_rs[l] a + b_rs[l]
+ *                l + 1 < layers: h += rs[0:H], out += rs[H:2H];  the last layer: out += rs
+ *   x1' = x1 + (W_post out + b_post);  x0 unchanged
+ * The post conv is passed as it is launched: the reverse direction (synthesis) passes the negated weights and bias, as the engine's load does, the forward
+ * direction (voice conversion) the plain ones. flipped: 0 = x0 is channels [0, half) of z and x1 channels [half, 2 half); 1 = the other way round (the engine's
+ * two placements). z: host [batch][2 half][t_stride] fp32, in and out. Weights in torch layout: w_pre [H][half][1]; w_in [layers][2H][H][k]; w_rs: layers - 1
+ * blocks [2H][H][1], then one [H][H][1], concatenated (b_rs the same: layers - 1 times 2H values, then H); w_post [half][H][1]. b_in [n_bias_rows][layers][2H]:
+ * the effective-bias table of a multi-speaker model (PackedConv::bias_rs); bias_rows [batch] (optional, NULL = row 0) names each utterance's row. lens optional,
+ * 0 <= lens[b] <= t <= t_stride. Arithmetic: vits_op_set_arith, VITS_ARITH_F32 / F16 / BF16 (the split arithmetic is refused).
+ * variant: 0 the engine's choice for this arithmetic and grid; 1 un-fused: the 1x1 pre conv, per layer the gated conv and the 1x1 res/skip conv, the post conv
+ * with residual x1, as Engine::run_coupling / run_wavenet build them; 2 the fused WaveNet layers between the un-fused pre and post convs (fp32:
+ * wavenet32_kernel, whatever the grid; 16-bit: wavenet16_kernel with ncw = 1 or 2 column tiles per wave, 0 = the planner's); 3 flow_couple16_kernel, 16-bit
+ * modes only, (ncw, nct) = (1, 1), (1, 2) or (2, 2), (0, 0) = the planner's. Variants 1-3 never fall back to another variant: where no such instantiation exists
+ * (variant 2: hidden != 192, k != 5, rate != 1; variant 3 also half != 96, layers != 4, fp32; an (ncw, nct) that does not exist) they return -1 with the cause in
+ * vits_last_error. Every refusal is made before the first device call.
+ * Staging is the engine's: rows of pitch t rounded up to 32; h lives in rows [0, H) and out in rows [H, 2H) of one [2H] buffer, and in variant 2 h alternates
+ * between that buffer and the gate buffer; 16-bit operands through the existing packers and the converter kernel. Every staged input and every intermediate
+ * buffer holds NaNs (0xFF bytes) behind lens[b] before the valid part goes in: a read past an utterance shows in the result. Columns [0, t) of every row of z
+ * are written back as the device holds them: behind lens[b] that is the staged NaN (all bits set) unless a kernel wrote there.
+ * All variants give the same bits; variant 1 gives the bits of the composition of vits_op_conv1d calls in the same arithmetic. */
+typedef struct vits_flow_coupling_desc {
+    int32_t batch, hidden, half, t, t_stride;
+    int32_t k, layers, rate;
+    int32_t flipped;
+    int32_t n_bias_rows;
+    int32_t variant, ncw, nct;
+} vits_flow_coupling_desc;
+VITS_API int vits_op_flow_coupling(const vits_flow_coupling_desc* d, float* z, const float* w_pre, const float* b_pre, const float* w_in, const float* b_in,
+                                   const float* w_rs, const float* b_rs, const float* w_post, const float* b_post, const int32_t* bias_rows, const int32_t* lens);
+/* What vits_op_flow_coupling would launch for d in the arithmetic of vits_op_set_arith, or -1 and the cause of its refusal. Host arithmetic only: no device
+ * call. kernel: the instantiation as the launch-plan tables print it (variant 1: the launcher, geometry fields 0); bo: output frames per block (64 / 48 / 16);
+ * halo: input frames a block reads beyond its outputs, per side (2 for a WaveNet layer, 8 for the coupling kernel); launches: kernel launches for the layer
+ * (the converter launches of the 16-bit un-fused convs not counted). */
+typedef struct vits_flow_coupling_plan {
+    char kernel[96];
+    int32_t variant; /* the variant that runs (1-3; what 0 resolved to) */
+    int32_t bo, halo, ncw, nct;
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t lds;
+    int32_t launches;
+} vits_flow_coupling_plan;
+VITS_API int vits_op_flow_coupling_plan(const vits_flow_coupling_desc* d, vits_flow_coupling_plan* plan);
+
 /* conv_transpose_1d_with_bias (vits.cpp:178-193). w is [Cin][Cout][K] (torch layout), K == 2*stride.
  * crop = (K-stride)/2 in HF mode (HF modeling_vits.py:483-490), 0 in reference mode (vits.cpp:187, Q1).
  * Output length = stride*T + K - stride - 2*crop. pre-activation leaky_relu(slope) is fused (vits.cpp:613). */

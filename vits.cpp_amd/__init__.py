@@ -25,6 +25,7 @@ SYNTH_DETERMINISTIC = 0x800  # OR-ed in: the deterministic duration predictor in
 DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
 DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
 RB_VARIANT_PLAN, RB_VARIANT_UNFUSED, RB_VARIANT_PAIRS, RB_VARIANT_BLOCK, RB_VARIANT_SEGMENTS = 0, 1, 2, 3, 4  # op_resblock
+FLOW_VARIANT_PLAN, FLOW_VARIANT_UNFUSED, FLOW_VARIANT_WAVENET, FLOW_VARIANT_COUPLING = 0, 1, 2, 3  # op_flow_coupling
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 # vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
@@ -52,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
+    "vits_op_flow_coupling", "vits_op_flow_coupling_plan",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -109,6 +111,17 @@ class ResblockPlan(C.Structure):
     _fields_ = [("kernel", C.c_char * 96), ("variant", C.c_int32), ("bo", C.c_int32), ("advance", C.c_int32), ("halo", C.c_int32),
                 ("segment", C.c_int32), ("tiles", C.c_int32), ("nr", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
                 ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64), ("launches", C.c_int32)]
+
+
+class FlowCouplingDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("hidden", C.c_int32), ("half", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32),
+                ("layers", C.c_int32), ("rate", C.c_int32), ("flipped", C.c_int32), ("n_bias_rows", C.c_int32), ("variant", C.c_int32),
+                ("ncw", C.c_int32), ("nct", C.c_int32)]
+
+
+class FlowCouplingPlan(C.Structure):
+    _fields_ = [("kernel", C.c_char * 96), ("variant", C.c_int32), ("bo", C.c_int32), ("halo", C.c_int32), ("ncw", C.c_int32), ("nct", C.c_int32),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64), ("launches", C.c_int32)]
 
 
 class DurationPredictorDesc(C.Structure):
@@ -287,6 +300,10 @@ def lib():
     L.vits_op_resblock.argtypes = [C.POINTER(ResblockDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_resblock_plan.restype = i32
     L.vits_op_resblock_plan.argtypes = [C.POINTER(ResblockDesc), C.POINTER(ResblockPlan)]
+    L.vits_op_flow_coupling.restype = i32
+    L.vits_op_flow_coupling.argtypes = [C.POINTER(FlowCouplingDesc)] + [vp] * 11
+    L.vits_op_flow_coupling_plan.restype = i32
+    L.vits_op_flow_coupling_plan.argtypes = [C.POINTER(FlowCouplingDesc), C.POINTER(FlowCouplingPlan)]
     L.vits_op_conv_transpose1d.restype = i32
     L.vits_op_conv_transpose1d.argtypes = [C.POINTER(ConvT1dDesc), vp, vp, vp, vp, vp]
     L.vits_op_rel_attention.restype = i32
@@ -1040,6 +1057,48 @@ def op_resblock(x, w1, b1, w2, b2, dils, slope, variant=RB_VARIANT_PLAN, tiles=0
     if lib().vits_op_resblock(C.byref(d), _ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(accum), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
+
+
+def op_flow_coupling_plan(t, batch=1, hidden=192, half=96, k=5, layers=4, rate=1, variant=FLOW_VARIANT_PLAN, ncw=0, nct=0):
+    """What op_flow_coupling would launch in the arithmetic of op_set_arith (vits_op_flow_coupling_plan; host arithmetic, no GPU needed): a dict with kernel,
+    variant (the one that runs), bo, halo, ncw, nct, grid, block, lds, launches — or a VitsError naming the cause of the refusal."""
+    d = FlowCouplingDesc(batch, hidden, half, t, t, k, layers, rate, 0, 1, variant, ncw, nct)
+    p = FlowCouplingPlan()
+    if lib().vits_op_flow_coupling_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "bo", "halo", "ncw", "nct", "block", "lds", "launches")}
+    out["kernel"] = p.kernel.decode()
+    out["grid"] = (p.grid_x, p.grid_y, p.grid_z)
+    return out
+
+
+def op_flow_coupling(z, w_pre, b_pre, w_in, b_in, w_rs, b_rs, w_post, b_post, flipped=0, rate=1, variant=FLOW_VARIANT_PLAN, ncw=0, nct=0, bias_rows=None,
+                     lens=None, t=None):
+    """One residual-coupling layer of the flow through the kernel `variant` names (vits_op_flow_coupling): z [B, 2 half, t_stride] (flipped 0: x0 = the first
+    half of the channels, x1 the second; 1: the other way round); w_pre [H, half, 1]; w_in [layers, 2H, H, k]; w_rs / b_rs: a list of the layers' arrays
+    ([2H, H, 1] / [2H], the last [H, H, 1] / [H]) or their concatenation; w_post [half, H, 1] as launched (reverse direction: negated, with b_post);
+    b_in [rows, layers, 2H] (or [layers, 2H]); bias_rows [B] or None (row 0); t = the longest utterance (default: t_stride). FLOW_VARIANT_UNFUSED | _WAVENET |
+    _COUPLING run that kernel or raise a VitsError naming the cause: never another one. Returns the new z: x1 updated on the valid columns, the staged NaN
+    (all bits set) behind lens[b] up to t, the input's values from t on."""
+    cat = lambda a: _f32(np.concatenate([np.asarray(v, np.float32).ravel() for v in a]) if isinstance(a, (list, tuple)) else a)
+    z, w_pre, b_pre, w_in, b_in, w_post, b_post = _f32(z), _f32(w_pre), _f32(b_pre), _f32(w_in), _f32(b_in), _f32(w_post), _f32(b_post)
+    w_rs, b_rs = cat(w_rs), cat(b_rs)
+    B, F, ts = z.shape
+    half = F // 2
+    layers, H2, H, k = w_in.shape
+    if b_in.ndim == 2:
+        b_in = b_in[None]
+    assert F == 2 * half and H2 == 2 * H and w_pre.shape == (H, half, 1) and w_post.shape == (half, H, 1) and b_pre.shape == (H,) and b_post.shape == (half,)
+    assert b_in.shape[1:] == (layers, 2 * H) and w_rs.size == (2 * layers - 1) * H * H and b_rs.size == (2 * layers - 1) * H
+    d = FlowCouplingDesc(B, H, half, ts if t is None else t, ts, k, layers, rate, int(flipped), b_in.shape[0], variant, ncw, nct)
+    out = z.copy()
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    bias_rows = None if bias_rows is None else np.ascontiguousarray(bias_rows, dtype=np.int32)
+    assert (lens is None or lens.shape == (B,)) and (bias_rows is None or bias_rows.shape == (B,))
+    if lib().vits_op_flow_coupling(C.byref(d), _ptr(out), _ptr(w_pre), _ptr(b_pre), _ptr(w_in), _ptr(b_in), _ptr(w_rs), _ptr(b_rs), _ptr(w_post), _ptr(b_post),
+                                   _ptr(bias_rows), _ptr(lens)) != 0:
+        raise VitsError(last_error())
+    return out
 
 
 def op_duration_predictor(x, w1, b1, g1, be1, w2, b2, g2, be2, wp, bp, spk_rows=None, lens=None, eps=1e-5, variant=DP_VARIANT_PLAN, t=None):

@@ -1450,6 +1450,241 @@ VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const
     VITS_CATCH(-1)
 }
 
+// ---- vits_op_flow_coupling: which kernel a descriptor names (host arithmetic only: launch_plan.h), then the engine's call structs on staged tensors ---------
+namespace {
+struct FlowOpPlan {
+    int variant = 0;
+    std::string kernel;
+    int bo = 0, halo = 0, ncw = 0, nct = 0, launches = 0;
+    vits::LaunchGrid g;
+};
+bool fc_fail(std::string& why, const std::string& m) {
+    why = "vits_op_flow_coupling: " + m;
+    return false;
+}
+bool flow_resolve(const vits_flow_coupling_desc* d, int arith, FlowOpPlan& r, std::string& why) {
+    using namespace vits;
+    if (arith != VITS_ARITH_F32 && arith != VITS_ARITH_F16 && arith != VITS_ARITH_BF16)
+        return fc_fail(why, "VITS_ARITH_F32, VITS_ARITH_F16 or VITS_ARITH_BF16 only (the split arithmetic has no flow kernels)");
+    const int H = d->hidden, HF = d->half, k = d->k, B = d->batch, T = d->t, NL = d->layers;
+    if (B < 1 || T < 1 || d->t_stride < T) return fc_fail(why, "batch >= 1 and 1 <= t <= t_stride are required");
+    if (H < 32 || (H & 31)) return fc_fail(why, "hidden = " + std::to_string(H) + ": a multiple of 32 is required");
+    if (HF < 32 || (HF & 31)) return fc_fail(why, "half = " + std::to_string(HF) + ": a multiple of 32 is required");
+    if (k < 1 || !(k & 1)) return fc_fail(why, "k = " + std::to_string(k) + ": an odd tap count is required");
+    if (NL < 1 || NL > 16) return fc_fail(why, "layers = " + std::to_string(NL) + ": 1 to 16 WaveNet layers");
+    if (d->rate < 1 || (d->rate > 1 && NL > 8)) return fc_fail(why, "rate = " + std::to_string(d->rate) + ": >= 1 is required (and at most 8 layers of a dilated stack)");
+    if (d->flipped != 0 && d->flipped != 1) return fc_fail(why, "flipped = " + std::to_string(d->flipped) + ": 0 (x0 first) or 1 (x1 first)");
+    if (d->n_bias_rows < 1) return fc_fail(why, "n_bias_rows = " + std::to_string(d->n_bias_rows) + ": the b_in table has at least one row");
+    if (d->variant < 0 || d->variant > 3) return fc_fail(why, "variant " + std::to_string(d->variant) + ": 0 (the engine's choice), 1 (un-fused), 2 (fused WaveNet layers), 3 (the coupling kernel)");
+    if (d->ncw < 0 || d->nct < 0) return fc_fail(why, "(ncw, nct) = (" + std::to_string(d->ncw) + ", " + std::to_string(d->nct) + "): negative");
+    const bool f32 = arith == VITS_ARITH_F32, bf = arith == VITS_ARITH_BF16;
+    const std::string tile = "(ncw, nct) = (" + std::to_string(d->ncw) + ", " + std::to_string(d->nct) + ")";
+    char name[96];
+    int v = d->variant;
+    if (v == 0) {  // engine_flow.cpp's order: the coupling kernel (16-bit modes), the fused WaveNet layers on large grids, nine launches
+        if (d->ncw || d->nct) return fc_fail(why, tile + ": variant 0 takes the planner's tile");
+        const bool wn = f32 ? plan_wavenet32(H, k, d->rate, B, T).ok : plan_wavenet16(H, k, d->rate, B, T).ok;
+        v = !f32 && plan_flow_couple16(H, HF, k, d->rate, NL, B, T).ok ? 3 : wn && (int64_t)blocks_for(T, 32) * B >= 384 ? 2 : 1;
+    }
+    r.variant = v;
+    if (v == 1) {
+        if (d->ncw || d->nct) return fc_fail(why, tile + ": variant 1 has no tile to choose");
+        r.kernel = f32 ? "launch_conv" : "launch_conv16";
+        r.launches = 2 * NL + 2;
+        return true;
+    }
+    if (v == 2) {
+        const char* fam = f32 ? "wavenet32_kernel" : "wavenet16_kernel";
+        if (H != 192) return fc_fail(why, std::string("variant 2: no ") + fam + " for hidden = " + std::to_string(H) + " (hidden = 192, k = 5, rate = 1)");
+        if (k != 5) return fc_fail(why, std::string("variant 2: no ") + fam + " for k = " + std::to_string(k) + " (hidden = 192, k = 5, rate = 1)");
+        if (d->rate != 1) return fc_fail(why, std::string("variant 2: no ") + fam + " for rate = " + std::to_string(d->rate) + " (hidden = 192, k = 5, rate = 1)");
+        if (d->nct) return fc_fail(why, tile + ": variant 2 has no nct (a block is two column tiles)");
+        if (f32 && d->ncw) return fc_fail(why, tile + ": wavenet32_kernel has one form (ncw = 0)");
+        const WaveNetPlan pl = f32 ? plan_wavenet32(H, k, 1, B, T) : plan_wavenet16(H, k, 1, B, T, d->ncw);
+        if (!pl.ok) return fc_fail(why, tile + ": no such wavenet16_kernel (ncw = 1 or 2)");
+        r.g = pl, r.ncw = pl.ncw, r.bo = kWaveNetBM, r.halo = (k - 1) / 2, r.launches = NL + 2;
+        if (f32) std::snprintf(name, sizeof(name), "wavenet32_kernel<%d, %d>", H, k);
+        else std::snprintf(name, sizeof(name), "wavenet16_kernel<%d, %d, %s, %d>", H, k, bf ? "true" : "false", pl.ncw);
+        r.kernel = name;
+        return true;
+    }
+    if (f32) return fc_fail(why, "variant 3: flow_couple16_kernel exists in the 16-bit modes only");
+    const char* only = " (hidden = 192, half = 96, k = 5, rate = 1, layers = 4)";
+    if (H != 192) return fc_fail(why, "variant 3: no flow_couple16_kernel for hidden = " + std::to_string(H) + only);
+    if (HF != 96) return fc_fail(why, "variant 3: no flow_couple16_kernel for half = " + std::to_string(HF) + only);
+    if (k != 5) return fc_fail(why, "variant 3: no flow_couple16_kernel for k = " + std::to_string(k) + only);
+    if (d->rate != 1) return fc_fail(why, "variant 3: no flow_couple16_kernel for rate = " + std::to_string(d->rate) + only);
+    if (NL != 4) return fc_fail(why, "variant 3: no flow_couple16_kernel for layers = " + std::to_string(NL) + only);
+    const FlowCouple16Plan pl = plan_flow_couple16(H, HF, k, 1, NL, B, T, d->ncw, d->nct);
+    if (!pl.ok) return fc_fail(why, tile + ": no such flow_couple16_kernel ((1, 1), (1, 2) or (2, 2))");
+    const FlowCouple16Geom ge = flow_couple16_geom(pl.ncw, pl.nct);
+    r.g = pl, r.ncw = pl.ncw, r.nct = pl.nct, r.bo = ge.bo, r.halo = ge.halo, r.launches = 1;
+    std::snprintf(name, sizeof(name), "flow_couple16_kernel<%s, %d, %d>", bf ? "true" : "false", pl.ncw, pl.nct);
+    r.kernel = name;
+    return true;
+}
+}  // namespace
+
+VITS_API int vits_op_flow_coupling_plan(const vits_flow_coupling_desc* d, vits_flow_coupling_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_flow_coupling_plan: null argument");
+    FlowOpPlan r;
+    std::string why;
+    if (!flow_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", r.kernel.c_str());
+    out->variant = r.variant, out->bo = r.bo, out->halo = r.halo, out->ncw = r.ncw, out->nct = r.nct;
+    out->grid_x = r.g.gx, out->grid_y = r.g.gy, out->grid_z = r.g.ok ? r.g.gz : 0, out->block = r.g.block, out->lds = (int64_t)r.g.lds, out->launches = r.launches;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_flow_coupling(const vits_flow_coupling_desc* d, float* z, const float* w_pre, const float* b_pre, const float* w_in, const float* b_in,
+                                   const float* w_rs, const float* b_rs, const float* w_post, const float* b_post, const int32_t* bias_rows, const int32_t* lens) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !z || !w_pre || !b_pre || !w_in || !b_in || !w_rs || !b_rs || !w_post || !b_post)
+        return fail("vits_op_flow_coupling: null argument (z and every weight and bias are required)");
+    const int arith = g_op_arith;
+    FlowOpPlan r;
+    std::string why;
+    if (!flow_resolve(d, arith, r, why)) return fail(why.c_str());
+    const int B = d->batch, H = d->hidden, HF = d->half, T = d->t, k = d->k, NL = d->layers, ts = round_up(T, 32);
+    for (int b = 0; b < B; ++b) {
+        if (lens && (lens[b] < 0 || lens[b] > T)) return fail("vits_op_flow_coupling: 0 <= lens[b] <= t is required");
+        if (bias_rows && (bias_rows[b] < 0 || bias_rows[b] >= d->n_bias_rows)) return fail("vits_op_flow_coupling: 0 <= bias_rows[b] < n_bias_rows is required");
+    }
+    const bool f32 = arith == VITS_ARITH_F32;
+    // the convs on the device: pre, in[l], rs[l], post
+    struct Conv {
+        PackedConv pc;
+        DevBytes w, wl, w16, b;
+    };
+    std::vector<Conv> cv(2 * NL + 2);
+    DevBytes dtab;  // the b_in table [n_bias_rows][layers][2H]: in[l] points at its segment of row 0, one row stride for all (engine_load.cpp load_speakers)
+    if (!dtab.put(b_in, (size_t)d->n_bias_rows * NL * 2 * H * 4)) return fail("device allocation failed");
+    auto upload = [&](Conv& c, const float* w, const float* bias, int cout, int cin, int kt, int epi) {
+        PackedConv& pc = c.pc;
+        pc.cin = cin, pc.cout = cout, pc.kt = kt, pc.epi = epi;
+        const std::vector<float> packed = pack_conv_weights(w, cout, cin, kt, epi, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+        if (bias) {
+            if (!c.b.put(bias, (size_t)cout * 4)) return false;
+            pc.bias = c.b.f();
+        }
+        if (f32) {
+            if (!c.w.put(packed.data(), packed.size() * 4)) return false;
+            pc.wp = c.w.f(), pc.bytes = (int64_t)packed.size() * 4;
+            if (conv_lat16_candidate(epi, kt, cin)) {
+                const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, kt);
+                if (!c.wl.put(pl.data(), pl.size() * 4)) return false;
+                pc.wp_l16 = c.wl.f();
+            }
+        } else {
+            const std::vector<uint16_t> p16 = pack_conv_weights16(w, cout, cin, kt, epi, 0, arith);
+            if (!c.w16.put(p16.data(), p16.size() * 2)) return false;
+            pc.wp16 = c.w16.h(), pc.bytes16 = (int64_t)p16.size() * 2;
+        }
+        return true;
+    };
+    Conv &pre = cv[0], &post = cv[2 * NL + 1];
+    if (!upload(pre, w_pre, b_pre, H, HF, 1, EPI_STD) || !upload(post, w_post, b_post, HF, H, 1, EPI_STD)) return fail("device allocation failed");
+    std::vector<PackedConv> in(NL), rs(NL);
+    for (int l = 0; l < NL; ++l) {
+        const int rows = l + 1 < NL ? 2 * H : H;
+        if (!upload(cv[1 + 2 * l], w_in + (size_t)l * 2 * H * H * k, nullptr, 2 * H, H, k, EPI_GATE) ||
+            !upload(cv[2 + 2 * l], w_rs + (size_t)l * 2 * H * H, b_rs + (size_t)l * 2 * H, rows, H, 1, EPI_STD))
+            return fail("device allocation failed");
+        in[l] = cv[1 + 2 * l].pc, rs[l] = cv[2 + 2 * l].pc;
+        in[l].bias = dtab.f() + (size_t)l * 2 * H;
+        in[l].bias_rs = bias_rows ? (int64_t)NL * 2 * H : 0;
+    }
+    // host staging: NaN everywhere, then the valid columns
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    auto len_of = [&](int b) { return lens ? lens[b] : T; };
+    const size_t nz = (size_t)B * 2 * HF * ts, nh = (size_t)B * 2 * H * ts, ng = (size_t)B * H * ts;
+    std::vector<float> hz(nz);
+    std::memset(hz.data(), 0xFF, nz * 4);
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < 2 * HF; ++c)
+            std::memcpy(&hz[((size_t)b * 2 * HF + c) * ts], z + ((size_t)b * 2 * HF + c) * d->t_stride, sizeof(float) * (size_t)len_of(b));
+    DevInts dl, dspk;
+    DevBytes dz, dhout, dgate, dx16;
+    if (!dl.put(lens, B) || !dspk.put(bias_rows, B) || !dz.put(hz.data(), nz * 4)) return fail("device allocation failed");
+    const TensorRef zr = tref(dz.f(), 2 * HF, ts);
+    TensorRef x0 = zr, x1 = zr;
+    (d->flipped ? x0 : x1).p += (size_t)HF * ts;
+    hipError_t e = hipSuccess;
+    if (r.variant == 3) {
+        FlowCouple16Call fc;
+        fc.x0 = x0, fc.x1 = x1, fc.lens = dl.p, fc.spk = dspk.p, fc.batch = B, fc.tmax = T, fc.hidden = H, fc.half = HF;
+        fc.force_ncw = r.ncw, fc.force_nct = r.nct;
+        e = launch_flow_couple16(pre.pc, in.data(), rs.data(), post.pc, fc, arith, nullptr);
+    } else {
+        // hout: h = rows [0, H), the skip sum `outputs` = rows [H, 2H), zero on the valid columns (launch_fill_rows of the engine); gate: the gated conv's
+        // output, and the other h buffer of the fused layers
+        {
+            std::vector<float> hh(nh, qnan);
+            for (int b = 0; b < B; ++b)
+                for (int c = H; c < 2 * H; ++c) std::fill_n(&hh[((size_t)b * 2 * H + c) * ts], len_of(b), 0.f);
+            if (!dhout.put(hh.data(), nh * 4) || !dgate.fill(ng * 4, 0xFF)) return fail("device allocation failed");
+        }
+        const size_t x16_bytes = f32 ? 0 : (size_t)B * (std::max(H, HF) / 8) * round_up(T, 8) * 8 * 2;
+        if (!f32 && !dx16.fill(x16_bytes, 0xFF)) return fail("device allocation failed");
+        // a conv of the fp32-layout orchestration (Engine::conv): the fp32 kernel, or the converter + the 16-bit-operand kernel (Engine::conv16_transparent)
+        auto conv = [&](const PackedConv& w, const ConvCall& c) -> hipError_t {
+            if (f32) return launch_conv(w, c, nullptr);
+            Ref16 x16;
+            x16.p = dx16.h(), x16.ts = round_up(c.t_in, 8), x16.bs = (int64_t)((w.cin + 7) / 8) * x16.ts * 8;
+            if (hipMemsetAsync(dx16.p, 0xFF, x16_bytes, nullptr) != hipSuccess) return hipErrorUnknown;
+            hipError_t e2 = launch_to_group16(c.x, c.len_in, c.batch, w.cin, c.t_in, 1.0f, x16, arith, nullptr);
+            if (e2 != hipSuccess) return e2;
+            Conv16Call q;
+            q.x = x16, q.len_in = c.len_in, q.len_out = c.len_out, q.spk = c.spk, q.batch = c.batch, q.t_in = c.t_in, q.t_out = c.t_out, q.dil = c.dil, q.pad_l = c.pad_l;
+            q.y = c.y, q.res = c.res;
+            return launch_conv16(w, q, arith, nullptr);
+        };
+        auto mk = [&](TensorRef xin, TensorRef yout) {
+            ConvCall c;
+            c.x = xin, c.y = yout, c.len_in = c.len_out = dl.p, c.spk = dspk.p, c.batch = B, c.t_in = c.t_out = T;
+            return c;
+        };
+        const TensorRef hout = tref(dhout.f(), 2 * H, ts), gate = tref(dgate.f(), H, ts);
+        TensorRef outputs = hout;
+        outputs.p += (size_t)H * ts;
+        e = conv(pre.pc, mk(x0, hout));
+        TensorRef hcur = hout;
+        for (int l = 0, dil = 1; l < NL && e == hipSuccess; ++l, dil *= d->rate) {
+            const bool last = l + 1 == NL;
+            if (r.variant == 2) {
+                WaveNet32Call w;
+                w.h = hcur, w.h_out = last ? TensorRef() : (hcur.p == gate.p ? hout : gate), w.outputs = outputs;
+                w.lens = dl.p, w.spk = dspk.p, w.batch = B, w.tmax = T, w.hidden = H, w.dil = dil, w.force_ncw = r.ncw;
+                e = f32 ? launch_wavenet32(in[l], rs[l], w, nullptr) : launch_wavenet16(in[l], rs[l], w, arith, nullptr);
+                if (w.h_out.p) hcur = w.h_out;
+                continue;
+            }
+            ConvCall g = mk(hout, gate);
+            g.dil = dil, g.pad_l = (k * dil - dil) / 2;
+            e = conv(in[l], g);
+            ConvCall q = mk(gate, last ? outputs : hout);
+            q.res = q.y;
+            if (e == hipSuccess) e = conv(rs[l], q);
+        }
+        if (e == hipSuccess) {
+            ConvCall pc = mk(outputs, x1);
+            pc.res = x1;
+            e = conv(post.pc, pc);
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_flow_coupling: ") + r.kernel + ": " + hipGetErrorString(e)).c_str());
+    if (hipMemcpy(hz.data(), dz.p, nz * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < 2 * HF; ++c) std::memcpy(z + ((size_t)b * 2 * HF + c) * d->t_stride, &hz[((size_t)b * 2 * HF + c) * ts], sizeof(float) * (size_t)T);
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y) {
     VITS_TRY
     using namespace vits;

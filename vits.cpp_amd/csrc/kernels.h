@@ -417,6 +417,7 @@ struct WaveNet32Call {
     const int* lens = nullptr;
     const int* spk = nullptr;  // effective-bias table rows of the gated conv's bias (see ConvCall::spk)
     int batch = 1, tmax = 0, hidden = 0, dil = 1;
+    int force_ncw = 0;  // 16-bit kernel: 1 or 2 = that many column tiles per wave whatever VITS_WN16_NCW says (vits_op_flow_coupling); 0: the planner's choice
 };
 bool wavenet32_supported(int hidden, int kt, int dil, const PackedConv& in, const PackedConv& rs);
 hipError_t launch_wavenet32(const PackedConv& in, const PackedConv& rs, const WaveNet32Call& c, hipStream_t s);
@@ -428,6 +429,7 @@ struct FlowCouple16Call {
     const int* lens = nullptr;
     const int* spk = nullptr;  // effective-bias table rows of the in_layers' biases (see ConvCall::spk)
     int batch = 1, tmax = 0, hidden = 0, half = 0;
+    int force_ncw = 0, force_nct = 0;  // both set: that (column tiles per wave, per block) whatever the grid and the knobs (vits_op_flow_coupling); 0, 0: the planner's choice
 };
 bool flow_couple16_supported(int hidden, int half, int kt, int rate, int layers, const PackedConv& pre, const PackedConv* in, const PackedConv* rs, const PackedConv& post);
 hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, const PackedConv* rs, const PackedConv& post, const FlowCouple16Call& c, int arith,

@@ -148,18 +148,26 @@ WaveNetPlan plan_wavenet32(int hidden, int kt, int dil, int batch, int tmax) {
     set_grid(p, blocks_for(tmax, kWaveNetBM), batch, 4 * hidden, wavenet32_lds(hidden, kt));
     return p;
 }
-WaveNetPlan plan_wavenet16(int hidden, int kt, int dil, int batch, int tmax) {
+WaveNetPlan plan_wavenet16(int hidden, int kt, int dil, int batch, int tmax, int force_ncw) {
     WaveNetPlan p;
     if (hidden != 192 || kt != 5 || dil != 1) return p;
-    p.ncw = kernel_knobs().wn16_ncw == 1 ? 1 : 2;  // (2: six waves, both column tiles each — measured 40.6 vs 38.4 us per layer)
+    if (force_ncw && !wavenet16_exists(force_ncw)) return p;  // the caller names the instantiation (vits_op_flow_coupling): no knob
+    p.ncw = force_ncw ? force_ncw : kernel_knobs().wn16_ncw == 1 ? 1 : 2;  // (2: six waves, both column tiles each — measured 40.6 vs 38.4 us per layer)
     set_grid(p, blocks_for(tmax, kWaveNetBM), batch, 4 * hidden / p.ncw, wavenet16_lds(hidden, kt));
     return p;
 }
 
 bool flow_couple16_narrow(int64_t wide_blocks) { return wide_blocks <= kernel_knobs().flow_narrow_max; }
-FlowCouple16Plan plan_flow_couple16(int hidden, int half, int kt, int rate, int layers, int batch, int tmax) {
+FlowCouple16Plan plan_flow_couple16(int hidden, int half, int kt, int rate, int layers, int batch, int tmax, int force_ncw, int force_nct) {
     FlowCouple16Plan p;
     if (hidden != 192 || half != 96 || kt != 5 || rate != 1 || layers != 4) return p;
+    if (force_ncw || force_nct) {  // the caller names the instantiation (vits_op_flow_coupling): no knob, no grid rule
+        if (!flow_couple16_exists(force_ncw, force_nct)) return p;
+        p.ncw = force_ncw, p.nct = force_nct;
+        const FlowCouple16Geom g = flow_couple16_geom(p.ncw, p.nct);
+        set_grid(p, blocks_for(tmax, g.bo), batch, g.block, g.lds);
+        return p;
+    }
     // small grids (batch 1 ... 4 at 225 frames): 16-frame blocks on one 32-column tile (see the kernel); otherwise 48-frame blocks of six waves owning both
     // column tiles of their channel group (VITS_FLOW_NCW=1: twelve waves, one column tile each)
     if (flow_couple16_narrow((int64_t)flow_wide_blocks(tmax) * batch)) p.ncw = 1, p.nct = 1;

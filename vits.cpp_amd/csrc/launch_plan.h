@@ -194,12 +194,14 @@ struct WaveNetPlan : LaunchGrid {
     int ncw = 0;
 };
 WaveNetPlan plan_wavenet32(int hidden, int kt, int dil, int batch, int tmax);
-WaveNetPlan plan_wavenet16(int hidden, int kt, int dil, int batch, int tmax);
+// force_ncw: that many column tiles per wave whatever VITS_WN16_NCW says, or a refusal where no such instantiation exists; 0: the policy
+WaveNetPlan plan_wavenet16(int hidden, int kt, int dil, int batch, int tmax, int force_ncw = 0);
 // one whole coupling layer; `ok` is the shape part of flow_couple16_supported
 struct FlowCouple16Plan : LaunchGrid {
     int ncw = 0, nct = 0;
 };
-FlowCouple16Plan plan_flow_couple16(int hidden, int half, int kt, int rate, int layers, int batch, int tmax);
+// force_ncw / force_nct (either set): that tile whatever the grid, VITS_FLOW_NCW and VITS_FLOW_NARROW_MAX say, or a refusal where no such instantiation exists; 0, 0: the policy
+FlowCouple16Plan plan_flow_couple16(int hidden, int half, int kt, int rate, int layers, int batch, int tmax, int force_ncw = 0, int force_nct = 0);
 bool flow_couple16_narrow(int64_t wide_blocks);  // a launch of this many 48-frame blocks runs on 16-frame blocks instead (VITS_FLOW_NARROW_MAX)
 // relative-position attention: the matrix-core kernel (nw waves, maxs k-steps, short / latency variant) or the VALU kernel (`block` threads, vshift)
 struct AttentionPlan : LaunchGrid {

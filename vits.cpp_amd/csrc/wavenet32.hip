@@ -828,7 +828,8 @@ hipError_t launch_wavenet16(const PackedConv& in, const PackedConv& rs, const Wa
     p.f.outputs = c.outputs.p, p.f.o_bs = c.outputs.bs, p.f.o_cs = c.outputs.cs, p.f.w_in = nullptr, p.f.b_in = in.bias;
     p.f.bias_rows = in.bias_rs ? c.spk : nullptr, p.f.bias_rs = in.bias_rs, p.f.w_rs = nullptr, p.f.b_rs = rs.bias, p.f.rs_rows = rs.cout;
     p.f.lens = c.lens, p.f.tmax = c.tmax, p.w_in16 = in.wp16, p.w_rs16 = rs.wp16;
-    const WaveNetPlan l = plan_wavenet16(c.hidden, in.kt, c.dil, c.batch, c.tmax);
+    const WaveNetPlan l = plan_wavenet16(c.hidden, in.kt, c.dil, c.batch, c.tmax, c.force_ncw);
+    if (!l.ok) return hipErrorInvalidValue;
     const dim3 grid(l.gx, l.gy), block(l.block);
     const bool bf = arith == VITS_ARITH_BF16;
     static_assert(wavenet16_exists(1) && wavenet16_exists(2), "the planner's predicate");
@@ -861,7 +862,7 @@ hipError_t launch_flow_couple16(const PackedConv& pre, const PackedConv* in, con
         p.b_rs[l] = rs[l].bias;
     }
     p.w_post = post.wp16, p.b_post = post.bias, p.lens = c.lens, p.tmax = c.tmax;
-    const FlowCouple16Plan l = plan_flow_couple16(c.hidden, c.half, in[0].kt, 1, 4, c.batch, c.tmax);  // (rate 1, four layers: what the call's arrays hold and the kernel is built for)
+    const FlowCouple16Plan l = plan_flow_couple16(c.hidden, c.half, in[0].kt, 1, 4, c.batch, c.tmax, c.force_ncw, c.force_nct);  // (rate 1, four layers: what the call's arrays hold and the kernel is built for)
     const dim3 grid(l.gx, l.gy), block(l.block);
     const bool bf = arith == VITS_ARITH_BF16;
 #define VITS_FLOW_GO(NCW, NCT)                                                     \
