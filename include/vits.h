@@ -414,7 +414,7 @@ VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t
  *   VITS_LEVEL_GAIN       10^(value_db / 20)
  *   VITS_LEVEL_PEAK       10^(value_db / 20) / P; 1 if P == 0
  *   VITS_LEVEL_LOUDNESS   min(10^((value_db - L) / 20), 10^(ceiling_db / 20) / P); 1 if unmeasurable or P == 0
- * Delivered sample = x * g, one fp32 multiply: no clamp, no limiter beyond the ceiling rule, no dither.
+ * Delivered sample = x * g, one fp32 multiply: no clamp, no limiter beyond the ceiling rule (unless vits_model_set_limiter, below, is on), no dither.
  * vits_model_set_level: 0, or -1 + message with the handle unchanged: an unknown kind, a value that is not finite, value_db outside
  * [-70, 0] (LOUDNESS), [-60, 0] (PEAK) or [-60, 40] (GAIN), ceiling_db outside [-60, 0] (LOUDNESS only; the other kinds ignore it),
  * batches in flight, or a call from inside on_chunk ("model busy").
@@ -441,6 +441,58 @@ VITS_API int64_t vits_model_last_levels(vits_model* model, float* dst, size_t ca
  * on n samples at `rate`: *lufs (-inf: unmeasurable), *peak, *blocks (each optional); 0, or -1 + message (a refused rate, pcm NULL with n > 0). */
 VITS_API int vits_loudness_plan(int32_t rate, double coef[10], int32_t* segment);
 VITS_API int vits_loudness_host(const float* pcm, size_t n, int32_t rate, double* lufs, double* peak, int32_t* blocks);
+
+/* ---- the loudness target under a ceiling: a 4x true-peak meter and a look-ahead limiter, on the device -------------------------------
+ * The ceiling rule of VITS_LEVEL_LOUDNESS cuts the gain of a whole utterance when its peaks are high: the utterance leaves quieter than asked,
+ * by another amount each time. vits_model_set_limiter(model, VITS_LIMIT_TRUE_PEAK) delivers the gain that was asked for and turns down only
+ * the neighbourhood of what would pass the ceiling. It is a stage of the levelling tail (vocoder -> measure -> limiter in place of the plain
+ * multiply -> resampler), defined WITHOUT a recurrence, so batch rows, pipelined and split batches, windows and a device buffer give the same
+ * bits, in every VITS_ARITH_* mode. With VITS_LIMIT_OFF (the default) nothing is queued or allocated and every bit is what it was.
+ *
+ * The definition. Model-rate row x[0, N) at rate fs in [4000, 48000] (4 fs is then a rate the resampler accepts); integer divisions truncate.
+ *   A = (fs + 100) / 200   5 ms of look-ahead and attack          H = (fs + 10) / 20   50 ms of hold (longer than a pitch period: the gain does
+ *                                                                                      not ride the glottal pulses)
+ *   u[0, 4N) = x resampled fs -> 4 fs by the filter of vits_model_set_rates (L = 4, M = 1, K = 71): the same table, the same ascending fmaf
+ *     chain, bit for bit what vits_op_resample(fs, 4 fs) returns for the row. Nothing behind N is read. The project's own filter is the meter:
+ *     this is not the coefficient table of BS.1770 annex 2.
+ *   TP(x) = max(P, max_j |u[j]|), P the sample peak: the true peak, exact in fp32 (a maximum does not round)
+ *   e[n] = max(|x[n]|, |u[j]| for j in [4n - 2, 4n + 2] within [0, 4N)): the detection envelope; every oversampled point belongs to some n
+ *   g0, the gain before limiting:   VITS_LEVEL_GAIN      10^(value_db / 20)
+ *                                   VITS_LEVEL_LOUDNESS  10^((value_db - L) / 20), 1 if unmeasurable: the ceiling no longer reduces it
+ *                                   VITS_LEVEL_PEAK      10^(value_db / 20) / TP, 1 if TP == 0: true-peak normalisation, delivered by the plain
+ *                                                        multiply (no limiter stage: under the stated peak by construction)
+ *   c = 10^(ceiling_db / 20); with the limiter on, vits_model_set_level checks and keeps ceiling_db in [-60, 0] under VITS_LEVEL_GAIN too (set the
+ *     limiter first: with it off a gain's ceiling is ignored and not kept)
+ *   1. r[k] = min(1, c / (g0 e[k])) for k in [0, N), 1 where e[k] == 0 and outside [0, N)
+ *   2. m[j] = min(r[j - H .. j + A]) for j in [-A, N): a sliding minimum, exact
+ *   3. s[n] = mean(m[n - A .. n]), in fp64, rounded once to fp32
+ *   4. y[n] = x[n] * (g0 * s[n]): two fp32 multiplies
+ * Every window m[n - A .. n] contains n, so s[n] <= r[n] and |y[n]| <= c in exact arithmetic. Where nothing passes the ceiling s == 1 exactly
+ * and the row is x * g0, bit for bit what VITS_LEVEL_GAIN delivers without the limiter. The guarantee holds at the model's rate: a resampler
+ * behind the limiter can overshoot slightly, which is not corrected. A, H and the factor 4 are constants of this definition, not knobs. How
+ * often a ceiling binds on real speech, and what the limiter does to it audibly, has not been judged: the project's fixtures are synthetic.
+ *
+ * vits_model_set_limiter: 0, or -1 + message with the handle unchanged: an unknown mode, a model rate above 48000 Hz, batches in flight, a
+ * call from inside on_chunk ("model busy"). Under VITS_LEVEL_NONE and _MEASURE nothing is queued. With the limiter on vits_model_last_levels
+ * reports g = g0, tap "waveform_level" is the limited model-rate row, and voice conversion delivers through it as through levelling.
+ * on_chunk with the limiter on and a kind that multiplies is REFUSED: a sample's gain looks A ahead and H + A back, and the halo of finished
+ * samples per window that streaming needs is not built; the message says so. vocoder_chunk_frames without on_chunk works: the limiter runs
+ * behind the last window, where levelling runs.
+ *
+ * vits_model_last_limits: the rows [B][4] = {TP(x) linear, TP(y) linear (a second meter pass over the delivered model-rate row), min_n s[n],
+ * the share of samples with s[n] < 1} of the most recently completed call; the return conventions of vits_model_last_levels, 0 when that
+ * call ran without the limiter. The device rows are counted in vits_model_weight_bytes once allocated, as is the 4x table. */
+#define VITS_LIMIT_OFF 0
+#define VITS_LIMIT_TRUE_PEAK 1
+VITS_API int vits_model_set_limiter(vits_model* model, int32_t mode);
+VITS_API int vits_model_get_limiter(const vits_model* model, int32_t* mode);
+VITS_API int64_t vits_model_last_limits(vits_model* model, float* dst, size_t cap);
+/* Host only, no device needed. vits_limiter_plan: A, H and the time tile of the device kernels (each optional) at a rate in [4000, 48000]; 0,
+ * or -1 + message. vits_limiter_host: the definition above in double, sequentially (u from vits_resample_taps, nothing rounded to fp32), on n
+ * samples at `rate` with the gain g0 > 0 and the ceiling ceiling_db in [-60, 0]: y[n] (optional) and limits[4] = {TP(x), TP(y), min s, share}
+ * (optional); 0, or -1 + message (a refused rate or value, pcm NULL with n > 0). */
+VITS_API int vits_limiter_plan(int32_t rate, int32_t* A, int32_t* H, int32_t* tile);
+VITS_API int vits_limiter_host(const float* pcm, size_t n, int32_t rate, double g0, double ceiling_db, double* y, double limits[4]);
 
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
@@ -732,6 +784,18 @@ typedef struct vits_level_desc {
     float ceiling_db;
 } vits_level_desc;
 VITS_API int vits_op_level(const vits_level_desc* d, const float* x, const int64_t* lens, float* y, float* levels);
+
+/* The levelling tail with the limiter (see vits_model_set_limiter for the definition) on a ragged batch, staged exactly as the engine stages it
+ * (the device copy of x holds NaNs behind every lens[b]): measure, true-peak meter, g0, limiter (VITS_LEVEL_GAIN, _LOUDNESS) or the plain
+ * multiply (VITS_LEVEL_PEAK), meter of y. y: host [batch][y_stride], required; row b gets its lens[b] samples, everything behind them is left
+ * as it was. levels: out, host [batch][4] with g = g0. limits: out, host [batch][4] = {TP(x), TP(y), min s, share}. Refused (-1 + message):
+ * what vits_op_level refuses, a rate above 48000, VITS_LEVEL_NONE and _MEASURE, an unknown mode or VITS_LIMIT_OFF, a ceiling_db outside
+ * [-60, 0] (VITS_LEVEL_GAIN too), a NULL y. */
+typedef struct vits_limit_desc {
+    vits_level_desc level;
+    int32_t mode; /* VITS_LIMIT_TRUE_PEAK */
+} vits_limit_desc;
+VITS_API int vits_op_limit(const vits_limit_desc* d, const float* x, const int64_t* lens, float* y, float* levels, float* limits);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

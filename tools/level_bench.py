@@ -1,8 +1,9 @@
 """Cost of delivering the PCM at a stated level (vits_model_set_level, loudness.hip) on the FULL synthetic model in fp32, PCM left on the device: the
 benchmark configuration (batch 64 x 128 ids) and batch 1 x 128 ids, without a level and under VITS_LEVEL_LOUDNESS (-23 LUFS, ceiling -1 dB). ms per call
 (wall clock around the call), median of interleaved rounds; a profiled pass gives the levelling kernels' own time per call (level_measure: the four
-measuring launches as one span; level_scale: the multiply) and their share of the call's kernel time. Prints one JSON line.
-usage: python tools/level_bench.py [--rounds 5] [--steps 4] [--ids 128]"""
+measuring launches as one span; level_scale: the multiply) and their share of the call's kernel time. --limit adds the same call with the true-peak
+limiter on (vits_model_set_limiter, limiter.hip; "limit": its launches as one span, in place of the multiply). Prints one JSON line.
+usage: python tools/level_bench.py [--rounds 5] [--steps 4] [--ids 128] [--limit]"""
 import argparse
 import json
 import os
@@ -20,11 +21,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--ids", type=int, default=128)
+    ap.add_argument("--limit", action="store_true", help="also time VITS_LEVEL_LOUDNESS with VITS_LIMIT_TRUE_PEAK")
     a = ap.parse_args()
     pkg = load_package()
     import torch
     m = pkg.Model(pkg.synth_model_bytes(0x5EED, pkg.SYNTH_FULL))
-    kinds = (("none", pkg.LEVEL_NONE), ("loudness", pkg.LEVEL_LOUDNESS))
+    kinds = (("none", pkg.LEVEL_NONE), ("loudness", pkg.LEVEL_LOUDNESS)) + ((("limit", pkg.LEVEL_LOUDNESS),) if a.limit else ())
     res = {}
     for batch in (64, 1):
         ids = pkg.synth_ids(batch, a.ids)
@@ -32,37 +34,39 @@ def main():
         stride = int(m.process_batch(ids, noise_seed=5, frames_only=True)[1].max()) + 64
         out_dev = torch.empty(batch * stride, dtype=torch.float32, device="cuda")
 
-        def call(kind):
+        def call(kind, name):
+            m.set_limiter(pkg.LIMIT_TRUE_PEAK if name == "limit" else pkg.LIMIT_OFF)
             m.set_level(kind, -23.0, -1.0)
             return m.process_batch(ids, noise_seed=5, out_device=out_dev.data_ptr(), out_device_stride=stride, skip_host_copy=True, keep_pcm=False)
 
-        for _, k in kinds:
-            call(k)
+        for n, k in kinds:
+            call(k, n)
         times = {n: [] for n, _ in kinds}
         for _ in range(a.rounds):
             for n, k in kinds:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(a.steps):
-                    call(k)
+                    call(k, n)
                 torch.cuda.synchronize()
                 times[n].append((time.perf_counter() - t0) * 1e3 / a.steps)
         base = float(np.median(times["none"]))
         for n, k in kinds:
             m.prof_enable(True)
             m.prof_reset()
-            _, lengths, _ = call(k)
+            _, lengths, _ = call(k, n)
             rep = m.prof_report()
             m.prof_enable(False)
             ks = rep["kernels"]
             tot = sum(x["ms"] for x in ks) or 1.0
-            lv = {x["name"]: x for x in ks if x["name"].startswith("level_")}
+            lv = {x["name"]: x for x in ks if x["name"].startswith("level_") or x["name"] == "limit"}
             lms = sum(x["ms"] for x in lv.values())
             ms = float(np.median(times[n]))
             res["b%d_%s" % (batch, n)] = {
                 "ms_per_call": round(ms, 4), "vs_no_level": round(ms / base, 4), "samples": int(lengths.sum()), "kernel_ms": round(tot, 4),
                 "level_us": {name: round(1e3 * x["ms"], 2) for name, x in lv.items()}, "level_share_of_kernel_time": round(lms / tot, 5),
-                "levels_row0": None if m.last_levels() is None else [float(v) for v in m.last_levels()[0]], "rounds_ms": [round(t, 4) for t in times[n]]}
+                "levels_row0": None if m.last_levels() is None else [float(v) for v in m.last_levels()[0]],
+                "limits_row0": None if m.last_limits() is None else [float(v) for v in m.last_limits()[0]], "rounds_ms": [round(t, 4) for t in times[n]]}
         del out_dev
     m.close()
     print(json.dumps({"tool": "level_bench", "model": "FULL synthetic", "arith": "f32", "ids": a.ids, "results": res}))

@@ -29,6 +29,8 @@ FLOW_VARIANT_PLAN, FLOW_VARIANT_UNFUSED, FLOW_VARIANT_WAVENET, FLOW_VARIANT_COUP
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 # vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
+# vits_model_set_limiter: the levelling kinds that multiply deliver through the true-peak meter and the look-ahead limiter
+LIMIT_OFF, LIMIT_TRUE_PEAK = 0, 1
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
 #: every symbol include/vits.h declares (checked by tests/test_abi.py)
@@ -52,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_align_batch", "vits_model_align", "vits_model_hop", "vits_op_align", "vits_op_resblock_pair",
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
+    "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
@@ -70,6 +73,11 @@ class LevelDesc(C.Structure):
     """vits_level_desc"""
     _fields_ = [("rate", C.c_int32), ("batch", C.c_int32), ("x_stride", C.c_int64), ("y_stride", C.c_int64), ("kind", C.c_int32),
                 ("value_db", C.c_float), ("ceiling_db", C.c_float)]
+
+
+class LimitDesc(C.Structure):
+    """vits_limit_desc"""
+    _fields_ = [("level", LevelDesc), ("mode", C.c_int32)]
 
 
 class ProcessOpts(C.Structure):
@@ -262,6 +270,18 @@ def lib():
     L.vits_loudness_host.argtypes = [vp, sz, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
     L.vits_op_level.restype = i32
     L.vits_op_level.argtypes = [C.POINTER(LevelDesc), vp, vp, vp, vp]
+    L.vits_model_set_limiter.restype = i32
+    L.vits_model_set_limiter.argtypes = [vp, i32]
+    L.vits_model_get_limiter.restype = i32
+    L.vits_model_get_limiter.argtypes = [vp, C.POINTER(i32)]
+    L.vits_model_last_limits.restype = i64
+    L.vits_model_last_limits.argtypes = [vp, vp, sz]
+    L.vits_limiter_plan.restype = i32
+    L.vits_limiter_plan.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.vits_limiter_host.restype = i32
+    L.vits_limiter_host.argtypes = [vp, sz, i32, C.c_double, C.c_double, vp, vp]
+    L.vits_op_limit.restype = i32
+    L.vits_op_limit.argtypes = [C.POINTER(LimitDesc), vp, vp, vp, vp, vp]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -713,6 +733,34 @@ class Model:
             return None
         out = np.zeros((n // 4, 4), np.float32)
         if lib().vits_model_last_levels(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
+
+    # -- the loudness target under a ceiling (vits_model_set_limiter): true-peak meter and look-ahead limiter behind the level ---------------------
+    @property
+    def limiter(self):
+        """the handle's limiter mode: LIMIT_OFF or LIMIT_TRUE_PEAK"""
+        m = C.c_int32()
+        if lib().vits_model_get_limiter(self._h, C.byref(m)) != 0:
+            raise VitsError(last_error())
+        return int(m.value)
+
+    def set_limiter(self, mode=LIMIT_OFF):
+        """vits_model_set_limiter: with LIMIT_TRUE_PEAK, LEVEL_GAIN and LEVEL_LOUDNESS deliver the gain that was asked for through a look-ahead limiter that
+        keeps the model-rate row at or below ceiling_db, and LEVEL_PEAK normalises the true peak; last_limits() reads what it did."""
+        if lib().vits_model_set_limiter(self._h, int(mode)) != 0:
+            raise VitsError(last_error())
+
+    def last_limits(self):
+        """vits_model_last_limits: float32 [B, 4] = (true peak of the waveform; true peak of the delivered model-rate row; the smallest limiter gain; the share
+        of samples it turned down) of the most recently completed call, or None when it ran without the limiter. After an async call: valid after sync()."""
+        n = lib().vits_model_last_limits(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n // 4, 4), np.float32)
+        if lib().vits_model_last_limits(self._h, _ptr(out), out.size) != n:
             raise VitsError(last_error())
         return out
 
@@ -1245,6 +1293,46 @@ def level(x, rate, kind=LEVEL_MEASURE, value_db=0.0, ceiling_db=0.0, lens=None, 
     if lib().vits_op_level(C.byref(d), _ptr(x), _ptr(ln), _ptr(out) if out is not None else None, _ptr(levels)) != 0:
         raise VitsError(last_error())
     return out, levels
+
+
+def limiter_plan(rate):
+    """vits_limiter_plan: (A = look-ahead and attack, H = hold, tile = samples per block of the device kernels) at `rate` (host only)"""
+    a, h, t = C.c_int32(), C.c_int32(), C.c_int32()
+    if lib().vits_limiter_plan(int(rate), C.byref(a), C.byref(h), C.byref(t)) != 0:
+        raise VitsError(last_error())
+    return int(a.value), int(h.value), int(t.value)
+
+
+def limiter_host(pcm, rate, g0, ceiling_db):
+    """vits_limiter_host: (y float64 [n], limits float64 [4] = TP(x), TP(y), min s, share) of one row, the definition of include/vits.h in double on the
+    host (no device needed)"""
+    x = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
+    y, lim = np.zeros(max(x.size, 1), np.float64), np.zeros(4, np.float64)
+    if lib().vits_limiter_host(_ptr(x), x.size, int(rate), float(g0), float(ceiling_db), _ptr(y), _ptr(lim)) != 0:
+        raise VitsError(last_error())
+    return y[:x.size], lim
+
+
+def limit(x, rate, kind=LEVEL_GAIN, value_db=0.0, ceiling_db=0.0, lens=None, out=None, mode=LIMIT_TRUE_PEAK):
+    """The levelling tail with the limiter on a ragged batch (vits_op_limit), staged as the engine stages it. x: float32 [B, x_stride] (or one 1-D row) at
+    `rate`; lens: samples per row (None = the whole row). Returns (y, levels, limits): y float32 [B, y_stride] holds row b's lens[b] limited samples (zeros,
+    or what `out` held, behind them); levels float32 [B, 4] = (L, P, g0, blocks); limits float32 [B, 4] = (TP(x), TP(y), min s, share)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    if out is None:
+        out = np.zeros((B, max(int(ln.max()), 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    d = LimitDesc(LevelDesc(int(rate), B, max(stride, 1), out.shape[1], int(kind), float(value_db), float(ceiling_db)), int(mode))
+    levels, limits = np.zeros((B, 4), np.float32), np.zeros((B, 4), np.float32)
+    if lib().vits_op_limit(C.byref(d), _ptr(x), _ptr(ln), _ptr(out), _ptr(levels), _ptr(limits)) != 0:
+        raise VitsError(last_error())
+    return out, levels, limits
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

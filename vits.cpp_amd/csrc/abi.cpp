@@ -636,6 +636,74 @@ VITS_API int vits_loudness_host(const float* pcm, size_t n, int32_t rate, double
     return 0;
     VITS_CATCH(-1)
 }
+// ---- the loudness target under a ceiling (include/vits.h: the definition) --------------------------------------------------------------
+VITS_API int vits_model_set_limiter(vits_model* model, int32_t mode) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_limiter(mode, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_get_limiter(const vits_model* model, int32_t* mode) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (mode) *mode = model->eng.limiter_mode();
+    return 0;
+}
+VITS_API int64_t vits_model_last_limits(vits_model* model, float* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const float* p = model->eng.last_limits(rows);
+    const size_t n = (size_t)4 * rows;
+    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(float) * n);
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_limiter_plan(int32_t rate, int32_t* A, int32_t* H, int32_t* tile) {
+    VITS_TRY
+    vits::LimiterPlan p;
+    std::string err;
+    if (!vits::limiter_plan(rate, p, err)) {
+        set_err("vits_limiter_plan: " + err);
+        return -1;
+    }
+    if (A) *A = p.A;
+    if (H) *H = p.H;
+    if (tile) *tile = p.tile;
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_limiter_host(const float* pcm, size_t n, int32_t rate, double g0, double ceiling_db, double* y, double limits[4]) {
+    VITS_TRY
+    vits::LimiterPlan p;
+    std::string err;
+    if (!vits::limiter_plan(rate, p, err)) {
+        set_err("vits_limiter_host: " + err);
+        return -1;
+    }
+    if (!pcm && n) {
+        set_err("vits_limiter_host: null argument (pcm is NULL with n > 0)");
+        return -1;
+    }
+    if (!(std::isfinite(g0) && g0 > 0.0) || !(std::isfinite(ceiling_db) && ceiling_db >= -60.0 && ceiling_db <= 0.0)) {
+        set_err("vits_limiter_host: g0 must be finite and positive, ceiling_db in [-60, 0] dB");
+        return -1;
+    }
+    const std::vector<float> h = vits::resample_taps(p.up);
+    vits::limiter_host(pcm, n, p, h.data(), g0, std::pow(10.0, ceiling_db / 20.0), y, limits);
+    return 0;
+    VITS_CATCH(-1)
+}
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }
@@ -1996,6 +2064,92 @@ VITS_API int vits_op_level(const vits_level_desc* d, const float* x, const int64
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipMemcpy(levels, dlv.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
     if (y && hipMemcpy(y, dy.p, (size_t)B * d->y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_limit(const vits_limit_desc* ld, const float* x, const int64_t* lens, float* y, float* levels, float* limits) {
+    VITS_TRY
+    using namespace vits;
+    if (!ld || !x || !y || !levels || !limits || ld->level.batch <= 0 || ld->level.x_stride <= 0 || ld->level.y_stride <= 0)
+        return fail("vits_op_limit: null argument or empty batch");
+    const vits_level_desc* d = &ld->level;
+    if (ld->mode != VITS_LIMIT_TRUE_PEAK)
+        return fail(ld->mode == VITS_LIMIT_OFF ? "vits_op_limit: VITS_LIMIT_OFF limits nothing (use vits_op_level)" : ("vits_op_limit: unknown mode " + std::to_string(ld->mode)).c_str());
+    if (d->kind == VITS_LEVEL_NONE || d->kind == VITS_LEVEL_MEASURE) return fail("vits_op_limit: VITS_LEVEL_NONE and VITS_LEVEL_MEASURE apply nothing: there is nothing to limit");
+    LoudnessPlan plan;
+    LimiterPlan lplan;
+    std::string err;
+    if (!limiter_plan(d->rate, lplan, err) || !loudness_plan(d->rate, plan, err)) return fail(("vits_op_limit: " + err).c_str());
+    if (!level_values_ok(d->kind, d->value_db, d->ceiling_db, err) || (d->kind == VITS_LEVEL_GAIN && !level_values_ok(VITS_LEVEL_LOUDNESS, 0.f, d->ceiling_db, err)))
+        return fail(("vits_op_limit: " + err).c_str());
+    const int B = d->batch;
+    std::vector<int32_t> n(B);
+    int64_t longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = lens ? lens[b] : d->x_stride;
+        if (len < 0 || len > d->x_stride)
+            return fail(("vits_op_limit: lens[" + std::to_string(b) + "] = " + std::to_string(len) + " is outside [0, x_stride = " + std::to_string(d->x_stride) + "]").c_str());
+        if (len > ((int64_t)1 << 30)) return fail(("vits_op_limit: row " + std::to_string(b) + " is too long (" + std::to_string(len) + " samples)").c_str());
+        n[b] = (int32_t)len;
+        longest = std::max(longest, len);
+    }
+    if (d->y_stride < longest) return fail(("vits_op_limit: y_stride = " + std::to_string(d->y_stride) + " is shorter than the longest row (" + std::to_string(longest) + " samples)").c_str());
+    // the engine's staging: rows at a stride of a multiple of 32 samples, NaN behind every utterance: a read past one shows in the result
+    const int64_t xs = (longest + 31) / 32 * 32 + 32;
+    std::vector<float> hx((size_t)B * xs, std::numeric_limits<float>::quiet_NaN());
+    for (int b = 0; b < B; ++b) std::memcpy(&hx[(size_t)b * xs], x + (size_t)b * d->x_stride, sizeof(float) * (size_t)n[b]);
+    // the 4x table as the kernels read it, [K][L]
+    const std::vector<float> h = resample_taps(lplan.up);
+    std::vector<float> ht(h.size());
+    for (int p = 0; p < lplan.up.L; ++p)
+        for (int k = 0; k < lplan.up.K; ++k) ht[(size_t)k * lplan.up.L + p] = h[(size_t)p * lplan.up.K + k];
+    const size_t scratch = level_scratch_bytes(B, longest, plan.S), lscratch = limit_scratch_bytes(B, longest);
+    DevBuf dx, dy, dlv, dlm, dscr, dlscr, dt;
+    DevInts dn;
+    // (y goes up too: what lies behind a row's samples must come back as it was)
+    if (!dx.put(hx.data(), hx.size()) || !dlv.put(nullptr, (size_t)B * 4) || !dlm.put(nullptr, (size_t)B * 4) || !dscr.put(nullptr, (scratch + 3) / 4) ||
+        !dlscr.put(nullptr, (lscratch + 3) / 4) || !dt.put(ht.data(), ht.size()) || !dn.put(n.data(), B) || !dy.put(y, (size_t)B * d->y_stride))
+        return fail("device allocation failed");
+    LevelCall c;
+    c.x = dx.p;
+    c.x_stride = xs;
+    c.lens = dn.p;
+    c.batch = B;
+    c.max_len = longest;
+    c.plan = plan;
+    c.scratch = dscr.p;
+    c.kind = d->kind;
+    c.value_db = d->value_db;
+    c.ceiling_db = d->ceiling_db;
+    c.gain = (float)std::pow(10.0, (double)d->value_db / 20.0);
+    c.levels = dlv.p;
+    hipError_t e = launch_level_measure(c, nullptr);
+    if (e == hipSuccess) {
+        LimitCall mc;
+        mc.x = dx.p;
+        mc.x_stride = xs;
+        mc.y = dy.p;
+        mc.y_stride = d->y_stride;
+        mc.lens = dn.p;
+        mc.batch = B;
+        mc.max_len = longest;
+        mc.plan = lplan;
+        mc.taps = dt.p;
+        mc.scratch = dlscr.p;
+        mc.kind = d->kind;
+        mc.value_db = d->value_db;
+        mc.gain = c.gain;
+        mc.ceiling = (float)std::pow(10.0, (double)(d->kind == VITS_LEVEL_PEAK ? 0.f : d->ceiling_db) / 20.0);
+        mc.levels = dlv.p;
+        mc.limits = dlm.p;
+        e = launch_limit(mc, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
+    if (hipMemcpy(levels, dlv.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(limits, dlm.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(y, dy.p, (size_t)B * d->y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail("copy back failed");
     return 0;
     VITS_CATCH(-1)
 }

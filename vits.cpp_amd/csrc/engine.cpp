@@ -117,6 +117,10 @@ int Engine::sync(std::string& err) {
         last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * last_lv_rows_);
         last_lv_ = last_lv_store_.data();
     }
+    if (async_tail_ && last_lm_rows_ && last_lm_ != last_lm_store_.data()) {
+        last_lm_store_.assign(last_lm_, last_lm_ + (size_t)4 * last_lm_rows_);
+        last_lm_ = last_lm_store_.data();
+    }
     async_tail_ = false;
     return 0;
 }
@@ -227,13 +231,61 @@ int Engine::set_level(int kind, float value_db, float ceiling_db, std::string& e
         }
         level_plan_ = p;
     }
+    // (with the limiter on a gain is delivered under the ceiling too: the value is checked and kept)
+    const bool gain_ceiling = kind == VITS_LEVEL_GAIN && limit_mode_ != VITS_LIMIT_OFF;
+    if (gain_ceiling && !level_values_ok(VITS_LEVEL_LOUDNESS, 0.f, ceiling_db, why)) {
+        err = who + why;
+        return -1;
+    }
     level_kind_ = kind;
     level_value_ = kind >= VITS_LEVEL_GAIN ? value_db : 0.f;
-    level_ceiling_ = kind == VITS_LEVEL_LOUDNESS ? ceiling_db : 0.f;
+    level_ceiling_ = kind == VITS_LEVEL_LOUDNESS || gain_ceiling ? ceiling_db : 0.f;
+    return 0;
+}
+
+int Engine::set_limiter(int mode, std::string& err) {
+    const char* who = "vits_model_set_limiter: ";
+    if (mode != VITS_LIMIT_OFF && mode != VITS_LIMIT_TRUE_PEAK) {
+        err = who + ("unknown mode " + std::to_string(mode));
+        return -1;
+    }
+    if (mode != VITS_LIMIT_OFF) {
+        LimiterPlan p;
+        std::string why;
+        if (!limiter_plan(hp.sampling_rate, p, why)) {
+            err = who + ("the model's " + why);
+            return -1;
+        }
+        limit_plan_ = p;
+    }
+    limit_mode_ = mode;
+    return 0;
+}
+
+int Engine::grow_rows(float*& rows, int& cap_now, int B, std::string& err) {
+    if (B <= cap_now) return 0;
+    // (grow-only; the old rows are the previous call's, already on their way to the host in stream order — hipFree waits for them)
+    const int cap = std::max(B, 64);
+    float* fresh = nullptr;
+    HIP_OK(hipMalloc((void**)&fresh, sizeof(float) * 4 * (size_t)cap));
+    if (rows) {
+        for (void*& p : owned_)
+            if (p == rows) p = fresh;
+        hipFree(rows);
+    } else owned_.push_back(fresh);
+    weight_bytes += (int64_t)sizeof(float) * 4 * (cap - cap_now);
+    rows = fresh, cap_now = cap;
     return 0;
 }
 
 int Engine::check_level(const vits_process_opts& o, std::string& err) const {
+    if (o.on_chunk && limit_mode_ != VITS_LIMIT_OFF && level_kind_ >= VITS_LEVEL_GAIN) {
+        err = "on_chunk streams an utterance while it is being made, and this handle's limiter (vits_model_set_limiter) is on: the gain of a sample looks " +
+              std::to_string(limit_plan_.A) + " samples ahead and " + std::to_string(limit_plan_.H + limit_plan_.A) +
+              " back, so a window's last samples are not final when it ends, and the halo of finished samples that streaming would need is not built: "
+              "stream with VITS_LIMIT_OFF, or limit without on_chunk";
+        return -1;
+    }
     if (o.on_chunk && level_kind_ != VITS_LEVEL_NONE && level_kind_ != VITS_LEVEL_GAIN) {
         err = "on_chunk streams an utterance while it is being made, and this handle's level (vits_model_set_level: measure, peak or loudness) needs the whole "
               "utterance before its first sample can leave: only VITS_LEVEL_GAIN streams";
@@ -248,19 +300,7 @@ int Engine::check_level(const vits_process_opts& o, std::string& err) const {
 int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up;
-    if (B > lv_cap_) {
-        // (grow-only; the old rows are the previous call's, already on their way to the host in stream order — hipFree waits for them)
-        const int cap = std::max(B, 64);
-        float* fresh = nullptr;
-        HIP_OK(hipMalloc((void**)&fresh, sizeof(float) * 4 * (size_t)cap));
-        if (lv_rows_) {
-            for (void*& p : owned_)
-                if (p == lv_rows_) p = fresh;
-            hipFree(lv_rows_);
-        } else owned_.push_back(fresh);
-        weight_bytes += (int64_t)sizeof(float) * 4 * (cap - lv_cap_);
-        lv_rows_ = fresh, lv_cap_ = cap;
-    }
+    if (grow_rows(lv_rows_, lv_cap_, B, err)) return -1;
     const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
     LevelCall lc;
     lc.x = c.wave_dst;
@@ -280,7 +320,37 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
     hipError_t e = launch_level_measure(lc, stream);
     prof.end(stream);
     HIP_OK(e);
-    if (c.lev_apply && !c.o.on_chunk) {
+    if (c.lim) {
+        // the limiter in place of the plain multiply: meter, g0 (which replaces the measured row's gain), limiter, meter of what is delivered
+        if (grow_rows(lm_rows_, lm_cap_, B, err)) return -1;
+        const RateTable* up = rate_table(hp.sampling_rate, 4 * hp.sampling_rate, err);
+        if (!up) return -1;
+        LimitCall mc;
+        mc.x = c.wave_dst;
+        mc.x_stride = c.wave_stride;
+        mc.y = dst;
+        mc.y_stride = dst_stride;
+        mc.lens = lc.lens;
+        mc.batch = B;
+        mc.max_len = c.smax[n_up];
+        mc.plan = limit_plan_;
+        mc.taps = up->taps;
+        mc.scratch = c.s2.lim_scratch;
+        mc.kind = c.lev;
+        mc.value_db = level_value_;
+        mc.gain = lc.gain;
+        mc.ceiling = (float)std::pow(10.0, (double)level_ceiling_ / 20.0);
+        mc.levels = lv_rows_;
+        mc.limits = lm_rows_;
+        // two meter passes (4 K fma a sample each); the doubling steps and the mean; x, e and y read, e and y written
+        prof.begin("limit", (2.0 * 2 * 4 * limit_plan_.up.K + limit_plan_.A + 16) * (double)samples, 20.0 * (double)samples, stream, /*chain=*/true);
+        e = launch_limit(mc, stream);
+        prof.end(stream);
+        HIP_OK(e);
+        PinnedBuf<float>& lh = lm_host_[a1_slot_ & 1];
+        HIP_OK(lh.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
+        HIP_OK(hipMemcpyAsync(lh.p, lm_rows_, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    } else if (c.lev_apply && !c.o.on_chunk) {
         LevelScale sc;
         sc.x = c.wave_dst;
         sc.x_stride = c.wave_stride;
@@ -339,6 +409,7 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
     if (check_level(o, err)) return -1;
     last_lv_rows_ = 0;
+    last_lm_rows_ = 0;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -404,6 +475,15 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
         }
         last_lv_ = last_lv_store_.data();
         last_lv_rows_ = (int)(last_lv_store_.size() / 4);
+    }
+    if (!rc && part[0]->lm_rows + part[1]->lm_rows > 0) {
+        last_lm_store_.clear();
+        for (int h = 0; h < 2; ++h) {
+            const float* rows = lm_host_[(wait_seq_ + h) & 1].p;
+            last_lm_store_.insert(last_lm_store_.end(), rows, rows + (size_t)4 * part[h]->lm_rows);
+        }
+        last_lm_ = last_lm_store_.data();
+        last_lm_rows_ = (int)(last_lm_store_.size() / 4);
     }
     if (!rc && out) {
         const size_t stride = std::max(part[0]->stride, part[1]->stride);
@@ -490,6 +570,10 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
     last_lv_store_.assign(rows, rows + (size_t)4 * p.lv_rows);
     last_lv_ = last_lv_store_.data();
     last_lv_rows_ = p.lv_rows;
+    const float* lrows = lm_host_[wait_seq_ & 1].p;
+    last_lm_store_.assign(lrows, lrows + (size_t)4 * p.lm_rows);
+    last_lm_ = last_lm_store_.data();
+    last_lm_rows_ = p.lm_rows;
     p.active = false;
     ++wait_seq_;
     return 0;
@@ -719,6 +803,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     // multiplies it into what is delivered, or into the resampler's input. VITS_LEVEL_MEASURE measures the waveform where the vocoder wrote it
     c.lev = level_kind_;  // (on_chunk with a kind that cannot stream was refused by process_batch / convert_batch, before stage one was queued)
     const bool la = c.lev_apply = level_kind_ >= VITS_LEVEL_GAIN;
+    c.lim = la && limit_mode_ != VITS_LIMIT_OFF;  // (never with on_chunk: check_level)
 
     if (layout_stage_two(c)) return -1;
     if (c.vc) {
@@ -1005,6 +1090,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             pend->frames[b] = frames[b];
         }
         pend->lv_rows = c.lev ? B : 0;
+        pend->lm_rows = c.lim ? B : 0;
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -1035,6 +1121,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     }
     last_lv_ = c.lev ? lv_host_[a1_slot_ & 1].p : nullptr;
     last_lv_rows_ = c.lev ? B : 0;
+    last_lm_ = c.lim ? lm_host_[a1_slot_ & 1].p : nullptr;
+    last_lm_rows_ = c.lim ? B : 0;
     async_tail_ = want_async;
     if (!want_async) {
         HIP_OK(hipStreamSynchronize(stream));
@@ -1042,6 +1130,10 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         if (c.lev) {  // (the rows have landed: keep them apart from the pinned copy, which a later submit into this slot overwrites)
             last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * B);
             last_lv_ = last_lv_store_.data();
+        }
+        if (c.lim) {
+            last_lm_store_.assign(last_lm_, last_lm_ + (size_t)4 * B);
+            last_lm_ = last_lm_store_.data();
         }
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)

@@ -294,6 +294,16 @@ class Engine {
         rows = last_lv_rows_;
         return last_lv_;
     }
+    // the loudness target under a ceiling (include/vits.h vits_model_set_limiter; limiter.hip): with a mode set, the levelling kinds that multiply deliver
+    // through the true-peak meter and the limiter. 0, or -1 + a message with the handle unchanged (an unknown mode, a model rate above 48000 Hz). Nothing
+    // touches the device here: the 4x table and the row buffer are allocated by the first call that limits.
+    int set_limiter(int mode, std::string& err);
+    int limiter_mode() const { return limit_mode_; }
+    // the rows [B][4] = {TP(x), TP(y), min s, share} of the most recently completed call (empty: it ran without the limiter)
+    const float* last_limits(int& rows) const {
+        rows = last_lm_rows_;
+        return last_lm_;
+    }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -411,6 +421,7 @@ class Engine {
         PinnedBuf<int> win_pinned;    // vocoder-window length table of a windowed batch (host side of its H2D copy)
         PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
         int lv_rows = 0;              // levelling: rows of lv_host_[slot] this batch fills (0: no level was set)
+        int lm_rows = 0;              // the limiter: rows of lm_host_[slot] this batch fills (0: it was off)
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -491,6 +502,17 @@ class Engine {
     int check_level(const vits_process_opts& o, std::string& err) const;  // the refusal of on_chunk with a kind that needs the whole utterance
     // measures c.s2.wave and multiplies it into dst (engine.cpp); queued behind the last vocoder window
     int run_level(Call& c, float* dst, int64_t dst_stride);
+    // the limiter: the handle's mode, the plan at the model's rate, and the limits rows, kept exactly as the levels rows are
+    int limit_mode_ = VITS_LIMIT_OFF;
+    LimiterPlan limit_plan_;
+    float* lm_rows_ = nullptr;
+    int lm_cap_ = 0;
+    PinnedBuf<float> lm_host_[2];
+    const float* last_lm_ = nullptr;
+    int last_lm_rows_ = 0;
+    std::vector<float> last_lm_store_;
+    // a device row buffer [cap][4] of the handle grown to at least B rows (owned_, counted in weight_bytes)
+    int grow_rows(float*& rows, int& cap, int B, std::string& err);
     // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
     hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 

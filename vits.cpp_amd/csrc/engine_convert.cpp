@@ -266,6 +266,7 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
         }
     if (check_level(o, err)) return -1;
     last_lv_rows_ = 0;
+    last_lm_rows_ = 0;
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
     std::vector<int64_t> n_model;

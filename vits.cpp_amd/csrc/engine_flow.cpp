@@ -71,6 +71,7 @@ int Engine::layout_stage_two(Call& c) {
         s2.out_ranges = c.rate_out && o.on_chunk ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
         s2.wave_lvl = c.lev_apply && (c.rate_out || !o.out_device) ? a.alloc<float>((size_t)B * S_stride) : nullptr;
         s2.lvl_scratch = c.lev ? a.alloc<char>(level_scratch_bytes(B, smax[n_up], level_plan_.S)) : nullptr;
+        s2.lim_scratch = c.lim ? a.alloc<char>(limit_scratch_bytes(B, smax[n_up])) : nullptr;
         s2.lvl_ranges = c.lev_apply && o.on_chunk ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;

@@ -207,6 +207,7 @@ struct Call {
         int* out_ranges;    // output rate set, streaming: [window][2][B]: the output samples [j0, j1) of each utterance that window w finalises
         float* wave_lvl;    // a level that multiplies (VITS_LEVEL_GAIN ..), unless it goes straight to out_device: the levelled waveform [B][S_stride]
         void* lvl_scratch;  // a level set: level_scratch_bytes of loudness.hip
+        void* lim_scratch;  // the limiter on: limit_scratch_bytes of limiter.hip
         int* lvl_ranges;    // VITS_LEVEL_GAIN, streaming: [window][2][B]: the model-rate samples [j0, j1) of each utterance that window w finalises
     } s2{};
     int ls = 0, lws = 0, S_stride = 0;
@@ -223,6 +224,7 @@ struct Call {
     // a level set (Engine::level_kind): the kind of this call, and whether it multiplies (every kind but VITS_LEVEL_MEASURE)
     int lev = 0;
     bool lev_apply = false;
+    bool lim = false;  // the limiter is on and the kind multiplies: limiter.hip delivers in place of the plain multiply
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
 };

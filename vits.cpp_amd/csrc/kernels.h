@@ -715,6 +715,49 @@ struct LevelScale {
 // y = x * g, one fp32 multiply per sample; samples outside a row's range are left as they are
 hipError_t launch_level_scale(const LevelScale& c, hipStream_t s);
 
+// ---- the loudness target under a ceiling: 4x true-peak meter and look-ahead limiter (limiter.hip; the definition: include/vits.h vits_model_set_limiter,
+// DESIGN.md §8 "Under a ceiling") ----
+// u = the row resampled fs -> 4 fs by the project's own filter (L = 4, M = 1, R = 35, K = 71: ResamplePlan), the same ascending fmaf chain as resample.hip;
+// e[n] = max(|x[n]|, |u[4n - 2 .. 4n + 2]|); r = min(1, c / (g0 e)); m = sliding minimum of r over [j - H, j + A]; s = mean of m over [n - A, n] in fp64;
+// y = x (g0 s). No recurrence: a sample depends on the row's own samples [n - H - A - R - 1, n + A + R] alone. Tiles of kLimitTile samples are anchored at
+// the row's sample 0, nothing is accumulated with atomics, and only minima, maxima and integer counts cross a tile: no bit depends on the cut either.
+constexpr int kLimitTile = 2048;      // samples of a row per block, in every kernel of limiter.hip
+constexpr int kLimitMaxRate = 48000;  // 4 fs must be a rate the resampler accepts
+constexpr int kLimitMaxA = (kLimitMaxRate + 100) / 200, kLimitMaxH = (kLimitMaxRate + 10) / 20;
+struct LimiterPlan {
+    int rate = 0;
+    int A = 0;  // (rate + 100) / 200: 5 ms of look-ahead and attack
+    int H = 0;  // (rate + 10) / 20: 50 ms of hold
+    int tile = kLimitTile;
+    ResamplePlan up;  // rate -> 4 rate
+};
+// host only (limiter_host.cpp). false + a message: a rate outside [4000, 48000]
+bool limiter_plan(int rate, LimiterPlan& p, std::string& err);
+// the definition in double, sequentially. taps: resample_taps(p.up), [4][K]. y (optional) gets n samples; limits = {TP(x), TP(y), min s, share of s < 1}
+void limiter_host(const float* pcm, size_t n, const LimiterPlan& p, const float* taps, double g0, double c, double* y, double limits[4]);
+// bytes of device scratch: the envelope [batch][max_len], two tile maxima and the tile statistics
+size_t limit_scratch_bytes(int batch, int64_t max_len);
+struct LimitCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    float* y = nullptr;  // device [batch][y_stride], not x: row b gets its lens[b] samples, the rest is left as it was
+    int64_t y_stride = 0;
+    const int* lens = nullptr;  // device [batch]; nothing behind a row's samples is read
+    int batch = 0;
+    int64_t max_len = 0;  // the longest row (host side: sizes the grid and the scratch)
+    LimiterPlan plan;
+    const float* taps = nullptr;  // device [K][4]: the table ResampleCall takes for rate -> 4 rate
+    void* scratch = nullptr;      // device, limit_scratch_bytes(batch, max_len)
+    int kind = 0;                 // VITS_LEVEL_GAIN, _PEAK or _LOUDNESS
+    float value_db = 0.f;
+    float gain = 1.f;     // VITS_LEVEL_GAIN: (float)10^(value_db / 20), rounded on the host
+    float ceiling = 1.f;  // c = (float)10^(ceiling_db / 20)
+    float* levels = nullptr;  // device [batch][4], filled by launch_level_measure: row[2] is REPLACED by g0 (no ceiling rule; true-peak normalisation)
+    float* limits = nullptr;  // device [batch][4], out: TP(x), TP(y), min s, share of samples with s < 1
+};
+// meter(x), g0 and TP per row, then the limiter (GAIN, LOUDNESS) or the plain multiply (PEAK), then meter(y) and the rows
+hipError_t launch_limit(const LimitCall& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
