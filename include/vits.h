@@ -754,6 +754,67 @@ VITS_API int vits_op_duration_predictor(const vits_duration_predictor_desc* d, c
                                         const float* be1, const float* w2, const float* b2, const float* g2, const float* be2, const float* wp,
                                         const float* bp, const float* spk_rows, const int32_t* lens, float* logw);
 
+/* One DDS block of the stochastic duration predictor (`layers` layers of depthwise conv, LayerNorm, GELU, 1x1 conv, LayerNorm, GELU, residual; layer i
+ * has dilation k^i and zero padding (k - 1) k^i / 2, as Engine::run_dds builds them) on caller-supplied tensors, in the arithmetic of vits_op_set_arith
+ * (fp32, f16, bf16; the split arithmetic is refused), optionally with the per-token op in front of it and the 1x1 conv behind it:
+ *   head 0: the block's input is x [batch][channels][t_stride];
+ *   head 1: the conv flow's 1 -> H conv of latent row zc plus conditioning: input = head_w[c] * z[zc][t] + head_b[c] + cond[c][t]; z [batch][2][t_stride],
+ *           cond [batch][channels][t_stride], head_w [channels], head_b [channels]; x is not read;
+ *   head 2: an H -> H 1x1 conv of x: head_w [channels][channels], head_b [n_bias_rows][channels] (the effective-bias table of a multi-speaker model);
+ *           bias_rows [batch] (optional, NULL = row 0) names each utterance's row;
+ *   tail 0: the block's output goes to y [batch][channels][t_stride];
+ *   tail 1: y2 = tail_w . output + tail_b, tail_w [tail_rows][channels], tail_b [tail_rows], y2 [batch][tail_rows][t_stride].
+ * Per-layer parameters, layer-major: dw_w [layers][channels][k], dw_b, g1, b1 [layers][channels], pw_w [layers][channels][channels], pw_b, g2, b2
+ * [layers][channels]. lens optional, 0 <= lens[b] <= t <= t_stride.
+ * variant: 0 the engine's choice for this arithmetic and grid; 1 three launches per layer (dds_depthwise_kernel, the 1x1 conv, add_layer_norm_kernel with GELU
+ * and residual); 2 dds_layer_kernel, one launch per layer; 3 dds_layer_lat_kernel, fp32 only, at most `channels` tail rows. Variants 1 and 2 run head and
+ * tail as launches of their own (launch_pointwise_from1, the engine's conv); variant 3 fuses them into the first and the last layer as Engine::run_dds_lat does.
+ * Variants 1-3 never fall back to another variant: a shape without an instantiation (channels no multiple of 32 or beyond 256, (k - 1) * dilation odd, a layer
+ * whose tile passes the LDS limit, 16-bit arithmetic in variant 3) returns -1 with the cause in vits_last_error. Every refusal is made before the first device call.
+ * Staging is the engine's: the ping-pong buffers of run_dds / run_dds_lat. Every staged input and every intermediate buffer holds NaNs (0xFF bytes)
+ * behind lens[b] before the valid part goes in: a read past an utterance shows in the result. y and y2 (either may be NULL) come back as the device holds
+ * them, columns [0, t_stride): the staged NaN wherever no kernel wrote. With a tail, variant 3 has no y to write: it comes back all NaN; variants 1 and 2
+ * hold the block's output there. All variants give the same bits. */
+typedef struct vits_dds_block_desc {
+    int32_t batch, channels, t, t_stride;
+    int32_t k, layers;
+    float eps;
+    int32_t variant, head, tail, tail_rows, zc, n_bias_rows;
+} vits_dds_block_desc;
+VITS_API int vits_op_dds_block(const vits_dds_block_desc* d, const float* x, const float* z, const float* cond, const float* head_w, const float* head_b,
+                               const int32_t* bias_rows, const float* dw_w, const float* dw_b, const float* g1, const float* b1, const float* pw_w,
+                               const float* pw_b, const float* g2, const float* b2, const float* tail_w, const float* tail_b, const int32_t* lens, float* y,
+                               float* y2);
+/* What vits_op_dds_block would launch for d in the arithmetic of vits_op_set_arith, or -1 and the cause of its refusal. Host arithmetic only: no device call.
+ * kernel / kernel_last: the first and the last layer's instantiation as the launch-plan tables print it (variant 3: the head is part of the first name, the
+ * tail of the last; layers between them are <0, 0, M>; variant 1: dds_depthwise_kernel); nt: tokens per block (64 / 32 / 16); halo[i], lds[i]: layer i's halo
+ * columns per side and LDS bytes (at most 8 layers); launches: kernel launches for the block with head and tail (the converter launches of 16-bit convs not counted). */
+typedef struct vits_dds_block_plan {
+    char kernel[96], kernel_last[96];
+    int32_t variant; /* the variant that runs (1-3; what 0 resolved to) */
+    int32_t nt, layers;
+    int32_t halo[8];
+    int64_t lds[8];
+    int32_t grid_x, grid_y, block;
+    int32_t launches;
+} vits_dds_block_plan;
+VITS_API int vits_op_dds_block_plan(const vits_dds_block_desc* d, vits_dds_block_plan* plan);
+
+/* The inverse rational-quadratic spline of a conv flow (launch_spline) on caller-supplied tensors: u host [batch][3 bins - 1][t_stride] (widths, heights,
+ * inner derivatives), z host [batch][2][t_stride], in and out: row zc is transformed on [0, lens[b]), everything else keeps its bits. mode: VITS_MODE_HF
+ * (identity outside [-tail, tail], bounds inclusive) or VITS_MODE_REFERENCE (the reference's width scaling, last-token row and masked get / set pair).
+ * u is staged with NaNs behind lens[b]. bins 1..16 and t <= 4096, or -1 with the cause, before the first device call. lens optional. */
+VITS_API int vits_op_spline(int32_t batch, int32_t t, int32_t t_stride, int32_t bins, float tail, float inv_sqrt, int32_t mode, int32_t zc, const float* u,
+                            float* z, const int32_t* lens);
+
+/* The durations kernel (launch_durations, the device library's expf) on caller-supplied log-durations: logw host [batch][rows][t_stride], row `row` is read
+ * on [0, lens[b]); dur = ceil(exp(logw) * scale), scale = length_scales[b] (optional) or length_scale; ovr [batch][t_stride] (optional): entries >= 0 replace
+ * the token's duration; fixed > 0 replaces every duration. Outputs: dur (float, integer-valued) and cum (inclusive sums) [batch][t_stride], 0 and INT32_MAX
+ * behind lens[b]; frames [batch] = max(1, sum); stage_lens [n_stage][batch] = frames * stage_mul[s] + stage_add[s]. The outputs are staged as 0xFF bytes. */
+VITS_API int vits_op_durations(int32_t batch, int32_t rows, int32_t row, int32_t t_stride, const float* logw, const int32_t* lens, float length_scale,
+                               const float* length_scales, const int32_t* ovr, int32_t fixed, int32_t n_stage, const int32_t* stage_mul,
+                               const int32_t* stage_add, float* dur, int32_t* cum, int32_t* frames, int32_t* stage_lens);
+
 /* The alignment kernels (align_logp + align_mas; see vits_model_align_batch) on caller-supplied statistics: m, ls host [batch][F][Tmax] (prior mean and
  * log-deviation per token), z host [batch][F][Lmax], Tmax = max T[b], Lmax = max L[b], 1 <= T[b] <= L[b]. durations: out, host [batch][Tmax] (0 past
  * T[b]); scores: out, host [batch], optional. */

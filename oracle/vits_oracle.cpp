@@ -1574,6 +1574,23 @@ VO_API void vo_masked_get(const float* t, const float* mask, int64_t n, float* d
 }
 /* latents outside the spline interval met by the last vo_process_ids / vo_log_durations call of this thread (all three flows) */
 VO_API int64_t vo_outside_latents(void) { return g_outside_latents; }
+/* the spline step of a conv flow on one utterance, as duration_predictor() above runs it: u [3 bins - 1][T], z_row [T] in and out */
+VO_API int vo_spline(const float* u, float* z_row, int32_t T, int32_t bins, float tail, float inv_sqrt, int32_t mode) {
+    if (!u || !z_row || T < 1 || bins < 1 || (mode != VO_MODE_REFERENCE && mode != VO_MODE_HF)) return -1;
+    const int nb = bins;
+    if (mode == VO_MODE_REFERENCE) {
+        unconstrained_spline_reference(z_row, u, T, nb, tail, inv_sqrt);
+        return 0;
+    }
+    std::vector<float> uw(nb), uh(nb), ud(nb > 1 ? nb - 1 : 1);
+    for (int t = 0; t < T; ++t) {
+        for (int i = 0; i < nb; ++i) uw[i] = u[(size_t)i * T + t] * inv_sqrt;
+        for (int i = 0; i < nb; ++i) uh[i] = u[(size_t)(nb + i) * T + t] * inv_sqrt;
+        for (int i = 0; i < nb - 1; ++i) ud[i] = u[(size_t)(2 * nb + i) * T + t];
+        z_row[t] = spline_inverse(z_row[t], uw.data(), uh.data(), ud.data(), nb, tail, mode, t == T - 1);
+    }
+    return 0;
+}
 /* ref: test_ggml_utils.cpp:585-590 (commented out there) expects the compacted form {2,4,5}; custom-ops.h:739-762 keeps the shape
  * (zeros) instead (Q6). This is the compacted form the test vector describes. */
 VO_API int64_t vo_masked_get_compact(const float* t, const float* mask, int64_t n, float* dst) {

@@ -138,6 +138,9 @@ VO_API void vo_masked_get(const float* t, const float* mask, int64_t n, float* d
 /* number of duration-predictor latents that lay outside [-tail_bound, tail_bound] in the last vo_process_ids / vo_log_durations call of
  * the calling thread (summed over the three spline flows): 0 means the Q6 misalignment of vits.cpp:832-849 did not come into play */
 VO_API int64_t vo_outside_latents(void);
+/* The spline step of a conv flow on one utterance (spline_inverse per token in VO_MODE_HF, unconstrained_spline_reference in VO_MODE_REFERENCE):
+ * u [3 bins - 1][T] (widths, heights, inner derivatives), z_row [T] in and out. Needs no model. 0, or -1 for a bad argument. */
+VO_API int vo_spline(const float* u, float* z_row, int32_t T, int32_t bins, float tail, float inv_sqrt, int32_t mode);
 VO_API void vo_gather0(const float* t, const int64_t ne[3], const float* index, int64_t n_index, float* dst);
 VO_API void vo_arange(int32_t end, float* dst);
 

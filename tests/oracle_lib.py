@@ -87,6 +87,8 @@ def lib():
     L.vo_max.restype = C.c_float
     L.vo_max.argtypes = [vp, i64]
     L.vo_masked_get_compact.restype = i64
+    L.vo_spline.restype = i32
+    L.vo_spline.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, i32]
     _lib = L
     return L
 
@@ -175,6 +177,17 @@ def _log_durations(self, ids, mode=MODE_REFERENCE, noise_kind=NOISE_COUNTER, noi
 
 
 Model.log_durations = _log_durations
+
+
+def spline(u, z_row, bins, tail, inv_sqrt, mode):
+    """The spline step of a conv flow on one utterance (vo_spline): u [3 bins - 1, T], z_row [T]; returns the transformed row (float32)."""
+    u = np.ascontiguousarray(u, np.float32)
+    z = np.array(z_row, np.float32)
+    T = z.size
+    assert u.shape == (3 * bins - 1, T)
+    if lib().vo_spline(u.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p), T, bins, tail, inv_sqrt, mode) != 0:
+        raise RuntimeError("vo_spline: bad argument")
+    return z
 
 
 def outside_latents():

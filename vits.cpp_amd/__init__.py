@@ -26,6 +26,8 @@ DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
 DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
 RB_VARIANT_PLAN, RB_VARIANT_UNFUSED, RB_VARIANT_PAIRS, RB_VARIANT_BLOCK, RB_VARIANT_SEGMENTS = 0, 1, 2, 3, 4  # op_resblock
 FLOW_VARIANT_PLAN, FLOW_VARIANT_UNFUSED, FLOW_VARIANT_WAVENET, FLOW_VARIANT_COUPLING = 0, 1, 2, 3  # op_flow_coupling
+DDS_VARIANT_PLAN, DDS_VARIANT_UNFUSED, DDS_VARIANT_LAYER, DDS_VARIANT_LAT = 0, 1, 2, 3  # op_dds_block
+DDS_HEAD_NONE, DDS_HEAD_FROM1, DDS_HEAD_CONV = 0, 1, 2
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 # vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
@@ -57,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan",
+    "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -130,6 +133,17 @@ class FlowCouplingDesc(C.Structure):
 class FlowCouplingPlan(C.Structure):
     _fields_ = [("kernel", C.c_char * 96), ("variant", C.c_int32), ("bo", C.c_int32), ("halo", C.c_int32), ("ncw", C.c_int32), ("nct", C.c_int32),
                 ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64), ("launches", C.c_int32)]
+
+
+class DdsBlockDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32), ("layers", C.c_int32),
+                ("eps", C.c_float), ("variant", C.c_int32), ("head", C.c_int32), ("tail", C.c_int32), ("tail_rows", C.c_int32), ("zc", C.c_int32),
+                ("n_bias_rows", C.c_int32)]
+
+
+class DdsBlockPlan(C.Structure):
+    _fields_ = [("kernel", C.c_char * 96), ("kernel_last", C.c_char * 96), ("variant", C.c_int32), ("nt", C.c_int32), ("layers", C.c_int32),
+                ("halo", C.c_int32 * 8), ("lds", C.c_int64 * 8), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("block", C.c_int32), ("launches", C.c_int32)]
 
 
 class DurationPredictorDesc(C.Structure):
@@ -324,6 +338,14 @@ def lib():
     L.vits_op_flow_coupling.argtypes = [C.POINTER(FlowCouplingDesc)] + [vp] * 11
     L.vits_op_flow_coupling_plan.restype = i32
     L.vits_op_flow_coupling_plan.argtypes = [C.POINTER(FlowCouplingDesc), C.POINTER(FlowCouplingPlan)]
+    L.vits_op_dds_block.restype = i32
+    L.vits_op_dds_block.argtypes = [C.POINTER(DdsBlockDesc)] + [vp] * 19
+    L.vits_op_dds_block_plan.restype = i32
+    L.vits_op_dds_block_plan.argtypes = [C.POINTER(DdsBlockDesc), C.POINTER(DdsBlockPlan)]
+    L.vits_op_spline.restype = i32
+    L.vits_op_spline.argtypes = [i32, i32, i32, i32, C.c_float, C.c_float, i32, i32, vp, vp, vp]
+    L.vits_op_durations.restype = i32
+    L.vits_op_durations.argtypes = [i32, i32, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.vits_op_conv_transpose1d.restype = i32
     L.vits_op_conv_transpose1d.argtypes = [C.POINTER(ConvT1dDesc), vp, vp, vp, vp, vp]
     L.vits_op_rel_attention.restype = i32
@@ -1169,6 +1191,92 @@ def op_duration_predictor(x, w1, b1, g1, be1, w2, b2, g2, be2, wp, bp, spk_rows=
                                         _ptr(spk_rows), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
+
+
+def op_dds_block_plan(channels, k, layers, t, batch=1, variant=DDS_VARIANT_PLAN, head=DDS_HEAD_NONE, tail_rows=0):
+    """What op_dds_block would launch in the arithmetic of op_set_arith (vits_op_dds_block_plan; host arithmetic, no GPU needed): a dict with kernel and
+    kernel_last (the first and the last layer's instantiation), variant (the one that runs), nt (tokens per block), halo and lds (per layer), grid, block,
+    launches — or a VitsError naming the cause of the refusal."""
+    d = DdsBlockDesc(batch, channels, t, t, k, layers, 1e-5, variant, head, 1 if tail_rows else 0, tail_rows, 0, 1)
+    p = DdsBlockPlan()
+    if lib().vits_op_dds_block_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "nt", "block", "launches")}
+    out["kernel"], out["kernel_last"] = p.kernel.decode(), p.kernel_last.decode()
+    out["halo"], out["lds"] = list(p.halo[:p.layers]), list(p.lds[:p.layers])
+    out["grid"] = (p.grid_x, p.grid_y)
+    return out
+
+
+def op_dds_block(dw_w, dw_b, g1, b1, pw_w, pw_b, g2, b2, x=None, z=None, cond=None, zc=0, head_w=None, head_b=None, bias_rows=None, tail_w=None, tail_b=None,
+                 lens=None, t=None, eps=1e-5, variant=DDS_VARIANT_PLAN):
+    """One DDS block through the kernels `variant` names (vits_op_dds_block): dw_w [layers, H, k]; dw_b, g1, b1, pw_b, g2, b2 [layers, H]; pw_w [layers, H, H].
+    Input: x [B, H, t_stride] (no head), or z [B, 2, t_stride] + cond [B, H, t_stride] + head_w [H] + head_b [H] (the 1 -> H conv of latent row zc plus
+    conditioning), or x + head_w [H, H] + head_b [rows, H] (or [H]) + bias_rows [B] or None (an H -> H 1x1 conv in front). tail_w [R, H] + tail_b [R]: the 1x1
+    projection behind the block. t = the longest utterance (default: t_stride). DDS_VARIANT_UNFUSED | _LAYER | _LAT run those kernels or raise a VitsError
+    naming the cause: never others. Returns (y [B, H, t_stride], y2 [B, R, t_stride] or None) as the device holds them: the staged NaN (all bits set) wherever
+    nothing was written."""
+    dw_w, pw_w = _f32(dw_w), _f32(pw_w)
+    layers, H, k = dw_w.shape
+    vec = [_f32(v).reshape(layers, H) for v in (dw_b, g1, b1, pw_b, g2, b2)]
+    assert pw_w.shape[:3] == (layers, H, H) and pw_w.size == layers * H * H
+    x, z, cond, head_w, head_b, tail_w, tail_b = _f32(x), _f32(z), _f32(cond), _f32(head_w), _f32(head_b), _f32(tail_w), _f32(tail_b)
+    if z is not None:
+        head, (B, _, ts), rows = DDS_HEAD_FROM1, z.shape, 1
+        assert x is None and z.shape[1] == 2 and cond.shape == (B, H, ts) and head_w.size == H and head_b.size == H
+    else:
+        B, _, ts = x.shape
+        assert x.shape[1] == H
+        head, rows = (DDS_HEAD_CONV, 1) if head_w is not None else (DDS_HEAD_NONE, 1)
+        if head:
+            head_b = head_b.reshape(-1, H)
+            rows = head_b.shape[0]
+            assert head_w.size == H * H
+    R = 0
+    if tail_w is not None:
+        R = tail_b.size
+        assert tail_w.size == R * H
+    d = DdsBlockDesc(B, H, ts if t is None else t, ts, k, layers, eps, variant, head, 1 if R else 0, R, zc, rows)
+    y = np.zeros((B, H, ts), np.float32)
+    y2 = np.zeros((B, R, ts), np.float32) if R else None
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    bias_rows = None if bias_rows is None else np.ascontiguousarray(bias_rows, dtype=np.int32)
+    assert (lens is None or lens.shape == (B,)) and (bias_rows is None or bias_rows.shape == (B,))
+    if lib().vits_op_dds_block(C.byref(d), _ptr(x), _ptr(z), _ptr(cond), _ptr(head_w), _ptr(head_b), _ptr(bias_rows), _ptr(dw_w), *[_ptr(v) for v in vec[:3]],
+                               _ptr(pw_w), *[_ptr(v) for v in vec[3:]], _ptr(tail_w), _ptr(tail_b), _ptr(lens), _ptr(y), _ptr(y2)) != 0:
+        raise VitsError(last_error())
+    return y, y2
+
+
+def op_spline(u, z, zc, bins, tail, inv_sqrt, mode, lens=None, t=None):
+    """The inverse rational-quadratic spline of a conv flow on caller-supplied tensors (vits_op_spline): u [B, 3 bins - 1, t_stride], z [B, 2, t_stride]; row zc
+    of z is transformed on [0, lens[b]) in MODE_HF or MODE_REFERENCE semantics. Returns the new z (every other bit as given)."""
+    u, z = _f32(u), _f32(z)
+    B, rows, ts = u.shape
+    assert rows == 3 * bins - 1 and z.shape == (B, 2, ts)
+    out = z.copy()
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    if lib().vits_op_spline(B, ts if t is None else t, ts, bins, tail, inv_sqrt, mode, zc, _ptr(u), _ptr(out), _ptr(lens)) != 0:
+        raise VitsError(last_error())
+    return out
+
+
+def op_durations(logw, row, lens, length_scale=1.0, length_scales=None, overrides=None, fixed=0, stage_mul=(), stage_add=()):
+    """The durations kernel on caller-supplied log-durations (vits_op_durations): logw [B, rows, t_stride], row `row` is read. Returns (dur float32 [B, t_stride],
+    cum int32 [B, t_stride], frames int32 [B], stage_lens int32 [n_stage, B])."""
+    logw = _f32(logw)
+    B, rows, ts = logw.shape
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    length_scales = None if length_scales is None else _f32(length_scales).reshape(B)
+    overrides = None if overrides is None else np.ascontiguousarray(overrides, dtype=np.int32).reshape(B, ts)
+    mul, add = np.ascontiguousarray(stage_mul, dtype=np.int32), np.ascontiguousarray(stage_add, dtype=np.int32)
+    assert mul.shape == add.shape and mul.ndim == 1
+    dur, cum = np.zeros((B, ts), np.float32), np.zeros((B, ts), np.int32)
+    frames, sl = np.zeros(B, np.int32), np.zeros((mul.size, B), np.int32)
+    if lib().vits_op_durations(B, rows, row, ts, _ptr(logw), _ptr(lens), length_scale, _ptr(length_scales), _ptr(overrides), fixed, mul.size,
+                               _ptr(mul) if mul.size else None, _ptr(add) if mul.size else None, _ptr(dur), _ptr(cum), _ptr(frames), _ptr(sl) if mul.size else None) != 0:
+        raise VitsError(last_error())
+    return dur, cum, frames, sl
 
 
 def op_conv_transpose1d(x, w, bias, stride, crop, pre_slope=1.0, lens=None):

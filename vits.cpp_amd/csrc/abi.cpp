@@ -1900,6 +1900,337 @@ VITS_API int vits_op_duration_predictor(const vits_duration_predictor_desc* d, c
     VITS_CATCH(-1)
 }
 
+// ---- vits_op_dds_block: which kernels a descriptor names (host arithmetic only: launch_plan.h), then the engine's launch sequences on staged tensors --------
+namespace {
+struct DdsOpPlan {
+    int variant = 0, nt = 0, launches = 0;
+    std::string kernel, kernel_last;
+    int halo[8] = {0}, dil[8] = {0};
+    size_t lds[8] = {0};
+    vits::LaunchGrid g;
+};
+bool dds_fail(std::string& why, const std::string& m) {
+    why = "vits_op_dds_block: " + m;
+    return false;
+}
+bool dds_resolve(const vits_dds_block_desc* d, int arith, DdsOpPlan& r, std::string& why) {
+    using namespace vits;
+    if (arith != VITS_ARITH_F32 && arith != VITS_ARITH_F16 && arith != VITS_ARITH_BF16)
+        return dds_fail(why, "VITS_ARITH_F32, VITS_ARITH_F16 or VITS_ARITH_BF16 only (the split arithmetic has no DDS kernels)");
+    const int H = d->channels, k = d->k, B = d->batch, T = d->t, NL = d->layers;
+    if (B < 1 || T < 1 || d->t_stride < T) return dds_fail(why, "batch >= 1 and 1 <= t <= t_stride are required");
+    if (H < 1) return dds_fail(why, "channels = " + std::to_string(H) + ": at least 1");
+    if (k < 1 || k > 64) return dds_fail(why, "k = " + std::to_string(k) + ": 1 to 64 taps");
+    if (NL < 1 || NL > 8) return dds_fail(why, "layers = " + std::to_string(NL) + ": 1 to 8 layers");
+    if (!(d->eps > 0.f)) return dds_fail(why, "eps must be positive");
+    if (d->variant < 0 || d->variant > 3)
+        return dds_fail(why, "variant " + std::to_string(d->variant) + ": 0 (the engine's choice), 1 (three launches per layer), 2 (dds_layer_kernel), 3 (dds_layer_lat_kernel)");
+    if (d->head < 0 || d->head > 2) return dds_fail(why, "head " + std::to_string(d->head) + ": 0 (none), 1 (1 -> H conv of a latent row + conditioning), 2 (H -> H 1x1 conv)");
+    if (d->tail < 0 || d->tail > 1) return dds_fail(why, "tail " + std::to_string(d->tail) + ": 0 (none) or 1 (a tail_rows x H 1x1 projection)");
+    if (d->tail == 1 && d->tail_rows < 1) return dds_fail(why, "tail_rows = " + std::to_string(d->tail_rows) + ": at least 1");
+    if (d->head == 1 && d->zc != 0 && d->zc != 1) return dds_fail(why, "zc = " + std::to_string(d->zc) + ": latent row 0 or 1");
+    if (d->head == 2 && d->n_bias_rows < 1) return dds_fail(why, "n_bias_rows = " + std::to_string(d->n_bias_rows) + ": the head conv's bias table has at least one row");
+    int64_t dl = 1;
+    for (int i = 0; i < NL; ++i, dl *= k) {
+        if (dl * (k - 1) > 8192) return dds_fail(why, "layer " + std::to_string(i) + ": dilation " + std::to_string(dl) + " is out of range");
+        r.dil[i] = (int)dl;
+        r.halo[i] = (int)((k * dl - dl) / 2);
+    }
+    const bool f32 = arith == VITS_ARITH_F32;
+    // why dds_layer_kernel (lat false) / dds_layer_lat_kernel (lat true) has no instantiation for this block, or ""
+    auto refusal = [&](bool lat) -> std::string {
+        const char* fam = lat ? "dds_layer_lat_kernel" : "dds_layer_kernel";
+        if (lat && !f32) return std::string("variant 3: ") + fam + " exists in fp32 only";
+        if (H < 32 || (H & 31) || H > 256)
+            return std::string("no ") + fam + " for channels = " + std::to_string(H) + " (32 to 256 in steps of 32)";
+        for (int i = 0; i < NL; ++i) {
+            const std::string at = "layer " + std::to_string(i) + " (k = " + std::to_string(k) + ", dilation " + std::to_string(r.dil[i]) + "): ";
+            if ((k * r.dil[i] - r.dil[i]) & 1) return at + "(k - 1) * dilation is odd: no symmetric halo for " + fam;
+            const size_t lds = lat ? dds_lat_lds(H, k, r.dil[i], true, H) : dds_layer_lds(H, k, r.dil[i]);
+            if (lds > kLdsSoft) return at + fam + " needs " + std::to_string(lds) + " bytes of LDS, the limit is " + std::to_string(kLdsSoft);
+            if (!(lat ? plan_dds_layer_lat(H, k, r.dil[i], true, B, T).ok : plan_dds_layer(H, k, r.dil[i], B, T).ok)) return at + "the planner refuses " + fam;
+        }
+        if (lat && d->tail == 1 && d->tail_rows > H) return "variant 3: tail_rows = " + std::to_string(d->tail_rows) + " exceeds channels = " + std::to_string(H);
+        return "";
+    };
+    int v = d->variant;
+    if (v == 0)  // Engine::dds_lat_ok, then Engine::run_dds
+        v = f32 && NL >= 2 && dds_lat_grid_ok(B, T) && refusal(true).empty() ? 3 : NL >= 2 && refusal(false).empty() ? 2 : 1;
+    r.variant = v;
+    const int ends = (d->head ? 1 : 0) + (d->tail ? 1 : 0);
+    char name[96];
+    if (v == 1) {
+        for (int i = 0; i < NL; ++i) {
+            const LaunchGrid g = plan_dds_depthwise(H, k, r.dil[i], B, T);
+            r.lds[i] = dds_depthwise_lds(H, k, r.dil[i]);
+            if (!g.ok)
+                return dds_fail(why, "variant 1: layer " + std::to_string(i) + ": dds_depthwise_kernel needs " + std::to_string(r.lds[i]) + " bytes of LDS, the limit is " +
+                                         std::to_string(kLdsSoft));
+            if (i == 0) r.g = g;
+        }
+        if (!plan_add_layer_norm(H, B, T).ok) return dds_fail(why, "variant 1: add_layer_norm_kernel has no tile for channels = " + std::to_string(H));
+        r.kernel = r.kernel_last = "dds_depthwise_kernel";
+        r.nt = 64, r.launches = 3 * NL + ends;
+        return true;
+    }
+    const std::string no = refusal(v == 3);
+    if (!no.empty()) return dds_fail(why, (no.rfind("variant", 0) == 0 ? "" : "variant " + std::to_string(v) + ": ") + no);
+    if (v == 2) {
+        const DdsLayerPlan pl = plan_dds_layer(H, k, 1, B, T);
+        std::snprintf(name, sizeof(name), "dds_layer_kernel<%d, %d>", arith, pl.m);
+        r.kernel = r.kernel_last = name;
+        for (int i = 0; i < NL; ++i) r.lds[i] = dds_layer_lds(H, k, r.dil[i]);
+        r.g = pl, r.nt = 32, r.launches = NL + ends;
+        return true;
+    }
+    const DdsLayerPlan pl = plan_dds_layer_lat(H, k, 1, d->head == 2, B, T);
+    std::snprintf(name, sizeof(name), "dds_layer_lat_kernel<%d, %d, %d>", d->head, NL == 1 ? d->tail : 0, pl.m);
+    r.kernel = name;
+    std::snprintf(name, sizeof(name), "dds_layer_lat_kernel<%d, %d, %d>", NL == 1 ? d->head : 0, d->tail, pl.m);
+    r.kernel_last = name;
+    for (int i = 0; i < NL; ++i) r.lds[i] = dds_lat_lds(H, k, r.dil[i], i == 0 && d->head == 2, H);
+    r.g = pl, r.nt = kLatNT, r.launches = NL;
+    return true;
+}
+}  // namespace
+
+VITS_API int vits_op_dds_block_plan(const vits_dds_block_desc* d, vits_dds_block_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_dds_block_plan: null argument");
+    DdsOpPlan r;
+    std::string why;
+    if (!dds_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", r.kernel.c_str());
+    std::snprintf(out->kernel_last, sizeof(out->kernel_last), "%s", r.kernel_last.c_str());
+    out->variant = r.variant, out->nt = r.nt, out->layers = d->layers, out->launches = r.launches;
+    for (int i = 0; i < d->layers; ++i) out->halo[i] = r.halo[i], out->lds[i] = (int64_t)r.lds[i];
+    out->grid_x = r.g.gx, out->grid_y = r.g.gy, out->block = r.g.block;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_dds_block(const vits_dds_block_desc* d, const float* x, const float* z, const float* cond, const float* head_w, const float* head_b,
+                               const int32_t* bias_rows, const float* dw_w, const float* dw_b, const float* g1, const float* b1, const float* pw_w,
+                               const float* pw_b, const float* g2, const float* b2, const float* tail_w, const float* tail_b, const int32_t* lens, float* y,
+                               float* y2) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !dw_w || !dw_b || !g1 || !b1 || !pw_w || !pw_b || !g2 || !b2) return fail("vits_op_dds_block: null argument (every per-layer parameter is required)");
+    const int arith = g_op_arith;
+    DdsOpPlan r;
+    std::string why;
+    if (!dds_resolve(d, arith, r, why)) return fail(why.c_str());
+    const int B = d->batch, H = d->channels, T = d->t, ts = d->t_stride, k = d->k, NL = d->layers, TR = d->tail ? d->tail_rows : 0;
+    if (d->head != 1 && !x) return fail("vits_op_dds_block: x is required with head 0 and head 2");
+    if (d->head == 1 && (!z || !cond)) return fail("vits_op_dds_block: z and cond are required with head 1");
+    if (d->head && (!head_w || !head_b)) return fail("vits_op_dds_block: head_w and head_b are required with a head");
+    if (d->tail && (!tail_w || !tail_b || !y2)) return fail("vits_op_dds_block: tail_w, tail_b and y2 are required with a tail");
+    if (!d->tail && !y) return fail("vits_op_dds_block: y is required without a tail");
+    for (int b = 0; b < B; ++b) {
+        if (lens && (lens[b] < 0 || lens[b] > T)) return fail("vits_op_dds_block: 0 <= lens[b] <= t is required");
+        if (d->head == 2 && bias_rows && (bias_rows[b] < 0 || bias_rows[b] >= d->n_bias_rows)) return fail("vits_op_dds_block: 0 <= bias_rows[b] < n_bias_rows is required");
+    }
+    const bool f32 = arith == VITS_ARITH_F32;
+    struct Conv {
+        PackedConv pc;
+        DevBytes w, wl, w16, b;
+    };
+    auto upload = [&](Conv& c, const float* w, const float* bias, size_t bias_n, int cout, int cin) {
+        PackedConv& pc = c.pc;
+        pc.cin = cin, pc.cout = cout, pc.kt = 1, pc.epi = EPI_STD;
+        const std::vector<float> packed = pack_conv_weights(w, cout, cin, 1, EPI_STD, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+        if (!c.b.put(bias, bias_n * 4)) return false;
+        pc.bias = c.b.f();
+        if (f32) {
+            if (!c.w.put(packed.data(), packed.size() * 4)) return false;
+            pc.wp = c.w.f(), pc.bytes = (int64_t)packed.size() * 4;
+            const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, 1);
+            if (!c.wl.put(pl.data(), pl.size() * 4)) return false;
+            pc.wp_l16 = c.wl.f();
+        } else {
+            const std::vector<uint16_t> p16 = pack_conv_weights16(w, cout, cin, 1, EPI_STD, 0, arith);
+            if (!c.w16.put(p16.data(), p16.size() * 2)) return false;
+            pc.wp16 = c.w16.h(), pc.bytes16 = (int64_t)p16.size() * 2;
+        }
+        return true;
+    };
+    std::vector<Conv> pw(NL);
+    Conv hconv, tconv;
+    DevBytes ddw_w, ddw_b, dg1, db1, dg2, db2, dhw, dhb;
+    const size_t nlh = (size_t)NL * H;
+    if (!ddw_w.put(dw_w, nlh * k * 4) || !ddw_b.put(dw_b, nlh * 4) || !dg1.put(g1, nlh * 4) || !db1.put(b1, nlh * 4) || !dg2.put(g2, nlh * 4) || !db2.put(b2, nlh * 4))
+        return fail("device allocation failed");
+    for (int i = 0; i < NL; ++i)
+        if (!upload(pw[i], pw_w + (size_t)i * H * H, pw_b + (size_t)i * H, H, H, H)) return fail("device allocation failed");
+    if (d->head == 1 && (!dhw.put(head_w, (size_t)H * 4) || !dhb.put(head_b, (size_t)H * 4))) return fail("device allocation failed");
+    if (d->head == 2) {
+        if (!upload(hconv, head_w, head_b, (size_t)d->n_bias_rows * H, H, H)) return fail("device allocation failed");
+        hconv.pc.bias_rs = bias_rows ? H : 0;
+    }
+    if (d->tail && !upload(tconv, tail_w, tail_b, TR, TR, H)) return fail("device allocation failed");
+    // host staging: NaN everywhere, then the valid columns; buffers nobody uploads into are NaN bytes
+    auto len_of = [&](int b) { return lens ? lens[b] : T; };
+    auto stage = [&](DevBytes& dst, const float* src, int rows) {
+        const size_t n = (size_t)B * rows * ts;
+        std::vector<float> h(n);
+        std::memset(h.data(), 0xFF, n * 4);
+        for (int b = 0; src && b < B; ++b)
+            for (int c = 0; c < rows; ++c) std::memcpy(&h[((size_t)b * rows + c) * ts], src + ((size_t)b * rows + c) * ts, sizeof(float) * (size_t)len_of(b));
+        return dst.put(h.data(), n * 4);
+    };
+    DevInts dl, dspk;
+    DevBytes dx, da, dbb, dc, dz, dcond, dy2, dx16;
+    if (!dl.put(lens, B) || !dspk.put(d->head == 2 ? bias_rows : nullptr, B)) return fail("device allocation failed");
+    if (!stage(dx, d->head == 1 ? nullptr : x, H) || !stage(da, nullptr, H) || !stage(dbb, nullptr, H) || !stage(dc, nullptr, H)) return fail("device allocation failed");
+    if (d->head == 1 && (!stage(dz, z, 2) || !stage(dcond, cond, H))) return fail("device allocation failed");
+    if (d->tail && !stage(dy2, nullptr, TR)) return fail("device allocation failed");
+    const size_t x16_bytes = f32 ? 0 : (size_t)B * (H / 8 + 1) * round_up(T, 8) * 8 * 2;
+    if (!f32 && !dx16.fill(x16_bytes, 0xFF)) return fail("device allocation failed");
+    // a conv of the fp32-layout orchestration (Engine::conv): the fp32 kernel, or the converter + the 16-bit-operand kernel (Engine::conv16_transparent)
+    auto conv = [&](const PackedConv& w, TensorRef xin, TensorRef yout) -> hipError_t {
+        ConvCall c;
+        c.x = xin, c.y = yout, c.len_in = c.len_out = dl.p, c.spk = dspk.p, c.batch = B, c.t_in = c.t_out = T;
+        if (f32) return launch_conv(w, c, nullptr);
+        Ref16 x16;
+        x16.p = dx16.h(), x16.ts = round_up(T, 8), x16.bs = (int64_t)((w.cin + 7) / 8) * x16.ts * 8;
+        if (hipMemsetAsync(dx16.p, 0xFF, x16_bytes, nullptr) != hipSuccess) return hipErrorUnknown;
+        hipError_t e2 = launch_to_group16(c.x, c.len_in, B, w.cin, T, 1.0f, x16, arith, nullptr);
+        if (e2 != hipSuccess) return e2;
+        Conv16Call q;
+        q.x = x16, q.len_in = c.len_in, q.len_out = c.len_out, q.spk = c.spk, q.batch = B, q.t_in = q.t_out = T, q.y = c.y;
+        return launch_conv16(w, q, arith, nullptr);
+    };
+    const TensorRef xin = tref(dx.f(), H, ts), ba = tref(da.f(), H, ts), bb = tref(dbb.f(), H, ts), bc = tref(dc.f(), H, ts);
+    const TensorRef zr = tref(dz.f(), 2, ts), cr = tref(dcond.f(), H, ts), y2r = tref(dy2.f(), std::max(TR, 1), ts);
+    auto lw = [&](const DevBytes& p, int i, int per) { return p.f() + (size_t)i * H * per; };
+    TensorRef none, out;  // out: where the block's output lies
+    hipError_t e = hipSuccess;
+    if (r.variant == 3) {
+        // Engine::run_dds_lat: a, b ping-pong; the last layer writes the output buffer (or, with a tail, only y2)
+        TensorRef src;
+        out = d->tail ? none : bc;
+        for (int i = 0; i < NL && e == hipSuccess; ++i) {
+            DdsLatCall c;
+            c.dw_w = lw(ddw_w, i, k), c.dw_b = lw(ddw_b, i, 1), c.g1 = lw(dg1, i, 1), c.b1 = lw(db1, i, 1), c.g2 = lw(dg2, i, 1), c.b2 = lw(db2, i, 1);
+            c.pw = &pw[i].pc;
+            c.lens = dl.p;
+            c.batch = B, c.channels = H, c.tmax = T, c.k = k, c.dil = r.dil[i];
+            c.eps = d->eps;
+            if (i == 0) {
+                if (d->head == 1) c.head_w = dhw.f(), c.head_b = dhb.f(), c.z = zr, c.cond = cr, c.zc = d->zc;
+                else if (d->head == 2) c.head_conv = &hconv.pc, c.x = xin, c.spk = dspk.p;
+                else c.x = xin;
+            } else
+                c.x = src;
+            const TensorRef dst = src.p == ba.p ? bb : ba;
+            if (i == NL - 1 && d->tail) c.tail_conv = &tconv.pc, c.y2 = y2r;
+            else c.y = i == NL - 1 ? bc : dst;
+            e = launch_dds_layer_lat(c, nullptr);
+            src = dst;
+        }
+    } else {
+        // head as its own launch, then Engine::run_dds on (x, y, p) = (cur, ba, bb), then the tail conv
+        TensorRef cur = xin;
+        if (d->head == 1) {
+            cur = bc;
+            e = launch_pointwise_from1(zr, d->zc, dhw.f(), dhb.f(), cr, cur, dl.p, B, H, T, nullptr, arith);
+        } else if (d->head == 2) {
+            cur = bc;
+            e = conv(hconv.pc, xin, cur);
+        }
+        out = cur;
+        if (r.variant == 2) {
+            TensorRef src = cur;
+            for (int i = 0; i < NL && e == hipSuccess; ++i) {
+                // (Engine::run_dds takes this path from two layers on, so that the last layer can write x again; one layer writes y here)
+                const TensorRef dst = NL == 1 ? ba : i == NL - 1 ? cur : (src.p == ba.p ? bb : ba);
+                e = launch_dds_layer(src, dst, lw(ddw_w, i, k), lw(ddw_b, i, 1), lw(dg1, i, 1), lw(db1, i, 1), pw[i].pc, lw(dg2, i, 1), lw(db2, i, 1), dl.p, B, H, T, k, r.dil[i],
+                                     d->eps, arith, nullptr);
+                src = dst;
+            }
+            if (NL == 1) out = ba;
+        } else {
+            for (int i = 0; i < NL && e == hipSuccess; ++i) {
+                e = launch_dds_depthwise(cur, none, lw(ddw_w, i, k), lw(ddw_b, i, 1), lw(dg1, i, 1), lw(db1, i, 1), ba, dl.p, B, H, T, k, r.dil[i], d->eps, nullptr, arith);
+                if (e == hipSuccess) e = conv(pw[i].pc, ba, bb);
+                if (e == hipSuccess) e = launch_add_layer_norm(bb, none, lw(dg2, i, 1), lw(db2, i, 1), none, dl.p, B, H, T, d->eps, 1, cur, nullptr);
+            }
+        }
+        if (e == hipSuccess && d->tail) e = conv(tconv.pc, out, y2r);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_dds_block: ") + r.kernel + ": " + hipGetErrorString(e)).c_str());
+    if (y) {
+        if (out.p) {
+            if (hipMemcpy(y, out.p, (size_t)B * H * ts * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+        } else
+            std::memset(y, 0xFF, (size_t)B * H * ts * 4);
+    }
+    if (d->tail && hipMemcpy(y2, dy2.p, (size_t)B * TR * ts * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_spline(int32_t batch, int32_t t, int32_t t_stride, int32_t bins, float tail, float inv_sqrt, int32_t mode, int32_t zc, const float* u,
+                            float* z, const int32_t* lens) {
+    VITS_TRY
+    using namespace vits;
+    if (!u || !z) return fail("vits_op_spline: null argument");
+    if (batch < 1 || t < 1 || t_stride < t) return fail("vits_op_spline: batch >= 1 and 1 <= t <= t_stride are required");
+    if (bins < 1 || bins > 16) return fail(("vits_op_spline: bins = " + std::to_string(bins) + ": spline_kernel takes 1 to 16 bins").c_str());
+    if (t > 4096) return fail(("vits_op_spline: t = " + std::to_string(t) + ": spline_kernel takes at most 4096 tokens").c_str());
+    if (mode != VITS_MODE_HF && mode != VITS_MODE_REFERENCE) return fail("vits_op_spline: mode is VITS_MODE_HF or VITS_MODE_REFERENCE");
+    if (zc != 0 && zc != 1) return fail("vits_op_spline: zc is latent row 0 or 1");
+    if (!(tail > 0.f)) return fail("vits_op_spline: tail must be positive");
+    if (!split_lens_ok(lens, batch, t, t_stride)) return fail("vits_op_spline: 0 <= lens[b] <= t <= t_stride is required");
+    const int rows = 3 * bins - 1;
+    const size_t nu = (size_t)batch * rows * t_stride, nz = (size_t)batch * 2 * t_stride;
+    std::vector<float> hu(nu);
+    std::memset(hu.data(), 0xFF, nu * 4);
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < rows; ++c)
+            std::memcpy(&hu[((size_t)b * rows + c) * t_stride], u + ((size_t)b * rows + c) * t_stride, sizeof(float) * (size_t)(lens ? lens[b] : t));
+    DevBytes du, dz;
+    DevInts dl;
+    if (!du.put(hu.data(), nu * 4) || !dz.put(z, nz * 4) || !dl.put(lens, batch)) return fail("device allocation failed");
+    hipError_t e = launch_spline(tref(du.f(), rows, t_stride), tref(dz.f(), 2, t_stride), zc, dl.p, batch, t, bins, tail, inv_sqrt, mode, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_spline: ") + hipGetErrorString(e)).c_str());
+    if (hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_durations(int32_t batch, int32_t rows, int32_t row, int32_t t_stride, const float* logw, const int32_t* lens, float length_scale,
+                               const float* length_scales, const int32_t* ovr, int32_t fixed, int32_t n_stage, const int32_t* stage_mul,
+                               const int32_t* stage_add, float* dur, int32_t* cum, int32_t* frames, int32_t* stage_lens) {
+    VITS_TRY
+    using namespace vits;
+    if (!logw || !dur || !cum || !frames) return fail("vits_op_durations: null argument");
+    if (batch < 1 || rows < 1 || row < 0 || row >= rows || t_stride < 1) return fail("vits_op_durations: batch, rows, t_stride >= 1 and 0 <= row < rows are required");
+    if (n_stage < 0 || n_stage > 16 || (n_stage && (!stage_mul || !stage_add || !stage_lens))) return fail("vits_op_durations: 0 to 16 stages, each with a multiplier and an addend");
+    if (!split_lens_ok(lens, batch, t_stride, t_stride)) return fail("vits_op_durations: 0 <= lens[b] <= t_stride is required");
+    const size_t nt = (size_t)batch * t_stride;
+    DevBytes dlogw, dls, dovr, ddur, dcum, dfr, dsl, dmul, dadd;
+    DevInts dl;
+    if (!dlogw.put(logw, nt * rows * 4) || !dl.put(lens, batch) || !ddur.fill(nt * 4, 0xFF) || !dcum.fill(nt * 4, 0xFF) || !dfr.fill((size_t)batch * 4, 0xFF) ||
+        !dsl.fill((size_t)std::max(n_stage, 1) * batch * 4, 0xFF) || (length_scales && !dls.put(length_scales, (size_t)batch * 4)) || (ovr && !dovr.put(ovr, nt * 4)) ||
+        (n_stage && (!dmul.put(stage_mul, (size_t)n_stage * 4) || !dadd.put(stage_add, (size_t)n_stage * 4))))
+        return fail("device allocation failed");
+    hipError_t e = launch_durations(tref(dlogw.f(), rows, t_stride), row, dl.p, batch, t_stride, length_scale, dls.f(), static_cast<const int*>(dovr.p), fixed, ddur.f(),
+                                    static_cast<int*>(dcum.p), static_cast<int*>(dfr.p), static_cast<int*>(dsl.p), n_stage, static_cast<const int*>(dmul.p),
+                                    static_cast<const int*>(dadd.p), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_durations: ") + hipGetErrorString(e)).c_str());
+    if (hipMemcpy(dur, ddur.p, nt * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cum, dcum.p, nt * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(frames, dfr.p, (size_t)batch * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (n_stage && hipMemcpy(stage_lens, dsl.p, (size_t)n_stage * batch * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, int32_t F, const float* m, const float* ls, const float* z, int32_t* durations,
                            float* scores) {
     VITS_TRY

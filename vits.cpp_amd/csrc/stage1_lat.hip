@@ -17,7 +17,8 @@
 //   * TAIL: the layer applies the 1x1 conv that consumes its output (the conv flow's projection H -> 3 bins - 1, vits.cpp:869; the predictor's
 //     H -> H projection, :941) from the output tile in LDS, and only that result goes to memory.
 // Same expressions as the kernels it replaces, statement by statement (hipcc contracts a * b + c the same way in both): the engine takes this path for
-// small grids only (Engine::run_dds, VITS_DDS_LAT_MAX_BLOCKS), and tests/test_gpu_edge_and_scale.py compares the two bit for bit.
+// small grids only (Engine::run_dds, VITS_DDS_LAT_MAX_BLOCKS), and tests/test_gpu_edge_and_scale.py compares the two bit for bit (and the operator-level DDS tests: every
+// head, tail and channel count, through vits_op_dds_block).
 // fp32 arithmetic only (stage one is exact fp32 under the default arithmetic scope; VITS_ARITH_SCOPE_ALL_CONVS with 16-bit operands keeps dds_layer_kernel).
 #include <hip/hip_runtime.h>
 
@@ -229,8 +230,8 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
     __syncthreads();
     // ---- LayerNorm over the channels of a token: 16 channel-group partial sums in ascending channel order, combined in ascending group order ----
     auto layer_norm_stats = [&](float& mean, float& inv) __attribute__((always_inline)) {
-        if (tid < LAT_GROUPS * NT) {
-            const int gq = tid >> 4;
+        // (a 32-channel block has 128 threads, eight groups' worth: the threads that exist walk the 16 groups; from 256 threads on, one group each as before)
+        for (int gq = rr; gq < LAT_GROUPS; gq += rstep) {
             float s = 0.f;
             for (int c = gq; c < H; c += LAT_GROUPS) s += ht[c * NT + tl];
             red[gq * NT + tl] = s;
@@ -240,8 +241,7 @@ __global__ __launch_bounds__(MAXCH * 2 * 64) void dds_layer_lat_kernel(DdsLatPar
 #pragma unroll
         for (int q = 0; q < LAT_GROUPS; ++q) msum += red[q * NT + tl];
         mean = msum / (float)H;
-        if (tid < LAT_GROUPS * NT) {
-            const int gq = tid >> 4;
+        for (int gq = rr; gq < LAT_GROUPS; gq += rstep) {
             float vs = 0.f;
             for (int c = gq; c < H; c += LAT_GROUPS) {
                 const float d = ht[c * NT + tl] - mean;
