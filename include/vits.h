@@ -726,6 +726,48 @@ typedef struct vits_convt1d_desc {
 VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x, const float* w, const float* bias,
                                       const int32_t* lens, float* y);
 
+/* One HiFiGAN upsampler (vits.cpp:178-193, 613-618; kernel = 2 x stride) of the 16-bit modes in the GROUP layout, through the kernel the caller names — what
+ * engine_vocoder.cpp launches per stage and vits_op_conv_transpose1d does not reach (its 16-bit form has standard-layout fp32 outputs: another epilogue). Per
+ * utterance, with L = lens[b], s = stride, x' = round16(leaky_relu(x, pre_slope)), w' = round16(w), x'[-1] = x'[L] = 0:
+ *   n in [0, s L + s - 2 crop):  q = (n + crop) / s,  ph = (n + crop) % s,
+ *   y[co][n] = bias[co] + sum_ci x'[ci][q] w'[ci][co][ph] + x'[ci][q - 1] w'[ci][co][ph + s]   (fp32 accumulation on the matrix cores),
+ *   y16[co][n] = round16(leaky_relu(y[co][n], y16_slope))                                       (the conv input of the stage's ResBlocks).
+ * x: host [batch][cin][t_stride] fp32; w: [cin][cout][2 stride] (torch layout); bias [cout] or NULL; lens optional, 0 <= lens[b] <= t. y: host
+ * [batch][cout][t_out_stride] fp32; y16 (optional): the 16-bit copy as raw bit patterns, same shape; x16 (optional): the converter's output, raw bit patterns
+ * [batch][cin][t_stride]. Columns [0, t_out) of every row of y / y16 with t_out = stride t + stride - 2 crop, and [0, t) of x16, are written back as the device
+ * holds them. With y16 == NULL the kernels get no 16-bit destination (the engine's form for stages of whole-ResBlock kernels).
+ * Arithmetic: vits_op_set_arith, VITS_ARITH_F16 or VITS_ARITH_BF16 only (the fp32 upsampler is vits_op_conv_transpose1d).
+ * variant: 0 the engine's choice as engine_vocoder.cpp writes it: the streaming kernel where convt16_stream_supported, else the GEMM tile; 1 the GEMM tile:
+ * launch_conv16 with the group outputs (conv16_kernel<2, -1, ..., E16_CONVT_GROUP>); 2 launch_convt16_stream (convt16_kernel / convt16_lines_kernel), or -1 with
+ * the failing condition named for a shape plan_convt16 does not take (c_in a multiple of 64 and <= 512, c_out a multiple of 32, stride x c_out <= 128 or stride
+ * a multiple of 4). split: 0 the planner's gridDim.z; 1, 2 or 4 force that many blocks per position tile, lines kernels only — on any other kernel, and for
+ * any other value, a refusal. Variants 1 and 2 never fall back. Neither the variant nor the split depends on an environment knob: the launch policy runs on the
+ * knobs' defaults. Every refusal is made before the first device call.
+ * Staging is the engine's: the 16-bit input buffer [b][cin/8][ts][8] (ts = t rounded up to 32) holds 0xFF bytes (NaN in both types) before the engine's converter
+ * (launch_to_group16 with pre_slope) writes t < lens[b], so a read past an utterance shows in the result; the outputs (fp32 [b][cout/8][g_ts][8], g_ts = t_out
+ * rounded up to 32, and the 16-bit copy) are zero-filled, so a store past len_out[b] = stride lens[b] + stride - 2 crop shows; an utterance with lens[b] = 0
+ * gets no store at all. All variants and splits give the same bits. */
+typedef struct vits_upsample16_desc {
+    int32_t batch, cin, cout, t, t_stride, t_out_stride;
+    int32_t stride, crop;
+    float pre_slope, y16_slope; /* 1.0 = none */
+    int32_t variant, split;
+} vits_upsample16_desc;
+VITS_API int vits_op_upsample16(const vits_upsample16_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y, uint16_t* y16,
+                                uint16_t* x16);
+/* What vits_op_upsample16 would launch for d in the arithmetic of vits_op_set_arith, or -1 and the cause of its refusal. Host arithmetic only: no device call.
+ * kernel: the instantiation as rocprofv3 prints it (convt16_kernel<NR, CSPLIT, RS, BF>, convt16_lines_kernel<BN, BF>, conv16_kernel<2, -1, WM, WN, MR, NR, 4, BF>);
+ * tag: convt16_stream_tag's (what the streaming kernel of this shape would be, also where the GEMM tile runs); bn: input positions per block. */
+typedef struct vits_upsample16_plan {
+    char kernel[96];
+    char tag[16];
+    int32_t variant; /* the variant that runs (1 or 2; what 0 resolved to) */
+    int32_t bn;
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t lds;
+} vits_upsample16_plan;
+VITS_API int vits_op_upsample16_plan(const vits_upsample16_desc* d, vits_upsample16_plan* plan);
+
 /* Relative-position multi-head self-attention core (vits.cpp:296-356):
  * q,k,v [B][H*hd][T] (q already scaled), rel_k/rel_v [2w+1][hd] shared by heads; out [B][H*hd][T]. */
 VITS_API int vits_op_rel_attention(int32_t batch, int32_t heads, int32_t head_dim, int32_t t, int32_t t_stride,

@@ -26,6 +26,7 @@ DP_STOCHASTIC, DP_DETERMINISTIC = 0, 1  # Model.duration_predictor_kind
 DP_VARIANT_PLAN, DP_VARIANT_LAT, DP_VARIANT_WIDE, DP_VARIANT_UNFUSED = 0, 1, 2, 3  # op_duration_predictor
 RB_VARIANT_PLAN, RB_VARIANT_UNFUSED, RB_VARIANT_PAIRS, RB_VARIANT_BLOCK, RB_VARIANT_SEGMENTS = 0, 1, 2, 3, 4  # op_resblock
 FLOW_VARIANT_PLAN, FLOW_VARIANT_UNFUSED, FLOW_VARIANT_WAVENET, FLOW_VARIANT_COUPLING = 0, 1, 2, 3  # op_flow_coupling
+UP16_VARIANT_PLAN, UP16_VARIANT_TILE, UP16_VARIANT_STREAM = 0, 1, 2  # op_upsample16
 DDS_VARIANT_PLAN, DDS_VARIANT_UNFUSED, DDS_VARIANT_LAYER, DDS_VARIANT_LAT = 0, 1, 2, 3  # op_dds_block
 DDS_HEAD_NONE, DDS_HEAD_FROM1, DDS_HEAD_CONV = 0, 1, 2
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
@@ -58,7 +59,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
-    "vits_op_flow_coupling", "vits_op_flow_coupling_plan",
+    "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
@@ -155,6 +156,18 @@ class ConvT1dDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32),
                 ("t_out_stride", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("crop", C.c_int32),
                 ("pre_slope", C.c_float)]
+
+
+class Upsample16Desc(C.Structure):
+    """vits_upsample16_desc"""
+    _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("t_out_stride", C.c_int32),
+                ("stride", C.c_int32), ("crop", C.c_int32), ("pre_slope", C.c_float), ("y16_slope", C.c_float), ("variant", C.c_int32), ("split", C.c_int32)]
+
+
+class Upsample16Plan(C.Structure):
+    """vits_upsample16_plan"""
+    _fields_ = [("kernel", C.c_char * 96), ("tag", C.c_char * 16), ("variant", C.c_int32), ("bn", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
+                ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64)]
 
 
 _lib = None
@@ -348,6 +361,10 @@ def lib():
     L.vits_op_durations.argtypes = [i32, i32, i32, i32, vp, vp, C.c_float, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.vits_op_conv_transpose1d.restype = i32
     L.vits_op_conv_transpose1d.argtypes = [C.POINTER(ConvT1dDesc), vp, vp, vp, vp, vp]
+    L.vits_op_upsample16.restype = i32
+    L.vits_op_upsample16.argtypes = [C.POINTER(Upsample16Desc), vp, vp, vp, vp, vp, vp, vp]
+    L.vits_op_upsample16_plan.restype = i32
+    L.vits_op_upsample16_plan.argtypes = [C.POINTER(Upsample16Desc), C.POINTER(Upsample16Plan)]
     L.vits_op_rel_attention.restype = i32
     L.vits_op_rel_attention.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_add_layer_norm.restype = i32
@@ -1290,6 +1307,54 @@ def op_conv_transpose1d(x, w, bias, stride, crop, pre_slope=1.0, lens=None):
     if lib().vits_op_conv_transpose1d(C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(lens), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
+
+
+def op_upsample16_plan(cin, cout, stride, t, batch=1, crop=0, variant=UP16_VARIANT_PLAN, split=0):
+    """What op_upsample16 would launch in the arithmetic of op_set_arith (vits_op_upsample16_plan; host arithmetic, no GPU needed): a dict with kernel (the
+    instantiation as rocprofv3 prints it), tag (convt16_stream_tag), variant (the one that runs), bn (input positions per block), grid, block, lds — or a
+    VitsError naming the cause of the refusal."""
+    t_out = stride * t + stride - 2 * crop
+    d = Upsample16Desc(batch, cin, cout, t, t, t_out, stride, crop, 0.1, 0.1, variant, split)
+    p = Upsample16Plan()
+    if lib().vits_op_upsample16_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "bn", "block", "lds")}
+    out["kernel"], out["tag"] = p.kernel.decode(), p.tag.decode()
+    out["grid"] = (p.grid_x, p.grid_y, p.grid_z)
+    return out
+
+
+def op_upsample16(x, w, bias, stride, crop, pre_slope=0.1, y16_slope=0.1, variant=UP16_VARIANT_PLAN, split=0, lens=None, want_y16=True, want_x16=False, t=None,
+                  t_out_stride=None):
+    """One HiFiGAN upsampler of the 16-bit modes in the group layout through the kernel `variant` names (vits_op_upsample16): x [B, cin, t_stride]; w [cin, cout,
+    2 stride]; bias [cout] or None; t = the longest utterance (default: t_stride); t_out_stride = row pitch of the outputs (default: t_out = stride t + stride -
+    2 crop). UP16_VARIANT_TILE | _STREAM run that kernel or raise a VitsError naming the cause: never another one; split 1 / 2 / 4 forces the lines kernels' deal
+    over gridDim.z. Returns a dict: y fp32 [B, cout, t_out_stride]; y16 (want_y16) and x16 (want_x16) as uint16 bit patterns [B, cout, t_out_stride] /
+    [B, cin, t_stride]. What was not written back is zero in y / y16 and 0xFFFF in x16. want_y16=False gives the kernel no 16-bit destination."""
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    B, cin, ts = x.shape
+    T = ts if t is None else t
+    if w.ndim != 3 or w.shape[0] != cin or w.shape[2] != 2 * stride:
+        raise VitsError("vits_op_upsample16: w %s is not [c_in = %d][c_out][2 x stride = %d]: the descriptor has no kernel-size field, k = 2 x stride only"
+                        % (list(w.shape), cin, 2 * stride))
+    cout = w.shape[1]
+    t_out = stride * T + stride - 2 * crop
+    tos = t_out if t_out_stride is None else t_out_stride
+    assert bias is None or bias.shape == (cout,)
+    d = Upsample16Desc(B, cin, cout, T, ts, tos, stride, crop, pre_slope, y16_slope, variant, split)
+    y = np.zeros((B, cout, max(tos, 0)), np.float32)
+    y16 = np.zeros((B, cout, max(tos, 0)), np.uint16) if want_y16 else None
+    x16 = np.full((B, cin, ts), 0xFFFF, np.uint16) if want_x16 else None
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    assert lens is None or lens.shape == (B,)
+    if lib().vits_op_upsample16(C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(lens), _ptr(y), _ptr(y16), _ptr(x16)) != 0:
+        raise VitsError(last_error())
+    out = {"y": y}
+    if want_y16:
+        out["y16"] = y16
+    if want_x16:
+        out["x16"] = x16
+    return out
 
 
 def op_align(m, ls, z, T=None, L=None):

@@ -1799,6 +1799,174 @@ VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x
     VITS_CATCH(-1)
 }
 
+// ---- vits_op_upsample16: which kernel a descriptor names (host arithmetic only: launch_plan.h, conv_plan.h), then the engine's Conv16Call on staged tensors ----------
+namespace {
+struct UpOpPlan {
+    int variant = 0, bn = 0, t_out = 0;
+    std::string kernel;
+    char tag[16] = "";
+    vits::LaunchGrid g;
+    vits::PackedConv pc;  // the shape fields; the op adds the device pointers
+};
+bool up_fail(std::string& why, const std::string& m) {
+    why = "vits_op_upsample16: " + m;
+    return false;
+}
+// (runs under the caller's KernelKnobsScope over the knobs' defaults: no environment variable reaches the choice)
+bool upsample16_resolve(const vits_upsample16_desc* d, int arith, UpOpPlan& r, std::string& why) {
+    using namespace vits;
+    if (arith != VITS_ARITH_F16 && arith != VITS_ARITH_BF16)
+        return up_fail(why, "VITS_ARITH_F16 or VITS_ARITH_BF16 only (the fp32 upsampler is vits_op_conv_transpose1d; the split arithmetic has no transposed conv)");
+    const int B = d->batch, cin = d->cin, cout = d->cout, T = d->t, s = d->stride;
+    if (B < 1 || T < 1 || d->t_stride < T) return up_fail(why, "batch >= 1 and 1 <= t <= t_stride are required");
+    if (s < 1) return up_fail(why, "stride = " + std::to_string(s) + ": >= 1 is required (the kernel size is 2 x stride)");
+    if (d->crop < 0 || 2 * d->crop > s) return up_fail(why, "crop = " + std::to_string(d->crop) + ": 0 <= 2 crop <= stride is required");
+    if (cin < 8 || (cin & 7) || cout < 8 || (cout & 7)) return up_fail(why, "c_in = " + std::to_string(cin) + ", c_out = " + std::to_string(cout) + ": the group layout takes multiples of 8");
+    r.t_out = s * T + s - 2 * d->crop;
+    if (d->t_out_stride < r.t_out) return up_fail(why, "t_out_stride = " + std::to_string(d->t_out_stride) + " < t_out = " + std::to_string(r.t_out));
+    if (d->variant < 0 || d->variant > 2) return up_fail(why, "variant " + std::to_string(d->variant) + ": 0 (the engine's choice), 1 (GEMM tile), 2 (streaming kernel)");
+    if (!(d->split == 0 || d->split == 1 || d->split == 2 || d->split == 4)) return up_fail(why, "split = " + std::to_string(d->split) + ": 0 (the planner's), 1, 2 or 4");
+    PackedConv& pc = r.pc;
+    pc.cin = cin, pc.cout = cout, pc.kt = 2, pc.epi = EPI_CONVT, pc.ct_stride = s;
+    const ConvPackDims pd = conv_pack_dims(cout, cin, 2 * s, EPI_CONVT, s);
+    pc.rows = pd.rows, pc.mtiles_used = pd.mtiles_used, pc.mtiles = pd.mtiles, pc.nchunks = pd.nchunks;
+    const bool bf = arith == VITS_ARITH_BF16;
+    const ConvT16Plan policy = plan_convt16(pc, B, T);
+    std::snprintf(r.tag, sizeof(r.tag), "%s", policy.tag);
+    const int v = d->variant ? d->variant : policy.supported ? 2 : 1;  // engine_vocoder.cpp: convt16_stream_supported, else conv16
+    r.variant = v;
+    char name[96];
+    if (v == 2) {
+        const std::string shape = "c_in = " + std::to_string(cin) + ", c_out = " + std::to_string(cout) + ", stride = " + std::to_string(s);
+        if (cin % 64) return up_fail(why, "variant 2: " + shape + ": c_in is not a multiple of 64");
+        if (cout % 32) return up_fail(why, "variant 2: " + shape + ": c_out is not a multiple of 32");
+        if (cin > 512) return up_fail(why, "variant 2: " + shape + ": c_in > 512 (the input tile of all channels does not fit LDS)");
+        if (pc.rows > 128 && s % 4 != 0) return up_fail(why, "variant 2: " + shape + ": rows = stride x c_out = " + std::to_string(pc.rows) + " > 128 and stride is not a multiple of 4");
+        const bool lines = policy.lines_bn != 0;
+        if (d->split && !lines) return up_fail(why, "split = " + std::to_string(d->split) + ": only convt16_lines_kernel deals its units over gridDim.z, this shape runs on convt16_kernel (" + policy.tag + ")");
+        const ConvT16Plan pl = plan_convt16(pc, B, T, d->split);
+        if (!pl.supported || !pl.ok) return up_fail(why, "variant 2: plan_convt16 refuses " + shape);
+        r.g = pl, r.bn = pl.lines_bn ? pl.lines_bn : convt16_bn(pl.nr, pl.csplit);
+        if (lines) std::snprintf(name, sizeof(name), "convt16_lines_kernel<%d, %s>", pl.lines_bn, bf ? "true" : "false");
+        else std::snprintf(name, sizeof(name), "convt16_kernel<%d, %d, %d, %s>", pl.nr, pl.csplit, pl.rs, bf ? "true" : "false");
+        r.kernel = name;
+        return true;
+    }
+    if (d->split) return up_fail(why, "split = " + std::to_string(d->split) + ": only convt16_lines_kernel deals its units over gridDim.z, variant 1 runs conv16_kernel");
+    Conv16Call c;
+    c.batch = B, c.t_in = T, c.t_out = r.t_out, c.ct_crop = d->crop;
+    c.yg = reinterpret_cast<float*>(sizeof(float));  // (never dereferenced: to plan_conv16 a non-null yg means "group outputs")
+    const Conv16Plan pl = plan_conv16(pc, c);
+    if (pl.lat || pl.epi16 != C16_CONVT_GROUP || pl.xwp > 384 || pl.dil_ct == kNoKernel || !conv16_tile_exists(pl.epi16, pl.dil_ct, pl.tile))
+        return up_fail(why, "variant 1: plan_conv16 has no conv16_kernel for this transposed conv");
+    const TileShape ts = tile16_shape(pl.tile);
+    r.bn = ts.bn();
+    r.g.ok = true, r.g.gx = pl.gx, r.g.gy = pl.gy, r.g.gz = pl.gz, r.g.block = 320, r.g.lds = pl.lds;
+    std::snprintf(name, sizeof(name), "conv16_kernel<2, -1, %d, %d, %d, %d, %d, %s>", ts.wm, ts.wn, ts.mr, ts.nr, (int)C16_CONVT_GROUP, bf ? "true" : "false");
+    r.kernel = name;
+    return true;
+}
+}  // namespace
+
+VITS_API int vits_op_upsample16_plan(const vits_upsample16_desc* d, vits_upsample16_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_upsample16_plan: null argument");
+    const vits::KernelKnobs defaults;
+    vits::KernelKnobsScope scope(&defaults);
+    UpOpPlan r;
+    std::string why;
+    if (!upsample16_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", r.kernel.c_str());
+    std::snprintf(out->tag, sizeof(out->tag), "%s", r.tag);
+    out->variant = r.variant, out->bn = r.bn;
+    out->grid_x = r.g.gx, out->grid_y = r.g.gy, out->grid_z = r.g.gz, out->block = r.g.block, out->lds = (int64_t)r.g.lds;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_upsample16(const vits_upsample16_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y, uint16_t* y16,
+                                uint16_t* x16) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !w || !y) return fail("vits_op_upsample16: null argument (x, w and y are required)");
+    const KernelKnobs defaults;
+    KernelKnobsScope scope(&defaults);
+    const int arith = g_op_arith;
+    UpOpPlan r;
+    std::string why;
+    if (!upsample16_resolve(d, arith, r, why)) return fail(why.c_str());
+    const int B = d->batch, cin = d->cin, cout = d->cout, T = d->t, s = d->stride, t_out = r.t_out;
+    for (int b = 0; lens && b < B; ++b)
+        if (lens[b] < 0 || lens[b] > T) return fail("vits_op_upsample16: 0 <= lens[b] <= t is required");
+    // the conv on the device
+    PackedConv& pc = r.pc;
+    DevBytes dw16, db;
+    {
+        const std::vector<uint16_t> p16 = pack_conv_weights16(w, cout, cin, 2 * s, EPI_CONVT, s, arith);
+        if (!dw16.put(p16.data(), p16.size() * 2) || (bias && !db.put(bias, (size_t)cout * 4))) return fail("device allocation failed");
+        pc.wp16 = dw16.h(), pc.bytes16 = (int64_t)p16.size() * 2, pc.bias = bias ? db.f() : nullptr;
+    }
+    // staging, as engine_vocoder.cpp hands a stage to its upsampler
+    const int x_ts = round_up(T, 32), g_ts = round_up(t_out, 32);
+    const size_t nx = (size_t)B * cin * d->t_stride, nx16 = (size_t)B * cin * x_ts, ng = (size_t)B * cout * g_ts;
+    std::vector<int32_t> lo;
+    if (lens) {
+        lo.resize(B);
+        for (int b = 0; b < B; ++b) lo[b] = s * lens[b] + s - 2 * d->crop;
+    }
+    DevInts dl, dlo;
+    DevBytes dx, dx16, dyg, dy16;
+    if (!dl.put(lens, B) || !dlo.put(lens ? lo.data() : nullptr, B) || !dx.put(x, nx * 4) || !dx16.fill(nx16 * 2, 0xFF) || !dyg.fill(ng * 4, 0) || (y16 && !dy16.fill(ng * 2, 0)))
+        return fail("device allocation failed");
+    Conv16Call cu;
+    cu.x.p = dx16.h(), cu.x.ts = x_ts, cu.x.bs = (int64_t)cin * x_ts;
+    cu.len_in = dl.p;
+    cu.len_out = dlo.p;
+    cu.batch = B;
+    cu.t_in = T;
+    cu.t_out = t_out;
+    cu.ct_crop = d->crop;
+    cu.yg = dyg.f();
+    cu.g_bs = (int64_t)cout * g_ts;
+    cu.g_ts = g_ts;
+    if (y16) {
+        cu.y16.p = dy16.h(), cu.y16.ts = g_ts, cu.y16.bs = (int64_t)cout * g_ts;
+        cu.y16_slope = d->y16_slope;
+    }
+    cu.force_split = d->split;
+    hipError_t e = launch_to_group16(tref(dx.f(), cin, d->t_stride), dl.p, B, cin, T, d->pre_slope, cu.x, arith, nullptr);
+    if (e == hipSuccess) e = r.variant == 2 ? launch_convt16_stream(pc, cu, arith, nullptr) : launch_conv16(pc, cu, arith, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_upsample16: ") + r.kernel + ": " + hipGetErrorString(e)).c_str());
+    // group layout [b][c / 8][ts][8] -> [b][c][stride]
+    {
+        std::vector<float> hg(ng);
+        if (hipMemcpy(hg.data(), dyg.p, ng * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < cout; ++c) {
+                const float* g = &hg[(size_t)b * cout * g_ts + (size_t)(c / 8) * g_ts * 8 + (c & 7)];
+                float* dst = y + ((size_t)b * cout + c) * d->t_out_stride;
+                for (int n = 0; n < t_out; ++n) dst[n] = g[(size_t)n * 8];
+            }
+    }
+    auto ungroup16 = [&](const DevBytes& m, int C, int ts, int cols, int stride, uint16_t* out) {
+        std::vector<uint16_t> h((size_t)B * C * ts);
+        if (hipMemcpy(h.data(), m.p, h.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < C; ++c) {
+                const uint16_t* g = &h[(size_t)b * C * ts + (size_t)(c / 8) * ts * 8 + (c & 7)];
+                uint16_t* dst = out + ((size_t)b * C + c) * stride;
+                for (int n = 0; n < cols; ++n) dst[n] = g[(size_t)n * 8];
+            }
+        return true;
+    };
+    if (y16 && !ungroup16(dy16, cout, g_ts, t_out, d->t_out_stride, y16)) return fail("copy back failed");
+    if (x16 && !ungroup16(dx16, cin, x_ts, T, d->t_stride, x16)) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_rel_attention(int32_t batch, int32_t heads, int32_t head_dim, int32_t t, int32_t t_stride, int32_t window, const float* q, const float* k,
                                    const float* v, const float* rel_k, const float* rel_v, const int32_t* lens, float* out) {
     VITS_TRY

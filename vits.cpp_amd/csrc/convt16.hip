@@ -16,7 +16,7 @@
 //                        apart: the half-written lines left L2 before they were complete and the layer ran at 1.3 TB/s, slower than
 //                        the GEMM tile; with whole lines 0.41 against 0.53 ms per step for the two stride-8 upsamplers.
 // Same A fragments, same k-order (chunk, tap, k-half), same epilogue (kernel_common.h: group_store) as conv16_kernel<2, -1, ..., E16_CONVT_GROUP>:
-// bit-identical (GPU test); VITS_NO_CONVT16S=1 keeps the GEMM-tile path, VITS_NO_CONVT16L=1 only for the stride-8 layers.
+// bit-identical (tests/test_gpu_upsample_ops.py: every instantiation against the tile at operator level); VITS_NO_CONVT16S=1 keeps the GEMM-tile path, VITS_NO_CONVT16L=1 only for the stride-8 layers.
 // Batch 64 x 128 ids, f16: the four upsamplers 1.05 -> 0.79 ms per step; config 5 (bf16): 79.8 -> 76.8 ms.
 #include <hip/hip_runtime.h>
 
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void convt16_lines_kernel(const ConvT16Para
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 hipError_t launch_convt16_stream(const PackedConv& w, const Conv16Call& c, int arith, hipStream_t s) {
-    const ConvT16Plan l = plan_convt16(w, c.batch, c.t_in);
+    const ConvT16Plan l = plan_convt16(w, c.batch, c.t_in, c.force_split);
     if (!l.ok || !w.wp16 || !c.yg) return hipErrorInvalidValue;
     ConvT16Params p;
     p.x = c.x.p, p.x_bs = c.x.bs, p.x_ts = c.x.ts, p.wp = w.wp16, p.bias = w.bias, p.len_in = c.len_in, p.len_out = c.len_out, p.t_in = c.t_in;

@@ -339,6 +339,7 @@ struct Conv16Call {
     Ref16 y16;
     float y16_slope = 1.f;  // leaky_relu fused into the 16-bit copy (1 = none)
     int64_t sum_in = -1, sum_out = -1;  // profiler accounting (see ConvCall)
+    int force_split = 0;  // launch_convt16_stream, lines kernels: 1, 2 or 4 = the units of a position tile over that many blocks whatever the grid (vits_op_upsample16); 0: the planner's choice
 };
 // One HiFiGAN ResBlock conv pair as a single kernel (rbpair16.hip): y' = y + conv2(leaky_relu(conv1(x) + b1)) + b2 with x =
 // the 16-bit leaky_relu(y); the intermediate stays in LDS. C = 32 / 64, k = 3 / 7 / 11, conv1 dilation 1 / 3 / 5.

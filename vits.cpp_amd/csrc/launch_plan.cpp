@@ -108,7 +108,7 @@ RbBlock32Plan plan_rbblock32(int C, int kt, int batch, int tmax) {
 // 64 when c_in = 512 (LDS for two blocks per CU). convt16_kernel<NR, CSPLIT, RS>: 128 positions per block; 64 when the input tile of 128
 // would not leave room for two blocks per CU (c_in = 512); 256 positions with two waves per row tile when there are only two row tiles (the
 // last upsampler: 64 rows); sixteen ring slots where the step count allows.
-ConvT16Plan plan_convt16(const PackedConv& w, int batch, int t_in) {
+ConvT16Plan plan_convt16(const PackedConv& w, int batch, int t_in, int force_split) {
     const KernelKnobs& kn = kernel_knobs();
     ConvT16Plan p;
     // the choice and its tag, for any transposed conv (convt16_stream_tag answers whether or not the streaming kernel is taken)
@@ -134,7 +134,10 @@ ConvT16Plan plan_convt16(const PackedConv& w, int batch, int t_in) {
     if (!convt16_exists(p.lines_bn, p.nr, p.csplit, p.rs)) return p;  // (an override that names no instantiation: the launch is refused)
     const int bn = p.lines_bn ? p.lines_bn : convt16_bn(p.nr, p.csplit), tiles_x = blocks_for(t_in + 1, bn);
     int zsplit = 1;
-    if (p.lines_bn && (int64_t)tiles_x * batch <= kn.convt16_split_max) {
+    if (force_split) {  // the caller names the deal (vits_op_upsample16): no knob, no grid rule
+        if (!p.lines_bn || !(force_split == 1 || force_split == 2 || force_split == 4)) return p;
+        zsplit = force_split;
+    } else if (p.lines_bn && (int64_t)tiles_x * batch <= kn.convt16_split_max) {
         const int nunits = (w.cout >> 5) * (w.ct_stride / 4) * (bn / 64);
         zsplit = nunits >= 16 ? 4 : nunits >= 8 ? 2 : 1;
     }

@@ -188,7 +188,9 @@ struct ConvT16Plan : LaunchGrid {
     int lines_bn = 0, nr = 0, csplit = 0, rs = 0;
     char tag[16] = "";
 };
-ConvT16Plan plan_convt16(const PackedConv& w, int batch, int t_in);
+// force_split 1, 2 or 4: the lines kernels deal their units over that many blocks whatever the grid and VITS_CONVT16_SPLIT_MAX say (vits_op_upsample16), or a refusal
+// (ok false) on a kernel that has no such deal; 0: the policy
+ConvT16Plan plan_convt16(const PackedConv& w, int batch, int t_in, int force_split = 0);
 // one WaveNet layer of the flow (fp32: ncw 0); `ok` is the shape part of wavenet32_supported / wavenet16_supported
 struct WaveNetPlan : LaunchGrid {
     int ncw = 0;
