@@ -346,7 +346,8 @@ VITS_API int vits_model_align_batch(vits_model* model,
 VITS_API int64_t vits_model_align(vits_model* model, const float* pcm, size_t n, const char* text, int32_t speaker,
                                   int32_t* ids, int32_t* durations, size_t cap);
 /* Samples per frame (the product of the vocoder's upsample rates = the STFT hop): token t of an alignment starts at
- * sum(durations[0 .. t)) * hop / sampling_rate seconds. */
+ * sum(durations[0 .. t)) * hop / sampling_rate seconds. In audio delivered with vits_model_set_edges on, token t of durations_out starts at
+ * (sum(d[0 .. t)) * hop - a + Pl) / sampling_rate seconds, a from vits_model_last_edges and Pl = samples(lead_ms) from vits_edges_plan. */
 VITS_API int32_t vits_model_hop(const vits_model* model);
 
 /* ---- any sample rate: a device resampler on both sides of the model -----------------------------------------------------------
@@ -493,6 +494,72 @@ VITS_API int64_t vits_model_last_limits(vits_model* model, float* dst, size_t ca
  * (optional); 0, or -1 + message (a refused rate or value, pcm NULL with n > 0). */
 VITS_API int vits_limiter_plan(int32_t rate, int32_t* A, int32_t* H, int32_t* tile);
 VITS_API int vits_limiter_host(const float* pcm, size_t n, int32_t rate, double g0, double ceiling_db, double* y, double limits[4]);
+
+/* ---- stated edges: trimmed silence, pauses and fades, on the device ---------------------------------------------------------------------
+ * A VITS vocoder delivers frames x hop samples, whatever is in them: the leading and trailing blank tokens of a model come out as near-silence
+ * of arbitrary length. vits_model_set_edges states where the delivered audio begins and ends: the near-silence at both ends is trimmed (or
+ * kept, VITS_EDGES_PAD), both ends are faded, and digital silence of a stated length is put in front and behind. It is a stage of the delivery
+ * tail, in front of levelling (vocoder -> edges -> measure / multiply / limiter -> resampler), so what is measured is what is delivered. It has
+ * no atomics and every sum has one shape, so batch rows, pipelined and split batches, vocoder windows and a device buffer give the same bits, in
+ * every VITS_ARITH_* mode. With VITS_EDGES_OFF (the default) nothing is queued or allocated and every bit, length and vits_model_weight_bytes is
+ * what it was.
+ *
+ * The definition. Model-rate row x[0, N) at rate fs in [4000, 192000]; integer divisions truncate.
+ *   samples(ms) = (int64) floor((double) ms * fs / 1000 + 0.5): Kh, Kt, Fi, Fo, Pl, Pt of the six durations of the desc, in field order
+ *   W = (fs + 50) / 100   10 ms. Window i covers [i W, min((i + 1) W, N)), i < n_win = ceil(N / W): the partial last window counts, over its own
+ *     samples. q_i = the mean of x^2 over window i in fp64 (a square of an fp32 value is exact in fp64). The association of the sum is the
+ *     implementation's; it is fixed per window and depends on nothing outside the window (not on the batch row, not on a tile).
+ *   f = 10^(threshold_db / 10), computed once in double on the host. T = q_max f (one fp64 multiply; q_max = the largest q_i that is not a NaN, 0
+ *     if there is none) under VITS_EDGES_TRIM_RELATIVE, T = f under VITS_EDGES_TRIM_ABSOLUTE (relative to a mean square of 1).
+ *   Window i is active iff q_i >= T and q_i > 0 (a NaN compares false); n_active counts them; i_first and i_last are the first and the last.
+ *   a = max(0, i_first W - Kh), b = min(N, (i_last + 1) W + Kt); with no active window a = b = 0. Under VITS_EDGES_PAD a = 0, b = N, nothing is
+ *     measured and n_active = 0. M = b - a.
+ *   win[k] = 0.5 - 0.5 cos(pi (k + 0.5) / Fi), k < Fi, and wout[k] likewise with Fo: computed in double on the host, rounded once to fp32.
+ *   The delivered row has N' = Pl + M + Pt samples: y[j] = +0 for j < Pl and for j >= Pl + M; y[Pl + k] = (x[a + k] * wi) * wo, two fp32
+ *     multiplies, wi = win[k] if k < Fi, else 1; wo = wout[M - 1 - k] if M - 1 - k < Fo, else 1. A multiply by 1 is exact: a row that nothing
+ *     touches is x bit for bit. Fades longer than M simply overlap; nothing is rescaled.
+ *   The bound of a row is N + Pl + Pt >= N': [N', bound) is written as zero, nothing is written behind the bound.
+ * Which threshold separates speech from a model's near-silence has not been judged on real speech: the project's fixtures are synthetic.
+ *
+ * vits_model_set_edges: NULL or mode VITS_EDGES_OFF switches the stage off. 0, or -1 + message with the handle unchanged: a struct_size that is
+ * not sizeof(vits_edges_desc), an unknown mode, a value that is not finite or outside its range (threshold_db is not looked at under
+ * VITS_EDGES_PAD), batches in flight, a call from inside on_chunk ("model busy"). vits_model_get_edges: the desc as it was set (mode
+ * VITS_EDGES_OFF and zeros when off).
+ * With the stage on: lengths[b] is N'_b (passed through vits_resample_length when an output rate is set), read from the device after the call's
+ * own synchronisation or at vits_model_wait; stride and the out_device_stride check use the bound N_max + Pl + Pt (at the output rate when one
+ * is set), which the host knows before the call; frames[] and durations_out are unchanged. frames_only reports lengths[] for the bound: exact
+ * under VITS_EDGES_PAD, an upper bound under the TRIM modes: the size to allocate. Levelling, the limiter and the resampler read the trimmed
+ * row: vits_model_last_levels and _last_limits describe it. Taps: "waveform" is unchanged, "waveform_edges" [1][N'] is the output of the stage,
+ * "waveform_level" and "waveform_out" follow it. Voice conversion delivers through the stage; alignment is unaffected. vocoder_chunk_frames
+ * without on_chunk works: the stage runs behind the last window. REFUSED with the stage on, with the reason: on_chunk (the end of the utterance
+ * decides what leaves) and async (the lengths need a host read).
+ * In the delivered audio token t of durations_out starts at (sum(d[0 .. t)) * hop - a + Pl) / fs seconds (see vits_model_hop).
+ *
+ * vits_model_last_edges: the rows int64 [B][4] = {a, b, N', n_active} of the most recently completed call, with the conventions of
+ * vits_model_last_levels: returns 4 B (dst is filled when cap >= 4 B), or 0 when that call ran with the stage off. The device rows and the fade
+ * tables are counted in vits_model_weight_bytes once allocated (by the first call that runs the stage). */
+#define VITS_EDGES_OFF 0
+#define VITS_EDGES_PAD 1
+#define VITS_EDGES_TRIM_RELATIVE 2
+#define VITS_EDGES_TRIM_ABSOLUTE 3
+typedef struct vits_edges_desc {
+    uint32_t struct_size;
+    int32_t mode;                     /* VITS_EDGES_OFF 0 | _PAD 1 | _TRIM_RELATIVE 2 | _TRIM_ABSOLUTE 3 */
+    float threshold_db;               /* [-120, 0]: relative to the loudest window (RELATIVE) or to mean square 1 (ABSOLUTE); ignored by PAD */
+    float keep_head_ms, keep_tail_ms; /* [0, 2000]: original signal kept in front of the first / behind the last active window */
+    float fade_in_ms, fade_out_ms;    /* [0, 2000] */
+    float lead_ms, tail_ms;           /* [0, 2000]: digital silence put in front / behind */
+} vits_edges_desc;
+VITS_API int vits_model_set_edges(vits_model* model, const vits_edges_desc* desc);
+VITS_API int vits_model_get_edges(const vits_model* model, vits_edges_desc* desc);
+VITS_API int64_t vits_model_last_edges(vits_model* model, int64_t* dst, size_t cap);
+/* Host only, no device needed. vits_edges_plan: out = {W, Kh, Kt, Fi, Fo, Pl, Pt, the time tile of the device's window kernel (a multiple of W)}
+ * at a rate in [4000, 192000]; 0, or -1 + message (what vits_model_set_edges refuses about the desc; mode VITS_EDGES_OFF is accepted here).
+ * vits_edges_host: the definition above evaluated sequentially on n samples at `rate`, with the same two fp32 multiplies, so y is comparable bit
+ * for bit with the device's: y (optional, y_cap floats, y_cap >= n + Pl + Pt) gets the delivered row and zeros up to the bound, row =
+ * {a, b, N', n_active}; 0, or -1 + message (a refused desc or rate, mode VITS_EDGES_OFF, pcm NULL with n > 0, a y_cap below the bound). */
+VITS_API int vits_edges_plan(int32_t rate, const vits_edges_desc* desc, int64_t out[8]);
+VITS_API int vits_edges_host(const float* pcm, size_t n, int32_t rate, const vits_edges_desc* desc, float* y, size_t y_cap, int64_t row[4]);
 
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
@@ -899,6 +966,15 @@ typedef struct vits_limit_desc {
     int32_t mode; /* VITS_LIMIT_TRUE_PEAK */
 } vits_limit_desc;
 VITS_API int vits_op_limit(const vits_limit_desc* d, const float* x, const int64_t* lens, float* y, float* levels, float* limits);
+
+/* The edges stage (see vits_model_set_edges for the definition) on a ragged batch that is ON THE DEVICE already: every pointer is a device
+ * pointer. x [batch][x_stride] at `rate`; lens [batch] int32, 0 <= lens[b] <= x_stride: nothing behind a row's samples is read; y
+ * [batch][y_stride], not x: row b gets its lens[b] + Pl + Pt samples (the delivered row, then zeros up to that bound), everything behind them
+ * is left as it was; lens_out [batch]: N' of every row; rows [batch][4] = {a, b, N', n_active}. Runs on the default stream and returns after
+ * hipDeviceSynchronize, as vits_op_level does. Refused (-1 + message): what vits_edges_plan refuses, mode VITS_EDGES_OFF, a NULL pointer, an
+ * empty batch, a lens[b] outside [0, x_stride] or above 2^30, a y_stride below the largest bound. */
+VITS_API int vits_op_edges(int32_t rate, const vits_edges_desc* desc, int32_t batch, const float* x, int64_t x_stride, const int32_t* lens, float* y,
+                           int64_t y_stride, int32_t* lens_out, int64_t* rows);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

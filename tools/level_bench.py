@@ -2,8 +2,10 @@
 benchmark configuration (batch 64 x 128 ids) and batch 1 x 128 ids, without a level and under VITS_LEVEL_LOUDNESS (-23 LUFS, ceiling -1 dB). ms per call
 (wall clock around the call), median of interleaved rounds; a profiled pass gives the levelling kernels' own time per call (level_measure: the four
 measuring launches as one span; level_scale: the multiply) and their share of the call's kernel time. --limit adds the same call with the true-peak
-limiter on (vits_model_set_limiter, limiter.hip; "limit": its launches as one span, in place of the multiply). Prints one JSON line.
-usage: python tools/level_bench.py [--rounds 5] [--steps 4] [--ids 128] [--limit]"""
+limiter on (vits_model_set_limiter, limiter.hip; "limit": its launches as one span, in place of the multiply). --edges adds the call without a level and
+with the edges stage on (vits_model_set_edges, edges.hip: TRIM_RELATIVE -40 dB, 20 ms kept, 5 ms fades, 50 ms and 150 ms of silence; edges_window, edges_bounds
+and edges_apply one span each). Prints one JSON line.
+usage: python tools/level_bench.py [--rounds 5] [--steps 4] [--ids 128] [--limit] [--edges]"""
 import argparse
 import json
 import os
@@ -22,20 +24,25 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--ids", type=int, default=128)
     ap.add_argument("--limit", action="store_true", help="also time VITS_LEVEL_LOUDNESS with VITS_LIMIT_TRUE_PEAK")
+    ap.add_argument("--edges", action="store_true", help="also time VITS_LEVEL_NONE with the edges stage on (VITS_EDGES_TRIM_RELATIVE)")
     a = ap.parse_args()
     pkg = load_package()
     import torch
     m = pkg.Model(pkg.synth_model_bytes(0x5EED, pkg.SYNTH_FULL))
-    kinds = (("none", pkg.LEVEL_NONE), ("loudness", pkg.LEVEL_LOUDNESS)) + ((("limit", pkg.LEVEL_LOUDNESS),) if a.limit else ())
+    kinds = (("none", pkg.LEVEL_NONE), ("loudness", pkg.LEVEL_LOUDNESS)) + ((("limit", pkg.LEVEL_LOUDNESS),) if a.limit else ()) + ((("edges", pkg.LEVEL_NONE),) if a.edges else ())
+    edges = dict(mode=pkg.EDGES_TRIM_RELATIVE, threshold_db=-40.0, keep_head_ms=20.0, keep_tail_ms=20.0, fade_in_ms=5.0, fade_out_ms=5.0, lead_ms=50.0, tail_ms=150.0) if a.edges else None
+    pads = sum(pkg.edges_plan(m.sampling_rate, **edges)[5:7]) if a.edges else 0  # (the stage's rows are checked against N + Pl + Pt)
     res = {}
     for batch in (64, 1):
         ids = pkg.synth_ids(batch, a.ids)
         m.set_level(pkg.LEVEL_NONE)
-        stride = int(m.process_batch(ids, noise_seed=5, frames_only=True)[1].max()) + 64
+        stride = int(m.process_batch(ids, noise_seed=5, frames_only=True)[1].max()) + 64 + pads
         out_dev = torch.empty(batch * stride, dtype=torch.float32, device="cuda")
 
         def call(kind, name):
             m.set_limiter(pkg.LIMIT_TRUE_PEAK if name == "limit" else pkg.LIMIT_OFF)
+            if a.edges:
+                m.set_edges(**(edges if name == "edges" else dict(mode=pkg.EDGES_OFF)))
             m.set_level(kind, -23.0, -1.0)
             return m.process_batch(ids, noise_seed=5, out_device=out_dev.data_ptr(), out_device_stride=stride, skip_host_copy=True, keep_pcm=False)
 
@@ -59,14 +66,15 @@ def main():
             m.prof_enable(False)
             ks = rep["kernels"]
             tot = sum(x["ms"] for x in ks) or 1.0
-            lv = {x["name"]: x for x in ks if x["name"].startswith("level_") or x["name"] == "limit"}
+            lv = {x["name"]: x for x in ks if x["name"].startswith(("level_", "edges_")) or x["name"] == "limit"}
             lms = sum(x["ms"] for x in lv.values())
             ms = float(np.median(times[n]))
             res["b%d_%s" % (batch, n)] = {
                 "ms_per_call": round(ms, 4), "vs_no_level": round(ms / base, 4), "samples": int(lengths.sum()), "kernel_ms": round(tot, 4),
                 "level_us": {name: round(1e3 * x["ms"], 2) for name, x in lv.items()}, "level_share_of_kernel_time": round(lms / tot, 5),
                 "levels_row0": None if m.last_levels() is None else [float(v) for v in m.last_levels()[0]],
-                "limits_row0": None if m.last_limits() is None else [float(v) for v in m.last_limits()[0]], "rounds_ms": [round(t, 4) for t in times[n]]}
+                "limits_row0": None if m.last_limits() is None else [float(v) for v in m.last_limits()[0]],
+                **({"edges_row0": None if m.last_edges() is None else [int(v) for v in m.last_edges()[0]]} if a.edges else {}), "rounds_ms": [round(t, 4) for t in times[n]]}
         del out_dev
     m.close()
     print(json.dumps({"tool": "level_bench", "model": "FULL synthetic", "arith": "f32", "ids": a.ids, "results": res}))

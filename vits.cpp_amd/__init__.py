@@ -34,6 +34,8 @@ ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
 # vits_model_set_limiter: the levelling kinds that multiply deliver through the true-peak meter and the look-ahead limiter
 LIMIT_OFF, LIMIT_TRUE_PEAK = 0, 1
+# vits_model_set_edges: where the delivered audio begins and ends (trimmed near-silence, fades, pauses of digital silence)
+EDGES_OFF, EDGES_PAD, EDGES_TRIM_RELATIVE, EDGES_TRIM_ABSOLUTE = 0, 1, 2, 3
 SCOPE_FLOW_VOCODER, SCOPE_ALL_CONVS = 0, 1
 
 #: every symbol include/vits.h declares (checked by tests/test_abi.py)
@@ -58,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_rates", "vits_model_get_rates", "vits_resample_plan", "vits_resample_taps", "vits_resample_length", "vits_op_resample",
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
+    "vits_model_set_edges", "vits_model_get_edges", "vits_model_last_edges", "vits_edges_plan", "vits_edges_host", "vits_op_edges",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
@@ -82,6 +85,18 @@ class LevelDesc(C.Structure):
 class LimitDesc(C.Structure):
     """vits_limit_desc"""
     _fields_ = [("level", LevelDesc), ("mode", C.c_int32)]
+
+
+class EdgesDesc(C.Structure):
+    """vits_edges_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("threshold_db", C.c_float), ("keep_head_ms", C.c_float), ("keep_tail_ms", C.c_float),
+                ("fade_in_ms", C.c_float), ("fade_out_ms", C.c_float), ("lead_ms", C.c_float), ("tail_ms", C.c_float)]
+
+
+def edges_desc(mode=EDGES_OFF, threshold_db=0.0, keep_head_ms=0.0, keep_tail_ms=0.0, fade_in_ms=0.0, fade_out_ms=0.0, lead_ms=0.0, tail_ms=0.0):
+    """a filled vits_edges_desc"""
+    return EdgesDesc(C.sizeof(EdgesDesc), int(mode), float(threshold_db), float(keep_head_ms), float(keep_tail_ms), float(fade_in_ms), float(fade_out_ms),
+                     float(lead_ms), float(tail_ms))
 
 
 class ProcessOpts(C.Structure):
@@ -309,6 +324,18 @@ def lib():
     L.vits_limiter_host.argtypes = [vp, sz, i32, C.c_double, C.c_double, vp, vp]
     L.vits_op_limit.restype = i32
     L.vits_op_limit.argtypes = [C.POINTER(LimitDesc), vp, vp, vp, vp, vp]
+    L.vits_model_set_edges.restype = i32
+    L.vits_model_set_edges.argtypes = [vp, C.POINTER(EdgesDesc)]
+    L.vits_model_get_edges.restype = i32
+    L.vits_model_get_edges.argtypes = [vp, C.POINTER(EdgesDesc)]
+    L.vits_model_last_edges.restype = i64
+    L.vits_model_last_edges.argtypes = [vp, vp, sz]
+    L.vits_edges_plan.restype = i32
+    L.vits_edges_plan.argtypes = [i32, C.POINTER(EdgesDesc), vp]
+    L.vits_edges_host.restype = i32
+    L.vits_edges_host.argtypes = [vp, sz, i32, C.POINTER(EdgesDesc), vp, sz, vp]
+    L.vits_op_edges.restype = i32
+    L.vits_op_edges.argtypes = [i32, C.POINTER(EdgesDesc), i32, vp, i64, vp, vp, i64, vp, vp]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -800,6 +827,35 @@ class Model:
             return None
         out = np.zeros((n // 4, 4), np.float32)
         if lib().vits_model_last_limits(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
+
+    # -- stated edges (vits_model_set_edges): trimmed silence, fades and pauses in front of levelling ------------------------------------------------
+    @property
+    def edges(self):
+        """the handle's vits_edges_desc as a dict (mode EDGES_OFF and zeros when the stage is off)"""
+        d = EdgesDesc()
+        if lib().vits_model_get_edges(self._h, C.byref(d)) != 0:
+            raise VitsError(last_error())
+        return {name: getattr(d, name) for name, _ in EdgesDesc._fields_ if name != "struct_size"}
+
+    def set_edges(self, mode=EDGES_OFF, **fields):
+        """vits_model_set_edges: EDGES_OFF (nothing is queued), EDGES_PAD (fades and pads only), EDGES_TRIM_RELATIVE / _ABSOLUTE (the near-silence at both
+        ends is trimmed first: threshold_db relative to the loudest 10 ms window, or to mean square 1). Fields: threshold_db, keep_head_ms, keep_tail_ms,
+        fade_in_ms, fade_out_ms, lead_ms, tail_ms. lengths of every result are then the trimmed, padded ones; last_edges() reads where each row was cut."""
+        d = edges_desc(mode, **fields)
+        if lib().vits_model_set_edges(self._h, C.byref(d)) != 0:
+            raise VitsError(last_error())
+
+    def last_edges(self):
+        """vits_model_last_edges: int64 [B, 4] = (a, b, N', n_active) of the most recently completed call, or None when it ran with EDGES_OFF"""
+        n = lib().vits_model_last_edges(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n // 4, 4), np.int64)
+        if lib().vits_model_last_edges(self._h, _ptr(out), out.size) != n:
             raise VitsError(last_error())
         return out
 
@@ -1506,6 +1562,85 @@ def limit(x, rate, kind=LEVEL_GAIN, value_db=0.0, ceiling_db=0.0, lens=None, out
     if lib().vits_op_limit(C.byref(d), _ptr(x), _ptr(ln), _ptr(out), _ptr(levels), _ptr(limits)) != 0:
         raise VitsError(last_error())
     return out, levels, limits
+
+
+def edges_plan(rate, mode=EDGES_PAD, **fields):
+    """vits_edges_plan: (W, Kh, Kt, Fi, Fo, Pl, Pt, tile) in samples at `rate` for a desc given as in Model.set_edges (host only)"""
+    d = edges_desc(mode, **fields)
+    out = np.zeros(8, np.int64)
+    if lib().vits_edges_plan(int(rate), C.byref(d), _ptr(out)) != 0:
+        raise VitsError(last_error())
+    return tuple(int(v) for v in out)
+
+
+def edges_host(pcm, rate, mode=EDGES_PAD, **fields):
+    """vits_edges_host: (y float32 [N'], row int64 [4] = a, b, N', n_active, tail float32: what was written behind N' up to the bound) of one row, the
+    definition of include/vits.h evaluated sequentially on the host (no device needed)"""
+    x = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
+    d = edges_desc(mode, **fields)
+    plan = np.zeros(8, np.int64)
+    if lib().vits_edges_plan(int(rate), C.byref(d), _ptr(plan)) != 0:
+        raise VitsError(last_error())
+    y, row = np.full(x.size + int(plan[5]) + int(plan[6]) + 1, np.nan, np.float32), np.zeros(4, np.int64)
+    if lib().vits_edges_host(_ptr(x), x.size, int(rate), C.byref(d), _ptr(y), y.size - 1, _ptr(row)) != 0:
+        raise VitsError(last_error())
+    assert np.isnan(y[-1])  # (nothing behind the bound)
+    return y[:row[2]].copy(), row, y[row[2]:-1].copy()
+
+
+_HIP = None
+
+
+def _hip():
+    """the HIP runtime the library is linked against, for the operator entry points that take device pointers"""
+    global _HIP
+    if _HIP is None:
+        h = C.CDLL("libamdhip64.so")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipFree.argtypes = [C.c_void_p]
+        _HIP = h
+    return _HIP
+
+
+def edges(x, rate, mode=EDGES_PAD, lens=None, out=None, **fields):
+    """The edges kernels on a ragged batch (vits_op_edges, which takes device pointers: the rows are staged here through the HIP runtime). x: float32
+    [B, x_stride] (or one 1-D row) at `rate`, uploaded as it is (what lies behind a row's samples included); lens: samples per row (None = the whole row);
+    out: float32 [B, y_stride] uploaded as the initial contents of y (None = zeros of the largest bound). Returns (y [B, y_stride], lens_out int32 [B],
+    rows int64 [B, 4] = a, b, N', n_active)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32).ravel()
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    d = edges_desc(mode, **fields)
+    if out is None:
+        plan = np.zeros(8, np.int64)
+        if lib().vits_edges_plan(int(rate), C.byref(d), _ptr(plan)) != 0:
+            raise VitsError(last_error())
+        out = np.zeros((B, max(int(ln.max()) + int(plan[5]) + int(plan[6]), 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    lens_out, rows = np.full(B, -1, np.int32), np.full((B, 4), -1, np.int64)
+    hip = _hip()
+    host = (x if x.size else np.zeros((B, 1), np.float32), ln, out, lens_out, rows)
+    dev = [C.c_void_p() for _ in host]
+    try:
+        for p, a in zip(dev, host):
+            if hip.hipMalloc(C.byref(p), max(a.nbytes, 4)) != 0 or hip.hipMemcpy(p, _ptr(a), a.nbytes, 1) != 0:
+                raise VitsError("staging a batch for vits_op_edges: hipMalloc / hipMemcpy failed")
+        if lib().vits_op_edges(int(rate), C.byref(d), B, dev[0], max(stride, 1), dev[1], dev[2], out.shape[1], dev[3], dev[4]) != 0:
+            raise VitsError(last_error())
+        for p, a in zip(dev[2:], host[2:]):
+            if hip.hipMemcpy(_ptr(a), p, a.nbytes, 2) != 0:
+                raise VitsError("reading the results of vits_op_edges: hipMemcpy failed")
+    finally:
+        for p in dev:
+            if p.value:
+                hip.hipFree(p)
+    return out, lens_out, rows
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

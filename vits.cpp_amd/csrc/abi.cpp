@@ -704,6 +704,87 @@ VITS_API int vits_limiter_host(const float* pcm, size_t n, int32_t rate, double 
     return 0;
     VITS_CATCH(-1)
 }
+// ---- stated edges (include/vits.h: the definition) -----------------------------------------------------------------------------------------
+VITS_API int vits_model_set_edges(vits_model* model, const vits_edges_desc* desc) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER_IDLE(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_edges(desc, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_get_edges(const vits_model* model, vits_edges_desc* desc) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (desc) *desc = model->eng.edges_desc();
+    return 0;
+}
+VITS_API int64_t vits_model_last_edges(vits_model* model, int64_t* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const int64_t* p = model->eng.last_edges(rows);
+    const size_t n = (size_t)4 * rows;
+    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(int64_t) * n);
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_edges_plan(int32_t rate, const vits_edges_desc* desc, int64_t out[8]) {
+    VITS_TRY
+    vits::EdgesPlan p;
+    std::string err;
+    if (!desc) {
+        set_err("vits_edges_plan: null argument");
+        return -1;
+    }
+    if (!vits::edges_plan(rate, *desc, p, err)) {
+        set_err("vits_edges_plan: " + err);
+        return -1;
+    }
+    if (out) {
+        const int64_t v[8] = {p.W, p.Kh, p.Kt, p.Fi, p.Fo, p.Pl, p.Pt, p.tile};
+        std::memcpy(out, v, sizeof(v));
+    }
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_edges_host(const float* pcm, size_t n, int32_t rate, const vits_edges_desc* desc, float* y, size_t y_cap, int64_t row[4]) {
+    VITS_TRY
+    vits::EdgesPlan p;
+    std::string err;
+    if (!desc || (!pcm && n)) {
+        set_err("vits_edges_host: null argument (desc, or pcm with n > 0)");
+        return -1;
+    }
+    if (!vits::edges_plan(rate, *desc, p, err)) {
+        set_err("vits_edges_host: " + err);
+        return -1;
+    }
+    if (p.mode == VITS_EDGES_OFF) {
+        set_err("vits_edges_host: VITS_EDGES_OFF delivers the row as it is: there is nothing to evaluate");
+        return -1;
+    }
+    if (n > (size_t)vits::kEdgesMaxLen) {
+        set_err("vits_edges_host: the row is too long (" + std::to_string(n) + " samples)");
+        return -1;
+    }
+    if (y && y_cap < (size_t)p.bound((int64_t)n)) {
+        set_err("vits_edges_host: y_cap = " + std::to_string(y_cap) + " is below the row's bound n + Pl + Pt = " + std::to_string(p.bound((int64_t)n)));
+        return -1;
+    }
+    const std::vector<float> fades = vits::edges_fades(p);
+    vits::edges_host(pcm, (int64_t)n, p, fades.data(), y, row);
+    return 0;
+    VITS_CATCH(-1)
+}
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }
@@ -2649,6 +2730,55 @@ VITS_API int vits_op_limit(const vits_limit_desc* ld, const float* x, const int6
     if (hipMemcpy(levels, dlv.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(limits, dlm.p, (size_t)B * 4 * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(y, dy.p, (size_t)B * d->y_stride * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_edges(int32_t rate, const vits_edges_desc* desc, int32_t batch, const float* x, int64_t x_stride, const int32_t* lens, float* y, int64_t y_stride,
+                           int32_t* lens_out, int64_t* rows) {
+    VITS_TRY
+    using namespace vits;
+    if (!desc || !x || !lens || !y || !lens_out || !rows || batch <= 0 || x_stride <= 0 || y_stride <= 0) return fail("vits_op_edges: null argument or empty batch");
+    EdgesPlan plan;
+    std::string err;
+    if (!edges_plan(rate, *desc, plan, err)) return fail(("vits_op_edges: " + err).c_str());
+    if (plan.mode == VITS_EDGES_OFF) return fail("vits_op_edges: VITS_EDGES_OFF delivers the rows as they are: there is nothing to run");
+    if (batch > 65535) return fail("vits_op_edges: more than 65535 rows");
+    if (x == y) return fail("vits_op_edges: y must not be x");
+    // (the one host read: the grids, the scratch and the y_stride check need the longest row)
+    std::vector<int32_t> n((size_t)batch);
+    if (hipMemcpy(n.data(), lens, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost) != hipSuccess) return fail("vits_op_edges: reading lens from the device failed");
+    int64_t longest = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (n[b] < 0 || n[b] > x_stride)
+            return fail(("vits_op_edges: lens[" + std::to_string(b) + "] = " + std::to_string(n[b]) + " is outside [0, x_stride = " + std::to_string(x_stride) + "]").c_str());
+        if (n[b] > kEdgesMaxLen) return fail(("vits_op_edges: row " + std::to_string(b) + " is too long (" + std::to_string(n[b]) + " samples)").c_str());
+        longest = std::max<int64_t>(longest, n[b]);
+    }
+    if (y_stride < plan.bound(longest))
+        return fail(("vits_op_edges: y_stride = " + std::to_string(y_stride) + " is below the largest bound (" + std::to_string(longest) + " samples + Pl + Pt = " +
+                     std::to_string(plan.bound(longest)) + ")").c_str());
+    const std::vector<float> fades = edges_fades(plan);
+    DevBuf dscr, df;
+    if (!dscr.put(nullptr, (edges_scratch_bytes(batch, longest, plan.W) + 3) / 4) || (!fades.empty() && !df.put(fades.data(), fades.size()))) return fail("device allocation failed");
+    EdgesCall c;
+    c.x = x;
+    c.x_stride = x_stride;
+    c.lens = lens;
+    c.y = y;
+    c.y_stride = y_stride;
+    c.batch = batch;
+    c.max_len = longest;
+    c.plan = plan;
+    c.fades = df.p;
+    c.scratch = dscr.p;
+    c.lens_out = lens_out;
+    c.rows = rows;
+    hipError_t e = launch_edges_window(c, nullptr);
+    if (e == hipSuccess) e = launch_edges_bounds(c, nullptr);
+    if (e == hipSuccess) e = launch_edges_apply(c, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
     VITS_CATCH(-1)
 }

@@ -305,9 +305,9 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
     LevelCall lc;
     lc.x = c.wave_dst;
     lc.x_stride = c.wave_stride;
-    lc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    lc.lens = c.mr_lens;
     lc.batch = B;
-    lc.max_len = c.smax[n_up];
+    lc.max_len = c.mr_max;
     lc.plan = level_plan_;
     lc.scratch = c.s2.lvl_scratch;
     lc.kind = c.lev;
@@ -332,7 +332,7 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
         mc.y_stride = dst_stride;
         mc.lens = lc.lens;
         mc.batch = B;
-        mc.max_len = c.smax[n_up];
+        mc.max_len = c.mr_max;
         mc.plan = limit_plan_;
         mc.taps = up->taps;
         mc.scratch = c.s2.lim_scratch;
@@ -359,7 +359,7 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
         sc.lens = lc.lens;
         sc.levels = lv_rows_;
         sc.batch = B;
-        sc.max_range = c.smax[n_up];
+        sc.max_range = c.mr_max;
         prof.begin("level_scale", (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
         e = launch_level_scale(sc, stream);
         prof.end(stream);
@@ -370,6 +370,132 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
     HIP_OK(hipMemcpyAsync(host.p, lv_rows_, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
     prof.fence();
     return 0;
+}
+
+int Engine::set_edges(const vits_edges_desc* d, std::string& err) {
+    const vits_edges_desc off{(uint32_t)sizeof(vits_edges_desc), VITS_EDGES_OFF, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (!d || (d->struct_size == sizeof(vits_edges_desc) && d->mode == VITS_EDGES_OFF)) {
+        edges_desc_ = off;
+        return 0;
+    }
+    EdgesPlan p;
+    std::string why;
+    if (!edges_plan(hp.sampling_rate, *d, p, why)) {
+        err = "vits_model_set_edges: " + why;
+        return -1;
+    }
+    ed_fades_stale_ = ed_fades_stale_ || p.Fi != edges_plan_.Fi || p.Fo != edges_plan_.Fo;  // (the tables depend on the two counts alone)
+    edges_plan_ = p;
+    edges_desc_ = *d;
+    if (p.mode == VITS_EDGES_PAD) edges_desc_.threshold_db = 0.f;  // (ignored, and not kept)
+    return 0;
+}
+
+int Engine::check_edges(const vits_process_opts& o, std::string& err) const {
+    if (!edges_on()) return 0;
+    if (o.on_chunk) {
+        err = "on_chunk streams an utterance while it is being made, and this handle's edges stage (vits_model_set_edges) is on: the end of the utterance decides "
+              "what leaves (the last active window, the fade-out and the silence behind it count from there), so no sample can leave before the last one is made: "
+              "stream with VITS_EDGES_OFF, or set edges without on_chunk";
+        return -1;
+    }
+    if (o.async) {
+        err = "async returns before the device has finished, and this handle's edges stage (vits_model_set_edges) is on: lengths[] of the result is read from the "
+              "device (the trimmed length depends on the audio), which needs a host read behind the call's work: call without async, or pipeline with "
+              "vits_model_submit_batch / vits_model_wait";
+        return -1;
+    }
+    return 0;
+}
+
+// the edges stage of a call: the vocoder's waveform c.s2.wave -> dst (the call's own buffer, or out_device when nothing follows), the trimmed lengths and
+// the rows on the device, and the rows on their way to the slot's pinned copy. From here on c.mr_lens is the stage's
+int Engine::run_edges(Call& c, float* dst, int64_t dst_stride) {
+    std::string& err = c.err;
+    const int B = c.B, n_up = c.n_up;
+    const EdgesPlan& p = edges_plan_;
+    if (B > ed_cap_) {
+        // (grow-only, as grow_rows: int64 [cap][4], then int32 [cap])
+        const int cap = std::max(B, 64);
+        const size_t per_row = sizeof(int64_t) * 4 + sizeof(int);
+        int64_t* fresh = nullptr;
+        HIP_OK(hipMalloc((void**)&fresh, per_row * (size_t)cap));
+        if (ed_rows_) {
+            for (void*& q : owned_)
+                if (q == ed_rows_) q = fresh;
+            hipFree(ed_rows_);
+        } else owned_.push_back(fresh);
+        weight_bytes += (int64_t)per_row * (cap - ed_cap_);
+        ed_rows_ = fresh, ed_cap_ = cap;
+    }
+    if (ed_fades_stale_) {
+        const std::vector<float> t = edges_fades(p);
+        if (ed_fades_) {
+            // (the previous desc's tables: nothing reads them any more once the device is idle, and hipFree waits for that)
+            owned_.erase(std::remove(owned_.begin(), owned_.end(), (void*)ed_fades_), owned_.end());
+            hipFree(ed_fades_);
+            weight_bytes -= (int64_t)ed_fades_n_ * 4;
+            ed_fades_ = nullptr, ed_fades_n_ = 0;
+        }
+        if (!t.empty()) {
+            if (!(ed_fades_ = upload(t))) {
+                err = "fade tables: device allocation failed";
+                return -1;
+            }
+            ed_fades_n_ = t.size();
+        }
+        ed_fades_stale_ = false;
+    }
+    EdgesCall ec;
+    ec.x = c.s2.wave;
+    ec.x_stride = c.S_stride;
+    ec.lens = c.s1.stage_lens + (size_t)n_up * B;
+    ec.y = dst;
+    ec.y_stride = dst_stride;
+    ec.batch = B;
+    ec.max_len = c.smax[n_up];
+    ec.plan = p;
+    ec.fades = ed_fades_;
+    ec.scratch = c.s2.ed_scratch;
+    ec.lens_out = reinterpret_cast<int*>(ed_rows_ + (size_t)4 * ed_cap_);
+    ec.rows = ed_rows_;
+    const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
+    hipError_t e = hipSuccess;
+    if (p.mode != VITS_EDGES_PAD) {
+        // one multiply-add per sample in fp64; the samples read once, one double per window written
+        prof.begin("edges_window", 2.0 * (double)samples, 4.0 * (double)samples + 8.0 * (double)samples / p.W, stream, /*chain=*/true);
+        e = launch_edges_window(ec, stream);
+        prof.end(stream);
+        HIP_OK(e);
+    }
+    prof.begin("edges_bounds", 0, 8.0 * (double)samples / p.W, stream, /*chain=*/true);
+    e = launch_edges_bounds(ec, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    // two multiplies per sample; the samples read once, the bound written once
+    prof.begin("edges_apply", 2.0 * (double)samples, 8.0 * (double)samples + 4.0 * (double)B * (p.Pl + p.Pt), stream, /*chain=*/true);
+    e = launch_edges_apply(ec, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    PinnedBuf<int64_t>& host = ed_host_[a1_slot_ & 1];
+    HIP_OK(host.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
+    HIP_OK(hipMemcpyAsync(host.p, ed_rows_, sizeof(int64_t) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    prof.fence();
+    c.mr_lens = ec.lens_out;
+    return 0;
+}
+
+void Engine::edges_lengths(const int64_t* rows, int B, int64_t* lengths) const {
+    ResamplePlan plan;  // (the identity without an output rate)
+    std::string ignored;
+    if (output_rate_) resample_plan(hp.sampling_rate, output_rate_, plan, ignored);  // (accepted by set_rates already)
+    for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(rows[(size_t)4 * b + 2]);
+}
+
+void Engine::keep_edges(const int64_t* rows, int B, bool append) {
+    if (!append) last_ed_store_.clear();
+    last_ed_store_.insert(last_ed_store_.end(), rows, rows + (size_t)4 * B);
+    last_ed_rows_ = (int)(last_ed_store_.size() / 4);
 }
 
 int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const {
@@ -408,8 +534,10 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
     if (check_level(o, err)) return -1;
+    if (check_edges(o, err)) return -1;
     last_lv_rows_ = 0;
     last_lm_rows_ = 0;
+    last_ed_rows_ = 0;
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -485,6 +613,13 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
         last_lm_ = last_lm_store_.data();
         last_lm_rows_ = (int)(last_lm_store_.size() / 4);
     }
+    if (!rc && part[0]->ed_rows + part[1]->ed_rows > 0)
+        for (int h = 0; h < 2; ++h) {
+            // (the trimmed lengths of a part are known now that its rows have landed)
+            const int64_t* rows = ed_host_[(wait_seq_ + h) & 1].p;
+            edges_lengths(rows, part[h]->ed_rows, part[h]->lengths.data());
+            keep_edges(rows, part[h]->ed_rows, /*append=*/h > 0);
+        }
     if (!rc && out) {
         const size_t stride = std::max(part[0]->stride, part[1]->stride);
         out->batch = (size_t)B;
@@ -551,6 +686,13 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
     }
     Pending& p = pend_[wait_seq_ & 1];
     HIP_OK(hipEventSynchronize(p.done));
+    last_ed_rows_ = 0;
+    if (p.ed_rows) {
+        // stated edges: the batch's lengths are its trimmed ones, on the host now that `done` has passed (copied: the slot's pinned rows are the next submit's)
+        const int64_t* rows = ed_host_[wait_seq_ & 1].p;
+        edges_lengths(rows, p.ed_rows, p.lengths.data());
+        keep_edges(rows, p.ed_rows);
+    }
     if (out) {
         // (the slot is released only once the result has been handed over: an allocation failure below leaves the batch waitable)
         out->batch = (size_t)p.B;
@@ -739,12 +881,14 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
             // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
             ResamplePlan plan;
             if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
-            out->stride = (size_t)plan.out_len(c.smax[n_up]);
+            // (stated edges: the bound N + Pl + Pt of every utterance, the size to allocate: exact under VITS_EDGES_PAD, an upper bound when the stage trims)
+            const int64_t pads = edges_on() ? edges_plan_.Pl + edges_plan_.Pt : 0;
+            out->stride = (size_t)plan.out_len(c.smax[n_up] + pads);
             out->lengths = new int64_t[B];
             out->frames = new int64_t[B];
             out->data = nullptr;
             for (int b = 0; b < B; ++b) {
-                out->lengths[b] = plan.out_len(c.slen[n_up][b]);
+                out->lengths[b] = plan.out_len(c.slen[n_up][b] + pads);
                 out->frames[b] = frames[b];
             }
         }
@@ -782,13 +926,28 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     // caller cannot know in advance, or collect_taps — streams as ONE window: the sink gets each utterance in a single call)
     for (const Call::Win& w : wins) c.Lw_max = std::max(c.Lw_max, w.hi - w.lo);
     const int M = c.M = c.smul[n_up];  // samples per frame
+    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
+    // (on_chunk and async with it on were refused by process_batch / convert_batch, before stage one was queued)
+    const bool ed = c.ed = edges_on();
+    c.mr_len = c.slen[n_up];
+    if (ed)
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = edges_plan_.bound(c.slen[n_up][b]);
+            if (n > (int64_t)INT32_MAX - 64) {
+                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
+                return -1;
+            }
+            c.mr_len[b] = (int)n;
+        }
+    c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
+    c.mr_lens = c.s1.stage_lens + (size_t)n_up * B;  // (device; run_edges swaps its own in)
     if (output_rate_) {
         // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and
         // resample.hip writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities
         if (!(c.rate_out = rate_table(hp.sampling_rate, output_rate_, err))) return -1;
         c.out_len.resize(B);
         for (int b = 0; b < B; ++b) {
-            const int64_t n = c.rate_out->plan.out_len(c.slen[n_up][b]);
+            const int64_t n = c.rate_out->plan.out_len(c.mr_len[b]);
             if (n > (int64_t)INT32_MAX - 64) {
                 err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples at the output rate: too long";
                 return -1;
@@ -822,31 +981,35 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     c.wave_dst = c.s2.wave;
     c.wave_stride = c.S_stride;
     // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
-    const std::vector<int>& pcm_len = rs ? c.out_len : c.slen[n_up];
-    const int pcm_max = rs ? c.out_max : smax[n_up];
+    // (stated edges: the bounds; the lengths proper are read from the stage's rows where the results are filled)
+    const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
+    const int pcm_max = rs ? c.out_max : c.mr_max;
     if (o.out_device) {
         if (o.out_device_stride < pcm_max) {
             err = "out_device_stride is smaller than the longest utterance";
             if (rs) err += " (" + std::to_string(pcm_max) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
             return -1;
         }
-        if (!rs && !la) {
+        if (!rs && !la && !ed) {
             c.wave_dst = (float*)o.out_device;
             c.wave_stride = o.out_device_stride;
         }
     }
+    // the stage's output: delivered as it is (straight to out_device), or what levelling / the resampler read
+    float* const ed_dst = !ed ? nullptr : (!rs && !la && o.out_device) ? (float*)o.out_device : c.s2.wave_edge;
+    const int64_t ed_stride = !ed ? 0 : (!rs && !la && o.out_device) ? o.out_device_stride : (int64_t)c.E_stride;
     float* const wave_dst = c.wave_dst;
     const int64_t wave_stride = c.wave_stride;
     // the levelled model-rate waveform: delivered as it is (straight to out_device), or the resampler's input
     float* const lvl_dst = !la ? nullptr : (!rs && o.out_device) ? (float*)o.out_device : c.s2.wave_lvl;
-    const int64_t lvl_stride = !la ? 0 : (!rs && o.out_device) ? o.out_device_stride : (int64_t)c.S_stride;
-    float* const pcm_dst = rs ? (o.out_device ? (float*)o.out_device : c.s2.wave_out) : la ? lvl_dst : wave_dst;
-    const int64_t pcm_stride = rs ? (o.out_device ? o.out_device_stride : (int64_t)c.out_ws) : la ? lvl_stride : wave_stride;
+    const int64_t lvl_stride = !la ? 0 : (!rs && o.out_device) ? o.out_device_stride : (int64_t)c.E_stride;
+    float* const pcm_dst = rs ? (o.out_device ? (float*)o.out_device : c.s2.wave_out) : la ? lvl_dst : ed ? ed_dst : wave_dst;
+    const int64_t pcm_stride = rs ? (o.out_device ? o.out_device_stride : (int64_t)c.out_ws) : la ? lvl_stride : ed ? ed_stride : wave_stride;
     ResampleCall rsc;
     if (rs) {
-        rsc.x = la ? lvl_dst : c.s2.wave;
-        rsc.x_stride = c.S_stride;
-        rsc.lens = c.s1.stage_lens + (size_t)n_up * B;  // (device: every utterance's samples at the model's rate)
+        rsc.x = la ? lvl_dst : ed ? ed_dst : c.s2.wave;
+        rsc.x_stride = c.E_stride;
+        rsc.lens = c.mr_lens;  // (device: every utterance's samples at the model's rate; run_edges swaps the trimmed ones in below)
         rsc.y = pcm_dst;
         rsc.y_stride = pcm_stride;
         rsc.taps = c.rate_out->taps;
@@ -1047,14 +1210,40 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             snapshot("waveform", w.wv, 1, w.smax[n_up], B, c.slen[n_up]);
         }
     }
+    // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
+    std::vector<int> tap_len = c.slen[n_up], tap_out_len = c.out_len;
+    int tap_max = smax[n_up], tap_out_max = c.out_max;
+    if (ed) {
+        if (run_edges(c, ed_dst, ed_stride)) return -1;
+        c.wave_dst = ed_dst;  // (what run_level measures and multiplies)
+        c.wave_stride = ed_stride;
+        rsc.lens = c.mr_lens;
+        if (o.collect_taps) {
+            // (a tap carries its rows' lengths: this debugging path reads the trimmed ones here, the call proper at its own synchronisation)
+            HIP_OK(hipStreamSynchronize(stream));
+            prof.fence();
+            const int64_t* rows = ed_host_[a1_slot_ & 1].p;
+            tap_max = tap_out_max = 0;
+            for (int b = 0; b < B; ++b) {
+                tap_len[b] = (int)rows[(size_t)4 * b + 2];
+                tap_max = std::max(tap_max, tap_len[b]);
+                if (rs) tap_out_max = std::max(tap_out_max, tap_out_len[b] = (int)c.rate_out->plan.out_len(tap_len[b]));
+            }
+            TensorRef t;
+            t.p = ed_dst;
+            t.bs = ed_stride;
+            t.cs = (int)t.bs;
+            snapshot("waveform_edges", t, 1, tap_max, B, tap_len);
+        }
+    }
     if (c.lev) {
         if (run_level(c, lvl_dst, lvl_stride)) return -1;
         if (o.collect_taps) {
             TensorRef t;
-            t.p = la ? lvl_dst : wave_dst;
-            t.bs = la ? lvl_stride : wave_stride;
+            t.p = la ? lvl_dst : c.wave_dst;
+            t.bs = la ? lvl_stride : c.wave_stride;
             t.cs = (int)t.bs;
-            snapshot("waveform_level", t, 1, smax[n_up], B, c.slen[n_up]);
+            snapshot("waveform_level", t, 1, tap_max, B, tap_len);
         }
     }
     if (rs && !o.on_chunk) {
@@ -1067,7 +1256,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         t.p = pcm_dst;
         t.bs = pcm_stride;
         t.cs = (int)pcm_stride;
-        snapshot("waveform_out", t, 1, c.out_max, B, c.out_len);
+        snapshot("waveform_out", t, 1, tap_out_max, B, tap_out_len);
     }
     if (o.on_chunk)
         if (int rc = deliver(wins.size() - 1)) {
@@ -1091,6 +1280,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         }
         pend->lv_rows = c.lev ? B : 0;
         pend->lm_rows = c.lim ? B : 0;
+        pend->ed_rows = ed ? B : 0;  // (lengths: the bounds until vits_model_wait reads the rows)
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -1134,6 +1324,12 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         if (c.lim) {
             last_lm_store_.assign(last_lm_, last_lm_ + (size_t)4 * B);
             last_lm_ = last_lm_store_.data();
+        }
+        if (ed) {
+            // the trimmed lengths have landed with the rows: what the call reports
+            const int64_t* rows = ed_host_[a1_slot_ & 1].p;
+            if (out) edges_lengths(rows, B, out->lengths);
+            keep_edges(rows, B);
         }
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)

@@ -304,6 +304,16 @@ class Engine {
         rows = last_lm_rows_;
         return last_lm_;
     }
+    // stated edges (include/vits.h vits_model_set_edges; edges.hip): with a mode set, what the vocoder made is trimmed, faded and padded in front of
+    // levelling. NULL or VITS_EDGES_OFF switches the stage off. 0, or -1 + a message with the handle unchanged (what edges_plan refuses). Nothing touches
+    // the device here: the fade tables and the row buffer are allocated by the first call that runs the stage.
+    int set_edges(const vits_edges_desc* d, std::string& err);
+    const vits_edges_desc& edges_desc() const { return edges_desc_; }
+    // the rows [B][4] = {a, b, N', n_active} of the most recently completed call (empty: it ran with the stage off)
+    const int64_t* last_edges(int& rows) const {
+        rows = last_ed_rows_;
+        return last_ed_store_.data();
+    }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -422,6 +432,7 @@ class Engine {
         PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
         int lv_rows = 0;              // levelling: rows of lv_host_[slot] this batch fills (0: no level was set)
         int lm_rows = 0;              // the limiter: rows of lm_host_[slot] this batch fills (0: it was off)
+        int ed_rows = 0;              // stated edges: rows of ed_host_[slot] this batch fills (0: off); `lengths` is derived from them once `done` has passed
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -513,6 +524,27 @@ class Engine {
     std::vector<float> last_lm_store_;
     // a device row buffer [cap][4] of the handle grown to at least B rows (owned_, counted in weight_bytes)
     int grow_rows(float*& rows, int& cap, int B, std::string& err);
+    // stated edges: the handle's desc (VITS_EDGES_OFF and zeros when off), its plan at the model's rate, the fade tables on the device (uploaded by the first
+    // call that needs them, and again after a set_edges that changed them), the device rows: int64 [ed_cap_][4], then the trimmed lengths int32 [ed_cap_]
+    // (owned_, counted in weight_bytes), and the rows' pinned copies, one per pipeline slot
+    vits_edges_desc edges_desc_{(uint32_t)sizeof(vits_edges_desc), VITS_EDGES_OFF, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    EdgesPlan edges_plan_;
+    float* ed_fades_ = nullptr;
+    size_t ed_fades_n_ = 0;
+    bool ed_fades_stale_ = false;
+    int64_t* ed_rows_ = nullptr;
+    int ed_cap_ = 0;
+    PinnedBuf<int64_t> ed_host_[2];
+    int last_ed_rows_ = 0;
+    std::vector<int64_t> last_ed_store_;
+    bool edges_on() const { return edges_desc_.mode != VITS_EDGES_OFF; }
+    int check_edges(const vits_process_opts& o, std::string& err) const;  // the refusals of on_chunk and async with the stage on
+    // the stage on c.s2.wave into dst (engine.cpp): queued behind the last vocoder window, in front of run_level; c.mr_lens / c.mr_max are its output's from here on
+    int run_edges(Call& c, float* dst, int64_t dst_stride);
+    // what a call delivers per utterance once its rows [B][4] have landed: N', or its length at the output rate
+    void edges_lengths(const int64_t* rows, int B, int64_t* lengths) const;
+    // the rows of a finished call -> last_ed_store_ (appended when `append`)
+    void keep_edges(const int64_t* rows, int B, bool append = false);
     // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
     hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 

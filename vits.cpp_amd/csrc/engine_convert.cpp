@@ -265,8 +265,10 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
             if (check_speaker(s, who, err)) return -1;
         }
     if (check_level(o, err)) return -1;
+    if (check_edges(o, err)) return -1;
     last_lv_rows_ = 0;
     last_lm_rows_ = 0;
+    last_ed_rows_ = 0;
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
     std::vector<int64_t> n_model;

@@ -208,6 +208,8 @@ struct Call {
         float* wave_lvl;    // a level that multiplies (VITS_LEVEL_GAIN ..), unless it goes straight to out_device: the levelled waveform [B][S_stride]
         void* lvl_scratch;  // a level set: level_scratch_bytes of loudness.hip
         void* lim_scratch;  // the limiter on: limit_scratch_bytes of limiter.hip
+        float* wave_edge;   // stated edges on, unless the stage writes straight to out_device: its output [B][E_stride]
+        void* ed_scratch;   // stated edges on: edges_scratch_bytes of edges.hip
         int* lvl_ranges;    // VITS_LEVEL_GAIN, streaming: [window][2][B]: the model-rate samples [j0, j1) of each utterance that window w finalises
     } s2{};
     int ls = 0, lws = 0, S_stride = 0;
@@ -225,6 +227,14 @@ struct Call {
     int lev = 0;
     bool lev_apply = false;
     bool lim = false;  // the limiter is on and the kind multiplies: limiter.hip delivers in place of the plain multiply
+    // stated edges (Engine::set_edges): the stage runs between the vocoder and levelling. What levelling, the limiter and the resampler read is then its output:
+    // E_stride = the row stride of the model-rate buffers behind the vocoder's own (S_stride with the stage off), mr_lens = the device lengths [B] of those rows
+    // (the stage's N'; the vocoder's sample counts with it off), mr_len / mr_max = what the host knows of them (under the stage: the bounds N + Pl + Pt)
+    bool ed = false;
+    int E_stride = 0;
+    const int* mr_lens = nullptr;
+    std::vector<int> mr_len;
+    int mr_max = 0;
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
 };

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+struct vits_edges_desc;  // include/vits.h
+
 namespace vits {
 
 // Tuning knobs of the launch functions: which tile shape / kernel variant a launch takes. None of them changes a bit of a result (GPU test:
@@ -758,6 +760,50 @@ struct LimitCall {
 };
 // meter(x), g0 and TP per row, then the limiter (GAIN, LOUDNESS) or the plain multiply (PEAK), then meter(y) and the rows
 hipError_t launch_limit(const LimitCall& c, hipStream_t s);
+
+// ---- stated edges: trimmed silence, pauses and fades (edges.hip; the definition: include/vits.h vits_model_set_edges, DESIGN.md §8 "Stated edges") ----
+// Windows of W = (rate + 50) / 100 samples anchored at the row's sample 0; q_i = the mean of x^2 over window i in fp64; a window is active iff q_i >= T and
+// q_i > 0 (T = q_max f or f, f = 10^(threshold_db / 10)); [a, b) = the first to the last active window widened by the keep margins; the delivered row is
+// Pl zeros, x[a, b) under the two fade tables, Pt zeros. The sum of a window is ONE shape: lane l of a wave adds the squares of the window's samples l,
+// l + 64, .. in ascending order, then the 64 partial sums meet in a butterfly (xor 32, 16, .. 1). It depends on the window's own samples and count alone.
+constexpr int kEdgesTileTarget = 4096;  // samples of a row per block of edges_window_kernel: the largest multiple of W at or under it
+constexpr int kEdgesApplyTile = 1024;   // delivered samples per block of edges_apply_kernel
+constexpr int64_t kEdgesMaxLen = (int64_t)1 << 30;
+struct EdgesPlan {
+    int rate = 0, mode = 0;  // VITS_EDGES_*
+    int W = 0;               // (rate + 50) / 100: 10 ms
+    int64_t Kh = 0, Kt = 0, Fi = 0, Fo = 0, Pl = 0, Pt = 0;  // samples(ms) of the desc's six durations, in field order
+    int tile = 0;    // (kEdgesTileTarget / W) W
+    double f = 1.0;  // 10^(threshold_db / 10), computed once on the host
+    int64_t bound(int64_t n) const { return n + Pl + Pt; }
+};
+// host only (edges_host.cpp). false + a message: a rate outside [4000, 192000], a wrong struct_size, an unknown mode, a value that is not finite or out of range
+bool edges_plan(int rate, const ::vits_edges_desc& d, EdgesPlan& p, std::string& err);
+// the two fade tables, win[Fi] then wout[Fo]: 0.5 - 0.5 cos(pi (k + 0.5) / F) in double, rounded once to fp32
+std::vector<float> edges_fades(const EdgesPlan& p);
+// the definition, sequentially. y (optional, at least p.bound(n) floats) gets the delivered row and zeros up to the bound; row = {a, b, N', n_active}
+void edges_host(const float* pcm, int64_t n, const EdgesPlan& p, const float* fades, float* y, int64_t row[4]);
+// bytes of device scratch: q [batch][ceil(max_len / W)] doubles
+size_t edges_scratch_bytes(int batch, int64_t max_len, int W);
+struct EdgesCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;  // device [batch]: valid samples of each row; nothing behind them is read
+    float* y = nullptr;         // device [batch][y_stride], not x: row b gets plan.bound(lens[b]) samples, the rest is left as it was
+    int64_t y_stride = 0;
+    int batch = 0;
+    int64_t max_len = 0;  // the longest row (host side: sizes the grids and the scratch); y_stride >= plan.bound(max_len)
+    EdgesPlan plan;
+    const float* fades = nullptr;  // device [Fi + Fo]: edges_fades (null when both are 0)
+    void* scratch = nullptr;       // device, edges_scratch_bytes(batch, max_len, plan.W), 8-byte aligned (unused under VITS_EDGES_PAD)
+    int* lens_out = nullptr;       // device [batch]: N' of each row
+    int64_t* rows = nullptr;       // device [batch][4]: a, b, N', n_active
+};
+// the three passes, in this order on one stream: q of every window (not under VITS_EDGES_PAD) | one block per row: q_max, T, the first and the last active
+// window, the rows | the shifted copy with the fades, the pads and the zeros up to the bound
+hipError_t launch_edges_window(const EdgesCall& c, hipStream_t s);
+hipError_t launch_edges_bounds(const EdgesCall& c, hipStream_t s);
+hipError_t launch_edges_apply(const EdgesCall& c, hipStream_t s);
 
 }  // namespace vits
 
