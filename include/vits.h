@@ -846,6 +846,85 @@ VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, 
                                     const float* x, const float* residual, const float* gamma, const float* beta,
                                     float* y);
 
+/* The same attention core through the kernel the caller names, with everything the text encoder's call passes: q is multiplied by q_scale on load, and exp_tab
+ * (optional, NULL = expf) is ggml's 65536-entry fp16 exponential table, indexed by the fp16 bits of the argument, as vits_model_set_ggml_tables builds it; with
+ * it the soft-max sums in double. q, k, v, out: host [batch][heads * head_dim][t_stride] fp32; rel_k, rel_v [2 window + 1][head_dim]; lens optional,
+ * 0 <= lens[b] <= t <= t_stride. The device rows have the pitch t_stride as given: a pitch that is no multiple of 4 takes the matrix-core kernel's scalar V loads.
+ * variant: 0 the planner's choice; 1 rel_attention_kernel<1024>; 2 rel_attention_kernel<256>; 3 rel_attention_mfma_kernel<4, 32, false, false>; 4 <8, 32, false,
+ * false>; 5 <4, 24, true, false> (the short-sequence variant); 6 <8, 24, false, true> (the latency variant). Every kernel's loops run over the utterance's own
+ * length and every block works for itself, so variants 5 and 6 are launchable at any length and grid. Variants 1-6 never fall back: a shape no instantiation can run
+ * (head_dim above 128; variants 3-6: head_dim no multiple of 16; variants 5 and 6: head_dim above 96; the block's LDS beyond the limit) returns -1 with the cause in
+ * vits_last_error. Neither the variant nor anything else depends on an environment knob: the launch policy runs on the knobs' defaults. Every refusal is made before
+ * the first device call.
+ * Staging: q, k and v hold 0xFF bytes (NaN) behind lens[b] before the valid part goes in, so a read past an utterance shows in the result; out is staged as 0xFF
+ * bytes and comes back, all of [batch][heads * head_dim][t_stride], as the device holds it. Variants 3-6 give the same bits as each other, 1 and 2 as each other. */
+typedef struct vits_attention_desc {
+    int32_t batch, heads, head_dim, t, t_stride, window;
+    float q_scale;
+    int32_t variant;
+} vits_attention_desc;
+VITS_API int vits_op_attention(const vits_attention_desc* d, const float* q, const float* k, const float* v, const float* rel_k, const float* rel_v,
+                               const uint16_t* exp_tab, const int32_t* lens, float* out);
+/* What vits_op_attention would launch for d, or -1 and the cause of its refusal. Host arithmetic only: no device call. kernel: the instantiation as the launch-plan
+ * tables print it; nw, maxs: waves per block and k-steps of the register arrays (matrix-core kernel; 0 otherwise); vshift: log2 of the V chunk (VALU kernel). */
+typedef struct vits_attention_plan {
+    char kernel[96];
+    int32_t variant; /* the variant that runs (1-6; what 0 resolved to) */
+    int32_t nw, maxs, vshift;
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t lds;
+} vits_attention_plan;
+VITS_API int vits_op_attention_plan(const vits_attention_desc* d, vits_attention_plan* plan);
+
+/* add_layer_norm_kernel with every argument its callers pass: v = LayerNorm_channels(x + residual) * gamma + beta, post_gelu: v = GELU(v) (erf, or gelu_tab:
+ * ggml's 65536-entry fp16 table as vits_model_set_ggml_tables builds it); add_to 0: y = v; add_to 1: y += v (y is read and written, as the DDS layers' residual).
+ * x, residual (optional), y: host [batch][channels][t_stride] fp32, device rows of the same pitch; lens optional, 0 <= lens[b] <= t <= t_stride. tw: time steps
+ * per block, 32 or 64, 0 = the planner's (on the knobs' defaults: no environment knob reaches the choice); both give the same bits. Refused (-1, the cause in
+ * vits_last_error, before the first device call): any other tw, a tile beyond the LDS limit, gelu_tab without post_gelu.
+ * Staging: x, residual and (add_to) y hold 0xFF bytes behind lens[b]; without add_to y is staged as 0xFF bytes. y comes back, all of it, as the device holds it. */
+typedef struct vits_layer_norm_desc {
+    int32_t batch, channels, t, t_stride;
+    float eps;
+    int32_t tw, post_gelu, add_to;
+} vits_layer_norm_desc;
+VITS_API int vits_op_layer_norm(const vits_layer_norm_desc* d, const float* x, const float* residual, const float* gamma, const float* beta, const uint16_t* gelu_tab,
+                                const int32_t* lens, float* y);
+typedef struct vits_layer_norm_plan {
+    char kernel[96]; /* add_layer_norm_kernel<32 | 64> */
+    int32_t tw, grid_x, grid_y, block;
+    int64_t lds;
+} vits_layer_norm_plan;
+VITS_API int vits_op_layer_norm_plan(const vits_layer_norm_desc* d, vits_layer_norm_plan* plan);
+
+/* A conv of a LayerNorm, as the text encoder runs its QKV, FFN and projection convs (Engine::run_text_encoder), fp32:
+ *   ln_out = LayerNorm_channels(x) * gamma + beta;  y = post(conv_k(ln_out) + bias) [+ residual],  post_act 0: none, 1: relu; zero padding, pad_left on the left.
+ * x, ln_out: host [batch][cin][t_stride]; y, residual (optional): [batch][cout][t_stride]; w [cout][cin][k] (torch layout); lens optional, 0 <= lens[b] <= t <=
+ * t_stride. pitch: the device rows' pitch, 0 = the engine's (t rounded up to 32); any other value >= t is taken as given, so that a pitch that is no multiple
+ * of 4 reaches the kernels' element-wise fill.
+ * variant: 1 launch_add_layer_norm, then launch_conv on the normalised tensor (the engine's fallback); 2 one launch_conv that normalises on load (ConvCall::ln_gamma,
+ * conv_lat16_kernel), or -1 with the failing condition of plan_conv's ln_ok named; 0 what the engine does: 2 where that is admissible, else 1. Variants 1 and 2 never
+ * fall back; the launch policy runs on the knobs' defaults; every refusal is made before the first device call. Both variants give the same bits in y and in ln_out.
+ * Staging: x and residual hold 0xFF bytes behind lens[b]; y and ln_out are staged as 0xFF bytes, and columns [0, t) of their rows come back as the device holds them. */
+typedef struct vits_norm_conv_desc {
+    int32_t batch, cin, cout, t, t_stride, pitch;
+    int32_t k, pad_left, post_act;
+    float eps;
+    int32_t variant;
+} vits_norm_conv_desc;
+VITS_API int vits_op_norm_conv(const vits_norm_conv_desc* d, const float* x, const float* gamma, const float* beta, const float* w, const float* bias,
+                               const float* residual, const int32_t* lens, float* y, float* ln_out);
+/* What vits_op_norm_conv would launch, or -1 and the cause. Host arithmetic only. tile: the conv's tile as conv_plan.h names it (TILE_LAT16, TILE_NARROW, ...);
+ * ln_ok: LayerNorm on load is admissible for this conv (ln_why: the condition that fails, or ""); launches: 1 or 2. */
+typedef struct vits_norm_conv_plan {
+    char tile[16];
+    char ln_why[96];
+    int32_t variant; /* the variant that runs (1 or 2; what 0 resolved to) */
+    int32_t pitch, ln_ok, launches;
+    int32_t grid_x, grid_y, grid_z, block;
+    int64_t lds;
+} vits_norm_conv_plan;
+VITS_API int vits_op_norm_conv_plan(const vits_norm_conv_desc* d, vits_norm_conv_plan* plan);
+
 /* The deterministic duration predictor (see vits_model_duration_predictor_kind) on caller-supplied tensors, fp32:
  *   logw = proj(LN2(relu(conv_2(LN1(relu(conv_1(x + spk_row))))))), x + spk_row inside [0, lens[b]) and 0 outside, LN outputs 0 outside.
  * x host [batch][hidden][t_stride]; w1 [filter][hidden][k], w2 [filter][filter][k], wp [1][filter][1] (torch layout); b1, b2 [filter], bp [1];

@@ -133,8 +133,10 @@ def test_rel_attention_does_not_depend_on_the_longest_member_of_the_batch(pkg):
     runs alone or beside a 2049-token one (same MFMA sequence in both paths)."""
     rng = np.random.default_rng(11)
     heads, hd, w = 2, 96, 4
-    # (100 tokens alone: the short-sequence variant — one key tile of look-ahead, four blocks per CU —; 300 alone: four waves, two tiles of
-    # look-ahead; beside 2049 tokens: eight waves. 100 and 300 are 16-byte aligned strides, 2049 is not: vector and scalar loads of V.)
+    # (100 and 300 tokens alone or together: at most 128 blocks, the latency variant <8, 24, false, true> — eight waves, the operands of a phase requested
+    # one phase ahead; beside 2049 tokens: 516 blocks, eight waves by the LDS footprint, <8, 32, false, false> with two key tiles of look-ahead. The
+    # short-sequence variant needs more than 128 blocks of at most 512 tokens: tests/test_gpu_attention_ops.py forces it. 100 and 300 are 16-byte
+    # aligned strides, 2049 is not: vector and scalar loads of V.)
     for T, TL in ((300, 2049), (100, 2049), (100, 300)):
         q, k, v = rnd(rng, 1, heads * hd, T, scale=0.3), rnd(rng, 1, heads * hd, T, scale=0.3), rnd(rng, 1, heads * hd, T)
         rk, rv = rnd(rng, 2 * w + 1, hd, scale=0.1), rnd(rng, 2 * w + 1, hd, scale=0.1)

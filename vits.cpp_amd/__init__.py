@@ -29,6 +29,9 @@ FLOW_VARIANT_PLAN, FLOW_VARIANT_UNFUSED, FLOW_VARIANT_WAVENET, FLOW_VARIANT_COUP
 UP16_VARIANT_PLAN, UP16_VARIANT_TILE, UP16_VARIANT_STREAM = 0, 1, 2  # op_upsample16
 DDS_VARIANT_PLAN, DDS_VARIANT_UNFUSED, DDS_VARIANT_LAYER, DDS_VARIANT_LAT = 0, 1, 2, 3  # op_dds_block
 DDS_HEAD_NONE, DDS_HEAD_FROM1, DDS_HEAD_CONV = 0, 1, 2
+# op_attention: the planner's choice, rel_attention_kernel<1024 | 256>, rel_attention_mfma_kernel<4, 32, false, false | 8, 32, false, false | 4, 24, true, false | 8, 24, false, true>
+ATT_VARIANT_PLAN, ATT_VARIANT_VALU1024, ATT_VARIANT_VALU256, ATT_VARIANT_MFMA4, ATT_VARIANT_MFMA8, ATT_VARIANT_SHORT, ATT_VARIANT_LAT = 0, 1, 2, 3, 4, 5, 6
+NC_VARIANT_PLAN, NC_VARIANT_SEPARATE, NC_VARIANT_ON_LOAD = 0, 1, 2  # op_norm_conv
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 # vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
@@ -64,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
+    "vits_op_attention", "vits_op_attention_plan", "vits_op_layer_norm", "vits_op_layer_norm_plan", "vits_op_norm_conv", "vits_op_norm_conv_plan",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -183,6 +187,41 @@ class Upsample16Plan(C.Structure):
     """vits_upsample16_plan"""
     _fields_ = [("kernel", C.c_char * 96), ("tag", C.c_char * 16), ("variant", C.c_int32), ("bn", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
                 ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64)]
+
+
+class AttentionDesc(C.Structure):
+    """vits_attention_desc"""
+    _fields_ = [("batch", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("window", C.c_int32),
+                ("q_scale", C.c_float), ("variant", C.c_int32)]
+
+
+class AttentionPlan(C.Structure):
+    """vits_attention_plan"""
+    _fields_ = [("kernel", C.c_char * 96), ("variant", C.c_int32), ("nw", C.c_int32), ("maxs", C.c_int32), ("vshift", C.c_int32), ("grid_x", C.c_int32),
+                ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64)]
+
+
+class LayerNormDesc(C.Structure):
+    """vits_layer_norm_desc"""
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("eps", C.c_float), ("tw", C.c_int32),
+                ("post_gelu", C.c_int32), ("add_to", C.c_int32)]
+
+
+class LayerNormPlan(C.Structure):
+    """vits_layer_norm_plan"""
+    _fields_ = [("kernel", C.c_char * 96), ("tw", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64)]
+
+
+class NormConvDesc(C.Structure):
+    """vits_norm_conv_desc"""
+    _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("pitch", C.c_int32), ("k", C.c_int32),
+                ("pad_left", C.c_int32), ("post_act", C.c_int32), ("eps", C.c_float), ("variant", C.c_int32)]
+
+
+class NormConvPlan(C.Structure):
+    """vits_norm_conv_plan"""
+    _fields_ = [("tile", C.c_char * 16), ("ln_why", C.c_char * 96), ("variant", C.c_int32), ("pitch", C.c_int32), ("ln_ok", C.c_int32), ("launches", C.c_int32),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("block", C.c_int32), ("lds", C.c_int64)]
 
 
 _lib = None
@@ -392,6 +431,18 @@ def lib():
     L.vits_op_upsample16.argtypes = [C.POINTER(Upsample16Desc), vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_upsample16_plan.restype = i32
     L.vits_op_upsample16_plan.argtypes = [C.POINTER(Upsample16Desc), C.POINTER(Upsample16Plan)]
+    L.vits_op_attention.restype = i32
+    L.vits_op_attention.argtypes = [C.POINTER(AttentionDesc)] + [vp] * 8
+    L.vits_op_attention_plan.restype = i32
+    L.vits_op_attention_plan.argtypes = [C.POINTER(AttentionDesc), C.POINTER(AttentionPlan)]
+    L.vits_op_layer_norm.restype = i32
+    L.vits_op_layer_norm.argtypes = [C.POINTER(LayerNormDesc)] + [vp] * 7
+    L.vits_op_layer_norm_plan.restype = i32
+    L.vits_op_layer_norm_plan.argtypes = [C.POINTER(LayerNormDesc), C.POINTER(LayerNormPlan)]
+    L.vits_op_norm_conv.restype = i32
+    L.vits_op_norm_conv.argtypes = [C.POINTER(NormConvDesc)] + [vp] * 9
+    L.vits_op_norm_conv_plan.restype = i32
+    L.vits_op_norm_conv_plan.argtypes = [C.POINTER(NormConvDesc), C.POINTER(NormConvPlan)]
     L.vits_op_rel_attention.restype = i32
     L.vits_op_rel_attention.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_add_layer_norm.restype = i32
@@ -1661,6 +1712,105 @@ def op_add_layer_norm(x, residual, gamma, beta, eps=1e-5):
     if lib().vits_op_add_layer_norm(B, Cc, T, T, eps, _ptr(x), _ptr(residual), _ptr(gamma), _ptr(beta), _ptr(y)) != 0:
         raise VitsError(last_error())
     return y
+
+
+def _lens32(lens):
+    return None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+
+
+def _tab16(tab):
+    if tab is None:
+        return None
+    tab = np.ascontiguousarray(tab, dtype=np.uint16)
+    assert tab.shape == (65536,), "a ggml table has 65536 fp16 entries (raw bits)"
+    return tab
+
+
+def op_attention_plan(heads, head_dim, t, batch=1, window=4, variant=ATT_VARIANT_PLAN):
+    """What op_attention would launch (vits_op_attention_plan; host arithmetic, no GPU needed): a dict with kernel, variant (the one that runs), nw, maxs, vshift,
+    grid, block, lds — or a VitsError naming the cause of the refusal."""
+    d = AttentionDesc(batch, heads, head_dim, t, t, window, 1.0, variant)
+    p = AttentionPlan()
+    if lib().vits_op_attention_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "nw", "maxs", "vshift", "block", "lds")}
+    out["kernel"] = p.kernel.decode()
+    out["grid"] = (p.grid_x, p.grid_y, p.grid_z)
+    return out
+
+
+def op_attention(q, k, v, rel_k, rel_v, heads, window, q_scale=1.0, variant=ATT_VARIANT_PLAN, exp_tab=None, lens=None, t=None):
+    """The relative-position attention core through the kernel `variant` names (vits_op_attention): q, k, v [B, heads * head_dim, t_stride]; rel_k, rel_v
+    [2 window + 1, head_dim]; exp_tab: ggml's fp16 exponential table (65536 raw uint16) or None (expf); t = the longest utterance (default: t_stride). The
+    ATT_VARIANT_* other than _PLAN run that kernel or raise a VitsError naming the cause: never another one. Returns out [B, heads * head_dim, t_stride] as the
+    device holds it: the staged NaN (all bits set) wherever no kernel wrote."""
+    q, k, v, rel_k, rel_v = map(_f32, (q, k, v, rel_k, rel_v))
+    B, HD, ts = q.shape
+    hd = HD // heads
+    assert HD == heads * hd and k.shape == q.shape and v.shape == q.shape and rel_k.shape == rel_v.shape == (2 * window + 1, hd)
+    d = AttentionDesc(B, heads, hd, ts if t is None else t, ts, window, q_scale, variant)
+    out = np.zeros_like(q)
+    lens, exp_tab = _lens32(lens), _tab16(exp_tab)
+    assert lens is None or lens.shape == (B,)
+    if lib().vits_op_attention(C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(rel_k), _ptr(rel_v), _ptr(exp_tab), _ptr(lens), _ptr(out)) != 0:
+        raise VitsError(last_error())
+    return out
+
+
+def op_layer_norm_plan(channels, t, batch=1, tw=0):
+    """What op_layer_norm would launch (vits_op_layer_norm_plan; no GPU needed): a dict with kernel, tw, grid, block, lds — or a VitsError naming the cause."""
+    d = LayerNormDesc(batch, channels, t, t, 1e-5, tw, 0, 0)
+    p = LayerNormPlan()
+    if lib().vits_op_layer_norm_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    return dict(kernel=p.kernel.decode(), tw=p.tw, grid=(p.grid_x, p.grid_y, 1), block=p.block, lds=p.lds)
+
+
+def op_layer_norm(x, gamma, beta, residual=None, eps=1e-5, tw=0, post_gelu=False, add_to=None, gelu_tab=None, lens=None, t=None):
+    """add_layer_norm_kernel on the tile `tw` names (vits_op_layer_norm): v = LN(x + residual) * gamma + beta, GELU'd with post_gelu (gelu_tab: ggml's fp16 table);
+    add_to [B, C, t_stride]: returns add_to + v computed in place on the device, otherwise v. Returned as the device holds it: the staged NaN behind lens[b]."""
+    x, gamma, beta, residual, add_to = _f32(x), _f32(gamma), _f32(beta), _f32(residual), _f32(add_to)
+    B, Cc, ts = x.shape
+    assert gamma.shape == beta.shape == (Cc,) and (residual is None or residual.shape == x.shape) and (add_to is None or add_to.shape == x.shape)
+    d = LayerNormDesc(B, Cc, ts if t is None else t, ts, eps, tw, int(bool(post_gelu)), 0 if add_to is None else 1)
+    y = np.zeros_like(x) if add_to is None else add_to.copy()
+    lens, gelu_tab = _lens32(lens), _tab16(gelu_tab)
+    assert lens is None or lens.shape == (B,)
+    if lib().vits_op_layer_norm(C.byref(d), _ptr(x), _ptr(residual), _ptr(gamma), _ptr(beta), _ptr(gelu_tab), _ptr(lens), _ptr(y)) != 0:
+        raise VitsError(last_error())
+    return y
+
+
+def op_norm_conv_plan(cin, cout, k, t, batch=1, pad_left=None, pitch=0, post_act=0, variant=NC_VARIANT_PLAN):
+    """What op_norm_conv would launch (vits_op_norm_conv_plan; no GPU needed): a dict with tile, variant (the one that runs), pitch, ln_ok, ln_why, launches,
+    grid, block, lds — or a VitsError naming the cause of the refusal."""
+    d = NormConvDesc(batch, cin, cout, t, t, pitch, k, (k - 1) // 2 if pad_left is None else pad_left, post_act, 1e-5, variant)
+    p = NormConvPlan()
+    if lib().vits_op_norm_conv_plan(C.byref(d), C.byref(p)) != 0:
+        raise VitsError(last_error())
+    out = {n: getattr(p, n) for n in ("variant", "pitch", "launches", "block", "lds")}
+    out.update(tile=p.tile.decode(), ln_why=p.ln_why.decode(), ln_ok=bool(p.ln_ok), grid=(p.grid_x, p.grid_y, p.grid_z))
+    return out
+
+
+def op_norm_conv(x, gamma, beta, w, bias=None, residual=None, pad_left=None, post_act=0, eps=1e-5, pitch=0, variant=NC_VARIANT_PLAN, lens=None, t=None):
+    """y = post(conv(LN(x)) + bias) [+ residual] and ln_out = LN(x) (vits_op_norm_conv): x [B, cin, t_stride], w [cout, cin, k]; NC_VARIANT_SEPARATE = the
+    LayerNorm launch, then the conv; NC_VARIANT_ON_LOAD = one conv launch that normalises on load, or a VitsError naming the condition that fails; pitch: the
+    device rows' pitch (0: t rounded up to 32). Returns (y [B, cout, t_stride], ln_out [B, cin, t_stride]): columns [0, t) as the device holds them (the staged
+    NaN, all bits set, wherever no kernel wrote), NaN bits from t on."""
+    x, gamma, beta, w, bias, residual = _f32(x), _f32(gamma), _f32(beta), _f32(w), _f32(bias), _f32(residual)
+    B, cin, ts = x.shape
+    cout, _, k = w.shape
+    assert w.shape == (cout, cin, k) and gamma.shape == beta.shape == (cin,) and (bias is None or bias.shape == (cout,))
+    assert residual is None or residual.shape == (B, cout, ts)
+    d = NormConvDesc(B, cin, cout, ts if t is None else t, ts, pitch, k, (k - 1) // 2 if pad_left is None else pad_left, post_act, eps, variant)
+    y = np.full((B, cout, ts), 0xFFFFFFFF, np.uint32).view(np.float32)
+    ln_out = np.full((B, cin, ts), 0xFFFFFFFF, np.uint32).view(np.float32)
+    lens = _lens32(lens)
+    assert lens is None or lens.shape == (B,)
+    if lib().vits_op_norm_conv(C.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(bias), _ptr(residual), _ptr(lens), _ptr(y), _ptr(ln_out)) != 0:
+        raise VitsError(last_error())
+    return y, ln_out
 
 
 def pcm16(pcm):

@@ -2085,6 +2085,294 @@ VITS_API int vits_op_add_layer_norm(int32_t batch, int32_t channels, int32_t t, 
     VITS_CATCH(-1)
 }
 
+// ---- vits_op_attention / vits_op_layer_norm / vits_op_norm_conv: which kernel a descriptor names (host arithmetic only: launch_plan.h, conv_plan.h), then the text
+// encoder's launches on staged tensors. (The resolvers run under the caller's KernelKnobsScope over the knobs' defaults: no environment variable reaches the choice)
+namespace {
+// [batch][rows][pitch] floats on the device: 0xFF bytes (NaN), then columns [0, lens[b]) of src's rows (host pitch src_pitch); src NULL: 0xFF only
+bool stage_ff(DevBytes& dst, const float* src, int batch, int rows, int src_pitch, int pitch, const int32_t* lens, int t) {
+    const size_t n = (size_t)batch * rows * pitch;
+    std::vector<float> h(std::max<size_t>(n, 4));
+    std::memset(h.data(), 0xFF, h.size() * 4);
+    for (int b = 0; src && b < batch; ++b)
+        for (int c = 0; c < rows; ++c)
+            std::memcpy(&h[((size_t)b * rows + c) * pitch], src + ((size_t)b * rows + c) * src_pitch, sizeof(float) * (size_t)(lens ? lens[b] : t));
+    return dst.put(h.data(), h.size() * 4);
+}
+bool op_fail(std::string& why, const char* op, const std::string& m) {
+    why = std::string(op) + ": " + m;
+    return false;
+}
+const char* tf(bool v) { return v ? "true" : "false"; }
+
+struct AttOpPlan {
+    int variant = 0;
+    std::string kernel;
+    vits::AttentionPlan p;
+};
+bool attention_resolve(const vits_attention_desc* d, AttOpPlan& r, std::string& why) {
+    using namespace vits;
+    const char* op = "vits_op_attention";
+    const int hd = d->head_dim, v = d->variant;
+    if (d->batch < 1 || d->heads < 1 || d->t < 1 || d->t_stride < d->t) return op_fail(why, op, "batch >= 1, heads >= 1 and 1 <= t <= t_stride are required");
+    if (d->window < 0) return op_fail(why, op, "window = " + std::to_string(d->window) + ": at least 0");
+    if (v < 0 || v > 6)
+        return op_fail(why, op, "variant " + std::to_string(v) + ": 0 (the planner's choice), 1 / 2 (rel_attention_kernel<1024> / <256>), 3 ... 6 (rel_attention_mfma_kernel<4, 32, false, false>, <8, 32, false, false>, <4, 24, true, false>, <8, 24, false, true>)");
+    if (hd < 1 || hd > 128) return op_fail(why, op, "head_dim = " + std::to_string(hd) + ": no attention kernel above 128 (1 to 128)");
+    if (v >= 3 && (hd & 15)) return op_fail(why, op, "variant " + std::to_string(v) + ": head_dim = " + std::to_string(hd) + " is not a multiple of 16 (the matrix-core kernel's d tiles)");
+    if (v >= 5 && hd > 96) return op_fail(why, op, "variant " + std::to_string(v) + ": head_dim = " + std::to_string(hd) + " is above 96 (the register arrays of the 24-step kernels)");
+    if (v >= 3 && att_mfma_lds(hd, d->t, d->window) > kLdsMax)
+        return op_fail(why, op, "variant " + std::to_string(v) + ": rel_attention_mfma_kernel needs " + std::to_string(att_mfma_lds(hd, d->t, d->window)) + " bytes of LDS, the limit is " + std::to_string(kLdsMax));
+    if ((v == 1 || v == 2) && att_valu_lds(hd, d->t, d->window, 3) > kLdsSoft)
+        return op_fail(why, op, "variant " + std::to_string(v) + ": rel_attention_kernel needs " + std::to_string(att_valu_lds(hd, d->t, d->window, 3)) + " bytes of LDS, the limit is " + std::to_string(kLdsSoft));
+    r.p = plan_rel_attention(d->batch, d->heads, hd, d->t, d->window, v);
+    if (!r.p.ok) return op_fail(why, op, v ? "variant " + std::to_string(v) + ": plan_rel_attention refuses the shape" : "no attention kernel takes this shape (the scores of one block pass the LDS limit)");
+    char name[96];
+    if (r.p.mfma) {
+        r.variant = r.p.lat ? 6 : r.p.sh ? 5 : r.p.nw == 8 ? 4 : 3;
+        std::snprintf(name, sizeof(name), "rel_attention_mfma_kernel<%d, %d, %s, %s>", r.p.nw, r.p.maxs, tf(r.p.sh), tf(r.p.lat));
+    } else {
+        r.variant = r.p.block == 1024 ? 1 : 2;
+        std::snprintf(name, sizeof(name), "rel_attention_kernel<%d>", r.p.block);
+    }
+    r.kernel = name;
+    return true;
+}
+
+bool layer_norm_resolve(const vits_layer_norm_desc* d, bool has_tab, vits::LayerNormPlan& p, std::string& why) {
+    using namespace vits;
+    const char* op = "vits_op_layer_norm";
+    if (d->batch < 1 || d->channels < 1 || d->t < 1 || d->t_stride < d->t) return op_fail(why, op, "batch >= 1, channels >= 1 and 1 <= t <= t_stride are required");
+    if (!(d->eps > 0.f)) return op_fail(why, op, "eps must be positive");
+    if (d->tw != 0 && d->tw != 32 && d->tw != 64) return op_fail(why, op, "tw = " + std::to_string(d->tw) + ": 0 (the planner's choice), 32 or 64 time steps per block");
+    if ((d->post_gelu != 0 && d->post_gelu != 1) || (d->add_to != 0 && d->add_to != 1)) return op_fail(why, op, "post_gelu and add_to are 0 or 1");
+    if (has_tab && !d->post_gelu) return op_fail(why, op, "gelu_tab without post_gelu: the table is the GELU's");
+    p = plan_add_layer_norm(d->channels, d->batch, d->t, d->tw);
+    if (!p.ok) {
+        const int tw = d->tw ? d->tw : 32;
+        return op_fail(why, op, "add_layer_norm_kernel<" + std::to_string(tw) + "> needs " + std::to_string(layer_norm_lds(d->channels, tw)) + " bytes of LDS for channels = " +
+                                    std::to_string(d->channels) + ", the limit is " + std::to_string(kLdsSoft));
+    }
+    return true;
+}
+
+struct NormConvOpPlan {
+    int variant = 0, pitch = 0, launches = 0;
+    bool ln_ok = false;
+    std::string ln_why;
+    vits::ConvPlan cp;    // of the conv that runs
+    vits::PackedConv pc;  // the shape fields; the op adds the device pointers
+};
+const char* conv_tile_name(int tile) {
+    static const char* const names[] = {"TILE_128x128", "TILE_64x256", "TILE_32x256", "TILE_64x64", "TILE_32x64", "TILE_NARROW", "TILE_LAT16"};
+    return tile >= 0 && tile <= 6 ? names[tile] : "?";
+}
+// the two calls of the op for the planner: `fused` with LayerNorm on load, `plain` on the normalised tensor (pointers: only whether they are set and equal matters)
+void norm_conv_calls(const vits_norm_conv_desc* d, const int* lens, vits::ConvCall& plain, vits::ConvCall& fused) {
+    plain.len_in = plain.len_out = lens;
+    plain.batch = d->batch, plain.t_in = plain.t_out = d->t;
+    plain.pad_l = d->pad_left, plain.post_act = d->post_act;
+    fused = plain;
+    fused.ln_gamma = fused.ln_beta = reinterpret_cast<const float*>(sizeof(float));  // (the op replaces them; to plan_conv non-null means "with the statistics' LDS")
+    fused.ln_eps = d->eps;
+}
+bool norm_conv_resolve(const vits_norm_conv_desc* d, int arith, NormConvOpPlan& r, std::string& why) {
+    using namespace vits;
+    const char* op = "vits_op_norm_conv";
+    if (arith != VITS_ARITH_F32) return op_fail(why, op, "VITS_ARITH_F32 only (the engine normalises on load in fp32 alone)");
+    if (d->batch < 1 || d->cin < 1 || d->cout < 1 || d->t < 1 || d->t_stride < d->t) return op_fail(why, op, "batch, cin, cout >= 1 and 1 <= t <= t_stride are required");
+    r.pitch = d->pitch ? d->pitch : round_up(d->t, 32);
+    if (r.pitch < d->t) return op_fail(why, op, "pitch = " + std::to_string(d->pitch) + " < t = " + std::to_string(d->t));
+    if (d->k < 1 || d->k > 64) return op_fail(why, op, "k = " + std::to_string(d->k) + ": 1 to 64 taps");
+    if (d->pad_left < 0 || d->pad_left > d->k - 1) return op_fail(why, op, "pad_left = " + std::to_string(d->pad_left) + ": 0 to k - 1 (every output reads its own column)");
+    if (d->post_act != 0 && d->post_act != 1) return op_fail(why, op, "post_act " + std::to_string(d->post_act) + ": 0 (none) or 1 (relu)");
+    if (!(d->eps > 0.f)) return op_fail(why, op, "eps must be positive");
+    if (d->variant < 0 || d->variant > 2) return op_fail(why, op, "variant " + std::to_string(d->variant) + ": 0 (the engine's choice), 1 (LayerNorm launch + conv), 2 (LayerNorm on load)");
+    PackedConv& pc = r.pc;
+    pc.cin = d->cin, pc.cout = d->cout, pc.kt = d->k, pc.epi = EPI_STD;
+    const ConvPackDims pd = conv_pack_dims(d->cout, d->cin, d->k, EPI_STD, 0);
+    pc.rows = pd.rows, pc.mtiles_used = pd.mtiles_used, pc.mtiles = pd.mtiles, pc.nchunks = pd.nchunks;
+    if (conv_lat16_candidate(EPI_STD, d->k, d->cin)) pc.wp_l16 = reinterpret_cast<float*>(sizeof(float));  // (as the engine's load gives the layer its second copy; the op replaces it)
+    ConvCall plain, fused;
+    norm_conv_calls(d, nullptr, plain, fused);
+    const ConvPlan pf = plan_conv(pc, fused), pp = plan_conv(pc, plain);
+    r.ln_ok = pf.ln_ok, r.ln_why = pf.ln_why ? pf.ln_why : "";
+    r.variant = d->variant ? d->variant : pf.ln_ok ? 2 : 1;  // Engine::run_text_encoder's conv_of_norm
+    if (r.variant == 2 && !pf.ln_ok) return op_fail(why, op, "variant 2: conv_ln_on_load_ok refuses: " + r.ln_why);
+    r.cp = r.variant == 2 ? pf : pp;
+    if (!r.cp.ok) return op_fail(why, op, "variant " + std::to_string(r.variant) + ": plan_conv has no kernel for this conv");
+    if (r.variant == 1 && !plan_add_layer_norm(d->cin, d->batch, d->t).ok) return op_fail(why, op, "variant 1: add_layer_norm_kernel has no tile for channels = " + std::to_string(d->cin));
+    r.launches = r.variant == 2 ? 1 : 2;
+    return true;
+}
+bool op_lens_ok(const int32_t* lens, int batch, int t) {
+    for (int b = 0; lens && b < batch; ++b)
+        if (lens[b] < 0 || lens[b] > t) return false;
+    return true;
+}
+}  // namespace
+
+VITS_API int vits_op_attention_plan(const vits_attention_desc* d, vits_attention_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_attention_plan: null argument");
+    const vits::KernelKnobs defaults;
+    vits::KernelKnobsScope scope(&defaults);
+    AttOpPlan r;
+    std::string why;
+    if (!attention_resolve(d, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", r.kernel.c_str());
+    out->variant = r.variant, out->nw = r.p.nw, out->maxs = r.p.maxs, out->vshift = r.p.mfma ? 0 : r.p.vshift;
+    out->grid_x = r.p.gx, out->grid_y = r.p.gy, out->grid_z = r.p.gz, out->block = r.p.block, out->lds = (int64_t)r.p.lds;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_attention(const vits_attention_desc* d, const float* q, const float* k, const float* v, const float* rel_k, const float* rel_v,
+                               const uint16_t* exp_tab, const int32_t* lens, float* out) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !q || !k || !v || !rel_k || !rel_v || !out) return fail("vits_op_attention: null argument");
+    const KernelKnobs defaults;
+    KernelKnobsScope scope(&defaults);
+    AttOpPlan r;
+    std::string why;
+    if (!attention_resolve(d, r, why)) return fail(why.c_str());
+    const int B = d->batch, C = d->heads * d->head_dim, T = d->t, ts = d->t_stride;
+    if (!op_lens_ok(lens, B, T)) return fail("vits_op_attention: 0 <= lens[b] <= t <= t_stride is required");
+    const size_t nr = (size_t)(2 * d->window + 1) * d->head_dim;
+    DevBytes dq, dk, dv, dout, drk, drv, dtab;
+    DevInts dl;
+    if (!stage_ff(dq, q, B, C, ts, ts, lens, T) || !stage_ff(dk, k, B, C, ts, ts, lens, T) || !stage_ff(dv, v, B, C, ts, ts, lens, T) || !stage_ff(dout, nullptr, B, C, ts, ts, lens, T) ||
+        !drk.put(rel_k, nr * 4) || !drv.put(rel_v, nr * 4) || !dl.put(lens, B) || (exp_tab && !dtab.put(exp_tab, 65536 * 2)))
+        return fail("device allocation failed");
+    GgmlTables tabs;
+    tabs.exp = exp_tab ? dtab.h() : nullptr;
+    hipError_t e = launch_rel_attention(tref(dq.f(), C, ts), tref(dk.f(), C, ts), tref(dv.f(), C, ts), drk.f(), drv.f(), tref(dout.f(), C, ts), dl.p, B, d->heads, d->head_dim, T,
+                                        d->window, d->q_scale, nullptr, tabs, r.variant);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_attention: ") + r.kernel + ": " + hipGetErrorString(e)).c_str());
+    if (hipMemcpy(out, dout.p, (size_t)B * C * ts * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_layer_norm_plan(const vits_layer_norm_desc* d, vits_layer_norm_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_layer_norm_plan: null argument");
+    const vits::KernelKnobs defaults;
+    vits::KernelKnobsScope scope(&defaults);
+    vits::LayerNormPlan p;
+    std::string why;
+    if (!layer_norm_resolve(d, false, p, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->kernel, sizeof(out->kernel), "add_layer_norm_kernel<%d>", p.tw);
+    out->tw = p.tw, out->grid_x = p.gx, out->grid_y = p.gy, out->block = p.block, out->lds = (int64_t)p.lds;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_layer_norm(const vits_layer_norm_desc* d, const float* x, const float* residual, const float* gamma, const float* beta, const uint16_t* gelu_tab,
+                                const int32_t* lens, float* y) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !gamma || !beta || !y) return fail("vits_op_layer_norm: null argument");
+    const KernelKnobs defaults;
+    KernelKnobsScope scope(&defaults);
+    LayerNormPlan p;
+    std::string why;
+    if (!layer_norm_resolve(d, gelu_tab != nullptr, p, why)) return fail(why.c_str());
+    const int B = d->batch, C = d->channels, T = d->t, ts = d->t_stride;
+    if (!op_lens_ok(lens, B, T)) return fail("vits_op_layer_norm: 0 <= lens[b] <= t <= t_stride is required");
+    DevBytes dx, dr, dy, dg, db, dtab;
+    DevInts dl;
+    if (!stage_ff(dx, x, B, C, ts, ts, lens, T) || (residual && !stage_ff(dr, residual, B, C, ts, ts, lens, T)) || !stage_ff(dy, d->add_to ? y : nullptr, B, C, ts, ts, lens, T) ||
+        !dg.put(gamma, (size_t)C * 4) || !db.put(beta, (size_t)C * 4) || !dl.put(lens, B) || (gelu_tab && !dtab.put(gelu_tab, 65536 * 2)))
+        return fail("device allocation failed");
+    GgmlTables tabs;
+    tabs.gelu = gelu_tab ? dtab.h() : nullptr;
+    TensorRef none;
+    const TensorRef yr = tref(dy.f(), C, ts);
+    hipError_t e = launch_add_layer_norm(tref(dx.f(), C, ts), residual ? tref(dr.f(), C, ts) : none, dg.f(), db.f(), d->add_to ? none : yr, dl.p, B, C, T, d->eps, d->post_gelu,
+                                         d->add_to ? yr : none, nullptr, tabs, p.tw);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_layer_norm: ") + hipGetErrorString(e)).c_str());
+    if (hipMemcpy(y, dy.p, (size_t)B * C * ts * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_norm_conv_plan(const vits_norm_conv_desc* d, vits_norm_conv_plan* out) {
+    VITS_TRY
+    if (!d || !out) return fail("vits_op_norm_conv_plan: null argument");
+    const vits::KernelKnobs defaults;
+    vits::KernelKnobsScope scope(&defaults);
+    NormConvOpPlan r;
+    std::string why;
+    if (!norm_conv_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    std::memset(out, 0, sizeof(*out));
+    std::snprintf(out->tile, sizeof(out->tile), "%s", conv_tile_name(r.cp.tile));
+    std::snprintf(out->ln_why, sizeof(out->ln_why), "%s", r.ln_why.c_str());
+    out->variant = r.variant, out->pitch = r.pitch, out->ln_ok = r.ln_ok ? 1 : 0, out->launches = r.launches;
+    out->grid_x = r.cp.gx, out->grid_y = r.cp.gy, out->grid_z = r.cp.gz, out->block = r.cp.block, out->lds = (int64_t)r.cp.lds;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_norm_conv(const vits_norm_conv_desc* d, const float* x, const float* gamma, const float* beta, const float* w, const float* bias,
+                               const float* residual, const int32_t* lens, float* y, float* ln_out) {
+    VITS_TRY
+    using namespace vits;
+    if (!d || !x || !gamma || !beta || !w || !y || !ln_out) return fail("vits_op_norm_conv: null argument (bias and residual alone are optional)");
+    const KernelKnobs defaults;
+    KernelKnobsScope scope(&defaults);
+    NormConvOpPlan r;
+    std::string why;
+    if (!norm_conv_resolve(d, g_op_arith, r, why)) return fail(why.c_str());
+    const int B = d->batch, cin = d->cin, cout = d->cout, T = d->t, ts = d->t_stride, P = r.pitch;
+    if (!op_lens_ok(lens, B, T)) return fail("vits_op_norm_conv: 0 <= lens[b] <= t <= t_stride is required");
+    PackedConv& pc = r.pc;
+    DevBytes dw, dwl, dbias, dg, dbe, dx, dln, dy, dres;
+    DevInts dl;
+    {
+        const std::vector<float> packed = pack_conv_weights(w, cout, cin, d->k, EPI_STD, 0, &pc.rows, &pc.mtiles_used, &pc.mtiles, &pc.nchunks);
+        if (!dw.put(packed.data(), packed.size() * 4)) return fail("device allocation failed");
+        pc.wp = dw.f(), pc.bytes = (int64_t)packed.size() * 4;
+        if (pc.wp_l16) {
+            const std::vector<float> pl = repack_conv_weights_l16(packed, pc.mtiles, pc.nchunks, d->k);
+            if (!dwl.put(pl.data(), pl.size() * 4)) return fail("device allocation failed");
+            pc.wp_l16 = dwl.f();
+        }
+    }
+    if ((bias && !dbias.put(bias, (size_t)cout * 4)) || !dg.put(gamma, (size_t)cin * 4) || !dbe.put(beta, (size_t)cin * 4) || !dl.put(lens, B) ||
+        !stage_ff(dx, x, B, cin, ts, P, lens, T) || !stage_ff(dln, nullptr, B, cin, ts, P, lens, T) || !stage_ff(dy, nullptr, B, cout, ts, P, lens, T) ||
+        (residual && !stage_ff(dres, residual, B, cout, ts, P, lens, T)))
+        return fail("device allocation failed");
+    pc.bias = bias ? dbias.f() : nullptr;
+    ConvCall plain, fused;
+    norm_conv_calls(d, dl.p, plain, fused);
+    const TensorRef xr = tref(dx.f(), cin, P), lnr = tref(dln.f(), cin, P);
+    plain.y = fused.y = tref(dy.f(), cout, P);
+    if (residual) plain.res = fused.res = tref(dres.f(), cout, P);
+    hipError_t e;
+    if (r.variant == 2) {  // Engine::run_text_encoder's conv_of_norm: the un-normalised tensor in, the normalised one out of the conv's first row group
+        fused.x = xr, fused.ln_gamma = dg.f(), fused.ln_beta = dbe.f(), fused.ln_out = lnr;
+        e = launch_conv(pc, fused, nullptr);
+    } else {  // its fallback: norm_now, then the conv on the normalised tensor
+        TensorRef none;
+        e = launch_add_layer_norm(xr, none, dg.f(), dbe.f(), lnr, dl.p, B, cin, T, d->eps, 0, none, nullptr);
+        plain.x = lnr;
+        if (e == hipSuccess) e = launch_conv(pc, plain, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail((std::string("vits_op_norm_conv: variant ") + std::to_string(r.variant) + ": " + hipGetErrorString(e)).c_str());
+    auto back = [&](const DevBytes& src, int rows, float* dst) {  // columns [0, t) of every row, as the device holds them
+        return hipMemcpy2D(dst, (size_t)ts * 4, src.p, (size_t)P * 4, (size_t)T * 4, (size_t)B * rows, hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    if (!back(dy, cout, y) || !back(dln, cin, ln_out)) return fail("copy back failed");
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_duration_predictor(const vits_duration_predictor_desc* d, const float* x, const float* w1, const float* b1, const float* g1, const float* be1,
                                         const float* w2, const float* b2, const float* g2, const float* be2, const float* wp, const float* bp, const float* spk_rows,
                                         const int32_t* lens, float* logw) {

@@ -982,10 +982,11 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
             }
         }
     }
-    float lng[3], lnb[3];  // LayerNorm on load: this thread's share of gamma / beta (c_in <= 768), requested with everything else
+    constexpr int LNU = kLnLoadMaxCin / 256;
+    float lng[LNU], lnb[LNU];  // LayerNorm on load: this thread's share of gamma / beta (c_in <= kLnLoadMaxCin: plan_conv's ln_ok), requested with everything else
     if (p.ln_gamma) {
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
+        for (int u = 0; u < LNU; ++u) {
             const int c = tid + 256 * u;
             lng[u] = c < p.cin ? p.ln_gamma[c] : 0.f;
             lnb[u] = c < p.cin ? p.ln_beta[c] : 0.f;
@@ -1065,7 +1066,7 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
         const int ncol = 16 + (KT - 1) * dil;  // the columns the K loop reads: LDS columns shift .. shift + ncol - 1 (<= 32: conv_ln_on_load_ok)
         const int tc0 = tile_start;            // time of the first of them
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {  // (the two parameter vectors once, into LDS: a load per element in the last pass was 18 exposed round trips)
+        for (int u = 0; u < LNU; ++u) {  // (the two parameter vectors once, into LDS: a load per element in the last pass was 18 exposed round trips)
             const int c = tid + 256 * u;
             if (c < C) gb[c] = lng[u], gb[C + c] = lnb[u];
         }

@@ -90,8 +90,17 @@ ConvPlan plan_conv(const PackedConv& w, const ConvCall& c, int forced_tile) {
     // whose tile choice is TILE_LAT16, with the statistics' scratch beside the input tile in LDS, and the input lengths = the output lengths (padded 'same' conv)
     const size_t ln_bytes = ((size_t)2 * 16 * 32 + 2 * (size_t)w.cin) * sizeof(float);  // partial sums of up to 32 columns; gamma, beta
     const size_t lat_bytes = ((size_t)w.nchunks + 1) * kConvCK * p.pitch * sizeof(float);  // (+ one chunk of slack rows: the look-ahead of the last tap)
-    p.ln_ok = w.epi == EPI_STD && !c.pre_act && w.wp_l16 && c.len_in == c.len_out && c.t_in == c.t_out && p.tile == TILE_LAT16 && p.pitch && span <= 16 &&
-              lat_bytes + ln_bytes <= 150 * 1024;
+    // (c_in <= kLnLoadMaxCin: the kernel stages gamma and beta as three elements per thread; a wider input takes the separate launch)
+    p.ln_why = w.epi != EPI_STD                                ? "not a standard conv (epilogue)"
+               : c.pre_act                                     ? "the conv has an input activation"
+               : !w.wp_l16                                     ? "the layer has no conv_lat16_kernel weights"
+               : c.len_in != c.len_out || c.t_in != c.t_out    ? "input and output lengths differ"
+               : p.tile != TILE_LAT16                          ? "the planner's tile is not TILE_LAT16"
+               : !p.pitch || span > 16                         ? "(k - 1) * dilation > 16"
+               : w.cin > kLnLoadMaxCin                         ? "c_in > 768 (gamma and beta are staged as three elements per thread)"
+               : lat_bytes + ln_bytes > 150 * 1024             ? "the input tile and the statistics pass 150 KB of LDS"
+                                                               : nullptr;
+    p.ln_ok = !p.ln_why;
     if (p.tile == TILE_LAT16) {
         p.ok = p.ok && p.pitch && w.wp_l16;
         p.xw = p.pitch;

@@ -50,6 +50,7 @@ inline int64_t tile_blocks(TileShape t, int ncols, int mtiles_used, int batch) {
 }
 constexpr int padded_xw(int xw) { return (xw + 3 + VITS_XWP_GRAN - 1) / VITS_XWP_GRAN * VITS_XWP_GRAN; }  // (+3: 16-byte aligned origin)
 constexpr int lat16_pitch(int span) { return span <= 4 ? 24 : span <= 20 ? 40 : span <= 52 ? 72 : 0; }  // conv_lat16_kernel's instantiated LDS pitches (0: none)
+constexpr int kLnLoadMaxCin = 3 * 256;  // LayerNorm on load (conv_lat16_kernel): every thread of the block stages three elements of gamma and of beta
 constexpr int conv16_lat_pitch(int nr, int kt, int dil) { return (32 * nr + (kt - 1) * dil + 7) / 8 * 8; }
 // GEMM shape of a conv's packed weights (pack_conv_weights / pack_conv_weights16): the row tiles are padded so that every tile shape (1, 2 or 4 per block) divides them
 struct ConvPackDims {
@@ -131,6 +132,7 @@ struct ConvPlan {
     int xw = 0, lds_off = 0, nbuf = 2, oneshot = 0;
     int pitch = 0;       // conv_lat16_kernel's LDS pitch for these taps (0: none)
     bool ln_ok = false;  // LayerNorm on load admissible (ConvCall::ln_gamma)
+    const char* ln_why = nullptr;  // !ln_ok: the first condition that fails
 };
 ConvPlan plan_conv(const PackedConv& w, const ConvCall& c, int forced_tile = -1);  // (forced_tile: the grouped launch's members, always 128 x 128)
 // block shape, pitch, grid and LDS bytes of a conv16_lat launch: `cin` channels in, `cout` rows out, grid z = `nz`

@@ -476,9 +476,9 @@ struct GgmlTables {
     const uint16_t* exp = nullptr;
 };
 hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const float* rel_k, const float* rel_v, TensorRef out, const int* lens, int batch,
-                                int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs = GgmlTables());
+                                int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs = GgmlTables(), int force = 0);  // force: plan_rel_attention's
 hipError_t launch_add_layer_norm(TensorRef x, TensorRef res, const float* gamma, const float* beta, TensorRef y, const int* lens, int batch, int channels,
-                                 int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs = GgmlTables());
+                                 int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs = GgmlTables(), int force_tw = 0);  // force_tw: plan_add_layer_norm's
 hipError_t launch_dds_depthwise(TensorRef x, TensorRef g, const float* w, const float* bias, const float* gamma, const float* beta, TensorRef y,
                                 const int* lens, int batch, int channels, int tmax, int k, int dil, float eps, hipStream_t s, int arith = 0,
                                 GgmlTables tabs = GgmlTables());

@@ -181,11 +181,31 @@ FlowCouple16Plan plan_flow_couple16(int hidden, int half, int kt, int rate, int 
 }
 
 // ---- stage one ---------------------------------------------------------------------------------------------------------------------------
-AttentionPlan plan_rel_attention(int batch, int heads, int head_dim, int tmax, int window) {
+AttentionPlan plan_rel_attention(int batch, int heads, int head_dim, int tmax, int window, int force) {
     const KernelKnobs& kn = kernel_knobs();
     AttentionPlan p;
     const int gx = blocks_for(tmax, kAttQ);
     const int64_t blocks = (int64_t)gx * heads * batch;
+    if (force) {  // the caller names the instantiation (vits_op_attention): no knob, no grid rule. Every kernel's loops run over the utterance's own length
+        // and every block works for itself: the short variant beyond VITS_ATT_SHORT tokens and the latency variant beyond 128 blocks compute the same sums
+        if (force < 1 || force > 6 || head_dim < 1 || head_dim > 128) return p;
+        if (force <= 2) {  // rel_attention_kernel<1024 | 256>: (d, 4-query group) items over 512 thread slots, V chunks of 2^vshift keys
+            size_t lds = 0;
+            for (p.vshift = 6; p.vshift >= 3; --p.vshift) {
+                lds = att_valu_lds(head_dim, tmax, window, p.vshift);
+                if (lds <= kLdsSoft) break;
+            }
+            if (lds > kLdsSoft) return p;
+            set_grid(p, gx, heads, force == 1 ? 1024 : 256, lds, batch);
+            return p;
+        }
+        p.nw = force == 3 || force == 5 ? 4 : 8, p.lat = force == 6, p.sh = force == 5, p.maxs = force >= 5 ? 24 : 32;
+        const size_t lds = att_mfma_lds(head_dim, tmax, window);
+        if ((head_dim & 15) || head_dim > 4 * p.maxs || lds > kLdsMax) return p;
+        p.mfma = true;
+        set_grid(p, gx, heads, 64 * p.nw, lds, batch);
+        return p;
+    }
     // matrix-core version. The number of waves (= how the key tiles and the d tiles are dealt out) does not change a single sum, so it may
     // depend on the launch: four waves while two or more blocks fit the LDS of a CU (up to ~1200 tokens: 1024 ids 0.178 ms against 0.222
     // with six waves), eight once the scores of a block leave room for one block only (2049 tokens: 0.87 against 1.29 ms with four)
@@ -214,14 +234,15 @@ AttentionPlan plan_rel_attention(int batch, int heads, int head_dim, int tmax, i
     return p;
 }
 
-LayerNormPlan plan_add_layer_norm(int channels, int batch, int tmax) {
+LayerNormPlan plan_add_layer_norm(int channels, int batch, int tmax, int force_tw) {
     // tile width (time steps per block): 32 = eight waves and channels x 128 B of LDS per block (29 KB at 192 channels); VITS_LN_TW=64 = the
     // sixteen-wave, 57 KB blocks of rounds 1-3. Every token's sums are the same either way (its channels are summed by the same sixteen channel
     // groups in the same order). The small block matters when this kernel shares the chip with another batch's vocoder (vits_model_submit_batch):
     // a 57 KB block only finds room in the tail of a vocoder kernel — stage one of a pipelined f16 batch took 10.2 ms of wall with it, 8.8 with
     // the small one (alone: 1.91 -> 1.87 ms).
     LayerNormPlan p;
-    p.tw = kernel_knobs().ln_tw == 64 ? 64 : 32;
+    if (force_tw && force_tw != 32 && force_tw != 64) return p;
+    p.tw = force_tw ? force_tw : kernel_knobs().ln_tw == 64 ? 64 : 32;  // (force_tw: the caller names the tile, vits_op_layer_norm)
     const size_t lds = layer_norm_lds(channels, p.tw);
     if (lds <= kLdsSoft) set_grid(p, blocks_for(tmax, p.tw), batch, p.tw * kLnGroups, lds);
     return p;

@@ -210,11 +210,14 @@ struct AttentionPlan : LaunchGrid {
     bool mfma = false, sh = false, lat = false;
     int nw = 0, maxs = 0, vshift = 0;
 };
-AttentionPlan plan_rel_attention(int batch, int heads, int head_dim, int tmax, int window);
+// force (vits_op_attention): 1 / 2 = rel_attention_kernel<1024> / <256>, 3 ... 6 = rel_attention_mfma_kernel<4, 32, false, false> / <8, 32, false, false> / <4, 24, true, false> /
+// <8, 24, false, true>, whatever the grid and the knobs say, or a refusal (ok false) where no instantiation can run the shape; 0: the policy
+AttentionPlan plan_rel_attention(int batch, int heads, int head_dim, int tmax, int window, int force = 0);
 struct LayerNormPlan : LaunchGrid {
     int tw = 0;  // time steps per block
 };
-LayerNormPlan plan_add_layer_norm(int channels, int batch, int tmax);
+// force_tw 32 or 64 (vits_op_layer_norm): that tile whatever VITS_LN_TW says, or a refusal for any other value; 0: the policy
+LayerNormPlan plan_add_layer_norm(int channels, int batch, int tmax, int force_tw = 0);
 LaunchGrid plan_dds_depthwise(int channels, int k, int dil, int batch, int tmax);
 // one DDS layer; `ok` is the shape part of dds_layer_supported / dds_layer_lat_supported. m: the kernel's bound on 32-channel chunks
 struct DdsLayerPlan : LaunchGrid {

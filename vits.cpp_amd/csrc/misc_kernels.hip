@@ -630,9 +630,9 @@ __global__ __launch_bounds__(64 * NW, LAT ? 2 : (SHORT ? 4 : 3)) void rel_attent
 }
 
 hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const float* rel_k, const float* rel_v, TensorRef out, const int* lens, int batch,
-                                int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs) {
+                                int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs, int force) {
     // (which kernel, how many waves, which variant, LDS: plan_rel_attention, launch_plan.cpp)
-    const AttentionPlan l = plan_rel_attention(batch, heads, head_dim, tmax, window);
+    const AttentionPlan l = plan_rel_attention(batch, heads, head_dim, tmax, window, force);
     if (!l.ok) return hipErrorInvalidValue;
     const dim3 grid(l.gx, l.gy, l.gz), block(l.block);
     if (l.mfma) {
@@ -742,8 +742,8 @@ __global__ __launch_bounds__(TW * LN_GROUPS) void add_layer_norm_kernel(const fl
 }
 
 hipError_t launch_add_layer_norm(TensorRef x, TensorRef res, const float* gamma, const float* beta, TensorRef y, const int* lens, int batch, int channels,
-                                 int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs) {
-    const LayerNormPlan l = plan_add_layer_norm(channels, batch, tmax);
+                                 int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs, int force_tw) {
+    const LayerNormPlan l = plan_add_layer_norm(channels, batch, tmax, force_tw);
     if (!l.ok) return hipErrorInvalidValue;
     const dim3 grid(l.gx, l.gy), block(l.block);
 #define VITS_LN_LAUNCH(TW)                                                                                                                                \
