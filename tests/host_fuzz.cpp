@@ -1,5 +1,5 @@
 // host_fuzz.cpp — TEST INFRASTRUCTURE: the product's host code that eats untrusted bytes (vits_model_load_from_bytes' parser, hyper-parameter reader,
-// per-tensor shape validation, packing, tokenizer, writer: model_file.cpp, engine_load.cpp, engine_support.cpp, abi.cpp) under AddressSanitizer + UBSan and a
+// per-tensor shape validation, packing, tokenizer, writer: model_file.cpp, engine_load.cpp, engine_support.cpp, abi.cpp; the operator files abi_ops_*.cpp are linked in and not reached) under AddressSanitizer + UBSan and a
 // seeded mutation fuzzer (only the oracle ever saw a sanitizer). Linked against the SANITIZED build of the product's host translation
 // units (vits.cpp_amd/csrc/Makefile target `asan`), driven through the C ABI only — the entry points a caller hands a file to:
 //   vits_model_file_validate (= everything Engine::load checks and packs, without a device), vits_model_file_reserialize, vits_model_file_tokenize.
