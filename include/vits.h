@@ -561,6 +561,60 @@ VITS_API int64_t vits_model_last_edges(vits_model* model, int64_t* dst, size_t c
 VITS_API int vits_edges_plan(int32_t rate, const vits_edges_desc* desc, int64_t out[8]);
 VITS_API int vits_edges_host(const float* pcm, size_t n, int32_t rate, const vits_edges_desc* desc, float* y, size_t y_cap, int64_t row[4]);
 
+/* ---- joined tracks: the utterances of a batch laid end to end, on the device ------------------------------------------------------------
+ * The stages above state rate, level, ceiling and edges of ONE utterance; a paragraph is several, laid end to end with a stated gap or overlap.
+ * This section states that layout and gives it as a device operator (vits_op_join, on model-rate rows: the rows a call delivers with no level
+ * and no output rate set) with its host-only plan and sequential definition. A model-level call that joins inside the engine, in front of the
+ * handle's level, limiter and resampler, is not part of the library yet.
+ *
+ * The definition. Model-rate rows x_b[0, n_b), b = 0 .. B - 1, at rate fs: n_b is the utterance's delivered length, N'_b as the edges stage
+ * leaves it, or the vocoder's sample count with the stage off. Integer divisions truncate.
+ *   track[b]   the track of utterance b: track[0] = 0 and each step track[b] - track[b - 1] is 0 or 1, so the utterances of a track are
+ *              consecutive and in order. NULL: one track. G = track[B - 1] + 1.
+ *   gap_ms[b]  a finite float in [-2000, 60000]: the distance between utterance b and its predecessor in the same track. NULL: 0 everywhere. For
+ *              the first utterance of a track it is validated and ignored.
+ *   g_b = sign(ms) * floor(|ms| * fs / 1000 + 0.5) as int64: the rounding of samples(ms) of the edges definition.
+ *   step_b (b not first in its track) = g_b if g_b >= 0, else -v_b with v_b = min(-g_b, n_(b-1) / 2, n_b / 2): no utterance gives more than half
+ *              of itself to either neighbour.
+ *   o_b = 0 for the first of a track, else o_(b-1) + n_(b-1) + step_b. The track's length is T_g = o_last + n_last.
+ *   y_g[j], 0 <= j < T_g, by the utterances of track g with o_b <= j < o_b + n_b: none: +0; one: x_b[j - o_b], bit for bit; two:
+ *              x_(b-1)[j - o_(b-1)] + x_b[j - o_b], one fp32 add.
+ *   There are never three, and the two are neighbours. o_b - o_(b-1) = n_(b-1) + step_b >= n_(b-1) - n_(b-1) / 2 >= 0 and (o_b + n_b) -
+ *   (o_(b-1) + n_(b-1)) = step_b + n_b >= n_b - n_b / 2 >= 0: starts and ends are non-decreasing along a track. And the end of b - 1 is
+ *   o_b - step_b <= o_b + n_b / 2 <= o_b + n_b - n_b / 2 <= o_(b+1): utterance b - 1 has ended where b + 1 begins.
+ *   bound_g = sum of bound(n_b) + sum of max(g_b, 0) over the track, bound(n_b) being what the host knows of n_b before the rows are read
+ *   (N + Pl + Pt under the edges stage, n_b itself where the lengths are on the host): [T_g, bound_g) is written as zero, nothing is written
+ *   behind the bound, nothing behind n_b is read.
+ * Cross-fades: with the edges stage on and fade_out_ms = fade_in_ms = -gap_ms (and no lead or tail pad), the two raised-cosine tables sum to 1
+ * sample by sample (0.5 - 0.5 cos(pi (k + 0.5) / F) and its mirror image), so the overlap is a constant-gain cross-fade, unless the half rule
+ * shortened it. With the stage off an overlap is a plain sum, and that is the caller's business. How such a cross-fade sounds on real speech
+ * has not been judged: the project's fixtures are synthetic.
+ * Only a copy and one add touch a sample: batch position, track partition, tiles and streams enter no bit. */
+/* Host only, no device needed. vits_join_plan: utt_bounds [batch] = bound(n_b) of every utterance at `rate` (from a frames_only call, or the
+ * lengths themselves), track and gap_ms as defined above -> *tracks_out = G, track_bounds_out [G] (room for `batch` entries) = bound_g,
+ * *tile_out = the samples of a track per block of the device's kernel: what a caller sizes the tracks' buffer with. Any output may be NULL. 0,
+ * or -1 + message: a batch outside [1, 65535], a track[0] that is not 0 or a step other than 0 or 1, a gap that is not finite or out of range
+ * (naming the utterance), a rate outside [4000, 192000], an utterance bound outside [0, 2^30], a track bound above 2^30 (from its pauses alone,
+ * or with its utterances).
+ * vits_join_host: the definition evaluated sequentially, with the same single fp32 add, so y is comparable bit for bit with the device's. x
+ * [batch][x_stride], lens [batch] = n_b (they are their own bounds), y [G][y_stride] (optional; row g gets its bound_g samples, T_g of the
+ * track, then zeros), track_lens_out [G] = T_g and offsets_out [batch][2] = {o_b, n_b} (both optional). 0, or -1 + message (as above, a lens[b]
+ * above x_stride, a y_stride below the largest bound). */
+VITS_API int vits_join_plan(int32_t rate, int32_t batch, const int32_t* track, const float* gap_ms, const int64_t* utt_bounds, int32_t* tracks_out,
+                            int64_t* track_bounds_out, int32_t* tile_out);
+VITS_API int vits_join_host(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const int32_t* track,
+                            const float* gap_ms, float* y, int64_t y_stride, int64_t* track_lens_out, int64_t* offsets_out);
+
+/* ---- text in: the sentences of a paragraph ------------------------------------------------------------------------------------------------------
+ * vits_split_sentences (host only) works on the bytes of a NUL-terminated text. A sentence ends at the end of the text, after a run of '.', '!',
+ * '?' that ASCII whitespace follows ("a.b" is one span; "wait... what?! ok" is three), or after U+3002, U+FF01 or U+FF1F, which need no
+ * whitespace. A whitespace run that holds two or more '\n' ends a span too, and the paragraph: the last span in front of it is of kind 1, every
+ * other of kind 0. Leading and trailing ASCII whitespace is dropped from each span; a span that is empty, or holds terminators alone, is not
+ * reported. Returns the number of spans; the first `cap` of them are written as byte ranges [starts[i], ends[i]) and kinds[i] (any array may be
+ * NULL), so a call with cap = 0 sizes the arrays. -1 + message: text NULL.
+ * The kinds are what a caller picks the gap in front of the next sentence by (vits_join_plan: gap_ms). */
+VITS_API int64_t vits_split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_t* kinds, size_t cap);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -1054,6 +1108,15 @@ VITS_API int vits_op_limit(const vits_limit_desc* d, const float* x, const int64
  * empty batch, a lens[b] outside [0, x_stride] or above 2^30, a y_stride below the largest bound. */
 VITS_API int vits_op_edges(int32_t rate, const vits_edges_desc* desc, int32_t batch, const float* x, int64_t x_stride, const int32_t* lens, float* y,
                            int64_t y_stride, int32_t* lens_out, int64_t* rows);
+
+/* The join kernels (see "joined tracks" above for the definition) on a ragged batch: host arrays in, host arrays out, staged as
+ * vits_op_level stages its rows. x [batch][x_stride] at `rate` goes up as it is; lens [batch] int32, 0 <= lens[b] <= x_stride, are the
+ * utterances' own bounds: nothing behind a row's samples is read; track and gap_ms as in vits_join_plan; y [G][y_stride] goes up too and comes
+ * back: row g gets its bound_g samples (T_g of the track, then zeros), everything behind them is as it was; track_lens_out [G] int32 = T_g;
+ * offsets_out [batch][2] int64 = {o_b, n_b}. Refused (-1 + message): what vits_join_plan refuses, a NULL x, lens, y, track_lens_out or
+ * offsets_out, a lens[b] outside [0, x_stride], a y_stride below the largest bound. */
+VITS_API int vits_op_join(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int32_t* lens, const int32_t* track, const float* gap_ms,
+                          float* y, int64_t y_stride, int32_t* track_lens_out, int64_t* offsets_out);
 
 /* ---- PCM16 / WAV sink (reference driver test/main.cpp:23-63: clamp to [-1,1], * 32767, truncate; 16 kHz mono) ------ */
 VITS_API void vits_pcm16_from_float(const float* pcm, size_t n, int16_t* out);

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_set_edges", "vits_model_get_edges", "vits_model_last_edges", "vits_edges_plan", "vits_edges_host", "vits_op_edges",
+    "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
@@ -375,6 +376,14 @@ def lib():
     L.vits_edges_host.argtypes = [vp, sz, i32, C.POINTER(EdgesDesc), vp, sz, vp]
     L.vits_op_edges.restype = i32
     L.vits_op_edges.argtypes = [i32, C.POINTER(EdgesDesc), i32, vp, i64, vp, vp, i64, vp, vp]
+    L.vits_join_plan.restype = i32
+    L.vits_join_plan.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp]
+    L.vits_join_host.restype = i32
+    L.vits_join_host.argtypes = [i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]
+    L.vits_op_join.restype = i32
+    L.vits_op_join.argtypes = [i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]
+    L.vits_split_sentences.restype = i64
+    L.vits_split_sentences.argtypes = [C.c_char_p, vp, vp, vp, sz]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -1692,6 +1701,80 @@ def edges(x, rate, mode=EDGES_PAD, lens=None, out=None, **fields):
             if p.value:
                 hip.hipFree(p)
     return out, lens_out, rows
+
+
+def _join_args(B, track, gap_ms):
+    tr = None if track is None else np.ascontiguousarray(track, dtype=np.int32).ravel()
+    gp = None if gap_ms is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gap_ms, np.float32).ravel(), (max(B, np.size(gap_ms)),)))
+    return tr, gp
+
+
+def join_plan(rate, utt_bounds, track=None, gap_ms=None):
+    """vits_join_plan: (G, bounds int64 [G], tile) of utterances whose bounds (model-rate samples) are utt_bounds, laid into tracks by
+    track (int32 [B], None = one track) and gap_ms (a scalar or float32 [B], None = 0), host only"""
+    ub = np.ascontiguousarray(utt_bounds, dtype=np.int64).ravel()
+    B = ub.size
+    tr, gp = _join_args(B, track, gap_ms)
+    G, tile, bounds = C.c_int32(0), C.c_int32(0), np.zeros(max(B, 1), np.int64)
+    if lib().vits_join_plan(int(rate), B, _ptr(tr), _ptr(gp), _ptr(ub), C.byref(G), _ptr(bounds), C.byref(tile)) != 0:
+        raise VitsError(last_error())
+    return G.value, bounds[: G.value].copy(), tile.value
+
+
+def join_host(x, rate, lens=None, track=None, gap_ms=None):
+    """vits_join_host: the definition of include/vits.h evaluated sequentially on the host (no device needed). x: float32 [B, x_stride]; lens: samples per
+    row (None = the whole row). Returns (y float32 [G, largest bound]: T_g samples of each track, then zeros up to its bound, track_lens int64 [G], rows
+    int64 [B, 2] = o_b, n_b)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    G, bounds, _ = join_plan(rate, ln, track, gap_ms)
+    tr, gp = _join_args(B, track, gap_ms)
+    ys = max(int(bounds.max()), 1)
+    y, tl, rows = np.full((G, ys + 1), np.nan, np.float32), np.zeros(G, np.int64), np.zeros((B, 2), np.int64)
+    if lib().vits_join_host(int(rate), B, _ptr(x), max(stride, 1), _ptr(ln), _ptr(tr), _ptr(gp), _ptr(y), ys + 1, _ptr(tl), _ptr(rows)) != 0:
+        raise VitsError(last_error())
+    for g in range(G):
+        assert np.isnan(y[g, bounds[g]:]).all()  # (nothing behind the bound)
+    return y[:, :ys], tl, rows
+
+
+def join(x, rate, lens=None, track=None, gap_ms=None, out=None):
+    """The join kernels on a ragged batch (vits_op_join). x: float32 [B, x_stride] at `rate`, uploaded as it is (what lies behind a row's samples
+    included); lens: samples per row (None = the whole row); out: float32 [G, y_stride] uploaded as the initial contents of y (None = zeros of the largest
+    bound). Returns (y [G, y_stride], track_lens int32 [G], rows int64 [B, 2] = o_b, n_b)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32).ravel()
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    tr, gp = _join_args(B, track, gap_ms)
+    if out is None:
+        G, bounds, _ = join_plan(rate, ln, track, gap_ms)
+        out = np.zeros((G, max(int(bounds.max()), 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [G, y_stride] array")
+    xs = x if x.size else np.zeros((B, 1), np.float32)
+    tl, rows = np.full(out.shape[0], -1, np.int32), np.full((B, 2), -1, np.int64)
+    if lib().vits_op_join(int(rate), B, _ptr(xs), max(stride, 1), _ptr(ln), _ptr(tr), _ptr(gp), _ptr(out), out.shape[1], _ptr(tl), _ptr(rows)) != 0:
+        raise VitsError(last_error())
+    return out, tl, rows
+
+
+def split_sentences(text):
+    """vits_split_sentences: [(start, end, kind)] of the sentences of a text, byte offsets into its UTF-8 encoding; kind 1: the span ends a paragraph"""
+    raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    n = lib().vits_split_sentences(raw, None, None, None, 0)
+    if n < 0:
+        raise VitsError(last_error())
+    st, en, kd = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+    if lib().vits_split_sentences(raw, _ptr(st), _ptr(en), _ptr(kd), n) != n:
+        raise VitsError(last_error())
+    return [(int(st[i]), int(en[i]), int(kd[i])) for i in range(n)]
 
 
 def op_rel_attention(q, k, v, rel_k, rel_v, heads, window, lens=None):

@@ -775,6 +775,46 @@ VITS_API int vits_edges_host(const float* pcm, size_t n, int32_t rate, const vit
     return 0;
     VITS_CATCH(-1)
 }
+
+// ---- joined tracks (include/vits.h: the definition): the host-only side -------------------------------------------------------------------
+VITS_API int vits_join_plan(int32_t rate, int32_t batch, const int32_t* track, const float* gap_ms, const int64_t* utt_bounds, int32_t* tracks_out,
+                            int64_t* track_bounds_out, int32_t* tile_out) {
+    VITS_TRY
+    if (!utt_bounds) return fail("vits_join_plan: null argument (utt_bounds)");
+    vits::JoinPlan p;
+    std::string err;
+    if (!vits::join_plan(rate, batch, track, gap_ms, p, err) || !vits::join_bounds(p, utt_bounds, err)) return fail("vits_join_plan: " + err);
+    if (tracks_out) *tracks_out = p.tracks;
+    if (track_bounds_out) std::copy(p.bound.begin(), p.bound.end(), track_bounds_out);
+    if (tile_out) *tile_out = vits::kJoinTile;
+    return 0;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_join_host(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const int32_t* track, const float* gap_ms, float* y,
+                            int64_t y_stride, int64_t* track_lens_out, int64_t* offsets_out) {
+    VITS_TRY
+    if (!lens || (y && !x)) return fail("vits_join_host: null argument (lens, or x with y given)");
+    vits::JoinPlan p;
+    std::string err;
+    if (!vits::join_plan(rate, batch, track, gap_ms, p, err)) return fail("vits_join_host: " + err);
+    for (int b = 0; b < batch; ++b)
+        if (y && lens[b] > x_stride) return fail("vits_join_host: lens[" + std::to_string(b) + "] = " + std::to_string(lens[b]) + " is above x_stride = " + std::to_string(x_stride));
+    if (!vits::join_bounds(p, lens, err)) return fail("vits_join_host: " + err);
+    if (y && y_stride < p.max_bound) return fail("vits_join_host: y_stride = " + std::to_string(y_stride) + " is below the largest track bound (" + std::to_string(p.max_bound) + " samples)");
+    vits::join_host(p, x, x_stride, lens, y, y_stride, track_lens_out, offsets_out);
+    return 0;
+    VITS_CATCH(-1)
+}
+
+// ---- text in: the sentences of a paragraph ---------------------------------------------------------------------------------------------------------
+VITS_API int64_t vits_split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_t* kinds, size_t cap) {
+    VITS_TRY
+    if (!text) return fail("vits_split_sentences: null argument (text)");
+    return vits::split_sentences(text, starts, ends, kinds, cap);
+    VITS_CATCH(-1)
+}
+
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }

@@ -1,5 +1,5 @@
 // abi_ops_pcm.cpp — operator-level entry points of the PCM kernels: vits_op_resample, vits_op_level, vits_op_limit (host arrays in, host arrays out; staging:
-// abi_ops_common.h) and vits_op_edges (device arrays, as the engine's delivery calls it).
+// abi_ops_common.h), vits_op_edges (device arrays, as the engine's delivery calls it) and vits_op_join (host arrays; y goes up and comes back).
 #include <cmath>
 
 #include "abi_ops_common.h"
@@ -222,5 +222,43 @@ VITS_API int vits_op_edges(int32_t rate, const vits_edges_desc* desc, int32_t ba
     if (e == hipSuccess) e = launch_edges_bounds(c, nullptr);
     if (e == hipSuccess) e = launch_edges_apply(c, nullptr);
     return finish(e) ? 0 : -1;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_join(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int32_t* lens, const int32_t* track, const float* gap_ms, float* y,
+                          int64_t y_stride, int32_t* track_lens_out, int64_t* offsets_out) {
+    VITS_TRY
+    if (!x || !lens || !y || !track_lens_out || !offsets_out || batch <= 0 || x_stride <= 0 || y_stride <= 0) return fail("vits_op_join: null argument or empty batch");
+    JoinPlan plan;
+    std::string err;
+    if (!join_plan(rate, batch, track, gap_ms, plan, err)) return fail("vits_op_join: " + err);
+    std::vector<int64_t> ub((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        if (lens[b] < 0 || lens[b] > x_stride) return fail("vits_op_join: lens[" + std::to_string(b) + "] = " + std::to_string(lens[b]) + " is outside [0, x_stride = " + std::to_string(x_stride) + "]");
+        ub[(size_t)b] = lens[b];
+    }
+    if (!join_bounds(plan, ub.data(), err)) return fail("vits_op_join: " + err);
+    if (y_stride < plan.max_bound) return fail("vits_op_join: y_stride = " + std::to_string(y_stride) + " is below the largest track bound (" + std::to_string(plan.max_bound) + " samples)");
+    const std::vector<int64_t> table = join_table(plan);
+    const int G = plan.tracks;
+    const size_t ny = (size_t)G * y_stride * 4;
+    DevMem dx, dy, dn, dt, drows, dtl;
+    // (y goes up too: what lies behind a track's bound must come back as it was)
+    if (!dx.put(x, (size_t)batch * x_stride * 4) || !dy.put(y, ny) || !dn.put(lens, (size_t)batch * 4) || !dt.put(table.data(), table.size() * 8) ||
+        !drows.fill((size_t)batch * 2 * 8, 0) || !dtl.fill((size_t)G * 4, 0))
+        return -1;
+    JoinCall c;
+    c.plan = &plan;
+    c.x = dx.f();
+    c.x_stride = x_stride;
+    c.lens = dn.i();
+    c.y = dy.f();
+    c.y_stride = y_stride;
+    c.table = static_cast<const int64_t*>(dt.p);
+    c.rows = static_cast<int64_t*>(drows.p);
+    c.track_lens = dtl.i();
+    hipError_t e = launch_join_offsets(c, nullptr);
+    if (e == hipSuccess) e = launch_join_apply(c, nullptr);
+    return finish(e) && dy.get(y, ny) && drows.get(offsets_out, (size_t)batch * 2 * 8) && dtl.get(track_lens_out, (size_t)G * 4) ? 0 : -1;
     VITS_CATCH(-1)
 }

@@ -805,6 +805,50 @@ hipError_t launch_edges_window(const EdgesCall& c, hipStream_t s);
 hipError_t launch_edges_bounds(const EdgesCall& c, hipStream_t s);
 hipError_t launch_edges_apply(const EdgesCall& c, hipStream_t s);
 
+// ---- joined tracks: the utterances of a batch laid end to end (join.hip; the definition: include/vits.h "joined tracks", DESIGN.md §8 "Joined
+// tracks") ----
+// Utterance b of track g lies at o_b: 0 for the first of a track, else o_(b-1) + n_(b-1) + step_b, step_b = g_b for a gap g_b >= 0 and
+// -min(-g_b, n_(b-1) / 2, n_b / 2) for an overlap. The half rule makes o_b and o_b + n_b non-decreasing along a track, and lets at most two utterances, always
+// neighbours, cover a sample: y is +0, a copy, or one fp32 add.
+constexpr int kJoinTile = 1024;  // samples of a track per block of join_apply_kernel
+constexpr float kJoinMinGapMs = -2000.f, kJoinMaxGapMs = 60000.f;
+struct JoinPlan {
+    int rate = 0, batch = 0, tracks = 0;
+    std::vector<int> first;       // [tracks + 1]: track g holds the utterances [first[g], first[g + 1])
+    std::vector<int64_t> gap;     // [batch]: g_b in samples; 0 for the first utterance of a track (validated and ignored)
+    std::vector<int64_t> ubound;  // [batch]: what the host knows of n_b (the device clamps n_b to it); empty until join_bounds
+    std::vector<int64_t> bound;   // [tracks]: the sum of the track's ubound and of its positive gaps; empty until join_bounds
+    int64_t max_bound = 0, max_ubound = 0;
+};
+// host only (join_host.cpp). join_plan: the tracks and the gaps. false + a message: a rate outside [4000, 192000], batch outside [1, 65535], track[0] != 0 or a step
+// other than 0 or 1, a gap that is not finite or outside [-2000, 60000] ms (naming the utterance), a track whose positive gaps alone pass kEdgesMaxLen. track NULL: one track; gap_ms NULL: 0 everywhere
+bool join_plan(int rate, int batch, const int32_t* track, const float* gap_ms, JoinPlan& p, std::string& err);
+// ... and the bounds, once the host knows every utterance's. false + a message: an utterance bound outside [0, kEdgesMaxLen], a track bound above kEdgesMaxLen
+bool join_bounds(JoinPlan& p, const int64_t* utt_bounds, std::string& err);
+// the table the kernels read, int64: [batch][2] = {g_b, ubound_b}, then [tracks][3] = {first, end, bound}
+std::vector<int64_t> join_table(const JoinPlan& p);
+inline size_t join_table_elems(int batch, int tracks) { return (size_t)2 * batch + (size_t)3 * tracks; }
+// the definition, sequentially: lens [batch] (clamped to [0, ubound_b] as the device does), x [batch][x_stride] -> y [tracks][y_stride] (optional: row g gets
+// bound_g samples), track_lens [tracks] = T_g, rows [batch][2] = {o_b, n_b} (both optional)
+void join_host(const JoinPlan& p, const float* x, int64_t x_stride, const int64_t* lens, float* y, int64_t y_stride, int64_t* track_lens, int64_t* rows);
+// vits_split_sentences (include/vits.h): the spans of a text, in bytes; returns how many there are (the first `cap` of them are written)
+int64_t split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_t* kinds, size_t cap);
+struct JoinCall {
+    const JoinPlan* plan = nullptr;  // host: what the table was made from (join_call_ok checks every index the kernels take from it)
+    const float* x = nullptr;        // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;  // device [batch]: valid samples of each row; nothing behind min(lens[b], ubound_b) is read
+    float* y = nullptr;         // device [tracks][y_stride], not x: row g gets bound_g samples, the rest is left as it was
+    int64_t y_stride = 0;
+    const int64_t* table = nullptr;  // device: join_table(plan), 8-byte aligned
+    int64_t* rows = nullptr;         // device [batch][2]: o_b, n_b
+    int* track_lens = nullptr;       // device [tracks]: T_g
+};
+// the two passes, in this order on one stream: one block per track walks its utterances (rows, track_lens) | grid (tiles of the largest bound, tracks): a
+// binary search over the monotone ends for the first utterance that reaches the tile, then a walk forward; every sample of [0, bound_g) is written once
+hipError_t launch_join_offsets(const JoinCall& c, hipStream_t s);
+hipError_t launch_join_apply(const JoinCall& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
