@@ -716,6 +716,22 @@ VITS_API int64_t vits_prof_report(vits_model* model, char* buf, size_t cap);
  * The plane buffers are filled with bf16 NaNs before the conversion, so a read past an utterance's length shows in the
  * result. vits_op_conv_transpose1d has no split form (the upsamplers are fp32 kernels in that mode) and refuses. */
 VITS_API int vits_op_set_arith(int32_t arith);
+/* Launches of this process (engine and operator calls alike) that ran over a list of existing tiles instead of their dense grid (ragged batches,
+ * VITS_TILE_MAP / VITS_NO_TILE_MAP). A counter for tests: the results never depend on the form of a launch. */
+VITS_API uint64_t vits_op_tile_map_launches(void);
+/* The byte every output buffer of vits_op_conv1d, vits_op_conv_transpose1d, vits_op_resblock_pair and vits_op_resblock holds on the device before the kernels
+ * run, on this thread: 0 (the default: what no kernel wrote comes back zero) or 0xFF (an fp32 NaN: a test sees a stray store of any value, zero included). */
+VITS_API int vits_op_set_output_fill(int32_t byte);
+/* The same-position convolutions of two or three ResBlocks of a vocoder stage as ONE launch (conv_group_kernel; over the lists of existing tiles:
+ * conv_group_list_kernel), as the engine's grouped schedule launches them: member i is y_i = leaky_relu(b_i + conv_i(leaky_relu(x_i))) with k[i] taps (11, 7 or 3,
+ * each at most once) at `dilation` (1, 3 or 5), channels a multiple of 128, fp32 only. x, y: host [n][batch][channels][t_stride]; w: the members' weights one
+ * behind the other, member i [C][C][k[i]] (torch layout); bias: [n][C] or NULL; lens optional. Columns the kernels do not write come back as 0xFF bytes. */
+typedef struct vits_conv_group_desc {
+    int32_t batch, channels, t, t_stride;
+    int32_t n, k[3], dilation;
+    float slope;
+} vits_conv_group_desc;
+VITS_API int vits_op_conv_group(const vits_conv_group_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y);
 
 /* conv1d_with_bias (vits.cpp:171-176 -> custom-ops.h:680-694) with the fusions the engine uses.
  * y = post( conv(pre(x)) + bias ), pre: 0 none, 1 leaky_relu(slope); post: 0 none, 1 relu,

@@ -18,7 +18,7 @@ _SPLIT = re.compile(r"conv_split_kernel<(-?\d+), (-?\d+), (\d+)>")
 _CONVT16 = re.compile(r"convt16_kernel<(\d+), (\d+), (\d+), (\w+)>")
 _CONVT16L = re.compile(r"convt16_lines_kernel<(\d+), (\w+)>")
 _RBBLOCK32 = re.compile(r"rbblock32_kernel<(\d+), (\d+)>")
-_GROUP = re.compile(r"conv_group_kernel<(-?\d+)>")
+_GROUP = re.compile(r"conv_group(?:_list)?_kernel<(-?\d+)>")  # (_list: the same launch over the lists of existing tiles of a ragged batch)
 _RBPAIR32 = re.compile(r"rbpair32_kernel<(-?\d+), (-?\d+), (\d+)>")
 _RBPAIR16 = re.compile(r"rbpair16_kernel<(-?\d+), (-?\d+), (\d+), (\d+), (\w+)(?:, \w+)?>")
 # conv16.hip: (WM, WN, MR, NR) -> tile index; Epi16 -> the epilogue tag the engine prints

@@ -51,7 +51,7 @@ EXPORTED_SYMBOLS = [
     "vits_prof_enable", "vits_prof_reset", "vits_prof_report", "vits_op_conv1d", "vits_op_conv_transpose1d",
     "vits_op_rel_attention", "vits_op_add_layer_norm", "vits_device_info", "vits_set_device", "vits_model_file_reserialize",
     "vits_model_file_tokenize", "vits_pcm16_from_float", "vits_write_wav16", "vits_pcm16_from_float_device",
-    "vits_model_set_arith", "vits_model_get_arith", "vits_model_file_validate", "vits_op_set_arith",
+    "vits_model_set_arith", "vits_model_get_arith", "vits_model_file_validate", "vits_op_set_arith", "vits_op_tile_map_launches", "vits_op_set_output_fill", "vits_op_conv_group",
     "vits_model_set_arith_scope", "vits_model_get_arith_scope", "vits_model_submit_batch", "vits_model_wait", "vits_model_pending",
     "vits_model_set_ggml_tables", "vits_model_get_ggml_tables",
     "vits_model_set_speaker", "vits_model_get_speaker", "vits_model_num_speakers",
@@ -130,6 +130,11 @@ class Conv1dDesc(C.Structure):
 
 class ResblockPairDesc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("k", C.c_int32),
+                ("dilation", C.c_int32), ("slope", C.c_float)]
+
+
+class ConvGroupDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("n", C.c_int32), ("k", C.c_int32 * 3),
                 ("dilation", C.c_int32), ("slope", C.c_float)]
 
 
@@ -1193,6 +1198,41 @@ def op_set_arith(arith):
     f.restype, f.argtypes = C.c_int32, [C.c_int32]
     if f(arith) != 0:
         raise VitsError(last_error())
+
+
+def op_tile_map_launches():
+    """Launches of this process that ran over a list of existing tiles instead of their dense grid (vits_op_tile_map_launches; ragged batches under
+    VITS_TILE_MAP / by default on large grids). For tests: results never depend on it."""
+    f = lib().vits_op_tile_map_launches
+    f.restype, f.argtypes = C.c_uint64, []
+    return int(f())
+
+
+def op_set_output_fill(byte):
+    """0 (default) or 0xFF: what the outputs of op_conv1d / op_conv_transpose1d / op_resblock_pair / op_resblock hold before the kernels run, on this thread
+    (vits_op_set_output_fill; 0xFF = fp32 NaN, so that a stray store of ANY value behind an utterance's end shows)."""
+    f = lib().vits_op_set_output_fill
+    f.restype, f.argtypes = C.c_int32, [C.c_int32]
+    if f(int(byte)) != 0:
+        raise VitsError(last_error())
+
+
+def op_conv_group(x, ws, biases, dilation, slope, lens=None):
+    """The grouped launch of two or three same-position ResBlock convolutions (vits_op_conv_group): x [n, B, C, T]; ws a list of n weights [C, C, k_i] with
+    k_i in {11, 7, 3}; biases [n, C] or None. Returns y [n, B, C, T], NaN (0xFF bytes) where no kernel wrote."""
+    x = _f32(x)
+    n, B, ch, T = x.shape
+    assert len(ws) == n and all(w.shape[:2] == (ch, ch) for w in ws)
+    w = np.concatenate([_f32(w).ravel() for w in ws])
+    d = ConvGroupDesc(B, ch, T, T, n, (C.c_int32 * 3)(*([int(w.shape[2]) for w in ws] + [0, 0, 0])[:3]), dilation, slope)
+    y = np.empty((n, B, ch, T), np.float32)
+    biases = _f32(biases)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    f = lib().vits_op_conv_group
+    f.restype, f.argtypes = C.c_int32, [C.POINTER(ConvGroupDesc)] + [C.c_void_p] * 5
+    if f(C.byref(d), _ptr(x), _ptr(w), _ptr(biases), _ptr(lens), _ptr(y)) != 0:
+        raise VitsError(last_error())
+    return y
 
 
 def op_conv1d(x, w, bias=None, dilation=1, pad_left=None, pre_slope=None, post_act=0, residual=None, accum=None,

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,6 +19,7 @@
 #include "engine.h"
 
 namespace vits {
+extern thread_local int g_op_out_fill;  // vits_op_set_output_fill (abi_ops_conv.cpp)
 extern thread_local int g_op_arith;  // vits_op_set_arith (abi_ops_conv.cpp): the arithmetic of this thread's operator calls
 
 // a helper's failure: the error text is set, the entry point returns -1
@@ -108,6 +110,42 @@ inline bool unstage_group8(const DevMem& src, T* dst, int batch, int channels, i
         }
     return true;
 }
+
+// ---- ragged batches on lists of existing tiles (tile_map.h) ------------------------------------------------------------------------------------------------
+// The operators' kernel knobs: the process defaults, with VITS_TILE_MAP / VITS_NO_TILE_MAP read again at EVERY call — a test runs the dense grid and the lists
+// in one process and compares the bits. (Operator calls are test infrastructure; the engine reads its knobs once, at load.)
+struct OpKnobs {
+    KernelKnobs k;
+    KernelKnobsScope scope;
+    OpKnobs() : k(kernel_knobs()), scope(&k) {
+        k.no_tile_map = getenv("VITS_NO_TILE_MAP") != nullptr;
+        k.tile_map = getenv("VITS_TILE_MAP") != nullptr;
+    }
+};
+// The lists of ONE length vector on the device, built by the engine's builder for the tile widths the operator names (those its launchers may plan; a width no
+// launch takes is a list nobody reads). As in the engine a list exists where the dense grid would hold empty blocks, or everywhere under VITS_TILE_MAP; whether
+// a launch is large enough to take it is the launcher's rule (tile_map_for). lens NULL: every utterance t_in / t_out long.
+struct OpTileMaps {
+    TileMapSet set;
+    std::vector<std::unique_ptr<DevMem>> mem;
+    bool add(const int32_t* len_in, const int32_t* len_out, int batch, int t_in, int t_out, int width, bool convt) {
+        const KernelKnobs& kn = kernel_knobs();
+        if (kn.no_tile_map || set.find(width, convt)) return true;
+        std::vector<int> la(batch, t_in), lb(batch, t_out);
+        if (len_in) la.assign(len_in, len_in + batch);
+        if (len_out) lb.assign(len_out, len_out + batch);
+        if (!kn.tile_map && !tile_map_needed(la.data(), lb.data(), batch, t_in, t_out, width, convt)) return true;
+        std::vector<TileEntry> e((size_t)tile_map_count(la.data(), lb.data(), batch, width, convt) + 1);  // (+ 1: an empty list still has an address)
+        const int64_t n = tile_map_fill(la.data(), lb.data(), batch, width, convt, e.data());
+        mem.emplace_back(new DevMem);
+        if (!mem.back()->put(e.data(), e.size() * sizeof(TileEntry))) return false;
+        return set.add(TileMapRef{static_cast<const TileEntry*>(mem.back()->p), (int)n, width, convt}) || refuse("too many tile widths for one length vector");
+    }
+    // every width a conv over these lengths can run a list on (conv_tile_mapped: the throughput tiles of conv_mfma.hip, 128 and 256 columns)
+    bool add_conv(const int32_t* len_in, const int32_t* len_out, int batch, int t_in, int t_out, bool convt) {
+        return add(len_in, len_out, batch, t_in, t_out, tile_shape(TILE_128x128).bn(), convt) && add(len_in, len_out, batch, t_in, t_out, tile_shape(TILE_64x256).bn(), convt);
+    }
+};
 
 // ---- convs ------------------------------------------------------------------------------------------------------------------------------------------------
 struct Conv {

@@ -7,6 +7,7 @@
 
 namespace vits {
 thread_local int g_op_arith = VITS_ARITH_F32;
+thread_local int g_op_out_fill = 0;  // vits_op_set_output_fill: the byte the conv operators' outputs hold before the kernels run
 }
 using namespace vits;
 
@@ -96,19 +97,70 @@ VITS_API int vits_op_set_arith(int32_t arith) {
     return 0;
 }
 
+VITS_API int vits_op_set_output_fill(int32_t byte) {
+    if (byte != 0 && byte != 0xFF) return fail("vits_op_set_output_fill: 0 (zeros) or 0xFF (NaN)");
+    g_op_out_fill = byte;
+    return 0;
+}
+
+// The same-position convolutions of two or three ResBlocks as ONE launch (launch_conv_group), each member as the engine builds the first conv of a pair
+// (mk_c1: leaky_relu on load, its result stored activated). Outputs are staged as 0xFF bytes.
+VITS_API int vits_op_conv_group(const vits_conv_group_desc* d, const float* x, const float* w, const float* bias, const int32_t* lens, float* y) {
+    VITS_TRY
+    if (!d || !x || !w || !y) return fail("vits_op_conv_group: null argument");
+    if (g_op_arith != VITS_ARITH_F32) return fail("vits_op_conv_group: VITS_ARITH_F32 only");
+    if (d->n < 2 || d->n > 3) return fail("vits_op_conv_group: two or three members");
+    if (!shape_lens_ok(lens, d->batch, d->t, d->t_stride)) return fail("vits_op_conv_group: 0 <= lens[b] <= t <= t_stride is required");
+    OpKnobs op_knobs;
+    OpTileMaps maps;
+    const int B = d->batch, C = d->channels, n = d->n;
+    const size_t per = (size_t)B * C * d->t_stride;
+    Conv cv[3];
+    ConvCall cc[3];
+    const PackedConv* pw[3];
+    DevMem dx, dy, dl;
+    if (!dx.put(x, per * n * 4) || !dy.fill(per * n * 4, 0xFF) || !dl.put_opt(lens, (size_t)B * 4)) return -1;
+    if (!maps.add(lens, lens, B, d->t, d->t, tile_shape(TILE_128x128).bn(), false)) return -1;
+    size_t woff = 0;
+    for (int i = 0; i < n; ++i) {
+        const int k = d->k[i];
+        if (k != 3 && k != 7 && k != 11) return fail("vits_op_conv_group: tap counts 11, 7 or 3");
+        if (!upload_conv(cv[i], w + woff, bias ? bias + (size_t)i * C : nullptr, C, C, C, k, EPI_STD, 0, VITS_ARITH_F32)) return -1;
+        woff += (size_t)C * C * k;
+        if (!conv_group_supported(cv[i].pc, d->dilation)) return fail("vits_op_conv_group: conv_group_supported refuses this conv (channels a multiple of 128, dilation 1, 3 or 5)");
+        ConvCall& c = cc[i];
+        c.x = tref(dx.f() + per * i, C, d->t_stride);
+        c.y = tref(dy.f() + per * i, C, d->t_stride);
+        c.len_in = c.len_out = dl.i();
+        c.maps = &maps.set;
+        c.batch = B;
+        c.t_in = c.t_out = d->t;
+        c.dil = d->dilation;
+        c.pad_l = (k * d->dilation - d->dilation) / 2;
+        c.pre_act = 1, c.slope = d->slope, c.post_act = 2, c.post_slope = d->slope;
+        pw[i] = &cv[i].pc;
+    }
+    return finish(launch_conv_group(pw, cc, n, nullptr), "vits_op_conv_group") && dy.get(y, per * n * 4) ? 0 : -1;
+    VITS_CATCH(-1)
+}
+
+VITS_API uint64_t vits_op_tile_map_launches(void) { return tile_map_launches().load(std::memory_order_relaxed); }
+
 VITS_API int vits_op_conv1d(const vits_conv1d_desc* d, const float* x, const float* w, const float* bias, const float* residual, const float* accum,
                             const int32_t* lens, float* y) {
     VITS_TRY
     if (!d || !x || !w || !y) return fail("null argument");
     const int arith = g_op_arith;
     if (arith == VITS_ARITH_F32_SPLIT) return op_conv1d_split(d, x, w, bias, residual, accum, lens, y);
+    OpKnobs op_knobs;
+    OpTileMaps maps;
     const int gate = d->post_act == 2;
     const int cy = gate ? d->cout / 2 : d->cout;
     Conv cv;
     DevMem dx, dy, dr, da, dl, x16;
     const size_t nx = (size_t)d->batch * d->cin * d->t_stride * 4, ny = (size_t)d->batch * cy * d->t_stride * 4;
     if (!upload_conv(cv, w, bias, d->cout, d->cout, d->cin, d->k, gate ? EPI_GATE : EPI_STD, 0, arith)) return -1;
-    if (!dx.put(x, nx) || !dy.fill(ny, 0) || !dl.put_opt(lens, (size_t)d->batch * 4)) return -1;
+    if (!dx.put(x, nx) || !dy.fill(ny, g_op_out_fill) || !dl.put_opt(lens, (size_t)d->batch * 4)) return -1;
     if ((residual && !dr.put(residual, ny)) || (accum && !da.put(accum, ny))) return -1;
     if (arith != VITS_ARITH_F32 && !x16.fill(group16_bytes(d->batch, d->cin, d->t), 0)) return -1;
     ConvCall c;
@@ -126,6 +178,10 @@ VITS_API int vits_op_conv1d(const vits_conv1d_desc* d, const float* x, const flo
     c.slope = d->pre_slope;
     c.post_act = d->post_act == 1 ? 1 : 0;
     c.scale = d->out_scale;
+    if (arith == VITS_ARITH_F32) {  // (the lists are the fp32 kernels')
+        if (!maps.add_conv(lens, lens, d->batch, d->t, d->t, false)) return -1;
+        c.maps = &maps.set;
+    }
     return finish(conv_transparent(cv.pc, c, arith, x16)) && dy.get(y, ny) ? 0 : -1;
     VITS_CATCH(-1)
 }
@@ -140,7 +196,7 @@ VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float
     const int C = d->channels, k = d->k;
     const size_t n = (size_t)d->batch * C * d->t_stride * 4;
     DevMem dx, dy, dl;
-    if (!dx.put(x, n) || !dy.fill(n, 0) || !dl.put_opt(lens, (size_t)d->batch * 4)) return -1;
+    if (!dx.put(x, n) || !dy.fill(n, g_op_out_fill) || !dl.put_opt(lens, (size_t)d->batch * 4)) return -1;
     const TensorRef bx = tref(dx.f(), C, d->t_stride), by = tref(dy.f(), C, d->t_stride);
     ConvCall c1, c2;
     pair_calls(dl.i(), d->batch, d->t, k, d->dilation, c1, c2);
@@ -170,8 +226,13 @@ VITS_API int vits_op_resblock_pair(const vits_resblock_pair_desc* d, const float
         c1.post_act = 2;  // t is stored activated: its only reader is conv 2
         c1.post_slope = d->slope;
         c2.x = c1.y;
+        OpKnobs op_knobs;
+        OpTileMaps maps;
+        if (!maps.add_conv(lens, lens, d->batch, d->t, d->t, false)) return -1;
+        c1.maps = c2.maps = &maps.set;
         e = launch_conv(v1.pc, c1, nullptr);
         if (e == hipSuccess) e = launch_conv(v2.pc, c2, nullptr);
+        if (!finish(e)) return -1;  // (the lists live until the device is done)
     }
     return finish(e) && dy.get(y, n) ? 0 : -1;
     VITS_CATCH(-1)
@@ -312,17 +373,24 @@ VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const
         if (!upload_conv(cv[i], (i & 1 ? w2 : w1) + (size_t)(i / 2) * wn, (i & 1 ? b2 : b1) + (size_t)(i / 2) * C, C, C, C, k, EPI_STD, 0, arith)) return -1;
     // staged at the engine's stride with NaN behind every lens[b]; the fp32 kernels take the standard layout, the 16-bit ones the group layout
     DevMem dl, dx, dxg, dacc, dout, dp[2], dt, dx16, dn16[2], dt16;
-    if (!dl.put_opt(lens, (size_t)B * 4) || !stage_rows(dx, x, B, C, d->t_stride, ts, lens, T) || !dout.fill(n * 4, 0) || !dp[0].fill(n * 4, 0xFF) || !dp[1].fill(n * 4, 0xFF)) return -1;
+    if (!dl.put_opt(lens, (size_t)B * 4) || !stage_rows(dx, x, B, C, d->t_stride, ts, lens, T) || !dout.fill(n * 4, g_op_out_fill) || !dp[0].fill(n * 4, 0xFF) || !dp[1].fill(n * 4, 0xFF)) return -1;
     if (accum && !(f32 ? stage_rows(dacc, accum, B, C, d->t_stride, ts, lens, T) : stage_group8(dacc, accum, B, C, d->t_stride, ts, lens, T))) return -1;
     hipError_t e = hipSuccess;
     const float scale = d->out_scale;
+    OpKnobs op_knobs;
+    OpTileMaps maps;
     if (f32) {
         if (r.variant == 1 && !dt.fill(n * 4, 0xFF)) return -1;
         const TensorRef bx = tref(dx.f(), C, ts), bout = tref(dout.f(), C, ts), bacc = accum ? tref(dacc.f(), C, ts) : TensorRef();
+        // the lists of existing tiles of `lens`, for the widths of the variant's kernels
+        bool mok = r.variant == 1 ? maps.add_conv(lens, lens, B, T, T, false) : r.variant == 3 ? maps.add(lens, lens, B, T, T, r.bo, false) : true;
+        for (int p = 0; p < nd && mok && r.variant == 2; ++p) mok = maps.add(lens, lens, B, T, T, rbpair32_geom(k, d->dil[p], C).bo, false);
+        if (!mok) return -1;
         if (r.variant == 3) {
             const PackedConv *c1[3] = {&cv[0].pc, &cv[2].pc, &cv[4].pc}, *c2[3] = {&cv[1].pc, &cv[3].pc, &cv[5].pc};
             RbBlock32Call f;
             f.x = bx, f.y = bout, f.acc = bacc, f.lens = dl.i(), f.batch = B, f.tmax = T, f.slope = d->slope, f.scale = scale, f.scale_div = d->scale_div;
+            f.maps = &maps.set;
             e = launch_rbblock32(c1, c2, f, nullptr);
         } else {
             TensorRef in = bx;
@@ -332,6 +400,7 @@ VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const
                 if (r.variant == 2) {
                     RbPair32Call f;
                     f.x = in, f.y = out, f.lens = dl.i(), f.batch = B, f.tmax = T, f.dil = d->dil[p], f.slope = d->slope;
+                    f.maps = &maps.set;
                     if (last) f.acc = bacc, f.scale = scale, f.scale_div = d->scale_div;
                     e = launch_rbpair32(cv[2 * p].pc, cv[2 * p + 1].pc, f, nullptr);
                 } else {
@@ -339,6 +408,7 @@ VITS_API int vits_op_resblock(const vits_resblock_desc* d, const float* x, const
                     ConvCall c1, c2;
                     pair_calls(dl.i(), B, T, k, d->dil[p], c1, c2);
                     c1.x = in, c1.y = tref(dt.f(), C, ts);
+                    c1.maps = c2.maps = &maps.set;
                     c1.pre_act = 1, c1.slope = d->slope, c1.post_act = 2, c1.post_slope = d->slope;
                     c2.x = c1.y, c2.res = in, c2.y = out;
                     if (last) c2.acc = bacc, c2.scale = scale, c2.scale_div = d->scale_div;
@@ -421,7 +491,7 @@ VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x
         for (int b = 0; b < d->batch; ++b) lo[b] = d->stride * lens[b] + d->k - d->stride - 2 * d->crop;
     }
     if (!upload_conv(cv, w, bias, d->cout, d->cout, d->cin, d->k, EPI_CONVT, d->stride, arith)) return -1;
-    if (!dx.put(x, nx) || !dy.fill(ny, 0) || !dl.put_opt(lens, (size_t)d->batch * 4) || !dlo.put_opt(lens ? lo.data() : nullptr, (size_t)d->batch * 4)) return -1;
+    if (!dx.put(x, nx) || !dy.fill(ny, g_op_out_fill) || !dl.put_opt(lens, (size_t)d->batch * 4) || !dlo.put_opt(lens ? lo.data() : nullptr, (size_t)d->batch * 4)) return -1;
     if (arith != VITS_ARITH_F32 && !x16.fill(group16_bytes(d->batch, d->cin, d->t), 0)) return -1;
     ConvCall c;
     c.x = tref(dx.f(), d->cin, d->t_stride);
@@ -434,6 +504,12 @@ VITS_API int vits_op_conv_transpose1d(const vits_convt1d_desc* d, const float* x
     c.pre_act = d->pre_slope != 1.0f;
     c.slope = d->pre_slope;
     c.ct_crop = d->crop;
+    OpKnobs op_knobs;
+    OpTileMaps maps;
+    if (arith == VITS_ARITH_F32) {  // (the lists are the fp32 kernels')
+        if (!maps.add_conv(lens, lens ? lo.data() : nullptr, d->batch, c.t_in, c.t_out, true)) return -1;
+        c.maps = &maps.set;
+    }
     return finish(conv_transparent(cv.pc, c, arith, x16)) && dy.get(y, ny) ? 0 : -1;
     VITS_CATCH(-1)
 }

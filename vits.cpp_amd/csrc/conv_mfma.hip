@@ -64,6 +64,8 @@ struct ConvParams {
     int64_t bias_rs;
     const int* len_in;
     const int* len_out;
+    const TileEntry* tmap;  // the list of existing tiles this launch's x runs over (tile_map.h), or nullptr = the dense grid
+    int tmap_n;             // its entries (host side: the grid's x)
     int t_in, t_out;
     int cin, cout, rows, nchunks;
     int mtiles;  // 32-row tiles in the packed weight array (a block may own row tiles past it: their fragments are read from the last one)
@@ -137,7 +139,9 @@ __device__ __forceinline__ void zero_oob_columns(float* lbase, int ts, int len, 
 // The kernel body as a device function of the block's (column tile, row-tile group, utterance) coordinates and the block's dynamic
 // LDS: conv_mfma_kernel runs it for one convolution; conv_group_kernel (below) runs the bodies of up to three convolutions with
 // different tap counts in ONE launch.
-template <int KT, int DIL, bool DB, int WM, int WN, int MR, int NR, int EPI>
+// TM: where the block's coordinates come from (tile_coord) — -1: the list p.tmap when the launch has one, else the dense grid (conv_mfma_kernel); 0: the
+// dense grid, 1: the list, decided at compile time (conv_group_kernel: with the run-time choice inlined three times its K loops came out 9 % slower).
+template <int KT, int DIL, bool DB, int WM, int WN, int MR, int NR, int EPI, int TM = -1>
 __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, const int bx, const int by, const int bz) {
     constexpr int BN = WN * NR * 32;
     constexpr int SPAN_C = (KT - 1) * (DIL < 0 ? -DIL : DIL);
@@ -153,17 +157,22 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-    const int b = bz;
-    const int t0 = bx * BN;
+    // the list of existing tiles on the throughput tiles only (conv_tile_mapped, conv_plan.h); dense grid: the transposed conv reads len_out only in its epilogue
+    constexpr bool TMAP = MR * NR >= 4 && TM != 0;
+    if constexpr (TM == 1) __builtin_assume(p.tmap != nullptr);
+    const TileEntry* const tmap = TMAP ? p.tmap : nullptr;
+    const TileCoord tc = tile_coord(tmap, bx, bz, BN, p.len_in, EPI == EPI_CONVT ? nullptr : p.len_out, p.t_in, p.t_out);
+    const int b = tc.b;
+    const int t0 = tc.t0;
     // multi-speaker calls: this utterance's row of the effective-bias table (a uniform pointer; without rows, the packed bias as before)
     const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;
     if constexpr (DB) VITS_ABL_SETPRIO(3);
     VITS_WSTART();
-    const int len_in = p.len_in ? p.len_in[b] : p.t_in;
+    const int len_in = tc.len_a;
     // number of valid GEMM columns for this utterance
     int ncols;
     if (EPI == EPI_CONVT) ncols = len_in + 1;  // q in [0, L_in]: the last phase group only sees the m=1 tap
-    else ncols = p.len_out ? p.len_out[b] : p.t_out;
+    else ncols = tc.len_b;
     if (t0 >= ncols || len_in <= 0) return;  // (an utterance that has no frames in this vocoder window has length 0)
     VITS_STAMP(0);
 
@@ -789,7 +798,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvParams& p, float* xs, c
         float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
         float* __restrict__ y2b = p.y2 ? p.y2 + (int64_t)b * p.y_bs : nullptr;  // leaky_relu(post_slope) copy for the resblocks' first convs
         const int s = p.ct_stride;
-        const int out_len = p.len_out ? p.len_out[b] : p.t_out;
+        const int out_len = tmap ? tc.len_b : (p.len_out ? p.len_out[b] : p.t_out);
         // stride 8: the 4 registers of a group are phases 4h..4h+3 of ONE output channel at one input position, i.e. 4
         // consecutive output samples -> one dwordx4 store (interior tiles; crop is 0 or 4 so the address stays 16-B aligned)
         // (boundary tiles too: at ~225 frames per utterance the first upsampler has no interior tile at all, and the scalar path below
@@ -1250,17 +1259,33 @@ static hipError_t launch_lat16(const PackedConv& w, const ConvPlan& pl, const Co
 // partially filled round of blocks (C = 256: 7.2 rounds of 80 us blocks -> 8; three such tails per position). Here blockIdx.z =
 // member * batch + utterance with the members ordered by DESCENDING tap count: the k = 11 blocks are dispatched first and the last
 // round is made of k = 3 blocks, a quarter as long. Same body per member as conv_mfma_kernel -> bit-identical results.
+// Ragged batches on the lists of existing tiles (tile_map.h): the members' lists are concatenated along x in the same order (11 taps first), z is 1, and
+// zend holds the ends of the lists: blockIdx.x < zend[i] -> member i. Every member's list pointer is moved back by its start in the concatenation, so that
+// blockIdx.x itself is the entry (the body ignores the utterance argument then).
 struct ConvGroupParams {
     ConvParams m[3];  // slot 0: 11 taps, 1: 7 taps, 2: 3 taps
-    int zend[3];      // blockIdx.z < zend[i] -> member i (an absent member has zend[i] == zend[i - 1])
+    int zend[3];      // blockIdx.z (MAPPED: blockIdx.x) < zend[i] -> member i (an absent member has zend[i] == zend[i - 1])
 };
+template <int DIL, bool MAPPED>
+__device__ __forceinline__ void conv_group_body(const ConvGroupParams& g, float* xs) {
+    constexpr int TM = MAPPED ? 1 : 0;
+    const int z = MAPPED ? blockIdx.x : blockIdx.z;
+    if (z < g.zend[0]) conv_mfma_body<11, DIL, true, 2, 2, 2, 2, EPI_STD, TM>(g.m[0], xs, blockIdx.x, blockIdx.y, z);
+    else if (z < g.zend[1]) conv_mfma_body<7, DIL, true, 2, 2, 2, 2, EPI_STD, TM>(g.m[1], xs, blockIdx.x, blockIdx.y, z - g.zend[0]);
+    else conv_mfma_body<3, DIL, true, 2, 2, 2, 2, EPI_STD, TM>(g.m[2], xs, blockIdx.x, blockIdx.y, z - g.zend[1]);
+}
 template <int DIL>
 __global__ __launch_bounds__(320) VITS_WAVES_ATTR void conv_group_kernel(const ConvGroupParams g) {
     extern __shared__ __attribute__((aligned(16))) float xs_dyn[];
-    const int z = blockIdx.z;
-    if (z < g.zend[0]) conv_mfma_body<11, DIL, true, 2, 2, 2, 2, EPI_STD>(g.m[0], xs_dyn, blockIdx.x, blockIdx.y, z);
-    else if (z < g.zend[1]) conv_mfma_body<7, DIL, true, 2, 2, 2, 2, EPI_STD>(g.m[1], xs_dyn, blockIdx.x, blockIdx.y, z - g.zend[0]);
-    else conv_mfma_body<3, DIL, true, 2, 2, 2, 2, EPI_STD>(g.m[2], xs_dyn, blockIdx.x, blockIdx.y, z - g.zend[1]);
+    conv_group_body<DIL, false>(g, xs_dyn);
+}
+// The same over the members' lists of existing tiles, held to three waves per SIMD (168 VGPRs; the dense kernel takes 165): a CU admits the successor block's five
+// waves beside the resident five only then. Left alone the compiler took 176 for this one, the successor waited for the resident block to end, and the launch came
+// out slower than the dense grid it replaces (serialised step 76.4 ms against 74.8 with the cap, 76.9 dense); the cap costs 20-24 spilled registers (44 bytes of scratch per lane).
+template <int DIL>
+__global__ __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(3))) void conv_group_list_kernel(const ConvGroupParams g) {
+    extern __shared__ __attribute__((aligned(16))) float xs_dyn[];
+    conv_group_body<DIL, true>(g, xs_dyn);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
@@ -1331,7 +1356,9 @@ std::vector<float> repack_conv_weights_l16(const std::vector<float>& packed, int
 
 template <int KT, int DIL, bool DB, int EPI>
 static hipError_t launch_tile(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
-    dim3 grid(pl.gx, pl.gy, pl.gz);
+    // (ragged batches: x over the list of existing tiles, row-tile groups along y as before, no z)
+    dim3 grid(p.tmap ? p.tmap_n : pl.gx, pl.gy, p.tmap ? 1 : pl.gz);
+    if (p.tmap) tile_map_launch_issued();
     const size_t lds = pl.lds;
     // (the arms an (epilogue, taps, dilation) lacks are the backstop: plan_conv asks conv_tile_exists before it chooses)
 #define VITS_TILE_ARM(LABEL, T)                                                      \
@@ -1387,7 +1414,8 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
         if (have[slot] >= 0) return hipErrorInvalidValue;
         have[slot] = i;
     }
-    int z = 0, ncols_max = 0;
+    int z = 0, ncols_max = 0, nmapped = 0, members = 0;
+    int64_t counts[3] = {0, 0, 0};
     size_t lds = 0;
     for (int slot = 0; slot < 3; ++slot) {
         if (have[slot] >= 0) {
@@ -1397,6 +1425,8 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
             make_conv_params(*w[i], c[i], pl, g.m[slot]);
             if (g.m[slot].bias_rows) return hipErrorInvalidValue;  // (never: the grouped launch serves the resblocks, which carry no speaker term)
             g.m[slot].nbuf = 2;
+            ++members;
+            if (g.m[slot].tmap) ++nmapped, counts[i] = g.m[slot].tmap_n;  // (per member)
             z += c[i].batch;
             ncols_max = std::max(ncols_max, c[i].t_out);
             lds = std::max(lds, (size_t)2 * CK * padded_xw(pl.xw) * sizeof(float));
@@ -1404,7 +1434,27 @@ hipError_t launch_conv_group(const PackedConv* const* w, const ConvCall* c, int 
         g.zend[slot] = z;
     }
     dim3 grid((ncols_max + 127) / 128, w[0]->mtiles_used / 4, z);
-#define VITS_GROUP_LAUNCH(D) return launch_lds<&conv_group_kernel<D>>(grid, dim3(320), lds, s, g)
+    // ragged batches: every member over its list of existing tiles (all of them or none: the dense decode and the lists do not share a grid)
+    bool mapped = false;
+    if (nmapped == members) {
+        int taps[3], slot_of[3];
+        int64_t xend[3];
+        for (int i = 0; i < n; ++i) taps[i] = w[i]->kt;
+        if (!tile_map_group_layout(taps, counts, n, slot_of, xend) || xend[2] > INT32_MAX) return hipErrorInvalidValue;
+        if (xend[2] == 0) return hipSuccess;  // (nothing to launch)
+        for (int slot = 0; slot < 3; ++slot) {
+            // (blockIdx.x is the entry: the slot's list pointer, minus where the slot starts; integer arithmetic — the host never forms the out-of-range pointer's object)
+            const int64_t start = slot ? xend[slot - 1] : 0;
+            if (g.m[slot].tmap) g.m[slot].tmap = reinterpret_cast<const TileEntry*>(reinterpret_cast<uintptr_t>(g.m[slot].tmap) - (uintptr_t)start * sizeof(TileEntry));
+            g.zend[slot] = (int)xend[slot];
+        }
+        mapped = true;
+        tile_map_launch_issued();
+        grid = dim3((unsigned)xend[2], grid.y, 1);
+    } else {
+        for (int slot = 0; slot < 3; ++slot) g.m[slot].tmap = nullptr;
+    }
+#define VITS_GROUP_LAUNCH(D) return mapped ? launch_lds<&conv_group_list_kernel<D>>(grid, dim3(320), lds, s, g) : launch_lds<&conv_group_kernel<D>>(grid, dim3(320), lds, s, g)
     if (c[0].dil == 1) VITS_GROUP_LAUNCH(1);
     else if (c[0].dil == 3) VITS_GROUP_LAUNCH(3);
     else VITS_GROUP_LAUNCH(5);
@@ -1433,6 +1483,10 @@ void make_conv_params(const PackedConv& w, const ConvCall& c, const ConvPlan& pl
     p.bias_rs = w.bias_rs;
     p.len_in = c.len_in;
     p.len_out = c.len_out;
+    // the list of existing tiles of this plan's tile width, where one was built and the launch is large (tile_map_for); the small tiles keep their dense grid
+    const TileMapRef* tm = !conv_tile_mapped(pl.tile) ? nullptr : tile_map_for(c.maps, tile_shape(pl.tile).bn(), w.epi == EPI_CONVT, (int64_t)pl.gx * pl.gy * pl.gz);
+    p.tmap = tm ? tm->dev : nullptr;
+    p.tmap_n = tm ? tm->n : 0;
     p.t_in = c.t_in;
     p.t_out = c.t_out;
     p.cin = w.cin;
@@ -1473,6 +1527,7 @@ hipError_t launch_conv(const PackedConv& w, const ConvCall& c, hipStream_t s) {
     make_conv_params(w, c, pl, p);
     if (c.ln_gamma && (!c.ln_beta || !c.ln_out.p || !pl.ln_ok)) return hipErrorInvalidValue;
     if (pl.tile == TILE_LAT16) return launch_lat16(w, pl, p, s);
+    if (p.tmap && p.tmap_n == 0) return hipSuccess;  // no utterance has a column here: nothing to launch (the dense grid's blocks would all return)
 #ifdef VITS_MICRO_KT  // developer microbenchmark (tools/conv_micro.hip): instantiate a single (taps, dilation) pair
     if ((VITS_MICRO_DIL) != 0 && pl.db) return launch_tile<VITS_MICRO_KT, VITS_MICRO_DIL, (VITS_MICRO_DIL) != 0, EPI_STD>(pl, p, s);
     return launch_tile<VITS_MICRO_KT, VITS_MICRO_DIL, false, EPI_STD>(pl, p, s);

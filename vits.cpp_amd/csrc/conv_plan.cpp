@@ -19,13 +19,13 @@ static int resolve_conv_tile(const PackedConv& w, const ConvCall& c) {
     if (w.epi != EPI_GATE && w.rows % 128 == 0 && kn.tile128) tile = TILE_128x128;
     auto blocks = [&](int tl) { return tile_blocks(tile_shape(tl), ncols_max, w.mtiles_used, c.batch); };
     if (w.epi == EPI_GATE) {
-        if (blocks(tile) < 512) tile = TILE_64x64;  // 64 x 128 keeps the tanh/sigmoid row pairing
+        if (blocks(tile) < kSmallGridBlocks) tile = TILE_64x64;  // 64 x 128 keeps the tanh/sigmoid row pairing
     } else {
         // small grids (batch 1, short inputs): fewer than ~2 blocks per CU leaves matrix pipes idle -> step down to
         // smaller tiles until the launch has >= 512 blocks (latency case, BASELINE.json config 2)
         // (k <= 3: 1024 — a short K loop costs a small tile little, and e.g. the encoder's 192 -> 768 FFN conv at batch 64 x 128 tokens is
         // 768 blocks of 64 x 128 = 1.5 rounds of the 512 resident blocks, but 3 even rounds of 32 x 128: 82 -> 74 us)
-        const int64_t min_blocks = kn.min_blocks > 0 ? kn.min_blocks : (w.kt <= 3 ? 1024 : 512);
+        const int64_t min_blocks = kn.min_blocks > 0 ? kn.min_blocks : (w.kt <= 3 ? 2 * kSmallGridBlocks : kSmallGridBlocks);
         if (blocks(tile) < min_blocks && (tile == TILE_128x128 || tile == TILE_64x256)) tile = TILE_64x64;  // 64 x 128
         if (blocks(tile) < min_blocks && (tile == TILE_64x64 || tile == TILE_32x256)) tile = TILE_32x64;    // 32 x 128
     }
@@ -151,8 +151,8 @@ static int choose_conv16_tile(int rows, int epi, int ncols_max, int mtiles_used,
     else tile = small_t ? 4 : 2;
     // small grids (batch 1, short inputs): step down until the launch has >= 512 blocks
     auto blocks = [&](int tl) { return tile_blocks(tile16_shape(tl), ncols_max, mtiles_used, batch); };
-    if (blocks(tile) < 512 && (tile == 0 || tile == 1 || tile == 5 || tile == 6)) tile = 3;
-    if (epi != EPI_GATE && blocks(tile) < 512 && (tile == 3 || tile == 2)) tile = 4;
+    if (blocks(tile) < kSmallGridBlocks && (tile == 0 || tile == 1 || tile == 5 || tile == 6)) tile = 3;
+    if (epi != EPI_GATE && blocks(tile) < kSmallGridBlocks && (tile == 3 || tile == 2)) tile = 4;
     return tile;
 }
 

@@ -45,6 +45,9 @@ constexpr TileShape tile16_shape(int tile) {
         default: return {1, 4, 1, 1};  // 32 x 128
     }
 }
+// The tiles whose kernels can run over a list of existing tiles instead of the dense grid (tile_map.h): the throughput tiles, four 32 x 32 accumulators per wave.
+// The small tiles serve the latency-bound launches; their kernels are compiled with the dense decode alone (their scalar registers are full).
+constexpr bool conv_tile_mapped(int tile) { return tile != TILE_LAT16 && tile != TILE_NARROW && tile_shape(tile).mr * tile_shape(tile).nr >= 4; }
 inline int64_t tile_blocks(TileShape t, int ncols, int mtiles_used, int batch) {
     return (int64_t)((ncols + t.bn() - 1) / t.bn()) * ((mtiles_used + t.bm() - 1) / t.bm()) * batch;
 }

@@ -900,6 +900,93 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     return run_stage_two(c, out, pend, want_async);
 }
 
+// ---- ragged batches: the lists of existing tiles of the fp32 vocoder's launches (tile_map.h) -------------------------------------------------------------
+// Which launches take one is asked of the planners with the shapes run_vocoder_window32 will pass (a launcher whose plan names another width finds no list and
+// keeps its dense grid). A list is planned where the launch is large (kSmallGridBlocks, as tile_map_for) and its dense grid would hold blocks past an
+// utterance's end; VITS_TILE_MAP plans it for every converted launch. Host arithmetic only.
+void Engine::plan_tile_maps(Call& c) {
+    c.tm_jobs.clear();
+    c.tm_total = 0;
+    const KernelKnobs& kn = knobs.kernel;
+    if (arith_now_ != VITS_ARITH_F32 || split_on() || kn.no_tile_map || (c.B < 2 && !kn.tile_map)) return;
+    const int B = c.B, n_up = c.n_up;
+    const size_t nk = hp.rb_k.size();
+    std::vector<int> la(B), lb(B);
+    for (size_t wi = 0; wi < c.wins.size(); ++wi) {
+        const int Lw = c.wins[wi].hi - c.wins[wi].lo;
+        auto smax = [&](int i) { return Lw * c.smul[i] + c.sadd[i]; };  // (WinCtx::smax)
+        auto want = [&](int vec, int width, bool convt, int64_t dense_blocks) {
+            for (const Call::TileMapJob& j : c.tm_jobs)
+                if (j.win == (int)wi && j.vec == vec && j.width == width && j.convt == convt) return;
+            if (!kn.tile_map && dense_blocks < kSmallGridBlocks) return;
+            const int vo = convt ? vec + 1 : vec;
+            for (int b = 0; b < B; ++b) la[b] = c.win_len(wi, vec, b), lb[b] = c.win_len(wi, vo, b);
+            if (!kn.tile_map && !tile_map_needed(la.data(), lb.data(), B, smax(vec), smax(vo), width, convt)) return;
+            const int64_t n = tile_map_count(la.data(), lb.data(), B, width, convt);
+            c.tm_jobs.push_back({(int)wi, vec, width, convt, c.tm_total, n});
+            c.tm_total += n;
+        };
+        // a convolution over the lengths of stage `vec` (the transposed conv: upsampler `vec`), on the tile plan_conv gives it
+        auto conv_width = [&](const PackedConv& w, int vec, int dil) {
+            const bool convt = w.epi == EPI_CONVT;
+            ConvCall shape;
+            shape.batch = B;
+            shape.t_in = smax(vec);
+            shape.t_out = smax(convt ? vec + 1 : vec);
+            shape.dil = dil;
+            const ConvPlan pl = plan_conv(w, shape);
+            if (!pl.ok || !conv_tile_mapped(pl.tile)) return;  // (the small tiles and the latency kernels keep their dense grids)
+            want(vec, tile_shape(pl.tile).bn(), convt, (int64_t)pl.gx * pl.gy * pl.gz);
+        };
+        conv_width(dec_pre_, 0, 1);
+        for (int i = 0; i < n_up; ++i) {
+            const UpStageW& U = ups_[i];
+            const int C = U.channels, vec = i + 1;
+            conv_width(U.up, i, 1);
+            for (size_t j = 0; j < nk; ++j) {
+                // (the kernel of resblock j by the rule run_vocoder_window32 schedules by; where the call's buffers then rule a fused kernel out, its launcher finds
+                // no list of its width and keeps the dense grid)
+                const ResBlockW& R = U.rbs[j];
+                const int kind = j < 3 ? rb32_kind(R, C) : 0;
+                const bool fused = kind >= 1;
+                if (kind == 2) {
+                    const RbBlock32Plan pl = plan_rbblock32(C, R.k, B, smax(vec));
+                    want(vec, rbblock32_geom(C, pl.nr).bo, false, (int64_t)pl.gx * pl.gy);
+                } else if (fused) {
+                    for (size_t d = 0; d < R.dil.size(); ++d) {
+                        const LaunchGrid pl = plan_rbpair32(C, R.k, R.dil[d], B, smax(vec));
+                        want(vec, rbpair32_geom(R.k, R.dil[d], C).bo, false, (int64_t)pl.gx * pl.gy);
+                    }
+                } else {
+                    for (size_t d = 0; d < R.dil.size(); ++d) {
+                        conv_width(R.c1[d], vec, R.dil[d]);
+                        conv_width(R.c2[d], vec, 1);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// the lists into `pinned` (which outlives the copy: the engine's own for a synchronous call, the slot's for a pipelined batch), then one copy on the stream
+hipError_t Engine::upload_tile_maps(Call& c, PinnedBuf<TileEntry>& pinned) {
+    if (!c.tm_total) return hipSuccess;
+    const size_t total = (size_t)c.tm_total;
+    if (hipError_t e = pinned.ensure(total, total + total / 4 + 64)) return e;
+    std::vector<int> la(c.B), lb(c.B);
+    for (const Call::TileMapJob& j : c.tm_jobs) {
+        for (int b = 0; b < c.B; ++b) la[b] = c.win_len(j.win, j.vec, b), lb[b] = c.win_len(j.win, j.convt ? j.vec + 1 : j.vec, b);
+        if (tile_map_fill(la.data(), lb.data(), c.B, j.width, j.convt, pinned.p + j.off) != j.n) return hipErrorUnknown;
+    }
+    prof.fence();
+    return hipMemcpyAsync(c.s2.tile_maps, pinned.p, sizeof(TileEntry) * total, hipMemcpyHostToDevice, stream);
+}
+
+void Engine::window_tile_maps(const Call& c, WinCtx& w) const {
+    for (const Call::TileMapJob& j : c.tm_jobs)
+        if (j.win == (int)w.wi && c.s2.tile_maps) (j.convt ? w.maps_up[j.vec] : w.maps[j.vec]).add(TileMapRef{c.s2.tile_maps + j.off, (int)j.n, j.width, j.convt});
+}
+
 // ---- stage two from the known frame counts on: vocoder windows, arena, latent (prior sampling, or the conversion front end), flow, vocoder,
 // results. Shared by process_impl and convert_batch.
 int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async) {
@@ -964,6 +1051,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     const bool la = c.lev_apply = level_kind_ >= VITS_LEVEL_GAIN;
     c.lim = la && limit_mode_ != VITS_LIMIT_OFF;  // (never with on_chunk: check_level)
 
+    // (a call that returns with device work queued owns no pinned memory that outlives the copy of its lists: it keeps the dense grids)
+    if (pend || !want_async) plan_tile_maps(c);
     if (layout_stage_two(c)) return -1;
     if (c.vc) {
         // voice conversion (engine_convert.cpp): spectrogram, posterior encoder and forward flow with the source speaker give z_p; the reverse
@@ -972,6 +1061,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         c.spk = c.vc->spk_tgt;
     } else if (run_prior_sampling(c)) return -1;
     if (run_flow(c)) return -1;
+    // (filled here, behind the flow's launches: the device has work while the host writes the lists)
+    HIP_OK(upload_tile_maps(c, pend ? pend->map_pinned : tile_map_host_));
 
     // ---- HiFiGAN (vits.cpp:583-644), window by window ---------------------------------------------------------------
     c.rx.phase("vits.hifigan");
@@ -1149,6 +1240,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         w.wv.bs = wave_stride;
         w.wv.cs = (int)wave_stride;
         w.final_slope = c.refmode ? hp.lrelu : 0.01f;  // Q2 (vits.cpp:638)
+        window_tile_maps(c, w);
         if (c.fast16 ? run_vocoder_window16(c, w) : run_vocoder_window32(c, w)) return -1;
         if (o.on_chunk) {
             // ship this window's samples to the host behind the kernels, then serve the PREVIOUS window's callbacks while

@@ -429,6 +429,7 @@ class Engine {
         PinnedBuf<char> host;  // (sized in bytes; read as float [B][stride])
         PinnedBuf<int> frames_pinned;
         PinnedBuf<int> win_pinned;    // vocoder-window length table of a windowed batch (host side of its H2D copy)
+        PinnedBuf<TileEntry> map_pinned;  // lists of existing tiles of a ragged batch (host side of their H2D copy)
         PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
         int lv_rows = 0;              // levelling: rows of lv_host_[slot] this batch fills (0: no level was set)
         int lm_rows = 0;              // the limiter: rows of lm_host_[slot] this batch fills (0: it was off)
@@ -471,6 +472,7 @@ class Engine {
     PinnedBuf<int> frames_host_;   // destination of a synchronous call's frame-count copy (into pageable memory the copy went through a staging buffer: + 15 us at batch 1)
     PinnedBuf<int> align_host_;    // durations and scores of an alignment call (engine_align.cpp)
     PinnedBuf<float> dur_host_;    // a synchronous call's durations for opts.durations_out, copied beside the frame counts
+    PinnedBuf<TileEntry> tile_map_host_;  // a synchronous call's lists of existing tiles (host side of their H2D copy; a call that returns with work queued builds none)
     // arithmetic of the convolutions being queued right now: `arith`, or fp32 while stage one runs under
     // VITS_ARITH_SCOPE_FLOW_VOCODER (every conv wrapper and fused kernel reads this one, never `arith` itself)
     int arith_now_ = VITS_ARITH_F32;
@@ -612,6 +614,12 @@ class Engine {
     int run_text_encoder(Call& c);
     int run_duration_predictor(Call& c);
     int layout_stage_two(Call& c);
+    // ragged batches on lists of existing tiles (tile_map.h; Call::tm_jobs): which lists the call's fp32 vocoder launches take, from the host's lengths and the
+    // planners (no device work); the fill into `pinned` + one in-stream copy; a window's sets as its launches find them
+    void plan_tile_maps(Call& c);
+    int rb32_kind(const ResBlockW& R, int C) const;  // 2 whole-resblock kernel, 1 fused pairs, 0 two launches per pair (engine_vocoder.cpp)
+    hipError_t upload_tile_maps(Call& c, PinnedBuf<TileEntry>& pinned);
+    void window_tile_maps(const Call& c, WinCtx& w) const;
     int run_prior_sampling(Call& c);
     int run_flow(Call& c) { return run_coupling(c, false); }
     int run_coupling(Call& c, bool forward);  // the residual coupling flow: reverse (TTS), or forward (voice conversion)

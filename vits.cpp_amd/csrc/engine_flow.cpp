@@ -77,6 +77,7 @@ int Engine::layout_stage_two(Call& c) {
         s2.wave_edge = c.ed && (c.lev_apply || c.rate_out || !o.out_device) ? a.alloc<float>((size_t)B * E_stride) : nullptr;
         s2.ed_scratch = c.ed ? a.alloc<char>(edges_scratch_bytes(B, smax[n_up], edges_plan_.W)) : nullptr;
         s2.lvl_ranges = c.lev_apply && o.on_chunk ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
+        s2.tile_maps = c.tm_total ? a.alloc<TileEntry>((size_t)c.tm_total) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

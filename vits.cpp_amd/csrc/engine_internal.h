@@ -211,7 +211,25 @@ struct Call {
         float* wave_edge;   // stated edges on, unless the stage writes straight to out_device: its output [B][E_stride]
         void* ed_scratch;   // stated edges on: edges_scratch_bytes of edges.hip
         int* lvl_ranges;    // VITS_LEVEL_GAIN, streaming: [window][2][B]: the model-rate samples [j0, j1) of each utterance that window w finalises
+        TileEntry* tile_maps;  // ragged fp32 calls: the lists of existing tiles of every window (tm_total entries), or null
     } s2{};
+    // Ragged batches, exact fp32 vocoder: the lists of existing tiles (tile_map.h) of the large launches whose dense grid would hold empty blocks. One list per
+    // (window, length vector, tile width): length vector i = the lengths at vocoder stage i (conv_pre, the stage's resblocks), convt = upsampler i (columns
+    // len_i + 1, output lengths of stage i + 1). Planned once the frame counts are known (Engine::plan_tile_maps), filled into pinned memory while the flow runs
+    // and copied in-stream (Engine::upload_tile_maps); a call that needs none (a batch of one, equal lengths, small grids) plans none.
+    struct TileMapJob {
+        int win, vec, width;
+        bool convt;
+        int64_t off, n;  // first entry in s2.tile_maps, entries
+    };
+    std::vector<TileMapJob> tm_jobs;
+    int64_t tm_total = 0;
+    // host copy of what the device holds in d_len[vec] of window `win`
+    int win_len(size_t win, int vec, int b) const {
+        if (!windowed) return slen[vec][b];
+        const int lf = std::min(frames[b], wins[win].hi) - wins[win].lo;
+        return lf <= 0 ? 0 : lf * smul[vec] + sadd[vec];
+    }
     int ls = 0, lws = 0, S_stride = 0;
     size_t big = 0;        // floats of the largest vocoder activation (of one window)
     std::vector<int> sts;  // [stage] time stride of that stage's buffers
@@ -251,6 +269,8 @@ struct WinCtx {
     int emit_lo;
     TensorRef zwin, pre, wv;
     float final_slope;
+    // the lists of existing tiles of this window (Call::tm_jobs): maps[i] for the launches over d_len[i], maps_up[i] for upsampler i; empty sets = dense grids
+    TileMapSet maps[9], maps_up[8];
 };
 
 }  // namespace vits

@@ -415,6 +415,18 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
     return 0;
 }
 
+// The kernel the exact-fp32 vocoder gives a resblock of a C-channel stage, by its shape, its weights and the knobs: 2 = the whole-resblock kernel (rbblock32.hip),
+// 1 = one fused kernel per conv pair (rbpair32.hip; all pairs or none), 0 = two launches per pair. Stated once: run_vocoder_window32 schedules by it and
+// plan_tile_maps (engine.cpp) plans the lists of existing tiles for the widths of the same kernels.
+int Engine::rb32_kind(const ResBlockW& R, int C) const {
+    bool pairs = !knobs.no_fuse32;
+    for (size_t d = 0; d < R.dil.size() && pairs; ++d) pairs = rbpair32_supported(C, R.k, R.dil[d]) && R.c1[d].bias && R.c2[d].bias;
+    if (!pairs) return 0;
+    bool block = !knobs.no_rbblock32 && rbblock32_supported(C, R.k, R.dil.data(), (int)R.dil.size());
+    for (size_t d = 0; d < R.dil.size() && block; ++d) block = R.c1[d].wp && R.c2[d].wp;
+    return block ? 2 : 1;
+}
+
 int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up, Lw = w.Lw;
@@ -427,6 +439,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
         cv.y = h0;
         cv.len_in = w.d_len[0];
         cv.len_out = w.d_len[0];
+        cv.maps = &w.maps[0];
         cv.spk = c.spk;  // (multi-speaker calls: conv_pre carries the speaker term)
         cv.batch = B;
         cv.t_in = cv.t_out = Lw;
@@ -471,8 +484,8 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
         bool fusedrb[3] = {false, false, false};
         for (size_t j = 0; j < nk && j < 3; ++j) {
             const ResBlockW& R = U.rbs[j];
-            bool f = exact32 && !knobs.no_fuse32 && al16(bu) && (reinterpret_cast<uintptr_t>(s2.by[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(s2.bt[0]) & 15) == 0 && (s.ts & 3) == 0;
-            for (size_t d = 0; d < R.dil.size() && f; ++d) f = rbpair32_supported(C, R.k, R.dil[d]) && R.c1[d].bias && R.c2[d].bias;
+            // (rb32_kind: the shape, weights and knobs — the rule plan_tile_maps reads too; here what only the call knows: the arithmetic, the buffers' alignment)
+            bool f = exact32 && rb32_kind(R, C) >= 1 && al16(bu) && (reinterpret_cast<uintptr_t>(s2.by[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(s2.bt[0]) & 15) == 0 && (s.ts & 3) == 0;
             // VITS_ARITH_F32_SPLIT: a resblock the split kernels take (conv_split.hip: C >= 128, any tap count) runs un-fused — the C = 128, k = 3 pairs, fused in
             // the exact mode, are 1.56 ms each there and 0.9 as two split convs
             if (f && split_on() && s2.sp_u && C >= 128) {
@@ -488,9 +501,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
         bool blockrb[3] = {false, false, false};
         for (size_t j = 0; j < nk && j < 3; ++j) {
             const ResBlockW& R = U.rbs[j];
-            bool f = fusedrb[j] && !knobs.no_rbblock32 && rbblock32_supported(C, R.k, R.dil.data(), (int)R.dil.size());
-            for (size_t d = 0; d < R.dil.size() && f; ++d) f = R.c1[d].wp && R.c2[d].wp;
-            blockrb[j] = f;
+            blockrb[j] = fusedrb[j] && rb32_kind(R, C) == 2;
         }
         // VITS_ARITH_F32_SPLIT: the un-fused resblocks of a wide stage run their convs on the bf16 matrix cores with split operands (conv_split.hip): their
         // inputs are three-plane tensors written by the producing epilogue — the stage input by a converter launch —, the fp32 stream and the sum stay put.
@@ -542,6 +553,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             cu.y = bu;
             cu.len_in = s.len_in;
             cu.len_out = s.len_out;
+            cu.maps = &w.maps_up[i];
             cu.batch = B;
             cu.t_in = s.t_in;
             cu.t_out = s.t_out;
@@ -574,6 +586,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             RbBlock32Call f;
             f.x = bu;
             f.lens = s.len_out;
+            f.maps = &w.maps[i + 1];
             f.batch = B;
             f.tmax = s.t_out;
             f.slope = hp.lrelu;
@@ -601,6 +614,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             c1.x = lcopy ? (d > 0 ? s.ref(s2.byl[q]) : bul) : (d == 0 ? bu : s.ref(s2.by[q]));
             c1.y = s.ref(s2.bt[q]);
             c1.len_in = c1.len_out = s.len_out;
+            c1.maps = &w.maps[i + 1];
             c1.batch = B;
             c1.t_in = c1.t_out = s.t_out;
             c1.sum_in = c1.sum_out = s.sum_out;
@@ -658,6 +672,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             RbPair32Call f;
             f.x = d == 0 ? bu : ((d & 1) ? by : bt);
             f.lens = s.len_out;
+            f.maps = &w.maps[i + 1];
             f.batch = B;
             f.tmax = s.t_out;
             f.dil = R.dil[d];

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "tile_map.h"
+
 #ifdef __HIPCC__
 namespace vits {
 
@@ -36,6 +38,25 @@ template <bool BF>
 __device__ __forceinline__ floatx16 mfma16(int4v a, int4v b, floatx16 c) {
     if constexpr (BF) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
+}
+
+// A block's coordinates in a ragged launch: its utterance, the first column of its tile, and its utterance's lengths. With a list of the existing tiles
+// (tile_map.h; the grid's x then runs over the list) they come from entry bx in ONE 16-byte load through the scalar cache; without one (map null) it is the
+// dense decode: column tile bx of `bn` columns of utterance bz, the lengths from the arrays (null: the launch's maxima). Every converted kernel calls this.
+struct TileCoord {
+    int b, t0, len_a, len_b;
+};
+__device__ __forceinline__ TileCoord tile_coord(const TileEntry* map, int bx, int bz, int bn, const int* len_a, const int* len_b, int max_a, int max_b) {
+    TileCoord c;
+    if (map) {
+        const int4v e = *reinterpret_cast<const int4v*>(map + bx);
+        c.b = e.x, c.t0 = e.y, c.len_a = e.z, c.len_b = e.w;
+    } else {
+        c.b = bz, c.t0 = bx * bn;
+        c.len_a = len_a ? len_a[bz] : max_a;
+        c.len_b = len_b ? len_b[bz] : max_b;
+    }
+    return c;
 }
 
 // Buffer descriptor over a whole tensor (no bounds clamp: the kernels clamp their own offsets) — the packed weights' A-fragment

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "tile_map.h"
+
 struct vits_edges_desc;  // include/vits.h
 
 namespace vits {
@@ -75,6 +77,8 @@ struct KernelKnobs {
     int lat16h_shape = 21;       // VITS_LAT16H_SHAPE: 10 x waves per block + 32-column tiles per wave of conv16_lat_kernel (21, 22, 42)
     bool no_lat16 = false;       // VITS_NO_LAT16: tiny grids with long K chains on the 128 x 32 tile of conv_mfma instead of conv_lat16_kernel
     int lat16_max_waves = 768;   // VITS_LAT16_MAX_WAVES: standard convs with at most this many 32 x 32 output tiles take conv_lat16_kernel (0: tiny grids only)
+    bool no_tile_map = false;    // VITS_NO_TILE_MAP: ragged batches always on the dense grid (blocks past an utterance's end load its length and return)
+    bool tile_map = false;       // VITS_TILE_MAP: the list of existing tiles (tile_map.h) wherever a converted kernel runs, small grids and full grids included
     static KernelKnobs from_env() {
         KernelKnobs k;
         auto num = [](const char* name, int& v) {
@@ -130,6 +134,8 @@ struct KernelKnobs {
         num("VITS_LAT16H_MAX_TILES_C128", k.lat16h_max_tiles_c128);
         num("VITS_LAT16H_SHAPE", k.lat16h_shape);
         num("VITS_LAT16_MAX_WAVES", k.lat16_max_waves);
+        flag("VITS_NO_TILE_MAP", k.no_tile_map);
+        flag("VITS_TILE_MAP", k.tile_map);
         return k;
     }
 };
@@ -148,6 +154,26 @@ struct KernelKnobsScope {
     KernelKnobsScope(const KernelKnobsScope&) = delete;
     KernelKnobsScope& operator=(const KernelKnobsScope&) = delete;
 };
+
+// A launch of fewer blocks than this is a small grid: under two blocks per CU (plan_conv steps its tile down below it, conv_plan.cpp).
+constexpr int kSmallGridBlocks = 512;
+// The list a ragged launch runs over instead of its dense grid (tile_map.h), or null = the dense grid. `maps`: the lists of the call's length vector (null: none
+// were built — a batch of one, equal lengths, a 16-bit mode); width: the kernel's columns per block; dense_blocks: the whole dense grid. The list is taken where
+// one of this width was built and the launch is large; VITS_TILE_MAP takes it wherever it exists, VITS_NO_TILE_MAP nowhere.
+// launches of this process that were issued over a list (vits_op_tile_map_launches: a test sees which form ran). Counted by the launcher where it hands the
+// list's extent to the grid: a launch that is skipped (an empty list) or falls back to the dense grid is not counted
+inline std::atomic<uint64_t>& tile_map_launches() {
+    static std::atomic<uint64_t> n{0};
+    return n;
+}
+inline void tile_map_launch_issued() { tile_map_launches().fetch_add(1, std::memory_order_relaxed); }
+inline const TileMapRef* tile_map_for(const TileMapSet* maps, int width, bool convt, int64_t dense_blocks) {
+    const KernelKnobs& kn = kernel_knobs();
+    if (!maps || kn.no_tile_map) return nullptr;
+    const TileMapRef* m = maps->find(width, convt);
+    if (!m || !m->dev) return nullptr;
+    return kn.tile_map || dense_blocks >= kSmallGridBlocks ? m : nullptr;
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is an attribute of a function ON A DEVICE. A kernel instantiation that needs more than
 // 64 KB of LDS raises its limit once per device: the once-flag is one bit per device, so a process that loads models on several
@@ -283,6 +309,7 @@ struct ConvCall {
     int scale_div = 0;
     int ct_crop = 0;  // EPI_CONVT: output crop
     int tile = -1;    // ConvTile override (-1: chosen from the shape)
+    const TileMapSet* maps = nullptr;  // ragged batches: the lists of existing tiles of (len_in, len_out), per tile width (tile_map_for), or null = the dense grid
     // LayerNorm over the input channels applied ON LOAD (round 6; conv_lat16_kernel only — conv_ln_on_load_ok() tells, launch_conv refuses otherwise):
     // x is the UN-normalised tensor (add_layer_norm_kernel's input), every block normalises the columns of its input tile in that kernel's order of
     // operations, and ln_out (any layout) receives the normalised tensor — each column written once, by the blocks of the first row group.
@@ -392,6 +419,7 @@ hipError_t launch_rb_sum3(const float* y0, const float* y1, const float* y2, int
 struct RbPair32Call {
     TensorRef x, y, acc;
     const int* lens = nullptr;
+    const TileMapSet* maps = nullptr;  // the lists of existing tiles of `lens` (see ConvCall::maps)
     int batch = 1, tmax = 0, dil = 1;
     float slope = 0.1f;
     float scale = 1.f;
@@ -405,6 +433,7 @@ bool rbpair32_supported(int channels, int kt, int dil);
 struct RbBlock32Call {
     TensorRef x, y, acc;
     const int* lens = nullptr;
+    const TileMapSet* maps = nullptr;  // the lists of existing tiles of `lens` (see ConvCall::maps)
     int batch = 1, tmax = 0;
     float slope = 0.1f;
     float scale = 1.f;

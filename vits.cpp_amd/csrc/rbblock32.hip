@@ -32,6 +32,7 @@ struct RbBlock32Params {
     const float* b1[3];
     const float* b2[3];
     const int* lens;
+    const TileEntry* tmap;  // the list of existing tiles the grid's x runs over (tile_map.h), or nullptr = the dense grid (x: tile, y: utterance)
     int tmax;
     float slope;  // leaky_relu in front of every conv
     float* y;
@@ -62,9 +63,10 @@ __global__ __launch_bounds__(256, C >= 64 ? 2 : 3) void rbblock32_kernel(const R
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-    const int b = blockIdx.y;
-    const int len = p.lens ? p.lens[b] : p.tmax;
-    const int t0 = blockIdx.x * BO;
+    const TileCoord tc = tile_coord(p.tmap, blockIdx.x, blockIdx.y, BO, p.lens, nullptr, p.tmax, 0);
+    const int b = tc.b;
+    const int len = tc.len_a;
+    const int t0 = tc.t0;
     if (t0 >= len) return;
     const int krow = lane >> 5, col = lane & 31;
     const int u0 = wn * (NR * 32) + col;  // this lane's tile column of column tile nr: u0 + 32 nr
@@ -243,7 +245,12 @@ hipError_t launch_rbblock32(const PackedConv* const* c1, const PackedConv* const
     p.acc = c.acc.p, p.a_bs = c.acc.bs, p.a_cs = c.acc.cs, p.scale = c.scale, p.scale_div = c.scale_div, p.post_act = c.post_act;
     p.post_slope = c.post_slope;
     static_assert(rbblock32_exists(32, rbblock32_nr(32)) && rbblock32_exists(64, rbblock32_nr(64)), "the planner's predicate");
-    const dim3 grid(l.gx, l.gy), block(l.block);
+    // ragged batches: the list of existing tiles of this kernel's output width, where one was built and the launch is large (tile_map_for)
+    const TileMapRef* tm = tile_map_for(c.maps, rbblock32_geom(C, l.nr).bo, false, (int64_t)l.gx * l.gy);
+    p.tmap = tm ? tm->dev : nullptr;
+    if (tm && tm->n == 0) return hipSuccess;  // no utterance has a column: nothing to launch
+    if (tm) tile_map_launch_issued();
+    const dim3 grid(tm ? tm->n : l.gx, tm ? 1 : l.gy), block(l.block);
     if (C == 32) return launch_lds<&rbblock32_kernel<32, rbblock32_nr(32)>>(grid, block, l.lds, s, p);
     return launch_lds<&rbblock32_kernel<64, rbblock32_nr(64)>>(grid, block, l.lds, s, p);
 }

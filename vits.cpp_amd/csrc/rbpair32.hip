@@ -34,6 +34,7 @@ struct RbPair32Params {
     const float *w1, *w2;  // packed A fragments (pack_conv_weights)
     const float *b1, *b2;
     const int* lens;
+    const TileEntry* tmap;  // the list of existing tiles the grid's x runs over (tile_map.h), or nullptr = the dense grid (x: tile, y: utterance)
     int tmax;
     float slope;  // leaky_relu in front of both convs
     float* y;
@@ -65,9 +66,10 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
     float* ts = lds;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int b = blockIdx.y;
-    const int len = p.lens ? p.lens[b] : p.tmax;
-    const int t0 = blockIdx.x * BO;
+    const TileCoord tc = tile_coord(p.tmap, blockIdx.x, blockIdx.y, BO, p.lens, nullptr, p.tmax, 0);
+    const int b = tc.b;
+    const int len = tc.len_a;
+    const int t0 = tc.t0;
     if (t0 >= len) return;
     const int wm = wid / WN, wn = wid % WN;
     const int cb = wn * (NR * 32);  // first mid column of this wave
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(256, C >= 128 ? 2 : 3) void rbpair32_kernel(const R
 template <int KT, int DIL, int C>
 static hipError_t launch_rb32(const RbPair32Params& p, const LaunchGrid& l, hipStream_t s) {
     static_assert(rbpair32_exists(KT, DIL, C), "the planner would never ask for it");
-    return launch_lds<&rbpair32_kernel<KT, DIL, C>>(dim3(l.gx, l.gy), dim3(l.block), l.lds, s, p);
+    return launch_lds<&rbpair32_kernel<KT, DIL, C>>(dim3(l.gx, l.gy), dim3(l.block), l.lds, s, p);  // (l: the dense grid, or x over the list of existing tiles)
 }
 
 template <int KT, int C>
@@ -250,7 +252,7 @@ static hipError_t launch_rb32_kt(int kt, int dil, const RbPair32Params& p, const
 }
 
 hipError_t launch_rbpair32(const PackedConv& c1, const PackedConv& c2, const RbPair32Call& c, hipStream_t s) {
-    const LaunchGrid l = plan_rbpair32(c1.cin, c1.kt, c.dil, c.batch, c.tmax);
+    LaunchGrid l = plan_rbpair32(c1.cin, c1.kt, c.dil, c.batch, c.tmax);
     if (!c1.wp || !c2.wp || c1.cin != c1.cout || c2.cin != c1.cout || c2.cout != c1.cout || c1.kt != c2.kt || !l.ok ||
         !c1.bias || !c2.bias || c.x.p == c.y.p)
         return hipErrorInvalidValue;
@@ -260,6 +262,14 @@ hipError_t launch_rbpair32(const PackedConv& c1, const PackedConv& c2, const RbP
     p.x = c.x.p, p.x_bs = c.x.bs, p.x_cs = c.x.cs, p.w1 = c1.wp, p.w2 = c2.wp, p.b1 = c1.bias, p.b2 = c2.bias, p.lens = c.lens, p.tmax = c.tmax;
     p.slope = c.slope, p.y = c.y.p, p.y_bs = c.y.bs, p.y_cs = c.y.cs, p.acc = c.acc.p, p.a_bs = c.acc.bs, p.a_cs = c.acc.cs, p.scale = c.scale;
     p.scale_div = c.scale_div, p.post_act = c.post_act, p.post_slope = c.post_slope;
+    // ragged batches: the list of existing tiles of this kernel's output width, where one was built and the launch is large (tile_map_for)
+    const TileMapRef* tm = tile_map_for(c.maps, rbpair32_geom(c1.kt, c.dil, c1.cin).bo, false, (int64_t)l.gx * l.gy);
+    p.tmap = tm ? tm->dev : nullptr;
+    if (tm) {
+        if (tm->n == 0) return hipSuccess;  // no utterance has a column: nothing to launch
+        l.gx = tm->n, l.gy = 1;
+        tile_map_launch_issued();
+    }
     if (c1.cin == 32) return launch_rb32_kt<32>(c1.kt, c.dil, p, l, s);
     if (c1.cin == 64) return launch_rb32_kt<64>(c1.kt, c.dil, p, l, s);
     return launch_rb32_dil<3, 128>(c.dil, p, l, s);
