@@ -1073,6 +1073,51 @@ VITS_API int vits_op_durations(int32_t batch, int32_t rows, int32_t row, int32_t
                                const float* length_scales, const int32_t* ovr, int32_t fixed, int32_t n_stage, const int32_t* stage_mul,
                                const int32_t* stage_add, float* dur, int32_t* cum, int32_t* frames, int32_t* stage_lens);
 
+/* The kernels between the conv families at operator level. Host arrays in, host arrays out; inputs are staged with 0xFF bytes (NaN) behind every utterance's
+ * length and between a row's extent and its device pitch, outputs hold the byte of vits_op_set_output_fill wherever no kernel writes. Each runs the engine's
+ * own launcher; what the launcher or the engine refuses is refused here with the cause named, before the first device call.
+ *
+ * vits_op_spectrogram: the linear magnitude spectrogram of voice conversion and alignment (launch_spectrogram; spectrogram_torch with center = False: reflection
+ * pad (n_fft - hop) / 2, periodic Hann, sqrt(re^2 + im^2 + 1e-6)). pcm host [batch][pcm_stride], n_samples host [batch]; utterance b has n_samples[b] / hop
+ * frames (the engine's rule); out host [batch][bins][t_stride], bins <= n_fft / 2 + 1: frame t < frames[b] in column t, +0 up to the batch's longest frame
+ * count, the fill behind that. Geometry as the engine checks it: n_fft a power of two in [16, 2048], 1 <= hop <= n_fft, n_fft - hop even, every
+ * n_samples[b] >= max(hop, pad + 1). */
+VITS_API int vits_op_spectrogram(int32_t n_fft, int32_t hop, int32_t bins, int32_t batch, const float* pcm, int64_t pcm_stride, const int32_t* n_samples,
+                                 int32_t t_stride, float* out);
+/* vits_op_prior_sample: prior sampling through the alignment as a gather (launch_zp): zp[b][c][j] = mean[b][c][a] + eps * exp(logvar[b][c][a]) * scale for
+ * j < frames[b], a = the first token with cum[b][a] > j (none: mean 0, logvar 0). mean, logvar host [batch][channels][t_tok]; cum host [batch][t_tok]
+ * (inclusive duration sums, uploaded as given: INT32_MAX behind tok_lens[b] as the durations kernel leaves it); tok_lens host [batch] or NULL (t_tok);
+ * frames host [batch], 0 <= frames[b] <= t_stride; zp host [batch][channels][t_stride]. eps: noise host [batch][channels][t_stride], or NULL = the counter
+ * stream vits_counter_normal(seed + (seed_offsets ? seed_offsets[b] : b), VITS_STREAM_NOISE_PRIOR, c * frames[b] + j). scale = noise_scales[b] (optional) or
+ * noise_scale. */
+VITS_API int vits_op_prior_sample(int32_t batch, int32_t channels, int32_t t_tok, int32_t t_stride, const float* mean, const float* logvar, const int32_t* cum,
+                                  const int32_t* tok_lens, const int32_t* frames, const float* noise, uint64_t seed, const int32_t* seed_offsets, float noise_scale,
+                                  const float* noise_scales, float* zp);
+/* vits_op_posterior_sample: zq[b][row][j] = mean[b][c][j] + (eps * eps_scale) * exp(logstd[b][c][j]) for j < frames[b] (launch_posterior_sample), row = c, or
+ * channels - 1 - c with flip = 1; every tensor host [batch][channels][t_stride]; eps as in vits_op_prior_sample. eps_scale = 0 is the mean: no noise is drawn or read. */
+VITS_API int vits_op_posterior_sample(int32_t batch, int32_t channels, int32_t t_stride, const float* mean, const float* logstd, const int32_t* frames,
+                                      const float* noise, uint64_t seed, const int32_t* seed_offsets, int32_t flip, float eps_scale, float* zq);
+/* vits_op_conv_post: leaky_relu(slope) -> Conv1d(cin -> 1, k, no bias) -> tanh, the vocoder's last kernel. x host [batch][cin][t], on the device at x_pitch
+ * floats per row; w host [cin][k]; lens host [batch] or NULL; wave host [batch][t]; pre host [batch][t] or NULL: the sums before the tanh, on the device at
+ * pre_pitch floats per row. Samples [emit_lo, min(emit_hi[b], lens[b])) of each row are written (emit_hi NULL: up to lens[b]), the streaming vocoder's window.
+ * VITS_ARITH_F32 runs launch_conv_post. In a 16-bit arithmetic (vits_op_set_arith) layout chooses: VITS_CONV_POST_FP32_LAYOUT = the same kernel with the operands
+ * rounded on load; VITS_CONV_POST_STREAM = launch_to_group16 with the slope, then launch_conv_post16, as the 16-bit vocoder runs them (cin a multiple of 8). */
+#define VITS_CONV_POST_FP32_LAYOUT 0
+#define VITS_CONV_POST_STREAM 1
+typedef struct vits_conv_post_desc {
+    int32_t batch, cin, k, t;
+    int32_t x_pitch, pre_pitch;
+    float slope;
+    int32_t emit_lo;
+    int32_t layout;
+} vits_conv_post_desc;
+VITS_API int vits_op_conv_post(const vits_conv_post_desc* d, const float* x, const float* w, const int32_t* lens, const int32_t* emit_hi, float* pre, float* wave);
+/* vits_op_resblock_sum: out = ((y0 + y1) [+ y2]) * scale (scale_div = 1: / scale) [then leaky_relu(slope) where act = 1] on [0, lens[b]) (launch_rb_sum3_std, the
+ * fp32 vocoder's sum over a stage's side-by-side resblocks). y0, y1, y2 (optional), out host [batch][channels][t]; on the device the addends lie at in_pitch
+ * and out at out_pitch floats per row. VITS_ARITH_F32 only. */
+VITS_API int vits_op_resblock_sum(int32_t batch, int32_t channels, int32_t t, int32_t in_pitch, int32_t out_pitch, float scale, int32_t scale_div, int32_t act,
+                                  float slope, const float* y0, const float* y1, const float* y2, const int32_t* lens, float* out);
+
 /* The alignment kernels (align_logp + align_mas; see vits_model_align_batch) on caller-supplied statistics: m, ls host [batch][F][Tmax] (prior mean and
  * log-deviation per token), z host [batch][F][Lmax], Tmax = max T[b], Lmax = max L[b], 1 <= T[b] <= L[b]. durations: out, host [batch][Tmax] (0 past
  * T[b]); scores: out, host [batch], optional. */

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT, golden
 from modelfile_py import parse_model_file
+from spectrogram_ref import np_spectrogram  # (the float64 reference of the spectrogram operator tests: the fixture comparison below checks it on the CPU)
 
 # sha256 of vits_synth_model_bytes(0x5EED, arch) on the commit before voice conversion: the flag only appends
 PARENT_SHA256 = {
@@ -53,17 +54,6 @@ def test_posterior_flag_appends_the_transformers_tensors(pkg, arch, H, F, bins, 
     added = {n: tuple(q["tensors"][n][0].shape) for n in names_p[len(names_b):]}
     assert added == posterior_shapes(H, F, bins, 5, nl, E)
     assert q["config"]["spectrogram_bins"] == str(bins) and q["config"]["posterior_encoder_num_wavenet_layers"] == str(nl)
-
-
-def np_spectrogram(y, n_fft, hop):
-    """spectrogram_torch (center=False) in numpy alone: reflection pad, periodic Hann, rfft, sqrt(|X|^2 + 1e-6)"""
-    p = (n_fft - hop) // 2
-    yp = np.pad(y.astype(np.float64), (p, p), mode="reflect")
-    L = (yp.size - n_fft) // hop + 1
-    win = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(n_fft) / n_fft)
-    frames = np.stack([yp[t * hop:t * hop + n_fft] * win for t in range(L)])
-    X = np.fft.rfft(frames, axis=1)
-    return np.sqrt(X.real ** 2 + X.imag ** 2 + 1e-6).T
 
 
 @pytest.mark.parametrize("fixture,n_fft,hop", [("vc_tiny_speakers_hf_export_taps.npz", 16, 8), ("vc_full_synth_taps.npz", 1024, 256)])

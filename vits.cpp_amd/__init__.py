@@ -32,6 +32,7 @@ DDS_HEAD_NONE, DDS_HEAD_FROM1, DDS_HEAD_CONV = 0, 1, 2
 # op_attention: the planner's choice, rel_attention_kernel<1024 | 256>, rel_attention_mfma_kernel<4, 32, false, false | 8, 32, false, false | 4, 24, true, false | 8, 24, false, true>
 ATT_VARIANT_PLAN, ATT_VARIANT_VALU1024, ATT_VARIANT_VALU256, ATT_VARIANT_MFMA4, ATT_VARIANT_MFMA8, ATT_VARIANT_SHORT, ATT_VARIANT_LAT = 0, 1, 2, 3, 4, 5, 6
 NC_VARIANT_PLAN, NC_VARIANT_SEPARATE, NC_VARIANT_ON_LOAD = 0, 1, 2  # op_norm_conv
+CONV_POST_FP32_LAYOUT, CONV_POST_STREAM = 0, 1  # op_conv_post in a 16-bit arithmetic: conv_post_kernel with rounded operands | the converter + conv_post16_kernel
 ARITH_F32, ARITH_BF16, ARITH_F16, ARITH_F32_SPLIT = 0, 1, 2, 3
 # vits_model_set_level: what every PCM a handle delivers is measured and multiplied by (include/vits.h)
 LEVEL_NONE, LEVEL_MEASURE, LEVEL_GAIN, LEVEL_PEAK, LEVEL_LOUDNESS = 0, 1, 2, 3, 4
@@ -69,6 +70,7 @@ EXPORTED_SYMBOLS = [
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
     "vits_op_attention", "vits_op_attention_plan", "vits_op_layer_norm", "vits_op_layer_norm_plan", "vits_op_norm_conv", "vits_op_norm_conv_plan",
+    "vits_op_spectrogram", "vits_op_prior_sample", "vits_op_posterior_sample", "vits_op_conv_post", "vits_op_resblock_sum",
     "vits_pcm_gather_unique_id", "vits_pcm_gather_init", "vits_pcm_gather", "vits_pcm_gather_destroy", "vits_pcm_gather_verdict",
 ]
 
@@ -222,6 +224,11 @@ class NormConvDesc(C.Structure):
     """vits_norm_conv_desc"""
     _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("t", C.c_int32), ("t_stride", C.c_int32), ("pitch", C.c_int32), ("k", C.c_int32),
                 ("pad_left", C.c_int32), ("post_act", C.c_int32), ("eps", C.c_float), ("variant", C.c_int32)]
+
+
+class ConvPostDesc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("cin", C.c_int32), ("k", C.c_int32), ("t", C.c_int32), ("x_pitch", C.c_int32), ("pre_pitch", C.c_int32),
+                ("slope", C.c_float), ("emit_lo", C.c_int32), ("layout", C.c_int32)]
 
 
 class NormConvPlan(C.Structure):
@@ -457,6 +464,16 @@ def lib():
     L.vits_op_norm_conv.argtypes = [C.POINTER(NormConvDesc)] + [vp] * 9
     L.vits_op_norm_conv_plan.restype = i32
     L.vits_op_norm_conv_plan.argtypes = [C.POINTER(NormConvDesc), C.POINTER(NormConvPlan)]
+    L.vits_op_spectrogram.restype = i32
+    L.vits_op_spectrogram.argtypes = [i32, i32, i32, i32, vp, i64, vp, i32, vp]
+    L.vits_op_prior_sample.restype = i32
+    L.vits_op_prior_sample.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, u64, vp, C.c_float, vp, vp]
+    L.vits_op_posterior_sample.restype = i32
+    L.vits_op_posterior_sample.argtypes = [i32, i32, i32, vp, vp, vp, vp, u64, vp, i32, C.c_float, vp]
+    L.vits_op_conv_post.restype = i32
+    L.vits_op_conv_post.argtypes = [C.POINTER(ConvPostDesc), vp, vp, vp, vp, vp, vp]
+    L.vits_op_resblock_sum.restype = i32
+    L.vits_op_resblock_sum.argtypes = [i32, i32, i32, i32, i32, C.c_float, i32, i32, C.c_float, vp, vp, vp, vp, vp]
     L.vits_op_rel_attention.restype = i32
     L.vits_op_rel_attention.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.vits_op_add_layer_norm.restype = i32
@@ -1934,6 +1951,117 @@ def op_norm_conv(x, gamma, beta, w, bias=None, residual=None, pad_left=None, pos
     if lib().vits_op_norm_conv(C.byref(d), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(bias), _ptr(residual), _ptr(lens), _ptr(y), _ptr(ln_out)) != 0:
         raise VitsError(last_error())
     return y, ln_out
+
+
+def _filled(shape):
+    """an output array of the operators below: they overwrite it whole, with the byte of op_set_output_fill wherever no kernel writes"""
+    return np.zeros(shape, np.float32)
+
+
+def op_spectrogram(pcm, n_fft, hop, bins=None, n_samples=None, t_stride=None):
+    """The linear magnitude spectrogram (vits_op_spectrogram): pcm [B, pcm_stride] (or one row), n_samples [B] (None: every row whole). Returns
+    [B, bins, t_stride] (bins None: n_fft / 2 + 1; t_stride None: the longest row's frames): frame t < n_samples[b] // hop in column t."""
+    pcm = _f32(pcm)
+    if pcm.ndim == 1:
+        pcm = pcm[None]
+    assert pcm.ndim == 2, "pcm is [B, pcm_stride]"
+    B, stride = pcm.shape
+    n = np.full(B, stride, np.int32) if n_samples is None else np.ascontiguousarray(n_samples, dtype=np.int32).reshape(-1)
+    assert n.shape == (B,), "one n_samples per row"
+    assert hop >= 1, "hop >= 1"
+    bins = n_fft // 2 + 1 if bins is None else bins
+    ts = max(1, int(n.max()) // hop) if t_stride is None else t_stride
+    assert ts >= 1 and bins >= 1
+    out = _filled((B, bins, ts))
+    if lib().vits_op_spectrogram(n_fft, hop, bins, B, _ptr(pcm), stride, _ptr(n), ts, _ptr(out)) != 0:
+        raise VitsError(last_error())
+    return out
+
+
+def _noise_args(B, noise, shape, seed_offsets, scales):
+    if noise is not None:
+        noise = _f32(noise)
+        assert noise.shape == shape, "noise has the output's shape"
+    if seed_offsets is not None:
+        seed_offsets = np.ascontiguousarray(seed_offsets, dtype=np.int32)
+        assert seed_offsets.shape == (B,), "one seed offset per row"
+    if scales is not None:
+        scales = _f32(scales)
+        assert scales.shape == (B,), "one noise scale per row"
+    return noise, seed_offsets, scales
+
+
+def op_prior_sample(mean, logvar, cum, frames, t_stride=None, tok_lens=None, noise=None, seed=0, seed_offsets=None, noise_scale=1.0, noise_scales=None):
+    """Prior sampling through the alignment (vits_op_prior_sample, zp_kernel): mean, logvar [B, C, t_tok], cum int32 [B, t_tok], frames [B]. noise [B, C, t_stride]
+    or None = the counter stream of `seed` (+ seed_offsets[b], or b). Returns zp [B, C, t_stride]."""
+    mean, logvar = _f32(mean), _f32(logvar)
+    B, Cn, T = mean.shape
+    assert logvar.shape == mean.shape
+    cum = np.ascontiguousarray(cum, dtype=np.int32)
+    frames = np.ascontiguousarray(frames, dtype=np.int32)
+    assert cum.shape == (B, T) and frames.shape == (B,)
+    tok_lens = None if tok_lens is None else np.ascontiguousarray(tok_lens, dtype=np.int32)
+    assert tok_lens is None or tok_lens.shape == (B,)
+    ts = max(1, int(frames.max())) if t_stride is None else t_stride
+    noise, seed_offsets, noise_scales = _noise_args(B, noise, (B, Cn, ts), seed_offsets, noise_scales)
+    zp = _filled((B, Cn, ts))
+    if lib().vits_op_prior_sample(B, Cn, T, ts, _ptr(mean), _ptr(logvar), _ptr(cum), _ptr(tok_lens), _ptr(frames), _ptr(noise), seed, _ptr(seed_offsets), noise_scale,
+                                  _ptr(noise_scales), _ptr(zp)) != 0:
+        raise VitsError(last_error())
+    return zp
+
+
+def op_posterior_sample(mean, logstd, frames, noise=None, seed=0, seed_offsets=None, flip=False, eps_scale=1.0):
+    """The posterior draw (vits_op_posterior_sample): mean, logstd [B, C, t_stride], frames [B]; noise as in op_prior_sample. flip: channel c goes to row C - 1 - c.
+    Returns zq [B, C, t_stride]."""
+    mean, logstd = _f32(mean), _f32(logstd)
+    B, Cn, ts = mean.shape
+    assert logstd.shape == mean.shape
+    frames = np.ascontiguousarray(frames, dtype=np.int32)
+    assert frames.shape == (B,)
+    noise, seed_offsets, _ = _noise_args(B, noise, (B, Cn, ts), seed_offsets, None)
+    zq = _filled((B, Cn, ts))
+    if lib().vits_op_posterior_sample(B, Cn, ts, _ptr(mean), _ptr(logstd), _ptr(frames), _ptr(noise), seed, _ptr(seed_offsets), 1 if flip else 0, eps_scale, _ptr(zq)) != 0:
+        raise VitsError(last_error())
+    return zq
+
+
+def op_conv_post(x, w, slope, lens=None, emit_lo=0, emit_hi=None, want_pre=True, x_pitch=None, pre_pitch=None, layout=CONV_POST_FP32_LAYOUT):
+    """The vocoder's last kernel (vits_op_conv_post): x [B, cin, T], w [cin, k] (or [1, cin, k]). x_pitch / pre_pitch: floats per device row of x and of pre (None:
+    T rounded up to 4). Returns (wave [B, T], pre [B, T] or None); only samples [emit_lo, min(emit_hi[b], lens[b])) are written."""
+    x, w = _f32(x), _f32(w)
+    if w.ndim == 3:
+        assert w.shape[0] == 1, "conv_post has one output channel"
+        w = w[0]
+    B, cin, T = x.shape
+    assert w.ndim == 2 and w.shape[0] == cin, "w is [cin, k]"
+    w = np.ascontiguousarray(w)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    emit_hi = None if emit_hi is None else np.ascontiguousarray(emit_hi, dtype=np.int32)
+    assert lens is None or lens.shape == (B,)
+    assert emit_hi is None or emit_hi.shape == (B,)
+    r4 = (T + 3) // 4 * 4
+    d = ConvPostDesc(B, cin, w.shape[1], T, r4 if x_pitch is None else x_pitch, r4 if pre_pitch is None else pre_pitch, slope, emit_lo, layout)
+    wave, pre = _filled((B, T)), _filled((B, T)) if want_pre else None
+    if lib().vits_op_conv_post(C.byref(d), _ptr(x), _ptr(w), _ptr(lens), _ptr(emit_hi), _ptr(pre), _ptr(wave)) != 0:
+        raise VitsError(last_error())
+    return wave, pre
+
+
+def op_resblock_sum(y0, y1, y2=None, scale=1.0, scale_div=False, act=False, slope=0.1, lens=None, in_pitch=None, out_pitch=None):
+    """((y0 + y1) [+ y2]) * scale (or / scale) [+ leaky_relu(slope)] (vits_op_resblock_sum, rb_sum3_std_kernel): addends [B, C, T]; in_pitch / out_pitch: floats per
+    device row (None: T). Returns [B, C, T]."""
+    y0, y1 = _f32(y0), _f32(y1)
+    y2 = None if y2 is None else _f32(y2)
+    B, Cn, T = y0.shape
+    assert y1.shape == y0.shape and (y2 is None or y2.shape == y0.shape)
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    assert lens is None or lens.shape == (B,)
+    out = _filled((B, Cn, T))
+    if lib().vits_op_resblock_sum(B, Cn, T, T if in_pitch is None else in_pitch, T if out_pitch is None else out_pitch, scale, 1 if scale_div else 0, 1 if act else 0,
+                                  slope, _ptr(y0), _ptr(y1), _ptr(y2), _ptr(lens), _ptr(out)) != 0:
+        raise VitsError(last_error())
+    return out
 
 
 def pcm16(pcm):

@@ -1,4 +1,4 @@
-// abi_ops_common.h — the staging layer of the operator-level entry points (vits_op_*: abi_ops_conv.cpp, abi_ops_stage1.cpp, abi_ops_pcm.cpp). An operator takes
+// abi_ops_common.h — the staging layer of the operator-level entry points (vits_op_*: abi_ops_conv.cpp, abi_ops_stage1.cpp, abi_ops_pcm.cpp, abi_ops_glue.cpp). An operator takes
 // host arrays, runs the engine's own launchers on device copies and hands host arrays back; what lies between is here, once: the device buffer, the conv upload,
 // the fp32-layout conv of a 16-bit mode, the NaN staging of ragged batches and the end of a run.
 //

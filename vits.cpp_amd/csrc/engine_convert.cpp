@@ -20,12 +20,8 @@ int Engine::prepare_conversion(std::string& err) {
     int hop = 1;
     for (int r : hp.up_rates) hop *= r;
     const int n_fft = 2 * (bins - 1);
-    if (n_fft < 16 || n_fft > 2048 || (n_fft & (n_fft - 1))) {
-        err = "spectrogram_bins = " + std::to_string(bins) + " gives n_fft = " + std::to_string(n_fft) + ": the spectrogram kernel needs a power of two in [16, 2048]";
-        return -1;
-    }
-    if (hop > n_fft || ((n_fft - hop) & 1)) {
-        err = "hop " + std::to_string(hop) + " (product of the upsample rates) does not fit n_fft " + std::to_string(n_fft) + ": (n_fft - hop) / 2 must be a whole pad";
+    if (const std::string why = stft_geometry(n_fft, hop); !why.empty()) {
+        err = "spectrogram_bins = " + std::to_string(bins) + " and the upsample rates' product " + std::to_string(hop) + " give " + why;
         return -1;
     }
     if (nl < 1) {
@@ -83,13 +79,8 @@ int Engine::prepare_conversion(std::string& err) {
     }
     // STFT tables, in double, rounded once to fp32: twiddles exp(-2 pi i m / n) and the periodic Hann window (torch.hann_window(n))
     {
-        std::vector<float> tw((size_t)n_fft), win((size_t)n_fft);
-        const double pi = 3.14159265358979323846;
-        for (int m = 0; m < n_fft / 2; ++m) {
-            tw[2 * m] = (float)std::cos(2.0 * pi * m / n_fft);
-            tw[2 * m + 1] = (float)-std::sin(2.0 * pi * m / n_fft);
-        }
-        for (int m = 0; m < n_fft; ++m) win[m] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * m / n_fft));
+        std::vector<float> tw, win;
+        stft_tables(n_fft, tw, win);
         if (!(stft_tw_ = upload(tw)) || !(stft_win_ = upload(win))) {
             err = "hipMalloc failed for the STFT tables";
             return -1;
@@ -97,7 +88,7 @@ int Engine::prepare_conversion(std::string& err) {
     }
     n_fft_ = n_fft;
     hop_ = hop;
-    stft_pad_ = (n_fft - hop) / 2;
+    stft_pad_ = stft_pad(n_fft, hop);
     // a handle already in a 16-bit arithmetic: the new convs get their fragments now (set_arith packs only on a change of mode)
     if (arith == VITS_ARITH_F16 || arith == VITS_ARITH_BF16) {
         for (size_t i = first_pack; i < packs_.size(); ++i) {
@@ -114,7 +105,7 @@ int Engine::prepare_conversion(std::string& err) {
 // the PCM side of a call (conversion and alignment): every utterance inside its row, at least one hop and more than the reflection pad; nmax = the longest
 // as given, n_model = every utterance's samples at the model's rate (the given count, or with an input rate set ceil(N L / M): what the length rule applies to)
 int Engine::check_conversion_pcm(const int64_t* pcm_lens, int B, int64_t pcm_stride, int64_t& nmax, std::vector<int64_t>& n_model, std::string& err) const {
-    const int hop = hop_, pad = stft_pad_, min_n = std::max(hop, pad + 1);
+    const int pad = stft_pad_, min_n = stft_min_samples(n_fft_, hop_);
     ResamplePlan plan;
     if (input_rate_ && !resample_plan(input_rate_, hp.sampling_rate, plan, err)) return -1;
     nmax = 0;

@@ -627,6 +627,14 @@ struct SpectrogramCall {
     TensorRef out;
 };
 hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s);
+// The STFT's geometry and tables, stated once for the engine (prepare_conversion, check_conversion_pcm) and for vits_op_spectrogram. Host arithmetic only.
+// stft_geometry: empty where launch_spectrogram takes (n_fft, hop) — n_fft a power of two in [16, 2048], 1 <= hop <= n_fft, n_fft - hop even (a whole
+// reflection pad on each side) —, else the cause. stft_min_samples: an utterance has at least one hop, and more samples than the pad (the reflection's reach).
+std::string stft_geometry(int n_fft, int hop);
+inline int stft_pad(int n_fft, int hop) { return (n_fft - hop) / 2; }
+inline int stft_min_samples(int n_fft, int hop) { return std::max(hop, stft_pad(n_fft, hop) + 1); }
+// tw [n_fft]: n_fft / 2 pairs (re, im) of exp(-2 pi i m / n_fft); win [n_fft]: the periodic Hann window (torch.hann_window(n)). In double, rounded once to fp32.
+void stft_tables(int n_fft, std::vector<float>& tw, std::vector<float>& win);
 // z_q = mean + (eps * eps_scale) * exp(log_std) over [0, frames[b]) (eps: the counter stream of prior sampling, or `noise`; eps_scale 1 is VITS's draw
 // (eps * 1.0f is exact), 0 the posterior mean: no noise is drawn or read then); flip: channel c -> row channels - 1 - c
 hipError_t launch_posterior_sample(TensorRef mean, TensorRef logstd, const int* frames, TensorRef noise, int noise_kind, uint64_t seed, const int* seed_off,

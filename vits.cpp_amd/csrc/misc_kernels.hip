@@ -1703,7 +1703,10 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* x, int64_t 
         }
         float* wp = wave + (int64_t)b * w_bs + t;
         if (t + 4 <= hi) {
-            if (pre) *reinterpret_cast<float4*>(pre + (int64_t)b * p_bs + t) = make_float4(a0, a1, a2, a3);
+            // (x's rows are aligned on this path; pre's row is the caller's: a pitch that is no multiple of 4 gets the four values one by one)
+            float* pp = pre ? pre + (int64_t)b * p_bs + t : nullptr;
+            if (pp && (reinterpret_cast<uintptr_t>(pp) & 15) == 0) *reinterpret_cast<float4*>(pp) = make_float4(a0, a1, a2, a3);
+            else if (pp) pp[0] = a0, pp[1] = a1, pp[2] = a2, pp[3] = a3;
             wp[0] = tanhf(a0), wp[1] = tanhf(a1), wp[2] = tanhf(a2), wp[3] = tanhf(a3);
         } else {
             const float av[4] = {a0, a1, a2, a3};

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/vits.h"
 #include "../../include/vits_synth_noise.h"
@@ -79,6 +80,25 @@ __global__ __launch_bounds__(256) void spectrogram_kernel(const float* __restric
         }
         ob[(int64_t)k * o_cs + t] = v;
     }
+}
+
+std::string stft_geometry(int n_fft, int hop) {
+    if (n_fft < 16 || n_fft > 2048 || (n_fft & (n_fft - 1)))
+        return "n_fft = " + std::to_string(n_fft) + ": the spectrogram kernel needs a power of two in [16, 2048]";
+    if (hop < 1 || hop > n_fft || ((n_fft - hop) & 1))
+        return "hop " + std::to_string(hop) + " does not fit n_fft " + std::to_string(n_fft) + ": 1 <= hop <= n_fft, and (n_fft - hop) / 2 must be a whole pad";
+    return std::string();
+}
+
+void stft_tables(int n_fft, std::vector<float>& tw, std::vector<float>& win) {
+    tw.assign((size_t)n_fft, 0.f);
+    win.assign((size_t)n_fft, 0.f);
+    const double pi = 3.14159265358979323846;
+    for (int m = 0; m < n_fft / 2; ++m) {
+        tw[2 * m] = (float)std::cos(2.0 * pi * m / n_fft);
+        tw[2 * m + 1] = (float)-std::sin(2.0 * pi * m / n_fft);
+    }
+    for (int m = 0; m < n_fft; ++m) win[m] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * m / n_fft));
 }
 
 hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s) {
