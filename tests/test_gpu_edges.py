@@ -12,24 +12,9 @@ import numpy as np
 import pytest
 
 import edges_ref as ER
+from delivery_helpers import FS, LENS, MARGIN, PADS, SHAPE, choose, same
 
 pytestmark = pytest.mark.gpu
-
-FS = 16000
-LENS = np.array([5, 12, 31], np.int32)
-MARGIN = 1e-6
-CANDIDATES = (-0.5, -1.0, -1.5, -2.0, -3.0)
-# keep margins shorter than a window (a trimmed window stays visible), fades and unequal pads
-SHAPE = dict(keep_head_ms=2.5, keep_tail_ms=1.25, fade_in_ms=5.0, fade_out_ms=9.0, lead_ms=20.0, tail_ms=30.0)
-PADS = 320 + 480
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 @pytest.fixture(scope="module")
@@ -55,18 +40,6 @@ def plain(pkg, tiny, ids):
         assert tiny.last_edges() is None
         out[fd] = (pcm, lengths, frames, d)
     return out
-
-
-def choose(waves, need=2):
-    """the rule above: the first candidate that trims at least `need` of the utterances, with the margin on all of them"""
-    for th in CANDIDATES:
-        rows = [ER.edges(w, FS, ER.TRIM_RELATIVE, th, **SHAPE)[1] for w in waves]
-        margins = [ER.margin(w, FS, ER.TRIM_RELATIVE, th, **SHAPE) for w in waves]
-        trimmed = sum(int(r[0] > 0 or r[1] < w.size) for r, w in zip(rows, waves))
-        print(f"threshold {th} dB: rows {[r.tolist() for r in rows]}, margins {['%.2e' % m for m in margins]}")
-        if trimmed >= need and min(margins) >= MARGIN:
-            return th
-    return None
 
 
 @pytest.fixture(scope="module")

@@ -560,6 +560,22 @@ VITS_API int64_t vits_resample_length(int32_t in_rate, int32_t out_rate, int64_t
     return p.out_len(n);
     VITS_CATCH(-1)
 }
+// the report rows [rows][4] of the most recently completed call (vits_model_last_levels / _last_limits / _last_edges): returns 4 rows, and copies them when dst has room
+template <class T, class Read>
+static int64_t last_rows(vits_model* model, T* dst, size_t cap, Read read) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const T* p = read(model->eng, rows);
+    const size_t n = (size_t)4 * rows;
+    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(T) * n);
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
 // ---- a stated level (include/vits.h: the definition and the kinds) -------------------------------------------------------------------
 VITS_API int vits_model_set_level(vits_model* model, int32_t kind, float value_db, float ceiling_db) {
     VITS_TRY
@@ -582,18 +598,7 @@ VITS_API int vits_model_get_level(const vits_model* model, int32_t* kind, float*
     return 0;
 }
 VITS_API int64_t vits_model_last_levels(vits_model* model, float* dst, size_t cap) {
-    VITS_TRY
-    if (!model || (!dst && cap)) {
-        set_err("null argument");
-        return -1;
-    }
-    VITS_ENTER(model, -1)
-    int rows = 0;
-    const float* p = model->eng.last_levels(rows);
-    const size_t n = (size_t)4 * rows;
-    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(float) * n);
-    return (int64_t)n;
-    VITS_CATCH(-1)
+    return last_rows(model, dst, cap, [](const vits::Engine& e, int& rows) { return e.last_levels(rows); });
 }
 VITS_API int vits_loudness_plan(int32_t rate, double coef[10], int32_t* segment) {
     VITS_TRY
@@ -646,18 +651,7 @@ VITS_API int vits_model_get_limiter(const vits_model* model, int32_t* mode) {
     return 0;
 }
 VITS_API int64_t vits_model_last_limits(vits_model* model, float* dst, size_t cap) {
-    VITS_TRY
-    if (!model || (!dst && cap)) {
-        set_err("null argument");
-        return -1;
-    }
-    VITS_ENTER(model, -1)
-    int rows = 0;
-    const float* p = model->eng.last_limits(rows);
-    const size_t n = (size_t)4 * rows;
-    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(float) * n);
-    return (int64_t)n;
-    VITS_CATCH(-1)
+    return last_rows(model, dst, cap, [](const vits::Engine& e, int& rows) { return e.last_limits(rows); });
 }
 VITS_API int vits_limiter_plan(int32_t rate, int32_t* A, int32_t* H, int32_t* tile) {
     VITS_TRY
@@ -714,18 +708,7 @@ VITS_API int vits_model_get_edges(const vits_model* model, vits_edges_desc* desc
     return 0;
 }
 VITS_API int64_t vits_model_last_edges(vits_model* model, int64_t* dst, size_t cap) {
-    VITS_TRY
-    if (!model || (!dst && cap)) {
-        set_err("null argument");
-        return -1;
-    }
-    VITS_ENTER(model, -1)
-    int rows = 0;
-    const int64_t* p = model->eng.last_edges(rows);
-    const size_t n = (size_t)4 * rows;
-    if (n && dst && cap >= n) std::memcpy(dst, p, sizeof(int64_t) * n);
-    return (int64_t)n;
-    VITS_CATCH(-1)
+    return last_rows(model, dst, cap, [](const vits::Engine& e, int& rows) { return e.last_edges(rows); });
 }
 VITS_API int vits_edges_plan(int32_t rate, const vits_edges_desc* desc, int64_t out[8]) {
     VITS_TRY

@@ -1,0 +1,90 @@
+// delivery_plan.h — how a call's PCM travels from the vocoder to what is handed out (host only, like launch_plan.h and tile_map.h: no kernel, no device).
+// The stages behind the vocoder — stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
+// stage in front of them wrote. delivery_plan() states that chain ONCE, from what the handle and the call ask for: who runs, which buffer each stage reads
+// and writes, which buffer is delivered, which arena buffers the call therefore needs, or why the combination is refused. The engine allocates from the
+// plan (layout_stage_two) and resolves its buffer ids to pointers in one place (Call::rows_of); tests/golden/delivery_plan_table.txt pins the whole table.
+#pragma once
+
+namespace vits {
+
+// the closed set of buffers a stage can read or write; every buffer has one row stride (DeliveryStride)
+enum DeliveryBuf : int {
+    BUF_NONE = 0,  // nothing: the vocoder's source, the destination of a level that only measures
+    BUF_WAVE,      // s2.wave: the vocoder's waveform [B][S_stride]
+    BUF_EDGE,      // s2.wave_edge: the edges stage's output [B][E_stride]
+    BUF_LVL,       // s2.wave_lvl: the levelled (or limited) waveform, rows as long as its input's
+    BUF_OUT,       // s2.wave_out: the PCM at the output rate [B][out_ws]
+    BUF_CALLER,    // opts.out_device, rows out_device_stride apart
+    BUF_COUNT
+};
+enum DeliveryStride : int {
+    STRIDE_NONE = 0,
+    STRIDE_S,       // S_stride: the vocoder's rows
+    STRIDE_E,       // E_stride: the model-rate rows behind the edges stage (the bounds N + Pl + Pt)
+    STRIDE_OUT_WS,  // out_ws: the rows at the output rate
+    STRIDE_CALLER,  // out_device_stride
+    STRIDE_COUNT
+};
+// the level kinds as delivery sees them. The kinds that multiply are two here because only a plain gain streams
+enum DeliveryLevel : int {
+    DLEVEL_NONE = 0,
+    DLEVEL_MEASURE,  // VITS_LEVEL_MEASURE: reads, writes nothing
+    DLEVEL_GAIN,     // VITS_LEVEL_GAIN
+    DLEVEL_WHOLE,    // VITS_LEVEL_PEAK, VITS_LEVEL_LOUDNESS: the gain is known once the whole utterance is
+    DLEVEL_COUNT
+};
+enum DeliveryRefusal : int {
+    DELIVER_OK = 0,
+    REFUSE_LIMIT_STREAM,  // on_chunk with the limiter on and a level that multiplies
+    REFUSE_LEVEL_STREAM,  // on_chunk with a level that needs the whole utterance
+    REFUSE_EDGES_STREAM,  // on_chunk with the edges stage on
+    REFUSE_EDGES_ASYNC,   // async with the edges stage on
+    REFUSE_COUNT
+};
+enum DeliveryNeed : unsigned {
+    NEED_WAVE_EDGE = 1u << 0,
+    NEED_WAVE_LVL = 1u << 1,
+    NEED_WAVE_OUT = 1u << 2,
+    NEED_ED_SCRATCH = 1u << 3,
+    NEED_LVL_SCRATCH = 1u << 4,
+    NEED_LIM_SCRATCH = 1u << 5,
+    NEED_OUT_RANGES = 1u << 6,  // streaming at another rate: the output samples each window finalises
+    NEED_LVL_RANGES = 1u << 7,  // streaming under a gain: the model-rate samples each window finalises
+    NEED_COUNT = 8
+};
+
+struct DeliveryAsk {
+    bool edges = false;        // the handle's edges stage is on
+    int level = DLEVEL_NONE;   // DeliveryLevel of the handle's level kind
+    bool limiter = false;      // the handle's limiter is on (it acts when the level multiplies)
+    bool rate = false;         // an output rate is set
+    bool out_device = false;   // opts.out_device
+    bool on_chunk = false;     // opts.on_chunk
+    bool async = false;        // opts.async
+};
+
+struct DeliveryRoute {
+    int buf = BUF_NONE, stride = STRIDE_NONE;
+    bool operator==(const DeliveryRoute& o) const { return buf == o.buf && stride == o.stride; }
+};
+
+enum DeliveryStage : int { STAGE_VOCODER = 0, STAGE_EDGES, STAGE_LEVEL, STAGE_RESAMPLE, STAGE_COUNT };
+
+struct DeliveryPlan {
+    int refusal = DELIVER_OK;  // not DELIVER_OK: nothing else is set
+    struct Stage {
+        bool runs = false;
+        DeliveryRoute src, dst;
+        DeliveryRoute after;  // what the chain holds behind this stage: its dst, or (a stage that only reads) its src
+    } stage[STAGE_COUNT];
+    bool multiplies = false;  // the level stage writes (a plain multiply, or the limiter)
+    bool limits = false;      // ... through the limiter
+    DeliveryRoute delivered;  // what the call hands out: the destination of the last stage that writes
+    unsigned needs = 0;       // DeliveryNeed bits
+    bool need(unsigned bit) const { return (needs & bit) != 0; }
+    const Stage& operator[](int s) const { return stage[s]; }
+};
+
+DeliveryPlan delivery_plan(const DeliveryAsk& ask);
+
+}  // namespace vits

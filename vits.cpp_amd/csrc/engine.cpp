@@ -112,15 +112,8 @@ hipError_t Engine::conv(const char* name, const PackedConv& w, ConvCall c, hipSt
 int Engine::sync(std::string& err) {
     if (front_) HIP_OK(hipStreamSynchronize(front_));
     HIP_OK(hipStreamSynchronize(stream));
-    if (async_tail_ && last_lv_rows_ && last_lv_ != last_lv_store_.data()) {
-        // the rows of the async call have landed: keep them apart from the pinned copy, which a later submit into that slot overwrites
-        last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * last_lv_rows_);
-        last_lv_ = last_lv_store_.data();
-    }
-    if (async_tail_ && last_lm_rows_ && last_lm_ != last_lm_store_.data()) {
-        last_lm_store_.assign(last_lm_, last_lm_ + (size_t)4 * last_lm_rows_);
-        last_lm_ = last_lm_store_.data();
-    }
+    // (the rows of an async call have landed now)
+    lv_.settle(), lm_.settle(), ed_.settle();
     async_tail_ = false;
     return 0;
 }
@@ -262,49 +255,60 @@ int Engine::set_limiter(int mode, std::string& err) {
     return 0;
 }
 
-int Engine::grow_rows(float*& rows, int& cap_now, int B, std::string& err) {
-    if (B <= cap_now) return 0;
-    // (grow-only; the old rows are the previous call's, already on their way to the host in stream order — hipFree waits for them)
-    const int cap = std::max(B, 64);
-    float* fresh = nullptr;
-    HIP_OK(hipMalloc((void**)&fresh, sizeof(float) * 4 * (size_t)cap));
-    if (rows) {
-        for (void*& p : owned_)
-            if (p == rows) p = fresh;
-        hipFree(rows);
-    } else owned_.push_back(fresh);
-    weight_bytes += (int64_t)sizeof(float) * 4 * (cap - cap_now);
-    rows = fresh, cap_now = cap;
-    return 0;
+int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err) const {
+    DeliveryAsk ask;
+    ask.edges = edges_on();
+    switch (level_kind_) {
+        case VITS_LEVEL_NONE: ask.level = DLEVEL_NONE; break;
+        case VITS_LEVEL_MEASURE: ask.level = DLEVEL_MEASURE; break;
+        case VITS_LEVEL_GAIN: ask.level = DLEVEL_GAIN; break;
+        default: ask.level = DLEVEL_WHOLE; break;  // (peak, loudness)
+    }
+    ask.limiter = limit_mode_ != VITS_LIMIT_OFF;
+    ask.rate = output_rate_ != 0;
+    ask.out_device = o.out_device != nullptr;
+    ask.on_chunk = o.on_chunk != nullptr;
+    ask.async = o.async != 0;
+    plan = delivery_plan(ask);
+    switch (plan.refusal) {
+        case DELIVER_OK: return 0;
+        case REFUSE_LIMIT_STREAM:
+            err = "on_chunk streams an utterance while it is being made, and this handle's limiter (vits_model_set_limiter) is on: the gain of a sample looks " +
+                  std::to_string(limit_plan_.A) + " samples ahead and " + std::to_string(limit_plan_.H + limit_plan_.A) +
+                  " back, so a window's last samples are not final when it ends, and the halo of finished samples that streaming would need is not built: "
+                  "stream with VITS_LIMIT_OFF, or limit without on_chunk";
+            break;
+        case REFUSE_LEVEL_STREAM:
+            err = "on_chunk streams an utterance while it is being made, and this handle's level (vits_model_set_level: measure, peak or loudness) needs the whole "
+                  "utterance before its first sample can leave: only VITS_LEVEL_GAIN streams";
+            break;
+        case REFUSE_EDGES_STREAM:
+            err = "on_chunk streams an utterance while it is being made, and this handle's edges stage (vits_model_set_edges) is on: the end of the utterance decides "
+                  "what leaves (the last active window, the fade-out and the silence behind it count from there), so no sample can leave before the last one is made: "
+                  "stream with VITS_EDGES_OFF, or set edges without on_chunk";
+            break;
+        case REFUSE_EDGES_ASYNC:
+            err = "async returns before the device has finished, and this handle's edges stage (vits_model_set_edges) is on: lengths[] of the result is read from the "
+                  "device (the trimmed length depends on the audio), which needs a host read behind the call's work: call without async, or pipeline with "
+                  "vits_model_submit_batch / vits_model_wait";
+            break;
+        default: err = "this combination of delivery stages is not supported"; break;
+    }
+    return -1;
 }
 
-int Engine::check_level(const vits_process_opts& o, std::string& err) const {
-    if (o.on_chunk && limit_mode_ != VITS_LIMIT_OFF && level_kind_ >= VITS_LEVEL_GAIN) {
-        err = "on_chunk streams an utterance while it is being made, and this handle's limiter (vits_model_set_limiter) is on: the gain of a sample looks " +
-              std::to_string(limit_plan_.A) + " samples ahead and " + std::to_string(limit_plan_.H + limit_plan_.A) +
-              " back, so a window's last samples are not final when it ends, and the halo of finished samples that streaming would need is not built: "
-              "stream with VITS_LIMIT_OFF, or limit without on_chunk";
-        return -1;
-    }
-    if (o.on_chunk && level_kind_ != VITS_LEVEL_NONE && level_kind_ != VITS_LEVEL_GAIN) {
-        err = "on_chunk streams an utterance while it is being made, and this handle's level (vits_model_set_level: measure, peak or loudness) needs the whole "
-              "utterance before its first sample can leave: only VITS_LEVEL_GAIN streams";
-        return -1;
-    }
-    return 0;
-}
-
-// the tail of a levelling call: loudness, peak and gain of every utterance of the vocoder's waveform (c.wave_dst: the call's own buffer, or out_device under
-// VITS_LEVEL_MEASURE, which changes no PCM path) -> lv_rows_, the multiply into dst (every kind but MEASURE; a
+// the tail of a levelling call: loudness, peak and gain of every utterance of the stage's source (the plan's: what the vocoder or the edges stage wrote; under
+// VITS_LEVEL_MEASURE that may be out_device, and no PCM path changes) -> the levels rows, the multiply into the stage's destination (every kind but MEASURE; a
 // streaming call has multiplied window by window already), and the rows on their way to the slot's pinned copy
-int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
+int Engine::run_level(Call& c) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up;
-    if (grow_rows(lv_rows_, lv_cap_, B, err)) return -1;
+    const Call::Rows src = c.rows_of(c.dp[STAGE_LEVEL].src), dst = c.rows_of(c.dp[STAGE_LEVEL].dst);
+    HIP_OK(lv_.grow(B, owned_, weight_bytes));
     const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
     LevelCall lc;
-    lc.x = c.wave_dst;
-    lc.x_stride = c.wave_stride;
+    lc.x = src.p;
+    lc.x_stride = src.stride;
     lc.lens = c.mr_lens;
     lc.batch = B;
     lc.max_len = c.mr_max;
@@ -314,22 +318,22 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
     lc.value_db = level_value_;
     lc.ceiling_db = level_ceiling_;
     lc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);
-    lc.levels = lv_rows_;
+    lc.levels = lv_.dev();
     // two walks of the cascade (9 fp64 fma a sample each) and the squares; the samples read twice
     prof.begin("level_measure", 2.0 * (2 * 9 + 1) * (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
     hipError_t e = launch_level_measure(lc, stream);
     prof.end(stream);
     HIP_OK(e);
-    if (c.lim) {
+    if (c.dp.limits) {
         // the limiter in place of the plain multiply: meter, g0 (which replaces the measured row's gain), limiter, meter of what is delivered
-        if (grow_rows(lm_rows_, lm_cap_, B, err)) return -1;
+        HIP_OK(lm_.grow(B, owned_, weight_bytes));
         const RateTable* up = rate_table(hp.sampling_rate, 4 * hp.sampling_rate, err);
         if (!up) return -1;
         LimitCall mc;
-        mc.x = c.wave_dst;
-        mc.x_stride = c.wave_stride;
-        mc.y = dst;
-        mc.y_stride = dst_stride;
+        mc.x = src.p;
+        mc.x_stride = src.stride;
+        mc.y = dst.p;
+        mc.y_stride = dst.stride;
         mc.lens = lc.lens;
         mc.batch = B;
         mc.max_len = c.mr_max;
@@ -340,24 +344,22 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
         mc.value_db = level_value_;
         mc.gain = lc.gain;
         mc.ceiling = (float)std::pow(10.0, (double)level_ceiling_ / 20.0);
-        mc.levels = lv_rows_;
-        mc.limits = lm_rows_;
+        mc.levels = lv_.dev();
+        mc.limits = lm_.dev();
         // two meter passes (4 K fma a sample each); the doubling steps and the mean; x, e and y read, e and y written
         prof.begin("limit", (2.0 * 2 * 4 * limit_plan_.up.K + limit_plan_.A + 16) * (double)samples, 20.0 * (double)samples, stream, /*chain=*/true);
         e = launch_limit(mc, stream);
         prof.end(stream);
         HIP_OK(e);
-        PinnedBuf<float>& lh = lm_host_[a1_slot_ & 1];
-        HIP_OK(lh.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
-        HIP_OK(hipMemcpyAsync(lh.p, lm_rows_, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
-    } else if (c.lev_apply && !c.o.on_chunk) {
+        HIP_OK(lm_.queue_copy(a1_slot_, B, stream));
+    } else if (c.dp.multiplies && !c.o.on_chunk) {
         LevelScale sc;
-        sc.x = c.wave_dst;
-        sc.x_stride = c.wave_stride;
-        sc.y = dst;
-        sc.y_stride = dst_stride;
+        sc.x = src.p;
+        sc.x_stride = src.stride;
+        sc.y = dst.p;
+        sc.y_stride = dst.stride;
         sc.lens = lc.lens;
-        sc.levels = lv_rows_;
+        sc.levels = lv_.dev();
         sc.batch = B;
         sc.max_range = c.mr_max;
         prof.begin("level_scale", (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
@@ -365,9 +367,7 @@ int Engine::run_level(Call& c, float* dst, int64_t dst_stride) {
         prof.end(stream);
         HIP_OK(e);
     }
-    PinnedBuf<float>& host = lv_host_[a1_slot_ & 1];
-    HIP_OK(host.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
-    HIP_OK(hipMemcpyAsync(host.p, lv_rows_, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    HIP_OK(lv_.queue_copy(a1_slot_, B, stream));
     prof.fence();
     return 0;
 }
@@ -391,43 +391,14 @@ int Engine::set_edges(const vits_edges_desc* d, std::string& err) {
     return 0;
 }
 
-int Engine::check_edges(const vits_process_opts& o, std::string& err) const {
-    if (!edges_on()) return 0;
-    if (o.on_chunk) {
-        err = "on_chunk streams an utterance while it is being made, and this handle's edges stage (vits_model_set_edges) is on: the end of the utterance decides "
-              "what leaves (the last active window, the fade-out and the silence behind it count from there), so no sample can leave before the last one is made: "
-              "stream with VITS_EDGES_OFF, or set edges without on_chunk";
-        return -1;
-    }
-    if (o.async) {
-        err = "async returns before the device has finished, and this handle's edges stage (vits_model_set_edges) is on: lengths[] of the result is read from the "
-              "device (the trimmed length depends on the audio), which needs a host read behind the call's work: call without async, or pipeline with "
-              "vits_model_submit_batch / vits_model_wait";
-        return -1;
-    }
-    return 0;
-}
-
-// the edges stage of a call: the vocoder's waveform c.s2.wave -> dst (the call's own buffer, or out_device when nothing follows), the trimmed lengths and
-// the rows on the device, and the rows on their way to the slot's pinned copy. From here on c.mr_lens is the stage's
-int Engine::run_edges(Call& c, float* dst, int64_t dst_stride) {
+// the edges stage of a call: the vocoder's waveform -> the stage's destination (the plan's: the call's own buffer, or out_device when nothing follows), the
+// trimmed lengths (c.mr_lens: what every stage behind this one reads its rows' lengths from) and the rows on the device, and the rows on their way to the
+// slot's pinned copy
+int Engine::run_edges(Call& c) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up;
     const EdgesPlan& p = edges_plan_;
-    if (B > ed_cap_) {
-        // (grow-only, as grow_rows: int64 [cap][4], then int32 [cap])
-        const int cap = std::max(B, 64);
-        const size_t per_row = sizeof(int64_t) * 4 + sizeof(int);
-        int64_t* fresh = nullptr;
-        HIP_OK(hipMalloc((void**)&fresh, per_row * (size_t)cap));
-        if (ed_rows_) {
-            for (void*& q : owned_)
-                if (q == ed_rows_) q = fresh;
-            hipFree(ed_rows_);
-        } else owned_.push_back(fresh);
-        weight_bytes += (int64_t)per_row * (cap - ed_cap_);
-        ed_rows_ = fresh, ed_cap_ = cap;
-    }
+    const Call::Rows src = c.rows_of(c.dp[STAGE_EDGES].src), dst = c.rows_of(c.dp[STAGE_EDGES].dst);
     if (ed_fades_stale_) {
         const std::vector<float> t = edges_fades(p);
         if (ed_fades_) {
@@ -447,18 +418,18 @@ int Engine::run_edges(Call& c, float* dst, int64_t dst_stride) {
         ed_fades_stale_ = false;
     }
     EdgesCall ec;
-    ec.x = c.s2.wave;
-    ec.x_stride = c.S_stride;
+    ec.x = src.p;
+    ec.x_stride = src.stride;
     ec.lens = c.s1.stage_lens + (size_t)n_up * B;
-    ec.y = dst;
-    ec.y_stride = dst_stride;
+    ec.y = dst.p;
+    ec.y_stride = dst.stride;
     ec.batch = B;
     ec.max_len = c.smax[n_up];
     ec.plan = p;
     ec.fades = ed_fades_;
     ec.scratch = c.s2.ed_scratch;
-    ec.lens_out = reinterpret_cast<int*>(ed_rows_ + (size_t)4 * ed_cap_);
-    ec.rows = ed_rows_;
+    ec.lens_out = static_cast<int*>(ed_.tail());  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
+    ec.rows = ed_.dev();
     const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
     hipError_t e = hipSuccess;
     if (p.mode != VITS_EDGES_PAD) {
@@ -477,11 +448,8 @@ int Engine::run_edges(Call& c, float* dst, int64_t dst_stride) {
     e = launch_edges_apply(ec, stream);
     prof.end(stream);
     HIP_OK(e);
-    PinnedBuf<int64_t>& host = ed_host_[a1_slot_ & 1];
-    HIP_OK(host.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64));
-    HIP_OK(hipMemcpyAsync(host.p, ed_rows_, sizeof(int64_t) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    HIP_OK(ed_.queue_copy(a1_slot_, B, stream));
     prof.fence();
-    c.mr_lens = ec.lens_out;
     return 0;
 }
 
@@ -492,10 +460,23 @@ void Engine::edges_lengths(const int64_t* rows, int B, int64_t* lengths) const {
     for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(rows[(size_t)4 * b + 2]);
 }
 
-void Engine::keep_edges(const int64_t* rows, int B, bool append) {
-    if (!append) last_ed_store_.clear();
-    last_ed_store_.insert(last_ed_store_.end(), rows, rows + (size_t)4 * B);
-    last_ed_rows_ = (int)(last_ed_store_.size() / 4);
+void Engine::batch_landed(Pending& p, int slot, bool append) {
+    lv_.landed(slot, p.lv_rows, append);
+    lm_.landed(slot, p.lm_rows, append);
+    if (p.ed_rows) edges_lengths(ed_.slot_rows(slot), p.ed_rows, p.lengths.data());
+    ed_.landed(slot, p.ed_rows, append);
+}
+
+// the one place that allocates what a call hands out: lengths[] and frames[] of B utterances, no PCM yet
+template <class LenIt, class FrameIt>
+static void fill_result(vits_batch_result* out, int B, size_t stride, LenIt lengths, FrameIt frames) {
+    out->batch = (size_t)B;
+    out->stride = stride;
+    out->lengths = new int64_t[B];
+    out->frames = new int64_t[B];
+    out->data = nullptr;
+    std::copy_n(lengths, B, out->lengths);
+    std::copy_n(frames, B, out->frames);
 }
 
 int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const {
@@ -533,11 +514,9 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
     if (refuse_pending(err)) return -1;
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
-    if (check_level(o, err)) return -1;
-    if (check_edges(o, err)) return -1;
-    last_lv_rows_ = 0;
-    last_lm_rows_ = 0;
-    last_ed_rows_ = 0;
+    DeliveryPlan refusable;  // (the refusals of the delivery chain, before stage one is queued; the call's own plan is made where its stage two begins)
+    if (plan_delivery(o, refusable, err)) return -1;
+    clear_reports();
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
@@ -594,44 +573,17 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
             }
         }
     } release{*this, part};
-    if (!rc && part[0]->lv_rows + part[1]->lv_rows > 0) {
-        // (the parts' rows side by side; part h lives in pipeline slot (wait_seq_ + h) & 1)
-        last_lv_store_.clear();
-        for (int h = 0; h < 2; ++h) {
-            const float* rows = lv_host_[(wait_seq_ + h) & 1].p;
-            last_lv_store_.insert(last_lv_store_.end(), rows, rows + (size_t)4 * part[h]->lv_rows);
-        }
-        last_lv_ = last_lv_store_.data();
-        last_lv_rows_ = (int)(last_lv_store_.size() / 4);
-    }
-    if (!rc && part[0]->lm_rows + part[1]->lm_rows > 0) {
-        last_lm_store_.clear();
-        for (int h = 0; h < 2; ++h) {
-            const float* rows = lm_host_[(wait_seq_ + h) & 1].p;
-            last_lm_store_.insert(last_lm_store_.end(), rows, rows + (size_t)4 * part[h]->lm_rows);
-        }
-        last_lm_ = last_lm_store_.data();
-        last_lm_rows_ = (int)(last_lm_store_.size() / 4);
-    }
-    if (!rc && part[0]->ed_rows + part[1]->ed_rows > 0)
-        for (int h = 0; h < 2; ++h) {
-            // (the trimmed lengths of a part are known now that its rows have landed)
-            const int64_t* rows = ed_host_[(wait_seq_ + h) & 1].p;
-            edges_lengths(rows, part[h]->ed_rows, part[h]->lengths.data());
-            keep_edges(rows, part[h]->ed_rows, /*append=*/h > 0);
-        }
+    // the parts' rows side by side (part h lives in pipeline slot (wait_seq_ + h) & 1); the trimmed lengths of a part are known now that its rows have landed
+    for (int h = 0; h < 2 && !rc; ++h) batch_landed(*part[h], (int)((wait_seq_ + h) & 1), /*append=*/h > 0);
     if (!rc && out) {
         const size_t stride = std::max(part[0]->stride, part[1]->stride);
-        out->batch = (size_t)B;
-        out->stride = stride;
-        out->lengths = new int64_t[B];
-        out->frames = new int64_t[B];
-        out->data = nullptr;
+        std::vector<int64_t> lengths(part[0]->lengths), frames(part[0]->frames);
+        lengths.insert(lengths.end(), part[1]->lengths.begin(), part[1]->lengths.end());
+        frames.insert(frames.end(), part[1]->frames.begin(), part[1]->frames.end());
+        fill_result(out, B, stride, lengths.begin(), frames.begin());
         if (!o.skip_host_copy) out->data = new float[(size_t)B * stride];
         for (int h = 0; h < 2; ++h) {
             const Pending& p = *part[h];
-            std::copy(p.lengths.begin(), p.lengths.end(), out->lengths + b0[h]);
-            std::copy(p.frames.begin(), p.frames.end(), out->frames + b0[h]);
             if (out->data)
                 for (int b = 0; b < nb[h]; ++b) {
                     float* dst = out->data + (size_t)(b0[h] + b) * stride;
@@ -686,36 +638,17 @@ int Engine::wait_batch(vits_batch_result* out, std::string& err) {
     }
     Pending& p = pend_[wait_seq_ & 1];
     HIP_OK(hipEventSynchronize(p.done));
-    last_ed_rows_ = 0;
-    if (p.ed_rows) {
-        // stated edges: the batch's lengths are its trimmed ones, on the host now that `done` has passed (copied: the slot's pinned rows are the next submit's)
-        const int64_t* rows = ed_host_[wait_seq_ & 1].p;
-        edges_lengths(rows, p.ed_rows, p.lengths.data());
-        keep_edges(rows, p.ed_rows);
-    }
+    // the reports of the batch that has just completed, on the host now that `done` has passed (copied: the slot's pinned rows are the next submit's); stated
+    // edges: the batch's lengths are its trimmed ones
+    batch_landed(p, (int)(wait_seq_ & 1));
     if (out) {
         // (the slot is released only once the result has been handed over: an allocation failure below leaves the batch waitable)
-        out->batch = (size_t)p.B;
-        out->stride = p.stride;
-        out->lengths = new int64_t[p.B];
-        out->frames = new int64_t[p.B];
-        std::copy(p.lengths.begin(), p.lengths.end(), out->lengths);
-        std::copy(p.frames.begin(), p.frames.end(), out->frames);
-        out->data = nullptr;
+        fill_result(out, p.B, p.stride, p.lengths.begin(), p.frames.begin());
         if (p.host_copy) {
             out->data = new float[(size_t)p.B * p.stride];
             std::memcpy(out->data, p.host.p, sizeof(float) * (size_t)p.B * p.stride);
         }
     }
-    // the levels of the batch that has just completed (copied: the slot's pinned rows are the next submit's)
-    const float* rows = lv_host_[wait_seq_ & 1].p;
-    last_lv_store_.assign(rows, rows + (size_t)4 * p.lv_rows);
-    last_lv_ = last_lv_store_.data();
-    last_lv_rows_ = p.lv_rows;
-    const float* lrows = lm_host_[wait_seq_ & 1].p;
-    last_lm_store_.assign(lrows, lrows + (size_t)4 * p.lm_rows);
-    last_lm_ = last_lm_store_.data();
-    last_lm_rows_ = p.lm_rows;
     p.active = false;
     ++wait_seq_;
     return 0;
@@ -877,20 +810,14 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     if (o.frames_only) {
         // dispatcher query: predicted frames / samples per utterance, no audio (buffer sizing, shard balancing by frames)
         if (out) {
-            out->batch = (size_t)B;
             // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
             ResamplePlan plan;
             if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
             // (stated edges: the bound N + Pl + Pt of every utterance, the size to allocate: exact under VITS_EDGES_PAD, an upper bound when the stage trims)
             const int64_t pads = edges_on() ? edges_plan_.Pl + edges_plan_.Pt : 0;
-            out->stride = (size_t)plan.out_len(c.smax[n_up] + pads);
-            out->lengths = new int64_t[B];
-            out->frames = new int64_t[B];
-            out->data = nullptr;
-            for (int b = 0; b < B; ++b) {
-                out->lengths[b] = plan.out_len(c.slen[n_up][b] + pads);
-                out->frames[b] = frames[b];
-            }
+            std::vector<int64_t> lengths(B);
+            for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.slen[n_up][b] + pads);
+            fill_result(out, B, (size_t)plan.out_len(c.smax[n_up] + pads), lengths.begin(), frames.begin());
         }
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
@@ -987,6 +914,86 @@ void Engine::window_tile_maps(const Call& c, WinCtx& w) const {
         if (j.win == (int)w.wi && c.s2.tile_maps) (j.convt ? w.maps_up[j.vec] : w.maps[j.vec]).add(TileMapRef{c.s2.tile_maps + j.off, (int)j.n, j.width, j.convt});
 }
 
+// After window w the model-rate samples [0, E_w) of an utterance are final: everything once it has ended, else up to the end of the frames the window owns.
+// Row w of the table holds, per utterance, [what was final before w, what is final after it) in final_of's unit; a window that finalises nothing for an
+// utterance holds an empty range there.
+int Engine::upload_ranges(Call& c, std::vector<int>& table, int* dev, const std::function<int(int, int64_t)>& final_of) {
+    std::string& err = c.err;
+    const int B = c.B;
+    table.assign(c.wins.size() * (size_t)2 * B, 0);
+    std::vector<int> prev(B, 0);
+    for (size_t w = 0; w < c.wins.size(); ++w)
+        for (int b = 0; b < B; ++b) {
+            const Call::Win& wn = c.wins[w];
+            int done = prev[b];
+            if (c.frames[b] > wn.f0) {
+                const int64_t e = c.frames[b] <= wn.f1 ? c.slen[c.n_up][b] : (int64_t)wn.f1 * c.M;
+                done = std::max(done, final_of(b, e));
+            }
+            table[(w * 2) * B + b] = prev[b];
+            table[(w * 2 + 1) * B + b] = done;
+            prev[b] = done;
+        }
+    HIP_OK(hipMemcpyAsync(dev, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice, stream));
+    prof.fence();
+    HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
+    return 0;
+}
+
+// ---- everything behind the last vocoder window: the stages the call's plan runs, each reading what the one in front of it wrote (Call::rows_of of the plan's
+// routes), their taps, and the last window's chunks of a streaming call
+int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<int()>& last_chunks) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const DeliveryPlan& dp = c.dp;
+    const int B = c.B, n_up = c.n_up;
+    const bool rs = dp[STAGE_RESAMPLE].runs;
+    auto tap = [&](const char* name, const DeliveryRoute& r, int max_len, const std::vector<int>& lens) {
+        const Call::Rows rows = c.rows_of(r);
+        TensorRef t;
+        t.p = rows.p;
+        t.bs = rows.stride;
+        t.cs = (int)t.bs;
+        snapshot(name, t, 1, max_len, B, lens);
+    };
+    // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
+    std::vector<int> tap_len = c.slen[n_up], tap_out_len = c.out_len;
+    int tap_max = c.smax[n_up], tap_out_max = c.out_max;
+    if (dp[STAGE_EDGES].runs) {
+        if (run_edges(c)) return -1;
+        if (o.collect_taps) {
+            // (a tap carries its rows' lengths: this debugging path reads the trimmed ones here, the call proper at its own synchronisation)
+            HIP_OK(hipStreamSynchronize(stream));
+            prof.fence();
+            const int64_t* rows = ed_.slot_rows(a1_slot_);
+            tap_max = tap_out_max = 0;
+            for (int b = 0; b < B; ++b) {
+                tap_len[b] = (int)rows[(size_t)4 * b + 2];
+                tap_max = std::max(tap_max, tap_len[b]);
+                if (rs) tap_out_max = std::max(tap_out_max, tap_out_len[b] = (int)c.rate_out->plan.out_len(tap_len[b]));
+            }
+            tap("waveform_edges", dp[STAGE_EDGES].after, tap_max, tap_len);
+        }
+    }
+    if (dp[STAGE_LEVEL].runs) {
+        if (run_level(c)) return -1;
+        if (o.collect_taps) tap("waveform_level", dp[STAGE_LEVEL].after, tap_max, tap_len);
+    }
+    if (rs && !o.on_chunk) {
+        // nobody waits for parts of it: one launch over every utterance, behind the last window
+        rsc.max_range = c.out_max;
+        HIP_OK(resample("resample_out", rsc, c.sum_frames * c.M + (int64_t)B * c.sadd[n_up], std::accumulate(c.out_len.begin(), c.out_len.end(), (int64_t)0)));
+    }
+    if (rs && o.collect_taps) tap("waveform_out", dp[STAGE_RESAMPLE].after, tap_out_max, tap_out_len);
+    if (last_chunks)
+        if (int rc = last_chunks()) {
+            hipStreamSynchronize(stream);
+            err = rc > 0 ? "aborted by the on_chunk callback" : "hipEventSynchronize failed";
+            return -1;
+        }
+    return 0;
+}
+
 // ---- stage two from the known frame counts on: vocoder windows, arena, latent (prior sampling, or the conversion front end), flow, vocoder,
 // results. Shared by process_impl and convert_batch.
 int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async) {
@@ -994,6 +1001,9 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     const vits_process_opts& o = c.o;
     const int B = c.B, n_up = c.n_up, Lmax = c.Lmax;
     const std::vector<int>& frames = c.frames;
+    // the delivery chain behind the vocoder, planned once (its refusals were the entry points', before stage one was queued: nothing is refused here that was not there)
+    if (plan_delivery(o, c.dp, err)) return -1;
+    const DeliveryPlan& dp = c.dp;
     // ---- vocoder windows (long-form / streaming, vits.h vocoder_chunk_frames) ------------------------------------
     // Window w owns frames [f0, f1) and computes frames [lo, hi) = the owned range widened by the vocoder's receptive
     // field (halo_frames_): every sample it emits sees exactly the inputs it sees in a whole-utterance run, in the same
@@ -1014,8 +1024,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     for (const Call::Win& w : wins) c.Lw_max = std::max(c.Lw_max, w.hi - w.lo);
     const int M = c.M = c.smul[n_up];  // samples per frame
     // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
-    // (on_chunk and async with it on were refused by process_batch / convert_batch, before stage one was queued)
-    const bool ed = c.ed = edges_on();
+    const bool ed = dp[STAGE_EDGES].runs;
     c.mr_len = c.slen[n_up];
     if (ed)
         for (int b = 0; b < B; ++b) {
@@ -1027,7 +1036,6 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             c.mr_len[b] = (int)n;
         }
     c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
-    c.mr_lens = c.s1.stage_lens + (size_t)n_up * B;  // (device; run_edges swaps its own in)
     if (output_rate_) {
         // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and
         // resample.hip writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities
@@ -1044,12 +1052,11 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         }
         c.out_ws = round_up(std::max(c.out_max, 1), 32);
     }
-    const bool rs = c.rate_out != nullptr;
+    const bool rs = dp[STAGE_RESAMPLE].runs;
     // a level that multiplies (every kind but VITS_LEVEL_MEASURE): the vocoder writes to the call's own buffer, loudness.hip measures it there and
     // multiplies it into what is delivered, or into the resampler's input. VITS_LEVEL_MEASURE measures the waveform where the vocoder wrote it
-    c.lev = level_kind_;  // (on_chunk with a kind that cannot stream was refused by process_batch / convert_batch, before stage one was queued)
-    const bool la = c.lev_apply = level_kind_ >= VITS_LEVEL_GAIN;
-    c.lim = la && limit_mode_ != VITS_LIMIT_OFF;  // (never with on_chunk: check_level)
+    c.lev = level_kind_;
+    const bool la = dp.multiplies;
 
     // (a call that returns with device work queued owns no pinned memory that outlives the copy of its lists: it keeps the dense grids)
     if (pend || !want_async) plan_tile_maps(c);
@@ -1066,11 +1073,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
 
     // ---- HiFiGAN (vits.cpp:583-644), window by window ---------------------------------------------------------------
     c.rx.phase("vits.hifigan");
-    const std::vector<int>& smax = c.smax;
     const std::vector<int>& smul = c.smul;
     const std::vector<int>& sadd = c.sadd;
-    c.wave_dst = c.s2.wave;
-    c.wave_stride = c.S_stride;
     // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
     // (stated edges: the bounds; the lengths proper are read from the stage's rows where the results are filled)
     const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
@@ -1081,26 +1085,23 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             if (rs) err += " (" + std::to_string(pcm_max) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
             return -1;
         }
-        if (!rs && !la && !ed) {
-            c.wave_dst = (float*)o.out_device;
-            c.wave_stride = o.out_device_stride;
-        }
     }
-    // the stage's output: delivered as it is (straight to out_device), or what levelling / the resampler read
-    float* const ed_dst = !ed ? nullptr : (!rs && !la && o.out_device) ? (float*)o.out_device : c.s2.wave_edge;
-    const int64_t ed_stride = !ed ? 0 : (!rs && !la && o.out_device) ? o.out_device_stride : (int64_t)c.E_stride;
-    float* const wave_dst = c.wave_dst;
-    const int64_t wave_stride = c.wave_stride;
-    // the levelled model-rate waveform: delivered as it is (straight to out_device), or the resampler's input
-    float* const lvl_dst = !la ? nullptr : (!rs && o.out_device) ? (float*)o.out_device : c.s2.wave_lvl;
-    const int64_t lvl_stride = !la ? 0 : (!rs && o.out_device) ? o.out_device_stride : (int64_t)c.E_stride;
-    float* const pcm_dst = rs ? (o.out_device ? (float*)o.out_device : c.s2.wave_out) : la ? lvl_dst : ed ? ed_dst : wave_dst;
-    const int64_t pcm_stride = rs ? (o.out_device ? o.out_device_stride : (int64_t)c.out_ws) : la ? lvl_stride : ed ? ed_stride : wave_stride;
+    // the device lengths [B] of the model-rate rows, for every stage behind the vocoder: its sample counts, or what the edges stage will write behind its rows
+    c.mr_lens = c.s1.stage_lens + (size_t)n_up * B;
+    if (ed) {
+        HIP_OK(ed_.grow(B, owned_, weight_bytes));
+        c.mr_lens = static_cast<const int*>(ed_.tail());
+    }
+    // where the plan routes the vocoder's waveform and what is delivered (Call::rows_of: straight to out_device when nothing follows)
+    const Call::Rows wave = c.rows_of(dp[STAGE_VOCODER].dst), pcm = c.rows_of(dp.delivered);
+    float* const pcm_dst = pcm.p;
+    const int64_t pcm_stride = pcm.stride;
     ResampleCall rsc;
     if (rs) {
-        rsc.x = la ? lvl_dst : ed ? ed_dst : c.s2.wave;
-        rsc.x_stride = c.E_stride;
-        rsc.lens = c.mr_lens;  // (device: every utterance's samples at the model's rate; run_edges swaps the trimmed ones in below)
+        const Call::Rows x = c.rows_of(dp[STAGE_RESAMPLE].src);
+        rsc.x = x.p;
+        rsc.x_stride = x.stride;
+        rsc.lens = c.mr_lens;  // (device: every utterance's samples at the model's rate, the trimmed ones under stated edges)
         rsc.y = pcm_dst;
         rsc.y_stride = pcm_stride;
         rsc.taps = c.rate_out->taps;
@@ -1116,48 +1117,21 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     } chunk_ev_guard{chunk_ev};
     float* host_pcm = nullptr;  // pinned [B][smax] staging of the streamed PCM
     const size_t out_stride = (size_t)pcm_max;
-    // streaming at another rate: after window w the model-rate samples [0, E_w) of an utterance are final (E_w: what deliver computes below), and with them
-    // the output samples whose taps all lie in there (ResamplePlan::final_prefix; everything once the utterance has ended: the zeros behind its end are
-    // final). Window w resamples and delivers [o_(w-1), o_w): rg [window][2][B], on the device as s2.out_ranges.
+    // streaming at another rate: after window w the model-rate samples [0, E_w) of an utterance are final, and with them the output samples whose taps all lie
+    // in there (ResamplePlan::final_prefix; everything once the utterance has ended: the zeros behind its end are final). Window w resamples and delivers
+    // [o_(w-1), o_w): rg [window][2][B], on the device as s2.out_ranges.
     std::vector<int> rg;
-    if (rs && o.on_chunk) {
-        rg.assign(wins.size() * (size_t)2 * B, 0);
-        std::vector<int> prev(B, 0);
-        for (size_t w = 0; w < wins.size(); ++w)
-            for (int b = 0; b < B; ++b) {
-                const Call::Win& wn = wins[w];
-                int done = prev[b];
-                if (frames[b] > wn.f0) {
-                    const int64_t n = c.slen[n_up][b], e = frames[b] <= wn.f1 ? n : (int64_t)wn.f1 * M;
-                    done = std::max(done, (int)c.rate_out->plan.final_prefix(e, n));
-                }
-                rg[(w * 2) * B + b] = prev[b];
-                rg[(w * 2 + 1) * B + b] = done;
-                prev[b] = done;
-            }
-        HIP_OK(hipMemcpyAsync(c.s2.out_ranges, rg.data(), sizeof(int) * rg.size(), hipMemcpyHostToDevice, stream));
-        prof.fence();
-        HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
-    }
+    if (rs && o.on_chunk && upload_ranges(c, rg, c.s2.out_ranges, [&](int b, int64_t e) { return (int)c.rate_out->plan.final_prefix(e, c.slen[n_up][b]); })) return -1;
     // streaming under VITS_LEVEL_GAIN: window w multiplies the model-rate samples it makes final, [E_(w-1), E_w) of every utterance, once: lrg [window][2][B]
     std::vector<int> lrg;
     LevelScale lsc;
     if (la && o.on_chunk) {
-        lrg.assign(wins.size() * (size_t)2 * B, 0);
-        for (size_t w = 0; w < wins.size(); ++w)
-            for (int b = 0; b < B; ++b) {
-                const Call::Win& wn = wins[w];
-                if (frames[b] <= wn.f0) continue;
-                lrg[(w * 2) * B + b] = wn.f0 * M;
-                lrg[(w * 2 + 1) * B + b] = frames[b] <= wn.f1 ? c.slen[n_up][b] : wn.f1 * M;
-            }
-        HIP_OK(hipMemcpyAsync(c.s2.lvl_ranges, lrg.data(), sizeof(int) * lrg.size(), hipMemcpyHostToDevice, stream));
-        prof.fence();
-        HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
-        lsc.x = wave_dst;  // (the call's own buffer: a level that multiplies keeps the vocoder there)
-        lsc.x_stride = wave_stride;
-        lsc.y = lvl_dst;
-        lsc.y_stride = lvl_stride;
+        if (upload_ranges(c, lrg, c.s2.lvl_ranges, [](int, int64_t e) { return (int)e; })) return -1;
+        const Call::Rows x = c.rows_of(dp[STAGE_LEVEL].src), y = c.rows_of(dp[STAGE_LEVEL].dst);
+        lsc.x = x.p;  // (the call's own buffer: a level that multiplies keeps the vocoder there)
+        lsc.x_stride = x.stride;
+        lsc.y = y.p;
+        lsc.y_stride = y.stride;
         lsc.lens = c.s1.stage_lens + (size_t)n_up * B;
         lsc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);  // (the float run_level reports)
         lsc.batch = B;
@@ -1236,9 +1210,9 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         w.pre.p = c.s2.pre;
         w.pre.bs = c.S_stride;
         w.pre.cs = c.S_stride;
-        w.wv.p = wave_dst + (int64_t)wn.lo * M;  // window-local sample 0 is global sample lo * M
-        w.wv.bs = wave_stride;
-        w.wv.cs = (int)wave_stride;
+        w.wv.p = wave.p + (int64_t)wn.lo * M;  // window-local sample 0 is global sample lo * M
+        w.wv.bs = wave.stride;
+        w.wv.cs = (int)wave.stride;
         w.final_slope = c.refmode ? hp.lrelu : 0.01f;  // Q2 (vits.cpp:638)
         window_tile_maps(c, w);
         if (c.fast16 ? run_vocoder_window16(c, w) : run_vocoder_window32(c, w)) return -1;
@@ -1302,77 +1276,23 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             snapshot("waveform", w.wv, 1, w.smax[n_up], B, c.slen[n_up]);
         }
     }
-    // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
-    std::vector<int> tap_len = c.slen[n_up], tap_out_len = c.out_len;
-    int tap_max = smax[n_up], tap_out_max = c.out_max;
-    if (ed) {
-        if (run_edges(c, ed_dst, ed_stride)) return -1;
-        c.wave_dst = ed_dst;  // (what run_level measures and multiplies)
-        c.wave_stride = ed_stride;
-        rsc.lens = c.mr_lens;
-        if (o.collect_taps) {
-            // (a tap carries its rows' lengths: this debugging path reads the trimmed ones here, the call proper at its own synchronisation)
-            HIP_OK(hipStreamSynchronize(stream));
-            prof.fence();
-            const int64_t* rows = ed_host_[a1_slot_ & 1].p;
-            tap_max = tap_out_max = 0;
-            for (int b = 0; b < B; ++b) {
-                tap_len[b] = (int)rows[(size_t)4 * b + 2];
-                tap_max = std::max(tap_max, tap_len[b]);
-                if (rs) tap_out_max = std::max(tap_out_max, tap_out_len[b] = (int)c.rate_out->plan.out_len(tap_len[b]));
-            }
-            TensorRef t;
-            t.p = ed_dst;
-            t.bs = ed_stride;
-            t.cs = (int)t.bs;
-            snapshot("waveform_edges", t, 1, tap_max, B, tap_len);
-        }
-    }
-    if (c.lev) {
-        if (run_level(c, lvl_dst, lvl_stride)) return -1;
-        if (o.collect_taps) {
-            TensorRef t;
-            t.p = la ? lvl_dst : c.wave_dst;
-            t.bs = la ? lvl_stride : c.wave_stride;
-            t.cs = (int)t.bs;
-            snapshot("waveform_level", t, 1, tap_max, B, tap_len);
-        }
-    }
-    if (rs && !o.on_chunk) {
-        // nobody waits for parts of it: one launch over every utterance, behind the last window
-        rsc.max_range = c.out_max;
-        HIP_OK(resample("resample_out", rsc, c.sum_frames * M + (int64_t)B * sadd[n_up], std::accumulate(c.out_len.begin(), c.out_len.end(), (int64_t)0)));
-    }
-    if (rs && o.collect_taps) {
-        TensorRef t;
-        t.p = pcm_dst;
-        t.bs = pcm_stride;
-        t.cs = (int)pcm_stride;
-        snapshot("waveform_out", t, 1, tap_out_max, B, tap_out_len);
-    }
-    if (o.on_chunk)
-        if (int rc = deliver(wins.size() - 1)) {
-            hipStreamSynchronize(stream);
-            err = rc > 0 ? "aborted by the on_chunk callback" : "hipEventSynchronize failed";
-            return -1;
-        }
+    std::function<int()> last_chunks;
+    if (o.on_chunk) last_chunks = [&] { return deliver(wins.size() - 1); };
+    if (run_delivery_tail(c, rsc, last_chunks)) return -1;
 
     // ---- results ------------------------------------------------------------------------------------------------
     c.rx.phase("vits.results");
+    const int lv_n = c.lev ? B : 0, lm_n = dp.limits ? B : 0, ed_n = ed ? B : 0;  // the rows of the three reports this call fills
     if (pend) {
         // a pipelined batch: everything the host will hand out is known now; the PCM (if a host copy was asked for) goes to the
         // slot's pinned staging behind the kernels, and `done` marks the end of the batch on the device
         pend->B = B;
         pend->stride = (size_t)pcm_max;
-        pend->lengths.resize(B);
-        pend->frames.resize(B);
-        for (int b = 0; b < B; ++b) {
-            pend->lengths[b] = pcm_len[b];
-            pend->frames[b] = frames[b];
-        }
-        pend->lv_rows = c.lev ? B : 0;
-        pend->lm_rows = c.lim ? B : 0;
-        pend->ed_rows = ed ? B : 0;  // (lengths: the bounds until vits_model_wait reads the rows)
+        pend->lengths.assign(pcm_len.begin(), pcm_len.end());
+        pend->frames.assign(frames.begin(), frames.end());
+        pend->lv_rows = lv_n;
+        pend->lm_rows = lm_n;
+        pend->ed_rows = ed_n;  // (lengths: the bounds until vits_model_wait reads the rows)
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -1384,15 +1304,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         return 0;
     }
     if (out) {
-        out->batch = (size_t)B;
-        out->stride = (size_t)pcm_max;
-        out->lengths = new int64_t[B];
-        out->frames = new int64_t[B];
-        for (int b = 0; b < B; ++b) {
-            out->lengths[b] = pcm_len[b];
-            out->frames[b] = frames[b];
-        }
-        out->data = nullptr;
+        fill_result(out, B, (size_t)pcm_max, pcm_len.begin(), frames.begin());
         if (!o.skip_host_copy) {
             out->data = new float[(size_t)B * out->stride];
             if (o.on_chunk) std::memcpy(out->data, host_pcm, sizeof(float) * (size_t)B * out->stride);  // already streamed to the host
@@ -1401,28 +1313,16 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
             prof.fence();
         }
     }
-    last_lv_ = c.lev ? lv_host_[a1_slot_ & 1].p : nullptr;
-    last_lv_rows_ = c.lev ? B : 0;
-    last_lm_ = c.lim ? lm_host_[a1_slot_ & 1].p : nullptr;
-    last_lm_rows_ = c.lim ? B : 0;
     async_tail_ = want_async;
-    if (!want_async) {
+    if (want_async) {
+        // (the rows are on their way to the slot's pinned copy: the reports are valid after sync())
+        lv_.expect(a1_slot_, lv_n), lm_.expect(a1_slot_, lm_n), ed_.expect(a1_slot_, ed_n);
+    } else {
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
-        if (c.lev) {  // (the rows have landed: keep them apart from the pinned copy, which a later submit into this slot overwrites)
-            last_lv_store_.assign(last_lv_, last_lv_ + (size_t)4 * B);
-            last_lv_ = last_lv_store_.data();
-        }
-        if (c.lim) {
-            last_lm_store_.assign(last_lm_, last_lm_ + (size_t)4 * B);
-            last_lm_ = last_lm_store_.data();
-        }
-        if (ed) {
-            // the trimmed lengths have landed with the rows: what the call reports
-            const int64_t* rows = ed_host_[a1_slot_ & 1].p;
-            if (out) edges_lengths(rows, B, out->lengths);
-            keep_edges(rows, B);
-        }
+        // the rows have landed: kept apart from the pinned copies, which a later submit into this slot overwrites; the trimmed lengths are what the call reports
+        if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
+        lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
         if (prof.on && prof.recs.size() > 50000) prof.collect();

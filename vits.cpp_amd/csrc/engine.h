@@ -4,7 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <memory>
@@ -14,6 +16,7 @@
 #include <vector>
 
 #include "../../include/vits.h"
+#include "delivery_plan.h"
 #include "kernels.h"
 #include "model_file.h"
 
@@ -108,6 +111,73 @@ struct PinnedBuf {
     ~PinnedBuf() {
         if (p) hipHostFree(p);
     }
+};
+
+// The report rows of one delivery stage (levels and limits: float, edges: int64), one life cycle for all three: the device rows [cap][4] of the call being
+// queued (grow-only; stream-ordered, so one buffer serves both pipeline slots) with `tail_bytes` more bytes per row behind them (the edges' trimmed lengths,
+// int32 [cap]), their pinned host copy per pipeline slot, and the rows of the most recently completed call on the host (copied out of the pinned slot once
+// they have landed: a later submit into that slot overwrites it).
+template <class T>
+class ReportRows {
+  public:
+    explicit ReportRows(size_t tail_bytes = 0) : per_row_(sizeof(T) * 4 + tail_bytes) {}
+    T* dev() const { return dev_; }
+    void* tail() const { return dev_ + (size_t)4 * cap_; }
+    // room for B rows on the device. A fresh buffer takes the old one's place in `owned` and is counted in `weight_bytes` (the old rows are the previous
+    // call's, already on their way to the host in stream order: hipFree waits for them)
+    hipError_t grow(int B, std::vector<void*>& owned, int64_t& weight_bytes) {
+        if (B <= cap_) return hipSuccess;
+        const int cap = std::max(B, 64);
+        T* fresh = nullptr;
+        if (hipError_t e = hipMalloc((void**)&fresh, per_row_ * (size_t)cap)) return e;
+        if (dev_) {
+            for (void*& p : owned)
+                if (p == dev_) p = fresh;
+            hipFree(dev_);
+        } else owned.push_back(fresh);
+        weight_bytes += (int64_t)per_row_ * (cap - cap_);
+        dev_ = fresh, cap_ = cap;
+        return hipSuccess;
+    }
+    // the B device rows of the call being queued, on their way to the slot's pinned copy
+    hipError_t queue_copy(int slot, int B, hipStream_t stream) {
+        PinnedBuf<T>& host = host_[slot & 1];
+        if (hipError_t e = host.ensure((size_t)4 * B, (size_t)4 * std::max(B, 64) + 64)) return e;
+        return hipMemcpyAsync(host.p, dev_, sizeof(T) * 4 * (size_t)B, hipMemcpyDeviceToHost, stream);
+    }
+    const T* slot_rows(int slot) const { return host_[slot & 1].p; }
+    // the first n rows of the slot's pinned copy have landed: they are the last call's rows (append: they follow the ones already kept)
+    void landed(int slot, int n, bool append = false) {
+        if (!append) store_.clear();
+        const T* rows = host_[slot & 1].p;
+        if (n > 0) store_.insert(store_.end(), rows, rows + (size_t)4 * n);
+        rows_ = (int)(store_.size() / 4);
+        unlanded_ = -1;
+    }
+    // a call that returned with its device work queued: n rows, valid once settle() has run behind a synchronisation
+    void expect(int slot, int n) {
+        store_.assign((size_t)4 * n, T());
+        rows_ = n;
+        unlanded_ = n > 0 ? slot : -1;
+    }
+    void settle() {
+        if (unlanded_ >= 0) landed(unlanded_, rows_);
+    }
+    void clear() { rows_ = 0, unlanded_ = -1; }
+    // the rows [rows][4] of the most recently completed call (0 rows: it ran without the stage)
+    const T* read(int& rows) const {
+        rows = rows_;
+        return store_.data();
+    }
+
+  private:
+    size_t per_row_;
+    T* dev_ = nullptr;
+    int cap_ = 0;
+    PinnedBuf<T> host_[2];
+    std::vector<T> store_;
+    int rows_ = 0;
+    int unlanded_ = -1;  // the slot whose pinned copy an async call's rows are still on their way to
 };
 
 struct Tap {
@@ -290,30 +360,21 @@ class Engine {
     float level_value_db() const { return level_value_; }
     float level_ceiling_db() const { return level_ceiling_; }
     // the rows [B][4] of the most recently completed call (empty: it ran without a level). After an async call they are valid after sync().
-    const float* last_levels(int& rows) const {
-        rows = last_lv_rows_;
-        return last_lv_;
-    }
+    const float* last_levels(int& rows) const { return lv_.read(rows); }
     // the loudness target under a ceiling (include/vits.h vits_model_set_limiter; limiter.hip): with a mode set, the levelling kinds that multiply deliver
     // through the true-peak meter and the limiter. 0, or -1 + a message with the handle unchanged (an unknown mode, a model rate above 48000 Hz). Nothing
     // touches the device here: the 4x table and the row buffer are allocated by the first call that limits.
     int set_limiter(int mode, std::string& err);
     int limiter_mode() const { return limit_mode_; }
     // the rows [B][4] = {TP(x), TP(y), min s, share} of the most recently completed call (empty: it ran without the limiter)
-    const float* last_limits(int& rows) const {
-        rows = last_lm_rows_;
-        return last_lm_;
-    }
+    const float* last_limits(int& rows) const { return lm_.read(rows); }
     // stated edges (include/vits.h vits_model_set_edges; edges.hip): with a mode set, what the vocoder made is trimmed, faded and padded in front of
     // levelling. NULL or VITS_EDGES_OFF switches the stage off. 0, or -1 + a message with the handle unchanged (what edges_plan refuses). Nothing touches
     // the device here: the fade tables and the row buffer are allocated by the first call that runs the stage.
     int set_edges(const vits_edges_desc* d, std::string& err);
     const vits_edges_desc& edges_desc() const { return edges_desc_; }
     // the rows [B][4] = {a, b, N', n_active} of the most recently completed call (empty: it ran with the stage off)
-    const int64_t* last_edges(int& rows) const {
-        rows = last_ed_rows_;
-        return last_ed_store_.data();
-    }
+    const int64_t* last_edges(int& rows) const { return ed_.read(rows); }
     // EMULATED ggml fp16 lookup tables for ggml_gelu / ggml_soft_max (Q8; inferred from upstream ggml, the fork is absent): builds the two
     // tables on the host as ggml_init does and uploads them on first use
     // mode 1: stage one additionally runs in the exact order of include/vits_exact_math.h (exact_stage1.hip), shared with the oracle: durations are
@@ -431,9 +492,9 @@ class Engine {
         PinnedBuf<int> win_pinned;    // vocoder-window length table of a windowed batch (host side of its H2D copy)
         PinnedBuf<TileEntry> map_pinned;  // lists of existing tiles of a ragged batch (host side of their H2D copy)
         PinnedBuf<float> dur_pinned;  // opts.durations_out: the batch's durations, copied beside the frame counts
-        int lv_rows = 0;              // levelling: rows of lv_host_[slot] this batch fills (0: no level was set)
-        int lm_rows = 0;              // the limiter: rows of lm_host_[slot] this batch fills (0: it was off)
-        int ed_rows = 0;              // stated edges: rows of ed_host_[slot] this batch fills (0: off); `lengths` is derived from them once `done` has passed
+        int lv_rows = 0;              // levelling: rows of the slot's pinned copy this batch fills (0: no level was set)
+        int lm_rows = 0;              // the limiter: likewise (0: it was off)
+        int ed_rows = 0;              // stated edges: likewise (0: off); `lengths` is derived from them once `done` has passed
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -501,52 +562,45 @@ class Engine {
     int input_rate_ = 0, output_rate_ = 0;
     std::map<std::pair<int, int>, RateTable> rate_tabs_;  // keyed by (fi, fo); device tables are owned_ and counted in weight_bytes
     const RateTable* rate_table(int fi, int fo, std::string& err);  // null + message: the pair is refused, or the upload failed
-    // levelling: the handle's setting, the plan at the model's rate, the device rows [lv_cap_][4] of the call being queued (stream-ordered: one buffer
-    // serves both pipeline slots; owned_ and counted in weight_bytes) and their pinned host copies, one per pipeline slot
+    // The delivery chain behind the vocoder (delivery_plan.h): what this handle and the call's options ask for -> the call's plan. 0, or -1 + the message of
+    // the combination the plan refuses (on_chunk with a level that needs the whole utterance, with the limiter, with edges; async with edges). Called before
+    // stage one is queued by every entry point that can be refused, and by run_stage_two, which keeps the plan in the call.
+    int plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err) const;
+    // the report rows of the three stages (ReportRows: device rows owned_ and counted in weight_bytes); the edges' carry the trimmed lengths int32 [cap] behind them
+    ReportRows<float> lv_, lm_;
+    ReportRows<int64_t> ed_{sizeof(int)};
+    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(); }
+    // levelling: the handle's setting and the plan at the model's rate
     int level_kind_ = VITS_LEVEL_NONE;
     float level_value_ = 0.f, level_ceiling_ = 0.f;
     LoudnessPlan level_plan_;
-    float* lv_rows_ = nullptr;
-    int lv_cap_ = 0;
-    PinnedBuf<float> lv_host_[2];
-    const float* last_lv_ = nullptr;
-    int last_lv_rows_ = 0;
-    std::vector<float> last_lv_store_;  // the rows of a waited-for batch (its slot's pinned copy is reused by the next submit)
-    int check_level(const vits_process_opts& o, std::string& err) const;  // the refusal of on_chunk with a kind that needs the whole utterance
-    // measures c.s2.wave and multiplies it into dst (engine.cpp); queued behind the last vocoder window
-    int run_level(Call& c, float* dst, int64_t dst_stride);
-    // the limiter: the handle's mode, the plan at the model's rate, and the limits rows, kept exactly as the levels rows are
+    // measures the level stage's source and multiplies (or limits) it into the stage's destination, as the call's plan routes them (engine.cpp); queued behind
+    // the last vocoder window
+    int run_level(Call& c);
+    // the limiter: the handle's mode and the plan at the model's rate
     int limit_mode_ = VITS_LIMIT_OFF;
     LimiterPlan limit_plan_;
-    float* lm_rows_ = nullptr;
-    int lm_cap_ = 0;
-    PinnedBuf<float> lm_host_[2];
-    const float* last_lm_ = nullptr;
-    int last_lm_rows_ = 0;
-    std::vector<float> last_lm_store_;
-    // a device row buffer [cap][4] of the handle grown to at least B rows (owned_, counted in weight_bytes)
-    int grow_rows(float*& rows, int& cap, int B, std::string& err);
     // stated edges: the handle's desc (VITS_EDGES_OFF and zeros when off), its plan at the model's rate, the fade tables on the device (uploaded by the first
-    // call that needs them, and again after a set_edges that changed them), the device rows: int64 [ed_cap_][4], then the trimmed lengths int32 [ed_cap_]
-    // (owned_, counted in weight_bytes), and the rows' pinned copies, one per pipeline slot
+    // call that needs them, and again after a set_edges that changed them)
     vits_edges_desc edges_desc_{(uint32_t)sizeof(vits_edges_desc), VITS_EDGES_OFF, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     EdgesPlan edges_plan_;
     float* ed_fades_ = nullptr;
     size_t ed_fades_n_ = 0;
     bool ed_fades_stale_ = false;
-    int64_t* ed_rows_ = nullptr;
-    int ed_cap_ = 0;
-    PinnedBuf<int64_t> ed_host_[2];
-    int last_ed_rows_ = 0;
-    std::vector<int64_t> last_ed_store_;
     bool edges_on() const { return edges_desc_.mode != VITS_EDGES_OFF; }
-    int check_edges(const vits_process_opts& o, std::string& err) const;  // the refusals of on_chunk and async with the stage on
-    // the stage on c.s2.wave into dst (engine.cpp): queued behind the last vocoder window, in front of run_level; c.mr_lens / c.mr_max are its output's from here on
-    int run_edges(Call& c, float* dst, int64_t dst_stride);
+    // the stage from its source into its destination, as the call's plan routes them (engine.cpp): queued behind the last vocoder window, in front of run_level
+    int run_edges(Call& c);
     // what a call delivers per utterance once its rows [B][4] have landed: N', or its length at the output rate
     void edges_lengths(const int64_t* rows, int B, int64_t* lengths) const;
-    // the rows of a finished call -> last_ed_store_ (appended when `append`)
-    void keep_edges(const int64_t* rows, int B, bool append = false);
+    // the rows of a batch that has completed in pipeline slot `slot` -> the three reports (append: a second part of the same call); the batch's lengths become
+    // its trimmed ones when the edges stage ran
+    void batch_landed(Pending& p, int slot, bool append = false);
+    // everything behind the last vocoder window (engine.cpp): edges, level or limiter, the resampler (rsc: its call, set up by run_stage_two), their taps, and
+    // the chunks of the last window of a streaming call (last_chunks: null without a sink; > 0 the sink aborted, < 0 the wait failed)
+    int run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<int()>& last_chunks);
+    // a streaming call's table [window][2][B] on the host and on the device (dev): the samples [j0, j1) of every utterance that each window makes final, in the
+    // unit of `final_of(b, e)`: what is final of utterance b once its model-rate samples [0, e) are
+    int upload_ranges(Call& c, std::vector<int>& table, int* dev, const std::function<int(int, int64_t)>& final_of);
     // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
     hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 

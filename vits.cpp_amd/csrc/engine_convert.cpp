@@ -255,11 +255,9 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
                                     (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
             if (check_speaker(s, who, err)) return -1;
         }
-    if (check_level(o, err)) return -1;
-    if (check_edges(o, err)) return -1;
-    last_lv_rows_ = 0;
-    last_lm_rows_ = 0;
-    last_ed_rows_ = 0;
+    DeliveryPlan refusable;  // (the refusals of the delivery chain, before anything is queued)
+    if (plan_delivery(o, refusable, err)) return -1;
+    clear_reports();
     if (prepare_conversion(err)) return -1;
     int64_t nmax = 0;
     std::vector<int64_t> n_model;

@@ -235,20 +235,41 @@ struct Call {
     std::vector<int> sts;  // [stage] time stride of that stage's buffers
     bool fast16 = false, fuse16 = false;
     const int* d_len_full[8] = {};
-    float* wave_dst = nullptr;
-    int64_t wave_stride = 0;
+    // The delivery chain behind the vocoder (delivery_plan.h), planned once per call (Engine::plan_delivery): who runs, and which buffer each stage reads and
+    // writes. layout_stage_two allocates what the plan needs; rows_of is the ONE place where a buffer id of the plan becomes this call's pointer and row stride.
+    DeliveryPlan dp;
+    struct Rows {
+        float* p = nullptr;
+        int64_t stride = 0;
+    };
+    Rows rows_of(const DeliveryRoute& r) const {
+        Rows out;
+        switch (r.buf) {
+            case BUF_WAVE: out.p = s2.wave; break;
+            case BUF_EDGE: out.p = s2.wave_edge; break;
+            case BUF_LVL: out.p = s2.wave_lvl; break;
+            case BUF_OUT: out.p = s2.wave_out; break;
+            case BUF_CALLER: out.p = (float*)o.out_device; break;
+            default: break;
+        }
+        switch (r.stride) {
+            case STRIDE_S: out.stride = S_stride; break;
+            case STRIDE_E: out.stride = E_stride; break;
+            case STRIDE_OUT_WS: out.stride = out_ws; break;
+            case STRIDE_CALLER: out.stride = o.out_device_stride; break;
+            default: break;
+        }
+        return out;
+    }
     // output rate set (Engine::output_rate): the filter, every utterance's delivered length ceil(N L / M), the longest, and the row stride of s2.wave_out
     const RateTable* rate_out = nullptr;
     std::vector<int> out_len;
     int out_max = 0, out_ws = 0;
-    // a level set (Engine::level_kind): the kind of this call, and whether it multiplies (every kind but VITS_LEVEL_MEASURE)
+    // a level set (Engine::level_kind): the kind of this call (dp.multiplies: every kind but VITS_LEVEL_MEASURE; dp.limits: through the limiter)
     int lev = 0;
-    bool lev_apply = false;
-    bool lim = false;  // the limiter is on and the kind multiplies: limiter.hip delivers in place of the plain multiply
     // stated edges (Engine::set_edges): the stage runs between the vocoder and levelling. What levelling, the limiter and the resampler read is then its output:
     // E_stride = the row stride of the model-rate buffers behind the vocoder's own (S_stride with the stage off), mr_lens = the device lengths [B] of those rows
     // (the stage's N'; the vocoder's sample counts with it off), mr_len / mr_max = what the host knows of them (under the stage: the bounds N + Pl + Pt)
-    bool ed = false;
     int E_stride = 0;
     const int* mr_lens = nullptr;
     std::vector<int> mr_len;
