@@ -564,8 +564,8 @@ VITS_API int vits_edges_host(const float* pcm, size_t n, int32_t rate, const vit
 /* ---- joined tracks: the utterances of a batch laid end to end, on the device ------------------------------------------------------------
  * The stages above state rate, level, ceiling and edges of ONE utterance; a paragraph is several, laid end to end with a stated gap or overlap.
  * This section states that layout and gives it as a device operator (vits_op_join, on model-rate rows: the rows a call delivers with no level
- * and no output rate set) with its host-only plan and sequential definition. A model-level call that joins inside the engine, in front of the
- * handle's level, limiter and resampler, is not part of the library yet.
+ * and no output rate set) with its host-only plan and sequential definition, and as a model-level call that joins inside the engine, in front
+ * of the handle's level, limiter and resampler (vits_model_process_joined below; vits_model_speak takes a whole text).
  *
  * The definition. Model-rate rows x_b[0, n_b), b = 0 .. B - 1, at rate fs: n_b is the utterance's delivered length, N'_b as the edges stage
  * leaves it, or the vocoder's sample count with the stage off. Integer divisions truncate.
@@ -614,6 +614,52 @@ VITS_API int vits_join_host(int32_t rate, int32_t batch, const float* x, int64_t
  * NULL), so a call with cap = 0 sizes the arrays. -1 + message: text NULL.
  * The kinds are what a caller picks the gap in front of the next sentence by (vits_join_plan: gap_ms). */
 VITS_API int64_t vits_split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_t* kinds, size_t cap);
+
+/* ---- a batch joined inside the call; a whole text spoken ----------------------------------------------------------------------------------------
+ * vits_model_process_joined is vits_model_process_batch with the join of the section above inside it: the batch runs per utterance up to and
+ * including the edges stage (vits_model_set_edges; off: the vocoder's rows), the utterances are laid into the tracks of (track, gap_ms) —
+ * exactly vits_join_plan's arguments at the model's rate: NULL = one track, gaps of 0 — with n_b the utterance's delivered length at that
+ * point and bound(n_b) what the host knows of it, and the handle's level or limiter and its resampler then run on the G TRACKS: a level is
+ * measured over the programme, not over each sentence. The result has out->batch = G rows: lengths[g] = T_g (at the output rate if one is set),
+ * frames[g] = the sum of the frames of the track's utterances, data [G][stride]; out_device is [G][out_device_stride] and must hold the largest
+ * track's bound at the delivered rate (a frames_only call returns exactly those bounds as lengths[g], and the summed frames; a full call stays
+ * within them). With the join as the last stage, [T_g, bound_g) of a row is +0 and nothing is written behind bound_g.
+ * Reports: vits_model_last_edges keeps its B rows; vits_model_last_levels and vits_model_last_limits have G rows, one per track;
+ * vits_model_last_joins writes int64 [B][4] = {index, track, o_b, n_b} of the most recently completed joined call (0 rows after any other
+ * call), o_b and n_b in samples at the MODEL's rate, index = b (under vits_model_speak: the span's index). With an output rate set, the
+ * position of utterance b in its delivered track is vits_resample_length(model rate, output rate, o_b) samples: the same integer rule that
+ * gives lengths[g] from T_g. Returns the number of rows, -1: model NULL.
+ * Synchronous, and simple on purpose: it never splits the batch across the front-end stream and has no submit form. Taken: the host copy,
+ * out_device, skip_host_copy, vocoder_chunk_frames (without on_chunk), fixed_duration, durations_out, every prosody and speaker field, every
+ * arithmetic mode, frames_only. Refused with a message under the prefix "vits_model_process_joined:": on_chunk, async, collect_taps (the taps
+ * in front of the join are per utterance, those behind it per track), a noise kind other than VITS_NOISE_COUNTER or VITS_NOISE_EXPLICIT,
+ * everything vits_join_plan refuses, an out_device_stride below a track's bound (naming the track and the samples it needs); and "batches in
+ * flight". What the host can decide from the arguments is refused before anything is queued: with fixed_duration > 0 that is every bound; with
+ * predicted durations the bounds are checked directly behind the read of the frame counts, before the flow and the vocoder are queued. A call
+ * that fails later (an allocation) returns with the device idle.
+ *
+ * vits_model_speak: vits_split_sentences cuts `text`, every span is tokenised with the model's tokenizer, and the spans that have ids form ONE
+ * batch of one joined call with noise VITS_NOISE_COUNTER. The gap in front of a span is sentence_gap_ms, or paragraph_gap_ms where the span in
+ * front of it ended a paragraph (both in vits_join_plan's range); track_per_paragraph = 1 gives each paragraph its own track, 0 one track. A
+ * span that tokenises to no ids (no symbol the tokenizer knows: the lone blank of an add_blank model counts as none) is dropped, and if it
+ * ended its paragraph the span in front of it does. `index` of vits_model_last_joins is the
+ * span's index in vits_split_sentences order, so the caller keeps the byte ranges. opts NULL: gaps of 0, one track. opts->process (optional)
+ * carries what vits_model_process_joined takes of vits_process_opts — speaker through the handle's default or voices, the model-level
+ * prosody, noise_seed, mode, out_device, skip_host_copy, frames_only ... — except the per-utterance arrays, whose length a caller cannot know
+ * before the text is cut: speaker_ids, speaking_rates, noise_scales, noise_scale_durations, duration_override, durations_out,
+ * noise_seed_offsets and noise_prior are refused, as is a noise_kind other than VITS_NOISE_COUNTER. Also refused: a NULL or empty text, a text
+ * without a speakable span, a span above 2048 ids (naming it), a phonetic model and an add_blank = 0 file as the other text entry points
+ * refuse them. */
+typedef struct vits_speak_opts {
+    uint32_t struct_size;
+    float sentence_gap_ms, paragraph_gap_ms; /* the gap in front of a sentence / in front of the first sentence of a paragraph; vits_join_plan's range */
+    int32_t track_per_paragraph;             /* 0: one track; 1: each paragraph its own track */
+    const vits_process_opts* process;        /* optional: speaker, prosody (model-level values), noise_seed, arithmetic mode, out_device ... */
+} vits_speak_opts;
+VITS_API int vits_model_process_joined(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch, int32_t id_stride,
+                                       const vits_process_opts* opts, const int32_t* track, const float* gap_ms, vits_batch_result* out);
+VITS_API int64_t vits_model_last_joins(vits_model* model, int64_t* dst, size_t cap);
+VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_speak_opts* opts, vits_batch_result* out);
 
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);

@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_set_edges", "vits_model_get_edges", "vits_model_last_edges", "vits_edges_plan", "vits_edges_host", "vits_op_edges",
-    "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences",
+    "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences", "vits_model_process_joined", "vits_model_last_joins", "vits_model_speak",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
     "vits_op_dds_block", "vits_op_dds_block_plan", "vits_op_spline", "vits_op_durations",
@@ -122,6 +122,12 @@ class ProcessOpts(C.Structure):
 class BatchResult(C.Structure):
     _fields_ = [("data", C.POINTER(C.c_float)), ("stride", C.c_size_t), ("lengths", C.POINTER(C.c_int64)),
                 ("frames", C.POINTER(C.c_int64)), ("batch", C.c_size_t)]
+
+
+class SpeakOpts(C.Structure):
+    """vits_speak_opts"""
+    _fields_ = [("struct_size", C.c_uint32), ("sentence_gap_ms", C.c_float), ("paragraph_gap_ms", C.c_float), ("track_per_paragraph", C.c_int32),
+                ("process", C.POINTER(ProcessOpts))]
 
 
 class Conv1dDesc(C.Structure):
@@ -396,6 +402,12 @@ def lib():
     L.vits_op_join.argtypes = [i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]
     L.vits_split_sentences.restype = i64
     L.vits_split_sentences.argtypes = [C.c_char_p, vp, vp, vp, sz]
+    L.vits_model_process_joined.restype = i32
+    L.vits_model_process_joined.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts), vp, vp, C.POINTER(BatchResult)]
+    L.vits_model_last_joins.restype = i64
+    L.vits_model_last_joins.argtypes = [vp, vp, sz]
+    L.vits_model_speak.restype = i32
+    L.vits_model_speak.argtypes = [vp, C.c_char_p, C.POINTER(SpeakOpts), C.POINTER(BatchResult)]
     L.vits_model_submit_batch.restype = i32
     L.vits_model_submit_batch.argtypes = [vp, vp, vp, i32, i32, C.POINTER(ProcessOpts)]
     L.vits_model_wait.restype = i32
@@ -1026,6 +1038,70 @@ class Model:
                 raise cb_error[0]
             raise VitsError(last_error())
         return _take_result(res, B, keep_pcm)
+
+    @staticmethod
+    def _joined_opts(B, stride, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False,
+                     out_device=None, out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False,
+                     noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None,
+                     durations_out=None):
+        """the options of process_batch's keywords (what a joined call refuses travels too, so that the library says why) -> (opts, keep, cb_error)"""
+        o, keep = _opts(B, mode, noise_kind, noise_seed, noise_dur, noise_prior, fixed_duration, collect_taps, out_device, out_device_stride, skip_host_copy,
+                        async_, vocoder_chunk_frames, frames_only, noise_seed_offsets, speaker_ids)
+        keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
+        return o, keep, _chunk_sink(o, on_chunk)
+
+    def process_joined(self, ids, id_lengths=None, track=None, gap_ms=None, keep_pcm=True, **kw):
+        """vits_model_process_joined: process_batch with the utterances laid end to end into tracks inside the call, in front of the handle's level, limiter and
+        resampler. track: int32 [B] (None: one track), gap_ms: float32 [B] (None: 0), as join_plan takes them; the other keywords are process_batch's.
+        Returns (list of per-TRACK PCM arrays or None, lengths [G], frames [G]); last_joins() reads where every utterance lies."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        B, stride = ids.shape
+        lens = np.full(B, stride, np.int32) if id_lengths is None else np.ascontiguousarray(id_lengths, dtype=np.int32)
+        tr = None if track is None else np.ascontiguousarray(track, dtype=np.int32).ravel()
+        gp = None if gap_ms is None else np.ascontiguousarray(gap_ms, dtype=np.float32).ravel()
+        for name, v in (("track", tr), ("gap_ms", gp)):
+            if v is not None and v.size != B:
+                raise ValueError("%s needs one entry per utterance" % name)
+        o, keep, cb_error = self._joined_opts(B, stride, **kw)
+        res = BatchResult()
+        if lib().vits_model_process_joined(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), _ptr(tr), _ptr(gp), C.byref(res)) != 0:
+            if cb_error:
+                raise cb_error[0]
+            raise VitsError(last_error())
+        return _take_result(res, int(res.batch), keep_pcm)
+
+    def speak(self, text, sentence_gap_ms=0.0, paragraph_gap_ms=0.0, track_per_paragraph=False, keep_pcm=True, **kw):
+        """vits_model_speak: a whole text -> one programme. split_sentences cuts it, the model's tokenizer turns every span into ids, and the spans that have
+        some run as one process_joined call: sentence_gap_ms in front of a sentence, paragraph_gap_ms in front of the first sentence of a paragraph, every
+        paragraph its own track if track_per_paragraph. The other keywords are process_batch's (the per-utterance arrays are refused). Returns (list of
+        per-track PCM arrays or None, lengths, frames); last_joins()[:, 0] are the span indices of split_sentences(text)."""
+        so = SpeakOpts()
+        so.struct_size = C.sizeof(SpeakOpts)
+        so.sentence_gap_ms, so.paragraph_gap_ms, so.track_per_paragraph = float(sentence_gap_ms), float(paragraph_gap_ms), int(bool(track_per_paragraph))
+        o, keep, cb_error = self._joined_opts(max(1, np.size(kw.get("speaker_ids", 0))), 1, **kw)
+        so.process = C.pointer(o)
+        res = BatchResult()
+        raw = None if text is None else text.encode("utf-8")
+        if lib().vits_model_speak(self._h, raw, C.byref(so), C.byref(res)) != 0:
+            if cb_error:
+                raise cb_error[0]
+            raise VitsError(last_error())
+        return _take_result(res, int(res.batch), keep_pcm)
+
+    def last_joins(self):
+        """vits_model_last_joins: int64 [B, 4] = (index, track, o_b, n_b) of the most recently completed joined call (o_b, n_b at the model's rate; with an
+        output rate set, resample_length(o_b) is the position in the delivered track), or None when the last call did not join"""
+        n = lib().vits_model_last_joins(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n // 4, 4), np.int64)
+        if lib().vits_model_last_joins(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
 
     def prepare_conversion(self):
         """vits_model_prepare_conversion: build the posterior encoder and the forward-flow weights now (the first conversion does it otherwise)"""

@@ -798,6 +798,71 @@ VITS_API int64_t vits_split_sentences(const char* text, int64_t* starts, int64_t
     VITS_CATCH(-1)
 }
 
+// ---- a batch joined inside the call; a whole text spoken (include/vits.h) ------------------------------------------------------------------------------
+VITS_API int vits_model_process_joined(vits_model* model, const int32_t* ids, const int32_t* id_lengths, int32_t batch, int32_t id_stride,
+                                       const vits_process_opts* opts, const int32_t* track, const float* gap_ms, vits_batch_result* out) {
+    VITS_TRY
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!model || !ids) {
+        set_err("vits_model_process_joined: null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    const vits_process_opts o = default_opts(opts, VITS_NOISE_COUNTER);
+    return run_engine(out, [&](std::string& err) { return model->eng.process_joined(ids, id_lengths, batch, id_stride, o, track, gap_ms, nullptr, out, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_model_last_joins(vits_model* model, int64_t* dst, size_t cap) {
+    return last_rows(model, dst, cap, [](const vits::Engine& e, int& rows) { return e.last_joins(rows); });
+}
+
+VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_speak_opts* opts, vits_batch_result* out) {
+    VITS_TRY
+    const std::string who = "vits_model_speak: ";
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!model) return fail(who + "null argument (model)");
+    vits_speak_opts so;
+    std::memset(&so, 0, sizeof(so));
+    so.struct_size = sizeof(so);
+    if (opts) std::memcpy(&so, opts, std::min<size_t>(sizeof(so), opts->struct_size ? opts->struct_size : sizeof(so)));
+    const vits_process_opts o = default_opts(so.process, VITS_NOISE_COUNTER);
+    // (the per-utterance arrays are as long as the batch, which the caller does not know before the text is cut)
+    const std::pair<const char*, bool> arrays[] = {{"speaker_ids", o.speaker_ids != nullptr},
+                                                   {"speaking_rates", o.speaking_rates != nullptr},
+                                                   {"noise_scales", o.noise_scales != nullptr},
+                                                   {"noise_scale_durations", o.noise_scale_durations != nullptr},
+                                                   {"duration_override", o.duration_override != nullptr},
+                                                   {"durations_out", o.durations_out != nullptr},
+                                                   {"noise_seed_offsets", o.noise_seed_offsets != nullptr},
+                                                   {"noise_dur", o.noise_dur != nullptr},
+                                                   {"noise_prior", o.noise_prior != nullptr}};
+    for (const auto& [name, set] : arrays)
+        if (set)
+            return fail(who + "process->" + name + " is a per-utterance array, and the text decides how many utterances there are: use the model-level settings, or "
+                              "vits_split_sentences and vits_model_process_joined");
+    if (o.noise_kind != VITS_NOISE_COUNTER) return fail(who + "process->noise_kind must be VITS_NOISE_COUNTER");
+    const vits::Tokenizer& tok = model->eng.tok;
+    struct Ctx {
+        const vits::Tokenizer& tok;
+    } ctx{tok};
+    const vits::SpeakTokenize tokenize = [](void* user, const std::string& span, std::vector<int32_t>& ids, std::string& err) {
+        const vits::Tokenizer& t = static_cast<Ctx*>(user)->tok;
+        if (!t.tokenize_checked(span, ids, err)) return false;  // (a phonetic model: refused with the text entry points' message)
+        if (t.add_blank && ids.size() == 1) ids.clear();        // (the lone blank of a span without a known symbol: nothing to say)
+        return true;
+    };
+    if (text && *text && !tok.phonetic && !tok.add_blank)  // Q11, as vits_model_process: the reference's tokenizer returns no ids at all without add_blank
+        return fail(who + "empty input: the model file says add_blank = 0, for which the reference tokenizer returns no ids (vits_tokenizer.cpp:200-208); pass ids");
+    vits::SpeakPlan p;
+    std::string err;
+    if (!vits::speak_plan(text, so.sentence_gap_ms, so.paragraph_gap_ms, so.track_per_paragraph != 0, tokenize, &ctx, p, err)) return fail(who + err);
+    VITS_ENTER(model, -1)
+    return run_engine(out, [&](std::string& e) {
+        return model->eng.process_joined(p.ids.data(), p.id_lens.data(), p.batch, p.id_stride, o, p.track.data(), p.gap_ms.data(), p.index.data(), out, e);
+    });
+    VITS_CATCH(-1)
+}
+
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }

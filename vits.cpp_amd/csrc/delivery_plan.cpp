@@ -6,8 +6,10 @@ namespace vits {
 DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     DeliveryPlan p;
     const bool multiplies = a.level >= DLEVEL_GAIN;
-    // the refusals, in the order the engine has always checked them (level before edges, the limiter's first)
-    if (a.on_chunk && a.limiter && multiplies) p.refusal = REFUSE_LIMIT_STREAM;
+    // the refusals, in the order the engine has always checked them (level before edges, the limiter's first); a joined ask is refused for what it is first
+    if (a.joined && a.on_chunk) p.refusal = REFUSE_JOIN_STREAM;
+    else if (a.joined && a.async) p.refusal = REFUSE_JOIN_ASYNC;
+    else if (a.on_chunk && a.limiter && multiplies) p.refusal = REFUSE_LIMIT_STREAM;
     else if (a.on_chunk && (a.level == DLEVEL_MEASURE || a.level == DLEVEL_WHOLE)) p.refusal = REFUSE_LEVEL_STREAM;
     else if (a.edges && a.on_chunk) p.refusal = REFUSE_EDGES_STREAM;
     else if (a.edges && a.async) p.refusal = REFUSE_EDGES_ASYNC;
@@ -16,17 +18,20 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     p.multiplies = multiplies;
     p.limits = multiplies && a.limiter;
     // The stages that write, in their order, each into its own arena buffer — except the last one, which writes straight to the caller's buffer when the
-    // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the vocoder's stride.
-    const bool writes[STAGE_COUNT] = {true, a.edges, multiplies, a.rate};
-    const int own[STAGE_COUNT] = {BUF_WAVE, BUF_EDGE, BUF_LVL, BUF_OUT};
-    const int own_stride[STAGE_COUNT] = {STRIDE_S, STRIDE_E, a.edges ? STRIDE_E : STRIDE_S, STRIDE_OUT_WS};
-    int last = STAGE_VOCODER;
-    for (int s = 0; s < STAGE_COUNT; ++s)
+    // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the vocoder's stride. Behind a join they are
+    // the tracks', J_stride apart.
+    constexpr int kSlots = STAGE_COUNT + 1;  // vocoder, edges, join, level, resample
+    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
+    const bool writes[kSlots] = {true, a.edges, a.joined, multiplies, a.rate};
+    const int own[kSlots] = {BUF_WAVE, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
+    const int own_stride[kSlots] = {STRIDE_S, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : STRIDE_S), STRIDE_OUT_WS};
+    int last = 0;
+    for (int s = 0; s < kSlots; ++s)
         if (writes[s]) last = s;
     DeliveryRoute cur;  // what the next stage reads
-    for (int s = 0; s < STAGE_COUNT; ++s) {
-        DeliveryPlan::Stage& st = p.stage[s];
-        if (s == STAGE_LEVEL && a.level == DLEVEL_MEASURE) {
+    for (int s = 0; s < kSlots; ++s) {
+        DeliveryPlan::Stage& st = *slot[s];
+        if (slot[s] == &p.stage[STAGE_LEVEL] && a.level == DLEVEL_MEASURE) {
             // measured where it lies (out_device included): the chain passes by
             st.runs = true;
             st.src = st.after = cur;
@@ -41,17 +46,19 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     }
     p.delivered = cur;
 
-    for (const DeliveryPlan::Stage& st : p.stage)
-        for (const int buf : {st.src.buf, st.dst.buf}) {
+    for (const DeliveryPlan::Stage* st : slot)
+        for (const int buf : {st->src.buf, st->dst.buf}) {
             if (buf == BUF_EDGE) p.needs |= NEED_WAVE_EDGE;
             if (buf == BUF_LVL) p.needs |= NEED_WAVE_LVL;
             if (buf == BUF_OUT) p.needs |= NEED_WAVE_OUT;
+            if (buf == BUF_JOIN) p.needs |= NEED_WAVE_JOIN;
         }
     if (a.edges) p.needs |= NEED_ED_SCRATCH;
     if (a.level != DLEVEL_NONE) p.needs |= NEED_LVL_SCRATCH;
     if (p.limits) p.needs |= NEED_LIM_SCRATCH;
     if (a.rate && a.on_chunk) p.needs |= NEED_OUT_RANGES;
     if (multiplies && a.on_chunk) p.needs |= NEED_LVL_RANGES;
+    if (a.joined) p.needs |= NEED_JOIN_TABLE;
     return p;
 }
 

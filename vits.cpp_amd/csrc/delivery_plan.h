@@ -15,6 +15,7 @@ enum DeliveryBuf : int {
     BUF_LVL,       // s2.wave_lvl: the levelled (or limited) waveform, rows as long as its input's
     BUF_OUT,       // s2.wave_out: the PCM at the output rate [B][out_ws]
     BUF_CALLER,    // opts.out_device, rows out_device_stride apart
+    BUF_JOIN,      // s2.wave_join: the joined tracks [G][J_stride] (a joined ask only)
     BUF_COUNT
 };
 enum DeliveryStride : int {
@@ -23,6 +24,7 @@ enum DeliveryStride : int {
     STRIDE_E,       // E_stride: the model-rate rows behind the edges stage (the bounds N + Pl + Pt)
     STRIDE_OUT_WS,  // out_ws: the rows at the output rate
     STRIDE_CALLER,  // out_device_stride
+    STRIDE_J,       // J_stride: the model-rate rows behind the join, one per track (the largest track bound; a joined ask only)
     STRIDE_COUNT
 };
 // the level kinds as delivery sees them. The kinds that multiply are two here because only a plain gain streams
@@ -39,6 +41,8 @@ enum DeliveryRefusal : int {
     REFUSE_LEVEL_STREAM,  // on_chunk with a level that needs the whole utterance
     REFUSE_EDGES_STREAM,  // on_chunk with the edges stage on
     REFUSE_EDGES_ASYNC,   // async with the edges stage on
+    REFUSE_JOIN_STREAM,   // a joined ask with on_chunk: no sample of a track is final before its last utterance is placed
+    REFUSE_JOIN_ASYNC,    // a joined ask with async: the track lengths are read from the device behind the call's work
     REFUSE_COUNT
 };
 enum DeliveryNeed : unsigned {
@@ -50,7 +54,9 @@ enum DeliveryNeed : unsigned {
     NEED_LIM_SCRATCH = 1u << 5,
     NEED_OUT_RANGES = 1u << 6,  // streaming at another rate: the output samples each window finalises
     NEED_LVL_RANGES = 1u << 7,  // streaming under a gain: the model-rate samples each window finalises
-    NEED_COUNT = 8
+    NEED_WAVE_JOIN = 1u << 8,   // a joined ask, unless the join writes straight to out_device: the tracks [G][J_stride]
+    NEED_JOIN_TABLE = 1u << 9,  // a joined ask: the table join.hip reads
+    NEED_COUNT = 10
 };
 
 struct DeliveryAsk {
@@ -61,6 +67,7 @@ struct DeliveryAsk {
     bool out_device = false;   // opts.out_device
     bool on_chunk = false;     // opts.on_chunk
     bool async = false;        // opts.async
+    bool joined = false;       // the call lays its utterances end to end into tracks (vits_model_process_joined): the join runs behind the edges stage
 };
 
 struct DeliveryRoute {
@@ -77,6 +84,9 @@ struct DeliveryPlan {
         DeliveryRoute src, dst;
         DeliveryRoute after;  // what the chain holds behind this stage: its dst, or (a stage that only reads) its src
     } stage[STAGE_COUNT];
+    // a joined ask: the join, between stage[STAGE_EDGES] and stage[STAGE_LEVEL]. It always writes (one row per track); the level and the resampler behind it
+    // read and write G rows, and a levelled buffer follows its input's stride (STRIDE_J). Off for every other ask, whose plan is what it always was.
+    Stage join;
     bool multiplies = false;  // the level stage writes (a plain multiply, or the limiter)
     bool limits = false;      // ... through the limiter
     DeliveryRoute delivered;  // what the call hands out: the destination of the last stage that writes

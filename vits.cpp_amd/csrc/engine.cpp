@@ -255,7 +255,7 @@ int Engine::set_limiter(int mode, std::string& err) {
     return 0;
 }
 
-int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err) const {
+int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err, bool joined) const {
     DeliveryAsk ask;
     ask.edges = edges_on();
     switch (level_kind_) {
@@ -269,6 +269,7 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
     ask.out_device = o.out_device != nullptr;
     ask.on_chunk = o.on_chunk != nullptr;
     ask.async = o.async != 0;
+    ask.joined = joined;
     plan = delivery_plan(ask);
     switch (plan.refusal) {
         case DELIVER_OK: return 0;
@@ -292,6 +293,14 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
                   "device (the trimmed length depends on the audio), which needs a host read behind the call's work: call without async, or pipeline with "
                   "vits_model_submit_batch / vits_model_wait";
             break;
+        case REFUSE_JOIN_STREAM:
+            err = "vits_model_process_joined: on_chunk streams an utterance while it is being made, and a track is laid out once every utterance of it has its length "
+                  "(an overlap reaches back into the utterance in front): call without on_chunk";
+            break;
+        case REFUSE_JOIN_ASYNC:
+            err = "vits_model_process_joined: async returns before the device has finished, and the lengths of the tracks are read from the device behind the call's "
+                  "work: call without async";
+            break;
         default: err = "this combination of delivery stages is not supported"; break;
     }
     return -1;
@@ -302,10 +311,10 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
 // streaming call has multiplied window by window already), and the rows on their way to the slot's pinned copy
 int Engine::run_level(Call& c) {
     std::string& err = c.err;
-    const int B = c.B, n_up = c.n_up;
+    const int B = c.rows, n_up = c.n_up;  // (the rows behind the edges stage: the utterances, or a joined call's tracks)
     const Call::Rows src = c.rows_of(c.dp[STAGE_LEVEL].src), dst = c.rows_of(c.dp[STAGE_LEVEL].dst);
     HIP_OK(lv_.grow(B, owned_, weight_bytes));
-    const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
+    const int64_t samples = c.sum_frames * c.M + (int64_t)c.B * c.sadd[n_up];
     LevelCall lc;
     lc.x = src.p;
     lc.x_stride = src.stride;
@@ -525,7 +534,55 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
         !o.frames_only && !o.async && o.vocoder_chunk_frames <= 0)
         return process_split(ids, id_lens, B, id_stride, o, out, err);
     a1_slot_ = 0;
-    return process_impl(ids, id_lens, B, id_stride, o, out, err, nullptr);
+    const int rc = process_impl(ids, id_lens, B, id_stride, o, out, err, nullptr);
+    if (rc) drain_streams();
+    return rc;
+}
+
+void Engine::drain_streams() {
+    // A call that fails behind its first launch returns with work queued (with fixed_duration > 0 there is no frame-count synchronise in front of stage two's
+    // refusals). Nothing orders the front-end stream of a later vits_model_submit_batch behind the main stream but the event of an async call, which a failed
+    // call does not record: left queued, that stage one and the next submit's would write stage-one arena 0 side by side.
+    if (front_) hipStreamSynchronize(front_);
+    hipStreamSynchronize(stream);
+}
+
+int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, const int32_t* track, const float* gap_ms,
+                           const int32_t* index, vits_batch_result* out, std::string& err) {
+    const std::string who = "vits_model_process_joined: ";
+    if (refuse_pending(err)) return -1;
+    // (on_chunk and async are the plan's refusals, below)
+    if (o.collect_taps) {
+        err = who + "opts.collect_taps is not taken: the taps of the stages in front of the join are per utterance and those behind it per track (run "
+                    "vits_model_process_batch for the former, the vits_op_* entry points for the latter)";
+        return -1;
+    }
+    if (o.noise_kind != VITS_NOISE_COUNTER && o.noise_kind != VITS_NOISE_EXPLICIT) {
+        err = who + "noise_kind " + std::to_string(o.noise_kind) + " is not taken: VITS_NOISE_COUNTER or VITS_NOISE_EXPLICIT (the reference's own stream is that of "
+                    "vits_model_process, one utterance at a time)";
+        return -1;
+    }
+    if (B <= 0 || id_stride <= 0) {
+        err = who + "empty batch";
+        return -1;
+    }
+    DeliveryPlan refusable;
+    if (plan_delivery(o, refusable, err, /*joined=*/true)) return -1;
+    JoinPlan plan;
+    std::string why;
+    if (!join_plan(hp.sampling_rate, B, track, gap_ms, plan, why)) {
+        err = who + why;
+        return -1;
+    }
+    if (check_speakers(o, B, err)) return -1;
+    if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
+    clear_reports();
+    a1_slot_ = 0;
+    join_index_.assign(B, 0);
+    for (int b = 0; b < B; ++b) join_index_[b] = index ? index[b] : b;
+    const int rc = process_impl(ids, id_lens, B, id_stride, o, out, err, nullptr, &plan);
+    if (rc) drain_streams();
+    return rc;
 }
 
 int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
@@ -667,7 +724,7 @@ void Engine::store_durations(const Call& c, const float* pinned) const {
 }
 
 int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
-                         std::string& err, Pending* pend) {
+                         std::string& err, Pending* pend, JoinPlan* join) {
     if (B <= 0 || id_stride <= 0) {
         err = "empty batch";
         return -1;
@@ -677,6 +734,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         return -1;
     }
     Call c(o, err, ids, B, id_stride);
+    c.join = join;
     // An error path between the speculative draw and its commit must not leave the reference stream locked — nor at a timing-dependent
     // position: finish(0) rewinds to the state behind the [T, 2] tensor, where the sequential path this replaces leaves the stream when a call
     // fails before prior sampling (finish(drawn()) committed however many values the helper happened to have drawn).
@@ -752,6 +810,15 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         ref_ahead_.start(hp.stochastic_duration ? (size_t)2 * c.tlen[0] : 0, ref_noise_pinned_.p, ref_noise_pinned_.cap);
         c.ref_ahead = &ref_ahead_;
     }
+    std::vector<int>& frames = c.frames;
+    if (o.fixed_duration > 0) {
+        // every frame count is host arithmetic: so is every bound behind it, and what they refuse is refused here, before anything is queued
+        set_stage_affine(c);
+        frames.resize(B);
+        for (int b = 0; b < B; ++b) frames[b] = std::max(1, o.fixed_duration * c.tlen[b]);
+        c.frames_known();
+        if (plan_rows(c)) return -1;
+    }
     if (layout_stage_one(c)) return -1;
     if (ggml_tables == 1) {
         // emulated-ggml mode: stage one in the exact order shared with the oracle (engine_stage1_exact.cpp)
@@ -764,11 +831,10 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
 
     // ---- the one data-dependent shape (vits.cpp:1133): frames per utterance ---------------------------------
     c.rx.phase("vits.frame_count_sync");
-    std::vector<int>& frames = c.frames;
-    frames.resize(B);
     if (o.fixed_duration > 0) {
-        for (int b = 0; b < B; ++b) frames[b] = std::max(1, o.fixed_duration * c.tlen[b]);
+        // (known since before stage one)
     } else if (pend) {
+        frames.resize(B);
         // through pinned memory behind an event on the stage-one stream: the host waits for this batch's stage one only, while the
         // previous batch's vocoder keeps the device busy
         HIP_OK(pend->frames_pinned.ensure((size_t)B, (size_t)B + 64));
@@ -780,6 +846,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         std::copy(pend->frames_pinned.p, pend->frames_pinned.p + B, frames.begin());
         if (o.durations_out) store_durations(c, pend->dur_pinned.p);
     } else {
+        frames.resize(B);
         // (pinned destination, owned by the engine: into the caller-side std::vector the copy went through the runtime's staging buffer, + 15 us per batch-1 call)
         HIP_OK(frames_host_.ensure((size_t)B, (size_t)B + 64));
         HIP_OK(hipMemcpyAsync(frames_host_.p, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
@@ -799,7 +866,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         HIP_OK(hipStreamWaitEvent(main_stream, pend->s1_done, 0));
     }
     s1_stream.restore();
-    c.frames_known();
+    if (o.fixed_duration <= 0) c.frames_known();
     if (o.collect_taps) {
         TensorRef d;
         d.p = c.s1.dur;
@@ -809,7 +876,15 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     }
     if (o.frames_only) {
         // dispatcher query: predicted frames / samples per utterance, no audio (buffer sizing, shard balancing by frames)
-        if (out) {
+        if (out && join) {
+            // per track: the bound a full call stays within, at the rate it would deliver at, and the frames of the track's utterances
+            if (plan_rows(c)) return -1;
+            const std::vector<int>& len = output_rate_ ? c.out_len : c.mr_len;
+            std::vector<int64_t> tf((size_t)join->tracks, 0);
+            for (int g = 0; g < join->tracks; ++g)
+                for (int b = join->first[(size_t)g]; b < join->first[(size_t)g + 1]; ++b) tf[(size_t)g] += frames[b];
+            fill_result(out, join->tracks, (size_t)(output_rate_ ? c.out_max : c.mr_max), len.begin(), tf.begin());
+        } else if (out) {
             // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
             ResamplePlan plan;
             if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
@@ -940,6 +1015,112 @@ int Engine::upload_ranges(Call& c, std::vector<int>& table, int* dev, const std:
     return 0;
 }
 
+// ---- what the host knows of the rows a call delivers (engine.h): host arithmetic from the frame counts, nothing is queued here
+int Engine::plan_rows(Call& c) {
+    if (c.rows_planned) return 0;
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const int B = c.B, n_up = c.n_up;
+    if (plan_delivery(o, c.dp, err, c.join != nullptr)) return -1;
+    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
+    c.mr_len = c.slen[n_up];
+    if (c.dp[STAGE_EDGES].runs)
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = edges_plan_.bound(c.slen[n_up][b]);
+            if (n > (int64_t)INT32_MAX - 64) {
+                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
+                return -1;
+            }
+            c.mr_len[b] = (int)n;
+        }
+    c.utt_max = c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
+    c.rows = B;
+    const char* row_name = "utterance ";
+    if (c.join) {
+        // a joined call: the rows behind the join are the tracks, and what the host knows of each is its bound (the utterances' bounds and the positive gaps)
+        const std::vector<int64_t> ub(c.mr_len.begin(), c.mr_len.end());
+        std::string why;
+        if (!join_bounds(*c.join, ub.data(), why)) {
+            err = "vits_model_process_joined: " + why;
+            return -1;
+        }
+        c.mr_len.assign(c.join->bound.begin(), c.join->bound.end());  // (each at most kEdgesMaxLen = 2^30)
+        c.mr_max = (int)c.join->max_bound;
+        c.rows = c.join->tracks;
+        row_name = "track ";
+    }
+    if (output_rate_) {
+        ResamplePlan plan;  // (the plan of the handle's table: set_rates accepted the pair)
+        if (!resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
+        c.out_len.resize((size_t)c.rows);
+        for (int r = 0; r < c.rows; ++r) {
+            const int64_t n = plan.out_len(c.mr_len[r]);
+            if (n > (int64_t)INT32_MAX - 64) {
+                err = row_name + std::to_string(r) + " has " + std::to_string(n) + " samples at the output rate: too long";
+                return -1;
+            }
+            c.out_len[r] = (int)n;
+            c.out_max = std::max(c.out_max, (int)n);
+        }
+        c.out_ws = round_up(std::max(c.out_max, 1), 32);
+    }
+    if (o.out_device && !o.frames_only) {
+        const bool rs = output_rate_ != 0;
+        const std::vector<int>& len = rs ? c.out_len : c.mr_len;
+        const int longest = rs ? c.out_max : c.mr_max;
+        if (o.out_device_stride < longest) {
+            if (c.join) {
+                const int g = (int)(std::find_if(len.begin(), len.end(), [&](int n) { return n > o.out_device_stride; }) - len.begin());
+                err = "vits_model_process_joined: out_device_stride = " + std::to_string(o.out_device_stride) + " is below track " + std::to_string(g) + "'s " +
+                      std::to_string(len[(size_t)g]) + " samples";
+            } else err = "out_device_stride is smaller than the longest utterance";
+            if (rs) err += " (" + std::to_string(longest) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
+            return -1;
+        }
+    }
+    c.rows_planned = true;
+    return 0;
+}
+
+// ---- the join of a joined call: the rows behind the edges stage -> the tracks (join.hip), the offsets and the track lengths on the device, and the joins'
+// rows on their way to the slot's pinned copy
+int Engine::run_join(Call& c) {
+    std::string& err = c.err;
+    const JoinPlan& p = *c.join;
+    const int B = c.B;
+    const Call::Rows src = c.rows_of(c.dp.join.src), dst = c.rows_of(c.dp.join.dst);
+    const std::vector<int64_t> table = join_table(p);
+    HIP_OK(join_table_host_.ensure(table.size(), table.size() + table.size() / 4 + 64));
+    std::memcpy(join_table_host_.p, table.data(), sizeof(int64_t) * table.size());
+    HIP_OK(hipMemcpyAsync(c.s2.join_table, join_table_host_.p, sizeof(int64_t) * table.size(), hipMemcpyHostToDevice, stream));
+    prof.fence();
+    JoinCall jc;
+    jc.plan = &p;
+    jc.x = src.p;
+    jc.x_stride = src.stride;
+    jc.lens = c.utt_lens;
+    jc.y = dst.p;
+    jc.y_stride = dst.stride;
+    jc.table = c.s2.join_table;
+    jc.rows = jn_.dev();
+    jc.track_lens = reinterpret_cast<int*>(jn_.dev() + (size_t)2 * B);  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
+    int64_t in_s = 0, out_s = 0;
+    for (const int64_t n : p.ubound) in_s += n;
+    for (const int64_t n : p.bound) out_s += n;
+    prof.begin("join_offsets", 0, 20.0 * (double)B, stream, /*chain=*/true);
+    hipError_t e = launch_join_offsets(jc, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    // at most one add per sample; every utterance read once, every track's bound written once
+    prof.begin("join_apply", (double)in_s, 4.0 * ((double)in_s + (double)out_s), stream, /*chain=*/true);
+    e = launch_join_apply(jc, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    HIP_OK(jn_.queue_copy(a1_slot_, B, stream));
+    prof.fence();
+    return 0;
+}
+
 // ---- everything behind the last vocoder window: the stages the call's plan runs, each reading what the one in front of it wrote (Call::rows_of of the plan's
 // routes), their taps, and the last window's chunks of a streaming call
 int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<int()>& last_chunks) {
@@ -975,6 +1156,7 @@ int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<in
             tap("waveform_edges", dp[STAGE_EDGES].after, tap_max, tap_len);
         }
     }
+    if (dp.join.runs && run_join(c)) return -1;
     if (dp[STAGE_LEVEL].runs) {
         if (run_level(c)) return -1;
         if (o.collect_taps) tap("waveform_level", dp[STAGE_LEVEL].after, tap_max, tap_len);
@@ -1001,8 +1183,9 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     const vits_process_opts& o = c.o;
     const int B = c.B, n_up = c.n_up, Lmax = c.Lmax;
     const std::vector<int>& frames = c.frames;
-    // the delivery chain behind the vocoder, planned once (its refusals were the entry points', before stage one was queued: nothing is refused here that was not there)
-    if (plan_delivery(o, c.dp, err)) return -1;
+    // the delivery chain behind the vocoder, planned once (its refusals were the entry points', before stage one was queued: nothing is refused here that was not
+    // there), and what the host knows of the rows the call delivers: refused here, with nothing of stage two queued, if it was not before stage one
+    if (plan_rows(c)) return -1;
     const DeliveryPlan& dp = c.dp;
     // ---- vocoder windows (long-form / streaming, vits.h vocoder_chunk_frames) ------------------------------------
     // Window w owns frames [f0, f1) and computes frames [lo, hi) = the owned range widened by the vocoder's receptive
@@ -1023,35 +1206,10 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     // caller cannot know in advance, or collect_taps — streams as ONE window: the sink gets each utterance in a single call)
     for (const Call::Win& w : wins) c.Lw_max = std::max(c.Lw_max, w.hi - w.lo);
     const int M = c.M = c.smul[n_up];  // samples per frame
-    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
     const bool ed = dp[STAGE_EDGES].runs;
-    c.mr_len = c.slen[n_up];
-    if (ed)
-        for (int b = 0; b < B; ++b) {
-            const int64_t n = edges_plan_.bound(c.slen[n_up][b]);
-            if (n > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
-                return -1;
-            }
-            c.mr_len[b] = (int)n;
-        }
-    c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
-    if (output_rate_) {
-        // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and
-        // resample.hip writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities
-        if (!(c.rate_out = rate_table(hp.sampling_rate, output_rate_, err))) return -1;
-        c.out_len.resize(B);
-        for (int b = 0; b < B; ++b) {
-            const int64_t n = c.rate_out->plan.out_len(c.mr_len[b]);
-            if (n > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples at the output rate: too long";
-                return -1;
-            }
-            c.out_len[b] = (int)n;
-            c.out_max = std::max(c.out_max, (int)n);
-        }
-        c.out_ws = round_up(std::max(c.out_max, 1), 32);
-    }
+    // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and resample.hip
+    // writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities (plan_rows)
+    if (output_rate_ && !(c.rate_out = rate_table(hp.sampling_rate, output_rate_, err))) return -1;
     const bool rs = dp[STAGE_RESAMPLE].runs;
     // a level that multiplies (every kind but VITS_LEVEL_MEASURE): the vocoder writes to the call's own buffer, loudness.hip measures it there and
     // multiplies it into what is delivered, or into the resampler's input. VITS_LEVEL_MEASURE measures the waveform where the vocoder wrote it
@@ -1079,18 +1237,17 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     // (stated edges: the bounds; the lengths proper are read from the stage's rows where the results are filled)
     const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
     const int pcm_max = rs ? c.out_max : c.mr_max;
-    if (o.out_device) {
-        if (o.out_device_stride < pcm_max) {
-            err = "out_device_stride is smaller than the longest utterance";
-            if (rs) err += " (" + std::to_string(pcm_max) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
-            return -1;
-        }
-    }
     // the device lengths [B] of the model-rate rows, for every stage behind the vocoder: its sample counts, or what the edges stage will write behind its rows
     c.mr_lens = c.s1.stage_lens + (size_t)n_up * B;
     if (ed) {
         HIP_OK(ed_.grow(B, owned_, weight_bytes));
         c.mr_lens = static_cast<const int*>(ed_.tail());
+    }
+    if (c.join) {
+        // behind the join the rows are the tracks: their lengths T_g lie behind the {o_b, n_b} rows of the joins' report
+        HIP_OK(jn_.grow(B, owned_, weight_bytes));
+        c.utt_lens = c.mr_lens;
+        c.mr_lens = reinterpret_cast<const int*>(jn_.dev() + (size_t)2 * B);
     }
     // where the plan routes the vocoder's waveform and what is delivered (Call::rows_of: straight to out_device when nothing follows)
     const Call::Rows wave = c.rows_of(dp[STAGE_VOCODER].dst), pcm = c.rows_of(dp.delivered);
@@ -1106,7 +1263,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         rsc.y_stride = pcm_stride;
         rsc.taps = c.rate_out->taps;
         rsc.plan = c.rate_out->plan;
-        rsc.batch = B;
+        rsc.batch = c.rows;
     }
     std::vector<hipEvent_t> chunk_ev;
     struct EvGuard {
@@ -1282,7 +1439,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
 
     // ---- results ------------------------------------------------------------------------------------------------
     c.rx.phase("vits.results");
-    const int lv_n = c.lev ? B : 0, lm_n = dp.limits ? B : 0, ed_n = ed ? B : 0;  // the rows of the three reports this call fills
+    const int R = c.rows;  // what the call hands out: one row per utterance, or per track
+    const int lv_n = c.lev ? R : 0, lm_n = dp.limits ? R : 0, ed_n = ed ? B : 0, jn_n = c.join ? B : 0;  // the rows of the reports this call fills
     if (pend) {
         // a pipelined batch: everything the host will hand out is known now; the PCM (if a host copy was asked for) goes to the
         // slot's pinned staging behind the kernels, and `done` marks the end of the batch on the device
@@ -1304,12 +1462,18 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         return 0;
     }
     if (out) {
-        fill_result(out, B, (size_t)pcm_max, pcm_len.begin(), frames.begin());
+        if (c.join) {
+            // (lengths: the bounds until the track lengths have landed below; frames: the sums over each track's utterances)
+            std::vector<int64_t> tf((size_t)R, 0);
+            for (int g = 0; g < R; ++g)
+                for (int b = c.join->first[(size_t)g]; b < c.join->first[(size_t)g + 1]; ++b) tf[(size_t)g] += frames[b];
+            fill_result(out, R, (size_t)pcm_max, pcm_len.begin(), tf.begin());
+        } else fill_result(out, B, (size_t)pcm_max, pcm_len.begin(), frames.begin());
         if (!o.skip_host_copy) {
-            out->data = new float[(size_t)B * out->stride];
+            out->data = new float[(size_t)R * out->stride];
             if (o.on_chunk) std::memcpy(out->data, host_pcm, sizeof(float) * (size_t)B * out->stride);  // already streamed to the host
             else
-                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, pcm_dst, (size_t)pcm_stride * 4, out->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, pcm_dst, (size_t)pcm_stride * 4, out->stride * 4, (size_t)R, hipMemcpyDeviceToHost, stream));
             prof.fence();
         }
     }
@@ -1321,7 +1485,20 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
         // the rows have landed: kept apart from the pinned copies, which a later submit into this slot overwrites; the trimmed lengths are what the call reports
-        if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
+        if (jn_n) {
+            // the joins' rows and the track lengths have landed: the report names each utterance and its track; the call reports T_g (at the output rate)
+            const int64_t* on = jn_.slot_rows(a1_slot_);
+            const int* tl = reinterpret_cast<const int*>(on + (size_t)2 * B);
+            std::vector<int64_t> rows((size_t)4 * B);
+            for (int g = 0; g < R; ++g)
+                for (int b = c.join->first[(size_t)g]; b < c.join->first[(size_t)g + 1]; ++b) {
+                    rows[(size_t)4 * b] = join_index_[(size_t)b], rows[(size_t)4 * b + 1] = g;
+                    rows[(size_t)4 * b + 2] = on[(size_t)2 * b], rows[(size_t)4 * b + 3] = on[(size_t)2 * b + 1];
+                }
+            jn_.store(std::move(rows));
+            if (out)
+                for (int g = 0; g < R; ++g) out->lengths[g] = rs ? c.rate_out->plan.out_len(tl[g]) : tl[g];
+        } else if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
         lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)

@@ -164,6 +164,12 @@ class ReportRows {
         if (unlanded_ >= 0) landed(unlanded_, rows_);
     }
     void clear() { rows_ = 0, unlanded_ = -1; }
+    // rows [n][4] made on the host from what has landed (the joins': the device holds {o_b, n_b}, the report adds the index and the track)
+    void store(std::vector<T> rows) {
+        store_ = std::move(rows);
+        rows_ = (int)(store_.size() / 4);
+        unlanded_ = -1;
+    }
     // the rows [rows][4] of the most recently completed call (0 rows: it ran without the stage)
     const T* read(int& rows) const {
         rows = rows_;
@@ -292,6 +298,13 @@ class Engine {
     bool validate(const uint8_t* bytes, size_t size, std::string& err);
     int process_batch(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                       std::string& err);
+    // the utterances of a batch laid end to end inside the call (include/vits.h vits_model_process_joined): the batch runs per utterance up to and including
+    // the edges stage, join.hip lays it into the tracks of (track, gap_ms) — as vits_join_plan takes them —, and the handle's level or limiter and the
+    // resampler run on the tracks. Synchronous, never split, never pipelined. index [batch]: what the joins report names each utterance (null: b)
+    int process_joined(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, const int32_t* track, const float* gap_ms,
+                       const int32_t* index, vits_batch_result* out, std::string& err);
+    // the rows [B][4] = {index, track, o_b, n_b} (model rate) of the most recently completed joined call (empty: the last call did not join)
+    const int64_t* last_joins(int& rows) const { return jn_.read(rows); }
     // pipelined batches (include/vits.h vits_model_submit_batch / vits_model_wait): up to two in flight
     int submit_batch(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, std::string& err);
     int wait_batch(vits_batch_result* out, std::string& err);
@@ -508,7 +521,9 @@ class Engine {
     hipEvent_t ev_async_ = nullptr;           // orders the front-end stream behind that tail
     int process_split(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err);
     int process_impl(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err,
-                     Pending* pend);
+                     Pending* pend, JoinPlan* join = nullptr);
+    // a synchronous entry point's error return: whatever the failed call queued has run before the handle takes another (submit_batch does the same)
+    void drain_streams();
     hipError_t copy_durations(const Call& c, PinnedBuf<float>& pinned);
     void store_durations(const Call& c, const float* pinned) const;
     // The three resblocks of a vocoder stage (kernel sizes 3/7/11) are independent chains of six convolutions; they run on
@@ -565,11 +580,21 @@ class Engine {
     // The delivery chain behind the vocoder (delivery_plan.h): what this handle and the call's options ask for -> the call's plan. 0, or -1 + the message of
     // the combination the plan refuses (on_chunk with a level that needs the whole utterance, with the limiter, with edges; async with edges). Called before
     // stage one is queued by every entry point that can be refused, and by run_stage_two, which keeps the plan in the call.
-    int plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err) const;
-    // the report rows of the three stages (ReportRows: device rows owned_ and counted in weight_bytes); the edges' carry the trimmed lengths int32 [cap] behind them
+    int plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err, bool joined = false) const;
+    // What the host knows of the rows a call delivers, from the frame counts alone (no device work): the call's plan, the model-rate bounds of every utterance
+    // (c.mr_len, with the edges' pads), the tracks' bounds of a joined call, the lengths at the output rate, and the refusals that follow from them — an
+    // utterance or track that is too long, an out_device_stride that cannot hold the longest row. Runs before anything is queued when the frame counts are
+    // host arithmetic (fixed_duration > 0), else as the first thing of stage two, directly behind the frame-count synchronise. Once per call.
+    int plan_rows(Call& c);
+    // the report rows of the stages (ReportRows: device rows owned_ and counted in weight_bytes); the edges' carry the trimmed lengths int32 [cap] behind them.
+    // The joins' device rows of a call of B utterances hold {o_b, n_b} [B][2] and, behind them, the track lengths T_g int32 [G]
     ReportRows<float> lv_, lm_;
-    ReportRows<int64_t> ed_{sizeof(int)};
-    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(); }
+    ReportRows<int64_t> ed_{sizeof(int)}, jn_;
+    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(); }
+    PinnedBuf<int64_t> join_table_host_;  // a joined call's table (host side of its H2D copy)
+    std::vector<int32_t> join_index_;     // ... and what its report names each utterance (process_joined: b, or the caller's index)
+    // the join of a joined call (join.hip) from its source into its destination, as the call's plan routes them: queued behind the edges stage, in front of run_level
+    int run_join(Call& c);
     // levelling: the handle's setting and the plan at the model's rate
     int level_kind_ = VITS_LEVEL_NONE;
     float level_value_ = 0.f, level_ceiling_ = 0.f;

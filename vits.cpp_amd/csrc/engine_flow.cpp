@@ -34,7 +34,11 @@ int Engine::layout_stage_two(Call& c) {
     c.fuse16 = fast16 && !knobs.no_fuse16;  // resblock conv pairs of the narrow stages as one kernel
     const size_t x16_elems2 = arith_now_ != VITS_ARITH_F32 ? std::max({big, (size_t)B * round_up(H, 8) * round_up(ls, 8), (size_t)B * round_up(hp.up_init, 8) * round_up(lws, 8), (size_t)B * round_up(F, 8) * round_up(ls, 8)}) + 64 : 0;
     const int S_stride = c.S_stride = round_up(smax[n_up], 32);
-    const int E_stride = c.E_stride = c.dp[STAGE_EDGES].runs ? round_up(std::max(c.mr_max, 1), 32) : S_stride;
+    const int E_stride = c.E_stride = c.dp[STAGE_EDGES].runs ? round_up(std::max(c.utt_max, 1), 32) : S_stride;
+    // the rows behind the edges stage (Engine::plan_rows): one per utterance at E_stride, or — a joined call — one per track at J_stride
+    const int R = c.rows;
+    const int J_stride = c.J_stride = c.join ? round_up(std::max(c.mr_max, 1), 32) : 0;
+    const int L_stride = c.join ? J_stride : E_stride;
     // VITS_ARITH_F32_SPLIT: three bf16 planes per conv input of the wide stages' resblocks (conv_split.hip): the stage input once, t and the stream per
     // concurrently running resblock
     size_t sp_elems = 0;
@@ -70,15 +74,17 @@ int Engine::layout_stage_two(Call& c) {
         s2.wave = a.alloc<float>((size_t)B * S_stride);
         // the buffers of the delivery chain: exactly what the call's plan names (delivery_plan.h; a stage that writes straight to out_device needs none)
         const DeliveryPlan& dp = c.dp;
-        s2.wave_out = dp.need(NEED_WAVE_OUT) ? a.alloc<float>((size_t)B * c.out_ws) : nullptr;
+        s2.wave_out = dp.need(NEED_WAVE_OUT) ? a.alloc<float>((size_t)R * c.out_ws) : nullptr;
         s2.out_ranges = dp.need(NEED_OUT_RANGES) ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
-        s2.wave_lvl = dp.need(NEED_WAVE_LVL) ? a.alloc<float>((size_t)B * E_stride) : nullptr;
-        s2.lvl_scratch = dp.need(NEED_LVL_SCRATCH) ? a.alloc<char>(level_scratch_bytes(B, c.mr_max, level_plan_.S)) : nullptr;
-        s2.lim_scratch = dp.need(NEED_LIM_SCRATCH) ? a.alloc<char>(limit_scratch_bytes(B, c.mr_max)) : nullptr;
+        s2.wave_lvl = dp.need(NEED_WAVE_LVL) ? a.alloc<float>((size_t)R * L_stride) : nullptr;
+        s2.lvl_scratch = dp.need(NEED_LVL_SCRATCH) ? a.alloc<char>(level_scratch_bytes(R, c.mr_max, level_plan_.S)) : nullptr;
+        s2.lim_scratch = dp.need(NEED_LIM_SCRATCH) ? a.alloc<char>(limit_scratch_bytes(R, c.mr_max)) : nullptr;
         s2.wave_edge = dp.need(NEED_WAVE_EDGE) ? a.alloc<float>((size_t)B * E_stride) : nullptr;
         s2.ed_scratch = dp.need(NEED_ED_SCRATCH) ? a.alloc<char>(edges_scratch_bytes(B, smax[n_up], edges_plan_.W)) : nullptr;
         s2.lvl_ranges = dp.need(NEED_LVL_RANGES) ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
         s2.tile_maps = c.tm_total ? a.alloc<TileEntry>((size_t)c.tm_total) : nullptr;
+        s2.wave_join = dp.need(NEED_WAVE_JOIN) ? a.alloc<float>((size_t)R * J_stride) : nullptr;
+        s2.join_table = dp.need(NEED_JOIN_TABLE) ? a.alloc<int64_t>(join_table_elems(B, R)) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

@@ -212,6 +212,8 @@ struct Call {
         void* ed_scratch;   // stated edges on: edges_scratch_bytes of edges.hip
         int* lvl_ranges;    // VITS_LEVEL_GAIN, streaming: [window][2][B]: the model-rate samples [j0, j1) of each utterance that window w finalises
         TileEntry* tile_maps;  // ragged fp32 calls: the lists of existing tiles of every window (tm_total entries), or null
+        float* wave_join;      // a joined call, unless the join writes straight to out_device: the tracks [G][J_stride]
+        int64_t* join_table;   // a joined call: join_table(plan)
     } s2{};
     // Ragged batches, exact fp32 vocoder: the lists of existing tiles (tile_map.h) of the large launches whose dense grid would hold empty blocks. One list per
     // (window, length vector, tile width): length vector i = the lengths at vocoder stage i (conv_pre, the stage's resblocks), convt = upsampler i (columns
@@ -250,6 +252,7 @@ struct Call {
             case BUF_LVL: out.p = s2.wave_lvl; break;
             case BUF_OUT: out.p = s2.wave_out; break;
             case BUF_CALLER: out.p = (float*)o.out_device; break;
+            case BUF_JOIN: out.p = s2.wave_join; break;
             default: break;
         }
         switch (r.stride) {
@@ -257,6 +260,7 @@ struct Call {
             case STRIDE_E: out.stride = E_stride; break;
             case STRIDE_OUT_WS: out.stride = out_ws; break;
             case STRIDE_CALLER: out.stride = o.out_device_stride; break;
+            case STRIDE_J: out.stride = J_stride; break;
             default: break;
         }
         return out;
@@ -274,6 +278,14 @@ struct Call {
     const int* mr_lens = nullptr;
     std::vector<int> mr_len;
     int mr_max = 0;
+    // The rows the stages behind the edges stage work on, and the call hands out (Engine::plan_rows): one per utterance, or — a joined call
+    // (vits_model_process_joined; join: its tracks and gaps, its bounds once plan_rows has run) — one per track. Behind the join mr_len / mr_max / mr_lens are the
+    // tracks' (bounds on the host, T_g on the device) and J_stride is their row stride; utt_max and utt_lens keep what they were per utterance, which the edges
+    // stage's stride and the join's input are sized and read by.
+    JoinPlan* join = nullptr;
+    int rows = 0, utt_max = 0, J_stride = 0;
+    const int* utt_lens = nullptr;
+    bool rows_planned = false;
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
 };

@@ -194,4 +194,64 @@ int64_t split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_
     return count;
 }
 
+// ---- vits_model_speak: spans, kinds and gaps -> the batch of one joined call --------------------------------------------------------------------------------
+bool speak_plan(const char* text, float sentence_gap_ms, float paragraph_gap_ms, bool track_per_paragraph, SpeakTokenize tokenize, void* user, SpeakPlan& p,
+                std::string& err) {
+    if (!text || !*text) {
+        err = "the text is NULL or empty";
+        return false;
+    }
+    for (const auto& [ms, name] : {std::make_pair(sentence_gap_ms, "sentence_gap_ms"), std::make_pair(paragraph_gap_ms, "paragraph_gap_ms")})
+        if (!(std::isfinite(ms) && ms >= kJoinMinGapMs && ms <= kJoinMaxGapMs)) {
+            err = std::string(name) + " = " + fmt(ms) + ": must be finite and in [-2000, 60000] ms";
+            return false;
+        }
+    const int64_t n = split_sentences(text, nullptr, nullptr, nullptr, 0);
+    std::vector<int64_t> starts((size_t)n), ends((size_t)n);
+    std::vector<int32_t> kinds((size_t)n);
+    split_sentences(text, starts.data(), ends.data(), kinds.data(), (size_t)n);
+    SpeakPlan q;
+    std::vector<std::vector<int32_t>> kept;
+    std::vector<char> ends_paragraph;  // [kept]
+    for (int64_t i = 0; i < n; ++i) {
+        std::vector<int32_t> ids;
+        if (!tokenize(user, std::string(text + starts[(size_t)i], (size_t)(ends[(size_t)i] - starts[(size_t)i])), ids, err)) return false;
+        if (ids.size() > (size_t)kSpeakMaxIds) {
+            err = "span " + std::to_string(i) + " (bytes " + std::to_string(starts[(size_t)i]) + " .. " + std::to_string(ends[(size_t)i]) + ") has " +
+                  std::to_string(ids.size()) + " ids, above the " + std::to_string(kSpeakMaxIds) + " an utterance may have: break the sentence up";
+            return false;
+        }
+        if (ids.empty()) {
+            // nothing to say: dropped; the paragraph it ended ends with the span in front of it
+            if (kinds[(size_t)i] == 1 && !kept.empty()) ends_paragraph.back() = 1;
+            continue;
+        }
+        q.id_stride = std::max(q.id_stride, (int)ids.size());
+        q.index.push_back((int32_t)i);
+        kept.push_back(std::move(ids));
+        ends_paragraph.push_back(kinds[(size_t)i] == 1);
+    }
+    if (kept.empty()) {
+        err = "no speakable span: the text holds " + std::to_string(n) + " span" + (n == 1 ? "" : "s") + " and none of them has a symbol the tokenizer knows";
+        return false;
+    }
+    if (kept.size() > 65535) {
+        err = "the text has " + std::to_string(kept.size()) + " speakable spans, above the 65535 a call may join: speak it in parts";
+        return false;
+    }
+    q.batch = (int)kept.size();
+    q.ids.assign((size_t)q.batch * q.id_stride, 0);
+    int32_t track = 0;
+    for (int k = 0; k < q.batch; ++k) {
+        const bool new_paragraph = k > 0 && ends_paragraph[(size_t)k - 1];
+        if (new_paragraph && track_per_paragraph) ++track;
+        q.track.push_back(track);
+        q.gap_ms.push_back(k == 0 ? 0.f : (new_paragraph ? paragraph_gap_ms : sentence_gap_ms));
+        q.id_lens.push_back((int32_t)kept[(size_t)k].size());
+        std::copy(kept[(size_t)k].begin(), kept[(size_t)k].end(), q.ids.begin() + (size_t)k * q.id_stride);
+    }
+    p = std::move(q);
+    return true;
+}
+
 }  // namespace vits

@@ -870,6 +870,23 @@ inline size_t join_table_elems(int batch, int tracks) { return (size_t)2 * batch
 void join_host(const JoinPlan& p, const float* x, int64_t x_stride, const int64_t* lens, float* y, int64_t y_stride, int64_t* track_lens, int64_t* rows);
 // vits_split_sentences (include/vits.h): the spans of a text, in bytes; returns how many there are (the first `cap` of them are written)
 int64_t split_sentences(const char* text, int64_t* starts, int64_t* ends, int32_t* kinds, size_t cap);
+// vits_model_speak's host side (join_host.cpp; no device, no model: the tokenizer comes in as a function): the text cut by split_sentences, every span
+// tokenised, the spans that have ids as ONE batch for vits_model_process_joined. A span without ids is dropped; if it ended its paragraph, the kept span in
+// front of it does. Kept span k > 0 gets paragraph_gap_ms when the kept span in front of it ended a paragraph (and, track_per_paragraph, opens the next
+// track), else sentence_gap_ms. false + a message: a NULL or empty text, a gap that is not finite or outside vits_join_plan's range, what the tokenizer
+// refuses, a span above kSpeakMaxIds ids (naming the span), no span with ids at all, more than 65535 of them.
+constexpr int kSpeakMaxIds = 2048;
+struct SpeakPlan {
+    int batch = 0, id_stride = 0;
+    std::vector<int32_t> index;    // [batch]: the span's index in split_sentences order
+    std::vector<int32_t> track;    // [batch]
+    std::vector<float> gap_ms;     // [batch]: 0 for the first span
+    std::vector<int32_t> id_lens;  // [batch]
+    std::vector<int32_t> ids;      // [batch][id_stride]: 0 past a span's length
+};
+typedef bool (*SpeakTokenize)(void* user, const std::string& span, std::vector<int32_t>& ids, std::string& err);
+bool speak_plan(const char* text, float sentence_gap_ms, float paragraph_gap_ms, bool track_per_paragraph, SpeakTokenize tokenize, void* user, SpeakPlan& p,
+                std::string& err);
 struct JoinCall {
     const JoinPlan* plan = nullptr;  // host: what the table was made from (join_call_ok checks every index the kernels take from it)
     const float* x = nullptr;        // device [batch][x_stride]
