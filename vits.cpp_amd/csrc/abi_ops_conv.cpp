@@ -266,18 +266,9 @@ bool resblock_resolve(const vits_resblock_desc* d, int arith, RbOpPlan& r, std::
     const std::string shape = "C = " + std::to_string(C) + ", k = " + std::to_string(k);
     char name[96];
     int v = d->variant;
-    if (v == 0) {  // engine_vocoder.cpp's order: the whole-ResBlock kernel, fused pairs (all pairs or none), two launches per pair
-        if (f32) {
-            bool pairs = true;
-            for (int p = 0; p < nd; ++p) pairs = pairs && rbpair32_supported(C, k, d->dil[p]);
-            v = pairs && rbblock32_supported(C, k, d->dil, nd) ? 3 : pairs ? 2 : 1;
-        } else if (rbblock16_supported(C, k, d->dil, nd, B, T)) {
-            v = plan_rbblock16(C, k, B, T).nt > 1 ? 4 : 3;
-        } else {
-            bool pairs = true, lat = C >= 128;
-            for (int p = 0; p < nd; ++p) pairs = pairs && rbpair16_supported(C, k, d->dil[p]), lat = lat && conv16_lat_shape_ok(C, k, d->dil[p], B, T);
-            v = pairs && !lat ? 2 : 1;
-        }
+    if (v == 0) {  // the engine's per-resblock rule (vocoder_plan.h) on the operator's weights (every plane, a bias) and a handle's default knobs
+        const RbKernel kernel = f32 ? rb_kernel32(C, k, d->dil, nd, RbHas(), VocPolicy()) : rb_kernel16(C, k, d->dil, nd, RbHas(), B, T, VocPolicy());
+        v = kernel != RbKernel::Block ? (kernel == RbKernel::Pairs ? 2 : 1) : !f32 && plan_rbblock16(C, k, B, T).nt > 1 ? 4 : 3;
     }
     r.variant = v;
     if (v == 1) {

@@ -903,8 +903,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
 }
 
 // ---- ragged batches: the lists of existing tiles of the fp32 vocoder's launches (tile_map.h) -------------------------------------------------------------
-// Which launches take one is asked of the planners with the shapes run_vocoder_window32 will pass (a launcher whose plan names another width finds no list and
-// keeps its dense grid). A list is planned where the launch is large (kSmallGridBlocks, as tile_map_for) and its dense grid would hold blocks past an
+// Which launches take one is asked of the planners with the shapes and the policy run_vocoder_window32 will pass. A list is planned where the launch is large (kSmallGridBlocks, as tile_map_for) and its dense grid would hold blocks past an
 // utterance's end; VITS_TILE_MAP plans it for every converted launch. Host arithmetic only.
 void Engine::plan_tile_maps(Call& c) {
     c.tm_jobs.clear();
@@ -913,9 +912,12 @@ void Engine::plan_tile_maps(Call& c) {
     if (arith_now_ != VITS_ARITH_F32 || split_on() || kn.no_tile_map || (c.B < 2 && !kn.tile_map)) return;
     const int B = c.B, n_up = c.n_up;
     const size_t nk = hp.rb_k.size();
+    const VocPolicy pol = voc_policy(c);
     std::vector<int> la(B), lb(B);
     for (size_t wi = 0; wi < c.wins.size(); ++wi) {
         const int Lw = c.wins[wi].hi - c.wins[wi].lo;
+        int64_t frames = 0;  // (WinCtx::ssum[0])
+        for (int b = 0; b < B; ++b) frames += c.win_len(wi, 0, b);
         auto smax = [&](int i) { return Lw * c.smul[i] + c.sadd[i]; };  // (WinCtx::smax)
         auto want = [&](int vec, int width, bool convt, int64_t dense_blocks) {
             for (const Call::TileMapJob& j : c.tm_jobs)
@@ -945,16 +947,14 @@ void Engine::plan_tile_maps(Call& c) {
             const UpStageW& U = ups_[i];
             const int C = U.channels, vec = i + 1;
             conv_width(U.up, i, 1);
+            const VocStage32Plan stage = plan_voc_stage32(U, B, smax(vec), frames, pol);
             for (size_t j = 0; j < nk; ++j) {
-                // (the kernel of resblock j by the rule run_vocoder_window32 schedules by; where the call's buffers then rule a fused kernel out, its launcher finds
-                // no list of its width and keeps the dense grid)
                 const ResBlockW& R = U.rbs[j];
-                const int kind = j < 3 ? rb32_kind(R, C) : 0;
-                const bool fused = kind >= 1;
-                if (kind == 2) {
+                const RbKernel kernel = stage.kernel_of(j);
+                if (kernel == RbKernel::Block) {
                     const RbBlock32Plan pl = plan_rbblock32(C, R.k, B, smax(vec));
                     want(vec, rbblock32_geom(C, pl.nr).bo, false, (int64_t)pl.gx * pl.gy);
-                } else if (fused) {
+                } else if (kernel == RbKernel::Pairs) {
                     for (size_t d = 0; d < R.dil.size(); ++d) {
                         const LaunchGrid pl = plan_rbpair32(C, R.k, R.dil[d], B, smax(vec));
                         want(vec, rbpair32_geom(R.k, R.dil[d], C).bo, false, (int64_t)pl.gx * pl.gy);

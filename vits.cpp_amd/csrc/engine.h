@@ -19,6 +19,7 @@
 #include "delivery_plan.h"
 #include "kernels.h"
 #include "model_file.h"
+#include "vocoder_plan.h"
 
 namespace vits {
 
@@ -210,21 +211,6 @@ struct FlowLayerW {
     PackedConv pre, post;
     std::vector<PackedConv> in_layers, res_skip;
 };
-struct ResBlockW {
-    std::vector<PackedConv> c1, c2;
-    std::vector<int> dil;
-    int k;
-    // the three conv pairs as the whole-resblock kernels take them
-    void pairs3(const PackedConv* (&w1)[3], const PackedConv* (&w2)[3]) const {
-        for (int d = 0; d < 3; ++d) w1[d] = &c1[d], w2[d] = &c2[d];
-    }
-};
-struct UpStageW {
-    PackedConv up;
-    std::vector<ResBlockW> rbs;
-    int channels, stride, k;
-};
-
 // Every VITS_* environment knob of the orchestrator, read ONCE when the model is loaded (never on the call path: getenv is
 // not thread-safe against setenv, and a per-layer lookup is host time inside the caller's timed region). INTEGRATION.md §9.
 struct Knobs {
@@ -696,7 +682,7 @@ class Engine {
     // ragged batches on lists of existing tiles (tile_map.h; Call::tm_jobs): which lists the call's fp32 vocoder launches take, from the host's lengths and the
     // planners (no device work); the fill into `pinned` + one in-stream copy; a window's sets as its launches find them
     void plan_tile_maps(Call& c);
-    int rb32_kind(const ResBlockW& R, int C) const;  // 2 whole-resblock kernel, 1 fused pairs, 0 two launches per pair (engine_vocoder.cpp)
+    VocPolicy voc_policy(const Call& c) const;  // what the vocoder planner reads of the handle and the call (vocoder_plan.h); aligned: true until the window tests its buffers
     hipError_t upload_tile_maps(Call& c, PinnedBuf<TileEntry>& pinned);
     void window_tile_maps(const Call& c, WinCtx& w) const;
     int run_prior_sampling(Call& c);

@@ -1,9 +1,11 @@
 // engine_vocoder.cpp — HiFiGAN (vits.cpp:583-644) over one window of frames: the 16-bit-operand path in the group layout of
 // conv16.hip and the exact fp32 path. Window-local lengths throughout (a whole-utterance run is one window).
 //
-// The two paths differ in layout and in which kernels exist, so they are two functions. What they share is stated once, up here: the stage
-// context (VocStage), how a resblock chain closes (ChainEnd + close_chain16 / close_chain32) and the fork / chain / join of the side streams
-// (Engine::rb_*). Inside each function a stage reads: decisions, upsampler, builders of the call structs, then the schedule that was chosen.
+// The two paths differ in layout and in which kernels exist, so they are two functions. Neither decides anything: which kernel a resblock runs on and how the
+// resblocks of a stage are scheduled is the host-only planner's answer (vocoder_plan.h: plan_voc_stage16 / plan_voc_stage32 over Engine::voc_policy), the one
+// Engine::plan_tile_maps and vits_op_resblock read too. What the paths share is stated once, up here: the stage context (VocStage), how a resblock chain closes
+// (ChainEnd + close_chain16 / close_chain32) and the fork / chain / join of the side streams (Engine::rb_*). Inside each function a stage reads: its plan, the
+// upsampler, the builders of the call structs, then the schedule the plan names. A launcher that refuses what the plan names is an error.
 #include "engine_internal.h"
 
 namespace vits {
@@ -98,13 +100,6 @@ void close_chain32(Call32& c, const ChainEnd& e, TensorRef own, TensorRef sum, f
     if (e.act) c.post_slope = lrelu;
 }
 
-// every conv of the resblock has a bias and packed 16-bit weights: what the whole-resblock kernels (rbblock16.hip) take
-bool rb_packed16(const ResBlockW& R) {
-    bool ok = true;
-    for (size_t d = 0; d < R.dil.size() && ok; ++d) ok = R.c1[d].bias && R.c2[d].bias && R.c1[d].wp16 && R.c2[d].wp16;
-    return ok;
-}
-
 }  // namespace
 
 // ---- the side streams of a stage's resblock chains (engine.h: side_[jj - 1] carries the jj-th chain enqueued) ---------------------------------
@@ -125,11 +120,22 @@ hipError_t Engine::rb_join(const RbChains& r) {
     return e;
 }
 
+// The handle's knobs and the call's state as the planner takes them. aligned stays true: run_vocoder_window32 tests its buffers once they are laid out.
+VocPolicy Engine::voc_policy(const Call& c) const {
+    VocPolicy p;
+    p.rb_streams = knobs.rb_streams, p.rb16_serial_max_frames = knobs.rb16_serial_max_frames, p.rb16_serial_min_frames = knobs.rb16_serial_min_frames;
+    p.rb32_sum3_max_frames = knobs.rb32_sum3_max_frames, p.lrelu_copy_minc = knobs.lrelu_copy_minc;
+    p.no_rbblock16 = knobs.no_rbblock16, p.no_fuse32 = knobs.no_fuse32, p.no_rbblock32 = knobs.no_rbblock32, p.no_rb_group = knobs.no_rb_group, p.rb_group_always = knobs.rb_group_always;
+    p.prof_on = prof.on, p.fuse16 = c.fuse16, p.arith_now = arith_now_, p.split_on = split_on(), p.split_planes = c.s2.sp_u != nullptr;
+    return p;
+}
+
 int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up, F = hp.flow_size, Lw = w.Lw;
     Call::S2& s2 = c.s2;
     const size_t nk = hp.rb_k.size();
+    const VocPolicy pol = voc_policy(c);
     // ---- 16-bit-operand vocoder in the group layout of conv16.hip -----------------------------------------------
     // Every conv input is a 16-bit tensor WRITTEN by its producer (leaky_relu and rounding fused into the writer's
     // epilogue: what the reference's leaky_relu node + fp16 im2col compute, vits.cpp:554,567,613 + custom-ops.h:684-690);
@@ -142,8 +148,7 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
     cur16.ts = c.lws;
     cur16.bs = (int64_t)hp.up_init * c.lws;
     // one to four utterances: conv_pre reads the fp32 flow output itself and runs on conv16_lat_kernel (conv16_lat.hip: no converter launch; same bits)
-    const bool pre_lat = !prof.on && F == dec_pre_.cin && conv16_lat_pre_wanted(dec_pre_, B, Lw);
-    if (pre_lat) {
+    if (plan_voc_pre_lat(dec_pre_, F, B, Lw, pol)) {
         HIP_OK(launch_conv16_lat_pre(dec_pre_, w.zwin, w.d_len[0], B, Lw, cur16, hp.lrelu, arith_now_, stream, c.spk));
     } else {
         prof.begin("to_group16", 0, 6.0 * F * (double)w.ssum[0], stream, true);
@@ -170,50 +175,10 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
         const Ref16 bul16 = s.ref16(s2.bul), bsum16 = s.ref16(s2.bs16);
         auto chain_end_of = [&](size_t j, bool side_by_side) { return chain_end(s, j, side_by_side, knobs.keep_stage_sum32, hp.lrelu); };
 
-        // ---- the schedule of this stage: every decision, before any launch ------------------------------------------------------------------
-        // narrow stages: each RESBLOCK as one kernel (rbblock16.hip: the fp32 stream stays in registers across its three pairs; bit-identical
-        // to the pair path). When every resblock of the stage runs that way nobody reads the 16-bit copy of the stage input.
-        bool blockrb[3] = {false, false, false};
-        bool all_block = nk <= 3;
-        for (size_t j = 0; j < nk && j < 3; ++j) {
-            const ResBlockW& R = U.rbs[j];
-            blockrb[j] = c.fuse16 && !knobs.no_rbblock16 && rbblock16_supported(C, R.k, R.dil.data(), (int)R.dil.size(), B, s.t_out) && rb_packed16(R);
-            all_block = all_block && blockrb[j];
-        }
-        // a resblock that is not one kernel: each pair as ONE kernel with t in LDS (rbpair16.hip; bit-identical to the two-kernel path) — all pairs of
-        // the resblock, or none: a two-kernel pair needs the second 16-bit buffer for its t, which the fused pairs use for the stream (mk_pair)
-        auto fused_pairs = [&](const ResBlockW& R) {
-            bool f = c.fuse16;
-            for (size_t d = 0; d < R.dil.size(); ++d) f = f && rbpair16_supported(C, R.k, R.dil[d]) && R.c1[d].bias && R.c2[d].bias;
-            if (!f || C < 128) return f;
-            // one or a few utterances on a wide stage: a fused pair is 28-32 blocks that each stream both convs' weights through one CU; two launches of
-            // conv16_lat_kernel deal the rows out over the chip (conv16_lat.hip; same bits)
-            bool lat = true;
-            for (size_t d = 0; d < R.dil.size(); ++d) lat = lat && conv16_lat_shape_ok(C, R.k, R.dil[d], B, s.t_out);
-            return !lat;
-        };
-        // (small windows — up to four 128-id utterances — run the three resblocks one behind the other: a fork and a join cost ~11 us each per
-        // stage, more than the overlap of these short kernels returns: f16 batch 4 2.33 -> 2.18 ms, batch 1 -1 %; from batch 8 on three streams win)
-        const bool par = knobs.rb_streams > 1 && nk >= 2 && nk <= 3 && !prof.on && (w.ssum[0] > knobs.rb16_serial_max_frames || w.ssum[0] < knobs.rb16_serial_min_frames);
-        // one or two utterances, every resblock of the stage a whole-resblock kernel: the kernels do NOT chain through the shared sum — each writes its own fp32
-        // output side by side with the others and launch_rb_sum3 adds them in the reference's order (rbblock16.hip; same bits; the C = 32 stage at batch 1:
-        // three chained 15-25 us kernels + two event hand-overs = 105 us, side by side + the sum ~40)
-        const bool sum3 = par && (all_block || !knobs.kernel.rb_sum3_block_only) && nk >= 2 && !knobs.kernel.no_rb_sum3 && w.ssum[0] < knobs.rb16_serial_min_frames;
-        // (side-by-side resblocks need no order: the LAST one, the longest chain (k = 11), is enqueued first and on the main stream, where it starts
-        // without the fork's cross-queue hand-over (10-40 us later on the side streams at batch 1); the short k = 3 chain takes the last side stream)
-        const RbChains rb{nk, par, sum3, sum3 && !knobs.kernel.rb_sum3_in_order};
-        // Side-by-side whole-resblock kernels (the C = 32 and C = 64 stages, k = 3 / 7 / 11) as ONE launch (rbblock16_group3_kernel) + the sum, on the main stream:
-        // no fork, no join (10-30 us of queue hand-over each at batch 1). The members are the kernels' bodies on the same operands: same bits. (The k = 11
-        // member need not pass rbblock16_supported — the group has its own grid rule — but its convs need what every member's need.)
-        bool group3 = sum3 && nk == 3 && c.fuse16 && !knobs.no_rbblock16 && blockrb[0] && blockrb[1] && rb_packed16(U.rbs[2]);
-        for (int m = 0; m < 3 && group3; ++m) {
-            const std::vector<int>& dl = U.rbs[m].dil;
-            group3 = dl.size() == 3 && dl[0] == 1 && dl[1] == 3 && dl[2] == 5;
-        }
-        if (group3) {
-            const int kts[3] = {U.rbs[0].k, U.rbs[1].k, U.rbs[2].k};
-            group3 = rbblock16_group3_supported(C, kts, B, s.t_out);
-        }
+        // ---- the schedule of this stage, before any launch (vocoder_plan.cpp states the rules and the measurements behind them) -------------------------
+        const VocStage16Plan pl = plan_voc_stage16(U, B, s.t_out, w.ssum[0], pol);
+        const bool par = pl.par, sum3 = pl.sum3;
+        const RbChains rb{nk, par, sum3, pl.longest_first};
 
         // ---- builders -----------------------------------------------------------------------------------------------------------------------
         // conv 1 / conv 2 of pair d of resblock j, on the buffers of chain q. `pingpong` (fused pairs): a fused block reads a halo of its neighbours' input
@@ -272,26 +237,18 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
             if (span) prof.end(stream);
             return 0;
         };
-        // Side-by-side resblocks whose convs all run on conv16_lat_kernel (the C = 256 stage at one to four utterances): the same-position convs of the three
-        // resblocks as ONE launch each (conv16_lat_group_kernel), six launches + the sum on the main stream — no fork, no join (each was 20-45 us of queue
-        // hand-over per stage at batch 1). Same kernels' bodies on the same operands: same bits. run = false only asks whether the kernels take every launch.
-        auto lat_group = [&](bool run) -> int {
+        // the same-position convs of the three resblocks as ONE launch each (conv16_lat_group_kernel), on the main stream
+        auto lat_group = [&]() -> int {
             for (size_t d = 0; d < U.rbs[0].dil.size(); ++d) {
                 const PackedConv* w1[3] = {&U.rbs[0].c1[d], &U.rbs[1].c1[d], &U.rbs[2].c1[d]};
                 const PackedConv* w2[3] = {&U.rbs[0].c2[d], &U.rbs[1].c2[d], &U.rbs[2].c2[d]};
                 Conv16Call a[3], bb[3];
                 for (size_t j = 0; j < 3; ++j) mk_pair(j, d, false, a[j], bb[j]);
-                if (!run) {
-                    if (!conv16_lat_group_wanted(w1, a) || !conv16_lat_group_wanted(w2, bb)) return -1;
-                    continue;
-                }
                 HIP_OK(launch_conv16_lat_group(w1, a, arith_now_, stream));
                 HIP_OK(launch_conv16_lat_group(w2, bb, arith_now_, stream));
             }
             return 0;
         };
-        const bool lat3 = sum3 && nk == 3 && !group3 && c.fuse16 && !blockrb[0] && !blockrb[1] && !blockrb[2] && U.rbs[0].dil == U.rbs[1].dil && U.rbs[0].dil == U.rbs[2].dil &&
-                          lat_group(false) == 0;
 
         // ---- the upsampler ------------------------------------------------------------------------------------------------------------------
         {
@@ -308,11 +265,11 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
             cu.yg = s2.bu;
             cu.g_bs = s.g_bs();
             cu.g_ts = s.ts;
-            if (!all_block) {
+            if (!pl.all_block) {
                 cu.y16 = bul16;
                 cu.y16_slope = hp.lrelu;
             }
-            const double ct_bytes = 2.0 * U.up.cin * (double)s.sum_in + (all_block ? 4.0 : 6.0) * n_out + (double)U.up.bytes16;
+            const double ct_bytes = 2.0 * U.up.cin * (double)s.sum_in + (pl.all_block ? 4.0 : 6.0) * n_out + (double)U.up.bytes16;
             if (convt16_stream_supported(U.up)) {
                 // the upsampler as a streaming kernel (convt16.hip: every phase of a tile of input positions in one block; bit-identical)
                 if (prof.on) {
@@ -330,7 +287,7 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
         cur16 = bsum16;
 
         // ---- the resblocks: the two single-stream forms of side-by-side resblocks, else one chain of launches per resblock ------------------
-        if (group3) {
+        if (pl.group3) {
             const PackedConv* w1[3][3];
             const PackedConv* w2[3][3];
             RbBlock16Call f[3];
@@ -342,8 +299,8 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
             if (stage_sum(false)) return -1;
             continue;
         }
-        if (lat3) {
-            if (lat_group(true) || stage_sum(false)) return -1;
+        if (pl.lat3) {
+            if (lat_group() || stage_sum(false)) return -1;
             continue;
         }
         if (par) HIP_OK(rb_fork(nk - 1));
@@ -352,7 +309,8 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
             const ResBlockW& R = U.rbs[j];
             const size_t nd = R.dil.size();
             hipStream_t sj = rb_stream(rb, jj);
-            if (j < 3 && blockrb[j]) {
+            const RbKernel kernel = rb_kernel16_of(pl, U, j, B, s.t_out, pol);
+            if (kernel == RbKernel::Block) {
                 const PackedConv *w1[3], *w2[3];
                 R.pairs3(w1, w2);
                 const RbBlock16Call f = mk_block(j);
@@ -369,7 +327,7 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
                 HIP_OK(rb_chain_done(rb, j, sj));
                 continue;
             }
-            const bool fuse = fused_pairs(R);
+            const bool fuse = kernel == RbKernel::Pairs;
             for (size_t d = 0; d < nd; ++d) {
                 const bool last = d + 1 == nd;
                 Conv16Call c1, c2;
@@ -415,23 +373,15 @@ int Engine::run_vocoder_window16(Call& c, WinCtx& w) {
     return 0;
 }
 
-// The kernel the exact-fp32 vocoder gives a resblock of a C-channel stage, by its shape, its weights and the knobs: 2 = the whole-resblock kernel (rbblock32.hip),
-// 1 = one fused kernel per conv pair (rbpair32.hip; all pairs or none), 0 = two launches per pair. Stated once: run_vocoder_window32 schedules by it and
-// plan_tile_maps (engine.cpp) plans the lists of existing tiles for the widths of the same kernels.
-int Engine::rb32_kind(const ResBlockW& R, int C) const {
-    bool pairs = !knobs.no_fuse32;
-    for (size_t d = 0; d < R.dil.size() && pairs; ++d) pairs = rbpair32_supported(C, R.k, R.dil[d]) && R.c1[d].bias && R.c2[d].bias;
-    if (!pairs) return 0;
-    bool block = !knobs.no_rbblock32 && rbblock32_supported(C, R.k, R.dil.data(), (int)R.dil.size());
-    for (size_t d = 0; d < R.dil.size() && block; ++d) block = R.c1[d].wp && R.c2[d].wp;
-    return block ? 2 : 1;
-}
-
 int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
     std::string& err = c.err;
     const int B = c.B, n_up = c.n_up, Lw = w.Lw;
     Call::S2& s2 = c.s2;
     const size_t nk = hp.rb_k.size();
+    VocPolicy pol = voc_policy(c);
+    // the 16-byte loads of the fused fp32 kernels (the arena aligns every buffer and the strides are rounded up to 32: a guard)
+    pol.aligned = ((reinterpret_cast<uintptr_t>(s2.bu) | reinterpret_cast<uintptr_t>(s2.by[0]) | reinterpret_cast<uintptr_t>(s2.bt[0])) & 15) == 0;
+    for (int i = 0; i < n_up; ++i) pol.aligned = pol.aligned && (c.sts[i + 1] & 3) == 0;
     TensorRef h0 = make_ref(s2.h0, hp.up_init, c.lws);
     {
         ConvCall cv;
@@ -466,85 +416,11 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             return r;
         };
 
-        // ---- the schedule of this stage: every decision, before any launch ------------------------------------------------------------------
-        // The resblocks of a stage (vits.cpp:622-635) are independent chains of `nd` conv pairs on the same input that meet only in the sum. Only the
-        // LAST launch of each chain touches the shared sum, and those run in the reference's order (RB0, += RB1, += RB2 and the 1/num_kernels scale)
-        // on the main stream. Everything before them is scheduled one of two ways:
-        //   grouped  — the same-position convs of the resblocks as ONE launch (conv_group_kernel: 11-tap blocks first, 3-tap blocks
-        //              last, one grid tail instead of three); resblocks that run as fused pairs (rbpair32) keep their own chain;
-        //   separate — every resblock its own chain of launches, on three streams (or serialised under the profiler, whose
-        //              per-kernel events need kernels that do not overlap).
-        // Same kernels bodies, same operands, same order of the additions either way: the PCM is bit-identical (GPU test).
-        const bool lcopy = C >= knobs.lrelu_copy_minc;  // activated copy of the stream for the first conv of each pair (see mk_c1)
-        auto al16 = [](const TensorRef& t) { return (reinterpret_cast<uintptr_t>(t.p) & 15) == 0 && (t.cs & 3) == 0 && (t.bs & 3) == 0; };
-        // which resblocks run as fused pairs (narrow stages; all pairs of a resblock or none). rbpair32 and the grouped launch are fp32
-        // kernels that do not go through conv(): in a 16-bit arithmetic mode on this (converter) path they would silently compute the
-        // wide-stage resblocks in fp32 — not the arithmetic that was asked for, and other bits with the profiler on than off.
-        const bool exact32 = arith_now_ == VITS_ARITH_F32;
-        bool fusedrb[3] = {false, false, false};
-        for (size_t j = 0; j < nk && j < 3; ++j) {
-            const ResBlockW& R = U.rbs[j];
-            // (rb32_kind: the shape, weights and knobs — the rule plan_tile_maps reads too; here what only the call knows: the arithmetic, the buffers' alignment)
-            bool f = exact32 && rb32_kind(R, C) >= 1 && al16(bu) && (reinterpret_cast<uintptr_t>(s2.by[0]) & 15) == 0 && (reinterpret_cast<uintptr_t>(s2.bt[0]) & 15) == 0 && (s.ts & 3) == 0;
-            // VITS_ARITH_F32_SPLIT: a resblock the split kernels take (conv_split.hip: C >= 128, any tap count) runs un-fused — the C = 128, k = 3 pairs, fused in
-            // the exact mode, are 1.56 ms each there and 0.9 as two split convs
-            if (f && split_on() && s2.sp_u && C >= 128) {
-                bool sp = true;
-                for (size_t d = 0; d < R.dil.size() && sp; ++d) sp = conv_split_supported(R.c1[d], R.dil[d]) && conv_split_supported(R.c2[d], 1);
-                if (sp) f = false;
-            }
-            fusedrb[j] = f;
-        }
-        // narrow stages, 3-tap resblocks: the WHOLE resblock as one kernel (rbblock32.hip: the stream stays in registers across its three pairs;
-        // bit-identical to the fused pairs). It carries the accumulation into the shared sum itself, so it is launched where the resblock's last
-        // launch would be.
-        bool blockrb[3] = {false, false, false};
-        for (size_t j = 0; j < nk && j < 3; ++j) {
-            const ResBlockW& R = U.rbs[j];
-            blockrb[j] = fusedrb[j] && rb32_kind(R, C) == 2;
-        }
-        // VITS_ARITH_F32_SPLIT: the un-fused resblocks of a wide stage run their convs on the bf16 matrix cores with split operands (conv_split.hip): their
-        // inputs are three-plane tensors written by the producing epilogue — the stage input by a converter launch —, the fp32 stream and the sum stay put.
-        bool splitrb[3] = {false, false, false};
-        bool any_split = false;
-        for (size_t j = 0; j < nk && j < 3 && split_on() && s2.sp_u; ++j) {
-            const ResBlockW& R = U.rbs[j];
-            bool f = !fusedrb[j] && C >= 128;
-            for (size_t d = 0; d < R.dil.size() && f; ++d) f = conv_split_supported(R.c1[d], R.dil[d]) && conv_split_supported(R.c2[d], 1);
-            splitrb[j] = f;
-            any_split = any_split || f;
-        }
-        // grouped schedule: at least two un-fused resblocks with distinct tap counts of {11, 7, 3}, the same dilation list, on the 128 x 128 tile
-        // (measured, batch 64 x 128 ids: serialised launches 79.7 ms per step, grouped 79.1, three streams 76.8 — kernels of DIFFERENT
-        // launches share a CU, which blocks of one launch do not, so the streams win where they can be used: the
-        // grouped schedule is for the single-stream case, i.e. under the per-kernel profiler; VITS_RB_GROUP=1 forces it)
-        bool grouped = exact32 && !any_split && !knobs.no_rb_group && nk >= 2 && nk <= 3 && knobs.rb_streams > 1 && (prof.on || knobs.rb_group_always);
-        {
-            int members = 0, seen = 0;
-            for (size_t j = 0; j < nk && grouped; ++j) {
-                const ResBlockW& R = U.rbs[j];
-                if (R.dil != U.rbs[0].dil) grouped = false;
-                if (fusedrb[j]) continue;
-                const int bit = R.k == 11 ? 1 : R.k == 7 ? 2 : R.k == 3 ? 4 : 0;
-                if (!bit || (seen & bit)) grouped = false;
-                seen |= bit;
-                ConvCall shape;  // (what the tile rule looks at: small grids step down from the 128 x 128 tile and are not grouped)
-                shape.batch = B;
-                shape.t_in = shape.t_out = s.t_out;
-                for (size_t d = 0; d < R.dil.size() && grouped; ++d)
-                    grouped = conv_group_supported(R.c1[d], R.dil[d]) && conv_group_supported(R.c2[d], 1) && plan_conv(R.c1[d], shape).tile == TILE_128x128;
-                ++members;
-            }
-            grouped = grouped && members >= 2;
-        }
-        const bool par = knobs.rb_streams > 1 && nk >= 2 && nk <= 3 && !prof.on;
-        // separate schedule, up to eight 128-id utterances (small grids): every resblock writes its own output — s2.by[j] — and launch_rb_sum3_std adds them in
-        // the reference's order: no resblock's last launch waits for the previous resblock's; same bits. The last — longest — chain is enqueued first and
-        // on the main stream (as the 16-bit path). (The last pair of a fused resblock reads bt and writes by: nd is odd.)
-        bool odd = true;
-        for (size_t j = 0; j < nk; ++j) odd = odd && (U.rbs[j].dil.size() & 1);
-        const bool sum3 = !grouped && par && odd && !any_split && !knobs.kernel.no_rb_sum3 && !knobs.kernel.no_rb_sum3_f32 && w.ssum[0] < knobs.rb32_sum3_max_frames;
-        const RbChains rb{nk, par, sum3, sum3};
+        // ---- the schedule of this stage, before any launch (vocoder_plan.cpp states the rules and the measurements behind them) -------------------------
+        const VocStage32Plan pl = plan_voc_stage32(U, B, s.t_out, w.ssum[0], pol);
+        const bool lcopy = pl.lcopy, grouped = pl.grouped, par = pl.par, sum3 = pl.sum3;
+        const RbChains rb{nk, par, sum3, sum3};  // (side by side: the last — longest — chain is enqueued first and on the main stream, as the 16-bit path)
+        auto is = [&](size_t j, RbKernel k) { return pl.kernel_of(j) == k; };
 
         // ---- the upsampler ------------------------------------------------------------------------------------------------------------------
         {
@@ -569,7 +445,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             HIP_OK(conv("hifigan_upsample_convT", U.up, cu));
         }
         cur = bsum;
-        if (any_split) {
+        if (pl.any_split) {
             prof.begin("split_planes", 0, 10.0 * n_out, stream);
             HIP_OK(launch_split_planes(bu, C, s.len_out, B, s.t_out, hp.lrelu, SR(s2.sp_u), stream));
             prof.end(stream);
@@ -624,7 +500,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             c1.slope = hp.lrelu;
             c1.post_act = 2;  // bt = leaky_relu(conv1(...)): what the second conv consumes (vits.cpp:556-566)
             c1.post_slope = hp.lrelu;
-            if (j < 3 && splitrb[j]) {
+            if (is(j, RbKernel::Split)) {
                 // split arithmetic: the input is the planes of leaky_relu(stage input / stream), the output ONLY the planes of leaky_relu(t)
                 c1.x = TensorRef();
                 c1.xs3 = d > 0 ? SR(s2.sp_y[q]) : SR(s2.sp_u);
@@ -649,7 +525,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             c2.dil = 1;
             c2.pad_l = (R.k - 1) / 2;
             c2.res = d == 0 ? bu : by;  // residual add (vits.cpp:578)
-            if (j < 3 && splitrb[j]) {
+            if (is(j, RbKernel::Split)) {
                 c2.xs3 = SR(s2.sp_t[q]);
                 c2.y2 = nullptr;
                 c2.ys3 = Split3Ref();
@@ -695,11 +571,11 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             // fused resblocks: their chain up to (not including) the last pair, beside the group — on a side stream unless the profiler
             // needs kernels that do not overlap
             bool any_fused = false;
-            for (size_t j = 0; j < nk; ++j) any_fused = any_fused || (fusedrb[j] && !blockrb[j]);
+            for (size_t j = 0; j < nk; ++j) any_fused = any_fused || is(j, RbKernel::Pairs);
             hipStream_t sf = (any_fused && !prof.on) ? side_[0] : stream;
             if (sf != stream) HIP_OK(rb_fork(1));
             for (size_t j = 0; j < nk; ++j)
-                if (fusedrb[j] && !blockrb[j])
+                if (is(j, RbKernel::Pairs))
                     for (size_t d = 0; d + 1 < nd; ++d)
                         if (run_fused(j, d, sf)) return -1;
             if (sf != stream) HIP_OK(hipEventRecord(ev_done_[0], sf));
@@ -709,7 +585,7 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
                 int n = 0;
                 double flop = 0, bytes = 0;
                 for (size_t j = 0; j < nk; ++j) {
-                    if (fusedrb[j]) continue;
+                    if (pl.fused(j)) continue;
                     const ResBlockW& R = U.rbs[j];
                     gw[n] = second ? &R.c2[d] : &R.c1[d];
                     gc[n] = second ? mk_c2(j, d) : mk_c1(j, d);
@@ -734,9 +610,9 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             // the last launch of every resblock, in the reference's order of the additions
             if (sf != stream) HIP_OK(hipStreamWaitEvent(stream, ev_done_[0], 0));
             for (size_t j = 0; j < nk; ++j) {
-                if (blockrb[j]) {
+                if (is(j, RbKernel::Block)) {
                     if (run_block(j, stream)) return -1;
-                } else if (fusedrb[j]) {
+                } else if (is(j, RbKernel::Pairs)) {
                     if (run_fused(j, nd - 1, stream)) return -1;
                 } else {
                     HIP_OK(conv("hifigan_resblock_conv", U.rbs[j].c2[nd - 1], mk_c2(j, nd - 1), stream));
@@ -751,8 +627,8 @@ int Engine::run_vocoder_window32(Call& c, WinCtx& w) {
             const ResBlockW& R = U.rbs[j];
             const size_t nd = R.dil.size();
             hipStream_t sj = rb_stream(rb, jj);
-            const bool fuse_rb = j < 3 && fusedrb[j];
-            if (j < 3 && blockrb[j]) {
+            const bool fuse_rb = is(j, RbKernel::Pairs);
+            if (is(j, RbKernel::Block)) {
                 // (the kernel adds into the shared sum: it takes the place of the resblock's last launch in the chain of additions)
                 HIP_OK(rb_chain_wait(rb, j, sj));
                 if (run_block(j, sj)) return -1;
