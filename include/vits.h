@@ -661,6 +661,72 @@ VITS_API int vits_model_process_joined(vits_model* model, const int32_t* ids, co
 VITS_API int64_t vits_model_last_joins(vits_model* model, int64_t* dst, size_t cap);
 VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_speak_opts* opts, vits_batch_result* out);
 
+/* ---- a stated pitch: a ratio per utterance, varispeed on the device -----------------------------------------------------------------------
+ * VITS has no F0 input. What it has is a free time stretch: speaking slower by p is the duration predictor's own length scale. So an utterance
+ * with pitch ratio p is (1) spoken at the speaking rate r' = (float)((double)rate / (double)p) and (2) played back p times faster by the
+ * band-limited interpolator below, at the model's rate, in front of the edges stage: the delivered duration is what it would have been without a
+ * pitch, and every frequency of the voice is multiplied by p. Pitch and formants move together, as with any varispeed: fine for the 2 or 3
+ * semitones the control is used for. Formant-preserving shifting is not built.
+ *
+ * The definition. p is a float in [0.5, 2]; vits_pitch_ratio(semitones) = (float)exp2((double)semitones / 12); p = 1 means off. All positions are
+ * integers, so device, host and any restatement agree on every index:
+ *   P = p 2^24 (an exact integer for every float in the range). A row of N samples gives N' = ceil(N 2^24 / P) samples.
+ *   Output m sits at t = m P (64-bit): n0 = t >> 24, f = t & (2^24 - 1).
+ *   Prototype: the resampler's Kaiser-windowed sinc (Z = 32 zero crossings, beta = 9, rolloff 0.92), tabulated at Q = 256 points per zero crossing:
+ *     G[i] = fp32(g0(i / Q)), g0(u) = sinc(u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta), i = 0 .. Z Q - 1;  G[Z Q] = G[Z Q + 1] = 0
+ *     D[i] = G[i + 1] - G[i] in fp32, i = 0 .. Z Q;  D[Z Q + 1] = 0.        Both tables are public: vits_pitch_table.
+ *   Per row: S0 = 15435038 (= floor(0.92 2^24)); S = S0 when P <= 2^24, else (S0 << 24) / P (integer division); a = S / 2^24 (exact in fp32);
+ *     R = ceil(2^29 / S), K = 2 R + 1: 71 taps up to p = 1, 141 at p = 2.
+ *   Tap k of output m: tau = |(k - R) 2^24 - f|, u = (tau S) >> 24, i = u >> 16, fr = (u & 65535) 2^-16;
+ *     h = 0 where i >= Z Q, else h = a fmaf(fr, D[i], G[i]).
+ *   y[m] is ONE ascending chain: acc = 0; acc = fmaf(h, x[n0 - R + k], acc) for k = 0 .. K - 1, x = 0 outside the row's own [0, N).
+ *   A row with P = 2^24 is copied bit for bit (the filter at p = 1 is a 0.92-Nyquist low-pass, not an identity).
+ * Rows are finite: where h = 0 the device still runs fmaf(+0, x, acc), so an Inf or NaN sample poisons the outputs within R samples of it even where its
+ * weight is 0 (vits_pitch_host skips such a tap); for finite rows the bits are the same either way.
+ * Nothing about tiles, batch position or neighbouring rows enters a sample. Restated in float64 (tests/pitch_ref.py): a 440 Hz tone comes out
+ * within 0.03 Hz of 440 p from -12 to +12 semitones; tones whose shifted frequency passes Nyquist come out at -95 dB or lower; the table with
+ * linear interpolation differs from the exact sinc by at most 3.3e-5 of the output RMS on white noise.
+ *
+ * In a call. The model value (vits_model_set_pitch, initially 1) holds for every utterance of every call. vits_model_set_pitch_ratios(model, ratios,
+ * n) gives the NEXT call one ratio per utterance instead (host [n], copied at once); NULL or n = 0 drops them. Exactly these calls take them, as the
+ * first thing they do once the engine has the call, and they are gone when the call returns, whether it succeeded or not: vits_model_process,
+ * _process_ids, _process_batch, _submit_batch, _process_joined, _speak, _convert, _convert_batch, _align and _align_batch. A call that never reaches
+ * the engine — a NULL model, ids, PCM or text, an empty input, a text the tokenizer refuses, "model busy" from inside on_chunk — leaves them where
+ * they are. Nothing else touches them: not vits_model_wait or _sync, not a setter, a getter, a tap or a report. A caller whose call may have
+ * been refused that early drops them itself before it goes on (the Python wrappers do). vits_process_opts keeps its size: like every delivery
+ * setting, pitch is stated on the handle, not in a field. Taken by vits_model_process, _process_ids, _process_batch, _submit_batch / _wait (bit for bit
+ * what _process_batch gives) and vits_model_process_joined (per utterance: a programme may mix pitches); n must be the call's batch. vits_model_speak
+ * takes the model value only and refuses given ratios as it refuses the per-utterance arrays. For an utterance with p_b != 1
+ * the call is, bit for bit, the same call with speaking rate r'_b — refused, naming the utterance, when r'_b leaves [0.1, 10] — followed by the
+ * varispeed of its vocoder row. Everything behind the vocoder sees the final audio: edges, join, level, limiter, the output resampler, PCM16.
+ * lengths[] (and so frames_only, the out_device_stride check and a joined call's bounds) derive from N'; frames[] and durations_out stay the
+ * model's frames: token t of durations_out starts at sum(d[0 .. t)) * hop * 2^24 / P model-rate samples (with the edges stage on, minus a plus
+ * Pl as in vits_model_hop's note). Taken with vocoder_chunk_frames (without on_chunk), out_device and skip_host_copy.
+ * Refused before anything is queued, each with a message: on_chunk or async with any ratio != 1 (streaming pitch is not built); fixed_duration >
+ * 0 or duration_override on an utterance with ratio != 1 (the stretch is the duration predictor's); a ratio that is not finite or outside [0.5,
+ * 2]; given ratios in vits_model_convert_batch and vits_model_align_batch, where the model value has no effect either, as with prosody.
+ * A vits_model_process_batch call that shifts is never split across the front-end stream inside the call (one launch serves the whole batch and the
+ * report has a row per utterance); its bits are the unsplit call's either way.
+ * Tap "waveform_pitch" [1][N'] is the stage's output; "waveform" stays the vocoder's row. vits_model_last_pitch writes int64 [B][3] = {P, N, N'}
+ * of the most recently completed call, 0 rows when it shifted nothing; returns the number of rows, -1: model NULL. With every ratio 1 nothing is
+ * queued and nothing is allocated: every bit and vits_model_weight_bytes are what they were. The interleaved table (64 KiB) is uploaded by the
+ * first call that shifts, kept with the handle and counted in vits_model_weight_bytes.
+ *
+ * vits_model_set_pitch: 0, or -1 + message with the handle unchanged (a ratio that is not finite or outside [0.5, 2]). vits_model_set_pitch_ratios: 0,
+ * or -1 + message (n < 0, ratios NULL with n > 0); the values are checked by the call that takes them, whose message names the utterance.
+ * Host only, no device needed. vits_pitch_plan: 0 and P, S, R, N' of a row of n samples (each pointer optional), or -1 + message (a ratio that
+ * is not finite or outside [0.5, 2], n outside [0, 2^30]). vits_pitch_table: writes [2][Z Q + 2] floats, G then D, when cap holds them (dst may
+ * be NULL with cap 0 to ask for the size); returns 2 (Z Q + 2), -1 on failure. vits_pitch_host: the definition evaluated in double,
+ * sequentially, from the same two tables: y (cap >= N' doubles) gets the row; returns N', -1 + message on failure. */
+VITS_API float vits_pitch_ratio(float semitones);
+VITS_API int vits_pitch_plan(float ratio, int64_t n, int64_t* P, int64_t* S, int32_t* R, int64_t* n_out);
+VITS_API int64_t vits_pitch_table(float* dst, size_t cap);
+VITS_API int64_t vits_pitch_host(const float* x, int64_t n, float ratio, double* y, size_t cap);
+VITS_API int vits_model_set_pitch(vits_model* model, float ratio);
+VITS_API int vits_model_get_pitch(const vits_model* model, float* ratio);
+VITS_API int vits_model_set_pitch_ratios(vits_model* model, const float* ratios, int32_t n);
+VITS_API int64_t vits_model_last_pitch(vits_model* model, int64_t* dst, size_t cap);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -1177,6 +1243,15 @@ VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, in
  * output row. */
 VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens,
                               float* y, int64_t y_stride);
+
+/* The varispeed kernel (see "a stated pitch" for the definition) on a ragged batch with a ratio per row: x host [batch][x_stride], lens host
+ * [batch] (0 <= lens[b] <= x_stride; NULL: every row has x_stride), ratios host [batch], y host [batch][y_stride], n_out host [batch] = N' of
+ * every row. The device copy of x keeps the caller's stride and the caller's alignment within 16 bytes and holds 0xFF bytes behind every
+ * lens[b], so a read past a row shows; the device copy of y holds the vits_op_set_output_fill byte before the kernel runs and comes back whole,
+ * so a write behind N' shows. Refused (-1 + message): what vits_pitch_plan refuses (naming the row), a length outside its row, a y_stride
+ * shorter than the longest output row. */
+VITS_API int vits_op_pitch(int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const float* ratios, float* y, int64_t y_stride,
+                           int64_t* n_out);
 
 /* The levelling kernels (see vits_model_set_level for the definition) on a ragged batch, staged exactly as the engine stages it: x host
  * [batch][x_stride] at `rate`, lens host [batch] (0 <= lens[b] <= x_stride; NULL: every row has x_stride). The device copy of x holds NaNs

@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_level", "vits_model_get_level", "vits_model_last_levels", "vits_loudness_plan", "vits_loudness_host", "vits_op_level",
     "vits_model_set_limiter", "vits_model_get_limiter", "vits_model_last_limits", "vits_limiter_plan", "vits_limiter_host", "vits_op_limit",
     "vits_model_set_edges", "vits_model_get_edges", "vits_model_last_edges", "vits_edges_plan", "vits_edges_host", "vits_op_edges",
+    "vits_pitch_ratio", "vits_pitch_plan", "vits_pitch_table", "vits_pitch_host", "vits_op_pitch",
+    "vits_model_set_pitch", "vits_model_get_pitch", "vits_model_set_pitch_ratios", "vits_model_last_pitch",
     "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences", "vits_model_process_joined", "vits_model_last_joins", "vits_model_speak",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
@@ -386,6 +388,24 @@ def lib():
     L.vits_model_set_edges.argtypes = [vp, C.POINTER(EdgesDesc)]
     L.vits_model_get_edges.restype = i32
     L.vits_model_get_edges.argtypes = [vp, C.POINTER(EdgesDesc)]
+    L.vits_pitch_ratio.restype = C.c_float
+    L.vits_pitch_ratio.argtypes = [C.c_float]
+    L.vits_pitch_plan.restype = i32
+    L.vits_pitch_plan.argtypes = [C.c_float, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
+    L.vits_pitch_table.restype = i64
+    L.vits_pitch_table.argtypes = [f32p, sz]
+    L.vits_pitch_host.restype = i64
+    L.vits_pitch_host.argtypes = [vp, i64, C.c_float, vp, sz]
+    L.vits_op_pitch.restype = i32
+    L.vits_op_pitch.argtypes = [i32, vp, i64, vp, vp, vp, i64, vp]
+    L.vits_model_set_pitch.restype = i32
+    L.vits_model_set_pitch.argtypes = [vp, C.c_float]
+    L.vits_model_get_pitch.restype = i32
+    L.vits_model_get_pitch.argtypes = [vp, C.POINTER(C.c_float)]
+    L.vits_model_set_pitch_ratios.restype = i32
+    L.vits_model_set_pitch_ratios.argtypes = [vp, vp, i32]
+    L.vits_model_last_pitch.restype = i64
+    L.vits_model_last_pitch.argtypes = [vp, vp, sz]
     L.vits_model_last_edges.restype = i64
     L.vits_model_last_edges.argtypes = [vp, vp, sz]
     L.vits_edges_plan.restype = i32
@@ -828,6 +848,53 @@ class Model:
             acc = (acc + weights[k] * self.speaker_embedding(i)).astype(np.float32)
         return self.add_voices(acc)[0]
 
+    # -- a stated pitch: the model-level ratio (vits_model_set_pitch) ------------------------------------------------------------
+    @property
+    def pitch(self):
+        """the model-level pitch ratio (1 = off): what every utterance a call gives no pitch_ratio for is shifted by"""
+        v = C.c_float()
+        if lib().vits_model_get_pitch(self._h, C.byref(v)) != 0:
+            raise VitsError(last_error())
+        return float(v.value)
+
+    def set_pitch(self, ratio=1.0):
+        """vits_model_set_pitch: a ratio in [0.5, 2] (pitch_ratio(semitones)); 1 switches the stage off"""
+        if lib().vits_model_set_pitch(self._h, float(ratio)) != 0:
+            raise VitsError(last_error())
+
+    def set_pitch_ratios(self, ratios=None):
+        """vits_model_set_pitch_ratios: one ratio per utterance for the NEXT call on this handle (None drops what was given); the pitch_ratio keyword of
+        process_batch, submit_batch and process_joined does this"""
+        a = None if ratios is None else np.ascontiguousarray(ratios, dtype=np.float32).ravel()
+        if lib().vits_model_set_pitch_ratios(self._h, _ptr(a), 0 if a is None else a.size) != 0:
+            raise VitsError(last_error())
+
+    def _with_pitch(self, pitch_ratio, B, c_call):
+        """The pitch_ratio keyword of a call: runs c_call() (the library call itself, with nothing of Python's between the two) with the ratios given to
+        the handle and returns what it returns. A scalar is broadcast to the batch; None gives nothing (the model value). Whatever happens, no ratio given
+        here is left on the handle for a later call."""
+        if pitch_ratio is None:
+            return c_call()
+        if np.ndim(pitch_ratio) and np.size(pitch_ratio) not in (1, B):
+            raise ValueError("pitch_ratio needs a scalar or one value per utterance")
+        self.set_pitch_ratios(np.broadcast_to(np.asarray(pitch_ratio, np.float32).ravel(), (B,)))
+        try:
+            return c_call()
+        finally:
+            self.set_pitch_ratios(None)
+
+    def last_pitch(self):
+        """vits_model_last_pitch: int64 [B, 3] = (P, N, N') of the most recently completed call, or None when it shifted nothing"""
+        n = lib().vits_model_last_pitch(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n, 3), np.int64)
+        if lib().vits_model_last_pitch(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
+
     # -- prosody: the transformers.VitsModel attributes, the model-level values (vits_model_set_prosody) --------------------------
     def get_prosody(self):
         """(speaking_rate, noise_scale, noise_scale_duration) the reference entry points and calls without per-utterance values use"""
@@ -1015,14 +1082,16 @@ class Model:
     def process_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321,
                       noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False, out_device=None,
                       out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False, noise_seed_offsets=None, keep_pcm=True,
-                      speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None, durations_out=None):
+                      speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None, durations_out=None,
+                      pitch_ratio=None):
         """ids: int32 [B, id_stride]. Returns (list of per-utterance PCM arrays or None, lengths, frames).
         vocoder_chunk_frames > 0 runs the vocoder window by window (bit-identical PCM, bounded activations);
         on_chunk(utt, offset, pcm ndarray) is then called as each window's samples reach the host (return True to abort).
         speaker_ids: one speaker per utterance (-1 = none; None = the model default, set_speaker).
         speaking_rate / noise_scale / noise_scale_duration: a scalar for the whole batch or one value per utterance (None = the model values);
         duration_override: int32 [B, id_stride] (>= 0: the token's frames, -1: the prediction); durations_out: a caller-owned int32 [B, id_stride]
-        array that receives every token's frames."""
+        array that receives every token's frames. pitch_ratio: a scalar or one ratio per utterance in [0.5, 2] (pitch_ratio(semitones); None = the
+        model value, set_pitch): the utterance is spoken slower by it and played back faster by it, on the device."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         if ids.ndim == 1:
             ids = ids[None, :]
@@ -1033,7 +1102,7 @@ class Model:
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
         cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
-        if lib().vits_model_process_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), C.byref(res)) != 0:
+        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_process_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), C.byref(res))) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1043,8 +1112,9 @@ class Model:
     def _joined_opts(B, stride, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False,
                      out_device=None, out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False,
                      noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None,
-                     durations_out=None):
-        """the options of process_batch's keywords (what a joined call refuses travels too, so that the library says why) -> (opts, keep, cb_error)"""
+                     durations_out=None, pitch_ratio=None):
+        """the options of process_batch's keywords (what a joined call refuses travels too, so that the library says why) -> (opts, keep, cb_error).
+        pitch_ratio is no field of the options: the caller gives it to the handle (Model._with_pitch)"""
         o, keep = _opts(B, mode, noise_kind, noise_seed, noise_dur, noise_prior, fixed_duration, collect_taps, out_device, out_device_stride, skip_host_copy,
                         async_, vocoder_chunk_frames, frames_only, noise_seed_offsets, speaker_ids)
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
@@ -1066,7 +1136,8 @@ class Model:
                 raise ValueError("%s needs one entry per utterance" % name)
         o, keep, cb_error = self._joined_opts(B, stride, **kw)
         res = BatchResult()
-        if lib().vits_model_process_joined(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), _ptr(tr), _ptr(gp), C.byref(res)) != 0:
+        if self._with_pitch(kw.get("pitch_ratio"), B,
+                            lambda: lib().vits_model_process_joined(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), _ptr(tr), _ptr(gp), C.byref(res))) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1084,7 +1155,8 @@ class Model:
         so.process = C.pointer(o)
         res = BatchResult()
         raw = None if text is None else text.encode("utf-8")
-        if lib().vits_model_speak(self._h, raw, C.byref(so), C.byref(res)) != 0:
+        # (given ratios are refused by the library: one per utterance, and the text decides how many there are)
+        if self._with_pitch(kw.get("pitch_ratio"), max(1, np.size(kw.get("pitch_ratio"))), lambda: lib().vits_model_speak(self._h, raw, C.byref(so), C.byref(res))) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1124,6 +1196,7 @@ class Model:
         if lens.size != B:
             raise ValueError("lengths needs one entry per utterance")
         sp = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,))) for v in (src, tgt)]
+        pitch_ratio = refused.pop("pitch_ratio", None)
         fields, keep = _refused_fields(refused, B)
         o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, out_device=out_device,
                         out_device_stride=out_device_stride, skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames,
@@ -1133,7 +1206,8 @@ class Model:
             setattr(o, field, v)
         cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
-        if lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o), C.byref(res)) != 0:
+        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o),
+                                                                                    C.byref(res))) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1176,6 +1250,7 @@ class Model:
         sp = np.ascontiguousarray(np.broadcast_to(np.asarray(speakers, np.int32), (B,)))
         own = {k: refused.pop(k) for k in ("out_device", "skip_host_copy", "vocoder_chunk_frames") if k in refused}
         on_chunk = refused.pop("on_chunk", None)
+        pitch_ratio = refused.pop("pitch_ratio", None)
         fields, keep = _refused_fields(refused, B, noise_scale_arg="noise_scales")
         o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, noise_seed_offsets=noise_seed_offsets, **own)
         keep += kept
@@ -1186,8 +1261,8 @@ class Model:
         durations = np.zeros((B, id_stride), np.int32)
         frames = np.zeros(B, np.int64)
         scores = np.zeros(B, np.float32)
-        if lib().vits_model_align_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(ids), _ptr(ilens), id_stride, _ptr(sp), float(noise_scale),
-                                        C.byref(o), _ptr(durations), _ptr(frames), _ptr(scores)) != 0:
+        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_align_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(ids), _ptr(ilens), id_stride, _ptr(sp),
+                                                                                  float(noise_scale), C.byref(o), _ptr(durations), _ptr(frames), _ptr(scores))) != 0:
             raise VitsError(last_error())
         return durations, frames, scores
 
@@ -1217,7 +1292,7 @@ class Model:
 
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
                      skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None,
-                     noise_scale_duration=None, duration_override=None, durations_out=None):
+                     noise_scale_duration=None, duration_override=None, durations_out=None, pitch_ratio=None):
         """vits_model_submit_batch: queue one batch on this handle's pipeline (at most two in flight); its stage one runs under the
         previous batch's vocoder. Results come from wait(), in submission order, bit-identical to process_batch. The prosody arguments are
         those of process_batch; durations_out is filled by the matching wait() at the latest (this handle keeps it alive until then)."""
@@ -1229,7 +1304,7 @@ class Model:
         o, keep = _opts(B, mode, NOISE_COUNTER, noise_seed, fixed_duration=fixed_duration, out_device=out_device, out_device_stride=out_device_stride,
                         skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames, noise_seed_offsets=noise_seed_offsets, speaker_ids=speaker_ids)
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
-        if lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o)) != 0:
+        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o))) != 0:
             raise VitsError(last_error())
         if not hasattr(self, "_durations_in_flight"):
             self._durations_in_flight = []
@@ -1671,6 +1746,64 @@ def resample(x, in_rate, out_rate, lens=None, out=None):
     elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
         raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
     if lib().vits_op_resample(int(in_rate), int(out_rate), B, _ptr(x), stride, _ptr(ln), _ptr(out), out.shape[1]) != 0:
+        raise VitsError(last_error())
+    return out, n_out
+
+
+def pitch_ratio(semitones):
+    """vits_pitch_ratio: (float)2^(semitones / 12)"""
+    return float(lib().vits_pitch_ratio(float(semitones)))
+
+
+def pitch_plan(ratio, n):
+    """vits_pitch_plan: (P, S, R, N') of a row of n samples at a pitch ratio (host only)"""
+    P, S, R, n_out = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+    if lib().vits_pitch_plan(float(ratio), int(n), C.byref(P), C.byref(S), C.byref(R), C.byref(n_out)) != 0:
+        raise VitsError(last_error())
+    return int(P.value), int(S.value), int(R.value), int(n_out.value)
+
+
+def pitch_table():
+    """vits_pitch_table: the prototype's two fp32 tables [2, Z Q + 2] = (G, D) (host only)"""
+    n = lib().vits_pitch_table(None, 0)
+    if n < 0:
+        raise VitsError(last_error())
+    t = np.zeros((2, n // 2), np.float32)
+    if lib().vits_pitch_table(_ptr(t), t.size) != n:
+        raise VitsError(last_error())
+    return t
+
+
+def pitch_host(x, ratio):
+    """vits_pitch_host: the varispeed's definition evaluated in double, sequentially, on one row (host only) -> float64 [N']"""
+    x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    y = np.zeros(max(pitch_plan(ratio, x.size)[3], 1), np.float64)
+    n = lib().vits_pitch_host(_ptr(x), x.size, float(ratio), _ptr(y), y.size)
+    if n < 0:
+        raise VitsError(last_error())
+    return y[:n]
+
+
+def pitch(x, ratios, lens=None, out=None):
+    """The varispeed kernel on a ragged batch (vits_op_pitch). x: float32 [B, x_stride] (or one 1-D row), passed as it lies when it is C-contiguous float32
+    (stride and alignment reach the device); ratios: a scalar or one ratio per row; lens: samples per row (None = the whole row). Returns (y float32
+    [B, y_stride], n_out int64 [B]): row b holds its n_out[b] samples and, behind them, the byte of op_set_output_fill. out: a caller-owned float32
+    [B, y_stride] array, which is overwritten whole."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    r = np.ascontiguousarray(np.broadcast_to(np.asarray(ratios, np.float32).ravel(), (B,)))
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    if out is None:
+        longest = max(-((-int(n) << 24) // max(int(float(p) * 2.0 ** 24), 1)) if np.isfinite(p) else 0 for n, p in zip(np.maximum(ln, 0), r))
+        out = np.zeros((B, max(longest, 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    n_out = np.zeros(B, np.int64)
+    if lib().vits_op_pitch(B, _ptr(x), stride, _ptr(ln), _ptr(r), _ptr(out), out.shape[1], _ptr(n_out)) != 0:
         raise VitsError(last_error())
     return out, n_out
 

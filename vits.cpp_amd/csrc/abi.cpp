@@ -821,6 +821,12 @@ VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_sp
     const std::string who = "vits_model_speak: ";
     if (out) std::memset(out, 0, sizeof(*out));
     if (!model) return fail(who + "null argument (model)");
+    {
+        std::vector<float> given;  // (taken first: whatever becomes of this call, the ratios given for it are gone)
+        if (model->eng.take_pitch_ratios(given))
+            return fail(who + "the ratios of vits_model_set_pitch_ratios are one per utterance, and the text decides how many utterances there are: use "
+                              "vits_model_set_pitch, or vits_split_sentences and vits_model_process_joined");
+    }
     vits_speak_opts so;
     std::memset(&so, 0, sizeof(so));
     so.struct_size = sizeof(so);
@@ -860,6 +866,84 @@ VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_sp
     return run_engine(out, [&](std::string& e) {
         return model->eng.process_joined(p.ids.data(), p.id_lens.data(), p.batch, p.id_stride, o, p.track.data(), p.gap_ms.data(), p.index.data(), out, e);
     });
+    VITS_CATCH(-1)
+}
+
+// ---- a stated pitch (include/vits.h: the definition) ---------------------------------------------------------------------------------------------------
+VITS_API float vits_pitch_ratio(float semitones) { return (float)std::exp2((double)semitones / 12.0); }
+VITS_API int vits_pitch_plan(float ratio, int64_t n, int64_t* P, int64_t* S, int32_t* R, int64_t* n_out) {
+    VITS_TRY
+    vits::PitchPlan p;
+    std::string err;
+    if (!vits::pitch_plan(ratio, n, p, err)) return fail("vits_pitch_plan: " + err);
+    if (P) *P = p.P;
+    if (S) *S = p.S;
+    if (R) *R = p.R;
+    if (n_out) *n_out = p.n_out;
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_pitch_table(float* dst, size_t cap) {
+    VITS_TRY
+    const size_t n = (size_t)2 * vits::kPitchTableN;
+    if (!dst && cap) return fail("vits_pitch_table: null argument (dst is NULL with cap > 0)");
+    if (dst && cap >= n) {
+        const std::vector<float> t = vits::pitch_table();
+        std::memcpy(dst, t.data(), sizeof(float) * n);
+    }
+    return (int64_t)n;
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_pitch_host(const float* x, int64_t n, float ratio, double* y, size_t cap) {
+    VITS_TRY
+    vits::PitchPlan p;
+    std::string err;
+    if (!y || (!x && n)) return fail("vits_pitch_host: null argument (y, or x with n > 0)");
+    if (!vits::pitch_plan(ratio, n, p, err)) return fail("vits_pitch_host: " + err);
+    if (cap < (size_t)p.n_out) return fail("vits_pitch_host: cap = " + std::to_string(cap) + " is below the row's " + std::to_string(p.n_out) + " output samples");
+    const std::vector<float> t = vits::pitch_table();
+    vits::pitch_host(x, n, p, t.data(), y);
+    return p.n_out;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_set_pitch(vits_model* model, float ratio) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_pitch(ratio, err); });
+}
+VITS_API int vits_model_set_pitch_ratios(vits_model* model, const float* ratios, int32_t n) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_pitch_ratios(ratios, n, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_get_pitch(const vits_model* model, float* ratio) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (ratio) *ratio = model->eng.pitch_ratio;
+    return 0;
+}
+VITS_API int64_t vits_model_last_pitch(vits_model* model, int64_t* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const int64_t* p = model->eng.last_pitch(rows);  // [rows][4]: P, N, N', K
+    if (rows && dst && cap >= (size_t)3 * rows)
+        for (int b = 0; b < rows; ++b) std::copy_n(p + (size_t)4 * b, 3, dst + (size_t)3 * b);
+    return rows;
     VITS_CATCH(-1)
 }
 

@@ -91,6 +91,50 @@ VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, 
     VITS_CATCH(-1)
 }
 
+VITS_API int vits_op_pitch(int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const float* ratios, float* y, int64_t y_stride, int64_t* n_out) {
+    VITS_TRY
+    if (batch <= 0 || !x || !ratios || !y || !n_out || x_stride <= 0 || y_stride <= 0) return fail("vits_op_pitch: null argument or empty batch");
+    std::vector<int32_t> n(batch);
+    int64_t longest = 0, longest_b = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int64_t len = lens ? lens[b] : x_stride;
+        if (len < 0 || len > x_stride) return fail("vits_op_pitch: lens[" + std::to_string(b) + "] = " + std::to_string(len) + " is outside [0, x_stride = " + std::to_string(x_stride) + "]");
+        PitchPlan p;
+        std::string err;
+        if (!pitch_plan(ratios[b], len, p, err)) return fail("vits_op_pitch: row " + std::to_string(b) + ": " + err);
+        n[b] = (int32_t)len;
+        n_out[b] = p.n_out;
+        if (p.n_out > longest) longest = p.n_out, longest_b = b;
+    }
+    if (y_stride < longest)
+        return fail("vits_op_pitch: y_stride = " + std::to_string(y_stride) + " is shorter than the longest output row (row " + std::to_string(longest_b) + ": " +
+                    std::to_string(n[longest_b]) + " samples in, " + std::to_string(longest) + " out)");
+    // the rows at the caller's own stride and at the caller's own alignment within 16 bytes (so that a test reaches the kernel's unaligned loads), 0xFF bytes
+    // behind every length
+    const size_t off = ((uintptr_t)x & 15) / 4;
+    std::vector<float> hx((size_t)batch * x_stride + 4);
+    std::memset(hx.data(), 0xFF, hx.size() * 4);
+    for (int b = 0; b < batch; ++b) std::memcpy(&hx[off + (size_t)b * x_stride], x + (size_t)b * x_stride, sizeof(float) * (size_t)n[b]);
+    const std::vector<float> gd = pitch_table_pairs();
+    const size_t ny = (size_t)batch * y_stride * 4;
+    DevMem dx, dy, dt, dn, dr;
+    if (!dx.put(hx.data(), hx.size() * 4) || !dy.fill(ny, g_op_out_fill) || !dt.put(gd.data(), gd.size() * 4) || !dn.put(n.data(), (size_t)batch * 4) ||
+        !dr.put(ratios, (size_t)batch * 4))
+        return -1;
+    PitchCall c;
+    c.x = dx.f() + off;
+    c.x_stride = x_stride;
+    c.lens = dn.i();
+    c.ratios = dr.f();
+    c.y = dy.f();
+    c.y_stride = y_stride;
+    c.table = dt.f();
+    c.batch = batch;
+    c.max_out = longest;
+    return finish(launch_pitch(c, nullptr)) && dy.get(y, ny) ? 0 : -1;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_level(const vits_level_desc* d, const float* x, const int64_t* lens, float* y, float* levels) {
     VITS_TRY
     if (!d || !x || !levels || d->batch <= 0 || d->x_stride <= 0 || (y && d->y_stride <= 0)) return fail("vits_op_level: null argument or empty batch");

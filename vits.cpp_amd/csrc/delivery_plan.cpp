@@ -6,9 +6,12 @@ namespace vits {
 DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     DeliveryPlan p;
     const bool multiplies = a.level >= DLEVEL_GAIN;
-    // the refusals, in the order the engine has always checked them (level before edges, the limiter's first); a joined ask is refused for what it is first
+    // the refusals, in the order the engine has always checked them (level before edges, the limiter's first); a joined ask is refused for what it is first,
+    // then an ask with pitch
     if (a.joined && a.on_chunk) p.refusal = REFUSE_JOIN_STREAM;
     else if (a.joined && a.async) p.refusal = REFUSE_JOIN_ASYNC;
+    else if (a.pitch && a.on_chunk) p.refusal = REFUSE_PITCH_STREAM;
+    else if (a.pitch && a.async) p.refusal = REFUSE_PITCH_ASYNC;
     else if (a.on_chunk && a.limiter && multiplies) p.refusal = REFUSE_LIMIT_STREAM;
     else if (a.on_chunk && (a.level == DLEVEL_MEASURE || a.level == DLEVEL_WHOLE)) p.refusal = REFUSE_LEVEL_STREAM;
     else if (a.edges && a.on_chunk) p.refusal = REFUSE_EDGES_STREAM;
@@ -18,13 +21,13 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     p.multiplies = multiplies;
     p.limits = multiplies && a.limiter;
     // The stages that write, in their order, each into its own arena buffer — except the last one, which writes straight to the caller's buffer when the
-    // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the vocoder's stride. Behind a join they are
-    // the tracks', J_stride apart.
-    constexpr int kSlots = STAGE_COUNT + 1;  // vocoder, edges, join, level, resample
-    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
-    const bool writes[kSlots] = {true, a.edges, a.joined, multiplies, a.rate};
-    const int own[kSlots] = {BUF_WAVE, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
-    const int own_stride[kSlots] = {STRIDE_S, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : STRIDE_S), STRIDE_OUT_WS};
+    // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the stride of what is in front of it: the
+    // pitch stage's, else the vocoder's. Behind a join they are the tracks', J_stride apart.
+    constexpr int kSlots = STAGE_COUNT + 2;  // vocoder, pitch, edges, join, level, resample
+    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.pitch, &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
+    const bool writes[kSlots] = {true, a.pitch, a.edges, a.joined, multiplies, a.rate};
+    const int own[kSlots] = {BUF_WAVE, BUF_PITCH, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
+    const int own_stride[kSlots] = {STRIDE_S, STRIDE_P, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : (a.pitch ? STRIDE_P : STRIDE_S)), STRIDE_OUT_WS};
     int last = 0;
     for (int s = 0; s < kSlots; ++s)
         if (writes[s]) last = s;
@@ -52,6 +55,7 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
             if (buf == BUF_LVL) p.needs |= NEED_WAVE_LVL;
             if (buf == BUF_OUT) p.needs |= NEED_WAVE_OUT;
             if (buf == BUF_JOIN) p.needs |= NEED_WAVE_JOIN;
+            if (buf == BUF_PITCH) p.needs |= NEED_WAVE_PITCH;
         }
     if (a.edges) p.needs |= NEED_ED_SCRATCH;
     if (a.level != DLEVEL_NONE) p.needs |= NEED_LVL_SCRATCH;

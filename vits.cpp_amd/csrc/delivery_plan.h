@@ -1,5 +1,5 @@
 // delivery_plan.h — how a call's PCM travels from the vocoder to what is handed out (host only, like launch_plan.h and tile_map.h: no kernel, no device).
-// The stages behind the vocoder — stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
+// The stages behind the vocoder — a stated pitch (pitch.hip), stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
 // stage in front of them wrote. delivery_plan() states that chain ONCE, from what the handle and the call ask for: who runs, which buffer each stage reads
 // and writes, which buffer is delivered, which arena buffers the call therefore needs, or why the combination is refused. The engine allocates from the
 // plan (layout_stage_two) and resolves its buffer ids to pointers in one place (Call::rows_of); tests/golden/delivery_plan_table.txt pins the whole table.
@@ -16,6 +16,7 @@ enum DeliveryBuf : int {
     BUF_OUT,       // s2.wave_out: the PCM at the output rate [B][out_ws]
     BUF_CALLER,    // opts.out_device, rows out_device_stride apart
     BUF_JOIN,      // s2.wave_join: the joined tracks [G][J_stride] (a joined ask only)
+    BUF_PITCH,     // s2.wave_pitch: the varispeed rows [B][P_stride] (an ask with pitch only)
     BUF_COUNT
 };
 enum DeliveryStride : int {
@@ -25,6 +26,7 @@ enum DeliveryStride : int {
     STRIDE_OUT_WS,  // out_ws: the rows at the output rate
     STRIDE_CALLER,  // out_device_stride
     STRIDE_J,       // J_stride: the model-rate rows behind the join, one per track (the largest track bound; a joined ask only)
+    STRIDE_P,       // P_stride = 2 S_stride: the rows behind the pitch stage (the bound of N' at the smallest ratio, 0.5; an ask with pitch only)
     STRIDE_COUNT
 };
 // the level kinds as delivery sees them. The kinds that multiply are two here because only a plain gain streams
@@ -43,6 +45,8 @@ enum DeliveryRefusal : int {
     REFUSE_EDGES_ASYNC,   // async with the edges stage on
     REFUSE_JOIN_STREAM,   // a joined ask with on_chunk: no sample of a track is final before its last utterance is placed
     REFUSE_JOIN_ASYNC,    // a joined ask with async: the track lengths are read from the device behind the call's work
+    REFUSE_PITCH_STREAM,  // pitch with on_chunk: streaming pitch is not built (a window's last samples need the next window's first)
+    REFUSE_PITCH_ASYNC,   // pitch with async: the ratios travel through memory the call owns
     REFUSE_COUNT
 };
 enum DeliveryNeed : unsigned {
@@ -56,7 +60,8 @@ enum DeliveryNeed : unsigned {
     NEED_LVL_RANGES = 1u << 7,  // streaming under a gain: the model-rate samples each window finalises
     NEED_WAVE_JOIN = 1u << 8,   // a joined ask, unless the join writes straight to out_device: the tracks [G][J_stride]
     NEED_JOIN_TABLE = 1u << 9,  // a joined ask: the table join.hip reads
-    NEED_COUNT = 10
+    NEED_WAVE_PITCH = 1u << 10,  // an ask with pitch, unless the stage writes straight to out_device: the rows [B][P_stride]
+    NEED_COUNT = 11
 };
 
 struct DeliveryAsk {
@@ -67,6 +72,7 @@ struct DeliveryAsk {
     bool out_device = false;   // opts.out_device
     bool on_chunk = false;     // opts.on_chunk
     bool async = false;        // opts.async
+    bool pitch = false;        // some utterance of the call has a pitch ratio other than 1: the varispeed runs behind the vocoder, in front of the edges stage
     bool joined = false;       // the call lays its utterances end to end into tracks (vits_model_process_joined): the join runs behind the edges stage
 };
 
@@ -87,6 +93,9 @@ struct DeliveryPlan {
     // a joined ask: the join, between stage[STAGE_EDGES] and stage[STAGE_LEVEL]. It always writes (one row per track); the level and the resampler behind it
     // read and write G rows, and a levelled buffer follows its input's stride (STRIDE_J). Off for every other ask, whose plan is what it always was.
     Stage join;
+    // an ask with pitch: the varispeed (pitch.hip), between stage[STAGE_VOCODER] and stage[STAGE_EDGES]. It always writes (rows P_stride apart); with the edges
+    // stage off, a levelled buffer behind it follows its stride (STRIDE_P). Off for every other ask, whose plan is what it always was.
+    Stage pitch;
     bool multiplies = false;  // the level stage writes (a plain multiply, or the limiter)
     bool limits = false;      // ... through the limiter
     DeliveryRoute delivered;  // what the call hands out: the destination of the last stage that writes

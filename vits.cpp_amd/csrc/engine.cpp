@@ -166,6 +166,84 @@ int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
     return 0;
 }
 
+int Engine::set_pitch(float ratio, std::string& err) {
+    PitchPlan p;
+    std::string why;
+    if (!pitch_plan(ratio, 0, p, why)) {
+        err = "vits_model_set_pitch: " + why;
+        return -1;
+    }
+    pitch_ratio = ratio;
+    return 0;
+}
+
+int Engine::set_pitch_ratios(const float* ratios, int n, std::string& err) {
+    if (n < 0 || (!ratios && n > 0)) {
+        err = "vits_model_set_pitch_ratios: " + std::string(n < 0 ? "n < 0" : "null argument (ratios is NULL with n > 0)");
+        return -1;
+    }
+    pitch_given_.assign(ratios, ratios + (ratios ? n : 0));
+    pitch_given_set_ = ratios && n > 0;
+    return 0;
+}
+
+bool Engine::take_pitch_ratios(std::vector<float>& given) {
+    const bool was = pitch_given_set_;
+    given.clear();
+    given.swap(pitch_given_);
+    pitch_given_set_ = false;
+    return was;
+}
+
+int Engine::resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const {
+    const vits_process_opts& o = rp.o;
+    const bool have = rp.have;
+    if (have && (int)rp.given.size() != B) {
+        err = "vits_model_set_pitch_ratios gave " + std::to_string(rp.given.size()) + " ratios, and this call has " + std::to_string(B) + " utterances";
+        return -1;
+    }
+    const float* given = have ? rp.given.data() : nullptr;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const float p = given ? given[b] : pitch_ratio;
+        if (!std::isfinite(p) || p < kPitchMinRatio || p > kPitchMaxRatio) {
+            err = "pitch_ratios[" + std::to_string(b) + "] = " + fmt_float(p) + ": must be finite and in [0.5, 2]";
+            return -1;
+        }
+        any = any || p != 1.f;
+    }
+    if (!any) return 0;
+    rp.ratios.resize((size_t)B);
+    rp.rates.resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const float p = rp.ratios[(size_t)b] = given ? given[b] : pitch_ratio;
+        const float rate = o.speaking_rates ? o.speaking_rates[b] : speaking_rate;
+        rp.rates[(size_t)b] = rate;  // (o.speaking_rates is the caller's until the last line)
+        if (p == 1.f) continue;
+        const std::string who = "utterance " + std::to_string(b) + " has the pitch ratio " + fmt_float(p) + ", which it pays for by being spoken slower by that ratio: ";
+        if (o.fixed_duration > 0) {
+            err = who + "fixed_duration > 0 leaves the duration predictor nothing to stretch";
+            return -1;
+        }
+        if (o.duration_override) {
+            const int len = std::min(id_stride, std::max(0, id_lens ? id_lens[b] : id_stride));
+            for (int t = 0; t < len; ++t)
+                if (o.duration_override[(size_t)b * id_stride + t] >= 0) {
+                    err = who + "duration_override states token " + std::to_string(t) + "'s frames, which the stretch would have to change";
+                    return -1;
+                }
+        }
+        const float r = rp.rates[(size_t)b] = (float)((double)rate / (double)p);
+        if (!rate_ok(r)) {
+            err = who + "its speaking rate " + fmt_float(rate) + " becomes " + fmt_float(r) + ", outside [0.1, 10]";
+            return -1;
+        }
+    }
+    rp.pitch = rp.ratios.data();
+    rp.o.speaking_rates = rp.rates.data();
+    return 0;
+}
+
 int Engine::set_rates(int in_rate, int out_rate, std::string& err) {
     int stored[2] = {in_rate, out_rate};
     for (int side = 0; side < 2; ++side) {
@@ -270,6 +348,7 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
     ask.on_chunk = o.on_chunk != nullptr;
     ask.async = o.async != 0;
     ask.joined = joined;
+    ask.pitch = call_pitch_ != nullptr;  // (resolved: Engine::resolve_pitch)
     plan = delivery_plan(ask);
     switch (plan.refusal) {
         case DELIVER_OK: return 0;
@@ -300,6 +379,16 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
         case REFUSE_JOIN_ASYNC:
             err = "vits_model_process_joined: async returns before the device has finished, and the lengths of the tracks are read from the device behind the call's "
                   "work: call without async";
+            break;
+        case REFUSE_PITCH_STREAM:
+            err = "on_chunk streams an utterance while it is being made, and an utterance of this call has a pitch ratio other than 1 (vits_model_set_pitch_ratios, "
+                  "vits_model_set_pitch): streaming pitch is not built (the varispeed of a window's last samples reads the next window's first): call without "
+                  "on_chunk, or with every ratio 1";
+            break;
+        case REFUSE_PITCH_ASYNC:
+            err = "async returns before the device has finished, and an utterance of this call has a pitch ratio other than 1 (vits_model_set_pitch_ratios, "
+                  "vits_model_set_pitch): streaming pitch is not built, and the ratios travel to the device through memory the next call reuses: call without async, "
+                  "or pipeline with vits_model_submit_batch / vits_model_wait";
             break;
         default: err = "this combination of delivery stages is not supported"; break;
     }
@@ -429,11 +518,11 @@ int Engine::run_edges(Call& c) {
     EdgesCall ec;
     ec.x = src.p;
     ec.x_stride = src.stride;
-    ec.lens = c.s1.stage_lens + (size_t)n_up * B;
+    ec.lens = c.head_lens();
     ec.y = dst.p;
     ec.y_stride = dst.stride;
     ec.batch = B;
-    ec.max_len = c.smax[n_up];
+    ec.max_len = c.head_max();
     ec.plan = p;
     ec.fades = ed_fades_;
     ec.scratch = c.s2.ed_scratch;
@@ -474,6 +563,7 @@ void Engine::batch_landed(Pending& p, int slot, bool append) {
     lm_.landed(slot, p.lm_rows, append);
     if (p.ed_rows) edges_lengths(ed_.slot_rows(slot), p.ed_rows, p.lengths.data());
     ed_.landed(slot, p.ed_rows, append);
+    pt_.store(p.pt_rows, append);
 }
 
 // the one place that allocates what a call hands out: lengths[] and frames[] of B utterances, no PCM yet
@@ -520,21 +610,25 @@ int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, cons
 
 int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                           std::string& err) {
+    ResolvedPitch rp(*this, o);
     if (refuse_pending(err)) return -1;
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
+    if (resolve_pitch(B, id_stride, id_lens, rp, err)) return -1;
+    ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
     DeliveryPlan refusable;  // (the refusals of the delivery chain, before stage one is queued; the call's own plan is made where its stage two begins)
-    if (plan_delivery(o, refusable, err)) return -1;
+    if (plan_delivery(rp.o, refusable, err)) return -1;
     clear_reports();
     // The drop-in callers' share of the pipeline: a large batch is split in two inside the call — stage one of the
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
     const int smin = knobs.split_min_batch;
+    // (a call that shifts stays whole: a part whose ratios are all 1 would run without the stage and leave the report without its rows)
     if (smin > 0 && B >= smin && B >= 2 && front_ && !prof.on && !knobs.no_pipeline && o.noise_kind == VITS_NOISE_COUNTER && !o.collect_taps && !o.on_chunk &&
-        !o.frames_only && !o.async && o.vocoder_chunk_frames <= 0)
+        !o.frames_only && !o.async && o.vocoder_chunk_frames <= 0 && !rp.pitch)
         return process_split(ids, id_lens, B, id_stride, o, out, err);
     a1_slot_ = 0;
-    const int rc = process_impl(ids, id_lens, B, id_stride, o, out, err, nullptr);
+    const int rc = process_impl(ids, id_lens, B, id_stride, rp.o, out, err, nullptr);
     if (rc) drain_streams();
     return rc;
 }
@@ -550,6 +644,7 @@ void Engine::drain_streams() {
 int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, const int32_t* track, const float* gap_ms,
                            const int32_t* index, vits_batch_result* out, std::string& err) {
     const std::string who = "vits_model_process_joined: ";
+    ResolvedPitch rp(*this, o);
     if (refuse_pending(err)) return -1;
     // (on_chunk and async are the plan's refusals, below)
     if (o.collect_taps) {
@@ -566,8 +661,17 @@ int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, in
         err = who + "empty batch";
         return -1;
     }
+    if (rp.have || pitch_ratio != 1.f) {
+        // (the ratios are validated here, in front of the plan's refusals, which ask whether the stage runs; the rates they divide, below, where they always were)
+        if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
+        if (resolve_pitch(B, id_stride, id_lens, rp, err)) {
+            err = who + err;
+            return -1;
+        }
+    }
+    ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
     DeliveryPlan refusable;
-    if (plan_delivery(o, refusable, err, /*joined=*/true)) return -1;
+    if (plan_delivery(rp.o, refusable, err, /*joined=*/true)) return -1;
     JoinPlan plan;
     std::string why;
     if (!join_plan(hp.sampling_rate, B, track, gap_ms, plan, why)) {
@@ -580,7 +684,7 @@ int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, in
     a1_slot_ = 0;
     join_index_.assign(B, 0);
     for (int b = 0; b < B; ++b) join_index_[b] = index ? index[b] : b;
-    const int rc = process_impl(ids, id_lens, B, id_stride, o, out, err, nullptr, &plan);
+    const int rc = process_impl(ids, id_lens, B, id_stride, rp.o, out, err, nullptr, &plan);
     if (rc) drain_streams();
     return rc;
 }
@@ -603,7 +707,7 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
         if (o.duration_override) oh.duration_override = o.duration_override + (size_t)b0[h] * id_stride;
         if (o.durations_out) oh.durations_out = o.durations_out + (size_t)b0[h] * id_stride;
         if (o.out_device) oh.out_device = (float*)o.out_device + (int64_t)b0[h] * o.out_device_stride;
-        if (submit_batch(ids + (size_t)b0[h] * id_stride, id_lens ? id_lens + b0[h] : nullptr, nb[h], id_stride, oh, err)) break;
+        if (submit_batch(ids + (size_t)b0[h] * id_stride, id_lens ? id_lens + b0[h] : nullptr, nb[h], id_stride, oh, err, /*part=*/true)) break;
         ++queued;
     }
     if (queued < 2) {
@@ -658,7 +762,8 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
 // which is running on the main stream —, the frame counts through pinned memory behind an event (the host waits for THAT event,
 // not for the device), stage two behind batch n - 1 on the main stream. Batch n - 2, the previous user of the arena, was waited
 // for before this submit was accepted, so nothing on the device still reads it.
-int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, std::string& err) {
+int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, std::string& err, bool part) {
+    ResolvedPitch rp(*this, o);  // (its arrays live until process_impl has returned: the ratios have gone to the slot's pinned memory by then, the rates into the header)
     if (pending() >= 2) {
         err = "two batches in flight already: call vits_model_wait first";
         return -1;
@@ -669,13 +774,15 @@ int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int 
     }
     if (check_speakers(o, B, err)) return -1;  // (the speakers are copied into the call's header below: the caller's array may go at once)
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;  // (so are the prosody arrays; durations_out is written when the frame counts are read)
+    if (!part && resolve_pitch(B, id_stride, id_lens, rp, err)) return -1;
+    ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
     Pending& p = pend_[submit_seq_ & 1];
     if (!p.done) {
         HIP_OK(hipEventCreateWithFlags(&p.s1_done, hipEventDisableTiming));
         HIP_OK(hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
     }
     a1_slot_ = (int)(submit_seq_ & 1);
-    const int rc = process_impl(ids, id_lens, B, id_stride, o, nullptr, err, &p);
+    const int rc = process_impl(ids, id_lens, B, id_stride, rp.o, nullptr, err, &p);
     a1_slot_ = 0;
     if (rc) {
         // (whatever was queued is harmless: it only touches this slot's arenas; leave the device idle before the slot is reused)
@@ -735,6 +842,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     }
     Call c(o, err, ids, B, id_stride);
     c.join = join;
+    c.pitch = call_pitch_;
     // An error path between the speculative draw and its commit must not leave the reference stream locked — nor at a timing-dependent
     // position: finish(0) rewinds to the state behind the [T, 2] tensor, where the sequential path this replaces leaves the stream when a call
     // fails before prior sampling (finish(drawn()) committed however many values the helper happened to have drawn).
@@ -770,7 +878,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     }
     const bool want_async = o.async && o.skip_host_copy && o.fixed_duration > 0 && !o.collect_taps;
     c.ts = round_up(c.Tmax, 32);
-    const int n_up = c.n_up = (int)ups_.size();
+    c.n_up = (int)ups_.size();
     clear_taps();
     tap_batch_ = B;
 
@@ -891,8 +999,10 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
             // (stated edges: the bound N + Pl + Pt of every utterance, the size to allocate: exact under VITS_EDGES_PAD, an upper bound when the stage trims)
             const int64_t pads = edges_on() ? edges_plan_.Pl + edges_plan_.Pt : 0;
             std::vector<int64_t> lengths(B);
-            for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.slen[n_up][b] + pads);
-            fill_result(out, B, (size_t)plan.out_len(c.smax[n_up] + pads), lengths.begin(), frames.begin());
+            // (a stated pitch: N' of every utterance in place of the vocoder's sample count)
+            if (c.pitched() && plan_rows(c)) return -1;
+            for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.head_len()[(size_t)b] + pads);
+            fill_result(out, B, (size_t)plan.out_len(c.head_max() + pads), lengths.begin(), frames.begin());
         }
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
@@ -1023,10 +1133,31 @@ int Engine::plan_rows(Call& c) {
     const int B = c.B, n_up = c.n_up;
     if (plan_delivery(o, c.dp, err, c.join != nullptr)) return -1;
     // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
-    c.mr_len = c.slen[n_up];
+    if (c.pitched()) {
+        // a stated pitch: N' of every row is host arithmetic, like everything else here; so are the rows of the report
+        c.pit_len.resize((size_t)B);
+        c.pit_rows.resize((size_t)4 * B);
+        for (int b = 0; b < B; ++b) {
+            PitchPlan pp;
+            std::string why;
+            if (!pitch_plan(c.pitch[b], c.slen[n_up][b], pp, why)) {
+                err = "utterance " + std::to_string(b) + ": " + why;
+                return -1;
+            }
+            c.pit_len[(size_t)b] = (int)pp.n_out;  // (at most 2^31: N <= 2^30 and p >= 0.5; the checks below refuse what does not fit)
+            if (pp.n_out > (int64_t)INT32_MAX - 64) {
+                err = "utterance " + std::to_string(b) + " has " + std::to_string(pp.n_out) + " samples at its pitch ratio: too long";
+                return -1;
+            }
+            c.pit_max = std::max(c.pit_max, c.pit_len[(size_t)b]);
+            const int64_t row[4] = {pp.P, c.slen[n_up][b], pp.n_out, pp.K};
+            std::copy_n(row, 4, c.pit_rows.begin() + (size_t)4 * b);
+        }
+    }
+    c.mr_len = c.head_len();
     if (c.dp[STAGE_EDGES].runs)
         for (int b = 0; b < B; ++b) {
-            const int64_t n = edges_plan_.bound(c.slen[n_up][b]);
+            const int64_t n = edges_plan_.bound(c.head_len()[(size_t)b]);
             if (n > (int64_t)INT32_MAX - 64) {
                 err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
                 return -1;
@@ -1079,6 +1210,46 @@ int Engine::plan_rows(Call& c) {
         }
     }
     c.rows_planned = true;
+    return 0;
+}
+
+// ---- the pitch stage of a call: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.pitch_lens: what the edges stage,
+// or with it off every stage behind it, reads its rows' lengths from). One launch serves every ratio of the batch; rows with ratio 1 are copied.
+int Engine::run_pitch(Call& c) {
+    std::string& err = c.err;
+    const int B = c.B, n_up = c.n_up;
+    const Call::Rows src = c.rows_of(c.dp.pitch.src), dst = c.rows_of(c.dp.pitch.dst);
+    if (!pitch_table_ && !(pitch_table_ = upload(pitch_table_pairs()))) {  // (owned by the handle and counted in weight_bytes from here on)
+        err = "pitch table: device allocation failed";
+        return -1;
+    }
+    HIP_OK(c.pitch_pin->ensure((size_t)B, (size_t)B + 64));
+    std::copy_n(c.pitch, B, c.pitch_pin->p);
+    HIP_OK(hipMemcpyAsync(c.s2.pitch_ratios, c.pitch_pin->p, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream));
+    prof.fence();
+    PitchCall pc;
+    pc.x = src.p;
+    pc.x_stride = src.stride;
+    pc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    pc.ratios = c.s2.pitch_ratios;
+    pc.y = dst.p;
+    pc.y_stride = dst.stride;
+    pc.table = pitch_table_;
+    pc.lens_out = c.s2.pitch_lens;
+    pc.batch = B;
+    pc.max_out = c.pit_max;
+    double taps = 0, in_s = 0, out_s = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t* row = c.pit_rows.data() + (size_t)4 * b;
+        in_s += (double)row[1], out_s += (double)row[2];
+        if (row[0] != kPitchOne) taps += (double)row[2] * (double)row[3];
+    }
+    // K fused multiply-adds a sample and the tap's own; every row read once and written once
+    prof.begin("pitch", 4.0 * taps, 4.0 * (in_s + out_s), stream, /*chain=*/true);
+    const hipError_t e = launch_pitch(pc, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    prof.fence();
     return 0;
 }
 
@@ -1138,8 +1309,12 @@ int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<in
         snapshot(name, t, 1, max_len, B, lens);
     };
     // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
-    std::vector<int> tap_len = c.slen[n_up], tap_out_len = c.out_len;
-    int tap_max = c.smax[n_up], tap_out_max = c.out_max;
+    std::vector<int> tap_len = c.head_len(), tap_out_len = c.out_len;
+    int tap_max = c.head_max(), tap_out_max = c.out_max;
+    if (dp.pitch.runs) {
+        if (run_pitch(c)) return -1;
+        if (o.collect_taps) tap("waveform_pitch", dp.pitch.after, tap_max, tap_len);
+    }
     if (dp[STAGE_EDGES].runs) {
         if (run_edges(c)) return -1;
         if (o.collect_taps) {
@@ -1238,7 +1413,8 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
     const int pcm_max = rs ? c.out_max : c.mr_max;
     // the device lengths [B] of the model-rate rows, for every stage behind the vocoder: its sample counts, or what the edges stage will write behind its rows
-    c.mr_lens = c.s1.stage_lens + (size_t)n_up * B;
+    c.mr_lens = c.head_lens();
+    c.pitch_pin = pend ? &pend->pitch_pinned : &pitch_host_;
     if (ed) {
         HIP_OK(ed_.grow(B, owned_, weight_bytes));
         c.mr_lens = static_cast<const int*>(ed_.tail());
@@ -1451,6 +1627,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         pend->lv_rows = lv_n;
         pend->lm_rows = lm_n;
         pend->ed_rows = ed_n;  // (lengths: the bounds until vits_model_wait reads the rows)
+        pend->pt_rows = c.pit_rows;
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -1500,6 +1677,7 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
                 for (int g = 0; g < R; ++g) out->lengths[g] = rs ? c.rate_out->plan.out_len(tl[g]) : tl[g];
         } else if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
         lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
+        pt_.store(c.pit_rows);
         // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
         // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
         if (prof.on && prof.recs.size() > 50000) prof.collect();

@@ -166,8 +166,9 @@ class ReportRows {
     }
     void clear() { rows_ = 0, unlanded_ = -1; }
     // rows [n][4] made on the host from what has landed (the joins': the device holds {o_b, n_b}, the report adds the index and the track)
-    void store(std::vector<T> rows) {
-        store_ = std::move(rows);
+    void store(std::vector<T> rows, bool append = false) {
+        if (append) store_.insert(store_.end(), rows.begin(), rows.end());
+        else store_ = std::move(rows);
         rows_ = (int)(store_.size() / 4);
         unlanded_ = -1;
     }
@@ -292,7 +293,8 @@ class Engine {
     // the rows [B][4] = {index, track, o_b, n_b} (model rate) of the most recently completed joined call (empty: the last call did not join)
     const int64_t* last_joins(int& rows) const { return jn_.read(rows); }
     // pipelined batches (include/vits.h vits_model_submit_batch / vits_model_wait): up to two in flight
-    int submit_batch(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, std::string& err);
+    // (part: a half of a batch split inside vits_model_process_batch, which has resolved the call's pitch — off, or it would not split)
+    int submit_batch(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, std::string& err, bool part = false);
     int wait_batch(vits_batch_result* out, std::string& err);
     int pending() const { return (int)(submit_seq_.load(std::memory_order_acquire) - wait_seq_.load(std::memory_order_acquire)); }  // (any thread may ask)
     // the refusal of every entry point that must not run beside submitted batches: true + the message while some are in flight
@@ -345,6 +347,30 @@ class Engine {
     // 0, or -1 + a message naming the utterance (and the token): the call's prosody arrays in range, neither speaking_rates nor
     // duration_override together with fixed_duration
     int check_prosody(const vits_process_opts& o, int B, int id_stride, const int32_t* id_lens, std::string& err) const;
+    // a stated pitch (include/vits.h "a stated pitch"; pitch.hip): the ratio of every utterance of a call that no per-utterance ratios were given for; 1 = off.
+    // 0, or -1 + a message with the handle unchanged (a ratio that is not finite or outside [0.5, 2]). Nothing touches the device here: the table is uploaded
+    // by the first call that shifts.
+    float pitch_ratio = 1.f;
+    int set_pitch(float ratio, std::string& err);
+    // the per-utterance ratios of the NEXT call (vits_model_set_pitch_ratios): copied here, taken by whichever entry point runs next (take_pitch_ratios: it
+    // uses them or refuses them; either way they are gone). NULL or n = 0 drops what was given. 0, or -1 + a message: n < 0, ratios NULL with n > 0
+    int set_pitch_ratios(const float* ratios, int n, std::string& err);
+    bool take_pitch_ratios(std::vector<float>& given);
+    // A call's pitch. An entry point constructs it first of all: that takes the ratios given for this call, whatever becomes of the call. resolve_pitch then
+    // decides: when some utterance's ratio is not 1, `pitch` points at `ratios` (the given ones, or the model value, per utterance) and o.speaking_rates at
+    // `rates` (r'_b = (float)((double)rate_b / (double)p_b)); with every ratio 1, `pitch` stays NULL and `o` the caller's struct as it was.
+    struct ResolvedPitch {
+        vits_process_opts o;
+        std::vector<float> given, ratios, rates;
+        bool have;  // (declared behind `given`, which its initialiser fills)
+        const float* pitch = nullptr;
+        ResolvedPitch(Engine& e, const vits_process_opts& opts) : o(opts), have(e.take_pitch_ratios(given)) {}
+    };
+    // 0, or -1 + a message naming the utterance: another count of ratios than utterances; a ratio that is not finite or outside [0.5, 2]; fixed_duration > 0
+    // or duration_override on an utterance whose ratio is not 1; an r'_b outside [0.1, 10]. The call's speaking_rates have passed check_prosody.
+    int resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const;
+    // the rows [B][4] = {P, N, N', K} of the most recently completed call (empty: it shifted nothing)
+    const int64_t* last_pitch(int& rows) const { return pt_.read(rows); }
     // any sample rate (include/vits.h vits_model_set_rates): 0 = the model's own rate (a rate equal to it is stored as 0). input: the PCM given to
     // conversion and alignment; output: every PCM the handle delivers. 0, or -1 + a message with the handle unchanged (a rate outside the range, a
     // table that is too large). Nothing touches the device here: a pair's table is uploaded by the first call that uses it (rate_table).
@@ -494,6 +520,8 @@ class Engine {
         int lv_rows = 0;              // levelling: rows of the slot's pinned copy this batch fills (0: no level was set)
         int lm_rows = 0;              // the limiter: likewise (0: it was off)
         int ed_rows = 0;              // stated edges: likewise (0: off); `lengths` is derived from them once `done` has passed
+        PinnedBuf<float> pitch_pinned;  // a stated pitch: the batch's ratios (host side of their H2D copy)
+        std::vector<int64_t> pt_rows;   // ... and its report rows [B][4], host arithmetic (empty: it shifted nothing)
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -576,7 +604,17 @@ class Engine {
     // The joins' device rows of a call of B utterances hold {o_b, n_b} [B][2] and, behind them, the track lengths T_g int32 [G]
     ReportRows<float> lv_, lm_;
     ReportRows<int64_t> ed_{sizeof(int)}, jn_;
-    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(); }
+    // the pitch stage's rows are host arithmetic (P, N and N' follow from the ratio and the frame count): the report never touches the device
+    ReportRows<int64_t> pt_;
+    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(); }
+    // a stated pitch: the interleaved table on the device (uploaded by the first call that shifts), a synchronous call's ratios on their way there, and the
+    // stage from its source into its destination, as the call's plan routes them: queued behind the last vocoder window, in front of run_edges
+    float* pitch_table_ = nullptr;
+    PinnedBuf<float> pitch_host_;
+    std::vector<float> pitch_given_;      // vits_model_set_pitch_ratios: the next call's ratios
+    bool pitch_given_set_ = false;
+    const float* call_pitch_ = nullptr;   // the resolved ratios [B] of the call being queued (ResolvedPitch::pitch): non-null MEANS that the stage runs
+    int run_pitch(Call& c);
     PinnedBuf<int64_t> join_table_host_;  // a joined call's table (host side of its H2D copy)
     std::vector<int32_t> join_index_;     // ... and what its report names each utterance (process_joined: b, or the caller's index)
     // the join of a joined call (join.hip) from its source into its destination, as the call's plan routes them: queued behind the edges stage, in front of run_level

@@ -10,6 +10,11 @@ namespace vits {
 int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* ids, const int32_t* id_lens, int id_stride,
                         const int32_t* speakers, float noise_scale, const vits_process_opts& o, int32_t* durations, int64_t* frames_out, float* scores,
                         std::string& err) {
+    std::vector<float> given;
+    if (take_pitch_ratios(given)) {
+        err = "alignment does not take the ratios of vits_model_set_pitch_ratios (it produces no audio)";
+        return -1;
+    }
     if (refuse_pending(err)) return -1;
     if (B <= 0 || id_stride <= 0) {
         err = "empty batch";

@@ -225,6 +225,12 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
 // ---- one conversion call -------------------------------------------------------------------------------------------------------
 int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
                           vits_batch_result* out, std::string& err) {
+    std::vector<float> given;
+    if (take_pitch_ratios(given)) {
+        err = "voice conversion does not take the ratios of vits_model_set_pitch_ratios (a pitch is paid for by the duration predictor's stretch, and a conversion "
+              "predicts no durations)";
+        return -1;
+    }
     if (refuse_pending(err)) return -1;
     if (B <= 0 || !pcm || !pcm_lens || pcm_stride <= 0) {
         err = B <= 0 ? "empty batch" : "null PCM, null lengths or pcm_stride <= 0";

@@ -38,7 +38,9 @@ int Engine::layout_stage_two(Call& c) {
     // the rows behind the edges stage (Engine::plan_rows): one per utterance at E_stride, or — a joined call — one per track at J_stride
     const int R = c.rows;
     const int J_stride = c.J_stride = c.join ? round_up(std::max(c.mr_max, 1), 32) : 0;
-    const int L_stride = c.join ? J_stride : E_stride;
+    // a stated pitch: the rows behind the stage, at the bound of N' at the smallest ratio; with the edges stage off a levelled buffer follows them (delivery_plan.cpp)
+    const int P_stride = c.P_stride = c.pitched() ? 2 * S_stride : 0;
+    const int L_stride = c.join ? J_stride : (c.dp[STAGE_EDGES].runs || !c.pitched() ? E_stride : P_stride);
     // VITS_ARITH_F32_SPLIT: three bf16 planes per conv input of the wide stages' resblocks (conv_split.hip): the stage input once, t and the stream per
     // concurrently running resblock
     size_t sp_elems = 0;
@@ -80,11 +82,14 @@ int Engine::layout_stage_two(Call& c) {
         s2.lvl_scratch = dp.need(NEED_LVL_SCRATCH) ? a.alloc<char>(level_scratch_bytes(R, c.mr_max, level_plan_.S)) : nullptr;
         s2.lim_scratch = dp.need(NEED_LIM_SCRATCH) ? a.alloc<char>(limit_scratch_bytes(R, c.mr_max)) : nullptr;
         s2.wave_edge = dp.need(NEED_WAVE_EDGE) ? a.alloc<float>((size_t)B * E_stride) : nullptr;
-        s2.ed_scratch = dp.need(NEED_ED_SCRATCH) ? a.alloc<char>(edges_scratch_bytes(B, smax[n_up], edges_plan_.W)) : nullptr;
+        s2.ed_scratch = dp.need(NEED_ED_SCRATCH) ? a.alloc<char>(edges_scratch_bytes(B, c.head_max(), edges_plan_.W)) : nullptr;
         s2.lvl_ranges = dp.need(NEED_LVL_RANGES) ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
         s2.tile_maps = c.tm_total ? a.alloc<TileEntry>((size_t)c.tm_total) : nullptr;
         s2.wave_join = dp.need(NEED_WAVE_JOIN) ? a.alloc<float>((size_t)R * J_stride) : nullptr;
         s2.join_table = dp.need(NEED_JOIN_TABLE) ? a.alloc<int64_t>(join_table_elems(B, R)) : nullptr;
+        s2.wave_pitch = dp.need(NEED_WAVE_PITCH) ? a.alloc<float>((size_t)B * P_stride) : nullptr;
+        s2.pitch_ratios = dp.pitch.runs ? a.alloc<float>((size_t)B) : nullptr;
+        s2.pitch_lens = dp.pitch.runs ? a.alloc<int>((size_t)B) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

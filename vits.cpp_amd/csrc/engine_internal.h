@@ -214,6 +214,9 @@ struct Call {
         TileEntry* tile_maps;  // ragged fp32 calls: the lists of existing tiles of every window (tm_total entries), or null
         float* wave_join;      // a joined call, unless the join writes straight to out_device: the tracks [G][J_stride]
         int64_t* join_table;   // a joined call: join_table(plan)
+        float* wave_pitch;     // a stated pitch, unless the stage writes straight to out_device: the varispeed rows [B][P_stride]
+        float* pitch_ratios;   // a stated pitch: the ratios [B]
+        int* pitch_lens;       // ... and N' of every row [B], written by the stage
     } s2{};
     // Ragged batches, exact fp32 vocoder: the lists of existing tiles (tile_map.h) of the large launches whose dense grid would hold empty blocks. One list per
     // (window, length vector, tile width): length vector i = the lengths at vocoder stage i (conv_pre, the stage's resblocks), convt = upsampler i (columns
@@ -253,6 +256,7 @@ struct Call {
             case BUF_OUT: out.p = s2.wave_out; break;
             case BUF_CALLER: out.p = (float*)o.out_device; break;
             case BUF_JOIN: out.p = s2.wave_join; break;
+            case BUF_PITCH: out.p = s2.wave_pitch; break;
             default: break;
         }
         switch (r.stride) {
@@ -261,6 +265,7 @@ struct Call {
             case STRIDE_OUT_WS: out.stride = out_ws; break;
             case STRIDE_CALLER: out.stride = o.out_device_stride; break;
             case STRIDE_J: out.stride = J_stride; break;
+            case STRIDE_P: out.stride = P_stride; break;
             default: break;
         }
         return out;
@@ -284,6 +289,19 @@ struct Call {
     // stage's stride and the join's input are sized and read by.
     JoinPlan* join = nullptr;
     int rows = 0, utt_max = 0, J_stride = 0;
+    // A stated pitch (pitch: the call's resolved ratios [B], Engine::resolve_pitch; null: the stage is off): the varispeed runs between the vocoder and the edges stage. What the edges stage (and,
+    // with it off, everything behind it) reads is then its output: pit_len / pit_max = N' of every row, host arithmetic from the frame counts (Engine::plan_rows);
+    // P_stride = 2 S_stride, the stage's row stride; pit_rows = the report [B][4]; pitch_pin = the pinned memory the ratios travel through (the slot's for a
+    // pipelined batch). head_lens / head_len / head_max = the rows at the head of the chain, which the edges stage reads: the pitch stage's, else the vocoder's.
+    std::vector<int> pit_len;
+    std::vector<int64_t> pit_rows;
+    int pit_max = 0, P_stride = 0;
+    PinnedBuf<float>* pitch_pin = nullptr;
+    const float* pitch = nullptr;
+    bool pitched() const { return pitch != nullptr; }
+    const int* head_lens() const { return pitched() ? s2.pitch_lens : s1.stage_lens + (size_t)n_up * B; }
+    const std::vector<int>& head_len() const { return pitched() ? pit_len : slen[n_up]; }
+    int head_max() const { return pitched() ? pit_max : smax[n_up]; }
     const int* utt_lens = nullptr;
     bool rows_planned = false;
 

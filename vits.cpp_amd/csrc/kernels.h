@@ -903,6 +903,45 @@ struct JoinCall {
 hipError_t launch_join_offsets(const JoinCall& c, hipStream_t s);
 hipError_t launch_join_apply(const JoinCall& c, hipStream_t s);
 
+// ---- a stated pitch: varispeed by a ratio per row (pitch.hip; the definition: include/vits.h "a stated pitch", DESIGN.md §8 "A stated pitch") ----
+// Row b of N samples is played back p_b times faster: P = p 2^24 (an integer for every float in [0.5, 2]), N' = ceil(N 2^24 / P), output m sits at t = m P
+// (64-bit), n0 = t >> 24, f = t & (2^24 - 1). The prototype is the resampler's (Kaiser-windowed sinc, Z = 32, beta = 9, rolloff 0.92), tabulated at Q = 256
+// points per zero crossing with its fp32 differences, and read with linear interpolation at an integer index: nothing about a tap's weight is floating point
+// until fmaf(fr, D[i], G[i]). y[m] is ONE ascending chain of K = 2 R + 1 fused multiply-adds; a row with P = 2^24 is copied bit for bit.
+constexpr int kPitchZ = 32, kPitchQ = 256, kPitchTableN = kPitchZ * kPitchQ + 2;  // G and D hold kPitchTableN floats each
+constexpr int64_t kPitchOne = (int64_t)1 << 24;
+constexpr int64_t kPitchS0 = 15435038;  // floor(0.92 2^24)
+constexpr float kPitchMinRatio = 0.5f, kPitchMaxRatio = 2.0f;
+constexpr int64_t kPitchMaxLen = (int64_t)1 << 30;
+constexpr int kPitchMaxR = 70;  // R at the largest ratio (K = 141)
+struct PitchPlan {
+    int64_t P = kPitchOne, S = kPitchS0;
+    int R = 35, K = 71;
+    int64_t n_out = 0;
+};
+// host only (pitch_host.cpp). false + a message: a ratio that is not finite or outside [0.5, 2], n outside [0, 2^30]
+bool pitch_plan(float ratio, int64_t n, PitchPlan& p, std::string& err);
+// [2][kPitchTableN]: G, then D
+std::vector<float> pitch_table();
+// ... and as the kernel reads it, [kPitchTableN][2] = {G[i], D[i]}
+std::vector<float> pitch_table_pairs();
+// the definition in double, sequentially; y gets p.n_out samples
+void pitch_host(const float* x, int64_t n, const PitchPlan& p, const float* table, double* y);
+constexpr int kPitchTile = 1024;  // output samples per block
+struct PitchCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;      // device [batch]: valid input samples of each row (<= x_stride); nothing behind them is read
+    const float* ratios = nullptr;  // device [batch]: p_b, each in [0.5, 2] (the host's check; the kernel clamps, so that no index depends on it)
+    float* y = nullptr;             // device [batch][y_stride], not x; samples behind N' are left as they are
+    int64_t y_stride = 0;
+    const float* table = nullptr;  // device [kPitchTableN][2]: {G[i], D[i]} (pitch_table INTERLEAVED: one 8-byte load per tap)
+    int* lens_out = nullptr;       // device [batch], optional: N' of each row
+    int batch = 0;
+    int64_t max_out = 0;  // the longest output row of the call (host side: sizes the grid); y_stride >= max_out
+};
+hipError_t launch_pitch(const PitchCall& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
