@@ -1,5 +1,6 @@
 // engine.cpp — one call from ids to PCM (see engine.h): input checks, the two arenas, the single host read of the frame counts,
-// vocoder windows / streaming, results. The phases themselves live in engine_stage1.cpp, engine_flow.cpp and engine_vocoder.cpp.
+// vocoder windows (window_plan.h) / streaming, results. The phases themselves live in engine_stage1.cpp, engine_flow.cpp and engine_vocoder.cpp, the delivery
+// chain behind the vocoder in engine_delivery.cpp.
 // Compiled with hipcc as host C++.
 #include <cmath>
 #include <numeric>
@@ -146,16 +147,6 @@ int Engine::check_speakers(const vits_process_opts& o, int B, std::string& err) 
     return 0;
 }
 
-namespace {
-bool rate_ok(float r) { return std::isfinite(r) && r >= 0.1f && r <= 10.f; }
-bool noise_scale_ok(float v) { return std::isfinite(v) && v >= 0.f && v <= 10.f; }
-std::string fmt_float(float v) {
-    char buf[32];
-    std::snprintf(buf, sizeof(buf), "%.9g", (double)v);
-    return buf;
-}
-}  // namespace
-
 int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
     if (!rate_ok(rate) || !noise_scale_ok(ns) || !noise_scale_ok(nsd)) {
         err = "vits_model_set_prosody(" + fmt_float(rate) + ", " + fmt_float(ns) + ", " + fmt_float(nsd) + "): " +
@@ -164,398 +155,6 @@ int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
     }
     speaking_rate = rate, noise_scale = ns, noise_scale_dur = nsd;
     return 0;
-}
-
-int Engine::set_pitch(float ratio, std::string& err) {
-    PitchPlan p;
-    std::string why;
-    if (!pitch_plan(ratio, 0, p, why)) {
-        err = "vits_model_set_pitch: " + why;
-        return -1;
-    }
-    pitch_ratio = ratio;
-    return 0;
-}
-
-int Engine::set_pitch_ratios(const float* ratios, int n, std::string& err) {
-    if (n < 0 || (!ratios && n > 0)) {
-        err = "vits_model_set_pitch_ratios: " + std::string(n < 0 ? "n < 0" : "null argument (ratios is NULL with n > 0)");
-        return -1;
-    }
-    pitch_given_.assign(ratios, ratios + (ratios ? n : 0));
-    pitch_given_set_ = ratios && n > 0;
-    return 0;
-}
-
-bool Engine::take_pitch_ratios(std::vector<float>& given) {
-    const bool was = pitch_given_set_;
-    given.clear();
-    given.swap(pitch_given_);
-    pitch_given_set_ = false;
-    return was;
-}
-
-int Engine::resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const {
-    const vits_process_opts& o = rp.o;
-    const bool have = rp.have;
-    if (have && (int)rp.given.size() != B) {
-        err = "vits_model_set_pitch_ratios gave " + std::to_string(rp.given.size()) + " ratios, and this call has " + std::to_string(B) + " utterances";
-        return -1;
-    }
-    const float* given = have ? rp.given.data() : nullptr;
-    bool any = false;
-    for (int b = 0; b < B; ++b) {
-        const float p = given ? given[b] : pitch_ratio;
-        if (!std::isfinite(p) || p < kPitchMinRatio || p > kPitchMaxRatio) {
-            err = "pitch_ratios[" + std::to_string(b) + "] = " + fmt_float(p) + ": must be finite and in [0.5, 2]";
-            return -1;
-        }
-        any = any || p != 1.f;
-    }
-    if (!any) return 0;
-    rp.ratios.resize((size_t)B);
-    rp.rates.resize((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        const float p = rp.ratios[(size_t)b] = given ? given[b] : pitch_ratio;
-        const float rate = o.speaking_rates ? o.speaking_rates[b] : speaking_rate;
-        rp.rates[(size_t)b] = rate;  // (o.speaking_rates is the caller's until the last line)
-        if (p == 1.f) continue;
-        const std::string who = "utterance " + std::to_string(b) + " has the pitch ratio " + fmt_float(p) + ", which it pays for by being spoken slower by that ratio: ";
-        if (o.fixed_duration > 0) {
-            err = who + "fixed_duration > 0 leaves the duration predictor nothing to stretch";
-            return -1;
-        }
-        if (o.duration_override) {
-            const int len = std::min(id_stride, std::max(0, id_lens ? id_lens[b] : id_stride));
-            for (int t = 0; t < len; ++t)
-                if (o.duration_override[(size_t)b * id_stride + t] >= 0) {
-                    err = who + "duration_override states token " + std::to_string(t) + "'s frames, which the stretch would have to change";
-                    return -1;
-                }
-        }
-        const float r = rp.rates[(size_t)b] = (float)((double)rate / (double)p);
-        if (!rate_ok(r)) {
-            err = who + "its speaking rate " + fmt_float(rate) + " becomes " + fmt_float(r) + ", outside [0.1, 10]";
-            return -1;
-        }
-    }
-    rp.pitch = rp.ratios.data();
-    rp.o.speaking_rates = rp.rates.data();
-    return 0;
-}
-
-int Engine::set_rates(int in_rate, int out_rate, std::string& err) {
-    int stored[2] = {in_rate, out_rate};
-    for (int side = 0; side < 2; ++side) {
-        int& r = stored[side];
-        if (r == 0 || r == hp.sampling_rate) {
-            r = 0;
-            continue;
-        }
-        ResamplePlan p;
-        std::string why;
-        if (!(side == 0 ? resample_plan(r, hp.sampling_rate, p, why) : resample_plan(hp.sampling_rate, r, p, why))) {
-            err = std::string("vits_model_set_rates: ") + (side == 0 ? "input_rate: " : "output_rate: ") + why + " (the model's rate is " + std::to_string(hp.sampling_rate) + " Hz; 0 = that rate)";
-            return -1;
-        }
-    }
-    input_rate_ = stored[0], output_rate_ = stored[1];
-    return 0;
-}
-
-const RateTable* Engine::rate_table(int fi, int fo, std::string& err) {
-    const auto it = rate_tabs_.find({fi, fo});
-    if (it != rate_tabs_.end()) return &it->second;
-    RateTable t;
-    if (!resample_plan(fi, fo, t.plan, err)) return nullptr;
-    // the kernel reads [K][L]: at one tap the threads of a wave differ in their phase only (resample.hip)
-    const std::vector<float> h = resample_taps(t.plan);
-    std::vector<float> ht(h.size());
-    for (int p = 0; p < t.plan.L; ++p)
-        for (int k = 0; k < t.plan.K; ++k) ht[(size_t)k * t.plan.L + p] = h[(size_t)p * t.plan.K + k];
-    if (!(t.taps = upload(ht))) {  // (owned by the handle and counted in weight_bytes from here on)
-        err = "resampling table: device allocation failed";
-        return nullptr;
-    }
-    return &rate_tabs_.emplace(std::make_pair(fi, fo), t).first->second;
-}
-
-hipError_t Engine::resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples) {
-    prof.begin(name, 2.0 * rc.plan.K * (double)out_samples, 4.0 * ((double)in_samples + (double)out_samples), stream, /*chain=*/true);
-    const hipError_t e = launch_resample(rc, stream);
-    prof.end(stream);
-    return e;
-}
-
-int Engine::set_level(int kind, float value_db, float ceiling_db, std::string& err) {
-    const char* who = "vits_model_set_level: ";
-    std::string why;
-    if (!level_values_ok(kind, value_db, ceiling_db, why)) {
-        err = who + why;
-        return -1;
-    }
-    if (kind != VITS_LEVEL_NONE) {
-        LoudnessPlan p;
-        if (!loudness_plan(hp.sampling_rate, p, why)) {
-            err = who + ("the model's " + why);
-            return -1;
-        }
-        level_plan_ = p;
-    }
-    // (with the limiter on a gain is delivered under the ceiling too: the value is checked and kept)
-    const bool gain_ceiling = kind == VITS_LEVEL_GAIN && limit_mode_ != VITS_LIMIT_OFF;
-    if (gain_ceiling && !level_values_ok(VITS_LEVEL_LOUDNESS, 0.f, ceiling_db, why)) {
-        err = who + why;
-        return -1;
-    }
-    level_kind_ = kind;
-    level_value_ = kind >= VITS_LEVEL_GAIN ? value_db : 0.f;
-    level_ceiling_ = kind == VITS_LEVEL_LOUDNESS || gain_ceiling ? ceiling_db : 0.f;
-    return 0;
-}
-
-int Engine::set_limiter(int mode, std::string& err) {
-    const char* who = "vits_model_set_limiter: ";
-    if (mode != VITS_LIMIT_OFF && mode != VITS_LIMIT_TRUE_PEAK) {
-        err = who + ("unknown mode " + std::to_string(mode));
-        return -1;
-    }
-    if (mode != VITS_LIMIT_OFF) {
-        LimiterPlan p;
-        std::string why;
-        if (!limiter_plan(hp.sampling_rate, p, why)) {
-            err = who + ("the model's " + why);
-            return -1;
-        }
-        limit_plan_ = p;
-    }
-    limit_mode_ = mode;
-    return 0;
-}
-
-int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err, bool joined) const {
-    DeliveryAsk ask;
-    ask.edges = edges_on();
-    switch (level_kind_) {
-        case VITS_LEVEL_NONE: ask.level = DLEVEL_NONE; break;
-        case VITS_LEVEL_MEASURE: ask.level = DLEVEL_MEASURE; break;
-        case VITS_LEVEL_GAIN: ask.level = DLEVEL_GAIN; break;
-        default: ask.level = DLEVEL_WHOLE; break;  // (peak, loudness)
-    }
-    ask.limiter = limit_mode_ != VITS_LIMIT_OFF;
-    ask.rate = output_rate_ != 0;
-    ask.out_device = o.out_device != nullptr;
-    ask.on_chunk = o.on_chunk != nullptr;
-    ask.async = o.async != 0;
-    ask.joined = joined;
-    ask.pitch = call_pitch_ != nullptr;  // (resolved: Engine::resolve_pitch)
-    plan = delivery_plan(ask);
-    switch (plan.refusal) {
-        case DELIVER_OK: return 0;
-        case REFUSE_LIMIT_STREAM:
-            err = "on_chunk streams an utterance while it is being made, and this handle's limiter (vits_model_set_limiter) is on: the gain of a sample looks " +
-                  std::to_string(limit_plan_.A) + " samples ahead and " + std::to_string(limit_plan_.H + limit_plan_.A) +
-                  " back, so a window's last samples are not final when it ends, and the halo of finished samples that streaming would need is not built: "
-                  "stream with VITS_LIMIT_OFF, or limit without on_chunk";
-            break;
-        case REFUSE_LEVEL_STREAM:
-            err = "on_chunk streams an utterance while it is being made, and this handle's level (vits_model_set_level: measure, peak or loudness) needs the whole "
-                  "utterance before its first sample can leave: only VITS_LEVEL_GAIN streams";
-            break;
-        case REFUSE_EDGES_STREAM:
-            err = "on_chunk streams an utterance while it is being made, and this handle's edges stage (vits_model_set_edges) is on: the end of the utterance decides "
-                  "what leaves (the last active window, the fade-out and the silence behind it count from there), so no sample can leave before the last one is made: "
-                  "stream with VITS_EDGES_OFF, or set edges without on_chunk";
-            break;
-        case REFUSE_EDGES_ASYNC:
-            err = "async returns before the device has finished, and this handle's edges stage (vits_model_set_edges) is on: lengths[] of the result is read from the "
-                  "device (the trimmed length depends on the audio), which needs a host read behind the call's work: call without async, or pipeline with "
-                  "vits_model_submit_batch / vits_model_wait";
-            break;
-        case REFUSE_JOIN_STREAM:
-            err = "vits_model_process_joined: on_chunk streams an utterance while it is being made, and a track is laid out once every utterance of it has its length "
-                  "(an overlap reaches back into the utterance in front): call without on_chunk";
-            break;
-        case REFUSE_JOIN_ASYNC:
-            err = "vits_model_process_joined: async returns before the device has finished, and the lengths of the tracks are read from the device behind the call's "
-                  "work: call without async";
-            break;
-        case REFUSE_PITCH_STREAM:
-            err = "on_chunk streams an utterance while it is being made, and an utterance of this call has a pitch ratio other than 1 (vits_model_set_pitch_ratios, "
-                  "vits_model_set_pitch): streaming pitch is not built (the varispeed of a window's last samples reads the next window's first): call without "
-                  "on_chunk, or with every ratio 1";
-            break;
-        case REFUSE_PITCH_ASYNC:
-            err = "async returns before the device has finished, and an utterance of this call has a pitch ratio other than 1 (vits_model_set_pitch_ratios, "
-                  "vits_model_set_pitch): streaming pitch is not built, and the ratios travel to the device through memory the next call reuses: call without async, "
-                  "or pipeline with vits_model_submit_batch / vits_model_wait";
-            break;
-        default: err = "this combination of delivery stages is not supported"; break;
-    }
-    return -1;
-}
-
-// the tail of a levelling call: loudness, peak and gain of every utterance of the stage's source (the plan's: what the vocoder or the edges stage wrote; under
-// VITS_LEVEL_MEASURE that may be out_device, and no PCM path changes) -> the levels rows, the multiply into the stage's destination (every kind but MEASURE; a
-// streaming call has multiplied window by window already), and the rows on their way to the slot's pinned copy
-int Engine::run_level(Call& c) {
-    std::string& err = c.err;
-    const int B = c.rows, n_up = c.n_up;  // (the rows behind the edges stage: the utterances, or a joined call's tracks)
-    const Call::Rows src = c.rows_of(c.dp[STAGE_LEVEL].src), dst = c.rows_of(c.dp[STAGE_LEVEL].dst);
-    HIP_OK(lv_.grow(B, owned_, weight_bytes));
-    const int64_t samples = c.sum_frames * c.M + (int64_t)c.B * c.sadd[n_up];
-    LevelCall lc;
-    lc.x = src.p;
-    lc.x_stride = src.stride;
-    lc.lens = c.mr_lens;
-    lc.batch = B;
-    lc.max_len = c.mr_max;
-    lc.plan = level_plan_;
-    lc.scratch = c.s2.lvl_scratch;
-    lc.kind = c.lev;
-    lc.value_db = level_value_;
-    lc.ceiling_db = level_ceiling_;
-    lc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);
-    lc.levels = lv_.dev();
-    // two walks of the cascade (9 fp64 fma a sample each) and the squares; the samples read twice
-    prof.begin("level_measure", 2.0 * (2 * 9 + 1) * (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
-    hipError_t e = launch_level_measure(lc, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    if (c.dp.limits) {
-        // the limiter in place of the plain multiply: meter, g0 (which replaces the measured row's gain), limiter, meter of what is delivered
-        HIP_OK(lm_.grow(B, owned_, weight_bytes));
-        const RateTable* up = rate_table(hp.sampling_rate, 4 * hp.sampling_rate, err);
-        if (!up) return -1;
-        LimitCall mc;
-        mc.x = src.p;
-        mc.x_stride = src.stride;
-        mc.y = dst.p;
-        mc.y_stride = dst.stride;
-        mc.lens = lc.lens;
-        mc.batch = B;
-        mc.max_len = c.mr_max;
-        mc.plan = limit_plan_;
-        mc.taps = up->taps;
-        mc.scratch = c.s2.lim_scratch;
-        mc.kind = c.lev;
-        mc.value_db = level_value_;
-        mc.gain = lc.gain;
-        mc.ceiling = (float)std::pow(10.0, (double)level_ceiling_ / 20.0);
-        mc.levels = lv_.dev();
-        mc.limits = lm_.dev();
-        // two meter passes (4 K fma a sample each); the doubling steps and the mean; x, e and y read, e and y written
-        prof.begin("limit", (2.0 * 2 * 4 * limit_plan_.up.K + limit_plan_.A + 16) * (double)samples, 20.0 * (double)samples, stream, /*chain=*/true);
-        e = launch_limit(mc, stream);
-        prof.end(stream);
-        HIP_OK(e);
-        HIP_OK(lm_.queue_copy(a1_slot_, B, stream));
-    } else if (c.dp.multiplies && !c.o.on_chunk) {
-        LevelScale sc;
-        sc.x = src.p;
-        sc.x_stride = src.stride;
-        sc.y = dst.p;
-        sc.y_stride = dst.stride;
-        sc.lens = lc.lens;
-        sc.levels = lv_.dev();
-        sc.batch = B;
-        sc.max_range = c.mr_max;
-        prof.begin("level_scale", (double)samples, 8.0 * (double)samples, stream, /*chain=*/true);
-        e = launch_level_scale(sc, stream);
-        prof.end(stream);
-        HIP_OK(e);
-    }
-    HIP_OK(lv_.queue_copy(a1_slot_, B, stream));
-    prof.fence();
-    return 0;
-}
-
-int Engine::set_edges(const vits_edges_desc* d, std::string& err) {
-    const vits_edges_desc off{(uint32_t)sizeof(vits_edges_desc), VITS_EDGES_OFF, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!d || (d->struct_size == sizeof(vits_edges_desc) && d->mode == VITS_EDGES_OFF)) {
-        edges_desc_ = off;
-        return 0;
-    }
-    EdgesPlan p;
-    std::string why;
-    if (!edges_plan(hp.sampling_rate, *d, p, why)) {
-        err = "vits_model_set_edges: " + why;
-        return -1;
-    }
-    ed_fades_stale_ = ed_fades_stale_ || p.Fi != edges_plan_.Fi || p.Fo != edges_plan_.Fo;  // (the tables depend on the two counts alone)
-    edges_plan_ = p;
-    edges_desc_ = *d;
-    if (p.mode == VITS_EDGES_PAD) edges_desc_.threshold_db = 0.f;  // (ignored, and not kept)
-    return 0;
-}
-
-// the edges stage of a call: the vocoder's waveform -> the stage's destination (the plan's: the call's own buffer, or out_device when nothing follows), the
-// trimmed lengths (c.mr_lens: what every stage behind this one reads its rows' lengths from) and the rows on the device, and the rows on their way to the
-// slot's pinned copy
-int Engine::run_edges(Call& c) {
-    std::string& err = c.err;
-    const int B = c.B, n_up = c.n_up;
-    const EdgesPlan& p = edges_plan_;
-    const Call::Rows src = c.rows_of(c.dp[STAGE_EDGES].src), dst = c.rows_of(c.dp[STAGE_EDGES].dst);
-    if (ed_fades_stale_) {
-        const std::vector<float> t = edges_fades(p);
-        if (ed_fades_) {
-            // (the previous desc's tables: nothing reads them any more once the device is idle, and hipFree waits for that)
-            owned_.erase(std::remove(owned_.begin(), owned_.end(), (void*)ed_fades_), owned_.end());
-            hipFree(ed_fades_);
-            weight_bytes -= (int64_t)ed_fades_n_ * 4;
-            ed_fades_ = nullptr, ed_fades_n_ = 0;
-        }
-        if (!t.empty()) {
-            if (!(ed_fades_ = upload(t))) {
-                err = "fade tables: device allocation failed";
-                return -1;
-            }
-            ed_fades_n_ = t.size();
-        }
-        ed_fades_stale_ = false;
-    }
-    EdgesCall ec;
-    ec.x = src.p;
-    ec.x_stride = src.stride;
-    ec.lens = c.head_lens();
-    ec.y = dst.p;
-    ec.y_stride = dst.stride;
-    ec.batch = B;
-    ec.max_len = c.head_max();
-    ec.plan = p;
-    ec.fades = ed_fades_;
-    ec.scratch = c.s2.ed_scratch;
-    ec.lens_out = static_cast<int*>(ed_.tail());  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
-    ec.rows = ed_.dev();
-    const int64_t samples = c.sum_frames * c.M + (int64_t)B * c.sadd[n_up];
-    hipError_t e = hipSuccess;
-    if (p.mode != VITS_EDGES_PAD) {
-        // one multiply-add per sample in fp64; the samples read once, one double per window written
-        prof.begin("edges_window", 2.0 * (double)samples, 4.0 * (double)samples + 8.0 * (double)samples / p.W, stream, /*chain=*/true);
-        e = launch_edges_window(ec, stream);
-        prof.end(stream);
-        HIP_OK(e);
-    }
-    prof.begin("edges_bounds", 0, 8.0 * (double)samples / p.W, stream, /*chain=*/true);
-    e = launch_edges_bounds(ec, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    // two multiplies per sample; the samples read once, the bound written once
-    prof.begin("edges_apply", 2.0 * (double)samples, 8.0 * (double)samples + 4.0 * (double)B * (p.Pl + p.Pt), stream, /*chain=*/true);
-    e = launch_edges_apply(ec, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    HIP_OK(ed_.queue_copy(a1_slot_, B, stream));
-    prof.fence();
-    return 0;
-}
-
-void Engine::edges_lengths(const int64_t* rows, int B, int64_t* lengths) const {
-    ResamplePlan plan;  // (the identity without an output rate)
-    std::string ignored;
-    if (output_rate_) resample_plan(hp.sampling_rate, output_rate_, plan, ignored);  // (accepted by set_rates already)
-    for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(rows[(size_t)4 * b + 2]);
 }
 
 void Engine::batch_landed(Pending& p, int slot, bool append) {
@@ -830,6 +429,34 @@ void Engine::store_durations(const Call& c, const float* pinned) const {
     for (size_t i = 0; i < n; ++i) c.o.durations_out[i] = (int32_t)pinned[i];
 }
 
+// the dispatcher query (opts.frames_only): predicted frames / samples per utterance — or, a joined call, per track — and no audio (buffer sizing, shard balancing by frames)
+int Engine::frames_only_result(Call& c, vits_batch_result* out) {
+    std::string& err = c.err;
+    const int B = c.B;
+    const JoinPlan* join = c.join;
+    const std::vector<int>& frames = c.frames;
+    if (out && join) {
+        // per track: the bound a full call stays within, at the rate it would deliver at, and the frames of the track's utterances
+        if (plan_rows(c)) return -1;
+        const std::vector<int>& len = output_rate_ ? c.out_len : c.mr_len;
+        fill_result(out, join->tracks, (size_t)(output_rate_ ? c.out_max : c.mr_max), len.begin(), c.track_frames().begin());
+    } else if (out) {
+        // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
+        ResamplePlan plan;
+        if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
+        // (stated edges: the bound N + Pl + Pt of every utterance, the size to allocate: exact under VITS_EDGES_PAD, an upper bound when the stage trims)
+        const int64_t pads = edges_on() ? edges_plan_.Pl + edges_plan_.Pt : 0;
+        std::vector<int64_t> lengths(B);
+        // (a stated pitch: N' of every utterance in place of the vocoder's sample count)
+        if (c.pitched() && plan_rows(c)) return -1;
+        for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.head_len()[(size_t)b] + pads);
+        fill_result(out, B, (size_t)plan.out_len(c.head_max() + pads), lengths.begin(), frames.begin());
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    prof.fence();
+    return 0;
+}
+
 int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                          std::string& err, Pending* pend, JoinPlan* join) {
     if (B <= 0 || id_stride <= 0) {
@@ -982,33 +609,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         d.bs = id_stride;
         snapshot("durations", d, 1, c.Tmax, B, c.tlen);
     }
-    if (o.frames_only) {
-        // dispatcher query: predicted frames / samples per utterance, no audio (buffer sizing, shard balancing by frames)
-        if (out && join) {
-            // per track: the bound a full call stays within, at the rate it would deliver at, and the frames of the track's utterances
-            if (plan_rows(c)) return -1;
-            const std::vector<int>& len = output_rate_ ? c.out_len : c.mr_len;
-            std::vector<int64_t> tf((size_t)join->tracks, 0);
-            for (int g = 0; g < join->tracks; ++g)
-                for (int b = join->first[(size_t)g]; b < join->first[(size_t)g + 1]; ++b) tf[(size_t)g] += frames[b];
-            fill_result(out, join->tracks, (size_t)(output_rate_ ? c.out_max : c.mr_max), len.begin(), tf.begin());
-        } else if (out) {
-            // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
-            ResamplePlan plan;
-            if (output_rate_ && !resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
-            // (stated edges: the bound N + Pl + Pt of every utterance, the size to allocate: exact under VITS_EDGES_PAD, an upper bound when the stage trims)
-            const int64_t pads = edges_on() ? edges_plan_.Pl + edges_plan_.Pt : 0;
-            std::vector<int64_t> lengths(B);
-            // (a stated pitch: N' of every utterance in place of the vocoder's sample count)
-            if (c.pitched() && plan_rows(c)) return -1;
-            for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.head_len()[(size_t)b] + pads);
-            fill_result(out, B, (size_t)plan.out_len(c.head_max() + pads), lengths.begin(), frames.begin());
-        }
-        HIP_OK(hipStreamSynchronize(stream));
-        prof.fence();
-        return 0;
-    }
-
+    if (o.frames_only) return frames_only_result(c, out);
     return run_stage_two(c, out, pend, want_async);
 }
 
@@ -1024,17 +625,16 @@ void Engine::plan_tile_maps(Call& c) {
     const size_t nk = hp.rb_k.size();
     const VocPolicy pol = voc_policy(c);
     std::vector<int> la(B), lb(B);
-    for (size_t wi = 0; wi < c.wins.size(); ++wi) {
-        const int Lw = c.wins[wi].hi - c.wins[wi].lo;
-        int64_t frames = 0;  // (WinCtx::ssum[0])
-        for (int b = 0; b < B; ++b) frames += c.win_len(wi, 0, b);
-        auto smax = [&](int i) { return Lw * c.smul[i] + c.sadd[i]; };  // (WinCtx::smax)
+    const WindowPlan& win = c.win;
+    for (size_t wi = 0; wi < win.size(); ++wi) {
+        const int64_t frames = win.stage_sum(wi, 0);
+        auto smax = [&](int i) { return win.stage_max(wi, i); };
         auto want = [&](int vec, int width, bool convt, int64_t dense_blocks) {
             for (const Call::TileMapJob& j : c.tm_jobs)
                 if (j.win == (int)wi && j.vec == vec && j.width == width && j.convt == convt) return;
             if (!kn.tile_map && dense_blocks < kSmallGridBlocks) return;
             const int vo = convt ? vec + 1 : vec;
-            for (int b = 0; b < B; ++b) la[b] = c.win_len(wi, vec, b), lb[b] = c.win_len(wi, vo, b);
+            for (int b = 0; b < B; ++b) la[b] = win.len(wi, vec, b), lb[b] = win.len(wi, vo, b);
             if (!kn.tile_map && !tile_map_needed(la.data(), lb.data(), B, smax(vec), smax(vo), width, convt)) return;
             const int64_t n = tile_map_count(la.data(), lb.data(), B, width, convt);
             c.tm_jobs.push_back({(int)wi, vec, width, convt, c.tm_total, n});
@@ -1087,7 +687,7 @@ hipError_t Engine::upload_tile_maps(Call& c, PinnedBuf<TileEntry>& pinned) {
     if (hipError_t e = pinned.ensure(total, total + total / 4 + 64)) return e;
     std::vector<int> la(c.B), lb(c.B);
     for (const Call::TileMapJob& j : c.tm_jobs) {
-        for (int b = 0; b < c.B; ++b) la[b] = c.win_len(j.win, j.vec, b), lb[b] = c.win_len(j.win, j.convt ? j.vec + 1 : j.vec, b);
+        for (int b = 0; b < c.B; ++b) la[b] = c.win.len(j.win, j.vec, b), lb[b] = c.win.len(j.win, j.convt ? j.vec + 1 : j.vec, b);
         if (tile_map_fill(la.data(), lb.data(), c.B, j.width, j.convt, pinned.p + j.off) != j.n) return hipErrorUnknown;
     }
     prof.fence();
@@ -1099,256 +699,181 @@ void Engine::window_tile_maps(const Call& c, WinCtx& w) const {
         if (j.win == (int)w.wi && c.s2.tile_maps) (j.convt ? w.maps_up[j.vec] : w.maps[j.vec]).add(TileMapRef{c.s2.tile_maps + j.off, (int)j.n, j.width, j.convt});
 }
 
-// After window w the model-rate samples [0, E_w) of an utterance are final: everything once it has ended, else up to the end of the frames the window owns.
-// Row w of the table holds, per utterance, [what was final before w, what is final after it) in final_of's unit; a window that finalises nothing for an
-// utterance holds an empty range there.
-int Engine::upload_ranges(Call& c, std::vector<int>& table, int* dev, const std::function<int(int, int64_t)>& final_of) {
-    std::string& err = c.err;
-    const int B = c.B;
-    table.assign(c.wins.size() * (size_t)2 * B, 0);
-    std::vector<int> prev(B, 0);
-    for (size_t w = 0; w < c.wins.size(); ++w)
-        for (int b = 0; b < B; ++b) {
-            const Call::Win& wn = c.wins[w];
-            int done = prev[b];
-            if (c.frames[b] > wn.f0) {
-                const int64_t e = c.frames[b] <= wn.f1 ? c.slen[c.n_up][b] : (int64_t)wn.f1 * c.M;
-                done = std::max(done, final_of(b, e));
-            }
-            table[(w * 2) * B + b] = prev[b];
-            table[(w * 2 + 1) * B + b] = done;
-            prev[b] = done;
-        }
-    HIP_OK(hipMemcpyAsync(dev, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice, stream));
-    prof.fence();
-    HIP_OK(hipStreamSynchronize(stream));  // (pageable source; a streaming call is never a pipelined one)
-    return 0;
-}
+// ---- the streaming state of a call with a sink (opts.on_chunk): window w's finished samples are multiplied (VITS_LEVEL_GAIN), resampled (an output rate) and
+// shipped to pinned staging behind its kernels, and the PREVIOUS window's callbacks are served while the device works on this one
+struct Engine::ChunkStream {
+    Engine& e;
+    Call& c;
+    const bool rs, la;           // the output resampler runs; a level that multiplies
+    Call::Rows pcm;              // what the call delivers
+    size_t out_stride = 0;       // the longest delivered row: the row stride of the staging
+    float* host_pcm = nullptr;   // pinned [B][out_stride] staging of the streamed PCM
+    std::vector<hipEvent_t> ev;  // one per window: its PCM is on the host
+    // streaming at another rate: after window w the model-rate samples [0, E_w) of an utterance are final, and with them the output samples whose taps all lie
+    // in there (ResamplePlan::final_prefix; everything once the utterance has ended: the zeros behind its end are final). Window w resamples and delivers
+    // [o_(w-1), o_w): rg [window][2][B], on the device as s2.out_ranges.
+    // streaming under VITS_LEVEL_GAIN: window w multiplies the model-rate samples it makes final, [E_(w-1), E_w) of every utterance, once: lrg [window][2][B]
+    std::vector<int> rg, lrg;
+    ResampleCall rsc;
+    LevelScale lsc;
+    ChunkStream(Engine& e_, Call& c_) : e(e_), c(c_), rs(c_.dp[STAGE_RESAMPLE].runs), la(c_.dp.multiplies) {}
+    ~ChunkStream() {
+        for (hipEvent_t x : ev) hipEventDestroy(x);
+    }
 
-// ---- what the host knows of the rows a call delivers (engine.h): host arithmetic from the frame counts, nothing is queued here
-int Engine::plan_rows(Call& c) {
-    if (c.rows_planned) return 0;
-    std::string& err = c.err;
-    const vits_process_opts& o = c.o;
-    const int B = c.B, n_up = c.n_up;
-    if (plan_delivery(o, c.dp, err, c.join != nullptr)) return -1;
-    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
-    if (c.pitched()) {
-        // a stated pitch: N' of every row is host arithmetic, like everything else here; so are the rows of the report
-        c.pit_len.resize((size_t)B);
-        c.pit_rows.resize((size_t)4 * B);
-        for (int b = 0; b < B; ++b) {
-            PitchPlan pp;
-            std::string why;
-            if (!pitch_plan(c.pitch[b], c.slen[n_up][b], pp, why)) {
-                err = "utterance " + std::to_string(b) + ": " + why;
-                return -1;
-            }
-            c.pit_len[(size_t)b] = (int)pp.n_out;  // (at most 2^31: N <= 2^30 and p >= 0.5; the checks below refuse what does not fit)
-            if (pp.n_out > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(pp.n_out) + " samples at its pitch ratio: too long";
-                return -1;
-            }
-            c.pit_max = std::max(c.pit_max, c.pit_len[(size_t)b]);
-            const int64_t row[4] = {pp.P, c.slen[n_up][b], pp.n_out, pp.K};
-            std::copy_n(row, 4, c.pit_rows.begin() + (size_t)4 * b);
+    int setup() {
+        std::string& err = c.err;
+        const int B = c.B, n_up = c.n_up;
+        pcm = c.rows_of(c.dp.delivered);
+        out_stride = (size_t)(rs ? c.out_max : c.mr_max);
+        const size_t need = (size_t)B * out_stride * sizeof(float);
+        HIP_OK(e.pinned_.ensure(need, need));
+        host_pcm = (float*)e.pinned_.p;
+        if (rs) {
+            rsc = e.resample_out_call(c);
+            if (e.upload_ranges(c, rg, c.s2.out_ranges, [&](int b, int64_t x) { return (int)c.rate_out->plan.final_prefix(x, c.slen[n_up][b]); })) return -1;
         }
+        if (la) {
+            if (e.upload_ranges(c, lrg, c.s2.lvl_ranges, [](int, int64_t x) { return (int)x; })) return -1;
+            const Call::Rows x = c.rows_of(c.dp[STAGE_LEVEL].src), y = c.rows_of(c.dp[STAGE_LEVEL].dst);
+            lsc.x = x.p;  // (the call's own buffer: a level that multiplies keeps the vocoder there)
+            lsc.x_stride = x.stride;
+            lsc.y = y.p;
+            lsc.y_stride = y.stride;
+            lsc.lens = c.s1.stage_lens + (size_t)n_up * B;
+            lsc.gain = e.level_gain();
+            lsc.batch = B;
+        }
+        return 0;
     }
-    c.mr_len = c.head_len();
-    if (c.dp[STAGE_EDGES].runs)
-        for (int b = 0; b < B; ++b) {
-            const int64_t n = edges_plan_.bound(c.head_len()[(size_t)b]);
-            if (n > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
-                return -1;
-            }
-            c.mr_len[b] = (int)n;
-        }
-    c.utt_max = c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
-    c.rows = B;
-    const char* row_name = "utterance ";
-    if (c.join) {
-        // a joined call: the rows behind the join are the tracks, and what the host knows of each is its bound (the utterances' bounds and the positive gaps)
-        const std::vector<int64_t> ub(c.mr_len.begin(), c.mr_len.end());
-        std::string why;
-        if (!join_bounds(*c.join, ub.data(), why)) {
-            err = "vits_model_process_joined: " + why;
-            return -1;
-        }
-        c.mr_len.assign(c.join->bound.begin(), c.join->bound.end());  // (each at most kEdgesMaxLen = 2^30)
-        c.mr_max = (int)c.join->max_bound;
-        c.rows = c.join->tracks;
-        row_name = "track ";
-    }
-    if (output_rate_) {
-        ResamplePlan plan;  // (the plan of the handle's table: set_rates accepted the pair)
-        if (!resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
-        c.out_len.resize((size_t)c.rows);
-        for (int r = 0; r < c.rows; ++r) {
-            const int64_t n = plan.out_len(c.mr_len[r]);
-            if (n > (int64_t)INT32_MAX - 64) {
-                err = row_name + std::to_string(r) + " has " + std::to_string(n) + " samples at the output rate: too long";
-                return -1;
-            }
-            c.out_len[r] = (int)n;
-            c.out_max = std::max(c.out_max, (int)n);
-        }
-        c.out_ws = round_up(std::max(c.out_max, 1), 32);
-    }
-    if (o.out_device && !o.frames_only) {
-        const bool rs = output_rate_ != 0;
-        const std::vector<int>& len = rs ? c.out_len : c.mr_len;
-        const int longest = rs ? c.out_max : c.mr_max;
-        if (o.out_device_stride < longest) {
-            if (c.join) {
-                const int g = (int)(std::find_if(len.begin(), len.end(), [&](int n) { return n > o.out_device_stride; }) - len.begin());
-                err = "vits_model_process_joined: out_device_stride = " + std::to_string(o.out_device_stride) + " is below track " + std::to_string(g) + "'s " +
-                      std::to_string(len[(size_t)g]) + " samples";
-            } else err = "out_device_stride is smaller than the longest utterance";
-            if (rs) err += " (" + std::to_string(longest) + " samples at the output rate of " + std::to_string(output_rate_) + " Hz)";
-            return -1;
-        }
-    }
-    c.rows_planned = true;
-    return 0;
-}
 
-// ---- the pitch stage of a call: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.pitch_lens: what the edges stage,
-// or with it off every stage behind it, reads its rows' lengths from). One launch serves every ratio of the batch; rows with ratio 1 are copied.
-int Engine::run_pitch(Call& c) {
-    std::string& err = c.err;
-    const int B = c.B, n_up = c.n_up;
-    const Call::Rows src = c.rows_of(c.dp.pitch.src), dst = c.rows_of(c.dp.pitch.dst);
-    if (!pitch_table_ && !(pitch_table_ = upload(pitch_table_pairs()))) {  // (owned by the handle and counted in weight_bytes from here on)
-        err = "pitch table: device allocation failed";
+    // behind the kernels of window wi: ship its samples to the host, then serve the previous window's callbacks
+    int after_window(size_t wi) {
+        std::string& err = c.err;
+        Profiler& prof = e.prof;
+        hipStream_t const stream = e.stream;
+        const int B = c.B;
+        // (+ the no-crop tail of utterances that end inside this window, Q1; the same columns of longer utterances are not
+        // final yet and travel again with the next window)
+        size_t g0 = 0, g1 = 0;
+        c.win.copy_span(wi, out_stride, g0, g1);
+        if (la) {
+            // the gain on what this window made final, before anything reads it (the resampler below, the copy to the host)
+            int64_t n = 0;
+            for (int b = 0; b < B; ++b) {
+                const int64_t r = lrg[(wi * 2 + 1) * B + b] - lrg[(wi * 2) * B + b];
+                lsc.max_range = std::max(lsc.max_range, r);
+                n += r;
+            }
+            lsc.j0 = c.s2.lvl_ranges + (wi * 2) * B;
+            lsc.j1 = lsc.j0 + B;
+            PROF_LAUNCH("level_scale", (double)n, 8.0 * (double)n, launch_level_scale(lsc, stream));
+            lsc.max_range = 0;
+        }
+        if (rs) {
+            // the output samples this window made final, one launch for every utterance, then the columns they span
+            g0 = out_stride, g1 = 0;
+            int64_t in_s = 0, out_s = 0;
+            for (int b = 0; b < B; ++b) {
+                const int j0 = rg[(wi * 2) * B + b], j1 = rg[(wi * 2 + 1) * B + b];
+                if (j1 <= j0) continue;
+                g0 = std::min(g0, (size_t)j0), g1 = std::max(g1, (size_t)j1);
+                rsc.max_range = std::max(rsc.max_range, (int64_t)(j1 - j0));
+                out_s += j1 - j0;
+                in_s += (int64_t)(j1 - j0) * rsc.plan.M / rsc.plan.L;
+            }
+            if (g1 > g0) {
+                rsc.j0 = c.s2.out_ranges + (wi * 2) * B;
+                rsc.j1 = rsc.j0 + B;
+                HIP_OK(e.resample("resample_out", rsc, in_s, out_s));
+            }
+            rsc.max_range = 0;
+        }
+        if (g1 > g0)
+            HIP_OK(hipMemcpy2DAsync(host_pcm + g0, out_stride * 4, pcm.p + g0, (size_t)pcm.stride * 4, (g1 - g0) * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+        prof.fence();
+        hipEvent_t done;
+        HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        ev.push_back(done);
+        HIP_OK(hipEventRecord(done, stream));
+        return wi > 0 ? flush(wi - 1) : 0;
+    }
+
+    int last_chunks() { return flush(c.win.size() - 1); }
+
+   private:
+    // hands the finished window `w` to the caller's sink (blocks until its PCM is on the host): 0, 1 the sink aborted, -1 the wait failed
+    int deliver(size_t w) {
+        const vits_process_opts& o = c.o;
+        const int B = c.B;
+        if (hipEventSynchronize(ev[w]) != hipSuccess) return -1;
+        for (int b = 0; b < B; ++b) {
+            if (rs) {
+                // (a window that finalises nothing for an utterance makes no call for it)
+                const size_t j0 = (size_t)rg[(w * 2) * B + b], j1 = (size_t)rg[(w * 2 + 1) * B + b];
+                if (j1 > j0 && o.on_chunk(o.on_chunk_user, b, j0, host_pcm + (size_t)b * out_stride + j0, j1 - j0)) return 1;
+                continue;
+            }
+            if (!c.win.owns(w, b)) continue;
+            const size_t off = (size_t)c.win.chunk_begin(w), end = (size_t)c.win.final_end(w, b);
+            if (o.on_chunk(o.on_chunk_user, b, off, host_pcm + (size_t)b * out_stride + off, end - off)) return 1;
+        }
+        return 0;
+    }
+    // ... and the one exit of a call whose sink aborted, or whose wait failed: the device idle, the message set
+    int flush(size_t w) {
+        const int rc = deliver(w);
+        if (!rc) return 0;
+        hipStreamSynchronize(e.stream);
+        c.err = rc > 0 ? "aborted by the on_chunk callback" : "hipEventSynchronize failed";
         return -1;
     }
-    HIP_OK(c.pitch_pin->ensure((size_t)B, (size_t)B + 64));
-    std::copy_n(c.pitch, B, c.pitch_pin->p);
-    HIP_OK(hipMemcpyAsync(c.s2.pitch_ratios, c.pitch_pin->p, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream));
-    prof.fence();
-    PitchCall pc;
-    pc.x = src.p;
-    pc.x_stride = src.stride;
-    pc.lens = c.s1.stage_lens + (size_t)n_up * B;
-    pc.ratios = c.s2.pitch_ratios;
-    pc.y = dst.p;
-    pc.y_stride = dst.stride;
-    pc.table = pitch_table_;
-    pc.lens_out = c.s2.pitch_lens;
-    pc.batch = B;
-    pc.max_out = c.pit_max;
-    double taps = 0, in_s = 0, out_s = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t* row = c.pit_rows.data() + (size_t)4 * b;
-        in_s += (double)row[1], out_s += (double)row[2];
-        if (row[0] != kPitchOne) taps += (double)row[2] * (double)row[3];
+};
+
+// the device table of a windowed call (WindowPlan::device_table) into s2.win_lens
+int Engine::upload_window_table(Call& c, Pending* pend) {
+    std::string& err = c.err;
+    const std::vector<int> wl = c.win.device_table();
+    if (pend) {
+        // a pipelined batch: the table travels through pinned memory owned by the slot (it outlives this call), so that the submit does not
+        // drain the main stream — the previous batch's vocoder is running there (the synchronise below serialised windowed submits)
+        HIP_OK(pend->win_pinned.ensure(wl.size(), wl.size() + wl.size() / 4 + 64));
+        std::memcpy(pend->win_pinned.p, wl.data(), sizeof(int) * wl.size());
+        HIP_OK(hipMemcpyAsync(c.s2.win_lens, pend->win_pinned.p, sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
+        prof.fence();
+    } else {
+        HIP_OK(hipMemcpyAsync(c.s2.win_lens, wl.data(), sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
+        prof.fence();
+        HIP_OK(hipStreamSynchronize(stream));  // wl goes out of scope
     }
-    // K fused multiply-adds a sample and the tap's own; every row read once and written once
-    prof.begin("pitch", 4.0 * taps, 4.0 * (in_s + out_s), stream, /*chain=*/true);
-    const hipError_t e = launch_pitch(pc, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    prof.fence();
     return 0;
 }
 
-// ---- the join of a joined call: the rows behind the edges stage -> the tracks (join.hip), the offsets and the track lengths on the device, and the joins'
-// rows on their way to the slot's pinned copy
-int Engine::run_join(Call& c) {
-    std::string& err = c.err;
-    const JoinPlan& p = *c.join;
-    const int B = c.B;
-    const Call::Rows src = c.rows_of(c.dp.join.src), dst = c.rows_of(c.dp.join.dst);
-    const std::vector<int64_t> table = join_table(p);
-    HIP_OK(join_table_host_.ensure(table.size(), table.size() + table.size() / 4 + 64));
-    std::memcpy(join_table_host_.p, table.data(), sizeof(int64_t) * table.size());
-    HIP_OK(hipMemcpyAsync(c.s2.join_table, join_table_host_.p, sizeof(int64_t) * table.size(), hipMemcpyHostToDevice, stream));
-    prof.fence();
-    JoinCall jc;
-    jc.plan = &p;
-    jc.x = src.p;
-    jc.x_stride = src.stride;
-    jc.lens = c.utt_lens;
-    jc.y = dst.p;
-    jc.y_stride = dst.stride;
-    jc.table = c.s2.join_table;
-    jc.rows = jn_.dev();
-    jc.track_lens = reinterpret_cast<int*>(jn_.dev() + (size_t)2 * B);  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
-    int64_t in_s = 0, out_s = 0;
-    for (const int64_t n : p.ubound) in_s += n;
-    for (const int64_t n : p.bound) out_s += n;
-    prof.begin("join_offsets", 0, 20.0 * (double)B, stream, /*chain=*/true);
-    hipError_t e = launch_join_offsets(jc, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    // at most one add per sample; every utterance read once, every track's bound written once
-    prof.begin("join_apply", (double)in_s, 4.0 * ((double)in_s + (double)out_s), stream, /*chain=*/true);
-    e = launch_join_apply(jc, stream);
-    prof.end(stream);
-    HIP_OK(e);
-    HIP_OK(jn_.queue_copy(a1_slot_, B, stream));
-    prof.fence();
-    return 0;
-}
-
-// ---- everything behind the last vocoder window: the stages the call's plan runs, each reading what the one in front of it wrote (Call::rows_of of the plan's
-// routes), their taps, and the last window's chunks of a streaming call
-int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<int()>& last_chunks) {
-    std::string& err = c.err;
-    const vits_process_opts& o = c.o;
-    const DeliveryPlan& dp = c.dp;
+// what the window functions see of window wi (engine_vocoder.cpp): everything in there is window-local
+void Engine::window_ctx(const Call& c, size_t wi, WinCtx& w) const {
+    const WindowPlan& win = c.win;
     const int B = c.B, n_up = c.n_up;
-    const bool rs = dp[STAGE_RESAMPLE].runs;
-    auto tap = [&](const char* name, const DeliveryRoute& r, int max_len, const std::vector<int>& lens) {
-        const Call::Rows rows = c.rows_of(r);
-        TensorRef t;
-        t.p = rows.p;
-        t.bs = rows.stride;
-        t.cs = (int)t.bs;
-        snapshot(name, t, 1, max_len, B, lens);
-    };
-    // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
-    std::vector<int> tap_len = c.head_len(), tap_out_len = c.out_len;
-    int tap_max = c.head_max(), tap_out_max = c.out_max;
-    if (dp.pitch.runs) {
-        if (run_pitch(c)) return -1;
-        if (o.collect_taps) tap("waveform_pitch", dp.pitch.after, tap_max, tap_len);
-    }
-    if (dp[STAGE_EDGES].runs) {
-        if (run_edges(c)) return -1;
-        if (o.collect_taps) {
-            // (a tap carries its rows' lengths: this debugging path reads the trimmed ones here, the call proper at its own synchronisation)
-            HIP_OK(hipStreamSynchronize(stream));
-            prof.fence();
-            const int64_t* rows = ed_.slot_rows(a1_slot_);
-            tap_max = tap_out_max = 0;
-            for (int b = 0; b < B; ++b) {
-                tap_len[b] = (int)rows[(size_t)4 * b + 2];
-                tap_max = std::max(tap_max, tap_len[b]);
-                if (rs) tap_out_max = std::max(tap_out_max, tap_out_len[b] = (int)c.rate_out->plan.out_len(tap_len[b]));
-            }
-            tap("waveform_edges", dp[STAGE_EDGES].after, tap_max, tap_len);
-        }
-    }
-    if (dp.join.runs && run_join(c)) return -1;
-    if (dp[STAGE_LEVEL].runs) {
-        if (run_level(c)) return -1;
-        if (o.collect_taps) tap("waveform_level", dp[STAGE_LEVEL].after, tap_max, tap_len);
-    }
-    if (rs && !o.on_chunk) {
-        // nobody waits for parts of it: one launch over every utterance, behind the last window
-        rsc.max_range = c.out_max;
-        HIP_OK(resample("resample_out", rsc, c.sum_frames * c.M + (int64_t)B * c.sadd[n_up], std::accumulate(c.out_len.begin(), c.out_len.end(), (int64_t)0)));
-    }
-    if (rs && o.collect_taps) tap("waveform_out", dp[STAGE_RESAMPLE].after, tap_out_max, tap_out_len);
-    if (last_chunks)
-        if (int rc = last_chunks()) {
-            hipStreamSynchronize(stream);
-            err = rc > 0 ? "aborted by the on_chunk callback" : "hipEventSynchronize failed";
-            return -1;
-        }
-    return 0;
+    const Call::Rows wave = c.rows_of(c.dp[STAGE_VOCODER].dst);  // (Call::rows_of: straight to out_device when nothing follows)
+    w.wi = wi;
+    w.wn = win[wi];
+    w.Lw = w.wn.hi - w.wn.lo;
+    w.smax.resize(n_up + 1);
+    w.ssum.resize(n_up + 1);
+    for (int i = 0; i <= n_up; ++i) w.smax[i] = win.stage_max(wi, i), w.ssum[i] = win.stage_sum(wi, i);
+    const int* table = win.windowed ? c.s2.win_lens + wi * win.table_rows() * B : nullptr;
+    for (int i = 0; i <= n_up && i < 8; ++i) w.d_len[i] = table ? table + (size_t)i * B : c.d_len_full[i];
+    w.emit_hi = table ? table + (size_t)(n_up + 1) * B : nullptr;
+    w.emit_lo = win.emit_lo(wi);
+    w.zwin = make_ref(c.s2.zp, hp.flow_size, c.ls);
+    w.zwin.p += w.wn.lo;
+    w.pre.p = c.s2.pre;
+    w.pre.bs = c.S_stride;
+    w.pre.cs = c.S_stride;
+    w.wv.p = wave.p + (int64_t)w.wn.lo * win.M;  // window-local sample 0 is global sample lo * M
+    w.wv.bs = wave.stride;
+    w.wv.cs = (int)wave.stride;
+    w.final_slope = c.refmode ? hp.lrelu : 0.01f;  // Q2 (vits.cpp:638)
+    window_tile_maps(c, w);
 }
 
 // ---- stage two from the known frame counts on: vocoder windows, arena, latent (prior sampling, or the conversion front end), flow, vocoder,
@@ -1356,40 +881,19 @@ int Engine::run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<in
 int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool want_async) {
     std::string& err = c.err;
     const vits_process_opts& o = c.o;
-    const int B = c.B, n_up = c.n_up, Lmax = c.Lmax;
-    const std::vector<int>& frames = c.frames;
+    const int B = c.B, n_up = c.n_up;
     // the delivery chain behind the vocoder, planned once (its refusals were the entry points', before stage one was queued: nothing is refused here that was not
     // there), and what the host knows of the rows the call delivers: refused here, with nothing of stage two queued, if it was not before stage one
     if (plan_rows(c)) return -1;
     const DeliveryPlan& dp = c.dp;
-    // ---- vocoder windows (long-form / streaming, vits.h vocoder_chunk_frames) ------------------------------------
-    // Window w owns frames [f0, f1) and computes frames [lo, hi) = the owned range widened by the vocoder's receptive
-    // field (halo_frames_): every sample it emits sees exactly the inputs it sees in a whole-utterance run, in the same
-    // order of accumulation, so the PCM is bit-identical while the activations are bounded by the window.
-    std::vector<Call::Win>& wins = c.wins;
-    {
-        const int W = (o.vocoder_chunk_frames > 0 && !o.collect_taps && o.vocoder_chunk_frames < Lmax) ? o.vocoder_chunk_frames : 0;
-        if (!W) wins.push_back({0, Lmax, 0, Lmax});
-        else
-            for (int f0 = 0; f0 < Lmax; f0 += W) {
-                const int f1 = std::min(Lmax, f0 + W);
-                wins.push_back({f0, f1, std::max(0, f0 - halo_frames_), std::min(Lmax, f1 + halo_frames_)});
-            }
-    }
-    const bool windowed = c.windowed = wins.size() > 1;
-    // (a run that is not windowed — no chunking asked for, a window at least as long as the longest utterance, which the
-    // caller cannot know in advance, or collect_taps — streams as ONE window: the sink gets each utterance in a single call)
-    for (const Call::Win& w : wins) c.Lw_max = std::max(c.Lw_max, w.hi - w.lo);
-    const int M = c.M = c.smul[n_up];  // samples per frame
-    const bool ed = dp[STAGE_EDGES].runs;
+    // the vocoder windows (long-form / streaming, vits.h vocoder_chunk_frames; window_plan.h): one window unless the call asked for chunks
+    c.win.plan(c.frames.data(), B, c.smul.data(), c.sadd.data(), n_up, halo_frames_, o.vocoder_chunk_frames, o.collect_taps != 0);
     // the call delivers its PCM at another rate (vits_model_set_rates): the vocoder writes the model-rate waveform to the call's own buffer and resample.hip
     // writes what the caller gets; lengths, strides and stream offsets below are output-rate quantities (plan_rows)
     if (output_rate_ && !(c.rate_out = rate_table(hp.sampling_rate, output_rate_, err))) return -1;
-    const bool rs = dp[STAGE_RESAMPLE].runs;
     // a level that multiplies (every kind but VITS_LEVEL_MEASURE): the vocoder writes to the call's own buffer, loudness.hip measures it there and
     // multiplies it into what is delivered, or into the resampler's input. VITS_LEVEL_MEASURE measures the waveform where the vocoder wrote it
     c.lev = level_kind_;
-    const bool la = dp.multiplies;
 
     // (a call that returns with device work queued owns no pinned memory that outlives the copy of its lists: it keeps the dense grids)
     if (pend || !want_async) plan_tile_maps(c);
@@ -1406,224 +910,60 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
 
     // ---- HiFiGAN (vits.cpp:583-644), window by window ---------------------------------------------------------------
     c.rx.phase("vits.hifigan");
-    const std::vector<int>& smul = c.smul;
-    const std::vector<int>& sadd = c.sadd;
-    // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
-    // (stated edges: the bounds; the lengths proper are read from the stage's rows where the results are filled)
-    const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
-    const int pcm_max = rs ? c.out_max : c.mr_max;
     // the device lengths [B] of the model-rate rows, for every stage behind the vocoder: its sample counts, or what the edges stage will write behind its rows
     c.mr_lens = c.head_lens();
     c.pitch_pin = pend ? &pend->pitch_pinned : &pitch_host_;
-    if (ed) {
+    if (dp[STAGE_EDGES].runs) {
         HIP_OK(ed_.grow(B, owned_, weight_bytes));
-        c.mr_lens = static_cast<const int*>(ed_.tail());
+        c.mr_lens = edges_lens();
     }
     if (c.join) {
         // behind the join the rows are the tracks: their lengths T_g lie behind the {o_b, n_b} rows of the joins' report
         HIP_OK(jn_.grow(B, owned_, weight_bytes));
         c.utt_lens = c.mr_lens;
-        c.mr_lens = reinterpret_cast<const int*>(jn_.dev() + (size_t)2 * B);
+        c.mr_lens = track_lens(B);
     }
-    // where the plan routes the vocoder's waveform and what is delivered (Call::rows_of: straight to out_device when nothing follows)
-    const Call::Rows wave = c.rows_of(dp[STAGE_VOCODER].dst), pcm = c.rows_of(dp.delivered);
-    float* const pcm_dst = pcm.p;
-    const int64_t pcm_stride = pcm.stride;
-    ResampleCall rsc;
-    if (rs) {
-        const Call::Rows x = c.rows_of(dp[STAGE_RESAMPLE].src);
-        rsc.x = x.p;
-        rsc.x_stride = x.stride;
-        rsc.lens = c.mr_lens;  // (device: every utterance's samples at the model's rate, the trimmed ones under stated edges)
-        rsc.y = pcm_dst;
-        rsc.y_stride = pcm_stride;
-        rsc.taps = c.rate_out->taps;
-        rsc.plan = c.rate_out->plan;
-        rsc.batch = c.rows;
-    }
-    std::vector<hipEvent_t> chunk_ev;
-    struct EvGuard {
-        std::vector<hipEvent_t>& v;
-        ~EvGuard() {
-            for (hipEvent_t e : v) hipEventDestroy(e);
-        }
-    } chunk_ev_guard{chunk_ev};
-    float* host_pcm = nullptr;  // pinned [B][smax] staging of the streamed PCM
-    const size_t out_stride = (size_t)pcm_max;
-    // streaming at another rate: after window w the model-rate samples [0, E_w) of an utterance are final, and with them the output samples whose taps all lie
-    // in there (ResamplePlan::final_prefix; everything once the utterance has ended: the zeros behind its end are final). Window w resamples and delivers
-    // [o_(w-1), o_w): rg [window][2][B], on the device as s2.out_ranges.
-    std::vector<int> rg;
-    if (rs && o.on_chunk && upload_ranges(c, rg, c.s2.out_ranges, [&](int b, int64_t e) { return (int)c.rate_out->plan.final_prefix(e, c.slen[n_up][b]); })) return -1;
-    // streaming under VITS_LEVEL_GAIN: window w multiplies the model-rate samples it makes final, [E_(w-1), E_w) of every utterance, once: lrg [window][2][B]
-    std::vector<int> lrg;
-    LevelScale lsc;
-    if (la && o.on_chunk) {
-        if (upload_ranges(c, lrg, c.s2.lvl_ranges, [](int, int64_t e) { return (int)e; })) return -1;
-        const Call::Rows x = c.rows_of(dp[STAGE_LEVEL].src), y = c.rows_of(dp[STAGE_LEVEL].dst);
-        lsc.x = x.p;  // (the call's own buffer: a level that multiplies keeps the vocoder there)
-        lsc.x_stride = x.stride;
-        lsc.y = y.p;
-        lsc.y_stride = y.stride;
-        lsc.lens = c.s1.stage_lens + (size_t)n_up * B;
-        lsc.gain = (float)std::pow(10.0, (double)level_value_ / 20.0);  // (the float run_level reports)
-        lsc.batch = B;
-    }
-    if (windowed) {
-        // per window and utterance: frames inside the window -> stage lengths (0 everywhere when the utterance has none),
-        // and the end of the sample range this window emits for it (window-local index)
-        std::vector<int> wl(wins.size() * (size_t)(n_up + 2) * B, 0);
-        for (size_t w = 0; w < wins.size(); ++w)
-            for (int b = 0; b < B; ++b) {
-                const Call::Win& wn = wins[w];
-                const int lf = std::min(frames[b], wn.hi) - wn.lo;
-                int* row = wl.data() + w * (size_t)(n_up + 2) * B;
-                if (lf <= 0) continue;
-                for (int i = 0; i <= n_up; ++i) row[(size_t)i * B + b] = lf * smul[i] + sadd[i];
-                if (frames[b] > wn.f0)  // owns frames here; the window holding the utterance's end also emits its tail (Q1)
-                    row[(size_t)(n_up + 1) * B + b] = frames[b] <= wn.f1 ? (frames[b] - wn.lo) * M + sadd[n_up] : (wn.f1 - wn.lo) * M;
-            }
-        if (pend) {
-            // a pipelined batch: the table travels through pinned memory owned by the slot (it outlives this call), so that the submit does not
-            // drain the main stream — the previous batch's vocoder is running there (the synchronise below serialised windowed submits)
-            HIP_OK(pend->win_pinned.ensure(wl.size(), wl.size() + wl.size() / 4 + 64));
-            std::memcpy(pend->win_pinned.p, wl.data(), sizeof(int) * wl.size());
-            HIP_OK(hipMemcpyAsync(c.s2.win_lens, pend->win_pinned.p, sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
-            prof.fence();
-        } else {
-            HIP_OK(hipMemcpyAsync(c.s2.win_lens, wl.data(), sizeof(int) * wl.size(), hipMemcpyHostToDevice, stream));
-            prof.fence();
-            HIP_OK(hipStreamSynchronize(stream));  // wl goes out of scope
-        }
-    }
-    if (o.on_chunk) {
-        const size_t need = (size_t)B * out_stride * sizeof(float);
-        HIP_OK(pinned_.ensure(need, need));
-        host_pcm = (float*)pinned_.p;
-    }
-    // hands the finished window `w` to the caller's sink (blocks until its PCM is on the host)
-    auto deliver = [&](size_t w) -> int {
-        const Call::Win& wn = wins[w];
-        if (hipEventSynchronize(chunk_ev[w]) != hipSuccess) return -1;
-        for (int b = 0; b < B; ++b) {
-            if (rs) {
-                // (a window that finalises nothing for an utterance makes no call for it)
-                const size_t j0 = (size_t)rg[(w * 2) * B + b], j1 = (size_t)rg[(w * 2 + 1) * B + b];
-                if (j1 > j0 && o.on_chunk(o.on_chunk_user, b, j0, host_pcm + (size_t)b * out_stride + j0, j1 - j0)) return 1;
-                continue;
-            }
-            if (frames[b] <= wn.f0) continue;
-            const size_t off = (size_t)wn.f0 * M;
-            const size_t end = frames[b] <= wn.f1 ? (size_t)c.slen[n_up][b] : (size_t)wn.f1 * M;
-            if (o.on_chunk(o.on_chunk_user, b, off, host_pcm + (size_t)b * out_stride + off, end - off)) return 1;
-        }
-        return 0;
-    };
-    for (size_t wi = 0; wi < wins.size(); ++wi) {
+    ChunkStream chunks(*this, c);
+    if (o.on_chunk && chunks.setup()) return -1;
+    if (c.win.windowed && upload_window_table(c, pend)) return -1;
+    for (size_t wi = 0; wi < c.win.size(); ++wi) {
         WinCtx w;
-        w.wi = wi;
-        w.wn = wins[wi];
-        const Call::Win& wn = w.wn;
-        w.Lw = wn.hi - wn.lo;
-        w.smax.resize(n_up + 1);  // (window-local maxima: everything inside the window functions is window-local)
-        for (int i = 0; i <= n_up && i < 8; ++i) {
-            w.d_len[i] = windowed ? c.s2.win_lens + (wi * (size_t)(n_up + 2) + i) * B : c.d_len_full[i];
-            w.smax[i] = w.Lw * smul[i] + sadd[i];
-        }
-        w.ssum.assign(n_up + 1, 0);
-        for (int b = 0; b < B; ++b) {
-            const int lf = std::min(frames[b], wn.hi) - wn.lo;
-            if (lf <= 0) continue;
-            for (int i = 0; i <= n_up; ++i) w.ssum[i] += (int64_t)lf * smul[i] + sadd[i];
-        }
-        w.emit_hi = windowed ? c.s2.win_lens + (wi * (size_t)(n_up + 2) + n_up + 1) * B : nullptr;
-        w.emit_lo = (wn.f0 - wn.lo) * M;
-        w.zwin = make_ref(c.s2.zp, hp.flow_size, c.ls);
-        w.zwin.p += wn.lo;
-        w.pre.p = c.s2.pre;
-        w.pre.bs = c.S_stride;
-        w.pre.cs = c.S_stride;
-        w.wv.p = wave.p + (int64_t)wn.lo * M;  // window-local sample 0 is global sample lo * M
-        w.wv.bs = wave.stride;
-        w.wv.cs = (int)wave.stride;
-        w.final_slope = c.refmode ? hp.lrelu : 0.01f;  // Q2 (vits.cpp:638)
-        window_tile_maps(c, w);
+        window_ctx(c, wi, w);
         if (c.fast16 ? run_vocoder_window16(c, w) : run_vocoder_window32(c, w)) return -1;
-        if (o.on_chunk) {
-            // ship this window's samples to the host behind the kernels, then serve the PREVIOUS window's callbacks while
-            // the device works on this one
-            // (+ the no-crop tail of utterances that end inside this window, Q1; the same columns of longer utterances are not
-            // final yet and travel again with the next window)
-            size_t g0 = (size_t)wn.f0 * M, g1 = std::min(out_stride, (size_t)wn.f1 * M + (size_t)sadd[n_up]);
-            if (la) {
-                // the gain on what this window made final, before anything reads it (the resampler below, the copy to the host)
-                int64_t n = 0;
-                for (int b = 0; b < B; ++b) {
-                    const int64_t r = lrg[(wi * 2 + 1) * B + b] - lrg[(wi * 2) * B + b];
-                    lsc.max_range = std::max(lsc.max_range, r);
-                    n += r;
-                }
-                lsc.j0 = c.s2.lvl_ranges + (wi * 2) * B;
-                lsc.j1 = lsc.j0 + B;
-                prof.begin("level_scale", (double)n, 8.0 * (double)n, stream, /*chain=*/true);
-                const hipError_t e = launch_level_scale(lsc, stream);
-                prof.end(stream);
-                HIP_OK(e);
-                lsc.max_range = 0;
-            }
-            if (rs) {
-                // the output samples this window made final, one launch for every utterance, then the columns they span
-                g0 = out_stride, g1 = 0;
-                int64_t in_s = 0, out_s = 0;
-                for (int b = 0; b < B; ++b) {
-                    const int j0 = rg[(wi * 2) * B + b], j1 = rg[(wi * 2 + 1) * B + b];
-                    if (j1 <= j0) continue;
-                    g0 = std::min(g0, (size_t)j0), g1 = std::max(g1, (size_t)j1);
-                    rsc.max_range = std::max(rsc.max_range, (int64_t)(j1 - j0));
-                    out_s += j1 - j0;
-                    in_s += (int64_t)(j1 - j0) * rsc.plan.M / rsc.plan.L;
-                }
-                if (g1 > g0) {
-                    rsc.j0 = c.s2.out_ranges + (wi * 2) * B;
-                    rsc.j1 = rsc.j0 + B;
-                    HIP_OK(resample("resample_out", rsc, in_s, out_s));
-                }
-                rsc.max_range = 0;
-            }
-            if (g1 > g0)
-                HIP_OK(hipMemcpy2DAsync(host_pcm + g0, out_stride * 4, pcm_dst + g0, (size_t)pcm_stride * 4, (g1 - g0) * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
-            prof.fence();
-            hipEvent_t ev;
-            HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            chunk_ev.push_back(ev);
-            HIP_OK(hipEventRecord(ev, stream));
-            if (wi > 0)
-                if (int rc = deliver(wi - 1)) {
-                    hipStreamSynchronize(stream);
-                    err = rc > 0 ? "aborted by the on_chunk callback" : "hipEventSynchronize failed";
-                    return -1;
-                }
-        }
+        if (o.on_chunk && chunks.after_window(wi)) return -1;
         if (o.collect_taps) {
             snapshot("pre_tanh", w.pre, 1, w.smax[n_up], B, c.slen[n_up]);
             snapshot("waveform", w.wv, 1, w.smax[n_up], B, c.slen[n_up]);
         }
     }
     std::function<int()> last_chunks;
-    if (o.on_chunk) last_chunks = [&] { return deliver(wins.size() - 1); };
-    if (run_delivery_tail(c, rsc, last_chunks)) return -1;
+    if (o.on_chunk) last_chunks = [&] { return chunks.last_chunks(); };
+    if (run_delivery_tail(c, last_chunks)) return -1;
+    return hand_over(c, out, pend, want_async, chunks.host_pcm);
+}
 
-    // ---- results ------------------------------------------------------------------------------------------------
+// ---- results: the pipelined slot, the synchronous result (streamed: the pinned staging a sink's call has filled already), or the async tail; the report rows
+// and the trimmed / track lengths once they have landed
+int Engine::hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_async, const float* streamed) {
+    std::string& err = c.err;
+    const vits_process_opts& o = c.o;
+    const DeliveryPlan& dp = c.dp;
     c.rx.phase("vits.results");
-    const int R = c.rows;  // what the call hands out: one row per utterance, or per track
-    const int lv_n = c.lev ? R : 0, lm_n = dp.limits ? R : 0, ed_n = ed ? B : 0, jn_n = c.join ? B : 0;  // the rows of the reports this call fills
+    const bool rs = dp[STAGE_RESAMPLE].runs;
+    // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
+    // (stated edges: the bounds; the lengths proper are read from the stage's rows below)
+    const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
+    const int pcm_max = rs ? c.out_max : c.mr_max;
+    const Call::Rows pcm = c.rows_of(dp.delivered);
+    const int B = c.B, R = c.rows;  // what the call hands out: one row per utterance, or per track
+    const int lv_n = c.lev ? R : 0, lm_n = dp.limits ? R : 0, ed_n = dp[STAGE_EDGES].runs ? B : 0, jn_n = c.join ? B : 0;  // the rows of the reports this call fills
     if (pend) {
         // a pipelined batch: everything the host will hand out is known now; the PCM (if a host copy was asked for) goes to the
         // slot's pinned staging behind the kernels, and `done` marks the end of the batch on the device
         pend->B = B;
         pend->stride = (size_t)pcm_max;
         pend->lengths.assign(pcm_len.begin(), pcm_len.end());
-        pend->frames.assign(frames.begin(), frames.end());
+        pend->frames.assign(c.frames.begin(), c.frames.end());
         pend->lv_rows = lv_n;
         pend->lm_rows = lm_n;
         pend->ed_rows = ed_n;  // (lengths: the bounds until vits_model_wait reads the rows)
@@ -1632,25 +972,21 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
             HIP_OK(pend->host.ensure(need, need + need / 8));
-            HIP_OK(hipMemcpy2DAsync(pend->host.p, pend->stride * 4, pcm_dst, (size_t)pcm_stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpy2DAsync(pend->host.p, pend->stride * 4, pcm.p, (size_t)pcm.stride * 4, pend->stride * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
         }
         HIP_OK(hipEventRecord(pend->done, stream));
         prof.fence();
         return 0;
     }
     if (out) {
-        if (c.join) {
-            // (lengths: the bounds until the track lengths have landed below; frames: the sums over each track's utterances)
-            std::vector<int64_t> tf((size_t)R, 0);
-            for (int g = 0; g < R; ++g)
-                for (int b = c.join->first[(size_t)g]; b < c.join->first[(size_t)g + 1]; ++b) tf[(size_t)g] += frames[b];
-            fill_result(out, R, (size_t)pcm_max, pcm_len.begin(), tf.begin());
-        } else fill_result(out, B, (size_t)pcm_max, pcm_len.begin(), frames.begin());
+        // (a joined call: the lengths are the bounds until the track lengths have landed below; frames: the sums over each track's utterances)
+        if (c.join) fill_result(out, R, (size_t)pcm_max, pcm_len.begin(), c.track_frames().begin());
+        else fill_result(out, B, (size_t)pcm_max, pcm_len.begin(), c.frames.begin());
         if (!o.skip_host_copy) {
             out->data = new float[(size_t)R * out->stride];
-            if (o.on_chunk) std::memcpy(out->data, host_pcm, sizeof(float) * (size_t)B * out->stride);  // already streamed to the host
+            if (o.on_chunk) std::memcpy(out->data, streamed, sizeof(float) * (size_t)B * out->stride);  // already streamed to the host
             else
-                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, pcm_dst, (size_t)pcm_stride * 4, out->stride * 4, (size_t)R, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpy2DAsync(out->data, out->stride * 4, pcm.p, (size_t)pcm.stride * 4, out->stride * 4, (size_t)R, hipMemcpyDeviceToHost, stream));
             prof.fence();
         }
     }
@@ -1658,30 +994,30 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
     if (want_async) {
         // (the rows are on their way to the slot's pinned copy: the reports are valid after sync())
         lv_.expect(a1_slot_, lv_n), lm_.expect(a1_slot_, lm_n), ed_.expect(a1_slot_, ed_n);
-    } else {
-        HIP_OK(hipStreamSynchronize(stream));
-        prof.fence();
-        // the rows have landed: kept apart from the pinned copies, which a later submit into this slot overwrites; the trimmed lengths are what the call reports
-        if (jn_n) {
-            // the joins' rows and the track lengths have landed: the report names each utterance and its track; the call reports T_g (at the output rate)
-            const int64_t* on = jn_.slot_rows(a1_slot_);
-            const int* tl = reinterpret_cast<const int*>(on + (size_t)2 * B);
-            std::vector<int64_t> rows((size_t)4 * B);
-            for (int g = 0; g < R; ++g)
-                for (int b = c.join->first[(size_t)g]; b < c.join->first[(size_t)g + 1]; ++b) {
-                    rows[(size_t)4 * b] = join_index_[(size_t)b], rows[(size_t)4 * b + 1] = g;
-                    rows[(size_t)4 * b + 2] = on[(size_t)2 * b], rows[(size_t)4 * b + 3] = on[(size_t)2 * b + 1];
-                }
-            jn_.store(std::move(rows));
-            if (out)
-                for (int g = 0; g < R; ++g) out->lengths[g] = rs ? c.rate_out->plan.out_len(tl[g]) : tl[g];
-        } else if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
-        lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
-        pt_.store(c.pit_rows);
-        // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
-        // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
-        if (prof.on && prof.recs.size() > 50000) prof.collect();
+        return 0;
     }
+    HIP_OK(hipStreamSynchronize(stream));
+    prof.fence();
+    // the rows have landed: kept apart from the pinned copies, which a later submit into this slot overwrites; the trimmed lengths are what the call reports
+    if (jn_n) {
+        // the joins' rows and the track lengths have landed: the report names each utterance and its track; the call reports T_g (at the output rate)
+        const int64_t* on = jn_.slot_rows(a1_slot_);
+        const int* tl = track_lens(on, B);
+        std::vector<int64_t> rows((size_t)4 * B);
+        for (int g = 0; g < R; ++g)
+            for (int b = c.join->first[(size_t)g]; b < c.join->first[(size_t)g + 1]; ++b) {
+                rows[(size_t)4 * b] = join_index_[(size_t)b], rows[(size_t)4 * b + 1] = g;
+                rows[(size_t)4 * b + 2] = on[(size_t)2 * b], rows[(size_t)4 * b + 3] = on[(size_t)2 * b + 1];
+            }
+        jn_.store(std::move(rows));
+        if (out)
+            for (int g = 0; g < R; ++g) out->lengths[g] = rs ? c.rate_out->plan.out_len(tl[g]) : tl[g];
+    } else if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
+    lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
+    pt_.store(c.pit_rows);
+    // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
+    // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
+    if (prof.on && prof.recs.size() > 50000) prof.collect();
     return 0;
 }
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <functional>
 #include <initializer_list>
 #include <map>
@@ -536,6 +537,7 @@ class Engine {
     int process_split(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err);
     int process_impl(const int32_t* ids, const int32_t* id_lens, int batch, int id_stride, const vits_process_opts& o, vits_batch_result* out, std::string& err,
                      Pending* pend, JoinPlan* join = nullptr);
+    int frames_only_result(Call& c, vits_batch_result* out);  // opts.frames_only: lengths[] and frames[] from the frame counts, no audio
     // a synchronous entry point's error return: whatever the failed call queued has run before the handle takes another (submit_batch does the same)
     void drain_streams();
     hipError_t copy_durations(const Call& c, PinnedBuf<float>& pinned);
@@ -606,6 +608,11 @@ class Engine {
     ReportRows<int64_t> ed_{sizeof(int)}, jn_;
     // the pitch stage's rows are host arithmetic (P, N and N' follow from the ratio and the frame count): the report never touches the device
     ReportRows<int64_t> pt_;
+    // the device lengths behind those rows: the trimmed lengths [B] that run_edges writes, and the track lengths T_g [G] that run_join writes behind the
+    // joins' {o_b, n_b} rows of a call of B utterances (device rows, or a slot's landed copy). What Call::mr_lens points at when the stage runs
+    int* edges_lens() { return static_cast<int*>(ed_.tail()); }
+    static const int* track_lens(const int64_t* join_rows, int B) { return reinterpret_cast<const int*>(join_rows + (size_t)2 * B); }
+    int* track_lens(int B) { return const_cast<int*>(track_lens(jn_.dev(), B)); }
     void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(); }
     // a stated pitch: the interleaved table on the device (uploaded by the first call that shifts), a synchronous call's ratios on their way there, and the
     // stage from its source into its destination, as the call's plan routes them: queued behind the last vocoder window, in front of run_edges
@@ -623,7 +630,8 @@ class Engine {
     int level_kind_ = VITS_LEVEL_NONE;
     float level_value_ = 0.f, level_ceiling_ = 0.f;
     LoudnessPlan level_plan_;
-    // measures the level stage's source and multiplies (or limits) it into the stage's destination, as the call's plan routes them (engine.cpp); queued behind
+    float level_gain() const { return (float)std::pow(10.0, (double)level_value_ / 20.0); }  // VITS_LEVEL_GAIN's factor, the float the levels rows report
+    // measures the level stage's source and multiplies (or limits) it into the stage's destination, as the call's plan routes them (engine_delivery.cpp); queued behind
     // the last vocoder window
     int run_level(Call& c);
     // the limiter: the handle's mode and the plan at the model's rate
@@ -637,19 +645,25 @@ class Engine {
     size_t ed_fades_n_ = 0;
     bool ed_fades_stale_ = false;
     bool edges_on() const { return edges_desc_.mode != VITS_EDGES_OFF; }
-    // the stage from its source into its destination, as the call's plan routes them (engine.cpp): queued behind the last vocoder window, in front of run_level
+    // the stage from its source into its destination, as the call's plan routes them (engine_delivery.cpp): queued behind the last vocoder window, in front of run_level
     int run_edges(Call& c);
     // what a call delivers per utterance once its rows [B][4] have landed: N', or its length at the output rate
     void edges_lengths(const int64_t* rows, int B, int64_t* lengths) const;
     // the rows of a batch that has completed in pipeline slot `slot` -> the three reports (append: a second part of the same call); the batch's lengths become
     // its trimmed ones when the edges stage ran
     void batch_landed(Pending& p, int slot, bool append = false);
-    // everything behind the last vocoder window (engine.cpp): edges, level or limiter, the resampler (rsc: its call, set up by run_stage_two), their taps, and
-    // the chunks of the last window of a streaming call (last_chunks: null without a sink; > 0 the sink aborted, < 0 the wait failed)
-    int run_delivery_tail(Call& c, ResampleCall& rsc, const std::function<int()>& last_chunks);
-    // a streaming call's table [window][2][B] on the host and on the device (dev): the samples [j0, j1) of every utterance that each window makes final, in the
-    // unit of `final_of(b, e)`: what is final of utterance b once its model-rate samples [0, e) are
+    // everything behind the last vocoder window (engine_delivery.cpp): pitch, edges, join, level or limiter, the resampler, their taps, and the chunks of the
+    // last window of a streaming call (last_chunks: null without a sink; -1 with the call's message set: the sink aborted, or the wait failed)
+    int run_delivery_tail(Call& c, const std::function<int()>& last_chunks);
+    ResampleCall resample_out_call(const Call& c) const;
+    // a streaming call's table [window][2][B] (WindowPlan::range_table) on the host and on the device (dev): the samples [j0, j1) of every utterance that
+    // each window makes final, in the unit of `final_of(b, e)`: what is final of utterance b once its model-rate samples [0, e) are
     int upload_ranges(Call& c, std::vector<int>& table, int* dev, const std::function<int(int, int64_t)>& final_of);
+    // the streaming state of a call with a sink (engine.cpp), and the hand-over of a call's results: the pipelined slot, the synchronous result, the async tail
+    struct ChunkStream;
+    int upload_window_table(Call& c, Pending* pend);         // the device table of a windowed call; through the slot's pinned memory for a pipelined batch
+    void window_ctx(const Call& c, size_t wi, WinCtx& w) const;  // what the vocoder's window functions see of window wi
+    int hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_async, const float* streamed);
     // one profiled resample launch ("resample_out" / "resample_in"): 2 K flops per output sample, the input read once and the output written once
     hipError_t resample(const char* name, const ResampleCall& rc, int64_t in_samples, int64_t out_samples);
 

@@ -13,9 +13,9 @@ int Engine::layout_stage_two(Call& c) {
     const int H = hp.hidden, F = hp.flow_size;
     const int Lmax = c.Lmax;
     Call::S2& s2 = c.s2;
-    const std::vector<Call::Win>& wins = c.wins;
-    const bool windowed = c.windowed;
-    const int Lw_max = c.Lw_max;
+    const WindowPlan& wins = c.win;
+    const bool windowed = wins.windowed;
+    const int Lw_max = wins.Lw_max;
     const std::vector<int>& smul = c.smul;
     const std::vector<int>& sadd = c.sadd;
     const std::vector<int>& smax = c.smax;
@@ -53,7 +53,7 @@ int Engine::layout_stage_two(Call& c) {
         s2.hout = a.alloc<float>((size_t)B * 2 * H * ls);
         s2.gate = a.alloc<float>((size_t)B * H * ls);
         s2.h0 = a.alloc<float>((size_t)B * hp.up_init * lws);
-        s2.win_lens = windowed ? a.alloc<int>(wins.size() * (size_t)(n_up + 2) * B) : nullptr;
+        s2.win_lens = windowed ? a.alloc<int>(wins.size() * wins.table_rows() * B) : nullptr;
         s2.bu = a.alloc<float>(big);
         s2.bul = a.alloc<float>(big);
         for (int j = 0; j < 3; ++j) {

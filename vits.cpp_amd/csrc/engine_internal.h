@@ -1,4 +1,4 @@
-// engine_internal.h — shared by the engine's translation units only (engine.cpp: one call from ids to PCM; engine_load.cpp:
+// engine_internal.h — shared by the engine's translation units only (engine.cpp: one call from ids to PCM; engine_delivery.cpp: the delivery chain behind the vocoder; engine_load.cpp:
 // weights; engine_stage1.cpp: text encoder + duration predictor; engine_flow.cpp: prior sampling + coupling flow;
 // engine_vocoder.cpp: HiFiGAN; engine_convert.cpp / engine_align.cpp: voice conversion and forced alignment; engine_support.cpp: profiler, arenas,
 // tokenizer, noise, roctx ranges).
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "window_plan.h"
 
 namespace vits {
 
@@ -69,6 +70,24 @@ struct RoctxRange {
         prof.end(stream);                  \
         if (e__ != hipSuccess) return e__; \
     } while (0)
+
+// one profiled launch of the delivery chain and the streaming loop (chain: it reads what the launch in front of it wrote); -1 + err when it fails
+#define PROF_LAUNCH(name, flops, bytes, call)                          \
+    do {                                                               \
+        prof.begin(name, flops, bytes, stream, /*chain=*/true);        \
+        const hipError_t e = (call);                                   \
+        prof.end(stream);                                              \
+        HIP_OK(e);                                                     \
+    } while (0)
+
+// the ranges the entry points accept, and a float as their messages print it
+inline bool rate_ok(float r) { return std::isfinite(r) && r >= 0.1f && r <= 10.f; }
+inline bool noise_scale_ok(float v) { return std::isfinite(v) && v >= 0.f && v <= 10.f; }
+inline std::string fmt_float(float v) {
+    char buf[32];
+    std::snprintf(buf, sizeof(buf), "%.9g", (double)v);
+    return buf;
+}
 
 static inline TensorRef make_ref(float* p, int channels, int stride) {
     TensorRef t;
@@ -189,13 +208,18 @@ struct Call {
             }
     }
 
-    // vocoder windows (long-form / streaming)
-    struct Win {
-        int f0, f1, lo, hi;
-    };
-    std::vector<Win> wins;
-    bool windowed = false;
-    int Lw_max = 0, M = 1;
+    // the vocoder's waveform of the whole call, in samples (profiler accounting of the stages behind it)
+    int64_t wave_samples() const { return sum_frames * smul[n_up] + (int64_t)B * sadd[n_up]; }
+    // the frames of every track of a joined call: the sums over its utterances
+    std::vector<int64_t> track_frames() const {
+        std::vector<int64_t> tf((size_t)join->tracks, 0);
+        for (int g = 0; g < join->tracks; ++g)
+            for (int b = join->first[(size_t)g]; b < join->first[(size_t)g + 1]; ++b) tf[(size_t)g] += frames[b];
+        return tf;
+    }
+
+    // vocoder windows (long-form / streaming): window_plan.h, planned where stage two begins (Engine::run_stage_two)
+    WindowPlan win;
 
     // stage two (sized by B x L after the host read of the frame counts)
     struct S2 {
@@ -229,12 +253,6 @@ struct Call {
     };
     std::vector<TileMapJob> tm_jobs;
     int64_t tm_total = 0;
-    // host copy of what the device holds in d_len[vec] of window `win`
-    int win_len(size_t win, int vec, int b) const {
-        if (!windowed) return slen[vec][b];
-        const int lf = std::min(frames[b], wins[win].hi) - wins[win].lo;
-        return lf <= 0 ? 0 : lf * smul[vec] + sadd[vec];
-    }
     int ls = 0, lws = 0, S_stride = 0;
     size_t big = 0;        // floats of the largest vocoder activation (of one window)
     std::vector<int> sts;  // [stage] time stride of that stage's buffers
@@ -311,7 +329,7 @@ struct Call {
 // one vocoder window, window-local lengths
 struct WinCtx {
     size_t wi;
-    Call::Win wn;
+    WindowPlan::Win wn;
     int Lw;
     const int* d_len[8];
     std::vector<int> smax;      // window-local maxima per stage
