@@ -727,6 +727,57 @@ VITS_API int vits_model_get_pitch(const vits_model* model, float* ratio);
 VITS_API int vits_model_set_pitch_ratios(vits_model* model, const float* ratios, int32_t n);
 VITS_API int64_t vits_model_last_pitch(vits_model* model, int64_t* dst, size_t cap);
 
+/* ---- a stated tempo: a pitch-preserving time stretch of PCM, on the device -------------------------------------------------------------------
+ * A voice conversion predicts no durations, so it has no free stretch to pay for a rate or a pitch with. What serves it is a time stretch of the
+ * PCM itself: waveform-similarity overlap-add, with every decision made in integers, so that device, host and any restatement agree bit for bit.
+ *
+ * The definition. The stage runs per row: N samples at the rate sr, and a tempo q, a float in [0.5, 2]; q > 1 is faster, q = 1 is off.
+ *   Plan: H = 4 floor(sr / 400) is the hop and the cross-fade length (160 at 16 kHz, 220 at 22.05 kHz); D = 4 floor(sr / 500) the search radius (128,
+ *     176); Q = q 2^24 (an exact integer); N' = ceil(N 2^24 / Q) (vits_pitch_plan's formula); F = ceil(N' / H) segments.
+ *   Search signal: xq[n] = 0 for a NaN sample, else clamp(rint(x[n] 32768), -32768, 32767) (to nearest even; the product is exact); xq[n] = 0 and
+ *     x[n] = 0 outside the row's own [0, N).
+ *   Segment starts s_k, k = 0 .. F: s_0 = 0. For k >= 1, a_k = (k H Q) >> 24 in 64 bits and c_k = s_(k-1) + H, where the segment before would go
+ *     on. SAD_k(d) = sum over i < H of |xq[c_k + i] - xq[a_k + d + i]| for d in [-D, D], exact in integers. s_k = a_k + d*, d* the FIRST minimum in
+ *     the order 0, -1, +1, -2, +2, .., -D, +D: ties go to the smallest |d|, of two equal |d| to the negative one. Silence keeps d = 0.
+ *   Output, for m = k H + i < N', 0 <= i < H: w[i] = fp32(2 i + 1) / fp32(2 H) (one correctly rounded division), v[i] = w[H - 1 - i],
+ *     y[m] = fp32(fp32(v[i] x[s_(k-1) + H + i]) + fp32(w[i] x[s_k + i])), with s_(-1) = -H: two rounded products and one rounded add, never
+ *     contracted into a fused multiply-add.
+ *   A row with Q = 2^24 is copied bit for bit.
+ * Nothing about tiles, batch position or neighbouring rows enters a sample or an offset. Measured on the restatement (tests/tempo_ref.py) with
+ * five-harmonic tones, F0 83 to 311 Hz, 1 s at 16 kHz, q from 0.5 to 2: the energy outside +-8 Hz of the harmonics stays below -33 dB of the
+ * total (the same overlap-add with every d = 0 scores about 0 dB), the spectral peak within 0.1 Hz, the RMS within 0.1 %.
+ *
+ * In a conversion. vits_model_set_conversion_prosody(model, rate, pitch) states the rate r and the pitch p of every utterance of every conversion (both
+ * initially 1; vits_model_get_conversion_prosody reads them, each pointer optional). vits_model_set_conversion_ratios(model, rates, pitches, n) gives the
+ * NEXT conversion one pair per utterance instead (host [n] each, copied at once; either array may be NULL: the model value for every utterance; both
+ * NULL or n = 0 drops what was given). Only vits_model_convert and vits_model_convert_batch take the pairs, as the first thing they do once the engine
+ * has the call, and they are gone when that call returns, whether it succeeded or not. Nothing else touches them: no text-to-speech call, no alignment,
+ * no setter, getter, tap or report. vits_process_opts keeps its size. Per utterance q = (float)((double)r / (double)p): the time stretch runs with
+ * q on the vocoder's row at the model's rate, and when p != 1 the varispeed of "a stated pitch" then runs with p on the stage's output (it restores
+ * the duration the rate asks for and multiplies every frequency by p). The result is, bit for bit, the plain conversion followed by vits_op_tempo, then
+ * vits_op_pitch. Everything behind them sees the final audio: edges, level, limiter, the output resampler, PCM16. lengths[] derives from the final
+ * length; frames[] stays floor(N / hop). Taken with vocoder_chunk_frames (without on_chunk), out_device and skip_host_copy.
+ * Refused before anything is queued, each with a message that names the utterance: r, p or q not finite or outside [0.5, 2]; another count of pairs
+ * than utterances; on_chunk with any r or p other than 1; a model rate outside [8000, 48000] with any r or p other than 1. The ratios of
+ * vits_model_set_pitch_ratios and the prosody fields stay refused in a conversion, and vits_model_set_pitch has no effect there.
+ * Tap "waveform_tempo" [1][N'] is the stage's output ("waveform_pitch" the varispeed's behind it; "waveform" stays the vocoder's row).
+ * vits_model_last_tempo writes int64 [B][4] = {Q, N, N', F} of the most recently completed call (cap >= 4 B), 0 rows when it stretched nothing; returns
+ * the number of rows, -1: model NULL. With r = p = 1 everywhere nothing is queued and nothing is allocated: every bit and vits_model_weight_bytes are
+ * what they were. The stage keeps no table on the device.
+ * vits_model_set_conversion_prosody: 0, or -1 + message with the handle unchanged. vits_model_set_conversion_ratios: 0, or -1 + message (n < 0); the
+ * values are checked by the conversion that takes them.
+ *
+ * Host only, no device needed. vits_tempo_plan: 0 and H, D, Q, F, N' of a row of n samples (each pointer optional), or -1 + message (a rate
+ * outside [8000, 48000], a tempo that is not finite or outside [0.5, 2], n outside [0, 2^30]). vits_tempo_host: the definition evaluated
+ * sequentially: y (y_cap >= N' floats) gets the row and offsets (optional; offsets_cap >= F) d*_k for k = 1 .. F; returns N', -1 + message on
+ * failure. */
+VITS_API int vits_tempo_plan(int32_t rate, float tempo, int64_t n, int32_t* H, int32_t* D, int64_t* Q, int64_t* F, int64_t* n_out);
+VITS_API int64_t vits_tempo_host(const float* x, int64_t n, int32_t rate, float tempo, float* y, size_t y_cap, int32_t* offsets, size_t offsets_cap);
+VITS_API int vits_model_set_conversion_prosody(vits_model* model, float rate, float pitch);
+VITS_API int vits_model_get_conversion_prosody(const vits_model* model, float* rate, float* pitch);
+VITS_API int vits_model_set_conversion_ratios(vits_model* model, const float* rates, const float* pitches, int32_t n);
+VITS_API int64_t vits_model_last_tempo(vits_model* model, int64_t* dst, size_t cap);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -1252,6 +1303,16 @@ VITS_API int vits_op_resample(int32_t in_rate, int32_t out_rate, int32_t batch, 
  * shorter than the longest output row. */
 VITS_API int vits_op_pitch(int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const float* ratios, float* y, int64_t y_stride,
                            int64_t* n_out);
+
+/* The time-stretch kernels (see "a stated tempo" for the definition) on a ragged batch at `rate` with a tempo per row: x host [batch][x_stride],
+ * lens host [batch] (0 <= lens[b] <= x_stride; NULL: every row has x_stride), tempos host [batch], y host [batch][y_stride], n_out host [batch] =
+ * N' of every row, offsets host int32 [batch][offsets_stride] or NULL = d*_1 .. d*_F of every row. The device copies of x and y keep the caller's
+ * strides and the caller's alignment within 16 bytes; x holds 0xFF bytes behind every lens[b], so a read past a row shows; y and offsets hold
+ * the vits_op_set_output_fill byte before the kernels run and come back whole, so a write behind N' or behind F shows. Refused (-1 + message): what
+ * vits_tempo_plan refuses (naming the row), a length outside its row, a y_stride shorter than the longest output row, an offsets_stride below
+ * the largest F. */
+VITS_API int vits_op_tempo(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const float* tempos, float* y,
+                           int64_t y_stride, int64_t* n_out, int32_t* offsets, int64_t offsets_stride);
 
 /* The levelling kernels (see vits_model_set_level for the definition) on a ragged batch, staged exactly as the engine stages it: x host
  * [batch][x_stride] at `rate`, lens host [batch] (0 <= lens[b] <= x_stride; NULL: every row has x_stride). The device copy of x holds NaNs

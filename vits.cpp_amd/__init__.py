@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_edges", "vits_model_get_edges", "vits_model_last_edges", "vits_edges_plan", "vits_edges_host", "vits_op_edges",
     "vits_pitch_ratio", "vits_pitch_plan", "vits_pitch_table", "vits_pitch_host", "vits_op_pitch",
     "vits_model_set_pitch", "vits_model_get_pitch", "vits_model_set_pitch_ratios", "vits_model_last_pitch",
+    "vits_tempo_plan", "vits_tempo_host", "vits_op_tempo",
+    "vits_model_set_conversion_prosody", "vits_model_get_conversion_prosody", "vits_model_set_conversion_ratios", "vits_model_last_tempo",
     "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences", "vits_model_process_joined", "vits_model_last_joins", "vits_model_speak",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
@@ -406,6 +408,20 @@ def lib():
     L.vits_model_set_pitch_ratios.argtypes = [vp, vp, i32]
     L.vits_model_last_pitch.restype = i64
     L.vits_model_last_pitch.argtypes = [vp, vp, sz]
+    L.vits_tempo_plan.restype = i32
+    L.vits_tempo_plan.argtypes = [i32, C.c_float, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.vits_tempo_host.restype = i64
+    L.vits_tempo_host.argtypes = [vp, i64, i32, C.c_float, vp, sz, vp, sz]
+    L.vits_model_set_conversion_prosody.restype = i32
+    L.vits_model_set_conversion_prosody.argtypes = [vp, C.c_float, C.c_float]
+    L.vits_model_get_conversion_prosody.restype = i32
+    L.vits_model_get_conversion_prosody.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.vits_model_set_conversion_ratios.restype = i32
+    L.vits_model_set_conversion_ratios.argtypes = [vp, vp, vp, i32]
+    L.vits_model_last_tempo.restype = i64
+    L.vits_model_last_tempo.argtypes = [vp, vp, sz]
+    L.vits_op_tempo.restype = i32
+    L.vits_op_tempo.argtypes = [i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, i64]
     L.vits_model_last_edges.restype = i64
     L.vits_model_last_edges.argtypes = [vp, vp, sz]
     L.vits_edges_plan.restype = i32
@@ -895,6 +911,59 @@ class Model:
             raise VitsError(last_error())
         return out
 
+    # -- a conversion's rate and pitch: the model-level values (vits_model_set_conversion_prosody) ------------------------------------
+    @property
+    def conversion_prosody(self):
+        """(rate, pitch) of every utterance of a conversion that vc_rate / vc_pitch give none for (1, 1 = off)"""
+        r, p = C.c_float(), C.c_float()
+        if lib().vits_model_get_conversion_prosody(self._h, C.byref(r), C.byref(p)) != 0:
+            raise VitsError(last_error())
+        return float(r.value), float(p.value)
+
+    def set_conversion_prosody(self, rate=1.0, pitch=1.0):
+        """vits_model_set_conversion_prosody: the rate and the pitch of a conversion, each in [0.5, 2]; 1, 1 switches both stages off"""
+        if lib().vits_model_set_conversion_prosody(self._h, float(rate), float(pitch)) != 0:
+            raise VitsError(last_error())
+
+    def set_conversion_ratios(self, rates=None, pitches=None):
+        """vits_model_set_conversion_ratios: one (rate, pitch) pair per utterance for the NEXT conversion on this handle (None for one of them: the model
+        value; None for both drops what was given); the vc_rate / vc_pitch keywords of convert_batch and convert do this"""
+        r = None if rates is None else np.ascontiguousarray(rates, dtype=np.float32).ravel()
+        p = None if pitches is None else np.ascontiguousarray(pitches, dtype=np.float32).ravel()
+        if r is not None and p is not None and r.size != p.size:
+            raise ValueError("rates and pitches need the same count")
+        n = 0 if r is None and p is None else (r if r is not None else p).size
+        if lib().vits_model_set_conversion_ratios(self._h, _ptr(r), _ptr(p), n) != 0:
+            raise VitsError(last_error())
+
+    def _with_conversion_ratios(self, vc_rate, vc_pitch, B, c_call):
+        """The vc_rate / vc_pitch keywords of a conversion: runs c_call() with the pairs given to the handle and returns what it returns. A scalar is broadcast
+        to the batch; None gives nothing (the model value). Whatever happens, no pair given here is left on the handle for a later call."""
+        if vc_rate is None and vc_pitch is None:
+            return c_call()
+        given = []
+        for v in (vc_rate, vc_pitch):
+            if v is not None and np.ndim(v) and np.size(v) not in (1, B):
+                raise ValueError("vc_rate and vc_pitch need a scalar or one value per utterance")
+            given.append(None if v is None else np.broadcast_to(np.asarray(v, np.float32).ravel(), (B,)))
+        self.set_conversion_ratios(*given)
+        try:
+            return c_call()
+        finally:
+            self.set_conversion_ratios(None, None)
+
+    def last_tempo(self):
+        """vits_model_last_tempo: int64 [B, 4] = (Q, N, N', F) of the most recently completed call, or None when it stretched nothing"""
+        n = lib().vits_model_last_tempo(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n, 4), np.int64)
+        if lib().vits_model_last_tempo(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
+
     # -- prosody: the transformers.VitsModel attributes, the model-level values (vits_model_set_prosody) --------------------------
     def get_prosody(self):
         """(speaking_rate, noise_scale, noise_scale_duration) the reference entry points and calls without per-utterance values use"""
@@ -1182,12 +1251,14 @@ class Model:
 
     def convert_batch(self, pcm, lengths=None, src=-1, tgt=-1, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_prior=None,
                       collect_taps=False, out_device=None, out_device_stride=0, skip_host_copy=False, vocoder_chunk_frames=0, on_chunk=None,
-                      noise_seed_offsets=None, keep_pcm=True, **refused):
+                      noise_seed_offsets=None, keep_pcm=True, vc_rate=None, vc_pitch=None, **refused):
         """Voice conversion (vits_model_convert_batch). pcm: float32 [B, stride] (or one 1-D utterance) at the model's sampling rate; lengths:
         valid samples per row (None = the whole row); src / tgt: the source and target speaker, one int for every utterance or one per
         utterance (-1 = none). Returns (list of per-utterance PCM arrays or None, lengths, frames) like process_batch. Keyword arguments
         that conversion refuses (fixed_duration, frames_only, async_, speaker_ids, and the prosody arguments of process_batch) are passed on, so that
-        the library says why. The model-level prosody (speaking_rate, noise_scale, noise_scale_duration) does not affect a conversion."""
+        the library says why. The model-level prosody (speaking_rate, noise_scale, noise_scale_duration) does not affect a conversion. vc_rate / vc_pitch:
+        a scalar or one value per utterance in [0.5, 2] (None = the model value, set_conversion_prosody): the converted audio is time-stretched to that rate
+        and shifted to that pitch on the device."""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         if pcm.ndim == 1:
             pcm = pcm[None, :]
@@ -1206,17 +1277,17 @@ class Model:
             setattr(o, field, v)
         cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
-        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o),
-                                                                                    C.byref(res))) != 0:
+        call = lambda: lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o), C.byref(res))
+        if self._with_conversion_ratios(vc_rate, vc_pitch, B, lambda: self._with_pitch(pitch_ratio, B, call)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
         return _take_result(res, B, keep_pcm)
 
-    def convert(self, pcm, src=-1, tgt=-1):
-        """vits_model_convert: one utterance, the model's default mode and the reference noise stream (like process)"""
+    def convert(self, pcm, src=-1, tgt=-1, vc_rate=None, vc_pitch=None):
+        """vits_model_convert: one utterance, the model's default mode and the reference noise stream (like process); vc_rate / vc_pitch as in convert_batch"""
         pcm = np.ascontiguousarray(pcm, dtype=np.float32).ravel()
-        r = lib().vits_model_convert(self._h, _ptr(pcm), pcm.size, int(src), int(tgt))
+        r = self._with_conversion_ratios(vc_rate, vc_pitch, 1, lambda: lib().vits_model_convert(self._h, _ptr(pcm), pcm.size, int(src), int(tgt)))
         if not r.data:
             raise VitsError(last_error())
         try:
@@ -1806,6 +1877,53 @@ def pitch(x, ratios, lens=None, out=None):
     if lib().vits_op_pitch(B, _ptr(x), stride, _ptr(ln), _ptr(r), _ptr(out), out.shape[1], _ptr(n_out)) != 0:
         raise VitsError(last_error())
     return out, n_out
+
+
+def tempo_plan(rate, q, n):
+    """vits_tempo_plan: (H, D, Q, F, N') of a row of n samples at `rate` and tempo q (host only)"""
+    H, D, Q, F, n_out = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+    if lib().vits_tempo_plan(int(rate), float(q), int(n), C.byref(H), C.byref(D), C.byref(Q), C.byref(F), C.byref(n_out)) != 0:
+        raise VitsError(last_error())
+    return int(H.value), int(D.value), int(Q.value), int(F.value), int(n_out.value)
+
+
+def tempo_host(x, rate, q):
+    """vits_tempo_host: the time stretch's definition evaluated sequentially on one row (host only) -> (y float32 [N'], offsets int32 [F])"""
+    x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    _, _, _, F, n_out = tempo_plan(rate, q, x.size)
+    y, off = np.zeros(max(n_out, 1), np.float32), np.zeros(max(F, 1), np.int32)
+    n = lib().vits_tempo_host(_ptr(x), x.size, int(rate), float(q), _ptr(y), y.size, _ptr(off), off.size)
+    if n < 0:
+        raise VitsError(last_error())
+    return y[:n], off[:F]
+
+
+def tempo(x, rate, tempos, lens=None, out=None):
+    """The time-stretch kernels on a ragged batch (vits_op_tempo). x: float32 [B, x_stride] (or one 1-D row), passed as it lies when it is C-contiguous float32
+    (stride and alignment reach the device, as do out's); tempos: a scalar or one tempo per row; lens: samples per row (None = the whole row). Returns (y float32
+    [B, y_stride], n_out int64 [B], offsets int32 [B, the largest F]): row b holds its n_out[b] samples and its F offsets and, behind them, the byte of
+    op_set_output_fill. out: a caller-owned float32 [B, y_stride] array, which is overwritten whole."""
+    x = np.asarray(x)
+    if x.dtype != np.float32 or not x.flags.c_contiguous:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    B, stride = x.shape
+    ln = np.full(B, stride, np.int64) if lens is None else np.ascontiguousarray(lens, dtype=np.int64).ravel()
+    r = np.ascontiguousarray(np.broadcast_to(np.asarray(tempos, np.float32).ravel(), (B,)))
+    if ln.size != B:
+        raise ValueError("lens needs one entry per row")
+    longest = max(-((-int(n) << 24) // max(int(float(p) * 2.0 ** 24), 1)) if np.isfinite(p) else 0 for n, p in zip(np.maximum(ln, 0), r))
+    if out is None:
+        out = np.zeros((B, max(longest, 1)), np.float32)
+    elif out.dtype != np.float32 or out.ndim != 2 or out.shape[0] != B or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 [B, y_stride] array")
+    H = 4 * (int(rate) // 400)
+    off = np.zeros((B, max(-(-longest // H) if H > 0 else 0, 1) + 1), np.int32)
+    n_out = np.zeros(B, np.int64)
+    if lib().vits_op_tempo(int(rate), B, _ptr(x), stride, _ptr(ln), _ptr(r), _ptr(out), out.shape[1], _ptr(n_out), _ptr(off), off.shape[1]) != 0:
+        raise VitsError(last_error())
+    return out, n_out, off
 
 
 def loudness_plan(rate):

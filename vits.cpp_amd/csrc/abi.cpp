@@ -947,6 +947,75 @@ VITS_API int64_t vits_model_last_pitch(vits_model* model, int64_t* dst, size_t c
     VITS_CATCH(-1)
 }
 
+// ---- a stated tempo (include/vits.h: the definition) ---------------------------------------------------------------------------------------------------
+VITS_API int vits_tempo_plan(int32_t rate, float tempo, int64_t n, int32_t* H, int32_t* D, int64_t* Q, int64_t* F, int64_t* n_out) {
+    VITS_TRY
+    vits::TempoPlan p;
+    std::string err;
+    if (!vits::tempo_plan(rate, tempo, n, p, err)) return fail("vits_tempo_plan: " + err);
+    if (H) *H = p.H;
+    if (D) *D = p.D;
+    if (Q) *Q = p.Q;
+    if (F) *F = p.F;
+    if (n_out) *n_out = p.n_out;
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_tempo_host(const float* x, int64_t n, int32_t rate, float tempo, float* y, size_t y_cap, int32_t* offsets, size_t offsets_cap) {
+    VITS_TRY
+    vits::TempoPlan p;
+    std::string err;
+    if (!y || (!x && n) || (!offsets && offsets_cap)) return fail("vits_tempo_host: null argument (y, x with n > 0, or offsets with offsets_cap > 0)");
+    if (!vits::tempo_plan(rate, tempo, n, p, err)) return fail("vits_tempo_host: " + err);
+    if (y_cap < (size_t)p.n_out) return fail("vits_tempo_host: y_cap = " + std::to_string(y_cap) + " is below the row's " + std::to_string(p.n_out) + " output samples");
+    if (offsets && offsets_cap < (size_t)p.F)
+        return fail("vits_tempo_host: offsets_cap = " + std::to_string(offsets_cap) + " is below the row's " + std::to_string(p.F) + " segments");
+    vits::tempo_host(x, n, p, y, offsets);
+    return p.n_out;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_model_set_conversion_prosody(vits_model* model, float rate, float pitch) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_conversion_prosody(rate, pitch, err); });
+}
+VITS_API int vits_model_get_conversion_prosody(const vits_model* model, float* rate, float* pitch) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    if (rate) *rate = model->eng.vc_rate;
+    if (pitch) *pitch = model->eng.vc_pitch;
+    return 0;
+}
+VITS_API int vits_model_set_conversion_ratios(vits_model* model, const float* rates, const float* pitches, int32_t n) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_conversion_ratios(rates, pitches, n, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_model_last_tempo(vits_model* model, int64_t* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const int64_t* p = model->eng.last_tempo(rows);  // [rows][4]: Q, N, N', F
+    if (rows && dst && cap >= (size_t)4 * rows) std::copy_n(p, (size_t)4 * rows, dst);
+    return rows;
+    VITS_CATCH(-1)
+}
+
 VITS_API int32_t vits_model_vocab_size(const vits_model* model) { return model ? model->eng.hp.vocab_size : 0; }
 VITS_API int64_t vits_model_weight_bytes(const vits_model* model) { return model ? model->eng.weight_bytes : 0; }
 VITS_API int32_t vits_model_duration_predictor_kind(const vits_model* model) { return model ? (model->eng.hp.stochastic_duration ? 0 : 1) : -1; }

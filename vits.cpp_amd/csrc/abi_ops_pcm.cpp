@@ -1,4 +1,4 @@
-// abi_ops_pcm.cpp — operator-level entry points of the PCM kernels: vits_op_resample, vits_op_level, vits_op_limit (host arrays in, host arrays out; staging:
+// abi_ops_pcm.cpp — operator-level entry points of the PCM kernels: vits_op_resample, vits_op_pitch, vits_op_tempo, vits_op_level, vits_op_limit (host arrays in, host arrays out; staging:
 // abi_ops_common.h), vits_op_edges (device arrays, as the engine's delivery calls it) and vits_op_join (host arrays; y goes up and comes back).
 #include <cmath>
 
@@ -132,6 +132,61 @@ VITS_API int vits_op_pitch(int32_t batch, const float* x, int64_t x_stride, cons
     c.batch = batch;
     c.max_out = longest;
     return finish(launch_pitch(c, nullptr)) && dy.get(y, ny) ? 0 : -1;
+    VITS_CATCH(-1)
+}
+
+VITS_API int vits_op_tempo(int32_t rate, int32_t batch, const float* x, int64_t x_stride, const int64_t* lens, const float* tempos, float* y, int64_t y_stride,
+                           int64_t* n_out, int32_t* offsets, int64_t offsets_stride) {
+    VITS_TRY
+    if (batch <= 0 || !x || !tempos || !y || !n_out || x_stride <= 0 || y_stride <= 0 || (offsets && offsets_stride <= 0))
+        return fail("vits_op_tempo: null argument or empty batch");
+    std::vector<int32_t> n(batch);
+    int64_t longest = 0, longest_b = 0, most = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int64_t len = lens ? lens[b] : x_stride;
+        if (len < 0 || len > x_stride) return fail("vits_op_tempo: lens[" + std::to_string(b) + "] = " + std::to_string(len) + " is outside [0, x_stride = " + std::to_string(x_stride) + "]");
+        TempoPlan p;
+        std::string err;
+        if (!tempo_plan(rate, tempos[b], len, p, err)) return fail("vits_op_tempo: row " + std::to_string(b) + ": " + err);
+        n[b] = (int32_t)len;
+        n_out[b] = p.n_out;
+        most = std::max(most, p.F);
+        if (p.n_out > longest) longest = p.n_out, longest_b = b;
+    }
+    if (y_stride < longest)
+        return fail("vits_op_tempo: y_stride = " + std::to_string(y_stride) + " is shorter than the longest output row (row " + std::to_string(longest_b) + ": " +
+                    std::to_string(n[longest_b]) + " samples in, " + std::to_string(longest) + " out)");
+    if (offsets && offsets_stride < most)
+        return fail("vits_op_tempo: offsets_stride = " + std::to_string(offsets_stride) + " is below the largest segment count (" + std::to_string(most) + ")");
+    // the rows of x and y at the caller's own strides and at the caller's own alignment within 16 bytes (so that a test reaches the unaligned path), 0xFF
+    // bytes behind every length of x, the fill byte all over y, the starts and the offsets
+    const size_t offx = ((uintptr_t)x & 15) / 4, offy = ((uintptr_t)y & 15) / 4;
+    std::vector<float> hx((size_t)batch * x_stride + 4);
+    std::memset(hx.data(), 0xFF, hx.size() * 4);
+    for (int b = 0; b < batch; ++b) std::memcpy(&hx[offx + (size_t)b * x_stride], x + (size_t)b * x_stride, sizeof(float) * (size_t)n[b]);
+    const size_t ny = (size_t)batch * y_stride * 4, nof = offsets ? (size_t)batch * offsets_stride * 4 : 0;
+    const int64_t ss = most + 1;
+    DevMem dx, dy, ds, dof, dn, dq;
+    if (!dx.put(hx.data(), hx.size() * 4) || !dy.fill(ny + 16, g_op_out_fill) || !ds.fill((size_t)batch * ss * 4, g_op_out_fill) || (offsets && !dof.fill(nof, g_op_out_fill)) ||
+        !dn.put(n.data(), (size_t)batch * 4) || !dq.put(tempos, (size_t)batch * 4))
+        return -1;
+    TempoCall c;
+    c.x = dx.f() + offx;
+    c.x_stride = x_stride;
+    c.lens = dn.i();
+    c.tempos = dq.f();
+    c.rate = rate;
+    c.starts = ds.i();
+    c.starts_stride = ss;
+    c.offsets = offsets ? dof.i() : nullptr;
+    c.offsets_stride = offsets_stride;
+    c.y = dy.f() + offy;
+    c.y_stride = y_stride;
+    c.batch = batch;
+    c.max_out = longest;
+    hipError_t e = launch_tempo_search(c, nullptr);
+    if (e == hipSuccess) e = launch_tempo_ola(c, nullptr);
+    return finish(e) && DevMem::ok(hipMemcpy(y, c.y, ny, hipMemcpyDeviceToHost), "copy back failed") && (!offsets || dof.get(offsets, nof)) ? 0 : -1;
     VITS_CATCH(-1)
 }
 

@@ -7,9 +7,10 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     DeliveryPlan p;
     const bool multiplies = a.level >= DLEVEL_GAIN;
     // the refusals, in the order the engine has always checked them (level before edges, the limiter's first); a joined ask is refused for what it is first,
-    // then an ask with pitch
+    // then an ask with tempo, then one with pitch
     if (a.joined && a.on_chunk) p.refusal = REFUSE_JOIN_STREAM;
     else if (a.joined && a.async) p.refusal = REFUSE_JOIN_ASYNC;
+    else if (a.tempo && a.on_chunk) p.refusal = REFUSE_TEMPO_STREAM;  // (async: a conversion, the one caller with a tempo, is synchronous and says so itself)
     else if (a.pitch && a.on_chunk) p.refusal = REFUSE_PITCH_STREAM;
     else if (a.pitch && a.async) p.refusal = REFUSE_PITCH_ASYNC;
     else if (a.on_chunk && a.limiter && multiplies) p.refusal = REFUSE_LIMIT_STREAM;
@@ -22,12 +23,14 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     p.limits = multiplies && a.limiter;
     // The stages that write, in their order, each into its own arena buffer — except the last one, which writes straight to the caller's buffer when the
     // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the stride of what is in front of it: the
-    // pitch stage's, else the vocoder's. Behind a join they are the tracks', J_stride apart.
-    constexpr int kSlots = STAGE_COUNT + 2;  // vocoder, pitch, edges, join, level, resample
-    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.pitch, &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
-    const bool writes[kSlots] = {true, a.pitch, a.edges, a.joined, multiplies, a.rate};
-    const int own[kSlots] = {BUF_WAVE, BUF_PITCH, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
-    const int own_stride[kSlots] = {STRIDE_S, STRIDE_P, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : (a.pitch ? STRIDE_P : STRIDE_S)), STRIDE_OUT_WS};
+    // pitch stage's, else the tempo stage's, else the vocoder's. Behind a join they are the tracks', J_stride apart. The row bounds, once: a tempo stage's rows
+    // hold at most 2 S_stride samples (T_stride), a pitch stage's at most twice what lies in front of it (P_stride: 2 S_stride, or 2 T_stride behind a tempo stage).
+    constexpr int kSlots = STAGE_COUNT + 3;  // vocoder, tempo, pitch, edges, join, level, resample
+    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.tempo, &p.pitch, &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
+    const bool writes[kSlots] = {true, a.tempo, a.pitch, a.edges, a.joined, multiplies, a.rate};
+    const int own[kSlots] = {BUF_WAVE, BUF_TEMPO, BUF_PITCH, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
+    const int head_stride = a.pitch ? STRIDE_P : (a.tempo ? STRIDE_T : STRIDE_S);
+    const int own_stride[kSlots] = {STRIDE_S, STRIDE_T, STRIDE_P, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : head_stride), STRIDE_OUT_WS};
     int last = 0;
     for (int s = 0; s < kSlots; ++s)
         if (writes[s]) last = s;
@@ -56,6 +59,7 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
             if (buf == BUF_OUT) p.needs |= NEED_WAVE_OUT;
             if (buf == BUF_JOIN) p.needs |= NEED_WAVE_JOIN;
             if (buf == BUF_PITCH) p.needs |= NEED_WAVE_PITCH;
+            if (buf == BUF_TEMPO) p.needs |= NEED_WAVE_TEMPO;
         }
     if (a.edges) p.needs |= NEED_ED_SCRATCH;
     if (a.level != DLEVEL_NONE) p.needs |= NEED_LVL_SCRATCH;

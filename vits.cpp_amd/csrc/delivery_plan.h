@@ -1,5 +1,5 @@
 // delivery_plan.h — how a call's PCM travels from the vocoder to what is handed out (host only, like launch_plan.h and tile_map.h: no kernel, no device).
-// The stages behind the vocoder — a stated pitch (pitch.hip), stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
+// The stages behind the vocoder — a stated tempo (tempo.hip), a stated pitch (pitch.hip), stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
 // stage in front of them wrote. delivery_plan() states that chain ONCE, from what the handle and the call ask for: who runs, which buffer each stage reads
 // and writes, which buffer is delivered, which arena buffers the call therefore needs, or why the combination is refused. The engine allocates from the
 // plan (layout_stage_two) and resolves its buffer ids to pointers in one place (Call::rows_of); tests/golden/delivery_plan_table.txt pins the whole table.
@@ -17,6 +17,7 @@ enum DeliveryBuf : int {
     BUF_CALLER,    // opts.out_device, rows out_device_stride apart
     BUF_JOIN,      // s2.wave_join: the joined tracks [G][J_stride] (a joined ask only)
     BUF_PITCH,     // s2.wave_pitch: the varispeed rows [B][P_stride] (an ask with pitch only)
+    BUF_TEMPO,     // s2.wave_tempo: the time-stretched rows [B][T_stride] (an ask with tempo only)
     BUF_COUNT
 };
 enum DeliveryStride : int {
@@ -26,7 +27,9 @@ enum DeliveryStride : int {
     STRIDE_OUT_WS,  // out_ws: the rows at the output rate
     STRIDE_CALLER,  // out_device_stride
     STRIDE_J,       // J_stride: the model-rate rows behind the join, one per track (the largest track bound; a joined ask only)
-    STRIDE_P,       // P_stride = 2 S_stride: the rows behind the pitch stage (the bound of N' at the smallest ratio, 0.5; an ask with pitch only)
+    STRIDE_P,       // P_stride: the rows behind the pitch stage, twice the stride of the rows in front of it (the bound of N' at the smallest ratio, 0.5): 2 S_stride,
+                    // or behind the tempo stage 2 T_stride (an ask with pitch only)
+    STRIDE_T,       // T_stride = 2 S_stride: the rows behind the tempo stage (the bound of N' at the smallest tempo, 0.5; an ask with tempo only)
     STRIDE_COUNT
 };
 // the level kinds as delivery sees them. The kinds that multiply are two here because only a plain gain streams
@@ -47,6 +50,7 @@ enum DeliveryRefusal : int {
     REFUSE_JOIN_ASYNC,    // a joined ask with async: the track lengths are read from the device behind the call's work
     REFUSE_PITCH_STREAM,  // pitch with on_chunk: streaming pitch is not built (a window's last samples need the next window's first)
     REFUSE_PITCH_ASYNC,   // pitch with async: the ratios travel through memory the call owns
+    REFUSE_TEMPO_STREAM,  // tempo with on_chunk: where a segment starts is decided by the samples around it, which a window's end does not have yet
     REFUSE_COUNT
 };
 enum DeliveryNeed : unsigned {
@@ -61,7 +65,8 @@ enum DeliveryNeed : unsigned {
     NEED_WAVE_JOIN = 1u << 8,   // a joined ask, unless the join writes straight to out_device: the tracks [G][J_stride]
     NEED_JOIN_TABLE = 1u << 9,  // a joined ask: the table join.hip reads
     NEED_WAVE_PITCH = 1u << 10,  // an ask with pitch, unless the stage writes straight to out_device: the rows [B][P_stride]
-    NEED_COUNT = 11
+    NEED_WAVE_TEMPO = 1u << 11,  // an ask with tempo, unless the stage writes straight to out_device: the rows [B][T_stride]
+    NEED_COUNT = 12
 };
 
 struct DeliveryAsk {
@@ -73,6 +78,7 @@ struct DeliveryAsk {
     bool on_chunk = false;     // opts.on_chunk
     bool async = false;        // opts.async
     bool pitch = false;        // some utterance of the call has a pitch ratio other than 1: the varispeed runs behind the vocoder, in front of the edges stage
+    bool tempo = false;        // some utterance of the call (a voice conversion) has a tempo other than 1: the time stretch runs behind the vocoder, in front of the varispeed
     bool joined = false;       // the call lays its utterances end to end into tracks (vits_model_process_joined): the join runs behind the edges stage
 };
 
@@ -96,6 +102,9 @@ struct DeliveryPlan {
     // an ask with pitch: the varispeed (pitch.hip), between stage[STAGE_VOCODER] and stage[STAGE_EDGES]. It always writes (rows P_stride apart); with the edges
     // stage off, a levelled buffer behind it follows its stride (STRIDE_P). Off for every other ask, whose plan is what it always was.
     Stage pitch;
+    // an ask with tempo: the time stretch (tempo.hip), between stage[STAGE_VOCODER] and the pitch stage. It always writes (rows T_stride apart); what follows it
+    // keeps that stride as it would the vocoder's. Off for every other ask, whose plan is what it always was.
+    Stage tempo;
     bool multiplies = false;  // the level stage writes (a plain multiply, or the limiter)
     bool limits = false;      // ... through the limiter
     DeliveryRoute delivered;  // what the call hands out: the destination of the last stage that writes

@@ -1015,6 +1015,7 @@ int Engine::hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_
     } else if (ed_n && out) edges_lengths(ed_.slot_rows(a1_slot_), B, out->lengths);
     lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
     pt_.store(c.pit_rows);
+    tm_.store(c.tem_rows);
     // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
     // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
     if (prof.on && prof.recs.size() > 50000) prof.collect();

@@ -372,6 +372,29 @@ class Engine {
     int resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const;
     // the rows [B][4] = {P, N, N', K} of the most recently completed call (empty: it shifted nothing)
     const int64_t* last_pitch(int& rows) const { return pt_.read(rows); }
+    // A conversion's rate and pitch (include/vits.h "a stated tempo": in a conversion; tempo.hip + pitch.hip): a conversion predicts no durations, so an
+    // utterance with rate r and pitch p is time-stretched by q = (float)((double)r / (double)p) behind the vocoder and, when p != 1, played back p times faster by
+    // the varispeed behind that. vc_rate / vc_pitch: the values of every utterance of a conversion that no pair was given for; 1 = off.
+    // set_conversion_prosody: 0, or -1 + a message with the handle unchanged (a value that is not finite or outside [0.5, 2]).
+    float vc_rate = 1.f, vc_pitch = 1.f;
+    int set_conversion_prosody(float rate, float pitch, std::string& err);
+    // the per-utterance pairs of the NEXT conversion (vits_model_set_conversion_ratios): copied here, taken by convert_batch alone (take_conversion_ratios:
+    // whatever becomes of the call they are gone). Either array may be NULL (the model value for every utterance); both NULL or n = 0 drops what was given.
+    int set_conversion_ratios(const float* rates, const float* pitches, int n, std::string& err);
+    struct ResolvedConversion {
+        std::vector<float> rates, pitches;  // as given (empty: not given)
+        int n = 0;
+        bool have = false;
+        std::vector<float> tempos, ratios;  // resolved: q_b and p_b [B]
+        const float* tempo = nullptr;       // non-null: some q_b != 1, the tempo stage runs
+        const float* pitch = nullptr;       // non-null: some p_b != 1, the pitch stage runs behind it
+    };
+    void take_conversion_ratios(ResolvedConversion& rc);
+    // 0, or -1 + a message naming the utterance: another count of pairs than utterances; r, p or q not finite or outside [0.5, 2]; on_chunk with any r or p
+    // other than 1; a model rate the stretch does not take
+    int resolve_conversion_prosody(int B, const vits_process_opts& o, ResolvedConversion& rc, std::string& err) const;
+    // the rows [B][4] = {Q, N, N', F} of the most recently completed call (empty: it stretched nothing)
+    const int64_t* last_tempo(int& rows) const { return tm_.read(rows); }
     // any sample rate (include/vits.h vits_model_set_rates): 0 = the model's own rate (a rate equal to it is stored as 0). input: the PCM given to
     // conversion and alignment; output: every PCM the handle delivers. 0, or -1 + a message with the handle unchanged (a rate outside the range, a
     // table that is too large). Nothing touches the device here: a pair's table is uploaded by the first call that uses it (rate_table).
@@ -608,12 +631,14 @@ class Engine {
     ReportRows<int64_t> ed_{sizeof(int)}, jn_;
     // the pitch stage's rows are host arithmetic (P, N and N' follow from the ratio and the frame count): the report never touches the device
     ReportRows<int64_t> pt_;
+    // ... and so are the tempo stage's (Q, N, N' and F follow from the tempo and the frame count)
+    ReportRows<int64_t> tm_;
     // the device lengths behind those rows: the trimmed lengths [B] that run_edges writes, and the track lengths T_g [G] that run_join writes behind the
     // joins' {o_b, n_b} rows of a call of B utterances (device rows, or a slot's landed copy). What Call::mr_lens points at when the stage runs
     int* edges_lens() { return static_cast<int*>(ed_.tail()); }
     static const int* track_lens(const int64_t* join_rows, int B) { return reinterpret_cast<const int*>(join_rows + (size_t)2 * B); }
     int* track_lens(int B) { return const_cast<int*>(track_lens(jn_.dev(), B)); }
-    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(); }
+    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(), tm_.clear(); }
     // a stated pitch: the interleaved table on the device (uploaded by the first call that shifts), a synchronous call's ratios on their way there, and the
     // stage from its source into its destination, as the call's plan routes them: queued behind the last vocoder window, in front of run_edges
     float* pitch_table_ = nullptr;
@@ -622,6 +647,15 @@ class Engine {
     bool pitch_given_set_ = false;
     const float* call_pitch_ = nullptr;   // the resolved ratios [B] of the call being queued (ResolvedPitch::pitch): non-null MEANS that the stage runs
     int run_pitch(Call& c);
+    // a stated tempo: the next conversion's pairs, the resolved tempos [B] of the conversion being queued (non-null MEANS that the stage runs), their pinned
+    // memory on the way to the device, and the stage (search, then overlap-add) from its source into its destination, as the call's plan routes them: queued
+    // behind the last vocoder window, in front of run_pitch
+    std::vector<float> vc_rates_given_, vc_pitches_given_;
+    int vc_given_n_ = 0;
+    bool vc_given_set_ = false;
+    const float* call_tempo_ = nullptr;
+    PinnedBuf<float> tempo_host_;
+    int run_tempo(Call& c);
     PinnedBuf<int64_t> join_table_host_;  // a joined call's table (host side of its H2D copy)
     std::vector<int32_t> join_index_;     // ... and what its report names each utterance (process_joined: b, or the caller's index)
     // the join of a joined call (join.hip) from its source into its destination, as the call's plan routes them: queued behind the edges stage, in front of run_level

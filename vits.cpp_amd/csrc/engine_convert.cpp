@@ -225,6 +225,8 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
 // ---- one conversion call -------------------------------------------------------------------------------------------------------
 int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
                           vits_batch_result* out, std::string& err) {
+    ResolvedConversion rc;  // (first of all: the pairs given for this conversion are taken, whatever becomes of it)
+    take_conversion_ratios(rc);
     std::vector<float> given;
     if (take_pitch_ratios(given)) {
         err = "voice conversion does not take the ratios of vits_model_set_pitch_ratios (a pitch is paid for by the duration predictor's stretch, and a conversion "
@@ -261,6 +263,9 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
                                     (side ? "target" : "source") + " speaker of utterance " + std::to_string(b) + ")";
             if (check_speaker(s, who, err)) return -1;
         }
+    // a rate and a pitch (include/vits.h "a stated tempo"): with every value 1 both stay null and the call is what it always was
+    if (resolve_conversion_prosody(B, o, rc, err)) return -1;
+    ScopedSet<const float*> tempo_scope(call_tempo_, rc.tempo), pitch_scope(call_pitch_, rc.pitch);
     DeliveryPlan refusable;  // (the refusals of the delivery chain, before anything is queued)
     if (plan_delivery(o, refusable, err)) return -1;
     clear_reports();
@@ -272,6 +277,7 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
     Call c(o, err, nullptr, B, 0);
     Call::Vc vc;
     c.vc = &vc;
+    c.tempo = call_tempo_, c.pitch = call_pitch_;
     c.md = o.mode == VITS_MODE_DEFAULT ? mode : o.mode;
     c.refmode = c.md == VITS_MODE_REFERENCE;
     c.n_up = (int)ups_.size();

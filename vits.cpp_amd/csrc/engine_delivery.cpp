@@ -1,5 +1,6 @@
-// engine_delivery.cpp — the delivery chain behind the vocoder (delivery_plan.h): the handle's settings (rates, level, limiter, edges, pitch) and their plans,
-// the call's routing plan and what the host knows of its rows, and the stages themselves: pitch, edges, join, level / limiter, the output resampler.
+// engine_delivery.cpp — the delivery chain behind the vocoder (delivery_plan.h): the handle's settings (rates, level, limiter, edges, pitch, a conversion's rate
+// and pitch) and their plans, the call's routing plan and what the host knows of its rows, and the stages themselves: tempo, pitch, edges, join, level / limiter,
+// the output resampler.
 // engine.cpp's run_stage_two calls run_delivery_tail behind the last vocoder window. Compiled with hipcc as host C++.
 #include <numeric>
 
@@ -83,6 +84,84 @@ int Engine::resolve_pitch(int B, int id_stride, const int32_t* id_lens, Resolved
     }
     rp.pitch = rp.ratios.data();
     rp.o.speaking_rates = rp.rates.data();
+    return 0;
+}
+
+int Engine::set_conversion_prosody(float rate, float pitch, std::string& err) {
+    for (int side = 0; side < 2; ++side) {
+        const float v = side ? pitch : rate;
+        if (!std::isfinite(v) || v < kTempoMin || v > kTempoMax) {
+            err = std::string("vits_model_set_conversion_prosody: ") + (side ? "pitch " : "rate ") + fmt_float(v) + " is not finite or outside [0.5, 2]";
+            return -1;
+        }
+    }
+    vc_rate = rate, vc_pitch = pitch;
+    return 0;
+}
+
+int Engine::set_conversion_ratios(const float* rates, const float* pitches, int n, std::string& err) {
+    if (n < 0) {
+        err = "vits_model_set_conversion_ratios: n < 0";
+        return -1;
+    }
+    const bool any = n > 0 && (rates || pitches);
+    vc_rates_given_.assign(rates, rates + (any && rates ? n : 0));
+    vc_pitches_given_.assign(pitches, pitches + (any && pitches ? n : 0));
+    vc_given_n_ = any ? n : 0;
+    vc_given_set_ = any;
+    return 0;
+}
+
+void Engine::take_conversion_ratios(ResolvedConversion& rc) {
+    rc.have = vc_given_set_;
+    rc.n = vc_given_n_;
+    rc.rates.clear(), rc.pitches.clear();
+    rc.rates.swap(vc_rates_given_);
+    rc.pitches.swap(vc_pitches_given_);
+    vc_given_set_ = false, vc_given_n_ = 0;
+}
+
+int Engine::resolve_conversion_prosody(int B, const vits_process_opts& o, ResolvedConversion& rc, std::string& err) const {
+    if (rc.have && rc.n != B) {
+        err = "vits_model_set_conversion_ratios gave " + std::to_string(rc.n) + " pairs, and this call has " + std::to_string(B) + " utterances";
+        return -1;
+    }
+    const float* rates = rc.have && !rc.rates.empty() ? rc.rates.data() : nullptr;
+    const float* pitches = rc.have && !rc.pitches.empty() ? rc.pitches.data() : nullptr;
+    rc.tempos.assign((size_t)B, 1.f);
+    rc.ratios.assign((size_t)B, 1.f);
+    bool any_q = false, any_p = false;
+    for (int b = 0; b < B; ++b) {
+        const float r = rates ? rates[b] : vc_rate, p = pitches ? pitches[b] : vc_pitch;
+        const std::string who = "utterance " + std::to_string(b) + ": ";
+        for (int side = 0; side < 2; ++side) {
+            const float v = side ? p : r;
+            if (!std::isfinite(v) || v < kTempoMin || v > kTempoMax) {
+                err = who + (side ? "conversion pitch " : "conversion rate ") + fmt_float(v) + " is not finite or outside [0.5, 2]";
+                return -1;
+            }
+        }
+        if (r == 1.f && p == 1.f) continue;
+        if (o.on_chunk) {
+            err = who + "on_chunk streams an utterance while it is being made, and this one has the conversion rate " + fmt_float(r) + " and pitch " + fmt_float(p) +
+                  " (vits_model_set_conversion_ratios, vits_model_set_conversion_prosody): where a segment of the time stretch starts is decided by samples a "
+                  "window's end does not have yet: call without on_chunk, or with every rate and pitch 1";
+            return -1;
+        }
+        const float q = (float)((double)r / (double)p);
+        if (!std::isfinite(q) || q < kTempoMin || q > kTempoMax) {
+            err = who + "conversion rate " + fmt_float(r) + " over pitch " + fmt_float(p) + " is the tempo " + fmt_float(q) + ", outside [0.5, 2]";
+            return -1;
+        }
+        if (hp.sampling_rate < kTempoMinRate || hp.sampling_rate > kTempoMaxRate) {
+            err = who + "a conversion rate or pitch other than 1 needs a model rate in [8000, 48000] Hz (this model: " + std::to_string(hp.sampling_rate) + " Hz)";
+            return -1;
+        }
+        rc.tempos[(size_t)b] = q, rc.ratios[(size_t)b] = p;
+        any_q = any_q || q != 1.f, any_p = any_p || p != 1.f;
+    }
+    if (any_q) rc.tempo = rc.tempos.data();
+    if (any_p) rc.pitch = rc.ratios.data();
     return 0;
 }
 
@@ -190,7 +269,8 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
     ask.on_chunk = o.on_chunk != nullptr;
     ask.async = o.async != 0;
     ask.joined = joined;
-    ask.pitch = call_pitch_ != nullptr;  // (resolved: Engine::resolve_pitch)
+    ask.pitch = call_pitch_ != nullptr;  // (resolved: Engine::resolve_pitch, or a conversion's Engine::resolve_conversion_prosody)
+    ask.tempo = call_tempo_ != nullptr;  // (resolved: Engine::resolve_conversion_prosody)
     plan = delivery_plan(ask);
     switch (plan.refusal) {
         case DELIVER_OK: return 0;
@@ -231,6 +311,11 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
             err = "async returns before the device has finished, and an utterance of this call has a pitch ratio other than 1 (vits_model_set_pitch_ratios, "
                   "vits_model_set_pitch): streaming pitch is not built, and the ratios travel to the device through memory the next call reuses: call without async, "
                   "or pipeline with vits_model_submit_batch / vits_model_wait";
+            break;
+        case REFUSE_TEMPO_STREAM:
+            err = "on_chunk streams an utterance while it is being made, and an utterance of this conversion has a rate or pitch other than 1 "
+                  "(vits_model_set_conversion_ratios, vits_model_set_conversion_prosody): where a segment of the time stretch starts is decided by samples a window's "
+                  "end does not have yet: call without on_chunk, or with every rate and pitch 1";
             break;
         default: err = "this combination of delivery stages is not supported"; break;
     }
@@ -397,6 +482,30 @@ int Engine::plan_rows(Call& c) {
     const int B = c.B, n_up = c.n_up;
     if (plan_delivery(o, c.dp, err, c.join != nullptr)) return -1;
     // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
+    if (c.tempoed()) {
+        // a stated tempo: N' and F of every row are host arithmetic; so are the rows of the report
+        c.tem_len.resize((size_t)B);
+        c.tem_rows.resize((size_t)4 * B);
+        int64_t most = 0;
+        for (int b = 0; b < B; ++b) {
+            TempoPlan tp;
+            std::string why;
+            if (!tempo_plan(hp.sampling_rate, c.tempo[b], c.slen[n_up][b], tp, why)) {
+                err = "utterance " + std::to_string(b) + ": " + why;
+                return -1;
+            }
+            if (tp.n_out > (int64_t)INT32_MAX - 64) {
+                err = "utterance " + std::to_string(b) + " has " + std::to_string(tp.n_out) + " samples at its tempo: too long";
+                return -1;
+            }
+            c.tem_len[(size_t)b] = (int)tp.n_out;
+            c.tem_max = std::max(c.tem_max, c.tem_len[(size_t)b]);
+            most = std::max(most, tp.F);
+            const int64_t row[4] = {tp.Q, c.slen[n_up][b], tp.n_out, tp.F};
+            std::copy_n(row, 4, c.tem_rows.begin() + (size_t)4 * b);
+        }
+        c.tem_starts = most + 1;
+    }
     if (c.pitched()) {
         // a stated pitch: N' of every row is host arithmetic, like everything else here; so are the rows of the report
         c.pit_len.resize((size_t)B);
@@ -404,7 +513,7 @@ int Engine::plan_rows(Call& c) {
         for (int b = 0; b < B; ++b) {
             PitchPlan pp;
             std::string why;
-            if (!pitch_plan(c.pitch[b], c.slen[n_up][b], pp, why)) {
+            if (!pitch_plan(c.pitch[b], c.stretched_len()[(size_t)b], pp, why)) {
                 err = "utterance " + std::to_string(b) + ": " + why;
                 return -1;
             }
@@ -414,7 +523,7 @@ int Engine::plan_rows(Call& c) {
                 return -1;
             }
             c.pit_max = std::max(c.pit_max, c.pit_len[(size_t)b]);
-            const int64_t row[4] = {pp.P, c.slen[n_up][b], pp.n_out, pp.K};
+            const int64_t row[4] = {pp.P, c.stretched_len()[(size_t)b], pp.n_out, pp.K};
             std::copy_n(row, 4, c.pit_rows.begin() + (size_t)4 * b);
         }
     }
@@ -481,7 +590,7 @@ int Engine::plan_rows(Call& c) {
 // or with it off every stage behind it, reads its rows' lengths from). One launch serves every ratio of the batch; rows with ratio 1 are copied.
 int Engine::run_pitch(Call& c) {
     std::string& err = c.err;
-    const int B = c.B, n_up = c.n_up;
+    const int B = c.B;
     const Call::Rows src = c.rows_of(c.dp.pitch.src), dst = c.rows_of(c.dp.pitch.dst);
     if (!pitch_table_ && !(pitch_table_ = upload(pitch_table_pairs()))) {  // (owned by the handle and counted in weight_bytes from here on)
         err = "pitch table: device allocation failed";
@@ -494,7 +603,7 @@ int Engine::run_pitch(Call& c) {
     PitchCall pc;
     pc.x = src.p;
     pc.x_stride = src.stride;
-    pc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    pc.lens = c.stretched_lens();  // (the vocoder's sample counts, or behind a tempo stage what its search wrote)
     pc.ratios = c.s2.pitch_ratios;
     pc.y = dst.p;
     pc.y_stride = dst.stride;
@@ -510,6 +619,47 @@ int Engine::run_pitch(Call& c) {
     }
     // K fused multiply-adds a sample and the tap's own; every row read once and written once
     PROF_LAUNCH("pitch", 4.0 * taps, 4.0 * (in_s + out_s), launch_pitch(pc, stream));
+    prof.fence();
+    return 0;
+}
+
+// ---- the tempo stage of a conversion: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.tempo_lens: what the pitch
+// stage, or with it off every stage behind it, reads its rows' lengths from). Two launches serve every tempo of the batch: the search (one block per row, its
+// segments a chain) and the overlap-add; rows with tempo 1 are copied.
+int Engine::run_tempo(Call& c) {
+    std::string& err = c.err;
+    const int B = c.B, n_up = c.n_up;
+    const Call::Rows src = c.rows_of(c.dp.tempo.src), dst = c.rows_of(c.dp.tempo.dst);
+    HIP_OK(tempo_host_.ensure((size_t)B, (size_t)B + 64));
+    std::copy_n(c.tempo, B, tempo_host_.p);
+    HIP_OK(hipMemcpyAsync(c.s2.tempo_q, tempo_host_.p, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream));
+    prof.fence();
+    TempoCall tc;
+    tc.x = src.p;
+    tc.x_stride = src.stride;
+    tc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    tc.tempos = c.s2.tempo_q;
+    tc.rate = hp.sampling_rate;
+    tc.starts = c.s2.tempo_starts;
+    tc.starts_stride = c.tem_starts;
+    tc.y = dst.p;
+    tc.y_stride = dst.stride;
+    tc.lens_out = c.s2.tempo_lens;
+    tc.batch = B;
+    tc.max_out = c.tem_max;
+    double diffs = 0, out_s = 0, steps = 0;
+    TempoPlan tp;
+    std::string ignored;
+    tempo_plan(hp.sampling_rate, 1.f, 0, tp, ignored);  // (H and D: resolve_conversion_prosody accepted the rate)
+    for (int b = 0; b < B; ++b) {
+        const int64_t* row = c.tem_rows.data() + (size_t)4 * b;
+        out_s += (double)row[2];
+        if (row[0] != kTempoOne) steps += (double)row[3], diffs += (double)row[3] * (2.0 * tp.D + 1.0) * tp.H;
+    }
+    // an absolute difference and an add per candidate sample; a window of samples read per step, the starts written
+    PROF_LAUNCH("tempo_search", 2.0 * diffs, 4.0 * steps * (2.0 * tp.D + 2.0 * tp.H) + 4.0 * steps, launch_tempo_search(tc, stream));
+    // two products and an add a sample; two samples read and one written
+    PROF_LAUNCH("tempo_ola", 3.0 * out_s, 12.0 * out_s, launch_tempo_ola(tc, stream));
     prof.fence();
     return 0;
 }
@@ -581,6 +731,10 @@ int Engine::run_delivery_tail(Call& c, const std::function<int()>& last_chunks) 
     // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
     std::vector<int> tap_len = c.head_len(), tap_out_len = c.out_len;
     int tap_max = c.head_max(), tap_out_max = c.out_max;
+    if (dp.tempo.runs) {
+        if (run_tempo(c)) return -1;
+        if (o.collect_taps) tap("waveform_tempo", dp.tempo.after, c.tem_max, c.tem_len);
+    }
     if (dp.pitch.runs) {
         if (run_pitch(c)) return -1;
         if (o.collect_taps) tap("waveform_pitch", dp.pitch.after, tap_max, tap_len);

@@ -39,8 +39,10 @@ int Engine::layout_stage_two(Call& c) {
     const int R = c.rows;
     const int J_stride = c.J_stride = c.join ? round_up(std::max(c.mr_max, 1), 32) : 0;
     // a stated pitch: the rows behind the stage, at the bound of N' at the smallest ratio; with the edges stage off a levelled buffer follows them (delivery_plan.cpp)
-    const int P_stride = c.P_stride = c.pitched() ? 2 * S_stride : 0;
-    const int L_stride = c.join ? J_stride : (c.dp[STAGE_EDGES].runs || !c.pitched() ? E_stride : P_stride);
+    // (a stated tempo in front of it: its rows hold up to 2 S_stride samples, and the pitch stage's twice that)
+    const int T_stride = c.T_stride = c.tempoed() ? 2 * S_stride : 0;
+    const int P_stride = c.P_stride = c.pitched() ? 2 * (c.tempoed() ? T_stride : S_stride) : 0;
+    const int L_stride = c.join ? J_stride : (c.dp[STAGE_EDGES].runs ? E_stride : (c.pitched() ? P_stride : (c.tempoed() ? T_stride : E_stride)));
     // VITS_ARITH_F32_SPLIT: three bf16 planes per conv input of the wide stages' resblocks (conv_split.hip): the stage input once, t and the stream per
     // concurrently running resblock
     size_t sp_elems = 0;
@@ -90,6 +92,10 @@ int Engine::layout_stage_two(Call& c) {
         s2.wave_pitch = dp.need(NEED_WAVE_PITCH) ? a.alloc<float>((size_t)B * P_stride) : nullptr;
         s2.pitch_ratios = dp.pitch.runs ? a.alloc<float>((size_t)B) : nullptr;
         s2.pitch_lens = dp.pitch.runs ? a.alloc<int>((size_t)B) : nullptr;
+        s2.wave_tempo = dp.need(NEED_WAVE_TEMPO) ? a.alloc<float>((size_t)B * T_stride) : nullptr;
+        s2.tempo_q = dp.tempo.runs ? a.alloc<float>((size_t)B) : nullptr;
+        s2.tempo_lens = dp.tempo.runs ? a.alloc<int>((size_t)B) : nullptr;
+        s2.tempo_starts = dp.tempo.runs ? a.alloc<int>((size_t)B * (size_t)c.tem_starts) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

@@ -241,6 +241,10 @@ struct Call {
         float* wave_pitch;     // a stated pitch, unless the stage writes straight to out_device: the varispeed rows [B][P_stride]
         float* pitch_ratios;   // a stated pitch: the ratios [B]
         int* pitch_lens;       // ... and N' of every row [B], written by the stage
+        float* wave_tempo;     // a stated tempo, unless the stage writes straight to out_device: the stretched rows [B][T_stride]
+        float* tempo_q;        // a stated tempo: the tempos [B]
+        int* tempo_lens;       // ... N' of every row [B], written by the search
+        int* tempo_starts;     // ... and the segment starts [B][tem_starts]: written by the search, read by the overlap-add
     } s2{};
     // Ragged batches, exact fp32 vocoder: the lists of existing tiles (tile_map.h) of the large launches whose dense grid would hold empty blocks. One list per
     // (window, length vector, tile width): length vector i = the lengths at vocoder stage i (conv_pre, the stage's resblocks), convt = upsampler i (columns
@@ -275,6 +279,7 @@ struct Call {
             case BUF_CALLER: out.p = (float*)o.out_device; break;
             case BUF_JOIN: out.p = s2.wave_join; break;
             case BUF_PITCH: out.p = s2.wave_pitch; break;
+            case BUF_TEMPO: out.p = s2.wave_tempo; break;
             default: break;
         }
         switch (r.stride) {
@@ -284,6 +289,7 @@ struct Call {
             case STRIDE_CALLER: out.stride = o.out_device_stride; break;
             case STRIDE_J: out.stride = J_stride; break;
             case STRIDE_P: out.stride = P_stride; break;
+            case STRIDE_T: out.stride = T_stride; break;
             default: break;
         }
         return out;
@@ -317,9 +323,22 @@ struct Call {
     PinnedBuf<float>* pitch_pin = nullptr;
     const float* pitch = nullptr;
     bool pitched() const { return pitch != nullptr; }
-    const int* head_lens() const { return pitched() ? s2.pitch_lens : s1.stage_lens + (size_t)n_up * B; }
-    const std::vector<int>& head_len() const { return pitched() ? pit_len : slen[n_up]; }
-    int head_max() const { return pitched() ? pit_max : smax[n_up]; }
+    // A stated tempo (tempo: the call's resolved tempos [B], Engine::resolve_conversion_prosody; null: the stage is off): the time stretch (tempo.hip) runs between
+    // the vocoder and the pitch stage, which then reads ITS rows: tem_len / tem_max = N' of every row, host arithmetic from the frame counts (Engine::plan_rows);
+    // T_stride = 2 S_stride, the stage's row stride (and P_stride = 2 T_stride behind it); tem_rows = the report [B][4] = {Q, N, N', F}; tem_starts = the
+    // longest row's F + 1, the row stride of s2.tempo_starts. stretched_* = what the pitch stage reads: the tempo stage's rows, else the vocoder's.
+    std::vector<int> tem_len;
+    std::vector<int64_t> tem_rows;
+    int tem_max = 0, T_stride = 0;
+    int64_t tem_starts = 0;
+    const float* tempo = nullptr;
+    bool tempoed() const { return tempo != nullptr; }
+    const int* stretched_lens() const { return tempoed() ? s2.tempo_lens : s1.stage_lens + (size_t)n_up * B; }
+    const std::vector<int>& stretched_len() const { return tempoed() ? tem_len : slen[n_up]; }
+    int stretched_max() const { return tempoed() ? tem_max : smax[n_up]; }
+    const int* head_lens() const { return pitched() ? s2.pitch_lens : stretched_lens(); }
+    const std::vector<int>& head_len() const { return pitched() ? pit_len : stretched_len(); }
+    int head_max() const { return pitched() ? pit_max : stretched_max(); }
     const int* utt_lens = nullptr;
     bool rows_planned = false;
 

@@ -942,6 +942,46 @@ struct PitchCall {
 };
 hipError_t launch_pitch(const PitchCall& c, hipStream_t s);
 
+// ---- a stated tempo: pitch-preserving time stretch by a tempo per row (tempo.hip; the definition: include/vits.h "a stated tempo", DESIGN.md §8 "A stated tempo") ----
+// Waveform-similarity overlap-add with every decision in integers. Row b of N samples at the rate sr is played q_b times faster: Q = q 2^24, N' = ceil(N 2^24 / Q),
+// hop and cross-fade H = 4 floor(sr / 400), search radius D = 4 floor(sr / 500), F = ceil(N' / H) segments. Segment k starts at s_k = a_k + delta_k, a_k =
+// (k H Q) >> 24, where delta_k in [-D, D] is the first minimum, in the order 0, -1, +1, -2, ..., of the sum of absolute differences between the 16-bit
+// quantised row at s_(k-1) + H (where the segment before would go on) and at a_k + delta. y[k H + i] = v[i] x[s_(k-1) + H + i] + w[i] x[s_k + i], two rounded
+// products and one rounded add, w[i] = (2 i + 1) / (2 H), v[i] = w[H - 1 - i]; a row with Q = 2^24 is copied bit for bit.
+constexpr int64_t kTempoOne = (int64_t)1 << 24;
+constexpr float kTempoMin = 0.5f, kTempoMax = 2.0f;
+constexpr int kTempoMinRate = 8000, kTempoMaxRate = 48000;
+constexpr int64_t kTempoMaxLen = (int64_t)1 << 30;
+constexpr int kTempoMaxH = 4 * (kTempoMaxRate / 400), kTempoMaxD = 4 * (kTempoMaxRate / 500);  // 480, 384
+struct TempoPlan {
+    int H = 0, D = 0;
+    int64_t Q = kTempoOne;
+    int64_t F = 0, n_out = 0;
+};
+// host only (tempo_host.cpp). false + a message: a rate outside [8000, 48000], a tempo that is not finite or outside [0.5, 2], n outside [0, 2^30]
+bool tempo_plan(int rate, float tempo, int64_t n, TempoPlan& p, std::string& err);
+// the definition, sequentially: y gets p.n_out samples, offsets (optional) delta_k for k = 1 ... F
+void tempo_host(const float* x, int64_t n, const TempoPlan& p, float* y, int32_t* offsets);
+constexpr int kTempoTile = 1024;  // output samples per block of the overlap-add
+struct TempoCall {
+    const float* x = nullptr;  // device [batch][x_stride]
+    int64_t x_stride = 0;
+    const int* lens = nullptr;      // device [batch]: valid input samples of each row (<= x_stride); nothing behind them is read
+    const float* tempos = nullptr;  // device [batch]: q_b, each in [0.5, 2] (the host's check; the kernels clamp, so that no index depends on it)
+    int rate = 0;                   // sr, in [8000, 48000]
+    int* starts = nullptr;          // device [batch][starts_stride]: s_0 ... s_F of each row, written by the search and read by the overlap-add
+    int64_t starts_stride = 0;      // >= the largest F + 1
+    int* offsets = nullptr;         // device [batch][offsets_stride], optional: delta_1 ... delta_F of each row
+    int64_t offsets_stride = 0;
+    float* y = nullptr;  // device [batch][y_stride], not x; samples behind N' are left as they are
+    int64_t y_stride = 0;
+    int* lens_out = nullptr;  // device [batch], optional: N' of each row
+    int batch = 0;
+    int64_t max_out = 0;  // the longest output row of the call (host side: sizes the grid); y_stride >= max_out
+};
+hipError_t launch_tempo_search(const TempoCall& c, hipStream_t s);
+hipError_t launch_tempo_ola(const TempoCall& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
