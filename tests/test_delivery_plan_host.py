@@ -28,7 +28,7 @@ def build(target):
 
 
 def test_plan_table_is_the_recorded_one():
-    out = subprocess.run([build("delivery_plan_dump")], check=True, capture_output=True).stdout
+    out = subprocess.run([build("delivery_plan_dump"), "base"], check=True, capture_output=True).stdout
     want = open(GOLDEN, "rb").read()
     if out != want:
         a, b = out.decode().splitlines(), want.decode().splitlines()
@@ -37,7 +37,7 @@ def test_plan_table_is_the_recorded_one():
                              % (len(a), len(b), "\n".join("%d: %s\n   %s" % d for d in diff)))
     # the same program under the sanitizers: same output, clean exit
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
-    got = subprocess.run([build("_asan/delivery_plan_dump")], capture_output=True, env=env)
+    got = subprocess.run([build("_asan/delivery_plan_dump"), "base"], capture_output=True, env=env)
     assert got.returncode == 0, got.stderr[-2000:]
     assert got.stdout == want
 

@@ -1,7 +1,7 @@
 """The joined half of the delivery planner (vits.cpp_amd/csrc/delivery_plan.cpp with DeliveryAsk::joined: where the join of vits_model_process_joined sits in
 the chain, what it reads and writes, what the level and the resampler behind it then work on) against its frozen table, on the CPU.
 
-tests/joined_plan_dump.cpp links delivery_plan.o ALONE, walks every combination of the ask with joined = true and prints one line per case; the output must
+tests/delivery_plan_dump.cpp (its slice `joined`) links delivery_plan.o ALONE, walks every combination of the ask with joined = true and prints one line per case; the output must
 equal tests/golden/joined_plan_table.txt byte for byte. The table was recorded once and read line by line against the rules the second test states; the
 test never regenerates it. The unjoined half is tests/test_delivery_plan_host.py's, whose table this change leaves as it was. The dump also runs as a
 stand-alone program under AddressSanitizer + UBSan."""
@@ -24,7 +24,7 @@ def build(target):
 
 
 def test_joined_plan_table_is_the_recorded_one():
-    out = subprocess.run([build("joined_plan_dump")], check=True, capture_output=True).stdout
+    out = subprocess.run([build("delivery_plan_dump"), "joined"], check=True, capture_output=True).stdout
     want = open(GOLDEN, "rb").read()
     if out != want:
         a, b = out.decode().splitlines(), want.decode().splitlines()
@@ -32,7 +32,7 @@ def test_joined_plan_table_is_the_recorded_one():
         raise AssertionError("joined_plan_dump differs from the golden table (%d lines against %d); first differing lines (got, want):\n%s"
                              % (len(a), len(b), "\n".join("%d: %s\n   %s" % d for d in diff)))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
-    got = subprocess.run([build("_asan/joined_plan_dump")], capture_output=True, env=env)
+    got = subprocess.run([build("_asan/delivery_plan_dump"), "joined"], capture_output=True, env=env)
     assert got.returncode == 0, got.stderr[-2000:]
     assert got.stdout == want
 

@@ -2,7 +2,7 @@
 vits_pitch_host — against the float64 numpy restatement (tests/pitch_ref.py); what the definition does to sinusoids and how far its table lies from the
 exact sinc, measured on the restatement; and the pitch half of the delivery planner against its frozen table.
 
-tests/pitch_plan_dump.cpp links delivery_plan.o ALONE, walks every combination of the ask with pitch = true, joined or not, and prints one line per case; the
+tests/delivery_plan_dump.cpp (its slice `pitch`) links delivery_plan.o ALONE, walks every combination of the ask with pitch = true, joined or not, and prints one line per case; the
 output must equal tests/golden/pitch_plan_table.txt byte for byte. The table was recorded once and is read line by line against the rules the last test
 states; the test never regenerates it. The tables of the asks without pitch are tests/test_delivery_plan_host.py's and tests/test_joined_plan_host.py's,
 which this stage leaves as they were."""
@@ -144,7 +144,7 @@ def build(target):
 
 
 def test_pitch_plan_table_is_the_recorded_one():
-    out = subprocess.run([build("pitch_plan_dump")], check=True, capture_output=True).stdout
+    out = subprocess.run([build("delivery_plan_dump"), "pitch"], check=True, capture_output=True).stdout
     want = open(GOLDEN, "rb").read()
     if out != want:
         a, b = out.decode().splitlines(), want.decode().splitlines()
@@ -152,7 +152,7 @@ def test_pitch_plan_table_is_the_recorded_one():
         raise AssertionError("pitch_plan_dump differs from the golden table (%d lines against %d); first differing lines (got, want):\n%s"
                              % (len(a), len(b), "\n".join("%d: %s\n   %s" % d for d in diff)))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
-    got = subprocess.run([build("_asan/pitch_plan_dump")], capture_output=True, env=env)
+    got = subprocess.run([build("_asan/delivery_plan_dump"), "pitch"], capture_output=True, env=env)
     assert got.returncode == 0, got.stderr[-2000:]
     assert got.stdout == want
 

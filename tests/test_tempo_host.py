@@ -2,7 +2,7 @@
 restatement (tests/tempo_ref.py) bit for bit; what the definition does to harmonic tones, measured on the product's host evaluation; the tempo half of the
 delivery planner against its frozen table; and both host pieces as stand-alone programs under AddressSanitizer + UBSan.
 
-tests/tempo_plan_dump.cpp links delivery_plan.o ALONE, walks every combination of the ask with tempo = true, with pitch and without, and prints one line per
+tests/delivery_plan_dump.cpp (its slice `tempo`) links delivery_plan.o ALONE, walks every combination of the ask with tempo = true, with pitch and without, and prints one line per
 case; the output must equal tests/golden/tempo_plan_table.txt byte for byte. The table was recorded once and is read line by line against the rules the last
 test states; the test never regenerates it. The tables of the asks without tempo are tests/test_delivery_plan_host.py's, tests/test_joined_plan_host.py's and
 tests/test_pitch_host.py's, which this stage leaves as they were."""
@@ -123,7 +123,7 @@ def build(target):
 
 
 def test_tempo_plan_table_is_the_recorded_one():
-    out = subprocess.run([build("tempo_plan_dump")], check=True, capture_output=True).stdout
+    out = subprocess.run([build("delivery_plan_dump"), "tempo"], check=True, capture_output=True).stdout
     want = open(GOLDEN, "rb").read()
     if out != want:
         a, b = out.decode().splitlines(), want.decode().splitlines()
@@ -131,7 +131,7 @@ def test_tempo_plan_table_is_the_recorded_one():
         raise AssertionError("tempo_plan_dump differs from the golden table (%d lines against %d); first differing lines (got, want):\n%s"
                              % (len(a), len(b), "\n".join("%d: %s\n   %s" % d for d in diff)))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
-    got = subprocess.run([build("_asan/tempo_plan_dump")], capture_output=True, env=env)
+    got = subprocess.run([build("_asan/delivery_plan_dump"), "tempo"], capture_output=True, env=env)
     assert got.returncode == 0, got.stderr[-2000:]
     assert got.stdout == want
 

@@ -25,19 +25,18 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     // call has one. The model-rate rows behind the edges stage are E_stride apart; with the stage off they keep the stride of what is in front of it: the
     // pitch stage's, else the tempo stage's, else the vocoder's. Behind a join they are the tracks', J_stride apart. The row bounds, once: a tempo stage's rows
     // hold at most 2 S_stride samples (T_stride), a pitch stage's at most twice what lies in front of it (P_stride: 2 S_stride, or 2 T_stride behind a tempo stage).
-    constexpr int kSlots = STAGE_COUNT + 3;  // vocoder, tempo, pitch, edges, join, level, resample
-    DeliveryPlan::Stage* const slot[kSlots] = {&p.stage[STAGE_VOCODER], &p.tempo, &p.pitch, &p.stage[STAGE_EDGES], &p.join, &p.stage[STAGE_LEVEL], &p.stage[STAGE_RESAMPLE]};
-    const bool writes[kSlots] = {true, a.tempo, a.pitch, a.edges, a.joined, multiplies, a.rate};
-    const int own[kSlots] = {BUF_WAVE, BUF_TEMPO, BUF_PITCH, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
+    // in the order of DeliveryStage: vocoder, tempo, pitch, edges, join, level, resample
+    const bool writes[STAGE_COUNT] = {true, a.tempo, a.pitch, a.edges, a.joined, multiplies, a.rate};
+    const int own[STAGE_COUNT] = {BUF_WAVE, BUF_TEMPO, BUF_PITCH, BUF_EDGE, BUF_JOIN, BUF_LVL, BUF_OUT};
     const int head_stride = a.pitch ? STRIDE_P : (a.tempo ? STRIDE_T : STRIDE_S);
-    const int own_stride[kSlots] = {STRIDE_S, STRIDE_T, STRIDE_P, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : head_stride), STRIDE_OUT_WS};
+    const int own_stride[STAGE_COUNT] = {STRIDE_S, STRIDE_T, STRIDE_P, STRIDE_E, STRIDE_J, a.joined ? STRIDE_J : (a.edges ? STRIDE_E : head_stride), STRIDE_OUT_WS};
     int last = 0;
-    for (int s = 0; s < kSlots; ++s)
+    for (int s = 0; s < STAGE_COUNT; ++s)
         if (writes[s]) last = s;
     DeliveryRoute cur;  // what the next stage reads
-    for (int s = 0; s < kSlots; ++s) {
-        DeliveryPlan::Stage& st = *slot[s];
-        if (slot[s] == &p.stage[STAGE_LEVEL] && a.level == DLEVEL_MEASURE) {
+    for (int s = 0; s < STAGE_COUNT; ++s) {
+        DeliveryPlan::Stage& st = p.stage[s];
+        if (s == STAGE_LEVEL && a.level == DLEVEL_MEASURE) {
             // measured where it lies (out_device included): the chain passes by
             st.runs = true;
             st.src = st.after = cur;
@@ -52,8 +51,8 @@ DeliveryPlan delivery_plan(const DeliveryAsk& a) {
     }
     p.delivered = cur;
 
-    for (const DeliveryPlan::Stage* st : slot)
-        for (const int buf : {st->src.buf, st->dst.buf}) {
+    for (const DeliveryPlan::Stage& st : p.stage)
+        for (const int buf : {st.src.buf, st.dst.buf}) {
             if (buf == BUF_EDGE) p.needs |= NEED_WAVE_EDGE;
             if (buf == BUF_LVL) p.needs |= NEED_WAVE_LVL;
             if (buf == BUF_OUT) p.needs |= NEED_WAVE_OUT;

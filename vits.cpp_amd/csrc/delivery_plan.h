@@ -1,8 +1,10 @@
 // delivery_plan.h — how a call's PCM travels from the vocoder to what is handed out (host only, like launch_plan.h and tile_map.h: no kernel, no device).
 // The stages behind the vocoder — a stated tempo (tempo.hip), a stated pitch (pitch.hip), stated edges (edges.hip), level or limiter (loudness.hip, limiter.hip), output rate (resample.hip) — each read what the
 // stage in front of them wrote. delivery_plan() states that chain ONCE, from what the handle and the call ask for: who runs, which buffer each stage reads
-// and writes, which buffer is delivered, which arena buffers the call therefore needs, or why the combination is refused. The engine allocates from the
-// plan (layout_stage_two) and resolves its buffer ids to pointers in one place (Call::rows_of); tests/golden/delivery_plan_table.txt pins the whole table.
+// and writes, which buffer is delivered, which arena buffers the call therefore needs, or why the combination is refused. The plan is ONE array in chain order,
+// DeliveryPlan::stage[STAGE_COUNT]; the engine keeps what it knows of the rows behind every stage in an array of the same order (Call::behind), allocates from
+// the plan (layout_stage_two) and resolves its buffer and stride ids to pointers and numbers in one place (Call::rows_of). tests/delivery_plan_dump.cpp prints
+// the plan of every ask; the four tables tests/golden/{delivery,joined,pitch,tempo}_plan_table.txt pin it.
 #pragma once
 
 namespace vits {
@@ -87,7 +89,9 @@ struct DeliveryRoute {
     bool operator==(const DeliveryRoute& o) const { return buf == o.buf && stride == o.stride; }
 };
 
-enum DeliveryStage : int { STAGE_VOCODER = 0, STAGE_EDGES, STAGE_LEVEL, STAGE_RESAMPLE, STAGE_COUNT };
+// the stages in chain order: each reads what the last stage in front of it that wrote left behind. The join (a joined ask only), the pitch stage (an ask with
+// pitch only) and the tempo stage (an ask with tempo only) always write when they run; off, they leave the plan of every other ask what it always was.
+enum DeliveryStage : int { STAGE_VOCODER = 0, STAGE_TEMPO, STAGE_PITCH, STAGE_EDGES, STAGE_JOIN, STAGE_LEVEL, STAGE_RESAMPLE, STAGE_COUNT };
 
 struct DeliveryPlan {
     int refusal = DELIVER_OK;  // not DELIVER_OK: nothing else is set
@@ -96,15 +100,6 @@ struct DeliveryPlan {
         DeliveryRoute src, dst;
         DeliveryRoute after;  // what the chain holds behind this stage: its dst, or (a stage that only reads) its src
     } stage[STAGE_COUNT];
-    // a joined ask: the join, between stage[STAGE_EDGES] and stage[STAGE_LEVEL]. It always writes (one row per track); the level and the resampler behind it
-    // read and write G rows, and a levelled buffer follows its input's stride (STRIDE_J). Off for every other ask, whose plan is what it always was.
-    Stage join;
-    // an ask with pitch: the varispeed (pitch.hip), between stage[STAGE_VOCODER] and stage[STAGE_EDGES]. It always writes (rows P_stride apart); with the edges
-    // stage off, a levelled buffer behind it follows its stride (STRIDE_P). Off for every other ask, whose plan is what it always was.
-    Stage pitch;
-    // an ask with tempo: the time stretch (tempo.hip), between stage[STAGE_VOCODER] and the pitch stage. It always writes (rows T_stride apart); what follows it
-    // keeps that stride as it would the vocoder's. Off for every other ask, whose plan is what it always was.
-    Stage tempo;
     bool multiplies = false;  // the level stage writes (a plain multiply, or the limiter)
     bool limits = false;      // ... through the limiter
     DeliveryRoute delivered;  // what the call hands out: the destination of the last stage that writes

@@ -438,8 +438,8 @@ int Engine::frames_only_result(Call& c, vits_batch_result* out) {
     if (out && join) {
         // per track: the bound a full call stays within, at the rate it would deliver at, and the frames of the track's utterances
         if (plan_rows(c)) return -1;
-        const std::vector<int>& len = output_rate_ ? c.out_len : c.mr_len;
-        fill_result(out, join->tracks, (size_t)(output_rate_ ? c.out_max : c.mr_max), len.begin(), c.track_frames().begin());
+        const Call::RowSet& pcm = c.behind[STAGE_RESAMPLE];
+        fill_result(out, join->tracks, (size_t)pcm.max, pcm.len.begin(), c.track_frames().begin());
     } else if (out) {
         // (samples at the rate the full call would deliver them at; no table is needed for that, and none is uploaded)
         ResamplePlan plan;
@@ -449,8 +449,10 @@ int Engine::frames_only_result(Call& c, vits_batch_result* out) {
         std::vector<int64_t> lengths(B);
         // (a stated pitch: N' of every utterance in place of the vocoder's sample count)
         if (c.pitched() && plan_rows(c)) return -1;
-        for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(c.head_len()[(size_t)b] + pads);
-        fill_result(out, B, (size_t)plan.out_len(c.head_max() + pads), lengths.begin(), frames.begin());
+        const std::vector<int>& len = c.pitched() ? c.behind[STAGE_PITCH].len : c.slen[c.n_up];
+        const int longest = c.pitched() ? c.behind[STAGE_PITCH].max : c.smax[c.n_up];
+        for (int b = 0; b < B; ++b) lengths[b] = plan.out_len(len[(size_t)b] + pads);
+        fill_result(out, B, (size_t)plan.out_len(longest + pads), lengths.begin(), frames.begin());
     }
     HIP_OK(hipStreamSynchronize(stream));
     prof.fence();
@@ -723,15 +725,15 @@ struct Engine::ChunkStream {
 
     int setup() {
         std::string& err = c.err;
-        const int B = c.B, n_up = c.n_up;
+        const int B = c.B;
         pcm = c.rows_of(c.dp.delivered);
-        out_stride = (size_t)(rs ? c.out_max : c.mr_max);
+        out_stride = (size_t)c.behind[STAGE_RESAMPLE].max;
         const size_t need = (size_t)B * out_stride * sizeof(float);
         HIP_OK(e.pinned_.ensure(need, need));
         host_pcm = (float*)e.pinned_.p;
         if (rs) {
             rsc = e.resample_out_call(c);
-            if (e.upload_ranges(c, rg, c.s2.out_ranges, [&](int b, int64_t x) { return (int)c.rate_out->plan.final_prefix(x, c.slen[n_up][b]); })) return -1;
+            if (e.upload_ranges(c, rg, c.s2.out_ranges, [&](int b, int64_t x) { return (int)c.rate_out->plan.final_prefix(x, c.behind[STAGE_RESAMPLE - 1].len[(size_t)b]); })) return -1;
         }
         if (la) {
             if (e.upload_ranges(c, lrg, c.s2.lvl_ranges, [](int, int64_t x) { return (int)x; })) return -1;
@@ -740,7 +742,7 @@ struct Engine::ChunkStream {
             lsc.x_stride = x.stride;
             lsc.y = y.p;
             lsc.y_stride = y.stride;
-            lsc.lens = c.s1.stage_lens + (size_t)n_up * B;
+            lsc.lens = c.behind[STAGE_LEVEL - 1].dev;
             lsc.gain = e.level_gain();
             lsc.batch = B;
         }
@@ -867,8 +869,7 @@ void Engine::window_ctx(const Call& c, size_t wi, WinCtx& w) const {
     w.zwin = make_ref(c.s2.zp, hp.flow_size, c.ls);
     w.zwin.p += w.wn.lo;
     w.pre.p = c.s2.pre;
-    w.pre.bs = c.S_stride;
-    w.pre.cs = c.S_stride;
+    w.pre.bs = w.pre.cs = c.behind[STAGE_VOCODER].stride;
     w.wv.p = wave.p + (int64_t)w.wn.lo * win.M;  // window-local sample 0 is global sample lo * M
     w.wv.bs = wave.stride;
     w.wv.cs = (int)wave.stride;
@@ -910,18 +911,17 @@ int Engine::run_stage_two(Call& c, vits_batch_result* out, Pending* pend, bool w
 
     // ---- HiFiGAN (vits.cpp:583-644), window by window ---------------------------------------------------------------
     c.rx.phase("vits.hifigan");
-    // the device lengths [B] of the model-rate rows, for every stage behind the vocoder: its sample counts, or what the edges stage will write behind its rows
-    c.mr_lens = c.head_lens();
     c.pitch_pin = pend ? &pend->pitch_pinned : &pitch_host_;
-    if (dp[STAGE_EDGES].runs) {
-        HIP_OK(ed_.grow(B, owned_, weight_bytes));
-        c.mr_lens = edges_lens();
-    }
-    if (c.join) {
-        // behind the join the rows are the tracks: their lengths T_g lie behind the {o_b, n_b} rows of the joins' report
-        HIP_OK(jn_.grow(B, owned_, weight_bytes));
-        c.utt_lens = c.mr_lens;
-        c.mr_lens = track_lens(B);
+    // the device lengths of the rows behind every stage (Call::behind): what the stage writes, else what lies in front of it. The vocoder's sample counts, N' of
+    // the tempo and the pitch stage in the arena, the trimmed lengths behind the edges' rows, the track lengths T_g behind the {o_b, n_b} rows of the joins' report
+    if (dp[STAGE_EDGES].runs) HIP_OK(ed_.grow(B, owned_, weight_bytes));
+    if (dp[STAGE_JOIN].runs) HIP_OK(jn_.grow(B, owned_, weight_bytes));
+    const int* const own_lens[STAGE_COUNT] = {c.s1.stage_lens + (size_t)n_up * B, c.s2.tempo_lens, c.s2.pitch_lens, dp[STAGE_EDGES].runs ? edges_lens() : nullptr,
+                                              dp[STAGE_JOIN].runs ? track_lens(B) : nullptr, nullptr, nullptr};
+    const int* lens = nullptr;
+    for (int s = 0; s < STAGE_RESAMPLE; ++s) {
+        if (own_lens[s]) lens = own_lens[s];
+        c.behind[s].dev = lens;
     }
     ChunkStream chunks(*this, c);
     if (o.on_chunk && chunks.setup()) return -1;
@@ -952,10 +952,10 @@ int Engine::hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_
     const bool rs = dp[STAGE_RESAMPLE].runs;
     // what the call delivers: the vocoder's waveform, or (output rate set) the resampler's
     // (stated edges: the bounds; the lengths proper are read from the stage's rows below)
-    const std::vector<int>& pcm_len = rs ? c.out_len : c.mr_len;
-    const int pcm_max = rs ? c.out_max : c.mr_max;
+    const std::vector<int>& pcm_len = c.behind[STAGE_RESAMPLE].len;
+    const int pcm_max = c.behind[STAGE_RESAMPLE].max;
     const Call::Rows pcm = c.rows_of(dp.delivered);
-    const int B = c.B, R = c.rows;  // what the call hands out: one row per utterance, or per track
+    const int B = c.B, R = c.behind[STAGE_RESAMPLE].n;  // what the call hands out: one row per utterance, or per track
     const int lv_n = c.lev ? R : 0, lm_n = dp.limits ? R : 0, ed_n = dp[STAGE_EDGES].runs ? B : 0, jn_n = c.join ? B : 0;  // the rows of the reports this call fills
     if (pend) {
         // a pipelined batch: everything the host will hand out is known now; the PCM (if a host copy was asked for) goes to the

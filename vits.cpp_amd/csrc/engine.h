@@ -353,10 +353,20 @@ class Engine {
     // by the first call that shifts.
     float pitch_ratio = 1.f;
     int set_pitch(float ratio, std::string& err);
-    // the per-utterance ratios of the NEXT call (vits_model_set_pitch_ratios): copied here, taken by whichever entry point runs next (take_pitch_ratios: it
-    // uses them or refuses them; either way they are gone). NULL or n = 0 drops what was given. 0, or -1 + a message: n < 0, ratios NULL with n > 0
+    // A value given for the NEXT call alone (vits_model_set_pitch_ratios, the two arrays of vits_model_set_conversion_ratios): give() copies it, NULL or n = 0
+    // drops what was given; take() hands it to whichever entry point runs next, which uses it or refuses it: whatever becomes of that call, it is gone.
+    struct TakeOnce {
+        std::vector<float> v;
+        void give(const float* p, int n) { v.assign(p, p + (p && n > 0 ? n : 0)); }
+        bool take(std::vector<float>& out) {  // true: something had been given
+            out.clear();
+            out.swap(v);
+            return !out.empty();
+        }
+    };
+    // the per-utterance ratios of the next call. 0, or -1 + a message: n < 0, ratios NULL with n > 0
     int set_pitch_ratios(const float* ratios, int n, std::string& err);
-    bool take_pitch_ratios(std::vector<float>& given);
+    bool take_pitch_ratios(std::vector<float>& given) { return pitch_given_.take(given); }
     // A call's pitch. An entry point constructs it first of all: that takes the ratios given for this call, whatever becomes of the call. resolve_pitch then
     // decides: when some utterance's ratio is not 1, `pitch` points at `ratios` (the given ones, or the model value, per utterance) and o.speaking_rates at
     // `rates` (r'_b = (float)((double)rate_b / (double)p_b)); with every ratio 1, `pitch` stays NULL and `o` the caller's struct as it was.
@@ -378,8 +388,8 @@ class Engine {
     // set_conversion_prosody: 0, or -1 + a message with the handle unchanged (a value that is not finite or outside [0.5, 2]).
     float vc_rate = 1.f, vc_pitch = 1.f;
     int set_conversion_prosody(float rate, float pitch, std::string& err);
-    // the per-utterance pairs of the NEXT conversion (vits_model_set_conversion_ratios): copied here, taken by convert_batch alone (take_conversion_ratios:
-    // whatever becomes of the call they are gone). Either array may be NULL (the model value for every utterance); both NULL or n = 0 drops what was given.
+    // the per-utterance pairs of the NEXT conversion (vits_model_set_conversion_ratios): copied here, taken by convert_batch alone, which constructs a
+    // ResolvedConversion first of all. Either array may be NULL (the model value for every utterance); both NULL or n = 0 drops what was given.
     int set_conversion_ratios(const float* rates, const float* pitches, int n, std::string& err);
     struct ResolvedConversion {
         std::vector<float> rates, pitches;  // as given (empty: not given)
@@ -388,8 +398,12 @@ class Engine {
         std::vector<float> tempos, ratios;  // resolved: q_b and p_b [B]
         const float* tempo = nullptr;       // non-null: some q_b != 1, the tempo stage runs
         const float* pitch = nullptr;       // non-null: some p_b != 1, the pitch stage runs behind it
+        explicit ResolvedConversion(Engine& e) {
+            const bool r = e.vc_rates_given_.take(rates), p = e.vc_pitches_given_.take(pitches);
+            have = r || p;
+            n = (int)std::max(rates.size(), pitches.size());
+        }
     };
-    void take_conversion_ratios(ResolvedConversion& rc);
     // 0, or -1 + a message naming the utterance: another count of pairs than utterances; r, p or q not finite or outside [0.5, 2]; on_chunk with any r or p
     // other than 1; a model rate the stretch does not take
     int resolve_conversion_prosody(int B, const vits_process_opts& o, ResolvedConversion& rc, std::string& err) const;
@@ -620,9 +634,10 @@ class Engine {
     // the combination the plan refuses (on_chunk with a level that needs the whole utterance, with the limiter, with edges; async with edges). Called before
     // stage one is queued by every entry point that can be refused, and by run_stage_two, which keeps the plan in the call.
     int plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::string& err, bool joined = false) const;
-    // What the host knows of the rows a call delivers, from the frame counts alone (no device work): the call's plan, the model-rate bounds of every utterance
-    // (c.mr_len, with the edges' pads), the tracks' bounds of a joined call, the lengths at the output rate, and the refusals that follow from them — an
-    // utterance or track that is too long, an out_device_stride that cannot hold the longest row. Runs before anything is queued when the frame counts are
+    // What the host knows of the rows a call delivers, from the frame counts alone (no device work): the call's plan and the row set behind every stage of it
+    // (Call::behind: rows, lengths or bounds, the longest, the row stride — N' behind tempo and pitch, the edges' pads, the tracks' bounds of a joined call,
+    // the lengths at the output rate), and the refusals that follow from them — an utterance or track that is too long, an out_device_stride that cannot
+    // hold the longest row. Runs before anything is queued when the frame counts are
     // host arithmetic (fixed_duration > 0), else as the first thing of stage two, directly behind the frame-count synchronise. Once per call.
     int plan_rows(Call& c);
     // the report rows of the stages (ReportRows: device rows owned_ and counted in weight_bytes); the edges' carry the trimmed lengths int32 [cap] behind them.
@@ -634,7 +649,7 @@ class Engine {
     // ... and so are the tempo stage's (Q, N, N' and F follow from the tempo and the frame count)
     ReportRows<int64_t> tm_;
     // the device lengths behind those rows: the trimmed lengths [B] that run_edges writes, and the track lengths T_g [G] that run_join writes behind the
-    // joins' {o_b, n_b} rows of a call of B utterances (device rows, or a slot's landed copy). What Call::mr_lens points at when the stage runs
+    // joins' {o_b, n_b} rows of a call of B utterances (device rows, or a slot's landed copy). What Call::behind[STAGE_EDGES].dev and behind[STAGE_JOIN].dev are when the stage runs
     int* edges_lens() { return static_cast<int*>(ed_.tail()); }
     static const int* track_lens(const int64_t* join_rows, int B) { return reinterpret_cast<const int*>(join_rows + (size_t)2 * B); }
     int* track_lens(int B) { return const_cast<int*>(track_lens(jn_.dev(), B)); }
@@ -643,19 +658,18 @@ class Engine {
     // stage from its source into its destination, as the call's plan routes them: queued behind the last vocoder window, in front of run_edges
     float* pitch_table_ = nullptr;
     PinnedBuf<float> pitch_host_;
-    std::vector<float> pitch_given_;      // vits_model_set_pitch_ratios: the next call's ratios
-    bool pitch_given_set_ = false;
+    TakeOnce pitch_given_;                // vits_model_set_pitch_ratios: the next call's ratios
     const float* call_pitch_ = nullptr;   // the resolved ratios [B] of the call being queued (ResolvedPitch::pitch): non-null MEANS that the stage runs
     int run_pitch(Call& c);
     // a stated tempo: the next conversion's pairs, the resolved tempos [B] of the conversion being queued (non-null MEANS that the stage runs), their pinned
     // memory on the way to the device, and the stage (search, then overlap-add) from its source into its destination, as the call's plan routes them: queued
     // behind the last vocoder window, in front of run_pitch
-    std::vector<float> vc_rates_given_, vc_pitches_given_;
-    int vc_given_n_ = 0;
-    bool vc_given_set_ = false;
+    TakeOnce vc_rates_given_, vc_pitches_given_;
     const float* call_tempo_ = nullptr;
     PinnedBuf<float> tempo_host_;
     int run_tempo(Call& c);
+    // the ratios [B] of either stage through `pin` (pinned: it outlives the copy) to `dev`, queued in front of the stage's launches
+    int upload_ratios(const Call& c, const float* ratios, PinnedBuf<float>& pin, float* dev);
     PinnedBuf<int64_t> join_table_host_;  // a joined call's table (host side of its H2D copy)
     std::vector<int32_t> join_index_;     // ... and what its report names each utterance (process_joined: b, or the caller's index)
     // the join of a joined call (join.hip) from its source into its destination, as the call's plan routes them: queued behind the edges stage, in front of run_level
@@ -686,7 +700,7 @@ class Engine {
     // the rows of a batch that has completed in pipeline slot `slot` -> the three reports (append: a second part of the same call); the batch's lengths become
     // its trimmed ones when the edges stage ran
     void batch_landed(Pending& p, int slot, bool append = false);
-    // everything behind the last vocoder window (engine_delivery.cpp): pitch, edges, join, level or limiter, the resampler, their taps, and the chunks of the
+    // everything behind the last vocoder window (engine_delivery.cpp): the plan's stages in chain order (tempo, pitch, edges, join, level or limiter, the resampler), their taps, and the chunks of the
     // last window of a streaming call (last_chunks: null without a sink; -1 with the call's message set: the sink aborted, or the wait failed)
     int run_delivery_tail(Call& c, const std::function<int()>& last_chunks);
     ResampleCall resample_out_call(const Call& c) const;

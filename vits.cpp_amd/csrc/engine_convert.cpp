@@ -225,8 +225,7 @@ int Engine::layout_conversion(Call& c, const float* pcm, const int64_t* pcm_lens
 // ---- one conversion call -------------------------------------------------------------------------------------------------------
 int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_t pcm_stride, const int32_t* src, const int32_t* tgt, const vits_process_opts& o,
                           vits_batch_result* out, std::string& err) {
-    ResolvedConversion rc;  // (first of all: the pairs given for this conversion are taken, whatever becomes of it)
-    take_conversion_ratios(rc);
+    ResolvedConversion rc(*this);  // (first of all: the pairs given for this conversion are taken, whatever becomes of it)
     std::vector<float> given;
     if (take_pitch_ratios(given)) {
         err = "voice conversion does not take the ratios of vits_model_set_pitch_ratios (a pitch is paid for by the duration predictor's stretch, and a conversion "

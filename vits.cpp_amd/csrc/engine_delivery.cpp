@@ -1,6 +1,6 @@
 // engine_delivery.cpp — the delivery chain behind the vocoder (delivery_plan.h): the handle's settings (rates, level, limiter, edges, pitch, a conversion's rate
-// and pitch) and their plans, the call's routing plan and what the host knows of its rows, and the stages themselves: tempo, pitch, edges, join, level / limiter,
-// the output resampler.
+// and pitch) and their plans, the call's routing plan (dp[STAGE_X], one array in chain order) and what the host knows of the rows behind every stage of it
+// (Call::behind, filled by plan_rows: a stage reads behind[X - 1]), and the stages themselves: tempo, pitch, edges, join, level / limiter, the output resampler.
 // engine.cpp's run_stage_two calls run_delivery_tail behind the last vocoder window. Compiled with hipcc as host C++.
 #include <numeric>
 
@@ -25,17 +25,8 @@ int Engine::set_pitch_ratios(const float* ratios, int n, std::string& err) {
         err = "vits_model_set_pitch_ratios: " + std::string(n < 0 ? "n < 0" : "null argument (ratios is NULL with n > 0)");
         return -1;
     }
-    pitch_given_.assign(ratios, ratios + (ratios ? n : 0));
-    pitch_given_set_ = ratios && n > 0;
+    pitch_given_.give(ratios, n);
     return 0;
-}
-
-bool Engine::take_pitch_ratios(std::vector<float>& given) {
-    const bool was = pitch_given_set_;
-    given.clear();
-    given.swap(pitch_given_);
-    pitch_given_set_ = false;
-    return was;
 }
 
 int Engine::resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const {
@@ -104,21 +95,9 @@ int Engine::set_conversion_ratios(const float* rates, const float* pitches, int 
         err = "vits_model_set_conversion_ratios: n < 0";
         return -1;
     }
-    const bool any = n > 0 && (rates || pitches);
-    vc_rates_given_.assign(rates, rates + (any && rates ? n : 0));
-    vc_pitches_given_.assign(pitches, pitches + (any && pitches ? n : 0));
-    vc_given_n_ = any ? n : 0;
-    vc_given_set_ = any;
+    vc_rates_given_.give(rates, n);
+    vc_pitches_given_.give(pitches, n);
     return 0;
-}
-
-void Engine::take_conversion_ratios(ResolvedConversion& rc) {
-    rc.have = vc_given_set_;
-    rc.n = vc_given_n_;
-    rc.rates.clear(), rc.pitches.clear();
-    rc.rates.swap(vc_rates_given_);
-    rc.pitches.swap(vc_pitches_given_);
-    vc_given_set_ = false, vc_given_n_ = 0;
 }
 
 int Engine::resolve_conversion_prosody(int B, const vits_process_opts& o, ResolvedConversion& rc, std::string& err) const {
@@ -327,16 +306,17 @@ int Engine::plan_delivery(const vits_process_opts& o, DeliveryPlan& plan, std::s
 // streaming call has multiplied window by window already), and the rows on their way to the slot's pinned copy
 int Engine::run_level(Call& c) {
     std::string& err = c.err;
-    const int B = c.rows;  // (the rows behind the edges stage: the utterances, or a joined call's tracks)
+    const Call::RowSet& in = c.behind[STAGE_LEVEL - 1];  // (the rows the stage reads: the utterances, or a joined call's tracks)
+    const int B = in.n;
     const Call::Rows src = c.rows_of(c.dp[STAGE_LEVEL].src), dst = c.rows_of(c.dp[STAGE_LEVEL].dst);
     HIP_OK(lv_.grow(B, owned_, weight_bytes));
     const int64_t samples = c.wave_samples();
     LevelCall lc;
     lc.x = src.p;
     lc.x_stride = src.stride;
-    lc.lens = c.mr_lens;
+    lc.lens = in.dev;
     lc.batch = B;
-    lc.max_len = c.mr_max;
+    lc.max_len = in.max;
     lc.plan = level_plan_;
     lc.scratch = c.s2.lvl_scratch;
     lc.kind = c.lev;
@@ -358,7 +338,7 @@ int Engine::run_level(Call& c) {
         mc.y_stride = dst.stride;
         mc.lens = lc.lens;
         mc.batch = B;
-        mc.max_len = c.mr_max;
+        mc.max_len = in.max;
         mc.plan = limit_plan_;
         mc.taps = up->taps;
         mc.scratch = c.s2.lim_scratch;
@@ -380,7 +360,7 @@ int Engine::run_level(Call& c) {
         sc.lens = lc.lens;
         sc.levels = lv_.dev();
         sc.batch = B;
-        sc.max_range = c.mr_max;
+        sc.max_range = in.max;
         PROF_LAUNCH("level_scale", (double)samples, 8.0 * (double)samples, launch_level_scale(sc, stream));
     }
     HIP_OK(lv_.queue_copy(a1_slot_, B, stream));
@@ -408,7 +388,7 @@ int Engine::set_edges(const vits_edges_desc* d, std::string& err) {
 }
 
 // the edges stage of a call: the vocoder's waveform -> the stage's destination (the plan's: the call's own buffer, or out_device when nothing follows), the
-// trimmed lengths (c.mr_lens: what every stage behind this one reads its rows' lengths from) and the rows on the device, and the rows on their way to the
+// trimmed lengths (behind[STAGE_EDGES].dev: what every stage behind this one reads its rows' lengths from) and the rows on the device, and the rows on their way to the
 // slot's pinned copy
 int Engine::run_edges(Call& c) {
     std::string& err = c.err;
@@ -436,15 +416,15 @@ int Engine::run_edges(Call& c) {
     EdgesCall ec;
     ec.x = src.p;
     ec.x_stride = src.stride;
-    ec.lens = c.head_lens();
+    ec.lens = c.behind[STAGE_EDGES - 1].dev;
     ec.y = dst.p;
     ec.y_stride = dst.stride;
     ec.batch = B;
-    ec.max_len = c.head_max();
+    ec.max_len = c.behind[STAGE_EDGES - 1].max;
     ec.plan = p;
     ec.fades = ed_fades_;
     ec.scratch = c.s2.ed_scratch;
-    ec.lens_out = edges_lens();  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
+    ec.lens_out = edges_lens();  // (= behind[STAGE_EDGES].dev: run_stage_two set it when it grew the rows)
     ec.rows = ed_.dev();
     const int64_t samples = c.wave_samples();
     // one multiply-add per sample in fp64; the samples read once, one double per window written
@@ -474,6 +454,36 @@ int Engine::upload_ranges(Call& c, std::vector<int>& table, int* dev, const std:
     return 0;
 }
 
+// A stage whose N' is host arithmetic from a ratio and the row in front of it (tempo, pitch): plan(b, N, row, why) fills the row of the stage's report
+// [B][4] = {the ratio as the stage holds it, N, N', a count of the stage's own}, or says why not. Fills behind[stage] from behind[stage - 1] (its rows hold at
+// most twice theirs: the smallest ratio is 0.5) and the report; returns the largest count, or -1 with the call's message set.
+template <class Plan>
+static int64_t ratio_stage_rows(Call& c, int stage, const char* at_its, std::vector<int64_t>& report, Plan&& plan) {
+    const Call::RowSet& in = c.behind[stage - 1];
+    Call::RowSet& out = c.behind[stage];
+    out.max = 0;
+    out.stride = 2 * in.stride;
+    report.resize((size_t)4 * c.B);
+    int64_t most = 0;
+    for (int b = 0; b < c.B; ++b) {
+        int64_t row[4];
+        std::string why;
+        if (!plan(b, in.len[(size_t)b], row, why)) {
+            c.err = "utterance " + std::to_string(b) + ": " + why;
+            return -1;
+        }
+        if (row[2] > (int64_t)INT32_MAX - 64) {
+            c.err = "utterance " + std::to_string(b) + " has " + std::to_string(row[2]) + " samples at its " + at_its + ": too long";
+            return -1;
+        }
+        out.len[(size_t)b] = (int)row[2];
+        out.max = std::max(out.max, out.len[(size_t)b]);
+        most = std::max(most, row[3]);
+        std::copy_n(row, 4, report.begin() + (size_t)4 * b);
+    }
+    return most;
+}
+
 // ---- what the host knows of the rows a call delivers (engine.h): host arithmetic from the frame counts, nothing is queued here
 int Engine::plan_rows(Call& c) {
     if (c.rows_planned) return 0;
@@ -481,97 +491,86 @@ int Engine::plan_rows(Call& c) {
     const vits_process_opts& o = c.o;
     const int B = c.B, n_up = c.n_up;
     if (plan_delivery(o, c.dp, err, c.join != nullptr)) return -1;
-    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
+    // the row sets behind every stage, in chain order (Call::behind): each starts as the set in front of it and changes what the stage changes; the strides are
+    // computed here and nowhere else (delivery_plan.h DeliveryStride explains them)
+    Call::RowSet* const set = c.behind;
+    Call::RowSet& voc = set[STAGE_VOCODER];
+    voc.n = B;
+    voc.len = c.slen[n_up];
+    voc.max = c.smax[n_up];
+    voc.stride = round_up(voc.max, 32);
+    set[STAGE_TEMPO] = voc;
     if (c.tempoed()) {
-        // a stated tempo: N' and F of every row are host arithmetic; so are the rows of the report
-        c.tem_len.resize((size_t)B);
-        c.tem_rows.resize((size_t)4 * B);
-        int64_t most = 0;
-        for (int b = 0; b < B; ++b) {
+        const int64_t most = ratio_stage_rows(c, STAGE_TEMPO, "tempo", c.tem_rows, [&](int b, int n, int64_t* row, std::string& why) {
             TempoPlan tp;
-            std::string why;
-            if (!tempo_plan(hp.sampling_rate, c.tempo[b], c.slen[n_up][b], tp, why)) {
-                err = "utterance " + std::to_string(b) + ": " + why;
-                return -1;
-            }
-            if (tp.n_out > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(tp.n_out) + " samples at its tempo: too long";
-                return -1;
-            }
-            c.tem_len[(size_t)b] = (int)tp.n_out;
-            c.tem_max = std::max(c.tem_max, c.tem_len[(size_t)b]);
-            most = std::max(most, tp.F);
-            const int64_t row[4] = {tp.Q, c.slen[n_up][b], tp.n_out, tp.F};
-            std::copy_n(row, 4, c.tem_rows.begin() + (size_t)4 * b);
-        }
+            if (!tempo_plan(hp.sampling_rate, c.tempo[b], n, tp, why)) return false;
+            row[0] = tp.Q, row[1] = n, row[2] = tp.n_out, row[3] = tp.F;
+            return true;
+        });
+        if (most < 0) return -1;
         c.tem_starts = most + 1;
     }
+    set[STAGE_PITCH] = set[STAGE_TEMPO];
     if (c.pitched()) {
-        // a stated pitch: N' of every row is host arithmetic, like everything else here; so are the rows of the report
-        c.pit_len.resize((size_t)B);
-        c.pit_rows.resize((size_t)4 * B);
-        for (int b = 0; b < B; ++b) {
+        const int64_t most = ratio_stage_rows(c, STAGE_PITCH, "pitch ratio", c.pit_rows, [&](int b, int n, int64_t* row, std::string& why) {
             PitchPlan pp;
-            std::string why;
-            if (!pitch_plan(c.pitch[b], c.stretched_len()[(size_t)b], pp, why)) {
-                err = "utterance " + std::to_string(b) + ": " + why;
-                return -1;
-            }
-            c.pit_len[(size_t)b] = (int)pp.n_out;  // (at most 2^31: N <= 2^30 and p >= 0.5; the checks below refuse what does not fit)
-            if (pp.n_out > (int64_t)INT32_MAX - 64) {
-                err = "utterance " + std::to_string(b) + " has " + std::to_string(pp.n_out) + " samples at its pitch ratio: too long";
-                return -1;
-            }
-            c.pit_max = std::max(c.pit_max, c.pit_len[(size_t)b]);
-            const int64_t row[4] = {pp.P, c.stretched_len()[(size_t)b], pp.n_out, pp.K};
-            std::copy_n(row, 4, c.pit_rows.begin() + (size_t)4 * b);
-        }
+            if (!pitch_plan(c.pitch[b], n, pp, why)) return false;
+            row[0] = pp.P, row[1] = n, row[2] = pp.n_out, row[3] = pp.K;  // (N' at most 2^31: N <= 2^30 and p >= 0.5; what does not fit is refused)
+            return true;
+        });
+        if (most < 0) return -1;
     }
-    c.mr_len = c.head_len();
-    if (c.dp[STAGE_EDGES].runs)
+    // stated edges (vits_model_set_edges): the stage runs behind the last window; what the host knows of its output is every row's bound N + Pl + Pt
+    Call::RowSet& ed = set[STAGE_EDGES] = set[STAGE_PITCH];
+    if (c.dp[STAGE_EDGES].runs) {
         for (int b = 0; b < B; ++b) {
-            const int64_t n = edges_plan_.bound(c.head_len()[(size_t)b]);
+            const int64_t n = edges_plan_.bound(ed.len[(size_t)b]);
             if (n > (int64_t)INT32_MAX - 64) {
                 err = "utterance " + std::to_string(b) + " has " + std::to_string(n) + " samples with its pads: too long";
                 return -1;
             }
-            c.mr_len[b] = (int)n;
+            ed.len[(size_t)b] = (int)n;
         }
-    c.utt_max = c.mr_max = *std::max_element(c.mr_len.begin(), c.mr_len.end());
-    c.rows = B;
+        ed.max = *std::max_element(ed.len.begin(), ed.len.end());
+        ed.stride = round_up(std::max(ed.max, 1), 32);
+    }
+    Call::RowSet& jn = set[STAGE_JOIN] = ed;
     const char* row_name = "utterance ";
     if (c.join) {
         // a joined call: the rows behind the join are the tracks, and what the host knows of each is its bound (the utterances' bounds and the positive gaps)
-        const std::vector<int64_t> ub(c.mr_len.begin(), c.mr_len.end());
+        const std::vector<int64_t> ub(ed.len.begin(), ed.len.end());
         std::string why;
         if (!join_bounds(*c.join, ub.data(), why)) {
             err = "vits_model_process_joined: " + why;
             return -1;
         }
-        c.mr_len.assign(c.join->bound.begin(), c.join->bound.end());  // (each at most kEdgesMaxLen = 2^30)
-        c.mr_max = (int)c.join->max_bound;
-        c.rows = c.join->tracks;
+        jn.n = c.join->tracks;
+        jn.len.assign(c.join->bound.begin(), c.join->bound.end());  // (each at most kEdgesMaxLen = 2^30)
+        jn.max = (int)c.join->max_bound;
+        jn.stride = round_up(std::max(jn.max, 1), 32);
         row_name = "track ";
     }
+    set[STAGE_LEVEL] = jn;  // (levelling changes no length, and a levelled buffer follows its input's stride)
+    Call::RowSet& pcm = set[STAGE_RESAMPLE] = jn;
     if (output_rate_) {
         ResamplePlan plan;  // (the plan of the handle's table: set_rates accepted the pair)
         if (!resample_plan(hp.sampling_rate, output_rate_, plan, err)) return -1;
-        c.out_len.resize((size_t)c.rows);
-        for (int r = 0; r < c.rows; ++r) {
-            const int64_t n = plan.out_len(c.mr_len[r]);
+        pcm.max = 0;
+        for (int r = 0; r < pcm.n; ++r) {
+            const int64_t n = plan.out_len(pcm.len[(size_t)r]);
             if (n > (int64_t)INT32_MAX - 64) {
                 err = row_name + std::to_string(r) + " has " + std::to_string(n) + " samples at the output rate: too long";
                 return -1;
             }
-            c.out_len[r] = (int)n;
-            c.out_max = std::max(c.out_max, (int)n);
+            pcm.len[(size_t)r] = (int)n;
+            pcm.max = std::max(pcm.max, (int)n);
         }
-        c.out_ws = round_up(std::max(c.out_max, 1), 32);
+        pcm.stride = round_up(std::max(pcm.max, 1), 32);
     }
     if (o.out_device && !o.frames_only) {
         const bool rs = output_rate_ != 0;
-        const std::vector<int>& len = rs ? c.out_len : c.mr_len;
-        const int longest = rs ? c.out_max : c.mr_max;
+        const std::vector<int>& len = pcm.len;
+        const int longest = pcm.max;
         if (o.out_device_stride < longest) {
             if (c.join) {
                 const int g = (int)(std::find_if(len.begin(), len.end(), [&](int n) { return n > o.out_device_stride; }) - len.begin());
@@ -586,31 +585,38 @@ int Engine::plan_rows(Call& c) {
     return 0;
 }
 
-// ---- the pitch stage of a call: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.pitch_lens: what the edges stage,
-// or with it off every stage behind it, reads its rows' lengths from). One launch serves every ratio of the batch; rows with ratio 1 are copied.
+// the ratios [B] of a stage on their way to the device, through pinned memory that outlives the copy
+int Engine::upload_ratios(const Call& c, const float* ratios, PinnedBuf<float>& pin, float* dev) {
+    std::string& err = c.err;
+    HIP_OK(pin.ensure((size_t)c.B, (size_t)c.B + 64));
+    std::copy_n(ratios, c.B, pin.p);
+    HIP_OK(hipMemcpyAsync(dev, pin.p, sizeof(float) * (size_t)c.B, hipMemcpyHostToDevice, stream));
+    prof.fence();
+    return 0;
+}
+
+// ---- the pitch stage of a call: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.pitch_lens = behind[STAGE_PITCH].dev: what the stages
+// behind it read their rows' lengths from). One launch serves every ratio of the batch; rows with ratio 1 are copied.
 int Engine::run_pitch(Call& c) {
     std::string& err = c.err;
     const int B = c.B;
-    const Call::Rows src = c.rows_of(c.dp.pitch.src), dst = c.rows_of(c.dp.pitch.dst);
+    const Call::Rows src = c.rows_of(c.dp[STAGE_PITCH].src), dst = c.rows_of(c.dp[STAGE_PITCH].dst);
     if (!pitch_table_ && !(pitch_table_ = upload(pitch_table_pairs()))) {  // (owned by the handle and counted in weight_bytes from here on)
         err = "pitch table: device allocation failed";
         return -1;
     }
-    HIP_OK(c.pitch_pin->ensure((size_t)B, (size_t)B + 64));
-    std::copy_n(c.pitch, B, c.pitch_pin->p);
-    HIP_OK(hipMemcpyAsync(c.s2.pitch_ratios, c.pitch_pin->p, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream));
-    prof.fence();
+    if (upload_ratios(c, c.pitch, *c.pitch_pin, c.s2.pitch_ratios)) return -1;
     PitchCall pc;
     pc.x = src.p;
     pc.x_stride = src.stride;
-    pc.lens = c.stretched_lens();  // (the vocoder's sample counts, or behind a tempo stage what its search wrote)
+    pc.lens = c.behind[STAGE_PITCH - 1].dev;  // (the vocoder's sample counts, or behind a tempo stage what its search wrote)
     pc.ratios = c.s2.pitch_ratios;
     pc.y = dst.p;
     pc.y_stride = dst.stride;
     pc.table = pitch_table_;
     pc.lens_out = c.s2.pitch_lens;
     pc.batch = B;
-    pc.max_out = c.pit_max;
+    pc.max_out = c.behind[STAGE_PITCH].max;
     double taps = 0, in_s = 0, out_s = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t* row = c.pit_rows.data() + (size_t)4 * b;
@@ -623,21 +629,18 @@ int Engine::run_pitch(Call& c) {
     return 0;
 }
 
-// ---- the tempo stage of a conversion: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.tempo_lens: what the pitch
-// stage, or with it off every stage behind it, reads its rows' lengths from). Two launches serve every tempo of the batch: the search (one block per row, its
+// ---- the tempo stage of a conversion: the vocoder's rows -> the stage's destination (the plan's), N' of every row on the device (c.s2.tempo_lens = behind[STAGE_TEMPO].dev: what the
+// stages behind it read their rows' lengths from). Two launches serve every tempo of the batch: the search (one block per row, its
 // segments a chain) and the overlap-add; rows with tempo 1 are copied.
 int Engine::run_tempo(Call& c) {
     std::string& err = c.err;
-    const int B = c.B, n_up = c.n_up;
-    const Call::Rows src = c.rows_of(c.dp.tempo.src), dst = c.rows_of(c.dp.tempo.dst);
-    HIP_OK(tempo_host_.ensure((size_t)B, (size_t)B + 64));
-    std::copy_n(c.tempo, B, tempo_host_.p);
-    HIP_OK(hipMemcpyAsync(c.s2.tempo_q, tempo_host_.p, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream));
-    prof.fence();
+    const int B = c.B;
+    const Call::Rows src = c.rows_of(c.dp[STAGE_TEMPO].src), dst = c.rows_of(c.dp[STAGE_TEMPO].dst);
+    if (upload_ratios(c, c.tempo, tempo_host_, c.s2.tempo_q)) return -1;
     TempoCall tc;
     tc.x = src.p;
     tc.x_stride = src.stride;
-    tc.lens = c.s1.stage_lens + (size_t)n_up * B;
+    tc.lens = c.behind[STAGE_TEMPO - 1].dev;
     tc.tempos = c.s2.tempo_q;
     tc.rate = hp.sampling_rate;
     tc.starts = c.s2.tempo_starts;
@@ -646,7 +649,7 @@ int Engine::run_tempo(Call& c) {
     tc.y_stride = dst.stride;
     tc.lens_out = c.s2.tempo_lens;
     tc.batch = B;
-    tc.max_out = c.tem_max;
+    tc.max_out = c.behind[STAGE_TEMPO].max;
     double diffs = 0, out_s = 0, steps = 0;
     TempoPlan tp;
     std::string ignored;
@@ -670,7 +673,7 @@ int Engine::run_join(Call& c) {
     std::string& err = c.err;
     const JoinPlan& p = *c.join;
     const int B = c.B;
-    const Call::Rows src = c.rows_of(c.dp.join.src), dst = c.rows_of(c.dp.join.dst);
+    const Call::Rows src = c.rows_of(c.dp[STAGE_JOIN].src), dst = c.rows_of(c.dp[STAGE_JOIN].dst);
     const std::vector<int64_t> table = join_table(p);
     HIP_OK(join_table_host_.ensure(table.size(), table.size() + table.size() / 4 + 64));
     std::memcpy(join_table_host_.p, table.data(), sizeof(int64_t) * table.size());
@@ -680,12 +683,12 @@ int Engine::run_join(Call& c) {
     jc.plan = &p;
     jc.x = src.p;
     jc.x_stride = src.stride;
-    jc.lens = c.utt_lens;
+    jc.lens = c.behind[STAGE_JOIN - 1].dev;
     jc.y = dst.p;
     jc.y_stride = dst.stride;
     jc.table = c.s2.join_table;
     jc.rows = jn_.dev();
-    jc.track_lens = track_lens(B);  // (= c.mr_lens: run_stage_two pointed it there when it grew the rows)
+    jc.track_lens = track_lens(B);  // (= behind[STAGE_JOIN].dev: run_stage_two set it when it grew the rows)
     int64_t in_s = 0, out_s = 0;
     for (const int64_t n : p.ubound) in_s += n;
     for (const int64_t n : p.bound) out_s += n;
@@ -697,18 +700,18 @@ int Engine::run_join(Call& c) {
     return 0;
 }
 
-// the call of the output resampler: what the plan routes into the stage -> what the call delivers, at the lengths every stage in front of it left (c.mr_lens)
+// the call of the output resampler: what the plan routes into the stage -> what the call delivers, at the lengths the stages in front of it left
 ResampleCall Engine::resample_out_call(const Call& c) const {
     const Call::Rows x = c.rows_of(c.dp[STAGE_RESAMPLE].src), y = c.rows_of(c.dp.delivered);
     ResampleCall rsc;
     rsc.x = x.p;
     rsc.x_stride = x.stride;
-    rsc.lens = c.mr_lens;  // (device: every utterance's samples at the model's rate, the trimmed ones under stated edges)
+    rsc.lens = c.behind[STAGE_RESAMPLE - 1].dev;  // (device: every utterance's samples at the model's rate, the trimmed ones under stated edges)
     rsc.y = y.p;
     rsc.y_stride = y.stride;
     rsc.taps = c.rate_out->taps;
     rsc.plan = c.rate_out->plan;
-    rsc.batch = c.rows;
+    rsc.batch = c.behind[STAGE_RESAMPLE].n;
     return rsc;
 }
 
@@ -729,15 +732,16 @@ int Engine::run_delivery_tail(Call& c, const std::function<int()>& last_chunks) 
         snapshot(name, t, 1, max_len, B, lens);
     };
     // what levelling and the taps behind it see of the model-rate rows on the host: the vocoder's sample counts, or (stated edges, taps only) the trimmed ones
-    std::vector<int> tap_len = c.head_len(), tap_out_len = c.out_len;
-    int tap_max = c.head_max(), tap_out_max = c.out_max;
-    if (dp.tempo.runs) {
+    const Call::RowSet& pcm = c.behind[STAGE_RESAMPLE];
+    std::vector<int> tap_len = c.behind[STAGE_PITCH].len, tap_out_len = pcm.len;
+    int tap_max = c.behind[STAGE_PITCH].max, tap_out_max = pcm.max;
+    if (dp[STAGE_TEMPO].runs) {
         if (run_tempo(c)) return -1;
-        if (o.collect_taps) tap("waveform_tempo", dp.tempo.after, c.tem_max, c.tem_len);
+        if (o.collect_taps) tap("waveform_tempo", dp[STAGE_TEMPO].after, c.behind[STAGE_TEMPO].max, c.behind[STAGE_TEMPO].len);
     }
-    if (dp.pitch.runs) {
+    if (dp[STAGE_PITCH].runs) {
         if (run_pitch(c)) return -1;
-        if (o.collect_taps) tap("waveform_pitch", dp.pitch.after, tap_max, tap_len);
+        if (o.collect_taps) tap("waveform_pitch", dp[STAGE_PITCH].after, tap_max, tap_len);
     }
     if (dp[STAGE_EDGES].runs) {
         if (run_edges(c)) return -1;
@@ -755,7 +759,7 @@ int Engine::run_delivery_tail(Call& c, const std::function<int()>& last_chunks) 
             tap("waveform_edges", dp[STAGE_EDGES].after, tap_max, tap_len);
         }
     }
-    if (dp.join.runs && run_join(c)) return -1;
+    if (dp[STAGE_JOIN].runs && run_join(c)) return -1;
     if (dp[STAGE_LEVEL].runs) {
         if (run_level(c)) return -1;
         if (o.collect_taps) tap("waveform_level", dp[STAGE_LEVEL].after, tap_max, tap_len);
@@ -763,8 +767,8 @@ int Engine::run_delivery_tail(Call& c, const std::function<int()>& last_chunks) 
     if (rs && !o.on_chunk) {
         // nobody waits for parts of it: one launch over every utterance, behind the last window
         ResampleCall rsc = resample_out_call(c);
-        rsc.max_range = c.out_max;
-        HIP_OK(resample("resample_out", rsc, c.wave_samples(), std::accumulate(c.out_len.begin(), c.out_len.end(), (int64_t)0)));
+        rsc.max_range = pcm.max;
+        HIP_OK(resample("resample_out", rsc, c.wave_samples(), std::accumulate(pcm.len.begin(), pcm.len.end(), (int64_t)0)));
     }
     if (rs && o.collect_taps) tap("waveform_out", dp[STAGE_RESAMPLE].after, tap_out_max, tap_out_len);
     return last_chunks ? last_chunks() : 0;

@@ -18,7 +18,6 @@ int Engine::layout_stage_two(Call& c) {
     const int Lw_max = wins.Lw_max;
     const std::vector<int>& smul = c.smul;
     const std::vector<int>& sadd = c.sadd;
-    const std::vector<int>& smax = c.smax;
     // ---- stage two buffers -------------------------------------------------------------------------------------
     const int ls = c.ls = round_up(Lmax, 32), lws = c.lws = round_up(Lw_max, 32);
     size_t& big = c.big;
@@ -33,16 +32,22 @@ int Engine::layout_stage_two(Call& c) {
     const bool fast16 = c.fast16 = arith_now_ != VITS_ARITH_F32 && vocoder_group_ok_ && !knobs.no_group16;
     c.fuse16 = fast16 && !knobs.no_fuse16;  // resblock conv pairs of the narrow stages as one kernel
     const size_t x16_elems2 = arith_now_ != VITS_ARITH_F32 ? std::max({big, (size_t)B * round_up(H, 8) * round_up(ls, 8), (size_t)B * round_up(hp.up_init, 8) * round_up(lws, 8), (size_t)B * round_up(F, 8) * round_up(ls, 8)}) + 64 : 0;
-    const int S_stride = c.S_stride = round_up(smax[n_up], 32);
-    const int E_stride = c.E_stride = c.dp[STAGE_EDGES].runs ? round_up(std::max(c.utt_max, 1), 32) : S_stride;
-    // the rows behind the edges stage (Engine::plan_rows): one per utterance at E_stride, or — a joined call — one per track at J_stride
-    const int R = c.rows;
-    const int J_stride = c.J_stride = c.join ? round_up(std::max(c.mr_max, 1), 32) : 0;
-    // a stated pitch: the rows behind the stage, at the bound of N' at the smallest ratio; with the edges stage off a levelled buffer follows them (delivery_plan.cpp)
-    // (a stated tempo in front of it: its rows hold up to 2 S_stride samples, and the pitch stage's twice that)
-    const int T_stride = c.T_stride = c.tempoed() ? 2 * S_stride : 0;
-    const int P_stride = c.P_stride = c.pitched() ? 2 * (c.tempoed() ? T_stride : S_stride) : 0;
-    const int L_stride = c.join ? J_stride : (c.dp[STAGE_EDGES].runs ? E_stride : (c.pitched() ? P_stride : (c.tempoed() ? T_stride : E_stride)));
+    // the delivery chain: the rows behind every stage (Call::behind, filled by Engine::plan_rows) and the plan's routes size its buffers. R: the rows behind the
+    // join, one per utterance or — a joined call — one per track
+    const DeliveryPlan& dp = c.dp;
+    const Call::RowSet* const behind = c.behind;
+    const int S_stride = behind[STAGE_VOCODER].stride;
+    const int R = behind[STAGE_JOIN].n;
+    // no stage writes a row longer than the stride of what it writes to: a wrong stride is refused here, on the host, before anything of stage two is queued
+    static const char* const stage_name[STAGE_COUNT] = {"vocoder", "tempo", "pitch", "edges", "join", "level", "resample"};
+    for (int s = 0; s < STAGE_COUNT; ++s) {
+        const int64_t stride = c.rows_of(dp[s].dst).stride;  // (out_device: out_device_stride)
+        if (dp[s].runs && dp[s].dst.buf != BUF_NONE && behind[s].max > stride) {
+            c.err = std::string("delivery chain: the ") + stage_name[s] + " stage's longest row has " + std::to_string(behind[s].max) +
+                    " samples, and the rows it writes are " + std::to_string(stride) + " apart";
+            return -1;
+        }
+    }
     // VITS_ARITH_F32_SPLIT: three bf16 planes per conv input of the wide stages' resblocks (conv_split.hip): the stage input once, t and the stream per
     // concurrently running resblock
     size_t sp_elems = 0;
@@ -77,25 +82,24 @@ int Engine::layout_stage_two(Call& c) {
         s2.pre = o.collect_taps ? a.alloc<float>((size_t)B * S_stride) : nullptr;
         s2.wave = a.alloc<float>((size_t)B * S_stride);
         // the buffers of the delivery chain: exactly what the call's plan names (delivery_plan.h; a stage that writes straight to out_device needs none)
-        const DeliveryPlan& dp = c.dp;
-        s2.wave_out = dp.need(NEED_WAVE_OUT) ? a.alloc<float>((size_t)R * c.out_ws) : nullptr;
+        s2.wave_out = dp.need(NEED_WAVE_OUT) ? a.alloc<float>((size_t)R * behind[STAGE_RESAMPLE].stride) : nullptr;
         s2.out_ranges = dp.need(NEED_OUT_RANGES) ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
-        s2.wave_lvl = dp.need(NEED_WAVE_LVL) ? a.alloc<float>((size_t)R * L_stride) : nullptr;
-        s2.lvl_scratch = dp.need(NEED_LVL_SCRATCH) ? a.alloc<char>(level_scratch_bytes(R, c.mr_max, level_plan_.S)) : nullptr;
-        s2.lim_scratch = dp.need(NEED_LIM_SCRATCH) ? a.alloc<char>(limit_scratch_bytes(R, c.mr_max)) : nullptr;
-        s2.wave_edge = dp.need(NEED_WAVE_EDGE) ? a.alloc<float>((size_t)B * E_stride) : nullptr;
-        s2.ed_scratch = dp.need(NEED_ED_SCRATCH) ? a.alloc<char>(edges_scratch_bytes(B, c.head_max(), edges_plan_.W)) : nullptr;
+        s2.wave_lvl = dp.need(NEED_WAVE_LVL) ? a.alloc<float>((size_t)R * c.rows_of(dp[STAGE_LEVEL].dst).stride) : nullptr;  // (it follows its input's stride)
+        s2.lvl_scratch = dp.need(NEED_LVL_SCRATCH) ? a.alloc<char>(level_scratch_bytes(R, behind[STAGE_LEVEL - 1].max, level_plan_.S)) : nullptr;
+        s2.lim_scratch = dp.need(NEED_LIM_SCRATCH) ? a.alloc<char>(limit_scratch_bytes(R, behind[STAGE_LEVEL - 1].max)) : nullptr;
+        s2.wave_edge = dp.need(NEED_WAVE_EDGE) ? a.alloc<float>((size_t)B * behind[STAGE_EDGES].stride) : nullptr;
+        s2.ed_scratch = dp.need(NEED_ED_SCRATCH) ? a.alloc<char>(edges_scratch_bytes(B, behind[STAGE_EDGES - 1].max, edges_plan_.W)) : nullptr;
         s2.lvl_ranges = dp.need(NEED_LVL_RANGES) ? a.alloc<int>(wins.size() * (size_t)2 * B) : nullptr;
         s2.tile_maps = c.tm_total ? a.alloc<TileEntry>((size_t)c.tm_total) : nullptr;
-        s2.wave_join = dp.need(NEED_WAVE_JOIN) ? a.alloc<float>((size_t)R * J_stride) : nullptr;
+        s2.wave_join = dp.need(NEED_WAVE_JOIN) ? a.alloc<float>((size_t)R * behind[STAGE_JOIN].stride) : nullptr;
         s2.join_table = dp.need(NEED_JOIN_TABLE) ? a.alloc<int64_t>(join_table_elems(B, R)) : nullptr;
-        s2.wave_pitch = dp.need(NEED_WAVE_PITCH) ? a.alloc<float>((size_t)B * P_stride) : nullptr;
-        s2.pitch_ratios = dp.pitch.runs ? a.alloc<float>((size_t)B) : nullptr;
-        s2.pitch_lens = dp.pitch.runs ? a.alloc<int>((size_t)B) : nullptr;
-        s2.wave_tempo = dp.need(NEED_WAVE_TEMPO) ? a.alloc<float>((size_t)B * T_stride) : nullptr;
-        s2.tempo_q = dp.tempo.runs ? a.alloc<float>((size_t)B) : nullptr;
-        s2.tempo_lens = dp.tempo.runs ? a.alloc<int>((size_t)B) : nullptr;
-        s2.tempo_starts = dp.tempo.runs ? a.alloc<int>((size_t)B * (size_t)c.tem_starts) : nullptr;
+        s2.wave_pitch = dp.need(NEED_WAVE_PITCH) ? a.alloc<float>((size_t)B * behind[STAGE_PITCH].stride) : nullptr;
+        s2.pitch_ratios = dp[STAGE_PITCH].runs ? a.alloc<float>((size_t)B) : nullptr;
+        s2.pitch_lens = dp[STAGE_PITCH].runs ? a.alloc<int>((size_t)B) : nullptr;
+        s2.wave_tempo = dp.need(NEED_WAVE_TEMPO) ? a.alloc<float>((size_t)B * behind[STAGE_TEMPO].stride) : nullptr;
+        s2.tempo_q = dp[STAGE_TEMPO].runs ? a.alloc<float>((size_t)B) : nullptr;
+        s2.tempo_lens = dp[STAGE_TEMPO].runs ? a.alloc<int>((size_t)B) : nullptr;
+        s2.tempo_starts = dp[STAGE_TEMPO].runs ? a.alloc<int>((size_t)B * (size_t)c.tem_starts) : nullptr;
     };
     if (arena_layout(a2_, stream, c.err, layout2)) return -1;
     set_x16_scratch(s2.x16[0], s2.x16[1], s2.x16[2], x16_elems2);

@@ -257,7 +257,7 @@ struct Call {
     };
     std::vector<TileMapJob> tm_jobs;
     int64_t tm_total = 0;
-    int ls = 0, lws = 0, S_stride = 0;
+    int ls = 0, lws = 0;
     size_t big = 0;        // floats of the largest vocoder activation (of one window)
     std::vector<int> sts;  // [stage] time stride of that stage's buffers
     bool fast16 = false, fuse16 = false;
@@ -265,6 +265,18 @@ struct Call {
     // The delivery chain behind the vocoder (delivery_plan.h), planned once per call (Engine::plan_delivery): who runs, and which buffer each stage reads and
     // writes. layout_stage_two allocates what the plan needs; rows_of is the ONE place where a buffer id of the plan becomes this call's pointer and row stride.
     DeliveryPlan dp;
+    // What the chain holds BEHIND every stage, in the plan's order. A stage that does not run, or only reads (VITS_LEVEL_MEASURE), holds the set of the stage in
+    // front of it: what stage X reads is always behind[X - 1], and what the call hands out is behind[STAGE_RESAMPLE]. Each field is filled where it becomes
+    // known: n, len, max and stride by Engine::plan_rows (host arithmetic from the frame counts), dev by run_stage_two (behind the arena layout and the growth
+    // of the edges' and the joins' rows, whose tails the trimmed and the track lengths are).
+    struct RowSet {
+        int n = 0;                 // rows: the utterances, or (from the join on) the tracks
+        std::vector<int> len;      // what the host knows of each row: exact, or its bound (edges: N + Pl + Pt; join: the track's)
+        int max = 0;               // the longest of them
+        const int* dev = nullptr;  // the rows' lengths on the device [n], at the model's rate (null behind the resampler, which writes none)
+        int stride = 0;            // row stride of the stage's own buffer (delivery_plan.h DeliveryStride states each)
+    };
+    RowSet behind[STAGE_COUNT];
     struct Rows {
         float* p = nullptr;
         int64_t stride = 0;
@@ -283,63 +295,34 @@ struct Call {
             default: break;
         }
         switch (r.stride) {
-            case STRIDE_S: out.stride = S_stride; break;
-            case STRIDE_E: out.stride = E_stride; break;
-            case STRIDE_OUT_WS: out.stride = out_ws; break;
+            case STRIDE_S: out.stride = behind[STAGE_VOCODER].stride; break;
+            case STRIDE_T: out.stride = behind[STAGE_TEMPO].stride; break;
+            case STRIDE_P: out.stride = behind[STAGE_PITCH].stride; break;
+            case STRIDE_E: out.stride = behind[STAGE_EDGES].stride; break;
+            case STRIDE_J: out.stride = behind[STAGE_JOIN].stride; break;
+            case STRIDE_OUT_WS: out.stride = behind[STAGE_RESAMPLE].stride; break;
             case STRIDE_CALLER: out.stride = o.out_device_stride; break;
-            case STRIDE_J: out.stride = J_stride; break;
-            case STRIDE_P: out.stride = P_stride; break;
-            case STRIDE_T: out.stride = T_stride; break;
             default: break;
         }
         return out;
     }
-    // output rate set (Engine::output_rate): the filter, every utterance's delivered length ceil(N L / M), the longest, and the row stride of s2.wave_out
-    const RateTable* rate_out = nullptr;
-    std::vector<int> out_len;
-    int out_max = 0, out_ws = 0;
+    const RateTable* rate_out = nullptr;  // output rate set (Engine::output_rate): the filter
     // a level set (Engine::level_kind): the kind of this call (dp.multiplies: every kind but VITS_LEVEL_MEASURE; dp.limits: through the limiter)
     int lev = 0;
-    // stated edges (Engine::set_edges): the stage runs between the vocoder and levelling. What levelling, the limiter and the resampler read is then its output:
-    // E_stride = the row stride of the model-rate buffers behind the vocoder's own (S_stride with the stage off), mr_lens = the device lengths [B] of those rows
-    // (the stage's N'; the vocoder's sample counts with it off), mr_len / mr_max = what the host knows of them (under the stage: the bounds N + Pl + Pt)
-    int E_stride = 0;
-    const int* mr_lens = nullptr;
-    std::vector<int> mr_len;
-    int mr_max = 0;
-    // The rows the stages behind the edges stage work on, and the call hands out (Engine::plan_rows): one per utterance, or — a joined call
-    // (vits_model_process_joined; join: its tracks and gaps, its bounds once plan_rows has run) — one per track. Behind the join mr_len / mr_max / mr_lens are the
-    // tracks' (bounds on the host, T_g on the device) and J_stride is their row stride; utt_max and utt_lens keep what they were per utterance, which the edges
-    // stage's stride and the join's input are sized and read by.
+    // a joined call (vits_model_process_joined): its tracks and gaps, and its bounds once plan_rows has run
     JoinPlan* join = nullptr;
-    int rows = 0, utt_max = 0, J_stride = 0;
-    // A stated pitch (pitch: the call's resolved ratios [B], Engine::resolve_pitch; null: the stage is off): the varispeed runs between the vocoder and the edges stage. What the edges stage (and,
-    // with it off, everything behind it) reads is then its output: pit_len / pit_max = N' of every row, host arithmetic from the frame counts (Engine::plan_rows);
-    // P_stride = 2 S_stride, the stage's row stride; pit_rows = the report [B][4]; pitch_pin = the pinned memory the ratios travel through (the slot's for a
-    // pipelined batch). head_lens / head_len / head_max = the rows at the head of the chain, which the edges stage reads: the pitch stage's, else the vocoder's.
-    std::vector<int> pit_len;
-    std::vector<int64_t> pit_rows;
-    int pit_max = 0, P_stride = 0;
-    PinnedBuf<float>* pitch_pin = nullptr;
+    // A stated pitch (the call's resolved ratios [B], Engine::resolve_pitch or a conversion's; null: the stage is off): pit_rows = the report [B][4] = {P, N, N', K},
+    // pitch_pin = the pinned memory the ratios travel through (the slot's for a pipelined batch)
     const float* pitch = nullptr;
     bool pitched() const { return pitch != nullptr; }
-    // A stated tempo (tempo: the call's resolved tempos [B], Engine::resolve_conversion_prosody; null: the stage is off): the time stretch (tempo.hip) runs between
-    // the vocoder and the pitch stage, which then reads ITS rows: tem_len / tem_max = N' of every row, host arithmetic from the frame counts (Engine::plan_rows);
-    // T_stride = 2 S_stride, the stage's row stride (and P_stride = 2 T_stride behind it); tem_rows = the report [B][4] = {Q, N, N', F}; tem_starts = the
-    // longest row's F + 1, the row stride of s2.tempo_starts. stretched_* = what the pitch stage reads: the tempo stage's rows, else the vocoder's.
-    std::vector<int> tem_len;
-    std::vector<int64_t> tem_rows;
-    int tem_max = 0, T_stride = 0;
-    int64_t tem_starts = 0;
+    std::vector<int64_t> pit_rows;
+    PinnedBuf<float>* pitch_pin = nullptr;
+    // A stated tempo (the call's resolved tempos [B], Engine::resolve_conversion_prosody; null: the stage is off): tem_rows = the report [B][4] = {Q, N, N', F};
+    // tem_starts = the longest row's F + 1, the row stride of s2.tempo_starts
     const float* tempo = nullptr;
     bool tempoed() const { return tempo != nullptr; }
-    const int* stretched_lens() const { return tempoed() ? s2.tempo_lens : s1.stage_lens + (size_t)n_up * B; }
-    const std::vector<int>& stretched_len() const { return tempoed() ? tem_len : slen[n_up]; }
-    int stretched_max() const { return tempoed() ? tem_max : smax[n_up]; }
-    const int* head_lens() const { return pitched() ? s2.pitch_lens : stretched_lens(); }
-    const std::vector<int>& head_len() const { return pitched() ? pit_len : stretched_len(); }
-    int head_max() const { return pitched() ? pit_max : stretched_max(); }
-    const int* utt_lens = nullptr;
+    std::vector<int64_t> tem_rows;
+    int64_t tem_starts = 0;
     bool rows_planned = false;
 
     Call(const vits_process_opts& o_, std::string& err_, const int32_t* ids_, int B_, int id_stride_) : o(o_), err(err_), ids(ids_), B(B_), id_stride(id_stride_) {}
