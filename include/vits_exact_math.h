@@ -18,7 +18,7 @@
  * What each function restates is cited on it; the loops follow the oracle's reading of those lines (oracle/vits_oracle.cpp), which stays the
  * independent restatement and is compared with this one at tolerance (tests/test_oracle.py).
  *
- * Not used by the default mode: the throughput kernels (conv_mfma.hip, misc_kernels.hip) are unchanged.
+ * Not used by the default mode: the throughput kernels (conv_mfma.hip and the stage-one kernel files) are unchanged.
  */
 #ifndef VITS_EXACT_MATH_H
 #define VITS_EXACT_MATH_H

@@ -1,6 +1,6 @@
 """numpy side of the operator tests of the stochastic duration predictor's kernels (tests/test_gpu_dds_ops.py, tests/test_gpu_spline_ops.py,
 tests/test_dp_op_host.py): a DDS block, the inverse rational-quadratic spline of a conv flow, and the durations, each restated from the project's own kernels
-(vits.cpp_amd/csrc/misc_kernels.hip, stage1_lat.hip), their comments and the published definition of the model (transformers modeling_vits.py).
+(vits.cpp_amd/csrc/dds.hip, spline.hip, stage1_lat.hip), their comments and the published definition of the model (transformers modeling_vits.py).
 
 Every function takes a `dtype`: float64 is the reference, float32 the "restatement" — the same statements with every tensor and every operation in fp32, whose
 error against float64 is the yardstick of the GPU tests (the 2x rule of tests/split_ref.py). Nothing here knows how a kernel tiles its work."""
@@ -16,7 +16,7 @@ _erf = np.frompyfunc(math.erf, 1, 1)
 
 
 def round_arith(v, arith):
-    """round_arith of misc_kernels.hip: a conv operand in the 16-bit arithmetics is rounded (nearest even) to fp16 / bf16"""
+    """round_arith of kernel_common.h: a conv operand in the 16-bit arithmetics is rounded (nearest even) to fp16 / bf16"""
     if arith == F16:
         return np.asarray(v).astype(np.float16).astype(np.float32)
     if arith == BF16:
@@ -107,13 +107,13 @@ def dds_block(P, lens, dtype, x=None, z=None, cond=None, zc=0, head=0, bias_rows
 
 # ---- the spline ------------------------------------------------------------------------------------------------------------------------------
 def _softplus(x, dtype):
-    """softplus_f of misc_kernels.hip: x beyond 20, else log(1 + exp(x)) taken in double and rounded to dtype"""
+    """softplus_f of spline.hip: x beyond 20, else log(1 + exp(x)) taken in double and rounded to dtype"""
     x = np.asarray(x, dtype)
     return np.where(x > dtype(20), x, np.log(1.0 + np.exp(np.minimum(x, dtype(30)).astype(np.float64))).astype(dtype))
 
 
 def _spline_rows(x, u, nb, B, inv_sqrt, mode, q4, masked, dtype):
-    """spline_row of misc_kernels.hip on every token at once: x [T], u [3 nb - 1, T]; q4, masked: bool [T]"""
+    """spline_row of spline.hip on every token at once: x [T], u [3 nb - 1, T]; q4, masked: bool [T]"""
     T = x.size
     one, B = dtype(1), dtype(B)
     min_w = min_h = min_d = dtype(1e-3)

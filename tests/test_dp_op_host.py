@@ -14,7 +14,7 @@ import test_gpu_spline_ops as S
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_plan_table.txt")
 INV_SQRT = S.INV_SQRT
-# every instantiation the launchers can name (misc_kernels.hip VITS_DDS_LAUNCH, stage1_lat.hip VITS_DDSL_M)
+# every instantiation the launchers can name (dds.hip VITS_DDS_LAUNCH, stage1_lat.hip VITS_DDSL_M)
 LAYER_KERNELS = {"dds_layer_kernel<%d, %d>" % (a, m) for a in (0, 1, 2) for m in (2, 4, 6, 8)}
 LAT_KERNELS = {"dds_layer_lat_kernel<%d, %d, %d>" % (h, t, m) for h in (0, 1, 2) for t in (0, 1) for m in (6, 8)}
 assert O.MODE_REFERENCE == D.MODE_REFERENCE and O.MODE_HF == D.MODE_HF

@@ -386,7 +386,7 @@ def test_long_form_1024_ids_in_f16_mode(pkg, oracle, full_bytes):
 
 @pytest.mark.parametrize("name,arith", [("f32", 0)] + [(n, a) for n, a, _ in ARITHS])
 def test_fused_dds_layer_is_bit_identical_to_the_three_kernel_path(pkg, full_bytes, monkeypatch, name, arith):
-    """misc_kernels.hip dds_layer_kernel (depthwise + LN + gelu + 1x1 conv + LN + gelu + residual of one DDS layer, vits.cpp:655-691,
+    """dds.hip dds_layer_kernel (depthwise + LN + gelu + 1x1 conv + LN + gelu + residual of one DDS layer, vits.cpp:655-691,
     as one kernel) takes every sum in the order of the three launches it replaces: the log-durations and everything behind them must
     not move by a bit — ragged batch with very short and long members (more 32-column tiles than one launch runs at once), both
     semantics modes, all arithmetic modes."""

@@ -10,7 +10,7 @@
 #ifndef B_
 #define B_ 8
 #endif
-#include "../vits.cpp_amd/csrc/misc_kernels.hip"
+#include "../vits.cpp_amd/csrc/attention.hip"
 #include "../vits.cpp_amd/csrc/launch_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 

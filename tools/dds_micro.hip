@@ -1,10 +1,10 @@
-// Developer microbenchmark for dds_layer_kernel (misc_kernels.hip) at batch-1 size: HIP-event time per launch with cold caches
-// (a 1 GiB fill between launches) and per-phase timestamps of every block. Not part of the product.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DVITS_PHASE_TIMING tools/dds_micro.hip vits.cpp_amd/csrc/conv_mfma*.o ... (see tools/jobs/ddsmicro.sh)
+// Developer microbenchmark for dds_layer_kernel (dds.hip) at batch-1 size: HIP-event time per launch with cold caches
+// (a 1 GiB fill between launches) and, with -DVITS_PHASE_TIMING, per-phase timestamps of every block (of the last launch). Not part of the product.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DVITS_PHASE_TIMING] tools/dds_micro.hip -o tools/bin/dds_micro
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
-#include "../vits.cpp_amd/csrc/misc_kernels.hip"
+#include "../vits.cpp_amd/csrc/dds.hip"
 #include "../vits.cpp_amd/csrc/launch_plan.cpp"  // (the launch policy: host code, included like the kernel file so that one hipcc line builds the harness)
 using namespace vits;
 // fragment order of conv_mfma.hip pack_conv_weights for a 1x1 conv (EPI_STD)
@@ -42,7 +42,6 @@ int main(int argc, char** argv) {
     const size_t bigN = 256u << 20; hipMalloc(&big, bigN * 4);
     pc.wp = dwp; pc.bias = db;
     const int nblk = (T + 31) / 32;
-    unsigned long long* dbg; hipMalloc(&dbg, nblk * 16 * 8); hipMemset(dbg, 0, nblk * 16 * 8);
     TensorRef x, y; x.p = dx; x.cs = ts; x.bs = (int64_t)H * ts; y = x; y.p = dy;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int cold = 0; cold < 2; ++cold) {
@@ -50,7 +49,6 @@ int main(int argc, char** argv) {
         const int reps = 10;
         for (int i = 0; i < reps + 1; ++i) {
             if (cold) hipMemsetAsync(big, i, bigN * 4, nullptr);
-            g_dds_dbg = i == reps ? dbg : nullptr;
             hipEventRecord(e0, nullptr);
             hipError_t e = launch_dds_layer(x, y, ddw, db, dg, db, pc, dg, db, nullptr, B, H, T, K, dil, 1e-5f, 0, nullptr);
             hipEventRecord(e1, nullptr);
@@ -60,8 +58,9 @@ int main(int argc, char** argv) {
             if (i > 0 && i < reps) { best = std::min(best, ms); sum += ms; }
         }
         printf("%s: avg %.1f us  best %.1f us per launch (T=%d B=%d dil=%d, %d blocks)\n", cold ? "cold" : "warm", sum / (reps - 1) * 1e3, best * 1e3, T, B, dil, nblk * B);
-        std::vector<unsigned long long> h(nblk * 16);
-        hipMemcpy(h.data(), dbg, nblk * 16 * 8, hipMemcpyDeviceToHost);
+#ifdef VITS_PHASE_TIMING
+        std::vector<unsigned long long> h(nblk * 16);  // (the rows of utterance 0: blocks 0 .. nblk - 1 of the grid)
+        hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(vits_dds_phase), h.size() * 8);
         unsigned long long t0 = ~0ull;
         for (int bl = 0; bl < nblk; ++bl) t0 = std::min(t0, h[bl * 16]);
         for (int bl = 0; bl < nblk; ++bl) {
@@ -69,6 +68,7 @@ int main(int argc, char** argv) {
                    (h[bl * 16 + 1] - h[bl * 16]) * 0.01, (h[bl * 16 + 2] - h[bl * 16 + 1]) * 0.01, (h[bl * 16 + 3] - h[bl * 16 + 2]) * 0.01, (h[bl * 16 + 4] - h[bl * 16 + 3]) * 0.01,
                    (h[bl * 16 + 5] - h[bl * 16 + 4]) * 0.01, (h[bl * 16 + 6] - h[bl * 16 + 5]) * 0.01, (h[bl * 16 + 7] - h[bl * 16 + 6]) * 0.01);
         }
+#endif
     }
     return 0;
 }

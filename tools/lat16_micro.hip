@@ -1,4 +1,4 @@
-// Developer microbenchmark for conv_lat16_kernel (phase stamps). Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DVITS_PHASE_TIMING
+// Developer microbenchmark for conv_lat16_kernel (phase stamps with -DVITS_PHASE_TIMING). Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DVITS_PHASE_TIMING]
 //   -DCIN_=768 -DCOUT_=192 -DKT_=3 -DT_=128 tools/lat16_micro.hip -o tools/bin/lat16_micro
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -54,6 +54,7 @@ int main() {
             if (e != hipSuccess) printf("launch error %s\n", hipGetErrorString(e));
         }
         printf("tile %d: %.1f us best, %.1f us mean (cold weights)\n", tile, best * 1e3, sum / 5 * 1e3);
+#ifdef VITS_PHASE_TIMING
         if (tile == TILE_LAT16) {
             std::vector<unsigned long long> ph(8 * 65536);
             hipMemcpyFromSymbol(ph.data(), HIP_SYMBOL(vits_phase_buf), ph.size() * 8);
@@ -67,6 +68,7 @@ int main() {
             if (n) printf("  %d blocks, 10 ns ticks -> us: setup + A prefetch issue %.2f | fill %.2f | barrier %.2f | K loop %.2f ; first start -> last K end %.1f us\n", n, d[0] / n / 100, d[1] / n / 100,
                           d[2] / n / 100, d[3] / n / 100, (tmax - tmin) / 100.0);
         }
+#endif
     }
     return 0;
 }

@@ -32,6 +32,7 @@
 
 #include "kernel_common.h"
 #include "kernels.h"
+#include "phase_timing.h"
 
 // The kernel template is instantiated for ~40 (taps, dilation, tile, epilogue) combinations; one translation unit takes
 // minutes, so the Makefile compiles this file five times: VITS_CONV_PART 0 = host code + taps 1/2/5, 1 = taps 3, 2 = taps 7, 4 = grouped launch,
@@ -935,17 +936,7 @@ __global__ __launch_bounds__(256) void conv_lat16_kernel(const ConvParams p) {
     const int ncols = p.len_out ? p.len_out[b] : p.t_out;
     if (t0 >= ncols || len_in <= 0) return;
     const float* const pbias = p.bias_rows ? p.bias + p.bias_rs * p.bias_rows[b] : p.bias;  // (see conv_mfma_body)
-#ifdef VITS_PHASE_TIMING
-#define L16_STAMP(k)                                                                                      \
-    do {                                                                                                  \
-        if (tid == 0) {                                                                                   \
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);          \
-            if (lin < 65536) vits_phase_buf[8 * lin + (k)] = __builtin_amdgcn_s_memrealtime();            \
-        }                                                                                                 \
-    } while (0)
-#else
-#define L16_STAMP(k)
-#endif
+#define L16_STAMP(k) VITS_PHASE_STAMP(vits_phase_buf, 8, k)  // (tools/lat16_micro.hip)
     L16_STAMP(0);
     const int KT = p.kt_rt, dil = p.dil;
     const int cin_pad = p.nchunks * CK;

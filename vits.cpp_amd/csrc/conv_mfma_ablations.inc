@@ -7,66 +7,29 @@
 //     VAR_NOSTAGE        register-staged kernels without their global loads                       VITS_TAP_ROLLED / VITS_ZERO_OOB_NOROT  the round-2 / round-3 forms of two loops
 // Every hook expands to NOTHING unless its macro is defined: the product kernels are what conv_mfma.hip reads like without them (the object files are byte-identical
 // to the ones built from the in-line #ifdef blocks this file replaced in round 6).
-#ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/conv_micro.hip): per-block phase timestamps, 100 MHz clock
-__device__ unsigned long long vits_phase_buf[8 * 65536];  // [block][0..3] 100 MHz stamps, [4..5] shader clock around the K loop, [6..7] HW_ID / XCC_ID
-__device__ unsigned long long vits_prod_buf[4 * 65536];  // [block][0..3]: producer wave, shader cycles in issue / DMA wait / post-processing / barrier
-__device__ unsigned long long vits_chunk_buf[8 * 65536];  // [block][2c], [2c+1]: shader clock at the end of chunk c < 4 and behind its barrier
-#define VITS_STAMP(k)                                                                                               \
-    do {                                                                                                            \
-        if (tid == 0) {                                                                                             \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);                                            \
-            if (lin < 65536) {                                                                                      \
-                vits_phase_buf[8 * lin + (k)] = __builtin_amdgcn_s_memrealtime();                                   \
-                if ((k) == 1 || (k) == 2) vits_phase_buf[8 * lin + 3 + (k)] = __builtin_amdgcn_s_memtime();         \
-                if ((k) == 0) {                                                                                     \
-                    unsigned hw, xcc;                                                                               \
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                               \
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                             \
-                    vits_phase_buf[8 * lin + 6] = hw;                                                               \
-                    vits_phase_buf[8 * lin + 7] = xcc;                                                              \
-                }                                                                                                   \
-            }                                                                                                       \
-        }                                                                                                           \
-    } while (0)
-__device__ unsigned long long vits_epi_buf[8 * 65536];  // [block][0..6]: shader clock at the epilogue's entry, in front of its first sub-tile, behind each of (up to) four sub-tiles, at its end
-__device__ unsigned long long vits_wave_end[8 * 65536];  // [block][wave]: 100 MHz clock when wave 0..4 retires
-#define VITS_WSTAMP()                                                                                               \
-    do {                                                                                                            \
-        if (lane == 0) {                                                                                            \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);                                            \
-            if (lin < 65536) vits_wave_end[8 * lin + wid] = __builtin_amdgcn_s_memrealtime();                       \
-        }                                                                                                           \
-    } while (0)
-__device__ unsigned long long vits_wave_start[8 * 65536];  // [block][wave]: 100 MHz clock at the first instructions of wave 0..4; [5..7]: HW_ID of waves 0, 1, 4
-#define VITS_WSTART()                                                                                               \
-    do {                                                                                                            \
-        if (lane == 0) {                                                                                            \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);                                            \
-            if (lin < 65536) {                                                                                      \
-                vits_wave_start[8 * lin + wid] = __builtin_amdgcn_s_memrealtime();                                  \
-                if (wid == 0 || wid == 1 || wid == 4) {                                                             \
-                    unsigned hw;                                                                                    \
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                               \
-                    vits_wave_start[8 * lin + (wid == 0 ? 5 : wid == 1 ? 6 : 7)] = hw;                             \
-                }                                                                                                   \
-            }                                                                                                       \
-        }                                                                                                           \
-    } while (0)
-#define VITS_ESTAMP(k)                                                                                              \
-    do {                                                                                                            \
-        if (tid == 0) {                                                                                             \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);                                            \
-            if (lin < 65536) vits_epi_buf[8 * lin + (k)] = __builtin_amdgcn_s_memtime();                           \
-        }                                                                                                           \
-    } while (0)
-#else
-#define VITS_STAMP(k)
-#define VITS_ESTAMP(k)
-#define VITS_WSTAMP()
-#define VITS_WSTART()
-#endif
-
-
+// Per-block phase timestamps (tools/conv_micro.hip): the buffers, the plain and the extended stamp and the block-index guard are phase_timing.h's (included
+// by conv_mfma.hip); the producer, chunk, epilogue and wave stamps below are this kernel's own. A body's block is (bx, by, bz), its arguments.
+#define VITS_CONV_BLOCK (bx + gridDim.x * (by + gridDim.y * bz))
+VITS_PHASE_BUF(vits_phase_buf, 8);   // [block][0..3] 100 MHz stamps, [4..5] shader clock around the K loop, [6..7] HW_ID / XCC_ID
+VITS_PHASE_BUF(vits_prod_buf, 4);    // [block][0..3]: producer wave, shader cycles in issue / DMA wait / post-processing / barrier
+VITS_PHASE_BUF(vits_chunk_buf, 8);   // [block][2c], [2c+1]: shader clock at the end of chunk c < 4 and behind its barrier
+VITS_PHASE_BUF(vits_epi_buf, 8);     // [block][0..6]: shader clock at the epilogue's entry, in front of its first sub-tile, behind each of (up to) four sub-tiles, at its end
+VITS_PHASE_BUF(vits_wave_end, 8);    // [block][wave]: 100 MHz clock when wave 0..4 retires
+VITS_PHASE_BUF(vits_wave_start, 8);  // [block][wave]: 100 MHz clock at the first instructions of wave 0..4; [5..7]: HW_ID of waves 0, 1, 4
+#define VITS_STAMP(k) VITS_PHASE_STAMP_EXT(vits_phase_buf, 8, VITS_CONV_BLOCK, k, 3, 6)
+#define VITS_ESTAMP(k) VITS_PHASE_ROW(tid == 0, VITS_CONV_BLOCK, vits_epi_buf[8 * lin + (k)] = __builtin_amdgcn_s_memtime())
+#define VITS_CHUNK_STAMP(slot) VITS_PHASE_ROW(tid == 0 && c < 4, VITS_CONV_BLOCK, vits_chunk_buf[8 * lin + (slot)] = __builtin_amdgcn_s_memtime())
+#define VITS_WSTAMP() VITS_PHASE_ROW(lane == 0, VITS_CONV_BLOCK, vits_wave_end[8 * lin + wid] = __builtin_amdgcn_s_memrealtime())
+#define VITS_WSTART()                                                                          \
+    VITS_PHASE_ROW(lane == 0, VITS_CONV_BLOCK, {                                               \
+        vits_wave_start[8 * lin + wid] = __builtin_amdgcn_s_memrealtime();                     \
+        if (wid == 0 || wid == 1 || wid == 4) {                                                \
+            unsigned hw;                                                                       \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                   \
+            vits_wave_start[8 * lin + (wid == 0 ? 5 : wid == 1 ? 6 : 7)] = hw;                 \
+        }                                                                                      \
+    })
+#define VITS_PSTAMP_END() VITS_PHASE_ROW(lane == 0, VITS_CONV_BLOCK, for (int k = 0; k < 4; ++k) vits_prod_buf[4 * lin + k] = pt[k])
 #ifdef VITS_PHASE_TIMING
 #define VITS_PSTAMP_BEGIN()                     \
     unsigned long long pt[4] = {0, 0, 0, 0};    \
@@ -77,26 +40,9 @@ __device__ unsigned long long vits_wave_start[8 * 65536];  // [block][wave]: 100
         pt[k] += now - pprev;                                        \
         pprev = now;                                                 \
     } while (0)
-#define VITS_PSTAMP_END()                                                   \
-    do {                                                                    \
-        if (lane == 0) {                                                    \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);    \
-            if (lin < 65536)                                                \
-                for (int k = 0; k < 4; ++k) vits_prod_buf[4 * lin + k] = pt[k]; \
-        }                                                                   \
-    } while (0)
-#define VITS_CHUNK_STAMP(slot)                                                               \
-    do {                                                                                     \
-        if (tid == 0 && c < 4) {                                                             \
-            const unsigned lin = bx + gridDim.x * (by + gridDim.y * bz);                     \
-            if (lin < 65536) vits_chunk_buf[8 * lin + (slot)] = __builtin_amdgcn_s_memtime(); \
-        }                                                                                    \
-    } while (0)
 #else
 #define VITS_PSTAMP_BEGIN()
 #define PSTAMP(k)
-#define VITS_PSTAMP_END()
-#define VITS_CHUNK_STAMP(slot)
 #endif
 
 #ifdef VITS_ZERO_OOB_NOROT  // every row starts at outside-column 0 (the round-3 walk, 16-way LDS bank conflicts)

@@ -9,7 +9,7 @@ hipError_t Engine::run_dds(const DdsW& d, TensorRef x, TensorRef y, TensorRef p,
     const int H = hp.hidden;
     TensorRef none;
     int dil = 1;
-    // Each layer as ONE kernel (misc_kernels.hip dds_layer_kernel; bit-identical to the three launches below). A fused block reads a
+    // Each layer as ONE kernel (dds.hip dds_layer_kernel; bit-identical to the three launches below). A fused block reads a
     // halo of its neighbours' columns, so a layer never writes the buffer it reads: x -> y -> p -> ... -> x.
     const int n = hp.dds_layers;
     bool fuse = n >= 2 && !knobs.no_dds_fuse;

@@ -2,7 +2,7 @@
 // per output element, call the element function of include/vits_exact_math.h" — the same functions, operands and order of operations as the
 // test oracle's exact-order translation unit (oracle/, never linked here), compiled with floating-point contraction off (Makefile: -ffp-contract=off), so that the log-durations —
 // and with them the path's integer output, the durations (vits.cpp:996-1001) — are bit-identical on both sides. NOT a throughput path: the default
-// mode's kernels (conv_mfma.hip, misc_kernels.hip) are what the benchmark runs. Layout as everywhere in stage one: [batch][channel][time], time fastest.
+// mode's kernels (conv_mfma.hip, attention.hip, layer_norm.hip, dds.hip, spline.hip) are what the benchmark runs. Layout as everywhere in stage one: [batch][channel][time], time fastest.
 #include <hip/hip_runtime.h>
 
 #include "../../include/vits_exact_math.h"

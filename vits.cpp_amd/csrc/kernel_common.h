@@ -33,6 +33,13 @@ __device__ __forceinline__ float unpack16(unsigned short h) {
     if constexpr (BF) return __builtin_bit_cast(float, (unsigned)h << 16);
     else return (float)__builtin_bit_cast(_Float16, h);
 }
+// Q7 (custom-ops.h:684-690): in the 16-bit arithmetic modes every conv operand is rounded (nearest even) to fp16 / bf16; the
+// products are then exact in fp32. arith: 0 fp32, 1 bf16, 2 fp16 (VITS_ARITH_*). The VALU convolutions' form (dds.hip, vocoder_glue.hip).
+__device__ __forceinline__ float round_arith(float v, int arith) {
+    if (arith == 2) return (float)(_Float16)v;
+    if (arith == 1) return (float)(__bf16)v;
+    return v;
+}
 // v_mfma_f32_32x32x16_{f16,bf16} on two 16-byte operands (8 x 16 bit each)
 template <bool BF>
 __device__ __forceinline__ floatx16 mfma16(int4v a, int4v b, floatx16 c) {

@@ -491,11 +491,7 @@ hipError_t launch_to_group16(TensorRef x, const int* lens, int batch, int channe
 hipError_t launch_conv_post16(Ref16 x, const float* w, int cin, int k, TensorRef pre, TensorRef wave, const int* lens, int batch, int tmax, int arith, hipStream_t s,
                               int emit_lo = 0, const int* emit_hi = nullptr);
 
-// ---- small kernels ------------------------------------------------------------------------------------
-hipError_t launch_embed(const int* ids, int id_stride, const int* lens, const float* table, int hidden, float scale, TensorRef x, int batch, int tmax,
-                        hipStream_t s);
-// x[b][c][t] *= scale, or scales[b] when scales (device [B]) is given
-hipError_t launch_scale_rows(TensorRef x, int channels, float scale, const float* scales, int batch, int tmax, hipStream_t s);
+// ---- the non-GEMM kernels, one block per file --------------------------------------------------------------
 // EMULATED ggml lookup tables (INFERRED from upstream ggerganov/ggml of the reference's era, the maxilevi/ggml fork is
 // absent): device copies of the two 65536-entry fp16 tables ggml builds at init — gelu[i] = fp16(tanh-GELU(fp16 value i)), exp[i] =
 // fp16(expf(fp16 value i)) — built on the host with the C library (Engine::set_ggml_tables). Kernels that receive a non-null pointer route
@@ -504,10 +500,15 @@ struct GgmlTables {
     const uint16_t* gelu = nullptr;
     const uint16_t* exp = nullptr;
 };
+// ---- attention (attention.hip) ------------------------------------------------------------------------
 hipError_t launch_rel_attention(TensorRef q, TensorRef k, TensorRef v, const float* rel_k, const float* rel_v, TensorRef out, const int* lens, int batch,
                                 int heads, int head_dim, int tmax, int window, float q_scale, hipStream_t s, GgmlTables tabs = GgmlTables(), int force = 0);  // force: plan_rel_attention's
+// ---- LayerNorm over channels (layer_norm.hip) ---------------------------------------------------------
 hipError_t launch_add_layer_norm(TensorRef x, TensorRef res, const float* gamma, const float* beta, TensorRef y, const int* lens, int batch, int channels,
                                  int tmax, float eps, int post_gelu, TensorRef add_to, hipStream_t s, GgmlTables tabs = GgmlTables(), int force_tw = 0);  // force_tw: plan_add_layer_norm's
+// ---- the duration predictor's DDS block (dds.hip; its latency kernel: stage1_lat.hip) -----------------
+hipError_t launch_pointwise_from1(TensorRef z, int zc, const float* w, const float* bias, TensorRef cond, TensorRef y, const int* lens, int batch,
+                                  int channels, int tmax, hipStream_t s, int arith = 0);
 hipError_t launch_dds_depthwise(TensorRef x, TensorRef g, const float* w, const float* bias, const float* gamma, const float* beta, TensorRef y,
                                 const int* lens, int batch, int channels, int tmax, int k, int dil, float eps, hipStream_t s, int arith = 0,
                                 GgmlTables tabs = GgmlTables());
@@ -537,6 +538,7 @@ struct DdsLatCall {
 };
 bool dds_layer_lat_supported(const PackedConv& pw, int channels, int k, int dil);
 hipError_t launch_dds_layer_lat(const DdsLatCall& c, hipStream_t s);
+// ---- the deterministic duration predictor (dp_det.hip) ------------------------------------------------
 // The deterministic duration predictor (transformers VitsDurationPredictor, eval mode) as ONE kernel (dp_det.hip), fp32 in every arithmetic mode:
 //   x' = x + row (inside the utterance only; the speaker term, added ON LOAD), a1 = LN(relu(conv_1(x'))), a2 = LN(relu(conv_2(a1))), logw = proj(a2)
 // with a1 / a2 zero outside [0, len). conv_1 / conv_2: k taps, zero padding k / 2; proj: 1x1 to one channel. Bit for bit the un-fused sequence
@@ -562,12 +564,16 @@ hipError_t launch_dp_det(const DpDetCall& c, hipStream_t s);
 hipError_t launch_dp_det_unfused(const DpDetCall& c, TensorRef xp, TensorRef a, TensorRef b, hipStream_t s);
 // y[b][c][t] = x[b][c][t] + rows[row(b)][c] for t < lens[b] (nothing is written behind an utterance): the un-fused predictor's first step
 hipError_t launch_add_rows(TensorRef x, TensorRef y, const float* rows, int64_t row_rs, const int* row_idx, const int* lens, int batch, int channels, int tmax, hipStream_t s);
-hipError_t launch_pointwise_from1(TensorRef z, int zc, const float* w, const float* bias, TensorRef cond, TensorRef y, const int* lens, int batch,
-                                  int channels, int tmax, hipStream_t s, int arith = 0);
+// ---- the element-wise part of the duration predictor's flows (spline.hip) -----------------------------
 hipError_t launch_spline(TensorRef u, TensorRef z, int zc, const int* lens, int batch, int tmax, int bins, float tail, float inv_sqrt, int mode,
                          hipStream_t s, GgmlTables tabs = GgmlTables());
 hipError_t launch_affine(TensorRef z, int c_first, const float* translate, const float* log_scale, int sign, const int* lens, int batch, int tmax,
                          hipStream_t s);
+// Per-utterance prosody: launch_noise_dur, launch_scale_rows, launch_durations and launch_zp each take an optional device array next to their scalar
+// (scales / length_scales / noise_scales [B]: utterance b's value instead of the scalar; null = the scalar for every utterance, as before).
+hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, const float* scales, hipStream_t s);
+// x[b][c][t] *= scale, or scales[b] when scales (device [B]) is given
+hipError_t launch_scale_rows(TensorRef x, int channels, float scale, const float* scales, int batch, int tmax, hipStream_t s);
 // ---- exact-order stage one of the emulated-ggml mode (exact_stage1.hip; element functions: include/vits_exact_math.h) -----------------------
 hipError_t launch_exact_conv(TensorRef x, const float* w, const float* bias, TensorRef y, TensorRef res, const int* lens, int batch, int cin, int cout, int K, int dil, int pad_l,
                              int tmax, bool relu, const float* post_scale, hipStream_t s);
@@ -581,21 +587,23 @@ hipError_t launch_exact_attention(TensorRef q, TensorRef k, TensorRef v, const f
 hipError_t launch_exact_affine(TensorRef z, int c_first, float t0, float t1, float e0, float e1, const int* lens, int batch, int tmax, hipStream_t s);
 hipError_t launch_exact_spline(TensorRef z, int row, TensorRef u, float* res, float* inside, float* tmp, int stride, const int* lens, int batch, int tmax, int nb, float B,
                                float inv_sqrt, float constant, bool refmode, const uint16_t* exp_tab, hipStream_t s);
-// Per-utterance prosody: each of the three takes an optional device array next to its scalar (scales / length_scales / noise_scales [B]: utterance
-// b's value instead of the scalar; null = the scalar for every utterance, as before). launch_durations also takes optional override rows
-// ovr [B][tmax] (>= 0: the token's duration; -1: the prediction).
-hipError_t launch_noise_dur(TensorRef z, const int* lens, int batch, int tmax, uint64_t seed, const int* seed_off, float scale, const float* scales, hipStream_t s);
+// ---- stage one's glue (stage1_glue.hip) ---------------------------------------------------------------
+hipError_t launch_embed(const int* ids, int id_stride, const int* lens, const float* table, int hidden, float scale, TensorRef x, int batch, int tmax,
+                        hipStream_t s);
+hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
+hipError_t launch_fill_rows(TensorRef x, int channels, float v, int batch, int tmax, hipStream_t s);
+// (per-utterance prosody: see launch_noise_dur.) launch_durations also takes optional override rows ovr [B][tmax] (>= 0: the token's duration; -1: the prediction).
 hipError_t launch_durations(TensorRef logw, int c, const int* lens, int batch, int tmax, float length_scale, const float* length_scales, const int* ovr, int fixed,
                             float* dur, int* cum, int* frames, int* stage_lens, int n_stage, const int* stage_mul, const int* stage_add, hipStream_t s,
                             bool exact = false);
 hipError_t launch_zp(TensorRef mean, TensorRef logvar, const int* cum, int cum_stride, const int* tok_lens, const int* frames, TensorRef noise, int noise_kind,
                      uint64_t seed, const int* seed_off, float noise_scale, const float* noise_scales, TensorRef zp, int batch, int channels, int lmax, hipStream_t s);
-hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 // one segment of the effective-bias table of a multi-speaker model (built once at load): row 0 (speaker -1) = bias, row 1 + s =
 // bias + (cond_w . emb[s] + cond_b) for the n channels of the segment; cond_w is the conditioning 1x1 conv [n][E], emb [n_spk][E]
 hipError_t launch_speaker_bias(const float* bias, const float* cond_w, const float* cond_b, const float* emb, int n, int E, int n_spk, float* table,
                                int64_t row_stride, hipStream_t s);
-// rows of an effective-bias table for voices registered at run time (voices.hip): ONE launch for every segment of the table and all n_voices new rows.
+// ---- voices registered at run time (voices.hip) -------------------------------------------------------
+// rows of an effective-bias table for voices registered at run time: ONE launch for every segment of the table and all n_voices new rows.
 // A segment = the n channels at float offset `off` of a table row, conditioned by rows w [n][E] / cb [n] of a 1x1 conv (device pointers); tile0 = the
 // sum of voice_seg_tiles(n) over the segments before it, `tiles` the sum over all. Row row_first + v = row 0 + (w . emb[v] + cb) in speaker_bias_kernel's
 // order of operations. The table must hold row_first + n_voices rows. Any n_voices: the launcher walks slices of the grid's y limit; few voices take a
@@ -609,9 +617,13 @@ struct VoiceSeg {
 int voice_seg_tiles(int n);
 hipError_t launch_voice_rows(const VoiceSeg* segs, int nseg, int tiles, const float* emb, int n_voices, int E, float* table, int64_t row_stride, int row_first,
                              hipStream_t s);
+// ---- around the vocoder's convolutions, and the delivery's int16 PCM (vocoder_glue.hip) ---------------
 hipError_t launch_rb_sum3_std(TensorRef y0, TensorRef y1, TensorRef y2, TensorRef out, int channels, const int* lens, int batch, int tmax, float scale, int scale_div, int post_act,
                               float post_slope, hipStream_t s);  // fp32 [b][c][t]: ((y0 + y1) [+ y2]) scaled [+ leaky_relu]: side-by-side resblocks of the fp32 path (small grids)
-hipError_t launch_fill_rows(TensorRef x, int channels, float v, int batch, int tmax, hipStream_t s);
+hipError_t launch_conv_post(TensorRef x, const float* w, int cin, int k, float slope, TensorRef pre_tanh, TensorRef wave, const int* lens, int batch,
+                            int tmax, hipStream_t s, int emit_lo = 0, const int* emit_hi = nullptr, int arith = 0);
+// fp32 -> int16 PCM rows on the device (test/main.cpp:31-33); lens (device, optional) limits each row
+hipError_t launch_pcm16(const float* src, int64_t src_stride, int16_t* dst, int64_t dst_stride, const int64_t* lens, int rows, int64_t cols, hipStream_t s);
 
 // ---- voice conversion front end (spectrogram.hip) -------------------------------------------------------------------------------
 // Linear magnitude spectrogram (VITS spectrogram_torch, center = False): frame t of utterance b covers samples [t hop - pad, t hop - pad + n_fft)
@@ -660,10 +672,6 @@ size_t align_mas_bits_words(int tmax, int lmax);
 bool align_mas_bits_in_lds(int tmax, int lmax);
 hipError_t launch_align_logp(const AlignCall& c, hipStream_t s);
 hipError_t launch_align_mas(const AlignCall& c, hipStream_t s);
-// fp32 -> int16 PCM rows on the device (test/main.cpp:31-33); lens (device, optional) limits each row
-hipError_t launch_pcm16(const float* src, int64_t src_stride, int16_t* dst, int64_t dst_stride, const int64_t* lens, int rows, int64_t cols, hipStream_t s);
-hipError_t launch_conv_post(TensorRef x, const float* w, int cin, int k, float slope, TensorRef pre_tanh, TensorRef wave, const int* lens, int batch,
-                            int tmax, hipStream_t s, int emit_lo = 0, const int* emit_hi = nullptr, int arith = 0);
 
 // ---- sample-rate conversion (resample.hip; the filter: include/vits.h vits_resample_plan, DESIGN.md §8 "Any sample rate") ----------------
 // fi -> fo as a rational L / M polyphase filter: output j of a row sits at input time j M / L; q = j M (int64), n_c = q / L, p = q % L,

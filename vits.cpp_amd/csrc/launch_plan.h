@@ -1,5 +1,5 @@
 // launch_plan.h — the launch policy of the fused kernels — the vocoder's (rbpair16.hip, rbblock16.hip, rbpair32.hip, rbblock32.hip, convt16.hip), the flow's
-// (wavenet32.hip) and stage one's attention, LayerNorm and DDS layers (misc_kernels.hip, stage1_lat.hip) — as plain host arithmetic, beside conv_plan.h: one constexpr geometry function per family, read by the kernel body AND by the planner; which instantiations exist; one
+// (wavenet32.hip) and stage one's attention, LayerNorm and DDS layers (attention.hip, layer_norm.hip, dds.hip, stage1_lat.hip) — as plain host arithmetic, beside conv_plan.h: one constexpr geometry function per family, read by the kernel body AND by the planner; which instantiations exist; one
 // plan per launch (launch_plan.cpp). No kernels, no HIP calls: the launchers copy fields and launch what the plan says; tests/launch_plan_dump.cpp links
 // launch_plan.o alone and freezes the policy as a table. The knobs of these families are read in launch_plan.cpp and nowhere else.
 #pragma once

@@ -26,6 +26,7 @@
 #include "../../include/vits.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "phase_timing.h"
 
 namespace vits {
 
@@ -61,18 +62,8 @@ struct RbBlockParams {
     int nt;  // STREAM: tiles a block walks (its segment = W - 2 H + (nt - 1) (W - H) output columns)
 };
 
-#ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/rb16_micro.hip)
-__device__ unsigned long long vits_rbb_phase[16 * 65536];
-#define RBB_STAMP(k)                                                                                            \
-    do {                                                                                                        \
-        if (threadIdx.x == 0) {                                                                                 \
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;                                           \
-            if (lin < 65536) vits_rbb_phase[16 * lin + (k)] = __builtin_amdgcn_s_memrealtime();                 \
-        }                                                                                                       \
-    } while (0)
-#else
-#define RBB_STAMP(k)
-#endif
+VITS_PHASE_BUF(vits_rbb_phase, 16);  // developer instrumentation (tools/rbb_micro.hip)
+#define RBB_STAMP(k) VITS_PHASE_STAMP(vits_rbb_phase, 16, k)
 
 // Block = NSTRIP column strips x C / (32 MRW) row groups of waves; wave (strip, rg) owns the MRW row tiles [MRW rg, MRW rg + MRW) (32 rows each)
 // of the NRW 32-column tiles of its strip.

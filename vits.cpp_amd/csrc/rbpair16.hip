@@ -21,31 +21,13 @@
 #include "../../include/vits.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "phase_timing.h"
 
 namespace vits {
 
-#ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/rb16_micro.hip): per-block phase timestamps
-__device__ unsigned long long vits_rb_phase[16 * 65536];  // [block][0..6] 100 MHz stamps, [7] HW_ID, [8] XCC_ID, [9..10] shader clock around conv1
-#define RB_STAMP(k)                                                                                     \
-    do {                                                                                                \
-        if (threadIdx.x == 0) {                                                                         \
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;                                   \
-            if (lin < 65536) {                                                                          \
-                vits_rb_phase[16 * lin + (k)] = __builtin_amdgcn_s_memrealtime();                       \
-                if ((k) == 1 || (k) == 2) vits_rb_phase[16 * lin + 8 + (k)] = __builtin_amdgcn_s_memtime(); \
-                if ((k) == 0) {                                                                         \
-                    unsigned hw, xcc;                                                                   \
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                   \
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                 \
-                    vits_rb_phase[16 * lin + 7] = hw;                                                   \
-                    vits_rb_phase[16 * lin + 8] = xcc;                                                  \
-                }                                                                                       \
-            }                                                                                           \
-        }                                                                                               \
-    } while (0)
-#else
-#define RB_STAMP(k)
-#endif
+// developer instrumentation (tools/rb16_micro.hip): per-block phase timestamps
+VITS_PHASE_BUF(vits_rb_phase, 16);  // [block][0..6] 100 MHz stamps, [7] HW_ID, [8] XCC_ID, [9..10] shader clock around conv1
+#define RB_STAMP(k) VITS_PHASE_STAMP_EXT(vits_rb_phase, 16, VITS_PHASE_BLOCK, k, 8, 7)
 
 struct RbPairParams {
     const uint16_t* x;  // leaky_relu(y), rounded: group layout [b][C/8][x_ts][8]

@@ -116,7 +116,7 @@ hipError_t launch_spectrogram(const SpectrogramCall& c, hipStream_t s) {
 }
 
 // z_q[b][c][t] = mean + (eps * eps_scale) * exp(log_std) for t < frames[b] (VitsPosteriorEncoder.forward), eps drawn like prior sampling's (zp_kernel,
-// misc_kernels.hip: the counter stream VITS_STREAM_NOISE_PRIOR, index c * L + t, or the explicit / reference tensor). flip = 1 writes
+// stage1_glue.hip: the counter stream VITS_STREAM_NOISE_PRIOR, index c * L + t, or the explicit / reference tensor). flip = 1 writes
 // channel c to row F - 1 - c: the physical layout of the forward flow's input when the flow has an odd number of layers (engine_flow.cpp).
 __global__ __launch_bounds__(256) void posterior_sample_kernel(const float* mean, int64_t m_bs, int m_cs, const float* logstd, int64_t v_bs, int v_cs,
                                                                const int* frames, const float* noise, int64_t n_bs, int n_cs, int noise_kind, uint64_t seed,

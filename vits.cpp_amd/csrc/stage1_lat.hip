@@ -8,7 +8,7 @@
 //   * 16 tokens per block instead of 32 (twice the blocks), twelve waves instead of eight;
 //   * the element-wise phases are element-parallel: a thread owns FOUR elements of one token column instead of twelve (each gelu is an erff);
 //     only the LayerNorm partial sums keep their 16 channel groups, and every sum keeps its order — channel group g adds channels g, g + 16, ...
-//     in ascending order, the groups are combined in ascending order — so every float is the one dds_layer_kernel (misc_kernels.hip) computes;
+//     in ascending order, the groups are combined in ascending order — so every float is the one dds_layer_kernel (dds.hip) computes;
 //   * the 1x1 conv runs on v_mfma_f32_16x16x4_f32 tiles (one 16-row tile per wave, 48 dependent MFMAs instead of 96 twice as long): bit for bit
 //     the same sequential fmaf chain over the input channels as v_mfma_f32_32x32x2_f32 (tools/mfma_bits.hip), from the layer's second weight copy in
 //     that instruction's operand order (repack_conv_weights_l16, conv_mfma.hip), all 12 quads of a wave fetched at the kernel's first instruction;

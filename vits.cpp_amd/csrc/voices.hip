@@ -1,5 +1,5 @@
 // voices.hip — rows of an effective-bias table for speaker embeddings registered at run time (include/vits.h vits_model_add_voices;
-// DESIGN.md §8 "Custom voices"). speaker_bias_kernel (misc_kernels.hip) builds the file's rows at load, one launch per segment and one thread
+// DESIGN.md §8 "Custom voices"). speaker_bias_kernel (stage1_glue.hip) builds the file's rows at load, one launch per segment and one thread
 // per (row, channel) walking its weight row with stride-E loads; registration is a serving-path call, so all segments of a table and all new
 // rows go in ONE launch here, with the weights read coalesced.
 //

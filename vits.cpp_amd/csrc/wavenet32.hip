@@ -20,6 +20,7 @@
 #include "../../include/vits.h"
 #include "kernel_common.h"
 #include "kernels.h"
+#include "phase_timing.h"
 
 namespace vits {
 
@@ -263,18 +264,8 @@ __device__ __forceinline__ uint16_t wn_round16(float v) {
     }
 }
 
-#ifdef VITS_PHASE_TIMING  // developer instrumentation (tools/wn16_micro.hip)
-__device__ unsigned long long vits_wn_phase[8 * 65536];
-#define WN_STAMP(k)                                                                                      \
-    do {                                                                                                 \
-        if (threadIdx.x == 0) {                                                                          \
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;                                    \
-            if (lin < 65536) vits_wn_phase[8 * lin + (k)] = __builtin_amdgcn_s_memrealtime();            \
-        }                                                                                                \
-    } while (0)
-#else
-#define WN_STAMP(k)
-#endif
+VITS_PHASE_BUF(vits_wn_phase, 8);  // developer instrumentation (tools/wn16_micro.hip)
+#define WN_STAMP(k) VITS_PHASE_STAMP(vits_wn_phase, 8, k)
 
 // NCW: 32-frame column tiles per wave. 1 = twelve waves, one (channel group, column tile) each; 2 = six waves that own BOTH column tiles of
 // their channel group. The gated conv of a block is bound by the weight-fragment traffic through the CU's vector memory path: twelve waves x
