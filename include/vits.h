@@ -778,6 +778,65 @@ VITS_API int vits_model_get_conversion_prosody(const vits_model* model, float* r
 VITS_API int vits_model_set_conversion_ratios(vits_model* model, const float* rates, const float* pitches, int32_t n);
 VITS_API int64_t vits_model_last_tempo(vits_model* model, int64_t* dst, size_t cap);
 
+/* ---- a stated duration: the length scale fitted to a target frame count, on the device ---------------------------------------------------------
+ * A dubbing, subtitle or prompt slot gives a sentence a time. VITS has the lever, the duration predictor's length scale, d = ceil(exp(logw) s), but the
+ * sum of those steps cannot be inverted from outside the call. The fit finds the scale inside stage one, directly in front of the durations kernel.
+ *
+ * The definition. IEEE fp32 multiply, ceil and integer arithmetic only: device, host (vits_fit_host) and any restatement (tests/fit_ref.py) agree on
+ * every integer. A group is a set of utterances of one call, taken in batch order, each with its tokens in order.
+ *   Token t has e_t = expf(logw_t), the value the durations kernel evaluates, and fixed_t: the caller's duration_override, or -1.
+ *   The group has a target F in [1, 2^22] frames and the call the rate limits 0.1 <= min_rate <= max_rate <= 10.
+ *   A free token lasts c_t(s) = (int64) min(ceilf(e_t s), 16777216.f) frames at the scale s; a fixed token c_t = fixed_t. n(s) = sum c_t(s) in int64:
+ *     non-decreasing in the bit pattern of a positive s.
+ *   Scale limits, the engine's own expression for a rate: s_lo = (float)(1.0 / (double)max_rate), s_hi = (float)(1.0 / (double)min_rate).
+ *   If n(s_lo) > F: s* = s_lo, status 1 (the text does not fit even at the fastest rate allowed; the frames exceed the target).
+ *   Else if n(s_hi) <= F: s* = s_hi, status 0 when n = F and 2 otherwise (the frames fall short of the target).
+ *   Otherwise bisect on the unsigned bit patterns between s_lo and s_hi (lo, hi; mid = lo + (hi - lo) / 2; n(mid) <= F moves lo, else hi; until
+ *     hi - lo = 1): s* = the largest float with n(s*) <= F, in at most 26 steps on the full range.
+ *   Remainder: s+ = the next float after s*, R = F - n(s*) >= 0; non-zero only where several tokens step at the same float, as with equal logw. The
+ *     R frames go to the free tokens in (utterance, token) order, token t receiving min(c_t(s+) - c_t(s*), what is left). n(s+) > F, so this ends
+ *     with sum d = F: status 0.
+ *   Per token d_t = c_t(s*) plus its share of the remainder; per group {F, sum d, s*, R, status}.
+ * A clamped group (status 1 or 2, or 0 at s_hi) has R = 0 and the durations of a speaking_rates call at max_rate or min_rate.
+ *
+ * In a call. vits_model_set_fit(model, target_frames, groups, n, min_rate, max_rate) states the fit of the NEXT call on the handle (arrays copied at once):
+ * groups[b] in [0, n) is the group of utterance b, NULL = utterance b is its own group; target_frames[g] is the target of group g, 0 = the group is not
+ * fitted and its utterances run as always; n must be the call's batch. NULL with n = 0 drops a pending fit. vits_model_set_fit_total(model,
+ * total_frames, min_rate, max_rate): the next call's utterances form ONE group, whatever their number: a whole text at one tempo in a stated time. The
+ * argument shape is checked by the setter; the values by the call that takes them, whose message names the group. vits_process_opts keeps its size:
+ * like a pitch, the fit is stated on the handle. Exactly the calls that take the ratios of vits_model_set_pitch_ratios take it, at the same moment,
+ * and it is gone when that call returns, whether it succeeded or not. vits_model_process, _process_ids, _process_batch, _submit_batch / _wait (bit
+ * for bit what _process_batch gives) and _process_joined use it; vits_model_speak uses the total form and refuses the per-group form, as it refuses
+ * per-utterance arrays; conversion and alignment, which predict no durations, refuse it.
+ * The fit writes the override rows the durations kernel then reads: the call is, bit for bit, the same call with duration_override = its own
+ * durations_out, and nothing behind stage one knows that a fit happened. Taken with frames_only, durations_out, duration_override (those tokens stay
+ * fixed), speakers and voices, both duration predictors, every arithmetic mode and scope, vocoder_chunk_frames and on_chunk. A fitted utterance's
+ * speaking rate is the fit's result: the model-level rate and speaking_rates[b] are validated as always and not used for that utterance.
+ * A call that fits is never split across the front-end stream inside the call (a group stays in one launch); its bits are the unsplit call's.
+ * frames[] stays max(1, sum d) per utterance, as with any duration_override: a member of a larger group whose tokens are ALL fixed at 0 still reports (and
+ * is spoken as) one frame, so the summed frames[] of such a group exceed F by one per such member while vits_model_last_fit reports sum d = F.
+ * Refused before anything is queued, each with a message: fixed_duration > 0; vits_model_set_ggml_tables(model, 1), whose duration is not exp x scale;
+ * async; a fitted utterance with a pitch ratio other than 1 (the varispeed's stretch and the fit both own the length scale); a target outside [1,
+ * 2^22]; rates outside the range; n different from the batch.
+ * A target counts spoken frames only: gaps, trimmed edges and pads of a joined call are the caller's to subtract. vits_model_fit_frames(model,
+ * seconds) is the largest L with L hop + sadd <= seconds x the model's rate (the frames-to-samples rule of INTEGRATION.md §5, in the model's mode), at
+ * least 1; -1: model NULL or seconds not finite.
+ * Tap "fit_exp" [1][T] is e. vits_model_last_fit writes double [B][6] = {group, F, sum d of the group, s*, R, status} per utterance of the most recently
+ * completed call (cap >= 6 B; an utterance whose group was not fitted: F = 0, status -1), 0 rows when it fitted nothing; returns the number of rows,
+ * -1: model NULL. With nothing set no kernel is queued and no scratch is taken: every bit and vits_model_weight_bytes are what they were.
+ *
+ * Host only, no device needed. vits_fit_host: e and fixed (optional) host [batch][t_stride], lens [batch] (optional: t_stride each), groups [batch]
+ * (optional), target_frames [batch] by group -> dur_out int32 [batch][t_stride] (d_t of a fitted utterance's tokens, fixed_t of every other token, -1
+ * behind every length) and group_rows_out double [batch][5] = {F, sum d, s*, R, status} by group (status -1: not fitted, or no utterance names the
+ * group). 0, or -1 + message: a null argument, an empty batch, a length outside [0, t_stride], a fixed value below -1 or above 2^24, a group outside
+ * [0, batch), a target outside [1, 2^22] and not 0, rates that are not finite or not 0.1 <= min_rate <= max_rate <= 10. */
+VITS_API int vits_fit_host(int32_t batch, int32_t t_stride, const float* e, const int32_t* fixed, const int32_t* lens, const int32_t* groups,
+                           const int64_t* target_frames, float min_rate, float max_rate, int32_t* dur_out, double* group_rows_out);
+VITS_API int vits_model_set_fit(vits_model* model, const int64_t* target_frames, const int32_t* groups, int32_t n, float min_rate, float max_rate);
+VITS_API int vits_model_set_fit_total(vits_model* model, int64_t total_frames, float min_rate, float max_rate);
+VITS_API int64_t vits_model_fit_frames(const vits_model* model, double seconds);
+VITS_API int64_t vits_model_last_fit(vits_model* model, double* dst, size_t cap);
+
 /* Block until everything queued by this model has finished. */
 VITS_API int vits_model_sync(vits_model* model);
 
@@ -1235,6 +1294,14 @@ VITS_API int vits_op_spline(int32_t batch, int32_t t, int32_t t_stride, int32_t 
 VITS_API int vits_op_durations(int32_t batch, int32_t rows, int32_t row, int32_t t_stride, const float* logw, const int32_t* lens, float length_scale,
                                const float* length_scales, const int32_t* ovr, int32_t fixed, int32_t n_stage, const int32_t* stage_mul,
                                const int32_t* stage_add, float* dur, int32_t* cum, int32_t* frames, int32_t* stage_lens);
+
+/* The fit kernel ("a stated duration"; launch_fit_durations) on caller-supplied log-durations: logw host [batch][rows][t_stride], row `row` is read on
+ * [0, lens[b]) and staged with NaN behind it; fixed [batch][t_stride] (optional) the override rows, groups [batch] (optional: utterance b is group b),
+ * target_frames [batch] by group (0: not fitted). Outputs: e_out [batch][t_stride] = expf(logw) on [0, lens[b]) (the output fill behind it), dur_out
+ * [batch][t_stride] and group_rows_out double [batch][5] as vits_fit_host writes them. Refused like vits_fit_host, before the first device call. */
+VITS_API int vits_op_fit_durations(int32_t batch, int32_t rows, int32_t row, int32_t t_stride, const float* logw, const int32_t* lens, const int32_t* fixed,
+                                   const int32_t* groups, const int64_t* target_frames, float min_rate, float max_rate, float* e_out, int32_t* dur_out,
+                                   double* group_rows_out);
 
 /* The kernels between the conv families at operator level. Host arrays in, host arrays out; inputs are staged with 0xFF bytes (NaN) behind every utterance's
  * length and between a row's extent and its device pitch, outputs hold the byte of vits_op_set_output_fill wherever no kernel writes. Each runs the engine's

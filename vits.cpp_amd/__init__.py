@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "vits_model_set_pitch", "vits_model_get_pitch", "vits_model_set_pitch_ratios", "vits_model_last_pitch",
     "vits_tempo_plan", "vits_tempo_host", "vits_op_tempo",
     "vits_model_set_conversion_prosody", "vits_model_get_conversion_prosody", "vits_model_set_conversion_ratios", "vits_model_last_tempo",
+    "vits_fit_host", "vits_op_fit_durations", "vits_model_set_fit", "vits_model_set_fit_total", "vits_model_fit_frames", "vits_model_last_fit",
     "vits_join_plan", "vits_join_host", "vits_op_join", "vits_split_sentences", "vits_model_process_joined", "vits_model_last_joins", "vits_model_speak",
     "vits_model_duration_predictor_kind", "vits_op_duration_predictor", "vits_op_resblock", "vits_op_resblock_plan",
     "vits_op_flow_coupling", "vits_op_flow_coupling_plan", "vits_op_upsample16", "vits_op_upsample16_plan",
@@ -420,6 +421,18 @@ def lib():
     L.vits_model_set_conversion_ratios.argtypes = [vp, vp, vp, i32]
     L.vits_model_last_tempo.restype = i64
     L.vits_model_last_tempo.argtypes = [vp, vp, sz]
+    L.vits_fit_host.restype = i32
+    L.vits_fit_host.argtypes = [i32, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp]
+    L.vits_op_fit_durations.restype = i32
+    L.vits_op_fit_durations.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
+    L.vits_model_set_fit.restype = i32
+    L.vits_model_set_fit.argtypes = [vp, vp, vp, i32, C.c_float, C.c_float]
+    L.vits_model_set_fit_total.restype = i32
+    L.vits_model_set_fit_total.argtypes = [vp, i64, C.c_float, C.c_float]
+    L.vits_model_fit_frames.restype = i64
+    L.vits_model_fit_frames.argtypes = [vp, C.c_double]
+    L.vits_model_last_fit.restype = i64
+    L.vits_model_last_fit.argtypes = [vp, vp, sz]
     L.vits_op_tempo.restype = i32
     L.vits_op_tempo.argtypes = [i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, i64]
     L.vits_model_last_edges.restype = i64
@@ -911,6 +924,59 @@ class Model:
             raise VitsError(last_error())
         return out
 
+    # -- a stated duration: the length scale fitted to a target frame count (vits_model_set_fit) ---------------------------------------
+    def set_fit(self, targets=None, groups=None, min_rate=0.1, max_rate=10.0):
+        """vits_model_set_fit: the fit of the NEXT call on this handle (None drops what was given). targets: int64 [n], one target in frames per group (0: the
+        group is not fitted); groups: int32 [n], the group of every utterance (None: utterance b is group b); n must be that call's batch. The fit= keyword of
+        process_batch, submit_batch and process_joined does this."""
+        t = None if targets is None else np.ascontiguousarray(targets, dtype=np.int64).ravel()
+        g = None if groups is None or t is None else np.ascontiguousarray(groups, dtype=np.int32).ravel()
+        if g is not None and g.size != t.size:
+            raise ValueError("groups needs one entry per target")
+        if lib().vits_model_set_fit(self._h, _ptr(t), _ptr(g), 0 if t is None else t.size, float(min_rate), float(max_rate)) != 0:
+            raise VitsError(last_error())
+
+    def set_fit_total(self, frames, min_rate=0.1, max_rate=10.0):
+        """vits_model_set_fit_total: the NEXT call's utterances form one group that lasts `frames` frames, whatever their number (what speak takes)"""
+        if lib().vits_model_set_fit_total(self._h, int(frames), float(min_rate), float(max_rate)) != 0:
+            raise VitsError(last_error())
+
+    def fit_frames(self, seconds):
+        """vits_model_fit_frames: the largest frame count whose samples fit into `seconds` at the model's rate, at least 1"""
+        n = lib().vits_model_fit_frames(self._h, float(seconds))
+        if n < 0:
+            raise VitsError(last_error())
+        return int(n)
+
+    def _with_fit(self, fit, c_call):
+        """The fit= keyword of a call: None gives nothing; an int is set_fit_total's frames; a dict holds set_fit's or set_fit_total's keywords (targets or
+        frames, groups, min_rate, max_rate). Runs c_call() with the fit given to the handle and returns what it returns. Whatever happens, no fit given here is
+        left on the handle for a later call."""
+        if fit is None:
+            return c_call()
+        kw = dict(fit) if isinstance(fit, dict) else {"frames": fit}
+        if "frames" in kw:
+            self.set_fit_total(**kw)
+        else:
+            self.set_fit(**kw)
+        try:
+            return c_call()
+        finally:
+            self.set_fit(None)
+
+    def last_fit(self):
+        """vits_model_last_fit: float64 [B, 6] = (group, F, sum d of the group, s*, R, status) per utterance of the most recently completed call, or None when
+        it fitted nothing"""
+        n = lib().vits_model_last_fit(self._h, None, 0)
+        if n < 0:
+            raise VitsError(last_error())
+        if n == 0:
+            return None
+        out = np.zeros((n, 6), np.float64)
+        if lib().vits_model_last_fit(self._h, _ptr(out), out.size) != n:
+            raise VitsError(last_error())
+        return out
+
     # -- a conversion's rate and pitch: the model-level values (vits_model_set_conversion_prosody) ------------------------------------
     @property
     def conversion_prosody(self):
@@ -1152,7 +1218,7 @@ class Model:
                       noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False, out_device=None,
                       out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False, noise_seed_offsets=None, keep_pcm=True,
                       speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None, durations_out=None,
-                      pitch_ratio=None):
+                      pitch_ratio=None, fit=None):
         """ids: int32 [B, id_stride]. Returns (list of per-utterance PCM arrays or None, lengths, frames).
         vocoder_chunk_frames > 0 runs the vocoder window by window (bit-identical PCM, bounded activations);
         on_chunk(utt, offset, pcm ndarray) is then called as each window's samples reach the host (return True to abort).
@@ -1160,7 +1226,9 @@ class Model:
         speaking_rate / noise_scale / noise_scale_duration: a scalar for the whole batch or one value per utterance (None = the model values);
         duration_override: int32 [B, id_stride] (>= 0: the token's frames, -1: the prediction); durations_out: a caller-owned int32 [B, id_stride]
         array that receives every token's frames. pitch_ratio: a scalar or one ratio per utterance in [0.5, 2] (pitch_ratio(semitones); None = the
-        model value, set_pitch): the utterance is spoken slower by it and played back faster by it, on the device."""
+        model value, set_pitch): the utterance is spoken slower by it and played back faster by it, on the device. fit: the frames the whole batch lasts as one
+        group (an int), or a dict of set_fit's keywords (targets, groups, min_rate, max_rate) or set_fit_total's (frames, min_rate, max_rate): the length scale is
+        fitted on the device; last_fit() reads the result."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         if ids.ndim == 1:
             ids = ids[None, :]
@@ -1171,7 +1239,8 @@ class Model:
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
         cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
-        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_process_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), C.byref(res))) != 0:
+        call = lambda: lib().vits_model_process_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), C.byref(res))
+        if self._with_fit(fit, lambda: self._with_pitch(pitch_ratio, B, call)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1181,9 +1250,9 @@ class Model:
     def _joined_opts(B, stride, mode=MODE_DEFAULT, noise_kind=NOISE_COUNTER, noise_seed=4321, noise_dur=None, noise_prior=None, fixed_duration=0, collect_taps=False,
                      out_device=None, out_device_stride=0, skip_host_copy=False, async_=False, vocoder_chunk_frames=0, on_chunk=None, frames_only=False,
                      noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None, noise_scale_duration=None, duration_override=None,
-                     durations_out=None, pitch_ratio=None):
+                     durations_out=None, pitch_ratio=None, fit=None):
         """the options of process_batch's keywords (what a joined call refuses travels too, so that the library says why) -> (opts, keep, cb_error).
-        pitch_ratio is no field of the options: the caller gives it to the handle (Model._with_pitch)"""
+        pitch_ratio and fit are no fields of the options: the caller gives them to the handle (Model._with_pitch, Model._with_fit)"""
         o, keep = _opts(B, mode, noise_kind, noise_seed, noise_dur, noise_prior, fixed_duration, collect_taps, out_device, out_device_stride, skip_host_copy,
                         async_, vocoder_chunk_frames, frames_only, noise_seed_offsets, speaker_ids)
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
@@ -1205,8 +1274,8 @@ class Model:
                 raise ValueError("%s needs one entry per utterance" % name)
         o, keep, cb_error = self._joined_opts(B, stride, **kw)
         res = BatchResult()
-        if self._with_pitch(kw.get("pitch_ratio"), B,
-                            lambda: lib().vits_model_process_joined(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), _ptr(tr), _ptr(gp), C.byref(res))) != 0:
+        call = lambda: lib().vits_model_process_joined(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o), _ptr(tr), _ptr(gp), C.byref(res))
+        if self._with_fit(kw.get("fit"), lambda: self._with_pitch(kw.get("pitch_ratio"), B, call)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1225,7 +1294,9 @@ class Model:
         res = BatchResult()
         raw = None if text is None else text.encode("utf-8")
         # (given ratios are refused by the library: one per utterance, and the text decides how many there are)
-        if self._with_pitch(kw.get("pitch_ratio"), max(1, np.size(kw.get("pitch_ratio"))), lambda: lib().vits_model_speak(self._h, raw, C.byref(so), C.byref(res))) != 0:
+        call = lambda: lib().vits_model_speak(self._h, raw, C.byref(so), C.byref(res))
+        # (so is the per-group form of a fit; the total form, fit=frames, is what a whole text takes)
+        if self._with_fit(kw.get("fit"), lambda: self._with_pitch(kw.get("pitch_ratio"), max(1, np.size(kw.get("pitch_ratio"))), call)) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1268,6 +1339,7 @@ class Model:
             raise ValueError("lengths needs one entry per utterance")
         sp = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,))) for v in (src, tgt)]
         pitch_ratio = refused.pop("pitch_ratio", None)
+        fit = refused.pop("fit", None)
         fields, keep = _refused_fields(refused, B)
         o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, out_device=out_device,
                         out_device_stride=out_device_stride, skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames,
@@ -1278,7 +1350,7 @@ class Model:
         cb_error = _chunk_sink(o, on_chunk)
         res = BatchResult()
         call = lambda: lib().vits_model_convert_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(sp[0]), _ptr(sp[1]), C.byref(o), C.byref(res))
-        if self._with_conversion_ratios(vc_rate, vc_pitch, B, lambda: self._with_pitch(pitch_ratio, B, call)) != 0:
+        if self._with_fit(fit, lambda: self._with_conversion_ratios(vc_rate, vc_pitch, B, lambda: self._with_pitch(pitch_ratio, B, call))) != 0:
             if cb_error:
                 raise cb_error[0]
             raise VitsError(last_error())
@@ -1322,6 +1394,7 @@ class Model:
         own = {k: refused.pop(k) for k in ("out_device", "skip_host_copy", "vocoder_chunk_frames") if k in refused}
         on_chunk = refused.pop("on_chunk", None)
         pitch_ratio = refused.pop("pitch_ratio", None)
+        fit = refused.pop("fit", None)
         fields, keep = _refused_fields(refused, B, noise_scale_arg="noise_scales")
         o, kept = _opts(B, mode, noise_kind, noise_seed, noise_prior=noise_prior, collect_taps=collect_taps, noise_seed_offsets=noise_seed_offsets, **own)
         keep += kept
@@ -1332,8 +1405,9 @@ class Model:
         durations = np.zeros((B, id_stride), np.int32)
         frames = np.zeros(B, np.int64)
         scores = np.zeros(B, np.float32)
-        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_align_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(ids), _ptr(ilens), id_stride, _ptr(sp),
-                                                                                  float(noise_scale), C.byref(o), _ptr(durations), _ptr(frames), _ptr(scores))) != 0:
+        call = lambda: lib().vits_model_align_batch(self._h, _ptr(pcm), _ptr(lens), B, stride, _ptr(ids), _ptr(ilens), id_stride, _ptr(sp), float(noise_scale),
+                                                    C.byref(o), _ptr(durations), _ptr(frames), _ptr(scores))
+        if self._with_fit(fit, lambda: self._with_pitch(pitch_ratio, B, call)) != 0:
             raise VitsError(last_error())
         return durations, frames, scores
 
@@ -1363,7 +1437,7 @@ class Model:
 
     def submit_batch(self, ids, id_lengths=None, mode=MODE_DEFAULT, noise_seed=4321, fixed_duration=0, out_device=None, out_device_stride=0,
                      skip_host_copy=False, vocoder_chunk_frames=0, noise_seed_offsets=None, speaker_ids=None, speaking_rate=None, noise_scale=None,
-                     noise_scale_duration=None, duration_override=None, durations_out=None, pitch_ratio=None):
+                     noise_scale_duration=None, duration_override=None, durations_out=None, pitch_ratio=None, fit=None):
         """vits_model_submit_batch: queue one batch on this handle's pipeline (at most two in flight); its stage one runs under the
         previous batch's vocoder. Results come from wait(), in submission order, bit-identical to process_batch. The prosody arguments are
         those of process_batch; durations_out is filled by the matching wait() at the latest (this handle keeps it alive until then)."""
@@ -1375,7 +1449,8 @@ class Model:
         o, keep = _opts(B, mode, NOISE_COUNTER, noise_seed, fixed_duration=fixed_duration, out_device=out_device, out_device_stride=out_device_stride,
                         skip_host_copy=skip_host_copy, vocoder_chunk_frames=vocoder_chunk_frames, noise_seed_offsets=noise_seed_offsets, speaker_ids=speaker_ids)
         keep += _prosody(o, B, stride, speaking_rate, noise_scale, noise_scale_duration, duration_override, durations_out)
-        if self._with_pitch(pitch_ratio, B, lambda: lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o))) != 0:
+        call = lambda: lib().vits_model_submit_batch(self._h, _ptr(ids), _ptr(lens), B, stride, C.byref(o))
+        if self._with_fit(fit, lambda: self._with_pitch(pitch_ratio, B, call)) != 0:
             raise VitsError(last_error())
         if not hasattr(self, "_durations_in_flight"):
             self._durations_in_flight = []
@@ -1689,6 +1764,40 @@ def op_durations(logw, row, lens, length_scale=1.0, length_scales=None, override
                                _ptr(mul) if mul.size else None, _ptr(add) if mul.size else None, _ptr(dur), _ptr(cum), _ptr(frames), _ptr(sl) if mul.size else None) != 0:
         raise VitsError(last_error())
     return dur, cum, frames, sl
+
+
+def _fit_args(B, ts, lens, fixed, groups, targets):
+    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(B)
+    fixed = None if fixed is None else np.ascontiguousarray(fixed, dtype=np.int32).reshape(B, ts)
+    groups = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(B)
+    targets = np.ascontiguousarray(targets, dtype=np.int64).reshape(B)
+    return lens, fixed, groups, targets
+
+
+def fit_host(e, targets, lens=None, fixed=None, groups=None, min_rate=0.1, max_rate=10.0):
+    """vits_fit_host: the fit's definition on the host (no device). e: float32 [B, t_stride] = expf(logw); targets: int64 [B] by group (0: not fitted); lens,
+    fixed (int32 [B, t_stride], -1: a free token), groups (int32 [B]) optional. Returns (dur int32 [B, t_stride], rows float64 [B, 5] = (F, sum d, s*, R,
+    status) by group)."""
+    e = _f32(e)
+    B, ts = e.shape
+    lens, fixed, groups, targets = _fit_args(B, ts, lens, fixed, groups, targets)
+    dur, rows = np.zeros((B, ts), np.int32), np.zeros((B, 5), np.float64)
+    if lib().vits_fit_host(B, ts, _ptr(e), _ptr(fixed), _ptr(lens), _ptr(groups), _ptr(targets), float(min_rate), float(max_rate), _ptr(dur), _ptr(rows)) != 0:
+        raise VitsError(last_error())
+    return dur, rows
+
+
+def op_fit_durations(logw, row, targets, lens=None, fixed=None, groups=None, min_rate=0.1, max_rate=10.0):
+    """The fit kernel on caller-supplied log-durations (vits_op_fit_durations): logw [B, rows, t_stride], row `row` is read. Returns (e float32 [B, t_stride],
+    dur int32 [B, t_stride], rows float64 [B, 5]) as fit_host gives them."""
+    logw = _f32(logw)
+    B, rows_, ts = logw.shape
+    lens, fixed, groups, targets = _fit_args(B, ts, lens, fixed, groups, targets)
+    e, dur, rows = np.zeros((B, ts), np.float32), np.zeros((B, ts), np.int32), np.zeros((B, 5), np.float64)
+    if lib().vits_op_fit_durations(B, rows_, row, ts, _ptr(logw), _ptr(lens), _ptr(fixed), _ptr(groups), _ptr(targets), float(min_rate), float(max_rate), _ptr(e),
+                                   _ptr(dur), _ptr(rows)) != 0:
+        raise VitsError(last_error())
+    return e, dur, rows
 
 
 def op_conv_transpose1d(x, w, bias, stride, crop, pre_slope=1.0, lens=None):

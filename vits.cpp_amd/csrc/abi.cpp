@@ -827,6 +827,11 @@ VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_sp
             return fail(who + "the ratios of vits_model_set_pitch_ratios are one per utterance, and the text decides how many utterances there are: use "
                               "vits_model_set_pitch, or vits_split_sentences and vits_model_process_joined");
     }
+    // (the fit of the next call: taken here like the ratios; the total form goes on to the joined call this one makes, once the text has said how many utterances it has)
+    vits::Engine::FitGiven fit;
+    if (model->eng.take_fit(fit) && !fit.total)
+        return fail(who + "the targets of vits_model_set_fit are one per group of utterances, and the text decides how many utterances there are: use "
+                          "vits_model_set_fit_total, or vits_split_sentences and vits_model_process_joined");
     vits_speak_opts so;
     std::memset(&so, 0, sizeof(so));
     so.struct_size = sizeof(so);
@@ -863,6 +868,7 @@ VITS_API int vits_model_speak(vits_model* model, const char* text, const vits_sp
     std::string err;
     if (!vits::speak_plan(text, so.sentence_gap_ms, so.paragraph_gap_ms, so.track_per_paragraph != 0, tokenize, &ctx, p, err)) return fail(who + err);
     VITS_ENTER(model, -1)
+    if (fit.set) model->eng.give_fit(std::move(fit));
     return run_engine(out, [&](std::string& e) {
         return model->eng.process_joined(p.ids.data(), p.id_lens.data(), p.batch, p.id_stride, o, p.track.data(), p.gap_ms.data(), p.index.data(), out, e);
     });
@@ -943,6 +949,68 @@ VITS_API int64_t vits_model_last_pitch(vits_model* model, int64_t* dst, size_t c
     const int64_t* p = model->eng.last_pitch(rows);  // [rows][4]: P, N, N', K
     if (rows && dst && cap >= (size_t)3 * rows)
         for (int b = 0; b < rows; ++b) std::copy_n(p + (size_t)4 * b, 3, dst + (size_t)3 * b);
+    return rows;
+    VITS_CATCH(-1)
+}
+
+// ---- a stated duration (include/vits.h: the definition) ------------------------------------------------------------------------------------------------
+VITS_API int vits_fit_host(int32_t batch, int32_t t_stride, const float* e, const int32_t* fixed, const int32_t* lens, const int32_t* groups,
+                           const int64_t* target_frames, float min_rate, float max_rate, int32_t* dur_out, double* group_rows_out) {
+    VITS_TRY
+    const std::string who = "vits_fit_host: ";
+    if (!e || !target_frames || !dur_out || !group_rows_out) return fail(who + "null argument (e, target_frames, dur_out or group_rows_out)");
+    vits::FitGroups g;
+    std::string err;
+    if (!vits::fit_check_rows(batch, t_stride, fixed, lens, err) || !vits::fit_check(batch, groups, target_frames, err) ||
+        !vits::fit_limits(min_rate, max_rate, g.s_lo, g.s_hi, err))
+        return fail(who + err);
+    const std::vector<int> tgt(target_frames, target_frames + batch);
+    std::vector<int64_t> rows((size_t)batch * vits::kFitRowInts);
+    g.group = groups, g.target = tgt.data();
+    vits::fit_host(batch, t_stride, e, fixed, lens, g, dur_out, rows.data());
+    vits::fit_rows_double(batch, rows.data(), group_rows_out);
+    return 0;
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_set_fit(vits_model* model, const int64_t* target_frames, const int32_t* groups, int32_t n, float min_rate, float max_rate) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_fit(target_frames, groups, n, min_rate, max_rate, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int vits_model_set_fit_total(vits_model* model, int64_t total_frames, float min_rate, float max_rate) {
+    VITS_TRY
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    return run_engine(nullptr, [&](std::string& err) { return model->eng.set_fit_total(total_frames, min_rate, max_rate, err); });
+    VITS_CATCH(-1)
+}
+VITS_API int64_t vits_model_fit_frames(const vits_model* model, double seconds) {
+    if (!model) {
+        set_err("null argument");
+        return -1;
+    }
+    const int64_t L = model->eng.fit_frames(seconds);
+    if (L < 0) set_err("vits_model_fit_frames: seconds is not finite");
+    return L;
+}
+VITS_API int64_t vits_model_last_fit(vits_model* model, double* dst, size_t cap) {
+    VITS_TRY
+    if (!model || (!dst && cap)) {
+        set_err("null argument");
+        return -1;
+    }
+    VITS_ENTER(model, -1)
+    int rows = 0;
+    const double* p = model->eng.last_fit(rows);  // [rows][6]
+    if (rows && dst && cap >= (size_t)6 * rows) std::copy_n(p, (size_t)6 * rows, dst);
     return rows;
     VITS_CATCH(-1)
 }

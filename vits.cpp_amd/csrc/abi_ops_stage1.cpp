@@ -765,6 +765,48 @@ VITS_API int vits_op_durations(int32_t batch, int32_t rows, int32_t row, int32_t
     VITS_CATCH(-1)
 }
 
+VITS_API int vits_op_fit_durations(int32_t batch, int32_t rows, int32_t row, int32_t t_stride, const float* logw, const int32_t* lens, const int32_t* fixed,
+                                   const int32_t* groups, const int64_t* target_frames, float min_rate, float max_rate, float* e_out, int32_t* dur_out,
+                                   double* group_rows_out) {
+    VITS_TRY
+    const std::string who = "vits_op_fit_durations: ";
+    if (!logw || !target_frames || !e_out || !dur_out || !group_rows_out) return fail(who + "null argument");
+    if (rows < 1 || row < 0 || row >= rows) return fail(who + "rows >= 1 and 0 <= row < rows are required");
+    std::string err;
+    FitCall c;
+    if (!fit_check_rows(batch, t_stride, fixed, lens, err) || !fit_check(batch, groups, target_frames, err) || !fit_limits(min_rate, max_rate, c.g.s_lo, c.g.s_hi, err))
+        return fail(who + err);
+    const size_t nt = (size_t)batch * t_stride * 4;
+    const std::vector<int> tgt(target_frames, target_frames + batch);
+    DevMem dlogw, dl, dfix, dgrp, dtgt, de, ddur, drows;
+    // (the override rows are staged like logw: INT_MIN-like 0xFF bytes = -1 behind every length would hide a read there, so the tail holds 0x7F bytes instead)
+    std::vector<int32_t> hfix;
+    if (fixed) {
+        hfix.assign((size_t)batch * t_stride, 0x7F7F7F7F);
+        for (int b = 0; b < batch; ++b) std::memcpy(&hfix[(size_t)b * t_stride], fixed + (size_t)b * t_stride, sizeof(int32_t) * (size_t)(lens ? lens[b] : t_stride));
+    }
+    if (!stage_rows(dlogw, logw, batch, rows, t_stride, t_stride, lens, t_stride) || !dl.put_opt(lens, (size_t)batch * 4) || (fixed && !dfix.put(hfix.data(), nt)) ||
+        !dgrp.put_opt(groups, (size_t)batch * 4) || !dtgt.put(tgt.data(), (size_t)batch * 4) || !de.fill(nt, g_op_out_fill) || !ddur.fill(nt, g_op_out_fill) ||
+        !drows.fill((size_t)batch * kFitRowInts * 8, g_op_out_fill))
+        return -1;
+    c.logw = tref(dlogw.f(), rows, t_stride);
+    c.c = row;
+    c.lens = dl.i();
+    c.fixed = dfix.i();
+    c.g.group = dgrp.i();
+    c.g.target = dtgt.i();
+    c.e = de.f();
+    c.dur = ddur.i();
+    c.rows = static_cast<int64_t*>(drows.p);
+    c.batch = batch, c.tmax = t_stride;
+    if (!finish(launch_fit_durations(c, nullptr), "vits_op_fit_durations")) return -1;
+    std::vector<int64_t> hrows((size_t)batch * kFitRowInts);
+    if (!de.get(e_out, nt) || !ddur.get(dur_out, nt) || !drows.get(hrows.data(), hrows.size() * 8)) return -1;
+    fit_rows_double(batch, hrows.data(), group_rows_out);
+    return 0;
+    VITS_CATCH(-1)
+}
+
 VITS_API int vits_op_align(int32_t batch, const int32_t* T, const int32_t* L, int32_t F, const float* m, const float* ls, const float* z, int32_t* durations,
                            float* scores) {
     VITS_TRY

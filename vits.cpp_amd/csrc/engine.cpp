@@ -157,12 +157,130 @@ int Engine::set_prosody(float rate, float ns, float nsd, std::string& err) {
     return 0;
 }
 
+// ---- a stated duration (include/vits.h): what is given for the next call, and what a call makes of it ---------------------------------------------
+int Engine::set_fit(const int64_t* targets, const int32_t* groups, int n, float min_rate, float max_rate, std::string& err) {
+    if (n < 0 || (!targets && n > 0)) {
+        err = "vits_model_set_fit: " + std::string(n < 0 ? "n < 0" : "null argument (target_frames is NULL with n > 0)");
+        return -1;
+    }
+    FitGiven g;
+    if (targets && n > 0) {
+        g.set = true;
+        g.targets.assign(targets, targets + n);
+        g.has_groups = groups != nullptr;
+        if (groups) g.groups.assign(groups, groups + n);
+        g.min_rate = min_rate, g.max_rate = max_rate;
+    }
+    fit_given_.give(std::move(g));
+    return 0;
+}
+
+int Engine::set_fit_total(int64_t total, float min_rate, float max_rate, std::string& err) {
+    (void)err;
+    FitGiven g;
+    g.set = g.total = true;
+    g.targets.assign(1, total);
+    g.min_rate = min_rate, g.max_rate = max_rate;
+    fit_given_.give(std::move(g));
+    return 0;
+}
+
+int Engine::resolve_fit(int B, const vits_process_opts& o, const float* pitch, ResolvedFit& rf, std::string& err) const {
+    if (!rf.have) return 0;
+    const FitGiven& g = rf.given;
+    const std::string who = g.total ? "vits_model_set_fit_total: " : "vits_model_set_fit: ";
+    if (B <= 0) return 0;  // (the call's own refusal follows)
+    if (!g.total && (int)g.targets.size() != B) {
+        err = who + "n = " + std::to_string(g.targets.size()) + " was given, and this call has " + std::to_string(B) + " utterances";
+        return -1;
+    }
+    rf.group.assign((size_t)B, 0);
+    rf.target.assign((size_t)B, 0);
+    if (g.total) {
+        rf.target[0] = g.targets[0];
+        if (g.targets[0] < 1 || g.targets[0] > kFitMaxTarget) {
+            err = who + "total_frames = " + std::to_string(g.targets[0]) + ": a target is 1 to 2^22 frames";
+            return -1;
+        }
+    } else {
+        for (int b = 0; b < B; ++b) rf.group[(size_t)b] = g.has_groups ? g.groups[(size_t)b] : b;
+        rf.target = g.targets;
+    }
+    std::string why;
+    if (!fit_check(B, rf.group.data(), rf.target.data(), why) || !fit_limits(g.min_rate, g.max_rate, rf.s_lo, rf.s_hi, why)) {
+        err = who + why;
+        return -1;
+    }
+    int fitted = -1;  // (the first utterance of a fitted group)
+    for (int b = B - 1; b >= 0; --b)
+        if (rf.target[(size_t)rf.group[(size_t)b]] != 0) fitted = b;
+    if (fitted < 0) return 0;  // (every target 0: the call runs as always)
+    const std::string what = who + "group " + std::to_string(rf.group[(size_t)fitted]) + " is fitted to " + std::to_string(rf.target[(size_t)rf.group[(size_t)fitted]]) + " frames: ";
+    if (o.fixed_duration > 0) {
+        err = what + "fixed_duration > 0 leaves the duration predictor nothing to scale";
+        return -1;
+    }
+    if (ggml_tables == 1) {
+        err = what + "vits_model_set_ggml_tables(model, 1) runs stage one in the CPU oracle's exact order, whose duration is not expf(logw) x scale (use tables mode 0 or 2)";
+        return -1;
+    }
+    if (o.async) {
+        err = what + "async returns before the device has finished, and the fit's rows are read from the device behind stage one: call without async, or pipeline "
+                     "with vits_model_submit_batch / vits_model_wait";
+        return -1;
+    }
+    for (int b = 0; pitch && b < B; ++b)
+        if (pitch[b] != 1.f && rf.target[(size_t)rf.group[(size_t)b]] != 0) {
+            err = who + "utterance " + std::to_string(b) + " of the fitted group " + std::to_string(rf.group[(size_t)b]) + " has the pitch ratio " + fmt_float(pitch[b]) +
+                  ": the varispeed's stretch and the fit both own the length scale (the combination is not built)";
+            return -1;
+        }
+    rf.on = true;
+    return 0;
+}
+
+int64_t Engine::fit_frames(double seconds) const {
+    if (!std::isfinite(seconds)) return -1;
+    int64_t hop = 1, sadd = 0;
+    const bool refmode = mode == VITS_MODE_REFERENCE;
+    for (const auto& u : ups_) {  // (set_stage_affine's recurrence)
+        const int s = u.stride, K = u.k;
+        const int crop = refmode ? 0 : (K - s) / 2;
+        hop *= s;
+        sadd = sadd * s + (K - s - 2 * crop);
+    }
+    const double samples = std::floor(seconds * (double)hp.sampling_rate);
+    if (!(samples < 9.0e15)) return (int64_t)kFitMaxTarget;
+    const int64_t L = ((int64_t)samples - sadd) / hop;
+    return std::min<int64_t>(std::max<int64_t>(samples < (double)sadd ? 1 : L, 1), kFitMaxTarget);
+}
+
+// the group rows [B][kFitRowInts] of a call that fits, queued for the host beside the frame counts; fit_report turns the landed copy into the rows of
+// vits_model_last_fit, one per utterance
+hipError_t Engine::copy_fit_rows(const Call& c, PinnedBuf<int64_t>& pinned) {
+    const size_t n = (size_t)c.B * kFitRowInts;
+    if (hipError_t e = pinned.ensure(n, n + 64)) return e;
+    return hipMemcpyAsync(pinned.p, c.s1.fit_rows, sizeof(int64_t) * n, hipMemcpyDeviceToHost, stream);
+}
+std::vector<double> Engine::fit_report(const Call& c, const int64_t* pinned) const {
+    std::vector<double> by_group((size_t)c.B * kFitRowInts), rows((size_t)c.B * 6);
+    fit_rows_double(c.B, pinned, by_group.data());
+    for (int b = 0; b < c.B; ++b) {
+        const int g = c.fit->group[(size_t)b];
+        rows[(size_t)6 * b] = g;
+        std::copy_n(by_group.begin() + (size_t)kFitRowInts * g, kFitRowInts, rows.begin() + (size_t)6 * b + 1);
+    }
+    return rows;
+}
+
 void Engine::batch_landed(Pending& p, int slot, bool append) {
     lv_.landed(slot, p.lv_rows, append);
     lm_.landed(slot, p.lm_rows, append);
     if (p.ed_rows) edges_lengths(ed_.slot_rows(slot), p.ed_rows, p.lengths.data());
     ed_.landed(slot, p.ed_rows, append);
     pt_.store(p.pt_rows, append);
+    if (!append) fit_rows_.clear();
+    fit_rows_.insert(fit_rows_.end(), p.fit_rows.begin(), p.fit_rows.end());
 }
 
 // the one place that allocates what a call hands out: lengths[] and frames[] of B utterances, no PCM yet
@@ -210,11 +328,14 @@ int Engine::check_prosody(const vits_process_opts& o, int B, int id_stride, cons
 int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, vits_batch_result* out,
                           std::string& err) {
     ResolvedPitch rp(*this, o);
+    ResolvedFit rf(*this);
     if (refuse_pending(err)) return -1;
     if (check_speakers(o, B, err)) return -1;
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;
     if (resolve_pitch(B, id_stride, id_lens, rp, err)) return -1;
+    if (resolve_fit(B, o, rp.pitch, rf, err)) return -1;
     ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
+    ScopedSet<const ResolvedFit*> fit_scope(call_fit_, rf.on ? &rf : nullptr);
     DeliveryPlan refusable;  // (the refusals of the delivery chain, before stage one is queued; the call's own plan is made where its stage two begins)
     if (plan_delivery(rp.o, refusable, err)) return -1;
     clear_reports();
@@ -222,9 +343,10 @@ int Engine::process_batch(const int32_t* ids, const int32_t* id_lens, int B, int
     // second part runs on the front-end stream under the flow / vocoder of the first, exactly as two vits_model_submit_batch calls would.
     // Every kernel is batch-invariant, so PCM, lengths and frames are those of the unsplit call bit for bit (GPU test, fuzz_identity.py).
     const int smin = knobs.split_min_batch;
-    // (a call that shifts stays whole: a part whose ratios are all 1 would run without the stage and leave the report without its rows)
+    // (a call that shifts stays whole: a part whose ratios are all 1 would run without the stage and leave the report without its rows; so does a call that
+    // fits: a group stays in one launch)
     if (smin > 0 && B >= smin && B >= 2 && front_ && !prof.on && !knobs.no_pipeline && o.noise_kind == VITS_NOISE_COUNTER && !o.collect_taps && !o.on_chunk &&
-        !o.frames_only && !o.async && o.vocoder_chunk_frames <= 0 && !rp.pitch)
+        !o.frames_only && !o.async && o.vocoder_chunk_frames <= 0 && !rp.pitch && !rf.on)
         return process_split(ids, id_lens, B, id_stride, o, out, err);
     a1_slot_ = 0;
     const int rc = process_impl(ids, id_lens, B, id_stride, rp.o, out, err, nullptr);
@@ -244,6 +366,7 @@ int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, in
                            const int32_t* index, vits_batch_result* out, std::string& err) {
     const std::string who = "vits_model_process_joined: ";
     ResolvedPitch rp(*this, o);
+    ResolvedFit rf(*this);
     if (refuse_pending(err)) return -1;
     // (on_chunk and async are the plan's refusals, below)
     if (o.collect_taps) {
@@ -268,7 +391,12 @@ int Engine::process_joined(const int32_t* ids, const int32_t* id_lens, int B, in
             return -1;
         }
     }
+    if (resolve_fit(B, o, rp.pitch, rf, err)) {
+        err = who + err;
+        return -1;
+    }
     ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
+    ScopedSet<const ResolvedFit*> fit_scope(call_fit_, rf.on ? &rf : nullptr);
     DeliveryPlan refusable;
     if (plan_delivery(rp.o, refusable, err, /*joined=*/true)) return -1;
     JoinPlan plan;
@@ -363,6 +491,7 @@ int Engine::process_split(const int32_t* ids, const int32_t* id_lens, int B, int
 // for before this submit was accepted, so nothing on the device still reads it.
 int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int id_stride, const vits_process_opts& o, std::string& err, bool part) {
     ResolvedPitch rp(*this, o);  // (its arrays live until process_impl has returned: the ratios have gone to the slot's pinned memory by then, the rates into the header)
+    ResolvedFit rf(*this);       // (likewise: its groups and targets have gone into the header)
     if (pending() >= 2) {
         err = "two batches in flight already: call vits_model_wait first";
         return -1;
@@ -374,7 +503,9 @@ int Engine::submit_batch(const int32_t* ids, const int32_t* id_lens, int B, int 
     if (check_speakers(o, B, err)) return -1;  // (the speakers are copied into the call's header below: the caller's array may go at once)
     if (check_prosody(o, B, id_stride, id_lens, err)) return -1;  // (so are the prosody arrays; durations_out is written when the frame counts are read)
     if (!part && resolve_pitch(B, id_stride, id_lens, rp, err)) return -1;
+    if (!part && resolve_fit(B, o, rp.pitch, rf, err)) return -1;
     ScopedSet<const float*> pitch_scope(call_pitch_, rp.pitch);
+    ScopedSet<const ResolvedFit*> fit_scope(call_fit_, rf.on ? &rf : nullptr);
     Pending& p = pend_[submit_seq_ & 1];
     if (!p.done) {
         HIP_OK(hipEventCreateWithFlags(&p.s1_done, hipEventDisableTiming));
@@ -456,6 +587,7 @@ int Engine::frames_only_result(Call& c, vits_batch_result* out) {
     }
     HIP_OK(hipStreamSynchronize(stream));
     prof.fence();
+    fit_rows_ = c.fit_report;
     return 0;
 }
 
@@ -472,6 +604,7 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
     Call c(o, err, ids, B, id_stride);
     c.join = join;
     c.pitch = call_pitch_;
+    c.fit = call_fit_;
     // An error path between the speculative draw and its commit must not leave the reference stream locked — nor at a timing-dependent
     // position: finish(0) rewinds to the state behind the [T, 2] tensor, where the sequential path this replaces leaves the stream when a call
     // fails before prior sampling (finish(drawn()) committed however many values the helper happened to have drawn).
@@ -577,22 +710,26 @@ int Engine::process_impl(const int32_t* ids, const int32_t* id_lens, int B, int 
         HIP_OK(pend->frames_pinned.ensure((size_t)B, (size_t)B + 64));
         HIP_OK(hipMemcpyAsync(pend->frames_pinned.p, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
         if (o.durations_out) HIP_OK(copy_durations(c, pend->dur_pinned));
+        if (c.fit) HIP_OK(copy_fit_rows(c, pend->fit_pinned));
         HIP_OK(hipEventRecord(pend->s1_done, stream));
         prof.fence();
         HIP_OK(hipEventSynchronize(pend->s1_done));
         std::copy(pend->frames_pinned.p, pend->frames_pinned.p + B, frames.begin());
         if (o.durations_out) store_durations(c, pend->dur_pinned.p);
+        if (c.fit) c.fit_report = fit_report(c, pend->fit_pinned.p);
     } else {
         frames.resize(B);
         // (pinned destination, owned by the engine: into the caller-side std::vector the copy went through the runtime's staging buffer, + 15 us per batch-1 call)
         HIP_OK(frames_host_.ensure((size_t)B, (size_t)B + 64));
         HIP_OK(hipMemcpyAsync(frames_host_.p, c.s1.frames, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
         if (o.durations_out) HIP_OK(copy_durations(c, dur_host_));
+        if (c.fit) HIP_OK(copy_fit_rows(c, fit_host_));
         prof.fence();
         HIP_OK(hipStreamSynchronize(stream));
         prof.fence();
         std::copy(frames_host_.p, frames_host_.p + B, frames.begin());
         if (o.durations_out) store_durations(c, dur_host_.p);
+        if (c.fit) c.fit_report = fit_report(c, fit_host_.p);
     }
     if (o.durations_out && o.fixed_duration > 0)  // (no device read: every token lasts fixed_duration frames)
         for (int b = 0; b < B; ++b)
@@ -968,6 +1105,7 @@ int Engine::hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_
         pend->lm_rows = lm_n;
         pend->ed_rows = ed_n;  // (lengths: the bounds until vits_model_wait reads the rows)
         pend->pt_rows = c.pit_rows;
+        pend->fit_rows = c.fit_report;
         pend->host_copy = !o.skip_host_copy;
         if (pend->host_copy) {
             const size_t need = sizeof(float) * (size_t)B * pend->stride;
@@ -1016,6 +1154,7 @@ int Engine::hand_over(Call& c, vits_batch_result* out, Pending* pend, bool want_
     lv_.landed(a1_slot_, lv_n), lm_.landed(a1_slot_, lm_n), ed_.landed(a1_slot_, ed_n);
     pt_.store(c.pit_rows);
     tm_.store(c.tem_rows);
+    fit_rows_ = c.fit_report;
     // (event timings are read back lazily — vits_prof_report / vits_prof_reset — not here: ~1 ms of host work per call
     // with the device idle would otherwise sit inside the caller's timed region; cap the backlog for long runs)
     if (prof.on && prof.recs.size() > 50000) prof.collect();

@@ -382,6 +382,48 @@ class Engine {
     int resolve_pitch(int B, int id_stride, const int32_t* id_lens, ResolvedPitch& rp, std::string& err) const;
     // the rows [B][4] = {P, N, N', K} of the most recently completed call (empty: it shifted nothing)
     const int64_t* last_pitch(int& rows) const { return pt_.read(rows); }
+    // A stated duration (include/vits.h "a stated duration"; fit.hip): the fit of the NEXT call alone, given and taken like the ratios above (TakeOnce's
+    // rule for a value that is not one float array). total: the call's utterances form one group whose target is targets[0], whatever their number.
+    struct FitGiven {
+        bool set = false, total = false, has_groups = false;
+        std::vector<int64_t> targets;
+        std::vector<int32_t> groups;
+        float min_rate = kFitMinRate, max_rate = kFitMaxRate;
+        void give(FitGiven g) { *this = std::move(g); }
+        bool take(FitGiven& out) {  // true: something had been given
+            out = std::move(*this);
+            *this = FitGiven();
+            return out.set;
+        }
+    };
+    // 0, or -1 + a message (the shape of the arguments alone: n < 0, targets NULL with n > 0). NULL or n = 0 drops what was given.
+    int set_fit(const int64_t* targets, const int32_t* groups, int n, float min_rate, float max_rate, std::string& err);
+    int set_fit_total(int64_t total, float min_rate, float max_rate, std::string& err);
+    bool take_fit(FitGiven& given) { return fit_given_.take(given); }
+    // (vits_model_speak holds the total form while it cuts the text, and hands it to the joined call it then makes)
+    void give_fit(FitGiven given) { fit_given_.give(std::move(given)); }
+    // A call's fit. An entry point constructs it first of all, beside its ResolvedPitch: that takes what was given for this call. resolve_fit then decides:
+    // `on` when some group has a target; group / target [B] are what the kernel reads (the header carries them to the device), s_lo / s_hi its limits.
+    struct ResolvedFit {
+        FitGiven given;
+        bool have;  // (declared behind `given`, which its initialiser fills)
+        bool on = false;
+        std::vector<int> group;
+        std::vector<int64_t> target;
+        float s_lo = 1.f, s_hi = 1.f;
+        explicit ResolvedFit(Engine& e) : have(e.take_fit(given)) {}
+    };
+    // 0, or -1 + a message naming the group or the utterance: another n than utterances; a group outside [0, B); a target outside [1, 2^22] and not 0;
+    // rates outside 0.1 <= min <= max <= 10; fixed_duration > 0, async or the exact-order stage one with some group fitted; a fitted utterance whose
+    // resolved pitch ratio (pitch [B], or NULL: all 1) is not 1
+    int resolve_fit(int B, const vits_process_opts& o, const float* pitch, ResolvedFit& rf, std::string& err) const;
+    // the largest L with L hop + sadd <= seconds x the model's rate, at least 1 (the model's mode decides sadd: set_stage_affine)
+    int64_t fit_frames(double seconds) const;
+    // the rows [B][6] = {group, F, sum d of the group, s*, R, status} of the most recently completed call (empty: it fitted nothing)
+    const double* last_fit(int& rows) const {
+        rows = (int)(fit_rows_.size() / 6);
+        return fit_rows_.data();
+    }
     // A conversion's rate and pitch (include/vits.h "a stated tempo": in a conversion; tempo.hip + pitch.hip): a conversion predicts no durations, so an
     // utterance with rate r and pitch p is time-stretched by q = (float)((double)r / (double)p) behind the vocoder and, when p != 1, played back p times faster by
     // the varispeed behind that. vc_rate / vc_pitch: the values of every utterance of a conversion that no pair was given for; 1 = off.
@@ -560,6 +602,8 @@ class Engine {
         int ed_rows = 0;              // stated edges: likewise (0: off); `lengths` is derived from them once `done` has passed
         PinnedBuf<float> pitch_pinned;  // a stated pitch: the batch's ratios (host side of their H2D copy)
         std::vector<int64_t> pt_rows;   // ... and its report rows [B][4], host arithmetic (empty: it shifted nothing)
+        PinnedBuf<int64_t> fit_pinned;  // a stated duration: the batch's group rows, copied beside the frame counts
+        std::vector<double> fit_rows;   // ... and its report rows [B][6] (empty: it fitted nothing)
         hipEvent_t s1_done = nullptr, done = nullptr;
     } pend_[2];
     std::atomic<uint64_t> submit_seq_{0}, wait_seq_{0};  // batch n lives in pend_[n & 1]; written under the busy flag, read by vits_model_pending
@@ -653,7 +697,17 @@ class Engine {
     int* edges_lens() { return static_cast<int*>(ed_.tail()); }
     static const int* track_lens(const int64_t* join_rows, int B) { return reinterpret_cast<const int*>(join_rows + (size_t)2 * B); }
     int* track_lens(int B) { return const_cast<int*>(track_lens(jn_.dev(), B)); }
-    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(), tm_.clear(); }
+    void clear_reports() { lv_.clear(), lm_.clear(), ed_.clear(), jn_.clear(), pt_.clear(), tm_.clear(), fit_rows_.clear(); }
+    // a stated duration: the next call's fit, the resolved fit of the call being queued (non-null MEANS that the kernel runs), a synchronous call's group
+    // rows on their way from the device, the report of the last completed call, and the kernel in front of either launch_durations: it returns the override
+    // rows that launch takes (the call's own where nothing is fitted)
+    FitGiven fit_given_;
+    const ResolvedFit* call_fit_ = nullptr;
+    PinnedBuf<int64_t> fit_host_;
+    std::vector<double> fit_rows_;
+    int run_fit(Call& c, TensorRef logw, int row, const int*& ovr);
+    hipError_t copy_fit_rows(const Call& c, PinnedBuf<int64_t>& pinned);
+    std::vector<double> fit_report(const Call& c, const int64_t* pinned) const;
     // a stated pitch: the interleaved table on the device (uploaded by the first call that shifts), a synchronous call's ratios on their way there, and the
     // stage from its source into its destination, as the call's plan routes them: queued behind the last vocoder window, in front of run_edges
     float* pitch_table_ = nullptr;

@@ -11,8 +11,14 @@ int Engine::align_batch(const float* pcm, const int64_t* pcm_lens, int B, int64_
                         const int32_t* speakers, float noise_scale, const vits_process_opts& o, int32_t* durations, int64_t* frames_out, float* scores,
                         std::string& err) {
     std::vector<float> given;
+    FitGiven fit_given;
+    const bool fit_was_given = take_fit(fit_given);  // (taken with the ratios: whatever becomes of this call, both are gone)
     if (take_pitch_ratios(given)) {
         err = "alignment does not take the ratios of vits_model_set_pitch_ratios (it produces no audio)";
+        return -1;
+    }
+    if (fit_was_given) {
+        err = "alignment does not take the fit of vits_model_set_fit (its durations are the recording's, not the predictor's)";
         return -1;
     }
     if (refuse_pending(err)) return -1;

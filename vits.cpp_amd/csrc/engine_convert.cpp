@@ -227,9 +227,16 @@ int Engine::convert_batch(const float* pcm, const int64_t* pcm_lens, int B, int6
                           vits_batch_result* out, std::string& err) {
     ResolvedConversion rc(*this);  // (first of all: the pairs given for this conversion are taken, whatever becomes of it)
     std::vector<float> given;
+    FitGiven fit_given;
+    const bool fit_was_given = take_fit(fit_given);  // (taken with the ratios: whatever becomes of this call, both are gone)
     if (take_pitch_ratios(given)) {
         err = "voice conversion does not take the ratios of vits_model_set_pitch_ratios (a pitch is paid for by the duration predictor's stretch, and a conversion "
               "predicts no durations)";
+        return -1;
+    }
+    if (fit_was_given) {
+        err = "voice conversion does not take the fit of vits_model_set_fit (a conversion predicts no durations to fit; its time stretch is "
+              "vits_model_set_conversion_prosody)";
         return -1;
     }
     if (refuse_pending(err)) return -1;

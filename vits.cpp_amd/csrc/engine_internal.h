@@ -167,6 +167,13 @@ struct Call {
         // prior noise scale, duration noise scale [B]; duration overrides [B][id_stride]
         float *len_scale, *noise_scale, *noise_scale_dur;
         int* dur_ovr;
+        // a stated duration (Engine::run_fit; null unless the call fits): the groups [B] and the targets [B] by group in the header, and from the arena
+        // e [B][id_stride], the override rows the kernel writes [B][id_stride], the group rows [B][kFitRowInts]
+        int* fit_group;
+        int* fit_target;
+        float* fit_e;
+        int* fit_ovr;
+        int64_t* fit_rows;
         float *x, *qkv, *att, *tmp, *ffn, *stats, *dpx, *dpy, *dpp, *cond, *z, *u, *dur;
         float *ex_scores, *ex_tok;  // emulated-ggml mode 1 only
         uint16_t* x16;
@@ -176,6 +183,8 @@ struct Call {
     // multi-speaker calls: the effective-bias table row of every utterance (device [B]: speaker + 1) — null when every utterance of the call is
     // speaker -1, so that such a call queues exactly the kernels (and reads exactly the biases) of a single-speaker model
     const int* spk = nullptr;
+    std::vector<double> fit_report;            // ... and its rows [B][6] for vits_model_last_fit, once the group rows have landed beside the frame counts
+    const Engine::ResolvedFit* fit = nullptr;  // a stated duration: the call's resolved fit (null: nothing is fitted, nothing is queued or allocated for it)
     RefNoiseAhead* ref_ahead = nullptr;  // batch 1, reference noise: the prior noise drawn while stage one runs (engine.cpp)
     // voice conversion (engine_convert.cpp): the call's input and the two speaker row arrays; null for text-to-speech
     struct Vc {

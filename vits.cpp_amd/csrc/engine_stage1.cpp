@@ -125,10 +125,10 @@ int Engine::layout_stage_one(Call& c) {
     const size_t base_ints = (size_t)B * id_stride + 3 * (size_t)B + 2 * (size_t)(n_up + 1);
     // per-utterance prosody: a section per array the call passes (a call without them copies exactly the header it always did)
     const size_t hdr_ints = base_ints + (size_t)B * ((o.speaking_rates ? 1 : 0) + (o.noise_scales ? 1 : 0) + (o.noise_scale_durations ? 1 : 0)) +
-                            (o.duration_override ? (size_t)B * id_stride : 0);
+                            (o.duration_override ? (size_t)B * id_stride : 0) + (c.fit ? (size_t)2 * B : 0);
     auto layout1 = [&](Arena& a) {
         // host-written header, one block = one H2D copy: ids | lens | stage_mul | stage_add | seed_off | spk_row [| len_scale] [| noise_scale]
-        // [| noise_scale_dur] [| dur_ovr]
+        // [| noise_scale_dur] [| dur_ovr] [| fit_group | fit_target]
         s1.ids = a.alloc<int>(hdr_ints);
         s1.lens = s1.ids + (size_t)B * id_stride;
         s1.stage_mul = s1.lens + B;
@@ -145,10 +145,16 @@ int Engine::layout_stage_one(Call& c) {
         s1.noise_scale = (float*)section(o.noise_scales, B);
         s1.noise_scale_dur = (float*)section(o.noise_scale_durations, B);
         s1.dur_ovr = section(o.duration_override, (size_t)B * id_stride);
+        s1.fit_group = section(c.fit != nullptr, B);
+        s1.fit_target = section(c.fit != nullptr, B);
         s1.cum = a.alloc<int>((size_t)B * id_stride);
         s1.frames = a.alloc<int>(B);
         s1.stage_lens = a.alloc<int>((size_t)(n_up + 1) * B);
         s1.dur = a.alloc<float>((size_t)B * id_stride);
+        // (a stated duration: the kernel's scratch and its rows; a call that fits nothing takes none of them)
+        s1.fit_e = c.fit ? a.alloc<float>((size_t)B * id_stride) : nullptr;
+        s1.fit_ovr = c.fit ? a.alloc<int>((size_t)B * id_stride) : nullptr;
+        s1.fit_rows = c.fit ? a.alloc<int64_t>((size_t)B * kFitRowInts) : nullptr;
         s1.x = a.alloc<float>((size_t)B * H * ts);
         s1.qkv = a.alloc<float>((size_t)B * 3 * H * ts);
         s1.att = a.alloc<float>((size_t)B * H * ts);
@@ -218,6 +224,10 @@ int Engine::layout_stage_one(Call& c) {
         if (o.noise_scales) std::memcpy(host_of(s1.noise_scale), o.noise_scales, sizeof(float) * B);
         if (o.noise_scale_durations) std::memcpy(host_of(s1.noise_scale_dur), o.noise_scale_durations, sizeof(float) * B);
         if (o.duration_override) std::memcpy(host_of(s1.dur_ovr), o.duration_override, sizeof(int) * (size_t)B * id_stride);
+        if (c.fit) {
+            std::memcpy(host_of(s1.fit_group), c.fit->group.data(), sizeof(int) * B);
+            for (int g = 0; g < B; ++g) host_of(s1.fit_target)[g] = (int)c.fit->target[(size_t)g];
+        }
         HIP_OK(hipMemcpyAsync(s1.ids, hdr, sizeof(int) * hdr_ints, hipMemcpyHostToDevice, stream));
         HIP_OK(hipEventRecord(hs.ev, stream));
         hs.pending = true;
@@ -433,11 +443,47 @@ int Engine::run_duration_predictor(Call& c) {
         }
     }
     if (o.collect_taps) snapshot("log_duration", sub(z, c_first), 1, Tmax, B, tlen);
+    const int* ovr = s1.dur_ovr;
+    if (c.fit && run_fit(c, z, c_first, ovr)) return -1;
     prof.begin("durations", 0, 0, stream);
-    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, s1.dur_ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames,
+    HIP_OK(launch_durations(z, c_first, dl, B, id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames,
                             s1.stage_lens, n_up + 1, s1.stage_mul, s1.stage_add, stream));
     prof.end(stream);
     c.c_first = c_first;
+    return 0;
+}
+
+// ---- a stated duration (include/vits.h; fit.hip): one block per group in front of launch_durations, which takes the rows this writes as its override rows.
+// The group rows stay on the device until the frame counts are read (copy_fit_rows, beside that copy).
+int Engine::run_fit(Call& c, TensorRef logw, int row, const int*& ovr) {
+    std::string& err = c.err;
+    Call::S1& s1 = c.s1;
+    FitCall f;
+    f.logw = logw;
+    f.c = row;
+    f.lens = s1.lens;
+    f.fixed = s1.dur_ovr;
+    f.g.group = s1.fit_group;
+    f.g.target = s1.fit_target;
+    f.g.s_lo = c.fit->s_lo, f.g.s_hi = c.fit->s_hi;
+    f.e = s1.fit_e;
+    f.dur = s1.fit_ovr;
+    f.rows = s1.fit_rows;
+    f.batch = c.B, f.tmax = c.id_stride;
+    // (the byte count is an annotation, not a measurement: e read once per sum at a GUESSED 30 sums, the full range's worst case; a narrow rate range or a
+    // clamped group takes fewer, and the reads of the override rows are not counted)
+    prof.begin("fit_durations", 0, 4.0 * 30 * (double)c.sum_t, stream);
+    const hipError_t e = launch_fit_durations(f, stream);
+    prof.end(stream);
+    HIP_OK(e);
+    if (c.o.collect_taps) {
+        TensorRef t;
+        t.p = s1.fit_e;
+        t.cs = c.id_stride;
+        t.bs = c.id_stride;
+        snapshot("fit_exp", t, 1, c.Tmax, c.B, c.tlen);
+    }
+    ovr = s1.fit_ovr;
     return 0;
 }
 
@@ -492,8 +538,10 @@ int Engine::run_duration_predictor_det(Call& c) {
         DET_STEP("dp_det_unfused", flop, launch_dp_det_unfused(d, make_ref(s1.dpx, H, ts), make_ref(s1.dpy, Fc, ts), make_ref(s1.dpp, Fc, ts), stream));
     }
     if (o.collect_taps) snapshot("log_duration", d.logw, 1, Tmax, B, c.tlen);
+    const int* ovr = s1.dur_ovr;
+    if (c.fit && run_fit(c, z, 0, ovr)) return -1;
     prof.begin("durations", 0, 0, stream);
-    HIP_OK(launch_durations(z, 0, dl, B, c.id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, s1.dur_ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames, s1.stage_lens,
+    HIP_OK(launch_durations(z, 0, dl, B, c.id_stride, (float)(1.0 / (double)speaking_rate), s1.len_scale, ovr, o.fixed_duration, s1.dur, s1.cum, s1.frames, s1.stage_lens,
                             c.n_up + 1, s1.stage_mul, s1.stage_add, stream));
     prof.end(stream);
     c.c_first = 0;

@@ -990,6 +990,45 @@ struct TempoCall {
 hipError_t launch_tempo_search(const TempoCall& c, hipStream_t s);
 hipError_t launch_tempo_ola(const TempoCall& c, hipStream_t s);
 
+// ---- a stated duration: the length scale fitted to a target frame count (fit.hip; the definition: include/vits.h "a stated duration") ----
+// A group is a set of utterances of one call. Token t has e_t = expf(logw_t) and fixed_t (the caller's override, or -1). A free token lasts
+// c_t(s) = (int64) min(ceilf(e_t * s), 2^24) frames at the scale s, a fixed one fixed_t; n(s) = sum c_t(s) is non-decreasing in the bit pattern of s > 0.
+// s* = the largest float in [s_lo, s_hi] with n(s*) <= F (s_lo = (float)(1.0 / max_rate), s_hi = (float)(1.0 / min_rate)), found by bisection on the bit
+// patterns; the R = F - n(s*) frames left go to the free tokens in (utterance, token) order, token t taking min(c_t(next s) - c_t(s*), what is left).
+// status: 0 = the group lasts F frames, 1 = s* = s_lo and n > F, 2 = s* = s_hi and n < F, -1 = the group was not fitted (target 0).
+constexpr int64_t kFitMaxTarget = (int64_t)1 << 22;
+constexpr float kFitMaxTokenFrames = 16777216.f;
+constexpr float kFitMinRate = 0.1f, kFitMaxRate = 10.f;
+constexpr int kFitRowInts = 5;  // a group's row: {F, sum d, the bits of s*, R, status}, int64 each
+struct FitGroups {
+    const int* group = nullptr;       // [batch]: the group of every utterance, in [0, batch); NULL: utterance b is group b
+    const int* target = nullptr;      // [batch], by group: F, or 0 = not fitted
+    float s_lo = 1.f, s_hi = 1.f;
+};
+// the two scale limits; false + a message: rates that are not finite, outside [0.1, 10] or min_rate > max_rate
+bool fit_limits(float min_rate, float max_rate, float& s_lo, float& s_hi, std::string& err);
+// host only (fit_host.cpp): e, fixed (or NULL) and dur [batch][t_stride], lens [batch] (or NULL: t_stride each), rows [batch][kFitRowInts] by group. dur gets
+// d_t of every token of a fitted utterance, fixed_t (or -1) of every other token and -1 behind every length. The values are the caller's to check (fit_check).
+void fit_host(int batch, int t_stride, const float* e, const int* fixed, const int* lens, const FitGroups& g, int* dur, int64_t* rows);
+// false + a message naming the group or the utterance: a group outside [0, batch), a target outside [1, 2^22] and not 0
+bool fit_check(int batch, const int* group, const int64_t* target, std::string& err);  // (the caller's 64-bit targets; FitGroups holds them as ints)
+// ... a batch or a stride below 1, a length outside [0, t_stride], a fixed value below -1 or above 2^24 in front of a length
+bool fit_check_rows(int batch, int t_stride, const int* fixed, const int* lens, std::string& err);
+// group rows as the entry points hand them out: double [groups][kFitRowInts] = {F, sum d, s* (0 where status is -1), R, status}
+void fit_rows_double(int groups, const int64_t* rows, double* out);
+struct FitCall {
+    TensorRef logw;              // [batch][rows][t]: row c is read
+    int c = 0;
+    const int* lens = nullptr;   // device [batch] (or NULL: tmax each); nothing behind a length is read
+    const int* fixed = nullptr;  // device [batch][tmax] (or NULL): the caller's override rows
+    FitGroups g;                 // device pointers
+    float* e = nullptr;          // device [batch][tmax]: e_t of every token (scratch of the search, and the tap)
+    int* dur = nullptr;          // device [batch][tmax]: the override rows launch_durations then takes
+    int64_t* rows = nullptr;     // device [batch][kFitRowInts]
+    int batch = 0, tmax = 0;
+};
+hipError_t launch_fit_durations(const FitCall& c, hipStream_t s);
+
 }  // namespace vits
 
 #include "conv_plan.h"  // the convolutions' launch policy (plan_conv, plan_conv16): host arithmetic over the types above
